@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- RCV1 examples/s of the synchronous SGD hot path on N MI355X (one process per GPU).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3          (the headline alone: exactly K timed steps)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full   (with every leg, check and baseline described below)
     python bench.py --gpus N ...            (no launcher: spawns its own N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -12,17 +13,20 @@ A "step" is one synchronous SGD step of the reference's Master.fit batch closure
 sub-gradient sum + support-only regulariser (core/Slave.scala:142-157), mean over workers
 (an RCCL all-reduce when N > 1), w <- w - lr * mean.  The batch is the worker's whole train
 shard (batch-size >= split size), i.e. every step streams the resident CSR shard once --
-the configuration in which the path is HBM-bound.  Beside the headline the line carries the
-reference's own shapes (N = 804,414 and 23,149 rows: `reference_shapes`), a batch sweep incl. the reference's default
-batch-size 100 (`sweep`), wall-clock time to the oracle's target loss per batch size (`time_to_target`), the lock-free
-mode with its traced parity check (`hogwild`) and the dense variant.
+the configuration in which the path is HBM-bound.  A plain run sets up, ramps the clocks, warms up, times
+the K steps once and prints the line (--dump-outputs DIR also writes the weights the last timed step left).  With --full
+the K steps are timed --repeats times (default 5, the median is quoted) and beside the headline the line carries the
+roofline of the dominant kernel, the CPU baseline, the reference's own shapes (N = 804,414 and 23,149 rows:
+`reference_shapes`), a batch sweep incl. the reference's default batch-size 100 (`sweep`), wall-clock time to the
+oracle's target loss per batch size (`time_to_target`), the lock-free mode with its traced parity check (`hogwild`) and
+the dense variant.
 
 Scaling: "weak" (default) gives every rank its own --rows rows; "strong" splits ONE data set of --rows-total rows over
 the ranks with the reference's SplitStrategy.vanilla (core/ml/SplitStrategy.scala:13-14), as its Master does over its
 slaves (core/Master.scala:136).
 
-Every number is gated by the oracle first (checker only, outside every timed region): the benchmarked whole-shard step
-at N = 1; with N > 1 a step over the first --gate-rows train rows of EVERY rank against the oracle hosting all of them
+With --full every number is gated by the oracle first (checker only, outside every timed region): the benchmarked
+whole-shard step at N = 1; with N > 1 a step over the first --gate-rows train rows of EVERY rank against the oracle hosting all of them
 as world x workers workers (Master.scala:194: the mean runs over the workers).
 
 Inputs are generated on the host, uploaded once and resident in HBM before the timed region.
@@ -58,8 +62,16 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the K timed steps are measured this many times (each between barriers); value = the median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the K timed steps are measured this many times (each between barriers); value = the median "
+                         "(default: 1, so that exactly K steps are timed; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the parity gate, the replica digest, roofline (HIP events "
+                         "inside the clock), the sweep and the other legs, the CPU baseline (each still subject to its "
+                         "--no-* switch); a plain run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (the weights a caller of the step "
+                         "receives) as DIR/weights.npy (float32); the inputs depend on the arguments alone")
     ap.add_argument("--rows", type=int, default=int(os.environ.get("DSGD_BENCH_ROWS", 8388608)),
                     help="weak scaling: rows per GPU.  8388608 (5.1 GB of CSR, BASELINE.md section 3) keeps the stream in HBM; "
                          "804414 = RCV1 full=true (DatasetTests.scala:18) fits mostly in the 256 MiB Infinity Cache")
@@ -69,9 +81,9 @@ def parse(argv=None):
     ap.add_argument("--workers", type=int, default=1, help="virtual workers (node-count share) per GPU")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--gate-rows", type=int, default=200000, help="N > 1: train rows per rank of the parity gate's step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true", help="skip every leg beside the headline (sweep, reference shapes, ...)")
-    ap.add_argument("--no-parity-gate", action="store_true", help="skip every oracle comparison (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-sweep", action="store_true", help="--full: skip every leg beside the headline (sweep, reference shapes, ...)")
+    ap.add_argument("--no-parity-gate", action="store_true", help="--full: skip every oracle comparison (profiling runs)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for each CPU baseline leg")
     ap.add_argument("--clock-ramp", type=float, default=0.5, help="seconds of untimed lr=0 steps before the warmup steps")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
@@ -328,6 +340,13 @@ def timed_steps(eng, ranges, lr, steps, repeats, sync_all, barrier, world, dist)
     return out
 
 
+def dump_outputs(path, eng):
+    """--dump-outputs: what the last timed step computed -- the weight vector (D + 1 floats, 189 KB) a caller of the
+    step reads back -- so that two builds run with the same arguments can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "weights.npy"), np.asarray(eng.get_weights(), dtype=np.float32))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -395,7 +414,7 @@ def main():
 
     # ---- parity gate (before any timing is reported) ------------------------------------------------------------
     parity = None
-    if not args.no_parity_gate:
+    if args.full and not args.no_parity_gate:
         if world == 1:
             parity = parity_gate_single(eng, data, n_train, ranges, LR)
         else:
@@ -420,28 +439,35 @@ def main():
     for _ in range(args.warmup):
         eng.sync_step_ranges(ranges, LR, asynchronous=True)
     sync_all(eng)
-    eng.prof_enable(2)   # HIP events around the DOMINANT kernel only: two event records per step inside the clock
-    eng.prof_read(reset=True)
-    times = timed_steps(eng, ranges, LR, args.steps, max(1, args.repeats), sync_all, barrier, world, dist)
+    repeats = max(1, args.repeats if args.repeats is not None else (5 if args.full else 1))
+    if args.full:
+        eng.prof_enable(2)   # HIP events around the DOMINANT kernel only: two event records per step inside the clock
+        eng.prof_read(reset=True)
+    times = timed_steps(eng, ranges, LR, args.steps, repeats, sync_all, barrier, world, dist)
     dt = float(np.median(times))
-    kernel_ms, n_launch = eng.prof_read(reset=True)
-    # (outside the clock) the two cold-stream kernels, bracketed the same way over a few more steps
-    eng.prof_enable(1)
-    for _ in range(5):
-        eng.sync_step_ranges(ranges, LR, asynchronous=True)
-    sync_all(eng)
-    kinds = eng.prof_read_kinds()
-    eng.prof_read(reset=True)
-    eng.prof_enable(0)
-    last = eng.sync_step_ranges(ranges, 0.0)   # (outside the clock) gate statistics of the state the timed steps ended in
+    if args.full:
+        kernel_ms, n_launch = eng.prof_read(reset=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng)   # the state the LAST timed step left, before anything else runs
 
-    loss, acc, _ = eng.loss_acc(n_train, data.n_rows)
-    value = n_train_job * args.steps / dt if args.scaling == "strong" else world * n_train * args.steps / dt
     identical = None
-    if world > 1:
-        identical = replicas_identical(eng, dist)
-        if not identical:
-            raise SystemExit("rank %d: weight replicas diverged after the timed steps" % rank)
+    if args.full:
+        # (outside the clock) the two cold-stream kernels, bracketed the same way over a few more steps
+        eng.prof_enable(1)
+        for _ in range(5):
+            eng.sync_step_ranges(ranges, LR, asynchronous=True)
+        sync_all(eng)
+        kinds = eng.prof_read_kinds()
+        eng.prof_read(reset=True)
+        eng.prof_enable(0)
+        last = eng.sync_step_ranges(ranges, 0.0)   # (outside the clock) gate statistics of the state the timed steps ended in
+
+        loss, acc, _ = eng.loss_acc(n_train, data.n_rows)
+        if world > 1:
+            identical = replicas_identical(eng, dist)
+            if not identical:
+                raise SystemExit("rank %d: weight replicas diverged after the timed steps" % rank)
+    value = n_train_job * args.steps / dt if args.scaling == "strong" else world * n_train * args.steps / dt
 
     if args.scaling == "weak":
         workload = ("rcv1-synth sync SGD: %d rows/GPU (D=47236, nnz/row=%.1f), 80/20 split, whole-shard batch B=%d rows/GPU/step, "
@@ -475,12 +501,12 @@ def main():
         },
         "repeats": {"n": len(times), "statistic": "median", "ms_per_step": [1e3 * t / args.steps for t in times],
                     "ms_per_step_min": 1e3 * min(times) / args.steps, "ms_per_step_max": 1e3 * max(times) / args.steps},
-        "active_fraction_after": last["n_active"] / max(1, last["n_samples"]),
-        "test_loss_after": loss,
-        "test_acc_after": acc,
         "setup_s": {"generate": round(t_gen, 2), "upload": round(t_up, 2), "clock_ramp": round(ramp_s, 2),
                     "communicator_layout_dim_sparsity": round(t_setup_coll, 2)},
     }
+    if args.full:
+        out.update({"active_fraction_after": last["n_active"] / max(1, last["n_samples"]), "test_loss_after": loss,
+                    "test_acc_after": acc})
     if identical is not None:
         out["replicas_bit_identical"] = identical
     if parity is not None:
@@ -494,11 +520,12 @@ def main():
     # ---- roofline of the dominant kernel (the gradient kernel) ---------------------------------------
     # Algorithmic bytes: 8 B per non-zero + 12 B per row.  In the split layout the cold entries are
     # read by the two cold-stream kernels, so the main kernel is credited with the hot entries and the per-row bytes only.
-    out["roofline"] = roofline(eng, args.rows if args.scaling == "weak" else None, n_train, nnz_train, bytes_per_row, kernel_ms,
-                               n_launch, args.steps * len(times), dt / args.steps, kinds)
+    if args.full:
+        out["roofline"] = roofline(eng, args.rows if args.scaling == "weak" else None, n_train, nnz_train, bytes_per_row,
+                                   kernel_ms, n_launch, args.steps * len(times), dt / args.steps, kinds)
 
     # ---- the other shapes and configurations, reported beside the headline (N = 1 only) ----------------------------
-    extras = rank == 0 and world == 1 and not args.no_sweep
+    extras = args.full and rank == 0 and world == 1 and not args.no_sweep
     gated = not args.no_parity_gate
     if extras:
         out["sweep"] = sweep(eng, data, n_train, with_parity=gated)
@@ -508,7 +535,7 @@ def main():
     if extras:
         if gated:
             out["hogwild"].update(hogwild_parity(dsgd_amd, device))
-        out["reference_shapes"] = [reference_shape(dsgd_amd, device, n, with_parity=gated, repeats=max(1, args.repeats))
+        out["reference_shapes"] = [reference_shape(dsgd_amd, device, n, with_parity=gated, repeats=repeats)
                                    for n in (804414, 23149, 100552)]   # DatasetTests.scala:18 (full = true), application.conf:24 (full
         # = false), and what ONE GPU of eight holds of the former (SplitStrategy.scala:13-14: ceil(804414 / 8) rows; 80,441 of
         # them train) -- the per-GPU step of an 8-GPU strong-scaled run, to which a 189 KB all-reduce is added there
@@ -517,7 +544,7 @@ def main():
         out["dense_logistic"] = dense_logistic(dsgd_amd, device)
 
     # ---- CPU baseline on this box's host cores (rank 0, N=1 only) --------------------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"], out["cpu_literal"] = cpu_baseline(data, n_train, args.cpu_seconds)
         # second half of BASELINE.json's metric ("epochs to target hinge loss"); the target is defined by the oracle, so
         # it is computed in this leg and shown at the top level as well

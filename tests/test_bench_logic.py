@@ -285,3 +285,52 @@ def test_final_line_is_compact_and_parses(tmp_path):
     line2 = bench.emit(fat, None, stream=buf2)
     c2 = json.loads(line2)
     assert len(line2) < bench.LINE_LIMIT and "sweep" in c2["legs_dropped_from_line"] and c2["value"] == c["value"] and "roofline" in c2
+
+
+def test_plain_run_times_exactly_k_steps_and_dumps_what_they_computed(fake, monkeypatch, tmp_path, capsys):
+    """A plain `bench.py --steps K --warmup W` runs the W warmup steps and exactly K timed steps with a learning rate
+    (the clock ramp's steps have lr = 0), and its line carries the contract keys but nothing another run has to measure.
+    --dump-outputs DIR writes the weights those steps left -- equal to the oracle's after W + K whole-shard steps from
+    zero, and the same for the same arguments.  --full brings the parity gate, the repeats and the roofline back."""
+    lrs = []
+
+    class Counting(FakeEngine):
+        def sync_step_ranges(self, ranges, lr, asynchronous=False):
+            lrs.append(lr)
+            return FakeEngine.sync_step_ranges(self, ranges, lr, asynchronous)
+
+        def prof_read_kinds(self):
+            return {"cdot": (0.0, 0), "cgrad": (0.0, 0)}
+
+    monkeypatch.setattr(dsgd_amd, "Engine", Counting)
+    monkeypatch.setattr(dsgd_amd, "device_count", lambda: 1)
+    for var in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(var, raising=False)
+    base = ["bench.py", "--rows", "3000", "--steps", "4", "--warmup", "2", "--clock-ramp", "0.01",
+            "--detail", str(tmp_path / "detail.json")]
+
+    def run(*extra):
+        lrs.clear()
+        monkeypatch.setattr(sys, "argv", base + list(extra))
+        bench.main()
+        return json.loads(capsys.readouterr().out.splitlines()[-1]), [lr for lr in lrs if lr != 0.0]
+
+    line, stepped = run("--dump-outputs", str(tmp_path / "a"))
+    assert len(stepped) == 2 + 4 and line["steps"] == 4 and line["warmup"] == 2 and line["repeats"]["n"] == 1
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert abs(line["value"] - 2400 / (line["ms_per_step"] * 1e-3)) <= 1e-5 * line["value"]
+    assert not {"roofline", "cpu_baseline", "parity_gate_rows", "test_loss_after", "legs"} & set(line)
+    data = dsgd_amd.synth.generate(3000, seed=0)
+    o = orc.Oracle(data.dim, data.row_ptr, data.col, data.val, data.label, bench.LAMBDA)
+    o.set_dim_sparsity(o.dim_sparsity(2400))
+    w = np.zeros(data.dim + 1)
+    for _ in range(2 + 4):
+        o.sync_step(w, [np.arange(2400, dtype=np.int32)], stepped[0])
+    got = np.load(tmp_path / "a" / "weights.npy")
+    assert got.dtype == np.float32 and got.shape == (data.dim + 1,) and np.abs(w).max() > 0
+    np.testing.assert_array_equal(got, w.astype(np.float32))
+    run("--dump-outputs", str(tmp_path / "b"))
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "weights.npy"), got)
+    line, stepped = run("--full", "--no-sweep", "--no-cpu-baseline")
+    assert len(stepped) == 2 + 2 + 5 * 4 + 5       # gate, warmup, 5 repeats of the K steps, the cold kernels' 5 steps
+    assert line["repeats"]["n"] == 5 and line["roofline"]["bound"] == "hbm" and line["parity_gate_rows"] == 2400

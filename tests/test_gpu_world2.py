@@ -251,7 +251,7 @@ def test_bench_parity_gate_with_two_ranks(mode, tmp_path):
     shape = ["--scaling", "strong", "--rows-total", "60000"] if mode == "strong" else ["--rows", "30000"]
     gate_rows = 8000 if mode == "strong" else 12000   # (below / above the row count from which ranges take the streaming kernels)
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--workers", "2", "--gate-rows", str(gate_rows),
-           "--steps", "3", "--warmup", "1", "--repeats", "2", "--clock-ramp", "0.05", "--no-cpu-baseline",
+           "--steps", "3", "--warmup", "1", "--repeats", "2", "--clock-ramp", "0.05", "--full", "--no-cpu-baseline",
            "--detail", str(tmp_path / "detail.json")] + shape
     proc = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-4000:]

