@@ -32,7 +32,11 @@ SYMBOLS = [
     "dsgd_dense_create", "dsgd_dense_destroy", "dsgd_dense_generate", "dsgd_dense_load", "dsgd_dense_set_weights",
     "dsgd_dense_get_weights", "dsgd_dense_step", "dsgd_dense_synchronize", "dsgd_dense_loss", "dsgd_dense_comm_init",
     "dsgd_dense_prof",
+    "dsgd_set_weights_f64", "dsgd_get_weights_f64", "dsgd_set_dim_sparsity_f64", "dsgd_get_dim_sparsity_f64",
+    "dsgd_plan_run_f64", "dsgd_precision",
 ]
+
+F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
 
 
 class Config(C.Structure):
@@ -109,6 +113,13 @@ def f32(a, n=None):
     a = np.ascontiguousarray(a, dtype=np.float32)
     if n is not None and a.shape != (n,):
         raise ValueError("expected %d floats, got shape %r" % (n, a.shape))
+    return a
+
+
+def f64(a, n=None):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if n is not None and a.shape != (n,):
+        raise ValueError("expected %d doubles, got shape %r" % (n, a.shape))
     return a
 
 

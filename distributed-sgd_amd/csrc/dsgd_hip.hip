@@ -126,6 +126,7 @@ static bool available() {
 #include "dsgd_fstep.hpp"
 #include "dsgd_tcol.hpp"
 #include "dsgd_shuffle.hpp"
+#include "dsgd_cs64.hpp"   // (last: the fp64 mode)
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -488,6 +489,17 @@ struct dsgd_ctx {
   double prof_kms[3] = {0.0, 0.0, 0.0};
   long long prof_kn[3] = {0, 0, 0};
   int n_cu = 256;
+  // the fp64 mode (DSGD_F_FP64, csrc/dsgd_cs64.hpp): the weights and dimSparsity in fp64, rank order like d_w / d_ds; while
+  // cs_w_G != 0 the weights are slice-major in d_cs_w64 (bind converts back, as for fp32)
+  bool fp64 = false;
+  double* d_w64 = nullptr;
+  double* d_ds64 = nullptr;
+  double* d_io64 = nullptr;               // dp staging (key order) / scratch
+  double* d_cs_w64 = nullptr;
+  double* d_cs_ds64 = nullptr;
+  double* d_nsq64 = nullptr;              // |w|^2 of the loss
+  unsigned long long* d_cs64_x = nullptr; // exchange buffer of dsgd_cs64_step_kernel: [2][CS64_G][2 * CS_XSTRIDE] granules
+  unsigned int cs64_tag0 = 0;
 };
 
 static int check_ctx(dsgd_ctx* c) {
@@ -500,6 +512,13 @@ static int cs_sp(int dp, int G) { return (((dp + G - 1) / G) + 4) & ~3; }   // p
 // mutex: the one place.
 static int cs_unslice(dsgd_ctx* c) {
   if (!c->cs_w_G) return DSGD_OK;
+  if (c->fp64) {
+    hipLaunchKernelGGL(dsgd_cs64_unslice_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, c->d_cs_w64, c->d_w64, c->dp,
+                       cs64_sp(c->dp));
+    HIP_TRY(hipGetLastError());
+    c->cs_w_G = 0;
+    return DSGD_OK;
+  }
   hipLaunchKernelGGL(dsgd_cs_unslice_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, c->d_cs_w, c->d_w, c->dp, c->cs_w_G,
                      cs_sp(c->dp, c->cs_w_G));
   HIP_TRY(hipGetLastError());
@@ -1198,7 +1217,9 @@ static int cs_build_device_impl(dsgd_ctx* c, dsgd_plan* p) {
   const int K = p->n_workers;
   const long long n_steps = p->n_steps, n_lists = n_steps * K;
   if (K > CS_MAX_K || p->max_step_rows > CS_MAX_SLOTS) return DSGD_OK;
-  const int G = cs_pick_G(c, K, false);
+  // (fp64: always CS64_G slices, the fp64 kernel's own LDS budget)
+  const int G = c->fp64 ? ((K <= CS64_MAX_K && cs64_lds_bytes(c->dp, K) <= CS64_LDS_MAX && c->dp >= 4 * CS64_G) ? CS64_G : 0)
+                        : cs_pick_G(c, K, false);
   if (!G) return DSGD_OK;
   if (n_steps * (long long)G > 0x7fffffffLL) return DSGD_OK;
   if (!p->idx_trusted) {
@@ -1278,7 +1299,7 @@ static int cs_build_device_impl(dsgd_ctx* c, dsgd_plan* p) {
   hipLaunchKernelGGL(dsgd_cs_layout_kernel<true>, dim3((unsigned)(n_steps * G)), dim3(CS_THREADS), 0, bs, ba);
   HIP_TRY(hipGetLastError());
   p->cs_G = G;
-  p->cs_nt = (c->cs_nt == CS_THREADS_NARROW && narrow_fits) ? CS_THREADS_NARROW : CS_THREADS;
+  p->cs_nt = (c->cs_nt == CS_THREADS_NARROW && narrow_fits && !c->fp64) ? CS_THREADS_NARROW : CS_THREADS;
   p->cs_spl = (p->cs_nt == CS_THREADS && one_fits) ? 1 : 2;
   p->cs_slot_stride = slot_stride;
   p->cs_row_stride = row_stride;
@@ -1465,7 +1486,7 @@ static int cs_build_impl(dsgd_ctx* c, dsgd_plan* p) {
 static int cs_build(dsgd_ctx* c, dsgd_plan* p) {
   int rc;
   try {
-    rc = c->cs_host_layout ? cs_build_impl(c, p) : cs_build_device_impl(c, p);
+    rc = (c->cs_host_layout && !c->fp64) ? cs_build_impl(c, p) : cs_build_device_impl(c, p);
   } catch (const std::bad_alloc&) {   // (nothing may unwind across the C ABI)
     rc = 1;
   }
@@ -1564,6 +1585,70 @@ static int launch_cs(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long 
   HIP_TRY(hipGetLastError());
   DSGD_TRY(prof_end(c, slot));
   cs_after_launch(c, p->cs_shift[(size_t)(step_end - 1)]);
+  return DSGD_OK;
+}
+
+// the steps [step_begin, step_end) of a plan in an fp64 context (csrc/dsgd_cs64.hpp): ONE launch
+static int launch_cs64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr) {
+  const int Sp = cs64_sp(c->dp), n = CS64_G * Sp;
+  if (!c->d_cs64_x) {
+    HIP_TRY(hipMalloc(&c->d_cs64_x, sizeof(unsigned long long) * 2 * CS64_G * CS64_XSTRIDE2));
+    HIP_TRY(hipMemsetAsync(c->d_cs64_x, 0, sizeof(unsigned long long) * 2 * CS64_G * CS64_XSTRIDE2, c->stream));
+  }
+  if (!c->d_cs_sync) {
+    HIP_TRY(hipMalloc(&c->d_cs_sync, sizeof(unsigned int) * 2));
+    HIP_TRY(hipMemsetAsync(c->d_cs_sync, 0, sizeof(unsigned int) * 2, c->stream));
+  }
+  if (c->cs_w_G != CS64_G) {   // the weights (and a copy of dimSparsity) slice-major; they stay so until something else binds
+    if (!c->d_cs_w64) HIP_TRY(hipMalloc(&c->d_cs_w64, sizeof(double) * (size_t)n));
+    if (!c->d_cs_ds64) HIP_TRY(hipMalloc(&c->d_cs_ds64, sizeof(double) * (size_t)n));
+    hipLaunchKernelGGL(dsgd_cs64_slice_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_w64, c->d_cs_w64, c->dp, Sp);
+    hipLaunchKernelGGL(dsgd_cs64_slice_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_ds64, c->d_cs_ds64, c->dp, Sp);
+    HIP_TRY(hipGetLastError());
+    c->cs_w_G = CS64_G;
+  }
+  const unsigned long long n_launch = (unsigned long long)(step_end - step_begin);
+  if ((unsigned long long)c->cs64_tag0 + n_launch + 1ull >= (1ull << 32)) {   // (the tags would wrap: start the count again)
+    HIP_TRY(hipMemsetAsync(c->d_cs64_x, 0, sizeof(unsigned long long) * 2 * CS64_G * CS64_XSTRIDE2, c->stream));
+    c->cs64_tag0 = 0;
+  }
+  Cs64Args a;
+  a.hdr = p->d_cs_hdr;
+  a.slot_meta = p->d_cs_meta;
+  a.row_first = p->d_cs_rf;
+  a.col = p->d_cs_col;
+  a.val = p->d_cs_val;
+  a.clist = p->d_cs_cl;
+  a.w = c->d_cs_w64;
+  a.ds = c->d_cs_ds64;
+  a.xbuf = c->d_cs64_x;
+  a.sync = c->d_cs_sync;
+  a.sc = c->d_sc;
+  a.n_steps_plan = p->n_steps;
+  a.step_begin = step_begin;
+  a.step_end = step_end;
+  a.slot_stride = p->cs_slot_stride;
+  a.row_stride = p->cs_row_stride;
+  a.cl_stride = p->cs_cl_stride;
+  a.tag0 = c->cs64_tag0;
+  c->cs64_tag0 += (unsigned int)n_launch;
+  a.lr = lr;
+  a.lambda = c->cfg.lambda;
+  a.vexp = c->vexp;
+  a.dp = c->dp;
+  a.K = p->n_workers;
+  a.gate_rec = p->d_gate_rec;
+  a.s_rec = p->d_s_rec;
+  a.gate_words = p->gate_words;
+  const size_t lds = (size_t)cs64_lds_bytes(c->dp, a.K);
+  c->ctr_known = false;
+  if (p->cs_spl == 1)
+    hipLaunchKernelGGL((dsgd_cs64_step_kernel<CS_THREADS, 1, 4>), dim3(CS64_G), dim3(CS_THREADS), lds, c->stream, a);
+  else
+    hipLaunchKernelGGL((dsgd_cs64_step_kernel<CS_THREADS, 2, 8>), dim3(CS64_G), dim3(CS_THREADS), lds, c->stream, a);
+  HIP_TRY(hipGetLastError());
+  c->last_grad_kernel = "dsgd_cs64_step_kernel";
+  c->last_shift = p->cs_shift[(size_t)(step_end - 1)] + 32;
   return DSGD_OK;
 }
 
@@ -1731,10 +1816,33 @@ static int launch_permute_out(dsgd_ctx* c, const float* d_in, float* d_out) {
   HIP_TRY(hipGetLastError());
   return DSGD_OK;
 }
+static int launch_promote64_in(dsgd_ctx* c, const float* d_in, double* d_out) {
+  hipLaunchKernelGGL(dsgd_promote64_in_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, d_in, d_out, c->d_perm, c->dp);
+  HIP_TRY(hipGetLastError());
+  return DSGD_OK;
+}
+static int launch_round64_out(dsgd_ctx* c, const double* d_in, float* d_out) {
+  hipLaunchKernelGGL(dsgd_round64_out_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, d_in, d_out, c->d_perm, c->dp);
+  HIP_TRY(hipGetLastError());
+  return DSGD_OK;
+}
 static int set_identity_perm(dsgd_ctx* c) {
   std::vector<int> id(c->dp);
   for (int j = 0; j < c->dp; ++j) id[j] = j;
   HIP_TRY(hipMemcpy(c->d_perm, id.data(), sizeof(int) * c->dp, hipMemcpyHostToDevice));
+  return DSGD_OK;
+}
+// the fp64 weights and dimSparsity into ranked order (in = true) or back to key order, d_io64 as scratch
+static int permute64_resident(dsgd_ctx* c, bool in) {
+  double* v[2] = {c->d_w64, c->d_ds64};
+  for (double* x : v) {
+    if (in)
+      hipLaunchKernelGGL(dsgd_permute64_in_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, x, c->d_io64, c->d_perm, c->dp);
+    else
+      hipLaunchKernelGGL(dsgd_permute64_out_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, x, c->d_io64, c->d_perm, c->dp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(x, c->d_io64, sizeof(double) * c->dp, hipMemcpyDeviceToDevice, c->stream));
+  }
   return DSGD_OK;
 }
 static int count_columns(dsgd_ctx* c, long long nnz, unsigned int* d_cnt) {
@@ -2014,6 +2122,7 @@ static int layout_finish(dsgd_ctx* c, unsigned int* d_cnt) {   // (takes ownersh
   HIP_TRY(hipMemcpyAsync(c->d_w, c->d_tmp, sizeof(float) * c->dp, hipMemcpyDeviceToDevice, c->stream));
   DSGD_TRY(launch_permute_in(c, c->d_ds, c->d_tmp));
   HIP_TRY(hipMemcpyAsync(c->d_ds, c->d_tmp, sizeof(float) * c->dp, hipMemcpyDeviceToDevice, c->stream));
+  if (c->fp64) DSGD_TRY(permute64_resident(c, true));
   if (c->nnz > 0) {
     const int blocks = (int)std::min<long long>((c->nnz + 255) / 256, (long long)c->n_cu * 8);
     hipLaunchKernelGGL(dsgd_remap_cols_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_col, c->nnz, c->d_perm);
@@ -2043,6 +2152,7 @@ static int reset_layout(dsgd_ctx* c) {
     HIP_TRY(hipMemcpyAsync(c->d_w, c->d_tmp, sizeof(float) * c->dp, hipMemcpyDeviceToDevice, c->stream));
     DSGD_TRY(launch_permute_out(c, c->d_ds, c->d_tmp));
     HIP_TRY(hipMemcpyAsync(c->d_ds, c->d_tmp, sizeof(float) * c->dp, hipMemcpyDeviceToDevice, c->stream));
+    if (c->fp64) DSGD_TRY(permute64_resident(c, false));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   DSGD_TRY(set_identity_perm(c));
@@ -2816,6 +2926,23 @@ static int require_ds(dsgd_ctx* c) {
   return DSGD_OK;
 }
 
+// the fp64 mode (DSGD_F_FP64) runs plans of column-slice steps, dsgd_sync_step, dsgd_forward and dsgd_loss_acc; every other
+// entry point that would run an fp32 training kernel refuses an fp64 context and leaves its state as it is
+static int refuse_fp64(dsgd_ctx* c, const char* what) {
+  if (c && c->fp64)
+    return fail(DSGD_EUNSUPPORTED, "%s is not available in an fp64 context (DSGD_F_FP64: plans of <= %d workers and <= %d rows per "
+                                   "step, dsgd_sync_step, dsgd_forward, dsgd_loss_acc)", what, CS64_MAX_K, CS_MAX_SLOTS);
+  return DSGD_OK;
+}
+static int refuse_fp64_all(dsgd_ctx* const* ctxs, int n, const char* what) {
+  for (int i = 0; i < n; ++i) DSGD_TRY(refuse_fp64(ctxs[i], what));
+  return DSGD_OK;
+}
+static int require_fp64(dsgd_ctx* c, const char* what) {
+  if (!c->fp64) return fail(DSGD_ESTATE, "%s needs an fp64 context (dsgd_config.flags = DSGD_F_FP64)", what);
+  return DSGD_OK;
+}
+
 extern "C" {
 
 int dsgd_abi_version(void) { return DSGD_ABI_VERSION; }
@@ -2836,7 +2963,7 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   if (!cfg || !out) return fail(DSGD_EINVAL, "null argument");
   if (cfg->n_features < 1) return fail(DSGD_EINVAL, "n_features must be >= 1");
   if (!(cfg->lambda == cfg->lambda)) return fail(DSGD_EINVAL, "lambda is NaN");
-  if (cfg->flags != DSGD_F_DEFAULT) return fail(DSGD_EINVAL, "unknown flags 0x%x (none are defined)", cfg->flags);
+  if (cfg->flags & ~DSGD_F_FP64) return fail(DSGD_EINVAL, "unknown flags 0x%x (only DSGD_F_FP64 is defined)", cfg->flags);
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
     return fail(DSGD_EUNSUPPORTED, "no HIP device visible: libdsgd_hip has no CPU fallback");
@@ -2850,6 +2977,7 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   c->cfg = *cfg;
   c->dp = cfg->n_features + 1;
   c->n_cu = prop.multiProcessorCount;
+  c->fp64 = (cfg->flags & DSGD_F_FP64) != 0;
   auto bail = [&](int rc) {
     dsgd_destroy(c);
     return rc;
@@ -2944,6 +3072,16 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   DSGD_ATTR(dsgd_wseg_bound_kernel);
   DSGD_ATTR(dsgd_fstep_kernel);
   DSGD_ATTR(dsgd_fstep_bound_kernel);
+  if (c->fp64) {   // the fp64 state (csrc/dsgd_cs64.hpp)
+    HIP_TRY_B(hipMalloc(&c->d_w64, sizeof(double) * c->dp));
+    HIP_TRY_B(hipMalloc(&c->d_ds64, sizeof(double) * c->dp));
+    HIP_TRY_B(hipMalloc(&c->d_io64, sizeof(double) * c->dp));
+    HIP_TRY_B(hipMalloc(&c->d_nsq64, sizeof(double)));
+    HIP_TRY_B(hipMemsetAsync(c->d_w64, 0, sizeof(double) * c->dp, c->stream));
+    HIP_TRY_B(hipMemsetAsync(c->d_ds64, 0, sizeof(double) * c->dp, c->stream));
+    DSGD_ATTR((dsgd_cs64_step_kernel<CS_THREADS, 1, 4>));
+    DSGD_ATTR((dsgd_cs64_step_kernel<CS_THREADS, 2, 8>));
+  }
   {   // the column lists' gradient kernel: its table, the bitmap, 16 words
     const int tc_lds = (int)(sizeof(long long) * TC_MAX_SHARE + TC_MAX_BITS / 8 + 64);
 #define DSGD_ATTR_TC(fn) HIP_TRY_B(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, tc_lds))
@@ -2995,6 +3133,13 @@ int dsgd_destroy(dsgd_ctx* c) {
   (void)hipFree(c->d_label);
   (void)hipFree(c->d_w);
   (void)hipFree(c->d_ds);
+  (void)hipFree(c->d_w64);
+  (void)hipFree(c->d_ds64);
+  (void)hipFree(c->d_io64);
+  (void)hipFree(c->d_nsq64);
+  (void)hipFree(c->d_cs_w64);
+  (void)hipFree(c->d_cs_ds64);
+  (void)hipFree(c->d_cs64_x);
   (void)hipFree(c->d_g);
   (void)hipFree(c->d_g64);
   (void)hipFree(c->d_gsum);
@@ -3203,6 +3348,7 @@ int dsgd_set_dim_sparsity(dsgd_ctx* c, const float* ds) {
   DSGD_TRY(require_sync_mode(c));
   HIP_TRY(hipMemcpyAsync(c->d_io, ds, sizeof(float) * c->dp, hipMemcpyHostToDevice, c->stream));
   DSGD_TRY(launch_permute_in(c, c->d_io, c->d_ds));
+  if (c->fp64) DSGD_TRY(launch_promote64_in(c, c->d_io, c->d_ds64));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->have_ds = true;
   c->s_dirty = true;
@@ -3245,6 +3391,8 @@ static int ds_finish(dsgd_ctx* c, unsigned int* d_cnt, float* ds_out) {   // (ta
   }
   if (!rc) {
     hipLaunchKernelGGL(dsgd_ds_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, d_cnt, c->d_perm, c->d_ds, c->dp);
+    if (c->fp64)
+      hipLaunchKernelGGL(dsgd_ds64_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, d_cnt, c->d_perm, c->d_ds64, c->dp);
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) rc = fail(DSGD_EHIP, "dimSparsity kernels: %s", hipGetErrorString(le));
   }
@@ -3256,7 +3404,10 @@ static int ds_finish(dsgd_ctx* c, unsigned int* d_cnt, float* ds_out) {   // (ta
   c->have_ds = true;
   c->s_dirty = true;
   if (ds_out) {
-    DSGD_TRY(launch_permute_out(c, c->d_ds, c->d_io));
+    if (c->fp64)   // (the fp64 values rounded)
+      DSGD_TRY(launch_round64_out(c, c->d_ds64, c->d_io));
+    else
+      DSGD_TRY(launch_permute_out(c, c->d_ds, c->d_io));
     HIP_TRY(hipMemcpyAsync(ds_out, c->d_io, sizeof(float) * c->dp, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
@@ -3291,7 +3442,10 @@ static int set_weights_locked(dsgd_ctx* c, const float* w) {
   memcpy(c->pin_w.p, w, bytes);   // the caller may reuse w as soon as this returns
   HIP_TRY(hipMemcpyAsync(c->d_io, c->pin_w.p, bytes, hipMemcpyHostToDevice, c->stream));
   DSGD_TRY(pin_sent(c, c->pin_w));
-  DSGD_TRY(launch_permute_in(c, c->d_io, c->d_w));
+  if (c->fp64)   // (promoted)
+    DSGD_TRY(launch_promote64_in(c, c->d_io, c->d_w64));
+  else
+    DSGD_TRY(launch_permute_in(c, c->d_io, c->d_w));
   c->s_dirty = true;
   return DSGD_OK;
 }
@@ -3312,10 +3466,76 @@ int dsgd_get_weights(dsgd_ctx* c, float* w_out) {
   DSGD_TRY(bind(c));
   const size_t bytes = sizeof(float) * (size_t)c->dp;
   DSGD_TRY(pin_acquire(c->pin_out, bytes));
-  DSGD_TRY(launch_permute_out(c, c->d_w, c->d_io));
+  if (c->fp64)   // (the fp64 weights rounded)
+    DSGD_TRY(launch_round64_out(c, c->d_w64, c->d_io));
+  else
+    DSGD_TRY(launch_permute_out(c, c->d_w, c->d_io));
   HIP_TRY(hipMemcpyAsync(c->pin_out.p, c->d_io, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   memcpy(w_out, c->pin_out.p, bytes);
+  return DSGD_OK;
+}
+
+// ---- the fp64 mode's own entry points (DSGD_F_FP64) ----
+static int put64(dsgd_ctx* c, const double* h, double* d_rank) {   // key order (host) -> rank order (device), filtered
+  HIP_TRY(hipMemcpyAsync(c->d_io64, h, sizeof(double) * c->dp, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(dsgd_permute64_in_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, c->d_io64, d_rank, c->d_perm, c->dp);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return DSGD_OK;
+}
+static int take64(dsgd_ctx* c, const double* d_rank, double* h) {   // rank order (device) -> key order (host)
+  hipLaunchKernelGGL(dsgd_permute64_out_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, d_rank, c->d_io64, c->d_perm, c->dp);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h, c->d_io64, sizeof(double) * c->dp, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return DSGD_OK;
+}
+
+int dsgd_set_weights_f64(dsgd_ctx* c, const double* w) {
+  DSGD_TRY(check_ctx(c));
+  if (!w) return fail(DSGD_EINVAL, "null w");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_set_weights_f64"));
+  DSGD_TRY(bind(c));
+  DSGD_TRY(require_sync_mode(c));
+  return put64(c, w, c->d_w64);
+}
+
+int dsgd_get_weights_f64(dsgd_ctx* c, double* w_out) {
+  DSGD_TRY(check_ctx(c));
+  if (!w_out) return fail(DSGD_EINVAL, "null w_out");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_get_weights_f64"));
+  DSGD_TRY(bind(c));
+  return take64(c, c->d_w64, w_out);
+}
+
+int dsgd_set_dim_sparsity_f64(dsgd_ctx* c, const double* ds) {
+  DSGD_TRY(check_ctx(c));
+  if (!ds) return fail(DSGD_EINVAL, "null ds");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_set_dim_sparsity_f64"));
+  DSGD_TRY(bind(c));
+  DSGD_TRY(require_sync_mode(c));
+  DSGD_TRY(put64(c, ds, c->d_ds64));
+  c->have_ds = true;
+  return DSGD_OK;
+}
+
+int dsgd_get_dim_sparsity_f64(dsgd_ctx* c, double* ds_out) {
+  DSGD_TRY(check_ctx(c));
+  if (!ds_out) return fail(DSGD_EINVAL, "null ds_out");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_get_dim_sparsity_f64"));
+  DSGD_TRY(bind(c));
+  return take64(c, c->d_ds64, ds_out);
+}
+
+int dsgd_precision(dsgd_ctx* c, int32_t* bits_out) {
+  DSGD_TRY(check_ctx(c));
+  if (!bits_out) return fail(DSGD_EINVAL, "null bits_out");
+  *bits_out = c->fp64 ? 64 : 32;
   return DSGD_OK;
 }
 
@@ -3369,6 +3589,7 @@ static int stage_lists(dsgd_ctx* c, const int32_t* const* idx_per_worker, const 
 
 int dsgd_gradient(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, float* g_out, dsgd_batch_stats* stats) {
   DSGD_TRY(check_ctx(c));
+  DSGD_TRY(refuse_fp64(c, "dsgd_gradient"));
   if (!g_out) return fail(DSGD_EINVAL, "null g_out");
   if (n <= 0 || !idx) return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors");  // ref: math/Vec.scala:129
   std::lock_guard<std::mutex> lk(c->mu);
@@ -3405,6 +3626,7 @@ int dsgd_gradient(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, fl
 
 int dsgd_apply(dsgd_ctx* c, const float* g_mean, float lr) {
   DSGD_TRY(check_ctx(c));
+  DSGD_TRY(refuse_fp64(c, "dsgd_apply"));
   if (!g_mean) return fail(DSGD_EINVAL, "null g_mean");
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(bind(c));
@@ -3465,6 +3687,8 @@ static int finish_mail(dsgd_ctx* c, dsgd_batch_stats* stats, long long total, un
   return DSGD_OK;
 }
 
+static int sync_step64(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int n_workers, double lr,
+                      dsgd_batch_stats* stats);
 int dsgd_sync_step(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers,
                    float lr, dsgd_batch_stats* stats) {
   DSGD_TRY(check_ctx(c));
@@ -3475,6 +3699,7 @@ int dsgd_sync_step(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int6
   DSGD_TRY(require_ds(c));
   DSGD_TRY(require_sync_mode(c));
   DSGD_TRY(prepare_layout(c));
+  if (c->fp64) return sync_step64(c, idx_per_worker, n_per_worker, n_workers, (double)lr, stats);
   long long mx = 0, tot = 0;
   {
     long long t = 0;
@@ -3589,6 +3814,7 @@ static int ranges_enqueue(dsgd_ctx* c, const int64_t* row_begin, const int64_t* 
 int dsgd_sync_step_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, float lr,
                           dsgd_batch_stats* stats) {
   DSGD_TRY(check_ctx(c));
+  DSGD_TRY(refuse_fp64(c, "dsgd_sync_step_ranges"));
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(bind(c));
   DSGD_TRY(reset_counters(c));
@@ -3600,6 +3826,7 @@ int dsgd_sync_step_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_t* 
 int dsgd_sync_step_ranges_async(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers,
                                 float lr) {
   DSGD_TRY(check_ctx(c));
+  DSGD_TRY(refuse_fp64(c, "dsgd_sync_step_ranges_async"));
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(bind(c));
   long long tot = 0;
@@ -3673,6 +3900,18 @@ static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int3
       return fail(DSGD_EINVAL, "list %lld is empty: Vec.sum requires a non-empty list", (long long)i);
     mx = std::max<long long>(mx, offsets[i + 1] - offsets[i]);
   }
+  if (c->fp64) {   // what dsgd_cs64_step_kernel can hold, refused here rather than at the first run
+    long long rows = 0;
+    for (int64_t st = 0; st < n_steps; ++st) rows = std::max<long long>(rows, offsets[(st + 1) * n_workers] - offsets[st * n_workers]);
+    if (n_workers > CS64_MAX_K)
+      return fail(DSGD_EUNSUPPORTED, "fp64 plans host at most %d workers per step (this plan has %d)", CS64_MAX_K, n_workers);
+    if (rows > CS_MAX_SLOTS)
+      return fail(DSGD_EUNSUPPORTED, "fp64 plans take at most %d rows per step (this plan has a step of %lld)", CS_MAX_SLOTS, rows);
+    if (cs64_lds_bytes(c->dp, n_workers) > CS64_LDS_MAX || c->dp < 4 * CS64_G)
+      return fail(DSGD_EUNSUPPORTED, "fp64 plans: a model of %d features needs %lld bytes of LDS per slice at %d workers (at most %lld; "
+                                     "at least %d features)", c->cfg.n_features, cs64_lds_bytes(c->dp, n_workers), n_workers, CS64_LDS_MAX,
+                  4 * CS64_G - 1);
+  }
   dsgd_plan* p = new (std::nothrow) dsgd_plan();
   if (!p) return fail(DSGD_ENOMEM, "out of host memory");
   p->n_steps = n_steps;
@@ -3710,14 +3949,41 @@ static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int3
   *out = p;
   return DSGD_OK;
 }
+static int cs64_refused(dsgd_ctx* c) {
+  return fail(DSGD_EUNSUPPORTED, "fp64 plan: a row index outside the loaded data, or a step whose layout exceeds dsgd_cs64_step_kernel "
+                                 "(%d slots or %d columns of one slice per step)", CS_MAX_SLOTS, CS_MAX_CLT * CS_THREADS);
+}
+// the steps of a plan in an fp64 context (locked; bound with the slice-major weights kept)
+static int plan_run64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr) {
+  DSGD_TRY(require_data(c));
+  DSGD_TRY(require_ds(c));
+  DSGD_TRY(require_sync_mode(c));
+  DSGD_TRY(prepare_layout(c));
+  if (p->cs_layout != c->layout_gen) {
+    DSGD_TRY(cs_build(c, p));
+    if (p->cs_device_built && c->build_stream) {
+      HIP_TRY(hipEventRecord(p->built_ev, c->build_stream));
+      p->built_pending = true;
+    }
+  }
+  if (p->built_pending) {
+    HIP_TRY(hipStreamWaitEvent(c->stream, p->built_ev, 0));
+    p->built_pending = false;
+  }
+  if (!(p->cs_ok && p->cs_layout == c->layout_gen)) return cs64_refused(c);
+  if (step_end > step_begin) DSGD_TRY(launch_cs64(c, p, step_begin, step_end, lr));
+  c->pending_samples += p->offsets[step_end * p->n_workers] - p->offsets[step_begin * p->n_workers];
+  return DSGD_OK;
+}
 // the lists are in p->d_idx (enqueued on the build stream): lay the plan out for the device, close its set-up
 static int plan_finish(dsgd_ctx* c, dsgd_plan* p, dsgd_plan** out) {
   int rc = DSGD_OK;
   // the column slices of the reference's own step sizes are laid out NOW (by the device, on the build stream), not inside
   // the first dsgd_plan_run -- a call its callers time; without a column layout yet (no data / no dimSparsity) at the first run
-  if (c->cs_enable && !c->comm && c->d_row_ptr && c->have_ds && !c->async_running) {
+  if ((c->cs_enable || c->fp64) && !c->comm && c->d_row_ptr && c->have_ds && !c->async_running) {
     rc = prepare_layout(c);
     if (rc == DSGD_OK) rc = cs_build(c, p);
+    if (rc == DSGD_OK && c->fp64 && !p->cs_ok) rc = cs64_refused(c);
   }
   if (rc == DSGD_OK && hipEventRecord(p->built_ev, c->build_stream) != hipSuccess) rc = fail(DSGD_EHIP, "hipEventRecord");
   if (rc != DSGD_OK) {
@@ -3751,6 +4017,46 @@ int dsgd_plan_create(dsgd_ctx* c, const int32_t* idx, const int64_t* offsets, in
     return fail(DSGD_EHIP, "plan upload: %s", hipGetErrorString(e));
   }
   return plan_finish(c, p, out);
+}
+
+// a per-request step in an fp64 context (locked, bound, layout ready): a one-step plan, created, run and given back here
+static int sync_step64(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int n_workers, double lr,
+                       dsgd_batch_stats* stats) {
+  std::vector<int64_t> offsets((size_t)n_workers + 1, 0);
+  for (int k = 0; k < n_workers; ++k) {
+    if (n_per_worker[k] <= 0)
+      return fail(DSGD_EINVAL, "worker %d has an empty sample list: Vec.sum requires a non-empty list", k);
+    if (!idx_per_worker[k]) return fail(DSGD_EINVAL, "null index list for worker %d", k);
+    for (int64_t t = 0; t < n_per_worker[k]; ++t)
+      if (idx_per_worker[k][t] < 0 || idx_per_worker[k][t] >= c->n_rows)
+        return fail(DSGD_ERANGE, "sample index %d of worker %d outside the %lld loaded rows", idx_per_worker[k][t], k, c->n_rows);
+    offsets[(size_t)k + 1] = offsets[(size_t)k] + n_per_worker[k];
+  }
+  dsgd_plan* p = nullptr;
+  DSGD_TRY(plan_frame(c, offsets.data(), 1, n_workers, &p));
+  p->h_idx.resize((size_t)offsets[(size_t)n_workers]);
+  for (int k = 0; k < n_workers; ++k)
+    std::copy(idx_per_worker[k], idx_per_worker[k] + n_per_worker[k], p->h_idx.begin() + offsets[(size_t)k]);
+  hipError_t e = hipMemcpyAsync(p->d_idx, p->h_idx.data(), sizeof(int) * p->h_idx.size(), hipMemcpyHostToDevice, c->build_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->build_stream);
+  if (e != hipSuccess) {
+    plan_abandon(c, p);
+    return fail(DSGD_EHIP, "sync step upload: %s", hipGetErrorString(e));
+  }
+  DSGD_TRY(plan_finish(c, p, &p));
+  int rc = reset_counters(c);
+  if (rc == DSGD_OK) {
+    rc = plan_run64(c, p, 0, 1, lr);
+    if (rc == DSGD_OK) c->pending_samples -= offsets[(size_t)n_workers];   // (a request reports its own samples, below)
+  }
+  if (p->built_pending) (void)hipStreamWaitEvent(c->stream, p->built_ev, 0);
+  cache_give(c, p->d_idx, p->idx_bytes);   // (the blocks go back behind the step: an event on the launch stream)
+  cache_give(c, p->d_segs, p->segs_bytes);
+  cs_free(c, p);
+  if (p->built_ev) (void)hipEventDestroy(p->built_ev);
+  delete p;
+  DSGD_TRY(rc);
+  return finish_stats(c, stats, offsets[(size_t)n_workers]);
 }
 
 // slot `i` of the from-seed scratch with room for `bytes`
@@ -4064,10 +4370,10 @@ int dsgd_plan_info(dsgd_ctx* c, dsgd_plan* p, int32_t* vals, int32_t n) {
   DSGD_TRY(check_ctx(c));
   if (!p || !vals || n < 0 || n > 8) return fail(DSGD_EINVAL, "bad plan_info arguments");
   std::lock_guard<std::mutex> lk(c->mu);
-  const bool cs = c->cs_enable && !c->comm && p->cs_ok && p->cs_layout == c->layout_gen;
+  const bool cs = (c->cs_enable || c->fp64) && !c->comm && p->cs_ok && p->cs_layout == c->layout_gen;
   const bool one_wg = !cs && plan_kernel_ok(c, p->max_step_rows, p->n_workers) && p->fits && p->fits_rows == c->n_rows;
   const bool vt = !cs && !one_wg && c->vt_enable && p->vt_ok && p->vt_layout == c->layout_gen;
-  const int32_t all[8] = {cs ? 1 : (one_wg ? 2 : (vt ? 3 : (p->cs_layout == c->layout_gen || p->vt_layout == c->layout_gen ? 4 : 0))),
+  const int32_t all[8] = {(cs && c->fp64) ? 5 : cs ? 1 : (one_wg ? 2 : (vt ? 3 : (p->cs_layout == c->layout_gen || p->vt_layout == c->layout_gen ? 4 : 0))),
                           cs ? p->cs_G : 0, cs ? p->cs_slot_stride : 0, cs ? p->cs_row_stride : 0, cs ? p->cs_cl_stride : 0,
                           cs ? p->cs_spl : 0, (cs && p->cs_device_built) ? 1 : 0, p->gate_words};
   for (int i = 0; i < n; ++i) vals[i] = all[i];
@@ -4114,6 +4420,7 @@ int dsgd_plan_run(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_en
                 p->n_steps);
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(bind(c, true));
+  if (c->fp64) return plan_run64(c, p, step_begin, step_end, (double)lr);
   DSGD_TRY(require_data(c));
   DSGD_TRY(require_ds(c));
   DSGD_TRY(require_sync_mode(c));
@@ -4167,6 +4474,18 @@ int dsgd_plan_run(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_en
   return DSGD_OK;
 }
 
+int dsgd_plan_run_f64(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_end, double lr) {
+  DSGD_TRY(check_ctx(c));
+  if (!p) return fail(DSGD_EINVAL, "null plan");
+  if (step_begin < 0 || step_end > p->n_steps || step_end < step_begin)
+    return fail(DSGD_EINVAL, "steps [%lld, %lld) outside the plan's %lld steps", (long long)step_begin, (long long)step_end,
+                p->n_steps);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_plan_run_f64"));
+  DSGD_TRY(bind(c, true));
+  return plan_run64(c, p, step_begin, step_end, lr);
+}
+
 int dsgd_forward(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, float* pred_out) {
   DSGD_TRY(check_ctx(c));
   if (n < 0 || (n > 0 && (!idx || !pred_out))) return fail(DSGD_EINVAL, "bad forward arguments");
@@ -4197,7 +4516,9 @@ int dsgd_forward(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, flo
   const int G = c->group;
   dim3 grid(grid_for(c, n, G));
   CsrView m = view(c);
-  switch (G) {
+  if (c->fp64) {
+    hipLaunchKernelGGL(dsgd_forward64_kernel, dim3(grid_for(c, n, 16)), dim3(256), 0, c->stream, m, c->d_w64, c->d_idx, (long long)n, d_pred, c->d_sc);
+  } else switch (G) {
     case 64: hipLaunchKernelGGL(dsgd_forward_kernel<64>, grid, dim3(256), 0, c->stream, m, c->d_w, c->d_idx, (long long)n, d_pred, c->d_sc); break;
     case 32: hipLaunchKernelGGL(dsgd_forward_kernel<32>, grid, dim3(256), 0, c->stream, m, c->d_w, c->d_idx, (long long)n, d_pred, c->d_sc); break;
     case 16: hipLaunchKernelGGL(dsgd_forward_kernel<16>, grid, dim3(256), 0, c->stream, m, c->d_w, c->d_idx, (long long)n, d_pred, c->d_sc); break;
@@ -4224,6 +4545,15 @@ static int eval_enqueue(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t 
   // |w|^2 of the loss: cached with s while the synchronous kernels own w; while the lock-free engine runs w moves
   // under the cache, so every check recomputes it (MasterAsync's leaky loss check, core/MasterAsync.scala:96-162,
   // compares successive losses).  The engine keeps its own s (HogState), so refreshing d_sc here disturbs nothing.
+  if (c->fp64) {   // fp64 tallies and |w|^2 (csrc/dsgd_cs64.hpp)
+    DSGD_TRY(reset_counters(c));
+    const long long rows = row_end - row_begin;
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>((long long)c->n_cu * 8, (rows + 15) / 16)));
+    hipLaunchKernelGGL(dsgd_eval64_kernel, grid, dim3(256), 0, c->stream, view(c), c->d_w64, (long long)row_begin, (long long)row_end, c->d_sc);
+    hipLaunchKernelGGL(dsgd_norm64_kernel, dim3(1), dim3(256), 0, c->stream, c->d_w64, c->dp, c->d_nsq64);
+    HIP_TRY(hipGetLastError());
+    return DSGD_OK;
+  }
   if (c->async_running || c->nsq_dirty) c->s_dirty = true;
   DSGD_TRY(ensure_s(c));  // also refreshes |w|^2
   if (c->async_running) c->s_dirty = true;
@@ -4265,7 +4595,9 @@ static int eval_read(dsgd_ctx* c, double* loss, double* acc, int64_t* counts) {
   DSGD_TRY(read_scalars(c));
   for (int i = 0; i < 4; ++i) tallies[i] = (long long)c->h_sc->counts[i];
   const double n = (double)tallies[3];
-  if (loss) *loss = c->cfg.lambda * (double)c->h_sc->wnorm2 + ((double)tallies[1] + 2.0 * (double)tallies[2]) / n;
+  double nsq = (double)c->h_sc->wnorm2;
+  if (c->fp64) HIP_TRY(hipMemcpy(&nsq, c->d_nsq64, sizeof(double), hipMemcpyDeviceToHost));
+  if (loss) *loss = c->cfg.lambda * nsq + ((double)tallies[1] + 2.0 * (double)tallies[2]) / n;
   if (acc) *acc = (double)tallies[0] / n;
   if (counts) {
     counts[0] = tallies[0];
@@ -4287,6 +4619,7 @@ int dsgd_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row_en
 
 int dsgd_async_step(dsgd_ctx* c, const int32_t* idx, int64_t n, float lr, float* delta_out, dsgd_batch_stats* stats) {
   DSGD_TRY(check_ctx(c));
+  DSGD_TRY(refuse_fp64(c, "dsgd_async_step"));
   if (n <= 0 || !idx) return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors");
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(bind(c));
@@ -4313,6 +4646,7 @@ int dsgd_async_step(dsgd_ctx* c, const int32_t* idx, int64_t n, float lr, float*
 
 int dsgd_update_grad(dsgd_ctx* c, const int32_t* key, const float* dv, int64_t nnz) {
   DSGD_TRY(check_ctx(c));
+  DSGD_TRY(refuse_fp64(c, "dsgd_update_grad"));
   if (nnz < 0 || (nnz > 0 && (!key || !dv))) return fail(DSGD_EINVAL, "bad update arguments");
   if (nnz == 0) return DSGD_OK;
   for (int64_t i = 0; i < nnz; ++i)   // the keys are host data: validated here, no device-side error flag to wait for
@@ -4434,6 +4768,7 @@ static int exchange_round(dsgd_ctx* c, long long upto) {
 int dsgd_async_start(dsgd_ctx* c, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,
                      float lr, int64_t max_updates, uint64_t seed, int32_t positional_bug) {
   DSGD_TRY(check_ctx(c));
+  DSGD_TRY(refuse_fp64(c, "dsgd_async_start"));
   if (!assigned_begin || !assigned_end || n_workers < 1) return fail(DSGD_EINVAL, "need at least one worker");
   if (batch < 1 || batch > HOG_MAX_BATCH) return fail(DSGD_EINVAL, "batch %d outside [1, %d]", batch, HOG_MAX_BATCH);
   if (max_updates < 0) return fail(DSGD_EINVAL, "negative max_updates");
@@ -4766,6 +5101,7 @@ int dsgd_comm_unique_id(char* id_out) {
 
 int dsgd_comm_init(dsgd_ctx* c, const char* unique_id, int32_t world_size, int32_t rank) {
   DSGD_TRY(check_ctx(c));
+  DSGD_TRY(refuse_fp64(c, "dsgd_comm_init"));
   if (!unique_id || world_size < 1 || rank < 0 || rank >= world_size) return fail(DSGD_EINVAL, "bad communicator arguments");
   if (!rccl::available()) return fail(DSGD_ERCCL, "librccl could not be loaded");
   std::lock_guard<std::mutex> lk(c->mu);
@@ -4882,6 +5218,7 @@ extern "C" {
 int dsgd_comm_init_all(dsgd_ctx* const* ctxs, int32_t n_ctx) {
   MultiLock ml;
   DSGD_TRY(ml.lock(ctxs, n_ctx));
+  DSGD_TRY(refuse_fp64_all(ctxs, n_ctx, "dsgd_comm_init_all"));
   if (!rccl::available()) return fail(DSGD_ERCCL, "librccl could not be loaded");
   for (int i = 0; i < n_ctx; ++i)
     if (ctxs[i]->comm) return fail(DSGD_ESTATE, "communicator already attached to context %d", i);
@@ -4912,6 +5249,7 @@ int dsgd_comm_init_all(dsgd_ctx* const* ctxs, int32_t n_ctx) {
 int dsgd_build_dim_sparsity_devices(dsgd_ctx* const* ctxs, int32_t n_ctx, const int64_t* n_train_per_ctx) {
   MultiLock ml;
   DSGD_TRY(ml.lock(ctxs, n_ctx));
+  DSGD_TRY(refuse_fp64_all(ctxs, n_ctx, "dsgd_build_dim_sparsity_devices"));
   if (!n_train_per_ctx) return fail(DSGD_EINVAL, "null n_train_per_ctx");
   DSGD_TRY(group_shape(ctxs, n_ctx));
   std::vector<unsigned int*> cnt((size_t)n_ctx, nullptr);
@@ -4993,6 +5331,7 @@ int dsgd_sync_step_devices(dsgd_ctx* const* ctxs, int32_t n_ctx, const int32_t* 
                            const int64_t* n_per_worker, int32_t workers_per_ctx, float lr, dsgd_batch_stats* stats) {
   MultiLock ml;
   DSGD_TRY(ml.lock(ctxs, n_ctx));
+  DSGD_TRY(refuse_fp64_all(ctxs, n_ctx, "dsgd_sync_step_devices"));
   if (workers_per_ctx < 1 || !idx_per_worker || !n_per_worker) return fail(DSGD_EINVAL, "need at least one worker per context");
   DSGD_TRY(devices_step_checks(ctxs, n_ctx));
   std::vector<long long> totals((size_t)n_ctx, 0);
@@ -5015,6 +5354,7 @@ int dsgd_sync_step_ranges_devices(dsgd_ctx* const* ctxs, int32_t n_ctx, const in
                                   int32_t workers_per_ctx, float lr, dsgd_batch_stats* stats) {
   MultiLock ml;
   DSGD_TRY(ml.lock(ctxs, n_ctx));
+  DSGD_TRY(refuse_fp64_all(ctxs, n_ctx, "dsgd_sync_step_ranges_devices"));
   if (workers_per_ctx < 1 || !row_begin || !row_end) return fail(DSGD_EINVAL, "need at least one worker per context");
   DSGD_TRY(devices_step_checks(ctxs, n_ctx));
   std::vector<long long> totals((size_t)n_ctx, 0);
@@ -5033,6 +5373,7 @@ int dsgd_loss_acc_devices(dsgd_ctx* const* ctxs, int32_t n_ctx, const int64_t* r
                           double* acc, int64_t* counts) {
   MultiLock ml;
   DSGD_TRY(ml.lock(ctxs, n_ctx));
+  DSGD_TRY(refuse_fp64_all(ctxs, n_ctx, "dsgd_loss_acc_devices"));
   if (!row_begin || !row_end) return fail(DSGD_EINVAL, "null row ranges");
   DSGD_TRY(group_shape(ctxs, n_ctx));
   for (int i = 0; i < n_ctx; ++i) {

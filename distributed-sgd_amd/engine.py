@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BatchStats, Config, check, f32, i32, ptr
+from ._lib import BatchStats, Config, check, f32, f64, i32, ptr
 
 
 class Plan:
@@ -30,7 +30,7 @@ class Plan:
         and, for column slices, the layout's shape; see dsgd_plan_info."""
         v = (C.c_int32 * 8)()
         check(_lib.load().dsgd_plan_info(self.engine._ctx, self.handle, v, C.c_int32(8)))
-        kinds = {0: "not_laid_out", 1: "column_slices", 2: "one_workgroup", 3: "virtual_tiles", 4: "row_parallel"}
+        kinds = {0: "not_laid_out", 1: "column_slices", 2: "one_workgroup", 3: "virtual_tiles", 4: "row_parallel", 5: "column_slices_fp64"}
         return {"kind": kinds.get(int(v[0]), "?"), "slices": int(v[1]), "slot_stride": int(v[2]), "row_stride": int(v[3]),
                 "col_list_stride": int(v[4]), "slots_per_lane": int(v[5]), "device_built": bool(v[6]), "record_words": int(v[7])}
 
@@ -54,12 +54,20 @@ class Plan:
 
 
 class Engine:
-    def __init__(self, n_features, lam, device=0, flags=0):
+    def __init__(self, n_features, lam, device=0, flags=0, precision="fp32"):
+        """precision: "fp32" (default) or "fp64" -- the fp64 mode (DSGD_F_FP64, include/dsgd.h "THE FP64 MODE"): fp64
+        weights and dimSparsity, plans of the reference's batch sizes (<= 4 workers, <= 1,024 rows per step) on the fp64
+        column-slice kernel; get_weights / build_dim_sparsity return float64 there."""
+        if precision not in ("fp32", "fp64"):
+            raise ValueError("precision must be 'fp32' or 'fp64', not %r" % (precision,))
         self._lib = _lib.load()
         self._ctx = C.c_void_p()
         self.dim = int(n_features)
         self.dp = self.dim + 1
         self.lam = float(lam)
+        self.precision = precision
+        if precision == "fp64":
+            flags = int(flags) | _lib.F_FP64
         cfg = Config(self.dim, int(device), self.lam, int(flags), 0)
         check(self._lib.dsgd_create(C.byref(cfg), C.byref(self._ctx)))
         self.n_rows = 0
@@ -97,21 +105,55 @@ class Engine:
         check(self._lib.dsgd_load_csr(self._ctx, C.c_int64(n_rows), ptr(row_ptr), ptr(col), ptr(val), ptr(label)))
         self.n_rows, self.nnz = n_rows, int(row_ptr[-1])
 
+    @property
+    def fp64(self):
+        return self.precision == "fp64"
+
     def set_dim_sparsity(self, ds):
+        if self.fp64 and np.asarray(ds).dtype == np.float64:   # (kept as it is)
+            check(self._lib.dsgd_set_dim_sparsity_f64(self._ctx, ptr(f64(ds, self.dp))))
+            return
         check(self._lib.dsgd_set_dim_sparsity(self._ctx, ptr(f32(ds, self.dp))))
 
     def build_dim_sparsity(self, n_train):
+        if self.fp64:   # (the fp64 values, bit for bit the oracle's)
+            check(self._lib.dsgd_build_dim_sparsity(self._ctx, C.c_int64(n_train), None))
+            return self.get_dim_sparsity()
         out = np.zeros(self.dp, dtype=np.float32)
         check(self._lib.dsgd_build_dim_sparsity(self._ctx, C.c_int64(n_train), ptr(out)))
         return out
 
+    def get_dim_sparsity(self):
+        """dimSparsity as the fp64 context holds it (float64; fp64 engines only)."""
+        out = np.zeros(self.dp, dtype=np.float64)
+        check(self._lib.dsgd_get_dim_sparsity_f64(self._ctx, ptr(out)))
+        return out
+
     def set_weights(self, w):
+        if self.fp64 and np.asarray(w).dtype == np.float64:   # (kept as it is)
+            check(self._lib.dsgd_set_weights_f64(self._ctx, ptr(f64(w, self.dp))))
+            return
         check(self._lib.dsgd_set_weights(self._ctx, ptr(f32(w, self.dp))))
 
     def get_weights(self):
+        if self.fp64:
+            out = np.zeros(self.dp, dtype=np.float64)
+            check(self._lib.dsgd_get_weights_f64(self._ctx, ptr(out)))
+            return out
         out = np.zeros(self.dp, dtype=np.float32)
         check(self._lib.dsgd_get_weights(self._ctx, ptr(out)))
         return out
+
+    def get_weights_f32(self):
+        """The weights through the float entry point (an fp64 context rounds its fp64 weights)."""
+        out = np.zeros(self.dp, dtype=np.float32)
+        check(self._lib.dsgd_get_weights(self._ctx, ptr(out)))
+        return out
+
+    def precision_bits(self):
+        v = C.c_int32(0)
+        check(self._lib.dsgd_precision(self._ctx, C.byref(v)))
+        return v.value
 
     # -- synchronous path ------------------------------------------------------------------------
     def gradient(self, idx, w=None):
@@ -212,6 +254,9 @@ class Engine:
         return held.value
 
     def plan_run(self, plan, step_begin, step_end, lr):
+        if self.fp64:   # (the reference's learning rate is a Double)
+            check(self._lib.dsgd_plan_run_f64(self._ctx, plan.handle, C.c_int64(step_begin), C.c_int64(step_end), C.c_double(lr)))
+            return
         check(self._lib.dsgd_plan_run(self._ctx, plan.handle, C.c_int64(step_begin), C.c_int64(step_end), C.c_float(lr)))
 
     # -- evaluation --------------------------------------------------------------------------------

@@ -560,7 +560,9 @@ class MasterSync:
         """One epoch's batch loop (core/Master.scala:179-199) as one resident plan."""
         K = len(split)
         n_expected = len(range(0, max_samples, batch_size))
-        if batch_size >= max_samples and all(r.step == 1 for r in split) and hasattr(self.backend, "sync_step_ranges"):
+        # (not for an fp64 backend: its steps run through plans only -- include/dsgd.h "THE FP64 MODE")
+        if batch_size >= max_samples and all(r.step == 1 for r in split) and hasattr(self.backend, "sync_step_ranges") \
+                and getattr(self.backend, "precision", "fp32") != "fp64":
             # batch-size >= split size: slice(0, batchSize) of a shuffled split is the WHOLE split, and a sum does not
             # depend on the order -- the step is a sum over contiguous row ranges (dsgd_sync_step_ranges: the streaming
             # kernels).  The shuffles are still drawn: the generator must stand where the reference's stands.

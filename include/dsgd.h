@@ -26,7 +26,10 @@
  *   - a context may be called from several host threads (the reference calls its model from an
  *     8-thread pool, utils/Pool.scala:13); calls on one context are serialised internally.
  *   - arithmetic is IEEE fp32 on the device ("fp32 CSR-SpMV gradient kernel" of BASELINE.json);
- *     the reference is fp64.  Stated tolerance: tests/test_gpu_parity.py.
+ *     the reference is fp64.  Stated tolerance: tests/test_gpu_parity.py.  A context created with
+ *     DSGD_F_FP64 keeps its weights and dimSparsity in fp64 and follows the reference's (and the
+ *     oracle's) fp64 trajectory for the reference's batch sizes; see "THE FP64 MODE" below and
+ *     tests/test_gpu_fp64.py.
  */
 #ifndef DSGD_H
 #define DSGD_H
@@ -50,8 +53,33 @@ enum {
   DSGD_EUNSUPPORTED = -7  /* no gfx950 device / feature not available                          */
 };
 
-/* dsgd_config.flags: none defined (must be 0) */
+/* dsgd_config.flags: 0, or DSGD_F_FP64 (any other bit: DSGD_EINVAL, checked before the device) */
 #define DSGD_F_DEFAULT 0u
+#define DSGD_F_FP64 0x1u
+
+/* THE FP64 MODE (dsgd_config.flags = DSGD_F_FP64; DESIGN.md "fp64 mode").  The reference computes in Double: an fp32
+ * engine decides a row whose margin y (x . w) lies within fp32 round-off of 0 differently (core/ml/SparseSVM.scala:27-28)
+ * and a constant-step run never forgets it.  An fp64 context keeps w and dimSparsity in fp64 and runs synchronous steps
+ * of the reference's sizes through dsgd_cs64_step_kernel (csrc/dsgd_cs64.hpp): fp64 dots, exact 64-bit fixed-point
+ * per-worker sums, the oracle's regulariser / mean / update operation for operation.
+ *   Limits (a plan beyond them is refused with DSGD_EUNSUPPORTED when it is CREATED): at most 4 workers per step, at
+ *   most 1,024 rows per step, and a model that fits the LDS of a slice: D <= 100,847 (1 worker), 75,631 (2),
+ *   60,463 (3), 50,415 (4).  RCV1's D = 47,236 fits all four.  A step whose slice layout exceeds 1,024 slots or
+ *   4,096 columns of one slice is refused as well (at creation once data and dimSparsity are there, else at the run).
+ *   The existing entry points in an fp64 context:
+ *   - dsgd_set_weights / dsgd_set_dim_sparsity (float): the values promoted to fp64.
+ *   - dsgd_get_weights (float): the fp64 weights rounded.
+ *   - dsgd_build_dim_sparsity: fp64 ds[i] = filt(1.0 / (count + 1.0)), bit for bit the oracle's; ds_out gets it rounded.
+ *   - dsgd_plan_create / _n / _from_seed: the same lists and layout as fp32 (see the limits above).
+ *   - dsgd_plan_run (float lr): runs with (double)lr; dsgd_plan_run_f64 takes the reference's Double.
+ *   - dsgd_plan_record / dsgd_plan_read_record: the same gate bits; s_used is the fp64 s rounded.
+ *   - dsgd_plan_info: vals[0] = 5 (fp64 column slices).   dsgd_grad_kernel_name: "dsgd_cs64_step_kernel".
+ *   - dsgd_sync_step: a one-step fp64 plan, created, run and given back inside the call.
+ *   - dsgd_forward, dsgd_loss_acc: evaluated with the fp64 weights (a float w is promoted and replaces them).
+ *   - everything else that would run an fp32 training kernel returns DSGD_EUNSUPPORTED and changes nothing:
+ *     dsgd_gradient, dsgd_apply, dsgd_sync_step_ranges(_async), dsgd_async_*, dsgd_update_grad, dsgd_comm_*,
+ *     dsgd_*_devices.
+ * The entry points below that name fp64 return DSGD_ESTATE on an fp32 context (dsgd_precision excepted).            */
 
 typedef struct dsgd_ctx dsgd_ctx;
 
@@ -108,6 +136,13 @@ int dsgd_build_dim_sparsity(dsgd_ctx* ctx, int64_t n_train, float* ds_out /* D+1
 /* resident weights (GradState.grad holds the WEIGHTS: core/ml/GradState.scala:6-10)           */
 int dsgd_set_weights(dsgd_ctx* ctx, const float* w /* D+1 */);
 int dsgd_get_weights(dsgd_ctx* ctx, float* w_out /* D+1 */);
+
+/* the fp64 mode's own vectors (key order, D+1 doubles) and its precision: *bits_out = 64 or 32                   */
+int dsgd_set_weights_f64(dsgd_ctx* ctx, const double* w /* D+1 */);
+int dsgd_get_weights_f64(dsgd_ctx* ctx, double* w_out /* D+1 */);
+int dsgd_set_dim_sparsity_f64(dsgd_ctx* ctx, const double* ds /* D+1 */);
+int dsgd_get_dim_sparsity_f64(dsgd_ctx* ctx, double* ds_out /* D+1 */);
+int dsgd_precision(dsgd_ctx* ctx, int32_t* bits_out);
 
 /* ---- synchronous path ----------------------------------------------------------------------
  * SlaveImpl.gradient (core/Slave.scala:142-157): g = regularize(sum_i backward(w, x_i, y_i), w).
@@ -191,6 +226,8 @@ int dsgd_plan_destroy(dsgd_ctx* ctx, dsgd_plan* plan);
  * contexts on one GPU (the dev role's JVM workers, Main.scala:144-158) and want the memory between fits.            */
 int dsgd_cache_trim(dsgd_ctx* ctx, int64_t keep_bytes, int64_t* held_out);
 int dsgd_plan_run(dsgd_ctx* ctx, dsgd_plan* plan, int64_t step_begin, int64_t step_end, float lr);
+/* the same in an fp64 context, with the reference's Double learning rate (DSGD_ESTATE on an fp32 context)           */
+int dsgd_plan_run_f64(dsgd_ctx* ctx, dsgd_plan* plan, int64_t step_begin, int64_t step_end, double lr);
 /* How a plan will run (nothing in the reference; benchmarks, tests): vals[0] = 1 column slices (dsgd_cs_step_kernel),
  * 2 the one-workgroup kernel, 3 virtual tiles, 4 the row-parallel kernels, 0 not laid out yet; [1] slices, [2..4] slot /
  * row / column-list strides, [5] slots per lane, [6] 1 if the device laid it out, [7] words per step of the record.

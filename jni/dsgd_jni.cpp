@@ -59,6 +59,7 @@ DSGD_ELEMS(Long, jlong, jlongArray)
 DSGD_ELEMS(Int, jint, jintArray)
 DSGD_ELEMS(Float, jfloat, jfloatArray)
 DSGD_ELEMS(Byte, jbyte, jbyteArray)
+DSGD_ELEMS(Double, jdouble, jdoubleArray)
 #undef DSGD_ELEMS
 }  // namespace
 
@@ -80,6 +81,45 @@ JNIEXPORT jlong JNICALL NATIVE(create)(JNIEnv* env, jobject, jint nFeatures, jdo
 }
 
 JNIEXPORT void JNICALL NATIVE(destroy)(JNIEnv*, jobject, jlong h) { dsgd_destroy(ctx(h)); }
+
+// the same in the fp64 mode (DSGD_F_FP64, include/dsgd.h "THE FP64 MODE"): the reference's Double weights and learning rate
+JNIEXPORT jlong JNICALL NATIVE(createF64)(JNIEnv* env, jobject, jint nFeatures, jdouble lambda, jint device) {
+  dsgd_config cfg{};
+  cfg.n_features = nFeatures;
+  cfg.device = device;
+  cfg.lambda = lambda;
+  cfg.flags = DSGD_F_FP64;
+  dsgd_ctx* c = nullptr;
+  int rc = dsgd_create(&cfg, &c);
+  if (rc) {
+    raise(env, rc);
+    return 0;
+  }
+  return reinterpret_cast<jlong>(c);
+}
+
+JNIEXPORT void JNICALL NATIVE(setWeightsF64)(JNIEnv* env, jobject, jlong h, jdoubleArray w) {
+  int rc;
+  {
+    DoubleElems wv(env, w, JNI_ABORT);
+    rc = dsgd_set_weights_f64(ctx(h), wv.p);
+  }
+  if (rc) raise(env, rc);
+}
+
+JNIEXPORT void JNICALL NATIVE(getWeightsF64)(JNIEnv* env, jobject, jlong h, jdoubleArray wOut) {
+  int rc;
+  {
+    DoubleElems wv(env, wOut, 0);
+    rc = dsgd_get_weights_f64(ctx(h), wv.p);
+  }
+  if (rc) raise(env, rc);
+}
+
+JNIEXPORT void JNICALL NATIVE(planRunF64)(JNIEnv* env, jobject, jlong h, jlong plan, jlong stepBegin, jlong stepEnd, jdouble lr) {
+  int rc = dsgd_plan_run_f64(ctx(h), reinterpret_cast<dsgd_plan*>(plan), stepBegin, stepEnd, lr);
+  if (rc) raise(env, rc);
+}
 
 // Array[(Vec, Int)] flattened by the Scala side to CSR (utils/Dataset.scala:11)
 JNIEXPORT void JNICALL NATIVE(loadCsr)(JNIEnv* env, jobject, jlong h, jlongArray rowPtr, jintArray col, jfloatArray val,

@@ -22,6 +22,11 @@ object NativeSVM {
 
   @native def create(nFeatures: Int, lambda: Double, device: Int): Long
   @native def destroy(ctx: Long): Unit
+  // the fp64 mode (include/dsgd.h "THE FP64 MODE"): Double weights and learning rate, the reference's own trajectory
+  @native def createF64(nFeatures: Int, lambda: Double, device: Int): Long
+  @native def setWeightsF64(ctx: Long, w: Array[Double]): Unit
+  @native def getWeightsF64(ctx: Long, wOut: Array[Double]): Unit
+  @native def planRunF64(ctx: Long, plan: Long, stepBegin: Long, stepEnd: Long, lr: Double): Unit
   @native def loadCsr(ctx: Long, rowPtr: Array[Long], col: Array[Int], value: Array[Float], label: Array[Byte]): Unit
   @native def buildDimSparsity(ctx: Long, nTrain: Long): Unit
   @native def gradient(ctx: Long, w: Array[Float], idx: Array[Int], gOut: Array[Float]): Long

@@ -4,6 +4,9 @@ loss and accuracy, fit (sync or async, early stopping by patience / conv-delta),
 accuracy -- with the HIP engine hosting all the workers.
 
     DSGD_DATA_PATH=/data/rcv1 python tools/train.py [--conf application.conf] [--synthetic ROWS] [--device 0] [--weights-out w.txt]
+                                                    [--precision fp64]
+
+--precision fp64: the engine keeps the reference's Double weights (include/dsgd.h "THE FP64 MODE"); synchronous fits only.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,6 +19,7 @@ ap.add_argument("--conf", help="application.conf to read the dsgd{...} block fro
 ap.add_argument("--synthetic", type=int, default=0, help="use N synthetic RCV1-like rows instead of data-path")
 ap.add_argument("--device", type=int, default=0)
 ap.add_argument("--weights-out", help="write the `idx:value` line of Main.scala:114 here instead of logging it")
+ap.add_argument("--precision", choices=("fp32", "fp64"), default="fp32", help="fp64: the reference's Double arithmetic (sync only)")
 a = ap.parse_args()
 
 
@@ -31,7 +35,9 @@ data = dsgd_amd.synth.generate(a.synthetic, seed=0) if a.synthetic else rcv1.loa
 log("data loaded: {} ({}s)", data.n_rows, round(time.time() - t0, 2))
 n_train = int(data.n_rows * 0.8)                                              # Main.scala:52
 metrics = host.Metrics()
-with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device) as eng:
+if a.precision == "fp64" and cfg.async_:
+    sys.exit("--precision fp64 runs the synchronous master only (the lock-free engine is fp32)")
+with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device, precision=a.precision) as eng:
     eng.load_csr(data.row_ptr, data.col, data.val, data.label)
     t0 = time.time()
     eng.build_dim_sparsity(n_train)                                            # Main.scala:54-65
@@ -50,14 +56,17 @@ with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device) as eng:
         master = host.MasterSync(eng, n_train, data.n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log, metrics=metrics)
         state = master.fit(w0, cfg.max_epochs, cfg.batch_size, cfg.learning_rate, stop)
     log("fit ({}s)", round(time.time() - t0, 3))
-    w1 = np.asarray(state.grad, dtype=np.float32)
+    w1 = np.asarray(state.grad, dtype=np.float64 if a.precision == "fp64" else np.float32)
     line = host.format_final_weights(w1)
     if a.weights_out:
         open(a.weights_out, "w").write(line + "\n")
         log("final weights: {} entries written to {}", int(np.count_nonzero(w1)), a.weights_out)
     else:
         log("final weights: {}", line)
-    l1, a1, _ = eng.loss_acc(n_train, data.n_rows, w=w1)                       # localLoss / localAccuracy on testData
+    if a.precision == "fp64":   # (the fp64 weights are the engine's own: no float copy replaces them)
+        l1, a1, _ = eng.loss_acc(n_train, data.n_rows)
+    else:
+        l1, a1, _ = eng.loss_acc(n_train, data.n_rows, w=w1)                   # localLoss / localAccuracy on testData
     log("final test loss: {}", l1)
     log("final test accuracy: {}", a1)
     if cfg.record:
