@@ -185,6 +185,28 @@ __device__ __forceinline__ void cs64_sweep(Cs64State& z, const unsigned short (&
   }
 }
 
+// The listed columns of an asynchronous iteration, one worker (orc_async_step per column, core/Slave.scala:92-101): ONE
+// rounding of the exact sum, filt; the mean over the n rows of the step, inactive ones included (Vec.mean); the
+// support-only regulariser filt(g + s); filt(g * lr), written to `delta` (the slice's [Sp], may be null); filt(w - upd).
+template <int NT, int CLT>
+__device__ __forceinline__ void cs64_async_sweep(Cs64State& z, const unsigned short (&cl)[CLT], int n_cols, int Sp, double inv_scale,
+                                                 double s, bool add, double lr, double n, double* delta) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < CLT; ++i) {
+    if (i * NT >= n_cols) break;   // (workgroup-uniform: the list is dense from entry 0)
+    const int c = cl[i] == 0xffffu ? Sp - 1 : (int)cl[i];
+    const long long t = (long long)z.acc[c];
+    z.acc[c] = 0ull;
+    const double g0 = filt64((double)t * inv_scale);            // one rounding of the exact sum (the power of two is exact)
+    const double gm = filt64(g0 / n);                           // Vec.mean (correctly rounded division)
+    const double g = (add && gm != 0.0) ? filt64(gm + s) : gm;  // ref: core/ml/SparseSVM.scala:31, math/Vec.scala:65-75
+    const double upd = filt64(g * lr);                          // learningRate * regularize(grad) (ref: core/Slave.scala:99)
+    if (delta != nullptr) delta[c] = upd;
+    z.w_l[c] = filt64(z.w_l[c] - upd);                          // ref: core/Slave.scala:101
+  }
+}
+
 // the slots of `step` into R (cs_issue over the plan's layout)
 template <int NT, int SPL, int CLT>
 __device__ __forceinline__ void cs64_issue(const Cs64Args& a, int b, long long step, CsSet<SPL, CLT>& R) {
@@ -204,8 +226,10 @@ __device__ __forceinline__ void cs64_issue(const Cs64Args& a, int b, long long s
 }
 
 // One step.  `cur`: the step's slots (landed); `nxt` receives the next step's.  false = the launch was aborted.
-template <int NT, int SPL, int CLT>
-__device__ __forceinline__ bool cs64_step(const Cs64Args& a, Cs64State& z, CsSet<SPL, CLT>& cur, CsSet<SPL, CLT>& nxt, long long step) {
+// ASYNC: one asynchronous iteration of the one worker (cs64_async_sweep), `delta` the slice's share of its update or null.
+template <int NT, int SPL, int CLT, bool ASYNC = false>
+__device__ __forceinline__ bool cs64_step(const Cs64Args& a, Cs64State& z, CsSet<SPL, CLT>& cur, CsSet<SPL, CLT>& nxt, long long step,
+                                          double* delta = nullptr) {
 #pragma clang fp contract(off)
   int tid = threadIdx.x, K = __builtin_amdgcn_readfirstlane(a.K), b = z.b, Sp = __builtin_amdgcn_readfirstlane(z.Sp);
   asm volatile("" : "+v"(tid));
@@ -328,11 +352,16 @@ __device__ __forceinline__ bool cs64_step(const Cs64Args& a, Cs64State& z, CsSet
   if (SPL != 1) cs64_issue<NT, SPL, CLT>(a, b, step + 1, nxt);
   cs_barrier();
   // ---- 5: the listed columns: the worker sums, regulariser, fold, mean, update ----
-  switch (K) {
-    case 1: cs64_sweep<NT, 1, CLT>(z, cur.cl, n_cols, Sp, inv_scale, s, add, a.lr); break;
-    case 2: cs64_sweep<NT, 2, CLT>(z, cur.cl, n_cols, Sp, inv_scale, s, add, a.lr); break;
-    case 3: cs64_sweep<NT, 3, CLT>(z, cur.cl, n_cols, Sp, inv_scale, s, add, a.lr); break;
-    default: cs64_sweep<NT, 4, CLT>(z, cur.cl, n_cols, Sp, inv_scale, s, add, a.lr); break;
+  if constexpr (ASYNC) {
+    cs64_async_sweep<NT, CLT>(z, cur.cl, n_cols, Sp, inv_scale, s, add, a.lr, (double)n_rows,
+                              delta != nullptr ? delta + (long long)b * Sp : nullptr);
+  } else {
+    switch (K) {
+      case 1: cs64_sweep<NT, 1, CLT>(z, cur.cl, n_cols, Sp, inv_scale, s, add, a.lr); break;
+      case 2: cs64_sweep<NT, 2, CLT>(z, cur.cl, n_cols, Sp, inv_scale, s, add, a.lr); break;
+      case 3: cs64_sweep<NT, 3, CLT>(z, cur.cl, n_cols, Sp, inv_scale, s, add, a.lr); break;
+      default: cs64_sweep<NT, 4, CLT>(z, cur.cl, n_cols, Sp, inv_scale, s, add, a.lr); break;
+    }
   }
   cs_barrier();
   z.sp = cs64_block_sum<NT>(cs64_wds_share<NT>(z), red);
@@ -377,6 +406,70 @@ __global__ void __launch_bounds__(NT) dsgd_cs64_step_kernel(Cs64Args a) {
     ok = cs64_step<NT, SPL, CLT>(a, z, A, B, step);
     if (!ok || step + 1 >= a.step_end) break;
     ok = cs64_step<NT, SPL, CLT>(a, z, B, A, step + 1);
+    if (!ok) break;
+  }
+  if (ok) {   // (given up: no slice writes back -- see cs_launch_body)
+    double2* ws2 = reinterpret_cast<double2*>(a.w + (long long)z.b * z.Sp);
+    const double2* wl2 = reinterpret_cast<const double2*>(z.w_l);
+    for (int i = tid; i < (z.Sp >> 1); i += NT) ws2[i] = wl2[i];
+  } else if (tid == 0) {
+    atomicOr(&a.sc->err, 8);
+  }
+  if (z.b != 0) return;
+  const unsigned int n_act = wave_sum_u32(ok ? z.n_act : 0u);
+  __syncthreads();
+  unsigned int* r4 = reinterpret_cast<unsigned int*>(z.red);
+  if ((tid & 63) == 0) r4[tid >> 6] = n_act;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned int tot = 0u;
+    for (int i = 0; i < NT / 64; ++i) tot += r4[i];
+    if (tot) atomicAdd(&a.sc->n_active, (unsigned long long)tot);
+  }
+}
+
+// The asynchronous iterations of a ONE-worker plan (core/Slave.scala:79-111 asyncTask, oracle.c orc_async_step): the
+// same layout, slices, exchange and abort word as dsgd_cs64_step_kernel (whose body this repeats: its own code stays as it
+// was compiled), the finish of cs64_async_sweep.  The weights are filtered as they are loaded -- the oracle writes
+// filt(w - 0) on every coordinate, listed or not.  delta: [G][Sp] slice-major updates of the listed columns, or null.
+template <int NT, int SPL, int CLT>
+__global__ void __launch_bounds__(NT) dsgd_cs64_async_kernel(Cs64Args a, double* delta) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) double lds64[];
+  const int tid = threadIdx.x;
+  const int K = a.K;
+  Cs64State z;
+  z.b = blockIdx.x;
+  z.Sp = cs64_sp(a.dp);
+  z.w_l = lds64;
+  z.ds_l = lds64 + z.Sp;
+  z.acc = reinterpret_cast<unsigned long long*>(lds64 + 2 * z.Sp);
+  z.ps = lds64 + (2 + K) * z.Sp;
+  z.red = z.ps + CS_MAX_SLOTS;
+  z.coef = reinterpret_cast<float*>(z.red + 32);
+  z.n_act = 0u;
+  z.n_rel = 0u;
+  CsSet<SPL, CLT> A, B;
+  cs64_issue<NT, SPL, CLT>(a, z.b, a.step_begin, A);
+  {   // the slice's weights and dimSparsity (the padding holds zeros); the accumulators cleared
+    const double2* ws2 = reinterpret_cast<const double2*>(a.w + (long long)z.b * z.Sp);
+    const double2* ds2 = reinterpret_cast<const double2*>(a.ds + (long long)z.b * z.Sp);
+    double2* wl2 = reinterpret_cast<double2*>(z.w_l);
+    double2* dl2 = reinterpret_cast<double2*>(z.ds_l);
+    for (int i = tid; i < (z.Sp >> 1); i += NT) {   // (filtered: see above)
+      const double2 v = ws2[i];
+      wl2[i] = make_double2(filt64(v.x), filt64(v.y));
+      dl2[i] = ds2[i];
+    }
+    for (int i = tid; i < K * z.Sp; i += NT) z.acc[i] = 0ull;
+  }
+  cs_barrier();
+  z.sp = cs64_block_sum<NT>(cs64_wds_share<NT>(z), z.red);
+  bool ok = true;
+  for (long long step = a.step_begin; step < a.step_end; step += 2) {
+    ok = cs64_step<NT, SPL, CLT, true>(a, z, A, B, step, delta);
+    if (!ok || step + 1 >= a.step_end) break;
+    ok = cs64_step<NT, SPL, CLT, true>(a, z, B, A, step + 1, delta);
     if (!ok) break;
   }
   if (ok) {   // (given up: no slice writes back -- see cs_launch_body)
@@ -496,4 +589,52 @@ __global__ void __launch_bounds__(256) dsgd_norm64_kernel(const double* __restri
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
   __syncthreads();
   if (threadIdx.x == 0) *out = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// The lists of an asynchronous run on the zero-lag schedule: update u = first + blockIdx.x is worker k = u mod K at its own
+// iteration u div K, and its rows are exactly what the lock-free engine's worker k draws there (hog_sampler / row_at of
+// dsgd_hogwild_kernel; oracle/hogwild_replay.hog_rows): base + (mul * t + off) mod n_k, t = 0..batch-1.
+struct AsyncListArgs {
+  const long long* asg_begin;   // [K] the workers' row ranges
+  const long long* asg_end;
+  int K, batch, positional_bug;
+  unsigned long long seed;
+  long long first;
+  int* idx_out;                 // [n_updates][batch]
+};
+__global__ void __launch_bounds__(256) dsgd_async_lists_kernel(AsyncListArgs a) {
+  __shared__ unsigned long long mo[2];
+  const long long u = a.first + (long long)blockIdx.x;
+  const int worker = (int)(u % a.K);
+  const unsigned long long it = (unsigned long long)(u / a.K);
+  const long long begin = a.asg_begin[worker];
+  const unsigned int n_k = (unsigned int)(a.asg_end[worker] - begin);
+  if (threadIdx.x == 0) {
+    const unsigned long long key = hog_mix(a.seed ^ hog_mix((unsigned long long)worker * 0x100000001B3ull + it));
+    unsigned int mul = 1u + (unsigned int)(hog_mix(key) % (unsigned long long)n_k);
+    while (hog_gcd32(mul, n_k) != 1u) mul = mul % n_k + 1u;
+    mo[0] = mul;
+    mo[1] = hog_mix(key ^ 0xABCDEF12345ull) % (unsigned long long)n_k;
+  }
+  __syncthreads();
+  const unsigned long long mul = mo[0], off = mo[1];
+  const long long base = a.positional_bug ? 0 : begin;   // ref: core/Slave.scala:87 indexes `data` by POSITION
+  int* out = a.idx_out + (long long)blockIdx.x * a.batch;
+  for (int t = threadIdx.x; t < a.batch; t += 256) out[t] = (int)(base + (long long)((mul * (unsigned long long)t + off) % n_k));
+}
+
+// A peer's update (core/Slave.scala:177-185, GradState.scala:8): w[k] = filt(w[k] - dv) for each (unique) key, in
+// whichever layout the weights are: rank order (Sp = 0) or slice-major [G][Sp]
+__global__ void __launch_bounds__(256) dsgd_update64_kernel(const int* __restrict__ key, const double* __restrict__ dv, int nnz,
+                                                           const int* __restrict__ perm, double* w, int Sp) {
+#pragma clang fp contract(off)
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += gridDim.x * blockDim.x) {
+    const int r = perm[key[i]];
+    const long long at = Sp ? (long long)(r % CS64_G) * Sp + r / CS64_G : (long long)r;
+    w[at] = filt64(w[at] - dv[i]);
+  }
+}
+// ... then the whole vector filtered, as dsgd_filter_kernel does for the fp32 weights
+__global__ void __launch_bounds__(256) dsgd_filter64_kernel(double* w, int n) {
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) w[j] = filt64(w[j]);
 }

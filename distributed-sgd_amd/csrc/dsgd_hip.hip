@@ -500,6 +500,10 @@ struct dsgd_ctx {
   double* d_nsq64 = nullptr;              // |w|^2 of the loss
   unsigned long long* d_cs64_x = nullptr; // exchange buffer of dsgd_cs64_step_kernel: [2][CS64_G][2 * CS_XSTRIDE] granules
   unsigned int cs64_tag0 = 0;
+  double* d_cs_dl64 = nullptr;            // dsgd_async_step_f64: the update of the listed columns, slice-major [CS64_G][Sp]
+  int* d_upd64_key = nullptr;             // dsgd_update_grad_f64: the keys and values of a peer's update (grow-only)
+  double* d_upd64_dv = nullptr;
+  long long upd64_cap = 0;
 };
 
 static int check_ctx(dsgd_ctx* c) {
@@ -1588,8 +1592,10 @@ static int launch_cs(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long 
   return DSGD_OK;
 }
 
-// the steps [step_begin, step_end) of a plan in an fp64 context (csrc/dsgd_cs64.hpp): ONE launch
-static int launch_cs64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr) {
+// the steps [step_begin, step_end) of a plan in an fp64 context (csrc/dsgd_cs64.hpp): ONE launch.  async: the asynchronous
+// iterations of a one-worker plan (dsgd_cs64_async_kernel), `delta` ([CS64_G][Sp]) receiving their updates or null
+static int launch_cs64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr, bool async = false,
+                       double* delta = nullptr) {
   const int Sp = cs64_sp(c->dp), n = CS64_G * Sp;
   if (!c->d_cs64_x) {
     HIP_TRY(hipMalloc(&c->d_cs64_x, sizeof(unsigned long long) * 2 * CS64_G * CS64_XSTRIDE2));
@@ -1642,12 +1648,16 @@ static int launch_cs64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long lon
   a.gate_words = p->gate_words;
   const size_t lds = (size_t)cs64_lds_bytes(c->dp, a.K);
   c->ctr_known = false;
-  if (p->cs_spl == 1)
+  if (async && p->cs_spl == 1)
+    hipLaunchKernelGGL((dsgd_cs64_async_kernel<CS_THREADS, 1, 4>), dim3(CS64_G), dim3(CS_THREADS), lds, c->stream, a, delta);
+  else if (async)
+    hipLaunchKernelGGL((dsgd_cs64_async_kernel<CS_THREADS, 2, 8>), dim3(CS64_G), dim3(CS_THREADS), lds, c->stream, a, delta);
+  else if (p->cs_spl == 1)
     hipLaunchKernelGGL((dsgd_cs64_step_kernel<CS_THREADS, 1, 4>), dim3(CS64_G), dim3(CS_THREADS), lds, c->stream, a);
   else
     hipLaunchKernelGGL((dsgd_cs64_step_kernel<CS_THREADS, 2, 8>), dim3(CS64_G), dim3(CS_THREADS), lds, c->stream, a);
   HIP_TRY(hipGetLastError());
-  c->last_grad_kernel = "dsgd_cs64_step_kernel";
+  c->last_grad_kernel = async ? "dsgd_cs64_async_kernel" : "dsgd_cs64_step_kernel";
   c->last_shift = p->cs_shift[(size_t)(step_end - 1)] + 32;
   return DSGD_OK;
 }
@@ -3081,6 +3091,8 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
     HIP_TRY_B(hipMemsetAsync(c->d_ds64, 0, sizeof(double) * c->dp, c->stream));
     DSGD_ATTR((dsgd_cs64_step_kernel<CS_THREADS, 1, 4>));
     DSGD_ATTR((dsgd_cs64_step_kernel<CS_THREADS, 2, 8>));
+    DSGD_ATTR((dsgd_cs64_async_kernel<CS_THREADS, 1, 4>));
+    DSGD_ATTR((dsgd_cs64_async_kernel<CS_THREADS, 2, 8>));
   }
   {   // the column lists' gradient kernel: its table, the bitmap, 16 words
     const int tc_lds = (int)(sizeof(long long) * TC_MAX_SHARE + TC_MAX_BITS / 8 + 64);
@@ -3140,6 +3152,9 @@ int dsgd_destroy(dsgd_ctx* c) {
   (void)hipFree(c->d_cs_w64);
   (void)hipFree(c->d_cs_ds64);
   (void)hipFree(c->d_cs64_x);
+  (void)hipFree(c->d_cs_dl64);
+  (void)hipFree(c->d_upd64_key);
+  (void)hipFree(c->d_upd64_dv);
   (void)hipFree(c->d_g);
   (void)hipFree(c->d_g64);
   (void)hipFree(c->d_gsum);
@@ -3953,8 +3968,9 @@ static int cs64_refused(dsgd_ctx* c) {
   return fail(DSGD_EUNSUPPORTED, "fp64 plan: a row index outside the loaded data, or a step whose layout exceeds dsgd_cs64_step_kernel "
                                  "(%d slots or %d columns of one slice per step)", CS_MAX_SLOTS, CS_MAX_CLT * CS_THREADS);
 }
-// the steps of a plan in an fp64 context (locked; bound with the slice-major weights kept)
-static int plan_run64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr) {
+// the steps of a plan in an fp64 context (locked; bound with the slice-major weights kept); async: see launch_cs64
+static int plan_run64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr, bool async = false,
+                      double* delta = nullptr) {
   DSGD_TRY(require_data(c));
   DSGD_TRY(require_ds(c));
   DSGD_TRY(require_sync_mode(c));
@@ -3971,7 +3987,7 @@ static int plan_run64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long
     p->built_pending = false;
   }
   if (!(p->cs_ok && p->cs_layout == c->layout_gen)) return cs64_refused(c);
-  if (step_end > step_begin) DSGD_TRY(launch_cs64(c, p, step_begin, step_end, lr));
+  if (step_end > step_begin) DSGD_TRY(launch_cs64(c, p, step_begin, step_end, lr, async, delta));
   c->pending_samples += p->offsets[step_end * p->n_workers] - p->offsets[step_begin * p->n_workers];
   return DSGD_OK;
 }
@@ -4484,6 +4500,169 @@ int dsgd_plan_run_f64(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t ste
   DSGD_TRY(require_fp64(c, "dsgd_plan_run_f64"));
   DSGD_TRY(bind(c, true));
   return plan_run64(c, p, step_begin, step_end, lr);
+}
+
+// ---- the fp64 asynchronous iteration (include/dsgd.h "THE FP64 MODE"; core/Slave.scala:79-111, 177-185) ----
+int dsgd_plan_run_async_f64(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_end, double lr) {
+  DSGD_TRY(check_ctx(c));
+  if (!p) return fail(DSGD_EINVAL, "null plan");
+  if (step_begin < 0 || step_end > p->n_steps || step_end < step_begin)
+    return fail(DSGD_EINVAL, "steps [%lld, %lld) outside the plan's %lld steps", (long long)step_begin, (long long)step_end,
+                p->n_steps);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_plan_run_async_f64"));
+  if (p->n_workers != 1)
+    return fail(DSGD_EINVAL, "an asynchronous iteration is one worker's: this plan has %d workers per step", p->n_workers);
+  DSGD_TRY(bind(c, true));
+  return plan_run64(c, p, step_begin, step_end, lr, true, nullptr);
+}
+
+int dsgd_async_step_f64(dsgd_ctx* c, const int32_t* idx, int64_t n, double lr, double* delta_out, dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  if (n <= 0 || !idx) return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_async_step_f64"));
+  DSGD_TRY(bind(c, true));
+  DSGD_TRY(require_data(c));
+  DSGD_TRY(require_ds(c));
+  DSGD_TRY(require_sync_mode(c));
+  DSGD_TRY(prepare_layout(c));
+  for (int64_t t = 0; t < n; ++t)
+    if (idx[t] < 0 || idx[t] >= c->n_rows) return fail(DSGD_ERANGE, "sample index %d outside the %lld loaded rows", idx[t], c->n_rows);
+  // a one-step, one-worker plan: created, run and given back here (as sync_step64)
+  const int64_t offsets[2] = {0, n};
+  dsgd_plan* p = nullptr;
+  DSGD_TRY(plan_frame(c, offsets, 1, 1, &p));
+  p->h_idx.assign(idx, idx + n);
+  hipError_t e = hipMemcpyAsync(p->d_idx, p->h_idx.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->build_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->build_stream);
+  if (e != hipSuccess) {
+    plan_abandon(c, p);
+    return fail(DSGD_EHIP, "async step upload: %s", hipGetErrorString(e));
+  }
+  DSGD_TRY(plan_finish(c, p, &p));
+  const int Sp = cs64_sp(c->dp);
+  int rc = DSGD_OK;
+  if (delta_out && !c->d_cs_dl64 && hipMalloc(&c->d_cs_dl64, sizeof(double) * ((size_t)CS64_G * Sp + (size_t)c->dp)) != hipSuccess)
+    rc = fail(DSGD_ENOMEM, "out of device memory (the delta of an async step)");
+  if (rc == DSGD_OK && delta_out && hipMemsetAsync(c->d_cs_dl64, 0, sizeof(double) * (size_t)CS64_G * Sp, c->stream) != hipSuccess)
+    rc = fail(DSGD_EHIP, "hipMemsetAsync");
+  if (rc == DSGD_OK) rc = reset_counters(c);
+  if (rc == DSGD_OK) {
+    rc = plan_run64(c, p, 0, 1, lr, true, delta_out ? c->d_cs_dl64 : nullptr);
+    if (rc == DSGD_OK) c->pending_samples -= n;   // (a request reports its own samples, below)
+  }
+  if (p->built_pending) (void)hipStreamWaitEvent(c->stream, p->built_ev, 0);
+  cache_give(c, p->d_idx, p->idx_bytes);   // (the blocks go back behind the step: an event on the launch stream)
+  cache_give(c, p->d_segs, p->segs_bytes);
+  cs_free(c, p);
+  if (p->built_ev) (void)hipEventDestroy(p->built_ev);
+  delete p;
+  DSGD_TRY(rc);
+  DSGD_TRY(finish_stats(c, stats, n));
+  if (delta_out) {   // slice-major -> rank order -> key order
+    double* rank = c->d_cs_dl64 + (size_t)CS64_G * Sp;
+    hipLaunchKernelGGL(dsgd_cs64_unslice_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, c->d_cs_dl64, rank, c->dp, Sp);
+    HIP_TRY(hipGetLastError());
+    DSGD_TRY(take64(c, rank, delta_out));
+  }
+  return DSGD_OK;
+}
+
+int dsgd_update_grad_f64(dsgd_ctx* c, const int32_t* key, const double* dv, int64_t nnz) {
+  DSGD_TRY(check_ctx(c));
+  if (nnz < 0 || (nnz > 0 && (!key || !dv))) return fail(DSGD_EINVAL, "bad update arguments");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_update_grad_f64"));
+  if (nnz == 0) return DSGD_OK;
+  {   // the keys are host data: validated here, before anything moves (a Sparse delta holds each key once)
+    std::vector<unsigned char> seen((size_t)c->dp, 0);
+    for (int64_t i = 0; i < nnz; ++i)
+      if (key[i] < 0 || key[i] >= c->dp) return fail(DSGD_ERANGE, "key %d at position %lld outside [0, %d]", key[i], (long long)i, c->dp - 1);
+    for (int64_t i = 0; i < nnz; ++i) {
+      if (seen[(size_t)key[i]]) return fail(DSGD_EINVAL, "key %d repeated at position %lld: a Sparse delta has unique keys", key[i], (long long)i);
+      seen[(size_t)key[i]] = 1;
+    }
+  }
+  DSGD_TRY(bind(c, true));   // (the weights stay in whichever layout they are: slice-major between plan runs)
+  DSGD_TRY(require_sync_mode(c));
+  if (c->upd64_cap < nnz) {
+    (void)hipFree(c->d_upd64_key);
+    (void)hipFree(c->d_upd64_dv);
+    c->d_upd64_key = nullptr;
+    c->d_upd64_dv = nullptr;
+    c->upd64_cap = 0;
+    const long long cap = std::max<long long>(nnz, 4096);
+    HIP_TRY(hipMalloc(&c->d_upd64_key, sizeof(int) * (size_t)cap));
+    HIP_TRY(hipMalloc(&c->d_upd64_dv, sizeof(double) * (size_t)cap));
+    c->upd64_cap = cap;
+  }
+  HIP_TRY(hipMemcpyAsync(c->d_upd64_key, key, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_upd64_dv, dv, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
+  const bool sliced = c->cs_w_G == CS64_G;
+  const int Sp = sliced ? cs64_sp(c->dp) : 0;
+  double* w = sliced ? c->d_cs_w64 : c->d_w64;
+  const int n = sliced ? CS64_G * Sp : c->dp;
+  hipLaunchKernelGGL(dsgd_update64_kernel, dim3((unsigned)std::min<long long>((nnz + 255) / 256, (long long)c->n_cu * 4)), dim3(256), 0,
+                     c->stream, c->d_upd64_key, c->d_upd64_dv, (int)nnz, c->d_perm, w, Sp);
+  hipLaunchKernelGGL(dsgd_filter64_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, w, n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->s_dirty = true;
+  return DSGD_OK;
+}
+
+int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,
+                           uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out) {
+  DSGD_TRY(check_ctx(c));
+  if (!assigned_begin || !assigned_end || !out || n_workers < 1 || batch < 1 || first_update < 0 || n_updates < 1)
+    return fail(DSGD_EINVAL, "bad async plan arguments");
+  *out = nullptr;
+  for (int k = 0; k < n_workers; ++k) {
+    const long long len = assigned_end[k] - assigned_begin[k];
+    if (assigned_begin[k] < 0 || len < 1 || len > 0x7fffffffLL) return fail(DSGD_EINVAL, "worker %d has no rows", k);
+  }
+  if (n_updates > 0x7fffffffLL) return fail(DSGD_EINVAL, "at most 2^31 - 1 updates per plan");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_async_plan_create"));
+  DSGD_TRY(bind(c, true));   // (nothing here touches w)
+  for (int k = 0; k < n_workers; ++k)
+    if (assigned_end[k] > c->n_rows)
+      return fail(DSGD_ERANGE, "worker %d's rows [%lld, %lld) outside the %lld loaded", k, (long long)assigned_begin[k],
+                  (long long)assigned_end[k], c->n_rows);
+  std::vector<int64_t> offsets((size_t)n_updates + 1);
+  for (int64_t u = 0; u <= n_updates; ++u) offsets[(size_t)u] = u * batch;
+  dsgd_plan* p = nullptr;
+  DSGD_TRY(plan_frame(c, offsets.data(), n_updates, 1, &p));
+  p->idx_trusted = true;   // (drawn here inside the callers' row ranges)
+  p->fits = false;
+  std::vector<long long> sb2(2 * (size_t)n_workers);
+  for (int k = 0; k < n_workers; ++k) {
+    sb2[(size_t)k] = assigned_begin[k];
+    sb2[(size_t)n_workers + (size_t)k] = assigned_end[k];
+  }
+  long long* d_sb = nullptr;
+  hipError_t e = seed_scratch(c, 7, sizeof(long long) * sb2.size(), (void**)&d_sb);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_sb, sb2.data(), sizeof(long long) * sb2.size(), hipMemcpyHostToDevice, c->build_stream);
+  if (e == hipSuccess) {
+    AsyncListArgs a;
+    a.asg_begin = d_sb;
+    a.asg_end = d_sb + n_workers;
+    a.K = n_workers;
+    a.batch = batch;
+    a.positional_bug = positional_bug ? 1 : 0;
+    a.seed = seed;
+    a.first = first_update;
+    a.idx_out = p->d_idx;
+    hipLaunchKernelGGL(dsgd_async_lists_kernel, dim3((unsigned)n_updates), dim3(256), 0, c->build_stream, a);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->build_stream);   // (sb2 and the scratch: done with before they go)
+  if (e != hipSuccess) {
+    plan_abandon(c, p);
+    return fail(DSGD_EHIP, "drawing the async lists: %s", hipGetErrorString(e));
+  }
+  return plan_finish(c, p, out);
 }
 
 int dsgd_forward(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, float* pred_out) {

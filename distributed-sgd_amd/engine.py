@@ -277,16 +277,42 @@ class Engine:
     # -- asynchronous path -------------------------------------------------------------------------
     def async_step(self, idx, lr, want_delta=False):
         idx = i32(idx)
+        if self.fp64:   # (dsgd_async_step_f64: a float64 delta, the reference's Double learning rate)
+            delta = np.zeros(self.dp, dtype=np.float64) if want_delta else None
+            st = BatchStats()
+            check(self._lib.dsgd_async_step_f64(self._ctx, ptr(idx), C.c_int64(len(idx)), C.c_double(lr), ptr(delta), C.byref(st)))
+            return delta, {"n_samples": st.n_samples, "n_active": st.n_active}
         delta = np.zeros(self.dp, dtype=np.float32) if want_delta else None
         st = BatchStats()
         check(self._lib.dsgd_async_step(self._ctx, ptr(idx), C.c_int64(len(idx)), C.c_float(lr), ptr(delta), C.byref(st)))
         return delta, {"n_samples": st.n_samples, "n_active": st.n_active}
 
     def update_grad(self, keys, values):
-        keys, values = i32(keys), f32(values)
+        keys = i32(keys)
+        values = f64(values) if self.fp64 else f32(values)   # (fp64: the Double values as they are, no float cast)
         if len(keys) != len(values):
             raise ValueError("keys / values length mismatch")
+        if self.fp64:
+            check(self._lib.dsgd_update_grad_f64(self._ctx, ptr(keys), ptr(values), C.c_int64(len(keys))))
+            return
         check(self._lib.dsgd_update_grad(self._ctx, ptr(keys), ptr(values), C.c_int64(len(keys))))
+
+    def async_plan(self, assigned_ranges, batch, seed=0, positional_bug=True, first_update=0, n_updates=1):
+        """fp64 engines: updates [first_update, first_update + n_updates) of the zero-lag asynchronous schedule as a
+        one-worker plan whose lists the device draws (dsgd_async_plan_create): update u is worker u mod K at its
+        iteration u div K, with the rows the lock-free engine's worker draws there (oracle/hogwild_replay.hog_rows)."""
+        k = len(assigned_ranges)
+        rb = (C.c_int64 * max(k, 1))(*[int(r[0]) for r in assigned_ranges])
+        re_ = (C.c_int64 * max(k, 1))(*[int(r[1]) for r in assigned_ranges])
+        h = C.c_void_p()
+        check(self._lib.dsgd_async_plan_create(self._ctx, rb, re_, C.c_int32(k), C.c_int32(batch), C.c_uint64(seed),
+                                               C.c_int32(1 if positional_bug else 0), C.c_int64(first_update),
+                                               C.c_int64(n_updates), C.byref(h)))
+        return Plan(self, h, int(n_updates), 1, int(n_updates) * int(batch))
+
+    def plan_run_async(self, plan, step_begin, step_end, lr):
+        """The asynchronous iterations [step_begin, step_end) of a one-worker plan on the fp64 weights."""
+        check(self._lib.dsgd_plan_run_async_f64(self._ctx, plan.handle, C.c_int64(step_begin), C.c_int64(step_end), C.c_double(lr)))
 
     def async_start(self, assigned_ranges, batch, lr, max_updates, seed=0, positional_bug=True):
         k = len(assigned_ranges)

@@ -688,6 +688,9 @@ class MasterAsync:
             raise ValueError("leaking coefficient must be between 0 and 1")  # MasterAsync.scala:97
         split = [(r.start, r.stop) for r in split_vanilla(self.n_train, self.node_count)]
         steps = self.n_train * max_epoch if max_steps is None else max_steps
+        if getattr(self.backend, "precision", "fp32") == "fp64":
+            return self._fit_fp64(initial_weights, split, steps, batch_size, learning_rate, stopping_criterion, check_every,
+                                  leak_loss_coef, seed, positional_bug)
         self.backend.set_weights(np.asarray(initial_weights, dtype=np.float32))
         self.backend.async_start(split, batch=batch_size, lr=learning_rate, max_updates=steps, seed=seed,
                                  positional_bug=positional_bug)
@@ -720,3 +723,54 @@ class MasterAsync:
         updates, _ = self.backend.async_updates()
         state = GradState(best_w, updates=int(updates)).finish(best_loss)
         return state
+
+    # updates drawn per device plan of the fp64 schedule (one plan holds chunk x batch row indices and its layout)
+    FP64_CHUNK = 4096
+
+    def _check(self, leak_loss_coef):
+        """One loss check (MasterAsync.scala:96-146): the leaky average of the test loss / accuracy."""
+        computed_loss, computed_acc, _ = self.backend.loss_acc(self.n_train, self.n_rows)
+        prev_l = self.test_losses[0] if self.test_losses else computed_loss
+        prev_a = self.test_accs[0] if self.test_accs else computed_acc
+        loss = leak_loss_coef * computed_loss + (1 - leak_loss_coef) * prev_l   # :122-125
+        acc = leak_loss_coef * computed_acc + (1 - leak_loss_coef) * prev_a
+        self.test_losses.insert(0, loss)
+        self.test_accs.insert(0, acc)
+        return loss
+
+    def _fit_fp64(self, initial_weights, split, steps, batch_size, learning_rate, stopping_criterion, check_every,
+                  leak_loss_coef, seed, positional_bug) -> GradState:
+        """An fp64 backend (include/dsgd.h "THE FP64 MODE"): the ZERO-LAG schedule -- one update at a time, update u by
+        worker u mod K at its iteration u div K, every update seen by all workers before the next one -- one
+        deterministic schedule among those the reference allows (its own is racy).  The updates run on device plans
+        drawn FP64_CHUNK at a time, check_every of them between two loss checks; no lock-free engine is started."""
+        w0 = np.asarray(initial_weights, dtype=np.float64)
+        self.backend.set_weights(w0)
+        best_w, best_loss = w0.copy(), float("inf")
+        updates, plan, plan_first = 0, None, 0
+        chunk = max(self.FP64_CHUNK, check_every)
+        try:
+            while True:
+                loss = self._check(leak_loss_coef)
+                if best_loss > loss:                                                         # :132-138
+                    best_loss, best_w = loss, np.asarray(self.backend.get_weights(), dtype=np.float64).copy()
+                if stopping_criterion(self.test_losses):                                    # :146
+                    self.log("converged to target: stopping computation")
+                    break
+                if updates >= steps:
+                    break
+                target = min(steps, updates + check_every)
+                while updates < target:
+                    if plan is None or updates >= plan_first + plan.n_steps:
+                        if plan is not None:
+                            plan.destroy()
+                        plan_first = updates
+                        plan = self.backend.async_plan(split, batch_size, seed=seed, positional_bug=positional_bug,
+                                                       first_update=plan_first, n_updates=min(chunk, steps - plan_first))
+                    end = min(target, plan_first + plan.n_steps)
+                    self.backend.plan_run_async(plan, updates - plan_first, end - plan_first, learning_rate)
+                    updates = end
+        finally:
+            if plan is not None:
+                plan.destroy()
+        return GradState(best_w, updates=int(updates)).finish(best_loss)

@@ -256,7 +256,9 @@ class SlaveWorker:
         if not self.asynchronous:
             raise ValueError("requirement failed: Cannot update gradient: slave is in synchronous mode.")
         keys = np.fromiter(request.gradUpdate.map.keys(), dtype=np.int32, count=len(request.gradUpdate.map))
-        vals = np.fromiter(request.gradUpdate.map.values(), dtype=np.float32, count=len(request.gradUpdate.map))
+        # (an fp64 backend takes the Double values as they came: no float32 rounding on the way)
+        dt = np.float64 if getattr(self.backend, "precision", "fp32") == "fp64" else np.float32
+        vals = np.fromiter(request.gradUpdate.map.values(), dtype=dt, count=len(request.gradUpdate.map))
         self.backend.update_grad(keys, vals)  # weights - gradUpdate
         self.metrics.counter("slave.async.grad.update")
         return messages()["Ack"]()

@@ -77,8 +77,16 @@ enum {
  *   - dsgd_sync_step: a one-step fp64 plan, created, run and given back inside the call.
  *   - dsgd_forward, dsgd_loss_acc: evaluated with the fp64 weights (a float w is promoted and replaces them).
  *   - everything else that would run an fp32 training kernel returns DSGD_EUNSUPPORTED and changes nothing:
- *     dsgd_gradient, dsgd_apply, dsgd_sync_step_ranges(_async), dsgd_async_*, dsgd_update_grad, dsgd_comm_*,
- *     dsgd_*_devices.
+ *     dsgd_gradient, dsgd_apply, dsgd_sync_step_ranges(_async), dsgd_async_* (the float dsgd_async_step and the
+ *     lock-free engine, dsgd_async_start, included), dsgd_update_grad, dsgd_comm_*, dsgd_*_devices.
+ *   The asynchronous iteration (Slave.asyncTask + updateGrad, core/Slave.scala:79-111,177-185; orc_async_step) has its
+ *   own fp64 entry points, declared with the asynchronous path below: dsgd_async_step_f64, dsgd_update_grad_f64,
+ *   dsgd_async_plan_create and dsgd_plan_run_async_f64.  They run on dsgd_cs64_async_kernel (the same plan layout,
+ *   slices and exchange as the synchronous steps; the finish divides the sum by the step's rows BEFORE the
+ *   regulariser), with the limits above at one worker (D <= 100,847).  An asynchronous plan is a ONE-worker plan: its
+ *   step u is update first_update + u of the zero-lag schedule -- worker k = u mod K at its own iteration u div K, every
+ *   update seen by every worker before the next one starts -- with the rows the lock-free engine's worker k draws at
+ *   that iteration.  One deterministic schedule among those the reference allows (its own is racy).
  * The entry points below that name fp64 return DSGD_ESTATE on an fp32 context (dsgd_precision excepted).            */
 
 typedef struct dsgd_ctx dsgd_ctx;
@@ -274,6 +282,24 @@ int dsgd_async_step(dsgd_ctx* ctx, const int32_t* idx, int64_t n, float lr, floa
  * concurrently with asyncTask): the update is applied with atomic adds on a side stream and folded into the engine's
  * regulariser scalar; the call returns when it has been applied and never waits for the engine.                    */
 int dsgd_update_grad(dsgd_ctx* ctx, const int32_t* key, const float* dv, int64_t nnz);
+/* The same in an fp64 context ("THE FP64 MODE"; DSGD_ESTATE on an fp32 context), with the reference's Double values.
+ * dsgd_async_step_f64: one iteration on the resident fp64 weights (a one-step, one-worker plan, run and given back inside
+ * the call); delta_out (D+1 doubles, key order, may be NULL) receives lr * regularize(mean) -- zero off the support.
+ * dsgd_update_grad_f64: w[k] = filt(w[k] - dv) for each key, then the whole vector filtered; synchronous (the update is
+ * applied when it returns).  The keys are checked on the host first: a key outside [0, D] gives DSGD_ERANGE, a repeated
+ * key DSGD_EINVAL (a Sparse delta has unique keys); w is unchanged then.
+ * dsgd_async_plan_create: a one-worker plan of n_updates steps whose lists the DEVICE draws -- step u holds the rows of
+ * update first_update + u of the zero-lag schedule (see "THE FP64 MODE"), the lock-free engine's sampler for the workers'
+ * row ranges [assigned_begin[k], assigned_end[k]), `batch`, `seed` and `positional_bug` (as dsgd_async_start).
+ * dsgd_plan_run_async_f64: the asynchronous iterations [step_begin, step_end) of a one-worker plan (DSGD_EINVAL for a
+ * plan of more workers); dsgd_plan_record / dsgd_plan_read_record serve these runs as they serve synchronous ones.      */
+int dsgd_async_step_f64(dsgd_ctx* ctx, const int32_t* idx, int64_t n, double lr, double* delta_out /* D+1, may be NULL */,
+                        dsgd_batch_stats* stats);
+int dsgd_update_grad_f64(dsgd_ctx* ctx, const int32_t* key, const double* dv, int64_t nnz);
+int dsgd_async_plan_create(dsgd_ctx* ctx, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers,
+                           int32_t batch, uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates,
+                           dsgd_plan** out);
+int dsgd_plan_run_async_f64(dsgd_ctx* ctx, dsgd_plan* plan, int64_t step_begin, int64_t step_end, double lr);
 
 /* SlaveImpl.startAsync (core/Slave.scala:159-175) for n_workers lock-free workers sharing ONE
  * device-resident weight vector: every worker (a workgroup) loops

@@ -346,6 +346,42 @@ JNIEXPORT void JNICALL NATIVE(updateGrad)(JNIEnv* env, jobject, jlong h, jintArr
   if (rc) raise(env, rc);
 }
 
+// the same two in the fp64 mode (include/dsgd.h "THE FP64 MODE"): Double learning rate, delta and values.  Null arrays
+// are refused before any array is taken; deltaOut holds D+1 doubles (key order), as the float form's D+1 floats.
+JNIEXPORT void JNICALL NATIVE(asyncStepF64)(JNIEnv* env, jobject, jlong h, jintArray idx, jdouble lr, jdoubleArray deltaOut) {
+  if (!idx || !deltaOut) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "null array");
+    return;
+  }
+  const jsize n = env->GetArrayLength(idx);
+  int rc;
+  {
+    IntElems iv(env, idx, JNI_ABORT);
+    DoubleElems dv(env, deltaOut, 0);
+    rc = dsgd_async_step_f64(ctx(h), reinterpret_cast<const int32_t*>(iv.p), n, lr, dv.p, nullptr);
+  }
+  if (rc) raise(env, rc);
+}
+
+JNIEXPORT void JNICALL NATIVE(updateGradF64)(JNIEnv* env, jobject, jlong h, jintArray keys, jdoubleArray values) {
+  if (!keys || !values) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "null array");
+    return;
+  }
+  const jsize n = env->GetArrayLength(keys);
+  if (env->GetArrayLength(values) != n) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "keys / values length mismatch");
+    return;
+  }
+  int rc;
+  {
+    IntElems kv(env, keys, JNI_ABORT);
+    DoubleElems vv(env, values, JNI_ABORT);
+    rc = dsgd_update_grad_f64(ctx(h), reinterpret_cast<const int32_t*>(kv.p), vv.p, n);
+  }
+  if (rc) raise(env, rc);
+}
+
 // SlaveImpl.startAsync (core/Slave.scala:159-175): the persistent lock-free engine on ONE device-resident w
 JNIEXPORT void JNICALL NATIVE(asyncStart)(JNIEnv* env, jobject, jlong h, jlongArray assignedBegin, jlongArray assignedEnd,
                                           jint batch, jfloat lr, jlong maxUpdates, jlong seed, jboolean positionalBug) {

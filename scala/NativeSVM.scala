@@ -43,6 +43,9 @@ object NativeSVM {
   @native def lossAcc(ctx: Long, w: Array[Float], rowBegin: Long, rowEnd: Long, out: Array[Double]): Unit
   @native def asyncStep(ctx: Long, idx: Array[Int], lr: Float, deltaOut: Array[Float]): Unit
   @native def updateGrad(ctx: Long, keys: Array[Int], values: Array[Float]): Unit
+  // the same in the fp64 mode: Double learning rate, delta (D+1) and values
+  @native def asyncStepF64(ctx: Long, idx: Array[Int], lr: Double, deltaOut: Array[Double]): Unit
+  @native def updateGradF64(ctx: Long, keys: Array[Int], values: Array[Double]): Unit
   @native def asyncStart(ctx: Long, assignedBegin: Array[Long], assignedEnd: Array[Long], batch: Int, lr: Float,
                          maxUpdates: Long, seed: Long, positionalBug: Boolean): Unit
   @native def asyncUpdates(ctx: Long): Long

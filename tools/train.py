@@ -6,7 +6,8 @@ accuracy -- with the HIP engine hosting all the workers.
     DSGD_DATA_PATH=/data/rcv1 python tools/train.py [--conf application.conf] [--synthetic ROWS] [--device 0] [--weights-out w.txt]
                                                     [--precision fp64]
 
---precision fp64: the engine keeps the reference's Double weights (include/dsgd.h "THE FP64 MODE"); synchronous fits only.
+--precision fp64: the engine keeps the reference's Double weights (include/dsgd.h "THE FP64 MODE"); an async fit runs the
+zero-lag schedule of host.MasterAsync (one update at a time, every update seen by every worker).
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,7 +20,7 @@ ap.add_argument("--conf", help="application.conf to read the dsgd{...} block fro
 ap.add_argument("--synthetic", type=int, default=0, help="use N synthetic RCV1-like rows instead of data-path")
 ap.add_argument("--device", type=int, default=0)
 ap.add_argument("--weights-out", help="write the `idx:value` line of Main.scala:114 here instead of logging it")
-ap.add_argument("--precision", choices=("fp32", "fp64"), default="fp32", help="fp64: the reference's Double arithmetic (sync only)")
+ap.add_argument("--precision", choices=("fp32", "fp64"), default="fp32", help="fp64: the reference's Double arithmetic")
 a = ap.parse_args()
 
 
@@ -35,8 +36,6 @@ data = dsgd_amd.synth.generate(a.synthetic, seed=0) if a.synthetic else rcv1.loa
 log("data loaded: {} ({}s)", data.n_rows, round(time.time() - t0, 2))
 n_train = int(data.n_rows * 0.8)                                              # Main.scala:52
 metrics = host.Metrics()
-if a.precision == "fp64" and cfg.async_:
-    sys.exit("--precision fp64 runs the synchronous master only (the lock-free engine is fp32)")
 with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device, precision=a.precision) as eng:
     eng.load_csr(data.row_ptr, data.col, data.val, data.label)
     t0 = time.time()
@@ -64,6 +63,8 @@ with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device, precision=a.precisi
     else:
         log("final weights: {}", line)
     if a.precision == "fp64":   # (the fp64 weights are the engine's own: no float copy replaces them)
+        if cfg.async_:          # (the best weights of the async fit, as they are)
+            eng.set_weights(w1)
         l1, a1, _ = eng.loss_acc(n_train, data.n_rows)
     else:
         l1, a1, _ = eng.loss_acc(n_train, data.n_rows, w=w1)                   # localLoss / localAccuracy on testData
