@@ -127,6 +127,7 @@ static bool available() {
 #include "dsgd_tcol.hpp"
 #include "dsgd_shuffle.hpp"
 #include "dsgd_cs64.hpp"   // (last: the fp64 mode)
+#include "dsgd_rp64.hpp"   // (... and its row-parallel gradient family)
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -504,6 +505,13 @@ struct dsgd_ctx {
   int* d_upd64_key = nullptr;             // dsgd_update_grad_f64: the keys and values of a peer's update (grow-only)
   double* d_upd64_dv = nullptr;
   long long upd64_cap = 0;
+  // the row-parallel fp64 family (csrc/dsgd_rp64.hpp): [rp64_k][rp64_stride] fixed-point column sums, zero between calls
+  // (grow-only), s of the call, the gradient in key order
+  unsigned long long* d_rp64_acc = nullptr;
+  long long rp64_stride = 0;
+  int rp64_k = 0;
+  double* d_rp64_s = nullptr;
+  double* d_rp64_g = nullptr;
 };
 
 static int check_ctx(dsgd_ctx* c) {
@@ -3155,6 +3163,9 @@ int dsgd_destroy(dsgd_ctx* c) {
   (void)hipFree(c->d_cs_dl64);
   (void)hipFree(c->d_upd64_key);
   (void)hipFree(c->d_upd64_dv);
+  (void)hipFree(c->d_rp64_acc);
+  (void)hipFree(c->d_rp64_s);
+  (void)hipFree(c->d_rp64_g);
   (void)hipFree(c->d_g);
   (void)hipFree(c->d_g64);
   (void)hipFree(c->d_gsum);
@@ -4612,6 +4623,142 @@ int dsgd_update_grad_f64(dsgd_ctx* c, const int32_t* key, const double* dv, int6
   return DSGD_OK;
 }
 
+// ---- the fp64 row-parallel family (include/dsgd.h "THE FP64 MODE"; csrc/dsgd_rp64.hpp): SlaveImpl.gradient in Double and
+//      synchronous steps of any number of workers and rows ----
+// the lists are host data: checked here, before anything moves (an index outside the data changes nothing)
+static int rp64_check_lists(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int n_workers) {
+  for (int k = 0; k < n_workers; ++k) {
+    if (n_per_worker[k] <= 0 || !idx_per_worker[k])
+      return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors (worker %d)", k);   // ref: math/Vec.scala:129
+    for (int64_t t = 0; t < n_per_worker[k]; ++t)
+      if (idx_per_worker[k][t] < 0 || idx_per_worker[k][t] >= c->n_rows)
+        return fail(DSGD_ERANGE, "sample index %d of worker %d outside the %lld loaded rows", idx_per_worker[k][t], k, c->n_rows);
+  }
+  return DSGD_OK;
+}
+static int rp64_ensure(dsgd_ctx* c, int n_workers) {
+  if (!c->d_rp64_s) {
+    HIP_TRY(hipMalloc(&c->d_rp64_s, sizeof(double)));
+    HIP_TRY(hipMalloc(&c->d_rp64_g, sizeof(double) * c->dp));
+  }
+  if (c->rp64_k < n_workers) {   // (zeroed once; every finish leaves them zeroed)
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    (void)hipFree(c->d_rp64_acc);
+    c->d_rp64_acc = nullptr;
+    c->rp64_k = 0;
+    const long long stride = ((long long)c->dp + 63) & ~63LL;
+    const int cap = std::max(n_workers, 4);
+    HIP_TRY(hipMalloc(&c->d_rp64_acc, sizeof(unsigned long long) * (size_t)stride * (size_t)cap));
+    HIP_TRY(hipMemsetAsync(c->d_rp64_acc, 0, sizeof(unsigned long long) * (size_t)stride * (size_t)cap, c->stream));
+    c->rp64_stride = stride;
+    c->rp64_k = cap;
+  }
+  return DSGD_OK;
+}
+// the two launches over the staged lists (c->cur_idx, c->d_segs); step = false: the gradient of worker 0 into d_rp64_g
+static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, bool step, double lr) {
+  const bool sliced = c->cs_w_G == CS64_G;   // (the weights stay in whichever layout they are: slice-major between plan runs)
+  const int Sp = sliced ? cs64_sp(c->dp) : 0;
+  double* w = sliced ? c->d_cs_w64 : c->d_w64;
+  constexpr long long rows_per_block = RP64_THREADS / RP64_GROUP;
+  const long long bpw = std::max<long long>(1, std::min<long long>((max_items + rows_per_block - 1) / rows_per_block,
+                                                                   std::max<long long>(1, (long long)c->n_cu * 2 / n_workers)));   // (each workgroup flushes its hot words once)
+  Rp64Args a;
+  a.m = view(c);
+  a.w = w;
+  a.ds = c->d_ds64;
+  a.Sp = Sp;
+  a.dp = c->dp;
+  a.vexp = c->vexp;
+  a.K = n_workers;
+  a.idx = c->cur_idx;
+  a.segs = c->d_segs;
+  a.blocks_per_worker = bpw;
+  a.acc = c->d_rp64_acc;
+  a.acc_stride = c->rp64_stride;
+  a.lambda = c->cfg.lambda;
+  a.s_out = c->d_rp64_s;
+  a.sc = c->d_sc;
+  hipLaunchKernelGGL(dsgd_rp64_grad_kernel, dim3((unsigned)(bpw * n_workers + 1)), dim3(RP64_THREADS), 0, c->stream, a);
+  HIP_TRY(hipGetLastError());
+  Rp64FinishArgs f;
+  f.acc = c->d_rp64_acc;
+  f.acc_stride = c->rp64_stride;
+  f.segs = c->d_segs;
+  f.K = n_workers;
+  f.dp = c->dp;
+  f.vexp = c->vexp;
+  f.Sp = Sp;
+  f.s = c->d_rp64_s;
+  f.perm = c->d_perm;
+  f.g_out = c->d_rp64_g;
+  f.w = w;
+  f.lr = lr;
+  const dim3 fg((unsigned)std::min<long long>(((long long)c->dp + RP64_THREADS - 1) / RP64_THREADS, (long long)c->n_cu * 4));
+  if (step)
+    hipLaunchKernelGGL(dsgd_rp64_finish_kernel<true>, fg, dim3(RP64_THREADS), 0, c->stream, f);
+  else
+    hipLaunchKernelGGL(dsgd_rp64_finish_kernel<false>, fg, dim3(RP64_THREADS), 0, c->stream, f);
+  HIP_TRY(hipGetLastError());
+  return DSGD_OK;
+}
+
+int dsgd_gradient_f64(dsgd_ctx* c, const double* w, const int32_t* idx, int64_t n, double* g_out, dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  if (!g_out) return fail(DSGD_EINVAL, "null g_out");
+  if (n <= 0 || !idx) return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors");  // ref: math/Vec.scala:129
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_gradient_f64"));
+  DSGD_TRY(bind(c, w == nullptr));   // (the request's weights replace the resident ones: rank order then)
+  DSGD_TRY(require_data(c));
+  DSGD_TRY(require_ds(c));
+  DSGD_TRY(require_sync_mode(c));   // the accumulators and (with w != NULL) the weights belong to the running engine
+  DSGD_TRY(prepare_layout(c));
+  const int64_t nn = n;
+  DSGD_TRY(rp64_check_lists(c, &idx, &nn, 1));
+  if (w) {
+    DSGD_TRY(put64(c, w, c->d_w64));
+    c->s_dirty = true;
+  }
+  DSGD_TRY(rp64_ensure(c, 1));
+  DSGD_TRY(reset_counters(c));
+  long long mx = 0, tot = 0;
+  DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
+  DSGD_TRY(rp64_launch(c, 1, mx, false, 0.0));
+  const size_t bytes = sizeof(double) * (size_t)c->dp;
+  DSGD_TRY(pin_acquire(c->pin_out, bytes));
+  HIP_TRY(hipMemcpyAsync(c->pin_out.p, c->d_rp64_g, bytes, hipMemcpyDeviceToHost, c->stream));
+  DSGD_TRY(read_scalars(c));   // the one synchronisation of the call
+  memcpy(g_out, c->pin_out.p, bytes);
+  DSGD_TRY(check_err_flag(c));
+  if (stats) {
+    stats->n_samples = n;
+    stats->n_active = (int64_t)c->h_sc->n_active;
+  }
+  return DSGD_OK;
+}
+
+int dsgd_sync_step_f64(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers, double lr,
+                       dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  if (n_workers < 1 || !idx_per_worker || !n_per_worker) return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors (no workers)");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_sync_step_f64"));
+  DSGD_TRY(bind(c, true));
+  DSGD_TRY(require_data(c));
+  DSGD_TRY(require_ds(c));
+  DSGD_TRY(require_sync_mode(c));
+  DSGD_TRY(prepare_layout(c));
+  DSGD_TRY(rp64_check_lists(c, idx_per_worker, n_per_worker, n_workers));
+  DSGD_TRY(rp64_ensure(c, n_workers));
+  DSGD_TRY(reset_counters(c));
+  long long mx = 0, tot = 0;
+  DSGD_TRY(stage_lists(c, idx_per_worker, n_per_worker, n_workers, &mx, &tot));
+  DSGD_TRY(rp64_launch(c, n_workers, mx, true, lr));
+  c->s_dirty = true;
+  return finish_stats(c, stats, tot);
+}
+
 int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,
                            uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out) {
   DSGD_TRY(check_ctx(c));
@@ -4665,6 +4812,7 @@ int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int
   return plan_finish(c, p, out);
 }
 
+static int forward_run(dsgd_ctx* c, const int32_t* idx, int64_t n, float* pred_out);
 int dsgd_forward(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, float* pred_out) {
   DSGD_TRY(check_ctx(c));
   if (n < 0 || (n > 0 && (!idx || !pred_out))) return fail(DSGD_EINVAL, "bad forward arguments");
@@ -4675,6 +4823,33 @@ int dsgd_forward(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, flo
   DSGD_TRY(prepare_layout(c));
   if (w) DSGD_TRY(set_weights_locked(c, w));
   if (n == 0) return DSGD_OK;  // samplesIdx.map over an empty Seq is an empty reply (ref: core/Slave.scala:133)
+  return forward_run(c, idx, n, pred_out);
+}
+
+int dsgd_forward_f64(dsgd_ctx* c, const double* w, const int32_t* idx, int64_t n, double* pred_out) {
+  DSGD_TRY(check_ctx(c));
+  if (n < 0 || (n > 0 && (!idx || !pred_out))) return fail(DSGD_EINVAL, "bad forward arguments");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_forward_f64"));
+  DSGD_TRY(bind(c));
+  DSGD_TRY(require_data(c));
+  if (w) DSGD_TRY(require_sync_mode(c));   // replacing the weights under the lock-free engine is refused
+  DSGD_TRY(prepare_layout(c));
+  for (int64_t t = 0; t < n; ++t)   // (host data: checked before the weights are replaced)
+    if (idx[t] < 0 || idx[t] >= c->n_rows) return fail(DSGD_ERANGE, "sample index %d outside the %lld loaded rows", idx[t], c->n_rows);
+  if (w) {
+    DSGD_TRY(put64(c, w, c->d_w64));   // (the Double weights as they are: no float rounding)
+    c->s_dirty = true;
+  }
+  if (n == 0) return DSGD_OK;
+  std::vector<float> pred((size_t)n);
+  DSGD_TRY(forward_run(c, idx, n, pred.data()));
+  for (int64_t t = 0; t < n; ++t) pred_out[t] = (double)pred[(size_t)t];   // (-1, 0 or +1: exact)
+  return DSGD_OK;
+}
+
+// the predictions of n >= 1 rows from the resident weights (bound: rank order)
+static int forward_run(dsgd_ctx* c, const int32_t* idx, int64_t n, float* pred_out) {
   DSGD_TRY(ensure_idx(c, n));
   DSGD_TRY(reset_counters(c));
   if (n > c->pred_cap) {

@@ -164,6 +164,34 @@ class Engine:
         check(self._lib.dsgd_gradient(self._ctx, ptr(wv), ptr(idx), C.c_int64(len(idx)), ptr(g), C.byref(st)))
         return g, {"n_samples": st.n_samples, "n_active": st.n_active}
 
+    def gradient_f64(self, idx, w=None):
+        """SlaveImpl.gradient in Double (dsgd_gradient_f64; fp64 engines): a float64 g of any list length, from the resident
+        fp64 weights or from w (float64, which then replaces them)."""
+        idx = i32(idx)
+        g = np.zeros(self.dp, dtype=np.float64)
+        st = BatchStats()
+        wv = None if w is None else f64(w, self.dp)
+        check(self._lib.dsgd_gradient_f64(self._ctx, ptr(wv), ptr(idx), C.c_int64(len(idx)), ptr(g), C.byref(st)))
+        return g, {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def sync_step_f64(self, idx_per_worker, lr):
+        """Master.fit's batch closure in Double (dsgd_sync_step_f64; fp64 engines): any number of workers and rows."""
+        lists = [i32(a) for a in idx_per_worker]
+        k = len(lists)
+        ptrs = (C.c_void_p * max(k, 1))(*[ptr(a) for a in lists])
+        ns = (C.c_int64 * max(k, 1))(*[len(a) for a in lists])
+        st = BatchStats()
+        check(self._lib.dsgd_sync_step_f64(self._ctx, ptrs, ns, C.c_int32(k), C.c_double(lr), C.byref(st)))
+        return {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def forward_f64(self, idx, w=None):
+        """SlaveImpl.forward with Double weights (dsgd_forward_f64; fp64 engines): float64 predictions in {-1, 0, +1}."""
+        idx = i32(idx)
+        pred = np.zeros(len(idx), dtype=np.float64)
+        wv = None if w is None else f64(w, self.dp)
+        check(self._lib.dsgd_forward_f64(self._ctx, ptr(wv), ptr(idx), C.c_int64(len(idx)), ptr(pred)))
+        return pred
+
     def apply(self, g_mean, lr):
         check(self._lib.dsgd_apply(self._ctx, ptr(f32(g_mean, self.dp)), C.c_float(lr)))
 

@@ -531,9 +531,31 @@ class MasterSync:
         self._lists_future = self._executor.submit(self._draw_lists, split, max_samples, batch_size)
 
     def _make_plan(self, lists, n_workers):
-        plan = self.backend.plan_flat(lists["idx"], lists["offsets"], lists["n_steps"], n_workers) if lists["n_steps"] else None
-        return {"plan": plan, "n_steps": lists["n_steps"], "n_samples": int(lists["offsets"][lists["n_steps"] * n_workers]),
-                "seed_before": lists["seed_before"]}
+        entry = {"plan": None, "n_steps": lists["n_steps"], "n_samples": int(lists["offsets"][lists["n_steps"] * n_workers]),
+                 "seed_before": lists["seed_before"]}
+        if lists["n_steps"]:
+            try:
+                entry["plan"] = self.backend.plan_flat(lists["idx"], lists["offsets"], lists["n_steps"], n_workers)
+            except Exception as e:
+                # an fp64 backend refuses plans beyond its column-slice limits (DSGD_EUNSUPPORTED: more than 4 workers or
+                # 1,024 rows per step): the epoch's steps run one by one through sync_step_f64, on the same lists
+                if getattr(e, "code", None) != -7 or not self._fp64_steps():
+                    raise
+                entry["lists"] = lists
+        return entry
+
+    def _fp64_steps(self):
+        return getattr(self.backend, "precision", "fp32") == "fp64" and hasattr(self.backend, "sync_step_f64")
+
+    def _run_steps_f64(self, lists, n_workers, learning_rate):
+        """The epoch's steps, one sync_step_f64 call each, in order; returns the rows whose gradient was computed."""
+        idx, offs = lists["idx"], lists["offsets"]
+        n_samples = 0
+        for s_ in range(lists["n_steps"]):
+            o = offs[s_ * n_workers:(s_ + 1) * n_workers + 1]
+            st = self.backend.sync_step_f64([idx[o[j]:o[j + 1]] for j in range(n_workers)], learning_rate)
+            n_samples += int(st.get("n_samples", 0)) if st else 0
+        return n_samples
 
     def _next_plan(self, split, max_samples, batch_size, n_workers, ahead_ok=False):
         """The next epoch as a plan: its lists drawn by the device where that applies, else by the host (csrc/jrand.c)."""
@@ -583,7 +605,9 @@ class MasterSync:
             cur = self._next_plan(split, max_samples, batch_size, K)
         t0 = time.perf_counter_ns()
         try:
-            if cur["n_steps"]:
+            if cur.get("lists") is not None:   # (an fp64 backend's refused plan: the steps one by one, synchronous)
+                self._run_steps_f64(cur["lists"], K, learning_rate)
+            elif cur["n_steps"]:
                 self.backend.plan_run(cur["plan"], 0, cur["n_steps"], learning_rate)   # enqueued: ALL the epoch's steps, one launch
             if self.prefetch and epochs_left > 1 and cur["n_steps"] == n_expected:
                 # ... and while they run: the next epoch's lists (drawn ahead already, from the second epoch on), the draw of the

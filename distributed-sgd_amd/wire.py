@@ -118,9 +118,10 @@ def to_sparse(dense, size: int):
     return out
 
 
-def from_sparse(sparse, dp: int) -> np.ndarray:
-    """Sparse -> dense float32[dp] indexed by key; a key outside [0, dp) is what Vec.apply would reject later."""
-    w = np.zeros(dp, dtype=np.float32)
+def from_sparse(sparse, dp: int, dtype=np.float32) -> np.ndarray:
+    """Sparse -> dense [dp] indexed by key (float32, or the Double values as they are with dtype=np.float64); a key
+    outside [0, dp) is what Vec.apply would reject later."""
+    w = np.zeros(dp, dtype=dtype)
     for k, v in sparse.map.items():
         if k < 0 or k >= dp:
             raise IndexError("key %d outside [0, %d)" % (k, dp))
@@ -223,20 +224,27 @@ class SlaveWorker:
             self.others.pop((node.host, node.port), None)
         return messages()["Ack"]()
 
+    @property
+    def _fp64(self):
+        """an fp64 backend: the master's Double weights go in and the Double gradient comes out as they are"""
+        return getattr(self.backend, "precision", "fp32") == "fp64"
+
     def _rpc_Forward(self, request):  # :129-140
-        w = from_sparse(request.weights, self.dp)
+        fp64 = self._fp64
+        w = from_sparse(request.weights, self.dp, np.float64 if fp64 else np.float32)
         idx = np.asarray(request.samples, dtype=np.int32)
         self.metrics.counter("slave.sync.forward", len(idx))
-        pred = self.backend.forward(idx, w)
+        pred = self.backend.forward_f64(idx, w) if fp64 else self.backend.forward(idx, w)
         return messages()["ForwardReply"](predictions=[float(p) for p in pred])
 
     def _rpc_Gradient(self, request):  # :142-157
-        w = from_sparse(request.weights, self.dp)
+        fp64 = self._fp64
+        w = from_sparse(request.weights, self.dp, np.float64 if fp64 else np.float32)
         idx = np.asarray(request.samples, dtype=np.int32)
         if len(idx) == 0:
             raise ValueError("requirement failed: Vec.sum of an empty batch (math/Vec.scala:129)")
         self.metrics.counter("slave.sync.backward", len(idx))
-        g, _ = self.backend.gradient(idx, w)
+        g, _ = self.backend.gradient_f64(idx, w) if fp64 else self.backend.gradient(idx, w)
         return messages()["GradUpdate"](gradUpdate=to_sparse(g, self.size))
 
     def _rpc_StartAsync(self, request):  # :159-175

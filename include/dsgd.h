@@ -87,6 +87,17 @@ enum {
  *   step u is update first_update + u of the zero-lag schedule -- worker k = u mod K at its own iteration u div K, every
  *   update seen by every worker before the next one starts -- with the rows the lock-free engine's worker k draws at
  *   that iteration.  One deterministic schedule among those the reference allows (its own is racy).
+ *   The request / response gradient and synchronous steps of ANY size have their own fp64 entry points, declared with
+ *   the synchronous path below: dsgd_gradient_f64 (SlaveImpl.gradient in Double), dsgd_sync_step_f64 (any number of
+ *   workers, any rows per worker, a whole split included) and dsgd_forward_f64.  They run on the row-parallel fp64
+ *   family (csrc/dsgd_rp64.hpp): one 16-lane group per listed row, fp64 dots, y * x of the active rows added into
+ *   64-bit fixed-point column sums with integer atomics at shift = 62 - ceil(log2 n) (n: the worker's list length,
+ *   duplicates counted) relative to the data's largest |x| <= 2^vexp, so no column sum overflows and the result does not
+ *   depend on the order of the list or of the adds (bit-reproducible).  EXACT RANGE: an entry of exponent e is exact on
+ *   the grid when e >= vexp - (39 - ceil(log2 n)): 32 binades at n = 100, 29 at 1,024, 23 at 65,536, 21 at 214,511
+ *   rows.  Inside it the results differ from the oracle's only by the rounding order of x . w and w . ds and by the
+ *   oracle's per-add rounding and mid-sum 1e-20 filter, which the exact sum does not have.  The limits and refusals
+ *   above are unchanged: dsgd_gradient, dsgd_sync_step_ranges and plans beyond them still return DSGD_EUNSUPPORTED.
  * The entry points below that name fp64 return DSGD_ESTATE on an fp32 context (dsgd_precision excepted).            */
 
 typedef struct dsgd_ctx dsgd_ctx;
@@ -159,6 +170,20 @@ int dsgd_precision(dsgd_ctx* ctx, int32_t* bits_out);
  * n == 0 fails with DSGD_EINVAL (Vec.sum requires a non-empty list, math/Vec.scala:129).      */
 int dsgd_gradient(dsgd_ctx* ctx, const float* w, const int32_t* idx, int64_t n, float* g_out /* D+1 */,
                   dsgd_batch_stats* stats /* may be NULL */);
+
+/* The same three in an fp64 context ("THE FP64 MODE"; DSGD_ESTATE on an fp32 context), any list length n >= 1, with
+ * the reference's Double values.  Errors as dsgd_gradient: n <= 0 or no workers DSGD_EINVAL ("Cannot sum an empty list
+ * of vectors", math/Vec.scala:129); an index outside the loaded rows DSGD_ERANGE with nothing changed; refused while
+ * the lock-free engine runs.  Between plan runs the weights stay in the plans' slice-major layout.
+ * dsgd_gradient_f64: SlaveImpl.gradient in Double (core/Slave.scala:142-157), g = regularize(sum_i backward(w, x_i, y_i)).
+ *   w == NULL uses the resident fp64 weights; otherwise w replaces them (as the GradientRequest's weights do).
+ * dsgd_sync_step_f64: Master.fit's batch closure in Double (core/Master.scala:184-197), ANY number of workers and rows.
+ * dsgd_forward_f64: SlaveImpl.forward with Double weights (w may be NULL): pred = -signum(x . w) in {-1, 0, +1}.      */
+int dsgd_gradient_f64(dsgd_ctx* ctx, const double* w, const int32_t* idx, int64_t n, double* g_out /* D+1 */,
+                      dsgd_batch_stats* stats /* may be NULL */);
+int dsgd_sync_step_f64(dsgd_ctx* ctx, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers,
+                       double lr, dsgd_batch_stats* stats /* may be NULL */);
+int dsgd_forward_f64(dsgd_ctx* ctx, const double* w, const int32_t* idx, int64_t n, double* pred_out /* n */);
 
 /* Master.fit batch closure, update half (core/Master.scala:194-197): w <- w - lr * g_mean      */
 int dsgd_apply(dsgd_ctx* ctx, const float* g_mean /* D+1 */, float lr);

@@ -382,6 +382,47 @@ JNIEXPORT void JNICALL NATIVE(updateGradF64)(JNIEnv* env, jobject, jlong h, jint
   if (rc) raise(env, rc);
 }
 
+// SlaveImpl.gradient / forward in the fp64 mode (dsgd_gradient_f64 / dsgd_forward_f64): the request's Double weights
+// (w may be null = the resident fp64 weights), any number of samples.  Null idx / output arrays are refused before any
+// array is taken; gOut holds D+1 doubles (key order), predOut one double per sample.
+JNIEXPORT jlong JNICALL NATIVE(gradientF64)(JNIEnv* env, jobject, jlong h, jdoubleArray w, jintArray idx, jdoubleArray gOut) {
+  if (!idx || !gOut) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "null array");
+    return 0;
+  }
+  dsgd_batch_stats st{};
+  const jsize n = env->GetArrayLength(idx);
+  int rc;
+  {
+    DoubleElems wv(env, w, JNI_ABORT);
+    IntElems iv(env, idx, JNI_ABORT);
+    DoubleElems gv(env, gOut, 0);
+    rc = dsgd_gradient_f64(ctx(h), wv.p, reinterpret_cast<const int32_t*>(iv.p), n, gv.p, &st);
+  }
+  if (rc) raise(env, rc);
+  return st.n_active;
+}
+
+JNIEXPORT void JNICALL NATIVE(forwardF64)(JNIEnv* env, jobject, jlong h, jdoubleArray w, jintArray idx, jdoubleArray predOut) {
+  if (!idx || !predOut) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "null array");
+    return;
+  }
+  const jsize n = env->GetArrayLength(idx);
+  if (env->GetArrayLength(predOut) != n) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "idx / predOut length mismatch");
+    return;
+  }
+  int rc;
+  {
+    DoubleElems wv(env, w, JNI_ABORT);
+    IntElems iv(env, idx, JNI_ABORT);
+    DoubleElems pv(env, predOut, 0);
+    rc = dsgd_forward_f64(ctx(h), wv.p, reinterpret_cast<const int32_t*>(iv.p), n, pv.p);
+  }
+  if (rc) raise(env, rc);
+}
+
 // SlaveImpl.startAsync (core/Slave.scala:159-175): the persistent lock-free engine on ONE device-resident w
 JNIEXPORT void JNICALL NATIVE(asyncStart)(JNIEnv* env, jobject, jlong h, jlongArray assignedBegin, jlongArray assignedEnd,
                                           jint batch, jfloat lr, jlong maxUpdates, jlong seed, jboolean positionalBug) {

@@ -46,6 +46,9 @@ object NativeSVM {
   // the same in the fp64 mode: Double learning rate, delta (D+1) and values
   @native def asyncStepF64(ctx: Long, idx: Array[Int], lr: Double, deltaOut: Array[Double]): Unit
   @native def updateGradF64(ctx: Long, keys: Array[Int], values: Array[Double]): Unit
+  // SlaveImpl.gradient / forward in Double: w may be null (the resident weights); gradientF64 returns the active rows
+  @native def gradientF64(ctx: Long, w: Array[Double], idx: Array[Int], gOut: Array[Double]): Long
+  @native def forwardF64(ctx: Long, w: Array[Double], idx: Array[Int], predOut: Array[Double]): Unit
   @native def asyncStart(ctx: Long, assignedBegin: Array[Long], assignedEnd: Array[Long], batch: Int, lr: Float,
                          maxUpdates: Long, seed: Long, positionalBug: Boolean): Unit
   @native def asyncUpdates(ctx: Long): Long
