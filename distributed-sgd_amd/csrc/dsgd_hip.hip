@@ -512,6 +512,13 @@ struct dsgd_ctx {
   int rp64_k = 0;
   double* d_rp64_s = nullptr;
   double* d_rp64_g = nullptr;
+  // ... across ranks (dsgd_comm_init_f64): the gather buffer ([world, padded][rp64_gk][rp64_gstride], zero between calls), the
+  // list ranges its header kernel writes for the finish, and the pinned words the ranks' worker counts are read into
+  unsigned long long* d_rp64_gath = nullptr;
+  long long rp64_gstride = 0;
+  int rp64_gk = 0;
+  WorkSeg* d_rp64_gsegs = nullptr;
+  unsigned long long* h_rp64_ranks = nullptr;
 };
 
 static int check_ctx(dsgd_ctx* c) {
@@ -1600,6 +1607,18 @@ static int launch_cs(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long 
   return DSGD_OK;
 }
 
+// the fp64 weights (and a copy of dimSparsity) slice-major
+static int cs64_slice(dsgd_ctx* c) {
+  if (c->cs_w_G == CS64_G) return DSGD_OK;
+  const int Sp = cs64_sp(c->dp), n = CS64_G * Sp;
+  if (!c->d_cs_w64) HIP_TRY(hipMalloc(&c->d_cs_w64, sizeof(double) * (size_t)n));
+  if (!c->d_cs_ds64) HIP_TRY(hipMalloc(&c->d_cs_ds64, sizeof(double) * (size_t)n));
+  hipLaunchKernelGGL(dsgd_cs64_slice_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_w64, c->d_cs_w64, c->dp, Sp);
+  hipLaunchKernelGGL(dsgd_cs64_slice_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_ds64, c->d_cs_ds64, c->dp, Sp);
+  HIP_TRY(hipGetLastError());
+  c->cs_w_G = CS64_G;
+  return DSGD_OK;
+}
 // the steps [step_begin, step_end) of a plan in an fp64 context (csrc/dsgd_cs64.hpp): ONE launch.  async: the asynchronous
 // iterations of a one-worker plan (dsgd_cs64_async_kernel), `delta` ([CS64_G][Sp]) receiving their updates or null
 static int launch_cs64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr, bool async = false,
@@ -1613,14 +1632,7 @@ static int launch_cs64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long lon
     HIP_TRY(hipMalloc(&c->d_cs_sync, sizeof(unsigned int) * 2));
     HIP_TRY(hipMemsetAsync(c->d_cs_sync, 0, sizeof(unsigned int) * 2, c->stream));
   }
-  if (c->cs_w_G != CS64_G) {   // the weights (and a copy of dimSparsity) slice-major; they stay so until something else binds
-    if (!c->d_cs_w64) HIP_TRY(hipMalloc(&c->d_cs_w64, sizeof(double) * (size_t)n));
-    if (!c->d_cs_ds64) HIP_TRY(hipMalloc(&c->d_cs_ds64, sizeof(double) * (size_t)n));
-    hipLaunchKernelGGL(dsgd_cs64_slice_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_w64, c->d_cs_w64, c->dp, Sp);
-    hipLaunchKernelGGL(dsgd_cs64_slice_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_ds64, c->d_cs_ds64, c->dp, Sp);
-    HIP_TRY(hipGetLastError());
-    c->cs_w_G = CS64_G;
-  }
+  DSGD_TRY(cs64_slice(c));   // they stay slice-major until something else binds
   const unsigned long long n_launch = (unsigned long long)(step_end - step_begin);
   if ((unsigned long long)c->cs64_tag0 + n_launch + 1ull >= (1ull << 32)) {   // (the tags would wrap: start the count again)
     HIP_TRY(hipMemsetAsync(c->d_cs64_x, 0, sizeof(unsigned long long) * 2 * CS64_G * CS64_XSTRIDE2, c->stream));
@@ -2152,11 +2164,33 @@ static int layout_finish(dsgd_ctx* c, unsigned int* d_cnt) {   // (takes ownersh
   c->s_dirty = true;
   return DSGD_OK;
 }
+// fp64 across ranks: ONE vexp, the largest over the ranks' data (the fixed-point grid of every worker's sums and the
+// finish that reads them).  ncclSum is the one reduction used anywhere here: a [world] vector with the own slot filled,
+// summed, the maximum taken locally.  (The value stays when the communicator goes; dsgd_load_csr sets the data's own.)
+static int vexp_collective(dsgd_ctx* c) {
+  if (!c->comm || !c->fp64) return DSGD_OK;
+  std::vector<long long> v((size_t)c->world, 0);
+  v[(size_t)c->rank] = c->vexp;
+  long long* d_v = nullptr;
+  HIP_TRY(hipMalloc(&d_v, sizeof(long long) * v.size()));
+  hipError_t e = hipMemcpyAsync(d_v, v.data(), sizeof(long long) * v.size(), hipMemcpyHostToDevice, c->stream);
+  int r = 0;
+  if (e == hipSuccess) r = rccl::AllReduce(d_v, d_v, v.size(), rccl::kInt64, rccl::kSum, c->comm, c->stream);
+  if (e == hipSuccess && !r) e = hipMemcpyAsync(v.data(), d_v, sizeof(long long) * v.size(), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && !r) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(d_v);
+  if (r) return fail(DSGD_ERCCL, "ncclAllReduce(vexp): %s", rccl::GetErrorString(r));
+  if (e != hipSuccess) return fail(DSGD_EHIP, "vexp: %s", hipGetErrorString(e));
+  c->vexp = (int)*std::max_element(v.begin(), v.end());
+  c->fix_scale = std::ldexp(1.0f, FIX_SHIFT - c->vexp);
+  return DSGD_OK;
+}
 static int prepare_layout(dsgd_ctx* c) {
   if (c->layout_ready) return DSGD_OK;
   unsigned int* d_cnt = nullptr;
   DSGD_TRY(layout_begin(c, &d_cnt));
-  const int rc = layout_collective(c, d_cnt);
+  int rc = layout_collective(c, d_cnt);
+  if (!rc) rc = vexp_collective(c);
   if (rc) {
     (void)hipFree(d_cnt);
     return rc;
@@ -2956,6 +2990,13 @@ static int refuse_fp64_all(dsgd_ctx* const* ctxs, int n, const char* what) {
   for (int i = 0; i < n; ++i) DSGD_TRY(refuse_fp64(ctxs[i], what));
   return DSGD_OK;
 }
+// ... and with a communicator attached (dsgd_comm_init_f64) the plans: the persistent column-slice kernel cannot hold a collective
+static int refuse_fp64_comm(dsgd_ctx* c, const char* what) {
+  if (c->fp64 && c->comm)
+    return fail(DSGD_EUNSUPPORTED, "%s is not available in an fp64 context with a communicator attached (dsgd_sync_step_f64 is "
+                                   "the step that spans the ranks)", what);
+  return DSGD_OK;
+}
 static int require_fp64(dsgd_ctx* c, const char* what) {
   if (!c->fp64) return fail(DSGD_ESTATE, "%s needs an fp64 context (dsgd_config.flags = DSGD_F_FP64)", what);
   return DSGD_OK;
@@ -3166,6 +3207,9 @@ int dsgd_destroy(dsgd_ctx* c) {
   (void)hipFree(c->d_rp64_acc);
   (void)hipFree(c->d_rp64_s);
   (void)hipFree(c->d_rp64_g);
+  (void)hipFree(c->d_rp64_gath);
+  (void)hipFree(c->d_rp64_gsegs);
+  if (c->h_rp64_ranks) (void)hipHostFree(c->h_rp64_ranks);
   (void)hipFree(c->d_g);
   (void)hipFree(c->d_g64);
   (void)hipFree(c->d_gsum);
@@ -3715,6 +3759,8 @@ static int finish_mail(dsgd_ctx* c, dsgd_batch_stats* stats, long long total, un
 
 static int sync_step64(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int n_workers, double lr,
                       dsgd_batch_stats* stats);
+static int sync_step64_ranks(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int n_workers, double lr,
+                             dsgd_batch_stats* stats);
 int dsgd_sync_step(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers,
                    float lr, dsgd_batch_stats* stats) {
   DSGD_TRY(check_ctx(c));
@@ -3725,6 +3771,7 @@ int dsgd_sync_step(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int6
   DSGD_TRY(require_ds(c));
   DSGD_TRY(require_sync_mode(c));
   DSGD_TRY(prepare_layout(c));
+  if (c->fp64 && c->comm) return sync_step64_ranks(c, idx_per_worker, n_per_worker, n_workers, (double)lr, stats);
   if (c->fp64) return sync_step64(c, idx_per_worker, n_per_worker, n_workers, (double)lr, stats);
   long long mx = 0, tot = 0;
   {
@@ -4030,6 +4077,7 @@ int dsgd_plan_create(dsgd_ctx* c, const int32_t* idx, const int64_t* offsets, in
   if (!idx || !offsets || !out || n_steps < 1 || n_workers < 1) return fail(DSGD_EINVAL, "bad plan arguments");
   const int64_t n_lists = n_steps * n_workers;
   std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_create"));
   DSGD_TRY(bind(c, true));   // (nothing here touches w: slice-major weights stay as they are)
   dsgd_plan* p = nullptr;
   DSGD_TRY(plan_frame(c, offsets, n_steps, n_workers, &p));
@@ -4136,6 +4184,7 @@ int dsgd_plan_create_from_seed(dsgd_ctx* c, uint64_t* jstate, const int64_t* spl
   }
   const long long nominal = start[(size_t)n_shuf];
   std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_create_from_seed"));
   DSGD_TRY(bind(c, true));
   for (int k = 0; k < n_splits; ++k)
     if (split_end[k] > c->n_rows) return fail(DSGD_ERANGE, "worker %d's rows [%lld, %lld) outside the %lld loaded", k, (long long)split_begin[k], (long long)split_end[k], c->n_rows);
@@ -4446,6 +4495,7 @@ int dsgd_plan_run(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_en
     return fail(DSGD_EINVAL, "steps [%lld, %lld) outside the plan's %lld steps", (long long)step_begin, (long long)step_end,
                 p->n_steps);
   std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_run"));
   DSGD_TRY(bind(c, true));
   if (c->fp64) return plan_run64(c, p, step_begin, step_end, (double)lr);
   DSGD_TRY(require_data(c));
@@ -4509,6 +4559,7 @@ int dsgd_plan_run_f64(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t ste
                 p->n_steps);
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(require_fp64(c, "dsgd_plan_run_f64"));
+  DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_run_f64"));
   DSGD_TRY(bind(c, true));
   return plan_run64(c, p, step_begin, step_end, lr);
 }
@@ -4522,6 +4573,7 @@ int dsgd_plan_run_async_f64(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64
                 p->n_steps);
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(require_fp64(c, "dsgd_plan_run_async_f64"));
+  DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_run_async_f64"));
   if (p->n_workers != 1)
     return fail(DSGD_EINVAL, "an asynchronous iteration is one worker's: this plan has %d workers per step", p->n_workers);
   DSGD_TRY(bind(c, true));
@@ -4533,6 +4585,7 @@ int dsgd_async_step_f64(dsgd_ctx* c, const int32_t* idx, int64_t n, double lr, d
   if (n <= 0 || !idx) return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors");
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(require_fp64(c, "dsgd_async_step_f64"));
+  DSGD_TRY(refuse_fp64_comm(c, "dsgd_async_step_f64"));
   DSGD_TRY(bind(c, true));
   DSGD_TRY(require_data(c));
   DSGD_TRY(require_ds(c));
@@ -4656,7 +4709,63 @@ static int rp64_ensure(dsgd_ctx* c, int n_workers) {
   return DSGD_OK;
 }
 // the two launches over the staged lists (c->cur_idx, c->d_segs); step = false: the gradient of worker 0 into d_rp64_g
-static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, bool step, double lr) {
+// ---- ... across ranks (a communicator attached with dsgd_comm_init_f64; csrc/dsgd_rp64.hpp "across ranks") ----
+static long long rp64_gather_pad(int world) { return ((long long)world + 63) & ~63LL; }
+static void rp64_gather_drop(dsgd_ctx* c) {   // (after a failure half way: the next step starts from a zeroed buffer)
+  (void)hipStreamSynchronize(c->stream);
+  (void)hipFree(c->d_rp64_gath);
+  (void)hipFree(c->d_rp64_gsegs);
+  c->d_rp64_gath = nullptr;
+  c->d_rp64_gsegs = nullptr;
+  c->rp64_gk = 0;
+}
+static int rp64_gather_ensure(dsgd_ctx* c, int K) {
+  if (!c->h_rp64_ranks) HIP_TRY(hipHostMalloc(&c->h_rp64_ranks, sizeof(unsigned long long) * 64, hipHostMallocDefault));
+  if (c->rp64_gk >= K && c->d_rp64_gath) return DSGD_OK;
+  rp64_gather_drop(c);
+  const long long stride = rp64_gather_stride(c->dp);
+  const size_t words = (size_t)rp64_gather_pad(c->world) + (size_t)stride * (size_t)K;
+  HIP_TRY(hipMalloc(&c->d_rp64_gath, sizeof(unsigned long long) * words));
+  HIP_TRY(hipMalloc(&c->d_rp64_gsegs, sizeof(WorkSeg) * (size_t)K));
+  HIP_TRY(hipMemsetAsync(c->d_rp64_gath, 0, sizeof(unsigned long long) * words, c->stream));
+  c->rp64_gstride = stride;
+  c->rp64_gk = K;
+  return DSGD_OK;
+}
+// Behind the gradient kernel: the ranks' words first -- every rank must have been called with the same number of hosted
+// workers, or the ranks would enqueue different numbers of messages and a collective that only some ranks join never
+// completes; this is the one host read of the step besides its statistics -- then the worker slots, one message each
+// (cut at RP64_MSG_WORDS), then the headers.  Returns with the finish still to launch.
+static int rp64_gather(dsgd_ctx* c, int k) {
+  const int W = c->world, K = k * W;
+  unsigned long long* slots = c->d_rp64_gath + rp64_gather_pad(W);
+  int r = rccl::AllReduce(c->d_rp64_gath, c->d_rp64_gath, (size_t)W, rccl::kInt64, rccl::kSum, c->comm, c->stream);
+  if (r) return fail(DSGD_ERCCL, "ncclAllReduce(hosted workers): %s", rccl::GetErrorString(r));
+  HIP_TRY(hipMemcpyAsync(c->h_rp64_ranks, c->d_rp64_gath, sizeof(unsigned long long) * (size_t)W, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int q = 0; q < W; ++q)
+    if (c->h_rp64_ranks[q] != (unsigned long long)k) {
+      // nothing of this step has left the rank besides these words: its own slots and the words are zeroed again
+      HIP_TRY(hipMemsetAsync(c->d_rp64_gath, 0, sizeof(unsigned long long) * (size_t)W, c->stream));
+      HIP_TRY(hipMemsetAsync(slots + (long long)c->rank * k * c->rp64_gstride, 0, sizeof(unsigned long long) * (size_t)k * (size_t)c->rp64_gstride,
+                             c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      return fail(DSGD_EINVAL, "rank %d was called with %llu hosted workers, this rank (%d) with %d: every rank of a step hosts the "
+                               "same number (the weights are unchanged)", q, c->h_rp64_ranks[q], c->rank, k);
+    }
+  for (int g = 0; g < K; ++g)
+    for (long long off = 0; off < c->rp64_gstride; off += RP64_MSG_WORDS) {
+      unsigned long long* at = slots + (long long)g * c->rp64_gstride + off;
+      const size_t n = (size_t)std::min<long long>(RP64_MSG_WORDS, c->rp64_gstride - off);
+      r = rccl::AllReduce(at, at, n, rccl::kInt64, rccl::kSum, c->comm, c->stream);
+      if (r) return fail(DSGD_ERCCL, "ncclAllReduce(worker %d's sums): %s", g, rccl::GetErrorString(r));
+    }
+  hipLaunchKernelGGL(dsgd_rp64_header_kernel, dim3(1), dim3(RP64_THREADS), 0, c->stream, c->d_rp64_gath, W, slots, c->rp64_gstride, K, c->dp,
+                     c->d_rp64_gsegs, c->d_sc);
+  HIP_TRY(hipGetLastError());
+  return DSGD_OK;
+}
+static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, bool step, double lr, bool gather = false) {
   const bool sliced = c->cs_w_G == CS64_G;   // (the weights stay in whichever layout they are: slice-major between plan runs)
   const int Sp = sliced ? cs64_sp(c->dp) : 0;
   double* w = sliced ? c->d_cs_w64 : c->d_w64;
@@ -4679,13 +4788,28 @@ static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, bool ste
   a.lambda = c->cfg.lambda;
   a.s_out = c->d_rp64_s;
   a.sc = c->d_sc;
-  hipLaunchKernelGGL(dsgd_rp64_grad_kernel, dim3((unsigned)(bpw * n_workers + 1)), dim3(RP64_THREADS), 0, c->stream, a);
-  HIP_TRY(hipGetLastError());
+  a.rank_word = nullptr;
   Rp64FinishArgs f;
   f.acc = c->d_rp64_acc;
   f.acc_stride = c->rp64_stride;
   f.segs = c->d_segs;
   f.K = n_workers;
+  if (gather) {   // this rank's slots of the gather buffer; the finish over every rank's workers
+    unsigned long long* slots = c->d_rp64_gath + rp64_gather_pad(c->world);
+    a.acc = slots + (long long)c->rank * n_workers * c->rp64_gstride;
+    a.acc_stride = c->rp64_gstride;
+    a.rank_word = c->d_rp64_gath + c->rank;
+    hipLaunchKernelGGL(dsgd_rp64_grad_gather_kernel, dim3((unsigned)(bpw * n_workers + 1)), dim3(RP64_THREADS), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    DSGD_TRY(rp64_gather(c, n_workers));
+    f.acc = slots;
+    f.acc_stride = c->rp64_gstride;
+    f.segs = c->d_rp64_gsegs;
+    f.K = n_workers * c->world;
+  } else {
+    hipLaunchKernelGGL(dsgd_rp64_grad_kernel, dim3((unsigned)(bpw * n_workers + 1)), dim3(RP64_THREADS), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+  }
   f.dp = c->dp;
   f.vexp = c->vexp;
   f.Sp = Sp;
@@ -4738,6 +4862,27 @@ int dsgd_gradient_f64(dsgd_ctx* c, const double* w, const int32_t* idx, int64_t 
   return DSGD_OK;
 }
 
+// the step of n_workers hosted workers under a communicator (locked, bound, layout ready): the oracle's synchronous step over
+// n_workers * world workers in rank-major order; the statistics are the job's
+static int sync_step64_ranks(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int n_workers, double lr,
+                             dsgd_batch_stats* stats) {
+  if (n_workers > 0x7fffffff / c->world) return fail(DSGD_EINVAL, "n_workers * world overflows");
+  DSGD_TRY(rp64_check_lists(c, idx_per_worker, n_per_worker, n_workers));
+  DSGD_TRY(rp64_ensure(c, 1));   // (s and the request's gradient; the local accumulators are not used)
+  DSGD_TRY(rp64_gather_ensure(c, n_workers * c->world));
+  DSGD_TRY(reset_counters(c));
+  long long mx = 0, tot = 0;
+  DSGD_TRY(stage_lists(c, idx_per_worker, n_per_worker, n_workers, &mx, &tot));
+  int rc = rp64_launch(c, n_workers, mx, true, lr, true);
+  if (rc == DSGD_OK) {
+    c->s_dirty = true;
+    rc = finish_stats(c, stats, tot);
+    if (rc == DSGD_OK && stats) stats->n_samples = (int64_t)c->h_sc->n_samples;
+  }
+  if (rc != DSGD_OK && rc != DSGD_EINVAL) rp64_gather_drop(c);   // (DSGD_EINVAL: the ranks disagreed, the buffer is clean)
+  return rc;
+}
+
 int dsgd_sync_step_f64(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers, double lr,
                        dsgd_batch_stats* stats) {
   DSGD_TRY(check_ctx(c));
@@ -4749,6 +4894,7 @@ int dsgd_sync_step_f64(dsgd_ctx* c, const int32_t* const* idx_per_worker, const 
   DSGD_TRY(require_ds(c));
   DSGD_TRY(require_sync_mode(c));
   DSGD_TRY(prepare_layout(c));
+  if (c->comm) return sync_step64_ranks(c, idx_per_worker, n_per_worker, n_workers, lr, stats);
   DSGD_TRY(rp64_check_lists(c, idx_per_worker, n_per_worker, n_workers));
   DSGD_TRY(rp64_ensure(c, n_workers));
   DSGD_TRY(reset_counters(c));
@@ -4772,6 +4918,7 @@ int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int
   if (n_updates > 0x7fffffffLL) return fail(DSGD_EINVAL, "at most 2^31 - 1 updates per plan");
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(require_fp64(c, "dsgd_async_plan_create"));
+  DSGD_TRY(refuse_fp64_comm(c, "dsgd_async_plan_create"));
   DSGD_TRY(bind(c, true));   // (nothing here touches w)
   for (int k = 0; k < n_workers; ++k)
     if (assigned_end[k] > c->n_rows)
@@ -5467,6 +5614,66 @@ int dsgd_comm_init(dsgd_ctx* c, const char* unique_id, int32_t world_size, int32
   c->comm_broken = false;
   c->world = world_size;
   c->rank = rank;
+  return DSGD_OK;
+}
+
+// The column layout of loaded data again, under the communicator that was just attached: the columns back to their keys,
+// the resident vectors to key order, then the ranking from the all-reduced counts (and the ranks' common vexp).  Every
+// plan's column slices belong to the layout that goes (layout_gen).
+static int relayout(dsgd_ctx* c) {
+  if (c->layout_ready) {
+    std::vector<int> perm((size_t)c->dp), inv((size_t)c->dp);
+    HIP_TRY(hipMemcpyAsync(perm.data(), c->d_perm, sizeof(int) * perm.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int j = 0; j < c->dp; ++j) inv[(size_t)perm[(size_t)j]] = j;
+    DSGD_TRY(reset_layout(c));   // (d_perm: the identity from here)
+    if (c->nnz > 0) {
+      int* d_inv = nullptr;
+      HIP_TRY(hipMalloc(&d_inv, sizeof(int) * inv.size()));
+      hipError_t e = hipMemcpy(d_inv, inv.data(), sizeof(int) * inv.size(), hipMemcpyHostToDevice);
+      if (e == hipSuccess) {
+        const int blocks = (int)std::min<long long>((c->nnz + 255) / 256, (long long)c->n_cu * 8);
+        hipLaunchKernelGGL(dsgd_remap_cols_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_col, c->nnz, d_inv);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      (void)hipFree(d_inv);
+      if (e != hipSuccess) return fail(DSGD_EHIP, "column keys: %s", hipGetErrorString(e));
+    }
+  }
+  return prepare_layout(c);
+}
+
+int dsgd_comm_init_f64(dsgd_ctx* c, const char* unique_id, int32_t world_size, int32_t rank) {
+  DSGD_TRY(check_ctx(c));
+  if (!unique_id || world_size < 1 || rank < 0 || rank >= world_size) return fail(DSGD_EINVAL, "bad communicator arguments");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_comm_init_f64"));
+  if (world_size > 64) return fail(DSGD_EUNSUPPORTED, "at most 64 ranks");
+  if (!rccl::available()) return fail(DSGD_ERCCL, "librccl could not be loaded");
+  const bool sliced = c->cs_w_G == CS64_G;
+  DSGD_TRY(bind(c));   // (rank order: the ranking may be about to change)
+  DSGD_TRY(require_sync_mode(c));
+  if (c->comm) return fail(DSGD_ESTATE, "communicator already attached");
+  rccl::unique_id_t id;
+  memcpy(id.internal, unique_id, DSGD_UNIQUE_ID_BYTES);
+  RCCL_TRY(rccl::CommInitRank(&c->comm, world_size, id, rank));
+  c->comm_broken = false;
+  c->world = world_size;
+  c->rank = rank;
+  // loaded data: ONE ranking and ONE vexp now, on every rank (data loaded later: at its first use, as in fp32)
+  int rc = c->d_row_ptr ? relayout(c) : DSGD_OK;
+  if (rc == DSGD_OK && sliced) rc = cs64_slice(c);   // (the weights back in the layout they were in)
+  if (rc != DSGD_OK) {
+    char msg[sizeof(g_err)];
+    snprintf(msg, sizeof(msg), "%s", g_err);
+    (void)hipStreamSynchronize(c->stream);
+    (void)rccl::CommDestroy(c->comm);
+    c->comm = nullptr;
+    c->world = 1;
+    c->rank = 0;
+    return fail(rc, "%s", msg);
+  }
   return DSGD_OK;
 }
 

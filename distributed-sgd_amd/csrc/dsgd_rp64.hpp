@@ -13,6 +13,10 @@
 //                            (oracle/oracle.c orc_gradient / orc_sync_step, operation for operation); the accumulators are
 //                            left zeroed for the next call.
 //
+// Under a communicator (dsgd_comm_init_f64; "across ranks" below) the sums go into this rank's slots of a gather buffer
+// (dsgd_rp64_grad_gather_kernel: the same body), the buffer travels, dsgd_rp64_header_kernel turns the gathered headers
+// into the finish's list ranges, and dsgd_rp64_finish_kernel<true> folds every rank's workers.
+//
 // The grid: a worker's list of n rows (duplicates count) adds entries of |x| <= 2^vexp scaled by 2^shift, shift = 62 -
 // ceil(log2 n): no column sum leaves the 64-bit range.  Integer sums do not depend on the order of the adds -- the result
 // is bit-reproducible, whatever the list's order or the grid.  An entry of exponent e is exact on the grid when
@@ -38,6 +42,19 @@ __host__ __device__ constexpr int rp64_ceil_log2(long long n) {
 }
 __host__ __device__ constexpr int rp64_shift(long long n) { return 62 - rp64_ceil_log2(n); }
 
+// ---- across ranks (a communicator attached with dsgd_comm_init_f64) ----
+// The gather buffer of a step of k hosted workers in a world of W ranks, K = k * W, 64-bit words, zero between calls:
+//   [W (padded to 64)]   one word per rank: the k it was called with (the ranks must agree before the slots travel)
+//   [K][stride]          global worker r * k + j's slot: [0, dp) its fixed-point column sums, rank order, then its header
+//                        words -- the list length n (its shift is 62 - ceil(log2 n)) and its active count
+// A slot is non-zero on exactly ONE rank, so ncclAllReduce(ncclInt64, ncclSum) over the buffer IS the all-gather: exact,
+// whatever the order of the sum.  Behind it every rank holds every worker's integers and folds them in worker order with
+// dsgd_rp64_finish_kernel<true> itself -- the bits of ONE process that hosts the K workers.
+constexpr int RP64_HDR_N = 0, RP64_HDR_ACTIVE = 1, RP64_HDR_WORDS = 2;
+// one message of the gather: at most 1 MiB (a slot is 378 KB at RCV1's D; wider slots are cut)
+constexpr long long RP64_MSG_WORDS = (1LL << 20) / (long long)sizeof(unsigned long long);
+__host__ __device__ constexpr long long rp64_gather_stride(int dp) { return ((long long)dp + RP64_HDR_WORDS + 63) & ~63LL; }
+
 struct Rp64Args {
   CsrView m;
   const double* w;                 // the weights, rank order (Sp = 0) or slice-major
@@ -51,6 +68,7 @@ struct Rp64Args {
   double lambda;
   double* s_out;                   // s = lambda * 2.0 * (w . ds)
   DevScalars* sc;                  // n_active, err (1: a row index outside the data)
+  unsigned long long* rank_word;   // (the gather of a communicator only) this rank's word of the gather buffer: K
 };
 
 // x . w of `row` by the 16 lanes of a group, in whichever layout the weights are (row_dot64's arithmetic and order)
@@ -65,7 +83,10 @@ __device__ __forceinline__ double rp64_row_dot(const CsrView& m, long long row, 
   return d;
 }
 
-__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_kernel(Rp64Args a) {
+// GATHER: `acc` are this rank's K slots of a communicator's gather buffer (see below) -- a slot's header words get the
+// list length and the active count, the rank's word gets K, all with ordinary stores / vector atomics
+template <bool GATHER>
+__device__ __forceinline__ void rp64_grad_body(const Rp64Args& a) {
 #pragma clang fp contract(off)
   __shared__ double red[RP64_THREADS / 64];
   __shared__ unsigned int n_act;
@@ -82,6 +103,7 @@ __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_kernel(Rp64Args a
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
     if (tid == 0) *a.s_out = a.lambda * 2.0 * ((red[0] + red[1]) + (red[2] + red[3]));   // ref: core/ml/SparseSVM.scala:31
+    if (GATHER && tid == 0) *a.rank_word = (unsigned long long)a.K;
     return;
   }
   const int k = (int)((long long)blockIdx.x / a.blocks_per_worker);
@@ -126,8 +148,14 @@ __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_kernel(Rp64Args a
     const unsigned long long v = hot[i];
     if (v) atomicAdd(&acc[i], v);
   }
-  if (tid == 0 && n_act) atomicAdd(&a.sc->n_active, (unsigned long long)n_act);
+  if (GATHER) {
+    if (tid == 0 && b == 0) acc[a.dp + RP64_HDR_N] = (unsigned long long)n;   // (zero until here, like every word of the slot)
+    if (tid == 0 && n_act) atomicAdd(&acc[a.dp + RP64_HDR_ACTIVE], (unsigned long long)n_act);
+  } else {
+    if (tid == 0 && n_act) atomicAdd(&a.sc->n_active, (unsigned long long)n_act);
+  }
 }
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_kernel(Rp64Args a) { rp64_grad_body<false>(a); }
 
 struct Rp64FinishArgs {
   unsigned long long* acc;   // [K][acc_stride], zeroed here
@@ -171,5 +199,39 @@ __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_finish_kernel(Rp64Fini
       const long long at = rp64_at(r, a.Sp);
       a.w[at] = filt64(a.w[at] - upd);
     }
+  }
+}
+
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_gather_kernel(Rp64Args a) { rp64_grad_body<true>(a); }
+
+// Behind the gather, ONE workgroup: the K headers become the list ranges the finish takes its shifts from ({0, n}), the
+// job's samples and active rows go to the context's scalars, and the header and rank words are zeroed again (the
+// finish zeroes the sums: the whole buffer is zero for the next call)
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_header_kernel(unsigned long long* rank_words, int W, unsigned long long* slots,
+                                                                        long long stride, int K, int dp, WorkSeg* segs, DevScalars* sc) {
+  __shared__ unsigned long long tot[2];
+  const int tid = threadIdx.x;
+  if (tid < 2) tot[tid] = 0ull;
+  __syncthreads();
+  unsigned long long n_sum = 0ull, a_sum = 0ull;
+  for (int k = tid; k < K; k += RP64_THREADS) {
+    unsigned long long* h = slots + (long long)k * stride + dp;
+    const unsigned long long n = h[RP64_HDR_N], act = h[RP64_HDR_ACTIVE];
+    h[RP64_HDR_N] = 0ull;
+    h[RP64_HDR_ACTIVE] = 0ull;
+    WorkSeg sg;
+    sg.begin = 0;
+    sg.end = (long long)n;
+    segs[k] = sg;
+    n_sum += n;
+    a_sum += act;
+  }
+  if (n_sum) atomicAdd(&tot[0], n_sum);
+  if (a_sum) atomicAdd(&tot[1], a_sum);
+  for (int r = tid; r < W; r += RP64_THREADS) rank_words[r] = 0ull;
+  __syncthreads();
+  if (tid == 0) {
+    sc->n_samples = tot[0];
+    sc->n_active = tot[1];
   }
 }

@@ -78,7 +78,8 @@ enum {
  *   - dsgd_forward, dsgd_loss_acc: evaluated with the fp64 weights (a float w is promoted and replaces them).
  *   - everything else that would run an fp32 training kernel returns DSGD_EUNSUPPORTED and changes nothing:
  *     dsgd_gradient, dsgd_apply, dsgd_sync_step_ranges(_async), dsgd_async_* (the float dsgd_async_step and the
- *     lock-free engine, dsgd_async_start, included), dsgd_update_grad, dsgd_comm_*, dsgd_*_devices.
+ *     lock-free engine, dsgd_async_start, included), dsgd_update_grad, dsgd_comm_init, dsgd_comm_init_all,
+ *     dsgd_*_devices (one thread driving several fp64 contexts is not built: see "Across ranks" below).
  *   The asynchronous iteration (Slave.asyncTask + updateGrad, core/Slave.scala:79-111,177-185; orc_async_step) has its
  *   own fp64 entry points, declared with the asynchronous path below: dsgd_async_step_f64, dsgd_update_grad_f64,
  *   dsgd_async_plan_create and dsgd_plan_run_async_f64.  They run on dsgd_cs64_async_kernel (the same plan layout,
@@ -98,6 +99,28 @@ enum {
  *   rows.  Inside it the results differ from the oracle's only by the rounding order of x . w and w . ds and by the
  *   oracle's per-add rounding and mid-sum 1e-20 filter, which the exact sum does not have.  The limits and refusals
  *   above are unchanged: dsgd_gradient, dsgd_sync_step_ranges and plans beyond them still return DSGD_EUNSUPPORTED.
+ *   ACROSS RANKS (dsgd_comm_init_f64, declared with the multi-GPU entry points; one process per GPU).
+ *   World W ranks, each an fp64 context with its own rows, every rank calling with the same number k of hosted workers:
+ *   a step is orc_sync_step over K = k * W workers in rank-major order (worker j of rank r is global worker r * k + j).
+ *   Every worker's exact 64-bit column sums, its list length and its active count are gathered on every rank -- an
+ *   all-gather written as ncclAllReduce(ncclInt64, ncclSum) over a buffer in which a slot is non-zero on exactly one
+ *   rank, in messages of at most 1 MiB -- and every rank folds them with the single-context finish.  So after every step
+ *   the replicas hold the same fp64 weights bit for bit, and those are bit for bit the weights of ONE fp64 context
+ *   that holds all the rows and runs dsgd_sync_step_f64 with the K lists (row indices shifted) from the same weights.
+ *   The ranks agree on what the finish depends on: ONE column ranking (column counts all-reduced), ONE vexp (the
+ *   largest over the ranks' data; it stays when the communicator goes, until dsgd_load_csr) and, from
+ *   dsgd_build_dim_sparsity, dimSparsity from the all-reduced feature counts -- what one process over all the train
+ *   rows builds.  With a communicator attached:
+ *   - dsgd_sync_step_f64, and dsgd_sync_step (float lr promoted), run that step; dsgd_batch_stats carry the job's
+ *     samples and active rows on every rank.  Ranks called with different n_workers all get DSGD_EINVAL, weights
+ *     unchanged (the counts travel first; a step moves K * (D + 3) * 8 bytes, rounded up to 512 per worker).
+ *   - dsgd_loss_acc returns the job's loss, accuracy and counts on every rank (ranges are local rows; the tallies are
+ *     summed), bit for bit a single context's over the union of the ranges.
+ *   - dsgd_gradient_f64, dsgd_forward_f64, dsgd_update_grad_f64 and the get / set of weights and dimSparsity stay local.
+ *   - dsgd_plan_create / _n / _from_seed, dsgd_plan_run / _f64 / _async_f64, dsgd_async_plan_create and
+ *     dsgd_async_step_f64 return DSGD_EUNSUPPORTED and change nothing: the persistent column-slice kernel cannot hold a
+ *     collective.  (host.MasterSync.fit falls back from a refused plan to one dsgd_sync_step_f64 per step.)
+ *   Without a communicator nothing changes.  Real RCCL with more than one rank has not run; no multi-GPU speed is claimed.
  * The entry points below that name fp64 return DSGD_ESTATE on an fp32 context (dsgd_precision excepted).            */
 
 typedef struct dsgd_ctx dsgd_ctx;
@@ -389,6 +412,11 @@ int dsgd_async_read_trace_dots(dsgd_ctx* ctx, int64_t* seen_from, float* dots, i
 int dsgd_comm_unique_id(char* id_out /* DSGD_UNIQUE_ID_BYTES */);
 int dsgd_comm_init(dsgd_ctx* ctx, const char* unique_id, int32_t world_size, int32_t rank);
 int dsgd_comm_destroy(dsgd_ctx* ctx);
+/* The same for an fp64 context ("THE FP64 MODE", "Across ranks"; DSGD_ESTATE on an fp32 context -- dsgd_comm_init keeps
+ * refusing an fp64 one with DSGD_EUNSUPPORTED).  A collective call: every rank attaches in the same state (its rows
+ * loaded, or not yet).  Loaded rows are ranked again here, from the column counts summed over the ranks, and the ranks
+ * agree on vexp; rows loaded later at their first use, as in fp32.  dsgd_comm_destroy detaches.                      */
+int dsgd_comm_init_f64(dsgd_ctx* ctx, const char* unique_id, int32_t world_size, int32_t rank);
 
 /* ---- several GPUs driven by ONE host thread --------------------------------------------------------------------
  * The reference's dev role runs the master and every slave in ONE JVM (Main.scala:144-158); SURVEY.md 8(b) lists the

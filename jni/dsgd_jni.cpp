@@ -498,6 +498,39 @@ JNIEXPORT void JNICALL NATIVE(commInitAll)(JNIEnv* env, jobject, jlongArray ctxs
   if (rc) raise(env, rc);
 }
 
+// one process per GPU in the fp64 mode (include/dsgd.h "ACROSS RANKS"): rank 0 fills idOut (DSGD_UNIQUE_ID_BYTES bytes) and
+// hands it to the other ranks over any host channel; every rank attaches its fp64 context with it
+JNIEXPORT void JNICALL NATIVE(commUniqueId)(JNIEnv* env, jobject, jbyteArray idOut) {
+  if (!idOut || env->GetArrayLength(idOut) != DSGD_UNIQUE_ID_BYTES) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "idOut: an array of DSGD_UNIQUE_ID_BYTES (128) bytes");
+    return;
+  }
+  int rc;
+  {
+    ByteElems id(env, idOut, 0);
+    rc = dsgd_comm_unique_id(reinterpret_cast<char*>(id.p));
+  }
+  if (rc) raise(env, rc);
+}
+
+JNIEXPORT void JNICALL NATIVE(commInitF64)(JNIEnv* env, jobject, jlong h, jbyteArray uniqueId, jint worldSize, jint rank) {
+  if (!uniqueId || env->GetArrayLength(uniqueId) != DSGD_UNIQUE_ID_BYTES) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "uniqueId: the DSGD_UNIQUE_ID_BYTES (128) bytes of commUniqueId");
+    return;
+  }
+  int rc;
+  {
+    ByteElems id(env, uniqueId, JNI_ABORT);
+    rc = dsgd_comm_init_f64(ctx(h), reinterpret_cast<const char*>(id.p), worldSize, rank);
+  }
+  if (rc) raise(env, rc);
+}
+
+JNIEXPORT void JNICALL NATIVE(commDestroy)(JNIEnv* env, jobject, jlong h) {
+  int rc = dsgd_comm_destroy(ctx(h));
+  if (rc) raise(env, rc);
+}
+
 // Main.scala:54-65 over the WHOLE train set: column ranking and feature counts summed over the contexts
 JNIEXPORT void JNICALL NATIVE(buildDimSparsityDevices)(JNIEnv* env, jobject, jlongArray ctxs, jlongArray nTrain) {
   std::vector<dsgd_ctx*> c = ctx_list(env, ctxs);

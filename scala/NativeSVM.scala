@@ -56,6 +56,11 @@ object NativeSVM {
   @native def asyncWait(ctx: Long): Unit
   @native def setWeights(ctx: Long, w: Array[Float]): Unit
   @native def getWeights(ctx: Long, wOut: Array[Float]): Unit
+  // one process per GPU in the fp64 mode: rank 0 fills idOut (128 bytes) and hands it to the other ranks; every rank attaches
+  // its fp64 context with it -- from then on syncStep / lossAcc span the ranks, bit for bit one process over all the rows
+  @native def commUniqueId(idOut: Array[Byte]): Unit
+  @native def commInitF64(ctx: Long, uniqueId: Array[Byte], worldSize: Int, rank: Int): Unit
+  @native def commDestroy(ctx: Long): Unit
   // several GPUs driven by ONE thread of this JVM (dev role: master + every slave in one JVM, Main.scala:144-158): one
   // context per device, rank i = ctxs(i); arrays over workers are context-major (include/dsgd.h, dsgd_*_devices)
   @native def commInitAll(ctxs: Array[Long]): Unit
