@@ -1114,16 +1114,18 @@ __device__ __forceinline__ void w_tile_q(const CsrView& m, const WTables& tt, co
     // lane (`trail`); the slots before the start close the row entering the lane (`head`)
     const unsigned int kstar = bits ? (unsigned int)__builtin_ctz(bits) : 0u;   // first slot of T
     bool in_t[8];
-    float mk[8];
+    float mk[8], hk[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       in_t[k] = (unsigned int)k >= kstar;
       mk[k] = in_t[k] ? pk[k] : 0.0f;
+      hk[k] = in_t[k] ? 0.0f : pk[k];
     }
-    // pairwise trees (packed adds); head = total - trail is exact when the lane holds no start or starts at slot 0
-    const float total = ((pk[0] + pk[1]) + (pk[2] + pk[3])) + ((pk[4] + pk[5]) + (pk[6] + pk[7]));
+    // pairwise trees (packed adds), one per row.  head is summed from its own slots, not taken as total - trail: the
+    // difference carries an error relative to the NEXT row's products, and a row whose products are ten binades below
+    // its neighbour's would be gated on round-off (tests/test_gpu_hard_values.py, `wide`).
     const float trail = ((mk[0] + mk[1]) + (mk[2] + mk[3])) + ((mk[4] + mk[5]) + (mk[6] + mk[7]));
-    const float head = total - trail;
+    const float head = ((hk[0] + hk[1]) + (hk[2] + hk[3])) + ((hk[4] + hk[5]) + (hk[6] + hk[7]));
     float s = trail;
     int f = bits != 0u;
     wave_seg_scan(s, f);

@@ -97,7 +97,17 @@ enum {
  *   depend on the order of the list or of the adds (bit-reproducible).  EXACT RANGE: an entry of exponent e is exact on
  *   the grid when e >= vexp - (39 - ceil(log2 n)): 32 binades at n = 100, 29 at 1,024, 23 at 65,536, 21 at 214,511
  *   rows.  Inside it the results differ from the oracle's only by the rounding order of x . w and w . ds and by the
- *   oracle's per-add rounding and mid-sum 1e-20 filter, which the exact sum does not have.  The limits and refusals
+ *   oracle's per-add rounding and mid-sum 1e-20 filter, which the exact sum does not have.  OUTSIDE it (derived in
+ *   oracle/bounds.py, out_of_range_bound; asserted per coordinate by tests/test_gpu_hard_values.py): an entry whose lowest
+ *   mantissa bit lies below the grid unit 2^(vexp - shift) is rounded to the grid, off by at most half a unit, so a
+ *   worker's sum of column j is off by at most out_j * 2^(vexp - shift - 1), out_j the number of such entries of the column
+ *   in the worker's list (shift = 62 - ceil(log2 n) here, the layout's shift + 32 = 62 - ceil(log2 largest list) in the
+ *   column-slice plans).  A column whose fixed-point sum is exactly 0 while its true sum is not -- certainly when every
+ *   entry is below half a unit, possibly whenever the true sum is within out_j half units of 0 -- leaves the support of the sum and gets NO regulariser (math/Vec.scala:65-75): an error of |s| = |2 lambda
+ *   (w . ds)| in that worker's gradient, lr / K * |s| in the weight, which is not a grid unit.  The fp32 kernels have the
+ *   same two terms at the shift they report (dsgd_tuning_info).  No gate decision depends on the grid: the dots are taken
+ *   on the float values as they are.  Data whose |x| spread over more than the exact range should be scaled per column,
+ *   or cosine-normalised as the reference's loader does, before it is loaded.  The limits and refusals
  *   above are unchanged: dsgd_gradient, dsgd_sync_step_ranges and plans beyond them still return DSGD_EUNSUPPORTED.
  *   ACROSS RANKS (dsgd_comm_init_f64, declared with the multi-GPU entry points; one process per GPU).
  *   World W ranks, each an fp64 context with its own rows, every rank calling with the same number k of hosted workers:

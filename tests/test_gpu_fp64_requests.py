@@ -16,6 +16,7 @@ import pytest
 import dsgd_amd
 from conftest import has_gpu
 from dsgd_amd import _lib, host
+from hard_data import check_exact_range as _check_exact_range   # (with its complement, outside_exact_range)
 from oracle import oracle as orc
 from oracle_backend import OracleBackend
 
@@ -63,21 +64,6 @@ def _check_grad(o, eng, w, idx):
     assert np.array_equal(np.flatnonzero(g), np.flatnonzero(g_o))
     assert np.abs(g - g_o).max() <= 1e-12 * _scale(g_o)
     return g
-
-
-def _vexp(data):
-    vmax = float(np.abs(data.val).max())
-    m, e = math.frexp(vmax)
-    return e - 1 if m == 0.5 else e
-
-
-def _check_exact_range(data, rows, n):
-    """every entry of the rows lies inside the exact range of a list of n rows: e >= vexp - (39 - ceil(log2 n))"""
-    v = np.concatenate([data.val[data.row_ptr[r]:data.row_ptr[r + 1]] for r in np.unique(rows)]).astype(np.float64)
-    v = v[np.abs(v) > 1e-20]
-    _, e = np.frexp(np.abs(v))   # |v| = f * 2^e, f in [0.5, 1): the float's exponent is e - 1
-    lo = _vexp(data) - (39 - math.ceil(math.log2(n)) if n > 1 else 39)
-    assert (e - 1).min() >= lo, ((e - 1).min(), lo)
 
 
 @pytest.mark.parametrize("n", [1, 100, 960, 4096, 65536])

@@ -25,6 +25,7 @@ import pytest
 import dsgd_amd
 import waivers
 from conftest import has_gpu
+from hard_data import ragged_data   # (shared with tests/test_hard_data.py, which runs without a device)
 from oracle import bounds as orb
 from oracle import oracle as orc
 from oracle import ref_dict as rd
@@ -634,27 +635,6 @@ def test_communicator_of_size_one_changes_nothing():
 
 
 # ---- ragged inputs: empty rows, one-element rows, values below the Sparse epsilon ---------------------
-def ragged_data(seed, n_rows=6000):
-    base = dsgd_amd.synth.generate(n_rows, seed=seed)
-    rng = np.random.default_rng(seed)
-    row_ptr, col, val = [0], [], []
-    for i in range(n_rows):
-        b, e = int(base.row_ptr[i]), int(base.row_ptr[i + 1])
-        kind = rng.integers(0, 10)
-        if kind == 0:
-            pass  # empty row: Sparse.zeros
-        elif kind == 1:
-            col.append(base.col[b]); val.append(np.float32(1.0))  # single-element row
-        else:
-            c, v = base.col[b:e], base.val[b:e].copy()
-            if kind == 2:
-                v[0] = np.float32(1e-25)  # dropped by the Sparse constructor (math/Sparse.scala:112-114)
-            col.extend(c.tolist()); val.extend(v.tolist())
-        row_ptr.append(len(col))
-    return dsgd_amd.synth.Csr(base.dim, np.asarray(row_ptr, np.int64), np.asarray(col, np.int32),
-                              np.asarray(val, np.float32), base.label.copy())
-
-
 def test_ragged_rows_all_kernel_paths():
     data = ragged_data(21, n_rows=24000)
     n_train = 20000
