@@ -37,6 +37,8 @@ SYMBOLS = [
     "dsgd_async_step_f64", "dsgd_update_grad_f64", "dsgd_async_plan_create", "dsgd_plan_run_async_f64",
     "dsgd_gradient_f64", "dsgd_sync_step_f64", "dsgd_forward_f64",
     "dsgd_comm_init_f64",
+    "dsgd_set_weights_sparse", "dsgd_set_weights_sparse_f64", "dsgd_get_weights_sparse", "dsgd_get_weights_sparse_f64",
+    "dsgd_gradient_sparse", "dsgd_gradient_sparse_f64", "dsgd_async_step_sparse", "dsgd_async_step_sparse_f64",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")

@@ -128,6 +128,7 @@ static bool available() {
 #include "dsgd_shuffle.hpp"
 #include "dsgd_cs64.hpp"   // (last: the fp64 mode)
 #include "dsgd_rp64.hpp"   // (... and its row-parallel gradient family)
+#include "dsgd_sparse.hpp" // (the Sparse form at the boundary: compaction and scatter-in)
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -519,6 +520,18 @@ struct dsgd_ctx {
   int rp64_gk = 0;
   WorkSeg* d_rp64_gsegs = nullptr;
   unsigned long long* h_rp64_ranks = nullptr;
+  // Sparse values at the boundary (csrc/dsgd_sparse.hpp): the compaction's output in host-mapped memory the kernel writes in
+  // place ([2 words: count, gave up][dp keys][dp values of 8 bytes]), its scan state, and the staged pairs of a sparse setter
+  unsigned long long* h_sp_out = nullptr;
+  unsigned long long* d_sp_out = nullptr;   // the same memory as the device sees it
+  unsigned long long* d_sp_state = nullptr;
+  unsigned long long sp_launches = 0;
+  unsigned int sp_epoch = 0;
+  Pinned pin_sp;
+  char* d_sp_in = nullptr;                  // [dp keys][dp values of 8 bytes]
+  std::vector<unsigned int> sp_seen;        // key -> the stamp of the call that saw it last (the repeated-key check)
+  unsigned int sp_stamp = 0;
+  std::vector<int32_t> row_len;             // the loaded rows' lengths (the bound on an asynchronous step's delta)
 };
 
 static int check_ctx(dsgd_ctx* c) {
@@ -3002,6 +3015,125 @@ static int require_fp64(dsgd_ctx* c, const char* what) {
   return DSGD_OK;
 }
 
+// ---- Sparse values at the boundary (csrc/dsgd_sparse.hpp; include/dsgd.h "SPARSE VALUES") ----
+static size_t sp_vals_off(dsgd_ctx* c) { return 16 + ((sizeof(int) * (size_t)c->dp + 7) & ~(size_t)7); }
+static int sp_tiles(dsgd_ctx* c) { return (c->dp + SP_TILE - 1) / SP_TILE; }
+static int sp_reset_state(dsgd_ctx* c) {
+  HIP_TRY(hipMemsetAsync(c->d_sp_state, 0, sizeof(unsigned long long) * (size_t)(SP_STATE_HEAD + sp_tiles(c)), c->stream));
+  c->sp_launches = 0;
+  c->sp_epoch = 0;
+  c->h_sp_out[0] = 0;
+  c->h_sp_out[1] = 0;
+  return DSGD_OK;
+}
+static int sp_ensure(dsgd_ctx* c) {
+  if (c->h_sp_out) return DSGD_OK;
+  void* h = nullptr;
+  HIP_TRY(hipHostMalloc(&h, sp_vals_off(c) + sizeof(double) * (size_t)c->dp, hipHostMallocMapped));
+  void* d = nullptr;
+  if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess || hipMalloc(&c->d_sp_state, sizeof(unsigned long long) * (size_t)(SP_STATE_HEAD + sp_tiles(c))) != hipSuccess) {
+    (void)hipHostFree(h);
+    c->d_sp_state = nullptr;
+    return fail(DSGD_ENOMEM, "out of memory (the sparse boundary's buffers)");
+  }
+  c->h_sp_out = static_cast<unsigned long long*>(h);
+  c->d_sp_out = static_cast<unsigned long long*>(d);
+  return sp_reset_state(c);
+}
+// enqueue the compaction of `in` (dp slots; perm == nullptr: already in key order) into the mapped buffer
+template <typename TIn, typename TOut, bool REG>
+static int sp_compact(dsgd_ctx* c, const TIn* in, const int* perm) {
+  DSGD_TRY(sp_ensure(c));
+  const int tiles = sp_tiles(c);
+  if (++c->sp_epoch == 0) c->sp_epoch = 1;
+  char* out = reinterpret_cast<char*>(c->d_sp_out);
+  hipLaunchKernelGGL((dsgd_sparse_compact_kernel<TIn, TOut, REG>), dim3(tiles), dim3(SP_THREADS), 0, c->stream, const_cast<TIn*>(in), perm, c->dp,
+                     c->d_sc, c->d_sp_state, c->sp_launches * (unsigned long long)tiles, c->sp_epoch, reinterpret_cast<int*>(out + 16),
+                     reinterpret_cast<TOut*>(out + sp_vals_off(c)), c->d_sp_out);
+  HIP_TRY(hipGetLastError());
+  ++c->sp_launches;
+  return DSGD_OK;
+}
+// behind the call's synchronisation: the count, and the pairs if they fit (otherwise the outputs stay as they are)
+template <typename T>
+static int sp_deliver(dsgd_ctx* c, int32_t* key_out, T* val_out, int64_t cap, int64_t* nnz_out) {
+  if (c->h_sp_out[1]) {
+    (void)sp_reset_state(c);
+    (void)hipStreamSynchronize(c->stream);
+    return fail(DSGD_ESTATE, "the compaction's scan across its workgroups timed out; nothing was delivered");
+  }
+  const int64_t nnz = (int64_t)c->h_sp_out[0];
+  *nnz_out = nnz;
+  if (nnz > cap) return fail(DSGD_EINVAL, "the Sparse value holds %lld entries, the output arrays %lld", (long long)nnz, (long long)cap);
+  const char* out = reinterpret_cast<const char*>(c->h_sp_out);
+  if (nnz > 0) {
+    memcpy(key_out, out + 16, sizeof(int32_t) * (size_t)nnz);
+    memcpy(val_out, out + sp_vals_off(c), sizeof(T) * (size_t)nnz);
+  }
+  return DSGD_OK;
+}
+static int sp_check_out(const void* key_out, const void* val_out, int64_t cap, const int64_t* nnz_out) {
+  if (!nnz_out || cap < 0 || (cap > 0 && (!key_out || !val_out))) return fail(DSGD_EINVAL, "null output arrays / negative cap");
+  return DSGD_OK;
+}
+// the keys of a Sparse value are host data: checked before anything moves (math/Sparse.scala:61-68 accepts 0..size; a map
+// holds a key once).  nnz < 0 ("the resident weights") passes.
+static int sp_check_keys(dsgd_ctx* c, const int32_t* key, const void* val, int64_t nnz) {
+  if (nnz <= 0) return DSGD_OK;
+  if (!key || !val) return fail(DSGD_EINVAL, "null key / value arrays");
+  for (int64_t i = 0; i < nnz; ++i)
+    if (key[i] < 0 || key[i] >= c->dp) return fail(DSGD_ERANGE, "key %d at position %lld outside [0, %d]", key[i], (long long)i, c->dp - 1);
+  if (nnz > c->dp) return fail(DSGD_EINVAL, "%lld keys for %d slots: a Sparse value has unique keys", (long long)nnz, c->dp);
+  if (c->sp_seen.size() != (size_t)c->dp) c->sp_seen.assign((size_t)c->dp, 0u);
+  if (++c->sp_stamp == 0) {
+    std::fill(c->sp_seen.begin(), c->sp_seen.end(), 0u);
+    c->sp_stamp = 1;
+  }
+  for (int64_t i = 0; i < nnz; ++i) {
+    if (c->sp_seen[(size_t)key[i]] == c->sp_stamp)
+      return fail(DSGD_EINVAL, "key %d repeated at position %lld: a Sparse value has unique keys", key[i], (long long)i);
+    c->sp_seen[(size_t)key[i]] = c->sp_stamp;
+  }
+  return DSGD_OK;
+}
+// w (rank order, dp slots) <- the checked pairs, 0 elsewhere; the caller may reuse its arrays when this returns
+template <typename TIn, typename TW>
+static int sp_scatter(dsgd_ctx* c, const int32_t* key, const TIn* val, int64_t nnz, TW* w) {
+  const size_t voff = (sizeof(int) * (size_t)c->dp + 7) & ~(size_t)7;
+  if (!c->d_sp_in) HIP_TRY(hipMalloc(&c->d_sp_in, voff + sizeof(double) * (size_t)c->dp));
+  if (nnz > 0) {
+    const size_t vo = (sizeof(int) * (size_t)nnz + 7) & ~(size_t)7;
+    DSGD_TRY(pin_acquire(c->pin_sp, vo + sizeof(TIn) * (size_t)nnz));
+    char* p = static_cast<char*>(c->pin_sp.p);
+    memcpy(p, key, sizeof(int) * (size_t)nnz);
+    memcpy(p + vo, val, sizeof(TIn) * (size_t)nnz);
+    HIP_TRY(hipMemcpyAsync(c->d_sp_in, p, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_sp_in + voff, p + vo, sizeof(TIn) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
+    DSGD_TRY(pin_sent(c, c->pin_sp));
+  }
+  const int blocks = std::max(1, std::min(SP_SCATTER_BLOCKS, (c->dp + SP_TILE - 1) / SP_TILE));
+  hipLaunchKernelGGL((dsgd_sparse_scatter_kernel<TIn, TW>), dim3(blocks), dim3(SP_THREADS), 0, c->stream, reinterpret_cast<const int*>(c->d_sp_in),
+                     reinterpret_cast<const TIn*>(c->d_sp_in + voff), (int)std::max<int64_t>(nnz, 0), c->d_perm, w, c->dp);
+  HIP_TRY(hipGetLastError());
+  c->s_dirty = true;
+  return DSGD_OK;
+}
+// An asynchronous step changes the weights, so its delta must fit BEFORE it runs.  The delta's support lies inside the
+// union of the listed rows' columns (the regulariser is support-only, math/Vec.scala:65-75): at most
+// min(D + 1, the listed rows' lengths summed) entries.  The rows are host data: one outside the loaded rows is DSGD_ERANGE here.
+static int sp_async_cap(dsgd_ctx* c, const int32_t* idx, int64_t n, int64_t cap) {
+  long long bound = 0;
+  for (int64_t t = 0; t < n; ++t) {
+    if (idx[t] < 0 || idx[t] >= c->n_rows) return fail(DSGD_ERANGE, "sample index %d outside the %lld loaded rows", idx[t], c->n_rows);
+    if (bound < c->dp) bound += c->row_len[(size_t)idx[t]];
+  }
+  bound = std::min<long long>(bound, c->dp);
+  if (cap < bound)
+    return fail(DSGD_EINVAL, "cap = %lld is below the bound on this step's delta, min(D + 1, the listed rows' lengths summed) = %lld: "
+                             "nothing ran", (long long)cap, bound);
+  return DSGD_OK;
+}
+
 extern "C" {
 
 int dsgd_abi_version(void) { return DSGD_ABI_VERSION; }
@@ -3210,6 +3342,10 @@ int dsgd_destroy(dsgd_ctx* c) {
   (void)hipFree(c->d_rp64_gath);
   (void)hipFree(c->d_rp64_gsegs);
   if (c->h_rp64_ranks) (void)hipHostFree(c->h_rp64_ranks);
+  if (c->h_sp_out) (void)hipHostFree(c->h_sp_out);
+  (void)hipFree(c->d_sp_state);
+  (void)hipFree(c->d_sp_in);
+  pin_free(c->pin_sp);
   (void)hipFree(c->d_g);
   (void)hipFree(c->d_g64);
   (void)hipFree(c->d_gsum);
@@ -3386,6 +3522,8 @@ int dsgd_load_csr(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in, const 
   }
   HIP_TRY(hipMemcpy(c->d_label, label, (size_t)n_rows, hipMemcpyHostToDevice));
   c->n_rows = n_rows;
+  c->row_len.resize((size_t)n_rows);
+  for (int64_t i = 0; i < n_rows; ++i) c->row_len[(size_t)i] = (int32_t)std::min<int64_t>(row_ptr_in[i + 1] - row_ptr_in[i], c->dp);
   c->nnz = nnz;
   {
     int e = 0;
@@ -4580,22 +4718,31 @@ int dsgd_plan_run_async_f64(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64
   return plan_run64(c, p, step_begin, step_end, lr, true, nullptr);
 }
 
-int dsgd_async_step_f64(dsgd_ctx* c, const int32_t* idx, int64_t n, double lr, double* delta_out, dsgd_batch_stats* stats) {
+// dsgd_async_step_f64 (sparse_cap < 0: the delta dense into delta_out, which may be NULL) and dsgd_async_step_sparse_f64
+// (sparse_cap >= 0: the delta compacted into the mapped buffer, for sp_deliver behind the call's synchronisation)
+static int async_step64(dsgd_ctx* c, const char* what, const int32_t* idx, int64_t n, double lr, double* delta_out, int64_t sparse_cap,
+                        int32_t* sp_key, double* sp_val, int64_t* sp_nnz, dsgd_batch_stats* stats) {
   DSGD_TRY(check_ctx(c));
   if (n <= 0 || !idx) return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors");
   std::lock_guard<std::mutex> lk(c->mu);
-  DSGD_TRY(require_fp64(c, "dsgd_async_step_f64"));
-  DSGD_TRY(refuse_fp64_comm(c, "dsgd_async_step_f64"));
+  DSGD_TRY(require_fp64(c, what));
+  DSGD_TRY(refuse_fp64_comm(c, what));
   DSGD_TRY(bind(c, true));
   DSGD_TRY(require_data(c));
   DSGD_TRY(require_ds(c));
   DSGD_TRY(require_sync_mode(c));
   DSGD_TRY(prepare_layout(c));
+  const bool sparse = sparse_cap >= 0;
+  const bool want_delta = delta_out || sparse;
   for (int64_t t = 0; t < n; ++t)
     if (idx[t] < 0 || idx[t] >= c->n_rows) return fail(DSGD_ERANGE, "sample index %d outside the %lld loaded rows", idx[t], c->n_rows);
   // a one-step, one-worker plan: created, run and given back here (as sync_step64)
   const int64_t offsets[2] = {0, n};
   dsgd_plan* p = nullptr;
+  if (sparse) {
+    DSGD_TRY(sp_async_cap(c, idx, n, sparse_cap));   // (before anything runs: a delta is never lost)
+    DSGD_TRY(sp_ensure(c));
+  }
   DSGD_TRY(plan_frame(c, offsets, 1, 1, &p));
   p->h_idx.assign(idx, idx + n);
   hipError_t e = hipMemcpyAsync(p->d_idx, p->h_idx.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->build_stream);
@@ -4607,13 +4754,13 @@ int dsgd_async_step_f64(dsgd_ctx* c, const int32_t* idx, int64_t n, double lr, d
   DSGD_TRY(plan_finish(c, p, &p));
   const int Sp = cs64_sp(c->dp);
   int rc = DSGD_OK;
-  if (delta_out && !c->d_cs_dl64 && hipMalloc(&c->d_cs_dl64, sizeof(double) * ((size_t)CS64_G * Sp + (size_t)c->dp)) != hipSuccess)
+  if (want_delta && !c->d_cs_dl64 && hipMalloc(&c->d_cs_dl64, sizeof(double) * ((size_t)CS64_G * Sp + (size_t)c->dp)) != hipSuccess)
     rc = fail(DSGD_ENOMEM, "out of device memory (the delta of an async step)");
-  if (rc == DSGD_OK && delta_out && hipMemsetAsync(c->d_cs_dl64, 0, sizeof(double) * (size_t)CS64_G * Sp, c->stream) != hipSuccess)
+  if (rc == DSGD_OK && want_delta && hipMemsetAsync(c->d_cs_dl64, 0, sizeof(double) * (size_t)CS64_G * Sp, c->stream) != hipSuccess)
     rc = fail(DSGD_EHIP, "hipMemsetAsync");
   if (rc == DSGD_OK) rc = reset_counters(c);
   if (rc == DSGD_OK) {
-    rc = plan_run64(c, p, 0, 1, lr, true, delta_out ? c->d_cs_dl64 : nullptr);
+    rc = plan_run64(c, p, 0, 1, lr, true, want_delta ? c->d_cs_dl64 : nullptr);
     if (rc == DSGD_OK) c->pending_samples -= n;   // (a request reports its own samples, below)
   }
   if (p->built_pending) (void)hipStreamWaitEvent(c->stream, p->built_ev, 0);
@@ -4623,15 +4770,33 @@ int dsgd_async_step_f64(dsgd_ctx* c, const int32_t* idx, int64_t n, double lr, d
   if (p->built_ev) (void)hipEventDestroy(p->built_ev);
   delete p;
   DSGD_TRY(rc);
+  double* rank = want_delta ? c->d_cs_dl64 + (size_t)CS64_G * Sp : nullptr;
+  if (sparse) {   // slice-major -> rank order -> the pairs, all in front of the call's synchronisation
+    hipLaunchKernelGGL(dsgd_cs64_unslice_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, c->d_cs_dl64, rank, c->dp, Sp);
+    HIP_TRY(hipGetLastError());
+    DSGD_TRY((sp_compact<double, double, false>(c, rank, c->d_perm)));
+  }
   DSGD_TRY(finish_stats(c, stats, n));
   if (delta_out) {   // slice-major -> rank order -> key order
-    double* rank = c->d_cs_dl64 + (size_t)CS64_G * Sp;
     hipLaunchKernelGGL(dsgd_cs64_unslice_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, c->d_cs_dl64, rank, c->dp, Sp);
     HIP_TRY(hipGetLastError());
     DSGD_TRY(take64(c, rank, delta_out));
   }
+  if (sparse) return sp_deliver<double>(c, sp_key, sp_val, sparse_cap, sp_nnz);
   return DSGD_OK;
 }
+
+int dsgd_async_step_f64(dsgd_ctx* c, const int32_t* idx, int64_t n, double lr, double* delta_out, dsgd_batch_stats* stats) {
+  return async_step64(c, "dsgd_async_step_f64", idx, n, lr, delta_out, -1, nullptr, nullptr, nullptr, stats);
+}
+
+int dsgd_async_step_sparse_f64(dsgd_ctx* c, const int32_t* idx, int64_t n, double lr, int32_t* d_key, double* d_val, int64_t cap,
+                               int64_t* d_nnz, dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  DSGD_TRY(sp_check_out(d_key, d_val, cap, d_nnz));
+  return async_step64(c, "dsgd_async_step_sparse_f64", idx, n, lr, nullptr, cap, d_key, d_val, d_nnz, stats);
+}
+
 
 int dsgd_update_grad_f64(dsgd_ctx* c, const int32_t* key, const double* dv, int64_t nnz) {
   DSGD_TRY(check_ctx(c));
@@ -5193,6 +5358,150 @@ int dsgd_update_grad(dsgd_ctx* c, const int32_t* key, const float* dv, int64_t n
   c->s_dirty = true;
   HIP_TRY(hipStreamSynchronize(st));   // the update is applied when the call returns (the RPC's Ack, proto.proto:40)
   return DSGD_OK;
+}
+
+
+// ---- the Sparse forms (include/dsgd.h "SPARSE VALUES"): the dense twins' kernels, state rules and errors ----
+int dsgd_set_weights_sparse(dsgd_ctx* c, const int32_t* key, const float* val, int64_t nnz) {
+  DSGD_TRY(check_ctx(c));
+  if (nnz < 0 || (nnz > 0 && (!key || !val))) return fail(DSGD_EINVAL, "null key / value arrays or negative nnz");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(sp_check_keys(c, key, val, nnz));
+  DSGD_TRY(bind(c));
+  DSGD_TRY(require_sync_mode(c));
+  if (c->fp64) return sp_scatter<float, double>(c, key, val, nnz, c->d_w64);   // (promoted, as dsgd_set_weights)
+  return sp_scatter<float, float>(c, key, val, nnz, c->d_w);
+}
+
+int dsgd_set_weights_sparse_f64(dsgd_ctx* c, const int32_t* key, const double* val, int64_t nnz) {
+  DSGD_TRY(check_ctx(c));
+  if (nnz < 0 || (nnz > 0 && (!key || !val))) return fail(DSGD_EINVAL, "null key / value arrays or negative nnz");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_set_weights_sparse_f64"));
+  DSGD_TRY(sp_check_keys(c, key, val, nnz));
+  DSGD_TRY(bind(c));
+  DSGD_TRY(require_sync_mode(c));
+  return sp_scatter<double, double>(c, key, val, nnz, c->d_w64);
+}
+
+int dsgd_get_weights_sparse(dsgd_ctx* c, int32_t* key_out, float* val_out, int64_t cap, int64_t* nnz_out) {
+  DSGD_TRY(check_ctx(c));
+  DSGD_TRY(sp_check_out(key_out, val_out, cap, nnz_out));
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(bind(c));
+  if (c->fp64)   // (the fp64 weights rounded, as dsgd_get_weights)
+    DSGD_TRY((sp_compact<double, float, false>(c, c->d_w64, c->d_perm)));
+  else
+    DSGD_TRY((sp_compact<float, float, false>(c, c->d_w, c->d_perm)));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return sp_deliver<float>(c, key_out, val_out, cap, nnz_out);
+}
+
+int dsgd_get_weights_sparse_f64(dsgd_ctx* c, int32_t* key_out, double* val_out, int64_t cap, int64_t* nnz_out) {
+  DSGD_TRY(check_ctx(c));
+  DSGD_TRY(sp_check_out(key_out, val_out, cap, nnz_out));
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_get_weights_sparse_f64"));
+  DSGD_TRY(bind(c));
+  DSGD_TRY((sp_compact<double, double, false>(c, c->d_w64, c->d_perm)));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return sp_deliver<double>(c, key_out, val_out, cap, nnz_out);
+}
+
+int dsgd_gradient_sparse(dsgd_ctx* c, const int32_t* w_key, const float* w_val, int64_t w_nnz, const int32_t* idx, int64_t n, int32_t* g_key,
+                         float* g_val, int64_t cap, int64_t* g_nnz, dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  DSGD_TRY(refuse_fp64(c, "dsgd_gradient_sparse"));
+  DSGD_TRY(sp_check_out(g_key, g_val, cap, g_nnz));
+  if (n <= 0 || !idx) return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors");  // ref: math/Vec.scala:129
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(sp_check_keys(c, w_key, w_val, w_nnz));
+  DSGD_TRY(bind(c));
+  DSGD_TRY(require_data(c));
+  DSGD_TRY(require_ds(c));
+  DSGD_TRY(require_sync_mode(c));
+  DSGD_TRY(prepare_layout(c));
+  DSGD_TRY(sp_ensure(c));
+  if (w_nnz >= 0) DSGD_TRY((sp_scatter<float, float>(c, w_key, w_val, w_nnz, c->d_w)));
+  DSGD_TRY(ensure_s(c));
+  DSGD_TRY(reset_counters(c));
+  long long mx = 0, tot = 0;
+  const int64_t nn = n;
+  DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
+  DSGD_TRY(launch_grad(c, c->cur_idx, c->d_segs, 1, mx));
+  // ONE launch in place of dsgd_regularize_kernel + permute-out + memset: the support-only regulariser on the way, d_g cleared
+  DSGD_TRY((sp_compact<float, float, true>(c, c->d_g, c->d_perm)));
+  DSGD_TRY(read_scalars(c));   // the one synchronisation of the call
+  DSGD_TRY(prof_collect(c));
+  DSGD_TRY(check_err_flag(c));
+  DSGD_TRY(sp_deliver<float>(c, g_key, g_val, cap, g_nnz));
+  if (stats) {
+    stats->n_samples = n;
+    stats->n_active = (int64_t)c->h_sc->n_active;
+  }
+  return DSGD_OK;
+}
+
+int dsgd_gradient_sparse_f64(dsgd_ctx* c, const int32_t* w_key, const double* w_val, int64_t w_nnz, const int32_t* idx, int64_t n,
+                             int32_t* g_key, double* g_val, int64_t cap, int64_t* g_nnz, dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  DSGD_TRY(sp_check_out(g_key, g_val, cap, g_nnz));
+  if (n <= 0 || !idx) return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors");  // ref: math/Vec.scala:129
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_gradient_sparse_f64"));
+  DSGD_TRY(sp_check_keys(c, w_key, w_val, w_nnz));
+  DSGD_TRY(bind(c, w_nnz < 0));   // (the request's weights replace the resident ones: rank order then)
+  DSGD_TRY(require_data(c));
+  DSGD_TRY(require_ds(c));
+  DSGD_TRY(require_sync_mode(c));
+  DSGD_TRY(prepare_layout(c));
+  const int64_t nn = n;
+  DSGD_TRY(rp64_check_lists(c, &idx, &nn, 1));
+  DSGD_TRY(sp_ensure(c));
+  if (w_nnz >= 0) DSGD_TRY((sp_scatter<double, double>(c, w_key, w_val, w_nnz, c->d_w64)));
+  DSGD_TRY(rp64_ensure(c, 1));
+  DSGD_TRY(reset_counters(c));
+  long long mx = 0, tot = 0;
+  DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
+  DSGD_TRY(rp64_launch(c, 1, mx, false, 0.0));
+  DSGD_TRY((sp_compact<double, double, false>(c, c->d_rp64_g, nullptr)));   // (the finish leaves the gradient in key order)
+  DSGD_TRY(read_scalars(c));   // the one synchronisation of the call
+  DSGD_TRY(check_err_flag(c));
+  DSGD_TRY(sp_deliver<double>(c, g_key, g_val, cap, g_nnz));
+  if (stats) {
+    stats->n_samples = n;
+    stats->n_active = (int64_t)c->h_sc->n_active;
+  }
+  return DSGD_OK;
+}
+
+int dsgd_async_step_sparse(dsgd_ctx* c, const int32_t* idx, int64_t n, float lr, int32_t* d_key, float* d_val, int64_t cap, int64_t* d_nnz,
+                           dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  DSGD_TRY(refuse_fp64(c, "dsgd_async_step_sparse"));
+  DSGD_TRY(sp_check_out(d_key, d_val, cap, d_nnz));
+  if (n <= 0 || !idx) return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(bind(c));
+  DSGD_TRY(require_data(c));
+  DSGD_TRY(require_ds(c));
+  DSGD_TRY(require_sync_mode(c));
+  DSGD_TRY(sp_async_cap(c, idx, n, cap));   // (before anything runs: a delta is never lost)
+  DSGD_TRY(prepare_layout(c));
+  DSGD_TRY(sp_ensure(c));
+  DSGD_TRY(ensure_s(c));
+  DSGD_TRY(reset_counters(c));
+  long long mx = 0, tot = 0;
+  const int64_t nn = n;
+  DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
+  DSGD_TRY(launch_grad(c, c->cur_idx, c->d_segs, 1, mx));
+  hipLaunchKernelGGL(dsgd_async_finish_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_w, c->d_g, c->dp, c->d_ds, (float)n, lr,
+                     (float)c->cfg.lambda, c->d_tmp, c->d_sc);
+  HIP_TRY(hipGetLastError());
+  c->s_dirty = false;
+  DSGD_TRY((sp_compact<float, float, false>(c, c->d_tmp, c->d_perm)));
+  DSGD_TRY(finish_stats(c, stats, tot));
+  return sp_deliver<float>(c, d_key, d_val, cap, d_nnz);
 }
 
 // ---- Hogwild persistent engine -------------------------------------------------------------------------

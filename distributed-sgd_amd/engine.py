@@ -325,6 +325,64 @@ class Engine:
             return
         check(self._lib.dsgd_update_grad(self._ctx, ptr(keys), ptr(values), C.c_int64(len(keys))))
 
+    # -- Sparse values at the boundary (include/dsgd.h "SPARSE VALUES") ------------------------------
+    # The reference's Sparse{map, size} as parallel arrays: int32 keys (ascending on the way out) and values of the
+    # engine's precision.  Results, statistics, state rules and errors are the dense twins'; the engine's precision picks
+    # the ABI form, as update_grad does.
+    def _sparse_out(self):
+        if getattr(self, "_sp_keys", None) is None:   # D + 1 slots of scratch, once per engine: always enough room
+            self._sp_keys = np.zeros(self.dp, dtype=np.int32)
+            self._sp_vals = np.zeros(self.dp, dtype=np.float64 if self.fp64 else np.float32)
+        return self._sp_keys, self._sp_vals
+
+    def _sparse_in(self, pairs):
+        keys, vals = pairs
+        keys = i32(keys)
+        vals = f64(vals) if self.fp64 else f32(vals)
+        if keys.ndim != 1 or keys.shape != vals.shape:
+            raise ValueError("keys / values length mismatch")
+        return keys, vals
+
+    def set_weights_sparse(self, keys, vals):
+        keys, vals = self._sparse_in((keys, vals))
+        fn = self._lib.dsgd_set_weights_sparse_f64 if self.fp64 else self._lib.dsgd_set_weights_sparse
+        check(fn(self._ctx, ptr(keys), ptr(vals), C.c_int64(len(keys))))
+
+    def get_weights_sparse(self):
+        """The resident weights as (keys ascending, values): the entries with abs(v) > 1e-20."""
+        k, v = self._sparse_out()
+        nnz = C.c_int64(0)
+        fn = self._lib.dsgd_get_weights_sparse_f64 if self.fp64 else self._lib.dsgd_get_weights_sparse
+        check(fn(self._ctx, ptr(k), ptr(v), C.c_int64(self.dp), C.byref(nnz)))
+        return k[:nnz.value].copy(), v[:nnz.value].copy()
+
+    def gradient_sparse(self, idx, w=None):
+        """SlaveImpl.gradient with Sparse in and out: (keys, vals, stats).  w: None (the resident weights) or a
+        (keys, vals) pair, which then replaces them."""
+        idx = i32(idx)
+        wk, wv, wn = (None, None, -1) if w is None else (*self._sparse_in(w), len(w[0]))
+        k, v = self._sparse_out()
+        nnz = C.c_int64(0)
+        st = BatchStats()
+        fn = self._lib.dsgd_gradient_sparse_f64 if self.fp64 else self._lib.dsgd_gradient_sparse
+        check(fn(self._ctx, ptr(wk), ptr(wv), C.c_int64(wn), ptr(idx), C.c_int64(len(idx)), ptr(k), ptr(v), C.c_int64(self.dp),
+                 C.byref(nnz), C.byref(st)))
+        return k[:nnz.value].copy(), v[:nnz.value].copy(), {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def async_step_sparse(self, idx, lr):
+        """One iteration of Slave.asyncTask; the delta it gossips as (keys, vals, stats)."""
+        idx = i32(idx)
+        k, v = self._sparse_out()
+        nnz = C.c_int64(0)
+        st = BatchStats()
+        if self.fp64:
+            check(self._lib.dsgd_async_step_sparse_f64(self._ctx, ptr(idx), C.c_int64(len(idx)), C.c_double(lr), ptr(k), ptr(v),
+                                                       C.c_int64(self.dp), C.byref(nnz), C.byref(st)))
+        else:
+            check(self._lib.dsgd_async_step_sparse(self._ctx, ptr(idx), C.c_int64(len(idx)), C.c_float(lr), ptr(k), ptr(v),
+                                                   C.c_int64(self.dp), C.byref(nnz), C.byref(st)))
+        return k[:nnz.value].copy(), v[:nnz.value].copy(), {"n_samples": st.n_samples, "n_active": st.n_active}
+
     def async_plan(self, assigned_ranges, batch, seed=0, positional_bug=True, first_update=0, n_updates=1):
         """fp64 engines: updates [first_update, first_update + n_updates) of the zero-lag asynchronous schedule as a
         one-worker plan whose lists the device draws (dsgd_async_plan_create): update u is worker u mod K at its

@@ -18,7 +18,9 @@ programmatically and the field numbers, types and method paths below ARE the pro
 The backend is anything with the Engine surface used below (`gradient(idx, w)`, `forward(idx, w)`,
 `async_step(idx, lr, want_delta)`, `update_grad(keys, values)`, `set_weights`, `get_weights`, `dp`): the HIP engine
 on a GPU box, the oracle-backed stand-in in the CPU tests.  Vectors cross the wire as the reference sends them
-(sparse fp64 maps keyed by feature id); the engine side is dense fp32 indexed by key.
+(sparse fp64 maps keyed by feature id); the engine side is dense fp32 indexed by key.  A backend that also has the
+sparse calls (`gradient_sparse(idx, (keys, vals))`, `async_step_sparse(idx, lr)`, `set_weights_sparse(keys, vals)`: the
+HIP engine) is handed the map's pairs and returns pairs -- no dense vector is built or scanned on this side.
 """
 
 from __future__ import annotations
@@ -127,6 +129,25 @@ def from_sparse(sparse, dp: int, dtype=np.float32) -> np.ndarray:
             raise IndexError("key %d outside [0, %d)" % (k, dp))
         w[k] = v
     return w
+
+
+def sparse_from_pairs(keys, vals, size: int):
+    """(keys, values) as a backend's sparse calls return them -> Sparse{map, size}, filled with ONE map.update: the backend
+    has dropped abs(v) <= 1e-20 already (math/Sparse.scala:108-118), nothing of D + 1 slots is scanned here."""
+    out = messages()["Sparse"]()
+    out.size = size
+    out.map.update(zip(np.asarray(keys).tolist(), np.asarray(vals).tolist()))
+    return out
+
+
+def pairs_from_sparse(sparse, dp: int, dtype=np.float32) -> Tuple[np.ndarray, np.ndarray]:
+    """Sparse -> (int32 keys, values of dtype) for a backend's sparse calls, with from_sparse's range check."""
+    n = len(sparse.map)
+    keys = np.fromiter(sparse.map.keys(), dtype=np.int64, count=n)
+    bad = keys[(keys < 0) | (keys >= dp)]
+    if len(bad):
+        raise IndexError("key %d outside [0, %d)" % (int(bad[0]), dp))
+    return keys.astype(np.int32), np.fromiter(sparse.map.values(), dtype=dtype, count=n)
 
 
 # ---- stubs ---------------------------------------------------------------------------------------------------------
@@ -239,11 +260,18 @@ class SlaveWorker:
 
     def _rpc_Gradient(self, request):  # :142-157
         fp64 = self._fp64
-        w = from_sparse(request.weights, self.dp, np.float64 if fp64 else np.float32)
+        sparse = hasattr(self.backend, "gradient_sparse")
+        if sparse:
+            w = pairs_from_sparse(request.weights, self.dp, np.float64 if fp64 else np.float32)
+        else:
+            w = from_sparse(request.weights, self.dp, np.float64 if fp64 else np.float32)
         idx = np.asarray(request.samples, dtype=np.int32)
         if len(idx) == 0:
             raise ValueError("requirement failed: Vec.sum of an empty batch (math/Vec.scala:129)")
         self.metrics.counter("slave.sync.backward", len(idx))
+        if sparse:   # (the engine's precision picks the form; the pairs go into the reply as they come)
+            keys, vals, _ = self.backend.gradient_sparse(idx, w)
+            return messages()["GradUpdate"](gradUpdate=sparse_from_pairs(keys, vals, self.size))
         g, _ = self.backend.gradient_f64(idx, w) if fp64 else self.backend.gradient(idx, w)
         return messages()["GradUpdate"](gradUpdate=to_sparse(g, self.size))
 
@@ -252,7 +280,10 @@ class SlaveWorker:
             raise ValueError("requirement failed: Cannot initialize async computation: slave is in synchronous mode.")
         if self.running_async:
             raise ValueError("requirement failed: Async computation already running, can't be initialized unless stopped first")
-        self.backend.set_weights(from_sparse(request.weights, self.dp))
+        if hasattr(self.backend, "set_weights_sparse"):   # (float32 values, as the dense path hands over)
+            self.backend.set_weights_sparse(*pairs_from_sparse(request.weights, self.dp))
+        else:
+            self.backend.set_weights(from_sparse(request.weights, self.dp))
         self.assigned = np.asarray(request.samples, dtype=np.int32)
         self.batch_size, self.learning_rate = int(request.batchSize), float(request.learningRate)
         self.running_async = True
@@ -290,12 +321,17 @@ class SlaveWorker:
     def _async_task(self):
         GradUpdate = messages()["GradUpdate"]
         pending: list = []
+        sparse = hasattr(self.backend, "async_step_sparse")
         try:
             while self.running_async:
                 idx = self._sample()
                 self.metrics.counter("slave.async.backward", len(idx))
-                delta, _ = self.backend.async_step(idx, self.learning_rate, want_delta=True)
-                update = GradUpdate(gradUpdate=to_sparse(delta, self.size))
+                if sparse:
+                    keys, vals, _ = self.backend.async_step_sparse(idx, self.learning_rate)
+                    update = GradUpdate(gradUpdate=sparse_from_pairs(keys, vals, self.size))
+                else:
+                    delta, _ = self.backend.async_step(idx, self.learning_rate, want_delta=True)
+                    update = GradUpdate(gradUpdate=to_sparse(delta, self.size))
                 with self.lock:
                     others = list(self.others.values())
                 # otherSlaves.values.foreach(_.updateGrad(...)); masterStub.updateGrad(...): fire and forget.  (A grpc

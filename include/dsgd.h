@@ -359,6 +359,44 @@ int dsgd_async_plan_create(dsgd_ctx* ctx, const int64_t* assigned_begin, const i
                            dsgd_plan** out);
 int dsgd_plan_run_async_f64(dsgd_ctx* ctx, dsgd_plan* plan, int64_t step_begin, int64_t step_end, double lr);
 
+/* ---- SPARSE VALUES at the boundary (csrc/dsgd_sparse.hpp) --------------------------------------
+ * The reference exchanges Sparse{map<int32, double>, size} values only (proto.proto:28-31) and stores no entry with
+ * abs(v) <= 1e-20 (math/Sparse.scala:104-118).  These forms take and return exactly that -- parallel arrays of keys and
+ * values -- so that no caller builds, copies or scans D + 1 slots.  Each is its dense twin (dsgd_set_weights /
+ * dsgd_get_weights / dsgd_gradient / dsgd_async_step and their _f64 forms) in results, side effects, statistics, state
+ * rules and errors: the same kernels compute the gradient, the values are bit for bit the twin's.
+ *   Output: the pairs with |(double)v| > 1e-20, keys ASCENDING, *nnz_out of them (-0.0, 0.0 and anything at or under the
+ *   threshold are dropped).  cap is the room in the two output arrays.  cap too small in a PURE form
+ *   (dsgd_get_weights_sparse*, dsgd_gradient_sparse*): DSGD_EINVAL, *nnz_out = the count needed, the arrays untouched --
+ *   call again.  dsgd_async_step_sparse* change the weights, so a delta must never be lost: they are refused with
+ *   DSGD_EINVAL BEFORE anything runs unless cap >= min(D + 1, the listed rows' lengths summed) -- the delta's support lies
+ *   inside the union of the listed rows' columns (the regulariser is support-only, math/Vec.scala:65-75).  cap = D + 1
+ *   always qualifies.
+ *   Input: nnz pairs, every key once and inside [0, D], in any order; nnz == 0 is the zero vector.  The keys are checked on
+ *   the host before anything moves: a key outside [0, D] DSGD_ERANGE, a repeated key DSGD_EINVAL, the weights unchanged.
+ *   fp32 values are stored as dsgd_set_weights stores them, fp64 values as dsgd_set_weights_f64 does (both drop
+ *   abs(v) <= 1e-20).  w_nnz < 0 in the gradient forms: the resident weights (no transfer).
+ *   Precision: the float forms behave on an fp64 context as their twins do (dsgd_set_weights_sparse promotes,
+ *   dsgd_get_weights_sparse rounds, dsgd_gradient_sparse and dsgd_async_step_sparse DSGD_EUNSUPPORTED); the _f64 forms
+ *   return DSGD_ESTATE on an fp32 context.  While the lock-free engine runs they are refused where their twins are
+ *   (dsgd_get_weights_sparse stays allowed).  One host synchronisation per call, as the twins have.                  */
+/* w <- the Sparse value {key -> val}, 0 elsewhere (GradientRequest.weights / StartAsyncRequest.weights, proto.proto:51-70) */
+int dsgd_set_weights_sparse(dsgd_ctx* ctx, const int32_t* key, const float* val, int64_t nnz);
+int dsgd_set_weights_sparse_f64(dsgd_ctx* ctx, const int32_t* key, const double* val, int64_t nnz);
+/* the resident weights as a Sparse value, keys ascending (GradState.grad, core/ml/GradState.scala:6-10) */
+int dsgd_get_weights_sparse(dsgd_ctx* ctx, int32_t* key_out, float* val_out, int64_t cap, int64_t* nnz_out);
+int dsgd_get_weights_sparse_f64(dsgd_ctx* ctx, int32_t* key_out, double* val_out, int64_t cap, int64_t* nnz_out);
+/* SlaveImpl.gradient (core/Slave.scala:142-157) with Sparse in and out.  w_nnz < 0: the resident weights. */
+int dsgd_gradient_sparse(dsgd_ctx* ctx, const int32_t* w_key, const float* w_val, int64_t w_nnz, const int32_t* idx, int64_t n,
+                         int32_t* g_key, float* g_val, int64_t cap, int64_t* g_nnz, dsgd_batch_stats* stats /* may be NULL */);
+int dsgd_gradient_sparse_f64(dsgd_ctx* ctx, const int32_t* w_key, const double* w_val, int64_t w_nnz, const int32_t* idx, int64_t n,
+                             int32_t* g_key, double* g_val, int64_t cap, int64_t* g_nnz, dsgd_batch_stats* stats /* may be NULL */);
+/* one iteration of Slave.asyncTask (core/Slave.scala:92-105) with the delta it gossips as a Sparse value */
+int dsgd_async_step_sparse(dsgd_ctx* ctx, const int32_t* idx, int64_t n, float lr, int32_t* d_key, float* d_val, int64_t cap,
+                           int64_t* d_nnz, dsgd_batch_stats* stats /* may be NULL */);
+int dsgd_async_step_sparse_f64(dsgd_ctx* ctx, const int32_t* idx, int64_t n, double lr, int32_t* d_key, double* d_val, int64_t cap,
+                               int64_t* d_nnz, dsgd_batch_stats* stats /* may be NULL */);
+
 /* SlaveImpl.startAsync (core/Slave.scala:159-175) for n_workers lock-free workers sharing ONE
  * device-resident weight vector: every worker (a workgroup) loops
  *   draw `batch` of its assigned rows -> mean gated gradient on a snapshot -> regularize ->

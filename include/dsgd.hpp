@@ -202,6 +202,41 @@ class SparseSVM {
     check(dsgd_gradient(ctx_, w.data(), samplesIdx.data(), (int64_t)samplesIdx.size(), g.data(), stats));
     return g;
   }
+  // ---- Sparse values (dsgd.h "SPARSE VALUES"): the reference's Sparse{map, size} as (keys, values), keys ascending on the
+  //      way out; results, statistics and errors are the dense methods'.  The scratch of D + 1 slots is the model's own.
+  struct SparseVec {
+    std::vector<int32_t> keys;
+    std::vector<float> values;
+  };
+  // `w == nullptr`: the resident weights
+  SparseVec gradientSparse(const SparseVec* w, const std::vector<int32_t>& samplesIdx, dsgd_batch_stats* stats = nullptr) {
+    if (w && w->keys.size() != w->values.size()) throw IllegalArgumentException("requirement failed");
+    if (samplesIdx.empty()) throw IllegalArgumentException("requirement failed");  // Vec.sum of nothing (math/Vec.scala:129)
+    int64_t nnz = 0;
+    scratch();
+    check(dsgd_gradient_sparse(ctx_, w ? w->keys.data() : nullptr, w ? w->values.data() : nullptr, w ? (int64_t)w->keys.size() : -1,
+                               samplesIdx.data(), (int64_t)samplesIdx.size(), spKeys_.data(), spVals_.data(), (int64_t)d_ + 1, &nnz, stats));
+    return taken(nnz);
+  }
+  // one iteration of Slave.asyncTask (core/Slave.scala:92-105); returns the delta it gossips
+  SparseVec asyncStepSparse(const std::vector<int32_t>& samplesIdx, float learningRate, dsgd_batch_stats* stats = nullptr) {
+    if (samplesIdx.empty()) throw IllegalArgumentException("requirement failed");
+    int64_t nnz = 0;
+    scratch();
+    check(dsgd_async_step_sparse(ctx_, samplesIdx.data(), (int64_t)samplesIdx.size(), learningRate, spKeys_.data(), spVals_.data(),
+                                 (int64_t)d_ + 1, &nnz, stats));
+    return taken(nnz);
+  }
+  void setWeightsSparse(const SparseVec& w) {
+    if (w.keys.size() != w.values.size()) throw IllegalArgumentException("requirement failed");
+    check(dsgd_set_weights_sparse(ctx_, w.keys.data(), w.values.data(), (int64_t)w.keys.size()));
+  }
+  SparseVec getWeightsSparse() {
+    int64_t nnz = 0;
+    scratch();
+    check(dsgd_get_weights_sparse(ctx_, spKeys_.data(), spVals_.data(), (int64_t)d_ + 1, &nnz));
+    return taken(nnz);
+  }
   // loss(w, samples) = lambda |w|^2 + mean hinge of the predictions; accuracy = mean [pred == y]   (:16-23)
   double loss(const Vec& w, int64_t rowBegin, int64_t rowEnd) {
     requireSize(w);
@@ -220,6 +255,17 @@ class SparseSVM {
   void requireSize(const Vec& v) const {
     if ((int)v.size() != d_ + 1) throw IllegalArgumentException("requirement failed: Can't perform operation: vectors have different sizes");
   }
+  void scratch() {
+    if (spKeys_.empty()) {
+      spKeys_.resize((size_t)d_ + 1);
+      spVals_.resize((size_t)d_ + 1);
+    }
+  }
+  SparseVec taken(int64_t nnz) const {
+    return SparseVec{std::vector<int32_t>(spKeys_.begin(), spKeys_.begin() + nnz), std::vector<float>(spVals_.begin(), spVals_.begin() + nnz)};
+  }
+  std::vector<int32_t> spKeys_;
+  std::vector<float> spVals_;
   double lambda_;
   int d_;
   int64_t nRows_ = 0;

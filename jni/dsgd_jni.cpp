@@ -22,6 +22,9 @@
 // (math/Sparse.scala:63), everything else -> RuntimeException.
 #include <jni.h>
 
+#include <map>
+#include <memory>
+#include <mutex>
 #include <vector>
 
 #include "dsgd.h"
@@ -61,6 +64,154 @@ DSGD_ELEMS(Float, jfloat, jfloatArray)
 DSGD_ELEMS(Byte, jbyte, jbyteArray)
 DSGD_ELEMS(Double, jdouble, jdoubleArray)
 #undef DSGD_ELEMS
+
+// Sparse values (include/dsgd.h "SPARSE VALUES"): per context, native scratch of D + 1 slots the library compacts into, so
+// that the JVM never allocates or scans D + 1 slots.  A sparse native leaves its pairs here and returns their count; the
+// caller allocates two arrays of exactly that length and collects them with takeSparse / takeSparseF64 (HipSVM holds its
+// monitor across the two calls).
+struct SparseScratch {
+  std::mutex mu;
+  int64_t dp = 0;
+  std::vector<int32_t> keys;
+  std::vector<double> vals;   // 8-byte slots: floats or doubles
+  int64_t nnz = 0;
+  bool f64 = false;
+};
+std::mutex g_scratch_mu;
+std::map<jlong, std::shared_ptr<SparseScratch>> g_scratch;
+void scratch_add(jlong h, jint nFeatures) {
+  auto s = std::make_shared<SparseScratch>();
+  s->dp = static_cast<int64_t>(nFeatures) + 1;
+  std::lock_guard<std::mutex> lk(g_scratch_mu);
+  g_scratch[h] = s;
+}
+void scratch_drop(jlong h) {
+  std::lock_guard<std::mutex> lk(g_scratch_mu);
+  g_scratch.erase(h);
+}
+std::shared_ptr<SparseScratch> scratch_of(JNIEnv* env, jlong h) {
+  std::shared_ptr<SparseScratch> s;
+  {
+    std::lock_guard<std::mutex> lk(g_scratch_mu);
+    auto it = g_scratch.find(h);
+    if (it != g_scratch.end()) s = it->second;
+  }
+  if (!s) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "not a context of this shim (create / createF64)");
+    return s;
+  }
+  if (s->keys.empty()) {
+    s->keys.resize(static_cast<size_t>(s->dp));
+    s->vals.resize(static_cast<size_t>(s->dp));
+  }
+  return s;
+}
+bool null_array(JNIEnv* env) {
+  env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "null array");
+  return true;
+}
+bool pair_mismatch(JNIEnv* env, jarray keys, jarray vals) {   // both null (the resident weights) or both of one length
+  if ((keys == nullptr) != (vals == nullptr) || (keys && env->GetArrayLength(keys) != env->GetArrayLength(vals))) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "keys / values: both null or of one length");
+    return true;
+  }
+  return false;
+}
+void set_region(JNIEnv* env, jfloatArray a, jsize n, const jfloat* p) { env->SetFloatArrayRegion(a, 0, n, p); }
+void set_region(JNIEnv* env, jdoubleArray a, jsize n, const jdouble* p) { env->SetDoubleArrayRegion(a, 0, n, p); }
+
+// the bodies of the sparse natives, for float and double (the C entry point comes as `fn`); -1 = an exception is pending
+template <typename T, typename Elems, typename TArr, typename Fn>
+jint gradient_sparse(JNIEnv* env, jlong h, jintArray wKeys, TArr wVals, jintArray idx, jlongArray statsOut, bool is64, Fn fn) {
+  if (!idx && null_array(env)) return -1;
+  if (pair_mismatch(env, wKeys, wVals)) return -1;
+  auto s = scratch_of(env, h);
+  if (!s) return -1;
+  const jsize n = env->GetArrayLength(idx);
+  const int64_t wn = wKeys ? env->GetArrayLength(wKeys) : -1;
+  dsgd_batch_stats st{};
+  std::lock_guard<std::mutex> lk(s->mu);
+  int rc;
+  {
+    IntElems kv(env, wKeys, JNI_ABORT);
+    Elems vv(env, wVals, JNI_ABORT);
+    IntElems iv(env, idx, JNI_ABORT);
+    rc = fn(ctx(h), reinterpret_cast<const int32_t*>(kv.p), vv.p, wn, reinterpret_cast<const int32_t*>(iv.p), n, s->keys.data(),
+            reinterpret_cast<T*>(s->vals.data()), s->dp, &s->nnz, &st);
+  }
+  if (rc) {
+    s->nnz = 0;
+    raise(env, rc);
+    return -1;
+  }
+  s->f64 = is64;
+  if (statsOut && env->GetArrayLength(statsOut) >= 1) {
+    const jlong a = st.n_active;
+    env->SetLongArrayRegion(statsOut, 0, 1, &a);
+  }
+  return static_cast<jint>(s->nnz);
+}
+template <typename T, typename Lr, typename Fn>
+jint async_step_sparse(JNIEnv* env, jlong h, jintArray idx, Lr lr, bool is64, Fn fn) {
+  if (!idx && null_array(env)) return -1;
+  auto s = scratch_of(env, h);
+  if (!s) return -1;
+  const jsize n = env->GetArrayLength(idx);
+  std::lock_guard<std::mutex> lk(s->mu);
+  int rc;
+  {
+    IntElems iv(env, idx, JNI_ABORT);
+    rc = fn(ctx(h), reinterpret_cast<const int32_t*>(iv.p), n, lr, s->keys.data(), reinterpret_cast<T*>(s->vals.data()), s->dp, &s->nnz,
+            nullptr);
+  }
+  if (rc) {
+    s->nnz = 0;
+    raise(env, rc);
+    return -1;
+  }
+  s->f64 = is64;
+  return static_cast<jint>(s->nnz);
+}
+template <typename T, typename Fn>
+jint get_weights_sparse(JNIEnv* env, jlong h, bool is64, Fn fn) {
+  auto s = scratch_of(env, h);
+  if (!s) return -1;
+  std::lock_guard<std::mutex> lk(s->mu);
+  const int rc = fn(ctx(h), s->keys.data(), reinterpret_cast<T*>(s->vals.data()), s->dp, &s->nnz);
+  if (rc) {
+    s->nnz = 0;
+    raise(env, rc);
+    return -1;
+  }
+  s->f64 = is64;
+  return static_cast<jint>(s->nnz);
+}
+template <typename Elems, typename TArr, typename Fn>
+void set_weights_sparse(JNIEnv* env, jlong h, jintArray keys, TArr vals, Fn fn) {
+  if ((!keys || !vals) && null_array(env)) return;
+  if (pair_mismatch(env, keys, vals)) return;
+  const jsize n = env->GetArrayLength(keys);
+  int rc;
+  {
+    IntElems kv(env, keys, JNI_ABORT);
+    Elems vv(env, vals, JNI_ABORT);
+    rc = fn(ctx(h), reinterpret_cast<const int32_t*>(kv.p), vv.p, n);
+  }
+  if (rc) raise(env, rc);
+}
+template <typename T, typename TArr>
+void take_sparse(JNIEnv* env, jlong h, jintArray keysOut, TArr valsOut, bool is64) {
+  if ((!keysOut || !valsOut) && null_array(env)) return;
+  auto s = scratch_of(env, h);
+  if (!s) return;
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (s->f64 != is64 || env->GetArrayLength(keysOut) != s->nnz || env->GetArrayLength(valsOut) != s->nnz) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "the arrays do not match the pairs held for this context");
+    return;
+  }
+  env->SetIntArrayRegion(keysOut, 0, static_cast<jsize>(s->nnz), reinterpret_cast<const jint*>(s->keys.data()));
+  set_region(env, valsOut, static_cast<jsize>(s->nnz), reinterpret_cast<const T*>(s->vals.data()));
+}
 }  // namespace
 
 extern "C" {
@@ -77,10 +228,14 @@ JNIEXPORT jlong JNICALL NATIVE(create)(JNIEnv* env, jobject, jint nFeatures, jdo
     raise(env, rc);
     return 0;
   }
+  scratch_add(reinterpret_cast<jlong>(c), nFeatures);
   return reinterpret_cast<jlong>(c);
 }
 
-JNIEXPORT void JNICALL NATIVE(destroy)(JNIEnv*, jobject, jlong h) { dsgd_destroy(ctx(h)); }
+JNIEXPORT void JNICALL NATIVE(destroy)(JNIEnv*, jobject, jlong h) {
+  scratch_drop(h);
+  dsgd_destroy(ctx(h));
+}
 
 // the same in the fp64 mode (DSGD_F_FP64, include/dsgd.h "THE FP64 MODE"): the reference's Double weights and learning rate
 JNIEXPORT jlong JNICALL NATIVE(createF64)(JNIEnv* env, jobject, jint nFeatures, jdouble lambda, jint device) {
@@ -95,6 +250,7 @@ JNIEXPORT jlong JNICALL NATIVE(createF64)(JNIEnv* env, jobject, jint nFeatures, 
     raise(env, rc);
     return 0;
   }
+  scratch_add(reinterpret_cast<jlong>(c), nFeatures);
   return reinterpret_cast<jlong>(c);
 }
 
@@ -421,6 +577,40 @@ JNIEXPORT void JNICALL NATIVE(forwardF64)(JNIEnv* env, jobject, jlong h, jdouble
     rc = dsgd_forward_f64(ctx(h), wv.p, reinterpret_cast<const int32_t*>(iv.p), n, pv.p);
   }
   if (rc) raise(env, rc);
+}
+
+// ---- Sparse values (include/dsgd.h "SPARSE VALUES"): Vec maps in and out as (keys, values) pairs -----------------------
+// A producing native compacts into the context's scratch and returns the count (-1 with an exception pending); takeSparse /
+// takeSparseF64 copy the pairs into arrays of exactly that length.  Null arrays are refused before any array is taken.
+JNIEXPORT jint JNICALL NATIVE(gradientSparse)(JNIEnv* env, jobject, jlong h, jintArray wKeys, jfloatArray wVals, jintArray idx, jlongArray statsOut) {
+  return gradient_sparse<jfloat, FloatElems>(env, h, wKeys, wVals, idx, statsOut, false, dsgd_gradient_sparse);
+}
+JNIEXPORT jint JNICALL NATIVE(gradientSparseF64)(JNIEnv* env, jobject, jlong h, jintArray wKeys, jdoubleArray wVals, jintArray idx, jlongArray statsOut) {
+  return gradient_sparse<jdouble, DoubleElems>(env, h, wKeys, wVals, idx, statsOut, true, dsgd_gradient_sparse_f64);
+}
+JNIEXPORT jint JNICALL NATIVE(asyncStepSparse)(JNIEnv* env, jobject, jlong h, jintArray idx, jfloat lr) {
+  return async_step_sparse<jfloat>(env, h, idx, lr, false, dsgd_async_step_sparse);
+}
+JNIEXPORT jint JNICALL NATIVE(asyncStepSparseF64)(JNIEnv* env, jobject, jlong h, jintArray idx, jdouble lr) {
+  return async_step_sparse<jdouble>(env, h, idx, lr, true, dsgd_async_step_sparse_f64);
+}
+JNIEXPORT jint JNICALL NATIVE(getWeightsSparse)(JNIEnv* env, jobject, jlong h) {
+  return get_weights_sparse<jfloat>(env, h, false, dsgd_get_weights_sparse);
+}
+JNIEXPORT jint JNICALL NATIVE(getWeightsSparseF64)(JNIEnv* env, jobject, jlong h) {
+  return get_weights_sparse<jdouble>(env, h, true, dsgd_get_weights_sparse_f64);
+}
+JNIEXPORT void JNICALL NATIVE(setWeightsSparse)(JNIEnv* env, jobject, jlong h, jintArray keys, jfloatArray vals) {
+  set_weights_sparse<FloatElems>(env, h, keys, vals, dsgd_set_weights_sparse);
+}
+JNIEXPORT void JNICALL NATIVE(setWeightsSparseF64)(JNIEnv* env, jobject, jlong h, jintArray keys, jdoubleArray vals) {
+  set_weights_sparse<DoubleElems>(env, h, keys, vals, dsgd_set_weights_sparse_f64);
+}
+JNIEXPORT void JNICALL NATIVE(takeSparse)(JNIEnv* env, jobject, jlong h, jintArray keysOut, jfloatArray valsOut) {
+  take_sparse<jfloat>(env, h, keysOut, valsOut, false);
+}
+JNIEXPORT void JNICALL NATIVE(takeSparseF64)(JNIEnv* env, jobject, jlong h, jintArray keysOut, jdoubleArray valsOut) {
+  take_sparse<jdouble>(env, h, keysOut, valsOut, true);
 }
 
 // SlaveImpl.startAsync (core/Slave.scala:159-175): the persistent lock-free engine on ONE device-resident w

@@ -49,6 +49,19 @@ object NativeSVM {
   // SlaveImpl.gradient / forward in Double: w may be null (the resident weights); gradientF64 returns the active rows
   @native def gradientF64(ctx: Long, w: Array[Double], idx: Array[Int], gOut: Array[Double]): Long
   @native def forwardF64(ctx: Long, w: Array[Double], idx: Array[Int], predOut: Array[Double]): Unit
+  // Sparse values (include/dsgd.h "SPARSE VALUES"): a Vec's map crosses as (keys, values).  A producing native compacts into
+  // native scratch of D + 1 slots the shim owns per context and returns the number of pairs; takeSparse copies them into
+  // arrays of exactly that length (hold the model's monitor across the two calls).  wKeys / wVals null: the resident weights.
+  @native def gradientSparse(ctx: Long, wKeys: Array[Int], wVals: Array[Float], idx: Array[Int], statsOut: Array[Long]): Int
+  @native def gradientSparseF64(ctx: Long, wKeys: Array[Int], wVals: Array[Double], idx: Array[Int], statsOut: Array[Long]): Int
+  @native def asyncStepSparse(ctx: Long, idx: Array[Int], lr: Float): Int
+  @native def asyncStepSparseF64(ctx: Long, idx: Array[Int], lr: Double): Int
+  @native def getWeightsSparse(ctx: Long): Int
+  @native def getWeightsSparseF64(ctx: Long): Int
+  @native def setWeightsSparse(ctx: Long, keys: Array[Int], vals: Array[Float]): Unit
+  @native def setWeightsSparseF64(ctx: Long, keys: Array[Int], vals: Array[Double]): Unit
+  @native def takeSparse(ctx: Long, keysOut: Array[Int], valsOut: Array[Float]): Unit
+  @native def takeSparseF64(ctx: Long, keysOut: Array[Int], valsOut: Array[Double]): Unit
   @native def asyncStart(ctx: Long, assignedBegin: Array[Long], assignedEnd: Array[Long], batch: Int, lr: Float,
                          maxUpdates: Long, seed: Long, positionalBug: Boolean): Unit
   @native def asyncUpdates(ctx: Long): Long
@@ -72,6 +85,25 @@ object NativeSVM {
 
 /** Dense float[D+1] indexed by KEY is the exchange format: feature ids are 1-based map keys
   * (utils/Dataset.scala:30), dimSparsity uses 0-based keys (Main.scala:60-62), so both slot 0 and slot D exist. */
+/** A Vec's map as the (keys, values) pairs the sparse natives take and return: nothing of D + 1 slots is built or scanned. */
+object SparsePairs {
+  def fromVec(v: Vec): (Array[Int], Array[Float]) = {
+    val n    = v.map.size
+    val keys = new Array[Int](n)
+    val vals = new Array[Float](n)
+    var i    = 0
+    v.map.foreach { case (k, x) => keys(i) = k; vals(i) = x.toDouble.toFloat; i += 1 }
+    (keys, vals)
+  }
+  def toVec(keys: Array[Int], vals: Array[Float], size: Int): Vec = {
+    val b = Map.newBuilder[Int, Number]
+    b.sizeHint(keys.length)
+    var i = 0
+    while (i < keys.length) { b += keys(i) -> Number(vals(i).toDouble); i += 1 }
+    Vec(b.result(), size)
+  }
+}
+
 object DenseKeys {
   def fromVec(v: Vec): Array[Float] = {
     val a = new Array[Float](v.size + 1)
@@ -107,9 +139,16 @@ class HipSVM(lambda: Number, dimSparsity: Vec, data: Array[(Vec, Int)], nTrain: 
 
   /** body of SlaveImpl.gradient (core/Slave.scala:142-157) */
   def gradientBatch(w: Vec, samplesIdx: Seq[Int]): Vec = {
-    val g = new Array[Float](dim + 1)
-    NativeSVM.gradient(ctx, DenseKeys.fromVec(w), samplesIdx.toArray, g)
-    DenseKeys.toVec(g, dim)
+    val (wk, wv) = SparsePairs.fromVec(w)
+    synchronized(take(NativeSVM.gradientSparse(ctx, wk, wv, samplesIdx.toArray, null)))
+  }
+
+  /** the pairs a sparse native left in the shim's scratch, as a Vec (called with this object's monitor held) */
+  private def take(n: Int): Vec = {
+    val keys = new Array[Int](n)
+    val vals = new Array[Float](n)
+    NativeSVM.takeSparse(ctx, keys, vals)
+    SparsePairs.toVec(keys, vals, dim)
   }
 
   /** body of SlaveImpl.forward (core/Slave.scala:129-140) */
@@ -133,13 +172,12 @@ class HipSVM(lambda: Number, dimSparsity: Vec, data: Array[(Vec, Int)], nTrain: 
     * device context holds every row and the weights can stay on the device between batches / iterations. */
   @volatile var resident: Boolean = false
 
-  def setWeights(w: Vec): Unit = NativeSVM.setWeights(ctx, DenseKeys.fromVec(w))
-
-  def weights(): Vec = {
-    val a = new Array[Float](dim + 1)
-    NativeSVM.getWeights(ctx, a)
-    DenseKeys.toVec(a, dim)
+  def setWeights(w: Vec): Unit = {
+    val (k, v) = SparsePairs.fromVec(w)
+    NativeSVM.setWeightsSparse(ctx, k, v)
   }
+
+  def weights(): Vec = synchronized(take(NativeSVM.getWeightsSparse(ctx)))
 
   /** the whole batch closure of Master.fit (core/Master.scala:184-197) for the workers hosted by this context: per-worker
     * regularised sums, mean over the workers, w <- w - learningRate * mean.  An empty list fails as Vec.sum does. */
@@ -211,11 +249,8 @@ class HipSVM(lambda: Number, dimSparsity: Vec, data: Array[(Vec, Int)], nTrain: 
 
   /** one iteration of Slave.asyncTask (core/Slave.scala:92-101) on the device-resident weights; returns the update that
     * is gossiped (core/Slave.scala:103-105) */
-  def asyncStepBatch(samplesIdx: Seq[Int], learningRate: Double): Vec = {
-    val d = new Array[Float](dim + 1)
-    NativeSVM.asyncStep(ctx, samplesIdx.toArray, learningRate.toFloat, d)
-    DenseKeys.toVec(d, dim)
-  }
+  def asyncStepBatch(samplesIdx: Seq[Int], learningRate: Double): Vec =
+    synchronized(take(NativeSVM.asyncStepSparse(ctx, samplesIdx.toArray, learningRate.toFloat)))
 
   /** SlaveImpl.updateGrad / MasterAsync.updateGrad (core/Slave.scala:177-185): w <- w - delta; may arrive while the
     * lock-free engine runs */
