@@ -279,7 +279,10 @@ int dsgd_plan_create_n(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const i
  * sequential part), and every (batch, worker) list is traced backwards through its Fisher-Yates by one workgroup straight
  * into the plan's index buffer.  DSGD_EUNSUPPORTED (nothing drawn, *jstate untouched): batch_size > 1,024, a split of more
  * than 2^20 rows, or a stream outside the device form's limits -- draw the lists on the host then (the Python / C++ host
- * mirrors do: csrc/jrand.c) and use dsgd_plan_create_n.  tests/test_gpu_shuffle.py: equal to csrc/jrand.c entry for entry. */
+ * mirrors do: csrc/jrand.c) and use dsgd_plan_create_n.  The practical ceiling is below the 2^20 rows: a shuffle of len rows
+ * rejects len^2 / 2^33 raw values on average and the device form holds 64 per shuffle, so from roughly 600,000 rows per
+ * split on almost every epoch is refused (one shuffle in its thousands exceeds 64) and at 2^20 rows (128 expected) all are.
+ * tests/test_gpu_shuffle.py, tests/test_gpu_shuffle_large.py: equal to csrc/jrand.c entry for entry.                         */
 int dsgd_plan_create_from_seed(dsgd_ctx* ctx, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end,
                                int32_t n_splits, int64_t max_samples, int32_t batch_size, dsgd_plan** out,
                                int64_t* n_steps_out, int64_t* draws_out);
