@@ -128,6 +128,7 @@ static bool available() {
 #include "dsgd_shuffle.hpp"
 #include "dsgd_cs64.hpp"   // (last: the fp64 mode)
 #include "dsgd_rp64.hpp"   // (... and its row-parallel gradient family)
+#include "dsgd_rp64v.hpp"  // (... and that family on Double feature values)
 #include "dsgd_sparse.hpp" // (the Sparse form at the boundary: compaction and scatter-in)
 
 // ------------------------------------------------------------------------------------------------
@@ -520,6 +521,13 @@ struct dsgd_ctx {
   int rp64_gk = 0;
   WorkSeg* d_rp64_gsegs = nullptr;
   unsigned long long* h_rp64_ranks = nullptr;
+  // Double feature values (dsgd_load_csr_f64; csrc/dsgd_rp64v.hpp): the values parallel to d_col / d_val (which holds them
+  // rounded), and the low words of the two-word column sums ([rp64v_k][rp64_stride], zero between calls; the high words
+  // are d_rp64_acc)
+  double* d_val64 = nullptr;
+  unsigned long long* d_rp64v_lo = nullptr;
+  int rp64v_k = 0;
+  long long rp64v_stride = 0;
   // Sparse values at the boundary (csrc/dsgd_sparse.hpp): the compaction's output in host-mapped memory the kernel writes in
   // place ([2 words: count, gave up][dp keys][dp values of 8 bytes]), its scan state, and the staged pairs of a sparse setter
   unsigned long long* h_sp_out = nullptr;
@@ -571,6 +579,16 @@ static CsrView view(dsgd_ctx* c) {
   v.row_ptr = c->d_row_ptr;
   v.col = c->d_col;
   v.val = c->d_val;
+  v.label = c->d_label;
+  return v;
+}
+
+static CsrView64 view64(dsgd_ctx* c) {   // (Double data loaded: dsgd_load_csr_f64)
+  CsrView64 v;
+  v.n_rows = c->n_rows;
+  v.row_ptr = c->d_row_ptr;
+  v.col = c->d_col;
+  v.val = c->d_val64;
   v.label = c->d_label;
   return v;
 }
@@ -1888,11 +1906,17 @@ static int permute64_resident(dsgd_ctx* c, bool in) {
   }
   return DSGD_OK;
 }
-static int count_columns(dsgd_ctx* c, long long nnz, unsigned int* d_cnt) {
+static int count_columns(dsgd_ctx* c, long long nnz, unsigned int* d_cnt, bool features = false) {
   HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned int) * c->dp, c->stream));
   if (nnz > 0) {
     const int hcnt = std::min(c->dp, DSGD_LDS_FLOATS);
     const int blocks = (int)std::max<long long>(1, std::min<long long>((nnz + 4095) / 4096, c->n_cu));
+    if (features && c->d_val64) {   // dimSparsity's feature counts: abs(v) > 1e-20 on the Double (the ranking needs no more than the floats)
+      hipLaunchKernelGGL(dsgd_colcount64v_kernel, dim3(blocks), dim3(1024), sizeof(unsigned int) * hcnt, c->stream, c->d_col, c->d_val64, nnz,
+                         d_cnt, c->dp, hcnt, c->d_sc);
+      HIP_TRY(hipGetLastError());
+      return DSGD_OK;
+    }
     hipLaunchKernelGGL(dsgd_colcount_kernel, dim3(blocks), dim3(1024), sizeof(unsigned int) * hcnt, c->stream, c->d_col,
                        c->d_val, nnz, d_cnt, c->dp, hcnt, c->d_sc);
     HIP_TRY(hipGetLastError());
@@ -3274,6 +3298,7 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
     DSGD_ATTR((dsgd_cs64_step_kernel<CS_THREADS, 2, 8>));
     DSGD_ATTR((dsgd_cs64_async_kernel<CS_THREADS, 1, 4>));
     DSGD_ATTR((dsgd_cs64_async_kernel<CS_THREADS, 2, 8>));
+    DSGD_ATTR(dsgd_colcount64v_kernel);
   }
   {   // the column lists' gradient kernel: its table, the bitmap, 16 words
     const int tc_lds = (int)(sizeof(long long) * TC_MAX_SHARE + TC_MAX_BITS / 8 + 64);
@@ -3341,6 +3366,8 @@ int dsgd_destroy(dsgd_ctx* c) {
   (void)hipFree(c->d_rp64_g);
   (void)hipFree(c->d_rp64_gath);
   (void)hipFree(c->d_rp64_gsegs);
+  (void)hipFree(c->d_val64);
+  (void)hipFree(c->d_rp64v_lo);
   if (c->h_rp64_ranks) (void)hipHostFree(c->h_rp64_ranks);
   if (c->h_sp_out) (void)hipHostFree(c->h_sp_out);
   (void)hipFree(c->d_sp_state);
@@ -3425,26 +3452,33 @@ int dsgd_destroy(dsgd_ctx* c) {
   return DSGD_OK;
 }
 
-int dsgd_load_csr(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in, const int32_t* col_in, const float* val_in,
-                  const int8_t* label) {
-  DSGD_TRY(check_ctx(c));
+// dsgd_load_csr (val64_in == nullptr) and dsgd_load_csr_f64 (val_in: the same values rounded to float, val64_in: as given)
+static int load_csr_impl(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in, const int32_t* col_in, const float* val_in,
+                         const double* val64_in, const int8_t* label) {
   if (n_rows < 1 || !row_ptr_in || !label) return fail(DSGD_EINVAL, "n_rows must be >= 1 and arrays non-null");
   if (row_ptr_in[0] != 0) return fail(DSGD_EINVAL, "row_ptr[0] must be 0");
   const int64_t* row_ptr = row_ptr_in;
   const int32_t* col = col_in;
   const float* val = val_in;
+  const double* val64 = val64_in;
   int64_t nnz = row_ptr[n_rows];
   if (nnz < 0 || (nnz > 0 && (!col || !val))) return fail(DSGD_EINVAL, "bad nnz / null col,val");
   for (int64_t i = 0; i < n_rows; ++i)
     if (row_ptr[i + 1] < row_ptr[i]) return fail(DSGD_EINVAL, "row_ptr not monotone at row %lld", (long long)i);
   // keys must be valid Sparse keys for a vector of size D (ref: math/Sparse.scala:61-68 accepts 0..size)
   float vmax = 0.0f;
+  double vmax64 = 0.0;   // (Double values: the largest |v| as a double)
   for (int64_t p = 0; p < nnz; ++p) {
     if (col[p] < 0 || col[p] > c->cfg.n_features)
       return fail(DSGD_ERANGE, "column id %d at nnz %lld outside [0, %d]", col[p], (long long)p, c->cfg.n_features);
     const float a = std::fabs(val[p]);
     if (!(a <= 3.0e38f)) return fail(DSGD_EINVAL, "non-finite value at nnz %lld", (long long)p);  // Vec.scala:14 NaN guard
     vmax = std::max(vmax, a);
+    if (val64) {
+      const double a64 = std::fabs(val64[p]);
+      if (!(a64 <= 3.0e38)) return fail(DSGD_EINVAL, "non-finite value at nnz %lld", (long long)p);
+      vmax64 = std::max(vmax64, a64);
+    }
   }
   for (int64_t i = 0; i < n_rows; ++i)
     if (label[i] != 1 && label[i] != -1) return fail(DSGD_EINVAL, "label[%lld] = %d, expected +1/-1", (long long)i, label[i]);
@@ -3470,6 +3504,7 @@ int dsgd_load_csr(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in, const 
   std::vector<int64_t> prow;
   std::vector<int32_t> pcol;
   std::vector<float> pval;
+  std::vector<double> pval64;
   {
     int64_t n_empty = 0;
     for (int64_t i = 0; i < n_rows; ++i) n_empty += row_ptr[i + 1] == row_ptr[i];
@@ -3477,36 +3512,45 @@ int dsgd_load_csr(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in, const 
       prow.resize((size_t)n_rows + 1);
       pcol.reserve((size_t)(nnz + n_empty));
       pval.reserve((size_t)(nnz + n_empty));
+      if (val64) pval64.reserve((size_t)(nnz + n_empty));
       prow[0] = 0;
       for (int64_t i = 0; i < n_rows; ++i) {
         if (row_ptr[i + 1] == row_ptr[i]) {
           pcol.push_back(0);
           pval.push_back(0.0f);
+          if (val64) pval64.push_back(0.0);
         } else {
           pcol.insert(pcol.end(), col + row_ptr[i], col + row_ptr[i + 1]);
           pval.insert(pval.end(), val + row_ptr[i], val + row_ptr[i + 1]);
+          if (val64) pval64.insert(pval64.end(), val64 + row_ptr[i], val64 + row_ptr[i + 1]);
         }
         prow[i + 1] = (int64_t)pcol.size();
       }
       row_ptr = prow.data();
       col = pcol.data();
       val = pval.data();
+      if (val64) val64 = pval64.data();
       nnz = row_ptr[n_rows];
     }
   }
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(bind(c));
   DSGD_TRY(require_sync_mode(c));   // the persistent engine reads the matrix that would be freed here
+  if (val64 && c->comm)
+    return fail(DSGD_EUNSUPPORTED, "dsgd_load_csr_f64 is not available while a communicator is attached (the gather's slots hold one "
+                                   "word per column; the data and the weights are unchanged)");
   HIP_TRY(hipStreamSynchronize(c->stream));
   DSGD_TRY(reset_layout(c));
   (void)hipFree(c->d_row_ptr);
   (void)hipFree(c->d_col);
   (void)hipFree(c->d_val);
   (void)hipFree(c->d_label);
+  (void)hipFree(c->d_val64);   // (float values again unless this load brings doubles)
   c->d_row_ptr = nullptr;
   c->d_col = nullptr;
   c->d_val = nullptr;
   c->d_label = nullptr;
+  c->d_val64 = nullptr;
   HIP_TRY(hipMalloc(&c->d_row_ptr, sizeof(long long) * (size_t)(n_rows + 1)));
   if (n_rows >= (int64_t)1 << 31) return fail(DSGD_EUNSUPPORTED, "more than 2^31-1 rows per context");
   // padding: the streaming kernels read whole windows (up to 512 slots) without clamping
@@ -3521,6 +3565,10 @@ int dsgd_load_csr(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in, const 
     HIP_TRY(hipMemcpy(c->d_val, val, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice));
   }
   HIP_TRY(hipMemcpy(c->d_label, label, (size_t)n_rows, hipMemcpyHostToDevice));
+  if (val64) {   // 8 bytes per non-zero, parallel to d_col / d_val (the ranking relabels d_col in place: the entries stay where they are)
+    HIP_TRY(hipMalloc(&c->d_val64, sizeof(double) * (size_t)(nnz + 1)));
+    if (nnz) HIP_TRY(hipMemcpy(c->d_val64, val64, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
+  }
   c->n_rows = n_rows;
   c->row_len.resize((size_t)n_rows);
   for (int64_t i = 0; i < n_rows; ++i) c->row_len[(size_t)i] = (int32_t)std::min<int64_t>(row_ptr_in[i + 1] - row_ptr_in[i], c->dp);
@@ -3532,12 +3580,47 @@ int dsgd_load_csr(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in, const 
     c->vexp = e;   // vmax2 = 2^e
     c->fix_scale = std::ldexp(1.0f, FIX_SHIFT - e);
   }
+  if (val64) {   // vexp from the largest |v| as a double (the same rule)
+    int e = 0;
+    std::frexp(vmax64 > 0.0 ? vmax64 : 1.0, &e);
+    if (vmax64 > 0.0 && std::ldexp(1.0, e - 1) == vmax64) e -= 1;
+    c->vexp = e;
+    c->fix_scale = std::ldexp(1.0f, FIX_SHIFT - e);
+  }
   c->h_row_ptr.assign(row_ptr, row_ptr + n_rows + 1);
   c->h_label.assign(label, label + n_rows);
   c->ssegs_last.clear();
   // (the wave tiles cover the hot stream and are built with the layout, at the first compute call)
   const double mean = (double)nnz / (double)n_rows;
   c->group = mean > 192.0 ? 64 : (mean > 96.0 ? 32 : (mean > 12.0 ? 16 : 8));
+  return DSGD_OK;
+}
+
+int dsgd_load_csr(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr, const int32_t* col, const float* val, const int8_t* label) {
+  DSGD_TRY(check_ctx(c));
+  return load_csr_impl(c, n_rows, row_ptr, col, val, nullptr, label);
+}
+
+// Double feature values (include/dsgd.h "THE FP64 MODE", csrc/dsgd_rp64v.hpp): dsgd_load_csr's validation and refusals; the
+// context keeps the doubles beside the values rounded to float (the ranking, the layout code: unchanged)
+int dsgd_load_csr_f64(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr, const int32_t* col, const double* val, const int8_t* label) {
+  DSGD_TRY(check_ctx(c));
+  DSGD_TRY(require_fp64(c, "dsgd_load_csr_f64"));
+  if (n_rows < 1 || !row_ptr || !label) return fail(DSGD_EINVAL, "n_rows must be >= 1 and arrays non-null");
+  if (row_ptr[0] != 0) return fail(DSGD_EINVAL, "row_ptr[0] must be 0");
+  const int64_t nnz = row_ptr[n_rows];
+  if (nnz < 0 || (nnz > 0 && (!col || !val))) return fail(DSGD_EINVAL, "bad nnz / null col,val");
+  std::vector<float> vf((size_t)nnz);
+  for (int64_t p = 0; p < nnz; ++p) vf[(size_t)p] = (float)val[p];   // (NaN stays NaN, beyond the float range: inf -- refused below, in order)
+  static const double zero64 = 0.0;
+  return load_csr_impl(c, n_rows, row_ptr, col, vf.data(), nnz ? val : &zero64, label);
+}
+
+int dsgd_value_bits(dsgd_ctx* c, int32_t* bits_out) {
+  DSGD_TRY(check_ctx(c));
+  if (!bits_out) return fail(DSGD_EINVAL, "null bits_out");
+  std::lock_guard<std::mutex> lk(c->mu);
+  *bits_out = c->d_val64 ? 64 : 32;
   return DSGD_OK;
 }
 
@@ -3571,7 +3654,7 @@ static int ds_begin(dsgd_ctx* c, long long n_train, unsigned int** d_cnt_out) { 
   unsigned int* d_cnt = nullptr;
   HIP_TRY(hipMalloc(&d_cnt, sizeof(unsigned int) * c->dp));
   int rc = reset_counters(c);
-  if (!rc) rc = count_columns(c, nnz_train, d_cnt);
+  if (!rc) rc = count_columns(c, nnz_train, d_cnt, true);
   if (rc) {
     (void)hipFree(d_cnt);
     return rc;
@@ -3899,6 +3982,24 @@ static int sync_step64(dsgd_ctx* c, const int32_t* const* idx_per_worker, const 
                       dsgd_batch_stats* stats);
 static int sync_step64_ranks(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int n_workers, double lr,
                              dsgd_batch_stats* stats);
+static int sync_step64_rows(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int n_workers, double lr,
+                            dsgd_batch_stats* stats);
+static int refuse_val64(dsgd_ctx* c, const char* what);
+// what a one-step fp64 plan of n_workers lists and `rows` rows in all can hold (plan_frame's refusals, word for word): the
+// calls that run such a plan on float data keep these limits on Double data, where the row-parallel pair serves them
+static int cs64_step_limits(dsgd_ctx* c, int n_workers, long long rows) {
+  if (n_workers > CS64_MAX_K)
+    return fail(DSGD_EUNSUPPORTED, "fp64 plans host at most %d workers per step (this plan has %d)", CS64_MAX_K, n_workers);
+  if (rows > CS_MAX_SLOTS)
+    return fail(DSGD_EUNSUPPORTED, "fp64 plans take at most %d rows per step (this plan has a step of %lld)", CS_MAX_SLOTS, rows);
+  if (cs64_lds_bytes(c->dp, n_workers) > CS64_LDS_MAX || c->dp < 4 * CS64_G)
+    return fail(DSGD_EUNSUPPORTED, "fp64 plans: a model of %d features needs %lld bytes of LDS per slice at %d workers (at most %lld; "
+                                   "at least %d features)", c->cfg.n_features, cs64_lds_bytes(c->dp, n_workers), n_workers, CS64_LDS_MAX,
+                4 * CS64_G - 1);
+  return DSGD_OK;
+}
+static int rp64_ensure(dsgd_ctx* c, int n_workers);
+static int rp64v_launch(dsgd_ctx* c, int n_workers, long long max_items, int mode, double lr, double* delta);
 int dsgd_sync_step(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers,
                    float lr, dsgd_batch_stats* stats) {
   DSGD_TRY(check_ctx(c));
@@ -3910,6 +4011,12 @@ int dsgd_sync_step(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int6
   DSGD_TRY(require_sync_mode(c));
   DSGD_TRY(prepare_layout(c));
   if (c->fp64 && c->comm) return sync_step64_ranks(c, idx_per_worker, n_per_worker, n_workers, (double)lr, stats);
+  if (c->fp64 && c->d_val64) {   // Double data: the row-parallel pair, inside the limits of the one-step plan this call is on float data
+    long long rows = 0;
+    for (int k = 0; k < n_workers; ++k) rows += std::max<long long>(0, n_per_worker[k]);
+    DSGD_TRY(cs64_step_limits(c, n_workers, rows));
+    return sync_step64_rows(c, idx_per_worker, n_per_worker, n_workers, (double)lr, stats);
+  }
   if (c->fp64) return sync_step64(c, idx_per_worker, n_per_worker, n_workers, (double)lr, stats);
   long long mx = 0, tot = 0;
   {
@@ -4216,6 +4323,7 @@ int dsgd_plan_create(dsgd_ctx* c, const int32_t* idx, const int64_t* offsets, in
   const int64_t n_lists = n_steps * n_workers;
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_create"));
+  DSGD_TRY(refuse_val64(c, "dsgd_plan_create"));
   DSGD_TRY(bind(c, true));   // (nothing here touches w: slice-major weights stay as they are)
   dsgd_plan* p = nullptr;
   DSGD_TRY(plan_frame(c, offsets, n_steps, n_workers, &p));
@@ -4292,6 +4400,10 @@ int dsgd_plan_create_from_seed(dsgd_ctx* c, uint64_t* jstate, const int64_t* spl
   DSGD_TRY(check_ctx(c));
   if (!jstate || !split_begin || !split_end || !out || !n_steps_out || n_splits < 1 || batch_size < 1)
     return fail(DSGD_EINVAL, "bad arguments");
+  {   // (refused with *out as it was)
+    std::lock_guard<std::mutex> lk0(c->mu);
+    DSGD_TRY(refuse_val64(c, "dsgd_plan_create_from_seed"));
+  }
   *out = nullptr;
   *n_steps_out = 0;
   if (draws_out) *draws_out = 0;
@@ -4323,6 +4435,7 @@ int dsgd_plan_create_from_seed(dsgd_ctx* c, uint64_t* jstate, const int64_t* spl
   const long long nominal = start[(size_t)n_shuf];
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_create_from_seed"));
+  DSGD_TRY(refuse_val64(c, "dsgd_plan_create_from_seed"));
   DSGD_TRY(bind(c, true));
   for (int k = 0; k < n_splits; ++k)
     if (split_end[k] > c->n_rows) return fail(DSGD_ERANGE, "worker %d's rows [%lld, %lld) outside the %lld loaded", k, (long long)split_begin[k], (long long)split_end[k], c->n_rows);
@@ -4743,6 +4856,29 @@ static int async_step64(dsgd_ctx* c, const char* what, const int32_t* idx, int64
     DSGD_TRY(sp_async_cap(c, idx, n, sparse_cap));   // (before anything runs: a delta is never lost)
     DSGD_TRY(sp_ensure(c));
   }
+  if (c->d_val64) {   // Double data: the row-parallel pair with the asynchronous finish; the delta in key order as it is written
+    DSGD_TRY(cs64_step_limits(c, 1, n));   // (the one-step plan's refusals, as on float data)
+    if (want_delta && !c->d_cs_dl64)
+      HIP_TRY(hipMalloc(&c->d_cs_dl64, sizeof(double) * ((size_t)CS64_G * cs64_sp(c->dp) + (size_t)c->dp)));
+    DSGD_TRY(rp64_ensure(c, 1));
+    DSGD_TRY(reset_counters(c));
+    long long mx = 0, tot = 0;
+    const int64_t nn = n;
+    DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
+    DSGD_TRY(rp64v_launch(c, 1, mx, RP64V_ASYNC, lr, want_delta ? c->d_cs_dl64 : nullptr));
+    c->s_dirty = true;
+    if (sparse) DSGD_TRY((sp_compact<double, double, false>(c, c->d_cs_dl64, nullptr)));
+    DSGD_TRY(finish_stats(c, stats, n));
+    if (delta_out) {   // (key order already: through the pinned buffer, as the gradient goes out)
+      const size_t bytes = sizeof(double) * (size_t)c->dp;
+      DSGD_TRY(pin_acquire(c->pin_out, bytes));
+      HIP_TRY(hipMemcpyAsync(c->pin_out.p, c->d_cs_dl64, bytes, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      memcpy(delta_out, c->pin_out.p, bytes);
+    }
+    if (sparse) return sp_deliver<double>(c, sp_key, sp_val, sparse_cap, sp_nnz);
+    return DSGD_OK;
+  }
   DSGD_TRY(plan_frame(c, offsets, 1, 1, &p));
   p->h_idx.assign(idx, idx + n);
   hipError_t e = hipMemcpyAsync(p->d_idx, p->h_idx.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->build_stream);
@@ -4992,6 +5128,86 @@ static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, bool ste
   return DSGD_OK;
 }
 
+// ---- ... on Double feature values (dsgd_load_csr_f64; csrc/dsgd_rp64v.hpp): the same two launches over two-word sums ----
+static int rp64v_ensure(dsgd_ctx* c) {   // (behind rp64_ensure: the high words are d_rp64_acc)
+  if (c->d_rp64v_lo && c->rp64v_k >= c->rp64_k && c->rp64v_stride == c->rp64_stride) return DSGD_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  (void)hipFree(c->d_rp64v_lo);
+  c->d_rp64v_lo = nullptr;
+  c->rp64v_k = 0;
+  const size_t words = (size_t)c->rp64_stride * (size_t)c->rp64_k;
+  HIP_TRY(hipMalloc(&c->d_rp64v_lo, sizeof(unsigned long long) * words));
+  HIP_TRY(hipMemsetAsync(c->d_rp64v_lo, 0, sizeof(unsigned long long) * words, c->stream));
+  c->rp64v_k = c->rp64_k;
+  c->rp64v_stride = c->rp64_stride;
+  return DSGD_OK;
+}
+// mode: RP64V_GRADIENT (worker 0's gradient into d_rp64_g), RP64V_STEP, RP64V_ASYNC (one worker; delta: key order, may be null)
+static int rp64v_launch(dsgd_ctx* c, int n_workers, long long max_items, int mode, double lr, double* delta) {
+  DSGD_TRY(rp64v_ensure(c));
+  const bool sliced = c->cs_w_G == CS64_G;   // (the weights stay in whichever layout they are: slice-major between plan runs)
+  const int Sp = sliced ? cs64_sp(c->dp) : 0;
+  double* w = sliced ? c->d_cs_w64 : c->d_w64;
+  constexpr long long rows_per_block = RP64_THREADS / RP64_GROUP;
+  const long long bpw = std::max<long long>(1, std::min<long long>((max_items + rows_per_block - 1) / rows_per_block,
+                                                                   std::max<long long>(1, (long long)c->n_cu * 2 / n_workers)));
+  Rp64vArgs a;
+  a.m = view64(c);
+  a.w = w;
+  a.ds = c->d_ds64;
+  a.Sp = Sp;
+  a.dp = c->dp;
+  a.vexp = c->vexp;
+  a.K = n_workers;
+  a.idx = c->cur_idx;
+  a.segs = c->d_segs;
+  a.blocks_per_worker = bpw;
+  a.hi = reinterpret_cast<long long*>(c->d_rp64_acc);
+  a.lo = c->d_rp64v_lo;
+  a.acc_stride = c->rp64_stride;
+  a.lambda = c->cfg.lambda;
+  a.s_out = c->d_rp64_s;
+  a.sc = c->d_sc;
+  a.with_s = mode == RP64V_ASYNC ? 0 : 1;   // (the asynchronous iteration: s from dsgd_rp64v_s_sliced_kernel below)
+  hipLaunchKernelGGL(dsgd_rp64v_grad_kernel, dim3((unsigned)(bpw * n_workers + a.with_s)), dim3(RP64_THREADS), 0, c->stream, a);
+  HIP_TRY(hipGetLastError());
+  if (mode == RP64V_ASYNC) {   // s in the order of the float data's asynchronous kernel (the same bits on values a float holds)
+    hipLaunchKernelGGL(dsgd_rp64v_s_sliced_kernel, dim3(1), dim3(CS_THREADS), 0, c->stream, w, c->d_ds64, Sp, c->dp, c->cfg.lambda, c->d_rp64_s);
+    HIP_TRY(hipGetLastError());
+  }
+  Rp64vFinishArgs f;
+  f.hi = a.hi;
+  f.lo = a.lo;
+  f.acc_stride = c->rp64_stride;
+  f.segs = c->d_segs;
+  f.K = n_workers;
+  f.dp = c->dp;
+  f.vexp = c->vexp;
+  f.Sp = Sp;
+  f.s = c->d_rp64_s;
+  f.perm = c->d_perm;
+  f.g_out = mode == RP64V_ASYNC ? delta : c->d_rp64_g;
+  f.w = w;
+  f.lr = lr;
+  const dim3 fg((unsigned)std::min<long long>(((long long)c->dp + RP64_THREADS - 1) / RP64_THREADS, (long long)c->n_cu * 4));
+  if (mode == RP64V_STEP)
+    hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64V_STEP>, fg, dim3(RP64_THREADS), 0, c->stream, f);
+  else if (mode == RP64V_ASYNC)
+    hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64V_ASYNC>, fg, dim3(RP64_THREADS), 0, c->stream, f);
+  else
+    hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64V_GRADIENT>, fg, dim3(RP64_THREADS), 0, c->stream, f);
+  HIP_TRY(hipGetLastError());
+  return DSGD_OK;
+}
+// Double data loaded: what a resident plan or a communicator would need is refused (nothing changed, the context usable)
+static int refuse_val64(dsgd_ctx* c, const char* what) {
+  if (c->d_val64)
+    return fail(DSGD_EUNSUPPORTED, "%s is not available on Double feature values (dsgd_load_csr_f64): the column-slice kernels hold "
+                                   "float values in registers and a communicator's gather slots one word per column; "
+                                   "dsgd_sync_step_f64 / dsgd_async_step_f64 serve Double data", what);
+  return DSGD_OK;
+}
+
 int dsgd_gradient_f64(dsgd_ctx* c, const double* w, const int32_t* idx, int64_t n, double* g_out, dsgd_batch_stats* stats) {
   DSGD_TRY(check_ctx(c));
   if (!g_out) return fail(DSGD_EINVAL, "null g_out");
@@ -5013,7 +5229,8 @@ int dsgd_gradient_f64(dsgd_ctx* c, const double* w, const int32_t* idx, int64_t 
   DSGD_TRY(reset_counters(c));
   long long mx = 0, tot = 0;
   DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
-  DSGD_TRY(rp64_launch(c, 1, mx, false, 0.0));
+  if (c->d_val64) DSGD_TRY(rp64v_launch(c, 1, mx, RP64V_GRADIENT, 0.0, nullptr));
+  else DSGD_TRY(rp64_launch(c, 1, mx, false, 0.0));
   const size_t bytes = sizeof(double) * (size_t)c->dp;
   DSGD_TRY(pin_acquire(c->pin_out, bytes));
   HIP_TRY(hipMemcpyAsync(c->pin_out.p, c->d_rp64_g, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -5060,12 +5277,18 @@ int dsgd_sync_step_f64(dsgd_ctx* c, const int32_t* const* idx_per_worker, const 
   DSGD_TRY(require_sync_mode(c));
   DSGD_TRY(prepare_layout(c));
   if (c->comm) return sync_step64_ranks(c, idx_per_worker, n_per_worker, n_workers, lr, stats);
+  return sync_step64_rows(c, idx_per_worker, n_per_worker, n_workers, lr, stats);
+}
+// the row-parallel step of one process (locked, bound, layout ready)
+static int sync_step64_rows(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int n_workers, double lr,
+                            dsgd_batch_stats* stats) {
   DSGD_TRY(rp64_check_lists(c, idx_per_worker, n_per_worker, n_workers));
   DSGD_TRY(rp64_ensure(c, n_workers));
   DSGD_TRY(reset_counters(c));
   long long mx = 0, tot = 0;
   DSGD_TRY(stage_lists(c, idx_per_worker, n_per_worker, n_workers, &mx, &tot));
-  DSGD_TRY(rp64_launch(c, n_workers, mx, true, lr));
+  if (c->d_val64) DSGD_TRY(rp64v_launch(c, n_workers, mx, RP64V_STEP, lr, nullptr));
+  else DSGD_TRY(rp64_launch(c, n_workers, mx, true, lr));
   c->s_dirty = true;
   return finish_stats(c, stats, tot);
 }
@@ -5075,6 +5298,10 @@ int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int
   DSGD_TRY(check_ctx(c));
   if (!assigned_begin || !assigned_end || !out || n_workers < 1 || batch < 1 || first_update < 0 || n_updates < 1)
     return fail(DSGD_EINVAL, "bad async plan arguments");
+  {   // (refused with *out as it was)
+    std::lock_guard<std::mutex> lk0(c->mu);
+    DSGD_TRY(refuse_val64(c, "dsgd_async_plan_create"));
+  }
   *out = nullptr;
   for (int k = 0; k < n_workers; ++k) {
     const long long len = assigned_end[k] - assigned_begin[k];
@@ -5084,6 +5311,7 @@ int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(require_fp64(c, "dsgd_async_plan_create"));
   DSGD_TRY(refuse_fp64_comm(c, "dsgd_async_plan_create"));
+  DSGD_TRY(refuse_val64(c, "dsgd_async_plan_create"));
   DSGD_TRY(bind(c, true));   // (nothing here touches w)
   for (int k = 0; k < n_workers; ++k)
     if (assigned_end[k] > c->n_rows)
@@ -5182,7 +5410,9 @@ static int forward_run(dsgd_ctx* c, const int32_t* idx, int64_t n, float* pred_o
   const int G = c->group;
   dim3 grid(grid_for(c, n, G));
   CsrView m = view(c);
-  if (c->fp64) {
+  if (c->fp64 && c->d_val64) {
+    hipLaunchKernelGGL(dsgd_forward64v_kernel, dim3(grid_for(c, n, 16)), dim3(256), 0, c->stream, view64(c), c->d_w64, c->d_idx, (long long)n, d_pred, c->d_sc);
+  } else if (c->fp64) {
     hipLaunchKernelGGL(dsgd_forward64_kernel, dim3(grid_for(c, n, 16)), dim3(256), 0, c->stream, m, c->d_w64, c->d_idx, (long long)n, d_pred, c->d_sc);
   } else switch (G) {
     case 64: hipLaunchKernelGGL(dsgd_forward_kernel<64>, grid, dim3(256), 0, c->stream, m, c->d_w, c->d_idx, (long long)n, d_pred, c->d_sc); break;
@@ -5215,7 +5445,10 @@ static int eval_enqueue(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t 
     DSGD_TRY(reset_counters(c));
     const long long rows = row_end - row_begin;
     const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>((long long)c->n_cu * 8, (rows + 15) / 16)));
-    hipLaunchKernelGGL(dsgd_eval64_kernel, grid, dim3(256), 0, c->stream, view(c), c->d_w64, (long long)row_begin, (long long)row_end, c->d_sc);
+    if (c->d_val64)
+      hipLaunchKernelGGL(dsgd_eval64v_kernel, grid, dim3(256), 0, c->stream, view64(c), c->d_w64, (long long)row_begin, (long long)row_end, c->d_sc);
+    else
+      hipLaunchKernelGGL(dsgd_eval64_kernel, grid, dim3(256), 0, c->stream, view(c), c->d_w64, (long long)row_begin, (long long)row_end, c->d_sc);
     hipLaunchKernelGGL(dsgd_norm64_kernel, dim3(1), dim3(256), 0, c->stream, c->d_w64, c->dp, c->d_nsq64);
     HIP_TRY(hipGetLastError());
     return DSGD_OK;
@@ -5463,7 +5696,8 @@ int dsgd_gradient_sparse_f64(dsgd_ctx* c, const int32_t* w_key, const double* w_
   DSGD_TRY(reset_counters(c));
   long long mx = 0, tot = 0;
   DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
-  DSGD_TRY(rp64_launch(c, 1, mx, false, 0.0));
+  if (c->d_val64) DSGD_TRY(rp64v_launch(c, 1, mx, RP64V_GRADIENT, 0.0, nullptr));
+  else DSGD_TRY(rp64_launch(c, 1, mx, false, 0.0));
   DSGD_TRY((sp_compact<double, double, false>(c, c->d_rp64_g, nullptr)));   // (the finish leaves the gradient in key order)
   DSGD_TRY(read_scalars(c));   // the one synchronisation of the call
   DSGD_TRY(check_err_flag(c));
@@ -5958,6 +6192,7 @@ int dsgd_comm_init_f64(dsgd_ctx* c, const char* unique_id, int32_t world_size, i
   if (!unique_id || world_size < 1 || rank < 0 || rank >= world_size) return fail(DSGD_EINVAL, "bad communicator arguments");
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(require_fp64(c, "dsgd_comm_init_f64"));
+  DSGD_TRY(refuse_val64(c, "dsgd_comm_init_f64"));
   if (world_size > 64) return fail(DSGD_EUNSUPPORTED, "at most 64 ranks");
   if (!rccl::available()) return fail(DSGD_ERCCL, "librccl could not be loaded");
   const bool sliced = c->cs_w_G == CS64_G;

@@ -29,6 +29,7 @@ typedef struct {
   int64_t* row_ptr;
   int32_t* col;
   float* val;
+  double* val64; /* the parsed Doubles as they are (elems(1).toDouble, Dataset.scala:30); val holds them rounded */
   int8_t* label;
   int32_t* doc_id;
   /* id -> label: open addressing, key 0 = empty (document ids are positive) */
@@ -160,6 +161,9 @@ static int reserve_nnz(dsgd_rcv1* h, int64_t need) {
   float* v = (float*)realloc(h->val, sizeof(float) * (size_t)nc);
   if (!v) return -1;
   h->val = v;
+  double* d = (double*)realloc(h->val64, sizeof(double) * (size_t)nc);
+  if (!d) return -1;
+  h->val64 = d;
   h->cap_nnz = nc;
   return 0;
 }
@@ -218,6 +222,7 @@ static int vec_tok(void* vctx, int64_t index, const char* p, size_t len) {
     for (int64_t q = c->row_start; q < h->nnz; ++q) {
       if (h->col[q] == key) {
         h->val[q] = (float)v;
+        h->val64[q] = v;
         return 0;
       }
     }
@@ -230,6 +235,7 @@ static int vec_tok(void* vctx, int64_t index, const char* p, size_t len) {
   }
   h->col[h->nnz] = key;
   h->val[h->nnz] = (float)v;
+  h->val64[h->nnz] = v;
   h->nnz++;
   return 0;
 }
@@ -262,6 +268,7 @@ void dsgd_rcv1_free(dsgd_rcv1* h) {
   free(h->row_ptr);
   free(h->col);
   free(h->val);
+  free(h->val64);
   free(h->label);
   free(h->doc_id);
   free(h->lab_key);
@@ -357,4 +364,8 @@ void dsgd_rcv1_copy(const dsgd_rcv1* h, int64_t* row_ptr, int32_t* col, float* v
   if (val && h->nnz) memcpy(val, h->val, sizeof(float) * (size_t)h->nnz);
   if (label && h->n_rows) memcpy(label, h->label, (size_t)h->n_rows);
   if (doc_id && h->n_rows) memcpy(doc_id, h->doc_id, sizeof(int32_t) * (size_t)h->n_rows);
+}
+/* the values as the reference holds them: Double, every digit of the file */
+void dsgd_rcv1_copy_f64(const dsgd_rcv1* h, double* val64) {
+  if (val64 && h->nnz) memcpy(val64, h->val64, sizeof(double) * (size_t)h->nnz);
 }

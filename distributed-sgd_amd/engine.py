@@ -93,16 +93,20 @@ class Engine:
 
     # -- data ------------------------------------------------------------------------------------
     def load_csr(self, row_ptr, col, val, label):
+        """The data as CSR.  An fp64 engine keeps a float64 `val` as it is (dsgd_load_csr_f64: the reference's Double
+        feature values); every other dtype, and every fp32 engine, loads float32 values."""
         row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
         col = i32(col)
-        val = f32(val)
+        as_f64 = self.precision == "fp64" and np.asarray(val).dtype == np.float64
+        val = f64(val) if as_f64 else f32(val)
         label = np.ascontiguousarray(label, dtype=np.int8)
         n_rows = len(row_ptr) - 1
         if len(label) != n_rows:
             raise ValueError("label has %d entries for %d rows" % (len(label), n_rows))
         if n_rows >= 1 and (len(col) < row_ptr[-1] or len(val) < row_ptr[-1]):
             raise ValueError("col/val shorter than row_ptr[-1]")
-        check(self._lib.dsgd_load_csr(self._ctx, C.c_int64(n_rows), ptr(row_ptr), ptr(col), ptr(val), ptr(label)))
+        load = self._lib.dsgd_load_csr_f64 if as_f64 else self._lib.dsgd_load_csr
+        check(load(self._ctx, C.c_int64(n_rows), ptr(row_ptr), ptr(col), ptr(val), ptr(label)))
         self.n_rows, self.nnz = n_rows, int(row_ptr[-1])
 
     @property
@@ -149,6 +153,12 @@ class Engine:
         out = np.zeros(self.dp, dtype=np.float32)
         check(self._lib.dsgd_get_weights(self._ctx, ptr(out)))
         return out
+
+    def value_bits(self):
+        """64 while Double feature values are loaded (load_csr with a float64 array on an fp64 engine), 32 otherwise."""
+        v = C.c_int32(0)
+        check(self._lib.dsgd_value_bits(self._ctx, C.byref(v)))
+        return v.value
 
     def precision_bits(self):
         v = C.c_int32(0)

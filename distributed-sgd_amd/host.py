@@ -713,6 +713,13 @@ class MasterAsync:
         split = [(r.start, r.stop) for r in split_vanilla(self.n_train, self.node_count)]
         steps = self.n_train * max_epoch if max_steps is None else max_steps
         if getattr(self.backend, "precision", "fp32") == "fp64":
+            value_bits = getattr(self.backend, "value_bits", None)
+            if value_bits is not None and value_bits() == 64:
+                # the zero-lag schedule runs resident asynchronous plans (column slices), which hold float values
+                raise NotImplementedError(
+                    "MasterAsync.fit is not available on Double feature values (Engine.load_csr with float64 values): resident "
+                    "asynchronous plans are refused there (include/dsgd.h \"THE FP64 MODE\"); async_step_f64 serves single "
+                    "iterations, or load float32 values")
             return self._fit_fp64(initial_weights, split, steps, batch_size, learning_rate, stopping_criterion, check_every,
                                   leak_loss_coef, seed, positional_bug)
         self.backend.set_weights(np.asarray(initial_weights, dtype=np.float32))

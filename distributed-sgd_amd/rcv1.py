@@ -38,6 +38,8 @@ def _load():
         lib.dsgd_rcv1_nnz.argtypes = [C.c_void_p]
         lib.dsgd_rcv1_copy.restype = None
         lib.dsgd_rcv1_copy.argtypes = [C.c_void_p] * 6
+        lib.dsgd_rcv1_copy_f64.restype = None
+        lib.dsgd_rcv1_copy_f64.argtypes = [C.c_void_p] * 2
         lib.dsgd_rcv1_free.restype = None
         lib.dsgd_rcv1_free.argtypes = [C.c_void_p]
         _lib = lib
@@ -46,7 +48,8 @@ def _load():
 
 def load(folder: str, full: bool = True, dim: int = RCV1_DIM, with_ids: bool = False):
     """Dataset.rcv1(folder, full).  Raises ValueError on what makes the reference throw (malformed line, missing label,
-    missing file)."""
+    missing file).  The returned Csr holds the values twice: `val` (float32, what the fp32 engine takes) and `val64`, the parsed
+    Doubles as the reference keeps them (elems(1).toDouble) -- what `Engine(precision="fp64").load_csr` takes."""
     lib = _load()
     err = C.create_string_buffer(512)
     h = lib.dsgd_rcv1_load(os.fsencode(folder), 1 if full else 0, err, len(err))
@@ -59,10 +62,12 @@ def load(folder: str, full: bool = True, dim: int = RCV1_DIM, with_ids: bool = F
         val = np.empty(nnz, dtype=np.float32)
         label = np.empty(n, dtype=np.int8)
         ids = np.empty(n, dtype=np.int32)
+        val64 = np.empty(nnz, dtype=np.float64)
         lib.dsgd_rcv1_copy(h, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data, label.ctypes.data, ids.ctypes.data)
+        lib.dsgd_rcv1_copy_f64(h, val64.ctypes.data)
     finally:
         lib.dsgd_rcv1_free(h)
-    data = Csr(dim, row_ptr, col, val, label)
+    data = Csr(dim, row_ptr, col, val, label, val64)
     return (data, ids) if with_ids else data
 
 

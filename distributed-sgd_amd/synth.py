@@ -42,6 +42,7 @@ class Csr:
     col: np.ndarray      # int32, 1-based, ascending per row
     val: np.ndarray      # float32
     label: np.ndarray    # int8 +1/-1
+    val64: np.ndarray | None = None   # float64: the values before their rounding to float32 (rcv1.load); None: val is all there is
 
     @property
     def n_rows(self):
@@ -59,7 +60,7 @@ class Csr:
         """Sub-matrix copy of rows [begin, end) (used for bounded CPU samples)."""
         b, e = int(self.row_ptr[begin]), int(self.row_ptr[end])
         return Csr(self.dim, (self.row_ptr[begin:end + 1] - b).astype(np.int64), self.col[b:e].copy(),
-                   self.val[b:e].copy(), self.label[begin:end].copy())
+                   self.val[b:e].copy(), self.label[begin:end].copy(), None if self.val64 is None else self.val64[b:e].copy())
 
 
 def generate(n_rows, seed=0, dim=RCV1_DIM, row0=0, zipf=None, nnz_mean=None):

@@ -131,6 +131,29 @@ enum {
  *     dsgd_async_step_f64 return DSGD_EUNSUPPORTED and change nothing: the persistent column-slice kernel cannot hold a
  *     collective.  (host.MasterSync.fit falls back from a refused plan to one dsgd_sync_step_f64 per step.)
  *   Without a communicator nothing changes.  Real RCCL with more than one rank has not run; no multi-GPU speed is claimed.
+ *   DOUBLE FEATURE VALUES (dsgd_load_csr_f64; csrc/dsgd_rp64v.hpp).  The reference reads `elems(1).toDouble`
+ *   (utils/Dataset.scala:30); dsgd_load_csr takes floats, which moves every value of a real data file by up to 6e-8
+ *   relative before the first step.  dsgd_load_csr_f64 keeps the doubles (8 bytes per non-zero beside the CSR) and the
+ *   values rounded to float (the column ranking and the layout code read those); vexp comes from the largest |v| as a
+ *   double, and every abs(v) > 1e-20 filter that decides a result (the gradient's entries, dimSparsity's feature counts)
+ *   reads the double.  dsgd_value_bits says which values are loaded (64 / 32); dsgd_load_csr brings floats back and
+ *   frees the doubles.  Served on Double data, each its float-data self in statistics, state rules and errors:
+ *   dsgd_gradient_f64, dsgd_gradient_sparse_f64, dsgd_sync_step_f64, dsgd_sync_step (the row-parallel step, inside the
+ *   one-step plan's limits of 4 workers and 1,024 rows), dsgd_async_step_f64 / _sparse_f64 (the row-parallel pair with
+ *   orc_async_step's finish, the delta in key order; the one-step plan's limits of 1,024 rows and the LDS as on float data), dsgd_forward / _f64, dsgd_loss_acc, dsgd_build_dim_sparsity,
+ *   dsgd_update_grad_f64 and the get / set of weights and dimSparsity.
+ *   The column sums have TWO words per column and worker.  With S = 62 - ceil(log2 n) and v = +-x * 2^(S - vexp):
+ *   floor(v) goes into a signed 64-bit word HI, rn((v - floor(v)) * 2^32) into an unsigned 64-bit word LO (no carry: n
+ *   <= 2^31 entries of <= 2^32), the sum is (HI * 2^32 + LO) * 2^(vexp - S - 32), rounded ONCE to double, to nearest even
+ *   (csrc/dsgd_round128.hpp).  EXACT RANGE: an entry of exponent e (|x| in [2^e, 2^(e+1)), all 53 bits used) is exact
+ *   when e >= vexp - (42 - ceil(log2 n)) -- 35 binades at 100 rows, 32 at 1,024, 26 at 65,536; below it an entry is
+ *   off by at most half a unit 2^(vexp - S - 32).  The sums are integers: order-free and bit-reproducible.  Values a
+ *   float holds exactly, inside the float grid's range, give the bits of the float-data call.
+ *   Refused on Double data with DSGD_EUNSUPPORTED, nothing changed, the context usable: dsgd_plan_create / _n /
+ *   _from_seed and dsgd_async_plan_create (the column-slice kernels hold 16 float values per slot in registers),
+ *   dsgd_comm_init_f64, and dsgd_load_csr_f64 while a communicator is attached (the gather's slots would double).
+ *   host.MasterSync.fit falls back from the refused plan to dsgd_sync_step_f64 on host-drawn lists; host.MasterAsync.fit
+ *   needs resident asynchronous plans and raises on Double data.
  * The entry points below that name fp64 return DSGD_ESTATE on an fp32 context (dsgd_precision excepted).            */
 
 typedef struct dsgd_ctx dsgd_ctx;
@@ -177,6 +200,12 @@ int dsgd_destroy(dsgd_ctx* ctx);
  * (core/Slave.scala:134,149; proto.proto:51-63). */
 int dsgd_load_csr(dsgd_ctx* ctx, int64_t n_rows, const int64_t* row_ptr, const int32_t* col_1based, const float* val,
                   const int8_t* label);
+/* The same data with Double values ("THE FP64 MODE", Double feature values): fp64 contexts only (DSGD_ESTATE on an fp32
+ * one), dsgd_load_csr's validation and refusals (|v| <= 3e38 as there), DSGD_EUNSUPPORTED while a communicator is
+ * attached.  *bits_out of dsgd_value_bits: 64 after dsgd_load_csr_f64, 32 otherwise.                                 */
+int dsgd_load_csr_f64(dsgd_ctx* ctx, int64_t n_rows, const int64_t* row_ptr, const int32_t* col_1based, const double* val,
+                      const int8_t* label);
+int dsgd_value_bits(dsgd_ctx* ctx, int32_t* bits_out);
 int dsgd_n_rows(dsgd_ctx* ctx, int64_t* n_rows, int64_t* nnz);
 
 /* SparseSVM.dimSparsity: either given (dense, 0-based keys as Main.scala:62 builds them) ...  */

@@ -177,6 +177,18 @@ class SparseSVM {
     check(dsgd_load_csr(ctx_, data.n_rows, data.row_ptr.data(), data.col.data(), data.val.data(), data.label.data()));
     nRows_ = data.n_rows;
   }
+  // the same rows with the reference's Double values (utils/Dataset.scala:30; an fp64 context: include/dsgd.h "THE FP64
+  // MODE", Double feature values); val64 is parallel to data.col
+  void loadCsrF64(const Data& data, const std::vector<double>& val64) {
+    if (val64.size() != data.col.size()) throw std::invalid_argument("val64 must hold one value per entry of data.col");
+    check(dsgd_load_csr_f64(ctx_, data.n_rows, data.row_ptr.data(), data.col.data(), val64.data(), data.label.data()));
+    nRows_ = data.n_rows;
+  }
+  int valueBits() const {
+    int32_t bits = 0;
+    check(dsgd_value_bits(ctx_, &bits));
+    return bits;
+  }
   // Main.scala:54-65: dimSparsity from the first nTrain rows (incl. its off-by-one)
   Vec buildDimSparsity(int64_t nTrain) {
     Vec ds((size_t)d_ + 1);

@@ -293,6 +293,27 @@ JNIEXPORT void JNICALL NATIVE(loadCsr)(JNIEnv* env, jobject, jlong h, jlongArray
   if (rc) raise(env, rc);
 }
 
+// the same rows with the Vec's Double values as they are (an fp64 context: include/dsgd.h "THE FP64 MODE", Double feature values)
+JNIEXPORT void JNICALL NATIVE(loadCsrF64)(JNIEnv* env, jobject, jlong h, jlongArray rowPtr, jintArray col, jdoubleArray val,
+                                          jbyteArray label) {
+  if (!rowPtr || !col || !val || !label || env->GetArrayLength(col) != env->GetArrayLength(val) ||
+      env->GetArrayLength(rowPtr) != env->GetArrayLength(label) + 1) {   // (refused before any array is taken)
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "null array, or rowPtr / col / value / label lengths that do not fit");
+    return;
+  }
+  const jsize nRows = env->GetArrayLength(label);
+  int rc;
+  {
+    LongElems rp(env, rowPtr, JNI_ABORT);
+    IntElems c(env, col, JNI_ABORT);
+    DoubleElems v(env, val, JNI_ABORT);
+    ByteElems y(env, label, JNI_ABORT);
+    rc = dsgd_load_csr_f64(ctx(h), nRows, reinterpret_cast<const int64_t*>(rp.p), reinterpret_cast<const int32_t*>(c.p), v.p,
+                           reinterpret_cast<const int8_t*>(y.p));
+  }
+  if (rc) raise(env, rc);
+}
+
 // Main.scala:54-65 on the device
 JNIEXPORT void JNICALL NATIVE(buildDimSparsity)(JNIEnv* env, jobject, jlong h, jlong nTrain) {
   int rc = dsgd_build_dim_sparsity(ctx(h), nTrain, nullptr);

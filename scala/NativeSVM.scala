@@ -28,6 +28,8 @@ object NativeSVM {
   @native def getWeightsF64(ctx: Long, wOut: Array[Double]): Unit
   @native def planRunF64(ctx: Long, plan: Long, stepBegin: Long, stepEnd: Long, lr: Double): Unit
   @native def loadCsr(ctx: Long, rowPtr: Array[Long], col: Array[Int], value: Array[Float], label: Array[Byte]): Unit
+  // an fp64 context only: the values as the Vec holds them (utils/Dataset.scala:30 reads Doubles), no rounding to Float
+  @native def loadCsrF64(ctx: Long, rowPtr: Array[Long], col: Array[Int], value: Array[Double], label: Array[Byte]): Unit
   @native def buildDimSparsity(ctx: Long, nTrain: Long): Unit
   @native def gradient(ctx: Long, w: Array[Float], idx: Array[Int], gOut: Array[Float]): Long
   @native def forward(ctx: Long, w: Array[Float], idx: Array[Int], predOut: Array[Float]): Unit
@@ -118,22 +120,26 @@ class HipSVM(lambda: Number, dimSparsity: Vec, data: Array[(Vec, Int)], nTrain: 
     extends SparseSVM(lambda, dimSparsity) {
 
   private val dim = data(0)._1.size
-  private val ctx = NativeSVM.create(dim, lambda.toDouble, device)
+  // -Ddsgd.precision=fp64: an fp64 context that is given the Vec values as they are (INTEGRATION.md 3a)
+  private val fp64 = sys.props.get("dsgd.precision").contains("fp64")
+  private val ctx =
+    if (fp64) NativeSVM.createF64(dim, lambda.toDouble, device) else NativeSVM.create(dim, lambda.toDouble, device)
 
   {
     // Array[(Vec, Int)] -> CSR, columns ascending (the order of the text files, utils/Dataset.scala:19-34)
     val rowPtr = new Array[Long](data.length + 1)
     val cols   = Array.newBuilder[Int]
-    val vals   = Array.newBuilder[Float]
+    val vals   = Array.newBuilder[Double]
     val labels = new Array[Byte](data.length)
     var nnz    = 0L
     data.zipWithIndex.foreach {
       case ((x, y), i) =>
-        x.map.toSeq.sortBy(_._1).foreach { case (k, n) => cols += k; vals += n.toDouble.toFloat; nnz += 1 }
+        x.map.toSeq.sortBy(_._1).foreach { case (k, n) => cols += k; vals += n.toDouble; nnz += 1 }
         rowPtr(i + 1) = nnz
         labels(i) = y.toByte
     }
-    NativeSVM.loadCsr(ctx, rowPtr, cols.result(), vals.result(), labels)
+    if (fp64) NativeSVM.loadCsrF64(ctx, rowPtr, cols.result(), vals.result(), labels)
+    else NativeSVM.loadCsr(ctx, rowPtr, cols.result(), vals.result().map(_.toFloat), labels)
     NativeSVM.buildDimSparsity(ctx, nTrain)
   }
 

@@ -37,7 +37,13 @@ log("data loaded: {} ({}s)", data.n_rows, round(time.time() - t0, 2))
 n_train = int(data.n_rows * 0.8)                                              # Main.scala:52
 metrics = host.Metrics()
 with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device, precision=a.precision) as eng:
-    eng.load_csr(data.row_ptr, data.col, data.val, data.label)
+    # fp64 on real files: the parsed Doubles as the reference holds them (--synthetic is float by construction; the
+    # asynchronous fit runs resident plans, which hold float values)
+    values = data.val64 if a.precision == "fp64" and not cfg.async_ and getattr(data, "val64", None) is not None else data.val
+    eng.load_csr(data.row_ptr, data.col, values, data.label)
+    log("feature values: {} bits{}", eng.value_bits() if a.precision == "fp64" else 32,
+        " (fp64 asynchronous fit: resident plans hold float values, NOT the Double feature values)"
+        if a.precision == "fp64" and cfg.async_ and getattr(data, "val64", None) is not None else "")
     t0 = time.time()
     eng.build_dim_sparsity(n_train)                                            # Main.scala:54-65
     log("dim sparsity ({}s)", round(time.time() - t0, 3))
