@@ -528,45 +528,66 @@ __global__ void dsgd_ds64_kernel(const unsigned int* __restrict__ cnt, const int
   }
 }
 
-// x . w of row `row` in fp64 by the G lanes of a group: filt((double)x * w) per entry, lane-strided, then a butterfly
-template <int GR>
-__device__ __forceinline__ double row_dot64(const CsrView& m, long long row, const double* __restrict__ w, int sub) {
+// where rank r's weight is: rank order (Sp = 0) or the column slices' slice-major [CS64_G][Sp] (dsgd_update64_kernel's rule)
+__device__ __forceinline__ long long rp64_at(long long r, int Sp) { return Sp ? (r % CS64_G) * Sp + r / CS64_G : r; }
+
+// x . w of row `row` in fp64 by the GR lanes of a group, on float or Double values, the weights in either layout:
+// filt((double)x * w) per entry, lane-strided, then a butterfly.  (The layout is decided once per row, not per entry.)
+template <int GR, typename V>
+__device__ __forceinline__ double row_dot64(const CsrViewT<V>& m, long long row, const double* __restrict__ w, int Sp, int sub) {
 #pragma clang fp contract(off)
   const long long st = m.row_ptr[row], en = m.row_ptr[row + 1];
   double d = 0.0;
-  for (long long p = st + sub; p < en; p += GR) d = d + filt64((double)m.val[p] * w[m.col[p]]);
+  if (Sp == 0) {
+    for (long long p = st + sub; p < en; p += GR) d = d + filt64((double)m.val[p] * w[m.col[p]]);
+  } else {
+    for (long long p = st + sub; p < en; p += GR) d = d + filt64((double)m.val[p] * w[rp64_at(m.col[p], Sp)]);
+  }
 #pragma unroll
   for (int off = GR / 2; off >= 1; off >>= 1) d = d + __shfl_xor(d, off, GR);
   return d;
 }
 
-// prediction p = -signum(x.w) in fp64 (ref: core/ml/SparseSVM.scala:14, core/Slave.scala:129-140)
-__global__ void __launch_bounds__(256) dsgd_forward64_kernel(CsrView m, const double* __restrict__ w, const int* __restrict__ idx,
-                                                            long long n, float* pred, DevScalars* sc) {
+// prediction p = -signum(x.w) in fp64 (ref: core/ml/SparseSVM.scala:14, core/Slave.scala:129-140); w in rank order.
+// (threads: blockDim.x, read by the kernel itself -- only there does the compiler fold it under the uniform workgroup
+// assumption; read in an inlined body it costs a dependent load at the head of every launch.  So in every shared body.)
+template <typename V>
+__device__ __forceinline__ void forward64_body(const CsrViewT<V>& m, const double* __restrict__ w, const int* __restrict__ idx, long long n,
+                                               float* pred, DevScalars* sc, unsigned int threads) {
   const int sub = threadIdx.x % 16;
-  const long long group = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / 16;
-  const long long n_groups = (long long)gridDim.x * blockDim.x / 16;
+  const long long group = ((long long)blockIdx.x * threads + threadIdx.x) / 16;
+  const long long n_groups = (long long)gridDim.x * threads / 16;
   for (long long t = group; t < n; t += n_groups) {
     const long long row = idx[t];
     if (row < 0 || row >= m.n_rows) {
       if (sub == 0) atomicOr(&sc->err, 1);
       continue;
     }
-    const double d = row_dot64<16>(m, row, w, sub);
+    const double d = row_dot64<16>(m, row, w, 0, sub);
     if (sub == 0) pred[t] = d > 0.0 ? -1.0f : (d < 0.0 ? 1.0f : 0.0f);
   }
 }
+__global__ void __launch_bounds__(256) dsgd_forward64_kernel(CsrView m, const double* __restrict__ w, const int* __restrict__ idx,
+                                                            long long n, float* pred, DevScalars* sc) {
+  forward64_body(m, w, idx, n, pred, sc, blockDim.x);
+}
+__global__ void __launch_bounds__(256) dsgd_forward64v_kernel(CsrView64 m, const double* __restrict__ w, const int* __restrict__ idx,
+                                                             long long n, float* pred, DevScalars* sc) {
+  forward64_body(m, w, idx, n, pred, sc, blockDim.x);
+}
 
 // loss / accuracy tallies in fp64 (ref: core/Master.scala:100-107, core/ml/SparseSVM.scala:16-23): exact integer counts
-__global__ void __launch_bounds__(256) dsgd_eval64_kernel(CsrView m, const double* __restrict__ w, long long row_begin, long long row_end,
-                                                         DevScalars* sc) {
+template <typename V>
+__device__ __forceinline__ void eval64_body(const CsrViewT<V>& m, const double* __restrict__ w, long long row_begin, long long row_end,
+                                            DevScalars* sc, unsigned int threads) {
+#pragma clang fp contract(off)
   __shared__ unsigned int tally[4];
   const int sub = threadIdx.x % 16;
-  const long long group = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / 16;
-  const long long n_groups = (long long)gridDim.x * blockDim.x / 16;
+  const long long group = ((long long)blockIdx.x * threads + threadIdx.x) / 16;
+  const long long n_groups = (long long)gridDim.x * threads / 16;
   unsigned int c0 = 0, c1 = 0, c2 = 0;
   for (long long row = row_begin + group; row < row_end; row += n_groups) {
-    const double d = row_dot64<16>(m, row, w, sub);
+    const double d = row_dot64<16>(m, row, w, 0, sub);
     const double yd = (double)m.label[row] * d;
     if (sub == 0) {
       if (yd < 0.0) c0++;
@@ -576,6 +597,20 @@ __global__ void __launch_bounds__(256) dsgd_eval64_kernel(CsrView m, const doubl
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&sc->counts[3], (unsigned long long)(row_end - row_begin));
   block_tally3(c0, c1, c2, sc, tally);
+}
+__global__ void __launch_bounds__(256) dsgd_eval64_kernel(CsrView m, const double* __restrict__ w, long long row_begin, long long row_end,
+                                                         DevScalars* sc) {
+  eval64_body(m, w, row_begin, row_end, sc, blockDim.x);
+}
+__global__ void __launch_bounds__(256) dsgd_eval64v_kernel(CsrView64 m, const double* __restrict__ w, long long row_begin, long long row_end,
+                                                          DevScalars* sc) {
+  eval64_body(m, w, row_begin, row_end, sc, blockDim.x);
+}
+
+// dimSparsity's feature counts on Double values (colcount_body of dsgd_kernels.hpp: abs(v) > 1e-20 decided on the double)
+__global__ void __launch_bounds__(1024) dsgd_colcount64v_kernel(const int* __restrict__ col, const double* __restrict__ val, long long nnz,
+                                                               unsigned int* cnt, int dp, int hcnt, DevScalars* sc) {
+  colcount_body(col, val, nnz, cnt, dp, hcnt, sc, CS64_EPS);
 }
 
 // |w|^2 in fp64 (ref: math/Vec.scala:55): one workgroup, lane-strided, then the wave and workgroup sums in order

@@ -127,8 +127,7 @@ static bool available() {
 #include "dsgd_tcol.hpp"
 #include "dsgd_shuffle.hpp"
 #include "dsgd_cs64.hpp"   // (last: the fp64 mode)
-#include "dsgd_rp64.hpp"   // (... and its row-parallel gradient family)
-#include "dsgd_rp64v.hpp"  // (... and that family on Double feature values)
+#include "dsgd_rp64.hpp"   // (... and its row-parallel gradient family, on float and on Double feature values)
 #include "dsgd_sparse.hpp" // (the Sparse form at the boundary: compaction and scatter-in)
 
 // ------------------------------------------------------------------------------------------------
@@ -521,7 +520,7 @@ struct dsgd_ctx {
   int rp64_gk = 0;
   WorkSeg* d_rp64_gsegs = nullptr;
   unsigned long long* h_rp64_ranks = nullptr;
-  // Double feature values (dsgd_load_csr_f64; csrc/dsgd_rp64v.hpp): the values parallel to d_col / d_val (which holds them
+  // Double feature values (dsgd_load_csr_f64; csrc/dsgd_rp64.hpp): the values parallel to d_col / d_val (which holds them
   // rounded), and the low words of the two-word column sums ([rp64v_k][rp64_stride], zero between calls; the high words
   // are d_rp64_acc)
   double* d_val64 = nullptr;
@@ -573,25 +572,18 @@ static int bind(dsgd_ctx* c, bool keep_sliced = false) {  // host threads migrat
   if (c->cs_w_G && !keep_sliced) return cs_unslice(c);
   return DSGD_OK;
 }
-static CsrView view(dsgd_ctx* c) {
-  CsrView v;
+template <typename V>
+static CsrViewT<V> view_of(dsgd_ctx* c, const V* val) {
+  CsrViewT<V> v;
   v.n_rows = c->n_rows;
   v.row_ptr = c->d_row_ptr;
   v.col = c->d_col;
-  v.val = c->d_val;
+  v.val = val;
   v.label = c->d_label;
   return v;
 }
-
-static CsrView64 view64(dsgd_ctx* c) {   // (Double data loaded: dsgd_load_csr_f64)
-  CsrView64 v;
-  v.n_rows = c->n_rows;
-  v.row_ptr = c->d_row_ptr;
-  v.col = c->d_col;
-  v.val = c->d_val64;
-  v.label = c->d_label;
-  return v;
-}
+static CsrView view(dsgd_ctx* c) { return view_of(c, c->d_val); }
+static CsrView64 view64(dsgd_ctx* c) { return view_of(c, c->d_val64); }   // (Double data loaded: dsgd_load_csr_f64)
 
 // host -> device through a pinned buffer of the context: wait until the previous copy out of it has executed, then the
 // caller fills it and enqueues the copy (pin_sent); device -> host: enqueue into pin_out, synchronise, copy out.
@@ -1911,14 +1903,11 @@ static int count_columns(dsgd_ctx* c, long long nnz, unsigned int* d_cnt, bool f
   if (nnz > 0) {
     const int hcnt = std::min(c->dp, DSGD_LDS_FLOATS);
     const int blocks = (int)std::max<long long>(1, std::min<long long>((nnz + 4095) / 4096, c->n_cu));
-    if (features && c->d_val64) {   // dimSparsity's feature counts: abs(v) > 1e-20 on the Double (the ranking needs no more than the floats)
-      hipLaunchKernelGGL(dsgd_colcount64v_kernel, dim3(blocks), dim3(1024), sizeof(unsigned int) * hcnt, c->stream, c->d_col, c->d_val64, nnz,
-                         d_cnt, c->dp, hcnt, c->d_sc);
-      HIP_TRY(hipGetLastError());
-      return DSGD_OK;
-    }
-    hipLaunchKernelGGL(dsgd_colcount_kernel, dim3(blocks), dim3(1024), sizeof(unsigned int) * hcnt, c->stream, c->d_col,
-                       c->d_val, nnz, d_cnt, c->dp, hcnt, c->d_sc);
+    const size_t lds = sizeof(unsigned int) * hcnt;
+    if (features && c->d_val64)   // dimSparsity's feature counts: abs(v) > 1e-20 on the Double (the ranking needs no more than the floats)
+      hipLaunchKernelGGL(dsgd_colcount64v_kernel, dim3(blocks), dim3(1024), lds, c->stream, c->d_col, c->d_val64, nnz, d_cnt, c->dp, hcnt, c->d_sc);
+    else
+      hipLaunchKernelGGL(dsgd_colcount_kernel, dim3(blocks), dim3(1024), lds, c->stream, c->d_col, c->d_val, nnz, d_cnt, c->dp, hcnt, c->d_sc);
     HIP_TRY(hipGetLastError());
   }
   return DSGD_OK;
@@ -3601,7 +3590,7 @@ int dsgd_load_csr(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr, const int
   return load_csr_impl(c, n_rows, row_ptr, col, val, nullptr, label);
 }
 
-// Double feature values (include/dsgd.h "THE FP64 MODE", csrc/dsgd_rp64v.hpp): dsgd_load_csr's validation and refusals; the
+// Double feature values (include/dsgd.h "THE FP64 MODE", csrc/dsgd_rp64.hpp): dsgd_load_csr's validation and refusals; the
 // context keeps the doubles beside the values rounded to float (the ranking, the layout code: unchanged)
 int dsgd_load_csr_f64(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr, const int32_t* col, const double* val, const int8_t* label) {
   DSGD_TRY(check_ctx(c));
@@ -3985,6 +3974,8 @@ static int sync_step64_ranks(dsgd_ctx* c, const int32_t* const* idx_per_worker, 
 static int sync_step64_rows(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int n_workers, double lr,
                             dsgd_batch_stats* stats);
 static int refuse_val64(dsgd_ctx* c, const char* what);
+static int rp64_ensure(dsgd_ctx* c, int n_workers);   // (the row-parallel family, further down: async_step64's Double branch runs it)
+static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, int mode, double lr, double* delta = nullptr, bool gather = false);
 // what a one-step fp64 plan of n_workers lists and `rows` rows in all can hold (plan_frame's refusals, word for word): the
 // calls that run such a plan on float data keep these limits on Double data, where the row-parallel pair serves them
 static int cs64_step_limits(dsgd_ctx* c, int n_workers, long long rows) {
@@ -3998,8 +3989,6 @@ static int cs64_step_limits(dsgd_ctx* c, int n_workers, long long rows) {
                 4 * CS64_G - 1);
   return DSGD_OK;
 }
-static int rp64_ensure(dsgd_ctx* c, int n_workers);
-static int rp64v_launch(dsgd_ctx* c, int n_workers, long long max_items, int mode, double lr, double* delta);
 int dsgd_sync_step(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers,
                    float lr, dsgd_batch_stats* stats) {
   DSGD_TRY(check_ctx(c));
@@ -4865,7 +4854,7 @@ static int async_step64(dsgd_ctx* c, const char* what, const int32_t* idx, int64
     long long mx = 0, tot = 0;
     const int64_t nn = n;
     DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
-    DSGD_TRY(rp64v_launch(c, 1, mx, RP64V_ASYNC, lr, want_delta ? c->d_cs_dl64 : nullptr));
+    DSGD_TRY(rp64_launch(c, 1, mx, RP64_ASYNC, lr, want_delta ? c->d_cs_dl64 : nullptr));
     c->s_dirty = true;
     if (sparse) DSGD_TRY((sp_compact<double, double, false>(c, c->d_cs_dl64, nullptr)));
     DSGD_TRY(finish_stats(c, stats, n));
@@ -5007,9 +4996,20 @@ static int rp64_ensure(dsgd_ctx* c, int n_workers) {
     c->rp64_stride = stride;
     c->rp64_k = cap;
   }
+  // the second word of a column sum, in the shape of the first: Double data only (a float-data context never allocates it)
+  if (c->d_val64 && !(c->d_rp64v_lo && c->rp64v_k >= c->rp64_k && c->rp64v_stride == c->rp64_stride)) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    (void)hipFree(c->d_rp64v_lo);
+    c->d_rp64v_lo = nullptr;
+    c->rp64v_k = 0;
+    const size_t words = (size_t)c->rp64_stride * (size_t)c->rp64_k;
+    HIP_TRY(hipMalloc(&c->d_rp64v_lo, sizeof(unsigned long long) * words));
+    HIP_TRY(hipMemsetAsync(c->d_rp64v_lo, 0, sizeof(unsigned long long) * words, c->stream));
+    c->rp64v_k = c->rp64_k;
+    c->rp64v_stride = c->rp64_stride;
+  }
   return DSGD_OK;
 }
-// the two launches over the staged lists (c->cur_idx, c->d_segs); step = false: the gradient of worker 0 into d_rp64_g
 // ---- ... across ranks (a communicator attached with dsgd_comm_init_f64; csrc/dsgd_rp64.hpp "across ranks") ----
 static long long rp64_gather_pad(int world) { return ((long long)world + 63) & ~63LL; }
 static void rp64_gather_drop(dsgd_ctx* c) {   // (after a failure half way: the next step starts from a zeroed buffer)
@@ -5066,15 +5066,27 @@ static int rp64_gather(dsgd_ctx* c, int k) {
   HIP_TRY(hipGetLastError());
   return DSGD_OK;
 }
-static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, bool step, double lr, bool gather = false) {
-  const bool sliced = c->cs_w_G == CS64_G;   // (the weights stay in whichever layout they are: slice-major between plan runs)
+// The two launches over the staged lists (c->cur_idx, c->d_segs), on the context's float or Double values (rp64_ensure
+// came first).  mode: RP64_GRADIENT (worker 0's gradient into d_rp64_g), RP64_STEP, RP64_ASYNC (one worker; Double data
+// only -- float data's asynchronous step is a column-slice plan; delta: key order, may be null).  gather: the step under
+// a communicator (float data only: Double data refuses one).
+// The weights stay in whichever layout they are, slice-major between plan runs.  Double data can meet slice-major weights
+// too: plans are refused at their CREATION on Double data, but a plan made on float data outlives dsgd_load_csr_f64 (it
+// is laid out again for the new data and runs on the values rounded to float), and its run leaves the weights
+// slice-major for the next dsgd_gradient_f64 (w = NULL), dsgd_sync_step_f64 or dsgd_async_step_f64.  The bodies read
+// either layout through rp64_at; tests/test_gpu_fp64_values.py takes that path.
+static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, int mode, double lr, double* delta, bool gather) {
+  const bool v64 = c->d_val64 != nullptr;
+  if ((mode == RP64_ASYNC && !v64) || (gather && v64))   // (no such kernel; the entry points never ask)
+    return fail(DSGD_ESTATE, "internal: no row-parallel fp64 kernel for %s on %s values", gather ? "a gather" : "an asynchronous step",
+                v64 ? "Double" : "float");
+  const bool sliced = c->cs_w_G == CS64_G;
   const int Sp = sliced ? cs64_sp(c->dp) : 0;
   double* w = sliced ? c->d_cs_w64 : c->d_w64;
   constexpr long long rows_per_block = RP64_THREADS / RP64_GROUP;
   const long long bpw = std::max<long long>(1, std::min<long long>((max_items + rows_per_block - 1) / rows_per_block,
                                                                    std::max<long long>(1, (long long)c->n_cu * 2 / n_workers)));   // (each workgroup flushes its hot words once)
   Rp64Args a;
-  a.m = view(c);
   a.w = w;
   a.ds = c->d_ds64;
   a.Sp = Sp;
@@ -5084,118 +5096,63 @@ static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, bool ste
   a.idx = c->cur_idx;
   a.segs = c->d_segs;
   a.blocks_per_worker = bpw;
-  a.acc = c->d_rp64_acc;
+  a.with_s = mode == RP64_ASYNC ? 0 : 1;   // (the asynchronous iteration: s from dsgd_rp64v_s_sliced_kernel below)
+  a.acc[0] = c->d_rp64_acc;
+  a.acc[1] = v64 ? c->d_rp64v_lo : nullptr;
   a.acc_stride = c->rp64_stride;
   a.lambda = c->cfg.lambda;
   a.s_out = c->d_rp64_s;
   a.sc = c->d_sc;
   a.rank_word = nullptr;
   Rp64FinishArgs f;
-  f.acc = c->d_rp64_acc;
-  f.acc_stride = c->rp64_stride;
+  f.acc[0] = a.acc[0];
+  f.acc[1] = a.acc[1];
+  f.acc_stride = a.acc_stride;
   f.segs = c->d_segs;
   f.K = n_workers;
+  const dim3 th(RP64_THREADS), gg((unsigned)(bpw * n_workers + a.with_s));
+  const dim3 fg((unsigned)std::min<long long>(((long long)c->dp + RP64_THREADS - 1) / RP64_THREADS, (long long)c->n_cu * 4));
   if (gather) {   // this rank's slots of the gather buffer; the finish over every rank's workers
     unsigned long long* slots = c->d_rp64_gath + rp64_gather_pad(c->world);
-    a.acc = slots + (long long)c->rank * n_workers * c->rp64_gstride;
+    a.acc[0] = slots + (long long)c->rank * n_workers * c->rp64_gstride;
     a.acc_stride = c->rp64_gstride;
     a.rank_word = c->d_rp64_gath + c->rank;
-    hipLaunchKernelGGL(dsgd_rp64_grad_gather_kernel, dim3((unsigned)(bpw * n_workers + 1)), dim3(RP64_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(dsgd_rp64_grad_gather_kernel, gg, th, 0, c->stream, view(c), a);
     HIP_TRY(hipGetLastError());
     DSGD_TRY(rp64_gather(c, n_workers));
-    f.acc = slots;
+    f.acc[0] = slots;
     f.acc_stride = c->rp64_gstride;
     f.segs = c->d_rp64_gsegs;
     f.K = n_workers * c->world;
+  } else if (v64) {
+    hipLaunchKernelGGL(dsgd_rp64v_grad_kernel, gg, th, 0, c->stream, view64(c), a);
+    HIP_TRY(hipGetLastError());
   } else {
-    hipLaunchKernelGGL(dsgd_rp64_grad_kernel, dim3((unsigned)(bpw * n_workers + 1)), dim3(RP64_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(dsgd_rp64_grad_kernel, gg, th, 0, c->stream, view(c), a);
     HIP_TRY(hipGetLastError());
   }
-  f.dp = c->dp;
-  f.vexp = c->vexp;
-  f.Sp = Sp;
-  f.s = c->d_rp64_s;
-  f.perm = c->d_perm;
-  f.g_out = c->d_rp64_g;
-  f.w = w;
-  f.lr = lr;
-  const dim3 fg((unsigned)std::min<long long>(((long long)c->dp + RP64_THREADS - 1) / RP64_THREADS, (long long)c->n_cu * 4));
-  if (step)
-    hipLaunchKernelGGL(dsgd_rp64_finish_kernel<true>, fg, dim3(RP64_THREADS), 0, c->stream, f);
-  else
-    hipLaunchKernelGGL(dsgd_rp64_finish_kernel<false>, fg, dim3(RP64_THREADS), 0, c->stream, f);
-  HIP_TRY(hipGetLastError());
-  return DSGD_OK;
-}
-
-// ---- ... on Double feature values (dsgd_load_csr_f64; csrc/dsgd_rp64v.hpp): the same two launches over two-word sums ----
-static int rp64v_ensure(dsgd_ctx* c) {   // (behind rp64_ensure: the high words are d_rp64_acc)
-  if (c->d_rp64v_lo && c->rp64v_k >= c->rp64_k && c->rp64v_stride == c->rp64_stride) return DSGD_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  (void)hipFree(c->d_rp64v_lo);
-  c->d_rp64v_lo = nullptr;
-  c->rp64v_k = 0;
-  const size_t words = (size_t)c->rp64_stride * (size_t)c->rp64_k;
-  HIP_TRY(hipMalloc(&c->d_rp64v_lo, sizeof(unsigned long long) * words));
-  HIP_TRY(hipMemsetAsync(c->d_rp64v_lo, 0, sizeof(unsigned long long) * words, c->stream));
-  c->rp64v_k = c->rp64_k;
-  c->rp64v_stride = c->rp64_stride;
-  return DSGD_OK;
-}
-// mode: RP64V_GRADIENT (worker 0's gradient into d_rp64_g), RP64V_STEP, RP64V_ASYNC (one worker; delta: key order, may be null)
-static int rp64v_launch(dsgd_ctx* c, int n_workers, long long max_items, int mode, double lr, double* delta) {
-  DSGD_TRY(rp64v_ensure(c));
-  const bool sliced = c->cs_w_G == CS64_G;   // (the weights stay in whichever layout they are: slice-major between plan runs)
-  const int Sp = sliced ? cs64_sp(c->dp) : 0;
-  double* w = sliced ? c->d_cs_w64 : c->d_w64;
-  constexpr long long rows_per_block = RP64_THREADS / RP64_GROUP;
-  const long long bpw = std::max<long long>(1, std::min<long long>((max_items + rows_per_block - 1) / rows_per_block,
-                                                                   std::max<long long>(1, (long long)c->n_cu * 2 / n_workers)));
-  Rp64vArgs a;
-  a.m = view64(c);
-  a.w = w;
-  a.ds = c->d_ds64;
-  a.Sp = Sp;
-  a.dp = c->dp;
-  a.vexp = c->vexp;
-  a.K = n_workers;
-  a.idx = c->cur_idx;
-  a.segs = c->d_segs;
-  a.blocks_per_worker = bpw;
-  a.hi = reinterpret_cast<long long*>(c->d_rp64_acc);
-  a.lo = c->d_rp64v_lo;
-  a.acc_stride = c->rp64_stride;
-  a.lambda = c->cfg.lambda;
-  a.s_out = c->d_rp64_s;
-  a.sc = c->d_sc;
-  a.with_s = mode == RP64V_ASYNC ? 0 : 1;   // (the asynchronous iteration: s from dsgd_rp64v_s_sliced_kernel below)
-  hipLaunchKernelGGL(dsgd_rp64v_grad_kernel, dim3((unsigned)(bpw * n_workers + a.with_s)), dim3(RP64_THREADS), 0, c->stream, a);
-  HIP_TRY(hipGetLastError());
-  if (mode == RP64V_ASYNC) {   // s in the order of the float data's asynchronous kernel (the same bits on values a float holds)
+  if (mode == RP64_ASYNC) {   // s in the order of the float data's asynchronous kernel (the same bits on values a float holds)
     hipLaunchKernelGGL(dsgd_rp64v_s_sliced_kernel, dim3(1), dim3(CS_THREADS), 0, c->stream, w, c->d_ds64, Sp, c->dp, c->cfg.lambda, c->d_rp64_s);
     HIP_TRY(hipGetLastError());
   }
-  Rp64vFinishArgs f;
-  f.hi = a.hi;
-  f.lo = a.lo;
-  f.acc_stride = c->rp64_stride;
-  f.segs = c->d_segs;
-  f.K = n_workers;
   f.dp = c->dp;
   f.vexp = c->vexp;
   f.Sp = Sp;
   f.s = c->d_rp64_s;
   f.perm = c->d_perm;
-  f.g_out = mode == RP64V_ASYNC ? delta : c->d_rp64_g;
+  f.g_out = mode == RP64_ASYNC ? delta : c->d_rp64_g;
   f.w = w;
   f.lr = lr;
-  const dim3 fg((unsigned)std::min<long long>(((long long)c->dp + RP64_THREADS - 1) / RP64_THREADS, (long long)c->n_cu * 4));
-  if (mode == RP64V_STEP)
-    hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64V_STEP>, fg, dim3(RP64_THREADS), 0, c->stream, f);
-  else if (mode == RP64V_ASYNC)
-    hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64V_ASYNC>, fg, dim3(RP64_THREADS), 0, c->stream, f);
+  if (mode == RP64_ASYNC)
+    hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64_ASYNC>, fg, th, 0, c->stream, f);
+  else if (mode == RP64_STEP && v64)
+    hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64_STEP>, fg, th, 0, c->stream, f);
+  else if (mode == RP64_STEP)
+    hipLaunchKernelGGL(dsgd_rp64_finish_kernel<true>, fg, th, 0, c->stream, f);
+  else if (v64)
+    hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64_GRADIENT>, fg, th, 0, c->stream, f);
   else
-    hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64V_GRADIENT>, fg, dim3(RP64_THREADS), 0, c->stream, f);
+    hipLaunchKernelGGL(dsgd_rp64_finish_kernel<false>, fg, th, 0, c->stream, f);
   HIP_TRY(hipGetLastError());
   return DSGD_OK;
 }
@@ -5229,8 +5186,7 @@ int dsgd_gradient_f64(dsgd_ctx* c, const double* w, const int32_t* idx, int64_t 
   DSGD_TRY(reset_counters(c));
   long long mx = 0, tot = 0;
   DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
-  if (c->d_val64) DSGD_TRY(rp64v_launch(c, 1, mx, RP64V_GRADIENT, 0.0, nullptr));
-  else DSGD_TRY(rp64_launch(c, 1, mx, false, 0.0));
+  DSGD_TRY(rp64_launch(c, 1, mx, RP64_GRADIENT, 0.0));
   const size_t bytes = sizeof(double) * (size_t)c->dp;
   DSGD_TRY(pin_acquire(c->pin_out, bytes));
   HIP_TRY(hipMemcpyAsync(c->pin_out.p, c->d_rp64_g, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -5255,7 +5211,7 @@ static int sync_step64_ranks(dsgd_ctx* c, const int32_t* const* idx_per_worker, 
   DSGD_TRY(reset_counters(c));
   long long mx = 0, tot = 0;
   DSGD_TRY(stage_lists(c, idx_per_worker, n_per_worker, n_workers, &mx, &tot));
-  int rc = rp64_launch(c, n_workers, mx, true, lr, true);
+  int rc = rp64_launch(c, n_workers, mx, RP64_STEP, lr, nullptr, true);
   if (rc == DSGD_OK) {
     c->s_dirty = true;
     rc = finish_stats(c, stats, tot);
@@ -5287,8 +5243,7 @@ static int sync_step64_rows(dsgd_ctx* c, const int32_t* const* idx_per_worker, c
   DSGD_TRY(reset_counters(c));
   long long mx = 0, tot = 0;
   DSGD_TRY(stage_lists(c, idx_per_worker, n_per_worker, n_workers, &mx, &tot));
-  if (c->d_val64) DSGD_TRY(rp64v_launch(c, n_workers, mx, RP64V_STEP, lr, nullptr));
-  else DSGD_TRY(rp64_launch(c, n_workers, mx, true, lr));
+  DSGD_TRY(rp64_launch(c, n_workers, mx, RP64_STEP, lr));
   c->s_dirty = true;
   return finish_stats(c, stats, tot);
 }
@@ -5696,8 +5651,7 @@ int dsgd_gradient_sparse_f64(dsgd_ctx* c, const int32_t* w_key, const double* w_
   DSGD_TRY(reset_counters(c));
   long long mx = 0, tot = 0;
   DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
-  if (c->d_val64) DSGD_TRY(rp64v_launch(c, 1, mx, RP64V_GRADIENT, 0.0, nullptr));
-  else DSGD_TRY(rp64_launch(c, 1, mx, false, 0.0));
+  DSGD_TRY(rp64_launch(c, 1, mx, RP64_GRADIENT, 0.0));
   DSGD_TRY((sp_compact<double, double, false>(c, c->d_rp64_g, nullptr)));   // (the finish leaves the gradient in key order)
   DSGD_TRY(read_scalars(c));   // the one synchronisation of the call
   DSGD_TRY(check_err_flag(c));

@@ -134,13 +134,16 @@ struct WorkSeg {
   long long end;
 };
 
-struct CsrView {
+template <typename V>   // V: float, or double for the fp64 mode's Double feature values (dsgd_load_csr_f64)
+struct CsrViewT {
   long long n_rows;
   const long long* __restrict__ row_ptr;
   const int* __restrict__ col;  // frequency-ranked ids
-  const float* __restrict__ val;
+  const V* __restrict__ val;
   const signed char* __restrict__ label;
 };
+using CsrView = CsrViewT<float>;
+using CsrView64 = CsrViewT<double>;
 
 // v + (v of the lane selected by a DPP control), no LDS crossbar round trip
 template <int CTRL>
@@ -386,15 +389,16 @@ __global__ void __launch_bounds__(1024) dsgd_eval_kernel(CsrView m, const float*
 // Entries with abs(value) <= 1e-20 are not counted: the reference's Sparse constructor drops them
 // before any key set is taken (math/Sparse.scala:108-118), and the padding element of an empty row
 // (value 0) must stay invisible.
-__global__ void __launch_bounds__(1024) dsgd_colcount_kernel(const int* __restrict__ col, const float* __restrict__ val,
-                                                            long long nnz, unsigned int* cnt, int dp, int hcnt,
-                                                            DevScalars* sc) {
+// (eps: the 1e-20 in the value's own type -- a Double value is decided as a double, (float)v may fall on the other side)
+template <typename V>
+__device__ __forceinline__ void colcount_body(const int* __restrict__ col, const V* __restrict__ val, long long nnz, unsigned int* cnt,
+                                              int dp, int hcnt, DevScalars* sc, V eps) {
   extern __shared__ __attribute__((aligned(16))) unsigned int lcnt[];
   for (int j = threadIdx.x; j < hcnt; j += 1024) lcnt[j] = 0u;
   __syncthreads();
   for (long long p = (long long)blockIdx.x * 1024 + threadIdx.x; p < nnz; p += (long long)gridDim.x * 1024) {
     const int c = col[p];
-    if (!(fabsf(val[p]) > DSGD_EPS)) continue;
+    if (!(fabs(val[p]) > eps)) continue;
     if (c < 0 || c >= dp) {
       atomicOr(&sc->err, 1);
       continue;
@@ -407,6 +411,11 @@ __global__ void __launch_bounds__(1024) dsgd_colcount_kernel(const int* __restri
     const unsigned int v = lcnt[j];
     if (v) atomicAdd(&cnt[j], v);
   }
+}
+__global__ void __launch_bounds__(1024) dsgd_colcount_kernel(const int* __restrict__ col, const float* __restrict__ val,
+                                                            long long nnz, unsigned int* cnt, int dp, int hcnt,
+                                                            DevScalars* sc) {
+  colcount_body(col, val, nnz, cnt, dp, hcnt, sc, DSGD_EPS);
 }
 
 // col[p] <- perm[col[p]]

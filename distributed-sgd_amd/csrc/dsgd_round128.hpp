@@ -1,4 +1,4 @@
-// ONE rounding of a two-word fixed-point sum to double (csrc/dsgd_rp64v.hpp: the finish of the Double-value gradient).
+// ONE rounding of a two-word fixed-point sum to double (csrc/dsgd_rp64.hpp, Rp64Acc<double>::round: the finish of the Double-value gradient).
 //
 // The sum is T = HI * 2^32 + LO, HI a signed and LO an unsigned 64-bit word: an exact integer of up to 97 bits.  The
 // result is the double nearest to T * 2^exp2, ties to even -- written out as shift, round bit and sticky bit over the two

@@ -1,31 +1,50 @@
 // Device code of libdsgd_hip, part 9 (gfx950 only): the fp64 mode's row-parallel gradient family -- the request /
 // response gradient of one worker (SlaveImpl.gradient in Double, core/Slave.scala:142-157) and synchronous steps of ANY
 // number of workers and rows (Master.fit's batch closure, core/Master.scala:184-197), where the column-slice plans of
-// dsgd_cs64.hpp stop (<= 4 workers, <= 1,024 rows per step).  Included by dsgd_hip.hip after dsgd_cs64.hpp.
+// dsgd_cs64.hpp stop (<= 4 workers, <= 1,024 rows per step) -- on float feature values and on DOUBLE ones
+// (dsgd_load_csr_f64: the reference reads `elems(1).toDouble`, utils/Dataset.scala:30, and keeps every digit of the file;
+// there also the asynchronous iteration, core/Slave.scala:99-101).  Included by dsgd_hip.hip after dsgd_cs64.hpp.
 //
-// Two launches per call:
-//   dsgd_rp64_grad_kernel    one 16-lane group per listed row: x . w in fp64 (filt((double)x * w) per entry, as
-//                            row_dot64), the gate !(y * d < 0) (core/ml/SparseSVM.scala:27-28), and for an active row
-//                            y * x added into the worker's 64-bit fixed-point column accumulators (rank order) with integer
-//                            atomics.  The last workgroup of the grid computes s = lambda * 2 * (w . ds) meanwhile.
-//   dsgd_rp64_finish_kernel  per column: ONE rounding of each worker's exact sum, the support-only regulariser, and either
-//                            the gradient in key order or the step's fold over the workers, mean and update
-//                            (oracle/oracle.c orc_gradient / orc_sync_step, operation for operation); the accumulators are
-//                            left zeroed for the next call.
+// Two launches per call, each ONE body over the value type V of the CSR view:
+//   rp64_grad_body<V, GATHER>   one 16-lane group per listed row: x . w in fp64 (row_dot64: filt((double)x * w) per entry),
+//                               the gate !(y * d < 0) (core/ml/SparseSVM.scala:27-28), and for an active row y * x added
+//                               into the worker's fixed-point column accumulators (rank order) with integer atomics.  The
+//                               last workgroup of the grid computes s = lambda * 2 * (w . ds) meanwhile (with_s).
+//   rp64_finish_body<V, MODE>   per column: ONE rounding of each worker's exact sum, the support-only regulariser, and
+//                               the gradient in key order (GRADIENT), the step's fold over the workers, mean and update
+//                               (STEP), or one worker's asynchronous iteration and its delta (ASYNC; Double values only:
+//                               float data's runs in dsgd_cs64_async_kernel) -- oracle/oracle.c orc_gradient /
+//                               orc_sync_step / orc_async_step, operation for operation; the accumulators are left zeroed
+//                               for the next call.
+// The kernels are thin wrappers with stable names: dsgd_rp64_grad_kernel, dsgd_rp64_grad_gather_kernel,
+// dsgd_rp64_finish_kernel<STEP> (float values), dsgd_rp64v_grad_kernel, dsgd_rp64v_finish_kernel<MODE> (Double values).
 //
-// Under a communicator (dsgd_comm_init_f64; "across ranks" below) the sums go into this rank's slots of a gather buffer
-// (dsgd_rp64_grad_gather_kernel: the same body), the buffer travels, dsgd_rp64_header_kernel turns the gathered headers
-// into the finish's list ranges, and dsgd_rp64_finish_kernel<true> folds every rank's workers.
+// Under a communicator (dsgd_comm_init_f64; "across ranks" below; float values only) the sums go into this rank's slots of a
+// gather buffer (GATHER), the buffer travels, dsgd_rp64_header_kernel turns the gathered headers into the finish's list
+// ranges, and dsgd_rp64_finish_kernel<true> folds every rank's workers.
 //
-// The grid: a worker's list of n rows (duplicates count) adds entries of |x| <= 2^vexp scaled by 2^shift, shift = 62 -
-// ceil(log2 n): no column sum leaves the 64-bit range.  Integer sums do not depend on the order of the adds -- the result
-// is bit-reproducible, whatever the list's order or the grid.  An entry of exponent e is exact on the grid when
-// e >= vexp - (39 - ceil(log2 n)) (include/dsgd.h "THE FP64 MODE").
+// The grid.  A worker's list of n rows (duplicates count) adds entries of |x| <= 2^vexp.  With S = 62 - ceil(log2 n) and
+// v = +-x * 2^(S - vexp) (a power of two: exact) an entry becomes Rp64Acc<V>::WORDS 64-bit integers, and no column sum of n
+// of them leaves its word:
+//   float values, ONE word    q  = rn(v)                 (|q| <= 2^S: n of them stay inside 2^62)
+//   Double values, TWO words  h  = floor(v)              signed HI      (|h| <= 2^S)
+//                             lo = rn((v - h) * 2^32)    unsigned LO    (v - h is exact and in [0, 1): lo <= 2^32, n of them
+//                                                                        stay inside 2^63 -- no carry between the words)
+// and the sum is q * 2^(vexp - S), or (HI * 2^32 + LO) * 2^(vexp - S - 32), rounded ONCE.  Integer sums do not depend on the
+// order of the adds: the result is bit-reproducible whatever the list's order or the launch's shape.  An entry of exponent
+// e (|x| in [2^e, 2^(e+1))) is exact on the grid when e >= vexp - (39 - ceil(log2 n)) as a float (its last bit is at
+// 2^(e - 23)) and when e >= vexp - (42 - ceil(log2 n)) as a double (2^(e - 52)): the two-word range is no narrower; below
+// it an entry is off by at most half a grid unit (include/dsgd.h "THE FP64 MODE").  A Double value that a float holds
+// exactly inside the one-word range has lo == 0 and h == q: its second atomic is skipped and dsgd_round128 of (h, 0) is
+// (double)q * 2^(vexp - S) -- the float-data call's bits.
+//
+// Rp64Acc<V>::quantise and Rp64Acc<V>::round are the ONLY code here that depends on the value type.
 //
 // The weights are read (and a step's update written) in whichever layout they are: rank order (Sp = 0) or the column
-// slices' slice-major [CS64_G][Sp] (dsgd_update64_kernel's rule).  Every function opens with
-// `#pragma clang fp contract(off)`, as in dsgd_cs64.hpp.
+// slices' slice-major [CS64_G][Sp] (rp64_at).  Every function opens with `#pragma clang fp contract(off)`, as in
+// dsgd_cs64.hpp.
 #pragma once
+#include "dsgd_round128.hpp"
 
 constexpr int RP64_THREADS = 256;
 constexpr int RP64_GROUP = 16;   // lanes per row (row_dot64<16>)
@@ -34,7 +53,6 @@ constexpr int RP64_GROUP = 16;   // lanes per row (row_dot64<16>)
 // of 65,536 rows: 1.9 ms, 13x the fp32 gradient)
 constexpr int RP64_HOT = 1024;
 
-__device__ __forceinline__ long long rp64_at(long long r, int Sp) { return Sp ? (r % CS64_G) * Sp + r / CS64_G : r; }
 __host__ __device__ constexpr int rp64_ceil_log2(long long n) {
   int l = 0;
   while ((1LL << l) < n) ++l;
@@ -55,15 +73,47 @@ constexpr int RP64_HDR_N = 0, RP64_HDR_ACTIVE = 1, RP64_HDR_WORDS = 2;
 constexpr long long RP64_MSG_WORDS = (1LL << 20) / (long long)sizeof(unsigned long long);
 __host__ __device__ constexpr long long rp64_gather_stride(int dp) { return ((long long)dp + RP64_HDR_WORDS + 63) & ~63LL; }
 
+// ---- the accumulator policy: how one entry becomes integer words, and how the words' sums become ONE double ----
+template <typename V>
+struct Rp64Acc;
+template <>
+struct Rp64Acc<float> {
+  static constexpr int WORDS = 1;
+  __device__ __forceinline__ static void quantise(double v, unsigned long long (&q)[1]) {
+#pragma clang fp contract(off)
+    q[0] = (unsigned long long)__double2ll_rn(v);   // (two's complement: one add)
+  }
+  // the sum t[0] * 2^e2 (the power of two is exact)
+  __device__ __forceinline__ static double round(const unsigned long long (&t)[1], int e2) {
+#pragma clang fp contract(off)
+    return (double)(long long)t[0] * ldexp(1.0, e2);
+  }
+};
+template <>
+struct Rp64Acc<double> {
+  static constexpr int WORDS = 2;   // HI (signed), LO
+  __device__ __forceinline__ static void quantise(double v, unsigned long long (&q)[2]) {
+#pragma clang fp contract(off)
+    const double fl = floor(v);
+    q[0] = (unsigned long long)(long long)fl;                                  // |fl| <= 2^62: exact
+    q[1] = (unsigned long long)__double2ll_rn((v - fl) * 4294967296.0);        // v - fl: exact, in [0, 1)
+  }
+  // the sum (t[0] * 2^32 + t[1]) * 2^(e2 - 32)
+  __device__ __forceinline__ static double round(const unsigned long long (&t)[2], int e2) {
+    return dsgd_round128((long long)t[0], t[1], e2 - 32);
+  }
+};
+constexpr int RP64_MAX_WORDS = 2;
+
 struct Rp64Args {
-  CsrView m;
   const double* w;                 // the weights, rank order (Sp = 0) or slice-major
   const double* ds;                // dimSparsity, rank order
   int Sp, dp, vexp, K;
   const int* idx;                  // the lists, concatenated
   const WorkSeg* segs;             // [K] each worker's [begin, end) in idx
-  long long blocks_per_worker;     // grid = K * blocks_per_worker + 1 (the last workgroup: s)
-  unsigned long long* acc;         // [K][acc_stride] fixed-point column sums, rank order; zero on entry
+  long long blocks_per_worker;     // grid = K * blocks_per_worker + with_s
+  int with_s;                      // 1: one more workgroup, the last, computes s (0: the caller's own kernel does)
+  unsigned long long* acc[RP64_MAX_WORDS];   // per word [K][acc_stride] fixed-point column sums, rank order; zero on entry
   long long acc_stride;
   double lambda;
   double* s_out;                   // s = lambda * 2.0 * (w . ds)
@@ -71,28 +121,18 @@ struct Rp64Args {
   unsigned long long* rank_word;   // (the gather of a communicator only) this rank's word of the gather buffer: K
 };
 
-// x . w of `row` by the 16 lanes of a group, in whichever layout the weights are (row_dot64's arithmetic and order)
-__device__ __forceinline__ double rp64_row_dot(const CsrView& m, long long row, const double* __restrict__ w, int Sp, int sub) {
+// GATHER: `acc[0]` are this rank's K slots of a communicator's gather buffer (see above: one word per column) -- a slot's
+// header words get the list length and the active count, the rank's word gets K, all with ordinary stores / vector atomics
+template <typename V, bool GATHER>
+__device__ __forceinline__ void rp64_grad_body(const CsrViewT<V>& m, const Rp64Args& a) {
 #pragma clang fp contract(off)
-  if (Sp == 0) return row_dot64<RP64_GROUP>(m, row, w, sub);
-  const long long st = m.row_ptr[row], en = m.row_ptr[row + 1];
-  double d = 0.0;
-  for (long long p = st + sub; p < en; p += RP64_GROUP) d = d + filt64((double)m.val[p] * w[rp64_at(m.col[p], Sp)]);
-#pragma unroll
-  for (int off = RP64_GROUP / 2; off >= 1; off >>= 1) d = d + __shfl_xor(d, off, RP64_GROUP);
-  return d;
-}
-
-// GATHER: `acc` are this rank's K slots of a communicator's gather buffer (see below) -- a slot's header words get the
-// list length and the active count, the rank's word gets K, all with ordinary stores / vector atomics
-template <bool GATHER>
-__device__ __forceinline__ void rp64_grad_body(const Rp64Args& a) {
-#pragma clang fp contract(off)
+  constexpr int WORDS = Rp64Acc<V>::WORDS;
+  static_assert(!GATHER || WORDS == 1, "a gather slot holds one word per column");
   __shared__ double red[RP64_THREADS / 64];
   __shared__ unsigned int n_act;
-  __shared__ unsigned long long hot[RP64_HOT];
+  __shared__ unsigned long long hot[WORDS][RP64_HOT];
   const int tid = threadIdx.x;
-  const long long last = (long long)gridDim.x - 1;
+  const long long last = a.with_s ? (long long)gridDim.x - 1 : -1;
   if ((long long)blockIdx.x == last) {
     // ---- s of the weights the rows see: filt(w * ds) per column (orc_dense_dot), lane-strided, then the wave
     //      butterflies and the four wave sums in order: the same bits on every call ----
@@ -111,89 +151,124 @@ __device__ __forceinline__ void rp64_grad_body(const Rp64Args& a) {
   const WorkSeg seg = a.segs[k];
   const long long n = seg.end - seg.begin;
   const double qscale = ldexp(1.0, rp64_shift(n) - a.vexp);   // (a power of two: x * qscale is exact)
-  unsigned long long* acc = a.acc + (long long)k * a.acc_stride;
+  unsigned long long* acc[WORDS];
+#pragma unroll
+  for (int i = 0; i < WORDS; ++i) acc[i] = a.acc[i] + (long long)k * a.acc_stride;
   const int sub = tid % RP64_GROUP;
   const long long groups = a.blocks_per_worker * (RP64_THREADS / RP64_GROUP);
   if (tid == 0) n_act = 0u;
-  for (int i = tid; i < RP64_HOT; i += RP64_THREADS) hot[i] = 0ull;
+  for (int j = tid; j < RP64_HOT; j += RP64_THREADS) {
+#pragma unroll
+    for (int i = 0; i < WORDS; ++i) hot[i][j] = 0ull;
+  }
   __syncthreads();
   unsigned int mine = 0u;
   for (long long t = b * (RP64_THREADS / RP64_GROUP) + tid / RP64_GROUP; t < n; t += groups) {
     const long long row = a.idx[seg.begin + t];
-    if (row < 0 || row >= a.m.n_rows) {   // (the host checked the lists: never taken)
+    if (row < 0 || row >= m.n_rows) {   // (the host checked the lists: never taken)
       if (sub == 0) atomicOr(&a.sc->err, 1);
       continue;
     }
-    const double d = rp64_row_dot(a.m, row, a.w, a.Sp, sub);
-    const double y = (double)a.m.label[row];
+    const double d = row_dot64<RP64_GROUP>(m, row, a.w, a.Sp, sub);
+    const double y = (double)m.label[row];
     if (y * d < 0.0) continue;                                   // ref: core/ml/SparseSVM.scala:27-28 (zerosLike)
     mine += sub == 0 ? 1u : 0u;
     const double cq = y > 0.0 ? qscale : -qscale;
-    const long long st = a.m.row_ptr[row], en = a.m.row_ptr[row + 1];
+    const long long st = m.row_ptr[row], en = m.row_ptr[row + 1];
     for (long long p = st + sub; p < en; p += RP64_GROUP) {
-      const float x = a.m.val[p];
-      if (!(fabs((double)x) > CS64_EPS)) continue;   // filt(x * y): the Sparse constructor's filter (math/Sparse.scala:104)
-      const long long q = __double2ll_rn((double)x * cq);
-      const int c = a.m.col[p];
-      if (q == 0) continue;
-      if (c < RP64_HOT)
-        atomicAdd(&hot[c], (unsigned long long)q);
-      else
-        atomicAdd(&acc[c], (unsigned long long)q);
+      const double x = (double)m.val[p];
+      if (!(fabs(x) > CS64_EPS)) continue;   // filt(x * y): the Sparse constructor's filter (math/Sparse.scala:104)
+      unsigned long long q[WORDS];
+      Rp64Acc<V>::quantise(x * cq, q);
+      const int c = m.col[p];
+#pragma unroll
+      for (int i = 0; i < WORDS; ++i) {   // (a zero word adds nothing: its atomic is skipped)
+        if (q[i] == 0ull) continue;
+        if (c < RP64_HOT)
+          atomicAdd(&hot[i][c], q[i]);
+        else
+          atomicAdd(&acc[i][c], q[i]);
+      }
     }
   }
   if (mine) atomicAdd(&n_act, mine);
   __syncthreads();
-  for (int i = tid; i < RP64_HOT; i += RP64_THREADS) {   // (a word is non-zero only below dp)
-    const unsigned long long v = hot[i];
-    if (v) atomicAdd(&acc[i], v);
+  for (int j = tid; j < RP64_HOT; j += RP64_THREADS) {   // (a word is non-zero only below dp)
+#pragma unroll
+    for (int i = 0; i < WORDS; ++i) {
+      const unsigned long long v = hot[i][j];
+      if (v) atomicAdd(&acc[i][j], v);
+    }
   }
   if (GATHER) {
-    if (tid == 0 && b == 0) acc[a.dp + RP64_HDR_N] = (unsigned long long)n;   // (zero until here, like every word of the slot)
-    if (tid == 0 && n_act) atomicAdd(&acc[a.dp + RP64_HDR_ACTIVE], (unsigned long long)n_act);
+    if (tid == 0 && b == 0) acc[0][a.dp + RP64_HDR_N] = (unsigned long long)n;   // (zero until here, like every word of the slot)
+    if (tid == 0 && n_act) atomicAdd(&acc[0][a.dp + RP64_HDR_ACTIVE], (unsigned long long)n_act);
   } else {
     if (tid == 0 && n_act) atomicAdd(&a.sc->n_active, (unsigned long long)n_act);
   }
 }
-__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_kernel(Rp64Args a) { rp64_grad_body<false>(a); }
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_kernel(CsrView m, Rp64Args a) { rp64_grad_body<float, false>(m, a); }
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_gather_kernel(CsrView m, Rp64Args a) { rp64_grad_body<float, true>(m, a); }
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_grad_kernel(CsrView64 m, Rp64Args a) { rp64_grad_body<double, false>(m, a); }
 
 struct Rp64FinishArgs {
-  unsigned long long* acc;   // [K][acc_stride], zeroed here
+  unsigned long long* acc[RP64_MAX_WORDS];   // per word [K][acc_stride], zeroed here
   long long acc_stride;
   const WorkSeg* segs;       // [K]: the list lengths give each worker's shift
   int K, dp, vexp, Sp;
-  const double* s;           // from dsgd_rp64_grad_kernel
+  const double* s;           // from the grad kernel (ASYNC: from dsgd_rp64v_s_sliced_kernel)
   const int* perm;           // key -> rank
-  double* g_out;             // GRADIENT: the regularised sum of worker 0, key order
-  double* w;                 // STEP: the weights, updated in their layout
+  double* g_out;             // GRADIENT: the regularised sum of worker 0, key order.  ASYNC: the delta, key order (may be null)
+  double* w;                 // STEP, ASYNC: the weights, updated in their layout
   double lr;
 };
 
+constexpr int RP64_GRADIENT = 0, RP64_STEP = 1, RP64_ASYNC = 2;
+
 // GRADIENT: over keys j, g[j] of the one worker (orc_gradient).  STEP: over ranks r, the fold over the workers in worker
 // order, filt(acc / K), filt(mean * lr), filt(w - upd) (orc_sync_step; w is filtered already: a column without a
-// gradient keeps its value, which is what filt(w - 0) gives)
-template <bool STEP>
-__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_finish_kernel(Rp64FinishArgs a) {
+// gradient keeps its value, which is what filt(w - 0) gives).  ASYNC: over keys j, the one worker's filt(g0 / n), the
+// support-only regulariser, filt(g * lr) written to the delta, filt(w - upd) on EVERY coordinate (orc_async_step: the
+// oracle writes filt(w - 0) where nothing is listed).  (threads: blockDim.x, see forward64_body)
+template <typename V, int MODE>
+__device__ __forceinline__ void rp64_finish_body(const Rp64FinishArgs& a, unsigned int threads) {
 #pragma clang fp contract(off)
+  constexpr int WORDS = Rp64Acc<V>::WORDS;
   const double s = *a.s;
   const bool add = fabs(s) > CS64_EPS;   // (regularize_inplace: s == 0 or filtered away -> g unchanged)
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < a.dp; j += gridDim.x * blockDim.x) {
-    const int r = STEP ? j : a.perm[j];
+  for (int j = blockIdx.x * threads + threadIdx.x; j < a.dp; j += gridDim.x * threads) {
+    const int r = MODE == RP64_STEP ? j : a.perm[j];
     double gsum = 0.0;
-    for (int k = 0; k < (STEP ? a.K : 1); ++k) {
-      unsigned long long* at = a.acc + (long long)k * a.acc_stride + r;
-      const long long t = (long long)*at;
-      if (t != 0) *at = 0ull;
-      const double inv_scale = ldexp(1.0, a.vexp - rp64_shift(a.segs[k].end - a.segs[k].begin));
-      const double g0 = filt64((double)t * inv_scale);           // one rounding of the exact sum (the power of two is exact)
-      const double g = (add && g0 != 0.0) ? filt64(g0 + s) : g0;  // ref: core/ml/SparseSVM.scala:31, math/Vec.scala:65-75
-      if (!STEP) {
-        a.g_out[j] = g;
+    for (int k = 0; k < (MODE == RP64_STEP ? a.K : 1); ++k) {
+      unsigned long long* at[WORDS];
+      unsigned long long t[WORDS];
+#pragma unroll
+      for (int i = 0; i < WORDS; ++i) {   // (every word's load in flight before the first store)
+        at[i] = a.acc[i] + (long long)k * a.acc_stride + r;
+        t[i] = *at[i];
+      }
+#pragma unroll
+      for (int i = 0; i < WORDS; ++i)
+        if (t[i] != 0ull) *at[i] = 0ull;
+      const long long n = a.segs[k].end - a.segs[k].begin;
+      const double g0 = filt64(Rp64Acc<V>::round(t, a.vexp - rp64_shift(n)));   // one rounding of the exact sum
+      if (MODE == RP64_ASYNC) {
+        const double gm = filt64(g0 / (double)n);                      // Vec.mean (correctly rounded division)
+        const double g = (add && gm != 0.0) ? filt64(gm + s) : gm;     // ref: core/ml/SparseSVM.scala:31, math/Vec.scala:65-75
+        const double upd = filt64(g * a.lr);                           // learningRate * regularize(grad) (ref: core/Slave.scala:99)
+        if (a.g_out != nullptr) a.g_out[j] = upd;
+        const long long at = rp64_at(r, a.Sp);
+        a.w[at] = filt64(a.w[at] - upd);                               // ref: core/Slave.scala:101
       } else {
-        gsum = filt64(gsum + g);                                  // Vec.sum over the workers
+        const double g = (add && g0 != 0.0) ? filt64(g0 + s) : g0;     // ref: core/ml/SparseSVM.scala:31, math/Vec.scala:65-75
+        if (MODE == RP64_GRADIENT) {
+          a.g_out[j] = g;
+        } else {
+          gsum = filt64(gsum + g);                                     // Vec.sum over the workers
+        }
       }
     }
-    if (STEP && gsum != 0.0) {
+    if (MODE == RP64_STEP && gsum != 0.0) {
       const double mean = filt64(gsum / (double)a.K);             // Vec.mean (correctly rounded division)
       const double upd = filt64(mean * a.lr);                     // learningRate * grad (ref: core/Master.scala:194-197)
       const long long at = rp64_at(r, a.Sp);
@@ -201,8 +276,14 @@ __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_finish_kernel(Rp64Fini
     }
   }
 }
-
-__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_gather_kernel(Rp64Args a) { rp64_grad_body<true>(a); }
+template <bool STEP>
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_finish_kernel(Rp64FinishArgs a) {
+  rp64_finish_body<float, STEP ? RP64_STEP : RP64_GRADIENT>(a, blockDim.x);
+}
+template <int MODE>
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_finish_kernel(Rp64FinishArgs a) {
+  rp64_finish_body<double, MODE>(a, blockDim.x);
+}
 
 // Behind the gather, ONE workgroup: the K headers become the list ranges the finish takes its shifts from ({0, n}), the
 // job's samples and active rows go to the context's scalars, and the header and rank words are zeroed again (the
@@ -234,4 +315,40 @@ __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_header_kernel(unsigned
     sc->n_samples = tot[0];
     sc->n_active = tot[1];
   }
+}
+
+// The ASYNC finish's s = lambda * 2 * (w . ds) in the summation order of dsgd_cs64_async_kernel, ONE workgroup of CS_THREADS
+// lanes: the asynchronous iteration on float data runs there, and a Double-data step on values a float holds must give its bits.
+// Per slice b (rank r = b + CS64_G * i at position i; the padding zero) lane t adds the pairs i2 = t, t + CS_THREADS, ...
+// as cs64_wds_share does, the workgroup sums as cs64_block_sum does, and the slices' sums are added in slice order from
+// 0.0 (cs64_gather).  The weights are filtered as that kernel filters them on loading.
+__global__ void __launch_bounds__(CS_THREADS) dsgd_rp64v_s_sliced_kernel(const double* __restrict__ w, const double* __restrict__ ds, int Sp_w,
+                                                                        int dp, double lambda, double* s_out) {
+#pragma clang fp contract(off)
+  __shared__ double red[CS_THREADS / 64];
+  const int Sp = cs64_sp(dp);
+  double tot = 0.0;
+  for (int b = 0; b < CS64_G; ++b) {
+    double sp = 0.0;
+    for (int i2 = threadIdx.x; i2 < (Sp >> 1); i2 += CS_THREADS) {
+      const long long r0 = (long long)b + (long long)CS64_G * (2 * i2), r1 = r0 + CS64_G;
+      const double w0 = r0 < dp ? filt64(w[rp64_at(r0, Sp_w)]) : 0.0, d0 = r0 < dp ? ds[r0] : 0.0;
+      const double w1 = r1 < dp ? filt64(w[rp64_at(r1, Sp_w)]) : 0.0, d1 = r1 < dp ? ds[r1] : 0.0;
+      sp = sp + (filt64(w0 * d0) + filt64(w1 * d1));
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sp = sp + __shfl_xor(sp, off, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sp;
+    __syncthreads();
+    double t[CS_THREADS / 64];
+#pragma unroll
+    for (int i = 0; i < CS_THREADS / 64; ++i) t[i] = red[i];
+#pragma unroll
+    for (int n = CS_THREADS / 64; n > 1; n >>= 1)
+#pragma unroll
+      for (int i = 0; i < n / 2; ++i) t[i] = t[2 * i] + t[2 * i + 1];
+    tot = tot + t[0];
+  }
+  if (threadIdx.x == 0) *s_out = lambda * 2.0 * tot;
 }

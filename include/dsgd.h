@@ -131,7 +131,7 @@ enum {
  *     dsgd_async_step_f64 return DSGD_EUNSUPPORTED and change nothing: the persistent column-slice kernel cannot hold a
  *     collective.  (host.MasterSync.fit falls back from a refused plan to one dsgd_sync_step_f64 per step.)
  *   Without a communicator nothing changes.  Real RCCL with more than one rank has not run; no multi-GPU speed is claimed.
- *   DOUBLE FEATURE VALUES (dsgd_load_csr_f64; csrc/dsgd_rp64v.hpp).  The reference reads `elems(1).toDouble`
+ *   DOUBLE FEATURE VALUES (dsgd_load_csr_f64; csrc/dsgd_rp64.hpp).  The reference reads `elems(1).toDouble`
  *   (utils/Dataset.scala:30); dsgd_load_csr takes floats, which moves every value of a real data file by up to 6e-8
  *   relative before the first step.  dsgd_load_csr_f64 keeps the doubles (8 bytes per non-zero beside the CSR) and the
  *   values rounded to float (the column ranking and the layout code read those); vexp comes from the largest |v| as a

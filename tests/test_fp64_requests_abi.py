@@ -41,6 +41,14 @@ def test_row_parallel_fp64_kernels_in_the_code_object_without_spills(tmp_path):
     for k, v in found.items():
         assert v["vgpr_spill_count"] == 0 and v["sgpr_spill_count"] == 0 and v["private_segment_fixed_size"] == 0, (k, v)
     assert sum("dsgd_cs64_step_kernel" in k for k in notes) == 2   # (no new instantiation of the plans' kernel)
+    # the Double-value wrappers of the same bodies (csrc/dsgd_rp64.hpp, csrc/dsgd_cs64.hpp)
+    twins = {k: v for k, v in notes.items()
+             if any(n in k for n in ("dsgd_rp64v_grad_kernel", "dsgd_rp64v_finish_kernel", "dsgd_forward64v_kernel", "dsgd_eval64v_kernel"))}
+    assert sum("dsgd_rp64v_grad_kernel" in k for k in twins) == 1
+    assert sum("dsgd_rp64v_finish_kernel" in k for k in twins) == 3   # the gradient, the step and the asynchronous step
+    assert sum("dsgd_forward64v_kernel" in k for k in twins) == 1 and sum("dsgd_eval64v_kernel" in k for k in twins) == 1
+    for k, v in twins.items():
+        assert v["vgpr_spill_count"] == 0 and v["sgpr_spill_count"] == 0 and v["private_segment_fixed_size"] == 0, (k, v)
 
 
 def test_jni_fp64_request_natives_through_the_stub_env(shim_lib):

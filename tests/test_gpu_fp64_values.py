@@ -1,4 +1,4 @@
-"""-m gpu: the fp64 mode on Double feature values (dsgd_load_csr_f64; csrc/dsgd_rp64v.hpp) against the Double oracle
+"""-m gpu: the fp64 mode on Double feature values (dsgd_load_csr_f64; csrc/dsgd_rp64.hpp) against the Double oracle
 oracle/ref_dict.py (Python floats; oracle/oracle.py holds float32 values).
 
 Shapes: D = 3,000 (ranks on both sides of the 1,024 hot ranks kept in LDS), about 2,000 rows of 0 - 40 entries (shorter
@@ -301,6 +301,40 @@ def test_float_representable_values_give_the_float_calls_bits():
         all_rows = np.arange(N_ROWS, dtype=np.int32)
         assert np.array_equal(a.forward_f64(all_rows), b.forward_f64(all_rows))
         assert a.loss_acc(N_TRAIN, N_ROWS) == b.loss_acc(N_TRAIN, N_ROWS)
+
+
+def test_double_data_on_slice_major_weights_gives_the_float_calls_bits():
+    """3: Double data can meet slice-major weights: a plan made on float data outlives load_csr with doubles (plans are
+    refused only at their creation there) and its run leaves the weights in the column slices' layout.  The row-parallel
+    calls behind it read and update that layout; on values a float holds they give the float-data twin's bits"""
+    csr = _csr(float_values=True)
+    row_ptr, col, val, label = csr
+    rng = np.random.default_rng(71)
+    split = host.split_vanilla(N_TRAIN, 3)
+    steps = [[rng.permutation(np.asarray(r))[:100].astype(np.int32) for r in split] for _ in range(2)]
+    idx = rng.integers(0, N_TRAIN, size=777).astype(np.int32)
+    lists = [rng.permutation(np.asarray(r))[:150].astype(np.int32) for r in split]
+    w0 = _decisive_w()
+    with _engine(csr, as_float=True) as a, _engine(csr, as_float=True) as b:
+        pa, pb = a.plan(steps), b.plan(steps)
+        a.load_csr(row_ptr, col, val, label)   # the doubles; the plan stays
+        a.build_dim_sparsity(N_TRAIN)
+        assert (a.value_bits(), b.value_bits()) == (64, 32)
+        for e, p in ((a, pa), (b, pb)):
+            e.set_weights(w0)
+            e.plan_run(p, 0, 2, 0.5)   # (reads the values as floats on both: the same steps)
+            e.synchronize()
+        ga, sa = a.gradient_f64(idx)   # w = NULL right after a plan run: the slice-major weights
+        gb, sb = b.gradient_f64(idx)
+        assert sa == sb and np.array_equal(_bits(ga), _bits(gb))
+        assert a.sync_step_f64(lists, 0.5) == b.sync_step_f64(lists, 0.5)
+        da, sa = a.async_step(idx[:100], 0.3, want_delta=True)
+        db, sb = b.async_step(idx[:100], 0.3, want_delta=True)
+        assert sa == sb and np.array_equal(_bits(da), _bits(db))
+        wa, wb = a.get_weights(), b.get_weights()
+        assert np.array_equal(_bits(wa), _bits(wb)) and not np.array_equal(_bits(wa), _bits(w0))
+        pa.destroy()
+        pb.destroy()
 
 
 @pytest.mark.parametrize("k,n", [(3, 100), (5, 37)])

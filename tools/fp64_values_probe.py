@@ -1,5 +1,5 @@
-"""The fp64 mode on Double feature values (dsgd_load_csr_f64; csrc/dsgd_rp64v.hpp) next to the same calls on the same data
-rounded to float (csrc/dsgd_rp64.hpp).
+"""The fp64 mode on Double feature values (dsgd_load_csr_f64) next to the same calls on the same data rounded to float:
+the two value types of the one row-parallel family (csrc/dsgd_rp64.hpp).
 
 One GPU run, one JSON line, over N = 804,414 synthetic RCV1-like rows (80 % train, 3 workers' splits).  The generator's
 values are float by construction, so the Double data set is made here: every value times (1 + u * 2^-24), u uniform in
