@@ -40,6 +40,7 @@ SYMBOLS = [
     "dsgd_set_weights_sparse", "dsgd_set_weights_sparse_f64", "dsgd_get_weights_sparse", "dsgd_get_weights_sparse_f64",
     "dsgd_gradient_sparse", "dsgd_gradient_sparse_f64", "dsgd_async_step_sparse", "dsgd_async_step_sparse_f64",
     "dsgd_load_csr_f64", "dsgd_value_bits",
+    "dsgd_sync_steps_f64",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")

@@ -527,6 +527,21 @@ struct dsgd_ctx {
   unsigned long long* d_rp64v_lo = nullptr;
   int rp64v_k = 0;
   long long rp64v_stride = 0;
+  // an epoch's steps in one call (dsgd_sync_steps_f64): the call's list ranges ([n_steps][K]) and per-step running active
+  // counts, the fused step's arrival counter, whose bit 62 says that a launch gave up (a 16-byte block of its own: word 0), with
+  // the pinned copy the host reads it into, the target the last fused launch was given, the bound of a workgroup's wait in ticks of the device's wall
+  // clock, and how many workgroups of each fused kernel a compute unit holds (0: not asked yet)
+  WorkSeg* d_rp64_ssegs = nullptr;
+  long long rp64_ssegs_cap = 0;
+  unsigned long long* d_rp64_cum = nullptr;
+  long long rp64_cum_cap = 0;
+  unsigned long long* d_rp64_sync = nullptr;
+  unsigned long long* h_rp64_sync = nullptr;
+  unsigned long long rp64_target = 0;
+  unsigned long long rp64_wait_ticks = 0;
+  int rp64_occ[2] = {0, 0};               // [0] dsgd_rp64_step_kernel, [1] dsgd_rp64v_step_kernel
+  bool rp64_occ_known[2] = {false, false};
+  bool rp64_fused = RP64_FUSED_DEFAULT;   // DSGD_RP64_FUSED
   // Sparse values at the boundary (csrc/dsgd_sparse.hpp): the compaction's output in host-mapped memory the kernel writes in
   // place ([2 words: count, gave up][dp keys][dp values of 8 bytes]), its scan state, and the staged pairs of a sparse setter
   unsigned long long* h_sp_out = nullptr;
@@ -3246,6 +3261,12 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   if (const char* e = getenv("DSGD_VT_TPW")) c->vt_tpw = std::max(1, atoi(e));
   if (const char* e = getenv("DSGD_VT_PACK_MB")) c->vt_pack_mb = std::max(0, atoi(e));
   if (const char* e = getenv("DSGD_HSPLIT")) c->hsplit = atoi(e);                 // hot/cold split rank (tests: wide models)
+  if (const char* e = getenv("DSGD_RP64_FUSED")) c->rp64_fused = atoi(e) != 0;    // dsgd_sync_steps_f64: 1 = one fused launch per step, 0 = two
+  {   // the fused step's wait is bounded in wall-clock time: 2 s of the device's constant-rate clock (kHz; 100 MHz where unknown)
+    int khz = 0;
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, cfg->device) != hipSuccess || khz <= 0) khz = 100000;
+    c->rp64_wait_ticks = (unsigned long long)khz * 2000ull;
+  }
   if (getenv("DSGD_PLAN_PROF") && atoi(getenv("DSGD_PLAN_PROF"))) {
     // (16 counters + four words per workgroup of the chunked launch's LAST run: start, end, cycles in the hot tiles, XCC id)
     HIP_TRY_B(hipMalloc(&c->d_tprof, sizeof(unsigned long long) * (16 + 4 * 1024)));
@@ -3358,6 +3379,10 @@ int dsgd_destroy(dsgd_ctx* c) {
   (void)hipFree(c->d_val64);
   (void)hipFree(c->d_rp64v_lo);
   if (c->h_rp64_ranks) (void)hipHostFree(c->h_rp64_ranks);
+  (void)hipFree(c->d_rp64_ssegs);
+  (void)hipFree(c->d_rp64_cum);
+  (void)hipFree(c->d_rp64_sync);
+  if (c->h_rp64_sync) (void)hipHostFree(c->h_rp64_sync);
   if (c->h_sp_out) (void)hipHostFree(c->h_sp_out);
   (void)hipFree(c->d_sp_state);
   (void)hipFree(c->d_sp_in);
@@ -5066,6 +5091,54 @@ static int rp64_gather(dsgd_ctx* c, int k) {
   HIP_TRY(hipGetLastError());
   return DSGD_OK;
 }
+// the workgroups a worker's list is spread over: one per 16 rows of the longest list, all lists together at most two per
+// compute unit (each workgroup flushes its hot words once)
+static long long rp64_bpw(dsgd_ctx* c, int n_workers, long long max_items) {
+  constexpr long long rows_per_block = RP64_THREADS / RP64_GROUP;
+  return std::max<long long>(1, std::min<long long>((max_items + rows_per_block - 1) / rows_per_block,
+                                                    std::max<long long>(1, (long long)c->n_cu * 2 / n_workers)));
+}
+// the arguments of the two bodies over the lists idx / segs (a local step: the context's own accumulators)
+static void rp64_fill(dsgd_ctx* c, int n_workers, long long bpw, int mode, double lr, double* delta, const int* idx, const WorkSeg* segs,
+                      Rp64Args& a, Rp64FinishArgs& f) {
+  const bool v64 = c->d_val64 != nullptr;
+  const bool sliced = c->cs_w_G == CS64_G;
+  const int Sp = sliced ? cs64_sp(c->dp) : 0;
+  double* w = sliced ? c->d_cs_w64 : c->d_w64;
+  a.w = w;
+  a.ds = c->d_ds64;
+  a.Sp = Sp;
+  a.dp = c->dp;
+  a.vexp = c->vexp;
+  a.K = n_workers;
+  a.idx = idx;
+  a.segs = segs;
+  a.blocks_per_worker = bpw;
+  a.with_s = mode == RP64_ASYNC ? 0 : 1;   // (the asynchronous iteration: s from dsgd_rp64v_s_sliced_kernel)
+  a.acc[0] = c->d_rp64_acc;
+  a.acc[1] = v64 ? c->d_rp64v_lo : nullptr;
+  a.acc_stride = c->rp64_stride;
+  a.lambda = c->cfg.lambda;
+  a.s_out = c->d_rp64_s;
+  a.sc = c->d_sc;
+  a.rank_word = nullptr;
+  f.acc[0] = a.acc[0];
+  f.acc[1] = a.acc[1];
+  f.acc_stride = a.acc_stride;
+  f.segs = segs;
+  f.K = n_workers;
+  f.dp = c->dp;
+  f.vexp = c->vexp;
+  f.Sp = Sp;
+  f.s = c->d_rp64_s;
+  f.perm = c->d_perm;
+  f.g_out = mode == RP64_ASYNC ? delta : c->d_rp64_g;
+  f.w = w;
+  f.lr = lr;
+}
+static dim3 rp64_finish_grid(dsgd_ctx* c) {
+  return dim3((unsigned)std::min<long long>(((long long)c->dp + RP64_THREADS - 1) / RP64_THREADS, (long long)c->n_cu * 4));
+}
 // The two launches over the staged lists (c->cur_idx, c->d_segs), on the context's float or Double values (rp64_ensure
 // came first).  mode: RP64_GRADIENT (worker 0's gradient into d_rp64_g), RP64_STEP, RP64_ASYNC (one worker; Double data
 // only -- float data's asynchronous step is a column-slice plan; delta: key order, may be null).  gather: the step under
@@ -5080,38 +5153,12 @@ static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, int mode
   if ((mode == RP64_ASYNC && !v64) || (gather && v64))   // (no such kernel; the entry points never ask)
     return fail(DSGD_ESTATE, "internal: no row-parallel fp64 kernel for %s on %s values", gather ? "a gather" : "an asynchronous step",
                 v64 ? "Double" : "float");
-  const bool sliced = c->cs_w_G == CS64_G;
-  const int Sp = sliced ? cs64_sp(c->dp) : 0;
-  double* w = sliced ? c->d_cs_w64 : c->d_w64;
-  constexpr long long rows_per_block = RP64_THREADS / RP64_GROUP;
-  const long long bpw = std::max<long long>(1, std::min<long long>((max_items + rows_per_block - 1) / rows_per_block,
-                                                                   std::max<long long>(1, (long long)c->n_cu * 2 / n_workers)));   // (each workgroup flushes its hot words once)
+  const long long bpw = rp64_bpw(c, n_workers, max_items);
   Rp64Args a;
-  a.w = w;
-  a.ds = c->d_ds64;
-  a.Sp = Sp;
-  a.dp = c->dp;
-  a.vexp = c->vexp;
-  a.K = n_workers;
-  a.idx = c->cur_idx;
-  a.segs = c->d_segs;
-  a.blocks_per_worker = bpw;
-  a.with_s = mode == RP64_ASYNC ? 0 : 1;   // (the asynchronous iteration: s from dsgd_rp64v_s_sliced_kernel below)
-  a.acc[0] = c->d_rp64_acc;
-  a.acc[1] = v64 ? c->d_rp64v_lo : nullptr;
-  a.acc_stride = c->rp64_stride;
-  a.lambda = c->cfg.lambda;
-  a.s_out = c->d_rp64_s;
-  a.sc = c->d_sc;
-  a.rank_word = nullptr;
   Rp64FinishArgs f;
-  f.acc[0] = a.acc[0];
-  f.acc[1] = a.acc[1];
-  f.acc_stride = a.acc_stride;
-  f.segs = c->d_segs;
-  f.K = n_workers;
+  rp64_fill(c, n_workers, bpw, mode, lr, delta, c->cur_idx, c->d_segs, a, f);
   const dim3 th(RP64_THREADS), gg((unsigned)(bpw * n_workers + a.with_s));
-  const dim3 fg((unsigned)std::min<long long>(((long long)c->dp + RP64_THREADS - 1) / RP64_THREADS, (long long)c->n_cu * 4));
+  const dim3 fg = rp64_finish_grid(c);
   if (gather) {   // this rank's slots of the gather buffer; the finish over every rank's workers
     unsigned long long* slots = c->d_rp64_gath + rp64_gather_pad(c->world);
     a.acc[0] = slots + (long long)c->rank * n_workers * c->rp64_gstride;
@@ -5132,17 +5179,9 @@ static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, int mode
     HIP_TRY(hipGetLastError());
   }
   if (mode == RP64_ASYNC) {   // s in the order of the float data's asynchronous kernel (the same bits on values a float holds)
-    hipLaunchKernelGGL(dsgd_rp64v_s_sliced_kernel, dim3(1), dim3(CS_THREADS), 0, c->stream, w, c->d_ds64, Sp, c->dp, c->cfg.lambda, c->d_rp64_s);
+    hipLaunchKernelGGL(dsgd_rp64v_s_sliced_kernel, dim3(1), dim3(CS_THREADS), 0, c->stream, a.w, c->d_ds64, a.Sp, c->dp, c->cfg.lambda, c->d_rp64_s);
     HIP_TRY(hipGetLastError());
   }
-  f.dp = c->dp;
-  f.vexp = c->vexp;
-  f.Sp = Sp;
-  f.s = c->d_rp64_s;
-  f.perm = c->d_perm;
-  f.g_out = mode == RP64_ASYNC ? delta : c->d_rp64_g;
-  f.w = w;
-  f.lr = lr;
   if (mode == RP64_ASYNC)
     hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64_ASYNC>, fg, th, 0, c->stream, f);
   else if (mode == RP64_STEP && v64)
@@ -5246,6 +5285,200 @@ static int sync_step64_rows(dsgd_ctx* c, const int32_t* const* idx_per_worker, c
   DSGD_TRY(rp64_launch(c, n_workers, mx, RP64_STEP, lr));
   c->s_dirty = true;
   return finish_stats(c, stats, tot);
+}
+
+// ---- an epoch's steps in one call (include/dsgd.h "THE FP64 MODE"; csrc/dsgd_rp64.hpp "an epoch's steps in one call") ----
+// how many workgroups of the fused kernel a compute unit holds: asked once per kernel.  A step takes the fused form only where
+// its grid is at most that figure x the compute units (a grid that is not resident as a whole would wait for itself); the
+// grids of rp64_bpw are at most two workgroups per unit and one more.
+static int rp64_fused_cap(dsgd_ctx* c, bool v64) {
+  const int i = v64 ? 1 : 0;
+  if (c->rp64_occ_known[i]) return DSGD_OK;
+  int n = 0;
+  const hipError_t e = v64 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dsgd_rp64v_step_kernel, RP64_THREADS, 0)
+                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dsgd_rp64_step_kernel, RP64_THREADS, 0);
+  if (e != hipSuccess) return fail(DSGD_EHIP, "hipOccupancyMaxActiveBlocksPerMultiprocessor: %s", hipGetErrorString(e));
+  c->rp64_occ[i] = std::max(0, n);
+  c->rp64_occ_known[i] = true;
+  return DSGD_OK;
+}
+static int rp64_steps_ensure(dsgd_ctx* c, long long n_lists, long long n_steps) {
+  if (c->rp64_ssegs_cap < n_lists || c->rp64_cum_cap < n_steps) HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->rp64_ssegs_cap < n_lists) {
+    (void)hipFree(c->d_rp64_ssegs);
+    c->d_rp64_ssegs = nullptr;
+    c->rp64_ssegs_cap = 0;
+    HIP_TRY(hipMalloc(&c->d_rp64_ssegs, sizeof(WorkSeg) * (size_t)n_lists));
+    c->rp64_ssegs_cap = n_lists;
+  }
+  if (c->rp64_cum_cap < n_steps) {
+    (void)hipFree(c->d_rp64_cum);
+    c->d_rp64_cum = nullptr;
+    c->rp64_cum_cap = 0;
+    HIP_TRY(hipMalloc(&c->d_rp64_cum, sizeof(unsigned long long) * (size_t)n_steps));
+    c->rp64_cum_cap = n_steps;
+  }
+  if (!c->d_rp64_sync) {
+    HIP_TRY(hipHostMalloc(&c->h_rp64_sync, sizeof(unsigned long long) * 2, hipHostMallocDefault));
+    HIP_TRY(hipMalloc(&c->d_rp64_sync, sizeof(unsigned long long) * 2));
+    HIP_TRY(hipMemsetAsync(c->d_rp64_sync, 0, sizeof(unsigned long long) * 2, c->stream));
+    c->rp64_target = 0;
+  }
+  return DSGD_OK;
+}
+
+int dsgd_sync_steps_f64(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const int64_t* offsets, int64_t n_steps, int32_t n_workers, double lr,
+                        int64_t* active_per_step_out, dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  if (!idx || !offsets || n_steps < 1 || n_workers < 1 || n_idx < 0) return fail(DSGD_EINVAL, "bad arguments (null lists, no steps or no workers)");
+  if (n_steps > INT64_MAX / n_workers) return fail(DSGD_EINVAL, "n_steps * n_workers overflows");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_sync_steps_f64"));
+  if (c->comm)
+    return fail(DSGD_EUNSUPPORTED, "dsgd_sync_steps_f64 is not available with a communicator attached: the gather needs a host read per "
+                                   "step (dsgd_sync_step_f64 is the step that spans the ranks)");
+  DSGD_TRY(bind(c, true));
+  DSGD_TRY(require_data(c));
+  DSGD_TRY(require_ds(c));
+  DSGD_TRY(require_sync_mode(c));
+  // the lists are host data: every step checked here, in one pass, by rp64_check_lists' rules, before anything moves
+  const int K = n_workers;
+  const int64_t n_lists = n_steps * K;
+  if (offsets[0] != 0) return fail(DSGD_EINVAL, "offsets[0] must be 0");
+  if (offsets[n_lists] != n_idx)
+    return fail(DSGD_EINVAL, "offsets end at %lld but idx holds %lld entries", (long long)offsets[n_lists], (long long)n_idx);
+  for (int64_t i = 0; i < n_lists; ++i) {
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] > n_idx)
+      return fail(DSGD_EINVAL, "offsets decrease or leave idx at list %lld (step %lld, worker %lld)", (long long)i, (long long)(i / K), (long long)(i % K));
+    if (offsets[i + 1] == offsets[i])
+      return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors (step %lld, worker %lld)", (long long)(i / K), (long long)(i % K));   // ref: math/Vec.scala:129
+  }
+  for (int64_t t = 0; t < n_idx; ++t)
+    if (idx[t] < 0 || idx[t] >= c->n_rows)
+      return fail(DSGD_ERANGE, "sample index %d at position %lld outside the %lld loaded rows", idx[t], (long long)t, c->n_rows);
+  DSGD_TRY(prepare_layout(c));
+  const bool v64 = c->d_val64 != nullptr;
+  if (c->rp64_fused) DSGD_TRY(rp64_fused_cap(c, v64));
+  DSGD_TRY(rp64_ensure(c, K));
+  DSGD_TRY(rp64_steps_ensure(c, n_lists, n_steps));
+  DSGD_TRY(reset_counters(c));
+  // ONE upload: the index array and the list ranges of every step
+  DSGD_TRY(ensure_idx(c, n_idx));
+  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int) * (size_t)n_idx));
+  memcpy(c->pin_idx.p, idx, sizeof(int) * (size_t)n_idx);
+  HIP_TRY(hipMemcpyAsync(c->d_idx, c->pin_idx.p, sizeof(int) * (size_t)n_idx, hipMemcpyHostToDevice, c->stream));
+  DSGD_TRY(pin_sent(c, c->pin_idx));
+  c->cur_idx = c->d_idx;
+  DSGD_TRY(pin_acquire(c->pin_segs, sizeof(WorkSeg) * (size_t)n_lists));
+  {
+    WorkSeg* sg = static_cast<WorkSeg*>(c->pin_segs.p);
+    for (int64_t i = 0; i < n_lists; ++i) {
+      sg[i].begin = offsets[i];
+      sg[i].end = offsets[i + 1];
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(c->d_rp64_ssegs, c->pin_segs.p, sizeof(WorkSeg) * (size_t)n_lists, hipMemcpyHostToDevice, c->stream));
+  DSGD_TRY(pin_sent(c, c->pin_segs));
+  const long long fused_max = c->rp64_fused ? (long long)c->rp64_occ[v64 ? 1 : 0] * c->n_cu : 0;
+  const dim3 th(RP64_THREADS), fg = rp64_finish_grid(c);
+  // every step's word of `cum` starts as all ones: a step that ran as a whole overwrites its word with the call's running
+  // n_active (the fused kernel itself; for the two launches a copy on the stream, which is needed only where the counts are
+  // asked for or fused launches share the call)
+  constexpr unsigned long long NOT_RUN = ~0ull;
+  HIP_TRY(hipMemsetAsync(c->d_rp64_cum, 0xff, sizeof(unsigned long long) * (size_t)n_steps, c->stream));
+  // a fused launch that gave up (bit 62 of the arrival counter): read behind a synchronisation
+  auto gave_up = [&](bool* yes) -> int {
+    HIP_TRY(hipMemcpyAsync(c->h_rp64_sync, c->d_rp64_sync, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *yes = (c->h_rp64_sync[0] & RP64_GAVE_UP) != 0;
+    return DSGD_OK;
+  };
+  long long n_fused = 0, n_pairs = 0;
+  bool fused_unchecked = false, aborted = false;
+  c->ctr_known = false;   // (n_active runs on through the call)
+  for (int64_t t = 0; t < n_steps && !aborted; ++t) {
+    long long mx = 0;
+    for (int k = 0; k < K; ++k) mx = std::max<long long>(mx, offsets[t * K + k + 1] - offsets[t * K + k]);
+    const long long bpw = rp64_bpw(c, K, mx);
+    Rp64Args a;
+    Rp64FinishArgs f;
+    rp64_fill(c, K, bpw, RP64_STEP, lr, nullptr, c->d_idx, c->d_rp64_ssegs + t * K, a, f);
+    const long long grid = bpw * K + 1;
+    if (grid <= fused_max) {   // resident as a whole: ONE launch
+      Rp64StepSync y;
+      y.arrived = c->d_rp64_sync;
+      c->rp64_target += (unsigned long long)grid;
+      y.target = c->rp64_target;
+      y.wait_ticks = c->rp64_wait_ticks;
+      y.cum = c->d_rp64_cum + t;
+      if (v64)
+        hipLaunchKernelGGL(dsgd_rp64v_step_kernel, dim3((unsigned)grid), th, 0, c->stream, view64(c), a, f, y);
+      else
+        hipLaunchKernelGGL(dsgd_rp64_step_kernel, dim3((unsigned)grid), th, 0, c->stream, view(c), a, f, y);
+      ++n_fused;
+      fused_unchecked = true;
+    } else {                   // the two launches of dsgd_sync_step_f64, back to back
+      // The existing kernels know nothing of a fused launch that gave up in front of them, so a call that mixes the forms (a
+      // grid beyond the fused cap: more than 2,000 workers) synchronises ONCE at each change from fused launches to the pair
+      // and stops there if one gave up: no step runs behind an aborted one.
+      if (fused_unchecked) {
+        DSGD_TRY(gave_up(&aborted));
+        fused_unchecked = false;
+        if (aborted) break;
+      }
+      if (v64) {
+        hipLaunchKernelGGL(dsgd_rp64v_grad_kernel, dim3((unsigned)grid), th, 0, c->stream, view64(c), a);
+        hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64_STEP>, fg, th, 0, c->stream, f);
+      } else {
+        hipLaunchKernelGGL(dsgd_rp64_grad_kernel, dim3((unsigned)grid), th, 0, c->stream, view(c), a);
+        hipLaunchKernelGGL(dsgd_rp64_finish_kernel<true>, fg, th, 0, c->stream, f);
+      }
+      if (active_per_step_out || c->rp64_fused)
+        HIP_TRY(hipMemcpyAsync(c->d_rp64_cum + t, &c->d_sc->n_active, sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
+      ++n_pairs;
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  // (dsgd_grad_kernel_name: which form served the call's steps)
+  c->last_grad_kernel = n_fused && n_pairs ? (v64 ? "dsgd_rp64v_step_kernel+dsgd_rp64v_grad_kernel" : "dsgd_rp64_step_kernel+dsgd_rp64_grad_kernel")
+                        : n_fused ? (v64 ? "dsgd_rp64v_step_kernel" : "dsgd_rp64_step_kernel")
+                                  : (v64 ? "dsgd_rp64v_grad_kernel" : "dsgd_rp64_grad_kernel");
+  c->s_dirty = true;
+  const bool want_cum = active_per_step_out != nullptr || n_fused > 0;
+  if (want_cum) {
+    DSGD_TRY(pin_acquire(c->pin_out, sizeof(unsigned long long) * (size_t)n_steps));
+    HIP_TRY(hipMemcpyAsync(c->pin_out.p, c->d_rp64_cum, sizeof(unsigned long long) * (size_t)n_steps, hipMemcpyDeviceToHost, c->stream));
+  }
+  c->h_rp64_sync[0] = 0;
+  if (n_fused) HIP_TRY(hipMemcpyAsync(c->h_rp64_sync, c->d_rp64_sync, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  DSGD_TRY(finish_stats(c, nullptr, n_idx));   // the ONE synchronisation of the call
+  const unsigned long long* cum = want_cum ? static_cast<const unsigned long long*>(c->pin_out.p) : nullptr;
+  if (aborted || (c->h_rp64_sync[0] & RP64_GAVE_UP) != 0) {
+    // A fused launch gave up waiting for its own grid.  The bit is set only while that launch's arrivals are incomplete and
+    // every workgroup that waits sees it, so NO workgroup of that launch ran phase 2 and every later launch returned on entry:
+    // the weights are those behind the last step whose word of `cum` is written.  The sums the aborted step left are zeroed
+    // and the counter starts again.
+    long long done = 0;
+    while (done < n_steps && cum[done] != NOT_RUN) ++done;
+    const unsigned long long seen = c->h_rp64_sync[0] & ~RP64_GAVE_UP, target = c->rp64_target;
+    HIP_TRY(hipMemsetAsync(c->d_rp64_sync, 0, sizeof(unsigned long long) * 2, c->stream));
+    c->rp64_target = 0;
+    HIP_TRY(hipMemsetAsync(c->d_rp64_acc, 0, sizeof(unsigned long long) * (size_t)c->rp64_stride * (size_t)c->rp64_k, c->stream));
+    if (c->d_rp64v_lo)
+      HIP_TRY(hipMemsetAsync(c->d_rp64v_lo, 0, sizeof(unsigned long long) * (size_t)c->rp64v_stride * (size_t)c->rp64v_k, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return fail(DSGD_ESTATE, "step %lld of %lld: the fused step's workgroups gave up waiting for each other (%llu arrivals seen, the call's last "
+                             "target %llu); the last completed step is %lld and the weights are those behind it%s (DSGD_RP64_FUSED=0 "
+                             "selects the two-launch queue)",
+                done, (long long)n_steps, seen, target, done - 1, done ? "" : " (-1: no step ran, the weights are unchanged)");
+  }
+  if (active_per_step_out)
+    for (int64_t t = 0; t < n_steps; ++t) active_per_step_out[t] = (int64_t)(cum[t] - (t ? cum[t - 1] : 0ull));
+  if (stats) {
+    stats->n_samples = n_idx;
+    stats->n_active = (int64_t)c->h_sc->n_active;
+  }
+  return DSGD_OK;
 }
 
 int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,

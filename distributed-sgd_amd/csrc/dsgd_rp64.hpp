@@ -352,3 +352,84 @@ __global__ void __launch_bounds__(CS_THREADS) dsgd_rp64v_s_sliced_kernel(const d
   }
   if (threadIdx.x == 0) *s_out = lambda * 2.0 * tot;
 }
+
+// ---- an epoch's steps in one call (dsgd_sync_steps_f64): ONE launch per step ----
+// The fused step: phase 1 is rp64_grad_body<V, false>, phase 2 rp64_finish_body<V, RP64_STEP> over the launch's own grid,
+// and between them every workgroup of the grid waits for every other one.  The host launches the fused form only for a
+// grid that is resident as a whole (rp64_fused_cap: the occupancy of the kernel times the compute units); every other
+// step is the two launches above, enqueued back to back.
+//   arrival   every wave makes its atomics (and the last workgroup's store of s) visible with a release fence at agent
+//             scope, the workgroup meets, and ONE lane adds 1 to a 64-bit counter in device memory.  The counter only
+//             grows over the context's life: the host passes each launch its own target (the previous one + the grid)
+//             and zeroes the counter only after an aborted call.
+//   wait      that lane polls the counter (relaxed, agent scope) until it reaches the target, the workgroup meets again,
+//             and every wave makes an acquire fence at agent scope in front of its own loads: the accumulators were
+//             written by atomics in L2, but s and phase 2's loads go through the vector L1.
+//   giving up the wait is bounded by the device's wall clock (wait_ticks: 2 s; phase 1 of a whole-split step is more
+//             than a millisecond, so a count of polls would not do).  The abort word is bit 62 of the counter itself
+//             (RP64_GAVE_UP), so that giving up and arriving are decided in ONE place: a workgroup out of time sets the
+//             bit with a compare-and-swap against the value it last read, which is below the target -- it succeeds only
+//             while the launch's arrivals are still incomplete, and from then on no poll of this launch can succeed
+//             (the bit is never cleared by the device); if the counter moved, the workgroup looks again.  So either
+//             every workgroup of a launch runs phase 2 or none does.  Every later launch of the call finds the bit on
+//             entry and returns at once (the shape of cs64_gather's abort word).  The host finds it behind its one
+//             synchronisation.
+//   counting  behind the arrival one lane of workgroup 0 stores the context's running n_active into the step's word of
+//             `cum` (all ones until then): the host takes the differences, and after an abort the written words name the
+//             last completed step.
+constexpr bool RP64_FUSED_DEFAULT = false;   // (DSGD_RP64_FUSED=1 selects the fused form: not measured yet)
+constexpr unsigned long long RP64_GAVE_UP = 1ull << 62;
+struct Rp64StepSync {
+  unsigned long long* arrived;     // the arrival counter (monotonic; bit 62: a launch gave up)
+  unsigned long long target;       // the counter's value once every workgroup of THIS launch has arrived
+  unsigned long long wait_ticks;   // of wall_clock64
+  unsigned long long* cum;         // this step's word: n_active of the call so far
+};
+
+template <typename V>
+__device__ __forceinline__ void rp64_step_body(const CsrViewT<V>& m, const Rp64Args& a, const Rp64FinishArgs& f, const Rp64StepSync& y) {
+#pragma clang fp contract(off)
+  __shared__ int go;
+  const int tid = threadIdx.x;
+  if (tid == 0) go = (__hip_atomic_load(y.arrived, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & RP64_GAVE_UP) == 0ull ? 1 : 0;
+  __syncthreads();
+  if (!go) return;   // (an earlier launch of the call gave up)
+  rp64_grad_body<V, false>(m, a);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // every wave: its own atomics are behind it
+  __syncthreads();
+  if (tid == 0) {
+    __hip_atomic_fetch_add(y.arrived, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int ok = 1;
+    const long long t0 = wall_clock64();
+    unsigned long long v = __hip_atomic_load(y.arrived, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (unsigned int spin = 0;; ++spin) {
+      if (v & RP64_GAVE_UP) {
+        ok = 0;
+        break;
+      }
+      if (v >= y.target) break;
+      if ((spin & 63u) == 63u && (unsigned long long)(wall_clock64() - t0) > y.wait_ticks) {
+        // (v < target here: the bit goes in only if nobody has arrived since; on failure v is the counter's new value)
+        if (__hip_atomic_compare_exchange_strong(y.arrived, &v, v | RP64_GAVE_UP, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+          ok = 0;
+          break;
+        }
+        continue;
+      }
+      __builtin_amdgcn_s_sleep(1);
+      v = __hip_atomic_load(y.arrived, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    go = ok;
+  }
+  __syncthreads();
+  if (!go) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // every wave, in front of its own loads of the others' sums and of s
+  if (blockIdx.x == 0 && tid == 0) *y.cum = __hip_atomic_load(&a.sc->n_active, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  rp64_finish_body<V, RP64_STEP>(f, RP64_THREADS);
+}
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_step_kernel(CsrView m, Rp64Args a, Rp64FinishArgs f, Rp64StepSync y) {
+  rp64_step_body<float>(m, a, f, y);
+}
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_step_kernel(CsrView64 m, Rp64Args a, Rp64FinishArgs f, Rp64StepSync y) {
+  rp64_step_body<double>(m, a, f, y);
+}

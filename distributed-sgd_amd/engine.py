@@ -194,6 +194,24 @@ class Engine:
         check(self._lib.dsgd_sync_step_f64(self._ctx, ptrs, ns, C.c_int32(k), C.c_double(lr), C.byref(st)))
         return {"n_samples": st.n_samples, "n_active": st.n_active}
 
+    def sync_steps_f64(self, idx, offsets, n_steps, n_workers, lr, per_step=False):
+        """n_steps steps of sync_step_f64 in ONE call (dsgd_sync_steps_f64; fp64 engines, no communicator): the flat form
+        plan_flat takes -- idx = all lists concatenated (step-major, worker-minor), offsets = n_steps * n_workers + 1 prefix
+        offsets.  The weights get the bits of the loop of sync_step_f64 calls; returns its totals, with per_step=True also
+        `active_per_step` (int64, one per step)."""
+        idx = i32(idx)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if n_steps >= 1 and n_workers >= 1 and len(offsets) != n_steps * n_workers + 1:
+            raise ValueError("offsets do not describe %d x %d lists" % (n_steps, n_workers))
+        act = np.zeros(max(int(n_steps), 1), dtype=np.int64) if per_step else None
+        st = BatchStats()
+        check(self._lib.dsgd_sync_steps_f64(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers),
+                                            C.c_double(lr), ptr(act), C.byref(st)))
+        out = {"n_samples": st.n_samples, "n_active": st.n_active}
+        if per_step:
+            out["active_per_step"] = act[:n_steps]
+        return out
+
     def forward_f64(self, idx, w=None):
         """SlaveImpl.forward with Double weights (dsgd_forward_f64; fp64 engines): float64 predictions in {-1, 0, +1}."""
         idx = i32(idx)

@@ -428,6 +428,10 @@ class HostAsyncExchange:
         self.rounds += 1
 
 
+# MasterSync._run_steps_f64: "1" = an epoch's refused fp64 plan runs as ONE Engine.sync_steps_f64 call, "0" = one sync_step_f64
+# call per step (DSGD_F64_STEPS overrides).  The batched call has not been measured yet: the default stays the loop
+F64_STEPS_DEFAULT = "0"
+
 # ---- Master.fit (synchronous) ---------------------------------------------------------------------------------
 class MasterSync:
     """core/Master.scala:120-218 for the workers hosted behind one backend.
@@ -548,8 +552,18 @@ class MasterSync:
         return getattr(self.backend, "precision", "fp32") == "fp64" and hasattr(self.backend, "sync_step_f64")
 
     def _run_steps_f64(self, lists, n_workers, learning_rate):
-        """The epoch's steps, one sync_step_f64 call each, in order; returns the rows whose gradient was computed."""
+        """The epoch's steps in order; returns the rows whose gradient was computed.  ONE sync_steps_f64 call where the backend
+        has it (Engine.sync_steps_f64: the same bits, the boundary paid once); one sync_step_f64 call per step where it has
+        not, where it refuses (DSGD_EUNSUPPORTED: a communicator is attached) or with DSGD_F64_STEPS=0."""
         idx, offs = lists["idx"], lists["offsets"]
+        # (an epoch without a step -- a worker's slice empty from the first batch -- makes no call: fit raises the reference's error)
+        if lists["n_steps"] >= 1 and hasattr(self.backend, "sync_steps_f64") and os.environ.get("DSGD_F64_STEPS", F64_STEPS_DEFAULT) != "0":
+            try:
+                st = self.backend.sync_steps_f64(idx, offs, lists["n_steps"], n_workers, learning_rate)
+                return int(st.get("n_samples", 0)) if st else 0
+            except RuntimeError as e:   # (DsgdError, and what the tests' backends raise)
+                if getattr(e, "code", None) != -7:
+                    raise
         n_samples = 0
         for s_ in range(lists["n_steps"]):
             o = offs[s_ * n_workers:(s_ + 1) * n_workers + 1]

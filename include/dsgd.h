@@ -154,6 +154,25 @@ enum {
  *   dsgd_comm_init_f64, and dsgd_load_csr_f64 while a communicator is attached (the gather's slots would double).
  *   host.MasterSync.fit falls back from the refused plan to dsgd_sync_step_f64 on host-drawn lists; host.MasterAsync.fit
  *   needs resident asynchronous plans and raises on Double data.
+ *   AN EPOCH'S STEPS IN ONE CALL (dsgd_sync_steps_f64, declared with the synchronous path below; csrc/dsgd_rp64.hpp).
+ *   Everything the plans refuse -- more than 4 workers, more than 1,024 rows per step, Double feature values -- pays
+ *   dsgd_sync_step_f64's boundary once per step: a staged list, two launches, a synchronisation.  dsgd_sync_steps_f64
+ *   takes a run of steps in the flat form dsgd_plan_create_n takes and IS that many dsgd_sync_step_f64 calls in order:
+ *   the same bits in the weights, the loop's totals in the statistics, each step's active count on request.  One upload
+ *   (the lists and their ranges), the steps enqueued without a host synchronisation between them, one synchronisation at
+ *   the end.  A step is ONE launch (dsgd_rp64_step_kernel / dsgd_rp64v_step_kernel: the two bodies of the per-call step
+ *   with a grid-wide arrival between them) where its grid is resident as a whole, else the per-call step's two launches;
+ *   DSGD_RP64_FUSED (read at dsgd_create; 1 / 0) selects the fused form or the two-launch queue for every step.  The
+ *   arrival's wait is bounded at 2 s of the device's wall clock.  A launch that gives up runs phase 2 in none of its
+ *   workgroups and every later launch of the call returns on entry; no step runs behind it (a call that mixes the two
+ *   forms synchronises once where it changes from fused launches to the pair).  The call then returns DSGD_ESTATE, the
+ *   message names the last completed step, the weights are those behind that step, and the context is usable.
+ *   dsgd_grad_kernel_name says which form served the last call's steps.  Float and Double values, any
+ *   n_workers >= 1, any list lengths; the weights stay in the layout they are found in.  Refused before anything is
+ *   enqueued, nothing changed, the context usable: DSGD_ESTATE on an fp32 context; DSGD_EUNSUPPORTED with a communicator
+ *   attached (the gather needs a host read per step: dsgd_sync_step_f64 stays the path there); DSGD_EINVAL for null
+ *   pointers, n_steps < 1, n_workers < 1, offsets that do not start at 0, decrease or do not end at n_idx, and an empty
+ *   list of any step; DSGD_ERANGE for a row index outside the loaded rows in any step.
  * The entry points below that name fp64 return DSGD_ESTATE on an fp32 context (dsgd_precision excepted).            */
 
 typedef struct dsgd_ctx dsgd_ctx;
@@ -246,6 +265,12 @@ int dsgd_gradient_f64(dsgd_ctx* ctx, const double* w, const int32_t* idx, int64_
 int dsgd_sync_step_f64(dsgd_ctx* ctx, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers,
                        double lr, dsgd_batch_stats* stats /* may be NULL */);
 int dsgd_forward_f64(dsgd_ctx* ctx, const double* w, const int32_t* idx, int64_t n, double* pred_out /* n */);
+/* n_steps steps of dsgd_sync_step_f64 in one call ("AN EPOCH'S STEPS IN ONE CALL" above): step t, worker j owns
+ * idx[offsets[t * n_workers + j] .. offsets[t * n_workers + j + 1]).  stats: the totals of the steps;
+ * active_per_step_out[t]: step t's active rows.                                                                       */
+int dsgd_sync_steps_f64(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const int64_t* offsets /* n_steps * n_workers + 1 */,
+                        int64_t n_steps, int32_t n_workers, double lr, int64_t* active_per_step_out /* n_steps, may be NULL */,
+                        dsgd_batch_stats* stats /* may be NULL */);
 
 /* Master.fit batch closure, update half (core/Master.scala:194-197): w <- w - lr * g_mean      */
 int dsgd_apply(dsgd_ctx* ctx, const float* g_mean /* D+1 */, float lr);

@@ -189,6 +189,20 @@ class SparseSVM {
     check(dsgd_value_bits(ctx_, &bits));
     return bits;
   }
+  // an epoch's steps of the fp64 mode in ONE call (include/dsgd.h "AN EPOCH'S STEPS IN ONE CALL"): idx = every list
+  // concatenated (step-major, worker-minor), offsets = nSteps * nWorkers + 1 prefix offsets; the bits of one
+  // dsgd_sync_step_f64 per step.  Returns the steps' totals; activePerStep (may be null) gets one count per step.
+  dsgd_batch_stats syncStepsF64(const std::vector<int32_t>& idx, const std::vector<int64_t>& offsets, int nWorkers, double learningRate,
+                                std::vector<int64_t>* activePerStep = nullptr) {
+    if (nWorkers < 1 || offsets.empty() || (offsets.size() - 1) % (size_t)nWorkers != 0)
+      throw IllegalArgumentException("requirement failed");   // offsets hold nSteps * nWorkers + 1 entries
+    const int64_t nSteps = (int64_t)((offsets.size() - 1) / (size_t)nWorkers);
+    if (activePerStep) activePerStep->assign((size_t)nSteps, 0);
+    dsgd_batch_stats st{};
+    check(dsgd_sync_steps_f64(ctx_, idx.data(), (int64_t)idx.size(), offsets.data(), nSteps, nWorkers, learningRate,
+                              activePerStep ? activePerStep->data() : nullptr, &st));
+    return st;
+  }
   // Main.scala:54-65: dimSparsity from the first nTrain rows (incl. its off-by-one)
   Vec buildDimSparsity(int64_t nTrain) {
     Vec ds((size_t)d_ + 1);

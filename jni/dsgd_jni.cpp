@@ -600,6 +600,39 @@ JNIEXPORT void JNICALL NATIVE(forwardF64)(JNIEnv* env, jobject, jlong h, jdouble
   if (rc) raise(env, rc);
 }
 
+// An epoch's steps of the fp64 mode in ONE call (dsgd_sync_steps_f64): what planCreate + planRunF64 do where the plans
+// apply, for everything they refuse (more than 4 workers, more than 1,024 rows per step, Double feature values) -- the
+// lists in planCreate's flat form, the bits of one dsgd_sync_step_f64 per step.  activeOut (may be null): nSteps longs,
+// each step's active rows.  Returns the active rows of all steps.  Under a communicator: UnsupportedOperationException.
+JNIEXPORT jlong JNICALL NATIVE(syncStepsF64)(JNIEnv* env, jobject, jlong h, jintArray idx, jlongArray offsets, jint nWorkers, jdouble lr,
+                                             jlongArray activeOut) {
+  if (!idx || !offsets) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "null array");
+    return 0;
+  }
+  const jsize nOff = env->GetArrayLength(offsets);
+  if (nWorkers < 1 || nOff < 1 || (nOff - 1) % nWorkers != 0) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "offsets must hold nSteps * nWorkers + 1 entries");
+    return 0;
+  }
+  const jsize nSteps = (nOff - 1) / nWorkers;
+  if (activeOut && env->GetArrayLength(activeOut) != nSteps) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "activeOut must hold one entry per step");
+    return 0;
+  }
+  dsgd_batch_stats st{};
+  int rc;
+  {
+    IntElems iv(env, idx, JNI_ABORT);
+    LongElems ov(env, offsets, JNI_ABORT);
+    LongElems av(env, activeOut, 0);
+    rc = dsgd_sync_steps_f64(ctx(h), reinterpret_cast<const int32_t*>(iv.p), (int64_t)env->GetArrayLength(idx),
+                             reinterpret_cast<const int64_t*>(ov.p), nSteps, nWorkers, lr, reinterpret_cast<int64_t*>(av.p), &st);
+  }
+  if (rc) raise(env, rc);
+  return st.n_active;
+}
+
 // ---- Sparse values (include/dsgd.h "SPARSE VALUES"): Vec maps in and out as (keys, values) pairs -----------------------
 // A producing native compacts into the context's scratch and returns the count (-1 with an exception pending); takeSparse /
 // takeSparseF64 copy the pairs into arrays of exactly that length.  Null arrays are refused before any array is taken.

@@ -51,6 +51,9 @@ object NativeSVM {
   // SlaveImpl.gradient / forward in Double: w may be null (the resident weights); gradientF64 returns the active rows
   @native def gradientF64(ctx: Long, w: Array[Double], idx: Array[Int], gOut: Array[Double]): Long
   @native def forwardF64(ctx: Long, w: Array[Double], idx: Array[Int], predOut: Array[Double]): Unit
+  // an epoch's steps of the fp64 mode in ONE call (dsgd_sync_steps_f64: planCreate's flat lists, the bits of one step call each; what
+  // the plans refuse -- Double values, > 4 workers, > 1,024 rows per step); activeOut: null or one Long per step; returns the active rows
+  @native def syncStepsF64(ctx: Long, idx: Array[Int], offsets: Array[Long], nWorkers: Int, lr: Double, activeOut: Array[Long]): Long
   // Sparse values (include/dsgd.h "SPARSE VALUES"): a Vec's map crosses as (keys, values).  A producing native compacts into
   // native scratch of D + 1 slots the shim owns per context and returns the number of pairs; takeSparse copies them into
   // arrays of exactly that length (hold the model's monitor across the two calls).  wKeys / wVals null: the resident weights.
