@@ -119,6 +119,7 @@ static bool available() {
     if (r__ != 0) return fail(DSGD_ERCCL, "%s: %s", #expr, rccl::GetErrorString(r__));          \
   } while (0)
 
+#include "dsgd_buf.hpp"      // (host only: the owners of device and pinned memory)
 #include "dsgd_kernels.hpp"
 #include "dsgd_batch.hpp"
 #include "dsgd_cs.hpp"
@@ -146,10 +147,10 @@ struct dsgd_plan {
   // virtual tiles (dsgd_vt_grad_kernel): the lists laid out over the split streams, built at the first run that needs them
   std::vector<int> h_idx;       // host copy of the lists (a plan drawn on the device fetches it only if a host builder asks: plan_host_idx)
   bool idx_trusted = false;     // the lists were drawn by the library inside the caller's row ranges: nothing to validate
-  VtLane* d_vt_lanes = nullptr; // 64 descriptors per tile
-  WorkSeg* d_vt_segs = nullptr; // tile range of every list, then (n_lists further entries) its range of d_vt_long
-  MbRec* d_vt_long = nullptr;   // rows of the lists that sit in no tile (long-row list, more than 64 cold entries)
-  uint4* d_vt_packed = nullptr; // plans up to vt_pack_mb: the tiles' own copy of the rows they touch (4 KiB per tile)
+  DevBuf<VtLane> d_vt_lanes; // 64 descriptors per tile
+  DevBuf<WorkSeg> d_vt_segs; // tile range of every list, then (n_lists further entries) its range of d_vt_long
+  DevBuf<MbRec> d_vt_long;   // rows of the lists that sit in no tile (long-row list, more than 64 cold entries)
+  DevBuf<uint4> d_vt_packed; // plans up to vt_pack_mb: the tiles' own copy of the rows they touch (4 KiB per tile)
   std::vector<long long> vt_off;       // n_lists + 1 tile offsets
   std::vector<int> vt_grid, vt_gxt, vt_shift;  // per step: workgroups per worker, those of them that walk tiles, shift
   long long vt_layout = -1;     // the layout generation the tiles were built for (-1: not built)
@@ -191,13 +192,13 @@ struct dsgd_ctx {
   hipStream_t stream = nullptr;
   // data
   long long n_rows = 0, nnz = 0;
-  long long* d_row_ptr = nullptr;
-  int* d_col = nullptr;
-  float* d_val = nullptr;
-  signed char* d_label = nullptr;
+  DevBuf<long long> d_row_ptr;
+  DevBuf<int> d_col;
+  DevBuf<float> d_val;
+  DevBuf<signed char> d_label;
   int group = 16;  // lanes per row of the row-wise prediction / evaluation kernels, from the mean row length
   // column layout: external keys <-> internal frequency ranks (identity until prepare_layout)
-  int* d_perm = nullptr;   // key  -> rank
+  DevBuf<int> d_perm;   // key  -> rank
   bool layout_ready = false;
   int hw_eval = DSGD_LDS_FLOATS;
   long long stream_min = 131072;  // row ranges with at least this many rows use the streaming kernels (DSGD_STREAM_MIN).  Four
@@ -205,8 +206,7 @@ struct dsgd_ctx {
                                   //   take 37 us for 18,519 rows and 57 us for 80,000 (streaming: 49 / 63 us;
                                   //   profiles/r04_stream_min.txt)
   // nnz-streaming kernels (contiguous row ranges)
-  StreamSeg* d_ssegs = nullptr;
-  int ssegs_cap = 0;
+  DevBuf<StreamSeg> d_ssegs;
   std::vector<StreamSeg> ssegs_last;
   // The matrix is SPLIT by column rank into a hot stream (rank < hsplit: wave tiles, weights and gradient in LDS, no
   // gathers) and a cold stream (col - hsplit, val, row) handled by two small kernels whose LDS holds the cold weights /
@@ -223,11 +223,11 @@ struct dsgd_ctx {
                                         //   builder of DSGD_CS_HOST_LAYOUT=1 holds a copy of it in host memory as well)
   int cs_nt = 0;                        // DSGD_CS_NT=256: tuning runs with 256 lanes per slice where a plan's steps fit them
   unsigned int cs_tag0 = 0;             // column-slice steps launched so far (the exchange granules' tags run on)
-  float* d_cs_w = nullptr;              // the weights slice-major while cs_w_G != 0: then d_w is STALE -- every entry point that
-  float* d_cs_ds = nullptr;             //   is not a column-slice launch converts back first (bind); dimSparsity likewise (a copy)
+  DevBuf<float> d_cs_w;              // the weights slice-major while cs_w_G != 0: then d_w is STALE -- every entry point that
+  DevBuf<float> d_cs_ds;             //   is not a column-slice launch converts back first (bind); dimSparsity likewise (a copy)
   int cs_w_G = 0;                       // slices of the slice-major state (0: the weights are in d_w, rank order)
-  unsigned long long* d_cs_x = nullptr; // exchange buffer of dsgd_cs_step_kernel: [2][CS_MAX_G][CS_XSTRIDE] granules
-  unsigned int* d_cs_sync = nullptr;    // its arrival counter and abort word
+  DevBuf<unsigned long long> d_cs_x; // exchange buffer of dsgd_cs_step_kernel: [2][CS_MAX_G][CS_XSTRIDE] granules
+  DevBuf<unsigned int> d_cs_sync;    // its arrival counter and abort word
   bool cs_host_layout = false;          // DSGD_CS_HOST_LAYOUT=1: a plan's slices laid out by the host (rounds 1-4; kept as the cross-check)
   bool cs_req = false;                  // DSGD_CS_REQ=1: per-request steps of the reference's sizes through dsgd_cs_request_kernel.  OFF by
                                         //   default: a slice's workgroup lays the step out before it runs it, one dependent trip to
@@ -235,8 +235,8 @@ struct dsgd_ctx {
                                         //   row-parallel kernels (profiles/r05_probe_v1.json); the kernel is kept, tested, and is what
                                         //   the abort-path test drives
   int cs_test_skip = 0;                 // (test builds: DSGD_TEST_CS_SKIP_PUBLISH -- slice 1 goes silent from this step of a launch on)
-  unsigned int* d_cs_max = nullptr;     // the layout kernels' maxima and flags (4 words) ...
-  unsigned int* h_cs_max = nullptr;     // ... and where pass 1's come back to (pinned)
+  DevBuf<unsigned int> d_cs_max;     // the layout kernels' maxima and flags (4 words) ...
+  HostBuf<unsigned int> h_cs_max;     // ... and where pass 1's come back to (pinned)
   hipStream_t build_stream = nullptr;   // a plan's set-up (uploads, layout kernels) runs here, beside the launch stream
   // device blocks that plans hand back (dsgd_plan_destroy) and take again (dsgd_plan_create): an epoch of the reference is
   // one plan (core/Master.scala:179-199), so plans come and go with every epoch -- hipMalloc / hipFree per plan (the
@@ -248,22 +248,21 @@ struct dsgd_ctx {
     unsigned long long tick = 0;        // cache_tick when it came back: a block no plan took for CACHE_MAX_AGE hand-backs is freed
   };
   std::vector<CacheBlock> cache;
+  std::vector<dsgd_plan*> plans;        // the plans alive: what dsgd_plan_destroy did not see, dsgd_destroy gives back and deletes
   size_t cache_bytes = 0;
   unsigned long long cache_tick = 0;
   size_t cache_cap = (size_t)8 << 30;   // DSGD_CACHE_MB (dsgd_cache_trim gives blocks back on request)
   std::vector<hipEvent_t> ev_pool;      // events of blocks in use, for the next ones
   // scratch of dsgd_plan_create_from_seed, kept across epochs (grow-only): a hipFree per epoch would wait for the whole
   // device -- i.e. for the epoch that is running on the launch stream while the next one's lists are drawn
-  void* seed_scratch[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t seed_scratch_bytes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  DevBuf<void> seed_scratch[9];   // (bytes)
   // the one-step layout of per-request steps (dsgd_cs_request_kernel), strides at their maxima, per slice count
   struct ReqLayout {
-    CsHdr* hdr = nullptr;
-    unsigned int* meta = nullptr;
-    unsigned short* rf = nullptr;
-    unsigned short* col = nullptr;
-    float* val = nullptr;
-    unsigned short* cl = nullptr;
+    DevBuf<CsHdr> hdr;
+    DevBuf<unsigned int> meta;
+    DevBuf<unsigned short> rf, col;
+    DevBuf<float> val;
+    DevBuf<unsigned short> cl;
     int G = 0;
   } req_layout;
   bool vt_enable = true;                // DSGD_VT=0: index-list steps of resident plans through dsgd_mb_grad_kernel
@@ -271,48 +270,48 @@ struct dsgd_ctx {
   int vt_tpw = 1;                       // DSGD_VT_TPW: virtual tiles per wave the grid is sized for (measured: 1 beats 2-4 up to B = 65,536)
   std::vector<signed char> h_label;
   // wave tiles over d_hcol/d_hval
-  WTile* d_wtiles = nullptr;
-  unsigned short* d_wmeta = nullptr;
+  DevBuf<WTile> d_wtiles;
+  DevBuf<unsigned short> d_wmeta;
   long long n_wtiles = 0;
   std::vector<int> h_wtile_r0;          // first row of every wave tile (+ sentinel n_rows)
   std::vector<long long> wlong_rows;    // rows that fit no wave tile (sorted): one wave per row, from the whole CSR
   std::vector<long long> wlong_weight;  // prefix sums of their weights in the row chunks' balance (slots; fstep_layout)
-  int* d_wlong_rows = nullptr;          // the same list on the device
-  int* d_part = nullptr;                // per-workgroup partial sums of the wseg gradient kernel: part_wgs x part_stride
+  DevBuf<int> d_wlong_rows;          // the same list on the device
+  DevBuf<int> d_part;                // per-workgroup partial sums of the wseg gradient kernel: part_wgs x part_stride
   long long part_wgs = 0;
   int part_stride = 0;
   int hsplit = (DSGD_LDS_FLOATS - 16 * WS_COEF_STRIDE - 4 - 64) / 2;         // hot ranks: 2 * hsplit words of LDS
-  unsigned short* d_hcol = nullptr;     // hot stream (16-bit ranks < hsplit), WS_PAD elements of padding
-  float* d_hval = nullptr;
-  long long* d_hrow_ptr = nullptr;      // n_rows + 1 (rows of the long list: empty)
+  DevBuf<unsigned short> d_hcol;     // hot stream (16-bit ranks < hsplit), WS_PAD elements of padding
+  DevBuf<float> d_hval;
+  DevBuf<long long> d_hrow_ptr;      // n_rows + 1 (rows of the long list: empty)
   long long hot_nnz = 0;
-  void* d_ccol = nullptr;               // cold stream in row order: rank - hsplit (16-bit words, or 32-bit when there
-  float* d_cval = nullptr;              // are more than 65536 cold columns), value; WS_PAD elements of padding
+  DevBuf<void> d_ccol;               // cold stream in row order: rank - hsplit (16-bit words, or 32-bit when there
+  DevBuf<float> d_cval;              // are more than 65536 cold columns), value; WS_PAD elements of padding
   bool cold_col16 = false;
-  long long* d_ctp = nullptr;           // n_rows + 1: slot offsets of the cold stream (a tiled row owns >= 1 slot)
+  DevBuf<long long> d_ctp;           // n_rows + 1: slot offsets of the cold stream (a tiled row owns >= 1 slot)
   long long coldm_nnz = 0;              // slots of the cold stream
-  WTile* d_ctiles = nullptr;            // wave tiles over d_ccol/d_cval (same records and lane descriptors as the hot ones)
-  unsigned short* d_cmeta = nullptr;
+  DevBuf<WTile> d_ctiles;            // wave tiles over d_ccol/d_cval (same records and lane descriptors as the hot ones)
+  DevBuf<unsigned short> d_cmeta;
   long long n_ctiles = 0;
   std::vector<int> h_ctile_r0;          // first row of every cold tile (+ sentinel n_rows)
-  float* d_dcold = nullptr;             // n_rows: cold part of x.w (rows without cold entries stay 0)
-  int* d_partc = nullptr;               // per-workgroup cold gradient partials: partc_wgs x partc_stride
+  DevBuf<float> d_dcold;             // n_rows: cold part of x.w (rows without cold entries stay 0)
+  DevBuf<int> d_partc;               // per-workgroup cold gradient partials: partc_wgs x partc_stride
   long long partc_wgs = 0;
   int partc_stride = 0;
-  signed char* d_coef8 = nullptr;  // n_rows: gate coefficient y * [y (x . w) >= 0] of the last whole-range step
+  DevBuf<signed char> d_coef8;  // n_rows: gate coefficient y * [y (x . w) >= 0] of the last whole-range step
   const char* last_grad_kernel = "";
   // vectors
-  float* d_w = nullptr;
-  float* d_ds = nullptr;
-  float* d_g = nullptr;  // g_cap x dp
-  long long* d_g64 = nullptr;  // g_cap x dp fixed-point accumulators of the streaming kernel (zero between steps)
+  DevBuf<float> d_w;
+  DevBuf<float> d_ds;
+  DevBuf<float> d_g;  // workers x dp
+  DevBuf<long long> d_g64;  // workers x dp fixed-point accumulators of the streaming kernel (zero between steps)
   float fix_scale = 4194304.0f;  // 2^FIX_SHIFT / vmax2
   int vexp = 0;                  // vmax2 = 2^vexp >= max |value|
   int last_shift = FIX_SHIFT;    // shift of the last gradient launch (streaming kernels or index-list kernel)
   std::vector<StreamSeg> bound_segs;   // split layout: the (ranges, grid) configuration bound_shift was measured for
   unsigned bound_grid = 0;
   int bound_shift = 0;
-  unsigned int* d_bound = nullptr;
+  DevBuf<unsigned int> d_bound;
   int max_shift = FIX_SHIFT;     // DSGD_FIX_SHIFT: cap of the per-launch fixed-point shift of the split layout
   // Row chunks (csrc/dsgd_fstep.hpp): the whole gradient of a row range in ONE launch.  Per (row ranges, workgroups per
   // worker) configuration the host cuts the ranges into chunks balanced by stream bytes and lays out wave tiles of both
@@ -321,19 +320,19 @@ struct dsgd_ctx {
   struct FstepLayout {
     std::vector<long long> ranges;   // row_begin, row_end per worker
     int n_wg = 0;                    // workgroups (chunks) per worker
-    WTile* d_tiles = nullptr;
-    unsigned short* d_meta = nullptr;
-    WTile* d_ctiles = nullptr;
-    unsigned short* d_cmeta = nullptr;
-    FChunk* d_chunks = nullptr;
+    DevBuf<WTile> d_tiles;
+    DevBuf<unsigned short> d_meta;
+    DevBuf<WTile> d_ctiles;
+    DevBuf<unsigned short> d_cmeta;
+    DevBuf<FChunk> d_chunks;
     long long worst_rows = 1;        // rows of the largest chunk
     int shift = -1;                  // the measured fixed-point shift of the hot accumulators (-1: not measured yet)
     unsigned long long used = 0;
     // measured balance (round 6): the workgroups' own durations, summed by the kernel over `launches` launches, re-cut the
     // chunks once or twice per configuration (a chunk's share of the weight follows its workgroup's measured rate)
-    unsigned long long* d_times = nullptr;
-    unsigned long long* h_times = nullptr;   // pinned
-    hipEvent_t times_ev = nullptr;
+    DevBuf<unsigned long long> d_times;
+    HostBuf<unsigned long long> h_times;   // pinned
+    Event times_ev;
     std::vector<double> share;       // per chunk: its share of its worker's weight (empty: equal shares)
     int launches = 0, rebalances = 0;
     bool times_pending = false;
@@ -359,12 +358,12 @@ struct dsgd_ctx {
     long long n_ent = 0;             // entries of the ranges' rows
     int share = 0, n_wg = 0;         // entries per workgroup of the gradient kernel, its workgroups
     int bm_words = 0;                // words of the step's bitmap (every worker's range padded to 64 rows; a multiple of 4)
-    unsigned int* d_ent_pk = nullptr;
-    float* d_ent_val = nullptr;
-    TcShare* d_shares = nullptr;
-    int* d_key_of_cid = nullptr;
-    int* d_bit_base = nullptr;       // [workers]
-    unsigned int* d_bitmap = nullptr;   // the gate's decisions of the last step over these ranges
+    DevBuf<unsigned int> d_ent_pk;
+    DevBuf<float> d_ent_val;
+    DevBuf<TcShare> d_shares;
+    DevBuf<int> d_key_of_cid;
+    DevBuf<int> d_bit_base;       // [workers]
+    DevBuf<unsigned int> d_bitmap;   // the gate's decisions of the last step over these ranges
     unsigned long long used = 0;
   };
   std::vector<TcolLayout> tcol_cache;
@@ -382,47 +381,41 @@ struct dsgd_ctx {
   int tcol_share = 0;                // DSGD_TCOL_SHARE: entries per workgroup of the gradient kernel (0: entries / CUs, within [1024, 8192])
   bool fused_apply_pending = false;
   FusedArgs fused_args{};
-  float* d_redpart = nullptr;    // per-block partial sums of w.ds and |w|^2 of the fused reduce + apply kernel
+  DevBuf<float> d_redpart;    // per-block partial sums of w.ds and |w|^2 of the fused reduce + apply kernel
   int redpart_cap = 0;
   // Pinned staging of the per-request entry points (Slave.gradient / Slave.forward hand over w and the sample indices
   // and get a dense vector back): a copy between pageable memory and the device is staged by the runtime, blocks the
   // calling thread and cannot overlap the kernels around it (151 us for a batch-size-100 dsgd_gradient, of which the
   // kernels are ~35: profiles/r02_boundary_latency.json).
   struct Pinned {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipEvent_t ev = nullptr;   // the last copy FROM this buffer to the device
+    HostBuf<void> p;           // (bytes)
+    Event ev;                  // the last copy FROM this buffer to the device
     bool armed = false;
   };
   Pinned pin_w, pin_idx, pin_segs, pin_out, pin_upd;
   // dsgd_update_grad: persistent device staging (keys, values) -- no allocation per call, nothing that synchronises the
   // device while the persistent engine is resident
-  int* d_upd_key = nullptr;
-  float* d_upd_dv = nullptr;
-  long long upd_cap = 0;
+  DevBuf<int> d_upd_key;
+  DevBuf<float> d_upd_dv;
   hipStream_t upd_stream = nullptr;
-  float* d_pred = nullptr;     // dsgd_forward's predictions (grown on demand)
-  long long pred_cap = 0;
+  DevBuf<float> d_pred;     // dsgd_forward's predictions (grown on demand)
   bool fix_bound = true;         // DSGD_FIX_BOUND=0: keep the data-independent bound (rows per workgroup x largest value)
-  int g_cap = 0;
-  float* d_gsum = nullptr;  // dp (all-reduce buffer / sum over hosted workers)
-  float* d_tmp = nullptr;   // dp scratch (ranked order)
-  float* d_io = nullptr;    // dp staging for vectors crossing the API in key order
-  DevScalars* d_sc = nullptr;
-  DevScalars* h_sc = nullptr;  // pinned
+  DevBuf<float> d_gsum;  // dp (all-reduce buffer / sum over hosted workers)
+  DevBuf<float> d_tmp;   // dp scratch (ranked order)
+  DevBuf<float> d_io;    // dp staging for vectors crossing the API in key order
+  DevBuf<DevScalars> d_sc;
+  HostBuf<DevScalars> h_sc;  // pinned
   // per-request steps: {n_active, err} written by the request's last kernel into host-mapped memory (no copy back);
   // n_active is read as a DIFFERENCE against the value the host last saw, so the request needs no memset either
-  int* h_req = nullptr;                   // host-mapped index lists of a per-request step (REQ_MAPPED_ITEMS entries) ...
-  int* d_req = nullptr;                   // ... their device address
+  HostBuf<int> h_req;                   // host-mapped index lists of a per-request step (REQ_MAPPED_ITEMS entries; the kernels read .dev())
   const int* cur_idx = nullptr;           // where stage_lists put the lists of the request in flight
   bool req_mapped = true;                 // DSGD_REQ_MAPPED=0: always the copy on the stream
   bool req_spin = true;                   // DSGD_REQ_SPIN=0: wait for the stream instead of polling the mailbox
   bool req_plan = false;                  // DSGD_REQ_PLAN=1: one-worker requests of <= 192 rows through the one-workgroup kernel (its
                                           //   launch re-derives s in fp64 and sets up 147 KB of LDS for ONE step: 37 us per request at the
                                           //   C ABI against 32 us through the row-parallel kernels -- profiles/r04_boundary_latency.json)
-  unsigned long long* h_mail = nullptr;   // host-mapped: {n_active, err, sequence number of the request that wrote them, -}
+  HostBuf<unsigned long long> h_mail;   // host-mapped: {n_active, err, sequence number of the request that wrote them, -}
   unsigned long long mail_seq = 0;        // requests answered through the mailbox so far
-  unsigned long long* d_mail = nullptr;   // ... its device address
   bool ctr_known = false;                 // the host knows the device's n_active (ctr_last) and that err is clear
   unsigned long long ctr_last = 0;
   bool s_dirty = true;
@@ -431,31 +424,27 @@ struct dsgd_ctx {
   bool nsq_dirty = false;   // |w|^2 stale although s is current (after dsgd_plan_kernel)
   bool have_ds = false;
   // staging for host-provided index lists
-  int* d_idx = nullptr;
-  long long idx_cap = 0;
-  WorkSeg* d_segs = nullptr;
-  int segs_cap = 0;
+  DevBuf<int> d_idx;
+  DevBuf<WorkSeg> d_segs;
   std::vector<WorkSeg> segs_last;  // what d_segs currently holds
   long long pending_samples = 0;   // rows enqueued by *_async calls since the last dsgd_synchronize
   // persistent Hogwild engine
   hipStream_t async_stream = nullptr;
   hipStream_t query_stream = nullptr;
-  HogState* d_hog = nullptr;
-  HogState* h_hog = nullptr;   // pinned
-  float* d_gcold = nullptr;
-  long long* d_asg = nullptr;  // begin[n], end[n]
-  unsigned long long* d_hog_it = nullptr;   // per worker: iterations done (continues across exchange rounds)
-  unsigned int* d_trace = nullptr;          // dsgd_async_set_trace: one record per update of the next engine runs
+  DevBuf<HogState> d_hog;
+  HostBuf<HogState> h_hog;   // pinned
+  DevBuf<float> d_gcold;
+  DevBuf<long long> d_asg;  // begin[n], end[n]
+  DevBuf<unsigned long long> d_hog_it;   // per worker: iterations done (continues across exchange rounds)
+  DevBuf<unsigned int> d_trace;          // dsgd_async_set_trace: one record per update of the next engine runs
   long long trace_cap = 0;                  // records asked for
-  long long trace_words = 0;                // words allocated at d_trace
   int trace_mw = 0;                         // mask words per record of the last traced run ((batch + 31) / 32)
   int trace_batch = 0;                      // ... and its batch size (a record carries one x . w per sampled row)
-  float* d_tdot = nullptr;                  // traced runs: n_workers x batch, the x . w of every worker's mini-batch in flight
-  long long tdot_words = 0;
-  int* h_one = nullptr;        // pinned constant 1: source of the stop-flag copy
+  DevBuf<float> d_tdot;                  // traced runs: n_workers x batch, the x . w of every worker's mini-batch in flight
+  HostBuf<int> h_one;        // pinned constant 1: source of the stop-flag copy
   // small-batch plan kernel (one persistent workgroup): cold strip and the multi-worker sum buffer
-  unsigned long long* d_tprof = nullptr;   // DSGD_PLAN_PROF=1: phase cycle counters of dsgd_plan_kernel (tuning runs)
-  float* d_plan_gcold = nullptr;
+  DevBuf<unsigned long long> d_tprof;   // DSGD_PLAN_PROF=1: phase cycle counters of dsgd_plan_kernel (tuning runs)
+  DevBuf<float> d_plan_gcold;
   bool plan_kernel = true;     // DSGD_PLAN_KERNEL=0: the multi-launch small-batch path
   int hog_hl = HOG_HL, hog_wl = HOG_WL;   // LDS-resident ranks of the Hogwild engine (accumulators / weight copy)
   long long plan_max_rows = 2048;   // steps with more rows in total use the multi-workgroup kernels
@@ -464,8 +453,8 @@ struct dsgd_ctx {
   float hog_lr = 0.0f;
   unsigned long long hog_seed = 0;
   long long exchange_every = 0;   // dsgd_async_set_exchange: cross-GPU exchange period in local updates (0 = none)
-  float* d_wprev = nullptr;       // weights at the last exchange
-  float* d_wdelta = nullptr;      // 2 x dp: all-reduced updates, this replica's own part
+  DevBuf<float> d_wprev;       // weights at the last exchange
+  DevBuf<float> d_wdelta;      // 2 x dp: all-reduced updates, this replica's own part
   bool async_running = false;
   bool join_in_progress = false;            // one thread blocks on the engine (without the mutex); the others wait for it
   std::condition_variable join_cv;
@@ -494,49 +483,46 @@ struct dsgd_ctx {
   // the fp64 mode (DSGD_F_FP64, csrc/dsgd_cs64.hpp): the weights and dimSparsity in fp64, rank order like d_w / d_ds; while
   // cs_w_G != 0 the weights are slice-major in d_cs_w64 (bind converts back, as for fp32)
   bool fp64 = false;
-  double* d_w64 = nullptr;
-  double* d_ds64 = nullptr;
-  double* d_io64 = nullptr;               // dp staging (key order) / scratch
-  double* d_cs_w64 = nullptr;
-  double* d_cs_ds64 = nullptr;
-  double* d_nsq64 = nullptr;              // |w|^2 of the loss
-  unsigned long long* d_cs64_x = nullptr; // exchange buffer of dsgd_cs64_step_kernel: [2][CS64_G][2 * CS_XSTRIDE] granules
+  DevBuf<double> d_w64;
+  DevBuf<double> d_ds64;
+  DevBuf<double> d_io64;               // dp staging (key order) / scratch
+  DevBuf<double> d_cs_w64;
+  DevBuf<double> d_cs_ds64;
+  DevBuf<double> d_nsq64;              // |w|^2 of the loss
+  DevBuf<unsigned long long> d_cs64_x; // exchange buffer of dsgd_cs64_step_kernel: [2][CS64_G][2 * CS_XSTRIDE] granules
   unsigned int cs64_tag0 = 0;
-  double* d_cs_dl64 = nullptr;            // dsgd_async_step_f64: the update of the listed columns, slice-major [CS64_G][Sp]
-  int* d_upd64_key = nullptr;             // dsgd_update_grad_f64: the keys and values of a peer's update (grow-only)
-  double* d_upd64_dv = nullptr;
-  long long upd64_cap = 0;
+  DevBuf<double> d_cs_dl64;            // dsgd_async_step_f64: the update of the listed columns, slice-major [CS64_G][Sp]
+  DevBuf<int> d_upd64_key;             // dsgd_update_grad_f64: the keys and values of a peer's update (grow-only)
+  DevBuf<double> d_upd64_dv;
   // the row-parallel fp64 family (csrc/dsgd_rp64.hpp): [rp64_k][rp64_stride] fixed-point column sums, zero between calls
   // (grow-only), s of the call, the gradient in key order
-  unsigned long long* d_rp64_acc = nullptr;
+  DevBuf<unsigned long long> d_rp64_acc;
   long long rp64_stride = 0;
   int rp64_k = 0;
-  double* d_rp64_s = nullptr;
-  double* d_rp64_g = nullptr;
+  DevBuf<double> d_rp64_s;
+  DevBuf<double> d_rp64_g;
   // ... across ranks (dsgd_comm_init_f64): the gather buffer ([world, padded][rp64_gk][rp64_gstride], zero between calls), the
   // list ranges its header kernel writes for the finish, and the pinned words the ranks' worker counts are read into
-  unsigned long long* d_rp64_gath = nullptr;
+  DevBuf<unsigned long long> d_rp64_gath;
   long long rp64_gstride = 0;
   int rp64_gk = 0;
-  WorkSeg* d_rp64_gsegs = nullptr;
-  unsigned long long* h_rp64_ranks = nullptr;
+  DevBuf<WorkSeg> d_rp64_gsegs;
+  HostBuf<unsigned long long> h_rp64_ranks;
   // Double feature values (dsgd_load_csr_f64; csrc/dsgd_rp64.hpp): the values parallel to d_col / d_val (which holds them
   // rounded), and the low words of the two-word column sums ([rp64v_k][rp64_stride], zero between calls; the high words
   // are d_rp64_acc)
-  double* d_val64 = nullptr;
-  unsigned long long* d_rp64v_lo = nullptr;
+  DevBuf<double> d_val64;
+  DevBuf<unsigned long long> d_rp64v_lo;
   int rp64v_k = 0;
   long long rp64v_stride = 0;
   // an epoch's steps in one call (dsgd_sync_steps_f64): the call's list ranges ([n_steps][K]) and per-step running active
   // counts, the fused step's arrival counter, whose bit 62 says that a launch gave up (a 16-byte block of its own: word 0), with
   // the pinned copy the host reads it into, the target the last fused launch was given, the bound of a workgroup's wait in ticks of the device's wall
   // clock, and how many workgroups of each fused kernel a compute unit holds (0: not asked yet)
-  WorkSeg* d_rp64_ssegs = nullptr;
-  long long rp64_ssegs_cap = 0;
-  unsigned long long* d_rp64_cum = nullptr;
-  long long rp64_cum_cap = 0;
-  unsigned long long* d_rp64_sync = nullptr;
-  unsigned long long* h_rp64_sync = nullptr;
+  DevBuf<WorkSeg> d_rp64_ssegs;
+  DevBuf<unsigned long long> d_rp64_cum;
+  DevBuf<unsigned long long> d_rp64_sync;
+  HostBuf<unsigned long long> h_rp64_sync;
   unsigned long long rp64_target = 0;
   unsigned long long rp64_wait_ticks = 0;
   int rp64_occ[2] = {0, 0};               // [0] dsgd_rp64_step_kernel, [1] dsgd_rp64v_step_kernel
@@ -544,13 +530,12 @@ struct dsgd_ctx {
   bool rp64_fused = RP64_FUSED_DEFAULT;   // DSGD_RP64_FUSED
   // Sparse values at the boundary (csrc/dsgd_sparse.hpp): the compaction's output in host-mapped memory the kernel writes in
   // place ([2 words: count, gave up][dp keys][dp values of 8 bytes]), its scan state, and the staged pairs of a sparse setter
-  unsigned long long* h_sp_out = nullptr;
-  unsigned long long* d_sp_out = nullptr;   // the same memory as the device sees it
-  unsigned long long* d_sp_state = nullptr;
+  HostBuf<unsigned long long> h_sp_out;
+  DevBuf<unsigned long long> d_sp_state;
   unsigned long long sp_launches = 0;
   unsigned int sp_epoch = 0;
   Pinned pin_sp;
-  char* d_sp_in = nullptr;                  // [dp keys][dp values of 8 bytes]
+  DevBuf<char> d_sp_in;                  // [dp keys][dp values of 8 bytes]
   std::vector<unsigned int> sp_seen;        // key -> the stamp of the call that saw it last (the repeated-key check)
   unsigned int sp_stamp = 0;
   std::vector<int32_t> row_len;             // the loaded rows' lengths (the bound on an asynchronous step's delta)
@@ -597,8 +582,8 @@ static CsrViewT<V> view_of(dsgd_ctx* c, const V* val) {
   v.label = c->d_label;
   return v;
 }
-static CsrView view(dsgd_ctx* c) { return view_of(c, c->d_val); }
-static CsrView64 view64(dsgd_ctx* c) { return view_of(c, c->d_val64); }   // (Double data loaded: dsgd_load_csr_f64)
+static CsrView view(dsgd_ctx* c) { return view_of(c, c->d_val.get()); }
+static CsrView64 view64(dsgd_ctx* c) { return view_of(c, c->d_val64.get()); }   // (Double data loaded: dsgd_load_csr_f64)
 
 // host -> device through a pinned buffer of the context: wait until the previous copy out of it has executed, then the
 // caller fills it and enqueues the copy (pin_sent); device -> host: enqueue into pin_out, synchronise, copy out.
@@ -607,15 +592,8 @@ static int pin_acquire(dsgd_ctx::Pinned& b, size_t bytes) {
     HIP_TRY(hipEventSynchronize(b.ev));
     b.armed = false;
   }
-  if (bytes > b.cap) {
-    if (b.p) HIP_TRY(hipHostFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    const size_t cap = std::max<size_t>(bytes, 4096);
-    HIP_TRY(hipHostMalloc(&b.p, cap, hipHostMallocDefault));
-    b.cap = cap;
-  }
-  if (!b.ev) HIP_TRY(hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
+  DSGD_TRY(b.p.reserve(std::max<size_t>(bytes, 4096)));
+  if (!b.ev) HIP_TRY(hipEventCreateWithFlags(&b.ev.e, hipEventDisableTiming));
   return DSGD_OK;
 }
 static int pin_sent(dsgd_ctx* c, dsgd_ctx::Pinned& b, hipStream_t on = nullptr) {
@@ -623,45 +601,29 @@ static int pin_sent(dsgd_ctx* c, dsgd_ctx::Pinned& b, hipStream_t on = nullptr) 
   b.armed = true;
   return DSGD_OK;
 }
-static void pin_free(dsgd_ctx::Pinned& b) {
-  if (b.ev) (void)hipEventDestroy(b.ev);
-  if (b.p) (void)hipHostFree(b.p);
-  b = dsgd_ctx::Pinned();
-}
 
 static int ensure_g(dsgd_ctx* c, int n_workers) {
-  if (n_workers <= c->g_cap) return DSGD_OK;
+  const size_t n = (size_t)n_workers * c->dp;
+  if (n <= c->d_g.cap() && n <= c->d_g64.cap()) return DSGD_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->d_g) HIP_TRY(hipFree(c->d_g));
-  if (c->d_g64) HIP_TRY(hipFree(c->d_g64));
-  c->d_g = nullptr;
-  c->d_g64 = nullptr;
-  HIP_TRY(hipMalloc(&c->d_g, sizeof(float) * (size_t)n_workers * c->dp));
-  HIP_TRY(hipMalloc(&c->d_g64, sizeof(long long) * (size_t)n_workers * c->dp));
+  c->d_g.reset();
+  c->d_g64.reset();
+  DSGD_TRY(c->d_g.alloc(n));
+  DSGD_TRY(c->d_g64.alloc(n));
   HIP_TRY(hipMemsetAsync(c->d_g, 0, sizeof(float) * (size_t)n_workers * c->dp, c->stream));
   HIP_TRY(hipMemsetAsync(c->d_g64, 0, sizeof(long long) * (size_t)n_workers * c->dp, c->stream));
-  c->g_cap = n_workers;
   return DSGD_OK;
 }
 static int ensure_idx(dsgd_ctx* c, long long n) {
-  if (n <= c->idx_cap) return DSGD_OK;
+  if ((size_t)n <= c->d_idx.cap()) return DSGD_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->d_idx) HIP_TRY(hipFree(c->d_idx));
-  c->d_idx = nullptr;
-  long long cap = std::max<long long>(n, 2 * c->idx_cap);
-  HIP_TRY(hipMalloc(&c->d_idx, sizeof(int) * (size_t)cap));
-  c->idx_cap = cap;
-  return DSGD_OK;
+  return c->d_idx.reserve((size_t)n, Grow::twice);
 }
 static int ensure_segs(dsgd_ctx* c, int n) {
-  if (n <= c->segs_cap) return DSGD_OK;
+  if ((size_t)n <= c->d_segs.cap()) return DSGD_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->d_segs) HIP_TRY(hipFree(c->d_segs));
-  c->d_segs = nullptr;
-  HIP_TRY(hipMalloc(&c->d_segs, sizeof(WorkSeg) * (size_t)n));
-  c->segs_cap = n;
   c->segs_last.clear();
-  return DSGD_OK;
+  return c->d_segs.reserve((size_t)n);
 }
 
 // upload work segments; identical consecutive uploads (timed loops over the same ranges) are skipped
@@ -683,9 +645,8 @@ static int ensure_redpart(dsgd_ctx* c) {
   const int blocks = (c->dp + FRA_COLS - 1) / FRA_COLS;
   if (blocks <= c->redpart_cap) return DSGD_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->d_redpart) HIP_TRY(hipFree(c->d_redpart));
-  c->d_redpart = nullptr;
-  HIP_TRY(hipMalloc(&c->d_redpart, sizeof(float) * 4 * (size_t)blocks));   // two halves: see red_out
+  c->redpart_cap = 0;
+  DSGD_TRY(c->d_redpart.alloc(4 * (size_t)blocks));   // two halves: see red_out
   c->redpart_cap = blocks;
   return DSGD_OK;
 }
@@ -727,7 +688,7 @@ static int read_scalars(dsgd_ctx* c) {
 }
 static int reset_counters(dsgd_ctx* c) {
   // err .. counts: everything after s_reg / wnorm2
-  HIP_TRY(hipMemsetAsync((char*)c->d_sc + offsetof(DevScalars, err), 0, sizeof(DevScalars) - offsetof(DevScalars, err),
+  HIP_TRY(hipMemsetAsync((char*)c->d_sc.get() + offsetof(DevScalars, err), 0, sizeof(DevScalars) - offsetof(DevScalars, err),
                          c->stream));
   c->ctr_known = true;   // (until the next gradient launch)
   c->ctr_last = 0;
@@ -795,7 +756,7 @@ static int prof_collect(dsgd_ctx* c) {  // stream must be idle
   return DSGD_OK;
 }
 
-static int ensure_part(dsgd_ctx* c, int** buf, long long* wgs, int* stride, long long need_wgs, int need_cols);
+static int ensure_part(dsgd_ctx* c, DevBuf<int>& buf, long long* wgs, int* stride, long long need_wgs, int need_cols);
 
 // Index-list batches spread over workgroups (dsgd_mb_grad_kernel): per-workgroup fixed-point partials, then the exact
 // finish of the streaming path.  `allow_fused`: the caller goes on to launch_finish_sync (one hosted worker without
@@ -806,7 +767,7 @@ static int launch_grad_mb(dsgd_ctx* c, const int* d_idx, const WorkSeg* d_segs, 
   const long long per_worker = std::max<long long>(1, c->n_cu / n_workers);
   long long rows_per_wg = std::max<long long>(64, (max_items + per_worker - 1) / per_worker);
   const long long wgs = std::max<long long>(1, (max_items + rows_per_wg - 1) / rows_per_wg);
-  DSGD_TRY(ensure_part(c, &c->d_part, &c->part_wgs, &c->part_stride, wgs * n_workers, hl));
+  DSGD_TRY(ensure_part(c, c->d_part, &c->part_wgs, &c->part_stride, wgs * n_workers, hl));
   int bits = 0;
   while ((1LL << bits) < rows_per_wg) ++bits;
   const int shift = 30 - bits;   // at most one contribution per row and column: a workgroup's sums stay below 2^30
@@ -866,17 +827,16 @@ static int launch_grad_mb(dsgd_ctx* c, const int* d_idx, const WorkSeg* d_segs, 
     }                                 \
   } while (0)
 static int plan_host_idx(dsgd_ctx* c, dsgd_plan* p);
+static void vt_drop(dsgd_plan* p) {
+  p->d_vt_lanes.reset();
+  p->d_vt_segs.reset();
+  p->d_vt_long.reset();
+  p->d_vt_packed.reset();
+}
 static int vt_build_impl(dsgd_ctx* c, dsgd_plan* p) {
   p->vt_layout = c->layout_gen;
   p->vt_ok = false;
-  (void)hipFree(p->d_vt_lanes);
-  (void)hipFree(p->d_vt_segs);
-  (void)hipFree(p->d_vt_long);
-  (void)hipFree(p->d_vt_packed);
-  p->d_vt_lanes = nullptr;
-  p->d_vt_segs = nullptr;
-  p->d_vt_long = nullptr;
-  p->d_vt_packed = nullptr;
+  vt_drop(p);
   const int H = std::min(c->hsplit, c->dp);
   const long long n_lists = (long long)p->n_steps * p->n_workers;
   if (!c->cold_col16 || c->dp <= H || c->hot_nnz + WS_PAD >= (1LL << 32) || c->coldm_nnz + WS_PAD >= (1LL << 32)) return DSGD_OK;
@@ -971,9 +931,9 @@ static int vt_build_impl(dsgd_ctx* c, dsgd_plan* p) {
     p->vt_grid[(size_t)s] = (int)(gx + gl);
     p->vt_shift[(size_t)s] = std::min(21, 30 - bits);   // (<= 21: the fixed-point conversion is one fma against 1.5 * 2^23)
   }
-  VT_SOFT(hipMalloc(&p->d_vt_lanes, sizeof(VtLane) * std::max<size_t>(lanes.size(), 64)));
-  VT_SOFT(hipMalloc(&p->d_vt_segs, sizeof(WorkSeg) * segs.size()));
-  VT_SOFT(hipMalloc(&p->d_vt_long, sizeof(MbRec) * std::max<size_t>(long_rows.size(), 1)));
+  VT_SOFT(p->d_vt_lanes.try_alloc(std::max<size_t>(lanes.size(), 64)));
+  VT_SOFT(p->d_vt_segs.try_alloc(segs.size()));
+  VT_SOFT(p->d_vt_long.try_alloc(std::max<size_t>(long_rows.size(), 1)));
   HIP_TRY(hipMemcpy(p->d_vt_lanes, lanes.data(), sizeof(VtLane) * lanes.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(p->d_vt_segs, segs.data(), sizeof(WorkSeg) * segs.size(), hipMemcpyHostToDevice));
   if (!long_rows.empty())
@@ -989,15 +949,13 @@ static int vt_build_impl(dsgd_ctx* c, dsgd_plan* p) {
     mem_free = 0;
   }
   if (n_tiles > 0 && n_tiles * 4096 <= c->vt_pack_mb * (1LL << 20) && (size_t)n_tiles * 4096 <= mem_free / 4 &&
-      hipMalloc(&p->d_vt_packed, (size_t)n_tiles * 4096) != hipSuccess) {
+      p->d_vt_packed.try_alloc((size_t)n_tiles * (4096 / sizeof(uint4))) != hipSuccess)
     (void)hipGetLastError();      // (no room for the copy: the plan runs from its descriptors)
-    p->d_vt_packed = nullptr;
-  }
   if (p->d_vt_packed) {
     VtArgs a{};
     a.hcol = c->d_hcol;
     a.hval = c->d_hval;
-    a.ccol = reinterpret_cast<const unsigned short*>(c->d_ccol);
+    a.ccol = reinterpret_cast<const unsigned short*>(c->d_ccol.get());
     a.cval = c->d_cval;
     a.w = c->d_w;
     a.lanes = p->d_vt_lanes;
@@ -1019,14 +977,7 @@ static int vt_build(dsgd_ctx* c, dsgd_plan* p) {
     rc = 1;
   }
   if (rc == 1) {
-    (void)hipFree(p->d_vt_lanes);
-    (void)hipFree(p->d_vt_segs);
-    (void)hipFree(p->d_vt_long);
-    (void)hipFree(p->d_vt_packed);
-    p->d_vt_lanes = nullptr;
-    p->d_vt_segs = nullptr;
-    p->d_vt_long = nullptr;
-    p->d_vt_packed = nullptr;
+    vt_drop(p);
     p->vt_ok = false;   // (vt_layout is stamped: the plan keeps the row-wise kernel until the layout changes)
     return DSGD_OK;
   }
@@ -1036,12 +987,12 @@ static int vt_build(dsgd_ctx* c, dsgd_plan* p) {
 static int launch_grad_vt(dsgd_ctx* c, dsgd_plan* p, long long step) {
   const int H = std::min(c->hsplit, c->dp);
   const int gx = p->vt_grid[(size_t)step], shift = p->vt_shift[(size_t)step];
-  DSGD_TRY(ensure_part(c, &c->d_part, &c->part_wgs, &c->part_stride, (long long)gx * p->n_workers, H));
+  DSGD_TRY(ensure_part(c, c->d_part, &c->part_wgs, &c->part_stride, (long long)gx * p->n_workers, H));
   c->last_shift = shift;
   VtArgs a;
   a.hcol = c->d_hcol;
   a.hval = c->d_hval;
-  a.ccol = reinterpret_cast<const unsigned short*>(c->d_ccol);
+  a.ccol = reinterpret_cast<const unsigned short*>(c->d_ccol.get());
   a.cval = c->d_cval;
   a.w = c->d_w;
   a.lanes = p->d_vt_lanes;
@@ -1108,16 +1059,16 @@ static int cache_take(dsgd_ctx* c, void** out, size_t bytes, size_t* got) {
     return DSGD_OK;
   }
   void* q = nullptr;
-  hipError_t e = hipMalloc(&q, bytes);
+  hipError_t e = dev_alloc(&q, bytes);
   if (e != hipSuccess && !c->cache.empty()) {   // (memory is tight: give the cached blocks back and try once more)
     (void)hipGetLastError();
     for (auto& b : c->cache) {
-      (void)hipFree(b.p);
+      dev_free(b.p);
       if (b.ev) c->ev_pool.push_back(b.ev);
     }
     c->cache.clear();
     c->cache_bytes = 0;
-    e = hipMalloc(&q, bytes);
+    e = dev_alloc(&q, bytes);
   }
   if (e != hipSuccess) {
     (void)hipGetLastError();
@@ -1136,7 +1087,7 @@ static void cache_trim(dsgd_ctx* c, size_t keep_bytes, bool aged_only) {
     const bool aged = c->cache_tick - b.tick > CACHE_MAX_AGE;
     const bool over = !aged_only && c->cache_bytes > keep_bytes;
     if ((aged || over) && (!b.ev || hipEventQuery(b.ev) == hipSuccess)) {
-      (void)hipFree(b.p);
+      dev_free(b.p);
       if (b.ev) c->ev_pool.push_back(b.ev);
       c->cache_bytes -= b.bytes;
       c->cache.erase(c->cache.begin() + (long)i);
@@ -1152,7 +1103,7 @@ static void cache_give(dsgd_ctx* c, void* q, size_t bytes) {
   ++c->cache_tick;
   if ((c->cache_tick & 15) == 0) cache_trim(c, c->cache_cap, true);
   if (bytes == 0 || c->cache_bytes + bytes > c->cache_cap || c->cache.size() >= 256) {
-    (void)hipFree(q);   // (not ours to keep: allocated outside the cache, or the cache is full)
+    dev_free(q);   // (not ours to keep: allocated outside the cache, or the cache is full)
     return;
   }
   dsgd_ctx::CacheBlock blk;
@@ -1163,7 +1114,7 @@ static void cache_give(dsgd_ctx* c, void* q, size_t bytes) {
     c->ev_pool.pop_back();
   } else if (hipEventCreateWithFlags(&blk.ev, hipEventDisableTiming) != hipSuccess) {
     (void)hipGetLastError();
-    (void)hipFree(q);
+    dev_free(q);
     return;
   }
   if (hipEventRecord(blk.ev, c->stream) != hipSuccess) {
@@ -1174,9 +1125,10 @@ static void cache_give(dsgd_ctx* c, void* q, size_t bytes) {
   c->cache.push_back(blk);
   c->cache_bytes += bytes;
 }
+static void plan_release(dsgd_ctx* c, dsgd_plan* p);   // (below, with the plans)
 static void cache_drop_all(dsgd_ctx* c) {   // (dsgd_destroy: the streams are idle)
   for (auto& b : c->cache) {
-    (void)hipFree(b.p);
+    dev_free(b.p);
     if (b.ev) (void)hipEventDestroy(b.ev);
   }
   for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1218,36 +1170,27 @@ static int ensure_build_stream(dsgd_ctx* c) {
 // the two must not leave the first behind alone)
 static int ensure_cs_exchange(dsgd_ctx* c) {
   if (!c->d_cs_x) {
-    unsigned long long* x = nullptr;
-    if (hipMalloc(&x, sizeof(unsigned long long) * 2 * CS_MAX_G * CS_XSTRIDE) != hipSuccess) {
+    DevBuf<unsigned long long> x;
+    const size_t n = (size_t)2 * CS_MAX_G * CS_XSTRIDE;
+    if (x.try_alloc(n) != hipSuccess || hipMemset(x, 0, sizeof(unsigned long long) * n) != hipSuccess) {
       (void)hipGetLastError();
       return 1;
     }
-    if (hipMemset(x, 0, sizeof(unsigned long long) * 2 * CS_MAX_G * CS_XSTRIDE) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(x);
-      return 1;
-    }
-    c->d_cs_x = x;
+    c->d_cs_x = std::move(x);
   }
   if (!c->d_cs_sync) {
-    unsigned int* y = nullptr;
-    if (hipMalloc(&y, sizeof(unsigned int) * 2) != hipSuccess) {
+    DevBuf<unsigned int> y;
+    if (y.try_alloc(2) != hipSuccess || hipMemset(y, 0, sizeof(unsigned int) * 2) != hipSuccess) {
       (void)hipGetLastError();
       return 1;
     }
-    if (hipMemset(y, 0, sizeof(unsigned int) * 2) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(y);
-      return 1;
-    }
-    c->d_cs_sync = y;
+    c->d_cs_sync = std::move(y);
   }
   return DSGD_OK;
 }
 static int ensure_cs_max(dsgd_ctx* c) {
-  if (!c->d_cs_max) HIP_TRY(hipMalloc(&c->d_cs_max, sizeof(unsigned int) * 4));
-  if (!c->h_cs_max) HIP_TRY(hipHostMalloc(&c->h_cs_max, sizeof(unsigned int) * 4, hipHostMallocDefault));
+  DSGD_TRY(c->d_cs_max.reserve(4));
+  DSGD_TRY(c->h_cs_max.reserve(4));
   return DSGD_OK;
 }
 // slices for K hosted workers: 8 up to four (wider slices, fewer peers in the exchange), 16 beyond or for a wide model
@@ -1395,17 +1338,12 @@ static int cs_build_impl(dsgd_ctx* c, dsgd_plan* p) {
   std::vector<int> ecol((size_t)std::max<long long>(E, 1));
   std::vector<float> eval((size_t)std::max<long long>(E, 1));
   {
-    long long* d_pre = nullptr;
-    int* d_ecol = nullptr;
-    float* d_eval = nullptr;
-    auto drop = [&]() {
-      (void)hipFree(d_pre);
-      (void)hipFree(d_ecol);
-      (void)hipFree(d_eval);
-    };
-    hipError_t e = hipMalloc(&d_pre, sizeof(long long) * pre.size());
-    if (e == hipSuccess) e = hipMalloc(&d_ecol, sizeof(int) * ecol.size());
-    if (e == hipSuccess) e = hipMalloc(&d_eval, sizeof(float) * eval.size());
+    DevBuf<long long> d_pre;   // (released at the end of this block, behind the synchronise)
+    DevBuf<int> d_ecol;
+    DevBuf<float> d_eval;
+    hipError_t e = d_pre.try_alloc(pre.size());
+    if (e == hipSuccess) e = d_ecol.try_alloc(ecol.size());
+    if (e == hipSuccess) e = d_eval.try_alloc(eval.size());
     if (e == hipSuccess) e = hipMemcpyAsync(d_pre, pre.data(), sizeof(long long) * pre.size(), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
       const int blocks = (int)std::max<long long>(1, std::min<long long>((N + 3) / 4, (long long)c->n_cu * 8));
@@ -1415,7 +1353,6 @@ static int cs_build_impl(dsgd_ctx* c, dsgd_plan* p) {
     if (e == hipSuccess && E > 0) e = hipMemcpyAsync(ecol.data(), d_ecol, sizeof(int) * (size_t)E, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && E > 0) e = hipMemcpyAsync(eval.data(), d_eval, sizeof(float) * (size_t)E, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    drop();
     if (e != hipSuccess) {
       (void)hipGetLastError();
       return 1;
@@ -1517,12 +1454,12 @@ static int cs_build_impl(dsgd_ctx* c, dsgd_plan* p) {
       }
     }
   }
-  CS_SOFT(hipMalloc(&p->d_cs_hdr, sizeof(CsHdr) * hdr.size()));
-  CS_SOFT(hipMalloc(&p->d_cs_meta, sizeof(unsigned int) * meta.size()));
-  CS_SOFT(hipMalloc(&p->d_cs_rf, sizeof(unsigned short) * rf.size()));
-  CS_SOFT(hipMalloc(&p->d_cs_col, sizeof(unsigned short) * col.size()));
-  CS_SOFT(hipMalloc(&p->d_cs_val, sizeof(float) * val.size()));
-  CS_SOFT(hipMalloc(&p->d_cs_cl, sizeof(unsigned short) * clist.size()));
+  CS_SOFT(dev_alloc((void**)&p->d_cs_hdr, sizeof(CsHdr) * hdr.size()));   // (outside the cache: cs_bytes stays 0, cs_free releases them)
+  CS_SOFT(dev_alloc((void**)&p->d_cs_meta, sizeof(unsigned int) * meta.size()));
+  CS_SOFT(dev_alloc((void**)&p->d_cs_rf, sizeof(unsigned short) * rf.size()));
+  CS_SOFT(dev_alloc((void**)&p->d_cs_col, sizeof(unsigned short) * col.size()));
+  CS_SOFT(dev_alloc((void**)&p->d_cs_val, sizeof(float) * val.size()));
+  CS_SOFT(dev_alloc((void**)&p->d_cs_cl, sizeof(unsigned short) * clist.size()));
   CS_SOFT(hipMemcpy(p->d_cs_cl, clist.data(), sizeof(unsigned short) * clist.size(), hipMemcpyHostToDevice));
   CS_SOFT(hipMemcpy(p->d_cs_hdr, hdr.data(), sizeof(CsHdr) * hdr.size(), hipMemcpyHostToDevice));
   CS_SOFT(hipMemcpy(p->d_cs_meta, meta.data(), sizeof(unsigned int) * meta.size(), hipMemcpyHostToDevice));
@@ -1559,9 +1496,9 @@ static int cs_ensure_sliced(dsgd_ctx* c, int G) {
   if (c->cs_w_G == G) return DSGD_OK;
   DSGD_TRY(cs_unslice(c));
   const int Sp = cs_sp(c->dp, G), n = G * Sp;
-  const size_t cap = sizeof(float) * (size_t)(c->dp + (CS_MAX_G + 1) * 8);
-  if (!c->d_cs_w) HIP_TRY(hipMalloc(&c->d_cs_w, cap));
-  if (!c->d_cs_ds) HIP_TRY(hipMalloc(&c->d_cs_ds, cap));
+  const size_t cap = (size_t)(c->dp + (CS_MAX_G + 1) * 8);
+  DSGD_TRY(c->d_cs_w.reserve(cap));
+  DSGD_TRY(c->d_cs_ds.reserve(cap));
   hipLaunchKernelGGL(dsgd_cs_slice_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_w, c->d_cs_w, c->dp, G, Sp);
   hipLaunchKernelGGL(dsgd_cs_slice_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_ds, c->d_cs_ds, c->dp, G, Sp);
   HIP_TRY(hipGetLastError());
@@ -1649,8 +1586,8 @@ static int launch_cs(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long 
 static int cs64_slice(dsgd_ctx* c) {
   if (c->cs_w_G == CS64_G) return DSGD_OK;
   const int Sp = cs64_sp(c->dp), n = CS64_G * Sp;
-  if (!c->d_cs_w64) HIP_TRY(hipMalloc(&c->d_cs_w64, sizeof(double) * (size_t)n));
-  if (!c->d_cs_ds64) HIP_TRY(hipMalloc(&c->d_cs_ds64, sizeof(double) * (size_t)n));
+  DSGD_TRY(c->d_cs_w64.reserve((size_t)n));
+  DSGD_TRY(c->d_cs_ds64.reserve((size_t)n));
   hipLaunchKernelGGL(dsgd_cs64_slice_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_w64, c->d_cs_w64, c->dp, Sp);
   hipLaunchKernelGGL(dsgd_cs64_slice_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_ds64, c->d_cs_ds64, c->dp, Sp);
   HIP_TRY(hipGetLastError());
@@ -1663,11 +1600,11 @@ static int launch_cs64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long lon
                        double* delta = nullptr) {
   const int Sp = cs64_sp(c->dp), n = CS64_G * Sp;
   if (!c->d_cs64_x) {
-    HIP_TRY(hipMalloc(&c->d_cs64_x, sizeof(unsigned long long) * 2 * CS64_G * CS64_XSTRIDE2));
+    DSGD_TRY(c->d_cs64_x.alloc((size_t)2 * CS64_G * CS64_XSTRIDE2));
     HIP_TRY(hipMemsetAsync(c->d_cs64_x, 0, sizeof(unsigned long long) * 2 * CS64_G * CS64_XSTRIDE2, c->stream));
   }
   if (!c->d_cs_sync) {
-    HIP_TRY(hipMalloc(&c->d_cs_sync, sizeof(unsigned int) * 2));
+    DSGD_TRY(c->d_cs_sync.alloc(2));
     HIP_TRY(hipMemsetAsync(c->d_cs_sync, 0, sizeof(unsigned int) * 2, c->stream));
   }
   DSGD_TRY(cs64_slice(c));   // they stay slice-major until something else binds
@@ -1744,19 +1681,13 @@ static int launch_cs_request(dsgd_ctx* c, int G, int K, long long worst_list, fl
   constexpr int SLOT_STRIDE = CS_MAX_SLOTS, ROW_STRIDE = CS_MAX_SLOTS + 64, CL_STRIDE = CS_MAX_CLT * CS_THREADS;
   if (L.G < G) {   // (grown once: 8 -> 16 slices)
     HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(L.hdr);
-    (void)hipFree(L.meta);
-    (void)hipFree(L.rf);
-    (void)hipFree(L.col);
-    (void)hipFree(L.val);
-    (void)hipFree(L.cl);
     L = dsgd_ctx::ReqLayout();
-    HIP_TRY(hipMalloc(&L.hdr, sizeof(CsHdr) * (size_t)G));
-    HIP_TRY(hipMalloc(&L.meta, sizeof(unsigned int) * (size_t)G * SLOT_STRIDE));
-    HIP_TRY(hipMalloc(&L.rf, sizeof(unsigned short) * (size_t)G * ROW_STRIDE));
-    HIP_TRY(hipMalloc(&L.col, sizeof(unsigned short) * (size_t)G * SLOT_STRIDE * CS_L));
-    HIP_TRY(hipMalloc(&L.val, sizeof(float) * (size_t)G * SLOT_STRIDE * CS_L));
-    HIP_TRY(hipMalloc(&L.cl, sizeof(unsigned short) * (size_t)G * CL_STRIDE));
+    DSGD_TRY(L.hdr.alloc((size_t)G));
+    DSGD_TRY(L.meta.alloc((size_t)G * SLOT_STRIDE));
+    DSGD_TRY(L.rf.alloc((size_t)G * ROW_STRIDE));
+    DSGD_TRY(L.col.alloc((size_t)G * SLOT_STRIDE * CS_L));
+    DSGD_TRY(L.val.alloc((size_t)G * SLOT_STRIDE * CS_L));
+    DSGD_TRY(L.cl.alloc((size_t)G * CL_STRIDE));
     L.G = G;
   }
   if (ensure_cs_exchange(c)) return fail(DSGD_ENOMEM, "out of device memory (column-slice exchange buffer)");
@@ -1766,8 +1697,8 @@ static int launch_cs_request(dsgd_ctx* c, int G, int K, long long worst_list, fl
   a.hdr = L.hdr;
   a.slot_meta = L.meta;
   a.row_first = L.rf;
-  a.col = reinterpret_cast<const uint4*>(L.col);
-  a.val = reinterpret_cast<const float4*>(L.val);
+  a.col = reinterpret_cast<const uint4*>(L.col.get());
+  a.val = reinterpret_cast<const float4*>(L.val.get());
   a.clist = L.cl;
   a.cl_stride = CL_STRIDE;
   cs_common_args(c, a, G, K, lr);
@@ -1776,7 +1707,7 @@ static int launch_cs_request(dsgd_ctx* c, int G, int K, long long worst_list, fl
   a.step_end = 1;
   a.slot_stride = SLOT_STRIDE;
   a.row_stride = ROW_STRIDE;
-  a.mail = c->d_mail;
+  a.mail = c->h_mail.dev();
   a.mail_seq = ++c->mail_seq;
   CsBuildArgs ba{};
   ba.m = view(c);
@@ -1834,7 +1765,7 @@ static int finish_pre(dsgd_ctx* c, int n_workers, float lr, bool mail) {
     hipLaunchKernelGGL(dsgd_fix_reduce_apply_kernel<true>, dim3(cblocks), dim3(1024), 0, c->stream, c->d_g64, (long long)dp,
                        n_workers, c->d_w, c->d_ds, dp, f.hg, c->d_part, c->part_stride, f.n_wg, f.hc, f.nc, c->d_partc, c->partc_stride, f.n_wgc,
                        f.inv_scale, f.inv_scale_cold, lr, (float)c->cfg.lambda, c->d_sc, red_out(c), (float*)nullptr,
-                       (const float*)red_cur(c), c->s_lazy ? 1 : 0, mail ? c->d_mail : (unsigned long long*)nullptr);
+                       (const float*)red_cur(c), c->s_lazy ? 1 : 0, mail ? c->h_mail.dev() : (unsigned long long*)nullptr);
     HIP_TRY(hipGetLastError());
     c->red_par ^= 1;
     c->s_lazy = true;   // the new pairs stay in d_redpart: the next step adds them itself, anyone else asks ensure_s
@@ -2011,23 +1942,20 @@ static void build_wave_tiles(const long long* row_ptr, long long n_rows, const s
   }
 }
 static int upload_wave_tiles(dsgd_ctx* c, HostTiles& ht) {
-  (void)hipFree(c->d_wtiles);
-  (void)hipFree(c->d_wmeta);
-  (void)hipFree(c->d_wlong_rows);
-  c->d_wtiles = nullptr;
-  c->d_wmeta = nullptr;
-  c->d_wlong_rows = nullptr;
+  c->d_wtiles.reset();
+  c->d_wmeta.reset();
+  c->d_wlong_rows.reset();
   c->n_wtiles = (long long)ht.r0.size() - 1;
   c->h_wtile_r0.swap(ht.r0);
-  HIP_TRY(hipMalloc(&c->d_wtiles, sizeof(WTile) * ht.wt.size()));
+  DSGD_TRY(c->d_wtiles.alloc(ht.wt.size()));
   const size_t meta_bytes = sizeof(unsigned short) * ht.meta16.size();
-  HIP_TRY(hipMalloc(&c->d_wmeta, meta_bytes));
+  DSGD_TRY(c->d_wmeta.alloc(ht.meta16.size()));
   HIP_TRY(hipMemcpy(c->d_wtiles, ht.wt.data(), sizeof(WTile) * ht.wt.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->d_wmeta, ht.meta16.data(), meta_bytes, hipMemcpyHostToDevice));
   c->bound_segs.clear();
   std::vector<int> lr(c->wlong_rows.begin(), c->wlong_rows.end());
   lr.push_back(0);
-  HIP_TRY(hipMalloc(&c->d_wlong_rows, sizeof(int) * lr.size()));
+  DSGD_TRY(c->d_wlong_rows.alloc(lr.size()));
   HIP_TRY(hipMemcpy(c->d_wlong_rows, lr.data(), sizeof(int) * lr.size(), hipMemcpyHostToDevice));
   c->ssegs_last.clear();
   return DSGD_OK;
@@ -2040,21 +1968,18 @@ static void tcol_drop_all(dsgd_ctx* c);
 static int build_split(dsgd_ctx* c) {
   fstep_drop_all(c);
   tcol_drop_all(c);   // (the chunked tile tables index the streams built here; the column lists are sorted by the ranks about to change)
-  (void)hipFree(c->d_hcol); (void)hipFree(c->d_hval); (void)hipFree(c->d_hrow_ptr);
-  (void)hipFree(c->d_ccol); (void)hipFree(c->d_cval); (void)hipFree(c->d_ctp); (void)hipFree(c->d_ctiles); (void)hipFree(c->d_cmeta);
-  (void)hipFree(c->d_dcold); (void)hipFree(c->d_coef8);
-  c->d_hcol = nullptr; c->d_hval = nullptr; c->d_hrow_ptr = nullptr;
-  c->d_ccol = nullptr; c->d_cval = nullptr; c->d_ctp = nullptr; c->d_ctiles = nullptr; c->d_cmeta = nullptr;
-  c->d_dcold = nullptr; c->d_coef8 = nullptr;
+  c->d_hcol.reset(), c->d_hval.reset(), c->d_hrow_ptr.reset();
+  c->d_ccol.reset(), c->d_cval.reset(), c->d_ctp.reset(), c->d_ctiles.reset(), c->d_cmeta.reset();
+  c->d_dcold.reset(), c->d_coef8.reset();
   const long long n_rows = c->n_rows;
   const int H = std::min(c->hsplit, c->dp);
-  HIP_TRY(hipMalloc(&c->d_coef8, (size_t)std::max<long long>(n_rows, 1)));
+  DSGD_TRY(c->d_coef8.alloc((size_t)std::max<long long>(n_rows, 1)));
   HIP_TRY(hipMemset(c->d_coef8, 0, (size_t)std::max<long long>(n_rows, 1)));
-  HIP_TRY(hipMalloc(&c->d_dcold, sizeof(float) * (size_t)std::max<long long>(n_rows, 1)));
+  DSGD_TRY(c->d_dcold.alloc((size_t)std::max<long long>(n_rows, 1)));
   HIP_TRY(hipMemset(c->d_dcold, 0, sizeof(float) * (size_t)std::max<long long>(n_rows, 1)));
   // cold entries per row
-  int* d_cnt = nullptr;
-  HIP_TRY(hipMalloc(&d_cnt, sizeof(int) * (size_t)std::max<long long>(n_rows, 1)));
+  DevBuf<int> d_cnt;
+  DSGD_TRY(d_cnt.alloc((size_t)std::max<long long>(n_rows, 1)));
   CsrView m = view(c);
   {
     const int blocks = (int)std::max<long long>(1, std::min<long long>((n_rows + 15) / 16, (long long)c->n_cu * 16));
@@ -2064,7 +1989,7 @@ static int build_split(dsgd_ctx* c) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * (size_t)n_rows, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_cnt);
+  d_cnt.reset();
   if (e != hipSuccess) return fail(DSGD_EHIP, "split counts: %s", hipGetErrorString(e));
   // hrp / ctp: slot offsets of the two streams (a tiled row owns at least one slot in each: an explicit zero when it
   // has no entry there); crp: the cold ENTRIES before each row (what dsgd_range_nnz reports)
@@ -2101,20 +2026,20 @@ static int build_split(dsgd_ctx* c) {
   }
   c->hot_nnz = hrp[n_rows];
   c->coldm_nnz = ctp[n_rows];
-  HIP_TRY(hipMalloc(&c->d_hcol, sizeof(unsigned short) * (size_t)(c->hot_nnz + WS_PAD)));
-  HIP_TRY(hipMalloc(&c->d_hval, sizeof(float) * (size_t)(c->hot_nnz + WS_PAD)));
+  DSGD_TRY(c->d_hcol.alloc((size_t)(c->hot_nnz + WS_PAD)));
+  DSGD_TRY(c->d_hval.alloc((size_t)(c->hot_nnz + WS_PAD)));
   HIP_TRY(hipMemset(c->d_hcol + c->hot_nnz, 0, sizeof(unsigned short) * WS_PAD));
   HIP_TRY(hipMemset(c->d_hval + c->hot_nnz, 0, sizeof(float) * WS_PAD));
-  HIP_TRY(hipMalloc(&c->d_hrow_ptr, sizeof(long long) * hrp.size()));
+  DSGD_TRY(c->d_hrow_ptr.alloc(hrp.size()));
   HIP_TRY(hipMemcpy(c->d_hrow_ptr, hrp.data(), sizeof(long long) * hrp.size(), hipMemcpyHostToDevice));
   // 16-bit cold ids whenever there are at most 65536 cold columns (DSGD_COLD_UNPACKED=1 forces the 32-bit form: tests)
   c->cold_col16 = c->dp - H <= 65536 && !getenv("DSGD_COLD_UNPACKED");
   const size_t csz = c->cold_col16 ? sizeof(unsigned short) : sizeof(unsigned int);
-  HIP_TRY(hipMalloc(&c->d_ccol, csz * (size_t)(c->coldm_nnz + WS_PAD)));
-  HIP_TRY(hipMalloc(&c->d_cval, sizeof(float) * (size_t)(c->coldm_nnz + WS_PAD)));
-  HIP_TRY(hipMemset((char*)c->d_ccol + csz * (size_t)c->coldm_nnz, 0, csz * WS_PAD));
+  DSGD_TRY(c->d_ccol.alloc(csz * (size_t)(c->coldm_nnz + WS_PAD)));
+  DSGD_TRY(c->d_cval.alloc((size_t)(c->coldm_nnz + WS_PAD)));
+  HIP_TRY(hipMemset((char*)c->d_ccol.get() + csz * (size_t)c->coldm_nnz, 0, csz * WS_PAD));
   HIP_TRY(hipMemset(c->d_cval + c->coldm_nnz, 0, sizeof(float) * WS_PAD));
-  HIP_TRY(hipMalloc(&c->d_ctp, sizeof(long long) * ctp.size()));
+  DSGD_TRY(c->d_ctp.alloc(ctp.size()));
   HIP_TRY(hipMemcpy(c->d_ctp, ctp.data(), sizeof(long long) * ctp.size(), hipMemcpyHostToDevice));
   {
     const int blocks = (int)std::max<long long>(1, std::min<long long>((n_rows + 3) / 4, (long long)c->n_cu * 16));
@@ -2139,8 +2064,8 @@ static int build_split(dsgd_ctx* c) {
   build_wave_tiles(ctp.data(), n_rows, c->h_label.data(), hc, CT_MAXROWS);
   c->n_ctiles = (long long)hc.r0.size() - 1;
   c->h_ctile_r0.swap(hc.r0);
-  HIP_TRY(hipMalloc(&c->d_ctiles, sizeof(WTile) * hc.wt.size()));
-  HIP_TRY(hipMalloc(&c->d_cmeta, sizeof(unsigned short) * hc.meta16.size()));
+  DSGD_TRY(c->d_ctiles.alloc(hc.wt.size()));
+  DSGD_TRY(c->d_cmeta.alloc(hc.meta16.size()));
   HIP_TRY(hipMemcpy(c->d_ctiles, hc.wt.data(), sizeof(WTile) * hc.wt.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->d_cmeta, hc.meta16.data(), sizeof(unsigned short) * hc.meta16.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2152,18 +2077,13 @@ static int build_split(dsgd_ctx* c) {
 // Runs once, lazily, at the first compute call after dsgd_load_csr.
 // (in three parts -- the counts, their all-reduce, the ranking and the split -- so that one host thread can prepare several
 //  contexts: dsgd_build_dim_sparsity_devices)
-static int layout_begin(dsgd_ctx* c, unsigned int** d_cnt_out) {
-  *d_cnt_out = nullptr;
+static int layout_begin(dsgd_ctx* c, DevBuf<unsigned int>& d_cnt) {   // (d_cnt stays empty when there is nothing to do)
+  d_cnt.reset();
   if (c->layout_ready) return DSGD_OK;
-  unsigned int* d_cnt = nullptr;
-  HIP_TRY(hipMalloc(&d_cnt, sizeof(unsigned int) * c->dp));
+  DSGD_TRY(d_cnt.alloc((size_t)c->dp));
   const int rc = count_columns(c, c->nnz, d_cnt);
-  if (rc) {
-    (void)hipFree(d_cnt);
-    return rc;
-  }
-  *d_cnt_out = d_cnt;
-  return DSGD_OK;
+  if (rc) d_cnt.reset();
+  return rc;
 }
 static int layout_collective(dsgd_ctx* c, unsigned int* d_cnt) {
   if (!d_cnt || !c->comm) return DSGD_OK;
@@ -2171,7 +2091,7 @@ static int layout_collective(dsgd_ctx* c, unsigned int* d_cnt) {
   if (r) return fail(DSGD_ERCCL, "ncclAllReduce(column counts): %s", rccl::GetErrorString(r));
   return DSGD_OK;
 }
-static int layout_finish(dsgd_ctx* c, unsigned int* d_cnt) {   // (takes ownership of d_cnt)
+static int layout_finish(dsgd_ctx* c, DevBuf<unsigned int>& d_cnt) {   // (releases d_cnt)
   if (!d_cnt) return DSGD_OK;
   std::vector<unsigned int> cnt(c->dp);
   int rc = DSGD_OK;
@@ -2180,7 +2100,7 @@ static int layout_finish(dsgd_ctx* c, unsigned int* d_cnt) {   // (takes ownersh
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) rc = fail(DSGD_EHIP, "column counts: %s", hipGetErrorString(e));
   }
-  (void)hipFree(d_cnt);
+  d_cnt.reset();
   DSGD_TRY(rc);
   std::vector<int> order(c->dp);
   for (int j = 0; j < c->dp; ++j) order[j] = j;
@@ -2212,14 +2132,14 @@ static int vexp_collective(dsgd_ctx* c) {
   if (!c->comm || !c->fp64) return DSGD_OK;
   std::vector<long long> v((size_t)c->world, 0);
   v[(size_t)c->rank] = c->vexp;
-  long long* d_v = nullptr;
-  HIP_TRY(hipMalloc(&d_v, sizeof(long long) * v.size()));
+  DevBuf<long long> d_v;
+  DSGD_TRY(d_v.alloc(v.size()));
   hipError_t e = hipMemcpyAsync(d_v, v.data(), sizeof(long long) * v.size(), hipMemcpyHostToDevice, c->stream);
   int r = 0;
   if (e == hipSuccess) r = rccl::AllReduce(d_v, d_v, v.size(), rccl::kInt64, rccl::kSum, c->comm, c->stream);
   if (e == hipSuccess && !r) e = hipMemcpyAsync(v.data(), d_v, sizeof(long long) * v.size(), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess && !r) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_v);
+  d_v.reset();
   if (r) return fail(DSGD_ERCCL, "ncclAllReduce(vexp): %s", rccl::GetErrorString(r));
   if (e != hipSuccess) return fail(DSGD_EHIP, "vexp: %s", hipGetErrorString(e));
   c->vexp = (int)*std::max_element(v.begin(), v.end());
@@ -2228,14 +2148,11 @@ static int vexp_collective(dsgd_ctx* c) {
 }
 static int prepare_layout(dsgd_ctx* c) {
   if (c->layout_ready) return DSGD_OK;
-  unsigned int* d_cnt = nullptr;
-  DSGD_TRY(layout_begin(c, &d_cnt));
+  DevBuf<unsigned int> d_cnt;
+  DSGD_TRY(layout_begin(c, d_cnt));
   int rc = layout_collective(c, d_cnt);
   if (!rc) rc = vexp_collective(c);
-  if (rc) {
-    (void)hipFree(d_cnt);
-    return rc;
-  }
+  if (rc) return rc;
   return layout_finish(c, d_cnt);
 }
 // back to the identity layout (before new data is loaded): resident vectors return to key order
@@ -2257,13 +2174,10 @@ static int reset_layout(dsgd_ctx* c) {
 // ---- nnz-streaming launches (contiguous row ranges) ----------------------------------------------------
 static int upload_ssegs(dsgd_ctx* c, const std::vector<StreamSeg>& segs) {
   const int n = (int)segs.size();
-  if (n > c->ssegs_cap) {
+  if ((size_t)n > c->d_ssegs.cap()) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_ssegs);
-    c->d_ssegs = nullptr;
-    HIP_TRY(hipMalloc(&c->d_ssegs, sizeof(StreamSeg) * (size_t)n));
-    c->ssegs_cap = n;
     c->ssegs_last.clear();
+    DSGD_TRY(c->d_ssegs.reserve((size_t)n));
   }
   if ((int)c->ssegs_last.size() == n && memcmp(c->ssegs_last.data(), segs.data(), sizeof(StreamSeg) * n) == 0) return DSGD_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2312,15 +2226,12 @@ static void locate_segs(dsgd_ctx* c, std::vector<StreamSeg>& segs, long long* ma
     if (max_ctiles) *max_ctiles = std::max(*max_ctiles, s.ctile_end - s.ctile_begin);
   }
 }
-static int ensure_part(dsgd_ctx* c, int** buf, long long* wgs, int* stride, long long need_wgs, int need_cols) {
+static int ensure_part(dsgd_ctx* c, DevBuf<int>& buf, long long* wgs, int* stride, long long need_wgs, int need_cols) {
   if (need_wgs <= *wgs && need_cols <= *stride) return DSGD_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  (void)hipFree(*buf);
-  *buf = nullptr;
   *wgs = std::max<long long>(need_wgs, c->n_cu);
   *stride = std::max(*stride, (need_cols + 63) / 64 * 64);
-  HIP_TRY(hipMalloc(buf, sizeof(int) * (size_t)*wgs * (size_t)*stride));
-  return DSGD_OK;
+  return buf.alloc((size_t)*wgs * (size_t)*stride);
 }
 
 // whole row ranges: hot stream in wave tiles, cold stream before (x.w) and after (gradient) it
@@ -2364,8 +2275,8 @@ static int launch_stream(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs) {
   const int hw = H, hg = SCATTER ? H : 0;
   const size_t lds = sizeof(float) * (size_t)(16 * WS_COEF_STRIDE + hw + hg + (SCATTER ? 64 : 0) + 4);
   if (SCATTER) {
-    DSGD_TRY(ensure_part(c, &c->d_part, &c->part_wgs, &c->part_stride, (long long)grid.x * grid.y, hg));
-    if (cold) DSGD_TRY(ensure_part(c, &c->d_partc, &c->partc_wgs, &c->partc_stride, (long long)gridc.x * gridc.y, nc_lds));
+    DSGD_TRY(ensure_part(c, c->d_part, &c->part_wgs, &c->part_stride, (long long)grid.x * grid.y, hg));
+    if (cold) DSGD_TRY(ensure_part(c, c->d_partc, &c->partc_wgs, &c->partc_stride, (long long)gridc.x * gridc.y, nc_lds));
   }
   // Fixed-point scale of THIS launch: a column receives at most one contribution per row, |contribution| <= 2^shift,
   // and workgroup b of a worker owns the 16-tile groups b, b + grid.x, ... of its tile range (plus its share of the
@@ -2396,7 +2307,7 @@ static int launch_stream(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs) {
       const bool hit = c->bound_grid == grid.x && c->bound_segs.size() == segs.size() &&
                        memcmp(c->bound_segs.data(), segs.data(), sizeof(StreamSeg) * segs.size()) == 0;
       if (!hit) {
-        if (!c->d_bound) HIP_TRY(hipMalloc(&c->d_bound, sizeof(unsigned int)));
+        DSGD_TRY(c->d_bound.reserve(1));
         HIP_TRY(hipMemsetAsync(c->d_bound, 0, sizeof(unsigned int), c->stream));
         hipLaunchKernelGGL(dsgd_wseg_bound_kernel, grid, dim3(1024), sizeof(unsigned int) * (size_t)(hg + 16), c->stream,
                            c->d_hrow_ptr, c->d_hcol, c->d_hval, c->d_wtiles, c->n_wtiles, c->n_rows, view(c),
@@ -2419,7 +2330,7 @@ static int launch_stream(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs) {
   }
   CsrView mh = view(c);
   mh.row_ptr = c->d_hrow_ptr;
-  mh.col = reinterpret_cast<const int*>(c->d_hcol);   // 16-bit ranks; the kernel reinterprets the pointer
+  mh.col = reinterpret_cast<const int*>(c->d_hcol.get());   // 16-bit ranks; the kernel reinterprets the pointer
   mh.val = c->d_hval;
   CsrView mf = view(c);
   size_t slot = 0;
@@ -2448,21 +2359,9 @@ static int launch_stream(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs) {
 }
 
 // ---- row chunks: the whole gradient of a row range in one launch (csrc/dsgd_fstep.hpp) -------------------------------
-static void fstep_free(dsgd_ctx::FstepLayout& L) {
-  (void)hipFree(L.d_times);
-  if (L.h_times) (void)hipHostFree(L.h_times);
-  if (L.times_ev) (void)hipEventDestroy(L.times_ev);
-  (void)hipFree(L.d_tiles);
-  (void)hipFree(L.d_meta);
-  (void)hipFree(L.d_ctiles);
-  (void)hipFree(L.d_cmeta);
-  (void)hipFree(L.d_chunks);
-  L = dsgd_ctx::FstepLayout();
-}
 static void fstep_drop_all(dsgd_ctx* c) {   // (the split streams are about to change, or the context goes away)
   if (c->fstep_cache.empty()) return;
   (void)hipStreamSynchronize(c->stream);
-  for (dsgd_ctx::FstepLayout& L : c->fstep_cache) fstep_free(L);
   c->fstep_cache.clear();
 }
 // can the chunked launch serve this context's layout at all?  (16-bit cold ids, every cold column inside the LDS tile)
@@ -2490,7 +2389,6 @@ static int fstep_layout(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
     for (size_t i = 1; i < c->fstep_cache.size(); ++i)
       if (c->fstep_cache[i].used < c->fstep_cache[v].used) v = i;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    fstep_free(c->fstep_cache[v]);
     c->fstep_cache.erase(c->fstep_cache.begin() + (long)v);
   }
   dsgd_ctx::FstepLayout L;
@@ -2498,7 +2396,7 @@ static int fstep_layout(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
   L.n_wg = n_wg;
   DSGD_TRY(fstep_build(c, row_segs, n_wg, L));
   L.used = ++c->fstep_clock;
-  c->fstep_cache.push_back(L);
+  c->fstep_cache.push_back(std::move(L));
   *out = &c->fstep_cache.back();
   return DSGD_OK;
 }
@@ -2589,36 +2487,27 @@ static int fstep_build(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int 
   if (ct.empty()) ct.push_back(pad);
   L.worst_rows = worst;
   L.shift = -1;
-  (void)hipFree(L.d_tiles);
-  (void)hipFree(L.d_meta);
-  (void)hipFree(L.d_ctiles);
-  (void)hipFree(L.d_cmeta);
-  (void)hipFree(L.d_chunks);
-  L.d_tiles = nullptr;
-  L.d_meta = nullptr;
-  L.d_ctiles = nullptr;
-  L.d_cmeta = nullptr;
-  L.d_chunks = nullptr;
-  hipError_t e = hipMalloc(&L.d_tiles, sizeof(WTile) * wt.size());
-  if (e == hipSuccess) e = hipMalloc(&L.d_meta, sizeof(unsigned short) * meta.size());
-  if (e == hipSuccess) e = hipMalloc(&L.d_ctiles, sizeof(WTile) * ct.size());
-  if (e == hipSuccess) e = hipMalloc(&L.d_cmeta, sizeof(unsigned short) * cmeta.size());
-  if (e == hipSuccess) e = hipMalloc(&L.d_chunks, sizeof(FChunk) * chunks.size());
+  // (alloc drops the tables of the cut before)
+  hipError_t e = L.d_tiles.try_alloc(wt.size());
+  if (e == hipSuccess) e = L.d_meta.try_alloc(meta.size());
+  if (e == hipSuccess) e = L.d_ctiles.try_alloc(ct.size());
+  if (e == hipSuccess) e = L.d_cmeta.try_alloc(cmeta.size());
+  if (e == hipSuccess) e = L.d_chunks.try_alloc(chunks.size());
   if (e == hipSuccess) e = hipMemcpy(L.d_tiles, wt.data(), sizeof(WTile) * wt.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(L.d_meta, meta.data(), sizeof(unsigned short) * meta.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(L.d_ctiles, ct.data(), sizeof(WTile) * ct.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(L.d_cmeta, cmeta.data(), sizeof(unsigned short) * cmeta.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(L.d_chunks, chunks.data(), sizeof(FChunk) * chunks.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess && !L.d_times) {
-    e = hipMalloc(&L.d_times, sizeof(unsigned long long) * chunks.size());
-    if (e == hipSuccess) e = hipHostMalloc(&L.h_times, sizeof(unsigned long long) * chunks.size(), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&L.times_ev, hipEventDisableTiming);
+    e = L.d_times.try_alloc(chunks.size());
+    if (e == hipSuccess) e = L.h_times.try_alloc(chunks.size());
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&L.times_ev.e, hipEventDisableTiming);
   }
   if (e == hipSuccess) e = hipMemset(L.d_times, 0, sizeof(unsigned long long) * chunks.size());
   L.launches = 0;
   L.times_pending = false;
   if (e != hipSuccess) {
-    fstep_free(L);
+    L = dsgd_ctx::FstepLayout();
     return fail(DSGD_EHIP, "row-chunk layout: %s", hipGetErrorString(e));
   }
   return DSGD_OK;
@@ -2690,8 +2579,8 @@ static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
   const int H = std::min(c->hsplit, c->dp);
   const int nc = c->dp - H;   // (fstep_possible: all of them inside the LDS tile)
   dim3 grid((unsigned)n_wg, (unsigned)n_workers);
-  DSGD_TRY(ensure_part(c, &c->d_part, &c->part_wgs, &c->part_stride, (long long)n_wg * n_workers, H));
-  DSGD_TRY(ensure_part(c, &c->d_partc, &c->partc_wgs, &c->partc_stride, (long long)n_wg * n_workers, nc));
+  DSGD_TRY(ensure_part(c, c->d_part, &c->part_wgs, &c->part_stride, (long long)n_wg * n_workers, H));
+  DSGD_TRY(ensure_part(c, c->d_partc, &c->partc_wgs, &c->partc_stride, (long long)n_wg * n_workers, nc));
   // LDS: the largest of the three phases' tiles
   const size_t lds_a = sizeof(float) * (size_t)(((nc + 3) & ~3) + 16 * CT_STRIP);
   const size_t lds_b = sizeof(float) * (size_t)(16 * WS_COEF_STRIDE + 2 * H + 64 + 4 + 4);   // (+ 4: the hot tiles' counter)
@@ -2705,7 +2594,7 @@ static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
   int shift = shift0;
   if (c->fix_bound && shift0 < c->max_shift) {
     if (L->shift < 0) {
-      if (!c->d_bound) HIP_TRY(hipMalloc(&c->d_bound, sizeof(unsigned int)));
+      DSGD_TRY(c->d_bound.reserve(1));
       HIP_TRY(hipMemsetAsync(c->d_bound, 0, sizeof(unsigned int), c->stream));
       hipLaunchKernelGGL(dsgd_fstep_bound_kernel, grid, dim3(1024), sizeof(unsigned int) * (size_t)(H + 16), c->stream, c->d_hrow_ptr,
                          c->d_hcol, c->d_hval, L->d_chunks, view(c), c->d_wlong_rows, H, std::ldexp(1.0f, shift0 - c->vexp), c->d_bound);
@@ -2724,7 +2613,7 @@ static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
   c->last_shift = shift;
   CsrView mh = view(c);
   mh.row_ptr = c->d_hrow_ptr;
-  mh.col = reinterpret_cast<const int*>(c->d_hcol);   // 16-bit ranks; the kernel reinterprets the pointer
+  mh.col = reinterpret_cast<const int*>(c->d_hcol.get());   // 16-bit ranks; the kernel reinterprets the pointer
   mh.val = c->d_hval;
   size_t slot = 0;
   DSGD_TRY(prof_begin(c, &slot));
@@ -2743,19 +2632,9 @@ static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
 }
 
 // ---- column lists: whole-split steps of 10^3 .. 10^5 rows (csrc/dsgd_tcol.hpp) ----------------------------------------
-static void tcol_free(dsgd_ctx::TcolLayout& L) {
-  (void)hipFree(L.d_ent_pk);
-  (void)hipFree(L.d_ent_val);
-  (void)hipFree(L.d_shares);
-  (void)hipFree(L.d_key_of_cid);
-  (void)hipFree(L.d_bit_base);
-  (void)hipFree(L.d_bitmap);
-  L = dsgd_ctx::TcolLayout();
-}
 static void tcol_drop_all(dsgd_ctx* c) {   // (the ranked CSR is about to change, or the context goes away)
   if (c->tcol_cache.empty()) return;
   (void)hipStreamSynchronize(c->stream);
-  for (dsgd_ctx::TcolLayout& L : c->tcol_cache) tcol_free(L);
   c->tcol_cache.clear();
 }
 static bool tcol_wanted(const dsgd_ctx* c, long long tot, int n_workers) {
@@ -2796,7 +2675,6 @@ static int tcol_layout(dsgd_ctx* c, const std::vector<WorkSeg>& segs, long long 
   for (size_t i = 0; i < c->tcol_cache.size();)   // layouts of an earlier ranking
     if (c->tcol_cache[i].gen != c->layout_gen) {
       HIP_TRY(hipStreamSynchronize(c->stream));
-      tcol_free(c->tcol_cache[i]);
       c->tcol_cache.erase(c->tcol_cache.begin() + (long)i);
     } else {
       ++i;
@@ -2806,28 +2684,22 @@ static int tcol_layout(dsgd_ctx* c, const std::vector<WorkSeg>& segs, long long 
     for (size_t i = 1; i < c->tcol_cache.size(); ++i)
       if (c->tcol_cache[i].used < c->tcol_cache[v].used) v = i;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    tcol_free(c->tcol_cache[v]);
     c->tcol_cache.erase(c->tcol_cache.begin() + (long)v);
   }
   const int n_keys = n_workers * c->dp;
-  unsigned int *d_cnt = nullptr, *d_ptr = nullptr, *d_cursor = nullptr;
-  int* d_cid = nullptr;
-  unsigned long long* d_tot = nullptr;
+  DevBuf<unsigned int> d_cnt, d_ptr, d_cursor;   // (the builder's scratch: released on return, the stream idle by then)
+  DevBuf<int> d_cid;
+  DevBuf<unsigned long long> d_tot;
   dsgd_ctx::TcolLayout L;
   auto give_up = [&](int rc) {
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d_cnt);
-    (void)hipFree(d_ptr);
-    (void)hipFree(d_cursor);
-    (void)hipFree(d_cid);
-    (void)hipFree(d_tot);
-    tcol_free(L);
+    L = dsgd_ctx::TcolLayout();
     if (rc == 2) return 1;   // out of memory / a failed call: declined for THIS step only (memory may be there the next time)
     if (rc == 1) {   // remembered as declined (n_wg = 0): the caller's other path takes this configuration from now on
       L.ranges = key;
       L.gen = c->layout_gen;
       L.used = ++c->tcol_clock;
-      c->tcol_cache.push_back(L);
+      c->tcol_cache.push_back(std::move(L));
     }
     return rc;
   };
@@ -2847,13 +2719,13 @@ static int tcol_layout(dsgd_ctx* c, const std::vector<WorkSeg>& segs, long long 
   }
   if (bits > TC_MAX_BITS) return give_up(1);
   L.bm_words = (int)(((bits >> 5) + 3) & ~3LL);
-  TC_SOFT(hipMalloc(&d_cnt, sizeof(unsigned int) * (size_t)n_keys));
-  TC_SOFT(hipMalloc(&d_ptr, sizeof(unsigned int) * ((size_t)n_keys + 1)));
-  TC_SOFT(hipMalloc(&d_cursor, sizeof(unsigned int) * (size_t)n_keys));
-  TC_SOFT(hipMalloc(&d_cid, sizeof(int) * (size_t)n_keys));
-  TC_SOFT(hipMalloc(&d_tot, sizeof(unsigned long long) * 2));
-  TC_SOFT(hipMalloc(&L.d_bit_base, sizeof(int) * (size_t)n_workers));
-  TC_SOFT(hipMalloc(&L.d_bitmap, sizeof(unsigned int) * (size_t)L.bm_words));
+  TC_SOFT(d_cnt.try_alloc((size_t)n_keys));
+  TC_SOFT(d_ptr.try_alloc((size_t)n_keys + 1));
+  TC_SOFT(d_cursor.try_alloc((size_t)n_keys));
+  TC_SOFT(d_cid.try_alloc((size_t)n_keys));
+  TC_SOFT(d_tot.try_alloc(2));
+  TC_SOFT(L.d_bit_base.try_alloc((size_t)n_workers));
+  TC_SOFT(L.d_bitmap.try_alloc((size_t)L.bm_words));
   TC_SOFT(hipMemcpyAsync(L.d_bit_base, bit_base.data(), sizeof(int) * (size_t)n_workers, hipMemcpyHostToDevice, c->stream));
   TC_SOFT(hipMemsetAsync(L.d_bitmap, 0, sizeof(unsigned int) * (size_t)L.bm_words, c->stream));
   TC_SOFT(hipMemsetAsync(d_cnt, 0, sizeof(unsigned int) * (size_t)n_keys, c->stream));
@@ -2875,13 +2747,13 @@ static int tcol_layout(dsgd_ctx* c, const std::vector<WorkSeg>& segs, long long 
   L.n_wg = (int)((L.n_ent + share - 1) / share);
   {   // whole 16-byte pieces; the last one's padding is zero
     const size_t n_pad = ((size_t)L.n_ent + 3) & ~(size_t)3;
-    TC_SOFT(hipMalloc(&L.d_ent_pk, sizeof(unsigned int) * n_pad));
-    TC_SOFT(hipMalloc(&L.d_ent_val, sizeof(float) * n_pad));
+    TC_SOFT(L.d_ent_pk.try_alloc(n_pad));
+    TC_SOFT(L.d_ent_val.try_alloc(n_pad));
     TC_SOFT(hipMemsetAsync(L.d_ent_pk + (n_pad - 4), 0, sizeof(unsigned int) * 4, c->stream));
     TC_SOFT(hipMemsetAsync(L.d_ent_val + (n_pad - 4), 0, sizeof(float) * 4, c->stream));
   }
-  TC_SOFT(hipMalloc(&L.d_shares, sizeof(TcShare) * (size_t)L.n_wg));
-  TC_SOFT(hipMalloc(&L.d_key_of_cid, sizeof(int) * (size_t)std::max<unsigned long long>(1, tot[1])));
+  TC_SOFT(L.d_shares.try_alloc((size_t)L.n_wg));
+  TC_SOFT(L.d_key_of_cid.try_alloc((size_t)std::max<unsigned long long>(1, tot[1])));
   hipLaunchKernelGGL(dsgd_tc_shares_kernel, dim3((unsigned)((L.n_wg + 255) / 256)), dim3(256), 0, c->stream, d_ptr, d_cid, n_keys, L.n_ent,
                      L.share, L.n_wg, L.d_shares);
   hipLaunchKernelGGL(dsgd_tc_fill_kernel, grid, dim3(TC_THREADS), 0, c->stream, view(c), c->d_segs, c->dp, d_cursor, d_cid, L.d_shares, L.share,
@@ -2889,13 +2761,8 @@ static int tcol_layout(dsgd_ctx* c, const std::vector<WorkSeg>& segs, long long 
   TC_SOFT(hipGetLastError());
   TC_SOFT(hipStreamSynchronize(c->stream));
 #undef TC_SOFT
-  (void)hipFree(d_cnt);
-  (void)hipFree(d_ptr);
-  (void)hipFree(d_cursor);
-  (void)hipFree(d_cid);
-  (void)hipFree(d_tot);
   L.used = ++c->tcol_clock;
-  c->tcol_cache.push_back(L);
+  c->tcol_cache.push_back(std::move(L));
   *out = &c->tcol_cache.back();
   return DSGD_OK;
 }
@@ -2970,7 +2837,7 @@ static int launch_plan_kernel(dsgd_ctx* c, const int* d_idx, const WorkSeg* d_se
                               long long step_end, float lr, bool mail = false) {
   if (!c->d_plan_gcold) {
     const size_t strip = (size_t)std::max(1, c->dp - plan_hl(c->dp));
-    HIP_TRY(hipMalloc(&c->d_plan_gcold, sizeof(float) * strip));
+    DSGD_TRY(c->d_plan_gcold.alloc(strip));
     HIP_TRY(hipMemsetAsync(c->d_plan_gcold, 0, sizeof(float) * strip, c->stream));
   }
   PlanArgs a;
@@ -2986,7 +2853,7 @@ static int launch_plan_kernel(dsgd_ctx* c, const int* d_idx, const WorkSeg* d_se
   a.lr = lr;
   a.lambda = (float)c->cfg.lambda;
   a.tprof = c->d_tprof;
-  a.mail = mail ? c->d_mail : nullptr;
+  a.mail = mail ? c->h_mail.dev() : nullptr;
   a.mail_seq = mail ? ++c->mail_seq : 0ull;
   a.vexp = c->vexp;
   a.dp = c->dp;
@@ -3056,16 +2923,12 @@ static int sp_reset_state(dsgd_ctx* c) {
 }
 static int sp_ensure(dsgd_ctx* c) {
   if (c->h_sp_out) return DSGD_OK;
-  void* h = nullptr;
-  HIP_TRY(hipHostMalloc(&h, sp_vals_off(c) + sizeof(double) * (size_t)c->dp, hipHostMallocMapped));
-  void* d = nullptr;
-  if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess || hipMalloc(&c->d_sp_state, sizeof(unsigned long long) * (size_t)(SP_STATE_HEAD + sp_tiles(c))) != hipSuccess) {
-    (void)hipHostFree(h);
-    c->d_sp_state = nullptr;
+  const size_t words = (sp_vals_off(c) + sizeof(double) * (size_t)c->dp + 7) / 8;
+  DSGD_TRY(c->h_sp_out.alloc(words, hipHostMallocMapped));
+  if (c->d_sp_state.try_alloc((size_t)(SP_STATE_HEAD + sp_tiles(c))) != hipSuccess) {
+    c->h_sp_out.reset();   // (neither without the other: sp_ensure starts from h_sp_out)
     return fail(DSGD_ENOMEM, "out of memory (the sparse boundary's buffers)");
   }
-  c->h_sp_out = static_cast<unsigned long long*>(h);
-  c->d_sp_out = static_cast<unsigned long long*>(d);
   return sp_reset_state(c);
 }
 // enqueue the compaction of `in` (dp slots; perm == nullptr: already in key order) into the mapped buffer
@@ -3074,10 +2937,10 @@ static int sp_compact(dsgd_ctx* c, const TIn* in, const int* perm) {
   DSGD_TRY(sp_ensure(c));
   const int tiles = sp_tiles(c);
   if (++c->sp_epoch == 0) c->sp_epoch = 1;
-  char* out = reinterpret_cast<char*>(c->d_sp_out);
+  char* out = reinterpret_cast<char*>(c->h_sp_out.dev());
   hipLaunchKernelGGL((dsgd_sparse_compact_kernel<TIn, TOut, REG>), dim3(tiles), dim3(SP_THREADS), 0, c->stream, const_cast<TIn*>(in), perm, c->dp,
                      c->d_sc, c->d_sp_state, c->sp_launches * (unsigned long long)tiles, c->sp_epoch, reinterpret_cast<int*>(out + 16),
-                     reinterpret_cast<TOut*>(out + sp_vals_off(c)), c->d_sp_out);
+                     reinterpret_cast<TOut*>(out + sp_vals_off(c)), c->h_sp_out.dev());
   HIP_TRY(hipGetLastError());
   ++c->sp_launches;
   return DSGD_OK;
@@ -3093,7 +2956,7 @@ static int sp_deliver(dsgd_ctx* c, int32_t* key_out, T* val_out, int64_t cap, in
   const int64_t nnz = (int64_t)c->h_sp_out[0];
   *nnz_out = nnz;
   if (nnz > cap) return fail(DSGD_EINVAL, "the Sparse value holds %lld entries, the output arrays %lld", (long long)nnz, (long long)cap);
-  const char* out = reinterpret_cast<const char*>(c->h_sp_out);
+  const char* out = reinterpret_cast<const char*>(c->h_sp_out.get());
   if (nnz > 0) {
     memcpy(key_out, out + 16, sizeof(int32_t) * (size_t)nnz);
     memcpy(val_out, out + sp_vals_off(c), sizeof(T) * (size_t)nnz);
@@ -3128,11 +2991,11 @@ static int sp_check_keys(dsgd_ctx* c, const int32_t* key, const void* val, int64
 template <typename TIn, typename TW>
 static int sp_scatter(dsgd_ctx* c, const int32_t* key, const TIn* val, int64_t nnz, TW* w) {
   const size_t voff = (sizeof(int) * (size_t)c->dp + 7) & ~(size_t)7;
-  if (!c->d_sp_in) HIP_TRY(hipMalloc(&c->d_sp_in, voff + sizeof(double) * (size_t)c->dp));
+  DSGD_TRY(c->d_sp_in.reserve(voff + sizeof(double) * (size_t)c->dp));
   if (nnz > 0) {
     const size_t vo = (sizeof(int) * (size_t)nnz + 7) & ~(size_t)7;
     DSGD_TRY(pin_acquire(c->pin_sp, vo + sizeof(TIn) * (size_t)nnz));
-    char* p = static_cast<char*>(c->pin_sp.p);
+    char* p = static_cast<char*>(c->pin_sp.p.get());
     memcpy(p, key, sizeof(int) * (size_t)nnz);
     memcpy(p + vo, val, sizeof(TIn) * (size_t)nnz);
     HIP_TRY(hipMemcpyAsync(c->d_sp_in, p, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
@@ -3140,7 +3003,7 @@ static int sp_scatter(dsgd_ctx* c, const int32_t* key, const TIn* val, int64_t n
     DSGD_TRY(pin_sent(c, c->pin_sp));
   }
   const int blocks = std::max(1, std::min(SP_SCATTER_BLOCKS, (c->dp + SP_TILE - 1) / SP_TILE));
-  hipLaunchKernelGGL((dsgd_sparse_scatter_kernel<TIn, TW>), dim3(blocks), dim3(SP_THREADS), 0, c->stream, reinterpret_cast<const int*>(c->d_sp_in),
+  hipLaunchKernelGGL((dsgd_sparse_scatter_kernel<TIn, TW>), dim3(blocks), dim3(SP_THREADS), 0, c->stream, reinterpret_cast<const int*>(c->d_sp_in.get()),
                      reinterpret_cast<const TIn*>(c->d_sp_in + voff), (int)std::max<int64_t>(nnz, 0), c->d_perm, w, c->dp);
   HIP_TRY(hipGetLastError());
   c->s_dirty = true;
@@ -3206,28 +3069,30 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
     hipError_t e__ = (expr);                                                                          \
     if (e__ != hipSuccess) return bail(fail(DSGD_EHIP, "%s: %s", #expr, hipGetErrorString(e__)));     \
   } while (0)
+#define DSGD_TRY_B(expr)              \
+  do {                                \
+    const int rc__ = (expr);          \
+    if (rc__ != DSGD_OK) return bail(rc__); \
+  } while (0)
   HIP_TRY_B(hipSetDevice(cfg->device));
   HIP_TRY_B(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIP_TRY_B(hipMalloc(&c->d_w, sizeof(float) * (c->dp + 1)));  // + the zero slot w[dp] of the wseg kernels
+  DSGD_TRY_B(c->d_w.alloc((size_t)c->dp + 1));  // + the zero slot w[dp] of the wseg kernels
   HIP_TRY_B(hipMemsetAsync(c->d_w + c->dp, 0, sizeof(float), c->stream));
-  HIP_TRY_B(hipMalloc(&c->d_ds, sizeof(float) * c->dp));
-  HIP_TRY_B(hipMalloc(&c->d_gsum, sizeof(float) * c->dp));
-  HIP_TRY_B(hipMalloc(&c->d_tmp, sizeof(float) * c->dp));
-  HIP_TRY_B(hipMalloc(&c->d_io, sizeof(float) * c->dp));
-  HIP_TRY_B(hipMalloc(&c->d_perm, sizeof(int) * c->dp));
-  HIP_TRY_B(hipMalloc(&c->d_sc, sizeof(DevScalars)));
-  HIP_TRY_B(hipHostMalloc(&c->h_sc, sizeof(DevScalars), hipHostMallocDefault));
-  HIP_TRY_B(hipHostMalloc(&c->h_mail, 4 * sizeof(unsigned long long), hipHostMallocMapped));
+  DSGD_TRY_B(c->d_ds.alloc((size_t)c->dp));
+  DSGD_TRY_B(c->d_gsum.alloc((size_t)c->dp));
+  DSGD_TRY_B(c->d_tmp.alloc((size_t)c->dp));
+  DSGD_TRY_B(c->d_io.alloc((size_t)c->dp));
+  DSGD_TRY_B(c->d_perm.alloc((size_t)c->dp));
+  DSGD_TRY_B(c->d_sc.alloc(1));
+  DSGD_TRY_B(c->h_sc.alloc(1));
+  DSGD_TRY_B(c->h_mail.alloc(4, hipHostMallocMapped));
   c->h_mail[0] = c->h_mail[1] = c->h_mail[2] = c->h_mail[3] = 0;
-  HIP_TRY_B(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_mail), c->h_mail, 0));
   HIP_TRY_B(hipMemsetAsync(c->d_w, 0, sizeof(float) * c->dp, c->stream));
   HIP_TRY_B(hipMemsetAsync(c->d_ds, 0, sizeof(float) * c->dp, c->stream));
   HIP_TRY_B(hipMemsetAsync(c->d_gsum, 0, sizeof(float) * c->dp, c->stream));
   HIP_TRY_B(hipMemsetAsync(c->d_sc, 0, sizeof(DevScalars), c->stream));
-  int rc = ensure_g(c, 1);
-  if (rc) return bail(rc);
-  rc = set_identity_perm(c);
-  if (rc) return bail(rc);
+  DSGD_TRY_B(ensure_g(c, 1));
+  DSGD_TRY_B(set_identity_perm(c));
   c->hw_eval = std::min(c->dp, DSGD_LDS_FLOATS);
   // Switches that stay: one per live decision (A/B measurements, tests that force a path), all read once here.
   if (const char* e = getenv("DSGD_FIX_SHIFT")) c->max_shift = std::max(8, std::min(FIX_SHIFT, atoi(e)));   // cap of the fixed-point shift
@@ -3269,7 +3134,7 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   }
   if (getenv("DSGD_PLAN_PROF") && atoi(getenv("DSGD_PLAN_PROF"))) {
     // (16 counters + four words per workgroup of the chunked launch's LAST run: start, end, cycles in the hot tiles, XCC id)
-    HIP_TRY_B(hipMalloc(&c->d_tprof, sizeof(unsigned long long) * (16 + 4 * 1024)));
+    DSGD_TRY_B(c->d_tprof.alloc(16 + 4 * 1024));
     HIP_TRY_B(hipMemsetAsync(c->d_tprof, 0, sizeof(unsigned long long) * (16 + 4 * 1024), c->stream));
   }
   c->hsplit = std::max(1, std::min(c->hsplit, (DSGD_LDS_FLOATS - 16 * WS_COEF_STRIDE - 4 - 64) / 2));   // (< 65536: 16-bit ranks)
@@ -3298,10 +3163,10 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   DSGD_ATTR(dsgd_fstep_kernel);
   DSGD_ATTR(dsgd_fstep_bound_kernel);
   if (c->fp64) {   // the fp64 state (csrc/dsgd_cs64.hpp)
-    HIP_TRY_B(hipMalloc(&c->d_w64, sizeof(double) * c->dp));
-    HIP_TRY_B(hipMalloc(&c->d_ds64, sizeof(double) * c->dp));
-    HIP_TRY_B(hipMalloc(&c->d_io64, sizeof(double) * c->dp));
-    HIP_TRY_B(hipMalloc(&c->d_nsq64, sizeof(double)));
+    DSGD_TRY_B(c->d_w64.alloc((size_t)c->dp));
+    DSGD_TRY_B(c->d_ds64.alloc((size_t)c->dp));
+    DSGD_TRY_B(c->d_io64.alloc((size_t)c->dp));
+    DSGD_TRY_B(c->d_nsq64.alloc(1));
     HIP_TRY_B(hipMemsetAsync(c->d_w64, 0, sizeof(double) * c->dp, c->stream));
     HIP_TRY_B(hipMemsetAsync(c->d_ds64, 0, sizeof(double) * c->dp, c->stream));
     DSGD_ATTR((dsgd_cs64_step_kernel<CS_THREADS, 1, 4>));
@@ -3328,6 +3193,7 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
 #undef DSGD_ATTR
   HIP_TRY_B(hipStreamSynchronize(c->stream));
 #undef HIP_TRY_B
+#undef DSGD_TRY_B
   *out = c;
   return DSGD_OK;
 }
@@ -3348,121 +3214,22 @@ int dsgd_destroy(dsgd_ctx* c) {
     (void)hipStreamSynchronize(c->async_stream);
     c->async_running = false;
   }
+  // every stream idle before anything is released: the members release themselves (delete c), in no particular order
   if (c->upd_stream) (void)hipStreamSynchronize(c->upd_stream);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->build_stream) (void)hipStreamSynchronize(c->build_stream);
   if (c->comm && rccl::available()) rccl::CommDestroy(c->comm);
   for (auto& e : c->prof_ev) {
     (void)hipEventDestroy(e.first);
     (void)hipEventDestroy(e.second);
   }
-  (void)hipFree(c->d_row_ptr);
-  (void)hipFree(c->d_col);
-  (void)hipFree(c->d_val);
-  (void)hipFree(c->d_label);
-  (void)hipFree(c->d_w);
-  (void)hipFree(c->d_ds);
-  (void)hipFree(c->d_w64);
-  (void)hipFree(c->d_ds64);
-  (void)hipFree(c->d_io64);
-  (void)hipFree(c->d_nsq64);
-  (void)hipFree(c->d_cs_w64);
-  (void)hipFree(c->d_cs_ds64);
-  (void)hipFree(c->d_cs64_x);
-  (void)hipFree(c->d_cs_dl64);
-  (void)hipFree(c->d_upd64_key);
-  (void)hipFree(c->d_upd64_dv);
-  (void)hipFree(c->d_rp64_acc);
-  (void)hipFree(c->d_rp64_s);
-  (void)hipFree(c->d_rp64_g);
-  (void)hipFree(c->d_rp64_gath);
-  (void)hipFree(c->d_rp64_gsegs);
-  (void)hipFree(c->d_val64);
-  (void)hipFree(c->d_rp64v_lo);
-  if (c->h_rp64_ranks) (void)hipHostFree(c->h_rp64_ranks);
-  (void)hipFree(c->d_rp64_ssegs);
-  (void)hipFree(c->d_rp64_cum);
-  (void)hipFree(c->d_rp64_sync);
-  if (c->h_rp64_sync) (void)hipHostFree(c->h_rp64_sync);
-  if (c->h_sp_out) (void)hipHostFree(c->h_sp_out);
-  (void)hipFree(c->d_sp_state);
-  (void)hipFree(c->d_sp_in);
-  pin_free(c->pin_sp);
-  (void)hipFree(c->d_g);
-  (void)hipFree(c->d_g64);
-  (void)hipFree(c->d_gsum);
-  (void)hipFree(c->d_tmp);
-  (void)hipFree(c->d_io);
-  (void)hipFree(c->d_perm);
-  (void)hipFree(c->d_sc);
-  (void)hipFree(c->d_idx);
-  (void)hipFree(c->d_segs);
-  (void)hipFree(c->d_ssegs);
-  (void)hipFree(c->d_coef8);
-  (void)hipFree(c->d_wtiles);
-  (void)hipFree(c->d_wmeta);
-  fstep_drop_all(c);
-  tcol_drop_all(c);
-  (void)hipFree(c->d_wlong_rows);
-  (void)hipFree(c->d_part);
-  (void)hipFree(c->d_partc);
-  (void)hipFree(c->d_hcol);
-  (void)hipFree(c->d_hval);
-  (void)hipFree(c->d_hrow_ptr);
-  (void)hipFree(c->d_ccol);
-  (void)hipFree(c->d_cval);
-  (void)hipFree(c->d_ctp);
-  (void)hipFree(c->d_ctiles);
-  (void)hipFree(c->d_cmeta);
-  (void)hipFree(c->d_dcold);
-  (void)hipFree(c->d_bound);
-  (void)hipFree(c->d_redpart);
-  (void)hipFree(c->d_pred);
-  pin_free(c->pin_w);
-  pin_free(c->pin_idx);
-  pin_free(c->pin_segs);
-  pin_free(c->pin_out);
-  pin_free(c->pin_upd);
-  (void)hipFree(c->d_upd_key);
-  (void)hipFree(c->d_upd_dv);
-  if (c->upd_stream) (void)hipStreamDestroy(c->upd_stream);
-  if (c->async_stream) (void)hipStreamDestroy(c->async_stream);
-  if (c->query_stream) (void)hipStreamDestroy(c->query_stream);
-  (void)hipFree(c->d_hog);
-  (void)hipFree(c->d_gcold);
-  (void)hipFree(c->d_asg);
-  if (c->h_hog) (void)hipHostFree(c->h_hog);
-  if (c->h_one) (void)hipHostFree(c->h_one);
-  (void)hipFree(c->d_hog_it);
-  (void)hipFree(c->d_trace);
-  (void)hipFree(c->d_tdot);
-  (void)hipFree(c->d_wprev);
-  (void)hipFree(c->d_wdelta);
-  (void)hipFree(c->d_tprof);
-  (void)hipFree(c->d_plan_gcold);
-  if (c->build_stream) {
-    (void)hipStreamSynchronize(c->build_stream);
-    (void)hipStreamDestroy(c->build_stream);
-  }
+  while (!c->plans.empty()) plan_release(c, c->plans.back());   // plans still alive: their blocks come back through the cache
   cache_drop_all(c);
-  for (int i = 0; i < 9; ++i) (void)hipFree(c->seed_scratch[i]);
-  (void)hipFree(c->req_layout.hdr);
-  (void)hipFree(c->req_layout.meta);
-  (void)hipFree(c->req_layout.rf);
-  (void)hipFree(c->req_layout.col);
-  (void)hipFree(c->req_layout.val);
-  (void)hipFree(c->req_layout.cl);
-  (void)hipFree(c->d_cs_max);
-  if (c->h_cs_max) (void)hipHostFree(c->h_cs_max);
-  (void)hipFree(c->d_cs_x);
-  (void)hipFree(c->d_cs_sync);
-  (void)hipFree(c->d_cs_w);
-  (void)hipFree(c->d_cs_ds);
-  if (c->h_sc) (void)hipHostFree(c->h_sc);
-  if (c->h_mail) (void)hipHostFree(c->h_mail);
-  if (c->h_req) (void)hipHostFree(c->h_req);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  const hipStream_t streams[] = {c->upd_stream, c->async_stream, c->query_stream, c->build_stream, c->stream};
   lk.unlock();
   delete c;
+  for (hipStream_t s : streams)
+    if (s) (void)hipStreamDestroy(s);
   return DSGD_OK;
 }
 
@@ -3555,24 +3322,19 @@ static int load_csr_impl(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in,
                                    "word per column; the data and the weights are unchanged)");
   HIP_TRY(hipStreamSynchronize(c->stream));
   DSGD_TRY(reset_layout(c));
-  (void)hipFree(c->d_row_ptr);
-  (void)hipFree(c->d_col);
-  (void)hipFree(c->d_val);
-  (void)hipFree(c->d_label);
-  (void)hipFree(c->d_val64);   // (float values again unless this load brings doubles)
-  c->d_row_ptr = nullptr;
-  c->d_col = nullptr;
-  c->d_val = nullptr;
-  c->d_label = nullptr;
-  c->d_val64 = nullptr;
-  HIP_TRY(hipMalloc(&c->d_row_ptr, sizeof(long long) * (size_t)(n_rows + 1)));
+  c->d_row_ptr.reset();
+  c->d_col.reset();
+  c->d_val.reset();
+  c->d_label.reset();
+  c->d_val64.reset();   // (float values again unless this load brings doubles)
+  DSGD_TRY(c->d_row_ptr.alloc((size_t)(n_rows + 1)));
   if (n_rows >= (int64_t)1 << 31) return fail(DSGD_EUNSUPPORTED, "more than 2^31-1 rows per context");
   // padding: the streaming kernels read whole windows (up to 512 slots) without clamping
-  HIP_TRY(hipMalloc(&c->d_col, sizeof(int) * (size_t)(nnz + WS_PAD)));
-  HIP_TRY(hipMalloc(&c->d_val, sizeof(float) * (size_t)(nnz + WS_PAD)));
+  DSGD_TRY(c->d_col.alloc((size_t)(nnz + WS_PAD)));
+  DSGD_TRY(c->d_val.alloc((size_t)(nnz + WS_PAD)));
   HIP_TRY(hipMemset(c->d_col + nnz, 0, sizeof(int) * WS_PAD));
   HIP_TRY(hipMemset(c->d_val + nnz, 0, sizeof(float) * WS_PAD));
-  HIP_TRY(hipMalloc(&c->d_label, (size_t)n_rows));
+  DSGD_TRY(c->d_label.alloc((size_t)n_rows));
   HIP_TRY(hipMemcpy(c->d_row_ptr, row_ptr, sizeof(long long) * (size_t)(n_rows + 1), hipMemcpyHostToDevice));
   if (nnz) {
     HIP_TRY(hipMemcpy(c->d_col, col, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
@@ -3580,7 +3342,7 @@ static int load_csr_impl(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in,
   }
   HIP_TRY(hipMemcpy(c->d_label, label, (size_t)n_rows, hipMemcpyHostToDevice));
   if (val64) {   // 8 bytes per non-zero, parallel to d_col / d_val (the ranking relabels d_col in place: the entries stay where they are)
-    HIP_TRY(hipMalloc(&c->d_val64, sizeof(double) * (size_t)(nnz + 1)));
+    DSGD_TRY(c->d_val64.alloc((size_t)(nnz + 1)));
     if (nnz) HIP_TRY(hipMemcpy(c->d_val64, val64, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
   }
   c->n_rows = n_rows;
@@ -3661,20 +3423,15 @@ int dsgd_set_dim_sparsity(dsgd_ctx* c, const float* ds) {
 }
 
 // dimSparsity in three parts around its all-reduce (one host thread, several contexts: dsgd_build_dim_sparsity_devices)
-static int ds_begin(dsgd_ctx* c, long long n_train, unsigned int** d_cnt_out) {   // (layout ready)
-  *d_cnt_out = nullptr;
+static int ds_begin(dsgd_ctx* c, long long n_train, DevBuf<unsigned int>& d_cnt) {   // (layout ready)
+  d_cnt.reset();
   long long nnz_train = 0;
   HIP_TRY(hipMemcpy(&nnz_train, c->d_row_ptr + n_train, sizeof(long long), hipMemcpyDeviceToHost));
-  unsigned int* d_cnt = nullptr;
-  HIP_TRY(hipMalloc(&d_cnt, sizeof(unsigned int) * c->dp));
+  DSGD_TRY(d_cnt.alloc((size_t)c->dp));
   int rc = reset_counters(c);
   if (!rc) rc = count_columns(c, nnz_train, d_cnt, true);
-  if (rc) {
-    (void)hipFree(d_cnt);
-    return rc;
-  }
-  *d_cnt_out = d_cnt;
-  return DSGD_OK;
+  if (rc) d_cnt.reset();
+  return rc;
 }
 static int ds_collective(dsgd_ctx* c, unsigned int* d_cnt) {
   if (!c->comm) return DSGD_OK;
@@ -3683,7 +3440,7 @@ static int ds_collective(dsgd_ctx* c, unsigned int* d_cnt) {
   if (r) return fail(DSGD_ERCCL, "ncclAllReduce(feature counts): %s", rccl::GetErrorString(r));
   return DSGD_OK;
 }
-static int ds_finish(dsgd_ctx* c, unsigned int* d_cnt, float* ds_out) {   // (takes ownership of d_cnt)
+static int ds_finish(dsgd_ctx* c, DevBuf<unsigned int>& d_cnt, float* ds_out) {   // (releases d_cnt)
   int rc = DSGD_OK;
   unsigned int cnt_key0 = 0;
   {
@@ -3702,7 +3459,7 @@ static int ds_finish(dsgd_ctx* c, unsigned int* d_cnt, float* ds_out) {   // (ta
     if (le != hipSuccess) rc = fail(DSGD_EHIP, "dimSparsity kernels: %s", hipGetErrorString(le));
   }
   if (!rc) rc = read_scalars(c);
-  (void)hipFree(d_cnt);
+  d_cnt.reset();
   DSGD_TRY(rc);
   DSGD_TRY(check_err_flag(c));
   if (cnt_key0) return fail(DSGD_ERANGE, "feature id 0 cannot be counted by Main.scala:60 (buff(idx - 1))");
@@ -3731,13 +3488,9 @@ int dsgd_build_dim_sparsity(dsgd_ctx* c, int64_t n_train, float* ds_out) {
   DSGD_TRY(bind(c));
   DSGD_TRY(ds_checks(c, n_train));
   DSGD_TRY(prepare_layout(c));
-  unsigned int* d_cnt = nullptr;
-  DSGD_TRY(ds_begin(c, n_train, &d_cnt));
-  const int rc = ds_collective(c, d_cnt);
-  if (rc) {
-    (void)hipFree(d_cnt);
-    return rc;
-  }
+  DevBuf<unsigned int> d_cnt;
+  DSGD_TRY(ds_begin(c, n_train, d_cnt));
+  DSGD_TRY(ds_collective(c, d_cnt));
   return ds_finish(c, d_cnt, ds_out);
 }
 
@@ -3861,23 +3614,20 @@ static int stage_lists(dsgd_ctx* c, const int32_t* const* idx_per_worker, const 
   if (c->req_mapped && tot <= REQ_MAPPED_ITEMS) {
     // the reference's batch sizes: the lists go into a host-mapped buffer the kernels read in place -- no copy on the
     // stream in front of the launch (every per-request entry point returns behind its kernels: the buffer is free again)
-    if (!c->h_req) {
-      HIP_TRY(hipHostMalloc(&c->h_req, sizeof(int) * (size_t)REQ_MAPPED_ITEMS, hipHostMallocMapped));
-      HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_req), c->h_req, 0));
-    }
+    if (!c->h_req) DSGD_TRY(c->h_req.alloc((size_t)REQ_MAPPED_ITEMS, hipHostMallocMapped));
     for (int k = 0; k < n_workers; ++k) {
       memcpy(c->h_req + off, idx_per_worker[k], sizeof(int) * (size_t)n_per_worker[k]);
       segs[k].begin = off;
       segs[k].end = off + n_per_worker[k];
       off += n_per_worker[k];
     }
-    c->cur_idx = c->d_req;
+    c->cur_idx = c->h_req.dev();
   } else {
     DSGD_TRY(ensure_idx(c, tot));
     // one copy for all lists, on the stream (behind the previous step's kernels, which may still be reading d_idx)
     DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int) * (size_t)tot));
     for (int k = 0; k < n_workers; ++k) {
-      memcpy(static_cast<int*>(c->pin_idx.p) + off, idx_per_worker[k], sizeof(int) * (size_t)n_per_worker[k]);
+      memcpy(static_cast<int*>(c->pin_idx.p.get()) + off, idx_per_worker[k], sizeof(int) * (size_t)n_per_worker[k]);
       segs[k].begin = off;
       segs[k].end = off + n_per_worker[k];
       off += n_per_worker[k];
@@ -4215,13 +3965,22 @@ int dsgd_plan_create_n(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const int
 
 // A plan's frame: offsets checked, the two device blocks taken from the cache, the list ranges uploaded (build stream).
 // The caller fills p->d_idx on the build stream and calls plan_finish; on failure everything is given back.
-static void plan_abandon(dsgd_ctx* c, dsgd_plan* p) {
-  (void)hipStreamSynchronize(c->build_stream);
-  cs_free(c, p);
+// the end of every plan: its cache blocks go back to the context behind whatever the launch stream still holds (an event per
+// block), its virtual tiles with the object (the caller has idled the launch stream if it holds any)
+static void plan_release(dsgd_ctx* c, dsgd_plan* p) {
   cache_give(c, p->d_idx, p->idx_bytes);
   cache_give(c, p->d_segs, p->segs_bytes);
+  cs_free(c, p);
+  cache_give(c, p->d_gate_rec, p->gate_bytes);
+  cache_give(c, p->d_s_rec, p->s_bytes);
+  // (the event may still be pending on the build stream: destroying a recorded event is allowed, its resources go when it completes)
   if (p->built_ev) (void)hipEventDestroy(p->built_ev);
+  c->plans.erase(std::remove(c->plans.begin(), c->plans.end(), p), c->plans.end());
   delete p;
+}
+static void plan_abandon(dsgd_ctx* c, dsgd_plan* p) {
+  (void)hipStreamSynchronize(c->build_stream);
+  plan_release(c, p);
 }
 static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int32_t n_workers, dsgd_plan** out) {
   const int64_t n_lists = n_steps * n_workers;
@@ -4246,6 +4005,7 @@ static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int3
   }
   dsgd_plan* p = new (std::nothrow) dsgd_plan();
   if (!p) return fail(DSGD_ENOMEM, "out of host memory");
+  c->plans.push_back(p);
   p->n_steps = n_steps;
   p->n_workers = n_workers;
   p->max_items = mx;
@@ -4385,28 +4145,17 @@ static int sync_step64(dsgd_ctx* c, const int32_t* const* idx_per_worker, const 
     if (rc == DSGD_OK) c->pending_samples -= offsets[(size_t)n_workers];   // (a request reports its own samples, below)
   }
   if (p->built_pending) (void)hipStreamWaitEvent(c->stream, p->built_ev, 0);
-  cache_give(c, p->d_idx, p->idx_bytes);   // (the blocks go back behind the step: an event on the launch stream)
-  cache_give(c, p->d_segs, p->segs_bytes);
-  cs_free(c, p);
-  if (p->built_ev) (void)hipEventDestroy(p->built_ev);
-  delete p;
+  plan_release(c, p);   // (the blocks go back behind the step: an event on the launch stream)
   DSGD_TRY(rc);
   return finish_stats(c, stats, offsets[(size_t)n_workers]);
 }
 
 // slot `i` of the from-seed scratch with room for `bytes`
 static hipError_t seed_scratch(dsgd_ctx* c, int i, size_t bytes, void** out) {
-  if (c->seed_scratch_bytes[i] < bytes) {
-    (void)hipFree(c->seed_scratch[i]);
-    c->seed_scratch[i] = nullptr;
-    c->seed_scratch_bytes[i] = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    const hipError_t e = hipMalloc(&c->seed_scratch[i], want);
-    if (e != hipSuccess) return e;
-    c->seed_scratch_bytes[i] = want;
-  }
-  *out = c->seed_scratch[i];
-  return hipSuccess;
+  DevBuf<void>& b = c->seed_scratch[i];
+  const hipError_t e = b.cap() < bytes ? b.try_alloc(bytes + bytes / 4 + 4096) : hipSuccess;
+  *out = b.get();
+  return e;
 }
 // ---- an epoch's lists drawn on the device, draw for draw the reference's stream (csrc/dsgd_shuffle.hpp) ---------------------
 int dsgd_plan_create_from_seed(dsgd_ctx* c, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
@@ -4705,6 +4454,13 @@ extern "C" int dsgd_test_cs_skip_publish(dsgd_ctx* c, int32_t from_step) {
   c->cs_test_skip = from_step < 0 ? 0 : from_step;
   return DSGD_OK;
 }
+// ... and the bytes the library holds right now, counted where it allocates (csrc/dsgd_buf.hpp): the whole process', every
+// context and dense engine together.  What a context took, dsgd_destroy gives back (tests/test_gpu_ctx_lifetime.py).
+extern "C" void dsgd_test_live_bytes(int64_t* device_bytes, int64_t* pinned_bytes) {
+  std::lock_guard<std::mutex> ld(g_live_dev.mu), lp(g_live_pin.mu);
+  if (device_bytes) *device_bytes = g_live_dev.bytes;
+  if (pinned_bytes) *pinned_bytes = g_live_pin.bytes;
+}
 #endif
 
 int dsgd_plan_info(dsgd_ctx* c, dsgd_plan* p, int32_t* vals, int32_t n) {
@@ -4733,23 +4489,9 @@ int dsgd_plan_destroy(dsgd_ctx* c, dsgd_plan* p) {
   // no hipFree, no device synchronisation -- an epoch of the reference is one plan); a set-up that never ran is ordered
   // in front of that first
   if (p->built_pending) HIP_TRY(hipStreamWaitEvent(c->stream, p->built_ev, 0));
-  cache_give(c, p->d_idx, p->idx_bytes);
-  cache_give(c, p->d_segs, p->segs_bytes);
-  cs_free(c, p);
-  cache_give(c, p->d_gate_rec, p->gate_bytes);
-  cache_give(c, p->d_s_rec, p->s_bytes);
-  if (p->d_vt_lanes || p->d_vt_segs || p->d_vt_long || p->d_vt_packed) {   // (the larger steps' tiles: allocated per plan)
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(p->d_vt_lanes);
-    (void)hipFree(p->d_vt_segs);
-    (void)hipFree(p->d_vt_long);
-    (void)hipFree(p->d_vt_packed);
-  }
-  if (p->built_ev) {
-    // (the event may still be pending on the build stream: destroying a recorded event is allowed, its resources go when it completes)
-    (void)hipEventDestroy(p->built_ev);
-  }
-  delete p;
+  // (the larger steps' tiles are allocated per plan and go with it: not before their last reader)
+  if (p->d_vt_lanes || p->d_vt_segs || p->d_vt_long || p->d_vt_packed) HIP_TRY(hipStreamSynchronize(c->stream));
+  plan_release(c, p);
   return DSGD_OK;
 }
 
@@ -4872,8 +4614,7 @@ static int async_step64(dsgd_ctx* c, const char* what, const int32_t* idx, int64
   }
   if (c->d_val64) {   // Double data: the row-parallel pair with the asynchronous finish; the delta in key order as it is written
     DSGD_TRY(cs64_step_limits(c, 1, n));   // (the one-step plan's refusals, as on float data)
-    if (want_delta && !c->d_cs_dl64)
-      HIP_TRY(hipMalloc(&c->d_cs_dl64, sizeof(double) * ((size_t)CS64_G * cs64_sp(c->dp) + (size_t)c->dp)));
+    if (want_delta) DSGD_TRY(c->d_cs_dl64.reserve((size_t)CS64_G * cs64_sp(c->dp) + (size_t)c->dp));
     DSGD_TRY(rp64_ensure(c, 1));
     DSGD_TRY(reset_counters(c));
     long long mx = 0, tot = 0;
@@ -4904,7 +4645,7 @@ static int async_step64(dsgd_ctx* c, const char* what, const int32_t* idx, int64
   DSGD_TRY(plan_finish(c, p, &p));
   const int Sp = cs64_sp(c->dp);
   int rc = DSGD_OK;
-  if (want_delta && !c->d_cs_dl64 && hipMalloc(&c->d_cs_dl64, sizeof(double) * ((size_t)CS64_G * Sp + (size_t)c->dp)) != hipSuccess)
+  if (want_delta && c->d_cs_dl64.reserve((size_t)CS64_G * Sp + (size_t)c->dp) != DSGD_OK)
     rc = fail(DSGD_ENOMEM, "out of device memory (the delta of an async step)");
   if (rc == DSGD_OK && want_delta && hipMemsetAsync(c->d_cs_dl64, 0, sizeof(double) * (size_t)CS64_G * Sp, c->stream) != hipSuccess)
     rc = fail(DSGD_EHIP, "hipMemsetAsync");
@@ -4914,11 +4655,7 @@ static int async_step64(dsgd_ctx* c, const char* what, const int32_t* idx, int64
     if (rc == DSGD_OK) c->pending_samples -= n;   // (a request reports its own samples, below)
   }
   if (p->built_pending) (void)hipStreamWaitEvent(c->stream, p->built_ev, 0);
-  cache_give(c, p->d_idx, p->idx_bytes);   // (the blocks go back behind the step: an event on the launch stream)
-  cache_give(c, p->d_segs, p->segs_bytes);
-  cs_free(c, p);
-  if (p->built_ev) (void)hipEventDestroy(p->built_ev);
-  delete p;
+  plan_release(c, p);   // (the blocks go back behind the step: an event on the launch stream)
   DSGD_TRY(rc);
   double* rank = want_delta ? c->d_cs_dl64 + (size_t)CS64_G * Sp : nullptr;
   if (sparse) {   // slice-major -> rank order -> the pairs, all in front of the call's synchronisation
@@ -4965,17 +4702,8 @@ int dsgd_update_grad_f64(dsgd_ctx* c, const int32_t* key, const double* dv, int6
   }
   DSGD_TRY(bind(c, true));   // (the weights stay in whichever layout they are: slice-major between plan runs)
   DSGD_TRY(require_sync_mode(c));
-  if (c->upd64_cap < nnz) {
-    (void)hipFree(c->d_upd64_key);
-    (void)hipFree(c->d_upd64_dv);
-    c->d_upd64_key = nullptr;
-    c->d_upd64_dv = nullptr;
-    c->upd64_cap = 0;
-    const long long cap = std::max<long long>(nnz, 4096);
-    HIP_TRY(hipMalloc(&c->d_upd64_key, sizeof(int) * (size_t)cap));
-    HIP_TRY(hipMalloc(&c->d_upd64_dv, sizeof(double) * (size_t)cap));
-    c->upd64_cap = cap;
-  }
+  DSGD_TRY(c->d_upd64_key.reserve((size_t)std::max<long long>(nnz, 4096)));
+  DSGD_TRY(c->d_upd64_dv.reserve((size_t)std::max<long long>(nnz, 4096)));
   HIP_TRY(hipMemcpyAsync(c->d_upd64_key, key, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->d_upd64_dv, dv, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
   const bool sliced = c->cs_w_G == CS64_G;
@@ -5005,18 +4733,14 @@ static int rp64_check_lists(dsgd_ctx* c, const int32_t* const* idx_per_worker, c
   return DSGD_OK;
 }
 static int rp64_ensure(dsgd_ctx* c, int n_workers) {
-  if (!c->d_rp64_s) {
-    HIP_TRY(hipMalloc(&c->d_rp64_s, sizeof(double)));
-    HIP_TRY(hipMalloc(&c->d_rp64_g, sizeof(double) * c->dp));
-  }
+  DSGD_TRY(c->d_rp64_s.reserve(1));
+  DSGD_TRY(c->d_rp64_g.reserve((size_t)c->dp));
   if (c->rp64_k < n_workers) {   // (zeroed once; every finish leaves them zeroed)
     HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_rp64_acc);
-    c->d_rp64_acc = nullptr;
     c->rp64_k = 0;
     const long long stride = ((long long)c->dp + 63) & ~63LL;
     const int cap = std::max(n_workers, 4);
-    HIP_TRY(hipMalloc(&c->d_rp64_acc, sizeof(unsigned long long) * (size_t)stride * (size_t)cap));
+    DSGD_TRY(c->d_rp64_acc.alloc((size_t)stride * (size_t)cap));
     HIP_TRY(hipMemsetAsync(c->d_rp64_acc, 0, sizeof(unsigned long long) * (size_t)stride * (size_t)cap, c->stream));
     c->rp64_stride = stride;
     c->rp64_k = cap;
@@ -5024,11 +4748,9 @@ static int rp64_ensure(dsgd_ctx* c, int n_workers) {
   // the second word of a column sum, in the shape of the first: Double data only (a float-data context never allocates it)
   if (c->d_val64 && !(c->d_rp64v_lo && c->rp64v_k >= c->rp64_k && c->rp64v_stride == c->rp64_stride)) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_rp64v_lo);
-    c->d_rp64v_lo = nullptr;
     c->rp64v_k = 0;
     const size_t words = (size_t)c->rp64_stride * (size_t)c->rp64_k;
-    HIP_TRY(hipMalloc(&c->d_rp64v_lo, sizeof(unsigned long long) * words));
+    DSGD_TRY(c->d_rp64v_lo.alloc(words));
     HIP_TRY(hipMemsetAsync(c->d_rp64v_lo, 0, sizeof(unsigned long long) * words, c->stream));
     c->rp64v_k = c->rp64_k;
     c->rp64v_stride = c->rp64_stride;
@@ -5039,20 +4761,18 @@ static int rp64_ensure(dsgd_ctx* c, int n_workers) {
 static long long rp64_gather_pad(int world) { return ((long long)world + 63) & ~63LL; }
 static void rp64_gather_drop(dsgd_ctx* c) {   // (after a failure half way: the next step starts from a zeroed buffer)
   (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(c->d_rp64_gath);
-  (void)hipFree(c->d_rp64_gsegs);
-  c->d_rp64_gath = nullptr;
-  c->d_rp64_gsegs = nullptr;
+  c->d_rp64_gath.reset();
+  c->d_rp64_gsegs.reset();
   c->rp64_gk = 0;
 }
 static int rp64_gather_ensure(dsgd_ctx* c, int K) {
-  if (!c->h_rp64_ranks) HIP_TRY(hipHostMalloc(&c->h_rp64_ranks, sizeof(unsigned long long) * 64, hipHostMallocDefault));
+  DSGD_TRY(c->h_rp64_ranks.reserve(64));
   if (c->rp64_gk >= K && c->d_rp64_gath) return DSGD_OK;
   rp64_gather_drop(c);
   const long long stride = rp64_gather_stride(c->dp);
   const size_t words = (size_t)rp64_gather_pad(c->world) + (size_t)stride * (size_t)K;
-  HIP_TRY(hipMalloc(&c->d_rp64_gath, sizeof(unsigned long long) * words));
-  HIP_TRY(hipMalloc(&c->d_rp64_gsegs, sizeof(WorkSeg) * (size_t)K));
+  DSGD_TRY(c->d_rp64_gath.alloc(words));
+  DSGD_TRY(c->d_rp64_gsegs.alloc((size_t)K));
   HIP_TRY(hipMemsetAsync(c->d_rp64_gath, 0, sizeof(unsigned long long) * words, c->stream));
   c->rp64_gstride = stride;
   c->rp64_gk = K;
@@ -5303,24 +5023,12 @@ static int rp64_fused_cap(dsgd_ctx* c, bool v64) {
   return DSGD_OK;
 }
 static int rp64_steps_ensure(dsgd_ctx* c, long long n_lists, long long n_steps) {
-  if (c->rp64_ssegs_cap < n_lists || c->rp64_cum_cap < n_steps) HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->rp64_ssegs_cap < n_lists) {
-    (void)hipFree(c->d_rp64_ssegs);
-    c->d_rp64_ssegs = nullptr;
-    c->rp64_ssegs_cap = 0;
-    HIP_TRY(hipMalloc(&c->d_rp64_ssegs, sizeof(WorkSeg) * (size_t)n_lists));
-    c->rp64_ssegs_cap = n_lists;
-  }
-  if (c->rp64_cum_cap < n_steps) {
-    (void)hipFree(c->d_rp64_cum);
-    c->d_rp64_cum = nullptr;
-    c->rp64_cum_cap = 0;
-    HIP_TRY(hipMalloc(&c->d_rp64_cum, sizeof(unsigned long long) * (size_t)n_steps));
-    c->rp64_cum_cap = n_steps;
-  }
+  if (c->d_rp64_ssegs.cap() < (size_t)n_lists || c->d_rp64_cum.cap() < (size_t)n_steps) HIP_TRY(hipStreamSynchronize(c->stream));
+  DSGD_TRY(c->d_rp64_ssegs.reserve((size_t)n_lists));
+  DSGD_TRY(c->d_rp64_cum.reserve((size_t)n_steps));
   if (!c->d_rp64_sync) {
-    HIP_TRY(hipHostMalloc(&c->h_rp64_sync, sizeof(unsigned long long) * 2, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&c->d_rp64_sync, sizeof(unsigned long long) * 2));
+    DSGD_TRY(c->h_rp64_sync.alloc(2));
+    DSGD_TRY(c->d_rp64_sync.alloc(2));
     HIP_TRY(hipMemsetAsync(c->d_rp64_sync, 0, sizeof(unsigned long long) * 2, c->stream));
     c->rp64_target = 0;
   }
@@ -5371,7 +5079,7 @@ int dsgd_sync_steps_f64(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const in
   c->cur_idx = c->d_idx;
   DSGD_TRY(pin_acquire(c->pin_segs, sizeof(WorkSeg) * (size_t)n_lists));
   {
-    WorkSeg* sg = static_cast<WorkSeg*>(c->pin_segs.p);
+    WorkSeg* sg = static_cast<WorkSeg*>(c->pin_segs.p.get());
     for (int64_t i = 0; i < n_lists; ++i) {
       sg[i].begin = offsets[i];
       sg[i].end = offsets[i + 1];
@@ -5452,7 +5160,7 @@ int dsgd_sync_steps_f64(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const in
   c->h_rp64_sync[0] = 0;
   if (n_fused) HIP_TRY(hipMemcpyAsync(c->h_rp64_sync, c->d_rp64_sync, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   DSGD_TRY(finish_stats(c, nullptr, n_idx));   // the ONE synchronisation of the call
-  const unsigned long long* cum = want_cum ? static_cast<const unsigned long long*>(c->pin_out.p) : nullptr;
+  const unsigned long long* cum = want_cum ? static_cast<const unsigned long long*>(c->pin_out.p.get()) : nullptr;
   if (aborted || (c->h_rp64_sync[0] & RP64_GAVE_UP) != 0) {
     // A fused launch gave up waiting for its own grid.  The bit is set only while that launch's arrivals are incomplete and
     // every workgroup that waits sees it, so NO workgroup of that launch ran phase 2 and every later launch returned on entry:
@@ -5580,14 +5288,9 @@ int dsgd_forward_f64(dsgd_ctx* c, const double* w, const int32_t* idx, int64_t n
 static int forward_run(dsgd_ctx* c, const int32_t* idx, int64_t n, float* pred_out) {
   DSGD_TRY(ensure_idx(c, n));
   DSGD_TRY(reset_counters(c));
-  if (n > c->pred_cap) {
+  if ((size_t)n > c->d_pred.cap()) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_pred) HIP_TRY(hipFree(c->d_pred));
-    c->d_pred = nullptr;
-    c->pred_cap = 0;
-    const long long cap = std::max<long long>(n, 4096);
-    HIP_TRY(hipMalloc(&c->d_pred, sizeof(float) * (size_t)cap));
-    c->pred_cap = cap;
+    DSGD_TRY(c->d_pred.reserve((size_t)std::max<long long>(n, 4096)));
   }
   float* d_pred = c->d_pred;
   DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int) * (size_t)n));
@@ -5746,20 +5449,17 @@ int dsgd_update_grad(dsgd_ctx* c, const int32_t* key, const float* dv, int64_t n
   // on a side stream while the engine is resident, atomic adds to w, and the engine's incremental regulariser scalar
   // told about the foreign update.
   if (!c->upd_stream) HIP_TRY(hipStreamCreateWithFlags(&c->upd_stream, hipStreamNonBlocking));
-  if (!c->d_upd_key) {
-    const long long cap = std::max<long long>(c->dp, 4096);   // a Sparse delta holds at most D + 1 entries; longer inputs go in pieces
-    HIP_TRY(hipMalloc(&c->d_upd_key, sizeof(int) * (size_t)cap));
-    HIP_TRY(hipMalloc(&c->d_upd_dv, sizeof(float) * (size_t)cap));
-    c->upd_cap = cap;
-  }
+  const long long upd_cap = std::max<long long>(c->dp, 4096);   // a Sparse delta holds at most D + 1 entries; longer inputs go in pieces
+  DSGD_TRY(c->d_upd_key.reserve((size_t)upd_cap));
+  DSGD_TRY(c->d_upd_dv.reserve((size_t)upd_cap));
   // (an engine that has reached its budget but has not been joined yet is not live: its kernel has exited, nothing adds
   //  to w any more and nobody reads HogState::s_reg -- the update takes the plain path with the Sparse filter pass)
   const bool live = c->async_running && !(c->exch_done.load() && hipStreamQuery(c->async_stream) == hipSuccess);
   hipStream_t st = live ? c->upd_stream : c->stream;
-  for (int64_t o = 0; o < nnz; o += c->upd_cap) {
-    const long long n = std::min<long long>(c->upd_cap, nnz - o);
+  for (int64_t o = 0; o < nnz; o += upd_cap) {
+    const long long n = std::min<long long>(upd_cap, nnz - o);
     DSGD_TRY(pin_acquire(c->pin_upd, (sizeof(int) + sizeof(float)) * (size_t)n));
-    int* pk = static_cast<int*>(c->pin_upd.p);
+    int* pk = static_cast<int*>(c->pin_upd.p.get());
     float* pv = reinterpret_cast<float*>(pk + n);
     memcpy(pk, key + o, sizeof(int) * (size_t)n);
     memcpy(pv, dv + o, sizeof(float) * (size_t)n);
@@ -6037,48 +5737,30 @@ int dsgd_async_start(dsgd_ctx* c, const int64_t* assigned_begin, const int64_t* 
   if (!c->async_stream) {
     HIP_TRY(hipStreamCreateWithFlags(&c->async_stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&c->query_stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc(&c->d_hog, sizeof(HogState)));
-    HIP_TRY(hipHostMalloc(&c->h_hog, sizeof(HogState), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc(&c->h_one, sizeof(int), hipHostMallocDefault));
+    DSGD_TRY(c->d_hog.alloc(1));
+    DSGD_TRY(c->h_hog.alloc(1));
+    DSGD_TRY(c->h_one.alloc(1));
     *c->h_one = 1;
   }
   const int hl = std::min(c->dp, c->hog_hl) & ~3;
   const size_t strip = (size_t)std::max(1, c->dp - hl);
   if (n_workers > c->hog_workers) {
-    (void)hipFree(c->d_gcold);
-    (void)hipFree(c->d_asg);
-    (void)hipFree(c->d_hog_it);
-    c->d_gcold = nullptr;
-    c->d_asg = nullptr;
-    c->d_hog_it = nullptr;
-    HIP_TRY(hipMalloc(&c->d_gcold, sizeof(float) * (size_t)n_workers * strip));
-    HIP_TRY(hipMalloc(&c->d_asg, sizeof(long long) * 2 * (size_t)n_workers));
-    HIP_TRY(hipMalloc(&c->d_hog_it, sizeof(unsigned long long) * (size_t)n_workers));
+    c->hog_workers = 0;
+    DSGD_TRY(c->d_gcold.alloc((size_t)n_workers * strip));
+    DSGD_TRY(c->d_asg.alloc(2 * (size_t)n_workers));
+    DSGD_TRY(c->d_hog_it.alloc((size_t)n_workers));
     c->hog_workers = n_workers;
   }
   if (c->trace_cap > 0) {   // traced run: records of hog_trace_words(batch) words (header, gate masks, one x . w per row)
     c->trace_mw = (batch + 31) / 32;
     c->trace_batch = batch;
     const long long need = c->trace_cap * hog_trace_words(batch);
-    if (need > c->trace_words) {
-      (void)hipFree(c->d_trace);
-      c->d_trace = nullptr;
-      c->trace_words = 0;
-      HIP_TRY(hipMalloc(&c->d_trace, sizeof(unsigned int) * (size_t)need));
-      c->trace_words = need;
-    }
-    const long long need_dot = (long long)n_workers * batch;
-    if (need_dot > c->tdot_words) {
-      (void)hipFree(c->d_tdot);
-      c->d_tdot = nullptr;
-      c->tdot_words = 0;
-      HIP_TRY(hipMalloc(&c->d_tdot, sizeof(float) * (size_t)need_dot));
-      c->tdot_words = need_dot;
-    }
+    DSGD_TRY(c->d_trace.reserve((size_t)need));
+    DSGD_TRY(c->d_tdot.reserve((size_t)n_workers * (size_t)batch));
   }
-  if (exchange && !c->d_wprev) {
-    HIP_TRY(hipMalloc(&c->d_wprev, sizeof(float) * c->dp));
-    HIP_TRY(hipMalloc(&c->d_wdelta, sizeof(float) * 2 * c->dp));
+  if (exchange) {
+    DSGD_TRY(c->d_wprev.reserve((size_t)c->dp));
+    DSGD_TRY(c->d_wdelta.reserve(2 * (size_t)c->dp));
   }
   HIP_TRY(hipMemsetAsync(c->d_gcold, 0, sizeof(float) * (size_t)n_workers * strip, c->stream));
   HIP_TRY(hipMemsetAsync(c->d_hog_it, 0, sizeof(unsigned long long) * (size_t)n_workers, c->stream));
@@ -6234,12 +5916,8 @@ int dsgd_async_set_trace(dsgd_ctx* c, int64_t capacity) {
   if (c->async_running) return fail(DSGD_ESTATE, "async computation running");
   c->trace_cap = capacity;   // (the buffer is sized at dsgd_async_start: a record's length depends on the batch size)
   if (capacity == 0) {
-    (void)hipFree(c->d_trace);   // (no engine is resident: hipFree's device synchronisation returns)
-    (void)hipFree(c->d_tdot);
-    c->d_trace = nullptr;
-    c->d_tdot = nullptr;
-    c->trace_words = 0;
-    c->tdot_words = 0;
+    c->d_trace.reset();   // (no engine is resident: the release's device synchronisation returns)
+    c->d_tdot.reset();
     c->trace_mw = 0;
     c->trace_batch = 0;
   }
@@ -6358,8 +6036,8 @@ static int relayout(dsgd_ctx* c) {
     for (int j = 0; j < c->dp; ++j) inv[(size_t)perm[(size_t)j]] = j;
     DSGD_TRY(reset_layout(c));   // (d_perm: the identity from here)
     if (c->nnz > 0) {
-      int* d_inv = nullptr;
-      HIP_TRY(hipMalloc(&d_inv, sizeof(int) * inv.size()));
+      DevBuf<int> d_inv;
+      DSGD_TRY(d_inv.alloc(inv.size()));
       hipError_t e = hipMemcpy(d_inv, inv.data(), sizeof(int) * inv.size(), hipMemcpyHostToDevice);
       if (e == hipSuccess) {
         const int blocks = (int)std::min<long long>((c->nnz + 255) / 256, (long long)c->n_cu * 8);
@@ -6367,7 +6045,7 @@ static int relayout(dsgd_ctx* c) {
         e = hipGetLastError();
       }
       if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      (void)hipFree(d_inv);
+      d_inv.reset();
       if (e != hipSuccess) return fail(DSGD_EHIP, "column keys: %s", hipGetErrorString(e));
     }
   }
@@ -6544,13 +6222,7 @@ int dsgd_build_dim_sparsity_devices(dsgd_ctx* const* ctxs, int32_t n_ctx, const 
   DSGD_TRY(refuse_fp64_all(ctxs, n_ctx, "dsgd_build_dim_sparsity_devices"));
   if (!n_train_per_ctx) return fail(DSGD_EINVAL, "null n_train_per_ctx");
   DSGD_TRY(group_shape(ctxs, n_ctx));
-  std::vector<unsigned int*> cnt((size_t)n_ctx, nullptr);
-  auto drop = [&]() {
-    for (auto& p : cnt) {
-      (void)hipFree(p);
-      p = nullptr;
-    }
-  };
+  std::vector<DevBuf<unsigned int>> cnt((size_t)n_ctx);   // (what a failure leaves is released on return)
   int rc = DSGD_OK;
   for (int i = 0; i < n_ctx && !rc; ++i) {
     rc = bind(ctxs[i]);
@@ -6559,30 +6231,23 @@ int dsgd_build_dim_sparsity_devices(dsgd_ctx* const* ctxs, int32_t n_ctx, const 
   // the column ranking: counts, their sum over the contexts, one order for all
   for (int i = 0; i < n_ctx && !rc; ++i) {
     rc = bind(ctxs[i]);
-    if (!rc) rc = layout_begin(ctxs[i], &cnt[(size_t)i]);
+    if (!rc) rc = layout_begin(ctxs[i], cnt[(size_t)i]);
   }
   if (!rc) rc = grouped(ctxs, n_ctx, [&](dsgd_ctx* c, int i) { return layout_collective(c, cnt[(size_t)i]); });
   for (int i = 0; i < n_ctx && !rc; ++i) {
     rc = bind(ctxs[i]);
-    if (!rc) {
-      rc = layout_finish(ctxs[i], cnt[(size_t)i]);   // (takes the buffer)
-      cnt[(size_t)i] = nullptr;
-    }
+    if (!rc) rc = layout_finish(ctxs[i], cnt[(size_t)i]);   // (releases the buffer)
   }
   // dimSparsity: feature counts of every context's train rows, summed (Main.scala:57-60 counts the whole train set)
   for (int i = 0; i < n_ctx && !rc; ++i) {
     rc = bind(ctxs[i]);
-    if (!rc) rc = ds_begin(ctxs[i], n_train_per_ctx[i], &cnt[(size_t)i]);
+    if (!rc) rc = ds_begin(ctxs[i], n_train_per_ctx[i], cnt[(size_t)i]);
   }
   if (!rc) rc = grouped(ctxs, n_ctx, [&](dsgd_ctx* c, int i) { return ds_collective(c, cnt[(size_t)i]); });
   for (int i = 0; i < n_ctx && !rc; ++i) {
     rc = bind(ctxs[i]);
-    if (!rc) {
-      rc = ds_finish(ctxs[i], cnt[(size_t)i], nullptr);
-      cnt[(size_t)i] = nullptr;
-    }
+    if (!rc) rc = ds_finish(ctxs[i], cnt[(size_t)i], nullptr);
   }
-  drop();
   return rc;
 }
 
@@ -6805,13 +6470,10 @@ struct dsgd_dense {
   std::mutex mu;
   hipStream_t stream = nullptr;
   long long n_rows = 0;
-  float* d_X = nullptr;
-  float* d_y = nullptr;
-  float* d_w = nullptr;
-  float* d_g = nullptr;
-  float* d_gpart = nullptr;   // n_wg x D
-  double* d_lpart = nullptr;  // n_wg x 2
-  double* h_lpart = nullptr;  // pinned
+  DevBuf<float> d_X, d_y, d_w, d_g;
+  DevBuf<float> d_gpart;      // n_wg x D
+  DevBuf<double> d_lpart;     // n_wg x 2
+  HostBuf<double> h_lpart;    // pinned
   int n_wg = 0;
   bool mfma = false;          // DSGD_DENSE_MFMA=1: forward product with v_mfma_f32_16x16x4_f32 (D a multiple of 256, <= 4096)
   rccl::comm_t comm = nullptr;
@@ -6899,15 +6561,16 @@ int dsgd_dense_create(int32_t n_features, int32_t device, dsgd_dense** out) {
   }
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc(&d->d_w, sizeof(float) * d->D);
-  if (e == hipSuccess) e = hipMalloc(&d->d_g, sizeof(float) * d->D);
-  if (e == hipSuccess) e = hipMalloc(&d->d_gpart, sizeof(float) * (size_t)d->n_wg * d->D);
-  if (e == hipSuccess) e = hipMalloc(&d->d_lpart, sizeof(double) * 2 * d->n_wg);
-  if (e == hipSuccess) e = hipHostMalloc(&d->h_lpart, sizeof(double) * 2 * d->n_wg, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMemset(d->d_w, 0, sizeof(float) * d->D);
-  if (e != hipSuccess) {
-    dsgd_dense_destroy(d);
-    return fail(DSGD_EHIP, "dense create: %s", hipGetErrorString(e));
+  int rc = e == hipSuccess ? DSGD_OK : fail(DSGD_EHIP, "dense create: %s", hipGetErrorString(e));
+  if (!rc) rc = d->d_w.alloc((size_t)d->D);
+  if (!rc) rc = d->d_g.alloc((size_t)d->D);
+  if (!rc) rc = d->d_gpart.alloc((size_t)d->n_wg * d->D);
+  if (!rc) rc = d->d_lpart.alloc(2 * (size_t)d->n_wg);
+  if (!rc) rc = d->h_lpart.alloc(2 * (size_t)d->n_wg);
+  if (!rc && (e = hipMemset(d->d_w, 0, sizeof(float) * d->D)) != hipSuccess) rc = fail(DSGD_EHIP, "dense create: %s", hipGetErrorString(e));
+  if (rc) {
+    dsgd_dense_destroy(d);   // (leaves the message alone)
+    return rc;
   }
   *out = d;
   return DSGD_OK;
@@ -6922,27 +6585,19 @@ int dsgd_dense_destroy(dsgd_dense* d) {
     (void)hipEventDestroy(e.first);
     (void)hipEventDestroy(e.second);
   }
-  (void)hipFree(d->d_X);
-  (void)hipFree(d->d_y);
-  (void)hipFree(d->d_w);
-  (void)hipFree(d->d_g);
-  (void)hipFree(d->d_gpart);
-  (void)hipFree(d->d_lpart);
-  if (d->h_lpart) (void)hipHostFree(d->h_lpart);
-  if (d->stream) (void)hipStreamDestroy(d->stream);
-  delete d;
+  const hipStream_t stream = d->stream;
+  delete d;   // (the stream is idle: the members release themselves)
+  if (stream) (void)hipStreamDestroy(stream);
   return DSGD_OK;
 }
 
 static int dn_alloc_rows(dsgd_dense* d, long long n_rows) {
   HIP_TRY(hipStreamSynchronize(d->stream));
-  (void)hipFree(d->d_X);
-  (void)hipFree(d->d_y);
-  d->d_X = nullptr;
-  d->d_y = nullptr;
+  d->d_X.reset();
+  d->d_y.reset();
   d->n_rows = 0;
-  HIP_TRY(hipMalloc(&d->d_X, sizeof(float) * (size_t)n_rows * (size_t)d->D));
-  HIP_TRY(hipMalloc(&d->d_y, sizeof(float) * (size_t)n_rows));
+  DSGD_TRY(d->d_X.alloc((size_t)n_rows * (size_t)d->D));
+  DSGD_TRY(d->d_y.alloc((size_t)n_rows));
   d->n_rows = n_rows;
   return DSGD_OK;
 }
