@@ -41,6 +41,7 @@ SYMBOLS = [
     "dsgd_gradient_sparse", "dsgd_gradient_sparse_f64", "dsgd_async_step_sparse", "dsgd_async_step_sparse_f64",
     "dsgd_load_csr_f64", "dsgd_value_bits",
     "dsgd_sync_steps_f64",
+    "dsgd_comm_init_f64v",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -97,6 +98,8 @@ def load():
             raise
         if name not in ("dsgd_last_error", "dsgd_grad_kernel_name"):
             fn.restype = C.c_int
+    if hasattr(lib, "dsgd_comm_init_f64v"):
+        lib.dsgd_comm_init_f64v.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32]
     _lib = lib
     return lib
 

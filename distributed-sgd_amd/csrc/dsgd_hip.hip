@@ -501,11 +501,15 @@ struct dsgd_ctx {
   int rp64_k = 0;
   DevBuf<double> d_rp64_s;
   DevBuf<double> d_rp64_g;
-  // ... across ranks (dsgd_comm_init_f64): the gather buffer ([world, padded][rp64_gk][rp64_gstride], zero between calls), the
-  // list ranges its header kernel writes for the finish, and the pinned words the ranks' worker counts are read into
+  // ... across ranks (dsgd_comm_init_f64, dsgd_comm_init_f64v): the gather buffer ([world, padded][rp64_gk][rp64_gwords]
+  // [rp64_gstride], zero between calls; csrc/dsgd_rp64_gather.hpp), the list ranges its header kernel writes for the finish,
+  // the pinned words the ranks' worker counts and value types are read into, and whether the communicator was attached
+  // through dsgd_comm_init_f64v (Double data accepted)
   DevBuf<unsigned long long> d_rp64_gath;
   long long rp64_gstride = 0;
   int rp64_gk = 0;
+  int rp64_gwords = 0;
+  bool comm_v64 = false;
   DevBuf<WorkSeg> d_rp64_gsegs;
   HostBuf<unsigned long long> h_rp64_ranks;
   // Double feature values (dsgd_load_csr_f64; csrc/dsgd_rp64.hpp): the values parallel to d_col / d_val (which holds them
@@ -3317,7 +3321,7 @@ static int load_csr_impl(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in,
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(bind(c));
   DSGD_TRY(require_sync_mode(c));   // the persistent engine reads the matrix that would be freed here
-  if (val64 && c->comm)
+  if (val64 && c->comm && !c->comm_v64)
     return fail(DSGD_EUNSUPPORTED, "dsgd_load_csr_f64 is not available while a communicator is attached (the gather's slots hold one "
                                    "word per column; the data and the weights are unchanged)");
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -4757,56 +4761,65 @@ static int rp64_ensure(dsgd_ctx* c, int n_workers) {
   }
   return DSGD_OK;
 }
-// ---- ... across ranks (a communicator attached with dsgd_comm_init_f64; csrc/dsgd_rp64.hpp "across ranks") ----
+// ---- ... across ranks (a communicator attached with dsgd_comm_init_f64 or dsgd_comm_init_f64v; csrc/dsgd_rp64_gather.hpp) ----
 static long long rp64_gather_pad(int world) { return ((long long)world + 63) & ~63LL; }
 static void rp64_gather_drop(dsgd_ctx* c) {   // (after a failure half way: the next step starts from a zeroed buffer)
   (void)hipStreamSynchronize(c->stream);
   c->d_rp64_gath.reset();
   c->d_rp64_gsegs.reset();
   c->rp64_gk = 0;
+  c->rp64_gwords = 0;
 }
-static int rp64_gather_ensure(dsgd_ctx* c, int K) {
+// K slots of `words` planes each (1: float values, 2: Double values); a buffer of the other width is replaced
+static int rp64_gather_ensure(dsgd_ctx* c, int K, int words) {
   DSGD_TRY(c->h_rp64_ranks.reserve(64));
-  if (c->rp64_gk >= K && c->d_rp64_gath) return DSGD_OK;
+  if (c->rp64_gk >= K && c->rp64_gwords == words && c->d_rp64_gath) return DSGD_OK;
   rp64_gather_drop(c);
   const long long stride = rp64_gather_stride(c->dp);
-  const size_t words = (size_t)rp64_gather_pad(c->world) + (size_t)stride * (size_t)K;
-  DSGD_TRY(c->d_rp64_gath.alloc(words));
+  const size_t n_words = (size_t)rp64_gather_pad(c->world) + (size_t)rp64_gather_slot_words(c->dp, words) * (size_t)K;
+  DSGD_TRY(c->d_rp64_gath.alloc(n_words));
   DSGD_TRY(c->d_rp64_gsegs.alloc((size_t)K));
-  HIP_TRY(hipMemsetAsync(c->d_rp64_gath, 0, sizeof(unsigned long long) * words, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_rp64_gath, 0, sizeof(unsigned long long) * n_words, c->stream));
   c->rp64_gstride = stride;
   c->rp64_gk = K;
+  c->rp64_gwords = words;
   return DSGD_OK;
 }
 // Behind the gradient kernel: the ranks' words first -- every rank must have been called with the same number of hosted
-// workers, or the ranks would enqueue different numbers of messages and a collective that only some ranks join never
-// completes; this is the one host read of the step besides its statistics -- then the worker slots, one message each
-// (cut at RP64_MSG_WORDS), then the headers.  Returns with the finish still to launch.
+// workers on the same value type, or the ranks would enqueue different numbers of messages and a collective that only some
+// ranks join never completes; this is the one host read of the step besides its statistics -- then the worker slots, one
+// message per slot and plane (cut at RP64_MSG_WORDS), then the headers.  Returns with the finish still to launch.
 static int rp64_gather(dsgd_ctx* c, int k) {
-  const int W = c->world, K = k * W;
+  const int W = c->world, K = k * W, words = c->rp64_gwords;
+  const long long slot = c->rp64_gstride * words;
+  const unsigned long long mine = rp64_rank_word(k, words == 2);
   unsigned long long* slots = c->d_rp64_gath + rp64_gather_pad(W);
   int r = rccl::AllReduce(c->d_rp64_gath, c->d_rp64_gath, (size_t)W, rccl::kInt64, rccl::kSum, c->comm, c->stream);
   if (r) return fail(DSGD_ERCCL, "ncclAllReduce(hosted workers): %s", rccl::GetErrorString(r));
   HIP_TRY(hipMemcpyAsync(c->h_rp64_ranks, c->d_rp64_gath, sizeof(unsigned long long) * (size_t)W, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (int q = 0; q < W; ++q)
-    if (c->h_rp64_ranks[q] != (unsigned long long)k) {
+    if (c->h_rp64_ranks[q] != mine) {
       // nothing of this step has left the rank besides these words: its own slots and the words are zeroed again
+      const unsigned long long theirs = c->h_rp64_ranks[q];
       HIP_TRY(hipMemsetAsync(c->d_rp64_gath, 0, sizeof(unsigned long long) * (size_t)W, c->stream));
-      HIP_TRY(hipMemsetAsync(slots + (long long)c->rank * k * c->rp64_gstride, 0, sizeof(unsigned long long) * (size_t)k * (size_t)c->rp64_gstride,
-                             c->stream));
+      HIP_TRY(hipMemsetAsync(slots + (long long)c->rank * k * slot, 0, sizeof(unsigned long long) * (size_t)k * (size_t)slot, c->stream));
       HIP_TRY(hipStreamSynchronize(c->stream));
+      if (rp64_rank_word_v64(theirs) != (words == 2))
+        return fail(DSGD_EINVAL, "rank %d holds %s feature values, this rank (%d) %s ones: every rank of a step holds the same value "
+                                 "type (dsgd_load_csr / dsgd_load_csr_f64; the weights are unchanged)", q, rp64_rank_word_v64(theirs) ? "Double" : "float",
+                    c->rank, words == 2 ? "Double" : "float");
       return fail(DSGD_EINVAL, "rank %d was called with %llu hosted workers, this rank (%d) with %d: every rank of a step hosts the "
-                               "same number (the weights are unchanged)", q, c->h_rp64_ranks[q], c->rank, k);
+                               "same number (the weights are unchanged)", q, (unsigned long long)(unsigned int)rp64_rank_word_k(theirs), c->rank, k);
     }
-  for (int g = 0; g < K; ++g)
+  for (long long g = 0; g < (long long)K * words; ++g)   // (plane g % words of worker g / words)
     for (long long off = 0; off < c->rp64_gstride; off += RP64_MSG_WORDS) {
-      unsigned long long* at = slots + (long long)g * c->rp64_gstride + off;
+      unsigned long long* at = slots + g * c->rp64_gstride + off;
       const size_t n = (size_t)std::min<long long>(RP64_MSG_WORDS, c->rp64_gstride - off);
       r = rccl::AllReduce(at, at, n, rccl::kInt64, rccl::kSum, c->comm, c->stream);
-      if (r) return fail(DSGD_ERCCL, "ncclAllReduce(worker %d's sums): %s", g, rccl::GetErrorString(r));
+      if (r) return fail(DSGD_ERCCL, "ncclAllReduce(worker %lld's sums): %s", g / words, rccl::GetErrorString(r));
     }
-  hipLaunchKernelGGL(dsgd_rp64_header_kernel, dim3(1), dim3(RP64_THREADS), 0, c->stream, c->d_rp64_gath, W, slots, c->rp64_gstride, K, c->dp,
+  hipLaunchKernelGGL(dsgd_rp64_header_kernel, dim3(1), dim3(RP64_THREADS), 0, c->stream, c->d_rp64_gath, W, slots, slot, K, c->dp,
                      c->d_rp64_gsegs, c->d_sc);
   HIP_TRY(hipGetLastError());
   return DSGD_OK;
@@ -4862,7 +4875,7 @@ static dim3 rp64_finish_grid(dsgd_ctx* c) {
 // The two launches over the staged lists (c->cur_idx, c->d_segs), on the context's float or Double values (rp64_ensure
 // came first).  mode: RP64_GRADIENT (worker 0's gradient into d_rp64_g), RP64_STEP, RP64_ASYNC (one worker; Double data
 // only -- float data's asynchronous step is a column-slice plan; delta: key order, may be null).  gather: the step under
-// a communicator (float data only: Double data refuses one).
+// a communicator (rp64_gather_ensure came first, with one plane per slot on float values and two on Double ones).
 // The weights stay in whichever layout they are, slice-major between plan runs.  Double data can meet slice-major weights
 // too: plans are refused at their CREATION on Double data, but a plan made on float data outlives dsgd_load_csr_f64 (it
 // is laid out again for the new data and runs on the values rounded to float), and its run leaves the weights
@@ -4870,8 +4883,8 @@ static dim3 rp64_finish_grid(dsgd_ctx* c) {
 // either layout through rp64_at; tests/test_gpu_fp64_values.py takes that path.
 static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, int mode, double lr, double* delta, bool gather) {
   const bool v64 = c->d_val64 != nullptr;
-  if ((mode == RP64_ASYNC && !v64) || (gather && v64))   // (no such kernel; the entry points never ask)
-    return fail(DSGD_ESTATE, "internal: no row-parallel fp64 kernel for %s on %s values", gather ? "a gather" : "an asynchronous step",
+  if ((mode == RP64_ASYNC && !v64) || (gather && mode != RP64_STEP) || (gather && c->rp64_gwords != (v64 ? 2 : 1)))   // (no such kernel; the entry points never ask)
+    return fail(DSGD_ESTATE, "internal: no row-parallel fp64 kernel for %s on %s values", gather ? "this gather" : "an asynchronous step",
                 v64 ? "Double" : "float");
   const long long bpw = rp64_bpw(c, n_workers, max_items);
   Rp64Args a;
@@ -4881,14 +4894,20 @@ static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, int mode
   const dim3 fg = rp64_finish_grid(c);
   if (gather) {   // this rank's slots of the gather buffer; the finish over every rank's workers
     unsigned long long* slots = c->d_rp64_gath + rp64_gather_pad(c->world);
-    a.acc[0] = slots + (long long)c->rank * n_workers * c->rp64_gstride;
-    a.acc_stride = c->rp64_gstride;
+    const long long slot = c->rp64_gstride * c->rp64_gwords;
+    a.acc[0] = slots + (long long)c->rank * n_workers * slot;
+    a.acc[1] = v64 ? a.acc[0] + c->rp64_gstride : nullptr;   // (the LO plane, directly behind the HI plane)
+    a.acc_stride = slot;
     a.rank_word = c->d_rp64_gath + c->rank;
-    hipLaunchKernelGGL(dsgd_rp64_grad_gather_kernel, gg, th, 0, c->stream, view(c), a);
+    if (v64)
+      hipLaunchKernelGGL(dsgd_rp64v_grad_gather_kernel, gg, th, 0, c->stream, view64(c), a);
+    else
+      hipLaunchKernelGGL(dsgd_rp64_grad_gather_kernel, gg, th, 0, c->stream, view(c), a);
     HIP_TRY(hipGetLastError());
     DSGD_TRY(rp64_gather(c, n_workers));
     f.acc[0] = slots;
-    f.acc_stride = c->rp64_gstride;
+    f.acc[1] = v64 ? slots + c->rp64_gstride : nullptr;
+    f.acc_stride = slot;
     f.segs = c->d_rp64_gsegs;
     f.K = n_workers * c->world;
   } else if (v64) {
@@ -4915,7 +4934,8 @@ static int rp64_launch(dsgd_ctx* c, int n_workers, long long max_items, int mode
   HIP_TRY(hipGetLastError());
   return DSGD_OK;
 }
-// Double data loaded: what a resident plan or a communicator would need is refused (nothing changed, the context usable)
+// Double data loaded: what a resident plan or dsgd_comm_init_f64's communicator would need is refused (nothing changed, the
+// context usable; dsgd_comm_init_f64v attaches one whose gather slots hold both words)
 static int refuse_val64(dsgd_ctx* c, const char* what) {
   if (c->d_val64)
     return fail(DSGD_EUNSUPPORTED, "%s is not available on Double feature values (dsgd_load_csr_f64): the column-slice kernels hold "
@@ -4966,7 +4986,7 @@ static int sync_step64_ranks(dsgd_ctx* c, const int32_t* const* idx_per_worker, 
   if (n_workers > 0x7fffffff / c->world) return fail(DSGD_EINVAL, "n_workers * world overflows");
   DSGD_TRY(rp64_check_lists(c, idx_per_worker, n_per_worker, n_workers));
   DSGD_TRY(rp64_ensure(c, 1));   // (s and the request's gradient; the local accumulators are not used)
-  DSGD_TRY(rp64_gather_ensure(c, n_workers * c->world));
+  DSGD_TRY(rp64_gather_ensure(c, n_workers * c->world, c->d_val64 ? 2 : 1));
   DSGD_TRY(reset_counters(c));
   long long mx = 0, tot = 0;
   DSGD_TRY(stage_lists(c, idx_per_worker, n_per_worker, n_workers, &mx, &tot));
@@ -6052,12 +6072,13 @@ static int relayout(dsgd_ctx* c) {
   return prepare_layout(c);
 }
 
-int dsgd_comm_init_f64(dsgd_ctx* c, const char* unique_id, int32_t world_size, int32_t rank) {
+// dsgd_comm_init_f64 (v64 = false: refused on Double data) and dsgd_comm_init_f64v (Double data accepted, now and in later loads)
+static int comm_init_f64_impl(dsgd_ctx* c, const char* unique_id, int32_t world_size, int32_t rank, bool v64, const char* what) {
   DSGD_TRY(check_ctx(c));
   if (!unique_id || world_size < 1 || rank < 0 || rank >= world_size) return fail(DSGD_EINVAL, "bad communicator arguments");
   std::lock_guard<std::mutex> lk(c->mu);
-  DSGD_TRY(require_fp64(c, "dsgd_comm_init_f64"));
-  DSGD_TRY(refuse_val64(c, "dsgd_comm_init_f64"));
+  DSGD_TRY(require_fp64(c, what));
+  if (!v64) DSGD_TRY(refuse_val64(c, what));
   if (world_size > 64) return fail(DSGD_EUNSUPPORTED, "at most 64 ranks");
   if (!rccl::available()) return fail(DSGD_ERCCL, "librccl could not be loaded");
   const bool sliced = c->cs_w_G == CS64_G;
@@ -6070,6 +6091,7 @@ int dsgd_comm_init_f64(dsgd_ctx* c, const char* unique_id, int32_t world_size, i
   c->comm_broken = false;
   c->world = world_size;
   c->rank = rank;
+  c->comm_v64 = v64;
   // loaded data: ONE ranking and ONE vexp now, on every rank (data loaded later: at its first use, as in fp32)
   int rc = c->d_row_ptr ? relayout(c) : DSGD_OK;
   if (rc == DSGD_OK && sliced) rc = cs64_slice(c);   // (the weights back in the layout they were in)
@@ -6079,11 +6101,18 @@ int dsgd_comm_init_f64(dsgd_ctx* c, const char* unique_id, int32_t world_size, i
     (void)hipStreamSynchronize(c->stream);
     (void)rccl::CommDestroy(c->comm);
     c->comm = nullptr;
+    c->comm_v64 = false;
     c->world = 1;
     c->rank = 0;
     return fail(rc, "%s", msg);
   }
   return DSGD_OK;
+}
+int dsgd_comm_init_f64(dsgd_ctx* c, const char* unique_id, int32_t world_size, int32_t rank) {
+  return comm_init_f64_impl(c, unique_id, world_size, rank, false, "dsgd_comm_init_f64");
+}
+int dsgd_comm_init_f64v(dsgd_ctx* c, const char* unique_id, int32_t world_size, int32_t rank) {
+  return comm_init_f64_impl(c, unique_id, world_size, rank, true, "dsgd_comm_init_f64v");
 }
 
 int dsgd_comm_destroy(dsgd_ctx* c) {
@@ -6095,6 +6124,7 @@ int dsgd_comm_destroy(dsgd_ctx* c) {
   DSGD_TRY(brc);
   c->comm_broken = false;   // (an aborted communicator is gone already: the context may attach a new one)
   if (!c->comm) {
+    c->comm_v64 = false;
     c->world = 1;
     c->rank = 0;
     return DSGD_OK;
@@ -6102,6 +6132,7 @@ int dsgd_comm_destroy(dsgd_ctx* c) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   RCCL_TRY(rccl::CommDestroy(c->comm));
   c->comm = nullptr;
+  c->comm_v64 = false;
   c->world = 1;
   c->rank = 0;
   return DSGD_OK;

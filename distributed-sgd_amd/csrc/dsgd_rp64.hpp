@@ -17,11 +17,13 @@
 //                               orc_sync_step / orc_async_step, operation for operation; the accumulators are left zeroed
 //                               for the next call.
 // The kernels are thin wrappers with stable names: dsgd_rp64_grad_kernel, dsgd_rp64_grad_gather_kernel,
-// dsgd_rp64_finish_kernel<STEP> (float values), dsgd_rp64v_grad_kernel, dsgd_rp64v_finish_kernel<MODE> (Double values).
+// dsgd_rp64_finish_kernel<STEP> (float values), dsgd_rp64v_grad_kernel, dsgd_rp64v_grad_gather_kernel,
+// dsgd_rp64v_finish_kernel<MODE> (Double values).
 //
-// Under a communicator (dsgd_comm_init_f64; "across ranks" below; float values only) the sums go into this rank's slots of a
-// gather buffer (GATHER), the buffer travels, dsgd_rp64_header_kernel turns the gathered headers into the finish's list
-// ranges, and dsgd_rp64_finish_kernel<true> folds every rank's workers.
+// Under a communicator ("across ranks" below: dsgd_comm_init_f64 on float values, dsgd_comm_init_f64v on either type) the
+// sums go into this rank's slots of a gather buffer (GATHER: dsgd_rp64_grad_gather_kernel, dsgd_rp64v_grad_gather_kernel),
+// the buffer travels, dsgd_rp64_header_kernel turns the gathered headers into the finish's list ranges, and the SAME finish
+// as without a communicator (dsgd_rp64_finish_kernel<true>, dsgd_rp64v_finish_kernel<RP64_STEP>) folds every rank's workers.
 //
 // The grid.  A worker's list of n rows (duplicates count) adds entries of |x| <= 2^vexp.  With S = 62 - ceil(log2 n) and
 // v = +-x * 2^(S - vexp) (a power of two: exact) an entry becomes Rp64Acc<V>::WORDS 64-bit integers, and no column sum of n
@@ -45,6 +47,7 @@
 // dsgd_cs64.hpp.
 #pragma once
 #include "dsgd_round128.hpp"
+#include "dsgd_rp64_gather.hpp"
 
 constexpr int RP64_THREADS = 256;
 constexpr int RP64_GROUP = 16;   // lanes per row (row_dot64<16>)
@@ -60,18 +63,9 @@ __host__ __device__ constexpr int rp64_ceil_log2(long long n) {
 }
 __host__ __device__ constexpr int rp64_shift(long long n) { return 62 - rp64_ceil_log2(n); }
 
-// ---- across ranks (a communicator attached with dsgd_comm_init_f64) ----
-// The gather buffer of a step of k hosted workers in a world of W ranks, K = k * W, 64-bit words, zero between calls:
-//   [W (padded to 64)]   one word per rank: the k it was called with (the ranks must agree before the slots travel)
-//   [K][stride]          global worker r * k + j's slot: [0, dp) its fixed-point column sums, rank order, then its header
-//                        words -- the list length n (its shift is 62 - ceil(log2 n)) and its active count
-// A slot is non-zero on exactly ONE rank, so ncclAllReduce(ncclInt64, ncclSum) over the buffer IS the all-gather: exact,
-// whatever the order of the sum.  Behind it every rank holds every worker's integers and folds them in worker order with
-// dsgd_rp64_finish_kernel<true> itself -- the bits of ONE process that hosts the K workers.
-constexpr int RP64_HDR_N = 0, RP64_HDR_ACTIVE = 1, RP64_HDR_WORDS = 2;
-// one message of the gather: at most 1 MiB (a slot is 378 KB at RCV1's D; wider slots are cut)
-constexpr long long RP64_MSG_WORDS = (1LL << 20) / (long long)sizeof(unsigned long long);
-__host__ __device__ constexpr long long rp64_gather_stride(int dp) { return ((long long)dp + RP64_HDR_WORDS + 63) & ~63LL; }
+// ---- across ranks (a communicator attached with dsgd_comm_init_f64 or dsgd_comm_init_f64v) ----
+// The gather buffer's layout -- the ranks' words, then per global worker a slot of one plane (float values) or two (Double
+// values: HI with the header words, LO behind it) -- its message size and the rank word's encoding: dsgd_rp64_gather.hpp.
 
 // ---- the accumulator policy: how one entry becomes integer words, and how the words' sums become ONE double ----
 template <typename V>
@@ -118,16 +112,18 @@ struct Rp64Args {
   double lambda;
   double* s_out;                   // s = lambda * 2.0 * (w . ds)
   DevScalars* sc;                  // n_active, err (1: a row index outside the data)
-  unsigned long long* rank_word;   // (the gather of a communicator only) this rank's word of the gather buffer: K
+  unsigned long long* rank_word;   // (the gather of a communicator only) this rank's word of the gather buffer: K and the value type
 };
 
-// GATHER: `acc[0]` are this rank's K slots of a communicator's gather buffer (see above: one word per column) -- a slot's
-// header words get the list length and the active count, the rank's word gets K, all with ordinary stores / vector atomics
+// GATHER: `acc[i]` are the planes of this rank's K slots of a communicator's gather buffer (dsgd_rp64_gather.hpp: one plane
+// per word of a column sum, acc[1] = acc[0] + the plane's stride, acc_stride the slot's) -- the header words behind plane 0's
+// sums get the list length and the active count, the rank's word gets K and the value type, all with ordinary stores /
+// vector atomics
 template <typename V, bool GATHER>
 __device__ __forceinline__ void rp64_grad_body(const CsrViewT<V>& m, const Rp64Args& a) {
 #pragma clang fp contract(off)
   constexpr int WORDS = Rp64Acc<V>::WORDS;
-  static_assert(!GATHER || WORDS == 1, "a gather slot holds one word per column");
+  static_assert(WORDS <= RP64_MAX_WORDS, "a gather slot holds one plane per word of a column sum");
   __shared__ double red[RP64_THREADS / 64];
   __shared__ unsigned int n_act;
   __shared__ unsigned long long hot[WORDS][RP64_HOT];
@@ -143,7 +139,7 @@ __device__ __forceinline__ void rp64_grad_body(const CsrViewT<V>& m, const Rp64A
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
     if (tid == 0) *a.s_out = a.lambda * 2.0 * ((red[0] + red[1]) + (red[2] + red[3]));   // ref: core/ml/SparseSVM.scala:31
-    if (GATHER && tid == 0) *a.rank_word = (unsigned long long)a.K;
+    if (GATHER && tid == 0) *a.rank_word = rp64_rank_word(a.K, WORDS == 2);
     return;
   }
   const int k = (int)((long long)blockIdx.x / a.blocks_per_worker);
@@ -210,6 +206,7 @@ __device__ __forceinline__ void rp64_grad_body(const CsrViewT<V>& m, const Rp64A
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_kernel(CsrView m, Rp64Args a) { rp64_grad_body<float, false>(m, a); }
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_gather_kernel(CsrView m, Rp64Args a) { rp64_grad_body<float, true>(m, a); }
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_grad_kernel(CsrView64 m, Rp64Args a) { rp64_grad_body<double, false>(m, a); }
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_grad_gather_kernel(CsrView64 m, Rp64Args a) { rp64_grad_body<double, true>(m, a); }
 
 struct Rp64FinishArgs {
   unsigned long long* acc[RP64_MAX_WORDS];   // per word [K][acc_stride], zeroed here
@@ -287,7 +284,8 @@ __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_finish_kernel(Rp64Fin
 
 // Behind the gather, ONE workgroup: the K headers become the list ranges the finish takes its shifts from ({0, n}), the
 // job's samples and active rows go to the context's scalars, and the header and rank words are zeroed again (the
-// finish zeroes the sums: the whole buffer is zero for the next call)
+// finish zeroes the sums: the whole buffer is zero for the next call).  `stride` is the SLOT's: with two planes per slot
+// (Double values) twice the plane's -- the headers are plane 0's, plane 1 has no word outside its sums.
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_header_kernel(unsigned long long* rank_words, int W, unsigned long long* slots,
                                                                         long long stride, int K, int dp, WorkSeg* segs, DevScalars* sc) {
   __shared__ unsigned long long tot[2];

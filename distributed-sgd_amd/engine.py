@@ -509,6 +509,15 @@ class Engine:
             raise ValueError("unique id must be %d bytes" % _lib.UNIQUE_ID_BYTES)
         check(self._lib.dsgd_comm_init_f64(self._ctx, C.c_char_p(unique_id), C.c_int32(world_size), C.c_int32(rank)))
 
+    def comm_init_f64v(self, unique_id, world_size, rank):
+        """comm_init_f64 for Double feature values (dsgd_comm_init_f64v): the same communicator, accepted with doubles loaded
+        (load_csr of a float64 array) and accepting that load while attached; sync_step_f64 on Double data gathers both words
+        of every column sum, so the replicas hold the bits of ONE context over all the rows as doubles.  Float data: exactly
+        comm_init_f64."""
+        if len(unique_id) != _lib.UNIQUE_ID_BYTES:
+            raise ValueError("unique id must be %d bytes" % _lib.UNIQUE_ID_BYTES)
+        check(self._lib.dsgd_comm_init_f64v(self._ctx, C.c_char_p(unique_id), C.c_int32(world_size), C.c_int32(rank)))
+
     def comm_destroy(self):
         check(self._lib.dsgd_comm_destroy(self._ctx))
 

@@ -109,7 +109,8 @@ enum {
  *   on the float values as they are.  Data whose |x| spread over more than the exact range should be scaled per column,
  *   or cosine-normalised as the reference's loader does, before it is loaded.  The limits and refusals
  *   above are unchanged: dsgd_gradient, dsgd_sync_step_ranges and plans beyond them still return DSGD_EUNSUPPORTED.
- *   ACROSS RANKS (dsgd_comm_init_f64, declared with the multi-GPU entry points; one process per GPU).
+ *   ACROSS RANKS (dsgd_comm_init_f64 on float feature values, dsgd_comm_init_f64v on float or Double ones; declared with
+ *   the multi-GPU entry points; one process per GPU).
  *   World W ranks, each an fp64 context with its own rows, every rank calling with the same number k of hosted workers:
  *   a step is orc_sync_step over K = k * W workers in rank-major order (worker j of rank r is global worker r * k + j).
  *   Every worker's exact 64-bit column sums, its list length and its active count are gathered on every rank -- an
@@ -130,6 +131,17 @@ enum {
  *   - dsgd_plan_create / _n / _from_seed, dsgd_plan_run / _f64 / _async_f64, dsgd_async_plan_create and
  *     dsgd_async_step_f64 return DSGD_EUNSUPPORTED and change nothing: the persistent column-slice kernel cannot hold a
  *     collective.  (host.MasterSync.fit falls back from a refused plan to one dsgd_sync_step_f64 per step.)
+ *   DOUBLE FEATURE VALUES ACROSS RANKS: a communicator attached with dsgd_comm_init_f64v is dsgd_comm_init_f64's in every
+ *   rule above, and also (1) attaches with Double data loaded, (2) accepts dsgd_load_csr_f64 while attached -- the load is
+ *   collective as dsgd_load_csr is: ranking and vexp are agreed at the rows' first use -- and (3) on Double data
+ *   dsgd_sync_step_f64 / dsgd_sync_step gather BOTH words of every column sum (below): a worker's slot is two planes, HI
+ *   with the header words and LO, one message per slot and plane, and every rank folds the K workers with the single
+ *   context's Double finish -- bit for bit ONE context that holds all the rows as doubles.  A Double step moves K * 2 *
+ *   (D + 3) * 8 bytes (each plane rounded up to 512): twice the float step's, the cost of the equality; LO planes are not
+ *   elided.  The word that carries a rank's n_workers carries its value type too: ranks that disagree on either all get
+ *   DSGD_EINVAL, weights unchanged, and the next matched step works.  Float data on every rank takes the one-word gather,
+ *   bit for bit dsgd_comm_init_f64's.  dsgd_loss_acc on Double data gives the job's tallies on every rank;
+ *   dsgd_sync_steps_f64, plans and dsgd_async_step_f64 stay refused as under dsgd_comm_init_f64.
  *   Without a communicator nothing changes.  Real RCCL with more than one rank has not run; no multi-GPU speed is claimed.
  *   DOUBLE FEATURE VALUES (dsgd_load_csr_f64; csrc/dsgd_rp64.hpp).  The reference reads `elems(1).toDouble`
  *   (utils/Dataset.scala:30); dsgd_load_csr takes floats, which moves every value of a real data file by up to 6e-8
@@ -151,7 +163,8 @@ enum {
  *   float holds exactly, inside the float grid's range, give the bits of the float-data call.
  *   Refused on Double data with DSGD_EUNSUPPORTED, nothing changed, the context usable: dsgd_plan_create / _n /
  *   _from_seed and dsgd_async_plan_create (the column-slice kernels hold 16 float values per slot in registers),
- *   dsgd_comm_init_f64, and dsgd_load_csr_f64 while a communicator is attached (the gather's slots would double).
+ *   dsgd_comm_init_f64, and dsgd_load_csr_f64 while a communicator of dsgd_comm_init_f64 is attached (its gather slots hold
+ *   one word per column; dsgd_comm_init_f64v attaches the communicator that serves Double data: "ACROSS RANKS").
  *   host.MasterSync.fit falls back from the refused plan to dsgd_sync_step_f64 on host-drawn lists; host.MasterAsync.fit
  *   needs resident asynchronous plans and raises on Double data.
  *   AN EPOCH'S STEPS IN ONE CALL (dsgd_sync_steps_f64, declared with the synchronous path below; csrc/dsgd_rp64.hpp).
@@ -522,6 +535,10 @@ int dsgd_comm_destroy(dsgd_ctx* ctx);
  * loaded, or not yet).  Loaded rows are ranked again here, from the column counts summed over the ranks, and the ranks
  * agree on vexp; rows loaded later at their first use, as in fp32.  dsgd_comm_destroy detaches.                      */
 int dsgd_comm_init_f64(dsgd_ctx* ctx, const char* unique_id, int32_t world_size, int32_t rank);
+/* dsgd_comm_init_f64 for Double feature values ("ACROSS RANKS", Double feature values across ranks): the same call and the
+ * same communicator, accepted with dsgd_load_csr_f64's data loaded and accepting that load while attached; steps on Double
+ * data gather both words of the column sums.  On float data everything is dsgd_comm_init_f64's, bit for bit.          */
+int dsgd_comm_init_f64v(dsgd_ctx* ctx, const char* unique_id, int32_t world_size, int32_t rank);
 
 /* ---- several GPUs driven by ONE host thread --------------------------------------------------------------------
  * The reference's dev role runs the master and every slave in ONE JVM (Main.scala:144-158); SURVEY.md 8(b) lists the

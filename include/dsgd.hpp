@@ -189,6 +189,14 @@ class SparseSVM {
     check(dsgd_value_bits(ctx_, &bits));
     return bits;
   }
+  // one process per GPU in the fp64 mode, on float or Double feature values (include/dsgd.h "ACROSS RANKS"): uniqueId is
+  // dsgd_comm_unique_id's DSGD_UNIQUE_ID_BYTES bytes from rank 0; dsgd_sync_step_f64 then steps over nWorkers x worldSize
+  // workers and the replicas keep the bits of one context over all the rows.  commDestroy detaches.
+  void commInitF64v(const std::vector<char>& uniqueId, int worldSize, int rank) {
+    if (uniqueId.size() != (size_t)DSGD_UNIQUE_ID_BYTES) throw std::invalid_argument("uniqueId must hold DSGD_UNIQUE_ID_BYTES bytes");
+    check(dsgd_comm_init_f64v(ctx_, uniqueId.data(), worldSize, rank));
+  }
+  void commDestroy() { check(dsgd_comm_destroy(ctx_)); }
   // an epoch's steps of the fp64 mode in ONE call (include/dsgd.h "AN EPOCH'S STEPS IN ONE CALL"): idx = every list
   // concatenated (step-major, worker-minor), offsets = nSteps * nWorkers + 1 prefix offsets; the bits of one
   // dsgd_sync_step_f64 per step.  Returns the steps' totals; activePerStep (may be null) gets one count per step.

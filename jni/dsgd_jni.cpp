@@ -770,6 +770,20 @@ JNIEXPORT void JNICALL NATIVE(commInitF64)(JNIEnv* env, jobject, jlong h, jbyteA
   if (rc) raise(env, rc);
 }
 
+// ... on Double feature values too (loadCsrF64): the communicator whose gather carries both words of every column sum
+JNIEXPORT void JNICALL NATIVE(commInitF64v)(JNIEnv* env, jobject, jlong h, jbyteArray uniqueId, jint worldSize, jint rank) {
+  if (!uniqueId || env->GetArrayLength(uniqueId) != DSGD_UNIQUE_ID_BYTES) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "uniqueId: the DSGD_UNIQUE_ID_BYTES (128) bytes of commUniqueId");
+    return;
+  }
+  int rc;
+  {
+    ByteElems id(env, uniqueId, JNI_ABORT);
+    rc = dsgd_comm_init_f64v(ctx(h), reinterpret_cast<const char*>(id.p), worldSize, rank);
+  }
+  if (rc) raise(env, rc);
+}
+
 JNIEXPORT void JNICALL NATIVE(commDestroy)(JNIEnv* env, jobject, jlong h) {
   int rc = dsgd_comm_destroy(ctx(h));
   if (rc) raise(env, rc);

@@ -78,6 +78,8 @@ object NativeSVM {
   // its fp64 context with it -- from then on syncStep / lossAcc span the ranks, bit for bit one process over all the rows
   @native def commUniqueId(idOut: Array[Byte]): Unit
   @native def commInitF64(ctx: Long, uniqueId: Array[Byte], worldSize: Int, rank: Int): Unit
+  // the same on Double feature values (loadCsrF64): both words of every column sum travel; float data: exactly commInitF64
+  @native def commInitF64v(ctx: Long, uniqueId: Array[Byte], worldSize: Int, rank: Int): Unit
   @native def commDestroy(ctx: Long): Unit
   // several GPUs driven by ONE thread of this JVM (dev role: master + every slave in one JVM, Main.scala:144-158): one
   // context per device, rank i = ctxs(i); arrays over workers are context-major (include/dsgd.h, dsgd_*_devices)
@@ -145,6 +147,15 @@ class HipSVM(lambda: Number, dimSparsity: Vec, data: Array[(Vec, Int)], nTrain: 
     else NativeSVM.loadCsr(ctx, rowPtr, cols.result(), vals.result().map(_.toFloat), labels)
     NativeSVM.buildDimSparsity(ctx, nTrain)
   }
+
+  /** one process per GPU (INTEGRATION.md 3b): this worker's context joins the job's communicator -- `uniqueId` is rank 0's
+    * NativeSVM.commUniqueId, handed over any host channel.  An fp64 context always holds Doubles (loadCsrF64 above), so it
+    * attaches through commInitF64v; from then on syncStep / lossAcc span the ranks, bit for bit one process over all rows. */
+  def attachRanks(uniqueId: Array[Byte], worldSize: Int, rank: Int): Unit = {
+    require(fp64, "a communicator across processes needs -Ddsgd.precision=fp64")
+    NativeSVM.commInitF64v(ctx, uniqueId, worldSize, rank)
+  }
+  def detachRanks(): Unit = NativeSVM.commDestroy(ctx)
 
   /** body of SlaveImpl.gradient (core/Slave.scala:142-157) */
   def gradientBatch(w: Vec, samplesIdx: Seq[Int]): Vec = {

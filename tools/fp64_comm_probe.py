@@ -1,14 +1,20 @@
-"""What a communicator costs the fp64 mode's synchronous step (dsgd_comm_init_f64; csrc/dsgd_rp64.hpp "across ranks").
+"""What a communicator costs the fp64 mode's synchronous step (dsgd_comm_init_f64, dsgd_comm_init_f64v; csrc/dsgd_rp64.hpp
+"across ranks").
 
 One GPU run, one JSON line, over N = 23,149 synthetic RCV1-like rows (80 % train): us per call of sync_step_f64 for
 3 x 100, 4 x 200 and one whole split (3 workers' splits of 6,173 rows),
   no_comm_us   without a communicator (the two row-parallel launches)
   world1_us    with real RCCL attached at world = 1: the gradient, 1 + K all-reduces of 64-bit integers, the headers, the
                finish -- RCCL's launches dominate it
+and, on DOUBLE feature values (the same rows with full 53-bit mantissas; 3 x 100 and 4 x 200),
+  f64v_double_us   real RCCL at world = 1 attached with dsgd_comm_init_f64v: two planes per slot, 1 + 2 K all-reduces
+  f64_float_us     the same data rounded to float under dsgd_comm_init_f64: one plane per slot, 1 + K all-reduces
+(--skip-double leaves that leg out: a library from before dsgd_comm_init_f64v, selected with DSGD_LIB_PATH for an A/B of the
+calls that did not change)
 (median over --reps calls, after one warm-up call).  RCCL may print its version banner first: the JSON is the last line.  Two ranks on one device run through the tests' stand-in only, which
 stages through host memory: no timing of those is meaningful, none is taken.
 
-    python tools/fp64_comm_probe.py [--rows 23149] [--reps 50]
+    python tools/fp64_comm_probe.py [--rows 23149] [--reps 50] [--skip-double]
 """
 import argparse
 import json
@@ -25,6 +31,7 @@ from dsgd_amd import host
 ap = argparse.ArgumentParser()
 ap.add_argument("--rows", type=int, default=23149)
 ap.add_argument("--reps", type=int, default=50)
+ap.add_argument("--skip-double", action="store_true")
 a = ap.parse_args()
 
 LAM, LR = 1e-5, 0.5
@@ -33,11 +40,14 @@ n_train = int(a.rows * 0.8)
 rng = np.random.default_rng(0)
 
 
-def engine(attach):
+val64 = data.val.astype(np.float64) * (1.0 + np.random.default_rng(1).random(len(data.val)) * 2.0 ** -20)   # no float holds these
+
+
+def engine(attach, val=None, v=False):
     eng = dsgd_amd.Engine(data.dim, LAM, precision="fp64")
-    eng.load_csr(data.row_ptr, data.col, data.val, data.label)
+    eng.load_csr(data.row_ptr, data.col, data.val if val is None else val, data.label)
     if attach:
-        eng.comm_init_f64(dsgd_amd.Engine.comm_unique_id(), 1, 0)
+        (eng.comm_init_f64v if v else eng.comm_init_f64)(dsgd_amd.Engine.comm_unique_id(), 1, 0)
     eng.build_dim_sparsity(n_train)
     return eng
 
@@ -63,5 +73,14 @@ for key, attach in (("no_comm_us", False), ("world1_us", True)):
             eng.set_weights(np.zeros(data.dim + 1))
             out["sync_step"][name][key] = median_us(lambda: eng.sync_step_f64(lists, LR), a.reps)
         if attach:
+            eng.comm_destroy()
+if not a.skip_double:
+    out["sync_step_double"] = {name: {} for name, _ in cases[:2]}
+    for key, val, v in (("f64v_double_us", val64, True), ("f64_float_us", val64.astype(np.float32), False)):
+        with engine(True, val, v) as eng:
+            assert eng.value_bits() == (64 if v else 32)
+            for name, lists in cases[:2]:
+                eng.set_weights(np.zeros(data.dim + 1))
+                out["sync_step_double"][name][key] = median_us(lambda: eng.sync_step_f64(lists, LR), a.reps)
             eng.comm_destroy()
 print(json.dumps(out))
