@@ -305,7 +305,8 @@ struct dsgd_ctx {
   DevBuf<float> d_ds;
   DevBuf<float> d_g;  // workers x dp
   DevBuf<long long> d_g64;  // workers x dp fixed-point accumulators of the streaming kernel (zero between steps)
-  float fix_scale = 4194304.0f;  // 2^FIX_SHIFT / vmax2
+  float fix_scale = 4194304.0f;  // 2^cold_shift / vmax2
+  int cold_shift = FIX_SHIFT;    // shift of the cold columns' words: FIX_SHIFT unless the data's cold tiles need less (build_split)
   int vexp = 0;                  // vmax2 = 2^vexp >= max |value|
   int last_shift = FIX_SHIFT;    // shift of the last gradient launch (streaming kernels or index-list kernel)
   std::vector<StreamSeg> bound_segs;   // split layout: the (ranges, grid) configuration bound_shift was measured for
@@ -992,7 +993,7 @@ static int launch_grad_vt(dsgd_ctx* c, dsgd_plan* p, long long step) {
   const int H = std::min(c->hsplit, c->dp);
   const int gx = p->vt_grid[(size_t)step], shift = p->vt_shift[(size_t)step];
   DSGD_TRY(ensure_part(c, c->d_part, &c->part_wgs, &c->part_stride, (long long)gx * p->n_workers, H));
-  c->last_shift = shift;
+  c->last_shift = std::min(shift, c->cold_shift);   // (the cold lanes add at the cold scale)
   VtArgs a;
   a.hcol = c->d_hcol;
   a.hval = c->d_hval;
@@ -2073,6 +2074,27 @@ static int build_split(dsgd_ctx* c) {
   HIP_TRY(hipMemcpy(c->d_ctiles, hc.wt.data(), sizeof(WTile) * hc.wt.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->d_cmeta, hc.meta16.data(), sizeof(unsigned short) * hc.meta16.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  // The cold words' scale.  A word is emptied by whoever sees it at 2^28; until then sixteen waves can each add the rest of
+  // a tile, at most 2 A at shift 21 (dsgd_cold_bound_kernel).  The finest s <= 21 with
+  // 2^28 + 2^s + 32 * (2^(s - 21) A + 256) < 2^30 keeps every word below the band the kernels refuse (+ 256: half a unit
+  // of rounding for each of a tile's 512 slots).  RCV1-like data has A of a few values: s = 21.
+  c->cold_shift = FIX_SHIFT;
+  if (c->n_ctiles > 0 && c->coldm_nnz > 0) {
+    DSGD_TRY(c->d_bound.reserve(1));
+    HIP_TRY(hipMemsetAsync(c->d_bound, 0, sizeof(unsigned int), c->stream));
+    const int blocks = (int)std::max<long long>(1, std::min<long long>((c->n_ctiles + 3) / 4, (long long)c->n_cu * 32));
+    hipLaunchKernelGGL(dsgd_cold_bound_kernel, dim3(blocks), dim3(CB_THREADS), 0, c->stream, c->d_ctiles, c->n_ctiles,
+                       (const void*)c->d_ccol, c->cold_col16 ? 1 : 0, c->d_cval, c->coldm_nnz + WS_PAD,
+                       std::ldexp(1.0f, FIX_SHIFT - c->vexp), c->d_bound);
+    HIP_TRY(hipGetLastError());
+    unsigned int amax = 0;
+    HIP_TRY(hipMemcpyAsync(&amax, c->d_bound, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int s = FIX_SHIFT;
+    while (s > 1 && (double)(1LL << 28) + std::ldexp(1.0, s) + 32.0 * (std::ldexp((double)amax, s - FIX_SHIFT) + 256.0) >= (double)(1LL << 30)) --s;
+    c->cold_shift = s;
+  }
+  c->fix_scale = std::ldexp(1.0f, c->cold_shift - c->vexp);
   return DSGD_OK;
 }
 
@@ -2147,7 +2169,7 @@ static int vexp_collective(dsgd_ctx* c) {
   if (r) return fail(DSGD_ERCCL, "ncclAllReduce(vexp): %s", rccl::GetErrorString(r));
   if (e != hipSuccess) return fail(DSGD_EHIP, "vexp: %s", hipGetErrorString(e));
   c->vexp = (int)*std::max_element(v.begin(), v.end());
-  c->fix_scale = std::ldexp(1.0f, FIX_SHIFT - c->vexp);
+  c->fix_scale = std::ldexp(1.0f, c->cold_shift - c->vexp);
   return DSGD_OK;
 }
 static int prepare_layout(dsgd_ctx* c) {
@@ -2330,7 +2352,7 @@ static int launch_stream(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs) {
       shift = c->bound_shift;
     }
     main_scale = std::ldexp(1.0f, shift - c->vexp);
-    c->last_shift = shift;
+    c->last_shift = cold ? std::min(shift, c->cold_shift) : shift;   // (the coarser of the two grids of this launch)
   }
   CsrView mh = view(c);
   mh.row_ptr = c->d_hrow_ptr;
@@ -2614,7 +2636,7 @@ static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
     shift = L->shift;
   }
   const float main_scale = std::ldexp(1.0f, shift - c->vexp);
-  c->last_shift = shift;
+  c->last_shift = std::min(shift, c->cold_shift);   // (the coarser of the two grids of this launch)
   CsrView mh = view(c);
   mh.row_ptr = c->d_hrow_ptr;
   mh.col = reinterpret_cast<const int*>(c->d_hcol.get());   // 16-bit ranks; the kernel reinterprets the pointer
@@ -3358,6 +3380,7 @@ static int load_csr_impl(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in,
     std::frexp(vmax > 0.0f ? vmax : 1.0f, &e);  // vmax = f * 2^e, f in [0.5, 1)  ->  vmax2 = 2^e >= vmax
     if (vmax > 0.0f && std::ldexp(1.0f, e - 1) == vmax) e -= 1;  // vmax itself a power of two
     c->vexp = e;   // vmax2 = 2^e
+    c->cold_shift = FIX_SHIFT;   // (until the layout of this data is built)
     c->fix_scale = std::ldexp(1.0f, FIX_SHIFT - e);
   }
   if (val64) {   // vexp from the largest |v| as a double (the same rule)

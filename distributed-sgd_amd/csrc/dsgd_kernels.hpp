@@ -1829,7 +1829,7 @@ __device__ __forceinline__ void cd_tile(const CRegs<COL16>& cur, float* strip, f
 }
 
 // cold gradient columns: q = round(value * coef[row] * scale) accumulated in the LDS tile of 32-bit integers at the
-// cold scale (shift 21) with returning atomics: whoever SEES |old| >= 2^28 moves the word into the 64-bit global
+// cold scale (shift <= 21: dsgd_cold_bound_kernel) with returning atomics: whoever SEES |old| >= 2^28 moves the word into the 64-bit global
 // accumulator, |old| >= 2^30 raises DevScalars::err (profiles/DESIGN_notes_r01-r05.md 3.5).  ref: core/Slave.scala:147-153 restricted to the
 // cold columns.
 template <bool COL16, bool WIDE>
@@ -1887,6 +1887,51 @@ __device__ __forceinline__ void cg_tile(const CRegs<COL16>& cur, float* strip, i
     }
   }
   __builtin_amdgcn_wave_barrier();
+}
+
+// ---- a data-dependent bound for the fixed-point scale of the COLD gradient words ---------------------------------
+// cg_tile's words are emptied by whoever SEES one at 2^28, so what a word can reach is 2^28 plus everything the sixteen
+// waves of a workgroup still add before that spill: each at most the rest of the tile it is in.  This kernel returns
+// A = the largest sum, over the cold tiles and their columns, of ceil(|x| * 2^21 / vmax2) (one wave per tile, every pair
+// of a tile's <= 512 slots compared in LDS; explicit zeros weigh nothing).  Any tile of <= CT_MAXROWS whole rows and <=
+// 512 slots -- the row chunks cut their own -- lies inside two consecutive tiles of this table, so no tile adds more than
+// 2 A to a word and the host (build_split) picks the finest cold shift s <= 21 with 2^28 + 2^s + 32 * (2^(s - 21) A + 256)
+// < 2^30: no lane can see a word at 2^30, whatever rows are active and whatever their signs.
+constexpr int CB_THREADS = 256;
+__global__ void __launch_bounds__(CB_THREADS) dsgd_cold_bound_kernel(const WTile* __restrict__ tiles, long long n_tiles,
+                                                                    const void* __restrict__ col, int col16,
+                                                                    const float* __restrict__ val, long long n_slots,
+                                                                    float scale21, unsigned int* __restrict__ out_max) {
+  __shared__ unsigned int ids[CB_THREADS / 64][WS_SLOTS];
+  __shared__ unsigned int wts[CB_THREADS / 64][WS_SLOTS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned int best = 0u;
+  for (long long t = (long long)blockIdx.x * (CB_THREADS / 64) + wave; t < n_tiles; t += (long long)gridDim.x * (CB_THREADS / 64)) {
+    const WTile T = tiles[t];
+    if ((int)(short)(T.info & 0xffff) <= 0 || T.pos0 < 0) continue;
+    int slots = (int)((unsigned int)T.info >> 16);
+    if (slots > WS_SLOTS) slots = WS_SLOTS;
+    for (int i = lane; i < slots; i += 64) {
+      const long long e = T.pos0 + i;
+      const bool in = e < n_slots;
+      ids[wave][i] = !in ? 0u
+                     : col16 ? (unsigned int)reinterpret_cast<const unsigned short*>(col)[e]
+                             : reinterpret_cast<const unsigned int*>(col)[e];
+      wts[wave][i] = in ? (unsigned int)ceilf(fabsf(val[e]) * scale21) : 0u;
+    }
+    __builtin_amdgcn_wave_barrier();   // (one wave writes and reads its own rows of the two arrays)
+    for (int i = lane; i < slots; i += 64) {
+      if (wts[wave][i] == 0u) continue;
+      const unsigned int id = ids[wave][i];
+      unsigned int sum = 0u;   // <= 512 * 2^21 = 2^30
+      for (int j = 0; j < slots; ++j) sum += ids[wave][j] == id ? wts[wave][j] : 0u;
+      best = max(best, sum);
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) best = max(best, (unsigned int)__shfl_xor((int)best, off, 64));
+  if (lane == 0 && best) atomicMax(out_max, best);
 }
 
 // GRAD = false: dsgd_cdot_kernel  (LDS: nc_lds cold weights at address 0, 16 strips)

@@ -17,6 +17,12 @@ what the trait planted.  Everything is deterministic from the seed.
                 row OFF if the product survived the filter of math/Sparse.scala:46; (c) rows supported only where w == 0.
   ragged64      the ragged recipe of the parity tests (ragged_data below: empty rows, one-element rows, a 1e-25 entry) plus rows of
                 3,000 and 8,000 entries.
+  concentrated  NOT the RCV1-like base: rows of 2 to 4 entries, column P in EVERY row with y * vmax and column M with
+                -y * vmax (every contribution y * x is +vmax / -vmax: the largest value of the data in one column of every
+                row with one sign), vmax = 1 (vexp's power-of-two branch) or the largest value below 2 (a contribution that
+                rounds UP to 2^shift).  With the weights at zero every row is active and the sums are n * vmax in closed form:
+                every integer accumulator of every family runs at the full scale its host rule allows (concentrated below,
+                and the host rules restated in Python beside it).
 """
 
 from __future__ import annotations
@@ -305,3 +311,213 @@ def lists_of(trait, name):
         rng = np.random.default_rng([SEED, TRAITS.index(trait) if trait in TRAITS else 99, list(LISTS).index(name)])
         _CACHE[key] = lists_with(rng, N_TRAIN, k, b, planted_rows(trait, build(trait), small=b <= 100))
     return _CACHE[key]
+
+
+# ---- concentrated columns: every accumulator at full scale --------------------------------------------------------------
+# Host rules of csrc/dsgd_hip.hip restated (tests/test_hard_data.py pins them on the CPU, tests/test_gpu_hard_values.py
+# holds the shift a launch REPORTS against them).
+WS_SLOTS, WS_MAXROWS, CT_MAXROWS, FIX_SHIFT_CAP, RP64_HOT, FSTEP_ROWS = 512, 254, 128, 21, 1024, 512
+HSPLIT_DEFAULT = 18000   # (any rank the concentrated data uses is far below the library's default split)
+N_CU = 256               # MI355X; the GPU tests pass the device's own count
+
+
+def ceil_log2(n):
+    b = 0
+    while (1 << b) < n:
+        b += 1
+    return b
+
+
+def shift_of_rows(rows, cap=None):
+    """the general rule: rows(b) <= 2^bits, shift = 30 - bits (capped where the launch caps it)"""
+    s = 30 - ceil_log2(rows)
+    return s if cap is None else max(1, min(cap, s))
+
+
+def refined_shift(shift0, a_max, rows, cap=FIX_SHIFT_CAP):
+    """dsgd_wseg_bound_kernel / dsgd_fstep_bound_kernel's host side: the finest s with 2^(s - s0) * A + rows <= 2^30"""
+    s = shift0
+    while s < cap and math.ldexp(float(a_max), s + 1 - shift0) <= float((1 << 30) - rows):
+        s += 1
+    return s
+
+
+def column_ranks(data):
+    """the library's ranking: count over ALL loaded rows descending, ties by ascending key -> rank_of_key [dim + 1]"""
+    cnt = np.bincount(data.col, minlength=data.dim + 1)
+    order = np.argsort(-cnt, kind="stable")
+    rank = np.empty(data.dim + 1, np.int64)
+    rank[order] = np.arange(data.dim + 1)
+    return rank
+
+
+def stream_slots(data, hsplit=HSPLIT_DEFAULT):
+    """slot offsets of the hot and the cold stream (build_split: a tiled row owns at least one slot in each)"""
+    hot_e = column_ranks(data)[data.col] < min(hsplit, data.dim + 1)
+    row_id = np.repeat(np.arange(data.n_rows), np.diff(data.row_ptr))
+    hot = np.bincount(row_id, weights=hot_e, minlength=data.n_rows).astype(np.int64)
+    cold = np.diff(data.row_ptr) - hot
+    assert hot.max() <= WS_SLOTS - 8 and cold.max() <= WS_SLOTS - 8   # (no long rows here)
+    hrp = np.concatenate([[0], np.cumsum(np.maximum(hot, 1))])
+    ctp = np.concatenate([[0], np.cumsum(np.maximum(cold, 1))])
+    return hrp, ctp
+
+
+def wave_tiles(slot_ptr, rb, re, max_rows=WS_MAXROWS):
+    """append_wave_tiles for rows without empty or long ones: the first row of every tile of [rb, re)"""
+    r0, start = [], -1
+    for i in range(rb, re):
+        if start >= 0 and (slot_ptr[i + 1] - (slot_ptr[start] & ~7) > WS_SLOTS - 1 or i - start >= max_rows):
+            start = -1
+        if start < 0:
+            start = i
+            r0.append(i)
+    return r0
+
+
+def streaming_worst_rows(data, ranges, n_cu=N_CU, hsplit=HSPLIT_DEFAULT):
+    """launch_stream: workgroup b of a worker owns the 16-tile groups b, b + grid.x, ...; the rows of a group are counted
+    between the first rows of tiles (the tiles cover ALL loaded rows)"""
+    import bisect
+
+    hrp, _ = stream_slots(data, hsplit)
+    wr0 = wave_tiles(hrp, 0, data.n_rows) + [data.n_rows]
+    spans = []
+    for lo, hi in ranges:
+        tb = max(0, bisect.bisect_right(wr0, lo, 0, len(wr0) - 1) - 1)
+        te = max(tb, bisect.bisect_left(wr0, hi, 0, len(wr0) - 1))
+        spans.append((tb, te))
+    per_worker = max(1, n_cu // len(ranges))
+    gx = max(1, min(per_worker, (max(max(te - tb for tb, te in spans), 1) + 15) // 16))
+    worst = 1
+    for tb, te in spans:
+        rows_of = [0] * gx
+        for g, t in enumerate(range(tb, te, 16)):
+            rows_of[g % gx] += wr0[min(t + 16, te)] - wr0[t]
+        worst = max(worst, max(rows_of))
+    return worst
+
+
+def chunk_worst_rows(data, ranges, n_cu=N_CU, hsplit=HSPLIT_DEFAULT, fstep_rows=FSTEP_ROWS):
+    """fstep_grid + fstep_build before any rebalance: n_wg chunks per worker of equal WEIGHT (slots of both streams + 2 per
+    row), cut at the first row whose weight prefix reaches the target; the largest chunk's rows"""
+    hrp, ctp = stream_slots(data, hsplit)
+    W = hrp + ctp + 2 * np.arange(data.n_rows + 1)
+    per_worker = max(1, n_cu // len(ranges))
+    n_wg = max(1, min(per_worker, min(hi - lo for lo, hi in ranges) // fstep_rows))
+    worst = 1
+    for lo, hi in ranges:
+        w0, wtot, cut = int(W[lo]), int(W[hi] - W[lo]), lo
+        for b in range(n_wg):
+            nxt = hi
+            if b + 1 < n_wg:
+                target = w0 + int(float(wtot) * float(b + 1) / float(n_wg))
+                nxt = cut + int(np.searchsorted(W[cut:hi + 1], target, side="left"))
+            worst = max(worst, nxt - cut)
+            cut = nxt
+    return worst, n_wg
+
+
+def cold_shift_rule(data, hsplit=HSPLIT_DEFAULT):
+    """build_split's scale of the cold words (dsgd_cold_bound_kernel): A = the largest column sum of ceil(|x| 2^21 / vmax2)
+    inside one cold tile; the finest s <= 21 with 2^28 + 2^s + 32 * (2^(s - 21) A + 256) < 2^30"""
+    rank = column_ranks(data)
+    h = min(hsplit, data.dim + 1)
+    _, ctp = stream_slots(data, hsplit)
+    r0 = wave_tiles(ctp, 0, data.n_rows, CT_MAXROWS) + [data.n_rows]
+    _, e = math.frexp(float(np.abs(data.val).max()))
+    vexp = e - 1 if float(np.abs(data.val).max()) == 2.0 ** (e - 1) else e
+    a = 0
+    for t in range(len(r0) - 1):
+        lo = int(ctp[r0[t]]) & ~7   # (the window starts at a multiple of 8 slots: up to 7 slots of the rows before count too)
+        first = int(np.searchsorted(ctp, lo, side="right")) - 1
+        b, e_ = int(data.row_ptr[first]), int(data.row_ptr[r0[t + 1]])
+        cold = rank[data.col[b:e_]] >= h
+        if cold.any():
+            q = np.ceil(np.abs(data.val[b:e_][cold].astype(np.float32)) * np.float32(2.0 ** (21 - vexp))).astype(np.int64)
+            a = max(a, int(np.bincount(data.col[b:e_][cold], weights=q).max()))
+    s = FIX_SHIFT_CAP
+    while s > 1 and 2 ** 28 + 2 ** s + 32 * (math.ldexp(a, s - 21) + 256) >= 2 ** 30:
+        s -= 1
+    return s, a
+
+
+VMAX = {"one": 1.0, "below2": float(np.float32(2.0) - np.float32(2.0 ** -23))}   # vexp 0 (power-of-two branch) / vexp 1
+VMAX64 = {"one": 1.0, "below2": 2.0 - 2.0 ** -52}                                 # the Double twins
+CONC_DIM, CONC_P, CONC_M, CONC_SEED, CONC_POOL = 47236, 7, 9, 17, 16384
+CONC_ORDINARY = np.arange(20, 26, dtype=np.int32)     # the third and fourth entries
+CONC_FILLER = np.arange(1000, 2200, dtype=np.int32)   # four tail rows of 300: 1,200 columns ranked before CONC_COLD
+CONC_COLD = CONC_DIM                                  # the duplicate list's column: count 1, the largest key
+CONC_RANGE_MIN = 8192   # tests/test_gpu_hard_values.py RANGE_FAMILIES: DSGD_STREAM_MIN (row_chunks start at 4,096)
+
+
+def _conc_rows(which, double):
+    """the pool of CONC_POOL candidate train rows: (row_ptr, col, val float64, label); the same shape and labels for both vmax"""
+    vmax = (VMAX64 if double else VMAX)[which]
+    rng = np.random.default_rng(CONC_SEED)
+    extra = rng.integers(0, 3, size=CONC_POOL)                  # 0, 1 or 2 ordinary entries
+    label = np.where(rng.random(CONC_POOL) < 0.5, 1, -1).astype(np.int8)
+    row_ptr = np.concatenate([[0], np.cumsum(2 + extra)]).astype(np.int64)
+    col = np.empty(row_ptr[-1], np.int32)
+    val = np.empty(row_ptr[-1], np.float64)
+    for i in range(CONC_POOL):
+        b, y = int(row_ptr[i]), float(label[i])
+        col[b], val[b], col[b + 1], val[b + 1] = CONC_P, y * vmax, CONC_M, -y * vmax
+        c = np.sort(rng.choice(CONC_ORDINARY, size=int(extra[i]), replace=False))
+        v = 0.25 * vmax * (1.0 - 0.999 * rng.random(len(c)))    # in (0, vmax / 4]
+        col[b + 2:b + 2 + len(c)] = c
+        val[b + 2:b + 2 + len(c)] = v if double else v.astype(np.float32)
+    return row_ptr, col, val, label
+
+
+def _conc_data(which, double, n_train):
+    """n_train pool rows, four filler rows and the duplicate list's row (its only full-scale entry in CONC_COLD)"""
+    vmax = (VMAX64 if double else VMAX)[which]
+    row_ptr, col, val, label = _conc_rows(which, double)
+    rng = np.random.default_rng(CONC_SEED + 1)
+    e = int(row_ptr[n_train])
+    cols, vals, lens, labels = [col[:e]], [val[:e]], [np.diff(row_ptr[:n_train + 1])], [label[:n_train]]
+    for part in CONC_FILLER.reshape(4, -1):
+        v = 0.25 * vmax * (1.0 - 0.999 * rng.random(len(part)))
+        cols.append(part); vals.append(v if double else v.astype(np.float32)); lens.append([len(part)]); labels.append([1])
+    cols.append(np.asarray([CONC_ORDINARY[0], CONC_COLD], np.int32)); vals.append(np.asarray([0.125 * vmax, -vmax]))
+    lens.append([2]); labels.append([-1])   # y * x = +vmax on CONC_COLD
+    val_all = np.concatenate(vals)
+    data = synth.Csr(CONC_DIM, np.concatenate([[0], np.cumsum(np.concatenate(lens))]).astype(np.int64), np.concatenate(cols).astype(np.int32),
+                     val_all if double else val_all.astype(np.float32), np.concatenate(labels).astype(np.int8))
+    return data
+
+
+def concentrated_rows():
+    """The smallest number of train rows (a multiple of 256, at least what the range families' dispatch needs) at which
+    BOTH the streaming launch and the row chunks get shift0 < 21 over the whole range: the worst workgroup's rows above 512,
+    by the 16-tile groups of launch_stream and the weight cut of fstep_build at 256 CUs."""
+    if "conc_rows" not in _CACHE:
+        n = CONC_RANGE_MIN
+        while True:
+            d = _conc_data("one", False, n)
+            if streaming_worst_rows(d, [(0, n)]) > 512 and chunk_worst_rows(d, [(0, n)])[0] > 512:
+                break
+            n += 256
+            assert n <= CONC_POOL
+        _CACHE["conc_rows"] = n
+    return _CACHE["conc_rows"]
+
+
+def concentrated(which, double=False):
+    """Hard: data (float32 values, or float64 for the Double twin), w = 0, planted = P, M, vmax, n_train, the row the
+    duplicate list names and its cold column"""
+    key = ("concentrated", which, double)
+    if key not in _CACHE:
+        n = concentrated_rows()
+        data = _conc_data(which, double, n)
+        _CACHE[key] = Hard(data, np.zeros(CONC_DIM + 1), {"P": CONC_P, "M": CONC_M, "vmax": (VMAX64 if double else VMAX)[which], "n_train": n,
+                                                          "dup_row": data.n_rows - 1, "cold_column": CONC_COLD})
+    return _CACHE[key]
+
+
+def conc_lists(n_train, k, b, seed=0):
+    """k lists of b DISTINCT train rows, one per contiguous split (k and b powers of two in the exact legs)"""
+    rng = np.random.default_rng([CONC_SEED, k, b, seed])
+    bounds = np.linspace(0, n_train, k + 1).astype(np.int64)
+    return [np.sort(rng.choice(np.arange(bounds[i], bounds[i + 1]), size=b, replace=False)).astype(np.int32) for i in range(k)]

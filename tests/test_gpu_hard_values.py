@@ -654,3 +654,352 @@ def test_fp64_two_ranks_with_different_vexp(tmp_path):
                 assert np.array_equal(bits(ranks[r]["w_hist"][i]), bits(w1)), "step %d: rank %d differs from the single context" % (i, r)
                 assert ranks[r]["stats"][i].tolist() == [st["n_samples"], st["n_active"]]
             assert 0 < st["n_active"] < st["n_samples"]
+
+
+# ---- concentrated columns: every integer accumulator at the full scale its host rule allows ------------------------------
+# tests/hard_data.py `concentrated`: column P holds y * vmax and column M holds -y * vmax in EVERY row, so from w = 0 (every
+# row active) a workgroup's word for P is rows * q(vmax) and for M its negative -- with vmax = 1 exactly rows * 2^shift,
+# with the largest float below 2 the same after rounding up.  Each leg reads the shift the launch reports and holds it
+# against the host rule restated in hard_data.py: a leg that finds slack FAILS.  A wrapped word is 2^32 grid units off;
+# nothing like that fits under the derived bound, and on vmax = 1 the two columns are asserted on BITS.
+#   step 1     w = 0: active == rows listed; w[P] = -lr * mean_k(n_k * vmax), w[M] = +that (powers of two: exact)
+#   steps 2-3  from the weights step 1 left, lambda = 1e-5.  Those weights classify every row with a margin (y * d =
+#              -2 lr n vmax^2 + ...), so both sides must find NO active row and leave the weights alone.
+#   step 4     from the NEGATED weights: every row active again at non-zero weights, the regulariser on a support that
+#              holds P and M.
+CONC_LR = 2.0 ** -12
+CONC_LIST_SHAPES = {   # family -> (workers, rows each): powers of two, each at the edge of its family's rule
+    "one_workgroup": ((1, 64),),
+    "row_wise": ((1, 4096), (2, 1024)),
+    "virtual_tiles": ((1, 4096), (2, 1024)),
+    "column_slices_host": ((1, 1024), (2, 512)),
+    "column_slices_device": ((1, 1024), (2, 512)),
+}
+CONC_MODES = {"default": {}, "hsplit1": {"DSGD_HSPLIT": "1"}, "bound_off": {"DSGD_FIX_BOUND": "0"}}
+
+
+def device_cus():
+    import torch
+
+    return int(torch.cuda.get_device_properties(0).multi_processor_count)
+
+
+def list_rows_per_workgroup(family, k, b, n_cu):
+    """the rows ONE accumulator word can meet, by the family's documented rule (rows of one lane each in the virtual tiles)"""
+    if family == "row_wise":     # launch_grad_mb
+        return max(64, -(-b // max(1, n_cu // k)))
+    if family == "virtual_tiles":   # vt_build: 64 rows a tile, workgroup g takes the 16-tile groups g, g + gx, ...
+        tiles = -(-b // 64)
+        gx = max(1, min(n_cu // k, -(-tiles // 16)))
+        rows_of = [0] * gx
+        for t in range(tiles):
+            rows_of[(t // 16) % gx] += min(64, b - 64 * t)
+        return max(rows_of)
+    return b   # one workgroup per list / one accumulator per worker and column
+
+
+def conc_pair(which, lam=LAM):
+    h = hd.concentrated(which)
+    o, eng = make_pair(h.data, lam, h.planted["n_train"])
+    return h, o, eng
+
+
+def conc_steps(o, eng, h, which, run, lists, lr, family, ranges):
+    """steps 1 to 4 of the header; returns the shift step 1 reported"""
+    p, m, vmax = h.planted["P"], h.planted["M"], h.planted["vmax"]
+    total = sum(len(a) for a in lists)
+    eng.set_weights(np.zeros(h.data.dim + 1, np.float32))
+    st, _ = hard_step(o, eng, "concentrated", h, run, lists, lr, family, ranges)
+    shift = eng.tuning_info()["fix_shift"]
+    assert st["n_active"] == total == o.last_stats["n_active"]
+    w1 = eng.get_weights()
+    mean = math.fsum(len(a) * vmax for a in lists) / len(lists)
+    if which == "one":
+        assert np.array_equal(bits(w1[[p, m]]), bits(np.asarray([-lr * mean, lr * mean], np.float32))), (family, w1[[p, m]], lr * mean)
+    for _ in range(2):
+        st, _ = hard_step(o, eng, "concentrated", h, run, lists, lr, family, ranges)
+        assert st["n_active"] == 0 == o.last_stats["n_active"]
+    assert np.array_equal(bits(eng.get_weights()), bits(w1))
+    eng.set_weights(-w1)
+    st, _ = hard_step(o, eng, "concentrated", h, run, lists, lr, family, ranges)
+    assert st["n_active"] == total == o.last_stats["n_active"] and orb.reg_scalar(o, -w1.astype(np.float64)) != 0.0
+    return shift
+
+
+@pytest.mark.parametrize("family,mode", [(f, "default") for f in LIST_FAMILIES] + [("row_wise", "hsplit1"), ("virtual_tiles", "hsplit1")])
+def test_fp32_list_families_at_full_scale(monkeypatch, family, mode):
+    env, how, _, kernel = LIST_FAMILIES[family]
+    pin(monkeypatch, dict(env, **CONC_MODES[mode]))
+    n_cu = device_cus()
+    for which in hd.VMAX:
+        h, o, eng = conc_pair(which)
+        edges = 0
+        with eng:
+            assert (eng.tuning_info()["hsplit"] == 1) == (mode == "hsplit1")
+            for k, b in CONC_LIST_SHAPES[family]:
+                lists = hd.conc_lists(h.planted["n_train"], k, b)
+                shift = conc_steps(o, eng, h, which, lambda: run_lists(eng, how, lists, CONC_LR, kernel), lists, CONC_LR, family, False)
+                if family == "virtual_tiles" and mode == "hsplit1":   # (rows of up to three lanes there: no closed rule, no edge)
+                    continue
+                rows = list_rows_per_workgroup(family, k, b, n_cu)
+                want = min(21, 30 - hd.ceil_log2(rows)) if family == "virtual_tiles" else 30 - hd.ceil_log2(rows)
+                if family == "one_workgroup":
+                    # dsgd_plan_kernel takes 30 - ceil(log2 B) of its sub-batch ON THE DEVICE (csrc/dsgd_batch.hpp) and the host
+                    # reports the cap, which the bound above used (coarser, so weaker, than the kernel's own 24): the edge is by
+                    # construction, B = 64 = 2^6 rows at 30 - 6, and is held by the bits of w[P] and w[M]
+                    assert shift == hd.FIX_SHIFT_CAP and want == 24
+                    shift = want
+                print("%s %s %s: %d x %d rows, %d rows per workgroup, shift %d" % (family, mode, which, k, b, rows, shift))
+                assert shift == want, (family, k, b, rows, shift, want)
+                edges += rows << shift == 1 << 30
+            assert edges > 0 or (family == "virtual_tiles" and mode == "hsplit1"), "no list length of %s ran with a full word" % family
+
+
+@pytest.mark.parametrize("family,mode", [(f, m) for f in RANGE_FAMILIES for m in ("default", "bound_off")])
+def test_fp32_range_families_at_full_scale(monkeypatch, family, mode):
+    range_family_at_full_scale(monkeypatch, family, mode)
+
+
+def test_fp32_streaming_with_a_cold_concentrated_column(monkeypatch):
+    """DSGD_HSPLIT=1: P (rank 0) stays hot, M (rank 1) goes through the cold tiles and the cold partials of the streaming
+    launches.  The cold words are emptied by whoever sees one at 2^28, and sixteen waves can each add the rest of a
+    128-row tile before that: at the fixed shift 21 this data left the band (DSGD_ESTATE).  build_split now takes the cold
+    shift from the data's cold tiles (hard_data.cold_shift_rule: 17 here), and the launch reports the coarser of its two
+    grids."""
+    range_family_at_full_scale(monkeypatch, "streaming", "hsplit1")
+
+
+def range_family_at_full_scale(monkeypatch, family, mode):
+    env, names, kernel = RANGE_FAMILIES[family]
+    pin(monkeypatch, dict(env, **CONC_MODES[mode]))
+    n_cu = device_cus()
+    hsplit = 1 if mode == "hsplit1" else hd.HSPLIT_DEFAULT
+    for which in hd.VMAX:
+        h, o, eng = conc_pair(which)
+        n = h.planted["n_train"]
+        with eng:
+            assert eng.tuning_info()["fix_bound"] == (0 if mode == "bound_off" else 1)
+            for name in names:
+                ranges = {"whole": [(0, n)], "halves": [(0, n // 2), (n // 2, n)]}[name]
+                lists = [np.arange(a, b, dtype=np.int32) for a, b in ranges]
+
+                def run():
+                    st = eng.sync_step_ranges(ranges, CONC_LR)
+                    ran(eng, kernel)
+                    return st
+
+                shift = conc_steps(o, eng, h, which, run, lists, CONC_LR, family, True)
+                if family == "column_lists":
+                    assert shift == 21   # 64-bit sums: the cap alone
+                    continue
+                rows = hd.streaming_worst_rows(h.data, ranges, n_cu, hsplit) if family == "streaming" else hd.chunk_worst_rows(h.data, ranges, n_cu, hsplit)[0]
+                shift0 = hd.shift_of_rows(rows, hd.FIX_SHIFT_CAP)
+                # the refinement's A on a concentrated column: every row of the worst workgroup adds ceil(vmax 2^s0 / vmax2) = 2^s0
+                want = shift0 if mode == "bound_off" else hd.refined_shift(shift0, rows << shift0, rows)
+                assert want == shift0
+                cold, a_cold = hd.cold_shift_rule(h.data, hsplit)   # (21 with the default split: no cold entry at all)
+                assert cold == (17 if mode == "hsplit1" else 21) and (a_cold >= 128 << 21) == (mode == "hsplit1")   # 128 rows of a cold tile hold M
+                print("%s %s %s %s: worst workgroup %d rows, shift0 %d, cold %d, shift %d" % (family, mode, which, name, rows, shift0, cold, shift))
+                assert rows > 512 and shift < 21 and shift == min(want, cold), (family, name, rows, shift0, want, cold, shift)
+
+
+def test_fp32_lock_free_engine_with_one_worker_at_full_scale(monkeypatch):
+    """batch = 64 = 2^6 rows at shift 30 - 6: 64 * 2^24 = 2^30, the rule of hog_launch with equality; replayed by the oracle as
+    test_fp32_lock_free_engine_with_one_worker does, P and M on bits for vmax = 1"""
+    pin(monkeypatch, {"DSGD_CS": "0"})
+    batch, n_upd, lr = 64, 3, 2.0 ** -8
+    for which in hd.VMAX:
+        h, o, eng = conc_pair(which)
+        n = h.planted["n_train"]
+        with eng:
+            eng.set_weights(np.zeros(h.data.dim + 1, np.float32))
+            w_ref = np.zeros(h.data.dim + 1)
+            eng.async_start([(0, n)], batch=batch, lr=lr, max_updates=n_upd, seed=77, positional_bug=False)
+            eng.async_wait()
+            assert eng.async_updates() == (n_upd, False)
+            active = []
+            for it in range(n_upd):
+                o.async_step(w_ref, hog_rows(77, 0, it, 0, n, batch, False), lr)
+                active.append(o.last_stats["n_active"])
+            w = eng.get_weights()
+            assert active == [batch, 0, 0] and w_ref[h.planted["P"]] < 0 < w_ref[h.planted["M"]]
+            assert np.abs(w.astype(np.float64) - w_ref).max() <= 4 * tol32(w_ref)
+            if which == "one":
+                pm = [h.planted["P"], h.planted["M"]]
+                assert np.array_equal(bits(w[pm]), bits(w_ref[pm].astype(np.float32))) and abs(w_ref[pm[0]]) in (lr * batch, lr)
+
+
+# ---- fp64 at full scale: n * 2^(62 - ceil(log2 n)) == 2^62 at n = 2^k, on float values and on the Double twin -------------
+CONC_N64 = (1, 2, 3, 1024, 1025, 4096, 4097)
+
+
+def conc_engine64(which, double, lam, monkeypatch=None, fused=None):
+    h = hd.concentrated(which, double=double)
+    if fused is not None:
+        monkeypatch.setenv("DSGD_RP64_FUSED", "1" if fused else "0")
+    eng = dsgd_amd.Engine(h.data.dim, lam, precision="fp64")
+    if fused is not None:
+        monkeypatch.delenv("DSGD_RP64_FUSED")
+    eng.load_csr(h.data.row_ptr, h.data.col, h.data.val, h.data.label)
+    eng.build_dim_sparsity(h.planted["n_train"])
+    assert eng.value_bits() == (64 if double else 32)
+    return h, eng
+
+
+def conc_exact(data, idx):
+    """the correctly rounded exact sum per column (tests/test_gpu_fp64_values.py _fsum_gradient)"""
+    from test_gpu_fp64_values import _fsum_gradient
+
+    return _fsum_gradient((data.row_ptr, data.col, data.val.astype(np.float64), data.label), [int(r) for r in idx], data.dim + 1)
+
+
+@pytest.mark.parametrize("double", [False, True])
+@pytest.mark.parametrize("which", list(hd.VMAX))
+def test_fp64_exact_sums_at_full_scale(monkeypatch, which, double):
+    pin(monkeypatch, {})
+    h, eng = conc_engine64(which, double, 0.0)
+    d, n_train, vmax, p, m = h.data, h.planted["n_train"], h.planted["vmax"], h.planted["P"], h.planted["M"]
+    zero = np.zeros(d.dim + 1)
+    perm = np.random.default_rng(23).permutation(n_train).astype(np.int32)
+    lr = 2.0 ** -9
+    with eng:
+        for n in CONC_N64 + (n_train,):
+            idx = perm[:n].copy()
+            want = conc_exact(d, idx)
+            assert want[p] == math.fsum([vmax] * n) == -want[m] and (double and which == "below2" or want[p] == n * vmax)
+            g, st = eng.gradient_f64(idx, w=zero)
+            assert st["n_active"] == n
+            assert g[p] == math.fsum([vmax] * n) and g[m] == -g[p], (n, g[p])
+            assert np.array_equal(bits(g), bits(want)), (n, np.flatnonzero(g != want)[:8])
+            for other in (idx[::-1].copy(), np.random.default_rng(n).permutation(idx)):
+                g2, _ = eng.gradient_f64(other, w=zero)
+                assert np.array_equal(bits(g2), bits(g)), n
+            # the duplicate list: one row n times, its full-scale entry in a column of rank >= RP64_HOT (plain global atomics)
+            dup = np.full(n, h.planted["dup_row"], np.int32)
+            gd, st = eng.gradient_f64(dup, w=zero)
+            assert st["n_active"] == n and gd[h.planted["cold_column"]] == math.fsum([vmax] * n)
+            assert np.array_equal(bits(gd), bits(conc_exact(d, dup)))
+            # one worker's synchronous step from w = 0: w = -lr * g (a power of two: exact)
+            for lists, wanted in (([idx], want), ([dup], conc_exact(d, dup))):
+                eng.set_weights(zero)
+                st = eng.sync_step_f64(lists, lr)
+                assert st["n_active"] == n and np.array_equal(bits(eng.get_weights()), bits(0.0 - lr * wanted)), n
+            if n <= 1024 and not double:   # the column-slice plan, inside its limits (float values: dsgd_plan_create refuses Double data)
+                eng.set_weights(zero)
+                plan = eng.plan([[idx]])
+                assert plan.info()["kind"] == "column_slices_fp64"
+                eng.plan_run(plan, 0, 1, lr)
+                eng.synchronize()
+                ran(eng, "dsgd_cs64_step_kernel")
+                plan.destroy()
+                assert np.array_equal(bits(eng.get_weights()), bits(0.0 - lr * want)), n
+            if n <= 1024:   # the asynchronous iteration: the MEAN over the listed rows (core/Slave.scala:92-101)
+                eng.set_weights(zero)
+                dl, st = eng.async_step(idx, lr, want_delta=True)
+                w = eng.get_weights()
+                assert st["n_active"] == n and np.array_equal(w, -dl)
+                assert np.abs(w + lr * want / n).max() <= 1e-12 * scale64(lr * want / n), n
+                if not double:   # n equal values: the quotient is vmax again, exactly
+                    ran(eng, "dsgd_cs64_async_kernel")
+                    assert w[p] == -lr * vmax and w[m] == lr * vmax, (n, w[p])
+    if double and which == "below2":   # both words, the high one near full scale
+        assert math.fsum([vmax] * 4096) == 8192.0 - 2.0 ** -40 != 4096 * 2.0
+
+
+@pytest.mark.parametrize("fused", [False, True])
+@pytest.mark.parametrize("double", [False, True])
+def test_fp64_steps_in_one_call_at_full_scale(monkeypatch, double, fused):
+    from test_gpu_fp64_steps import _served
+
+    pin(monkeypatch, {})
+    lr = 2.0 ** -9
+    for which in hd.VMAX:
+        h, eng = conc_engine64(which, double, 0.0, monkeypatch, fused)
+        d = h.data
+        perm = np.random.default_rng(29).permutation(h.planted["n_train"]).astype(np.int32)
+        with eng:
+            for n in CONC_N64:
+                for idx in (perm[:n].copy(), np.full(n, h.planted["dup_row"], np.int32)):
+                    want = conc_exact(d, idx)
+                    eng.set_weights(np.zeros(d.dim + 1))
+                    st = eng.sync_steps_f64(idx, np.asarray([0, n]), 1, 1, lr, per_step=True)
+                    assert eng.grad_kernel_name() == _served(fused, double), (fused, eng.grad_kernel_name())
+                    assert st["n_active"] == n == int(st["active_per_step"][0])
+                    assert np.array_equal(bits(eng.get_weights()), bits(0.0 - lr * want)), (which, n)
+
+
+@pytest.mark.parametrize("double", [False, True])
+@pytest.mark.parametrize("which", list(hd.VMAX))
+def test_fp64_steps_at_full_scale_against_the_reference(monkeypatch, which, double):
+    """steps 1 to 4 of the fp32 header at lambda = 1e-5: orc_sync_step on float values, ref_dict on the Double twin; 1e-12 *
+    max(1, |ref|_inf), equal supports and active counts.  sync_step_f64 (2 x 1,024 rows, 1 x 4,096), the cs64 plan (2 x 512)."""
+    from oracle import ref_dict as rd
+
+    pin(monkeypatch, {})
+    h, eng = conc_engine64(which, double, LAM)
+    d, n_train, dp = h.data, h.planted["n_train"], h.data.dim + 1
+    lr = 2.0 ** -9
+    if double:
+        rows = {}
+
+        def sample(r):
+            if r not in rows:
+                b, e = int(d.row_ptr[r]), int(d.row_ptr[r + 1])
+                rows[r] = (rd.Sparse({int(c): float(v) for c, v in zip(d.col[b:e], d.val[b:e])}, dp), int(d.label[r]))
+            return rows[r]
+
+        model = rd.SparseSVM(LAM, rd.dim_sparsity([sample(r) for r in range(n_train)]))
+    else:
+        o = orc.Oracle(d.dim, d.row_ptr, d.col, d.val, d.label, LAM)
+        o.set_dim_sparsity(o.dim_sparsity(n_train))
+
+    def ref_step(w, lists):
+        """-> (weights after, active rows) from the dense float64 w"""
+        if not double:
+            out = w.copy()
+            o.sync_step(out, lists, lr)
+            return out, o.last_stats["n_active"]
+        data = {int(r): sample(int(r)) for a in lists for r in a}
+        ws = rd.Sparse({int(k): float(w[k]) for k in np.flatnonzero(w)}, dp)
+        act = sum(1 for a in lists for r in a if not (data[int(r)][1] * data[int(r)][0].dot(ws) < 0))
+        after = rd.master_sync_step(model, data, ws, [[int(r) for r in a] for a in lists], lr)
+        out = np.zeros(dp)
+        for k, v in after.map.items():
+            out[k] = v
+        return out, act
+
+    with eng:
+        if double:
+            ds = np.zeros(dp)
+            for k, v in model.dim_sparsity.map.items():
+                ds[k] = v
+            assert np.array_equal(bits(eng.get_dim_sparsity()), bits(ds))
+        for k, b, planned in ((2, 1024, False), (1, 4096, False)) + (() if double else ((2, 512, True),)):   # (no plans on Double data)
+            lists = hd.conc_lists(n_train, k, b, seed=1)
+            total = k * b
+
+            def step():
+                if not planned:
+                    return eng.sync_step_f64(lists, lr)["n_active"]
+                plan = eng.plan([lists])
+                assert plan.info()["kind"] == "column_slices_fp64"
+                plan.record(True)
+                eng.plan_run(plan, 0, 1, lr)
+                eng.synchronize()
+                mask, _ = plan.read_record()
+                plan.destroy()
+                return int(mask[0][:total].sum())
+
+            w = np.zeros(dp)
+            eng.set_weights(w)
+            for leg, active in enumerate((total, 0, 0, total)):
+                if leg == 3:
+                    w = -w
+                    eng.set_weights(w)
+                w_ref, act_ref = ref_step(w, lists)
+                act = step()
+                w = eng.get_weights()
+                assert act == act_ref == active, (k, b, leg, act, act_ref)
+                assert np.array_equal(np.flatnonzero(w), np.flatnonzero(w_ref)), (k, b, leg)
+                assert np.abs(w - w_ref).max() <= 1e-12 * scale64(w_ref), (k, b, leg)
+            assert w[h.planted["P"]] != 0.0 and w[h.planted["M"]] != 0.0

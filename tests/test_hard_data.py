@@ -252,3 +252,116 @@ def test_the_vanishing_term_prices_only_columns_that_can_vanish():
         diff = np.zeros(o.dim + 1)
         diff[at] = amount
         assert (orb.vanished(diff, base, -s, cand)[1].max() <= 1.0) == ok
+
+
+# ---- concentrated columns: the data and the reference side of tests/test_gpu_hard_values.py's full-scale legs -------------
+FP64_LIST_ROWS = (1, 2, 3, 1024, 1025, 4096, 4097)
+
+
+def _exact_sums(data, rows):
+    """math.fsum of y * x per column over the listed rows (duplicates count)"""
+    per = {}
+    for r in rows:
+        for p in range(int(data.row_ptr[r]), int(data.row_ptr[r + 1])):
+            per.setdefault(int(data.col[p]), []).append(float(data.val[p]) * float(data.label[r]))
+    return {c: math.fsum(v) for c, v in per.items()}
+
+
+@pytest.mark.parametrize("which,vexp", [("one", 0), ("below2", 1)])
+def test_concentrated_vexp_and_shape(which, vexp):
+    h = hd.concentrated(which)
+    d, n = h.data, h.planted["n_train"]
+    assert hd.vexp_of(d.val) == vexp and orb.vmax2_of(d.val) == 2.0 ** vexp
+    assert float(np.abs(d.val).max()) == h.planted["vmax"] == hd.VMAX[which]
+    m, e = math.frexp(hd.VMAX64[which])   # the Double twin by the same rule on doubles (dsgd_load_csr_f64)
+    assert (e - 1 if m == 0.5 else e) == vexp and np.abs(hd.concentrated(which, double=True).data.val).max() == hd.VMAX64[which]
+    lens = np.diff(d.row_ptr)[:n]
+    assert lens.min() == 2 and lens.max() == 4 and {int(y) for y in d.label[:n]} == {1, -1}
+    first, y = d.row_ptr[:n], d.label[:n].astype(np.float64)
+    assert (d.col[first] == hd.CONC_P).all() and (d.col[first + 1] == hd.CONC_M).all()
+    assert (d.val[first] * y == h.planted["vmax"]).all() and (d.val[first + 1] * y == -h.planted["vmax"]).all()
+    rest = np.abs(d.val[~np.isin(d.col, [hd.CONC_P, hd.CONC_M, hd.CONC_COLD])])
+    assert rest.min() > 0 and rest.max() <= h.planted["vmax"] / 4
+    # the contribution of the second vmax rounds UP to exactly 2^shift on every fp32 grid up to shift 23 (a tie to even
+    # there): the bound is met with equality; at shift 24 (64 rows) it is the integer 2^24 - 1
+    if which == "below2":
+        for shift in range(1, 24):
+            assert np.rint(np.float32(math.ldexp(h.planted["vmax"], shift - vexp))) == 2.0 ** shift
+        assert math.ldexp(h.planted["vmax"], 24 - vexp) == 2.0 ** 24 - 1
+
+
+@pytest.mark.parametrize("which", ["one", "below2"])
+def test_concentrated_rows_are_all_active_at_zero_and_sum_in_closed_form(which):
+    from oracle import ref_dict as rd
+
+    h = hd.concentrated(which)
+    d, n, vmax = h.data, h.planted["n_train"], h.planted["vmax"]
+    o = oracle_of(d, n_train=n)
+    rows = np.arange(n, dtype=np.int32)
+    g = o.gradient(np.zeros(d.dim + 1), rows)
+    assert o.last_stats["n_active"] == n
+    want = _exact_sums(d, rows.tolist())
+    assert g[hd.CONC_P] == math.fsum([vmax] * n) == n * vmax == want[hd.CONC_P]
+    assert g[hd.CONC_M] == -math.fsum([vmax] * n) == -n * vmax == want[hd.CONC_M]
+    # ref_dict: every row passes the gate at w = 0, on float and on Double values
+    for double in (False, True):
+        dd = hd.concentrated(which, double=double).data
+        w0 = rd.Sparse({}, dd.dim + 1)
+        sub = list(range(0, n, 7))
+        data = {r: (rd.Sparse({int(c): float(v) for c, v in zip(dd.col[dd.row_ptr[r]:dd.row_ptr[r + 1]], dd.val[dd.row_ptr[r]:dd.row_ptr[r + 1]])},
+                              dd.dim + 1), int(dd.label[r])) for r in sub}
+        assert all(not (y * x.dot(w0) < 0) for x, y in data.values())
+        model = rd.SparseSVM(0.0, rd.Sparse({}, dd.dim + 1))
+        gs = rd.slave_gradient(model, data, w0, sub)
+        v = hd.VMAX64[which] if double else vmax
+        assert gs.map[hd.CONC_P] == math.fsum([v] * len(sub)) and gs.map[hd.CONC_M] == -math.fsum([v] * len(sub))
+
+
+def test_concentrated_size_comes_from_the_host_rules():
+    """the smallest count (in steps of 256, from the range families' dispatch floor) with shift0 < 21 in both range launches"""
+    n = hd.concentrated_rows()
+    d = hd.concentrated("one").data
+    assert n < 30000 and n % 256 == 0
+    for ranges in ([(0, n)], [(0, n // 2), (n // 2, n)]):
+        ws, (wc, n_wg) = hd.streaming_worst_rows(d, ranges), hd.chunk_worst_rows(d, ranges)
+        assert ws > 512 and wc > 512 and n_wg == min(ranges[0][1] - ranges[0][0], hd.N_CU * hd.FSTEP_ROWS // len(ranges)) // hd.FSTEP_ROWS
+        assert hd.shift_of_rows(ws, hd.FIX_SHIFT_CAP) < 21 and hd.shift_of_rows(wc, hd.FIX_SHIFT_CAP) < 21
+    if n > hd.CONC_RANGE_MIN:
+        smaller = hd._conc_data("one", False, n - 256)
+        assert min(hd.streaming_worst_rows(smaller, [(0, n - 256)]), hd.chunk_worst_rows(smaller, [(0, n - 256)])[0]) <= 512
+    # the refinement cannot lift a concentrated column: A = rows * 2^shift0 > 2^29, so 2 A + rows > 2^30
+    for rows in (513, 517, 1024, 2692, 4064):
+        s0 = hd.shift_of_rows(rows, hd.FIX_SHIFT_CAP)
+        assert hd.refined_shift(s0, rows << s0, rows) == s0
+    assert hd.refined_shift(18, 1 << 20, 2692) == 21 and hd.refined_shift(18, (1 << 28) - 2692, 2692) == 20   # (it does lift ordinary data)
+    # lowered split: M's rank 1 is at the split of 1, P's rank 0 stays hot
+    r = hd.column_ranks(d)
+    assert (r[hd.CONC_P], r[hd.CONC_M]) == (0, 1)
+    # ... and the cold words' scale follows the cold tiles: a 128-row tile holds M 128 times (2^28 at shift 21), sixteen waves
+    # twice that each: 17 is the finest shift that keeps a word below 2^30; no cold entry at the default split: 21
+    for which in hd.VMAX:
+        dd = hd.concentrated(which).data
+        s, a = hd.cold_shift_rule(dd, 1)
+        assert s == 17 and a >= 128 << 21 and 2 ** 28 + 2 ** s + 32 * (a // 16 + 256) < 2 ** 30 <= 2 ** 28 + 2 ** (s + 1) + 32 * (a // 8 + 256)
+        assert hd.cold_shift_rule(dd) == (21, 0)
+
+
+def test_the_duplicate_lists_column_is_cold_for_the_fp64_kernels():
+    h = hd.concentrated("one")
+    d = h.data
+    cnt = np.bincount(d.col, minlength=d.dim + 1)
+    rank = sorted(range(d.dim + 1), key=lambda c: (-cnt[c], c)).index(h.planted["cold_column"])   # count descending, ties by key
+    assert rank >= hd.RP64_HOT and rank == hd.column_ranks(d)[h.planted["cold_column"]]
+    b, e = int(d.row_ptr[h.planted["dup_row"]]), int(d.row_ptr[h.planted["dup_row"] + 1])
+    full = np.abs(d.val[b:e]) == h.planted["vmax"]
+    assert full.sum() == 1 and d.col[b:e][full][0] == h.planted["cold_column"] and cnt[h.planted["cold_column"]] == 1
+    assert float(d.val[b:e][full][0]) * float(d.label[h.planted["dup_row"]]) == h.planted["vmax"]
+
+
+def test_fp64_shift_is_tight_at_powers_of_two():
+    for n in FP64_LIST_ROWS + (hd.concentrated_rows(),):
+        s = 62 - hd.ceil_log2(n)
+        assert hd.ceil_log2(n) == (math.ceil(math.log2(n)) if n > 1 else 0)
+        assert n * 2 ** s <= 2 ** 62 and (n * 2 ** s == 2 ** 62) == (n & (n - 1) == 0)
+        if n & (n - 1):
+            assert n * 2 ** (s + 1) > 2 ** 62   # one finer would not fit
