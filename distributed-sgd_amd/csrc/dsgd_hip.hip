@@ -120,6 +120,7 @@ static bool available() {
   } while (0)
 
 #include "dsgd_buf.hpp"      // (host only: the owners of device and pinned memory)
+#include "dsgd_plan_check.hpp"   // (host only: a plan's lists against the rows loaded now)
 #include "dsgd_kernels.hpp"
 #include "dsgd_batch.hpp"
 #include "dsgd_cs.hpp"
@@ -147,6 +148,9 @@ struct dsgd_plan {
   // virtual tiles (dsgd_vt_grad_kernel): the lists laid out over the split streams, built at the first run that needs them
   std::vector<int> h_idx;       // host copy of the lists (a plan drawn on the device fetches it only if a host builder asks: plan_host_idx)
   bool idx_trusted = false;     // the lists were drawn by the library inside the caller's row ranges: nothing to validate
+                                //   (ranges of the data loaded THEN: cleared by plan_revalidate after a load)
+  bool drawn = false;           // ... drawn by the library at all (such plans never take the one-workgroup kernel: fits stays false)
+  long long checked_load = -1;  // the context's load_gen the lists were last checked against (plan_revalidate)
   DevBuf<VtLane> d_vt_lanes; // 64 descriptors per tile
   DevBuf<WorkSeg> d_vt_segs; // tile range of every list, then (n_lists further entries) its range of d_vt_long
   DevBuf<MbRec> d_vt_long;   // rows of the lists that sit in no tile (long-row list, more than 64 cold entries)
@@ -215,7 +219,9 @@ struct dsgd_ctx {
   std::vector<long long> h_crow_ptr;    // cold ENTRIES before each row
   std::vector<long long> h_hrp, h_ctp;  // slot offsets of the hot / cold stream (virtual tiles are built from them)
   std::vector<unsigned short> h_ccol;   // host copy of the 16-bit cold ranks (a virtual tile's descriptor carries its cold rank)
-  long long layout_gen = 0;             // bumped whenever the split streams are rebuilt
+  long long layout_gen = 0;             // bumped whenever the split streams are rebuilt, and by every load (what a plan or a
+                                        //   column-list layout stamped is stale from the load on, not from the next ranking on)
+  long long load_gen = 0;               // bumped by every successful dsgd_load_csr / _f64 (plan_revalidate)
   bool layout_seen_by_build = false;    // the build stream is ordered behind the kernels that wrote the current split streams
   bool cs_enable = true;                // DSGD_CS=0: small steps of resident plans through the row-parallel kernels
   int cs_g = 0;                         // DSGD_CS_G: slices (8 or 16; 0 = 8 up to four hosted workers, 16 beyond)
@@ -2844,15 +2850,31 @@ static int hog_raise_stop(dsgd_ctx* c);
 // gradient and the update and a step is small enough for one CU
 // does the list fit the staged sub-batch of dsgd_plan_kernel (at most PLAN_CAP rows and PLAN_CAP work items of 128
 // non-zeros)?  Row lengths from the host copy of the internal row pointers.
+static_assert(PLAN_STAGE_CAP == PLAN_CAP && PLAN_STAGE_CH == BT_CH, "csrc/dsgd_plan_check.hpp restates the staged sub-batch");
+static const long long* host_row_ptr(const dsgd_ctx* c) {   // (NULL: no host copy of these rows)
+  return c->h_row_ptr.size() == (size_t)c->n_rows + 1 ? c->h_row_ptr.data() : nullptr;
+}
 static bool list_fits_staged(const dsgd_ctx* c, const int32_t* idx, long long n) {
-  if (n > PLAN_CAP || c->h_row_ptr.size() != (size_t)c->n_rows + 1) return false;
-  long long items = 0;
-  for (long long t = 0; t < n; ++t) {
-    const long long r = idx[t];
-    if (r < 0 || r >= c->n_rows) return false;
-    items += (c->h_row_ptr[(size_t)r + 1] - c->h_row_ptr[(size_t)r] + BT_CH - 1) / BT_CH;
-  }
-  return items <= PLAN_CAP;
+  return plan_list_fits_staged(host_row_ptr(c), c->n_rows, idx, n);
+}
+// A plan that outlived a load (include/dsgd.h, dsgd_load_csr): its lists are judged against the rows loaded NOW before they
+// reach a kernel or a layout builder.  An index outside them: DSGD_ERANGE, nothing enqueued, the plan as it was (asked again
+// at its next use, so a later load under which the lists fit lets it run).  Inside: the one-workgroup kernel's "fits" from
+// the new row lengths, and the lists are no longer trusted unseen -- dsgd_cs_layout_kernel reads row_ptr[r] unchecked.
+static int plan_revalidate(dsgd_ctx* c, dsgd_plan* p) {
+  if (p->checked_load == c->load_gen) return DSGD_OK;
+  const long long n_lists = (long long)p->n_steps * p->n_workers;
+  DSGD_TRY(plan_host_idx(c, p));
+  if ((long long)p->h_idx.size() != p->offsets[(size_t)n_lists]) return fail(DSGD_ESTATE, "internal: the plan's lists are not on the host");
+  const PlanCheck v = plan_check_lists(p->h_idx.data(), p->offsets.data(), n_lists, host_row_ptr(c), c->n_rows);
+  if (v.bad_at >= 0)
+    return fail(DSGD_ERANGE, "the plan holds sample index %d (position %lld), outside the %lld rows loaded since it was made; nothing ran, "
+                             "the plan runs again under data that holds its rows", p->h_idx[(size_t)v.bad_at], v.bad_at, c->n_rows);
+  p->fits = v.fits && !p->drawn;
+  p->fits_rows = c->n_rows;
+  p->idx_trusted = false;
+  p->checked_load = c->load_gen;
+  return DSGD_OK;
 }
 static bool plan_kernel_ok(const dsgd_ctx* c, long long step_rows, int n_workers) {
   // (several hosted workers: their batches would run one after the other in the one workgroup -- 44 us for 3 x 100 --
@@ -3393,6 +3415,15 @@ static int load_csr_impl(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in,
   c->h_row_ptr.assign(row_ptr, row_ptr + n_rows + 1);
   c->h_label.assign(label, label + n_rows);
   c->ssegs_last.clear();
+  // everything stamped with the old data is stale from here on, not only from the next ranking on (build_split bumps
+  // layout_gen again): plans' slices and tiles, column-list layouts; the plans' lists are checked at their next use
+  ++c->layout_gen;
+  ++c->load_gen;
+  c->bound_segs.clear();
+  c->tcol_miss_streak = 0;   // (the column lists' misses were about the old rows' ranges)
+  c->tcol_cooldown = 0;
+  c->last_grad_kernel = "";  // (dsgd_grad_kernel_name / dsgd_tuning_info report launches over THIS data: calls that record none --
+  c->last_shift = FIX_SHIFT; //  the row-parallel fp64 requests -- would go on reporting the old data's)
   // (the wave tiles cover the hot stream and are built with the layout, at the first compute call)
   const double mean = (double)nnz / (double)n_rows;
   c->group = mean > 192.0 ? 64 : (mean > 96.0 ? 32 : (mean > 12.0 ? 16 : 8));
@@ -4040,6 +4071,7 @@ static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int3
   for (int64_t st = 0; st < n_steps; ++st)
     p->max_step_rows = std::max<long long>(p->max_step_rows, offsets[(st + 1) * n_workers] - offsets[st * n_workers]);
   p->fits_rows = c->n_rows;
+  p->checked_load = c->load_gen;   // (what the creators establish -- fits, lists drawn inside the rows -- is about this load)
   std::vector<WorkSeg> segs((size_t)n_lists);
   for (int64_t i = 0; i < n_lists; ++i) {
     segs[i].begin = offsets[i];
@@ -4078,6 +4110,7 @@ static int plan_run64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long
   DSGD_TRY(require_data(c));
   DSGD_TRY(require_ds(c));
   DSGD_TRY(require_sync_mode(c));
+  DSGD_TRY(plan_revalidate(c, p));   // (a plan from before the last load: DSGD_ERANGE here, before anything is enqueued)
   DSGD_TRY(prepare_layout(c));
   if (p->cs_layout != c->layout_gen) {
     DSGD_TRY(cs_build(c, p));
@@ -4348,6 +4381,7 @@ int dsgd_plan_create_from_seed(dsgd_ctx* c, uint64_t* jstate, const int64_t* spl
   DSGD_TRY(plan_frame(c, offsets.data(), n_steps, n_splits, &p));
   lap("plan frame");
   p->idx_trusted = true;
+  p->drawn = true;
   p->fits = false;   // (the one-workgroup kernel's test reads the lists on the host; these plans run on column slices)
   JrShuf* d_shuf = nullptr;
   int *d_rej = nullptr, *d_err = nullptr;
@@ -4494,6 +4528,10 @@ int dsgd_plan_info(dsgd_ctx* c, dsgd_plan* p, int32_t* vals, int32_t n) {
   DSGD_TRY(check_ctx(c));
   if (!p || !vals || n < 0 || n > 8) return fail(DSGD_EINVAL, "bad plan_info arguments");
   std::lock_guard<std::mutex> lk(c->mu);
+  if (p->checked_load != c->load_gen) {   // (data loaded since: how the plan will run is a question about the new rows)
+    DSGD_TRY(bind(c, true));
+    DSGD_TRY(plan_revalidate(c, p));
+  }
   const bool cs = (c->cs_enable || c->fp64) && !c->comm && p->cs_ok && p->cs_layout == c->layout_gen;
   const bool one_wg = !cs && plan_kernel_ok(c, p->max_step_rows, p->n_workers) && p->fits && p->fits_rows == c->n_rows;
   const bool vt = !cs && !one_wg && c->vt_enable && p->vt_ok && p->vt_layout == c->layout_gen;
@@ -4535,6 +4573,7 @@ int dsgd_plan_run(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_en
   DSGD_TRY(require_data(c));
   DSGD_TRY(require_ds(c));
   DSGD_TRY(require_sync_mode(c));
+  DSGD_TRY(plan_revalidate(c, p));   // (a plan from before the last load: DSGD_ERANGE here, before anything is enqueued)
   DSGD_TRY(prepare_layout(c));
   // the reference's own batch sizes: column slices, the whole range of steps in ONE launch (csrc/dsgd_cs.hpp)
   if (c->cs_enable && !c->comm) {
@@ -5261,6 +5300,7 @@ int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int
   dsgd_plan* p = nullptr;
   DSGD_TRY(plan_frame(c, offsets.data(), n_updates, 1, &p));
   p->idx_trusted = true;   // (drawn here inside the callers' row ranges)
+  p->drawn = true;
   p->fits = false;
   std::vector<long long> sb2(2 * (size_t)n_workers);
   for (int k = 0; k < n_workers; ++k) {

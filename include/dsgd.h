@@ -229,7 +229,23 @@ int dsgd_destroy(dsgd_ctx* ctx);
  * each at most once per row in any order (a row is a Map: DSGD_EINVAL for a repeated key), label +1/-1.
  * Copied to HBM once; resident afterwards.  Indices in later calls refer to it,
  * exactly as GradientRequest.samples / ForwardRequest.samples index Slave.data
- * (core/Slave.scala:134,149; proto.proto:51-63). */
+ * (core/Slave.scala:134,149; proto.proto:51-63).
+ *
+ * LOADING AGAIN.  dsgd_load_csr / dsgd_load_csr_f64 may be called on a context that holds data (not while the lock-free
+ * engine runs: DSGD_ESTATE).  A successful load replaces the data and everything the library derived from it: the column
+ * ranking, the split streams and their tiles, vexp and the fixed-point shifts, every cached layout of row ranges, the
+ * evaluation kernels' lane group.  What stays:
+ *   - the resident weights and dimSparsity, value for value in key order (dsgd_get_weights returns the bits it returned
+ *     before the load); dimSparsity stays "set", i.e. it is the CALLER's to set or build again for the new rows
+ *     (dsgd_set_dim_sparsity / dsgd_build_dim_sparsity) -- until then the steps use the old data's values;
+ *   - every plan handle.  A plan made before the load is judged against the data loaded at its next use (dsgd_plan_run,
+ *     dsgd_plan_run_f64, dsgd_plan_run_async_f64, dsgd_plan_info): if every index it holds is a row of that data it is laid
+ *     out again and runs exactly as a plan created now from the same lists would; otherwise the call returns DSGD_ERANGE
+ *     before anything is enqueued -- the weights untouched, the context and the plan usable, and the plan runs again after
+ *     a later load under which its lists fit.  This holds for lists the library drew itself (dsgd_plan_create_from_seed,
+ *     dsgd_async_plan_create: drawn inside row ranges of the data loaded THEN) as for the caller's;
+ *   - under Double feature values the refusals of "THE FP64 MODE" stay as they are: no plan is created, a plan made on
+ *     float data runs on the values rounded to float.  */
 int dsgd_load_csr(dsgd_ctx* ctx, int64_t n_rows, const int64_t* row_ptr, const int32_t* col_1based, const float* val,
                   const int8_t* label);
 /* The same data with Double values ("THE FP64 MODE", Double feature values): fp64 contexts only (DSGD_ESTATE on an fp32
