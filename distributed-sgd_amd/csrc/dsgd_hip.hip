@@ -182,6 +182,9 @@ struct dsgd_plan {
   float* d_s_rec = nullptr;
   int gate_words = 0;
   size_t gate_bytes = 0, s_bytes = 0;
+  // a row-parallel fp64 plan (dsgd_plan_create_rp64_n and its kin): the lists and their ranges only, no layout -- its steps are
+  // the two launches of dsgd_sync_step_f64 over d_idx / d_segs, on whichever value type is loaded at the run (plan_run_rp64)
+  bool rp64 = false;
 };
 
 struct FusedArgs {
@@ -4040,7 +4043,7 @@ static void plan_abandon(dsgd_ctx* c, dsgd_plan* p) {
   (void)hipStreamSynchronize(c->build_stream);
   plan_release(c, p);
 }
-static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int32_t n_workers, dsgd_plan** out) {
+static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int32_t n_workers, dsgd_plan** out, bool rp64 = false) {
   const int64_t n_lists = n_steps * n_workers;
   if (offsets[0] != 0) return fail(DSGD_EINVAL, "offsets[0] must be 0");
   long long mx = 0;
@@ -4049,7 +4052,7 @@ static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int3
       return fail(DSGD_EINVAL, "list %lld is empty: Vec.sum requires a non-empty list", (long long)i);
     mx = std::max<long long>(mx, offsets[i + 1] - offsets[i]);
   }
-  if (c->fp64) {   // what dsgd_cs64_step_kernel can hold, refused here rather than at the first run
+  if (c->fp64 && !rp64) {   // what dsgd_cs64_step_kernel can hold, refused here rather than at the first run
     long long rows = 0;
     for (int64_t st = 0; st < n_steps; ++st) rows = std::max<long long>(rows, offsets[(st + 1) * n_workers] - offsets[st * n_workers]);
     if (n_workers > CS64_MAX_K)
@@ -4064,6 +4067,7 @@ static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int3
   dsgd_plan* p = new (std::nothrow) dsgd_plan();
   if (!p) return fail(DSGD_ENOMEM, "out of host memory");
   c->plans.push_back(p);
+  p->rp64 = rp64;
   p->n_steps = n_steps;
   p->n_workers = n_workers;
   p->max_items = mx;
@@ -4104,6 +4108,7 @@ static int cs64_refused(dsgd_ctx* c) {
   return fail(DSGD_EUNSUPPORTED, "fp64 plan: a row index outside the loaded data, or a step whose layout exceeds dsgd_cs64_step_kernel "
                                  "(%d slots or %d columns of one slice per step)", CS_MAX_SLOTS, CS_MAX_CLT * CS_THREADS);
 }
+static int plan_run_rp64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr, bool async);   // (with the row-parallel family, further down)
 // the steps of a plan in an fp64 context (locked; bound with the slice-major weights kept); async: see launch_cs64
 static int plan_run64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr, bool async = false,
                       double* delta = nullptr) {
@@ -4112,6 +4117,7 @@ static int plan_run64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long
   DSGD_TRY(require_sync_mode(c));
   DSGD_TRY(plan_revalidate(c, p));   // (a plan from before the last load: DSGD_ERANGE here, before anything is enqueued)
   DSGD_TRY(prepare_layout(c));
+  if (p->rp64) return plan_run_rp64(c, p, step_begin, step_end, lr, async);
   if (p->cs_layout != c->layout_gen) {
     DSGD_TRY(cs_build(c, p));
     if (p->cs_device_built && c->build_stream) {
@@ -4133,7 +4139,7 @@ static int plan_finish(dsgd_ctx* c, dsgd_plan* p, dsgd_plan** out) {
   int rc = DSGD_OK;
   // the column slices of the reference's own step sizes are laid out NOW (by the device, on the build stream), not inside
   // the first dsgd_plan_run -- a call its callers time; without a column layout yet (no data / no dimSparsity) at the first run
-  if ((c->cs_enable || c->fp64) && !c->comm && c->d_row_ptr && c->have_ds && !c->async_running) {
+  if (!p->rp64 && (c->cs_enable || c->fp64) && !c->comm && c->d_row_ptr && c->have_ds && !c->async_running) {   // (a row-parallel plan has no layout)
     rc = prepare_layout(c);
     if (rc == DSGD_OK) rc = cs_build(c, p);
     if (rc == DSGD_OK && c->fp64 && !p->cs_ok) rc = cs64_refused(c);
@@ -4218,14 +4224,21 @@ static hipError_t seed_scratch(dsgd_ctx* c, int i, size_t bytes, void** out) {
   return e;
 }
 // ---- an epoch's lists drawn on the device, draw for draw the reference's stream (csrc/dsgd_shuffle.hpp) ---------------------
-int dsgd_plan_create_from_seed(dsgd_ctx* c, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
-                               int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
+// (rp64: dsgd_plan_create_from_seed_rp64 -- the same draws into a row-parallel plan: an fp64 context, float or Double data, no
+//  limit of the column slices; `what` names the entry point in the messages)
+static int plan_from_seed_impl(dsgd_ctx* c, const char* what, bool rp64, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end,
+                               int32_t n_splits, int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
   DSGD_TRY(check_ctx(c));
   if (!jstate || !split_begin || !split_end || !out || !n_steps_out || n_splits < 1 || batch_size < 1)
     return fail(DSGD_EINVAL, "bad arguments");
   {   // (refused with *out as it was)
     std::lock_guard<std::mutex> lk0(c->mu);
-    DSGD_TRY(refuse_val64(c, "dsgd_plan_create_from_seed"));
+    if (rp64) {
+      DSGD_TRY(require_fp64(c, what));
+      DSGD_TRY(refuse_fp64_comm(c, what));
+    } else {
+      DSGD_TRY(refuse_val64(c, what));
+    }
   }
   *out = nullptr;
   *n_steps_out = 0;
@@ -4257,8 +4270,8 @@ int dsgd_plan_create_from_seed(dsgd_ctx* c, uint64_t* jstate, const int64_t* spl
   }
   const long long nominal = start[(size_t)n_shuf];
   std::lock_guard<std::mutex> lk(c->mu);
-  DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_create_from_seed"));
-  DSGD_TRY(refuse_val64(c, "dsgd_plan_create_from_seed"));
+  DSGD_TRY(refuse_fp64_comm(c, what));
+  if (!rp64) DSGD_TRY(refuse_val64(c, what));
   DSGD_TRY(bind(c, true));
   for (int k = 0; k < n_splits; ++k)
     if (split_end[k] > c->n_rows) return fail(DSGD_ERANGE, "worker %d's rows [%lld, %lld) outside the %lld loaded", k, (long long)split_begin[k], (long long)split_end[k], c->n_rows);
@@ -4378,7 +4391,7 @@ int dsgd_plan_create_from_seed(dsgd_ctx* c, uint64_t* jstate, const int64_t* spl
       return fail(DSGD_EUNSUPPORTED, "more than %d rejections inside one shuffle (draw the lists on the host)", JR_MAX_REJ);
   // ---- the plan's frame, then pass B straight into its index buffer ----
   dsgd_plan* p = nullptr;
-  DSGD_TRY(plan_frame(c, offsets.data(), n_steps, n_splits, &p));
+  DSGD_TRY(plan_frame(c, offsets.data(), n_steps, n_splits, &p, rp64));
   lap("plan frame");
   p->idx_trusted = true;
   p->drawn = true;
@@ -4440,6 +4453,16 @@ int dsgd_plan_create_from_seed(dsgd_ctx* c, uint64_t* jstate, const int64_t* spl
   if (draws_out) *draws_out = nominal + rej_total;
   return DSGD_OK;
 }
+int dsgd_plan_create_from_seed(dsgd_ctx* c, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
+                               int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
+  return plan_from_seed_impl(c, "dsgd_plan_create_from_seed", false, jstate, split_begin, split_end, n_splits, max_samples, batch_size, out,
+                             n_steps_out, draws_out);
+}
+int dsgd_plan_create_from_seed_rp64(dsgd_ctx* c, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
+                                    int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
+  return plan_from_seed_impl(c, "dsgd_plan_create_from_seed_rp64", true, jstate, split_begin, split_end, n_splits, max_samples, batch_size,
+                             out, n_steps_out, draws_out);
+}
 
 // the lists of a plan as the device holds them (tests: the device-drawn lists against csrc/jrand.c's)
 int dsgd_plan_read_lists(dsgd_ctx* c, dsgd_plan* p, int32_t* idx_out, int64_t n, int64_t* offsets_out, int64_t n_offsets) {
@@ -4494,8 +4517,8 @@ int dsgd_plan_read_record(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t
   if (mask_words_out) *mask_words_out = p->gate_words;
   if (!gate_mask && !s_used) return DSGD_OK;
   if (!p->d_gate_rec) return fail(DSGD_ESTATE, "the plan keeps no record (dsgd_plan_record)");
-  if (!(p->cs_ok && p->cs_layout == c->layout_gen))
-    return fail(DSGD_EUNSUPPORTED, "only plans that run on column slices keep a record (see dsgd_plan_info)");
+  if (!p->rp64 && !(p->cs_ok && p->cs_layout == c->layout_gen))
+    return fail(DSGD_EUNSUPPORTED, "only plans that run on column slices and row-parallel fp64 plans keep a record (see dsgd_plan_info)");
   if (step_begin < 0 || step_end > p->n_steps || step_end < step_begin) return fail(DSGD_EINVAL, "steps outside the plan");
   HIP_TRY(hipStreamSynchronize(c->stream));
   const size_t n = (size_t)(step_end - step_begin);
@@ -4535,7 +4558,7 @@ int dsgd_plan_info(dsgd_ctx* c, dsgd_plan* p, int32_t* vals, int32_t n) {
   const bool cs = (c->cs_enable || c->fp64) && !c->comm && p->cs_ok && p->cs_layout == c->layout_gen;
   const bool one_wg = !cs && plan_kernel_ok(c, p->max_step_rows, p->n_workers) && p->fits && p->fits_rows == c->n_rows;
   const bool vt = !cs && !one_wg && c->vt_enable && p->vt_ok && p->vt_layout == c->layout_gen;
-  const int32_t all[8] = {(cs && c->fp64) ? 5 : cs ? 1 : (one_wg ? 2 : (vt ? 3 : (p->cs_layout == c->layout_gen || p->vt_layout == c->layout_gen ? 4 : 0))),
+  const int32_t all[8] = {p->rp64 ? 6 : (cs && c->fp64) ? 5 : cs ? 1 : (one_wg ? 2 : (vt ? 3 : (p->cs_layout == c->layout_gen || p->vt_layout == c->layout_gen ? 4 : 0))),
                           cs ? p->cs_G : 0, cs ? p->cs_slot_stride : 0, cs ? p->cs_row_stride : 0, cs ? p->cs_cl_stride : 0,
                           cs ? p->cs_spl : 0, (cs && p->cs_device_built) ? 1 : 0, p->gate_words};
   for (int i = 0; i < n; ++i) vals[i] = all[i];
@@ -5271,14 +5294,20 @@ int dsgd_sync_steps_f64(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const in
   return DSGD_OK;
 }
 
-int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,
-                           uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out) {
+// (rp64: dsgd_async_plan_create_rp64 -- the same lists into a row-parallel plan)
+static int async_plan_impl(dsgd_ctx* c, const char* what, bool rp64, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers,
+                           int32_t batch, uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out) {
   DSGD_TRY(check_ctx(c));
   if (!assigned_begin || !assigned_end || !out || n_workers < 1 || batch < 1 || first_update < 0 || n_updates < 1)
     return fail(DSGD_EINVAL, "bad async plan arguments");
   {   // (refused with *out as it was)
     std::lock_guard<std::mutex> lk0(c->mu);
-    DSGD_TRY(refuse_val64(c, "dsgd_async_plan_create"));
+    if (rp64) {
+      DSGD_TRY(require_fp64(c, what));
+      DSGD_TRY(refuse_fp64_comm(c, what));
+    } else {
+      DSGD_TRY(refuse_val64(c, what));
+    }
   }
   *out = nullptr;
   for (int k = 0; k < n_workers; ++k) {
@@ -5287,9 +5316,9 @@ int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int
   }
   if (n_updates > 0x7fffffffLL) return fail(DSGD_EINVAL, "at most 2^31 - 1 updates per plan");
   std::lock_guard<std::mutex> lk(c->mu);
-  DSGD_TRY(require_fp64(c, "dsgd_async_plan_create"));
-  DSGD_TRY(refuse_fp64_comm(c, "dsgd_async_plan_create"));
-  DSGD_TRY(refuse_val64(c, "dsgd_async_plan_create"));
+  DSGD_TRY(require_fp64(c, what));
+  DSGD_TRY(refuse_fp64_comm(c, what));
+  if (!rp64) DSGD_TRY(refuse_val64(c, what));
   DSGD_TRY(bind(c, true));   // (nothing here touches w)
   for (int k = 0; k < n_workers; ++k)
     if (assigned_end[k] > c->n_rows)
@@ -5298,7 +5327,7 @@ int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int
   std::vector<int64_t> offsets((size_t)n_updates + 1);
   for (int64_t u = 0; u <= n_updates; ++u) offsets[(size_t)u] = u * batch;
   dsgd_plan* p = nullptr;
-  DSGD_TRY(plan_frame(c, offsets.data(), n_updates, 1, &p));
+  DSGD_TRY(plan_frame(c, offsets.data(), n_updates, 1, &p, rp64));
   p->idx_trusted = true;   // (drawn here inside the callers' row ranges)
   p->drawn = true;
   p->fits = false;
@@ -5329,6 +5358,114 @@ int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int
     return fail(DSGD_EHIP, "drawing the async lists: %s", hipGetErrorString(e));
   }
   return plan_finish(c, p, out);
+}
+int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,
+                           uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out) {
+  return async_plan_impl(c, "dsgd_async_plan_create", false, assigned_begin, assigned_end, n_workers, batch, seed, positional_bug, first_update,
+                         n_updates, out);
+}
+int dsgd_async_plan_create_rp64(dsgd_ctx* c, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,
+                                uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out) {
+  return async_plan_impl(c, "dsgd_async_plan_create_rp64", true, assigned_begin, assigned_end, n_workers, batch, seed, positional_bug,
+                         first_update, n_updates, out);
+}
+
+// ---- row-parallel plans (include/dsgd.h "THE FP64 MODE", ROW-PARALLEL PLANS) ----
+// The caller's lists as a row-parallel plan: dsgd_sync_steps_f64's checks, then the lists and their ranges resident.
+int dsgd_plan_create_rp64_n(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const int64_t* offsets, int64_t n_steps, int32_t n_workers,
+                            dsgd_plan** out) {
+  DSGD_TRY(check_ctx(c));
+  if (!idx || !offsets || !out || n_steps < 1 || n_workers < 1 || n_idx < 0) return fail(DSGD_EINVAL, "bad plan arguments (null pointers, no steps or no workers)");
+  if (n_steps > INT64_MAX / n_workers) return fail(DSGD_EINVAL, "n_steps * n_workers overflows");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_plan_create_rp64_n"));
+  DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_create_rp64_n"));
+  DSGD_TRY(bind(c, true));   // (nothing here touches w: slice-major weights stay as they are)
+  const int K = n_workers;
+  const int64_t n_lists = n_steps * K;
+  if (offsets[0] != 0) return fail(DSGD_EINVAL, "offsets[0] must be 0");
+  if (offsets[n_lists] != n_idx)
+    return fail(DSGD_EINVAL, "offsets end at %lld but idx holds %lld entries", (long long)offsets[n_lists], (long long)n_idx);
+  for (int64_t i = 0; i < n_lists; ++i) {
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] > n_idx)
+      return fail(DSGD_EINVAL, "offsets decrease or leave idx at list %lld (step %lld, worker %lld)", (long long)i, (long long)(i / K), (long long)(i % K));
+    if (offsets[i + 1] == offsets[i])
+      return fail(DSGD_EINVAL, "Cannot sum an empty list of vectors (step %lld, worker %lld)", (long long)(i / K), (long long)(i % K));   // ref: math/Vec.scala:129
+  }
+  if (c->d_row_ptr)   // (without data the lists are judged at the first run: plan_revalidate)
+    for (int64_t t = 0; t < n_idx; ++t)
+      if (idx[t] < 0 || idx[t] >= c->n_rows)
+        return fail(DSGD_ERANGE, "sample index %d at position %lld outside the %lld loaded rows", idx[t], (long long)t, c->n_rows);
+  dsgd_plan* p = nullptr;
+  DSGD_TRY(plan_frame(c, offsets, n_steps, n_workers, &p, true));
+  p->h_idx.assign(idx, idx + n_idx);
+  hipError_t e = hipMemcpyAsync(p->d_idx, idx, sizeof(int) * (size_t)n_idx, hipMemcpyHostToDevice, c->build_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->build_stream);
+  if (e != hipSuccess) {
+    plan_abandon(c, p);
+    return fail(DSGD_EHIP, "plan upload: %s", hipGetErrorString(e));
+  }
+  return plan_finish(c, p, out);
+}
+// The steps [step_begin, step_end) of a row-parallel plan (locked, bound with the weights in their layout, revalidated, layout
+// ready): per step rp64_fill over the plan's resident ranges and the pair of dsgd_sync_step_f64 -- or, async, one worker's
+// iteration as dsgd_async_step_f64 takes it on Double data -- enqueued on the launch stream; no upload, no synchronisation.
+// The fused one-launch step is not used: its give-up protocol needs a host read inside the call.
+static int plan_run_rp64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr, bool async) {
+  const int K = p->n_workers;
+  if (p->built_pending) {
+    HIP_TRY(hipStreamWaitEvent(c->stream, p->built_ev, 0));
+    p->built_pending = false;
+  }
+  if (step_end <= step_begin) return DSGD_OK;
+  const bool v64 = c->d_val64 != nullptr;
+  const bool rec = p->d_gate_rec != nullptr;
+  DSGD_TRY(rp64_ensure(c, K));
+  const dim3 th(RP64_THREADS), fg = rp64_finish_grid(c);
+  c->ctr_known = false;   // (n_active runs on until dsgd_synchronize)
+  for (long long t = step_begin; t < step_end; ++t) {
+    long long mx = 0;
+    for (int k = 0; k < K; ++k) mx = std::max<long long>(mx, p->offsets[(size_t)(t * K + k + 1)] - p->offsets[(size_t)(t * K + k)]);
+    const long long bpw = rp64_bpw(c, K, mx);
+    Rp64Args a;
+    Rp64FinishArgs f;
+    rp64_fill(c, K, bpw, async ? RP64_ASYNC : RP64_STEP, lr, nullptr, p->d_idx, p->d_segs + t * K, a, f);
+    if (rec) {   // (the asynchronous iteration's s comes from the sliced kernel below: the record's from the last workgroup here)
+      a.with_s = 1;
+      Rp64Rec r;
+      r.mask = p->d_gate_rec + (size_t)t * p->gate_words;
+      r.s_used = p->d_s_rec + t;
+      r.step_base = p->offsets[(size_t)(t * K)];
+      HIP_TRY(hipMemsetAsync(r.mask, 0, sizeof(unsigned int) * (size_t)p->gate_words, c->stream));
+      const dim3 gg((unsigned)(bpw * K + 1));
+      if (v64)
+        hipLaunchKernelGGL(dsgd_rp64v_grad_rec_kernel, gg, th, 0, c->stream, view64(c), a, r);
+      else
+        hipLaunchKernelGGL(dsgd_rp64_grad_rec_kernel, gg, th, 0, c->stream, view(c), a, r);
+    } else {
+      const dim3 gg((unsigned)(bpw * K + a.with_s));
+      if (v64)
+        hipLaunchKernelGGL(dsgd_rp64v_grad_kernel, gg, th, 0, c->stream, view64(c), a);
+      else
+        hipLaunchKernelGGL(dsgd_rp64_grad_kernel, gg, th, 0, c->stream, view(c), a);
+    }
+    if (async) {
+      hipLaunchKernelGGL(dsgd_rp64v_s_sliced_kernel, dim3(1), dim3(CS_THREADS), 0, c->stream, a.w, c->d_ds64, a.Sp, c->dp, c->cfg.lambda, c->d_rp64_s);
+      if (v64)
+        hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64_ASYNC>, fg, th, 0, c->stream, f);
+      else
+        hipLaunchKernelGGL(dsgd_rp64_finish_async_kernel, fg, th, 0, c->stream, f);
+    } else if (v64) {
+      hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64_STEP>, fg, th, 0, c->stream, f);
+    } else {
+      hipLaunchKernelGGL(dsgd_rp64_finish_kernel<true>, fg, th, 0, c->stream, f);
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  c->last_grad_kernel = rec ? (v64 ? "dsgd_rp64v_grad_rec_kernel" : "dsgd_rp64_grad_rec_kernel") : (v64 ? "dsgd_rp64v_grad_kernel" : "dsgd_rp64_grad_kernel");
+  c->s_dirty = true;
+  c->pending_samples += p->offsets[(size_t)(step_end * K)] - p->offsets[(size_t)(step_begin * K)];
+  return DSGD_OK;
 }
 
 static int forward_run(dsgd_ctx* c, const int32_t* idx, int64_t n, float* pred_out);

@@ -12,13 +12,14 @@
 //                               last workgroup of the grid computes s = lambda * 2 * (w . ds) meanwhile (with_s).
 //   rp64_finish_body<V, MODE>   per column: ONE rounding of each worker's exact sum, the support-only regulariser, and
 //                               the gradient in key order (GRADIENT), the step's fold over the workers, mean and update
-//                               (STEP), or one worker's asynchronous iteration and its delta (ASYNC; Double values only:
-//                               float data's runs in dsgd_cs64_async_kernel) -- oracle/oracle.c orc_gradient /
+//                               (STEP), or one worker's asynchronous iteration and its delta (ASYNC; on float values only for
+//                               row-parallel plans: float data's per-call step runs in dsgd_cs64_async_kernel) -- oracle/oracle.c orc_gradient /
 //                               orc_sync_step / orc_async_step, operation for operation; the accumulators are left zeroed
 //                               for the next call.
 // The kernels are thin wrappers with stable names: dsgd_rp64_grad_kernel, dsgd_rp64_grad_gather_kernel,
 // dsgd_rp64_finish_kernel<STEP> (float values), dsgd_rp64v_grad_kernel, dsgd_rp64v_grad_gather_kernel,
-// dsgd_rp64v_finish_kernel<MODE> (Double values).
+// dsgd_rp64v_finish_kernel<MODE> (Double values); for row-parallel plans (dsgd_plan_create_rp64_n and its kin) also
+// dsgd_rp64_grad_rec_kernel / dsgd_rp64v_grad_rec_kernel (the gate record) and dsgd_rp64_finish_async_kernel.
 //
 // Under a communicator ("across ranks" below: dsgd_comm_init_f64 on float values, dsgd_comm_init_f64v on either type) the
 // sums go into this rank's slots of a gather buffer (GATHER: dsgd_rp64_grad_gather_kernel, dsgd_rp64v_grad_gather_kernel),
@@ -119,8 +120,20 @@ struct Rp64Args {
 // per word of a column sum, acc[1] = acc[0] + the plane's stride, acc_stride the slot's) -- the header words behind plane 0's
 // sums get the list length and the active count, the rank's word gets K and the value type, all with ordinary stores /
 // vector atomics
-template <typename V, bool GATHER>
-__device__ __forceinline__ void rp64_grad_body(const CsrViewT<V>& m, const Rp64Args& a) {
+//
+// RECORD (the steps of a row-parallel plan under dsgd_plan_record; dsgd_rp64_grad_rec_kernel, dsgd_rp64v_grad_rec_kernel): the
+// gate's decision of every listed row goes into the step's mask words -- bit (seg.begin - step_base + t) for entry t of the
+// worker's list, i.e. the rows of the step in worker order, each list in order -- with a 32-bit vector atomic OR by lane 0
+// of the row's group (the host zeroes the words on the stream in front of the step), and the last workgroup stores
+// (float)s into the step's slot.  Nothing of the dots, the gate or the integer sums changes: the weights are the bits of
+// the unrecorded kernels.  RECORD = false never reads `rec`.
+struct Rp64Rec {
+  unsigned int* mask;      // the step's ceil(max_step_rows / 32) words, zero on entry
+  float* s_used;           // the step's slot of the s record
+  long long step_base;     // position in idx of the step's first entry (worker 0's seg.begin)
+};
+template <typename V, bool GATHER, bool RECORD = false>
+__device__ __forceinline__ void rp64_grad_body(const CsrViewT<V>& m, const Rp64Args& a, const Rp64Rec& rec = Rp64Rec{}) {
 #pragma clang fp contract(off)
   constexpr int WORDS = Rp64Acc<V>::WORDS;
   static_assert(WORDS <= RP64_MAX_WORDS, "a gather slot holds one plane per word of a column sum");
@@ -138,6 +151,14 @@ __device__ __forceinline__ void rp64_grad_body(const CsrViewT<V>& m, const Rp64A
     for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
+    if (RECORD) {
+      if (tid == 0) {
+        const double s = a.lambda * 2.0 * ((red[0] + red[1]) + (red[2] + red[3]));
+        *a.s_out = s;
+        *rec.s_used = (float)s;
+      }
+      return;
+    }
     if (tid == 0) *a.s_out = a.lambda * 2.0 * ((red[0] + red[1]) + (red[2] + red[3]));   // ref: core/ml/SparseSVM.scala:31
     if (GATHER && tid == 0) *a.rank_word = rp64_rank_word(a.K, WORDS == 2);
     return;
@@ -169,6 +190,10 @@ __device__ __forceinline__ void rp64_grad_body(const CsrViewT<V>& m, const Rp64A
     const double y = (double)m.label[row];
     if (y * d < 0.0) continue;                                   // ref: core/ml/SparseSVM.scala:27-28 (zerosLike)
     mine += sub == 0 ? 1u : 0u;
+    if (RECORD && sub == 0) {
+      const long long bit = seg.begin - rec.step_base + t;
+      atomicOr(&rec.mask[bit >> 5], 1u << (unsigned int)(bit & 31));
+    }
     const double cq = y > 0.0 ? qscale : -qscale;
     const long long st = m.row_ptr[row], en = m.row_ptr[row + 1];
     for (long long p = st + sub; p < en; p += RP64_GROUP) {
@@ -207,6 +232,8 @@ __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_kernel(CsrView m,
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_gather_kernel(CsrView m, Rp64Args a) { rp64_grad_body<float, true>(m, a); }
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_grad_kernel(CsrView64 m, Rp64Args a) { rp64_grad_body<double, false>(m, a); }
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_grad_gather_kernel(CsrView64 m, Rp64Args a) { rp64_grad_body<double, true>(m, a); }
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_rec_kernel(CsrView m, Rp64Args a, Rp64Rec rec) { rp64_grad_body<float, false, true>(m, a, rec); }
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_grad_rec_kernel(CsrView64 m, Rp64Args a, Rp64Rec rec) { rp64_grad_body<double, false, true>(m, a, rec); }
 
 struct Rp64FinishArgs {
   unsigned long long* acc[RP64_MAX_WORDS];   // per word [K][acc_stride], zeroed here
@@ -280,6 +307,11 @@ __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_finish_kernel(Rp64Fini
 template <int MODE>
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_finish_kernel(Rp64FinishArgs a) {
   rp64_finish_body<double, MODE>(a, blockDim.x);
+}
+// one worker's asynchronous iteration on FLOAT values: an asynchronous row-parallel plan (dsgd_async_plan_create_rp64) beyond
+// what dsgd_cs64_async_kernel holds; s from dsgd_rp64v_s_sliced_kernel, as on Double values
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_finish_async_kernel(Rp64FinishArgs a) {
+  rp64_finish_body<float, RP64_ASYNC>(a, blockDim.x);
 }
 
 // Behind the gather, ONE workgroup: the K headers become the list ranges the finish takes its shifts from ({0, n}), the

@@ -27,15 +27,17 @@ class Plan:
 
     def info(self):
         """How the plan will run: kind ('column_slices', 'one_workgroup', 'virtual_tiles', 'row_parallel', 'not_laid_out')
-        and, for column slices, the layout's shape; see dsgd_plan_info."""
+        and, for column slices, the layout's shape ('row_parallel_fp64': a plan made with rp64=True); see dsgd_plan_info."""
         v = (C.c_int32 * 8)()
         check(_lib.load().dsgd_plan_info(self.engine._ctx, self.handle, v, C.c_int32(8)))
-        kinds = {0: "not_laid_out", 1: "column_slices", 2: "one_workgroup", 3: "virtual_tiles", 4: "row_parallel", 5: "column_slices_fp64"}
+        kinds = {0: "not_laid_out", 1: "column_slices", 2: "one_workgroup", 3: "virtual_tiles", 4: "row_parallel", 5: "column_slices_fp64",
+                 6: "row_parallel_fp64"}
         return {"kind": kinds.get(int(v[0]), "?"), "slices": int(v[1]), "slot_stride": int(v[2]), "row_stride": int(v[3]),
                 "col_list_stride": int(v[4]), "slots_per_lane": int(v[5]), "device_built": bool(v[6]), "record_words": int(v[7])}
 
     def record(self, on=True):
-        """Keep the gate decision of every row and the regulariser scalar of every step this plan runs (column slices)."""
+        """Keep the gate decision of every row and the regulariser scalar of every step this plan runs (column slices and
+        row-parallel fp64 plans)."""
         check(_lib.load().dsgd_plan_record(self.engine._ctx, self.handle, C.c_int32(1 if on else 0)))
 
     def read_record(self, step_begin=0, step_end=None):
@@ -248,8 +250,9 @@ class Engine:
         check(self._lib.dsgd_synchronize(self._ctx, C.byref(st)))
         return {"n_samples": st.n_samples, "n_active": st.n_active}
 
-    def plan(self, steps):
-        """steps: list (per step) of lists (per worker) of index arrays."""
+    def plan(self, steps, rp64=False):
+        """steps: list (per step) of lists (per worker) of index arrays.  rp64=True (fp64 engines): a row-parallel plan
+        (dsgd_plan_create_rp64_n) -- any number of workers, any list length, any D, float or Double data."""
         n_steps = len(steps)
         n_workers = len(steps[0]) if n_steps else 0
         flat, offs = [], [0]
@@ -263,10 +266,11 @@ class Engine:
         idx = np.concatenate(flat) if flat else np.zeros(0, np.int32)
         offsets = np.asarray(offs, dtype=np.int64)
         h = C.c_void_p()
-        check(self._lib.dsgd_plan_create_n(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers), C.byref(h)))
+        create = self._lib.dsgd_plan_create_rp64_n if rp64 else self._lib.dsgd_plan_create_n
+        check(create(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers), C.byref(h)))
         return Plan(self, h, n_steps, n_workers, int(offsets[-1]))
 
-    def plan_flat(self, idx, offsets, n_steps, n_workers):
+    def plan_flat(self, idx, offsets, n_steps, n_workers, rp64=False):
         """A plan from the flat form: idx = all lists concatenated (step-major, worker-minor), offsets = n_steps * n_workers
         + 1 prefix offsets (what host.epoch_lists returns: one epoch of Master.fit)."""
         idx = i32(idx)
@@ -274,21 +278,24 @@ class Engine:
         if len(offsets) != n_steps * n_workers + 1 or (n_steps and int(offsets[-1]) != len(idx)):
             raise ValueError("offsets do not describe %d x %d lists over %d entries" % (n_steps, n_workers, len(idx)))
         h = C.c_void_p()
-        check(self._lib.dsgd_plan_create_n(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers), C.byref(h)))
+        create = self._lib.dsgd_plan_create_rp64_n if rp64 else self._lib.dsgd_plan_create_n
+        check(create(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers), C.byref(h)))
         return Plan(self, h, n_steps, n_workers, int(offsets[-1]))
 
-    def plan_from_seed(self, jstate, split, max_samples, batch_size):
+    def plan_from_seed(self, jstate, split, max_samples, batch_size, rp64=False):
         """One epoch of Master.fit as a plan whose lists the DEVICE draws, draw for draw the reference's stream
         (dsgd_plan_create_from_seed).  jstate: java.util.Random's internal 48-bit state in front of the epoch; split: the
         workers' row ranges (SplitStrategy.vanilla).  Returns (plan or None, n_steps, new jstate, draws); raises
-        DsgdError with code EUNSUPPORTED when the device form does not apply (draw the lists on the host then)."""
+        DsgdError with code EUNSUPPORTED when the device form does not apply (draw the lists on the host then).
+        rp64=True (fp64 engines): the same lists as a row-parallel plan (dsgd_plan_create_from_seed_rp64)."""
         sb = np.asarray([r.start if isinstance(r, range) else r[0] for r in split], dtype=np.int64)
         se = np.asarray([r.stop if isinstance(r, range) else r[1] for r in split], dtype=np.int64)
         st = C.c_uint64(int(jstate))
         h = C.c_void_p()
         n_steps, draws = C.c_int64(0), C.c_int64(0)
-        check(self._lib.dsgd_plan_create_from_seed(self._ctx, C.byref(st), ptr(sb), ptr(se), C.c_int32(len(sb)), C.c_int64(max_samples),
-                                                   C.c_int32(batch_size), C.byref(h), C.byref(n_steps), C.byref(draws)))
+        create = self._lib.dsgd_plan_create_from_seed_rp64 if rp64 else self._lib.dsgd_plan_create_from_seed
+        check(create(self._ctx, C.byref(st), ptr(sb), ptr(se), C.c_int32(len(sb)), C.c_int64(max_samples),
+                     C.c_int32(batch_size), C.byref(h), C.byref(n_steps), C.byref(draws)))
         if not h.value:
             return None, 0, int(st.value), 0
         total = int(sum(min(batch_size, int(e - b) - s_ * batch_size) for s_ in range(n_steps.value) for b, e in zip(sb, se)))
@@ -411,17 +418,18 @@ class Engine:
                                                    C.c_int64(self.dp), C.byref(nnz), C.byref(st)))
         return k[:nnz.value].copy(), v[:nnz.value].copy(), {"n_samples": st.n_samples, "n_active": st.n_active}
 
-    def async_plan(self, assigned_ranges, batch, seed=0, positional_bug=True, first_update=0, n_updates=1):
+    def async_plan(self, assigned_ranges, batch, seed=0, positional_bug=True, first_update=0, n_updates=1, rp64=False):
         """fp64 engines: updates [first_update, first_update + n_updates) of the zero-lag asynchronous schedule as a
         one-worker plan whose lists the device draws (dsgd_async_plan_create): update u is worker u mod K at its
-        iteration u div K, with the rows the lock-free engine's worker draws there (oracle/hogwild_replay.hog_rows)."""
+        iteration u div K, with the rows the lock-free engine's worker draws there (oracle/hogwild_replay.hog_rows).
+        rp64=True: the same lists as a row-parallel plan (dsgd_async_plan_create_rp64: Double data, any batch, any D)."""
         k = len(assigned_ranges)
         rb = (C.c_int64 * max(k, 1))(*[int(r[0]) for r in assigned_ranges])
         re_ = (C.c_int64 * max(k, 1))(*[int(r[1]) for r in assigned_ranges])
         h = C.c_void_p()
-        check(self._lib.dsgd_async_plan_create(self._ctx, rb, re_, C.c_int32(k), C.c_int32(batch), C.c_uint64(seed),
-                                               C.c_int32(1 if positional_bug else 0), C.c_int64(first_update),
-                                               C.c_int64(n_updates), C.byref(h)))
+        create = self._lib.dsgd_async_plan_create_rp64 if rp64 else self._lib.dsgd_async_plan_create
+        check(create(self._ctx, rb, re_, C.c_int32(k), C.c_int32(batch), C.c_uint64(seed), C.c_int32(1 if positional_bug else 0),
+                     C.c_int64(first_update), C.c_int64(n_updates), C.byref(h)))
         return Plan(self, h, int(n_updates), 1, int(n_updates) * int(batch))
 
     def plan_run_async(self, plan, step_begin, step_end, lr):

@@ -431,6 +431,21 @@ class HostAsyncExchange:
 # MasterSync._run_steps_f64: "1" = an epoch's refused fp64 plan runs as ONE Engine.sync_steps_f64 call, "0" = one sync_step_f64
 # call per step (DSGD_F64_STEPS overrides).  The batched call has not been measured yet: the default stays the loop
 F64_STEPS_DEFAULT = "0"
+# DSGD_F64_RP_PLANS=1: what an fp64 backend's column-slice plans refuse (Double feature values, more than 4 workers or 1,024
+# rows per step, a model beyond a slice's LDS) runs as a resident ROW-PARALLEL plan (Engine.plan_from_seed / plan_flat /
+# async_plan with rp64=True; include/dsgd.h "THE FP64 MODE", ROW-PARALLEL PLANS) -- the same lists and the same bits, no upload
+# per epoch, and MasterAsync.fit works on Double data.  Measured (50 us per 3 x 100 step on Double data against
+# 122 us through sync_steps_f64 with host-drawn lists); off by default because the mirrors' behaviour on Double data is pinned
+F64_RP_PLANS_DEFAULT = "0"
+
+
+def _f64_rp_plans() -> bool:
+    return os.environ.get("DSGD_F64_RP_PLANS", F64_RP_PLANS_DEFAULT) == "1"
+
+class _Refused(RuntimeError):
+    """(MasterSync._make_plan: the column-slice plan of this fit was refused before)"""
+    code = -7
+
 
 # ---- Master.fit (synchronous) ---------------------------------------------------------------------------------
 class MasterSync:
@@ -470,6 +485,8 @@ class MasterSync:
         self._pending = None
         self._lists_future = None
         self._executor = None
+        self._rp_plans = False       # DSGD_F64_RP_PLANS=1 and an fp64 plan was refused: row-parallel plans from here on
+        self._rp_seed_ok = True      # ... their lists drawn by the device until it refuses
         self.batch_loop_s = 0.0      # wall time of the batch loops (shuffles, plan set-up, steps): Master.scala:179-199
         self.shuffle_s = 0.0         # ... of which drawing the lists (not overlapped by prefetch: see fit)
         self.steps_run = 0
@@ -534,19 +551,55 @@ class MasterSync:
             self._executor = ThreadPoolExecutor(max_workers=1, thread_name_prefix="dsgd-lists")
         self._lists_future = self._executor.submit(self._draw_lists, split, max_samples, batch_size)
 
-    def _make_plan(self, lists, n_workers):
+    def _make_plan(self, lists, n_workers, split=None, max_samples=0, batch_size=0):
         entry = {"plan": None, "n_steps": lists["n_steps"], "n_samples": int(lists["offsets"][lists["n_steps"] * n_workers]),
                  "seed_before": lists["seed_before"]}
         if lists["n_steps"]:
             try:
+                if self._rp_plans:   # (refused before: not asked again)
+                    raise _Refused()
                 entry["plan"] = self.backend.plan_flat(lists["idx"], lists["offsets"], lists["n_steps"], n_workers)
             except Exception as e:
                 # an fp64 backend refuses plans beyond its column-slice limits (DSGD_EUNSUPPORTED: more than 4 workers or
                 # 1,024 rows per step): the epoch's steps run one by one through sync_step_f64, on the same lists
                 if getattr(e, "code", None) != -7 or not self._fp64_steps():
                     raise
+                if _f64_rp_plans():
+                    # DSGD_F64_RP_PLANS=1: a row-parallel plan instead -- the device draws the lists the host has just drawn (the
+                    # same stream from the same state: the generator stays where the host left it), else the host's go up
+                    self._rp_plans = True
+                    rp = self._rp64_from_seed(lists["seed_before"], split, max_samples, batch_size) if split is not None else None
+                    if rp is not None and rp["n_steps"] == lists["n_steps"]:
+                        entry["plan"] = rp["plan"]
+                        return entry
+                    if rp is not None and rp["plan"] is not None:
+                        rp["plan"].destroy()
+                    try:
+                        entry["plan"] = self.backend.plan_flat(lists["idx"], lists["offsets"], lists["n_steps"], n_workers, rp64=True)
+                        return entry
+                    except Exception as e2:
+                        if getattr(e2, "code", None) != -7:
+                            raise
                 entry["lists"] = lists
         return entry
+
+    def _rp64_from_seed(self, seed_before, split, max_samples, batch_size):
+        """The epoch in front of generator state seed_before as a row-parallel plan whose lists the device draws
+        (Engine.plan_from_seed(rp64=True)); None where that does not apply or is refused (DSGD_EUNSUPPORTED)."""
+        if not (self._rp_seed_ok and hasattr(self.backend, "plan_from_seed") and os.environ.get("DSGD_DEVICE_LISTS", "1") != "0"
+                and all(r.step == 1 for r in split)):
+            return None
+        t0 = time.perf_counter()
+        try:
+            plan, n_steps, state, _ = self.backend.plan_from_seed(seed_before, split, max_samples, batch_size, rp64=True)
+        except Exception as e:
+            if getattr(e, "code", None) != -7:
+                raise
+            self._rp_seed_ok = False
+            return None
+        self.shuffle_s += time.perf_counter() - t0
+        return {"plan": plan, "n_steps": n_steps, "n_samples": plan.n_samples if plan is not None else 0, "seed_before": seed_before,
+                "state": state}
 
     def _fp64_steps(self):
         return getattr(self.backend, "precision", "fp32") == "fp64" and hasattr(self.backend, "sync_step_f64")
@@ -574,7 +627,13 @@ class MasterSync:
     def _next_plan(self, split, max_samples, batch_size, n_workers, ahead_ok=False):
         """The next epoch as a plan: its lists drawn by the device where that applies, else by the host (csrc/jrand.c)."""
         draws = len(range(0, max_samples, batch_size)) * sum(len(r) - 1 for r in split)
-        if self.device_lists and draws >= self.device_lists_min_draws and all(r.step == 1 for r in split):
+        if self._rp_plans and getattr(self, "_lists_future", None) is None:   # (no draw of the host's is under way)
+            seed_before = self.rnd.seed
+            rp = self._rp64_from_seed(seed_before, split, max_samples, batch_size)
+            if rp is not None:
+                self.rnd.seed = rp.pop("state")
+                return rp
+        if not self._rp_plans and self.device_lists and draws >= self.device_lists_min_draws and all(r.step == 1 for r in split):
             seed_before = self.rnd.seed
             t0 = time.perf_counter()
             try:
@@ -583,6 +642,12 @@ class MasterSync:
                 if getattr(e, "code", None) != -7:
                     raise
                 self.device_lists = False
+                if _f64_rp_plans() and self._fp64_steps():   # (DSGD_F64_RP_PLANS=1: the same draws into a row-parallel plan)
+                    self._rp_plans = True
+                    rp = self._rp64_from_seed(seed_before, split, max_samples, batch_size)
+                    if rp is not None:
+                        self.rnd.seed = rp.pop("state")
+                        return rp
             else:
                 self.rnd.seed = state
                 self.shuffle_s += time.perf_counter() - t0
@@ -590,7 +655,7 @@ class MasterSync:
         lists = self._take_lists(split, max_samples, batch_size)
         if ahead_ok and lists["n_steps"] == len(range(0, max_samples, batch_size)):
             self._draw_ahead(split, max_samples, batch_size)
-        return self._make_plan(lists, n_workers)
+        return self._make_plan(lists, n_workers, split, max_samples, batch_size)
 
     def _epoch_through_a_plan(self, split, max_samples, batch_size, learning_rate, epochs_left):
         """One epoch's batch loop (core/Master.scala:179-199) as one resident plan."""
@@ -728,12 +793,12 @@ class MasterAsync:
         steps = self.n_train * max_epoch if max_steps is None else max_steps
         if getattr(self.backend, "precision", "fp32") == "fp64":
             value_bits = getattr(self.backend, "value_bits", None)
-            if value_bits is not None and value_bits() == 64:
+            if value_bits is not None and value_bits() == 64 and not _f64_rp_plans():
                 # the zero-lag schedule runs resident asynchronous plans (column slices), which hold float values
                 raise NotImplementedError(
                     "MasterAsync.fit is not available on Double feature values (Engine.load_csr with float64 values): resident "
                     "asynchronous plans are refused there (include/dsgd.h \"THE FP64 MODE\"); async_step_f64 serves single "
-                    "iterations, or load float32 values")
+                    "iterations, DSGD_F64_RP_PLANS=1 runs the schedule on row-parallel plans, or load float32 values")
             return self._fit_fp64(initial_weights, split, steps, batch_size, learning_rate, stopping_criterion, check_every,
                                   leak_loss_coef, seed, positional_bug)
         self.backend.set_weights(np.asarray(initial_weights, dtype=np.float32))
@@ -794,6 +859,7 @@ class MasterAsync:
         best_w, best_loss = w0.copy(), float("inf")
         updates, plan, plan_first = 0, None, 0
         chunk = max(self.FP64_CHUNK, check_every)
+        rp64 = False   # DSGD_F64_RP_PLANS=1: from the first refused plan on (Double data, a batch or a model beyond the column slices)
         try:
             while True:
                 loss = self._check(leak_loss_coef)
@@ -810,8 +876,14 @@ class MasterAsync:
                         if plan is not None:
                             plan.destroy()
                         plan_first = updates
-                        plan = self.backend.async_plan(split, batch_size, seed=seed, positional_bug=positional_bug,
-                                                       first_update=plan_first, n_updates=min(chunk, steps - plan_first))
+                        kw = dict(seed=seed, positional_bug=positional_bug, first_update=plan_first, n_updates=min(chunk, steps - plan_first))
+                        try:
+                            plan = self.backend.async_plan(split, batch_size, rp64=True, **kw) if rp64 else self.backend.async_plan(split, batch_size, **kw)
+                        except Exception as e:
+                            if rp64 or getattr(e, "code", None) != -7 or not _f64_rp_plans():
+                                raise
+                            rp64 = True
+                            plan = self.backend.async_plan(split, batch_size, rp64=True, **kw)
                     end = min(target, plan_first + plan.n_steps)
                     self.backend.plan_run_async(plan, updates - plan_first, end - plan_first, learning_rate)
                     updates = end

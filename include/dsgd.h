@@ -186,6 +186,32 @@ enum {
  *   attached (the gather needs a host read per step: dsgd_sync_step_f64 stays the path there); DSGD_EINVAL for null
  *   pointers, n_steps < 1, n_workers < 1, offsets that do not start at 0, decrease or do not end at n_idx, and an empty
  *   list of any step; DSGD_ERANGE for a row index outside the loaded rows in any step.
+ *   ROW-PARALLEL PLANS (dsgd_plan_create_rp64_n, dsgd_plan_create_from_seed_rp64, dsgd_async_plan_create_rp64, declared
+ *   behind dsgd_plan_run_async_f64; csrc/dsgd_rp64.hpp).  Everything the column-slice plans refuse had no resident form:
+ *   more than 4 workers, more than 1,024 rows per step, a model beyond a slice's LDS, Double feature values.  These three
+ *   creators take their twins' arguments and return an ordinary dsgd_plan* that holds only the lists and their ranges on
+ *   the device.  NO layout is built: whether a run reads float or Double values is decided at each run from the data
+ *   loaded then, so one plan serves both and outlives a reload between them (re-validated like any plan: DSGD_ERANGE
+ *   before anything is enqueued while an index lies outside the loaded rows).  Any n_workers >= 1, any list length, any
+ *   D.  _from_seed_rp64 and dsgd_async_plan_create_rp64 draw the lists of their twins entry for entry and leave the same
+ *   *jstate and *draws_out; _from_seed_rp64 keeps the device shuffle's limits (DSGD_EUNSUPPORTED, *jstate untouched).
+ *   dsgd_plan_run_f64 (dsgd_plan_run: its float lr promoted) enqueues, per step, the two launches of dsgd_sync_step_f64
+ *   over the plan's resident ranges -- no upload, no host synchronisation; dsgd_synchronize collects the statistics --
+ *   and gives bit for bit dsgd_sync_steps_f64 on the same lists, however the steps are cut into calls; the weights stay
+ *   in the layout they are found in.  The fused one-launch step is NOT used: its give-up protocol needs a host read
+ *   inside the call, and an enqueue-only entry point has none.  dsgd_plan_run_async_f64 (one-worker plans): per step
+ *   dsgd_rp64v_s_sliced_kernel, the gradient kernel and the asynchronous finish -- on Double data bit for bit a loop of
+ *   dsgd_async_step_f64 over the lists; on float data dsgd_rp64_finish_async_kernel, which also serves batches above 1,024
+ *   rows and models beyond 100,847 features.  dsgd_plan_record: the documented format (bit r = row r of the step, workers
+ *   in order; ceil(max_step_rows / 32) words per step; s_used = (float)s), written by dsgd_rp64_grad_rec_kernel /
+ *   dsgd_rp64v_grad_rec_kernel with vector atomics into words zeroed on the stream in front of each step (a step run
+ *   again overwrites its record); the weights are the bits of an unrecorded run.  In an asynchronous run s_used is the
+ *   float rounding of s summed in rank order, the iteration itself uses the slice-order sum (they differ in the last bits
+ *   of the double).  dsgd_plan_info: vals[0] = 6, strides 0, [7] words per step of the record.  dsgd_grad_kernel_name
+ *   names the gradient kernel of the last run.  Refused, nothing changed, the context usable: DSGD_ESTATE on an fp32
+ *   context; DSGD_EUNSUPPORTED with a communicator attached; DSGD_EINVAL / DSGD_ERANGE as dsgd_sync_steps_f64 (null
+ *   pointers, an empty list, offsets that are no prefix sum ending at n_idx; a row index outside the rows loaded, where
+ *   data is loaded).  The existing creators refuse exactly as before.
  * The entry points below that name fp64 return DSGD_ESTATE on an fp32 context (dsgd_precision excepted).            */
 
 typedef struct dsgd_ctx dsgd_ctx;
@@ -381,7 +407,8 @@ int dsgd_plan_run(dsgd_ctx* ctx, dsgd_plan* plan, int64_t step_begin, int64_t st
 /* the same in an fp64 context, with the reference's Double learning rate (DSGD_ESTATE on an fp32 context)           */
 int dsgd_plan_run_f64(dsgd_ctx* ctx, dsgd_plan* plan, int64_t step_begin, int64_t step_end, double lr);
 /* How a plan will run (nothing in the reference; benchmarks, tests): vals[0] = 1 column slices (dsgd_cs_step_kernel),
- * 2 the one-workgroup kernel, 3 virtual tiles, 4 the row-parallel kernels, 0 not laid out yet; [1] slices, [2..4] slot /
+ * 2 the one-workgroup kernel, 3 virtual tiles, 4 the row-parallel kernels, 5 fp64 column slices, 6 a row-parallel fp64
+ * plan (dsgd_plan_create_rp64_n and its kin: strides 0), 0 not laid out yet; [1] slices, [2..4] slot /
  * row / column-list strides, [5] slots per lane, [6] 1 if the device laid it out, [7] words per step of the record.
  * n <= 8 slots.                                                                                                       */
 int dsgd_plan_info(dsgd_ctx* ctx, dsgd_plan* plan, int32_t* vals, int32_t n);
@@ -444,6 +471,17 @@ int dsgd_async_plan_create(dsgd_ctx* ctx, const int64_t* assigned_begin, const i
                            int32_t batch, uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates,
                            dsgd_plan** out);
 int dsgd_plan_run_async_f64(dsgd_ctx* ctx, dsgd_plan* plan, int64_t step_begin, int64_t step_end, double lr);
+/* Row-parallel plans ("THE FP64 MODE", ROW-PARALLEL PLANS): the arguments of dsgd_plan_create_n,
+ * dsgd_plan_create_from_seed and dsgd_async_plan_create; fp64 contexts only, float or Double data, any number of workers,
+ * any list length, any D.  The plan runs through dsgd_plan_run / _f64 / _async_f64 like any other.                    */
+int dsgd_plan_create_rp64_n(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const int64_t* offsets, int64_t n_steps,
+                            int32_t n_workers, dsgd_plan** out);
+int dsgd_plan_create_from_seed_rp64(dsgd_ctx* ctx, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end,
+                                    int32_t n_splits, int64_t max_samples, int32_t batch_size, dsgd_plan** out,
+                                    int64_t* n_steps_out, int64_t* draws_out);
+int dsgd_async_plan_create_rp64(dsgd_ctx* ctx, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers,
+                                int32_t batch, uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates,
+                                dsgd_plan** out);
 
 /* ---- SPARSE VALUES at the boundary (csrc/dsgd_sparse.hpp) --------------------------------------
  * The reference exchanges Sparse{map<int32, double>, size} values only (proto.proto:28-31) and stores no entry with

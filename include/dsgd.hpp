@@ -211,6 +211,48 @@ class SparseSVM {
                               activePerStep ? activePerStep->data() : nullptr, &st));
     return st;
   }
+  // Row-parallel plans of the fp64 mode (include/dsgd.h "THE FP64 MODE", ROW-PARALLEL PLANS): what the column-slice plans
+  // refuse -- Double feature values, more than 4 workers, more than 1,024 rows per step, a model beyond a slice's LDS -- as
+  // a resident plan; dsgd_plan_run_f64 / dsgd_plan_run_async_f64 / dsgd_plan_destroy take the handle like any other.
+  // planRp64: syncStepsF64's flat lists.
+  dsgd_plan* planRp64(const std::vector<int32_t>& idx, const std::vector<int64_t>& offsets, int nWorkers) {
+    if (nWorkers < 1 || offsets.empty() || (offsets.size() - 1) % (size_t)nWorkers != 0)
+      throw IllegalArgumentException("requirement failed");   // offsets hold nSteps * nWorkers + 1 entries
+    dsgd_plan* plan = nullptr;
+    check(dsgd_plan_create_rp64_n(ctx_, idx.data(), (int64_t)idx.size(), offsets.data(), (int64_t)((offsets.size() - 1) / (size_t)nWorkers),
+                                  nWorkers, &plan));
+    return plan;
+  }
+  // planFromSeedRp64: one epoch of Master.fit, the lists drawn by the device from rnd's stream (left where the JVM's generator
+  // would stand); split = the workers' row ranges.  Returns the plan (null: no step) and *nSteps.
+  dsgd_plan* planFromSeedRp64(JavaRandom& rnd, const std::vector<std::pair<int64_t, int64_t>>& split, int64_t maxSamples, int batchSize,
+                              int64_t* nSteps) {
+    std::vector<int64_t> sb, se;
+    for (const auto& r : split) {
+      sb.push_back(r.first);
+      se.push_back(r.second);
+    }
+    uint64_t st = rnd.state();
+    dsgd_plan* plan = nullptr;
+    int64_t n = 0;
+    check(dsgd_plan_create_from_seed_rp64(ctx_, &st, sb.data(), se.data(), (int32_t)split.size(), maxSamples, batchSize, &plan, &n, nullptr));
+    rnd.setState(st);
+    if (nSteps) *nSteps = n;
+    return plan;
+  }
+  // asyncPlanRp64: updates [firstUpdate, firstUpdate + nUpdates) of the zero-lag asynchronous schedule, one worker per step
+  dsgd_plan* asyncPlanRp64(const std::vector<std::pair<int64_t, int64_t>>& assigned, int batch, uint64_t seed, bool positionalBug,
+                           int64_t firstUpdate, int64_t nUpdates) {
+    std::vector<int64_t> ab, ae;
+    for (const auto& r : assigned) {
+      ab.push_back(r.first);
+      ae.push_back(r.second);
+    }
+    dsgd_plan* plan = nullptr;
+    check(dsgd_async_plan_create_rp64(ctx_, ab.data(), ae.data(), (int32_t)assigned.size(), batch, seed, positionalBug ? 1 : 0, firstUpdate,
+                                      nUpdates, &plan));
+    return plan;
+  }
   // Main.scala:54-65: dimSparsity from the first nTrain rows (incl. its off-by-one)
   Vec buildDimSparsity(int64_t nTrain) {
     Vec ds((size_t)d_ + 1);

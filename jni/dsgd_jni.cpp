@@ -378,7 +378,7 @@ JNIEXPORT jlong JNICALL NATIVE(syncStep)(JNIEnv* env, jobject, jlong h, jobjectA
 // nWorkers + 1 prefix offsets.  planRun(0, nSteps) then runs the whole epoch in ONE launch of the column-slice kernel
 // (5 us per 3 x 100 batch against 40 us per syncStep call); planCreate lays the lists out on the device beside whatever is
 // running, so the next epoch's plan can be created while this epoch's batches run.
-JNIEXPORT jlong JNICALL NATIVE(planCreate)(JNIEnv* env, jobject, jlong h, jintArray idx, jlongArray offsets, jint nWorkers) {
+static jlong plan_create(JNIEnv* env, jlong h, jintArray idx, jlongArray offsets, jint nWorkers, bool rp64) {
   const jsize nOff = env->GetArrayLength(offsets);
   if (nWorkers < 1 || nOff < 1 || (nOff - 1) % nWorkers != 0) {
     env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "offsets must hold nSteps * nWorkers + 1 entries");
@@ -390,14 +390,23 @@ JNIEXPORT jlong JNICALL NATIVE(planCreate)(JNIEnv* env, jobject, jlong h, jintAr
     IntElems iv(env, idx, JNI_ABORT);
     LongElems ov(env, offsets, JNI_ABORT);
     // (the stated length: offsets that end beyond the pinned array are refused instead of read)
-    rc = dsgd_plan_create_n(ctx(h), reinterpret_cast<const int32_t*>(iv.p), (int64_t)env->GetArrayLength(idx),
-                            reinterpret_cast<const int64_t*>(ov.p), (nOff - 1) / nWorkers, nWorkers, &plan);
+    rc = (rp64 ? dsgd_plan_create_rp64_n : dsgd_plan_create_n)(ctx(h), reinterpret_cast<const int32_t*>(iv.p), (int64_t)env->GetArrayLength(idx),
+                                                               reinterpret_cast<const int64_t*>(ov.p), (nOff - 1) / nWorkers, nWorkers, &plan);
   }
   if (rc) {
     raise(env, rc);
     return 0;
   }
   return reinterpret_cast<jlong>(plan);
+}
+JNIEXPORT jlong JNICALL NATIVE(planCreate)(JNIEnv* env, jobject, jlong h, jintArray idx, jlongArray offsets, jint nWorkers) {
+  return plan_create(env, h, idx, offsets, nWorkers, false);
+}
+// The same lists as a ROW-PARALLEL plan of an fp64 context (dsgd_plan_create_rp64_n; include/dsgd.h "THE FP64 MODE", ROW-PARALLEL
+// PLANS): what planCreate refuses there -- Double feature values, more than 4 workers, more than 1,024 rows per batch, a model
+// beyond a slice's LDS.  planRun / planRunF64 / planSynchronize / planDestroy serve it like any plan.
+JNIEXPORT jlong JNICALL NATIVE(planCreateRp64)(JNIEnv* env, jobject, jlong h, jintArray idx, jlongArray offsets, jint nWorkers) {
+  return plan_create(env, h, idx, offsets, nWorkers, true);
 }
 
 // The same epoch with its lists DRAWN BY THE DEVICE, draw for draw scala.util.Random's stream (dsgd_plan_create_from_seed:
@@ -406,8 +415,8 @@ JNIEXPORT jlong JNICALL NATIVE(planCreate)(JNIEnv* env, jobject, jlong h, jintAr
 // values consumed}; on return state[0] is where the JVM's generator would stand behind the epoch's last shuffle.  Returns 0
 // with state[1] = 0 when the first batch already hands a worker an empty slice.  An epoch outside the device form's limits
 // raises UnsupportedOperationException: the caller draws the lists itself and uses planCreate.
-JNIEXPORT jlong JNICALL NATIVE(planCreateFromSeed)(JNIEnv* env, jobject, jlong h, jlongArray state, jlongArray splitBegin,
-                                                   jlongArray splitEnd, jlong maxSamples, jint batchSize) {
+static jlong plan_create_from_seed(JNIEnv* env, jlong h, jlongArray state, jlongArray splitBegin, jlongArray splitEnd, jlong maxSamples,
+                                   jint batchSize, bool rp64) {
   const jsize n = env->GetArrayLength(splitBegin);
   if (env->GetArrayLength(state) < 3 || n < 1 || env->GetArrayLength(splitEnd) != n) {
     env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "state must hold 3 entries, splitBegin / splitEnd one per worker");
@@ -421,8 +430,9 @@ JNIEXPORT jlong JNICALL NATIVE(planCreateFromSeed)(JNIEnv* env, jobject, jlong h
     LongElems ev(env, splitEnd, JNI_ABORT);
     uint64_t js = (uint64_t)sv.p[0];
     int64_t n_steps = 0, draws = 0;
-    rc = dsgd_plan_create_from_seed(ctx(h), &js, reinterpret_cast<const int64_t*>(bv.p), reinterpret_cast<const int64_t*>(ev.p), (int32_t)n,
-                                    (int64_t)maxSamples, (int32_t)batchSize, &plan, &n_steps, &draws);
+    rc = (rp64 ? dsgd_plan_create_from_seed_rp64 : dsgd_plan_create_from_seed)(ctx(h), &js, reinterpret_cast<const int64_t*>(bv.p),
+                                                                               reinterpret_cast<const int64_t*>(ev.p), (int32_t)n, (int64_t)maxSamples,
+                                                                               (int32_t)batchSize, &plan, &n_steps, &draws);
     if (rc == DSGD_OK) {
       sv.p[0] = (jlong)js;
       sv.p[1] = (jlong)n_steps;
@@ -432,6 +442,39 @@ JNIEXPORT jlong JNICALL NATIVE(planCreateFromSeed)(JNIEnv* env, jobject, jlong h
   if (rc == DSGD_EUNSUPPORTED) {
     env->ThrowNew(env->FindClass("java/lang/UnsupportedOperationException"), dsgd_last_error());
     return 0;
+  }
+  if (rc) {
+    raise(env, rc);
+    return 0;
+  }
+  return reinterpret_cast<jlong>(plan);
+}
+JNIEXPORT jlong JNICALL NATIVE(planCreateFromSeed)(JNIEnv* env, jobject, jlong h, jlongArray state, jlongArray splitBegin,
+                                                   jlongArray splitEnd, jlong maxSamples, jint batchSize) {
+  return plan_create_from_seed(env, h, state, splitBegin, splitEnd, maxSamples, batchSize, false);
+}
+// ... into a row-parallel plan of an fp64 context (dsgd_plan_create_from_seed_rp64): the same draws, the same state behind them
+JNIEXPORT jlong JNICALL NATIVE(planCreateFromSeedRp64)(JNIEnv* env, jobject, jlong h, jlongArray state, jlongArray splitBegin,
+                                                       jlongArray splitEnd, jlong maxSamples, jint batchSize) {
+  return plan_create_from_seed(env, h, state, splitBegin, splitEnd, maxSamples, batchSize, true);
+}
+// Updates [firstUpdate, firstUpdate + nUpdates) of the fp64 mode's zero-lag asynchronous schedule as a one-worker row-parallel
+// plan whose lists the device draws (dsgd_async_plan_create_rp64): the lock-free engine's sampler for the workers' row ranges,
+// batch, seed and positionalBug as asyncStart takes them; Double or float feature values, any batch, any model width.
+JNIEXPORT jlong JNICALL NATIVE(asyncPlanCreateRp64)(JNIEnv* env, jobject, jlong h, jlongArray assignedBegin, jlongArray assignedEnd, jint batch,
+                                                    jlong seed, jboolean positionalBug, jlong firstUpdate, jlong nUpdates) {
+  const jsize n = env->GetArrayLength(assignedBegin);
+  if (n < 1 || env->GetArrayLength(assignedEnd) != n) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "assignedBegin / assignedEnd hold one entry per worker");
+    return 0;
+  }
+  dsgd_plan* plan = nullptr;
+  int rc;
+  {
+    LongElems bv(env, assignedBegin, JNI_ABORT);
+    LongElems ev(env, assignedEnd, JNI_ABORT);
+    rc = dsgd_async_plan_create_rp64(ctx(h), reinterpret_cast<const int64_t*>(bv.p), reinterpret_cast<const int64_t*>(ev.p), (int32_t)n,
+                                     (int32_t)batch, (uint64_t)seed, positionalBug ? 1 : 0, (int64_t)firstUpdate, (int64_t)nUpdates, &plan);
   }
   if (rc) {
     raise(env, rc);

@@ -39,6 +39,13 @@ object NativeSVM {
   // (batch-major, worker-minor), offsets = nSteps * nWorkers + 1 prefix offsets
   @native def planCreate(ctx: Long, idx: Array[Int], offsets: Array[Long], nWorkers: Int): Long
   @native def planCreateFromSeed(ctx: Long, state: Array[Long], splitBegin: Array[Long], splitEnd: Array[Long], maxSamples: Long, batchSize: Int): Long
+  // row-parallel plans of an fp64 context (include/dsgd.h "THE FP64 MODE", ROW-PARALLEL PLANS): the twins' arguments; what the
+  // creators above refuse there -- Double values, > 4 workers, > 1,024 rows per batch, a model beyond a slice's LDS
+  @native def planCreateRp64(ctx: Long, idx: Array[Int], offsets: Array[Long], nWorkers: Int): Long
+  @native def planCreateFromSeedRp64(ctx: Long, state: Array[Long], splitBegin: Array[Long], splitEnd: Array[Long], maxSamples: Long, batchSize: Int): Long
+  // updates [firstUpdate, firstUpdate + nUpdates) of the zero-lag asynchronous schedule, the lists drawn by the device
+  @native def asyncPlanCreateRp64(ctx: Long, assignedBegin: Array[Long], assignedEnd: Array[Long], batch: Int, seed: Long,
+                                  positionalBug: Boolean, firstUpdate: Long, nUpdates: Long): Long
   @native def planRun(ctx: Long, plan: Long, stepBegin: Long, stepEnd: Long, lr: Float): Unit
   @native def planSynchronize(ctx: Long): Long
   @native def planDestroy(ctx: Long, plan: Long): Unit
@@ -127,6 +134,11 @@ class HipSVM(lambda: Number, dimSparsity: Vec, data: Array[(Vec, Int)], nTrain: 
   private val dim = data(0)._1.size
   // -Ddsgd.precision=fp64: an fp64 context that is given the Vec values as they are (INTEGRATION.md 3a)
   private val fp64 = sys.props.get("dsgd.precision").contains("fp64")
+  // -Ddsgd.f64.rpPlans=true (fp64 only; off by default, DESIGN.md 3.8): an epoch whose plan the column slices refuse runs
+  // as a resident row-parallel plan (planCreateRp64 / planCreateFromSeedRp64) instead of failing
+  private val rpPlans = fp64 && sys.props.get("dsgd.f64.rpPlans").contains("true")
+  private def refused(e: RuntimeException): Boolean =
+    rpPlans && !e.isInstanceOf[IllegalArgumentException] && !e.isInstanceOf[IndexOutOfBoundsException]
   private val ctx =
     if (fp64) NativeSVM.createF64(dim, lambda.toDouble, device) else NativeSVM.create(dim, lambda.toDouble, device)
 
@@ -231,7 +243,8 @@ class HipSVM(lambda: Number, dimSparsity: Vec, data: Array[(Vec, Int)], nTrain: 
       i += 1
       offsets(i) = at
     })
-    NativeSVM.planCreate(ctx, idx, offsets, nWorkers)
+    try NativeSVM.planCreate(ctx, idx, offsets, nWorkers)
+    catch { case e: RuntimeException if refused(e) => NativeSVM.planCreateRp64(ctx, idx, offsets, nWorkers) }
   }
 
   /** `fitEpoch` with the epoch's sample lists DRAWN BY THE DEVICE -- draw for draw what
@@ -249,9 +262,15 @@ class HipSVM(lambda: Number, dimSparsity: Vec, data: Array[(Vec, Int)], nTrain: 
     seedField.setAccessible(true)
     val seed  = seedField.get(rnd).asInstanceOf[java.util.concurrent.atomic.AtomicLong]
     val state = Array(seed.get(), 0L, 0L)
+    val (begins, ends) = (split.map(_.start.toLong).toArray, split.map(r => (r.last + 1).toLong).toArray)
     val plan =
-      try NativeSVM.planCreateFromSeed(ctx, state, split.map(_.start.toLong).toArray, split.map(r => (r.last + 1).toLong).toArray, maxSamples.toLong, batchSize)
-      catch { case _: UnsupportedOperationException => return None }
+      try NativeSVM.planCreateFromSeed(ctx, state, begins, ends, maxSamples.toLong, batchSize)
+      catch {
+        case _: UnsupportedOperationException if rpPlans =>   // (state is untouched by a refusal)
+          try NativeSVM.planCreateFromSeedRp64(ctx, state, begins, ends, maxSamples.toLong, batchSize)
+          catch { case _: UnsupportedOperationException => return None }
+        case _: UnsupportedOperationException => return None
+      }
     seed.set(state(0))
     if (plan != 0L) {
       try runEpochPlan(plan, state(1).toInt, learningRate)

@@ -4,10 +4,13 @@ loss and accuracy, fit (sync or async, early stopping by patience / conv-delta),
 accuracy -- with the HIP engine hosting all the workers.
 
     DSGD_DATA_PATH=/data/rcv1 python tools/train.py [--conf application.conf] [--synthetic ROWS] [--device 0] [--weights-out w.txt]
-                                                    [--precision fp64]
+                                                    [--precision fp64] [--f64-rp-plans]
 
 --precision fp64: the engine keeps the reference's Double weights (include/dsgd.h "THE FP64 MODE"); an async fit runs the
 zero-lag schedule of host.MasterAsync (one update at a time, every update seen by every worker).
+--f64-rp-plans (or DSGD_F64_RP_PLANS=1; with --precision fp64): what the column-slice plans refuse -- real files' Double
+feature values, more than 4 workers, batches beyond 1,024 rows -- runs as resident row-parallel plans (include/dsgd.h
+"THE FP64 MODE", ROW-PARALLEL PLANS); the asynchronous fit then keeps the files' Doubles too.  Off by default.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,7 +24,11 @@ ap.add_argument("--synthetic", type=int, default=0, help="use N synthetic RCV1-l
 ap.add_argument("--device", type=int, default=0)
 ap.add_argument("--weights-out", help="write the `idx:value` line of Main.scala:114 here instead of logging it")
 ap.add_argument("--precision", choices=("fp32", "fp64"), default="fp32", help="fp64: the reference's Double arithmetic")
+ap.add_argument("--f64-rp-plans", action="store_true", help="fp64: refused plans run as row-parallel plans (DSGD_F64_RP_PLANS=1)")
 a = ap.parse_args()
+if a.f64_rp_plans:
+    os.environ["DSGD_F64_RP_PLANS"] = "1"   # (host.MasterSync / host.MasterAsync read it at every fit)
+rp_plans = a.precision == "fp64" and os.environ.get("DSGD_F64_RP_PLANS", host.F64_RP_PLANS_DEFAULT) == "1"
 
 
 def log(msg, *args):  # logback's pattern is not reproduced; the messages are
@@ -38,12 +45,12 @@ n_train = int(data.n_rows * 0.8)                                              # 
 metrics = host.Metrics()
 with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device, precision=a.precision) as eng:
     # fp64 on real files: the parsed Doubles as the reference holds them (--synthetic is float by construction; the
-    # asynchronous fit runs resident plans, which hold float values)
-    values = data.val64 if a.precision == "fp64" and not cfg.async_ and getattr(data, "val64", None) is not None else data.val
+    # asynchronous fit runs resident column-slice plans, which hold float values -- unless row-parallel plans are on)
+    values = data.val64 if a.precision == "fp64" and (rp_plans or not cfg.async_) and getattr(data, "val64", None) is not None else data.val
     eng.load_csr(data.row_ptr, data.col, values, data.label)
     log("feature values: {} bits{}", eng.value_bits() if a.precision == "fp64" else 32,
         " (fp64 asynchronous fit: resident plans hold float values, NOT the Double feature values)"
-        if a.precision == "fp64" and cfg.async_ and getattr(data, "val64", None) is not None else "")
+        if a.precision == "fp64" and cfg.async_ and not rp_plans and getattr(data, "val64", None) is not None else "")
     t0 = time.time()
     eng.build_dim_sparsity(n_train)                                            # Main.scala:54-65
     log("dim sparsity ({}s)", round(time.time() - t0, 3))
