@@ -43,6 +43,7 @@ SYMBOLS = [
     "dsgd_sync_steps_f64",
     "dsgd_comm_init_f64v",
     "dsgd_plan_create_rp64_n", "dsgd_plan_create_from_seed_rp64", "dsgd_async_plan_create_rp64",
+    "dsgd_predict_ranges", "dsgd_predict_ranges_f64",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")

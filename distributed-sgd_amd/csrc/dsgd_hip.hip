@@ -131,6 +131,7 @@ static bool available() {
 #include "dsgd_cs64.hpp"   // (last: the fp64 mode)
 #include "dsgd_rp64.hpp"   // (... and its row-parallel gradient family, on float and on Double feature values)
 #include "dsgd_sparse.hpp" // (the Sparse form at the boundary: compaction and scatter-in)
+#include "dsgd_predict.hpp" // (distributed evaluation: predictions and per-split tallies of K row ranges in one launch)
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -409,6 +410,8 @@ struct dsgd_ctx {
   DevBuf<float> d_upd_dv;
   hipStream_t upd_stream = nullptr;
   DevBuf<float> d_pred;     // dsgd_forward's predictions (grown on demand)
+  DevBuf<signed char> d_pred8;          // dsgd_predict_ranges' predictions (grown on demand) ...
+  DevBuf<long long> d_pred_tab;         // ... its range table (off[K + 1], begin[K]) followed by the tallies [K][3], K at its maximum
   bool fix_bound = true;         // DSGD_FIX_BOUND=0: keep the data-independent bound (rows per workgroup x largest value)
   DevBuf<float> d_gsum;  // dp (all-reduce buffer / sum over hosted workers)
   DevBuf<float> d_tmp;   // dp scratch (ranked order)
@@ -3196,6 +3199,10 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   DSGD_ATTR(dsgd_eval_kernel<32>);
   DSGD_ATTR(dsgd_eval_kernel<16>);
   DSGD_ATTR(dsgd_eval_kernel<8>);
+  DSGD_ATTR(dsgd_predict_kernel<64>);
+  DSGD_ATTR(dsgd_predict_kernel<32>);
+  DSGD_ATTR(dsgd_predict_kernel<16>);
+  DSGD_ATTR(dsgd_predict_kernel<8>);
   DSGD_ATTR(dsgd_colcount_kernel);
   DSGD_ATTR((dsgd_hogwild_kernel<false, false>));
   DSGD_ATTR((dsgd_hogwild_kernel<true, false>));
@@ -5625,6 +5632,149 @@ int dsgd_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row_en
   DSGD_TRY(eval_enqueue(c, w, row_begin, row_end));
   DSGD_TRY(eval_collective(c));
   return eval_read(c, loss, acc, counts);
+}
+
+// ---- distributed evaluation (csrc/dsgd_predict.hpp; ref: core/Master.scala:61-98) ----
+// The checks of dsgd_predict_ranges / _f64 that need no device: nothing has changed when one of them fails.
+static int predict_check(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int32_t n_ranges, const int8_t* pred_out,
+                         long long* total_out) {
+  if (n_ranges < 1 || !row_begin || !row_end) return fail(DSGD_EINVAL, "bad predict arguments: no ranges");
+  if (n_ranges > PRED_MAX_RANGES) return fail(DSGD_EINVAL, "%d ranges in one call (at most %d)", n_ranges, PRED_MAX_RANGES);
+  if (!pred_out) return fail(DSGD_EINVAL, "null pred_out");
+  long long total = 0;
+  std::vector<std::pair<long long, long long>> iv;
+  for (int k = 0; k < n_ranges; ++k) {
+    if (row_begin[k] > row_end[k])
+      return fail(DSGD_EINVAL, "range %d: begin %lld > end %lld", k, (long long)row_begin[k], (long long)row_end[k]);
+    if (row_begin[k] == row_end[k]) continue;   // an empty split: an empty reply (ref: core/Slave.scala:133 over an empty Seq)
+    if (row_begin[k] < 0 || row_end[k] > c->n_rows)
+      return fail(DSGD_ERANGE, "rows [%lld, %lld) of range %d outside the %lld loaded rows", (long long)row_begin[k], (long long)row_end[k], k,
+                  c->n_rows);
+    iv.emplace_back((long long)row_begin[k], (long long)row_end[k]);
+    total += row_end[k] - row_begin[k];
+  }
+  // preds.size is the row count only while no row repeats: .toMap collapses repeated keys (core/Master.scala:73)
+  std::sort(iv.begin(), iv.end());
+  for (size_t i = 1; i < iv.size(); ++i)
+    if (iv[i].first < iv[i - 1].second)
+      return fail(DSGD_EINVAL, "ranges overlap: [%lld, %lld) and [%lld, %lld)", iv[i - 1].first, iv[i - 1].second, iv[i].first, iv[i].second);
+  if (total == 0)   // preds.map(...).reduce over an empty map throws (core/Master.scala:96)
+    return fail(DSGD_EINVAL, "no rows in any range: reduce on an empty prediction map");
+  *total_out = total;
+  return DSGD_OK;
+}
+
+// the launch, the copies back and the fold, from the resident weights (bound; the ranges checked)
+static int predict_run(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int K, long long total, int8_t* pred_out,
+                       int64_t* counts_out, double* loss, double* acc) {
+  const size_t tab_words = (size_t)(2 * K + 1), cnt_words = (size_t)(3 * K);
+  if (!c->d_pred_tab || (size_t)total > c->d_pred8.cap()) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    DSGD_TRY(c->d_pred_tab.reserve((size_t)(2 * PRED_MAX_RANGES + 1) + 3 * PRED_MAX_RANGES));
+    DSGD_TRY(c->d_pred8.reserve((size_t)std::max<long long>(total, 4096), Grow::twice));
+  }
+  long long* d_tab = c->d_pred_tab;
+  unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(d_tab + (2 * PRED_MAX_RANGES + 1));
+  // |w|^2 of the loss, as dsgd_loss_acc takes it (eval_enqueue)
+  if (loss && c->fp64) {
+    hipLaunchKernelGGL(dsgd_norm64_kernel, dim3(1), dim3(256), 0, c->stream, c->d_w64, c->dp, c->d_nsq64);
+  } else if (loss) {
+    if (c->nsq_dirty) c->s_dirty = true;
+    DSGD_TRY(ensure_s(c));
+  }
+  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(long long) * tab_words));
+  long long* h_tab = static_cast<long long*>(c->pin_idx.p.get());
+  h_tab[0] = 0;
+  for (int k = 0; k < K; ++k) {
+    h_tab[k + 1] = h_tab[k] + (long long)(row_end[k] - row_begin[k]);
+    h_tab[K + 1 + k] = (long long)row_begin[k];
+  }
+  HIP_TRY(hipMemcpyAsync(d_tab, h_tab, sizeof(long long) * tab_words, hipMemcpyHostToDevice, c->stream));
+  DSGD_TRY(pin_sent(c, c->pin_idx));
+  HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * cnt_words, c->stream));
+  signed char* d_pred = c->d_pred8;
+  if (c->fp64) {
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>((long long)c->n_cu * 8, (total + 15) / 16)));
+    const size_t lds = sizeof(float) * (size_t)pred_lds_words(K);
+    if (c->d_val64)
+      hipLaunchKernelGGL(dsgd_predict64v_kernel, grid, dim3(256), lds, c->stream, view64(c), c->d_w64, d_tab, K, d_pred, d_cnt);
+    else
+      hipLaunchKernelGGL(dsgd_predict64_kernel, grid, dim3(256), lds, c->stream, view(c), c->d_w64, d_tab, K, d_pred, d_cnt);
+  } else {
+    // dsgd_eval_kernel's launch: one 1024-lane workgroup per CU at most, a small weight tile for small calls
+    const int G = c->group;
+    const long long groups_per_block = 1024 / G;
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(c->n_cu, (total + groups_per_block - 1) / groups_per_block)));
+    const int hw = std::min(total >= 4096 ? c->hw_eval : std::min(c->hw_eval, 1024), (DSGD_LDS_FLOATS - pred_lds_words(K)) & ~3);
+    const size_t lds = sizeof(float) * (size_t)(((hw + 3) & ~3) + pred_lds_words(K));
+    CsrView m = view(c);
+    switch (G) {
+      case 64: hipLaunchKernelGGL(dsgd_predict_kernel<64>, grid, dim3(1024), lds, c->stream, m, c->d_w, d_tab, K, d_pred, d_cnt, hw); break;
+      case 32: hipLaunchKernelGGL(dsgd_predict_kernel<32>, grid, dim3(1024), lds, c->stream, m, c->d_w, d_tab, K, d_pred, d_cnt, hw); break;
+      case 16: hipLaunchKernelGGL(dsgd_predict_kernel<16>, grid, dim3(1024), lds, c->stream, m, c->d_w, d_tab, K, d_pred, d_cnt, hw); break;
+      default: hipLaunchKernelGGL(dsgd_predict_kernel<8>, grid, dim3(1024), lds, c->stream, m, c->d_w, d_tab, K, d_pred, d_cnt, hw); break;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  // both replies through the pinned buffer: the tallies in front (8-byte aligned), the bytes behind them
+  DSGD_TRY(pin_acquire(c->pin_out, sizeof(unsigned long long) * cnt_words + (size_t)total));
+  unsigned long long* h_cnt = static_cast<unsigned long long*>(c->pin_out.p.get());
+  signed char* h_pred = reinterpret_cast<signed char*>(h_cnt + cnt_words);
+  HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, sizeof(unsigned long long) * cnt_words, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(h_pred, d_pred, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+  DSGD_TRY(read_scalars(c));   // (synchronises; wnorm2 of the fp32 loss)
+  memcpy(pred_out, h_pred, (size_t)total);
+  long long t3[3] = {0, 0, 0};
+  for (int k = 0; k < K; ++k)
+    for (int j = 0; j < 3; ++j) {
+      t3[j] += (long long)h_cnt[3 * k + j];
+      if (counts_out) counts_out[3 * k + j] = (int64_t)h_cnt[3 * k + j];
+    }
+  if (t3[0] + t3[1] + t3[2] != total) return fail(DSGD_ESTATE, "internal: %lld rows tallied of %lld", t3[0] + t3[1] + t3[2], total);
+  const double n = (double)total;
+  if (loss) {
+    double nsq = (double)c->h_sc->wnorm2;
+    if (c->fp64) HIP_TRY(hipMemcpy(&nsq, c->d_nsq64, sizeof(double), hipMemcpyDeviceToHost));
+    *loss = c->cfg.lambda * nsq + ((double)t3[1] + 2.0 * (double)t3[2]) / n;   // (eval_read's expression)
+  }
+  if (acc) *acc = (double)t3[0] / n;
+  return DSGD_OK;
+}
+
+int dsgd_predict_ranges(dsgd_ctx* c, const float* w, const int64_t* row_begin, const int64_t* row_end, int32_t n_ranges,
+                        int8_t* pred_out, int64_t* counts_out, double* loss, double* acc) {
+  DSGD_TRY(check_ctx(c));
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (c->fp64 && w)
+    return fail(DSGD_EINVAL, "dsgd_predict_ranges on an fp64 context takes w == NULL (the resident Double weights); "
+                             "dsgd_predict_ranges_f64 takes a Double w");
+  DSGD_TRY(require_data(c));
+  long long total = 0;
+  DSGD_TRY(predict_check(c, row_begin, row_end, n_ranges, pred_out, &total));
+  DSGD_TRY(require_sync_mode(c));   // (the concurrent loss check of the lock-free engine is dsgd_loss_acc's)
+  if (loss && !c->fp64) DSGD_TRY(require_ds(c));   // (|w|^2 comes with s, as in dsgd_loss_acc)
+  DSGD_TRY(bind(c));
+  DSGD_TRY(prepare_layout(c));
+  if (w) DSGD_TRY(set_weights_locked(c, w));
+  return predict_run(c, row_begin, row_end, n_ranges, total, pred_out, counts_out, loss, acc);
+}
+
+int dsgd_predict_ranges_f64(dsgd_ctx* c, const double* w, const int64_t* row_begin, const int64_t* row_end, int32_t n_ranges,
+                            int8_t* pred_out, int64_t* counts_out, double* loss, double* acc) {
+  DSGD_TRY(check_ctx(c));
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(require_fp64(c, "dsgd_predict_ranges_f64"));
+  DSGD_TRY(require_data(c));
+  long long total = 0;
+  DSGD_TRY(predict_check(c, row_begin, row_end, n_ranges, pred_out, &total));
+  DSGD_TRY(require_sync_mode(c));
+  DSGD_TRY(bind(c));
+  DSGD_TRY(prepare_layout(c));
+  if (w) {
+    DSGD_TRY(put64(c, w, c->d_w64));   // (the Double weights as they are: no float rounding)
+    c->s_dirty = true;
+  }
+  return predict_run(c, row_begin, row_end, n_ranges, total, pred_out, counts_out, loss, acc);
 }
 
 int dsgd_async_step(dsgd_ctx* c, const int32_t* idx, int64_t n, float lr, float* delta_out, dsgd_batch_stats* stats) {

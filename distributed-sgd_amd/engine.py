@@ -337,6 +337,30 @@ class Engine:
         check(self._lib.dsgd_loss_acc(self._ctx, ptr(wv), C.c_int64(row_begin), C.c_int64(row_end), C.byref(loss), C.byref(acc), counts))
         return loss.value, acc.value, list(counts)
 
+    predict_max_ranges = 256   # K of one dsgd_predict_ranges call (host.MasterSync asks forward per split beyond it)
+
+    def predict_ranges(self, ranges, w=None):
+        """Master.predict over the workers' splits in ONE launch (dsgd_predict_ranges; core/Master.scala:61-98): `ranges` =
+        the splits as (begin, end) row ranges.  Returns (pred, counts, loss, acc): pred int8 in {-1, 0, +1}, one per row,
+        range after range; counts int64 [K, 3], the exact tallies {#p==y, #p==0, #p==-y} of every range; loss and accuracy
+        over all the rows, loss_acc's expression.  w: None (the resident weights) or a vector that replaces them -- float64
+        through dsgd_predict_ranges_f64 on an fp64 engine, float32 otherwise."""
+        k = len(ranges)
+        rb = (C.c_int64 * max(k, 1))(*[int(r[0]) for r in ranges])
+        re_ = (C.c_int64 * max(k, 1))(*[int(r[1]) for r in ranges])
+        total = sum(max(0, int(r[1]) - int(r[0])) for r in ranges)
+        pred = np.zeros(max(total, 1), dtype=np.int8)   # (never a null pointer: the library decides what is refused)
+        counts = np.zeros((max(k, 1), 3), dtype=np.int64)
+        loss, acc = C.c_double(0), C.c_double(0)
+        if self.fp64 and w is not None:
+            check(self._lib.dsgd_predict_ranges_f64(self._ctx, ptr(f64(w, self.dp)), rb, re_, C.c_int32(k), ptr(pred), ptr(counts),
+                                                    C.byref(loss), C.byref(acc)))
+        else:
+            wv = None if w is None else f32(w, self.dp)
+            check(self._lib.dsgd_predict_ranges(self._ctx, ptr(wv), rb, re_, C.c_int32(k), ptr(pred), ptr(counts), C.byref(loss),
+                                                C.byref(acc)))
+        return pred[:total], counts[:k], loss.value, acc.value
+
     # -- asynchronous path -------------------------------------------------------------------------
     def async_step(self, idx, lr, want_delta=False):
         idx = i32(idx)

@@ -10,6 +10,7 @@ the reference.  Citations are relative to /root/reference/src/main/scala/epfl/di
     JavaRandom        java.util.Random (the generator behind scala.util.Random, seeded 0 at Main.scala:32)
     scala_shuffle     scala.util.Random.shuffle (2.12): the per-batch reshuffle of Master.scala:184
     MasterSync.fit    core/Master.scala:120-218
+    predict, distributed_loss, distributed_accuracy (both masters)   core/Master.scala:61-98
     MasterAsync.fit   core/MasterAsync.scala:32-62, 96-177
     Metrics           the Kamon instruments of the path, same names (core/Slave.scala:90-181, core/Master.scala:150-183)
     format_final_weights   the `final weights: idx:val ...` log line (Main.scala:114)
@@ -447,8 +448,95 @@ class _Refused(RuntimeError):
     code = -7
 
 
+# ---- Master.predict / distributedLoss / distributedAccuracy ---------------------------------------------------------
+class _DistributedEval:
+    """core/Master.scala:61-98 for the workers hosted behind one backend (shared by MasterSync and MasterAsync, which
+    both extend AbstractMaster there).  The rows are split as fit splits them (SplitStrategy.vanilla over the train rows,
+    one split per worker), every split is one ForwardRequest, the replies are zipped back to their rows.
+
+    A backend with predict_ranges(ranges, w) (Engine: ONE launch for all splits, one byte per prediction and exact
+    per-split tallies) serves every call from it, as long as the splits are within its predict_max_ranges.  Any other
+    backend needs get_weights(), lam and either forward_splits(idx_lists, w) (wire.WireBackend: the reference's own fan-out,
+    split k to slave k, all requests in flight together) or forward(idx, w) (asked once per split: the oracle backend, a
+    recording backend); loss and accuracy are then folded here over the labels -- the master's own (`master.labels = y`,
+    one label per row: the reference's master holds `data`), else the backend's `labels` / `label` array or its
+    labels(rows) method.  weights: None evaluates the backend's resident weights."""
+
+    labels = None   # one label per row, where the fold runs on the host and the backend offers none
+
+    def _splits(self):
+        return split_vanilla(self.n_train, self.node_count)   # splitStrategy(data, workers.size)
+
+    def _predict_ranges(self, weights):
+        split = self._splits()
+        if not all(r.step == 1 for r in split):
+            raise ValueError("distributed evaluation needs contiguous splits")
+        ranges = [(r.start, r.stop) for r in split]
+        if hasattr(self.backend, "predict_ranges") and len(ranges) <= getattr(self.backend, "predict_max_ranges", len(ranges)):
+            pred, counts, loss, acc = self.backend.predict_ranges(ranges, weights)
+            return split, np.asarray(pred), counts, loss, acc
+        return split, None, None, None, None
+
+    def _forward_splits(self, split, weights):
+        lists = [np.arange(r.start, r.stop, dtype=np.int32) for r in split]
+        if hasattr(self.backend, "forward_splits"):   # workers.zip(split) ... Future.sequence(work): Master.scala:67-73
+            preds = self.backend.forward_splits(lists) if weights is None else self.backend.forward_splits(lists, weights)
+        else:                                         # worker.forward(ForwardRequest(idx, weights)), split after split
+            preds = [self.backend.forward(idx) if weights is None else self.backend.forward(idx, weights) for idx in lists]
+        if getattr(self, "metrics", None) is not None:
+            self.metrics.counter("slave.sync.forward", sum(len(idx) for idx in lists))   # one increment per sample: Slave.scala:131
+        return np.concatenate([np.asarray(p, dtype=np.float64) for p in preds]) if preds else np.zeros(0)
+
+    def _labels(self, rows):
+        for src in (self.labels, getattr(self.backend, "labels", None), getattr(self.backend, "label", None)):
+            if src is None:
+                continue
+            return np.asarray(src(rows) if callable(src) else np.asarray(src)[rows], dtype=np.float64)
+        raise ValueError("the fold over the predictions needs the rows' labels: set master.labels (one per row), or give the "
+                         "backend a `labels` array")
+
+    def _norm_squared(self, weights):
+        """math/Vec.scala:55 over the stored entries, added one by one in ascending key order (numpy's pairwise sum rounds
+        differently in the last place)."""
+        w = np.asarray(self.backend.get_weights() if weights is None else weights, dtype=np.float64)
+        w = w[np.abs(w) > SPARSE_EPSILON]
+        acc = 0.0
+        for v in (w * w).tolist():
+            acc += v
+        return acc
+
+    def predict(self, weights=None):
+        """Master.predict (:61-75): (rows, predictions) in split order -- the reference's Map[Int, Number] as two parallel
+        arrays (rows int64; predictions int8 from predict_ranges, else what the backend's forward returns)."""
+        split, pred, _, _, _ = self._predict_ranges(weights)
+        rows = np.concatenate([np.arange(r.start, r.stop, dtype=np.int64) for r in split]) if split else np.zeros(0, np.int64)
+        if pred is None:
+            pred = self._forward_splits(split, weights)
+        return rows, pred
+
+    def distributed_loss_and_accuracy(self, weights=None):
+        """(distributedLoss, distributedAccuracy) from ONE pass over the splits (the reference runs predict once for each)."""
+        split, pred, _, loss, acc = self._predict_ranges(weights)
+        if pred is not None:
+            return loss, acc
+        rows = np.concatenate([np.arange(r.start, r.stop, dtype=np.int64) for r in split]) if split else np.zeros(0, np.int64)
+        if len(rows) == 0:   # preds.map(...).reduce(_ + _) on an empty map (:96)
+            raise ValueError("empty.reduceLeft: no predictions to fold")
+        y = self._labels(rows)   # (looked up first: a fold that cannot be made sends no request)
+        pred = self._forward_splits(split, weights)
+        hinge = np.maximum(0.0, 1.0 - y * pred)   # model.loss(p, y): core/ml/SparseSVM.scala:16
+        lam = float(getattr(self.backend, "lam"))
+        return lam * self._norm_squared(weights) + float(hinge.sum()) / len(rows), float(np.count_nonzero(pred == y)) / len(rows)
+
+    def distributed_loss(self, weights=None):       # Master.scala:87-98
+        return self.distributed_loss_and_accuracy(weights)[0]
+
+    def distributed_accuracy(self, weights=None):   # Master.scala:77-85
+        return self.distributed_loss_and_accuracy(weights)[1]
+
+
 # ---- Master.fit (synchronous) ---------------------------------------------------------------------------------
-class MasterSync:
+class MasterSync(_DistributedEval):
     """core/Master.scala:120-218 for the workers hosted behind one backend.
 
     data layout: rows [0, n_train) are the train set, [n_train, n_rows) the test set (Main.scala:52)."""
@@ -772,7 +860,7 @@ class MasterSync:
 
 
 # ---- MasterAsync.fit ------------------------------------------------------------------------------------------------
-class MasterAsync:
+class MasterAsync(_DistributedEval):
     """core/MasterAsync.scala:32-177 on top of the lock-free engine: start the workers, check the test loss
     every `check_every` updates with a leaky average, keep the best weights, stop on the criterion or at
     maxSteps = n_train * max_epochs updates (MasterAsync.scala:83)."""

@@ -452,6 +452,24 @@ class WireBackend:
         self.w = self.w - lr * (total / len(idx_lists))   # Vec.mean, then weights - learningRate * grad
         return {"n_samples": sum(len(i) for i in idx_lists), "n_active": None}
 
+    def forward_splits(self, idx_lists, w=None):
+        """Master.predict's fan-out (`core/Master.scala:64-73`): split k goes to slave k as one `Forward` RPC carrying the
+        weights, all requests in flight together; the replies in split order.  w: None sends the master's own weights,
+        otherwise w replaces them first (the ForwardRequest's weights are the master's)."""
+        M = messages()
+        if len(idx_lists) > len(self.slaves):
+            raise ValueError("%d splits but %d slaves registered" % (len(idx_lists), len(self.slaves)))
+        if w is not None:
+            self.set_weights(w)
+        weights = to_sparse(self.w, self.size)
+        calls = [stub.Forward.future(M["ForwardRequest"](samples=[int(i) for i in idx], weights=weights))
+                 for stub, idx in zip(self.slaves, idx_lists)]
+        return [np.asarray(c.result().predictions, dtype=np.float64) for c in calls]   # Future.sequence: a failed RPC fails the call
+
+    def forward(self, idx, w=None):
+        """One `Forward` RPC to the first slave (every slave holds all the rows)."""
+        return self.forward_splits([idx], w)[0]
+
     def loss_acc(self, lo, hi):
         M = messages()
         rows = np.arange(lo, hi)

@@ -439,6 +439,36 @@ int dsgd_forward(dsgd_ctx* ctx, const float* w /* or NULL */, const int32_t* idx
 int dsgd_loss_acc(dsgd_ctx* ctx, const float* w /* or NULL */, int64_t row_begin, int64_t row_end, double* loss,
                   double* acc, int64_t* counts /* 3 or NULL */);
 
+/* Master.predict / distributedLoss / distributedAccuracy (core/Master.scala:61-98) for the workers hosted by this
+ * context, in ONE launch (csrc/dsgd_predict.hpp).  The reference splits the rows over the workers, sends each a
+ * ForwardRequest (core/Slave.scala:129-140: pred_i = -signum(x_i . w)), zips the replies back to the rows and folds
+ * loss and accuracy over the resulting map.  Here range k = rows [row_begin[k], row_end[k]) is worker k's split:
+ *   pred_out     one int8 in {-1, 0, +1} per row, range-major: row row_begin[k] + t is at off[k] + t, off the prefix
+ *                sums of the range lengths.
+ *   counts_out   (may be NULL) 3 exact tallies per range, {#p==y, #p==0, #p==-y} as dsgd_loss_acc counts them.
+ *   loss, acc    (may be NULL) with n all rows and c the tallies summed over the ranges:
+ *                loss = lambda*|w|^2 + (c1 + 2 c2) / n, acc = c0 / n -- dsgd_loss_acc's expression and |w|^2.
+ * A row's prediction and its tally are decided on the same x . w, computed as the row-wise evaluation kernel of the
+ * context's precision computes it (and as dsgd_forward / dsgd_forward_f64 do: the predictions are theirs, entry for
+ * entry).  So the counts of a range are the ones dsgd_loss_acc returns for the same rows and weights in an fp64 context,
+ * and in an fp32 context for ranges below 4,096 rows; from 4,096 rows on the fp32 dsgd_loss_acc streams the split matrix
+ * with another summation order of x . w, and a row within fp32 rounding of x . w = 0 may be counted differently there.
+ * An empty range (begin == end) is an empty reply: no bytes, zero tallies.  DSGD_EINVAL, nothing changed: n_ranges < 1
+ * or > 256, begin > end, ranges that overlap (the reference's .toMap would collapse repeated rows and preds.size would
+ * no longer be the row count; SplitStrategy.vanilla never overlaps), no rows at all (.reduce over an empty map
+ * throws, :96).  Rows outside the loaded data: DSGD_ERANGE, nothing changed.  While the lock-free engine runs the call
+ * is refused with DSGD_ESTATE (its concurrent loss check is dsgd_loss_acc).
+ * w == NULL uses the resident weights; otherwise w replaces them, under dsgd_forward's / dsgd_forward_f64's rules.
+ * dsgd_predict_ranges on an fp64 context takes w == NULL only (the resident Double weights; a float w is DSGD_EINVAL:
+ * Double weights go through dsgd_predict_ranges_f64, which needs an fp64 context, DSGD_ESTATE otherwise).
+ * LOCAL to the rank: no collective is entered whether or not a communicator is attached; predictions, tallies, loss
+ * and accuracy cover this context's rows only (dsgd_loss_acc is the call that sums tallies over ranks).           */
+int dsgd_predict_ranges(dsgd_ctx* ctx, const float* w /* D+1 or NULL */, const int64_t* row_begin, const int64_t* row_end,
+                        int32_t n_ranges, int8_t* pred_out /* sum of lengths */, int64_t* counts_out /* 3 * n_ranges or NULL */,
+                        double* loss /* may be NULL */, double* acc /* may be NULL */);
+int dsgd_predict_ranges_f64(dsgd_ctx* ctx, const double* w /* D+1 or NULL */, const int64_t* row_begin, const int64_t* row_end,
+                            int32_t n_ranges, int8_t* pred_out, int64_t* counts_out, double* loss, double* acc);
+
 /* ---- asynchronous ("Hogwild") path ---------------------------------------------------------
  * one iteration of Slave.asyncTask (core/Slave.scala:92-101) on the resident weights with the
  * given sample list: grad = MEAN_i backward; delta = lr * regularize(grad, w); w -= delta.

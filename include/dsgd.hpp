@@ -9,6 +9,7 @@
 //   SparseSVM                core/ml/SparseSVM.scala:11-31 with the data resident on the device
 //   Slave                    core/Slave.scala:113-198 (handlers of SlaveImpl)
 //   Master::fit              core/Master.scala:120-218
+//   Master::predict, distributedLoss, distributedAccuracy   core/Master.scala:61-98 (one launch: dsgd_predict_ranges)
 //   SplitStrategy::vanilla   core/ml/SplitStrategy.scala:13-14
 //   EarlyStopping            core/ml/EarlyStopping.scala:11-46
 //   GradState                core/ml/GradState.scala:6-24
@@ -326,6 +327,32 @@ class SparseSVM {
     check(dsgd_loss_acc(ctx_, w.data(), rowBegin, rowEnd, &l, &a, nullptr));
     return a;
   }
+  // The forward passes of all workers' splits in one launch (dsgd_predict_ranges; core/Master.scala:61-98): one int8 in
+  // {-1, 0, +1} per row, range-major, the exact tallies {#p==y, #p==0, #p==-y} per range, and loss / accuracy folded
+  // over all the rows.
+  struct RangePredictions {
+    std::vector<int8_t> predictions;
+    std::vector<int64_t> counts;   // 3 per range
+    double loss = 0, accuracy = 0;
+  };
+  RangePredictions predictRanges(const Vec& w, const std::vector<std::pair<int64_t, int64_t>>& ranges) {
+    requireSize(w);
+    std::vector<int64_t> b, e;
+    int64_t total = 0;
+    for (const auto& r : ranges) {
+      b.push_back(r.first);
+      e.push_back(r.second);
+      total += std::max<int64_t>(0, r.second - r.first);
+    }
+    RangePredictions out;
+    out.predictions.resize((size_t)std::max<int64_t>(total, 1));   // (never a null pointer: the library decides what is refused)
+    out.counts.assign(3 * std::max<size_t>(ranges.size(), 1), 0);
+    check(dsgd_predict_ranges(ctx_, w.data(), b.data(), e.data(), (int32_t)ranges.size(), out.predictions.data(), out.counts.data(), &out.loss,
+                              &out.accuracy));
+    out.predictions.resize((size_t)total);
+    out.counts.resize(3 * ranges.size());
+    return out;
+  }
 
  private:
   void requireSize(const Vec& v) const {
@@ -426,6 +453,22 @@ class Master {
 
   double localLoss(const Vec& w, bool test = false) { return test ? model_.loss(w, nTrain_, nRows_) : model_.loss(w, 0, nTrain_); }  // :104
   double localAccuracy(const Vec& w, bool test = false) { return test ? model_.accuracy(w, nTrain_, nRows_) : model_.accuracy(w, 0, nTrain_); }  // :100
+
+  // :61-75 -- the rows split over the workers (SplitStrategy.vanilla, as fit splits them), one ForwardRequest each; the
+  // replies zipped back to their rows.  Returns (row, prediction) in split order: the reference's Map[Int, Number].
+  std::vector<std::pair<int64_t, int>> predict(const Vec& w) {
+    const auto split = SplitStrategy::vanilla(nTrain_, nodeCount_);
+    const auto r = model_.predictRanges(w, split);
+    std::vector<std::pair<int64_t, int>> preds;
+    preds.reserve(r.predictions.size());
+    size_t t = 0;
+    for (const auto& s : split)
+      for (int64_t row = s.first; row < s.second; ++row) preds.emplace_back(row, (int)r.predictions[t++]);
+    return preds;
+  }
+  // :87-98 -- lambda |w|^2 + sum of loss(p, y) / preds.size     :77-85 -- count(p === y) / preds.size
+  double distributedLoss(const Vec& w) { return model_.predictRanges(w, SplitStrategy::vanilla(nTrain_, nodeCount_)).loss; }
+  double distributedAccuracy(const Vec& w) { return model_.predictRanges(w, SplitStrategy::vanilla(nTrain_, nodeCount_)).accuracy; }
 
   GradState fit(const Vec& initialWeights, int maxEpochs, int batchSize, double learningRate, const EarlyStopping::Criterion& stoppingCriterion) {
     const auto split = SplitStrategy::vanilla(nTrain_, nodeCount_);  // :136

@@ -538,6 +538,47 @@ JNIEXPORT void JNICALL NATIVE(lossAcc)(JNIEnv* env, jobject, jlong h, jfloatArra
   env->SetDoubleArrayRegion(out, 0, 2, la);
 }
 
+// Master.predict / distributedLoss / distributedAccuracy (core/Master.scala:61-98) for the workers hosted by this context:
+// range k = worker k's split; predOut gets one byte in {-1, 0, +1} per row, range-major; out = {loss, accuracy}.
+// w may be null (the resident weights; the only form an fp64 context takes).  The ranges are a few words: copied out
+// first, so that predOut's length is checked against their rows before any array is taken.
+JNIEXPORT void JNICALL NATIVE(predictRanges)(JNIEnv* env, jobject, jlong h, jfloatArray w, jlongArray rowBegin, jlongArray rowEnd,
+                                             jbyteArray predOut, jdoubleArray out) {
+  if ((!rowBegin || !rowEnd || !predOut || !out) && null_array(env)) return;
+  const jsize k = env->GetArrayLength(rowBegin);
+  if (env->GetArrayLength(rowEnd) != k || env->GetArrayLength(out) < 2) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "rowBegin / rowEnd length mismatch, or out shorter than 2");
+    return;
+  }
+  std::vector<jlong> rb(static_cast<size_t>(k > 0 ? k : 1)), re(static_cast<size_t>(k > 0 ? k : 1));
+  if (k > 0) {
+    env->GetLongArrayRegion(rowBegin, 0, k, rb.data());
+    env->GetLongArrayRegion(rowEnd, 0, k, re.data());
+  }
+  // (ranges the library refuses -- begin > end, rows outside the data -- write nothing; the others' rows are counted here)
+  const jlong room = env->GetArrayLength(predOut);
+  jlong total = 0;
+  for (jsize i = 0; i < k && total <= room; ++i)
+    if (rb[i] >= 0 && re[i] > rb[i]) total = re[i] - rb[i] > room - total ? room + 1 : total + (re[i] - rb[i]);
+  if (total > room) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "predOut is shorter than the ranges' rows");
+    return;
+  }
+  double la[2] = {0, 0};
+  int rc;
+  {
+    FloatElems wv(env, w, JNI_ABORT);
+    ByteElems pv(env, predOut, 0);
+    rc = dsgd_predict_ranges(ctx(h), wv.p, reinterpret_cast<const int64_t*>(rb.data()), reinterpret_cast<const int64_t*>(re.data()), k,
+                             reinterpret_cast<int8_t*>(pv.p), nullptr, &la[0], &la[1]);
+  }
+  if (rc) {
+    raise(env, rc);
+    return;
+  }
+  env->SetDoubleArrayRegion(out, 0, 2, la);
+}
+
 // Slave.asyncTask body (core/Slave.scala:92-101); deltaOut receives what Slave.scala:103-105 gossips
 JNIEXPORT void JNICALL NATIVE(asyncStep)(JNIEnv* env, jobject, jlong h, jintArray idx, jfloat lr, jfloatArray deltaOut) {
   const jsize n = env->GetArrayLength(idx);

@@ -50,6 +50,9 @@ object NativeSVM {
   @native def planSynchronize(ctx: Long): Long
   @native def planDestroy(ctx: Long, plan: Long): Unit
   @native def lossAcc(ctx: Long, w: Array[Float], rowBegin: Long, rowEnd: Long, out: Array[Double]): Unit
+  // Master.predict / distributedLoss / distributedAccuracy (core/Master.scala:61-98) in one launch: range k = worker k's split;
+  // predOut: one byte in {-1, 0, +1} per row, range-major; out = {loss, accuracy}; w null = the resident weights
+  @native def predictRanges(ctx: Long, w: Array[Float], rowBegin: Array[Long], rowEnd: Array[Long], predOut: Array[Byte], out: Array[Double]): Unit
   @native def asyncStep(ctx: Long, idx: Array[Int], lr: Float, deltaOut: Array[Float]): Unit
   @native def updateGrad(ctx: Long, keys: Array[Int], values: Array[Float]): Unit
   // the same in the fp64 mode: Double learning rate, delta (D+1) and values
@@ -199,6 +202,28 @@ class HipSVM(lambda: Number, dimSparsity: Vec, data: Array[(Vec, Int)], nTrain: 
     NativeSVM.lossAcc(ctx, if (resident) null else DenseKeys.fromVec(w), rowBegin, rowEnd, out)
     (Number(out(0)), out(1))
   }
+
+  /** Master.predict over the workers' splits (core/Master.scala:61-75) in ONE launch: `ranges` = the splits as [begin, end)
+    * row ranges (SplitStrategy.vanilla yields contiguous ones); one Byte in {-1, 0, +1} per row, split after split.  The loss
+    * and accuracy the reference folds over the same predictions (:77-98) are kept for lastPredictLoss / lastPredictAccuracy.
+    * Resident mode evaluates the weights on the device in place, as lossAndAccuracy does; an fp64 context takes no Float
+    * `w` here, so outside resident mode `w` is stored first (setWeights) and then evaluated in place. */
+  def predict(w: Vec, ranges: Seq[(Int, Int)]): Array[Byte] = synchronized {
+    val p   = new Array[Byte](ranges.map { case (b, e) => math.max(0, e - b) }.sum)
+    val out = new Array[Double](2)
+    if (fp64 && !resident) setWeights(w)
+    NativeSVM.predictRanges(ctx, if (resident || fp64) null else DenseKeys.fromVec(w), ranges.map(_._1.toLong).toArray,
+                            ranges.map(_._2.toLong).toArray, p, out)
+    predictLoss = out(0)
+    predictAccuracy = out(1)
+    p
+  }
+  private var predictLoss: Double     = Double.NaN
+  private var predictAccuracy: Double = Double.NaN
+
+  /** Master.distributedLoss / distributedAccuracy (core/Master.scala:77-98) of the last predict call */
+  def lastPredictLoss: Number      = synchronized(Number(predictLoss))
+  def lastPredictAccuracy: Double = synchronized(predictAccuracy)
 
   /** dev mode (Main.scala "launch: master + slaves"): master and slaves live in ONE JVM and share this object, i.e. ONE
     * device context holds every row and the weights can stay on the device between batches / iterations. */

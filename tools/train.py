@@ -56,7 +56,14 @@ with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device, precision=a.precisi
     log("dim sparsity ({}s)", round(time.time() - t0, 3))
     w0 = np.zeros(data.dim + 1, dtype=np.float32)
     eng.set_weights(w0)
-    l0, a0, _ = eng.loss_acc(0, n_train)                                       # distributedLoss / Accuracy over the train split
+    # Main.scala:74-78: master.distributedLoss(w0, ss) / distributedAccuracy(w0, ss) -- the train rows split over the workers,
+    # one forward pass per split, folded: ONE launch for all splits and both figures (Engine.predict_ranges).  Beyond its 256
+    # ranges the tallies of the whole train range are the same numbers (dsgd_loss_acc).
+    split = host.split_vanilla(n_train, cfg.node_count)
+    if len(split) <= eng.predict_max_ranges:
+        _, _, l0, a0 = eng.predict_ranges([(r.start, r.stop) for r in split])
+    else:
+        l0, a0, _ = eng.loss_acc(0, n_train)
     log("initial loss: {}", l0)
     log("initial accuracy: {}", a0)
     stop = host.EarlyStopping.no_improvement(cfg.patience, cfg.conv_delta, None)
