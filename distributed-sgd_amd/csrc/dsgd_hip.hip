@@ -441,6 +441,8 @@ struct dsgd_ctx {
   DevBuf<WorkSeg> d_segs;
   std::vector<WorkSeg> segs_last;  // what d_segs currently holds
   long long pending_samples = 0;   // rows enqueued by *_async calls since the last dsgd_synchronize
+  bool job_pending = false;        // ... and row-parallel fp64 plan runs under a communicator among them: the JOB's rows run on in d_sc->n_samples
+                                   // (until dsgd_synchronize or the next call that resets the counters: reset_counters)
   // persistent Hogwild engine
   hipStream_t async_stream = nullptr;
   hipStream_t query_stream = nullptr;
@@ -709,6 +711,7 @@ static int reset_counters(dsgd_ctx* c) {
                          c->stream));
   c->ctr_known = true;   // (until the next gradient launch)
   c->ctr_last = 0;
+  c->job_pending = false;   // (n_samples is zero again: the rows of plan runs under a communicator no longer run on in it)
   return DSGD_OK;
 }
 static int check_err_flag(dsgd_ctx* c) {
@@ -3993,8 +3996,9 @@ int dsgd_synchronize(dsgd_ctx* c, dsgd_batch_stats* stats) {
   DSGD_TRY(prof_collect(c));
   const long long act = (long long)c->h_sc->n_active;
   const int err = c->h_sc->err;
-  const long long pending = c->pending_samples;
+  const long long pending = c->pending_samples + (c->job_pending ? (long long)c->h_sc->n_samples : 0);
   c->pending_samples = 0;   // (whatever the outcome: the rows of a rejected run are not carried into the next report)
+  c->job_pending = false;
   DSGD_TRY(reset_counters(c));
   if ((err & (8 | 16)) && c->d_cs_sync) HIP_TRY(hipMemsetAsync(c->d_cs_sync, 0, sizeof(unsigned int) * 2, c->stream));   // the abort word, first
   if (err & 2)
@@ -4116,6 +4120,7 @@ static int cs64_refused(dsgd_ctx* c) {
                                  "(%d slots or %d columns of one slice per step)", CS_MAX_SLOTS, CS_MAX_CLT * CS_THREADS);
 }
 static int plan_run_rp64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr, bool async);   // (with the row-parallel family, further down)
+static int plan_run_rp64_ranks(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr);
 // the steps of a plan in an fp64 context (locked; bound with the slice-major weights kept); async: see launch_cs64
 static int plan_run64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr, bool async = false,
                       double* delta = nullptr) {
@@ -4124,6 +4129,10 @@ static int plan_run64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long
   DSGD_TRY(require_sync_mode(c));
   DSGD_TRY(plan_revalidate(c, p));   // (a plan from before the last load: DSGD_ERANGE here, before anything is enqueued)
   DSGD_TRY(prepare_layout(c));
+  if (p->rp64 && c->comm) {   // (the asynchronous entry point refused the communicator before it came here)
+    if (async) return fail(DSGD_ESTATE, "internal: an asynchronous plan run under a communicator");
+    return plan_run_rp64_ranks(c, p, step_begin, step_end, lr);
+  }
   if (p->rp64) return plan_run_rp64(c, p, step_begin, step_end, lr, async);
   if (p->cs_layout != c->layout_gen) {
     DSGD_TRY(cs_build(c, p));
@@ -4597,7 +4606,7 @@ int dsgd_plan_run(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_en
     return fail(DSGD_EINVAL, "steps [%lld, %lld) outside the plan's %lld steps", (long long)step_begin, (long long)step_end,
                 p->n_steps);
   std::lock_guard<std::mutex> lk(c->mu);
-  DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_run"));
+  if (!p->rp64) DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_run"));   // (a row-parallel plan spans the ranks: plan_run_rp64_ranks)
   DSGD_TRY(bind(c, true));
   if (c->fp64) return plan_run64(c, p, step_begin, step_end, (double)lr);
   DSGD_TRY(require_data(c));
@@ -4662,7 +4671,7 @@ int dsgd_plan_run_f64(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t ste
                 p->n_steps);
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(require_fp64(c, "dsgd_plan_run_f64"));
-  DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_run_f64"));
+  if (!p->rp64) DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_run_f64"));   // (a row-parallel plan spans the ranks: plan_run_rp64_ranks)
   DSGD_TRY(bind(c, true));
   return plan_run64(c, p, step_begin, step_end, lr);
 }
@@ -4877,6 +4886,19 @@ static int rp64_gather_ensure(dsgd_ctx* c, int K, int words) {
   c->rp64_gwords = words;
   return DSGD_OK;
 }
+// the K worker slots' messages: one per slot and plane, cut at RP64_MSG_WORDS (a step's, and a plan run's per step)
+static int rp64_gather_slots(dsgd_ctx* c, int K) {
+  const int words = c->rp64_gwords;
+  unsigned long long* slots = c->d_rp64_gath + rp64_gather_pad(c->world);
+  for (long long g = 0; g < (long long)K * words; ++g)   // (plane g % words of worker g / words)
+    for (long long off = 0; off < c->rp64_gstride; off += RP64_MSG_WORDS) {
+      unsigned long long* at = slots + g * c->rp64_gstride + off;
+      const size_t n = (size_t)std::min<long long>(RP64_MSG_WORDS, c->rp64_gstride - off);
+      const int r = rccl::AllReduce(at, at, n, rccl::kInt64, rccl::kSum, c->comm, c->stream);
+      if (r) return fail(DSGD_ERCCL, "ncclAllReduce(worker %lld's sums): %s", g / words, rccl::GetErrorString(r));
+    }
+  return DSGD_OK;
+}
 // Behind the gradient kernel: the ranks' words first -- every rank must have been called with the same number of hosted
 // workers on the same value type, or the ranks would enqueue different numbers of messages and a collective that only some
 // ranks join never completes; this is the one host read of the step besides its statistics -- then the worker slots, one
@@ -4904,13 +4926,7 @@ static int rp64_gather(dsgd_ctx* c, int k) {
       return fail(DSGD_EINVAL, "rank %d was called with %llu hosted workers, this rank (%d) with %d: every rank of a step hosts the "
                                "same number (the weights are unchanged)", q, (unsigned long long)(unsigned int)rp64_rank_word_k(theirs), c->rank, k);
     }
-  for (long long g = 0; g < (long long)K * words; ++g)   // (plane g % words of worker g / words)
-    for (long long off = 0; off < c->rp64_gstride; off += RP64_MSG_WORDS) {
-      unsigned long long* at = slots + g * c->rp64_gstride + off;
-      const size_t n = (size_t)std::min<long long>(RP64_MSG_WORDS, c->rp64_gstride - off);
-      r = rccl::AllReduce(at, at, n, rccl::kInt64, rccl::kSum, c->comm, c->stream);
-      if (r) return fail(DSGD_ERCCL, "ncclAllReduce(worker %lld's sums): %s", g / words, rccl::GetErrorString(r));
-    }
+  DSGD_TRY(rp64_gather_slots(c, K));
   hipLaunchKernelGGL(dsgd_rp64_header_kernel, dim3(1), dim3(RP64_THREADS), 0, c->stream, c->d_rp64_gath, W, slots, slot, K, c->dp,
                      c->d_rp64_gsegs, c->d_sc);
   HIP_TRY(hipGetLastError());
@@ -5385,8 +5401,7 @@ int dsgd_plan_create_rp64_n(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, cons
   if (!idx || !offsets || !out || n_steps < 1 || n_workers < 1 || n_idx < 0) return fail(DSGD_EINVAL, "bad plan arguments (null pointers, no steps or no workers)");
   if (n_steps > INT64_MAX / n_workers) return fail(DSGD_EINVAL, "n_steps * n_workers overflows");
   std::lock_guard<std::mutex> lk(c->mu);
-  DSGD_TRY(require_fp64(c, "dsgd_plan_create_rp64_n"));
-  DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_create_rp64_n"));
+  DSGD_TRY(require_fp64(c, "dsgd_plan_create_rp64_n"));   // (with a communicator attached too: local, the rank's own rows)
   DSGD_TRY(bind(c, true));   // (nothing here touches w: slice-major weights stay as they are)
   const int K = n_workers;
   const int64_t n_lists = n_steps * K;
@@ -5472,6 +5487,119 @@ static int plan_run_rp64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long l
   c->last_grad_kernel = rec ? (v64 ? "dsgd_rp64v_grad_rec_kernel" : "dsgd_rp64_grad_rec_kernel") : (v64 ? "dsgd_rp64v_grad_kernel" : "dsgd_rp64_grad_kernel");
   c->s_dirty = true;
   c->pending_samples += p->offsets[(size_t)(step_end * K)] - p->offsets[(size_t)(step_begin * K)];
+  return DSGD_OK;
+}
+
+// ... under a communicator (dsgd_comm_init_f64 / dsgd_comm_init_f64v; include/dsgd.h "ACROSS RANKS", csrc/dsgd_rp64_gather.hpp): a
+// COLLECTIVE call.  The ranks agree ONCE -- the [world] words in front of the gather buffer's slots, each rank's rp64_call_word
+// (its plan's hosted workers, its value type, the steps of the call) in its own position, all-reduced and read back: the
+// call's one host read -- and then every step is enqueued with no synchronisation in between: the gather form of the gradient
+// kernel without a rank word, the slots' messages as rp64_gather cuts them, dsgd_rp64_header_plan_kernel, and the finish of a
+// single context over the k * world slots.  Ranks that disagree all return DSGD_EINVAL in front of the first slot message:
+// nothing but the words has travelled, and they are zero again.  The job's samples and active rows run on in the
+// context's scalars until dsgd_synchronize.  A collective error half way: the gather buffer is dropped, DSGD_ERCCL, the
+// weights are those behind the last completed step.
+static int plan_run_rp64_ranks(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr) {
+  const int k = p->n_workers, W = c->world;
+  const long long steps = step_end - step_begin;
+  if (p->d_gate_rec)
+    return fail(DSGD_EUNSUPPORTED, "dsgd_plan_run_f64: a plan that keeps a record (dsgd_plan_record) does not run with a communicator "
+                                   "attached; switch the record off or detach (nothing ran)");
+  if (k > 0x7fffffff / W) return fail(DSGD_EINVAL, "n_workers * world overflows");
+  if (steps > RP64_CALL_MAX_STEPS)
+    return fail(DSGD_EINVAL, "a plan run under a communicator takes at most %lld steps per call (%lld asked): cut the range", RP64_CALL_MAX_STEPS,
+                steps);
+  if (p->built_pending) {
+    HIP_TRY(hipStreamWaitEvent(c->stream, p->built_ev, 0));
+    p->built_pending = false;
+  }
+  const bool v64 = c->d_val64 != nullptr;
+  const int K = k * W, words = v64 ? 2 : 1;
+  DSGD_TRY(rp64_ensure(c, 1));   // (s; the local accumulators are not used)
+  DSGD_TRY(rp64_gather_ensure(c, K, words));
+  // ---- the agreement: own word up, the words all-reduced, read back, zeroed again ----
+  const unsigned long long mine = rp64_call_word(k, v64, steps);
+  c->h_rp64_ranks[c->rank] = mine;
+  // (any failure from here to the read: the words may be left non-zero, so the buffer goes and the next call starts from a zeroed one)
+  hipError_t he = hipMemcpyAsync(c->d_rp64_gath + c->rank, &c->h_rp64_ranks[c->rank], sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream);
+  if (he == hipSuccess) {
+    int r = rccl::AllReduce(c->d_rp64_gath, c->d_rp64_gath, (size_t)W, rccl::kInt64, rccl::kSum, c->comm, c->stream);
+    if (r) {
+      rp64_gather_drop(c);
+      return fail(DSGD_ERCCL, "ncclAllReduce(the plan run's agreement): %s", rccl::GetErrorString(r));
+    }
+    he = hipMemcpyAsync(c->h_rp64_ranks, c->d_rp64_gath, sizeof(unsigned long long) * (size_t)W, hipMemcpyDeviceToHost, c->stream);
+  }
+  if (he == hipSuccess) he = hipMemsetAsync(c->d_rp64_gath, 0, sizeof(unsigned long long) * (size_t)W, c->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+  if (he != hipSuccess) {
+    rp64_gather_drop(c);
+    return fail(DSGD_EHIP, "the plan run's agreement: %s (nothing ran, the weights are unchanged)", hipGetErrorString(he));
+  }
+  for (int q = 0; q < W; ++q) {
+    const unsigned long long theirs = c->h_rp64_ranks[q];
+    if (theirs == mine) continue;
+    if (rp64_call_word_v64(theirs) != v64)
+      return fail(DSGD_EINVAL, "rank %d holds %s feature values, this rank (%d) %s ones: every rank of a plan run holds the same value type "
+                               "(dsgd_load_csr / dsgd_load_csr_f64; nothing ran, the weights are unchanged)", q,
+                  rp64_call_word_v64(theirs) ? "Double" : "float", c->rank, v64 ? "Double" : "float");
+    if (rp64_call_word_k(theirs) != k)
+      return fail(DSGD_EINVAL, "rank %d runs a plan of %d hosted workers, this rank (%d) one of %d: every rank of a plan run hosts the same "
+                               "number (nothing ran, the weights are unchanged)", q, rp64_call_word_k(theirs), c->rank, k);
+    return fail(DSGD_EINVAL, "rank %d runs %lld steps, this rank (%d) %lld: every rank of a plan run runs the same number (nothing ran, the "
+                             "weights are unchanged)", q, rp64_call_word_steps(theirs), c->rank, steps);
+  }
+  if (steps == 0) return DSGD_OK;
+  // ---- the steps, back to back ----
+  if (!c->job_pending) {   // (the job's rows run on from zero: a step under the communicator leaves its own count behind)
+    HIP_TRY(hipMemsetAsync(&c->d_sc->n_samples, 0, sizeof(unsigned long long), c->stream));
+    c->job_pending = true;
+  }
+  unsigned long long* slots = c->d_rp64_gath + rp64_gather_pad(W);
+  const long long slot = c->rp64_gstride * words;
+  const dim3 th(RP64_THREADS), fg = rp64_finish_grid(c);
+  c->ctr_known = false;   // (n_active runs on until dsgd_synchronize)
+  c->s_dirty = true;
+  c->last_grad_kernel = v64 ? "dsgd_rp64v_grad_gather_plan_kernel" : "dsgd_rp64_grad_gather_plan_kernel";
+  for (long long t = step_begin; t < step_end; ++t) {
+    long long mx = 0;
+    for (int j = 0; j < k; ++j) mx = std::max<long long>(mx, p->offsets[(size_t)(t * k + j + 1)] - p->offsets[(size_t)(t * k + j)]);
+    const long long bpw = rp64_bpw(c, k, mx);
+    Rp64Args a;
+    Rp64FinishArgs f;
+    rp64_fill(c, k, bpw, RP64_STEP, lr, nullptr, p->d_idx, p->d_segs + t * k, a, f);
+    a.acc[0] = slots + (long long)c->rank * k * slot;   // this rank's slots; the finish over every rank's workers
+    a.acc[1] = v64 ? a.acc[0] + c->rp64_gstride : nullptr;
+    a.acc_stride = slot;
+    a.rank_word = nullptr;
+    f.acc[0] = slots;
+    f.acc[1] = v64 ? slots + c->rp64_gstride : nullptr;
+    f.acc_stride = slot;
+    f.segs = c->d_rp64_gsegs;
+    f.K = K;
+    const dim3 gg((unsigned)(bpw * k + a.with_s));
+    if (v64)
+      hipLaunchKernelGGL(dsgd_rp64v_grad_gather_plan_kernel, gg, th, 0, c->stream, view64(c), a);
+    else
+      hipLaunchKernelGGL(dsgd_rp64_grad_gather_plan_kernel, gg, th, 0, c->stream, view(c), a);
+    hipError_t e = hipGetLastError();
+    int rc = e == hipSuccess ? rp64_gather_slots(c, K) : fail(DSGD_EHIP, "step %lld's gradient launch: %s", t, hipGetErrorString(e));
+    if (rc == DSGD_OK) {
+      hipLaunchKernelGGL(dsgd_rp64_header_plan_kernel, dim3(1), th, 0, c->stream, slots, slot, K, c->dp, c->d_rp64_gsegs, c->d_sc);
+      if (v64)
+        hipLaunchKernelGGL(dsgd_rp64v_finish_kernel<RP64_STEP>, fg, th, 0, c->stream, f);
+      else
+        hipLaunchKernelGGL(dsgd_rp64_finish_kernel<true>, fg, th, 0, c->stream, f);
+      e = hipGetLastError();
+      if (e != hipSuccess) rc = fail(DSGD_EHIP, "step %lld's finish launch: %s", t, hipGetErrorString(e));
+    }
+    if (rc != DSGD_OK) {   // (half way: the next call starts from a zeroed buffer; the weights are those behind step t - 1)
+      char msg[sizeof(g_err)];
+      snprintf(msg, sizeof(msg), "%s", g_err);
+      rp64_gather_drop(c);
+      return fail(rc, "%s (the weights are those behind step %lld)", msg, t - 1);
+    }
+  }
   return DSGD_OK;
 }
 

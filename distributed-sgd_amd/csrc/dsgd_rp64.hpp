@@ -25,6 +25,9 @@
 // sums go into this rank's slots of a gather buffer (GATHER: dsgd_rp64_grad_gather_kernel, dsgd_rp64v_grad_gather_kernel),
 // the buffer travels, dsgd_rp64_header_kernel turns the gathered headers into the finish's list ranges, and the SAME finish
 // as without a communicator (dsgd_rp64_finish_kernel<true>, dsgd_rp64v_finish_kernel<RP64_STEP>) folds every rank's workers.
+// A row-parallel PLAN's run under a communicator agrees once per call on the host (rp64_call_word) and then runs per step the
+// gather kernels without the rank word (dsgd_rp64_grad_gather_plan_kernel, dsgd_rp64v_grad_gather_plan_kernel), the messages,
+// dsgd_rp64_header_plan_kernel (no rank words; the job's samples and active rows run on) and the same finish.
 //
 // The grid.  A worker's list of n rows (duplicates count) adds entries of |x| <= 2^vexp.  With S = 62 - ceil(log2 n) and
 // v = +-x * 2^(S - vexp) (a power of two: exact) an entry becomes Rp64Acc<V>::WORDS 64-bit integers, and no column sum of n
@@ -132,7 +135,9 @@ struct Rp64Rec {
   float* s_used;           // the step's slot of the s record
   long long step_base;     // position in idx of the step's first entry (worker 0's seg.begin)
 };
-template <typename V, bool GATHER, bool RECORD = false>
+// RANK_WORD (GATHER only; its default keeps the per-step kernels as they were): false for the steps of a plan run under a
+// communicator, whose ranks agreed once per call -- no rank word travels and `a.rank_word` is null.
+template <typename V, bool GATHER, bool RECORD = false, bool RANK_WORD = GATHER>
 __device__ __forceinline__ void rp64_grad_body(const CsrViewT<V>& m, const Rp64Args& a, const Rp64Rec& rec = Rp64Rec{}) {
 #pragma clang fp contract(off)
   constexpr int WORDS = Rp64Acc<V>::WORDS;
@@ -160,7 +165,7 @@ __device__ __forceinline__ void rp64_grad_body(const CsrViewT<V>& m, const Rp64A
       return;
     }
     if (tid == 0) *a.s_out = a.lambda * 2.0 * ((red[0] + red[1]) + (red[2] + red[3]));   // ref: core/ml/SparseSVM.scala:31
-    if (GATHER && tid == 0) *a.rank_word = rp64_rank_word(a.K, WORDS == 2);
+    if (GATHER && RANK_WORD && tid == 0) *a.rank_word = rp64_rank_word(a.K, WORDS == 2);
     return;
   }
   const int k = (int)((long long)blockIdx.x / a.blocks_per_worker);
@@ -232,6 +237,9 @@ __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_kernel(CsrView m,
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_gather_kernel(CsrView m, Rp64Args a) { rp64_grad_body<float, true>(m, a); }
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_grad_kernel(CsrView64 m, Rp64Args a) { rp64_grad_body<double, false>(m, a); }
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_grad_gather_kernel(CsrView64 m, Rp64Args a) { rp64_grad_body<double, true>(m, a); }
+// (the steps of a row-parallel plan under a communicator: the gather form without the rank word)
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_gather_plan_kernel(CsrView m, Rp64Args a) { rp64_grad_body<float, true, false, false>(m, a); }
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_grad_gather_plan_kernel(CsrView64 m, Rp64Args a) { rp64_grad_body<double, true, false, false>(m, a); }
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_grad_rec_kernel(CsrView m, Rp64Args a, Rp64Rec rec) { rp64_grad_body<float, false, true>(m, a, rec); }
 __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64v_grad_rec_kernel(CsrView64 m, Rp64Args a, Rp64Rec rec) { rp64_grad_body<double, false, true>(m, a, rec); }
 
@@ -344,6 +352,37 @@ __global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_header_kernel(unsigned
   if (tid == 0) {
     sc->n_samples = tot[0];
     sc->n_active = tot[1];
+  }
+}
+// The header kernel of a plan run's step (dsgd_plan_run_f64 on a row-parallel plan under a communicator): the same ranges and
+// the same zeroing of the header words, no rank words (none travel: the ranks agreed once per call), and the job's samples
+// and active rows ADDED to the context's scalars -- they run on over the call's steps, and over the calls until
+// dsgd_synchronize, as a local plan run's n_active does.  ONE workgroup; the stream orders the steps.
+__global__ void __launch_bounds__(RP64_THREADS) dsgd_rp64_header_plan_kernel(unsigned long long* slots, long long stride, int K, int dp,
+                                                                             WorkSeg* segs, DevScalars* sc) {
+  __shared__ unsigned long long tot[2];
+  const int tid = threadIdx.x;
+  if (tid < 2) tot[tid] = 0ull;
+  __syncthreads();
+  unsigned long long n_sum = 0ull, a_sum = 0ull;
+  for (int k = tid; k < K; k += RP64_THREADS) {
+    unsigned long long* h = slots + (long long)k * stride + dp;
+    const unsigned long long n = h[RP64_HDR_N], act = h[RP64_HDR_ACTIVE];
+    h[RP64_HDR_N] = 0ull;
+    h[RP64_HDR_ACTIVE] = 0ull;
+    WorkSeg sg;
+    sg.begin = 0;
+    sg.end = (long long)n;
+    segs[k] = sg;
+    n_sum += n;
+    a_sum += act;
+  }
+  if (n_sum) atomicAdd(&tot[0], n_sum);
+  if (a_sum) atomicAdd(&tot[1], a_sum);
+  __syncthreads();
+  if (tid == 0) {
+    sc->n_samples += tot[0];
+    sc->n_active += tot[1];
   }
 }
 

@@ -41,3 +41,21 @@ RP64_HD constexpr unsigned long long rp64_rank_word(int k, bool v64) {
 }
 RP64_HD constexpr int rp64_rank_word_k(unsigned long long w) { return (int)(unsigned int)(w & 0xffffffffull); }
 RP64_HD constexpr bool rp64_rank_word_v64(unsigned long long w) { return ((w >> RP64_RANK_V64_BIT) & 1ull) != 0ull; }
+
+// A plan run's word (dsgd_plan_run_f64 on a row-parallel plan under a communicator: ONE agreement per call, in front of the
+// first slot message; the steps behind it travel without rank words).  The ranks all-reduce the [W] words in front of the
+// slots with each rank's own word in its own position, and every rank reads all of them back:
+//   bits 0..30   the hosted workers k of the rank's plan (1 <= k <= 2^31 - 1)
+//   bit  31      the value type (1: Double values, two planes per slot)
+//   bits 32..63  the steps of the call, step_end - step_begin (0: an empty run, which still takes part)
+// A call runs at most RP64_CALL_MAX_STEPS = 2^32 - 1 steps: a longer range is refused before the agreement and is cut by the
+// caller.
+constexpr int RP64_CALL_V64_BIT = 31, RP64_CALL_STEPS_SHIFT = 32;
+constexpr long long RP64_CALL_MAX_STEPS = 0xffffffffLL;
+RP64_HD constexpr unsigned long long rp64_call_word(int k, bool v64, long long steps) {
+  return ((unsigned long long)(unsigned int)k & 0x7fffffffull) | ((v64 ? 1ull : 0ull) << RP64_CALL_V64_BIT) |
+         ((unsigned long long)steps << RP64_CALL_STEPS_SHIFT);
+}
+RP64_HD constexpr int rp64_call_word_k(unsigned long long w) { return (int)(w & 0x7fffffffull); }
+RP64_HD constexpr bool rp64_call_word_v64(unsigned long long w) { return ((w >> RP64_CALL_V64_BIT) & 1ull) != 0ull; }
+RP64_HD constexpr long long rp64_call_word_steps(unsigned long long w) { return (long long)(w >> RP64_CALL_STEPS_SHIFT); }

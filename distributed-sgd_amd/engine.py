@@ -536,7 +536,9 @@ class Engine:
 
     def comm_init_f64(self, unique_id, world_size, rank):
         """Attach this fp64 engine to a communicator (dsgd_comm_init_f64): one column ranking and one vexp on every rank
-        from here on, sync_step_f64 / sync_step / loss_acc span the ranks, plans are refused until comm_destroy."""
+        from here on, sync_step_f64 / sync_step / loss_acc span the ranks; row-parallel plans (plan(..., rp64=True),
+        plan_flat(rp64=True)) are accepted and their plan_run is a collective call with one agreement per call; every other
+        plan is refused until comm_destroy."""
         if len(unique_id) != _lib.UNIQUE_ID_BYTES:
             raise ValueError("unique id must be %d bytes" % _lib.UNIQUE_ID_BYTES)
         check(self._lib.dsgd_comm_init_f64(self._ctx, C.c_char_p(unique_id), C.c_int32(world_size), C.c_int32(rank)))

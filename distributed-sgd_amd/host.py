@@ -655,6 +655,8 @@ class MasterSync(_DistributedEval):
                 if _f64_rp_plans():
                     # DSGD_F64_RP_PLANS=1: a row-parallel plan instead -- the device draws the lists the host has just drawn (the
                     # same stream from the same state: the generator stays where the host left it), else the host's go up
+                    # (with a communicator attached the device draw is refused, -7: "try the next", and plan_flat(rp64=True)
+                    # succeeds -- the epoch is ONE plan_run per rank)
                     self._rp_plans = True
                     rp = self._rp64_from_seed(lists["seed_before"], split, max_samples, batch_size) if split is not None else None
                     if rp is not None and rp["n_steps"] == lists["n_steps"]:

@@ -128,9 +128,40 @@ enum {
  *   - dsgd_loss_acc returns the job's loss, accuracy and counts on every rank (ranges are local rows; the tallies are
  *     summed), bit for bit a single context's over the union of the ranges.
  *   - dsgd_gradient_f64, dsgd_forward_f64, dsgd_update_grad_f64 and the get / set of weights and dimSparsity stay local.
- *   - dsgd_plan_create / _n / _from_seed, dsgd_plan_run / _f64 / _async_f64, dsgd_async_plan_create and
- *     dsgd_async_step_f64 return DSGD_EUNSUPPORTED and change nothing: the persistent column-slice kernel cannot hold a
- *     collective.  (host.MasterSync.fit falls back from a refused plan to one dsgd_sync_step_f64 per step.)
+ *   - ROW-PARALLEL PLANS RUN ACROSS THE RANKS.  dsgd_plan_create_rp64_n is accepted (local, not collective: the lists index
+ *     the rank's own rows and are checked as without a communicator), and dsgd_plan_run_f64 on such a plan (dsgd_plan_run:
+ *     its float lr promoted) is a COLLECTIVE call: every rank runs steps [step_begin, step_end) of its own plan, which
+ *     hosts k workers, and after every step every rank holds the same bits -- those of a loop of dsgd_sync_step_f64 calls
+ *     under the same communicator on the same lists, i.e. of ONE fp64 context over all the rows running dsgd_sync_steps_f64
+ *     with the K = k * W lists in rank-major order.  Float and Double values (Double under dsgd_comm_init_f64v, both words
+ *     gathered, as below).  The ranks agree ONCE PER CALL: before any worker's sums travel they all-reduce one word per rank
+ *     (csrc/dsgd_rp64_gather.hpp rp64_call_word: k, the value type, step_end - step_begin) and the host reads them back --
+ *     the call's one host read; the steps behind it are enqueued back to back (per step: the gather form of the gradient
+ *     kernel, the slots' messages, a header kernel, the single context's finish; no upload, no synchronisation) and
+ *     dsgd_synchronize collects the statistics, which are the JOB's samples and active rows on every rank.  Ranks that
+ *     disagree on k, the value type or the number of steps all get DSGD_EINVAL with nothing changed (the weights keep
+ *     their bits, the gather buffer is clean, the next matched call works); the message names the rank and what differed.
+ *     An empty run (step_begin == step_end) takes part in the agreement and does nothing else.  At most 2^32 - 1 steps per
+ *     call (DSGD_EINVAL before the agreement: cut the range).  A plan holds lists and nothing else: one created detached
+ *     runs attached, and the other way round.  A plan whose record is switched on (dsgd_plan_record) is refused at its run
+ *     with DSGD_EUNSUPPORTED while a communicator is attached.  WHAT A RANK CHECKS ALONE: the record, the 2^32 - 1 steps,
+ *     k * W overflowing an int, and everything dsgd_plan_run_f64 checks without a communicator (the step range against the
+ *     plan, data and dimSparsity present, a plan from before the last load) are judged from the rank's own arguments and
+ *     state BEFORE the agreement, so they must hold, or fail, on every rank: a rank refused there alone has not
+ *     entered the agreement, and the others wait in its all-reduce.  Only k, the value type and the number of steps are
+ *     compared between the ranks.  THE STATISTICS WINDOW: the job's samples and active rows run on over the calls until
+ *     dsgd_synchronize, or until the next call that writes statistics of its own (dsgd_sync_step_f64, dsgd_loss_acc, ...),
+ *     whichever comes first; such a call closes the window and discards what the plan runs had counted (the weights are
+ *     not affected), and a dsgd_synchronize behind it reports no rows of those runs.  Call dsgd_synchronize between a
+ *     plan run and a per-step call if the run's totals matter.  A collective error inside the call returns DSGD_ERCCL and
+ *     drops the gather buffer; the weights are then those behind the LAST COMPLETED STEP, as for any multi-step call (the
+ *     message names it), the same on every rank only if every rank failed at the same step.
+ *   - dsgd_plan_create / _n / _from_seed / _from_seed_rp64, dsgd_plan_run / _f64 on a column-slice plan,
+ *     dsgd_plan_run_async_f64, dsgd_async_plan_create / _rp64, dsgd_sync_steps_f64 and dsgd_async_step_f64 return
+ *     DSGD_EUNSUPPORTED and change nothing: the persistent column-slice kernel cannot hold a collective, and the device
+ *     shuffle and the asynchronous iteration have no form that spans the ranks.  (host.MasterSync.fit falls back from a
+ *     refused plan to one dsgd_sync_step_f64 per step; with DSGD_F64_RP_PLANS=1 to a row-parallel plan on host-drawn
+ *     lists, ONE dsgd_plan_run_f64 per epoch and rank.)
  *   DOUBLE FEATURE VALUES ACROSS RANKS: a communicator attached with dsgd_comm_init_f64v is dsgd_comm_init_f64's in every
  *   rule above, and also (1) attaches with Double data loaded, (2) accepts dsgd_load_csr_f64 while attached -- the load is
  *   collective as dsgd_load_csr is: ranking and vexp are agreed at the rows' first use -- and (3) on Double data
@@ -141,7 +172,8 @@ enum {
  *   elided.  The word that carries a rank's n_workers carries its value type too: ranks that disagree on either all get
  *   DSGD_EINVAL, weights unchanged, and the next matched step works.  Float data on every rank takes the one-word gather,
  *   bit for bit dsgd_comm_init_f64's.  dsgd_loss_acc on Double data gives the job's tallies on every rank;
- *   dsgd_sync_steps_f64, plans and dsgd_async_step_f64 stay refused as under dsgd_comm_init_f64.
+ *   dsgd_sync_steps_f64, the plans listed above and dsgd_async_step_f64 stay refused as under dsgd_comm_init_f64; a
+ *   row-parallel plan's run on Double data gathers both words per step as dsgd_sync_step_f64 does.
  *   Without a communicator nothing changes.  Real RCCL with more than one rank has not run; no multi-GPU speed is claimed.
  *   DOUBLE FEATURE VALUES (dsgd_load_csr_f64; csrc/dsgd_rp64.hpp).  The reference reads `elems(1).toDouble`
  *   (utils/Dataset.scala:30); dsgd_load_csr takes floats, which moves every value of a real data file by up to 6e-8
@@ -183,7 +215,8 @@ enum {
  *   dsgd_grad_kernel_name says which form served the last call's steps.  Float and Double values, any
  *   n_workers >= 1, any list lengths; the weights stay in the layout they are found in.  Refused before anything is
  *   enqueued, nothing changed, the context usable: DSGD_ESTATE on an fp32 context; DSGD_EUNSUPPORTED with a communicator
- *   attached (the gather needs a host read per step: dsgd_sync_step_f64 stays the path there); DSGD_EINVAL for null
+ *   attached (the lists of a call are not resident; a row-parallel plan is the epoch form there: "ACROSS RANKS");
+ *   DSGD_EINVAL for null
  *   pointers, n_steps < 1, n_workers < 1, offsets that do not start at 0, decrease or do not end at n_idx, and an empty
  *   list of any step; DSGD_ERANGE for a row index outside the loaded rows in any step.
  *   ROW-PARALLEL PLANS (dsgd_plan_create_rp64_n, dsgd_plan_create_from_seed_rp64, dsgd_async_plan_create_rp64, declared
@@ -209,9 +242,12 @@ enum {
  *   float rounding of s summed in rank order, the iteration itself uses the slice-order sum (they differ in the last bits
  *   of the double).  dsgd_plan_info: vals[0] = 6, strides 0, [7] words per step of the record.  dsgd_grad_kernel_name
  *   names the gradient kernel of the last run.  Refused, nothing changed, the context usable: DSGD_ESTATE on an fp32
- *   context; DSGD_EUNSUPPORTED with a communicator attached; DSGD_EINVAL / DSGD_ERANGE as dsgd_sync_steps_f64 (null
- *   pointers, an empty list, offsets that are no prefix sum ending at n_idx; a row index outside the rows loaded, where
- *   data is loaded).  The existing creators refuse exactly as before.
+ *   context; DSGD_EINVAL / DSGD_ERANGE as dsgd_sync_steps_f64 (null pointers, an empty list, offsets that are no prefix
+ *   sum ending at n_idx; a row index outside the rows loaded, where data is loaded).  WITH A COMMUNICATOR ATTACHED
+ *   ("ACROSS RANKS"): dsgd_plan_create_rp64_n is accepted and dsgd_plan_run_f64 / dsgd_plan_run on its plan is a collective
+ *   call, one agreement and one host read per call; dsgd_plan_create_from_seed_rp64, dsgd_async_plan_create_rp64 and
+ *   dsgd_plan_run_async_f64 return DSGD_EUNSUPPORTED, as does the run of a plan that keeps a record.  The existing
+ *   creators refuse exactly as before.
  * The entry points below that name fp64 return DSGD_ESTATE on an fp32 context (dsgd_precision excepted).            */
 
 typedef struct dsgd_ctx dsgd_ctx;

@@ -10,7 +10,9 @@ accuracy -- with the HIP engine hosting all the workers.
 zero-lag schedule of host.MasterAsync (one update at a time, every update seen by every worker).
 --f64-rp-plans (or DSGD_F64_RP_PLANS=1; with --precision fp64): what the column-slice plans refuse -- real files' Double
 feature values, more than 4 workers, batches beyond 1,024 rows -- runs as resident row-parallel plans (include/dsgd.h
-"THE FP64 MODE", ROW-PARALLEL PLANS); the asynchronous fit then keeps the files' Doubles too.  Off by default.
+"THE FP64 MODE", ROW-PARALLEL PLANS); the asynchronous fit then keeps the files' Doubles too.  With a communicator attached
+(one process per GPU, comm_init_f64 / comm_init_f64v) a synchronous epoch then runs as ONE row-parallel plan run per rank on
+host-drawn lists, one agreement between the ranks per epoch, instead of one sync_step_f64 per step.  Off by default.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,7 +26,7 @@ ap.add_argument("--synthetic", type=int, default=0, help="use N synthetic RCV1-l
 ap.add_argument("--device", type=int, default=0)
 ap.add_argument("--weights-out", help="write the `idx:value` line of Main.scala:114 here instead of logging it")
 ap.add_argument("--precision", choices=("fp32", "fp64"), default="fp32", help="fp64: the reference's Double arithmetic")
-ap.add_argument("--f64-rp-plans", action="store_true", help="fp64: refused plans run as row-parallel plans (DSGD_F64_RP_PLANS=1)")
+ap.add_argument("--f64-rp-plans", action="store_true", help="fp64: refused plans run as row-parallel plans, under a communicator too: one plan run per epoch and rank (DSGD_F64_RP_PLANS=1)")
 a = ap.parse_args()
 if a.f64_rp_plans:
     os.environ["DSGD_F64_RP_PLANS"] = "1"   # (host.MasterSync / host.MasterAsync read it at every fit)
