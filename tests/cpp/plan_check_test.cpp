@@ -141,6 +141,52 @@ int main() {
     CHECK(v.bad_at == -1 && !v.fits);                             // 2,400 items: the stale "fits" was the fault
   }
 
+  // ---- the caller's flat lists of n_steps x n_workers workers (dsgd_sync_steps_f64, dsgd_plan_create_rp64_n) ----
+  {
+    auto flat = [](const std::vector<int32_t>& idx, const std::vector<int64_t>& off, long long n_steps, long long n_workers, long long n_rows) {
+      return flat_lists_check(idx.data(), (long long)idx.size(), off.data(), n_steps, n_workers, n_rows);   // (off: exactly n_lists + 1 entries)
+    };
+    const std::vector<int32_t> idx = {0, 9, 4, 4, 0, 7};
+    const std::vector<int64_t> off = {0, 2, 3, 5, 6};   // two steps of two workers
+    FlatListsCheck v = flat(idx, off, 2, 2, 10);
+    CHECK(v.kind == FLAT_LISTS_OK && v.list == -1 && v.pos == -1);
+    v = flat(idx, {1, 2, 3, 5, 6}, 2, 2, 10);
+    CHECK(v.kind == FLAT_LISTS_FIRST_OFFSET && v.value == 1);
+    v = flat(idx, {0, 2, 3, 5, 5}, 2, 2, 10);            // the end disagrees with n_idx: judged before any list
+    CHECK(v.kind == FLAT_LISTS_END && v.value == 5);
+    v = flat(idx, {0, 2, 3, 5, 7}, 2, 2, 10);
+    CHECK(v.kind == FLAT_LISTS_END && v.value == 7);
+    v = flat(idx, {0, 3, 2, 5, 6}, 2, 2, 10);            // a decreasing offset: list 1 is worker 1 of step 0
+    CHECK(v.kind == FLAT_LISTS_OFFSETS && v.list == 1 && v.list / 2 == 0 && v.list % 2 == 1 && v.value == 2);
+    v = flat(idx, {0, 2, 9, 5, 6}, 2, 2, 10);            // an offset that leaves idx (idx[9] is never read)
+    CHECK(v.kind == FLAT_LISTS_OFFSETS && v.list == 1 && v.value == 9);
+    v = flat(idx, {0, 2, 2, 5, 6}, 2, 2, 10);            // an empty list in the middle ...
+    CHECK(v.kind == FLAT_LISTS_EMPTY && v.list == 1);
+    v = flat(idx, {0, 2, 3, 6, 6}, 2, 2, 10);            // ... and as the last list: worker 1 of step 1
+    CHECK(v.kind == FLAT_LISTS_EMPTY && v.list == 3 && v.list / 2 == 1 && v.list % 2 == 1);
+    v = flat(idx, {0, 0, 3, 5, 6}, 2, 2, 10);            // ... and as the first
+    CHECK(v.kind == FLAT_LISTS_EMPTY && v.list == 0);
+    // indices outside the rows, at the first and the last position: -1 and n_rows
+    for (const int32_t bad : {-1, 10}) {
+      std::vector<int32_t> first = idx, last = idx;
+      first.front() = bad;
+      last.back() = bad;
+      v = flat(first, off, 2, 2, 10);
+      CHECK(v.kind == FLAT_LISTS_INDEX && v.pos == 0 && v.value == bad);
+      v = flat(last, off, 2, 2, 10);
+      CHECK(v.kind == FLAT_LISTS_INDEX && v.pos == 5 && v.value == bad);
+      CHECK(flat(first, off, 2, 2, -1).kind == FLAT_LISTS_OK);   // the rows are not known: the indices are not judged
+      CHECK(flat(last, off, 2, 2, -1).kind == FLAT_LISTS_OK);
+      CHECK(flat(last, off, 2, 2, 11).kind == (bad < 0 ? FLAT_LISTS_INDEX : FLAT_LISTS_OK));   // one row more
+    }
+    CHECK(flat(idx, {0, 2, 2, 5, 6}, 2, 2, -1).kind == FLAT_LISTS_EMPTY);   // (the offsets are judged either way)
+    // no entries at all with one step: the one list is empty (idx may be an empty array: nothing of it is read)
+    v = flat({}, {0, 0}, 1, 1, 10);
+    CHECK(v.kind == FLAT_LISTS_EMPTY && v.list == 0);
+    v = flat({}, {0, 0, 0}, 1, 2, -1);
+    CHECK(v.kind == FLAT_LISTS_EMPTY && v.list == 0);
+  }
+
   std::fprintf(stderr, "plan_check_test: all checks passed (%d)\n", g_checks);
   return 0;
 }
