@@ -44,6 +44,7 @@ SYMBOLS = [
     "dsgd_comm_init_f64v",
     "dsgd_plan_create_rp64_n", "dsgd_plan_create_from_seed_rp64", "dsgd_async_plan_create_rp64",
     "dsgd_predict_ranges", "dsgd_predict_ranges_f64",
+    "dsgd_plan_create_from_seed_job", "dsgd_plan_create_from_seed_job_rp64",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -102,6 +103,10 @@ def load():
             fn.restype = C.c_int
     if hasattr(lib, "dsgd_comm_init_f64v"):
         lib.dsgd_comm_init_f64v.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32]
+    for name in ("dsgd_plan_create_from_seed_job", "dsgd_plan_create_from_seed_job_rp64"):
+        if hasattr(lib, name):   # (ctx, jstate*, job_len*, n_job, first, n_local, split_begin*, max_samples, batch_size, out*, n_steps*, draws*)
+            getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 

@@ -4017,16 +4017,31 @@ static hipError_t seed_scratch(dsgd_ctx* c, int i, size_t bytes, void** out) {
 // ---- an epoch's lists drawn on the device, draw for draw the reference's stream (csrc/dsgd_shuffle.hpp) ---------------------
 // (rp64: dsgd_plan_create_from_seed_rp64 -- the same draws into a row-parallel plan: an fp64 context, float or Double data, no
 //  limit of the column slices; `what` names the entry point in the messages)
-static int plan_from_seed_impl(dsgd_ctx* c, const char* what, bool rp64, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end,
-                               int32_t n_splits, int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
+//
+// ONE function behind both forms.  The stream is a pure function of the seed and the lengths of the JOB's n_splits splits:
+// the scan and the walk below run over all of them.  The plan holds the lists of the n_local workers this context hosts
+// (job workers first .. first + n_local - 1; split_begin has n_local entries), and only their start records and
+// rejections go to the device.
+//   job == false   dsgd_plan_create_from_seed / _rp64: the context hosts the whole job (first = 0, n_local = n_splits), a
+//                  worker's length is split_end - split_begin, batches up to JR_MAX_TAKE rows, up to JR_MAX_REJ rejections
+//                  inside a shuffle, dsgd_jr_slice_kernel; refused in an fp64 context with a communicator.
+//   job == true    dsgd_plan_create_from_seed_job / _rp64: the lengths are job_len (split_end is not read), any batch size,
+//                  up to JR_JOB_MAX_REJ rejections, dsgd_jr_slice_job_kernel; the row-parallel form is a LOCAL call that a
+//                  communicator does not refuse (the plan then runs through plan_run_rp64_ranks).
+static int plan_from_seed_impl(dsgd_ctx* c, const char* what, bool rp64, bool job, uint64_t* jstate, const int64_t* job_len, int32_t first,
+                               int32_t n_local, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits, int64_t max_samples,
+                               int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
   DSGD_TRY(check_ctx(c));
-  if (!jstate || !split_begin || !split_end || !out || !n_steps_out || n_splits < 1 || batch_size < 1)
+  if (!jstate || !split_begin || (job ? !job_len : !split_end) || !out || !n_steps_out || n_splits < 1 || batch_size < 1)
     return fail(DSGD_EINVAL, "bad arguments");
+  if (job && (n_local < 1 || first < 0 || (long long)first + n_local > n_splits))
+    return fail(DSGD_EINVAL, "the hosted workers %d .. %lld are not workers of a job of %d", first, (long long)first + n_local - 1, n_splits);
+  const bool comm_ok = job && rp64;   // (a row-parallel plan spans the ranks at its run; creating it is local)
   {   // (refused with *out as it was)
     std::lock_guard<std::mutex> lk0(c->mu);
     if (rp64) {
       DSGD_TRY(require_fp64(c, what));
-      DSGD_TRY(refuse_fp64_comm(c, what));
+      if (!comm_ok) DSGD_TRY(refuse_fp64_comm(c, what));
     } else {
       DSGD_TRY(refuse_val64(c, what));
     }
@@ -4034,38 +4049,53 @@ static int plan_from_seed_impl(dsgd_ctx* c, const char* what, bool rp64, uint64_
   *out = nullptr;
   *n_steps_out = 0;
   if (draws_out) *draws_out = 0;
+  auto len_of = [&](long long j) -> long long { return job ? (long long)job_len[j] : (long long)(split_end[j] - split_begin[j]); };
   long long max_len = 0;
   for (int k = 0; k < n_splits; ++k) {
-    const long long len = split_end[k] - split_begin[k];
-    if (len < 1 || split_begin[k] < 0) return fail(DSGD_EINVAL, "worker %d has no rows", k);
+    const long long len = len_of(k);
+    if (len < 1 || (!job && split_begin[k] < 0)) return fail(DSGD_EINVAL, "worker %d has no rows", k);
     max_len = std::max(max_len, len);
   }
-  if (batch_size > JR_MAX_TAKE || max_len > JR_MAX_LEN)
+  if (job) {
+    for (int i = 0; i < n_local; ++i)
+      if (split_begin[i] < 0) return fail(DSGD_EINVAL, "hosted worker %d starts at a negative row", i);
+    if (max_len > JR_MAX_LEN)
+      return fail(DSGD_EUNSUPPORTED, "device-drawn lists serve splits up to %d rows (draw them on the host)", JR_MAX_LEN);
+  } else if (batch_size > JR_MAX_TAKE || max_len > JR_MAX_LEN)
     return fail(DSGD_EUNSUPPORTED, "device-drawn lists serve batches up to %d rows of splits up to %d rows (draw them on the host)", JR_MAX_TAKE, JR_MAX_LEN);
+  const int max_rej = job ? JR_JOB_MAX_REJ : JR_MAX_REJ;
+  const int chunks = job ? (int)(((long long)batch_size + JR_MAX_TAKE - 1) / JR_MAX_TAKE) : 1;   // workgroups per list
   // steps the reference runs before an empty slice (core/Master.scala:184-188; the slave's Vec.sum throws on it)
   long long n_steps = 0;
   for (long long b = 0; b < max_samples; b += batch_size) {
     bool ok = true;
-    for (int k = 0; k < n_splits; ++k) ok = ok && b < split_end[k] - split_begin[k];
+    for (int k = 0; k < n_splits; ++k) ok = ok && b < len_of(k);
     if (!ok) break;
     ++n_steps;
   }
   if (n_steps == 0) return DSGD_OK;
-  const long long n_shuf = n_steps * n_splits;
-  std::vector<int64_t> offsets((size_t)n_shuf + 1, 0);
+  const long long n_shuf = n_steps * n_splits;          // shuffles of the job
+  const long long n_lists = n_steps * n_local;          // lists of the plan: the hosted workers'
+  if (job && n_lists * chunks > 0x7fffffffLL) return fail(DSGD_EUNSUPPORTED, "more lists than one launch draws (draw them on the host)");
+  std::vector<int64_t> offsets((size_t)n_lists + 1, 0);
   std::vector<long long> start((size_t)n_shuf + 1, 0);   // nominal raw index of every shuffle's start (no rejections)
   for (long long q = 0; q < n_shuf; ++q) {
-    const long long len = split_end[q % n_splits] - split_begin[q % n_splits], b = (q / n_splits) * (long long)batch_size;
-    offsets[(size_t)q + 1] = offsets[(size_t)q] + std::min<long long>(batch_size, len - b);
+    const long long len = len_of(q % n_splits);
     start[(size_t)q + 1] = start[(size_t)q] + (len >= 2 ? len - 1 : 0);
+  }
+  for (long long q = 0; q < n_lists; ++q) {
+    const long long len = len_of(first + q % n_local), b = (q / n_local) * (long long)batch_size;
+    offsets[(size_t)q + 1] = offsets[(size_t)q] + std::min<long long>(batch_size, len - b);
   }
   const long long nominal = start[(size_t)n_shuf];
   std::lock_guard<std::mutex> lk(c->mu);
-  DSGD_TRY(refuse_fp64_comm(c, what));
+  if (!comm_ok) DSGD_TRY(refuse_fp64_comm(c, what));
   if (!rp64) DSGD_TRY(refuse_val64(c, what));
   DSGD_TRY(bind(c, true));
-  for (int k = 0; k < n_splits; ++k)
-    if (split_end[k] > c->n_rows) return fail(DSGD_ERANGE, "worker %d's rows [%lld, %lld) outside the %lld loaded", k, (long long)split_begin[k], (long long)split_end[k], c->n_rows);
+  for (int i = 0; i < n_local; ++i)
+    if (split_begin[i] + len_of(first + i) > c->n_rows)
+      return fail(DSGD_ERANGE, "worker %d's rows [%lld, %lld) outside the %lld loaded", first + i, (long long)split_begin[i],
+                  (long long)(split_begin[i] + len_of(first + i)), c->n_rows);
   DSGD_TRY(ensure_build_stream(c));
   hipStream_t bs = c->build_stream;
   const unsigned long long s0 = *jstate & JR_MASK;
@@ -4158,7 +4188,7 @@ static int plan_from_seed_impl(dsgd_ctx* c, const char* what, bool rp64, uint64_
           }
           while (start[(size_t)j + 1] <= d) ++j;
           close_upto(j);
-          const long long len = split_end[j % n_splits] - split_begin[j % n_splits];
+          const long long len = len_of(j % n_splits);
           const unsigned int n = (unsigned int)(len - (d - start[(size_t)j]));
           if ((n & (n - 1)) != 0 && cu[(size_t)(at + t)] >= (0x80000000u / n) * n) {
             rej_list.push_back((int)(ci[(size_t)(at + t)] - shuf[(size_t)j].raw0));
@@ -4178,11 +4208,25 @@ static int plan_from_seed_impl(dsgd_ctx* c, const char* what, bool rp64, uint64_
     }
   }
   for (long long q = 0; q < n_shuf; ++q)
-    if (shuf[(size_t)q].rej_end - shuf[(size_t)q].rej_begin > JR_MAX_REJ)
-      return fail(DSGD_EUNSUPPORTED, "more than %d rejections inside one shuffle (draw the lists on the host)", JR_MAX_REJ);
+    if (shuf[(size_t)q].rej_end - shuf[(size_t)q].rej_begin > max_rej)
+      return fail(DSGD_EUNSUPPORTED, "more than %d rejections inside one shuffle (draw the lists on the host)", max_rej);
+  if (job) {   // the hosted workers' records and rejections alone, step-major, hosted-worker-minor
+    std::vector<JrShuf> mine((size_t)n_lists);
+    std::vector<int> rej_mine;
+    long long hosted_max = 0;
+    for (int i = 0; i < n_local; ++i) hosted_max = std::max(hosted_max, len_of(first + i));
+    for (long long q = 0; q < n_lists; ++q) {
+      const JrShuf& s = shuf[(size_t)((q / n_local) * n_splits + first + q % n_local)];
+      mine[(size_t)q] = JrShuf{s.raw0, (int)rej_mine.size(), (int)rej_mine.size() + (s.rej_end - s.rej_begin)};
+      rej_mine.insert(rej_mine.end(), rej_list.begin() + s.rej_begin, rej_list.begin() + s.rej_end);
+    }
+    shuf.swap(mine);
+    rej_list.swap(rej_mine);
+    max_len = hosted_max;   // (the bitmap of the slice kernel: the longest split traced HERE)
+  }
   // ---- the plan's frame, then pass B straight into its index buffer ----
   dsgd_plan* p = nullptr;
-  DSGD_TRY(plan_frame(c, offsets.data(), n_steps, n_splits, &p, rp64));
+  DSGD_TRY(plan_frame(c, offsets.data(), n_steps, n_local, &p, rp64));
   lap("plan frame");
   p->idx_trusted = true;
   p->drawn = true;
@@ -4191,25 +4235,42 @@ static int plan_from_seed_impl(dsgd_ctx* c, const char* what, bool rp64, uint64_
   int *d_rej = nullptr, *d_err = nullptr;
   long long *d_sb = nullptr, *d_off = nullptr;
   auto drop2 = [&]() {};   // (scratch of the context)
-  std::vector<long long> sb2(2 * (size_t)n_splits);
-  for (int k = 0; k < n_splits; ++k) {
+  std::vector<long long> sb2(2 * (size_t)n_local);   // job: begin | length, else begin | end
+  for (int k = 0; k < n_local; ++k) {
     sb2[(size_t)k] = split_begin[k];
-    sb2[(size_t)n_splits + (size_t)k] = split_end[k];
+    sb2[(size_t)n_local + (size_t)k] = job ? (long long)job_len[first + k] : (long long)split_end[k];
   }
   int h_err = 0;
-  hipError_t e = seed_scratch(c, 4, sizeof(JrShuf) * (size_t)n_shuf, (void**)&d_shuf);
+  hipError_t e = seed_scratch(c, 4, sizeof(JrShuf) * (size_t)n_lists, (void**)&d_shuf);
   if (e == hipSuccess) e = seed_scratch(c, 5, sizeof(int) * std::max<size_t>(1, rej_list.size()), (void**)&d_rej);
   if (e == hipSuccess) e = seed_scratch(c, 6, sizeof(int), (void**)&d_err);
   if (e == hipSuccess) e = seed_scratch(c, 7, sizeof(long long) * sb2.size(), (void**)&d_sb);
   if (e == hipSuccess) e = seed_scratch(c, 8, sizeof(long long) * offsets.size(), (void**)&d_off);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_shuf, shuf.data(), sizeof(JrShuf) * (size_t)n_shuf, hipMemcpyHostToDevice, bs);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_shuf, shuf.data(), sizeof(JrShuf) * (size_t)n_lists, hipMemcpyHostToDevice, bs);
   if (e == hipSuccess && !rej_list.empty()) e = hipMemcpyAsync(d_rej, rej_list.data(), sizeof(int) * rej_list.size(), hipMemcpyHostToDevice, bs);
   if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(int), bs);
   if (e == hipSuccess) e = hipMemcpyAsync(d_sb, sb2.data(), sizeof(long long) * sb2.size(), hipMemcpyHostToDevice, bs);
   if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets.data(), sizeof(long long) * offsets.size(), hipMemcpyHostToDevice, bs);
-  if (e == hipSuccess) {
-    static const JrAffine back_one = jr_inverse_step();
-    static const JrAffine back_block = jr_power(back_one, JR_SLICE_THREADS);
+  static const JrAffine back_one = jr_inverse_step();
+  static const JrAffine back_block = jr_power(back_one, JR_SLICE_THREADS);
+  if (e == hipSuccess && job) {
+    JrSliceJobArgs a;
+    a.s0 = s0;
+    a.back_block = back_block;
+    a.back_one = back_one;
+    a.shuf = d_shuf;
+    a.rej = d_rej;
+    a.split_begin = d_sb;
+    a.len = d_sb + n_local;
+    a.offsets = d_off;
+    a.idx_out = p->d_idx;
+    a.n_local = n_local;
+    a.batch_size = batch_size;
+    a.chunks = chunks;
+    a.err = d_err;
+    hipLaunchKernelGGL(dsgd_jr_slice_job_kernel, dim3((unsigned)(n_lists * chunks)), dim3(JR_SLICE_THREADS), jr_slice_job_lds_bytes(max_len), bs, a);
+    e = hipGetLastError();
+  } else if (e == hipSuccess) {
     JrSliceArgs a;
     a.s0 = s0;
     a.back_block = back_block;
@@ -4246,13 +4307,26 @@ static int plan_from_seed_impl(dsgd_ctx* c, const char* what, bool rp64, uint64_
 }
 int dsgd_plan_create_from_seed(dsgd_ctx* c, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
                                int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
-  return plan_from_seed_impl(c, "dsgd_plan_create_from_seed", false, jstate, split_begin, split_end, n_splits, max_samples, batch_size, out,
-                             n_steps_out, draws_out);
+  return plan_from_seed_impl(c, "dsgd_plan_create_from_seed", false, false, jstate, nullptr, 0, n_splits, split_begin, split_end, n_splits,
+                             max_samples, batch_size, out, n_steps_out, draws_out);
 }
 int dsgd_plan_create_from_seed_rp64(dsgd_ctx* c, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
                                     int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
-  return plan_from_seed_impl(c, "dsgd_plan_create_from_seed_rp64", true, jstate, split_begin, split_end, n_splits, max_samples, batch_size,
-                             out, n_steps_out, draws_out);
+  return plan_from_seed_impl(c, "dsgd_plan_create_from_seed_rp64", true, false, jstate, nullptr, 0, n_splits, split_begin, split_end, n_splits,
+                             max_samples, batch_size, out, n_steps_out, draws_out);
+}
+// ... for a job's share of workers (include/dsgd.h): the stream over all n_job workers, the lists of the n_local hosted here
+int dsgd_plan_create_from_seed_job(dsgd_ctx* c, uint64_t* jstate, const int64_t* job_len, int32_t n_job, int32_t first, int32_t n_local,
+                                   const int64_t* split_begin, int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out,
+                                   int64_t* draws_out) {
+  return plan_from_seed_impl(c, "dsgd_plan_create_from_seed_job", false, true, jstate, job_len, first, n_local, split_begin, nullptr, n_job,
+                             max_samples, batch_size, out, n_steps_out, draws_out);
+}
+int dsgd_plan_create_from_seed_job_rp64(dsgd_ctx* c, uint64_t* jstate, const int64_t* job_len, int32_t n_job, int32_t first, int32_t n_local,
+                                        const int64_t* split_begin, int64_t max_samples, int32_t batch_size, dsgd_plan** out,
+                                        int64_t* n_steps_out, int64_t* draws_out) {
+  return plan_from_seed_impl(c, "dsgd_plan_create_from_seed_job_rp64", true, true, jstate, job_len, first, n_local, split_begin, nullptr, n_job,
+                             max_samples, batch_size, out, n_steps_out, draws_out);
 }
 
 // the lists of a plan as the device holds them (tests: the device-drawn lists against csrc/jrand.c's)

@@ -348,3 +348,201 @@ __global__ void __launch_bounds__(JR_SLICE_THREADS) dsgd_jr_slice_kernel(JrSlice
 __host__ __device__ constexpr size_t jr_slice_lds_bytes(long long len) {
   return sizeof(unsigned int) * (size_t)(((len + 31) >> 5) + JR_MAX_TAKE + JR_SLICE_THREADS + JR_MAX_HITS + JR_MAX_REJ + 4);
 }
+
+// ---- pass B for a JOB's share of workers: any batch size, up to 512 rejections a shuffle --------------------------------
+// dsgd_plan_create_from_seed_job (include/dsgd.h): the epoch's stream runs over ALL workers of a job, a context traces the
+// slices of the workers it hosts.  The trace is dsgd_jr_slice_kernel's, with three changes:
+//
+//   chunks      one workgroup per (step, hosted worker, chunk): a list of `take` entries is cut into C = ceil(batch / 1,024)
+//               chunks of at most 1,024 entries, and the chunk [b + 1,024 c, ...) of a shuffle is itself a slice of it --
+//               phases 1 and 2 run with the chunk's b and take.  Up to 1,024 rows per step that is one chunk and the
+//               existing work, (len - b) draw evaluations per list.  Beyond, EVERY chunk sweeps the steps above it:
+//               sum over c of (len - b - 1,024 c), about C x (len - b) evaluations per list -- a list of 4,096 rows costs
+//               four sweeps where four lists of 1,024 rows would have cost four sweeps as well: the cost per ENTRY is that
+//               of batch 1,024.
+//   rejections  up to JR_JOB_MAX_REJ = 512 in LDS (expected len^2 / 2^33: 128 +- 11 at 2^20 rows); phase 1 finds the raw
+//               value of a draw by bisection (csrc/dsgd_jr_bisect.hpp), phase 2 keeps the falling uniform pointer.
+//   indexing    split_begin / len by hosted worker, shuf / offsets by (step, hosted worker): the stream's position of every
+//               shuffle comes from the host's walk over the whole job (JrShuf::raw0), nothing here knows the other workers.
+#include "dsgd_jr_bisect.hpp"
+
+constexpr int JR_JOB_MAX_REJ = 512;
+struct JrSliceJobArgs {
+  unsigned long long s0;               // state in front of raw value 0
+  JrAffine back_block;                 // JR_SLICE_THREADS inverse steps at once
+  JrAffine back_one;                   // one inverse step
+  const JrShuf* shuf;                  // n_steps * n_local records, step-major, hosted-worker-minor
+  const int* rej;
+  const long long* split_begin;        // per hosted worker: where its split starts in the rows loaded here
+  const long long* len;                // per hosted worker: rows of its split
+  const long long* offsets;            // n_steps * n_local + 1 prefix offsets of the lists
+  int* idx_out;
+  int n_local, batch_size, chunks;     // chunks = ceil(batch_size / JR_MAX_TAKE): workgroups per list
+  int* err;                            // != 0: a shuffle exceeded a limit (the caller refuses)
+};
+__host__ __device__ constexpr size_t jr_slice_job_lds_bytes(long long len) {
+  return sizeof(unsigned int) * (size_t)(((len + 31) >> 5) + JR_MAX_TAKE + JR_SLICE_THREADS + JR_MAX_HITS + JR_JOB_MAX_REJ + 4);
+}
+
+__global__ void __launch_bounds__(JR_SLICE_THREADS) dsgd_jr_slice_job_kernel(JrSliceJobArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned int jr_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long q = (long long)blockIdx.x / a.chunks;       // the list: (step, hosted worker)
+  const int chunk = (int)((long long)blockIdx.x % a.chunks);
+  const int k = (int)(q % a.n_local);
+  const long long st = q / a.n_local;
+  const long long len = a.len[k];
+  const long long list_take = a.offsets[q + 1] - a.offsets[q];
+  const long long c0 = (long long)chunk * JR_MAX_TAKE;        // the chunk's first entry of the list
+  if (c0 >= list_take) return;                                // (a short last slice has fewer chunks)
+  const long long b = st * (long long)a.batch_size + c0;
+  const long long o0 = a.offsets[q] + c0;
+  const int take = (int)(list_take - c0 < JR_MAX_TAKE ? list_take - c0 : JR_MAX_TAKE);
+  const JrShuf sh = a.shuf[q];
+  const int n_rej = sh.rej_end - sh.rej_begin;
+  if (len < 1 || len > JR_MAX_LEN || n_rej < 0 || n_rej > JR_JOB_MAX_REJ || b + take > len) {
+    if (tid == 0) atomicOr(a.err, 1);
+    return;
+  }
+  // LDS: bitmap of the wanted positions | wanted[1024] | karr[1024] (the block's draws) | hits | rejections | counters
+  const int bm_words = (int)((len + 31) >> 5);
+  unsigned int* bitmap = jr_lds;
+  int* wanted = reinterpret_cast<int*>(bitmap + bm_words);
+  int* karr = wanted + JR_MAX_TAKE;
+  int* hits = karr + JR_SLICE_THREADS;
+  int* rej = hits + JR_MAX_HITS;
+  int* ctl = rej + JR_JOB_MAX_REJ;   // [0] hits of the block
+  for (int i = tid; i < bm_words; i += JR_SLICE_THREADS) bitmap[i] = 0u;
+  for (int i = tid; i < n_rej; i += JR_SLICE_THREADS) rej[i] = a.rej[sh.rej_begin + i];
+  if (tid == 0) ctl[0] = 0;
+  __syncthreads();
+  const unsigned long long s_first = jr_jump_dev(a.s0, (unsigned long long)sh.raw0);   // state in front of the shuffle's first raw value
+  // the draw of step n (n = len .. 2) is draw m = len - n of the shuffle
+  auto draw_of_step = [&](long long n) -> int {
+    const long long raw = dsgd_jr_raw_of_draw_bisect(len - n, rej, n_rej);
+    const unsigned long long s = jr_jump_dev(s_first, (unsigned long long)(raw + 1));
+    return jr_next_int_of((unsigned int)(s >> 17), (unsigned int)n);
+  };
+
+  // ---- phase 1: the steps whose TOP is an entry of the chunk, n = b + 1 .. b + take (position p = n - 1), in order ----
+  for (int t = tid; t < take; t += JR_SLICE_THREADS) {
+    const long long p = b + t;
+    karr[t] = p >= 1 ? draw_of_step(p + 1) : 0;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    // wave 0 holds the entries in registers: entry t in lane t % 64, slot t / 64
+    int w[JR_MAX_TAKE / 64];
+#pragma unroll
+    for (int e = 0; e < JR_MAX_TAKE / 64; ++e) w[e] = -1;
+    for (int t = 0; t < take; ++t) {
+      const long long p = b + t;
+      if (p == 0) {   // position 0 is never on top: it wants itself from the start
+        if (lane == 0) w[0] = 0;
+        continue;
+      }
+      const int kk = karr[t];   // (uniform)
+#pragma unroll
+      for (int e = 0; e < JR_MAX_TAKE / 64; ++e)
+        if (w[e] == kk) w[e] = (int)p;
+      const int e_t = t >> 6;
+#pragma unroll
+      for (int e = 0; e < JR_MAX_TAKE / 64; ++e)
+        if (e == e_t && lane == (t & 63)) w[e] = kk;
+    }
+#pragma unroll
+    for (int e = 0; e < JR_MAX_TAKE / 64; ++e) {
+      const int t = e * 64 + lane;
+      if (t < take) {
+        wanted[t] = w[e];
+        atomicOr(&bitmap[(unsigned int)w[e] >> 5], 1u << (w[e] & 31));
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 2: the steps above the chunk, n = b + take + 1 .. len, 1,024 at a time in increasing order ----
+  const long long n_first = b + take + 1;
+  if (n_first <= len) {
+    long long n_mine = n_first + tid;                          // this lane's step of the current block
+    long long raw_mine = 0;
+    unsigned long long s_mine = 0;
+    bool have = false;
+    // (the falling uniform pointer of dsgd_jr_slice_kernel: the count of rejections at or below the block's highest draw)
+    int cnt_hi = n_rej;
+    for (long long n0 = n_first; n0 <= len; n0 += JR_SLICE_THREADS, n_mine += JR_SLICE_THREADS) {
+      int kk = -1;
+      const long long m_hi = len - n0;
+      while (cnt_hi > 0 && (long long)(rej[cnt_hi - 1] - (cnt_hi - 1)) > m_hi) --cnt_hi;   // (uniform)
+      if (n_mine <= len) {
+        const long long m = len - n_mine;
+        int cnt = cnt_hi;
+        while (cnt > 0 && (long long)(rej[cnt - 1] - (cnt - 1)) > m) --cnt;                // (rarely one iteration)
+        const long long raw = m + cnt;
+        if (!have) {   // (first block of this lane -- a lane that was beyond the end never comes back)
+          s_mine = jr_jump_dev(s_first, (unsigned long long)(raw + 1));
+          have = true;
+        } else {       // the next block's step is 1,024 draws EARLIER in the stream, plus whatever rejections lie between
+          s_mine = jr_apply(a.back_block, s_mine);
+          for (long long d = (raw_mine - JR_SLICE_THREADS) - raw; d > 0; --d) s_mine = jr_apply(a.back_one, s_mine);
+        }
+        raw_mine = raw;
+        kk = jr_next_int_of((unsigned int)(s_mine >> 17), (unsigned int)n_mine);
+        if ((bitmap[(unsigned int)kk >> 5] >> (kk & 31)) & 1u) {
+          const int h = atomicAdd(&ctl[0], 1);
+          if (h < JR_MAX_HITS) hits[h] = tid;
+        }
+      }
+      karr[tid] = kk;
+      __syncthreads();
+      const int n_hits = ctl[0];
+      if (n_hits > 0) {
+        if (n_hits > JR_MAX_HITS) {
+          if (tid == 0) atomicOr(a.err, 1);
+          return;   // (uniform)
+        }
+        if (wave == 0) {
+          // the hits in step order: repeatedly the smallest unprocessed lane index (a hit may create later ones)
+          int done_upto = -1;
+          for (;;) {
+            int best = 0x7fffffff;
+            const int nh = ctl[0] < JR_MAX_HITS ? ctl[0] : JR_MAX_HITS;
+            for (int i = lane; i < nh; i += 64) {
+              const int h = hits[i];
+              if (h > done_upto && h < best) best = h;
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) best = min(best, __shfl_xor(best, o, 64));
+            if (best == 0x7fffffff) break;
+            done_upto = best;
+            const int kq = karr[best];
+            // which entry wants position kq?  (none: a stale hit -- the entry moved on inside this block)
+            int found = -1;
+            for (int t = lane; t < take; t += 64)
+              if (wanted[t] == kq) found = t;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) found = max(found, __shfl_xor(found, o, 64));
+            if (found < 0) continue;
+            const int top = (int)(n0 + best - 1);   // step n0 + best swaps (n - 1, kq)
+            if (lane == 0) {
+              wanted[found] = top;
+              atomicAnd(&bitmap[(unsigned int)kq >> 5], ~(1u << (kq & 31)));
+              atomicOr(&bitmap[(unsigned int)top >> 5], 1u << (top & 31));
+            }
+            // later steps of THIS block that target the new position were tested against the old bitmap
+            for (int j = best + 1 + lane; j < JR_SLICE_THREADS; j += 64)
+              if (karr[j] == top) {
+                const int h = atomicAdd(&ctl[0], 1);
+                if (h < JR_MAX_HITS) hits[h] = j;
+              }
+            __builtin_amdgcn_wave_barrier();
+          }
+          if (lane == 0) ctl[0] = 0;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // ---- what the wanted positions held in the identity: the split's own row numbers ----
+  for (int t = tid; t < take; t += JR_SLICE_THREADS) a.idx_out[o0 + t] = (int)(a.split_begin[k] + wanted[t]);
+}

@@ -301,6 +301,30 @@ class Engine:
         total = int(sum(min(batch_size, int(e - b) - s_ * batch_size) for s_ in range(n_steps.value) for b, e in zip(sb, se)))
         return Plan(self, h, n_steps.value, len(sb), total), n_steps.value, int(st.value), draws.value
 
+    def plan_from_seed_job(self, jstate, job_lens, first, split_begins, max_samples, batch_size, rp64=False):
+        """The epoch of a JOB of len(job_lens) workers drawn by the device, the lists of the workers hosted here
+        (dsgd_plan_create_from_seed_job): job workers first .. first + len(split_begins) - 1, hosted worker i over the rows
+        split_begins[i] .. + job_lens[first + i] of this engine.  Any batch size, splits up to 2^20 rows; usable with a
+        communicator attached (every rank passes the same jstate, job_lens, max_samples, batch_size and number of hosted
+        workers).  Returns (plan or None, n_steps, new jstate, draws) -- the state and the draws are the JOB's, the same
+        on every rank; DsgdError with code EUNSUPPORTED where the device form does not apply.
+        rp64=True (fp64 engines): a row-parallel plan (dsgd_plan_create_from_seed_job_rp64)."""
+        jl = np.ascontiguousarray(job_lens, dtype=np.int64)
+        sb = np.ascontiguousarray(split_begins, dtype=np.int64)
+        if jl.ndim != 1 or sb.ndim != 1:
+            raise ValueError("job_lens and split_begins are flat lists")
+        st = C.c_uint64(int(jstate))
+        h = C.c_void_p()
+        n_steps, draws = C.c_int64(0), C.c_int64(0)
+        create = self._lib.dsgd_plan_create_from_seed_job_rp64 if rp64 else self._lib.dsgd_plan_create_from_seed_job
+        check(create(self._ctx, C.byref(st), ptr(jl), len(jl), int(first), len(sb), ptr(sb), int(max_samples), int(batch_size),
+                     C.byref(h), C.byref(n_steps), C.byref(draws)))
+        if not h.value:
+            return None, 0, int(st.value), 0
+        mine = jl[int(first):int(first) + len(sb)]
+        total = int(sum(min(batch_size, int(ln) - s_ * batch_size) for s_ in range(n_steps.value) for ln in mine))
+        return Plan(self, h, n_steps.value, len(sb), total), n_steps.value, int(st.value), draws.value
+
     def plan_lists(self, plan):
         """(idx, offsets) of a plan as the device holds them (tests)."""
         n_lists = plan.n_steps * plan.n_workers

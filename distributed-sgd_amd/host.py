@@ -575,6 +575,9 @@ class MasterSync(_DistributedEval):
         self._executor = None
         self._rp_plans = False       # DSGD_F64_RP_PLANS=1 and an fp64 plan was refused: row-parallel plans from here on
         self._rp_seed_ok = True      # ... their lists drawn by the device until it refuses
+        # DSGD_DEVICE_LISTS_JOB=1: where the device draw is refused, its job form is tried before the host's generator
+        # (_plan_from_seed), per form (rp64 or not): "" = off or refused, "on" = to be tried, "serving" = it drew the last epoch
+        self._job_form = dict.fromkeys((False, True), "on" if os.environ.get("DSGD_DEVICE_LISTS_JOB", "0") == "1" else "")
         self.batch_loop_s = 0.0      # wall time of the batch loops (shuffles, plan set-up, steps): Master.scala:179-199
         self.shuffle_s = 0.0         # ... of which drawing the lists (not overlapped by prefetch: see fit)
         self.steps_run = 0
@@ -681,7 +684,7 @@ class MasterSync(_DistributedEval):
             return None
         t0 = time.perf_counter()
         try:
-            plan, n_steps, state, _ = self.backend.plan_from_seed(seed_before, split, max_samples, batch_size, rp64=True)
+            plan, n_steps, state, _ = self._plan_from_seed(seed_before, split, max_samples, batch_size, rp64=True)
         except Exception as e:
             if getattr(e, "code", None) != -7:
                 raise
@@ -690,6 +693,35 @@ class MasterSync(_DistributedEval):
         self.shuffle_s += time.perf_counter() - t0
         return {"plan": plan, "n_steps": n_steps, "n_samples": plan.n_samples if plan is not None else 0, "seed_before": seed_before,
                 "state": state}
+
+    def _plan_from_seed(self, seed_before, split, max_samples, batch_size, rp64=False):
+        """backend.plan_from_seed -- and, with DSGD_DEVICE_LISTS_JOB=1, where that is refused (DSGD_EUNSUPPORTED: a batch
+        beyond 1,024 rows, more than 64 rejections inside a shuffle, a communicator attached) the job form before the
+        refusal reaches the caller (Engine.plan_from_seed_job: any batch size, 512 rejections, a local call under a
+        communicator).  The job is the split hosted here -- or, where the backend reports `job_window` = (the split lengths
+        of every worker of the job, the job index of the first worker hosted here), the window of that job, the hosted
+        workers' rows starting where `split` says.  The same stream from the same state: the lists, the step count and the
+        generator's state are the host's.  Once the job form has served an epoch the refused form is not asked again; a
+        refusal of the job form is remembered too, and the first refusal is what the caller sees."""
+        e1 = None
+        if self._job_form[rp64] != "serving":
+            try:
+                return self.backend.plan_from_seed(seed_before, split, max_samples, batch_size, rp64=rp64) if rp64 else \
+                    self.backend.plan_from_seed(seed_before, split, max_samples, batch_size)
+            except Exception as e:
+                if getattr(e, "code", None) != -7 or not self._job_form[rp64] or not hasattr(self.backend, "plan_from_seed_job"):
+                    raise
+                e1 = e
+        job_lens, first = getattr(self.backend, "job_window", None) or ([len(r) for r in split], 0)
+        try:
+            out = self.backend.plan_from_seed_job(seed_before, job_lens, first, [r.start for r in split], max_samples, batch_size, rp64=rp64)
+        except Exception as e2:
+            if getattr(e2, "code", None) != -7:
+                raise
+            self._job_form[rp64] = ""
+            raise (e1 or e2)
+        self._job_form[rp64] = "serving"
+        return out
 
     def _fp64_steps(self):
         return getattr(self.backend, "precision", "fp32") == "fp64" and hasattr(self.backend, "sync_step_f64")
@@ -727,7 +759,7 @@ class MasterSync(_DistributedEval):
             seed_before = self.rnd.seed
             t0 = time.perf_counter()
             try:
-                plan, n_steps, state, _ = self.backend.plan_from_seed(seed_before, split, max_samples, batch_size)
+                plan, n_steps, state, _ = self._plan_from_seed(seed_before, split, max_samples, batch_size)
             except Exception as e:   # (DSGD_EUNSUPPORTED: outside the device form -- the host draws from here on)
                 if getattr(e, "code", None) != -7:
                     raise

@@ -159,7 +159,9 @@ enum {
  *   - dsgd_plan_create / _n / _from_seed / _from_seed_rp64, dsgd_plan_run / _f64 on a column-slice plan,
  *     dsgd_plan_run_async_f64, dsgd_async_plan_create / _rp64, dsgd_sync_steps_f64 and dsgd_async_step_f64 return
  *     DSGD_EUNSUPPORTED and change nothing: the persistent column-slice kernel cannot hold a collective, and the device
- *     shuffle and the asynchronous iteration have no form that spans the ranks.  (host.MasterSync.fit falls back from a
+ *     shuffle of THESE entry points and the asynchronous iteration have no form that spans the ranks -- the device shuffle
+ *     that does is dsgd_plan_create_from_seed_job_rp64: a local call, accepted here, its plan run by the collective
+ *     dsgd_plan_run_f64.  (host.MasterSync.fit falls back from a
  *     refused plan to one dsgd_sync_step_f64 per step; with DSGD_F64_RP_PLANS=1 to a row-parallel plan on host-drawn
  *     lists, ONE dsgd_plan_run_f64 per epoch and rank.)
  *   DOUBLE FEATURE VALUES ACROSS RANKS: a communicator attached with dsgd_comm_init_f64v is dsgd_comm_init_f64's in every
@@ -246,7 +248,8 @@ enum {
  *   sum ending at n_idx; a row index outside the rows loaded, where data is loaded).  WITH A COMMUNICATOR ATTACHED
  *   ("ACROSS RANKS"): dsgd_plan_create_rp64_n is accepted and dsgd_plan_run_f64 / dsgd_plan_run on its plan is a collective
  *   call, one agreement and one host read per call; dsgd_plan_create_from_seed_rp64, dsgd_async_plan_create_rp64 and
- *   dsgd_plan_run_async_f64 return DSGD_EUNSUPPORTED, as does the run of a plan that keeps a record.  The existing
+ *   dsgd_plan_run_async_f64 return DSGD_EUNSUPPORTED, as does the run of a plan that keeps a record;
+ *   dsgd_plan_create_from_seed_job_rp64 (the lists of a job's share of workers, drawn by the device) is accepted.  The existing
  *   creators refuse exactly as before.
  * The entry points below that name fp64 return DSGD_ESTATE on an fp32 context (dsgd_precision excepted).            */
 
@@ -427,10 +430,39 @@ int dsgd_plan_create_n(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const i
  * mirrors do: csrc/jrand.c) and use dsgd_plan_create_n.  The practical ceiling is below the 2^20 rows: a shuffle of len rows
  * rejects len^2 / 2^33 raw values on average and the device form holds 64 per shuffle, so from roughly 600,000 rows per
  * split on almost every epoch is refused (one shuffle in its thousands exceeds 64) and at 2^20 rows (128 expected) all are.
+ * dsgd_plan_create_from_seed_job below lifts the three limits (any batch size, 512 rejections, a rank's window of a job).
  * tests/test_gpu_shuffle.py, tests/test_gpu_shuffle_large.py: equal to csrc/jrand.c entry for entry.                         */
 int dsgd_plan_create_from_seed(dsgd_ctx* ctx, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end,
                                int32_t n_splits, int64_t max_samples, int32_t batch_size, dsgd_plan** out,
                                int64_t* n_steps_out, int64_t* draws_out);
+/* The same epoch for A JOB'S SHARE OF WORKERS, at any batch size.  The reference's stream is ONE stream over all workers
+ * of the job (core/Master.scala:184): for every batch b = 0, B, 2B, ... < max_samples and for every job worker j in the
+ * master's order one Random.shuffle of job_len[j] entries is drawn and its slice [b, b + B) taken; the steps end at the
+ * first b at which ANY job worker's split is exhausted.  This context hosts job workers first .. first + n_local - 1: the
+ * plan holds their n_steps x n_local lists (step-major, worker-minor), hosted worker i mapping position p of its shuffle to
+ * row split_begin[i] + p of the rows loaded HERE (split_begin has n_local entries and need not follow the job's order).
+ * *jstate advances over ALL the job's draws and *draws_out is the job's total, whatever the window: every rank of a job
+ * leaves with the same generator state, the one csrc/jrand.c leaves after dsgd_jrand_epoch_lists over the n_job splits.
+ * With first = 0 and n_local = n_job the lists, step count, state and draws are those of dsgd_plan_create_from_seed / _rp64
+ * wherever that form accepts the arguments.
+ *   Limits: any batch_size >= 1 (a list is traced in chunks of 1,024 entries, each sweeping the steps above it: about
+ *   ceil(B / 1,024) x (len - b) draw evaluations per list); every job_len[j] in 1 .. 2^20; up to 512 rejected raw values
+ *   inside one shuffle (128 +- 11 expected at 2^20 rows).  Beyond them DSGD_EUNSUPPORTED: nothing drawn, *jstate
+ *   untouched, *out = NULL, *n_steps_out = 0.  DSGD_EINVAL: null pointers, n_job < 1, n_local < 1, first < 0,
+ *   first + n_local > n_job, a job_len < 1, a negative split_begin.  DSGD_ERANGE: a hosted split ends beyond the rows loaded.
+ *   The fp32 form refuses Double data, the _rp64 form needs an fp64 context (float or Double data), as their twins do.
+ *   UNDER A COMMUNICATOR both are local calls with no collective: the fp32 form is accepted under dsgd_comm_init, the
+ *   _rp64 form under dsgd_comm_init_f64 / _f64v, and its plan runs through the collective dsgd_plan_run_f64 as a
+ *   host-drawn row-parallel plan does.  EVERY RANK MUST PASS THE SAME *jstate, job_len, max_samples, batch_size AND n_local
+ *   (its own `first` and split_begin): nothing here compares them across ranks -- the collective run checks the number of
+ *   workers and the step count as it does for any plan.  (dsgd_plan_create_from_seed_rp64 stays refused there.)
+ * tests/test_gpu_seed_job.py, tests/test_gpu_seed_job_world2.py: equal to csrc/jrand.c entry for entry.                     */
+int dsgd_plan_create_from_seed_job(dsgd_ctx* ctx, uint64_t* jstate, const int64_t* job_len, int32_t n_job, int32_t first,
+                                   int32_t n_local, const int64_t* split_begin, int64_t max_samples, int32_t batch_size,
+                                   dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out);
+int dsgd_plan_create_from_seed_job_rp64(dsgd_ctx* ctx, uint64_t* jstate, const int64_t* job_len, int32_t n_job, int32_t first,
+                                        int32_t n_local, const int64_t* split_begin, int64_t max_samples, int32_t batch_size,
+                                        dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out);
 /* the lists of a plan as the device holds them: the first n entries and the first n_offsets prefix offsets (tests) */
 int dsgd_plan_read_lists(dsgd_ctx* ctx, dsgd_plan* plan, int32_t* idx_out, int64_t n, int64_t* offsets_out, int64_t n_offsets);
 int dsgd_plan_destroy(dsgd_ctx* ctx, dsgd_plan* plan);

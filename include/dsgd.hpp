@@ -241,6 +241,23 @@ class SparseSVM {
     if (nSteps) *nSteps = n;
     return plan;
   }
+  // planCreateFromSeedJob: the same epoch for a JOB's share of workers (dsgd_plan_create_from_seed_job / _rp64): jobLen = the
+  // split length of every worker of the job, this model hosts job workers first .. first + splitBegin.size() - 1 over the rows
+  // [splitBegin[i], splitBegin[i] + jobLen[first + i]) it has loaded.  Any batch size; usable with a communicator attached
+  // (every rank passes the same rnd state, jobLen, maxSamples, batchSize and number of hosted workers).  rnd is left where
+  // the JVM's generator would stand behind the JOB's epoch.  Returns the plan (null: no step) and *nSteps.
+  dsgd_plan* planCreateFromSeedJob(JavaRandom& rnd, const std::vector<int64_t>& jobLen, int first, const std::vector<int64_t>& splitBegin,
+                                   int64_t maxSamples, int batchSize, bool rp64, int64_t* nSteps) {
+    uint64_t st = rnd.state();
+    dsgd_plan* plan = nullptr;
+    int64_t n = 0;
+    check((rp64 ? dsgd_plan_create_from_seed_job_rp64 : dsgd_plan_create_from_seed_job)(
+        ctx_, &st, jobLen.data(), (int32_t)jobLen.size(), (int32_t)first, (int32_t)splitBegin.size(), splitBegin.data(), maxSamples,
+        batchSize, &plan, &n, nullptr));
+    rnd.setState(st);
+    if (nSteps) *nSteps = n;
+    return plan;
+  }
   // asyncPlanRp64: updates [firstUpdate, firstUpdate + nUpdates) of the zero-lag asynchronous schedule, one worker per step
   dsgd_plan* asyncPlanRp64(const std::vector<std::pair<int64_t, int64_t>>& assigned, int batch, uint64_t seed, bool positionalBug,
                            int64_t firstUpdate, int64_t nUpdates) {

@@ -458,6 +458,49 @@ JNIEXPORT jlong JNICALL NATIVE(planCreateFromSeedRp64)(JNIEnv* env, jobject, jlo
                                                        jlongArray splitEnd, jlong maxSamples, jint batchSize) {
   return plan_create_from_seed(env, h, state, splitBegin, splitEnd, maxSamples, batchSize, true);
 }
+// The same epoch for a JOB's share of workers (dsgd_plan_create_from_seed_job / _rp64; include/dsgd.h): jobLen = the split length
+// of EVERY worker of the job in the master's order, this context hosts job workers first .. first + splitBegin.length - 1 over
+// the rows [splitBegin[i], splitBegin[i] + jobLen[first + i]) it has loaded.  Any batch size; a local call that a communicator does
+// not refuse.  state as planCreateFromSeed takes and leaves it -- the JOB's state and draws, the same on every rank.
+JNIEXPORT jlong JNICALL NATIVE(planCreateFromSeedJob)(JNIEnv* env, jobject, jlong h, jlongArray state, jlongArray jobLen, jint first,
+                                                      jlongArray splitBegin, jlong maxSamples, jint batchSize, jboolean rp64) {
+  if (!state || !jobLen || !splitBegin) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "state, jobLen and splitBegin must not be null");
+    return 0;
+  }
+  const jsize nJob = env->GetArrayLength(jobLen), nLocal = env->GetArrayLength(splitBegin);
+  if (env->GetArrayLength(state) < 3 || nJob < 1 || nLocal < 1 || first < 0 || (int64_t)first + nLocal > (int64_t)nJob) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"),
+                  "state must hold 3 entries, jobLen one per worker of the job, splitBegin one per hosted worker first .. of them");
+    return 0;
+  }
+  dsgd_plan* plan = nullptr;
+  int rc;
+  {
+    LongElems sv(env, state, 0);
+    LongElems lv(env, jobLen, JNI_ABORT);
+    LongElems bv(env, splitBegin, JNI_ABORT);
+    uint64_t js = (uint64_t)sv.p[0];
+    int64_t n_steps = 0, draws = 0;
+    rc = (rp64 ? dsgd_plan_create_from_seed_job_rp64 : dsgd_plan_create_from_seed_job)(
+        ctx(h), &js, reinterpret_cast<const int64_t*>(lv.p), (int32_t)nJob, (int32_t)first, (int32_t)nLocal,
+        reinterpret_cast<const int64_t*>(bv.p), (int64_t)maxSamples, (int32_t)batchSize, &plan, &n_steps, &draws);
+    if (rc == DSGD_OK) {
+      sv.p[0] = (jlong)js;
+      sv.p[1] = (jlong)n_steps;
+      sv.p[2] = (jlong)draws;
+    }
+  }
+  if (rc == DSGD_EUNSUPPORTED) {
+    env->ThrowNew(env->FindClass("java/lang/UnsupportedOperationException"), dsgd_last_error());
+    return 0;
+  }
+  if (rc) {
+    raise(env, rc);
+    return 0;
+  }
+  return reinterpret_cast<jlong>(plan);
+}
 // Updates [firstUpdate, firstUpdate + nUpdates) of the fp64 mode's zero-lag asynchronous schedule as a one-worker row-parallel
 // plan whose lists the device draws (dsgd_async_plan_create_rp64): the lock-free engine's sampler for the workers' row ranges,
 // batch, seed and positionalBug as asyncStart takes them; Double or float feature values, any batch, any model width.

@@ -43,6 +43,9 @@ object NativeSVM {
   // creators above refuse there -- Double values, > 4 workers, > 1,024 rows per batch, a model beyond a slice's LDS
   @native def planCreateRp64(ctx: Long, idx: Array[Int], offsets: Array[Long], nWorkers: Int): Long
   @native def planCreateFromSeedRp64(ctx: Long, state: Array[Long], splitBegin: Array[Long], splitEnd: Array[Long], maxSamples: Long, batchSize: Int): Long
+  // the same epoch for a JOB's share of workers (dsgd_plan_create_from_seed_job / _rp64): the stream over all jobLen.length workers, the lists of
+  // the splitBegin.length hosted here (job workers first ..); any batch size, usable with a communicator attached; state as planCreateFromSeed
+  @native def planCreateFromSeedJob(ctx: Long, state: Array[Long], jobLen: Array[Long], first: Int, splitBegin: Array[Long], maxSamples: Long, batchSize: Int, rp64: Boolean): Long
   // updates [firstUpdate, firstUpdate + nUpdates) of the zero-lag asynchronous schedule, the lists drawn by the device
   @native def asyncPlanCreateRp64(ctx: Long, assignedBegin: Array[Long], assignedEnd: Array[Long], batch: Int, seed: Long,
                                   positionalBug: Boolean, firstUpdate: Long, nUpdates: Long): Long
