@@ -1,7 +1,7 @@
 // Host code of libdsgd_hip's fp64 mode (DSGD_F_FP64; include/dsgd.h "THE FP64 MODE"): everything that exists only for it, to be
 // read from top to bottom.  Host only, like dsgd_buf.hpp; included ONCE by dsgd_hip.hip, inside its translation unit, behind
 // the context, the plans' frame (plan_frame / plan_finish / plan_release) and the helpers fp32 shares (stage_lists,
-// finish_stats, the sp_* of the Sparse boundary, async_plan_impl and plan_from_seed_impl further down), and in front of the
+// finish_stats, the sp_* of the Sparse boundary, async_plan_impl and the from-seed plans of dsgd_seed_host.hpp further down), and in front of the
 // entry points that dispatch into it (dsgd_sync_step, dsgd_plan_run, dsgd_load_csr_f64, the *_f64 twins of fp32 calls).  The
 // kernels are in dsgd_cs64.hpp (column slices) and dsgd_rp64.hpp (the row-parallel family).
 //

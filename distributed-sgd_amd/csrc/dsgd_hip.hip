@@ -4007,327 +4007,8 @@ int dsgd_plan_create(dsgd_ctx* c, const int32_t* idx, const int64_t* offsets, in
   return plan_finish(c, p, out);
 }
 
-// slot `i` of the from-seed scratch with room for `bytes`
-static hipError_t seed_scratch(dsgd_ctx* c, int i, size_t bytes, void** out) {
-  DevBuf<void>& b = c->seed_scratch[i];
-  const hipError_t e = b.cap() < bytes ? b.try_alloc(bytes + bytes / 4 + 4096) : hipSuccess;
-  *out = b.get();
-  return e;
-}
-// ---- an epoch's lists drawn on the device, draw for draw the reference's stream (csrc/dsgd_shuffle.hpp) ---------------------
-// (rp64: dsgd_plan_create_from_seed_rp64 -- the same draws into a row-parallel plan: an fp64 context, float or Double data, no
-//  limit of the column slices; `what` names the entry point in the messages)
-//
-// ONE function behind both forms.  The stream is a pure function of the seed and the lengths of the JOB's n_splits splits:
-// the scan and the walk below run over all of them.  The plan holds the lists of the n_local workers this context hosts
-// (job workers first .. first + n_local - 1; split_begin has n_local entries), and only their start records and
-// rejections go to the device.
-//   job == false   dsgd_plan_create_from_seed / _rp64: the context hosts the whole job (first = 0, n_local = n_splits), a
-//                  worker's length is split_end - split_begin, batches up to JR_MAX_TAKE rows, up to JR_MAX_REJ rejections
-//                  inside a shuffle, dsgd_jr_slice_kernel; refused in an fp64 context with a communicator.
-//   job == true    dsgd_plan_create_from_seed_job / _rp64: the lengths are job_len (split_end is not read), any batch size,
-//                  up to JR_JOB_MAX_REJ rejections, dsgd_jr_slice_job_kernel; the row-parallel form is a LOCAL call that a
-//                  communicator does not refuse (the plan then runs through plan_run_rp64_ranks).
-static int plan_from_seed_impl(dsgd_ctx* c, const char* what, bool rp64, bool job, uint64_t* jstate, const int64_t* job_len, int32_t first,
-                               int32_t n_local, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits, int64_t max_samples,
-                               int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
-  DSGD_TRY(check_ctx(c));
-  if (!jstate || !split_begin || (job ? !job_len : !split_end) || !out || !n_steps_out || n_splits < 1 || batch_size < 1)
-    return fail(DSGD_EINVAL, "bad arguments");
-  if (job && (n_local < 1 || first < 0 || (long long)first + n_local > n_splits))
-    return fail(DSGD_EINVAL, "the hosted workers %d .. %lld are not workers of a job of %d", first, (long long)first + n_local - 1, n_splits);
-  const bool comm_ok = job && rp64;   // (a row-parallel plan spans the ranks at its run; creating it is local)
-  {   // (refused with *out as it was)
-    std::lock_guard<std::mutex> lk0(c->mu);
-    if (rp64) {
-      DSGD_TRY(require_fp64(c, what));
-      if (!comm_ok) DSGD_TRY(refuse_fp64_comm(c, what));
-    } else {
-      DSGD_TRY(refuse_val64(c, what));
-    }
-  }
-  *out = nullptr;
-  *n_steps_out = 0;
-  if (draws_out) *draws_out = 0;
-  auto len_of = [&](long long j) -> long long { return job ? (long long)job_len[j] : (long long)(split_end[j] - split_begin[j]); };
-  long long max_len = 0;
-  for (int k = 0; k < n_splits; ++k) {
-    const long long len = len_of(k);
-    if (len < 1 || (!job && split_begin[k] < 0)) return fail(DSGD_EINVAL, "worker %d has no rows", k);
-    max_len = std::max(max_len, len);
-  }
-  if (job) {
-    for (int i = 0; i < n_local; ++i)
-      if (split_begin[i] < 0) return fail(DSGD_EINVAL, "hosted worker %d starts at a negative row", i);
-    if (max_len > JR_MAX_LEN)
-      return fail(DSGD_EUNSUPPORTED, "device-drawn lists serve splits up to %d rows (draw them on the host)", JR_MAX_LEN);
-  } else if (batch_size > JR_MAX_TAKE || max_len > JR_MAX_LEN)
-    return fail(DSGD_EUNSUPPORTED, "device-drawn lists serve batches up to %d rows of splits up to %d rows (draw them on the host)", JR_MAX_TAKE, JR_MAX_LEN);
-  const int max_rej = job ? JR_JOB_MAX_REJ : JR_MAX_REJ;
-  const int chunks = job ? (int)(((long long)batch_size + JR_MAX_TAKE - 1) / JR_MAX_TAKE) : 1;   // workgroups per list
-  // steps the reference runs before an empty slice (core/Master.scala:184-188; the slave's Vec.sum throws on it)
-  long long n_steps = 0;
-  for (long long b = 0; b < max_samples; b += batch_size) {
-    bool ok = true;
-    for (int k = 0; k < n_splits; ++k) ok = ok && b < len_of(k);
-    if (!ok) break;
-    ++n_steps;
-  }
-  if (n_steps == 0) return DSGD_OK;
-  const long long n_shuf = n_steps * n_splits;          // shuffles of the job
-  const long long n_lists = n_steps * n_local;          // lists of the plan: the hosted workers'
-  if (job && n_lists * chunks > 0x7fffffffLL) return fail(DSGD_EUNSUPPORTED, "more lists than one launch draws (draw them on the host)");
-  std::vector<int64_t> offsets((size_t)n_lists + 1, 0);
-  std::vector<long long> start((size_t)n_shuf + 1, 0);   // nominal raw index of every shuffle's start (no rejections)
-  for (long long q = 0; q < n_shuf; ++q) {
-    const long long len = len_of(q % n_splits);
-    start[(size_t)q + 1] = start[(size_t)q] + (len >= 2 ? len - 1 : 0);
-  }
-  for (long long q = 0; q < n_lists; ++q) {
-    const long long len = len_of(first + q % n_local), b = (q / n_local) * (long long)batch_size;
-    offsets[(size_t)q + 1] = offsets[(size_t)q] + std::min<long long>(batch_size, len - b);
-  }
-  const long long nominal = start[(size_t)n_shuf];
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (!comm_ok) DSGD_TRY(refuse_fp64_comm(c, what));
-  if (!rp64) DSGD_TRY(refuse_val64(c, what));
-  DSGD_TRY(bind(c, true));
-  for (int i = 0; i < n_local; ++i)
-    if (split_begin[i] + len_of(first + i) > c->n_rows)
-      return fail(DSGD_ERANGE, "worker %d's rows [%lld, %lld) outside the %lld loaded", first + i, (long long)split_begin[i],
-                  (long long)(split_begin[i] + len_of(first + i)), c->n_rows);
-  DSGD_TRY(ensure_build_stream(c));
-  hipStream_t bs = c->build_stream;
-  const unsigned long long s0 = *jstate & JR_MASK;
-  const bool seed_prof = getenv("DSGD_SEED_PROF") != nullptr;   // (tuning: where an epoch's 14 ms go)
-  const auto tp0 = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (seed_prof) fprintf(stderr, "[dsgd_plan_create_from_seed] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count());
-  };
-  // ---- pass A on the device: the candidates for a rejection; the walk over them here ----
-  std::vector<JrShuf> shuf((size_t)n_shuf);
-  std::vector<int> rej_list;
-  long long rej_total = 0;
-  {
-    const unsigned int cand_min = (unsigned int)(0x80000000ULL - (unsigned long long)max_len);
-    const int per_lane = (int)std::max<long long>(1, std::min<long long>(1024, (1LL << 30) / max_len));
-    long long scan = nominal + 64 + nominal / 4096;
-    for (int attempt = 0;; ++attempt) {
-      const long long span = (long long)JR_SCAN_THREADS * per_lane;
-      const long long n_wg = (scan + span - 1) / span;
-      const long long cap = (long long)((double)scan * (double)max_len / 2147483648.0 * 2.0) + 65536;
-      long long* d_ci = nullptr;
-      unsigned int* d_cu = nullptr;
-      unsigned long long *d_base = nullptr, *d_tot = nullptr;
-      auto drop = [&]() {};   // (the buffers are the context's scratch: kept)
-      hipError_t e = n_wg > 0x7fffffffLL ? hipErrorInvalidValue : seed_scratch(c, 0, sizeof(long long) * (size_t)cap, (void**)&d_ci);
-      if (e == hipSuccess) e = seed_scratch(c, 1, sizeof(unsigned int) * (size_t)cap, (void**)&d_cu);
-      if (e == hipSuccess) e = seed_scratch(c, 2, sizeof(unsigned long long) * (size_t)n_wg, (void**)&d_base);
-      if (e == hipSuccess) e = seed_scratch(c, 3, sizeof(unsigned long long) * 2, (void**)&d_tot);
-      if (e == hipSuccess) e = hipMemsetAsync(d_tot, 0, sizeof(unsigned long long) * 2, bs);
-      std::vector<unsigned long long> base((size_t)n_wg);
-      unsigned long long tot[2] = {0, 0};
-      if (e == hipSuccess) {
-        JrScanArgs sa;
-        sa.s0 = s0;
-        sa.scan = scan;
-        sa.per_lane = per_lane;
-        sa.cand_min = cand_min;
-        sa.cap = cap;
-        sa.cand_i = d_ci;
-        sa.cand_u = d_cu;
-        sa.wg_base = d_base;
-        sa.total = d_tot;
-        hipLaunchKernelGGL(dsgd_jr_scan_kernel, dim3((unsigned)n_wg), dim3(JR_SCAN_THREADS), 0, bs, sa);
-        e = hipGetLastError();
-      }
-      if (e == hipSuccess) e = hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, bs);
-      if (e == hipSuccess) e = hipMemcpyAsync(base.data(), d_base, sizeof(unsigned long long) * (size_t)n_wg, hipMemcpyDeviceToHost, bs);
-      if (e == hipSuccess) e = hipStreamSynchronize(bs);
-      std::vector<long long> ci;
-      std::vector<unsigned int> cu;
-      if (e == hipSuccess && tot[1] == 0 && tot[0] > 0) {
-        ci.resize((size_t)tot[0]);
-        cu.resize((size_t)tot[0]);
-        e = hipMemcpyAsync(ci.data(), d_ci, sizeof(long long) * ci.size(), hipMemcpyDeviceToHost, bs);
-        if (e == hipSuccess) e = hipMemcpyAsync(cu.data(), d_cu, sizeof(unsigned int) * cu.size(), hipMemcpyDeviceToHost, bs);
-        if (e == hipSuccess) e = hipStreamSynchronize(bs);
-      }
-      lap("scan + candidates on the host");
-      drop();
-      lap("... scan buffers freed");
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DSGD_EHIP, "scanning the random stream: %s", hipGetErrorString(e));
-      }
-      if (tot[1] != 0) return fail(DSGD_EUNSUPPORTED, "more rejection candidates than the device scan holds (draw the lists on the host)");
-      // walk the candidates in raw order (workgroup by workgroup, each block in order): `rej` = rejections so far.  Raw index
-      // i serves draw d = i - rej of the epoch; draw d belongs to shuffle j (start[j] <= d < start[j + 1]), bound len_j - (d - start[j])
-      long long rej = 0, j = 0;
-      bool beyond = false;
-      rej_list.clear();
-      for (long long q = 0; q < n_shuf; ++q) shuf[(size_t)q] = JrShuf{start[(size_t)q], 0, 0};
-      long long next_begin = 0;   // shuffles < next_begin have their record closed
-      auto close_upto = [&](long long jj) {   // shuffles before jj start with the rejections counted so far ... hmm: see below
-        for (; next_begin < jj; ++next_begin) {
-          shuf[(size_t)next_begin].rej_end = (int)rej_list.size();
-          if (next_begin + 1 < n_shuf) {
-            shuf[(size_t)next_begin + 1].raw0 = start[(size_t)next_begin + 1] + rej;
-            shuf[(size_t)next_begin + 1].rej_begin = (int)rej_list.size();
-          }
-        }
-      };
-      for (long long w = 0; w < n_wg && !beyond; ++w) {
-        const unsigned long long bw = base[(size_t)w];
-        const unsigned long long at = bw >> 16, cnt = bw & 0xffffULL;
-        for (unsigned long long t = 0; t < cnt; ++t) {
-          const long long d = ci[(size_t)(at + t)] - rej;
-          if (d >= nominal) {
-            beyond = true;
-            break;
-          }
-          while (start[(size_t)j + 1] <= d) ++j;
-          close_upto(j);
-          const long long len = len_of(j % n_splits);
-          const unsigned int n = (unsigned int)(len - (d - start[(size_t)j]));
-          if ((n & (n - 1)) != 0 && cu[(size_t)(at + t)] >= (0x80000000u / n) * n) {
-            rej_list.push_back((int)(ci[(size_t)(at + t)] - shuf[(size_t)j].raw0));
-            ++rej;
-          }
-        }
-      }
-      close_upto(n_shuf);
-      if (nominal + rej > scan) {   // more rejections than the margin scanned: scan further and walk again
-        if (attempt >= 3) return fail(DSGD_EUNSUPPORTED, "the random stream keeps outrunning its scan (draw the lists on the host)");
-        scan = nominal + rej + 64 + rej / 8;
-        continue;
-      }
-      rej_total = rej;
-      lap("candidates walked");
-      break;
-    }
-  }
-  for (long long q = 0; q < n_shuf; ++q)
-    if (shuf[(size_t)q].rej_end - shuf[(size_t)q].rej_begin > max_rej)
-      return fail(DSGD_EUNSUPPORTED, "more than %d rejections inside one shuffle (draw the lists on the host)", max_rej);
-  if (job) {   // the hosted workers' records and rejections alone, step-major, hosted-worker-minor
-    std::vector<JrShuf> mine((size_t)n_lists);
-    std::vector<int> rej_mine;
-    long long hosted_max = 0;
-    for (int i = 0; i < n_local; ++i) hosted_max = std::max(hosted_max, len_of(first + i));
-    for (long long q = 0; q < n_lists; ++q) {
-      const JrShuf& s = shuf[(size_t)((q / n_local) * n_splits + first + q % n_local)];
-      mine[(size_t)q] = JrShuf{s.raw0, (int)rej_mine.size(), (int)rej_mine.size() + (s.rej_end - s.rej_begin)};
-      rej_mine.insert(rej_mine.end(), rej_list.begin() + s.rej_begin, rej_list.begin() + s.rej_end);
-    }
-    shuf.swap(mine);
-    rej_list.swap(rej_mine);
-    max_len = hosted_max;   // (the bitmap of the slice kernel: the longest split traced HERE)
-  }
-  // ---- the plan's frame, then pass B straight into its index buffer ----
-  dsgd_plan* p = nullptr;
-  DSGD_TRY(plan_frame(c, offsets.data(), n_steps, n_local, &p, rp64));
-  lap("plan frame");
-  p->idx_trusted = true;
-  p->drawn = true;
-  p->fits = false;   // (the one-workgroup kernel's test reads the lists on the host; these plans run on column slices)
-  JrShuf* d_shuf = nullptr;
-  int *d_rej = nullptr, *d_err = nullptr;
-  long long *d_sb = nullptr, *d_off = nullptr;
-  auto drop2 = [&]() {};   // (scratch of the context)
-  std::vector<long long> sb2(2 * (size_t)n_local);   // job: begin | length, else begin | end
-  for (int k = 0; k < n_local; ++k) {
-    sb2[(size_t)k] = split_begin[k];
-    sb2[(size_t)n_local + (size_t)k] = job ? (long long)job_len[first + k] : (long long)split_end[k];
-  }
-  int h_err = 0;
-  hipError_t e = seed_scratch(c, 4, sizeof(JrShuf) * (size_t)n_lists, (void**)&d_shuf);
-  if (e == hipSuccess) e = seed_scratch(c, 5, sizeof(int) * std::max<size_t>(1, rej_list.size()), (void**)&d_rej);
-  if (e == hipSuccess) e = seed_scratch(c, 6, sizeof(int), (void**)&d_err);
-  if (e == hipSuccess) e = seed_scratch(c, 7, sizeof(long long) * sb2.size(), (void**)&d_sb);
-  if (e == hipSuccess) e = seed_scratch(c, 8, sizeof(long long) * offsets.size(), (void**)&d_off);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_shuf, shuf.data(), sizeof(JrShuf) * (size_t)n_lists, hipMemcpyHostToDevice, bs);
-  if (e == hipSuccess && !rej_list.empty()) e = hipMemcpyAsync(d_rej, rej_list.data(), sizeof(int) * rej_list.size(), hipMemcpyHostToDevice, bs);
-  if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(int), bs);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_sb, sb2.data(), sizeof(long long) * sb2.size(), hipMemcpyHostToDevice, bs);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets.data(), sizeof(long long) * offsets.size(), hipMemcpyHostToDevice, bs);
-  static const JrAffine back_one = jr_inverse_step();
-  static const JrAffine back_block = jr_power(back_one, JR_SLICE_THREADS);
-  if (e == hipSuccess && job) {
-    JrSliceJobArgs a;
-    a.s0 = s0;
-    a.back_block = back_block;
-    a.back_one = back_one;
-    a.shuf = d_shuf;
-    a.rej = d_rej;
-    a.split_begin = d_sb;
-    a.len = d_sb + n_local;
-    a.offsets = d_off;
-    a.idx_out = p->d_idx;
-    a.n_local = n_local;
-    a.batch_size = batch_size;
-    a.chunks = chunks;
-    a.err = d_err;
-    hipLaunchKernelGGL(dsgd_jr_slice_job_kernel, dim3((unsigned)(n_lists * chunks)), dim3(JR_SLICE_THREADS), jr_slice_job_lds_bytes(max_len), bs, a);
-    e = hipGetLastError();
-  } else if (e == hipSuccess) {
-    JrSliceArgs a;
-    a.s0 = s0;
-    a.back_block = back_block;
-    a.back_one = back_one;
-    a.shuf = d_shuf;
-    a.rej = d_rej;
-    a.split_begin = d_sb;
-    a.split_end = d_sb + n_splits;
-    a.offsets = d_off;
-    a.idx_out = p->d_idx;
-    a.n_splits = n_splits;
-    a.batch_size = batch_size;
-    a.err = d_err;
-    hipLaunchKernelGGL(dsgd_jr_slice_kernel, dim3((unsigned)n_shuf), dim3(JR_SLICE_THREADS), jr_slice_lds_bytes(max_len), bs, a);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, bs);
-  if (e == hipSuccess) e = hipStreamSynchronize(bs);
-  lap("lists drawn (slice kernel)");
-  drop2();
-  lap("... slice buffers freed");
-  if (e != hipSuccess || h_err) {
-    (void)hipGetLastError();
-    plan_abandon(c, p);
-    if (h_err) return fail(DSGD_EUNSUPPORTED, "a shuffle left the limits of the device form (draw the lists on the host)");
-    return fail(DSGD_EHIP, "drawing the lists: %s", hipGetErrorString(e));
-  }
-  DSGD_TRY(plan_finish(c, p, out));
-  lap("plan laid out");
-  *n_steps_out = n_steps;
-  *jstate = jr_jump_dev(s0, (unsigned long long)(nominal + rej_total));
-  if (draws_out) *draws_out = nominal + rej_total;
-  return DSGD_OK;
-}
-int dsgd_plan_create_from_seed(dsgd_ctx* c, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
-                               int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
-  return plan_from_seed_impl(c, "dsgd_plan_create_from_seed", false, false, jstate, nullptr, 0, n_splits, split_begin, split_end, n_splits,
-                             max_samples, batch_size, out, n_steps_out, draws_out);
-}
-int dsgd_plan_create_from_seed_rp64(dsgd_ctx* c, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
-                                    int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
-  return plan_from_seed_impl(c, "dsgd_plan_create_from_seed_rp64", true, false, jstate, nullptr, 0, n_splits, split_begin, split_end, n_splits,
-                             max_samples, batch_size, out, n_steps_out, draws_out);
-}
-// ... for a job's share of workers (include/dsgd.h): the stream over all n_job workers, the lists of the n_local hosted here
-int dsgd_plan_create_from_seed_job(dsgd_ctx* c, uint64_t* jstate, const int64_t* job_len, int32_t n_job, int32_t first, int32_t n_local,
-                                   const int64_t* split_begin, int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out,
-                                   int64_t* draws_out) {
-  return plan_from_seed_impl(c, "dsgd_plan_create_from_seed_job", false, true, jstate, job_len, first, n_local, split_begin, nullptr, n_job,
-                             max_samples, batch_size, out, n_steps_out, draws_out);
-}
-int dsgd_plan_create_from_seed_job_rp64(dsgd_ctx* c, uint64_t* jstate, const int64_t* job_len, int32_t n_job, int32_t first, int32_t n_local,
-                                        const int64_t* split_begin, int64_t max_samples, int32_t batch_size, dsgd_plan** out,
-                                        int64_t* n_steps_out, int64_t* draws_out) {
-  return plan_from_seed_impl(c, "dsgd_plan_create_from_seed_job_rp64", true, true, jstate, job_len, first, n_local, split_begin, nullptr, n_job,
-                             max_samples, batch_size, out, n_steps_out, draws_out);
-}
+// ---- an epoch's lists drawn on the device (seed_scratch, the scan, the walk's call, the draw; the four entry points) ----
+#include "dsgd_seed_host.hpp"
 
 // the lists of a plan as the device holds them (tests: the device-drawn lists against csrc/jrand.c's)
 int dsgd_plan_read_lists(dsgd_ctx* c, dsgd_plan* p, int32_t* idx_out, int64_t n, int64_t* offsets_out, int64_t n_offsets) {

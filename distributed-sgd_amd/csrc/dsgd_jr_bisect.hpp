@@ -1,9 +1,9 @@
-// Which raw value of a shuffle serves its draw m (csrc/dsgd_shuffle.hpp, dsgd_jr_slice_job_kernel's phase 1).
+// Which raw value of a shuffle serves its draw m (csrc/dsgd_shuffle.hpp, phase 1 of the two slice kernels).
 //
 // `rej` holds the raw values rejected inside the shuffle as offsets from its first raw value, ascending.  Rejection i
 // happened while draw T_i = rej[i] - i was being served, and T is non-decreasing (rej is strictly ascending), so draw m is
 // served by raw offset m + #{i : T_i <= m}: an upper bound over T by bisection, 10 probes for the 512 rejections the job
-// form keeps where the linear walk of jr_raw_of_draw takes one probe per rejection in front of the draw.
+// form keeps where the linear walk below takes one probe per rejection in front of the draw.
 //
 // No device type and no library call, so that the kernel and a host test compile the same lines
 // (tests/test_seed_job_abi.py compares it with the linear walk on hand-made lists).
@@ -24,7 +24,7 @@ DSGD_JRB_HD inline long long dsgd_jr_raw_of_draw_bisect(long long m, const int* 
   }
   return m + (long long)lo;
 }
-// the linear walk the bisection replaces (dsgd_jr_slice_kernel's jr_raw_of_draw, for the host test)
+// the linear walk the bisection replaces: what dsgd_jr_slice_kernel calls (at most JR_MAX_REJ = 64 rejections)
 DSGD_JRB_HD inline long long dsgd_jr_raw_of_draw_linear(long long m, const int* rej, int n_rej) {
   long long x = m;
   for (int i = 0; i < n_rej; ++i) {

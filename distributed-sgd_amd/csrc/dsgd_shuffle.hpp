@@ -35,6 +35,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include "dsgd_jr_bisect.hpp"   // (host and device: which raw value of a shuffle serves its draw m)
+#include "dsgd_jr_walk.hpp"     // (host only: JrShuf, and the walk over the candidates that fills it)
+
 constexpr unsigned long long JR_MULT = 0x5DEECE66DULL;
 constexpr unsigned long long JR_ADD = 0xBULL;
 constexpr unsigned long long JR_MASK = (1ULL << 48) - 1;
@@ -150,10 +153,6 @@ constexpr int JR_MAX_TAKE = 1024;            // list entries per (batch, worker)
 constexpr int JR_MAX_LEN = 1 << 20;          // rows of a split: the bitmap of wanted positions is len / 8 bytes of LDS
 constexpr int JR_MAX_REJ = 64;               // rejected raw values inside ONE shuffle (expected len^2 / 2^32: 10 at 214 K rows)
 constexpr int JR_MAX_HITS = 2048;
-struct JrShuf {            // per (batch, worker), from the host's walk over the candidates
-  long long raw0;          // raw index of the shuffle's first raw value
-  int rej_begin, rej_end;  // its rejected raw values (offsets from raw0, ascending) in JrSliceArgs::rej
-};
 struct JrSliceArgs {
   unsigned long long s0;               // state in front of raw value 0
   JrAffine back_block;                 // JR_SLICE_THREADS inverse steps at once
@@ -173,14 +172,9 @@ __device__ __forceinline__ int jr_next_int_of(unsigned int u, unsigned int bound
   if ((bound & (bound - 1u)) == 0u) return (int)(((unsigned long long)bound * (unsigned long long)u) >> 31);
   return (int)(u % bound);
 }
-// raw offset (from the shuffle's first raw value) of the raw value that serves draw m: the (m + 1)-th accepted one
-__device__ __forceinline__ long long jr_raw_of_draw(long long m, const int* rej, int n_rej) {
-  long long x = m;
-  for (int i = 0; i < n_rej; ++i) {
-    if ((long long)rej[i] <= x) ++x;
-    else break;
-  }
-  return x;
+// LDS of a slice kernel that keeps up to rej_cap rejections: bitmap of the wanted positions | wanted | karr | hits | rej | ctl
+__host__ __device__ constexpr size_t jr_trace_lds_bytes(long long len, int rej_cap) {
+  return sizeof(unsigned int) * (size_t)(((len + 31) >> 5) + JR_MAX_TAKE + JR_SLICE_THREADS + JR_MAX_HITS + rej_cap + 4);
 }
 
 __global__ void __launch_bounds__(JR_SLICE_THREADS) dsgd_jr_slice_kernel(JrSliceArgs a) {
@@ -215,7 +209,7 @@ __global__ void __launch_bounds__(JR_SLICE_THREADS) dsgd_jr_slice_kernel(JrSlice
   const unsigned long long s_first = jr_jump_dev(a.s0, (unsigned long long)sh.raw0);   // state in front of the shuffle's first raw value
   // the draw of step n (n = len .. 2) is draw m = len - n of the shuffle
   auto draw_of_step = [&](long long n) -> int {
-    const long long raw = jr_raw_of_draw(len - n, rej, n_rej);
+    const long long raw = dsgd_jr_raw_of_draw_linear(len - n, rej, n_rej);   // (the (m + 1)-th accepted raw value serves draw m)
     const unsigned long long s = jr_jump_dev(s_first, (unsigned long long)(raw + 1));
     return jr_next_int_of((unsigned int)(s >> 17), (unsigned int)n);
   };
@@ -345,9 +339,7 @@ __global__ void __launch_bounds__(JR_SLICE_THREADS) dsgd_jr_slice_kernel(JrSlice
   // ---- what the wanted positions held in the identity: the split's own row numbers ----
   for (int t = tid; t < take; t += JR_SLICE_THREADS) a.idx_out[o0 + t] = (int)(a.split_begin[k] + wanted[t]);
 }
-__host__ __device__ constexpr size_t jr_slice_lds_bytes(long long len) {
-  return sizeof(unsigned int) * (size_t)(((len + 31) >> 5) + JR_MAX_TAKE + JR_SLICE_THREADS + JR_MAX_HITS + JR_MAX_REJ + 4);
-}
+__host__ __device__ constexpr size_t jr_slice_lds_bytes(long long len) { return jr_trace_lds_bytes(len, JR_MAX_REJ); }
 
 // ---- pass B for a JOB's share of workers: any batch size, up to 512 rejections a shuffle --------------------------------
 // dsgd_plan_create_from_seed_job (include/dsgd.h): the epoch's stream runs over ALL workers of a job, a context traces the
@@ -364,8 +356,11 @@ __host__ __device__ constexpr size_t jr_slice_lds_bytes(long long len) {
 //               value of a draw by bisection (csrc/dsgd_jr_bisect.hpp), phase 2 keeps the falling uniform pointer.
 //   indexing    split_begin / len by hosted worker, shuf / offsets by (step, hosted worker): the stream's position of every
 //               shuffle comes from the host's walk over the whole job (JrShuf::raw0), nothing here knows the other workers.
-#include "dsgd_jr_bisect.hpp"
-
+//
+// KEEP IN STEP with dsgd_jr_slice_kernel: from the LDS carve-up to the write-out the two bodies are the same text but for the
+// table's capacity, its load and phase 1's raw value.  They stay two copies on purpose -- moved into one function template
+// the body is optimised on its own before it is inlined, and both kernels' code changes inside phase 2's loop
+// (profiles/jr_trace.json holds the attempt); a fix to one body goes into the other.
 constexpr int JR_JOB_MAX_REJ = 512;
 struct JrSliceJobArgs {
   unsigned long long s0;               // state in front of raw value 0
@@ -380,9 +375,7 @@ struct JrSliceJobArgs {
   int n_local, batch_size, chunks;     // chunks = ceil(batch_size / JR_MAX_TAKE): workgroups per list
   int* err;                            // != 0: a shuffle exceeded a limit (the caller refuses)
 };
-__host__ __device__ constexpr size_t jr_slice_job_lds_bytes(long long len) {
-  return sizeof(unsigned int) * (size_t)(((len + 31) >> 5) + JR_MAX_TAKE + JR_SLICE_THREADS + JR_MAX_HITS + JR_JOB_MAX_REJ + 4);
-}
+__host__ __device__ constexpr size_t jr_slice_job_lds_bytes(long long len) { return jr_trace_lds_bytes(len, JR_JOB_MAX_REJ); }
 
 __global__ void __launch_bounds__(JR_SLICE_THREADS) dsgd_jr_slice_job_kernel(JrSliceJobArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned int jr_lds[];

@@ -8,7 +8,8 @@ after dsgd_load_csr replaced the data under a live plan.
   first and the last place it can stand;
 * the library asks through that header and nowhere else: the constants it restates are tied to the kernel's by a static_assert,
   and every entry point that hands a plan's lists to a kernel re-validates first;
-* every kernel of the fp64 row-parallel family has ONE launch site in the host sources."""
+* every kernel of the fp64 row-parallel family, and each of the three that draw an epoch's lists, has ONE launch site in the
+  host sources."""
 
 import os
 import re
@@ -25,8 +26,9 @@ def _read(name):
 
 
 def _host_sources():
-    """The library's host code: dsgd_hip.hip and the fp64 mode's dsgd_fp64_host.hpp, which it includes."""
-    return _read("dsgd_hip.hip") + "\n" + _read("dsgd_fp64_host.hpp")
+    """The library's host code: dsgd_hip.hip, the fp64 mode's dsgd_fp64_host.hpp and the device-drawn lists' dsgd_seed_host.hpp,
+    which it includes."""
+    return _read("dsgd_hip.hip") + "\n" + _read("dsgd_fp64_host.hpp") + "\n" + _read("dsgd_seed_host.hpp")
 
 
 def test_plan_check_under_sanitizers(tmp_path):
@@ -70,3 +72,12 @@ def test_every_kernel_of_the_fp64_row_parallel_family_has_one_launch_site():
     launched = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*(\w+)", _host_sources())
     for name in sorted(names):
         assert launched.count(name) == 1, (name, launched.count(name))
+
+
+def test_every_kernel_of_the_device_drawn_lists_has_one_launch_site():
+    names = set(re.findall(r"__global__[^;{]*?\b(dsgd_jr_\w*)\s*\(", _read("dsgd_shuffle.hpp")))
+    assert names == {"dsgd_jr_scan_kernel", "dsgd_jr_slice_kernel", "dsgd_jr_slice_job_kernel"}
+    launched = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*(\w+)", _host_sources())
+    for name in sorted(names):
+        assert launched.count(name) == 1, (name, launched.count(name))
+    assert _read("dsgd_hip.hip").count('#include "dsgd_seed_host.hpp"') == 1
