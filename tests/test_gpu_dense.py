@@ -2,7 +2,10 @@
 (oracle/dense_ref.py).  No reference counterpart: parity unpinned by construction (see the oracle's header).
 
 Stated tolerance: weights after T steps within 2e-6 * max(1, |w|_inf) of the oracle fed the same fp32 data (fp32
-products and sums of <= 8192 terms per row and <= 4096 rows per column partial); loss within 1e-6 relative."""
+products and sums of <= 8192 terms per row and <= 4096 rows per column partial); loss within 1e-6 relative.
+These flat tolerances hold for THIS file's small-logit data only (x ~ N(0,1)/sqrt(D), weights grown from zero: |z| << 1,
+at most one block per workgroup); larger logits, several blocks per workgroup, range edges and the entry points are in
+tests/test_gpu_dense_edges.py under the derived bounds of tests/dense_bound.py."""
 
 import numpy as np
 import pytest
