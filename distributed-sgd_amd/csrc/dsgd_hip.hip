@@ -120,6 +120,7 @@ static bool available() {
   } while (0)
 
 #include "dsgd_buf.hpp"      // (host only: the owners of device and pinned memory)
+#include "dsgd_plan_cache.hpp"   // (host only: the device blocks plans take and hand back, and a plan's hold on one)
 #include "dsgd_plan_check.hpp"   // (host only: a plan's lists against the rows loaded now)
 #include "dsgd_kernels.hpp"
 #include "dsgd_batch.hpp"
@@ -137,9 +138,10 @@ static bool available() {
 // host side
 // ------------------------------------------------------------------------------------------------
 struct dsgd_plan {
-  int* d_idx = nullptr;
+  // (the blocks from the context's cache -- d_idx, d_segs, d_cs_*, the record -- go back to it with the plan, in this order)
+  CacheBuf<int> d_idx;
   std::vector<long long> offsets;  // n_steps * n_workers + 1
-  WorkSeg* d_segs = nullptr;       // n_steps * n_workers
+  CacheBuf<WorkSeg> d_segs;        // n_steps * n_workers
   long long n_steps = 0;
   int n_workers = 0;
   long long max_items = 0;  // largest single list
@@ -161,31 +163,37 @@ struct dsgd_plan {
   long long vt_layout = -1;     // the layout generation the tiles were built for (-1: not built)
   bool vt_ok = false;           // every row of every list sits in the tiled streams
   // column slices (dsgd_cs_step_kernel): the lists laid out per (slice, step), built at the first run that can use them
-  CsHdr* d_cs_hdr = nullptr;
-  unsigned int* d_cs_meta = nullptr;
-  unsigned short* d_cs_rf = nullptr;
-  uint4* d_cs_col = nullptr;
-  float4* d_cs_val = nullptr;
-  unsigned short* d_cs_cl = nullptr;
+  CacheBuf<CsHdr> d_cs_hdr;     // the six layout arrays: from the cache (device-built) or the plan's own (host-built)
+  CacheBuf<unsigned int> d_cs_meta;
+  CacheBuf<unsigned short> d_cs_rf;
+  CacheBuf<uint4> d_cs_col;
+  CacheBuf<float4> d_cs_val;
+  CacheBuf<unsigned short> d_cs_cl;
   int cs_G = 0, cs_spl = 0, cs_nt = 0, cs_slot_stride = 0, cs_row_stride = 0, cs_cl_stride = 0;
   std::vector<int> cs_shift;    // per step
   long long cs_layout = -1;     // the layout generation (column ranking) the slices were built for
   bool cs_ok = false;
   bool cs_device_built = false; // laid out by dsgd_cs_layout_kernel (false: by the host, DSGD_CS_HOST_LAYOUT=1)
-  size_t cs_bytes[6] = {0, 0, 0, 0, 0, 0};   // sizes of the six layout arrays (hdr, meta, rf, col, val, cl) as taken from the cache
-  size_t idx_bytes = 0, segs_bytes = 0;
   // what the plan's set-up enqueued on the context's BUILD stream (lists uploaded, cells laid out) ends with this event;
   // the first run makes the launch stream wait for it
-  hipEvent_t built_ev = nullptr;
+  Event built_ev;
   bool built_pending = false;
   // dsgd_plan_record: gate decisions and regulariser scalars of the steps run (column-slice plans)
-  unsigned int* d_gate_rec = nullptr;
-  float* d_s_rec = nullptr;
+  CacheBuf<unsigned int> d_gate_rec;
+  CacheBuf<float> d_s_rec;
   int gate_words = 0;
-  size_t gate_bytes = 0, s_bytes = 0;
   // a row-parallel fp64 plan (dsgd_plan_create_rp64_n and its kin): the lists and their ranges only, no layout -- its steps are
   // the two launches of dsgd_sync_step_f64 over d_idx / d_segs, on whichever value type is loaded at the run (plan_run_rp64)
   bool rp64 = false;
+  void cs_free() {
+    d_cs_hdr.reset(), d_cs_meta.reset(), d_cs_rf.reset(), d_cs_col.reset(), d_cs_val.reset(), d_cs_cl.reset();
+    cs_ok = false;
+  }
+  ~dsgd_plan() {   // (members go in reverse order: the hand-backs are spelled out to keep theirs)
+    d_idx.reset(), d_segs.reset();
+    cs_free();
+    d_gate_rec.reset(), d_s_rec.reset();
+  }
 };
 
 struct FusedArgs {
@@ -248,21 +256,8 @@ struct dsgd_ctx {
   DevBuf<unsigned int> d_cs_max;     // the layout kernels' maxima and flags (4 words) ...
   HostBuf<unsigned int> h_cs_max;     // ... and where pass 1's come back to (pinned)
   hipStream_t build_stream = nullptr;   // a plan's set-up (uploads, layout kernels) runs here, beside the launch stream
-  // device blocks that plans hand back (dsgd_plan_destroy) and take again (dsgd_plan_create): an epoch of the reference is
-  // one plan (core/Master.scala:179-199), so plans come and go with every epoch -- hipMalloc / hipFree per plan (the
-  // latter synchronises the device) would sit in the fit loop
-  struct CacheBlock {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipEvent_t ev = nullptr;            // recorded on the launch stream when the block came back: its last reader
-    unsigned long long tick = 0;        // cache_tick when it came back: a block no plan took for CACHE_MAX_AGE hand-backs is freed
-  };
-  std::vector<CacheBlock> cache;
+  PlanCache plan_cache;                 // device blocks that plans hand back (dsgd_plan_destroy) and take again (dsgd_plan_create)
   std::vector<dsgd_plan*> plans;        // the plans alive: what dsgd_plan_destroy did not see, dsgd_destroy gives back and deletes
-  size_t cache_bytes = 0;
-  unsigned long long cache_tick = 0;
-  size_t cache_cap = (size_t)8 << 30;   // DSGD_CACHE_MB (dsgd_cache_trim gives blocks back on request)
-  std::vector<hipEvent_t> ev_pool;      // events of blocks in use, for the next ones
   // scratch of dsgd_plan_create_from_seed, kept across epochs (grow-only): a hipFree per epoch would wait for the whole
   // device -- i.e. for the epoch that is running on the launch stream while the next one's lists are drawn
   DevBuf<void> seed_scratch[9];   // (bytes)
@@ -489,7 +484,7 @@ struct dsgd_ctx {
   // profiling of the gradient kernel
   bool prof = false;
   bool prof_main_only = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
+  std::vector<std::pair<Event, Event>> prof_ev;
   size_t prof_used = 0;
   std::vector<int> prof_kind;
   double prof_kms[3] = {0.0, 0.0, 0.0};
@@ -748,10 +743,10 @@ static int prof_begin(dsgd_ctx* c, size_t* slot, int kind = 0) {
     return DSGD_OK;
   }
   if (c->prof_used == c->prof_ev.size()) {
-    hipEvent_t a, b;
-    HIP_TRY(hipEventCreate(&a));
-    HIP_TRY(hipEventCreate(&b));
-    c->prof_ev.emplace_back(a, b);
+    Event a, b;
+    HIP_TRY(hipEventCreate(&a.e));
+    HIP_TRY(hipEventCreate(&b.e));
+    c->prof_ev.emplace_back(std::move(a), std::move(b));
     c->prof_kind.push_back(0);
   }
   *slot = c->prof_used++;
@@ -1058,118 +1053,12 @@ static int launch_grad_vt(dsgd_ctx* c, dsgd_plan* p, long long step) {
       return 1;                       \
     }                                 \
   } while (0)
-// ---- device blocks of plans, cached across plans (see dsgd_ctx::CacheBlock) -------------------------------------
-// take: the smallest cached block of at least `bytes` and at most twice that; the BUILD stream waits for the block's last
-// reader on the launch stream (an event recorded when it came back).  Otherwise hipMalloc.
-static int cache_take(dsgd_ctx* c, void** out, size_t bytes, size_t* got) {
-  bytes = (std::max<size_t>(bytes, 1) + 4095) & ~(size_t)4095;
-  int best = -1;
-  for (int i = 0; i < (int)c->cache.size(); ++i)
-    if (c->cache[i].bytes >= bytes && c->cache[i].bytes <= 2 * bytes + (1u << 16) && (best < 0 || c->cache[i].bytes < c->cache[best].bytes)) best = i;
-  if (best >= 0) {
-    dsgd_ctx::CacheBlock blk = c->cache[(size_t)best];
-    c->cache.erase(c->cache.begin() + best);
-    c->cache_bytes -= blk.bytes;
-    if (blk.ev) {
-      if (c->build_stream) HIP_TRY(hipStreamWaitEvent(c->build_stream, blk.ev, 0));
-      c->ev_pool.push_back(blk.ev);
-    }
-    *out = blk.p;
-    *got = blk.bytes;
-    return DSGD_OK;
-  }
-  void* q = nullptr;
-  hipError_t e = dev_alloc(&q, bytes);
-  if (e != hipSuccess && !c->cache.empty()) {   // (memory is tight: give the cached blocks back and try once more)
-    (void)hipGetLastError();
-    for (auto& b : c->cache) {
-      dev_free(b.p);
-      if (b.ev) c->ev_pool.push_back(b.ev);
-    }
-    c->cache.clear();
-    c->cache_bytes = 0;
-    e = dev_alloc(&q, bytes);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return 1;   // soft: the caller falls back
-  }
-  *out = q;
-  *got = bytes;
-  return DSGD_OK;
-}
-// blocks beyond `keep_bytes` (oldest first) or older than CACHE_MAX_AGE hand-backs go back to the device: a block whose
-// last reader has finished is freed at once, one still being read stays (hipFree would wait for the device)
-constexpr unsigned long long CACHE_MAX_AGE = 48;   // (an epoch's plan hands back ~10 blocks: blocks unused for ~5 plans)
-static void cache_trim(dsgd_ctx* c, size_t keep_bytes, bool aged_only) {
-  for (size_t i = 0; i < c->cache.size();) {
-    dsgd_ctx::CacheBlock& b = c->cache[i];
-    const bool aged = c->cache_tick - b.tick > CACHE_MAX_AGE;
-    const bool over = !aged_only && c->cache_bytes > keep_bytes;
-    if ((aged || over) && (!b.ev || hipEventQuery(b.ev) == hipSuccess)) {
-      dev_free(b.p);
-      if (b.ev) c->ev_pool.push_back(b.ev);
-      c->cache_bytes -= b.bytes;
-      c->cache.erase(c->cache.begin() + (long)i);
-    } else {
-      (void)hipGetLastError();   // (hipErrorNotReady of the query)
-      ++i;
-    }
-  }
-}
-// give back: the block's last reader is whatever the launch stream holds now
-static void cache_give(dsgd_ctx* c, void* q, size_t bytes) {
-  if (!q) return;
-  ++c->cache_tick;
-  if ((c->cache_tick & 15) == 0) cache_trim(c, c->cache_cap, true);
-  if (bytes == 0 || c->cache_bytes + bytes > c->cache_cap || c->cache.size() >= 256) {
-    dev_free(q);   // (not ours to keep: allocated outside the cache, or the cache is full)
-    return;
-  }
-  dsgd_ctx::CacheBlock blk;
-  blk.p = q;
-  blk.bytes = bytes;
-  if (!c->ev_pool.empty()) {
-    blk.ev = c->ev_pool.back();
-    c->ev_pool.pop_back();
-  } else if (hipEventCreateWithFlags(&blk.ev, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    dev_free(q);
-    return;
-  }
-  if (hipEventRecord(blk.ev, c->stream) != hipSuccess) {
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(c->stream);
-  }
-  blk.tick = c->cache_tick;
-  c->cache.push_back(blk);
-  c->cache_bytes += bytes;
-}
-static void plan_release(dsgd_ctx* c, dsgd_plan* p);   // (below, with the plans)
-static void cache_drop_all(dsgd_ctx* c) {   // (dsgd_destroy: the streams are idle)
-  for (auto& b : c->cache) {
-    dev_free(b.p);
-    if (b.ev) (void)hipEventDestroy(b.ev);
-  }
-  for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-  c->cache.clear();
-  c->ev_pool.clear();
-  c->cache_bytes = 0;
-}
-
-static void cs_free(dsgd_ctx* c, dsgd_plan* p) {
-  void* q[6] = {p->d_cs_hdr, p->d_cs_meta, p->d_cs_rf, p->d_cs_col, p->d_cs_val, p->d_cs_cl};
-  for (int i = 0; i < 6; ++i) {
-    cache_give(c, q[i], p->cs_bytes[i]);   // (size 0: a block the host builder allocated itself -- freed)
-    p->cs_bytes[i] = 0;
-  }
-  p->d_cs_cl = nullptr;
-  p->d_cs_hdr = nullptr;
-  p->d_cs_meta = nullptr;
-  p->d_cs_rf = nullptr;
-  p->d_cs_col = nullptr;
-  p->d_cs_val = nullptr;
-  p->cs_ok = false;
+// the end of every plan: its cache blocks go back to the context behind whatever the launch stream still holds (an event per
+// block), its virtual tiles with the object (the caller has idled the launch stream if it holds any).  (built_ev may still be
+// pending on the build stream: destroying a recorded event is allowed, its resources go when it completes)
+static void plan_release(dsgd_ctx* c, dsgd_plan* p) {
+  c->plans.erase(std::remove(c->plans.begin(), c->plans.end(), p), c->plans.end());
+  delete p;
 }
 // the host copy of a plan's lists: plans drawn on the device (dsgd_plan_create_from_seed) have none until a HOST builder
 // (virtual tiles, DSGD_CS_HOST_LAYOUT=1) needs it
@@ -1231,7 +1120,7 @@ static int cs_build_device_impl(dsgd_ctx* c, dsgd_plan* p) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->layout_seen_by_build = true;
   }
-  cs_free(c, p);
+  p->cs_free();
   p->cs_layout = c->layout_gen;
   p->cs_device_built = true;
   const int K = p->n_workers;
@@ -1285,33 +1174,20 @@ static int cs_build_device_impl(dsgd_ctx* c, dsgd_plan* p) {
   const long long cells = (long long)G * n_steps;
   const long long bytes = cells * ((long long)slot_stride * (4 + CS_L * 2 + CS_L * 4) + (long long)row_stride * 2 + (long long)cl_stride * 2 + 8);
   if (bytes > c->cs_max_mb * (1LL << 20)) return DSGD_OK;
-  const size_t want[6] = {sizeof(CsHdr) * (size_t)cells,
-                          sizeof(unsigned int) * (size_t)(cells * slot_stride),
-                          sizeof(unsigned short) * (size_t)(cells * row_stride),
-                          sizeof(unsigned short) * (size_t)(cells * slot_stride * CS_L),
-                          sizeof(float) * (size_t)(cells * slot_stride * CS_L),
-                          sizeof(unsigned short) * (size_t)(cells * cl_stride)};
-  void* got[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < 6; ++i) {
-    if (int rc = cache_take(c, &got[i], want[i], &p->cs_bytes[i])) {
-      for (int j = 0; j < i; ++j) {
-        cache_give(c, got[j], p->cs_bytes[j]);
-        p->cs_bytes[j] = 0;
-      }
-      return rc;
-    }
-  }
-  p->d_cs_hdr = static_cast<CsHdr*>(got[0]);
-  p->d_cs_meta = static_cast<unsigned int*>(got[1]);
-  p->d_cs_rf = static_cast<unsigned short*>(got[2]);
-  p->d_cs_col = static_cast<uint4*>(got[3]);
-  p->d_cs_val = static_cast<float4*>(got[4]);
-  p->d_cs_cl = static_cast<unsigned short*>(got[5]);
+  // (a slot's CS_L columns are 16-bit, CS_L / 8 uint4; its values CS_L / 4 float4.  After a failure the blocks taken so
+  // far stay with the plan: cs_build's cs_free hands them back)
+  PlanCache& pc = c->plan_cache;
+  DSGD_TRY(p->d_cs_hdr.take(pc, (size_t)cells));
+  DSGD_TRY(p->d_cs_meta.take(pc, (size_t)(cells * slot_stride)));
+  DSGD_TRY(p->d_cs_rf.take(pc, (size_t)(cells * row_stride)));
+  DSGD_TRY(p->d_cs_col.take(pc, (size_t)(cells * slot_stride * (CS_L / 8))));
+  DSGD_TRY(p->d_cs_val.take(pc, (size_t)(cells * slot_stride * (CS_L / 4))));
+  DSGD_TRY(p->d_cs_cl.take(pc, (size_t)(cells * cl_stride)));
   ba.hdr = p->d_cs_hdr;
   ba.slot_meta = p->d_cs_meta;
   ba.row_first = p->d_cs_rf;
-  ba.col = reinterpret_cast<unsigned short*>(p->d_cs_col);
-  ba.val = reinterpret_cast<float*>(p->d_cs_val);
+  ba.col = reinterpret_cast<unsigned short*>(p->d_cs_col.get());
+  ba.val = reinterpret_cast<float*>(p->d_cs_val.get());
   ba.clist = p->d_cs_cl;
   ba.slot_stride = slot_stride;
   ba.row_stride = row_stride;
@@ -1328,7 +1204,7 @@ static int cs_build_device_impl(dsgd_ctx* c, dsgd_plan* p) {
   return DSGD_OK;
 }
 static int cs_build_impl(dsgd_ctx* c, dsgd_plan* p) {
-  cs_free(c, p);
+  p->cs_free();
   p->cs_layout = c->layout_gen;
   p->cs_device_built = false;
   // (the lists were uploaded on the build stream: the gather below runs on the launch stream)
@@ -1474,12 +1350,14 @@ static int cs_build_impl(dsgd_ctx* c, dsgd_plan* p) {
       }
     }
   }
-  CS_SOFT(dev_alloc((void**)&p->d_cs_hdr, sizeof(CsHdr) * hdr.size()));   // (outside the cache: cs_bytes stays 0, cs_free releases them)
-  CS_SOFT(dev_alloc((void**)&p->d_cs_meta, sizeof(unsigned int) * meta.size()));
-  CS_SOFT(dev_alloc((void**)&p->d_cs_rf, sizeof(unsigned short) * rf.size()));
-  CS_SOFT(dev_alloc((void**)&p->d_cs_col, sizeof(unsigned short) * col.size()));
-  CS_SOFT(dev_alloc((void**)&p->d_cs_val, sizeof(float) * val.size()));
-  CS_SOFT(dev_alloc((void**)&p->d_cs_cl, sizeof(unsigned short) * clist.size()));
+  // (outside the cache: the synchronous copies below are not ordered behind a cached block's last reader)
+  PlanCache& pc = c->plan_cache;
+  CS_SOFT(p->d_cs_hdr.alloc_uncached(pc, hdr.size()));
+  CS_SOFT(p->d_cs_meta.alloc_uncached(pc, meta.size()));
+  CS_SOFT(p->d_cs_rf.alloc_uncached(pc, rf.size()));
+  CS_SOFT(p->d_cs_col.alloc_uncached(pc, col.size() / 8));   // (uint4: eight 16-bit columns)
+  CS_SOFT(p->d_cs_val.alloc_uncached(pc, val.size() / 4));   // (float4)
+  CS_SOFT(p->d_cs_cl.alloc_uncached(pc, clist.size()));
   CS_SOFT(hipMemcpy(p->d_cs_cl, clist.data(), sizeof(unsigned short) * clist.size(), hipMemcpyHostToDevice));
   CS_SOFT(hipMemcpy(p->d_cs_hdr, hdr.data(), sizeof(CsHdr) * hdr.size(), hipMemcpyHostToDevice));
   CS_SOFT(hipMemcpy(p->d_cs_meta, meta.data(), sizeof(unsigned int) * meta.size(), hipMemcpyHostToDevice));
@@ -1504,11 +1382,8 @@ static int cs_build(dsgd_ctx* c, dsgd_plan* p) {
   } catch (const std::bad_alloc&) {   // (nothing may unwind across the C ABI)
     rc = 1;
   }
-  if (rc == 1) {
-    cs_free(c, p);   // (cs_layout is stamped: the plan keeps the row-parallel kernels until the layout changes)
-    return DSGD_OK;
-  }
-  return rc;
+  if (rc != DSGD_OK) p->cs_free();   // (whatever the builder had taken when it gave up)
+  return rc == 1 ? DSGD_OK : rc;    // (soft: cs_layout is stamped, the plan keeps the row-parallel kernels until the layout changes)
 }
 
 // the weights slice-major for G slices (they stay so until something else touches w: bind)
@@ -3027,6 +2902,8 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
     return fail(DSGD_EUNSUPPORTED, "device %d is %s; this library is built for gfx950 only", cfg->device, prop.gcnArchName);
   dsgd_ctx* c = new (std::nothrow) dsgd_ctx();
   if (!c) return fail(DSGD_ENOMEM, "out of host memory");
+  c->plan_cache.launch = &c->stream;
+  c->plan_cache.build = &c->build_stream;
   c->cfg = *cfg;
   c->dp = cfg->n_features + 1;
   c->n_cu = prop.multiProcessorCount;
@@ -3075,7 +2952,7 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   if (const char* e = getenv("DSGD_CS_MAX_MB")) c->cs_max_mb = std::max(0, atoi(e));
   if (const char* e = getenv("DSGD_CS_HOST_LAYOUT")) c->cs_host_layout = atoi(e) != 0;
   if (const char* e = getenv("DSGD_CS_REQ")) c->cs_req = atoi(e) != 0;
-  if (const char* e = getenv("DSGD_CACHE_MB")) c->cache_cap = (size_t)std::max(0, atoi(e)) << 20;
+  if (const char* e = getenv("DSGD_CACHE_MB")) c->plan_cache.cache_cap = (size_t)std::max(0, atoi(e)) << 20;
 #ifdef DSGD_TEST_COLLECTIVE_SEAM
   if (const char* e = getenv("DSGD_TEST_CS_SKIP_PUBLISH")) c->cs_test_skip = std::max(0, atoi(e));
 #endif
@@ -3194,12 +3071,10 @@ int dsgd_destroy(dsgd_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->build_stream) (void)hipStreamSynchronize(c->build_stream);
   if (c->comm && rccl::available()) rccl::CommDestroy(c->comm);
-  for (auto& e : c->prof_ev) {
-    (void)hipEventDestroy(e.first);
-    (void)hipEventDestroy(e.second);
-  }
-  while (!c->plans.empty()) plan_release(c, c->plans.back());   // plans still alive: their blocks come back through the cache
-  cache_drop_all(c);
+  // plans still alive: their blocks come back through the cache, which then lets go of everything -- in this order, and both
+  // before the members go
+  while (!c->plans.empty()) plan_release(c, c->plans.back());
+  c->plan_cache.drop_all();
   const hipStream_t streams[] = {c->upd_stream, c->async_stream, c->query_stream, c->build_stream, c->stream};
   lk.unlock();
   delete c;
@@ -3760,8 +3635,8 @@ int dsgd_cache_trim(dsgd_ctx* c, int64_t keep_bytes, int64_t* held_out) {
   if (keep_bytes < 0) return fail(DSGD_EINVAL, "negative keep_bytes");
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(bind(c, true));
-  cache_trim(c, (size_t)keep_bytes, false);
-  if (held_out) *held_out = (int64_t)c->cache_bytes;
+  c->plan_cache.trim((size_t)keep_bytes, false);
+  if (held_out) *held_out = (int64_t)c->plan_cache.cache_bytes;
   return DSGD_OK;
 }
 
@@ -3775,25 +3650,12 @@ int dsgd_plan_create_n(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const int
   return dsgd_plan_create(c, idx, offsets, n_steps, n_workers, out);
 }
 
-// A plan's frame: offsets checked, the two device blocks taken from the cache, the list ranges uploaded (build stream).
-// The caller fills p->d_idx on the build stream and calls plan_finish; on failure everything is given back.
-// the end of every plan: its cache blocks go back to the context behind whatever the launch stream still holds (an event per
-// block), its virtual tiles with the object (the caller has idled the launch stream if it holds any)
-static void plan_release(dsgd_ctx* c, dsgd_plan* p) {
-  cache_give(c, p->d_idx, p->idx_bytes);
-  cache_give(c, p->d_segs, p->segs_bytes);
-  cs_free(c, p);
-  cache_give(c, p->d_gate_rec, p->gate_bytes);
-  cache_give(c, p->d_s_rec, p->s_bytes);
-  // (the event may still be pending on the build stream: destroying a recorded event is allowed, its resources go when it completes)
-  if (p->built_ev) (void)hipEventDestroy(p->built_ev);
-  c->plans.erase(std::remove(c->plans.begin(), c->plans.end(), p), c->plans.end());
-  delete p;
-}
 static void plan_abandon(dsgd_ctx* c, dsgd_plan* p) {
   (void)hipStreamSynchronize(c->build_stream);
   plan_release(c, p);
 }
+// A plan's frame: offsets checked, the two device blocks taken from the cache, the list ranges uploaded (build stream).
+// The caller fills p->d_idx on the build stream and calls plan_finish; on failure everything is given back.
 static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int32_t n_workers, dsgd_plan** out, bool rp64 = false) {
   const int64_t n_lists = n_steps * n_workers;
   if (offsets[0] != 0) return fail(DSGD_EINVAL, "offsets[0] must be 0");
@@ -3835,15 +3697,11 @@ static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int3
   // the lists go up on the context's BUILD stream (beside whatever the launch stream is running: the next epoch's plan
   // can be set up while this epoch's steps run), into blocks earlier plans handed back
   int rc = ensure_build_stream(c);
-  void *qi = nullptr, *qs = nullptr;
-  const size_t ib = sizeof(int) * (size_t)offsets[n_lists], sb = sizeof(WorkSeg) * (size_t)n_lists;
-  if (rc == DSGD_OK && (cache_take(c, &qi, ib, &p->idx_bytes) || cache_take(c, &qs, sb, &p->segs_bytes)))
+  if (rc == DSGD_OK && (p->d_idx.take(c->plan_cache, (size_t)offsets[n_lists]) || p->d_segs.take(c->plan_cache, (size_t)n_lists)))
     rc = fail(DSGD_ENOMEM, "out of device memory (plan of %lld index entries)", (long long)offsets[n_lists]);
-  p->d_idx = static_cast<int*>(qi);
-  p->d_segs = static_cast<WorkSeg*>(qs);
-  if (rc == DSGD_OK && hipEventCreateWithFlags(&p->built_ev, hipEventDisableTiming) != hipSuccess) rc = fail(DSGD_EHIP, "hipEventCreate");
+  if (rc == DSGD_OK && hipEventCreateWithFlags(&p->built_ev.e, hipEventDisableTiming) != hipSuccess) rc = fail(DSGD_EHIP, "hipEventCreate");
   hipError_t e = hipSuccess;
-  if (rc == DSGD_OK) e = hipMemcpyAsync(p->d_segs, segs.data(), sb, hipMemcpyHostToDevice, c->build_stream);
+  if (rc == DSGD_OK) e = hipMemcpyAsync(p->d_segs, segs.data(), sizeof(WorkSeg) * segs.size(), hipMemcpyHostToDevice, c->build_stream);
   if (rc == DSGD_OK && e == hipSuccess) e = hipStreamSynchronize(c->build_stream);   // (segs is a local: staged before it goes)
   if (rc == DSGD_OK && e != hipSuccess) rc = fail(DSGD_EHIP, "plan upload: %s", hipGetErrorString(e));
   if (rc != DSGD_OK) {
@@ -4031,21 +3889,15 @@ int dsgd_plan_record(dsgd_ctx* c, dsgd_plan* p, int32_t on) {
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(bind(c, true));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  cache_give(c, p->d_gate_rec, p->gate_bytes);
-  cache_give(c, p->d_s_rec, p->s_bytes);
-  p->d_gate_rec = nullptr;
-  p->d_s_rec = nullptr;
+  p->d_gate_rec.reset();
+  p->d_s_rec.reset();
   p->gate_words = 0;
   if (!on) return DSGD_OK;
   const int words = (int)((std::max<long long>(p->max_step_rows, 1) + 31) / 32);
-  void *g = nullptr, *sv = nullptr;
-  if (cache_take(c, &g, sizeof(unsigned int) * (size_t)p->n_steps * words, &p->gate_bytes) ||
-      cache_take(c, &sv, sizeof(float) * (size_t)p->n_steps, &p->s_bytes)) {
-    cache_give(c, g, p->gate_bytes);
+  if (p->d_gate_rec.take(c->plan_cache, (size_t)p->n_steps * words) || p->d_s_rec.take(c->plan_cache, (size_t)p->n_steps)) {
+    p->d_gate_rec.reset();
     return fail(DSGD_ENOMEM, "out of device memory (plan record)");
   }
-  p->d_gate_rec = static_cast<unsigned int*>(g);
-  p->d_s_rec = static_cast<float*>(sv);
   p->gate_words = words;
   // (blocks from the cache were ordered against the BUILD stream: order them against the launch stream, which clears them)
   HIP_TRY(hipStreamSynchronize(c->build_stream ? c->build_stream : c->stream));

@@ -101,6 +101,13 @@ def context_cycle(name, precision, double_values):
             eng.synchronize()
             seeded.destroy()
         alive = eng.plan(lists(rng, 3, 2, 100))
+        if not fp64:   # the record's two blocks: taken, handed back, taken again -- and held at dsgd_destroy
+            alive.record(True)
+            eng.plan_run(alive, 0, 1, 0.5)
+            alive.record(False)
+            alive.record(True)
+            kernels["alive_plan"] = alive.info()["kind"]
+            kernels["alive_record_words"] = alive.info()["record_words"]
         eng.plan_run(alive, 0, 3, 0.5)   # (left alive at dsgd_destroy, its steps not synchronised)
     if not fp64:
         eng.async_set_trace(64)
@@ -114,6 +121,35 @@ def context_cycle(name, precision, double_values):
     if alive is not None:
         alive.handle = None
     report(name, before, during, live(), kernels=kernels)
+
+
+def host_layout_cycle():
+    """The column slices laid out by the host (DSGD_CS_HOST_LAYOUT=1, read at dsgd_create): blocks of the plan's own, outside
+    the cache.  Built, run, rebuilt over the freed ones after a second load, and alive at dsgd_destroy."""
+    rng = np.random.default_rng(9)
+    data = dsgd_amd.synth.generate(N_ROWS, seed=11, dim=DIM)
+    before = live()
+    os.environ["DSGD_CS_HOST_LAYOUT"] = "1"
+    try:
+        eng = dsgd_amd.Engine(DIM, LAM)
+    finally:
+        del os.environ["DSGD_CS_HOST_LAYOUT"]
+    eng.load_csr(data.row_ptr, data.col, data.val, data.label)
+    eng.set_dim_sparsity(eng.build_dim_sparsity(N_TRAIN))
+    eng.set_weights(rng.normal(scale=0.05, size=DIM + 1).astype(np.float32))
+    plan = eng.plan(lists(rng, 3, 2, 100))
+    eng.plan_run(plan, 0, 3, 0.5)
+    eng.synchronize()
+    first = plan.info()
+    during = live()
+    eng.load_csr(data.row_ptr, data.col, data.val, data.label)   # the slices are stale: the next run frees and rebuilds them
+    eng.set_dim_sparsity(eng.build_dim_sparsity(N_TRAIN))
+    eng.plan_run(plan, 0, 3, 0.5)
+    eng.synchronize()
+    second = plan.info()
+    eng.close()   # (the plan alive, holding host-built slices)
+    plan.handle = None
+    report("host_layout", before, during, live(), kinds=[first["kind"], second["kind"]], device_built=[first["device_built"], second["device_built"]])
 
 
 def failure_cycle():
@@ -143,7 +179,7 @@ def dense_cycle():
     report("dense", before, during, live())
 
 
-which = sys.argv[1:] or ["fp32", "fp64_float", "fp64_double", "failure_path", "dense"]
+which = sys.argv[1:] or ["fp32", "host_layout", "fp64_float", "fp64_double", "failure_path", "dense"]
 for w in which:
     if w == "fp32":
         context_cycle("fp32", "fp32", False)
@@ -151,6 +187,8 @@ for w in which:
         context_cycle("fp64_float", "fp64", False)
     elif w == "fp64_double":
         context_cycle("fp64_double", "fp64", True)
+    elif w == "host_layout":
+        host_layout_cycle()
     elif w == "failure_path":
         failure_cycle()
     elif w == "dense":

@@ -10,8 +10,11 @@ chunks each take one of the range steps.  Between create and destroy every owner
 dimSparsity, dense and Sparse weights, gradients, an index-list step of 2 workers, range steps, plans from lists (column
 slices, virtual tiles) and from a seed, forward and loss, an asynchronous step, a peer's update, a traced Hogwild run and a
 start / stop; on fp64 the row-parallel family (gradient, a step, an epoch's steps on the two-launch queue).  The last plan is
-never destroyed: it is alive at dsgd_destroy, which gives its blocks back through the context's cache and deletes it.  A context that only loads data and has one call refused, and the dense engine (4,096 x 512: the
-narrowest it accepts), are cycles of their own."""
+never destroyed: it is alive at dsgd_destroy, which gives its blocks back through the context's cache and deletes it; on fp32
+it keeps a record (dsgd_plan_record on, a step, off, on again) and holds the record's blocks then.  A context whose plans'
+column slices the host lays out (DSGD_CS_HOST_LAYOUT=1: blocks outside the cache; built, run, rebuilt over the freed ones
+after a second load, alive at dsgd_destroy), a context that only loads data and has one call refused, and the dense engine
+(4,096 x 512: the narrowest it accepts), are cycles of their own."""
 
 import json
 import os
@@ -25,7 +28,7 @@ from conftest import has_gpu
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="no gfx950 device")]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-CYCLES = ("fp32", "fp64_float", "fp64_double", "failure_path", "dense")
+CYCLES = ("fp32", "host_layout", "fp64_float", "fp64_double", "failure_path", "dense")
 
 
 @pytest.fixture(scope="module")
@@ -64,5 +67,8 @@ def test_the_cycles_took_the_paths_they_are_meant_to(cycles):
     assert k["column_lists"] == "dsgd_tc_grad_kernel" and k["row_chunks"] == "dsgd_fstep_kernel", k
     assert k["row_wise"] not in (k["column_lists"], k["row_chunks"]), k
     assert k["plan"] == "column_slices" and k["big_plan"] == "virtual_tiles", k
+    assert k["alive_plan"] == "column_slices" and k["alive_record_words"] > 0, k
+    h = cycles["host_layout"]
+    assert h["kinds"] == ["column_slices", "column_slices"] and h["device_built"] == [False, False], h
     assert cycles["fp64_float"]["kernels"]["plan"] == "column_slices_fp64"
     assert cycles["failure_path"]["refused"]
