@@ -45,6 +45,7 @@ SYMBOLS = [
     "dsgd_plan_create_rp64_n", "dsgd_plan_create_from_seed_rp64", "dsgd_async_plan_create_rp64",
     "dsgd_predict_ranges", "dsgd_predict_ranges_f64",
     "dsgd_plan_create_from_seed_job", "dsgd_plan_create_from_seed_job_rp64",
+    "dsgd_loss_acc_list", "dsgd_loss_acc_list_f64", "dsgd_loss_acc_sampled", "dsgd_loss_acc_sampled_f64",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -107,6 +108,13 @@ def load():
         if hasattr(lib, name):   # (ctx, jstate*, job_len*, n_job, first, n_local, split_begin*, max_samples, batch_size, out*, n_steps*, draws*)
             getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name in ("dsgd_loss_acc_list", "dsgd_loss_acc_list_f64"):
+        if hasattr(lib, name):   # (ctx, w*, idx*, n, loss*, acc*, counts*)
+            getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name in ("dsgd_loss_acc_sampled", "dsgd_loss_acc_sampled_f64"):
+        if hasattr(lib, name):   # (ctx, w*, jstate*, row_begin, row_end, samples_count, loss*, acc*, counts*, idx_out*, n*, draws*)
+            getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 

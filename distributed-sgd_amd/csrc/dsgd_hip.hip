@@ -133,6 +133,7 @@ static bool available() {
 #include "dsgd_rp64.hpp"   // (... and its row-parallel gradient family, on float and on Double feature values)
 #include "dsgd_sparse.hpp" // (the Sparse form at the boundary: compaction and scatter-in)
 #include "dsgd_predict.hpp" // (distributed evaluation: predictions and per-split tallies of K row ranges in one launch)
+#include "dsgd_eval_list.hpp" // (sampled evaluation: the tallies of the rows a device-resident list names in one launch)
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -2997,6 +2998,10 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   DSGD_ATTR(dsgd_predict_kernel<32>);
   DSGD_ATTR(dsgd_predict_kernel<16>);
   DSGD_ATTR(dsgd_predict_kernel<8>);
+  DSGD_ATTR(dsgd_eval_list_kernel<64>);
+  DSGD_ATTR(dsgd_eval_list_kernel<32>);
+  DSGD_ATTR(dsgd_eval_list_kernel<16>);
+  DSGD_ATTR(dsgd_eval_list_kernel<8>);
   DSGD_ATTR(dsgd_colcount_kernel);
   DSGD_ATTR((dsgd_hogwild_kernel<false, false>));
   DSGD_ATTR((dsgd_hogwild_kernel<true, false>));
@@ -4418,6 +4423,167 @@ int dsgd_predict_ranges_f64(dsgd_ctx* c, const double* w, const int64_t* row_beg
     c->s_dirty = true;
   }
   return predict_run(c, row_begin, row_end, n_ranges, total, pred_out, counts_out, loss, acc);
+}
+
+// ---- evaluation over a list of rows, given or drawn (csrc/dsgd_eval_list.hpp; ref: core/Master.scala:109-118) ----
+// |w|^2 of the loss, ONE launch over the n >= 1 rows c->d_idx names, the tallies back (bound, the weights resident, the list
+// enqueued on the context's stream).  Outputs are written when everything has succeeded, idx_out (n entries) among them.
+static int eval_list_run(dsgd_ctx* c, long long n, double* loss, double* acc, int64_t* counts, int32_t* idx_out) {
+  // |w|^2 as dsgd_predict_ranges takes it
+  if (loss && c->fp64) {
+    hipLaunchKernelGGL(dsgd_norm64_kernel, dim3(1), dim3(256), 0, c->stream, c->d_w64, c->dp, c->d_nsq64);
+  } else if (loss) {
+    if (c->nsq_dirty) c->s_dirty = true;
+    DSGD_TRY(ensure_s(c));
+  }
+  DSGD_TRY(reset_counters(c));
+  const int* d_idx = c->d_idx;
+  if (c->fp64) {
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>((long long)c->n_cu * 8, (n + 15) / 16)));
+    if (c->d_val64)
+      hipLaunchKernelGGL(dsgd_eval_list64v_kernel, grid, dim3(256), 0, c->stream, view64(c), c->d_w64, d_idx, n, c->d_sc);
+    else
+      hipLaunchKernelGGL(dsgd_eval_list64_kernel, grid, dim3(256), 0, c->stream, view(c), c->d_w64, d_idx, n, c->d_sc);
+  } else {
+    // dsgd_predict_ranges' launch: one 1024-lane workgroup per CU at most, a small weight tile for small calls
+    const int G = c->group;
+    const long long groups_per_block = 1024 / G;
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(c->n_cu, (n + groups_per_block - 1) / groups_per_block)));
+    const int hw = std::min(n >= 4096 ? c->hw_eval : std::min(c->hw_eval, 1024), DSGD_LDS_FLOATS - 4);
+    const size_t lds = sizeof(float) * (size_t)(hw + 4);   // (+ the workgroup's tally words)
+    CsrView m = view(c);
+    switch (G) {
+      case 64: hipLaunchKernelGGL(dsgd_eval_list_kernel<64>, grid, dim3(1024), lds, c->stream, m, c->d_w, d_idx, n, c->d_sc, hw); break;
+      case 32: hipLaunchKernelGGL(dsgd_eval_list_kernel<32>, grid, dim3(1024), lds, c->stream, m, c->d_w, d_idx, n, c->d_sc, hw); break;
+      case 16: hipLaunchKernelGGL(dsgd_eval_list_kernel<16>, grid, dim3(1024), lds, c->stream, m, c->d_w, d_idx, n, c->d_sc, hw); break;
+      default: hipLaunchKernelGGL(dsgd_eval_list_kernel<8>, grid, dim3(1024), lds, c->stream, m, c->d_w, d_idx, n, c->d_sc, hw); break;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  if (idx_out) {
+    DSGD_TRY(pin_acquire(c->pin_out, sizeof(int) * (size_t)n));
+    HIP_TRY(hipMemcpyAsync(c->pin_out.p, d_idx, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  }
+  DSGD_TRY(read_scalars(c));   // (synchronises; wnorm2 of the fp32 loss)
+  DSGD_TRY(check_err_flag(c));
+  long long t3[3];
+  for (int j = 0; j < 3; ++j) t3[j] = (long long)c->h_sc->counts[j];
+  if (t3[0] + t3[1] + t3[2] != n) return fail(DSGD_ESTATE, "internal: %lld rows tallied of %lld", t3[0] + t3[1] + t3[2], n);
+  double nsq = (double)c->h_sc->wnorm2;
+  if (loss && c->fp64) HIP_TRY(hipMemcpy(&nsq, c->d_nsq64, sizeof(double), hipMemcpyDeviceToHost));
+  if (loss) *loss = c->cfg.lambda * nsq + ((double)t3[1] + 2.0 * (double)t3[2]) / (double)n;   // (eval_read's expression)
+  if (acc) *acc = (double)t3[0] / (double)n;
+  for (int j = 0; counts && j < 3; ++j) counts[j] = (int64_t)t3[j];
+  if (idx_out) memcpy(idx_out, c->pin_out.p, sizeof(int) * (size_t)n);
+  return DSGD_OK;
+}
+
+// what the float and the Double form of a call share up to the layout: dsgd_predict_ranges' / _f64's rules for w and the mode
+static int eval_list_mode(dsgd_ctx* c, const char* what, bool f64, bool have_w) {
+  if (f64) DSGD_TRY(require_fp64(c, what));
+  else if (c->fp64 && have_w)
+    return fail(DSGD_EINVAL, "%s on an fp64 context takes w == NULL (the resident Double weights); %s_f64 takes a Double w", what, what);
+  DSGD_TRY(require_data(c));
+  return DSGD_OK;
+}
+// the weights of a call replace the resident ones (bound, the layout prepared)
+static int eval_list_weights(dsgd_ctx* c, const float* w, const double* w64) {
+  if (w) DSGD_TRY(set_weights_locked(c, w));
+  if (w64) {
+    DSGD_TRY(put64(c, w64, c->d_w64));   // (the Double weights as they are: no float rounding)
+    c->s_dirty = true;
+  }
+  return DSGD_OK;
+}
+
+static int loss_acc_list_impl(dsgd_ctx* c, const char* what, bool f64, const float* w, const double* w64, const int32_t* idx, int64_t n,
+                              double* loss, double* acc, int64_t* counts) {
+  DSGD_TRY(check_ctx(c));
+  if (!idx || n < 1)   // samples.map(...).reduce on an empty collection throws (ref: SparseSVM.scala:21-23)
+    return fail(DSGD_EINVAL, "%s: no list, or an empty one (reduce on an empty sample list)", what);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(eval_list_mode(c, what, f64, w != nullptr));
+  DSGD_TRY(require_sync_mode(c));
+  if (loss && !c->fp64) DSGD_TRY(require_ds(c));   // (|w|^2 comes with s, as in dsgd_loss_acc)
+  DSGD_TRY(bind(c));
+  DSGD_TRY(prepare_layout(c));
+  DSGD_TRY(eval_list_weights(c, w, w64));
+  DSGD_TRY(ensure_idx(c, n));
+  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int) * (size_t)n));
+  memcpy(c->pin_idx.p, idx, sizeof(int) * (size_t)n);
+  HIP_TRY(hipMemcpyAsync(c->d_idx, c->pin_idx.p, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  DSGD_TRY(pin_sent(c, c->pin_idx));
+  return eval_list_run(c, n, loss, acc, counts, nullptr);
+}
+int dsgd_loss_acc_list(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, double* loss, double* acc, int64_t* counts) {
+  return loss_acc_list_impl(c, "dsgd_loss_acc_list", false, w, nullptr, idx, n, loss, acc, counts);
+}
+int dsgd_loss_acc_list_f64(dsgd_ctx* c, const double* w, const int32_t* idx, int64_t n, double* loss, double* acc, int64_t* counts) {
+  return loss_acc_list_impl(c, "dsgd_loss_acc_list_f64", true, nullptr, w, idx, n, loss, acc, counts);
+}
+
+// The first n entries of Random.shuffle(0 until len) as the rows row_begin + entry, drawn into c->d_idx on the context's
+// stream: a one-worker, one-step job of dsgd_plan_create_from_seed_job with max_samples = batch_size = n (seed_walk and
+// seed_draw of csrc/dsgd_seed_host.hpp, a scratch list in place of a plan).  Refuses before anything is enqueued.
+static int sampled_draw(dsgd_ctx* c, const char* what, unsigned long long s0, int64_t row_begin, long long len, long long n, long long* draws) {
+  DSGD_TRY(ensure_idx(c, n));
+  *draws = 0;
+  if (len == 1) {   // (a shuffle of one entry draws nothing: the row itself)
+    DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int)));
+    *static_cast<int*>(c->pin_idx.p.get()) = (int)row_begin;
+    HIP_TRY(hipMemcpyAsync(c->d_idx, c->pin_idx.p, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    return pin_sent(c, c->pin_idx);
+  }
+  const int chunks = (int)((n + JR_MAX_TAKE - 1) / JR_MAX_TAKE);
+  const SeedRequest r{what, false, true, true, std::vector<long long>(1, len), 0, 1, &row_begin, (int)n, 0x7fffffff, chunks, JR_JOB_MAX_REJ, ""};
+  const JrFrame f = jr_frame(r.len, 0, 1, 1, (int)n);
+  DSGD_TRY(ensure_build_stream(c));
+  const SeedLaps lap;
+  JrWalked w;
+  DSGD_TRY(seed_walk(c, r, f, s0, len, lap, &w));
+  DSGD_TRY(seed_draw(c, r, f, w, s0, len, c->d_idx, c->stream, lap));
+  *draws = f.nominal + w.rej_total;
+  return DSGD_OK;
+}
+
+static int loss_acc_sampled_impl(dsgd_ctx* c, const char* what, bool f64, const float* w, const double* w64, uint64_t* jstate, int64_t row_begin,
+                                 int64_t row_end, int64_t samples_count, double* loss, double* acc, int64_t* counts, int32_t* idx_out,
+                                 int64_t* n_out, int64_t* draws_out) {
+  DSGD_TRY(check_ctx(c));
+  if (!jstate) return fail(DSGD_EINVAL, "%s: null jstate", what);
+  if (samples_count < 1 || row_begin >= row_end)   // (the JVM would have spent the shuffle's draws before .reduce throws; not here)
+    return fail(DSGD_EINVAL, "%s: an empty sample (samples_count %lld of rows [%lld, %lld)): reduce on an empty sample list", what,
+                (long long)samples_count, (long long)row_begin, (long long)row_end);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(eval_list_mode(c, what, f64, w != nullptr));
+  if (row_begin < 0 || row_end > c->n_rows)
+    return fail(DSGD_ERANGE, "rows [%lld, %lld) outside the %lld loaded rows", (long long)row_begin, (long long)row_end, c->n_rows);
+  DSGD_TRY(require_sync_mode(c));
+  if (loss && !c->fp64) DSGD_TRY(require_ds(c));
+  const long long len = row_end - row_begin, n = std::min<long long>(samples_count, len);   // (the reference's `take`)
+  if (len > JR_MAX_LEN) return fail(DSGD_EUNSUPPORTED, "%s draws windows up to %d rows (dsgd_jrand_shuffle, then %s)", what, JR_MAX_LEN,
+                                    f64 ? "dsgd_loss_acc_list_f64" : "dsgd_loss_acc_list");
+  DSGD_TRY(bind(c));
+  DSGD_TRY(prepare_layout(c));
+  const unsigned long long s0 = *jstate & JR_MASK;
+  long long draws = 0;
+  DSGD_TRY(sampled_draw(c, what, s0, row_begin, len, n, &draws));   // (a refusal leaves the weights as they were)
+  DSGD_TRY(eval_list_weights(c, w, w64));
+  DSGD_TRY(eval_list_run(c, n, loss, acc, counts, idx_out));
+  *jstate = jr_jump_dev(s0, (unsigned long long)draws);
+  if (n_out) *n_out = n;
+  if (draws_out) *draws_out = draws;
+  return DSGD_OK;
+}
+int dsgd_loss_acc_sampled(dsgd_ctx* c, const float* w, uint64_t* jstate, int64_t row_begin, int64_t row_end, int64_t samples_count, double* loss,
+                          double* acc, int64_t* counts, int32_t* idx_out, int64_t* n_out, int64_t* draws_out) {
+  return loss_acc_sampled_impl(c, "dsgd_loss_acc_sampled", false, w, nullptr, jstate, row_begin, row_end, samples_count, loss, acc, counts, idx_out,
+                               n_out, draws_out);
+}
+int dsgd_loss_acc_sampled_f64(dsgd_ctx* c, const double* w, uint64_t* jstate, int64_t row_begin, int64_t row_end, int64_t samples_count,
+                              double* loss, double* acc, int64_t* counts, int32_t* idx_out, int64_t* n_out, int64_t* draws_out) {
+  return loss_acc_sampled_impl(c, "dsgd_loss_acc_sampled_f64", true, nullptr, w, jstate, row_begin, row_end, samples_count, loss, acc, counts,
+                               idx_out, n_out, draws_out);
 }
 
 int dsgd_async_step(dsgd_ctx* c, const int32_t* idx, int64_t n, float lr, float* delta_out, dsgd_batch_stats* stats) {

@@ -102,11 +102,11 @@ static int seed_scan(dsgd_ctx* c, unsigned long long s0, long long scan, long lo
   return DSGD_OK;
 }
 
-// ---- pass B: the hosted workers' records to the device, the lists straight into the plan's index buffer ----
-// (max_len: the longest split traced HERE -- the bitmap of the slice kernels; abandons the plan where it fails)
+// ---- pass B: the hosted workers' records to the device, the lists straight into d_idx_out (a plan's index buffer, or the
+// scratch list of a sampled evaluation: dsgd_loss_acc_sampled) on stream `bs`, which is synchronised before the return ----
+// (max_len: the longest split traced HERE -- the bitmap of the slice kernels; a caller with a plan abandons it on failure)
 static int seed_draw(dsgd_ctx* c, const SeedRequest& r, const JrFrame& f, const JrWalked& w, unsigned long long s0, long long max_len,
-                     dsgd_plan* p, const SeedLaps& lap) {
-  hipStream_t bs = c->build_stream;
+                     int* d_idx_out, hipStream_t bs, const SeedLaps& lap) {
   const size_t n_local = (size_t)r.n_local;
   JrShuf* d_shuf = nullptr;
   int *d_rej = nullptr, *d_err = nullptr;
@@ -139,7 +139,7 @@ static int seed_draw(dsgd_ctx* c, const SeedRequest& r, const JrFrame& f, const 
     a.split_begin = d_sb;
     a.len = d_sb + n_local;
     a.offsets = d_off;
-    a.idx_out = p->d_idx;
+    a.idx_out = d_idx_out;
     a.n_local = r.n_local;
     a.batch_size = r.batch_size;
     a.chunks = r.chunks;
@@ -156,7 +156,7 @@ static int seed_draw(dsgd_ctx* c, const SeedRequest& r, const JrFrame& f, const 
     a.split_begin = d_sb;
     a.split_end = d_sb + n_local;
     a.offsets = d_off;
-    a.idx_out = p->d_idx;
+    a.idx_out = d_idx_out;
     a.n_splits = r.n_local;
     a.batch_size = r.batch_size;
     a.err = d_err;
@@ -168,10 +168,30 @@ static int seed_draw(dsgd_ctx* c, const SeedRequest& r, const JrFrame& f, const 
   lap("lists drawn (slice kernel)");
   if (e != hipSuccess || h_err) {
     (void)hipGetLastError();
-    plan_abandon(c, p);
     if (h_err) return fail(DSGD_EUNSUPPORTED, "a shuffle left the limits of the device form (draw the lists on the host)");
     return fail(DSGD_EHIP, "drawing the lists: %s", hipGetErrorString(e));
   }
+  return DSGD_OK;
+}
+
+// ---- pass A and the walk: where every hosted list's shuffle starts in the stream and what it rejects ----
+// (max_len: the longest split of the JOB; the context bound and its build stream made; refuses before anything is drawn)
+static int seed_walk(dsgd_ctx* c, const SeedRequest& r, const JrFrame& f, unsigned long long s0, long long max_len, const SeedLaps& lap,
+                     JrWalked* w) {
+  // scan, walk; a stream with more rejections than the margin scanned is scanned further and walked again
+  long long scan = f.nominal + 64 + f.nominal / 4096;
+  for (int attempt = 0;; ++attempt) {
+    SeedCandidates cands;
+    DSGD_TRY(seed_scan(c, s0, scan, max_len, lap, &cands));
+    if (jr_walk(f, r.len, cands.view(), scan, w)) break;
+    if (attempt >= 3) return fail(DSGD_EUNSUPPORTED, "the random stream keeps outrunning its scan (draw the lists on the host)");
+    scan = w->scan_at_least + 64 + w->rej_total / 8;
+  }
+  lap("candidates walked");
+  for (const JrShuf& s : w->shuf)
+    if (s.rej_end - s.rej_begin > r.max_rej)
+      return fail(DSGD_EUNSUPPORTED, "more than %d rejections inside one shuffle (draw the lists on the host)", r.max_rej);
+  jr_select_hosted(f, w);
   return DSGD_OK;
 }
 
@@ -216,21 +236,8 @@ static int plan_from_seed(dsgd_ctx* c, const SeedRequest& r, uint64_t* jstate, i
   DSGD_TRY(ensure_build_stream(c));
   const unsigned long long s0 = *jstate & JR_MASK;
   const SeedLaps lap;
-  // scan, walk; a stream with more rejections than the margin scanned is scanned further and walked again
   JrWalked w;
-  long long scan = f.nominal + 64 + f.nominal / 4096;
-  for (int attempt = 0;; ++attempt) {
-    SeedCandidates cands;
-    DSGD_TRY(seed_scan(c, s0, scan, max_len, lap, &cands));
-    if (jr_walk(f, r.len, cands.view(), scan, &w)) break;
-    if (attempt >= 3) return fail(DSGD_EUNSUPPORTED, "the random stream keeps outrunning its scan (draw the lists on the host)");
-    scan = w.scan_at_least + 64 + w.rej_total / 8;
-  }
-  lap("candidates walked");
-  for (const JrShuf& s : w.shuf)
-    if (s.rej_end - s.rej_begin > r.max_rej)
-      return fail(DSGD_EUNSUPPORTED, "more than %d rejections inside one shuffle (draw the lists on the host)", r.max_rej);
-  jr_select_hosted(f, &w);
+  DSGD_TRY(seed_walk(c, r, f, s0, max_len, lap, &w));
   // the plan's frame, then pass B straight into its index buffer
   dsgd_plan* p = nullptr;
   DSGD_TRY(plan_frame(c, f.offsets.data(), n_steps, r.n_local, &p, r.rp64));
@@ -238,7 +245,10 @@ static int plan_from_seed(dsgd_ctx* c, const SeedRequest& r, uint64_t* jstate, i
   p->idx_trusted = true;
   p->drawn = true;
   p->fits = false;   // (the one-workgroup kernel's test reads the lists on the host; these plans run on column slices)
-  DSGD_TRY(seed_draw(c, r, f, w, s0, hosted_max, p, lap));
+  if (const int rc = seed_draw(c, r, f, w, s0, hosted_max, p->d_idx, c->build_stream, lap)) {
+    plan_abandon(c, p);
+    return rc;
+  }
   DSGD_TRY(plan_finish(c, p, out));
   lap("plan laid out");
   *n_steps_out = n_steps;

@@ -385,6 +385,46 @@ class Engine:
                                                 C.byref(acc)))
         return pred[:total], counts[:k], loss.value, acc.value
 
+    def loss_acc_list(self, idx, w=None):
+        """Loss and accuracy over the rows `idx` names, tallied in ONE launch (dsgd_loss_acc_list; the fold of
+        Master.localSampledLoss / localSampledAccuracy, core/Master.scala:109-118, over a list drawn elsewhere).  A row
+        named twice counts twice.  Returns (loss, acc, counts) as loss_acc does; w as in predict_ranges."""
+        idx = i32(idx)
+        loss, acc = C.c_double(0), C.c_double(0)
+        counts = (C.c_int64 * 3)()
+        if self.fp64 and w is not None:
+            check(self._lib.dsgd_loss_acc_list_f64(self._ctx, ptr(f64(w, self.dp)), ptr(idx), C.c_int64(len(idx)), C.byref(loss),
+                                                   C.byref(acc), counts))
+        else:
+            wv = None if w is None else f32(w, self.dp)
+            check(self._lib.dsgd_loss_acc_list(self._ctx, ptr(wv), ptr(idx), C.c_int64(len(idx)), C.byref(loss), C.byref(acc), counts))
+        return loss.value, acc.value, list(counts)
+
+    def loss_acc_sampled(self, jstate, row_begin, row_end, samples_count, w=None, want_idx=False):
+        """Master.localSampledLoss / localSampledAccuracy (core/Master.scala:109-118) over a sample the DEVICE draws, draw
+        for draw the reference's stream (dsgd_loss_acc_sampled): the first min(samples_count, row_end - row_begin) entries of
+        Random.shuffle over the window, from java.util.Random's 48-bit state `jstate`.  Returns (loss, acc, counts, new
+        jstate, draws[, idx]) -- idx (want_idx) the rows evaluated, in the shuffle's order.  Raises DsgdError with code
+        EUNSUPPORTED where the device form does not apply (windows beyond 2^20 rows, more than 512 rejections): nothing was
+        drawn -- draw the list on the host (csrc/jrand.c) and call loss_acc_list."""
+        st = C.c_uint64(int(jstate))
+        loss, acc = C.c_double(0), C.c_double(0)
+        counts = (C.c_int64 * 3)()
+        n, draws = C.c_int64(0), C.c_int64(0)
+        cap = max(1, min(int(samples_count), int(row_end) - int(row_begin)))
+        idx = np.zeros(cap, dtype=np.int32) if want_idx else None
+        if self.fp64 and w is not None:
+            check(self._lib.dsgd_loss_acc_sampled_f64(self._ctx, ptr(f64(w, self.dp)), C.byref(st), C.c_int64(row_begin), C.c_int64(row_end),
+                                                      C.c_int64(samples_count), C.byref(loss), C.byref(acc), counts, ptr(idx),
+                                                      C.byref(n), C.byref(draws)))
+        else:
+            wv = None if w is None else f32(w, self.dp)
+            check(self._lib.dsgd_loss_acc_sampled(self._ctx, ptr(wv), C.byref(st), C.c_int64(row_begin), C.c_int64(row_end),
+                                                  C.c_int64(samples_count), C.byref(loss), C.byref(acc), counts, ptr(idx), C.byref(n),
+                                                  C.byref(draws)))
+        out = (loss.value, acc.value, list(counts), int(st.value), draws.value)
+        return out + (idx[:n.value],) if want_idx else out
+
     # -- asynchronous path -------------------------------------------------------------------------
     def async_step(self, idx, lr, want_delta=False):
         idx = i32(idx)

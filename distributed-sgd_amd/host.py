@@ -11,6 +11,7 @@ the reference.  Citations are relative to /root/reference/src/main/scala/epfl/di
     scala_shuffle     scala.util.Random.shuffle (2.12): the per-batch reshuffle of Master.scala:184
     MasterSync.fit    core/Master.scala:120-218
     predict, distributed_loss, distributed_accuracy (both masters)   core/Master.scala:61-98
+    local_sampled_loss, local_sampled_accuracy (both masters)        core/Master.scala:109-118
     MasterAsync.fit   core/MasterAsync.scala:32-62, 96-177
     Metrics           the Kamon instruments of the path, same names (core/Slave.scala:90-181, core/Master.scala:150-183)
     format_final_weights   the `final weights: idx:val ...` log line (Main.scala:114)
@@ -43,7 +44,8 @@ class Metrics:
     `slave.async.backward` (per sample, :90-95), `slave.async.batch` (:107), `slave.async.grad.update` (:181),
     `master.async.loss` (MasterAsync.scala:126); histograms `master.sync.loss`, `master.sync.acc`
     (Master.scala:150-151 record `losses.head.toLong` and `100 * accs.head.toLong`: the values are TRUNCATED to
-    integers before they are recorded -- kept); timer `master.sync.batch.duration` (:183)."""
+    integers before they are recorded -- kept); timer `master.sync.batch.duration` (:183); timers
+    `master.sampled.loss.duration`, `master.sampled.accuracy.duration` (the mirrors' own: one entry per sampled check)."""
 
     def __init__(self):
         import threading
@@ -535,8 +537,110 @@ class _DistributedEval:
         return self.distributed_loss_and_accuracy(weights)[1]
 
 
+# ---- Master.localSampledLoss / localSampledAccuracy -----------------------------------------------------------------
+# DSGD_SAMPLED_DEVICE=1: the sample of a sampled check is drawn by the device (Engine.loss_acc_sampled).  Off by default:
+# nobody has measured the device draw of ONE shuffle against the host's (tools/sampled_eval_probe.py is the measurement).
+SAMPLED_DEVICE_DEFAULT = "0"
+
+
+def sampled_list(rnd: JavaRandom, length: int, samples_count: int, native: Optional[bool] = None):
+    """`Random.shuffle(0 until length) take samples_count` (core/Master.scala:111, :116) as int32: one WHOLE shuffle from
+    `rnd`, which advances over its length - 1 draws (plus rejections), and its first min(samples_count, length) entries.
+    Natively (csrc/jrand.c: dsgd_jrand_shuffle) where lib/libdsgd_host.so is there, else scala_shuffle; `native` forces
+    one of the two."""
+    lib = _host_lib() if native in (None, True) else None
+    if native is True and lib is None:
+        raise RuntimeError("libdsgd_host.so is not built")
+    if lib is None or length < 1 or length > 2 ** 31 - 1:
+        return np.asarray(scala_shuffle(range(length), rnd)[:samples_count], dtype=np.int32)
+    import ctypes as C
+
+    buf = np.arange(length, dtype=np.int32)
+    state = C.c_uint64(rnd.seed)
+    lib.dsgd_jrand_shuffle(C.byref(state), buf.ctypes.data_as(C.c_void_p), C.c_int64(length))
+    rnd.seed = int(state.value)
+    return buf[:samples_count].copy()
+
+
+class _SampledEval:
+    """core/Master.scala:109-118 (shared by MasterSync and MasterAsync, which both extend AbstractMaster there): loss /
+    accuracy over `Random.shuffle(workingData.indices) take samplesCount map workingData`.  Every call spends ONE shuffle of
+    the whole window from self.rnd, as the reference spends it from the global generator that fit's per-batch shuffles
+    use (:184) -- loss and accuracy are two calls and two different samples, and a fit that follows continues from where
+    they left the stream.
+
+    A chain of backends, each falling through to the next when it refuses (an error with code EUNSUPPORTED):
+      1. backend.loss_acc_sampled (Engine: the DEVICE draws the sample and tallies it, one call), with DSGD_SAMPLED_DEVICE=1;
+      2. backend.loss_acc_list (Engine: one launch) over a list drawn here (sampled_list: csrc/jrand.c, else scala_shuffle);
+      3. backend.forward over that list and a fold here, as _DistributedEval folds (labels, get_weights and lam likewise).
+    The three routes return the same tallies and leave self.rnd in the same state.  For use BETWEEN fits: while a prefetch of
+    fit holds lists drawn ahead, the stream is not where the reference's would be, and the calls raise."""
+
+    def _sampled_window(self, samples_count, test):
+        lo, hi = (self.n_train, self.n_rows) if test else (0, self.n_train)
+        # samples.map(...).reduce on an empty sample throws (core/ml/SparseSVM.scala:21-23).  (The JVM has spent the
+        # shuffle's draws by then; here nothing is drawn.)
+        if int(samples_count) < 1 or hi <= lo:
+            raise ValueError("empty.reduceLeft: no samples to fold (samples_count %d of %d rows)" % (samples_count, max(0, hi - lo)))
+        if getattr(self, "_pending", None) is not None or getattr(self, "_lists_future", None) is not None:
+            raise RuntimeError("a prefetch of fit holds lists drawn ahead: the random stream is not where a sampled check "
+                               "would draw from (sampled checks run between fits)")
+        if getattr(self, "rnd", None) is None:
+            self.rnd = JavaRandom(0)   # (the global Random, seeded 0 at Main.scala:32)
+        return lo, hi
+
+    @staticmethod
+    def _refusal(e):
+        return getattr(e, "code", None) == -7   # DSGD_EUNSUPPORTED
+
+    def _sampled(self, samples_count, test, want_loss):
+        """(loss or None, accuracy, counts {#p==y, #p==0, #p==-y}) over one freshly drawn sample."""
+        lo, hi = self._sampled_window(samples_count, test)
+        k = int(samples_count)
+        if os.environ.get("DSGD_SAMPLED_DEVICE", SAMPLED_DEVICE_DEFAULT) == "1" and hasattr(self.backend, "loss_acc_sampled"):
+            try:
+                loss, acc, counts, state, _ = self.backend.loss_acc_sampled(self.rnd.seed, lo, hi, k)[:5]
+                self.rnd.seed = int(state)
+                return loss, acc, [int(c) for c in counts]
+            except Exception as e:   # (refused: nothing was drawn)
+                if not self._refusal(e):
+                    raise
+        idx = (sampled_list(self.rnd, hi - lo, k) + np.int32(lo)).astype(np.int32)
+        if hasattr(self.backend, "loss_acc_list"):
+            try:
+                loss, acc, counts = self.backend.loss_acc_list(idx)
+                return loss, acc, [int(c) for c in counts]
+            except Exception as e:
+                if not self._refusal(e):
+                    raise
+        y = self._labels(idx)   # (looked up first: a fold that cannot be made sends no request)
+        pred = np.asarray(self.backend.forward(idx), dtype=np.float64)
+        if getattr(self, "metrics", None) is not None:
+            self.metrics.counter("slave.sync.forward", len(idx))   # one increment per sample: Slave.scala:131
+        yp = y * pred
+        counts = [int(np.count_nonzero(yp > 0)), int(np.count_nonzero(yp == 0)), int(np.count_nonzero(yp < 0))]
+        n = len(idx)
+        loss = None
+        if want_loss:   # model.loss(p, y) = max(0, 1 - y p): 0, 1 or 2 per row (core/ml/SparseSVM.scala:16)
+            loss = float(getattr(self.backend, "lam")) * self._norm_squared(None) + (counts[1] + 2.0 * counts[2]) / n
+        return loss, counts[0] / n, counts
+
+    def _sampled_timed(self, name, samples_count, test, want_loss):
+        metrics = getattr(self, "metrics", None)
+        if metrics is None:
+            return self._sampled(samples_count, test, want_loss)
+        with metrics.timer(name):
+            return self._sampled(samples_count, test, want_loss)
+
+    def local_sampled_loss(self, samples_count: int, test: bool = False):       # Master.scala:109-112
+        return self._sampled_timed("master.sampled.loss.duration", samples_count, test, True)[0]
+
+    def local_sampled_accuracy(self, samples_count: int, test: bool = False):   # Master.scala:114-118
+        return self._sampled_timed("master.sampled.accuracy.duration", samples_count, test, False)[1]
+
+
 # ---- Master.fit (synchronous) ---------------------------------------------------------------------------------
-class MasterSync(_DistributedEval):
+class MasterSync(_DistributedEval, _SampledEval):
     """core/Master.scala:120-218 for the workers hosted behind one backend.
 
     data layout: rows [0, n_train) are the train set, [n_train, n_rows) the test set (Main.scala:52)."""
@@ -894,13 +998,15 @@ class MasterSync(_DistributedEval):
 
 
 # ---- MasterAsync.fit ------------------------------------------------------------------------------------------------
-class MasterAsync(_DistributedEval):
+class MasterAsync(_DistributedEval, _SampledEval):
     """core/MasterAsync.scala:32-177 on top of the lock-free engine: start the workers, check the test loss
     every `check_every` updates with a leaky average, keep the best weights, stop on the criterion or at
     maxSteps = n_train * max_epochs updates (MasterAsync.scala:83)."""
 
-    def __init__(self, backend, n_train: int, n_rows: int, node_count: int, log=None, poll_s: float = 0.0):
+    def __init__(self, backend, n_train: int, n_rows: int, node_count: int, log=None, poll_s: float = 0.0,
+                 rnd: Optional[JavaRandom] = None):
         self.backend, self.n_train, self.n_rows, self.node_count = backend, n_train, n_rows, node_count
+        self.rnd = rnd or JavaRandom(0)   # (the stream of the sampled checks: local_sampled_loss / local_sampled_accuracy)
         self.log = log or (lambda *a: None)
         self.poll_s = poll_s
         self.test_losses: List[float] = []

@@ -537,6 +537,47 @@ int dsgd_predict_ranges(dsgd_ctx* ctx, const float* w /* D+1 or NULL */, const i
 int dsgd_predict_ranges_f64(dsgd_ctx* ctx, const double* w /* D+1 or NULL */, const int64_t* row_begin, const int64_t* row_end,
                             int32_t n_ranges, int8_t* pred_out, int64_t* counts_out, double* loss, double* acc);
 
+/* Master.localSampledLoss / localSampledAccuracy (core/Master.scala:109-118): loss and accuracy folded over
+ *   Random.shuffle(workingData.indices) take samplesCount map workingData
+ * in ONE launch over rows already resident (csrc/dsgd_eval_list.hpp).  Two forms:
+ *
+ * dsgd_loss_acc_list evaluates the n >= 1 rows idx names.  A row named twice is counted twice (`map workingData`
+ * keeps duplicates; the sampled form never produces any).  An entry outside the loaded rows: DSGD_ERANGE, no output
+ * written.  With c the exact tallies {#p==y, #p==0, #p==-y} (counts, may be NULL):
+ *   loss = lambda*|w|^2 + (c1 + 2 c2) / n, acc = c0 / n -- dsgd_loss_acc's expression and its |w|^2 (either may be NULL).
+ * A row is decided on the x . w that dsgd_predict_ranges decides it on, so the tallies are the ones folded from
+ * dsgd_forward / dsgd_forward_f64 over the same list, and for idx = row_begin .. row_end - 1 the ones dsgd_loss_acc
+ * returns, under the condition dsgd_predict_ranges states (fp64: always; fp32: below 4,096 rows).
+ *
+ * dsgd_loss_acc_sampled draws the list itself, on the device, draw for draw the reference's stream: *jstate is
+ * java.util.Random's 48-bit state in front of the shuffle's first draw and, on success, the state behind its last;
+ * *draws_out (may be NULL) the raw values consumed, rejections included.  With len = row_end - row_begin the list is
+ * the first n = min(samples_count, len) entries (the reference's `take`; *n_out, may be NULL) of
+ * Random.shuffle(0 until len), entry p naming row row_begin + p; idx_out (n entries, may be NULL) receives the rows --
+ * the list does not visit the host otherwise.  One shuffle with its slice [0, n) is a one-worker, one-step job of
+ * dsgd_plan_create_from_seed_job, and its limits hold: len up to 2^20 rows and at most 512 rejections inside the
+ * shuffle.  Beyond them DSGD_EUNSUPPORTED: nothing is drawn, *jstate is untouched, nothing is written -- draw with
+ * dsgd_jrand_shuffle (csrc/jrand.c) and use the list form.  len == 1 draws nothing and evaluates that row.
+ *
+ * DSGD_EINVAL, nothing written or drawn: null ctx / idx / jstate, n < 1, samples_count < 1, row_begin >= row_end (the
+ * reference's .reduce over an empty sample throws; the JVM would have spent the shuffle's draws before throwing, this
+ * call does NOT).  A window outside the loaded rows: DSGD_ERANGE.  While the lock-free engine runs: DSGD_ESTATE.
+ * w == NULL uses the resident weights; otherwise w replaces them, under dsgd_predict_ranges' / _f64's rules: the float
+ * forms on an fp64 context take w == NULL only (DSGD_EINVAL otherwise), the _f64 forms need an fp64 context
+ * (DSGD_ESTATE otherwise).
+ * LOCAL to the rank: no collective is entered whether or not a communicator is attached.                          */
+int dsgd_loss_acc_list(dsgd_ctx* ctx, const float* w /* D+1 or NULL */, const int32_t* idx, int64_t n, double* loss, double* acc,
+                       int64_t* counts /* 3 or NULL */);
+int dsgd_loss_acc_list_f64(dsgd_ctx* ctx, const double* w /* D+1 or NULL */, const int32_t* idx, int64_t n, double* loss, double* acc,
+                           int64_t* counts /* 3 or NULL */);
+int dsgd_loss_acc_sampled(dsgd_ctx* ctx, const float* w /* D+1 or NULL */, uint64_t* jstate, int64_t row_begin, int64_t row_end,
+                          int64_t samples_count, double* loss, double* acc, int64_t* counts /* 3 or NULL */,
+                          int32_t* idx_out /* min(samples_count, row_end - row_begin) rows or NULL */, int64_t* n_out,
+                          int64_t* draws_out);
+int dsgd_loss_acc_sampled_f64(dsgd_ctx* ctx, const double* w /* D+1 or NULL */, uint64_t* jstate, int64_t row_begin, int64_t row_end,
+                              int64_t samples_count, double* loss, double* acc, int64_t* counts, int32_t* idx_out, int64_t* n_out,
+                              int64_t* draws_out);
+
 /* ---- asynchronous ("Hogwild") path ---------------------------------------------------------
  * one iteration of Slave.asyncTask (core/Slave.scala:92-101) on the resident weights with the
  * given sample list: grad = MEAN_i backward; delta = lr * regularize(grad, w); w -= delta.

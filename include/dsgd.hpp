@@ -10,6 +10,7 @@
 //   Slave                    core/Slave.scala:113-198 (handlers of SlaveImpl)
 //   Master::fit              core/Master.scala:120-218
 //   Master::predict, distributedLoss, distributedAccuracy   core/Master.scala:61-98 (one launch: dsgd_predict_ranges)
+//   Master::localSampledLoss, localSampledAccuracy           core/Master.scala:109-118 (dsgd_loss_acc_sampled / _list)
 //   SplitStrategy::vanilla   core/ml/SplitStrategy.scala:13-14
 //   EarlyStopping            core/ml/EarlyStopping.scala:11-46
 //   GradState                core/ml/GradState.scala:6-24
@@ -19,6 +20,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <deque>
 #include <functional>
 #include <limits>
@@ -370,6 +373,37 @@ class SparseSVM {
     out.counts.resize(3 * ranges.size());
     return out;
   }
+  // Loss and accuracy over a list of rows in one launch (dsgd_loss_acc_list / dsgd_loss_acc_sampled; the folds of
+  // core/Master.scala:109-118): the exact tallies {#p==y, #p==0, #p==-y}, the rows evaluated and, for a sample the device
+  // drew, the raw values it consumed and (wantIdx) the rows in the shuffle's order.
+  struct ListEval {
+    double loss = 0, accuracy = 0;
+    int64_t counts[3] = {0, 0, 0};
+    int64_t n = 0, draws = 0;
+    std::vector<int32_t> idx;
+  };
+  // a row named twice counts twice (`map workingData` keeps duplicates)
+  ListEval lossAccList(const Vec& w, const std::vector<int32_t>& idx) {
+    requireSize(w);
+    ListEval out;
+    check(dsgd_loss_acc_list(ctx_, w.data(), idx.data(), (int64_t)idx.size(), &out.loss, &out.accuracy, out.counts));
+    out.n = (int64_t)idx.size();
+    return out;
+  }
+  // `Random.shuffle(0 until rowEnd - rowBegin) take samplesCount`, drawn by the device from rnd's stream (left where the JVM's
+  // generator would stand behind the shuffle).  Outside the device form's limits NativeError with code DSGD_EUNSUPPORTED is
+  // thrown and rnd is untouched: shuffle on the host and call lossAccList.
+  ListEval lossAccSampled(const Vec& w, JavaRandom& rnd, int64_t rowBegin, int64_t rowEnd, int64_t samplesCount, bool wantIdx = false) {
+    requireSize(w);
+    ListEval out;
+    uint64_t st = rnd.state();
+    if (wantIdx) out.idx.resize((size_t)std::max<int64_t>(1, std::min(samplesCount, rowEnd - rowBegin)));
+    check(dsgd_loss_acc_sampled(ctx_, w.data(), &st, rowBegin, rowEnd, samplesCount, &out.loss, &out.accuracy, out.counts,
+                                wantIdx ? out.idx.data() : nullptr, &out.n, &out.draws));
+    rnd.setState(st);
+    if (wantIdx) out.idx.resize((size_t)out.n);
+    return out;
+  }
 
  private:
   void requireSize(const Vec& v) const {
@@ -470,6 +504,15 @@ class Master {
 
   double localLoss(const Vec& w, bool test = false) { return test ? model_.loss(w, nTrain_, nRows_) : model_.loss(w, 0, nTrain_); }  // :104
   double localAccuracy(const Vec& w, bool test = false) { return test ? model_.accuracy(w, nTrain_, nRows_) : model_.accuracy(w, 0, nTrain_); }  // :100
+
+  // :109-118 -- loss / accuracy over `Random.shuffle(workingData.indices) take samplesCount map workingData`: every call spends
+  // ONE shuffle of the whole window from the master's generator, the one fit's per-batch shuffles use (:184); loss and
+  // accuracy are two calls and two samples.  The sample is drawn by the device where DSGD_SAMPLED_DEVICE=1 and the device form
+  // applies (SparseSVM::lossAccSampled), else here (shuffle) and tallied in one launch (lossAccList): the same sample, the
+  // same numbers and the same generator state either way.  For use between fits.
+  double localSampledLoss(const Vec& w, int samplesCount, bool test = false) { return sampled(w, samplesCount, test).loss; }
+  double localSampledAccuracy(const Vec& w, int samplesCount, bool test = false) { return sampled(w, samplesCount, test).accuracy; }
+  const JavaRandom& random() const { return rnd_; }   // (where the stream stands)
 
   // :61-75 -- the rows split over the workers (SplitStrategy.vanilla, as fit splits them), one ForwardRequest each; the
   // replies zipped back to their rows.  Returns (row, prediction) in split order: the reference's Map[Int, Number].
@@ -588,6 +631,27 @@ class Master {
   int64_t nTrain_, nRows_;
   int nodeCount_;
   JavaRandom rnd_;
+
+  SparseSVM::ListEval sampled(const Vec& w, int samplesCount, bool test) {
+    const int64_t lo = test ? nTrain_ : 0, hi = test ? nRows_ : nTrain_;
+    // .reduce over an empty sample throws (core/ml/SparseSVM.scala:21-23).  (The JVM has spent the shuffle's draws by then;
+    // here nothing is drawn.)
+    if (samplesCount < 1 || hi <= lo) throw IllegalArgumentException("empty.reduceLeft: no samples to fold");
+    const char* dev = std::getenv("DSGD_SAMPLED_DEVICE");
+    if (dev && std::strcmp(dev, "1") == 0) {
+      try {
+        return model_.lossAccSampled(w, rnd_, lo, hi, samplesCount);
+      } catch (const NativeError& e) {   // (refused: nothing was drawn)
+        if (e.code != DSGD_EUNSUPPORTED) throw;
+      }
+    }
+    std::vector<int32_t> idx((size_t)(hi - lo));
+    for (size_t i = 0; i < idx.size(); ++i) idx[i] = (int32_t)i;
+    idx = shuffle(std::move(idx), rnd_);
+    idx.resize((size_t)std::min<int64_t>(samplesCount, hi - lo));
+    for (int32_t& r : idx) r += (int32_t)lo;
+    return model_.lossAccList(w, idx);
+  }
 };
 
 }  // namespace dsgd

@@ -622,6 +622,61 @@ JNIEXPORT void JNICALL NATIVE(predictRanges)(JNIEnv* env, jobject, jlong h, jflo
   env->SetDoubleArrayRegion(out, 0, 2, la);
 }
 
+// Master.localSampledLoss / localSampledAccuracy (core/Master.scala:109-118) over a list drawn by the caller
+// (dsgd_loss_acc_list): out = {loss, accuracy}.  w may be null (the resident weights; the only form an fp64 context takes).
+JNIEXPORT void JNICALL NATIVE(lossAccList)(JNIEnv* env, jobject, jlong h, jfloatArray w, jintArray idx, jdoubleArray out) {
+  if ((!idx || !out) && null_array(env)) return;
+  if (env->GetArrayLength(out) < 2) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "out shorter than 2");
+    return;
+  }
+  const jsize n = env->GetArrayLength(idx);
+  double la[2] = {0, 0};
+  int rc;
+  {
+    FloatElems wv(env, w, JNI_ABORT);
+    IntElems iv(env, idx, JNI_ABORT);
+    rc = dsgd_loss_acc_list(ctx(h), wv.p, reinterpret_cast<const int32_t*>(iv.p), n, &la[0], &la[1], nullptr);
+  }
+  if (rc) {
+    raise(env, rc);
+    return;
+  }
+  env->SetDoubleArrayRegion(out, 0, 2, la);
+}
+// ... over a sample the DEVICE draws (dsgd_loss_acc_sampled): state = java.util.Random's internal 48-bit state in front of the
+// shuffle, the return value the state behind it (planCreateFromSeed's meaning of the word, here by value); out = {loss,
+// accuracy, rows evaluated, raw values drawn}.  Beyond the device form's limits UnsupportedOperationException is thrown and
+// nothing was drawn: shuffle on the JVM and call lossAccList.
+JNIEXPORT jlong JNICALL NATIVE(lossAccSampled)(JNIEnv* env, jobject, jlong h, jfloatArray w, jlong state, jlong rowBegin, jlong rowEnd,
+                                               jlong samplesCount, jdoubleArray out) {
+  if (!out && null_array(env)) return state;
+  if (env->GetArrayLength(out) < 4) {
+    env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "out shorter than 4");
+    return state;
+  }
+  double la[4] = {0, 0, 0, 0};
+  uint64_t js = (uint64_t)state;
+  int64_t n = 0, draws = 0;
+  int rc;
+  {
+    FloatElems wv(env, w, JNI_ABORT);
+    rc = dsgd_loss_acc_sampled(ctx(h), wv.p, &js, rowBegin, rowEnd, samplesCount, &la[0], &la[1], nullptr, nullptr, &n, &draws);
+  }
+  if (rc == DSGD_EUNSUPPORTED) {
+    env->ThrowNew(env->FindClass("java/lang/UnsupportedOperationException"), dsgd_last_error());
+    return state;
+  }
+  if (rc) {
+    raise(env, rc);
+    return state;
+  }
+  la[2] = (double)n;
+  la[3] = (double)draws;
+  env->SetDoubleArrayRegion(out, 0, 4, la);
+  return (jlong)js;
+}
+
 // Slave.asyncTask body (core/Slave.scala:92-101); deltaOut receives what Slave.scala:103-105 gossips
 JNIEXPORT void JNICALL NATIVE(asyncStep)(JNIEnv* env, jobject, jlong h, jintArray idx, jfloat lr, jfloatArray deltaOut) {
   const jsize n = env->GetArrayLength(idx);

@@ -56,6 +56,12 @@ object NativeSVM {
   // Master.predict / distributedLoss / distributedAccuracy (core/Master.scala:61-98) in one launch: range k = worker k's split;
   // predOut: one byte in {-1, 0, +1} per row, range-major; out = {loss, accuracy}; w null = the resident weights
   @native def predictRanges(ctx: Long, w: Array[Float], rowBegin: Array[Long], rowEnd: Array[Long], predOut: Array[Byte], out: Array[Double]): Unit
+  // Master.localSampledLoss / localSampledAccuracy (core/Master.scala:109-118) in one launch: over the rows idx names (lossAccList,
+  // out = {loss, accuracy}), or over a sample the device draws from java.util.Random's 48-bit state (lossAccSampled: returns the
+  // state behind the shuffle; out = {loss, accuracy, rows evaluated, raw values drawn}; UnsupportedOperationException beyond the
+  // device form's limits, nothing drawn); w null = the resident weights
+  @native def lossAccList(ctx: Long, w: Array[Float], idx: Array[Int], out: Array[Double]): Unit
+  @native def lossAccSampled(ctx: Long, w: Array[Float], state: Long, rowBegin: Long, rowEnd: Long, samplesCount: Long, out: Array[Double]): Long
   @native def asyncStep(ctx: Long, idx: Array[Int], lr: Float, deltaOut: Array[Float]): Unit
   @native def updateGrad(ctx: Long, keys: Array[Int], values: Array[Float]): Unit
   // the same in the fp64 mode: Double learning rate, delta (D+1) and values
@@ -227,6 +233,27 @@ class HipSVM(lambda: Number, dimSparsity: Vec, data: Array[(Vec, Int)], nTrain: 
   /** Master.distributedLoss / distributedAccuracy (core/Master.scala:77-98) of the last predict call */
   def lastPredictLoss: Number      = synchronized(Number(predictLoss))
   def lastPredictAccuracy: Double = synchronized(predictAccuracy)
+
+  /** Master.localSampledLoss / localSampledAccuracy (core/Master.scala:109-118) over rows [rowBegin, rowEnd): (loss, accuracy,
+    * state behind the shuffle).  `state` is the internal 48-bit state of the java.util.Random the reference would shuffle with;
+    * the device draws `Random.shuffle(0 until len) take samplesCount` from it and tallies the sample in one launch.  Where the
+    * device form does not apply (a window beyond 2^20 rows) UnsupportedOperationException is thrown and nothing was drawn: the
+    * caller shuffles on the JVM and calls sampledLossAndAccuracy(w, idx).  The weights as in predict. */
+  def sampledLossAndAccuracy(w: Vec, state: Long, rowBegin: Int, rowEnd: Int, samplesCount: Int): (Number, Double, Long) = synchronized {
+    val out = new Array[Double](4)
+    if (fp64 && !resident) setWeights(w)
+    val after = NativeSVM.lossAccSampled(ctx, if (resident || fp64) null else DenseKeys.fromVec(w), state, rowBegin.toLong, rowEnd.toLong,
+                                         samplesCount.toLong, out)
+    (Number(out(0)), out(1), after)
+  }
+
+  /** ... over the rows `idx` names (a sample drawn by the caller; a row named twice counts twice): (loss, accuracy) */
+  def sampledLossAndAccuracy(w: Vec, idx: Array[Int]): (Number, Double) = synchronized {
+    val out = new Array[Double](2)
+    if (fp64 && !resident) setWeights(w)
+    NativeSVM.lossAccList(ctx, if (resident || fp64) null else DenseKeys.fromVec(w), idx, out)
+    (Number(out(0)), out(1))
+  }
 
   /** dev mode (Main.scala "launch: master + slaves"): master and slaves live in ONE JVM and share this object, i.e. ONE
     * device context holds every row and the weights can stay on the device between batches / iterations. */
