@@ -390,11 +390,7 @@ constexpr int MB_WL = 11264;     // ranks with an LDS copy of their weight (44 K
 constexpr int MB_SHORT = BT_CH;          // 128
 constexpr int MB_MEDIUM = 4 * BT_CH;     // 512
 constexpr int MB_WIDE = 4 * BT_CH * MB_R;  // 1024: one row over both slots of a pass
-struct __attribute__((aligned(16))) MbRec {   // one row of a wave's batch, as the passes need it
-  long long st;    // first non-zero
-  int len;
-  float y;         // label (+1 / -1)
-};
+// (MbRec, one row of a wave's batch as the passes need it: csrc/dsgd_layout_types.hpp)
 __host__ __device__ constexpr int mb_lds_words(int hl, int wl) { return ((hl + 3) & ~3) + wl + (MB_THREADS / 64) * 64 * 4 + 4; }
 
 template <int R>
@@ -843,14 +839,7 @@ __global__ void __launch_bounds__(MB_THREADS) dsgd_mb_grad_kernel(MbArgs a) {
 // found under all of it: 55 of the 67 us went to 4,096 waves finishing together and adding their active-row counts
 // to ONE address -- one atomic per workgroup: 24.6 us for B = 65,536 (dsgd_mb_grad_kernel: 40), 15.7 for 4,096 (18.4),
 // 12.3 for 3 x 100 (15.4).
-struct VtLane {          // 16 bytes, one per lane of a virtual tile (written by the host: vt_build)
-  unsigned int hp;       // first of the lane's <= 8 slots in the hot stream
-  unsigned int info;     // valid slots (bits 0-3) | first lane of its row (4) | last lane (5) | label > 0 (6) |
-                         // has a cold entry (8) | local row of the tile (bits 16-21)
-  unsigned int cp;       // the lane's cold entry in the cold stream
-  unsigned int crank;    // ... and its rank - hsplit (the host keeps a copy of the cold ranks: no load depends on a load)
-};
-constexpr unsigned int VT_START = 1u << 4, VT_LAST = 1u << 5, VT_YPOS = 1u << 6, VT_COLD = 1u << 8;
+// (the lane descriptor VtLane and its VT_* flag bits: csrc/dsgd_layout_types.hpp)
 
 struct VtArgs {
   const unsigned short* hcol;   // hot stream: 16-bit ranks, values

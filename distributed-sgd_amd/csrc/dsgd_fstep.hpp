@@ -30,12 +30,7 @@
 
 #include "dsgd_kernels.hpp"
 
-struct FChunk {          // 32 bytes, read with scalar loads
-  int row_begin, row_end;      // the chunk's rows
-  int tile_begin, tile_end;    // its hot tiles (of the chunked tile table)
-  int ctile_begin, ctile_end;  // its cold tiles
-  int long_begin, long_end;    // its range of the long-row list
-};
+// (the chunk record FChunk: csrc/dsgd_layout_types.hpp)
 
 // m: the hot stream (col = 16-bit ranks); mfull: the whole ranked CSR (long rows).  16-bit cold ids, every cold column in
 // the LDS tile (the host takes the three-launch path otherwise).

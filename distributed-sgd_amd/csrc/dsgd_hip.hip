@@ -122,6 +122,7 @@ static bool available() {
 #include "dsgd_buf.hpp"      // (host only: the owners of device and pinned memory)
 #include "dsgd_plan_cache.hpp"   // (host only: the device blocks plans take and hand back, and a plan's hold on one)
 #include "dsgd_plan_check.hpp"   // (host only: a plan's lists against the rows loaded now)
+#include "dsgd_layout_host.hpp"  // (host only: the arithmetic behind every table the gradient kernels read)
 #include "dsgd_kernels.hpp"
 #include "dsgd_batch.hpp"
 #include "dsgd_cs.hpp"
@@ -784,9 +785,7 @@ static int launch_grad_mb(dsgd_ctx* c, const int* d_idx, const WorkSeg* d_segs, 
   long long rows_per_wg = std::max<long long>(64, (max_items + per_worker - 1) / per_worker);
   const long long wgs = std::max<long long>(1, (max_items + rows_per_wg - 1) / rows_per_wg);
   DSGD_TRY(ensure_part(c, c->d_part, &c->part_wgs, &c->part_stride, wgs * n_workers, hl));
-  int bits = 0;
-  while ((1LL << bits) < rows_per_wg) ++bits;
-  const int shift = 30 - bits;   // at most one contribution per row and column: a workgroup's sums stay below 2^30
+  const int shift = 30 - rows_bits(rows_per_wg);   // at most one contribution per row and column: a workgroup's sums stay below 2^30
   c->last_shift = shift;
   MbArgs a;
   a.m = view(c);
@@ -859,94 +858,17 @@ static int vt_build_impl(dsgd_ctx* c, dsgd_plan* p) {
   DSGD_TRY(plan_host_idx(c, p));
   if (c->h_hrp.size() != (size_t)c->n_rows + 1 || (long long)p->h_idx.size() != p->offsets[n_lists]) return DSGD_OK;
   if ((long long)c->h_ccol.size() != c->coldm_nnz) return DSGD_OK;
-  const std::vector<long long>&hrp = c->h_hrp, &ctp = c->h_ctp, &crp = c->h_crow_ptr;
-  std::vector<VtLane> lanes;
-  lanes.reserve((size_t)p->offsets[n_lists] * 10);
-  std::vector<int> tile_rows;
-  std::vector<MbRec> long_rows;
-  std::vector<long long> long_off((size_t)n_lists + 1, 0);
-  p->vt_off.assign((size_t)n_lists + 1, 0);
-  const VtLane empty{0u, 0u, 0u, 0u};
-  for (long long li = 0; li < n_lists; ++li) {
-    int used = 0, rows = 0;   // lanes and rows of the open tile
-    for (long long t = p->offsets[li]; t < p->offsets[li + 1]; ++t) {
-      const long long r = p->h_idx[(size_t)t];
-      if (r < 0 || r >= c->n_rows) return DSGD_OK;       // (the mb kernel reports the bad index)
-      const long long hot = hrp[r + 1] - hrp[r], cold = crp[r + 1] - crp[r];
-      if (hot <= 0 || cold > 64) {   // long-row list / too many cold entries for a tile: one wave per row, whole CSR
-        MbRec lr;
-        lr.st = c->h_row_ptr[(size_t)r];
-        lr.len = (int)(c->h_row_ptr[(size_t)r + 1] - c->h_row_ptr[(size_t)r]);
-        lr.y = (float)c->h_label[(size_t)r];
-        long_rows.push_back(lr);
-        continue;
-      }
-      const int nl = (int)std::max<long long>(std::max<long long>((hot + 7) / 8, cold), 1);
-      if (used + nl > 64) {                               // close the tile
-        lanes.resize(lanes.size() + (size_t)(64 - used), empty);
-        tile_rows.push_back(rows);
-        used = 0;
-        rows = 0;
-      }
-      const unsigned int ypos = c->h_label[(size_t)r] > 0 ? VT_YPOS : 0u;
-      for (int j = 0; j < nl; ++j) {
-        VtLane L;
-        const long long left = hot - 8LL * j;
-        const unsigned int cnt = (unsigned int)std::max<long long>(0, std::min<long long>(8, left));
-        L.hp = cnt ? (unsigned int)(hrp[r] + 8LL * j) : 0u;
-        L.info = cnt | (j == 0 ? VT_START : 0u) | (j == nl - 1 ? VT_LAST : 0u) | ypos | (j < cold ? VT_COLD : 0u) |
-                 ((unsigned int)rows << 16);
-        L.cp = j < cold ? (unsigned int)(ctp[r] + j) : 0u;
-        L.crank = j < cold ? (unsigned int)c->h_ccol[(size_t)(ctp[r] + j)] : 0u;
-        lanes.push_back(L);
-      }
-      used += nl;
-      ++rows;
-    }
-    lanes.resize(lanes.size() + (size_t)(64 - used), empty);   // (a list is never empty: its last tile is open)
-    tile_rows.push_back(rows);
-    p->vt_off[(size_t)li + 1] = (long long)tile_rows.size();
-    long_off[(size_t)li + 1] = (long long)long_rows.size();
-  }
-  // per step: the grid (workgroups per worker) and the fixed-point shift from the rows ONE workgroup can meet
-  p->vt_grid.assign((size_t)p->n_steps, 1);
-  p->vt_gxt.assign((size_t)p->n_steps, 1);
-  p->vt_shift.assign((size_t)p->n_steps, 21);
-  const long long per_worker = std::max<long long>(1, c->n_cu / p->n_workers);
-  std::vector<WorkSeg> segs((size_t)n_lists * 2);
-  for (long long li = 0; li < n_lists; ++li) {
-    segs[(size_t)(n_lists + li)].begin = long_off[(size_t)li];
-    segs[(size_t)(n_lists + li)].end = long_off[(size_t)li + 1];
-  }
-  for (long long s = 0; s < p->n_steps; ++s) {
-    long long max_t = 1;
-    for (int k = 0; k < p->n_workers; ++k) {
-      const long long li = s * p->n_workers + k;
-      segs[(size_t)li].begin = p->vt_off[(size_t)li];
-      segs[(size_t)li].end = p->vt_off[(size_t)li + 1];
-      max_t = std::max(max_t, segs[(size_t)li].end - segs[(size_t)li].begin);
-    }
-    long long max_long = 0;
-    for (int k = 0; k < p->n_workers; ++k)
-      max_long = std::max(max_long, long_off[(size_t)(s * p->n_workers + k) + 1] - long_off[(size_t)(s * p->n_workers + k)]);
-    // workgroups of their own for the rows outside the tiled streams (one wave per row), beside the tile workgroups
-    const long long gl = max_long ? std::max<long long>(1, std::min<long long>((max_long + 15) / 16, std::max<long long>(1, per_worker / 8))) : 0;
-    const long long gx = std::max<long long>(1, std::min(per_worker - gl, (max_t + 16LL * c->vt_tpw - 1) / (16LL * c->vt_tpw)));
-    long long worst = 1;
-    std::vector<long long> rows_of((size_t)gx);
-    for (int k = 0; k < p->n_workers; ++k) {
-      const WorkSeg& sg = segs[(size_t)(s * p->n_workers + k)];
-      std::fill(rows_of.begin(), rows_of.end(), 0);
-      for (long long t = sg.begin; t < sg.end; ++t) rows_of[(size_t)(((t - sg.begin) / 16) % gx)] += tile_rows[(size_t)t];
-      for (long long v : rows_of) worst = std::max(worst, v);
-    }
-    if (gl) worst = std::max(worst, (max_long + 16 * gl - 1) / (16 * gl) * 16);   // rows one long-row workgroup can meet
-    int bits = 0;
-    while ((1LL << bits) < worst) ++bits;
-    p->vt_gxt[(size_t)s] = (int)gx;
-    p->vt_grid[(size_t)s] = (int)(gx + gl);
-    p->vt_shift[(size_t)s] = std::min(21, 30 - bits);   // (<= 21: the fixed-point conversion is one fma against 1.5 * 2^23)
-  }
+  const VtStreams m{c->n_rows, c->h_hrp.data(), c->h_ctp.data(), c->h_crow_ptr.data(), c->h_row_ptr.data(), c->h_label.data(), c->h_ccol.data()};
+  VtTables T;
+  const bool inside = vt_tables(p->h_idx.data(), p->offsets.data(), p->n_steps, p->n_workers, c->n_cu, c->vt_tpw, m, T);
+  p->vt_off.swap(T.vt_off);
+  if (!inside) return DSGD_OK;   // (the mb kernel reports the bad index)
+  p->vt_grid.swap(T.grid);
+  p->vt_gxt.swap(T.gxt);
+  p->vt_shift.swap(T.shift);
+  const std::vector<VtLane>& lanes = T.lanes;
+  const std::vector<WorkSeg>& segs = T.segs;
+  const std::vector<MbRec>& long_rows = T.long_rows;
   VT_SOFT(p->d_vt_lanes.try_alloc(std::max<size_t>(lanes.size(), 64)));
   VT_SOFT(p->d_vt_segs.try_alloc(segs.size()));
   VT_SOFT(p->d_vt_long.try_alloc(std::max<size_t>(long_rows.size(), 1)));
@@ -956,7 +878,7 @@ static int vt_build_impl(dsgd_ctx* c, dsgd_plan* p) {
     HIP_TRY(hipMemcpy(p->d_vt_long, long_rows.data(), sizeof(MbRec) * long_rows.size(), hipMemcpyHostToDevice));
   // small and mid-size plans get their own copy of the rows they touch, in tile order (dsgd_vt_pack_kernel): one
   // coalesced round trip per step instead of descriptors -> scattered rows
-  const long long n_tiles = (long long)tile_rows.size();
+  const long long n_tiles = (long long)T.tile_rows.size();
   // (bounded by DSGD_VT_PACK_MB and by a quarter of the device memory that is free right now: a plan's copy must not be
   //  what makes the next allocation of the data path fail)
   size_t mem_free = 0, mem_total = 0;
@@ -1141,9 +1063,7 @@ static int cs_build_device_impl(dsgd_ctx* c, dsgd_plan* p) {
   for (long long st = 0; st < n_steps; ++st) {
     long long worst_list = 1;
     for (int k = 0; k < K; ++k) worst_list = std::max(worst_list, p->offsets[(size_t)(st * K + k) + 1] - p->offsets[(size_t)(st * K + k)]);
-    int bits = 0;
-    while ((1LL << bits) < worst_list) ++bits;
-    p->cs_shift[(size_t)st] = 30 - bits;   // at most one contribution per row and column: a worker's sums stay below 2^30
+    p->cs_shift[(size_t)st] = 30 - rows_bits(worst_list);   // at most one contribution per row and column: a worker's sums stay below 2^30
   }
   DSGD_TRY(ensure_build_stream(c));
   DSGD_TRY(ensure_cs_max(c));
@@ -1282,9 +1202,7 @@ static int cs_build_impl(dsgd_ctx* c, dsgd_plan* p) {
         max_cols = std::max(max_cols, cols[(size_t)b]);
       }
       max_rows = std::max(max_rows, p->offsets[(size_t)((s + 1) * K)] - p->offsets[(size_t)(s * K)]);
-      int bits = 0;
-      while ((1LL << bits) < worst_list) ++bits;
-      p->cs_shift[(size_t)s] = 30 - bits;   // at most one contribution per row and column: a worker's sums stay below 2^30
+      p->cs_shift[(size_t)s] = 30 - rows_bits(worst_list);   // at most one contribution per row and column: a worker's sums stay below 2^30
     }
   }
   if (max_slots > CS_MAX_SLOTS || max_rows > CS_MAX_SLOTS || max_cols > (long long)CS_MAX_CLT * CS_THREADS) return DSGD_OK;
@@ -1553,9 +1471,7 @@ static int launch_cs_request(dsgd_ctx* c, int G, int K, long long worst_list, fl
   c->ctr_known = false;
   hipLaunchKernelGGL(dsgd_cs_request_kernel, dim3((unsigned)G), dim3(CS_THREADS), lds, c->stream, a, ba);
   HIP_TRY(hipGetLastError());
-  int bits = 0;
-  while ((1LL << bits) < worst_list) ++bits;
-  cs_after_launch(c, 30 - bits);
+  cs_after_launch(c, 30 - rows_bits(worst_list));
   c->last_grad_kernel = "dsgd_cs_request_kernel";
   return DSGD_OK;
 }
@@ -1680,88 +1596,7 @@ static int count_columns(dsgd_ctx* c, long long nnz, unsigned int* d_cnt, bool f
   return DSGD_OK;
 }
 
-// ---- wave tiles ------------------------------------------------------------------------------------------
-// Tiles of WHOLE rows of the hot stream with <= WS_MAXNNZ non-zeros and <= WS_MAXROWS rows.  Lane l owns the 8
-// contiguous slots [8l, 8l+8) of the 512-slot window at pos0 (a multiple of 8 slots: one 16-byte load of eight 16-bit
-// column ranks per lane).  Lane descriptor (16 bits): row-start bits | label sign of the row ENDING at each start << 8
-// (the kernel derives each lane's first row with a wave prefix sum over the start bits).  Rows of length 0 in
-// `row_ptr` are skipped: the caller emptied them and put them on the long-row list.
-struct HostTiles {
-  std::vector<WTile> wt;
-  std::vector<int> r0;              // first row of every tile + sentinel n_rows
-  std::vector<unsigned short> meta16;   // n_tiles x 64
-};
-// wave tiles of WHOLE rows over the rows [rb, re) of a stream given by its slot offsets (a window of <= WS_SLOTS slots that
-// starts at a multiple of 8; rows without a slot or longer than a tile close the open tile and stay out), appended to wt
-static void append_wave_tiles(const long long* row_ptr, long long rb, long long re, std::vector<WTile>& wt, int max_rows) {
-  const long long amask = ~7LL;
-  long long start = -1;  // first row of the open tile
-  auto close = [&](long long end_row) {
-    if (start < 0) return;
-    WTile t;
-    t.pos0 = row_ptr[start] & amask;
-    t.r0 = (int)start;
-    t.info = (int)(((end_row - start) & 0xffff) | ((row_ptr[end_row] - t.pos0) << 16));
-    wt.push_back(t);
-    start = -1;
-  };
-  for (long long i = rb; i < re; ++i) {
-    const long long len = row_ptr[i + 1] - row_ptr[i];
-    if (len > WS_MAXNNZ || len == 0) {
-      close(i);
-      continue;
-    }
-    if (start >= 0 && (row_ptr[i + 1] - (row_ptr[start] & amask) > WS_SLOTS - 1 || i - start >= max_rows)) close(i);
-    if (start < 0) start = i;
-  }
-  close(re);
-}
-// the 64 lane descriptors of every tile: row-start bits of the lane's eight slots | label signs of the rows ending there << 8
-static void wave_tile_meta(const long long* row_ptr, const signed char* label, const std::vector<WTile>& wt,
-                           std::vector<unsigned short>& meta16) {
-  const long long n_tiles = (long long)wt.size();
-  meta16.assign((size_t)std::max<long long>(n_tiles, 1) * 64, (unsigned short)0);
-  for (long long t = 0; t < n_tiles; ++t) {
-    const WTile& T = wt[(size_t)t];
-    const int t_nrows = (int)(short)(T.info & 0xffff);
-    int cur_row = 0, next = 0;
-    for (int l = 0; l < 64; ++l) {  // lane l owns slots [8l, 8l+8)
-      unsigned int bits = 0, ys = 0;
-      for (int k = 0; k < 8; ++k) {
-        const long long slot = 8LL * l + k;
-        bool st = false;
-        if (next < t_nrows && row_ptr[T.r0 + next] - T.pos0 == slot) st = true;
-        else if (next == t_nrows && row_ptr[T.r0 + t_nrows] - T.pos0 == slot) st = true;  // end mark
-        if (st) {
-          bits |= 1u << k;
-          // the row that ends here is local row cur_row (1-based); row 0 = leading padding
-          if (cur_row >= 1 && label[T.r0 + cur_row - 1] > 0) ys |= 1u << k;
-          ++cur_row;
-          ++next;
-        }
-      }
-      meta16[(size_t)t * 64 + l] = (unsigned short)(bits | (ys << 8));
-    }
-  }
-}
-static void build_wave_tiles(const long long* row_ptr, long long n_rows, const signed char* label, HostTiles& out,
-                             int max_rows = WS_MAXROWS) {
-  std::vector<WTile>& wt = out.wt;
-  std::vector<int>& wr0 = out.r0;
-  wt.clear();
-  wr0.clear();
-  append_wave_tiles(row_ptr, 0, n_rows, wt, max_rows);
-  for (const WTile& t : wt) wr0.push_back(t.r0);
-  wr0.push_back((int)n_rows);
-  wave_tile_meta(row_ptr, label, wt, out.meta16);
-  if (wt.empty()) {
-    WTile t;
-    t.pos0 = 0;
-    t.r0 = 0;
-    t.info = 0xffff;   // -1 rows, 0 slots
-    wt.push_back(t);
-  }
-}
+// ---- wave tiles (laid out by csrc/dsgd_layout_host.hpp: build_wave_tiles) ----------------------------------------
 static int upload_wave_tiles(dsgd_ctx* c, HostTiles& ht) {
   c->d_wtiles.reset();
   c->d_wmeta.reset();
@@ -1812,39 +1647,10 @@ static int build_split(dsgd_ctx* c) {
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   d_cnt.reset();
   if (e != hipSuccess) return fail(DSGD_EHIP, "split counts: %s", hipGetErrorString(e));
-  // hrp / ctp: slot offsets of the two streams (a tiled row owns at least one slot in each: an explicit zero when it
-  // has no entry there); crp: the cold ENTRIES before each row (what dsgd_range_nnz reports)
-  std::vector<long long>&hrp = c->h_hrp, &ctp = c->h_ctp, &crp = c->h_crow_ptr;
-  hrp.assign((size_t)n_rows + 1, 0);
-  ctp.assign((size_t)n_rows + 1, 0);
+  std::vector<long long>&hrp = c->h_hrp, &ctp = c->h_ctp;
   ++c->layout_gen;
   c->layout_seen_by_build = false;
-  crp.assign((size_t)n_rows + 1, 0);
-  c->wlong_rows.clear();
-  hrp[0] = 0;
-  ctp[0] = 0;
-  const std::vector<long long>& rp = c->h_row_ptr;
-  const bool has_cold = c->dp > H;
-  for (long long i = 0; i < n_rows; ++i) {
-    const long long len = rp[i + 1] - rp[i], cold = cnt[(size_t)i], hot = len - cold;
-    if (hot > WS_MAXNNZ || cold > WS_MAXNNZ) {   // served whole from the ranked CSR, one wave per row
-      c->wlong_rows.push_back(i);
-      hrp[i + 1] = hrp[i];
-      ctp[i + 1] = ctp[i];
-      crp[i + 1] = crp[i];
-    } else {
-      hrp[i + 1] = hrp[i] + std::max<long long>(hot, 1);
-      ctp[i + 1] = ctp[i] + (has_cold ? std::max<long long>(cold, 1) : 0);
-      crp[i + 1] = crp[i] + cold;
-    }
-  }
-  // (what a long row weighs when row chunks are cut: its own non-zeros plus ~1,300 slots' worth of its wave's waiting --
-  //  0.7 us per long row measured against 75 us for a chunk of ~200 K slots, profiles/r06_fstep_wg_times.txt)
-  c->wlong_weight.assign(c->wlong_rows.size() + 1, 0);
-  for (size_t k = 0; k < c->wlong_rows.size(); ++k) {
-    const long long i = c->wlong_rows[k];
-    c->wlong_weight[k + 1] = c->wlong_weight[k] + (rp[(size_t)i + 1] - rp[(size_t)i]) + 1300;
-  }
+  split_offsets(c->h_row_ptr, cnt, c->dp > H, hrp, ctp, c->h_crow_ptr, c->wlong_rows, c->wlong_weight);
   c->hot_nnz = hrp[n_rows];
   c->coldm_nnz = ctp[n_rows];
   DSGD_TRY(c->d_hcol.alloc((size_t)(c->hot_nnz + WS_PAD)));
@@ -1890,10 +1696,7 @@ static int build_split(dsgd_ctx* c) {
   HIP_TRY(hipMemcpy(c->d_ctiles, hc.wt.data(), sizeof(WTile) * hc.wt.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->d_cmeta, hc.meta16.data(), sizeof(unsigned short) * hc.meta16.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  // The cold words' scale.  A word is emptied by whoever sees it at 2^28; until then sixteen waves can each add the rest of
-  // a tile, at most 2 A at shift 21 (dsgd_cold_bound_kernel).  The finest s <= 21 with
-  // 2^28 + 2^s + 32 * (2^(s - 21) A + 256) < 2^30 keeps every word below the band the kernels refuse (+ 256: half a unit
-  // of rounding for each of a tile's 512 slots).  RCV1-like data has A of a few values: s = 21.
+  // the cold words' scale: the finest that keeps every word below the band the kernels refuse (cold_shift_for)
   c->cold_shift = FIX_SHIFT;
   if (c->n_ctiles > 0 && c->coldm_nnz > 0) {
     DSGD_TRY(c->d_bound.reserve(1));
@@ -1906,9 +1709,7 @@ static int build_split(dsgd_ctx* c) {
     unsigned int amax = 0;
     HIP_TRY(hipMemcpyAsync(&amax, c->d_bound, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    int s = FIX_SHIFT;
-    while (s > 1 && (double)(1LL << 28) + std::ldexp(1.0, s) + 32.0 * (std::ldexp((double)amax, s - FIX_SHIFT) + 256.0) >= (double)(1LL << 30)) --s;
-    c->cold_shift = s;
+    c->cold_shift = cold_shift_for(amax);
   }
   c->fix_scale = std::ldexp(1.0f, c->cold_shift - c->vexp);
   return DSGD_OK;
@@ -2033,41 +1834,6 @@ static StreamSeg make_sseg(long long rb, long long re) {
   s.row_end = re;
   return s;
 }
-// tile and long-row ranges of every worker's row range (wave tiles of whatever stream the mode uses)
-static void locate_segs(dsgd_ctx* c, std::vector<StreamSeg>& segs, long long* max_tiles, long long* max_long,
-                        long long* max_ctiles = nullptr) {
-  const std::vector<int>& wr0 = c->h_wtile_r0;  // n_wtiles + 1 entries (sentinel n_rows)
-  *max_tiles = 1;
-  *max_long = 0;
-  if (max_ctiles) *max_ctiles = 0;
-  for (StreamSeg& s : segs) {
-    // first tile whose rows reach row_begin: the last tile with r0 <= row_begin (it may end before row_begin when a
-    // long row sits in between -- then all its rows are masked) ... one past the last tile with r0 < row_end
-    long long tb = (std::upper_bound(wr0.begin(), wr0.end() - 1, (int)s.row_begin) - wr0.begin()) - 1;
-    if (tb < 0) tb = 0;
-    long long te = std::lower_bound(wr0.begin(), wr0.end() - 1, (int)s.row_end) - wr0.begin();
-    if (te < tb) te = tb;
-    s.tile_begin = tb;
-    s.tile_end = te;
-    *max_tiles = std::max(*max_tiles, te - tb);
-    // the rows that fit no tile: a range of the sorted long-row list, handled by the same kernel (one wave per row)
-    s.long_begin = std::lower_bound(c->wlong_rows.begin(), c->wlong_rows.end(), s.row_begin) - c->wlong_rows.begin();
-    s.long_end = std::lower_bound(c->wlong_rows.begin(), c->wlong_rows.end(), s.row_end) - c->wlong_rows.begin();
-    *max_long = std::max(*max_long, s.long_end - s.long_begin);
-    // the cold stream's tiles of the range, located the same way
-    const std::vector<int>& cr0 = c->h_ctile_r0;   // n_ctiles + 1 entries (sentinel n_rows)
-    s.ctile_begin = s.ctile_end = 0;
-    if (cr0.size() > 1) {
-      long long cb = (std::upper_bound(cr0.begin(), cr0.end() - 1, (int)s.row_begin) - cr0.begin()) - 1;
-      if (cb < 0) cb = 0;
-      long long ce = std::lower_bound(cr0.begin(), cr0.end() - 1, (int)s.row_end) - cr0.begin();
-      if (ce < cb) ce = cb;
-      s.ctile_begin = cb;
-      s.ctile_end = ce;
-    }
-    if (max_ctiles) *max_ctiles = std::max(*max_ctiles, s.ctile_end - s.ctile_begin);
-  }
-}
 static int ensure_part(dsgd_ctx* c, DevBuf<int>& buf, long long* wgs, int* stride, long long need_wgs, int need_cols) {
   if (need_wgs <= *wgs && need_cols <= *stride) return DSGD_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2082,7 +1848,7 @@ static int launch_stream(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs) {
   const int n_workers = (int)row_segs.size();
   std::vector<StreamSeg> segs(row_segs);
   long long max_tiles, max_long, max_ctiles;
-  locate_segs(c, segs, &max_tiles, &max_long, &max_ctiles);
+  locate_segs(c->h_wtile_r0, c->h_ctile_r0, c->wlong_rows, segs, &max_tiles, &max_long, &max_ctiles);
   DSGD_TRY(upload_ssegs(c, segs));
   const int H = std::min(c->hsplit, c->dp);
   const int nc = c->dp - H;                                     // cold columns
@@ -2120,28 +1886,12 @@ static int launch_stream(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs) {
     DSGD_TRY(ensure_part(c, c->d_part, &c->part_wgs, &c->part_stride, (long long)grid.x * grid.y, hg));
     if (cold) DSGD_TRY(ensure_part(c, c->d_partc, &c->partc_wgs, &c->partc_stride, (long long)gridc.x * gridc.y, nc_lds));
   }
-  // Fixed-point scale of THIS launch: a column receives at most one contribution per row, |contribution| <= 2^shift,
-  // and workgroup b of a worker owns the 16-tile groups b, b + grid.x, ... of its tile range (plus its share of the
-  // long rows): with rows(b) <= 2^bits, shift = 30 - bits keeps every 32-bit LDS sum below 2^30.  (Rows between the
-  // first rows of two tiles bound the rows of a tile from above.)
+  // Fixed-point scale of THIS launch: a column receives at most one contribution per row, |contribution| <= 2^shift:
+  // with rows(b) <= 2^bits for every workgroup b (stream_worst_rows), shift = 30 - bits keeps every 32-bit LDS sum below 2^30.
   float main_scale = c->fix_scale;
   if (SCATTER) {
-    const std::vector<int>& wr0 = c->h_wtile_r0;
-    long long worst = 1;
-    std::vector<long long> rows_of((size_t)grid.x);
-    for (const StreamSeg& sg : segs) {
-      std::fill(rows_of.begin(), rows_of.end(), 0);
-      long long g = 0;
-      for (long long t = sg.tile_begin; t < sg.tile_end; t += 16, ++g) {
-        const long long t1 = std::min<long long>(t + 16, sg.tile_end);
-        rows_of[(size_t)(g % grid.x)] += (long long)wr0[(size_t)t1] - (long long)wr0[(size_t)t];
-      }
-      const long long n_long = sg.long_end - sg.long_begin;
-      const long long long_share = (n_long + 16LL * grid.x - 1) / (16LL * grid.x) * 16;
-      for (long long v : rows_of) worst = std::max(worst, v + long_share);
-    }
-    int bits = 0;
-    while ((1LL << bits) < worst) ++bits;
+    const long long worst = stream_worst_rows(segs, c->h_wtile_r0, grid.x);
+    const int bits = rows_bits(worst);
     const int shift0 = std::max(1, std::min(c->max_shift, 30 - bits));   // safe for ANY data: rows x largest value
     int shift = shift0;
     if (c->fix_bound && shift0 < c->max_shift) {
@@ -2158,12 +1908,9 @@ static int launch_stream(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs) {
         unsigned int amax = 0;
         HIP_TRY(hipMemcpyAsync(&amax, c->d_bound, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        int s2 = shift0;
-        const double room = (double)(1LL << 30) - (double)worst;
-        while (s2 < c->max_shift && std::ldexp((double)amax, s2 + 1 - shift0) <= room) ++s2;
         c->bound_segs = segs;
         c->bound_grid = grid.x;
-        c->bound_shift = s2;
+        c->bound_shift = refine_shift(shift0, c->max_shift, amax, worst);
       }
       shift = c->bound_shift;
     }
@@ -2244,90 +1991,12 @@ static int fstep_layout(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
 }
 // the tile tables and chunk records of a configuration (L.share: the chunks' shares of their worker's weight, or empty)
 static int fstep_build(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int n_wg, dsgd_ctx::FstepLayout& L) {
-  const int n_workers = (int)row_segs.size();
-  const std::vector<long long>&hrp = c->h_hrp, &ctp = c->h_ctp;
-  std::vector<WTile> wt, ct;
-  std::vector<FChunk> chunks((size_t)n_workers * (size_t)n_wg);
-  long long worst = 1;
-  for (int k = 0; k < n_workers; ++k) {
-    const long long rb = row_segs[(size_t)k].row_begin, re = row_segs[(size_t)k].row_end;
-    // a row's weight: its slots in the two streams (6 bytes each) plus what every row costs (descriptor share, dcold, coef8);
-    // a LONG row (in neither stream) its own non-zeros plus what its wave waits for it: ~10 us, five tiles' worth (round 6:
-    // the chunks with the most long rows were the launch's last, 0.7-0.9 us per long row)
-    const std::vector<long long>& lrw = c->wlong_weight;   // prefix sums over the long-row list
-    auto W = [&](long long i) {
-      const size_t nl = (size_t)(std::lower_bound(c->wlong_rows.begin(), c->wlong_rows.end(), i) - c->wlong_rows.begin());
-      return hrp[(size_t)i] + ctp[(size_t)i] + 2 * i + lrw[nl];
-    };
-    const long long w0 = W(rb), wtot = W(re) - w0;
-    long long cut = rb;
-    double share_total = 0.0, share_run = 0.0;
-    const bool shares = L.share.size() == (size_t)n_workers * (size_t)n_wg;
-    for (int b = 0; b < n_wg; ++b) share_total += shares ? L.share[(size_t)k * (size_t)n_wg + (size_t)b] : 1.0;
-    for (int b = 0; b < n_wg; ++b) {
-      long long nxt = re;
-      share_run += shares ? L.share[(size_t)k * (size_t)n_wg + (size_t)b] : 1.0;
-      if (b + 1 < n_wg) {
-        const long long target = w0 + (long long)((double)wtot * share_run / share_total);
-        long long lo = cut, hi = re;   // first row i in [cut, re] with W(i) >= target
-        while (lo < hi) {
-          const long long mid = (lo + hi) >> 1;
-          if (W(mid) >= target) hi = mid;
-          else lo = mid + 1;
-        }
-        nxt = lo;
-      }
-      FChunk& ch = chunks[(size_t)k * (size_t)n_wg + (size_t)b];
-      ch.row_begin = (int)cut;
-      ch.row_end = (int)nxt;
-      ch.tile_begin = (int)wt.size();
-      append_wave_tiles(hrp.data(), cut, nxt, wt, WS_MAXROWS);
-      ch.tile_end = (int)wt.size();
-      ch.ctile_begin = (int)ct.size();
-      append_wave_tiles(ctp.data(), cut, nxt, ct, CT_MAXROWS);
-      {
-        // The chunk's cold tiles are walked twice by 16 waves with a stride of 16: 29-35 tiles of ~90 rows left some waves
-        // three tiles and most two (phases A and C: 11 of a workgroup's 70 us).  Smaller tiles in a number just below a
-        // multiple of 16 give every wave the same count (round 6).
-        const size_t c0 = (size_t)ch.ctile_begin;
-        auto waste = [](size_t n) { return n == 0 ? 1.0 : (double)((n + 15) / 16 * 16) / (double)n; };
-        size_t n_best = ct.size() - c0;
-        if (n_best % 16 != 0 && nxt > cut) {
-          int mr_best = CT_MAXROWS;
-          const long long target = (long long)((n_best + 15) / 16 * 16);
-          int mr = (int)std::min<long long>(CT_MAXROWS, std::max<long long>(8, (nxt - cut + target - 1) / target));
-          std::vector<WTile> tmp;
-          for (int tries = 0; tries < 6 && mr >= 8 && waste(n_best) > 1.04; ++tries, --mr) {
-            tmp.clear();
-            append_wave_tiles(ctp.data(), cut, nxt, tmp, mr);
-            if (waste(tmp.size()) < waste(n_best) && tmp.size() <= 3 * (size_t)target) {
-              n_best = tmp.size();
-              mr_best = mr;
-            }
-          }
-          if (mr_best != CT_MAXROWS) {
-            ct.resize(c0);
-            append_wave_tiles(ctp.data(), cut, nxt, ct, mr_best);
-          }
-        }
-      }
-      ch.ctile_end = (int)ct.size();
-      ch.long_begin = (int)(std::lower_bound(c->wlong_rows.begin(), c->wlong_rows.end(), cut) - c->wlong_rows.begin());
-      ch.long_end = (int)(std::lower_bound(c->wlong_rows.begin(), c->wlong_rows.end(), nxt) - c->wlong_rows.begin());
-      worst = std::max(worst, nxt - cut);
-      cut = nxt;
-    }
-  }
-  std::vector<unsigned short> meta, cmeta;
-  wave_tile_meta(hrp.data(), c->h_label.data(), wt, meta);
-  wave_tile_meta(ctp.data(), c->h_label.data(), ct, cmeta);
-  WTile pad;   // (the tables are never empty: a clamped record read must stay inside them)
-  pad.pos0 = 0;
-  pad.r0 = 0;
-  pad.info = 0xffff;
-  if (wt.empty()) wt.push_back(pad);
-  if (ct.empty()) ct.push_back(pad);
-  L.worst_rows = worst;
+  ChunkTables T;
+  cut_row_chunks(row_segs, n_wg, L.share, c->h_hrp, c->h_ctp, c->wlong_rows, c->wlong_weight, c->h_label.data(), T);
+  const std::vector<WTile>&wt = T.wt, &ct = T.ct;
+  const std::vector<unsigned short>&meta = T.meta, &cmeta = T.cmeta;
+  const std::vector<FChunk>& chunks = T.chunks;
+  L.worst_rows = T.worst_rows;
   L.shift = -1;
   // (alloc drops the tables of the cut before)
   hipError_t e = L.d_tiles.try_alloc(wt.size());
@@ -2430,9 +2099,7 @@ static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
   const size_t lds = std::max(lds_a, std::max(lds_b, lds_c));
   // the fixed-point scale of the hot accumulators: one contribution per row and column, |contribution| <= 2^shift, a
   // chunk's rows known -- refined once per configuration by the data (dsgd_fstep_bound_kernel)
-  int bits = 0;
-  while ((1LL << bits) < L->worst_rows) ++bits;
-  const int shift0 = std::max(1, std::min(c->max_shift, 30 - bits));
+  const int shift0 = std::max(1, std::min(c->max_shift, 30 - rows_bits(L->worst_rows)));
   int shift = shift0;
   if (c->fix_bound && shift0 < c->max_shift) {
     if (L->shift < 0) {
@@ -2444,10 +2111,7 @@ static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
       unsigned int amax = 0;
       HIP_TRY(hipMemcpyAsync(&amax, c->d_bound, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(hipStreamSynchronize(c->stream));
-      int s2 = shift0;
-      const double room = (double)(1LL << 30) - (double)L->worst_rows;
-      while (s2 < c->max_shift && std::ldexp((double)amax, s2 + 1 - shift0) <= room) ++s2;
-      L->shift = s2;
+      L->shift = refine_shift(shift0, c->max_shift, amax, L->worst_rows);
     }
     shift = L->shift;
   }

@@ -19,6 +19,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "dsgd_layout_types.hpp"   // (the records and constants the host writes and these kernels read)
+
 #define DSGD_EPS 1e-20f  // ref: math/Sparse.scala:104 (Sparse.epsilon); representable in fp32
 #define DSGD_LDS_FLOATS 40960  // 160 KiB / 4
 
@@ -125,13 +127,6 @@ struct DevScalars {
   float part_nsq[64];
   unsigned int ticket;
   unsigned int pad2;
-};
-
-// one unit of gradient work: worker k processes items [begin, end) -- positions in the resident
-// index list (idx != nullptr) or CSR row numbers themselves (contiguous range)
-struct WorkSeg {
-  long long begin;
-  long long end;
 };
 
 template <typename V>   // V: float, or double for the fp64 mode's Double feature values (dsgd_load_csr_f64)
@@ -452,21 +447,7 @@ __global__ void dsgd_ds_kernel(const unsigned int* __restrict__ cnt, const int* 
 // ones are processed.  (Two earlier generations -- LDS-staged products, then workgroup tiles with a register
 // segmented scan -- are in the git history; profiles/README.md keeps their measurements.)
 
-// Fixed-point gradient accumulation.  Measured on MI355X (tools/microbench3.hip): ds_add_f32 retires
-// 0.31 lanes/clk/CU (188 Gnnz/s chip-wide) while ds_add_u32 runs at the HBM streaming rate
-// (671 Gnnz/s).  The scatter therefore accumulates round(y*x * 2^21 / vmax2) as 32-bit integers in
-// LDS (vmax2 = max|x| rounded up to a power of two, so the scaling is exact; overflow control of the
-// 32-bit accumulators: see w_scatter).  Integer addition is
-// associative: the gradient of a whole-shard batch is bit-reproducible run to run, and exact up to
-// the 2^-22 * vmax2 rounding of each contribution (fp32 atomics round at the ulp of the RUNNING sum).
-constexpr int FIX_SHIFT = 21;
-
-struct StreamSeg {
-  long long row_begin, row_end;    // rows of this worker's batch
-  long long tile_begin, tile_end;  // tiles intersecting [row_begin, row_end)
-  long long long_begin, long_end;  // wave-tile mode: range of the long-row list (rows that fit no tile)
-  long long ctile_begin, ctile_end;  // cold-stream tiles intersecting [row_begin, row_end)
-};
+// (fixed-point gradient accumulation: FIX_SHIFT, and the StreamSeg record of a worker's ranges, in csrc/dsgd_layout_types.hpp)
 
 // the same with per-workgroup partial sums: worker k owns workgroups [k * n_wg, (k + 1) * n_wg) of `part` (main
 // kernel, columns [0, hg)) and [k * n_wgc, (k + 1) * n_wgc) of `partc` (dsgd_cgrad_kernel, columns [hc, hc + nc));
@@ -894,19 +875,7 @@ __device__ __forceinline__ void wave_seg_scan(float& v, int& f) {
 // a per-launch scale that rules out overflow).  The first generation (all columns in one stream, cold weights
 // gathered, returning atomics with a spill rule) is in the git history; profiles/README.md keeps its numbers.
 // Rounding to the fixed-point grid also absorbs the reference's 1e-20 filter on y*x.
-constexpr int WS_SLOTS = 512;
-constexpr int WS_MAXNNZ = WS_SLOTS - 8;
-constexpr int WS_MAXROWS = 254;
-constexpr int WS_PAD = WS_SLOTS + 8;   // padding elements behind col/val
-constexpr int WS_SPILL_AT = 1 << 28;   // cold-stream accumulators (shift 21, returning atomics): spill / panic bands
-constexpr int WS_PANIC_AT = 1 << 30;
-constexpr int WS_COEF_STRIDE = 256;
-
-struct WTile {       // 16 bytes, read with one scalar load
-  long long pos0;    // first slot of the window (multiple of 4)
-  int r0;            // global row of local row 1
-  int info;          // rows in the tile (low 16 bits, signed; -1: unused entry) | slots holding its non-zeros << 16
-};
+// (the WS_* constants and the WTile record: csrc/dsgd_layout_types.hpp)
 
 struct WTables {
   const WTile* __restrict__ tiles;
@@ -1646,10 +1615,7 @@ __global__ void __launch_bounds__(256) dsgd_split_fill_kernel(CsrView m, int hsp
 }
 
 // ---- the cold tile walk ------------------------------------------------------------------------------------
-// Cold tiles: WTile records and 16-bit lane descriptors exactly as the hot stream's (build_wave_tiles on the cold row
-// offsets), at most CT_MAXROWS rows per tile: cold rows hold ~6 entries, a 512-slot tile ~90 rows, and the gradient
-// kernel keeps a tile's gate coefficients as two bytes per lane.
-constexpr int CT_MAXROWS = 128;
+// (cold tiles and CT_MAXROWS: csrc/dsgd_layout_types.hpp)
 constexpr int CT_STRIP = 256;        // floats per wave: [0, CT_MAXROWS + 2) by local row, [192, 256) per-lane dummy slots
 constexpr int CT_DUMMY = 192;
 
