@@ -33,11 +33,9 @@
 #pragma once
 
 constexpr int CS_THREADS = 512;     // 8 waves, two per SIMD (<= 256 VGPRs): one or two slots per lane and register set, two sets
-constexpr int CS_THREADS_NARROW = 256;   // (tuning runs: DSGD_CS_NT=256)
 constexpr int CS_L = 16;            // entries per slot
 constexpr int CS_MAX_G = 16;        // slices = workgroups
-constexpr int CS_MAX_K = 8;         // hosted workers
-constexpr int CS_MAX_SLOTS = 1024;   // per (step, slice); also the most rows of a step
+// (CS_THREADS_NARROW, CS_MAX_K, CS_MAX_SLOTS, cs_lds_words, cs_req_lds_words: csrc/dsgd_limits.hpp)
 constexpr int CS_XSTRIDE = CS_MAX_SLOTS + 64;           // granules per (parity, slice) of the exchange buffer: [row] partial x.w, [CS_MAX_SLOTS] share of w . ds
 constexpr unsigned int CS_POLL_LIMIT = 1u << 18;        // polls of one granule set before the launch is given up
 constexpr int CS_MAX_CLT = 8;                           // listed columns per lane: a step may touch 4,096 columns of a slice
@@ -80,17 +78,6 @@ struct CsArgs {
   int gate_words;
   int test_skip_publish;            // TEST BUILDS ONLY (DSGD_TEST_COLLECTIVE_SEAM): slice 1 dies at this step of the launch (1-based; 0: never)
 };
-
-__host__ __device__ constexpr int cs_lds_words(int dp, int G, int K) {
-  return (2 + K) * ((((dp + G - 1) / G) + 4) & ~3) + 2 * CS_MAX_SLOTS + 32;   // (a slice is padded by 1 .. 4 columns)
-}
-
-// a per-request launch: the builder's scratch sits where the accumulators, partial dots and coefficients go afterwards
-__host__ __device__ constexpr int cs_req_lds_words(int dp, int G, int K) {
-  const int sp = (((dp + G - 1) / G) + 4) & ~3;
-  const int rest = K * sp + 2 * CS_MAX_SLOTS;
-  return 2 * sp + (rest > 7000 ? rest : 7000) + 32;   // 7000 >= CS_BUILD_WORDS (static_assert below)
-}
 
 template <int SPL, int CLT>
 struct CsSet {              // the slots of one step, as loaded (nothing is computed on them before their step runs)

@@ -649,7 +649,7 @@ int dsgd_sync_steps_f64(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const in
   DSGD_TRY(rp64_check_flat(c, idx, n_idx, offsets, n_steps, K, true));
   DSGD_TRY(prepare_layout(c));
   const bool v64 = c->d_val64 != nullptr;
-  if (c->rp64_fused) DSGD_TRY(rp64_fused_cap(c, v64));
+  if (c->k.rp64_fused) DSGD_TRY(rp64_fused_cap(c, v64));
   DSGD_TRY(rp64_ensure(c, K));
   DSGD_TRY(rp64_steps_ensure(c, n_lists, n_steps));
   DSGD_TRY(reset_counters(c));
@@ -670,7 +670,7 @@ int dsgd_sync_steps_f64(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const in
   }
   HIP_TRY(hipMemcpyAsync(c->d_rp64_ssegs, c->pin_segs.p, sizeof(WorkSeg) * (size_t)n_lists, hipMemcpyHostToDevice, c->stream));
   DSGD_TRY(pin_sent(c, c->pin_segs));
-  const long long fused_max = c->rp64_fused ? (long long)c->rp64_occ[v64 ? 1 : 0] * c->n_cu : 0;
+  const long long fused_max = c->k.rp64_fused ? (long long)c->rp64_occ[v64 ? 1 : 0] * c->n_cu : 0;
   // every step's word of `cum` starts as all ones: a step that ran as a whole overwrites its word with the call's running
   // n_active (the fused kernel itself; for the two launches a copy on the stream, which is needed only where the counts are
   // asked for or fused launches share the call)
@@ -710,7 +710,7 @@ int dsgd_sync_steps_f64(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const in
       }
       DSGD_TRY(rp64_launched(rp64_enqueue_grad(c, s)));
       DSGD_TRY(rp64_launched(rp64_enqueue_finish(c, s)));
-      if (active_per_step_out || c->rp64_fused)
+      if (active_per_step_out || c->k.rp64_fused)
         HIP_TRY(hipMemcpyAsync(c->d_rp64_cum + t, &c->d_sc->n_active, sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
       ++n_pairs;
     }
@@ -928,7 +928,9 @@ static int plan_run64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long
     HIP_TRY(hipStreamWaitEvent(c->stream, p->built_ev, 0));
     p->built_pending = false;
   }
-  if (!(p->cs_ok && p->cs_layout == c->layout_gen)) return cs64_refused(c);
+  // (route_plan also asks for no communicator, which the line this replaced did not: every caller has refused one by here --
+  //  refuse_fp64_comm in the plan entry points, REQ_F64_RANKS ahead of sync_step64 -- so the condition is the old one)
+  if (plan_route(c, p) != PLAN_CS64) return cs64_refused(c);
   if (step_end > step_begin) DSGD_TRY(launch_cs64(c, p, step_begin, step_end, lr, async, delta));
   c->pending_samples += p->offsets[step_end * p->n_workers] - p->offsets[step_begin * p->n_workers];
   return DSGD_OK;

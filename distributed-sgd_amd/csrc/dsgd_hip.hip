@@ -123,6 +123,7 @@ static bool available() {
 #include "dsgd_plan_cache.hpp"   // (host only: the device blocks plans take and hand back, and a plan's hold on one)
 #include "dsgd_plan_check.hpp"   // (host only: a plan's lists against the rows loaded now)
 #include "dsgd_layout_host.hpp"  // (host only: the arithmetic behind every table the gradient kernels read)
+#include "dsgd_route.hpp"        // (host only: the switches, and which kernel family serves a call)
 #include "dsgd_kernels.hpp"
 #include "dsgd_batch.hpp"
 #include "dsgd_cs.hpp"
@@ -205,6 +206,7 @@ struct FusedArgs {
 
 struct dsgd_ctx {
   dsgd_config cfg{};
+  Knobs k;     // every DSGD_* switch, read once by dsgd_create (csrc/dsgd_route.hpp)
   int dp = 0;  // D + 1
   std::mutex mu;
   hipStream_t stream = nullptr;
@@ -219,10 +221,6 @@ struct dsgd_ctx {
   DevBuf<int> d_perm;   // key  -> rank
   bool layout_ready = false;
   int hw_eval = DSGD_LDS_FLOATS;
-  long long stream_min = 131072;  // row ranges with at least this many rows use the streaming kernels (DSGD_STREAM_MIN).  Four
-                                  //   launches of the split streams cost ~50 us whatever the range; the row-wise kernel + reduce
-                                  //   take 37 us for 18,519 rows and 57 us for 80,000 (streaming: 49 / 63 us;
-                                  //   profiles/r04_stream_min.txt)
   // nnz-streaming kernels (contiguous row ranges)
   DevBuf<StreamSeg> d_ssegs;
   std::vector<StreamSeg> ssegs_last;
@@ -237,24 +235,12 @@ struct dsgd_ctx {
                                         //   column-list layout stamped is stale from the load on, not from the next ranking on)
   long long load_gen = 0;               // bumped by every successful dsgd_load_csr / _f64 (plan_revalidate)
   bool layout_seen_by_build = false;    // the build stream is ordered behind the kernels that wrote the current split streams
-  bool cs_enable = true;                // DSGD_CS=0: small steps of resident plans through the row-parallel kernels
-  int cs_g = 0;                         // DSGD_CS_G: slices (8 or 16; 0 = 8 up to four hosted workers, 16 beyond)
-  long long cs_max_mb = 8192;           // DSGD_CS_MAX_MB: largest column-slice layout of one plan (device-built; the host
-                                        //   builder of DSGD_CS_HOST_LAYOUT=1 holds a copy of it in host memory as well)
-  int cs_nt = 0;                        // DSGD_CS_NT=256: tuning runs with 256 lanes per slice where a plan's steps fit them
   unsigned int cs_tag0 = 0;             // column-slice steps launched so far (the exchange granules' tags run on)
   DevBuf<float> d_cs_w;              // the weights slice-major while cs_w_G != 0: then d_w is STALE -- every entry point that
   DevBuf<float> d_cs_ds;             //   is not a column-slice launch converts back first (bind); dimSparsity likewise (a copy)
   int cs_w_G = 0;                       // slices of the slice-major state (0: the weights are in d_w, rank order)
   DevBuf<unsigned long long> d_cs_x; // exchange buffer of dsgd_cs_step_kernel: [2][CS_MAX_G][CS_XSTRIDE] granules
   DevBuf<unsigned int> d_cs_sync;    // its arrival counter and abort word
-  bool cs_host_layout = false;          // DSGD_CS_HOST_LAYOUT=1: a plan's slices laid out by the host (rounds 1-4; kept as the cross-check)
-  bool cs_req = false;                  // DSGD_CS_REQ=1: per-request steps of the reference's sizes through dsgd_cs_request_kernel.  OFF by
-                                        //   default: a slice's workgroup lays the step out before it runs it, one dependent trip to
-                                        //   memory per row and wave -- measured 126 us per 3 x 100 request against 40 us through the
-                                        //   row-parallel kernels (profiles/r05_probe_v1.json); the kernel is kept, tested, and is what
-                                        //   the abort-path test drives
-  int cs_test_skip = 0;                 // (test builds: DSGD_TEST_CS_SKIP_PUBLISH -- slice 1 goes silent from this step of a launch on)
   DevBuf<unsigned int> d_cs_max;     // the layout kernels' maxima and flags (4 words) ...
   HostBuf<unsigned int> h_cs_max;     // ... and where pass 1's come back to (pinned)
   hipStream_t build_stream = nullptr;   // a plan's set-up (uploads, layout kernels) runs here, beside the launch stream
@@ -272,9 +258,6 @@ struct dsgd_ctx {
     DevBuf<unsigned short> cl;
     int G = 0;
   } req_layout;
-  bool vt_enable = true;                // DSGD_VT=0: index-list steps of resident plans through dsgd_mb_grad_kernel
-  long long vt_pack_mb = 2048;          // DSGD_VT_PACK_MB: plans whose packed copy fits get one (0: descriptors only)
-  int vt_tpw = 1;                       // DSGD_VT_TPW: virtual tiles per wave the grid is sized for (measured: 1 beats 2-4 up to B = 65,536)
   std::vector<signed char> h_label;
   // wave tiles over d_hcol/d_hval
   DevBuf<WTile> d_wtiles;
@@ -287,7 +270,7 @@ struct dsgd_ctx {
   DevBuf<int> d_part;                // per-workgroup partial sums of the wseg gradient kernel: part_wgs x part_stride
   long long part_wgs = 0;
   int part_stride = 0;
-  int hsplit = (DSGD_LDS_FLOATS - 16 * WS_COEF_STRIDE - 4 - 64) / 2;         // hot ranks: 2 * hsplit words of LDS
+  int hsplit = HSPLIT_MAX;              // hot ranks: 2 * hsplit words of LDS (DSGD_HSPLIT, clamped and aligned by dsgd_create)
   DevBuf<unsigned short> d_hcol;     // hot stream (16-bit ranks < hsplit), WS_PAD elements of padding
   DevBuf<float> d_hval;
   DevBuf<long long> d_hrow_ptr;      // n_rows + 1 (rows of the long list: empty)
@@ -320,7 +303,6 @@ struct dsgd_ctx {
   unsigned bound_grid = 0;
   int bound_shift = 0;
   DevBuf<unsigned int> d_bound;
-  int max_shift = FIX_SHIFT;     // DSGD_FIX_SHIFT: cap of the per-launch fixed-point shift of the split layout
   // Row chunks (csrc/dsgd_fstep.hpp): the whole gradient of a row range in ONE launch.  Per (row ranges, workgroups per
   // worker) configuration the host cuts the ranges into chunks balanced by stream bytes and lays out wave tiles of both
   // streams that end at the chunk boundaries; a few configurations stay cached (a fit alternates train steps only; the
@@ -347,16 +329,7 @@ struct dsgd_ctx {
   };
   std::vector<FstepLayout> fstep_cache;
   unsigned long long fstep_clock = 0;
-  bool fstep_enable = true;          // DSGD_FSTEP=0: row ranges through the three streaming launches / the row-wise kernel
-  bool fstep_rebalance = false;      // DSGD_FSTEP_REBALANCE=1: the chunks re-cut by their workgroups' measured durations (measured: 98.4 ->
-                                     //   97.5 us at N = 804,414, nothing at 2 M / 6.7 M rows, and two layout rebuilds per configuration --
-                                     //   which workgroup is slow is not a stable property of its chunk: OFF, profiles/r06_fstep_wg_times.txt)
-  int last_fstep_rebalances = 0;     // ... how often the configuration of the last chunked launch has been re-cut (dsgd_tuning_info)
-  long long fstep_min = 65536;       // DSGD_FSTEP_MIN / DSGD_FSTEP_MAX: row ranges of this many rows in total take the chunked launch
-  long long fstep_max = 1LL << 31;   //   (measured, whole-split steps, us: 80 K rows 56 -> 50-54, 643 K 118 -> 105, 1.6 M 213 -> 199,
-                                     //    3.2 M 374 -> 343, 6.7 M 699 -> 663; at 18.5 K rows the row-wise kernel stays ahead: 37 vs 35-41)
-  long long fstep_rows = 512;        // DSGD_FSTEP_ROWS: a chunk holds at least this many rows (fewer workgroups for small ranges:
-                                     //   every workgroup moves 378 KB of LDS tiles in and out whatever its chunk)
+  int last_fstep_rebalances = 0;     // how often the configuration of the last chunked launch has been re-cut (dsgd_tuning_info)
   // Column lists (csrc/dsgd_tcol.hpp): whole-split steps of 10^3 .. 10^5 rows as dot + column-wise gradient + reduce, no
   // partials.  Per (row ranges) configuration the device sorts the ranges' entries by (worker, column) once; a few
   // configurations stay cached.
@@ -376,17 +349,7 @@ struct dsgd_ctx {
   };
   std::vector<TcolLayout> tcol_cache;
   unsigned long long tcol_clock = 0;
-  int tcol_miss_streak = 0;          // layouts built in a row without one being used again
-  int tcol_cooldown = 0;             // steps the column lists still sit out after such a streak (then they try again)
-  bool tcol_enable = true;           // DSGD_TCOL=0: such ranges through the row-wise kernel
-  long long tcol_min = 512;          // DSGD_TCOL_MIN / DSGD_TCOL_MAX: row ranges of this many rows in total take the column lists
-  long long tcol_max = 98303;        //   (above: row chunks, dsgd_fstep.hpp.  Measured, whole-split steps, us, row-wise / chunks / columns:
-                                     //    4,800 rows 22.7 / 27.4 / 18.1; 18,519: 30.9 / 34.8 / 20.6; 40,000: 36.6 / 42.7 / 31.7; 80,441: 49 / 48 / 42.8;
-                                     //    160,000: 73 / 57.5 / 73; 320,000: 117 / 65 / 162 -- profiles/r05_tcol_probe_*.json)
-  long long tcol_max_nnz = 4500000;  // DSGD_TCOL_MAX_NNZ: ... and of at most this many non-zeros where row chunks can take over (round 6: the
-                                     //   crossover is a matter of ENTRIES -- 80 K rows of 150 non-zeros: columns 67.8 us, chunks 51.7; of 40: 33.3 / 37.8;
-                                     //   RCV1-like rows of 75: columns win up to ~60 K rows = 4.5 M entries, profiles/r06_dispatch_table.txt)
-  int tcol_share = 0;                // DSGD_TCOL_SHARE: entries per workgroup of the gradient kernel (0: entries / CUs, within [1024, 8192])
+  TcolGate tcol_gate;                // their back-off from callers that never repeat a configuration
   bool fused_apply_pending = false;
   FusedArgs fused_args{};
   DevBuf<float> d_redpart;    // per-block partial sums of w.ds and |w|^2 of the fused reduce + apply kernel
@@ -409,7 +372,6 @@ struct dsgd_ctx {
   DevBuf<float> d_pred;     // dsgd_forward's predictions (grown on demand)
   DevBuf<signed char> d_pred8;          // dsgd_predict_ranges' predictions (grown on demand) ...
   DevBuf<long long> d_pred_tab;         // ... its range table (off[K + 1], begin[K]) followed by the tallies [K][3], K at its maximum
-  bool fix_bound = true;         // DSGD_FIX_BOUND=0: keep the data-independent bound (rows per workgroup x largest value)
   DevBuf<float> d_gsum;  // dp (all-reduce buffer / sum over hosted workers)
   DevBuf<float> d_tmp;   // dp scratch (ranked order)
   DevBuf<float> d_io;    // dp staging for vectors crossing the API in key order
@@ -419,11 +381,6 @@ struct dsgd_ctx {
   // n_active is read as a DIFFERENCE against the value the host last saw, so the request needs no memset either
   HostBuf<int> h_req;                   // host-mapped index lists of a per-request step (REQ_MAPPED_ITEMS entries; the kernels read .dev())
   const int* cur_idx = nullptr;           // where stage_lists put the lists of the request in flight
-  bool req_mapped = true;                 // DSGD_REQ_MAPPED=0: always the copy on the stream
-  bool req_spin = true;                   // DSGD_REQ_SPIN=0: wait for the stream instead of polling the mailbox
-  bool req_plan = false;                  // DSGD_REQ_PLAN=1: one-worker requests of <= 192 rows through the one-workgroup kernel (its
-                                          //   launch re-derives s in fp64 and sets up 147 KB of LDS for ONE step: 37 us per request at the
-                                          //   C ABI against 32 us through the row-parallel kernels -- profiles/r04_boundary_latency.json)
   HostBuf<unsigned long long> h_mail;   // host-mapped: {n_active, err, sequence number of the request that wrote them, -}
   unsigned long long mail_seq = 0;        // requests answered through the mailbox so far
   bool ctr_known = false;                 // the host knows the device's n_active (ctr_last) and that err is clear
@@ -457,9 +414,7 @@ struct dsgd_ctx {
   // small-batch plan kernel (one persistent workgroup): cold strip and the multi-worker sum buffer
   DevBuf<unsigned long long> d_tprof;   // DSGD_PLAN_PROF=1: phase cycle counters of dsgd_plan_kernel (tuning runs)
   DevBuf<float> d_plan_gcold;
-  bool plan_kernel = true;     // DSGD_PLAN_KERNEL=0: the multi-launch small-batch path
   int hog_hl = HOG_HL, hog_wl = HOG_WL;   // LDS-resident ranks of the Hogwild engine (accumulators / weight copy)
-  long long plan_max_rows = 2048;   // steps with more rows in total use the multi-workgroup kernels
   int hog_workers = 0;      // capacity of the per-worker buffers
   int hog_n = 0, hog_batch = 0, hog_bug = 0;   // the running configuration
   float hog_lr = 0.0f;
@@ -543,7 +498,6 @@ struct dsgd_ctx {
   unsigned long long rp64_wait_ticks = 0;
   int rp64_occ[2] = {0, 0};               // [0] dsgd_rp64_step_kernel, [1] dsgd_rp64v_step_kernel
   bool rp64_occ_known[2] = {false, false};
-  bool rp64_fused = RP64_FUSED_DEFAULT;   // DSGD_RP64_FUSED
   // Sparse values at the boundary (csrc/dsgd_sparse.hpp): the compaction's output in host-mapped memory the kernel writes in
   // place ([2 words: count, gave up][dp keys][dp values of 8 bytes]), its scan state, and the staged pairs of a sparse setter
   HostBuf<unsigned long long> h_sp_out;
@@ -557,6 +511,22 @@ struct dsgd_ctx {
   std::vector<int32_t> row_len;             // the loaded rows' lengths (the bound on an asynchronous step's delta)
 };
 
+// what the route functions of csrc/dsgd_route.hpp need from the context
+static RouteFacts route_facts(const dsgd_ctx* c) {
+  RouteFacts f;
+  f.dp = c->dp;
+  f.n_rows = c->n_rows;
+  f.n_cu = c->n_cu;
+  f.hsplit = c->hsplit;
+  f.cold_col16 = c->cold_col16;
+  f.coldm_nnz = c->coldm_nnz;
+  f.comm = c->comm != nullptr;
+  f.prof = c->prof;
+  f.fp64 = c->fp64;
+  f.val64 = (bool)c->d_val64;
+  f.async_running = c->async_running;
+  return f;
+}
 static int check_ctx(dsgd_ctx* c) {
   if (!c) return fail(DSGD_EINVAL, "null context");
   return DSGD_OK;
@@ -860,7 +830,7 @@ static int vt_build_impl(dsgd_ctx* c, dsgd_plan* p) {
   if ((long long)c->h_ccol.size() != c->coldm_nnz) return DSGD_OK;
   const VtStreams m{c->n_rows, c->h_hrp.data(), c->h_ctp.data(), c->h_crow_ptr.data(), c->h_row_ptr.data(), c->h_label.data(), c->h_ccol.data()};
   VtTables T;
-  const bool inside = vt_tables(p->h_idx.data(), p->offsets.data(), p->n_steps, p->n_workers, c->n_cu, c->vt_tpw, m, T);
+  const bool inside = vt_tables(p->h_idx.data(), p->offsets.data(), p->n_steps, p->n_workers, c->n_cu, c->k.vt_tpw, m, T);
   p->vt_off.swap(T.vt_off);
   if (!inside) return DSGD_OK;   // (the mb kernel reports the bad index)
   p->vt_grid.swap(T.grid);
@@ -886,7 +856,7 @@ static int vt_build_impl(dsgd_ctx* c, dsgd_plan* p) {
     (void)hipGetLastError();
     mem_free = 0;
   }
-  if (n_tiles > 0 && n_tiles * 4096 <= c->vt_pack_mb * (1LL << 20) && (size_t)n_tiles * 4096 <= mem_free / 4 &&
+  if (n_tiles > 0 && n_tiles * 4096 <= ((long long)c->k.vt_pack_mb << 20) && (size_t)n_tiles * 4096 <= mem_free / 4 &&
       p->d_vt_packed.try_alloc((size_t)n_tiles * (4096 / sizeof(uint4))) != hipSuccess)
     (void)hipGetLastError();      // (no room for the copy: the plan runs from its descriptors)
   if (p->d_vt_packed) {
@@ -1025,16 +995,6 @@ static int ensure_cs_max(dsgd_ctx* c) {
   DSGD_TRY(c->h_cs_max.reserve(4));
   return DSGD_OK;
 }
-// slices for K hosted workers: 8 up to four (wider slices, fewer peers in the exchange), 16 beyond or for a wide model
-static int cs_pick_G(const dsgd_ctx* c, int K, bool request) {
-  auto fits = [&](int G) {
-    const int words = request ? cs_req_lds_words(c->dp, G, K) : cs_lds_words(c->dp, G, K);
-    return c->dp >= 4 * G && words <= DSGD_LDS_FLOATS && (c->dp + G - 1) / G <= 65536;
-  };
-  int G = c->cs_g ? c->cs_g : (K <= 4 ? 8 : 16);
-  if (!c->cs_g && G == 8 && !fits(8)) G = 16;
-  return fits(G) ? G : 0;
-}
 
 // A plan's column slices laid out by the device (csrc/dsgd_cs.hpp: dsgd_cs_layout_kernel), on the build stream: pass 1
 // counts (one read-back of four words: the strides), pass 2 fills.  Returns 1 for a soft failure (memory).
@@ -1051,7 +1011,7 @@ static int cs_build_device_impl(dsgd_ctx* c, dsgd_plan* p) {
   if (K > CS_MAX_K || p->max_step_rows > CS_MAX_SLOTS) return DSGD_OK;
   // (fp64: always CS64_G slices, the fp64 kernel's own LDS budget)
   const int G = c->fp64 ? ((K <= CS64_MAX_K && cs64_lds_bytes(c->dp, K) <= CS64_LDS_MAX && c->dp >= 4 * CS64_G) ? CS64_G : 0)
-                        : cs_pick_G(c, K, false);
+                        : cs_pick_G(c->k, route_facts(c), K, false);
   if (!G) return DSGD_OK;
   if (n_steps * (long long)G > 0x7fffffffLL) return DSGD_OK;
   if (!p->idx_trusted) {
@@ -1094,7 +1054,7 @@ static int cs_build_device_impl(dsgd_ctx* c, dsgd_plan* p) {
   const int cl_stride = (int)((max_cols + CS_THREADS - 1) / CS_THREADS * CS_THREADS);
   const long long cells = (long long)G * n_steps;
   const long long bytes = cells * ((long long)slot_stride * (4 + CS_L * 2 + CS_L * 4) + (long long)row_stride * 2 + (long long)cl_stride * 2 + 8);
-  if (bytes > c->cs_max_mb * (1LL << 20)) return DSGD_OK;
+  if (bytes > ((long long)c->k.cs_max_mb << 20)) return DSGD_OK;
   // (a slot's CS_L columns are 16-bit, CS_L / 8 uint4; its values CS_L / 4 float4.  After a failure the blocks taken so
   // far stay with the plan: cs_build's cs_free hands them back)
   PlanCache& pc = c->plan_cache;
@@ -1116,7 +1076,7 @@ static int cs_build_device_impl(dsgd_ctx* c, dsgd_plan* p) {
   hipLaunchKernelGGL(dsgd_cs_layout_kernel<true>, dim3((unsigned)(n_steps * G)), dim3(CS_THREADS), 0, bs, ba);
   HIP_TRY(hipGetLastError());
   p->cs_G = G;
-  p->cs_nt = (c->cs_nt == CS_THREADS_NARROW && narrow_fits && !c->fp64) ? CS_THREADS_NARROW : CS_THREADS;
+  p->cs_nt = (c->k.cs_nt == CS_THREADS_NARROW && narrow_fits && !c->fp64) ? CS_THREADS_NARROW : CS_THREADS;
   p->cs_spl = (p->cs_nt == CS_THREADS && one_fits) ? 1 : 2;
   p->cs_slot_stride = slot_stride;
   p->cs_row_stride = row_stride;
@@ -1136,9 +1096,8 @@ static int cs_build_impl(dsgd_ctx* c, dsgd_plan* p) {
   const int K = p->n_workers;
   const long long n_steps = p->n_steps, n_lists = n_steps * K;
   if (K > CS_MAX_K || p->max_step_rows > CS_MAX_SLOTS) return DSGD_OK;
-  int G = c->cs_g ? c->cs_g : (K <= 4 ? 8 : 16);
-  if (!c->cs_g && G == 8 && cs_lds_words(c->dp, 8, K) > DSGD_LDS_FLOATS) G = 16;   // (a wide model: narrower slices)
-  if (c->dp < 4 * G || cs_lds_words(c->dp, G, K) > DSGD_LDS_FLOATS || (c->dp + G - 1) / G > 65536) return DSGD_OK;
+  const int G = cs_pick_G(c->k, route_facts(c), K, false);   // (a wide model: narrower slices)
+  if (!G) return DSGD_OK;
   DSGD_TRY(plan_host_idx(c, p));
   if (c->h_row_ptr.size() != (size_t)c->n_rows + 1 || (long long)p->h_idx.size() != p->offsets[n_lists]) return DSGD_OK;
   const long long N = p->offsets[n_lists];
@@ -1213,7 +1172,7 @@ static int cs_build_impl(dsgd_ctx* c, dsgd_plan* p) {
   const int cl_stride = (int)((max_cols + CS_THREADS - 1) / CS_THREADS * CS_THREADS);
   const long long cells = (long long)G * n_steps;
   const long long bytes = cells * ((long long)slot_stride * (4 + CS_L * 2 + CS_L * 4) + (long long)row_stride * 2 + (long long)cl_stride * 2 + 8);
-  if (bytes > c->cs_max_mb * (1LL << 20)) return DSGD_OK;
+  if (bytes > ((long long)c->k.cs_max_mb << 20)) return DSGD_OK;
   // pass 2: the layout
   std::vector<CsHdr> hdr((size_t)cells);
   std::vector<unsigned int> meta((size_t)(cells * slot_stride), 0u);
@@ -1285,7 +1244,7 @@ static int cs_build_impl(dsgd_ctx* c, dsgd_plan* p) {
   CS_SOFT(hipMemcpy(p->d_cs_val, val.data(), sizeof(float) * val.size(), hipMemcpyHostToDevice));
   if (ensure_cs_exchange(c)) return 1;
   p->cs_G = G;
-  p->cs_nt = (c->cs_nt == CS_THREADS_NARROW && narrow_fits) ? CS_THREADS_NARROW : CS_THREADS;
+  p->cs_nt = (c->k.cs_nt == CS_THREADS_NARROW && narrow_fits) ? CS_THREADS_NARROW : CS_THREADS;
   p->cs_spl = (p->cs_nt == CS_THREADS && one_fits) ? 1 : 2;
   p->cs_slot_stride = slot_stride;
   p->cs_row_stride = row_stride;
@@ -1297,7 +1256,7 @@ static int cs_build_impl(dsgd_ctx* c, dsgd_plan* p) {
 static int cs_build(dsgd_ctx* c, dsgd_plan* p) {
   int rc;
   try {
-    rc = (c->cs_host_layout && !c->fp64) ? cs_build_impl(c, p) : cs_build_device_impl(c, p);
+    rc = (c->k.cs_host_layout && !c->fp64) ? cs_build_impl(c, p) : cs_build_device_impl(c, p);
   } catch (const std::bad_alloc&) {   // (nothing may unwind across the C ABI)
     rc = 1;
   }
@@ -1348,7 +1307,7 @@ static void cs_common_args(dsgd_ctx* c, CsArgs& a, int G, int K, float lr) {
   a.gate_rec = nullptr;
   a.s_rec = nullptr;
   a.gate_words = 0;
-  a.test_skip_publish = c->cs_test_skip;
+  a.test_skip_publish = c->k.cs_test_skip;
 }
 static void cs_after_launch(dsgd_ctx* c, int shift) {
   c->last_grad_kernel = "dsgd_cs_step_kernel";
@@ -1396,25 +1355,9 @@ static int launch_cs(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long 
   return DSGD_OK;
 }
 
-// A per-request step of the reference's sizes (<= CS_MAX_K hosted workers, <= CS_MAX_SLOTS rows): the lists staged by
-// stage_lists (c->cur_idx, c->d_segs) go through dsgd_cs_request_kernel -- every slice lays its cell out and runs the step,
-// ONE launch.  Returns 1 when the path is not available (the caller takes the row-parallel kernels).
-static int cs_request_ok(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int K, int* G_out) {
-  if (!c->cs_enable || !c->cs_req || c->comm || c->prof || K > CS_MAX_K) return 1;
-  long long tot = 0;
-  for (int k = 0; k < K; ++k) {
-    if (n_per_worker[k] <= 0 || !idx_per_worker[k]) return 1;   // (stage_lists reports it)
-    tot += n_per_worker[k];
-  }
-  if (tot > CS_MAX_SLOTS) return 1;
-  for (int k = 0; k < K; ++k)
-    for (int64_t t = 0; t < n_per_worker[k]; ++t)
-      if (idx_per_worker[k][t] < 0 || idx_per_worker[k][t] >= c->n_rows) return 1;   // (the row-wise kernel reports the bad index)
-  const int G = cs_pick_G(c, K, true);
-  if (!G) return 1;
-  *G_out = G;
-  return DSGD_OK;
-}
+// A per-request step of the reference's sizes (<= CS_MAX_K hosted workers, <= CS_MAX_SLOTS rows; route_request): the lists staged
+// by stage_lists (c->cur_idx, c->d_segs) go through dsgd_cs_request_kernel -- every slice lays its cell out and runs the step,
+// ONE launch.
 static int launch_cs_request(dsgd_ctx* c, int G, int K, long long worst_list, float lr) {
   dsgd_ctx::ReqLayout& L = c->req_layout;
   constexpr int SLOT_STRIDE = CS_MAX_SLOTS, ROW_STRIDE = CS_MAX_SLOTS + 64, CL_STRIDE = CS_MAX_CLT * CS_THREADS;
@@ -1679,7 +1622,7 @@ static int build_split(dsgd_ctx* c) {
     HIP_TRY(hipGetLastError());
   }
   c->h_ccol.clear();
-  if (c->cold_col16 && c->vt_enable && c->coldm_nnz > 0) {   // (75 MB for the 8.4 M-row shard)
+  if (c->cold_col16 && c->k.vt_enable && c->coldm_nnz > 0) {   // (75 MB for the 8.4 M-row shard)
     c->h_ccol.resize((size_t)c->coldm_nnz);
     HIP_TRY(hipMemcpyAsync(c->h_ccol.data(), c->d_ccol, sizeof(unsigned short) * (size_t)c->coldm_nnz, hipMemcpyDeviceToHost, c->stream));
   }
@@ -1892,9 +1835,9 @@ static int launch_stream(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs) {
   if (SCATTER) {
     const long long worst = stream_worst_rows(segs, c->h_wtile_r0, grid.x);
     const int bits = rows_bits(worst);
-    const int shift0 = std::max(1, std::min(c->max_shift, 30 - bits));   // safe for ANY data: rows x largest value
+    const int shift0 = std::max(1, std::min(c->k.max_shift, 30 - bits));   // safe for ANY data: rows x largest value
     int shift = shift0;
-    if (c->fix_bound && shift0 < c->max_shift) {
+    if (c->k.fix_bound && shift0 < c->k.max_shift) {
       // data-dependent refinement (dsgd_wseg_bound_kernel): measured once per (ranges, grid) configuration
       const bool hit = c->bound_grid == grid.x && c->bound_segs.size() == segs.size() &&
                        memcmp(c->bound_segs.data(), segs.data(), sizeof(StreamSeg) * segs.size()) == 0;
@@ -1910,7 +1853,7 @@ static int launch_stream(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->bound_segs = segs;
         c->bound_grid = grid.x;
-        c->bound_shift = refine_shift(shift0, c->max_shift, amax, worst);
+        c->bound_shift = refine_shift(shift0, c->k.max_shift, amax, worst);
       }
       shift = c->bound_shift;
     }
@@ -1952,13 +1895,6 @@ static void fstep_drop_all(dsgd_ctx* c) {   // (the split streams are about to c
   if (c->fstep_cache.empty()) return;
   (void)hipStreamSynchronize(c->stream);
   c->fstep_cache.clear();
-}
-// can the chunked launch serve this context's layout at all?  (16-bit cold ids, every cold column inside the LDS tile)
-static bool fstep_possible(const dsgd_ctx* c) {
-  const int H = std::min(c->hsplit, c->dp);
-  const int nc = c->dp - H;
-  const int nc_lds = std::min(nc, DSGD_LDS_FLOATS - 16 * CT_STRIP - 64 - 4);
-  return c->fstep_enable && nc > 0 && nc <= nc_lds && c->cold_col16 && c->coldm_nnz > 0 && c->n_rows < (1LL << 31);
 }
 static int fstep_build(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int n_wg, dsgd_ctx::FstepLayout& L);
 static int fstep_layout(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int n_wg, dsgd_ctx::FstepLayout** out) {
@@ -2029,7 +1965,7 @@ static int fstep_build(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int 
 // the same workgroups every time (profiles/r06_fstep_wg_times.txt).  Integer sums: the re-cut changes no bit.
 constexpr int FSTEP_CAL = 24;
 static int fstep_maybe_rebalance(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, dsgd_ctx::FstepLayout* L) {
-  if (!c->fstep_rebalance || L->rebalances >= 2 || !L->d_times || c->d_tprof) return DSGD_OK;
+  if (!c->k.fstep_rebalance || L->rebalances >= 2 || !L->d_times || c->d_tprof) return DSGD_OK;
   const size_t n = (size_t)L->n_wg * row_segs.size();
   if (!L->times_pending) {
     if (L->launches >= FSTEP_CAL) {
@@ -2068,18 +2004,6 @@ static int fstep_maybe_rebalance(dsgd_ctx* c, const std::vector<StreamSeg>& row_
   return fstep_build(c, row_segs, L->n_wg, *L);
 }
 
-// workgroups per worker of the chunked launch for these ranges (0: not this path)
-static int fstep_grid(const dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, long long tot, long long ent) {
-  // (from DSGD_FSTEP_MIN rows on -- or from 8,192 rows on when the range holds more entries than the column lists take)
-  if (!fstep_possible(c) || tot > c->fstep_max || (tot < c->fstep_min && !(ent > c->tcol_max_nnz && tot >= 8192))) return 0;
-  const int n_workers = (int)row_segs.size();
-  if (n_workers > c->n_cu) return 0;
-  long long smallest = tot;
-  for (const StreamSeg& sg : row_segs) smallest = std::min(smallest, sg.row_end - sg.row_begin);
-  const long long per_worker = std::max<long long>(1, c->n_cu / n_workers);
-  return (int)std::max<long long>(1, std::min(per_worker, smallest / std::max<long long>(1, c->fstep_rows)));
-}
-
 static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int n_wg) {
   const int n_workers = (int)row_segs.size();
   dsgd_ctx::FstepLayout* L = nullptr;
@@ -2099,9 +2023,9 @@ static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
   const size_t lds = std::max(lds_a, std::max(lds_b, lds_c));
   // the fixed-point scale of the hot accumulators: one contribution per row and column, |contribution| <= 2^shift, a
   // chunk's rows known -- refined once per configuration by the data (dsgd_fstep_bound_kernel)
-  const int shift0 = std::max(1, std::min(c->max_shift, 30 - rows_bits(L->worst_rows)));
+  const int shift0 = std::max(1, std::min(c->k.max_shift, 30 - rows_bits(L->worst_rows)));
   int shift = shift0;
-  if (c->fix_bound && shift0 < c->max_shift) {
+  if (c->k.fix_bound && shift0 < c->k.max_shift) {
     if (L->shift < 0) {
       DSGD_TRY(c->d_bound.reserve(1));
       HIP_TRY(hipMemsetAsync(c->d_bound, 0, sizeof(unsigned int), c->stream));
@@ -2111,7 +2035,7 @@ static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
       unsigned int amax = 0;
       HIP_TRY(hipMemcpyAsync(&amax, c->d_bound, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(hipStreamSynchronize(c->stream));
-      L->shift = refine_shift(shift0, c->max_shift, amax, L->worst_rows);
+      L->shift = refine_shift(shift0, c->k.max_shift, amax, L->worst_rows);
     }
     shift = L->shift;
   }
@@ -2127,7 +2051,7 @@ static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
   hipLaunchKernelGGL(dsgd_fstep_kernel, grid, dim3(1024), lds, c->stream, mh, view(c), L->d_tiles, L->d_meta, L->d_ctiles, L->d_cmeta,
                      (const void*)c->d_ccol, c->d_cval, L->d_chunks, c->d_w, c->d_g64, (long long)c->dp, c->d_sc, H, nc, main_scale,
                      c->fix_scale, c->d_coef8, c->d_dcold, c->d_wlong_rows, c->d_part, c->part_stride, c->d_partc, c->partc_stride,
-                     c->d_tprof, (c->fstep_rebalance && L->rebalances < 2) ? L->d_times : nullptr);
+                     c->d_tprof, (c->k.fstep_rebalance && L->rebalances < 2) ? L->d_times : nullptr);
   HIP_TRY(hipGetLastError());
   DSGD_TRY(prof_end(c, slot));
   c->last_grad_kernel = "dsgd_fstep_kernel";
@@ -2142,10 +2066,6 @@ static void tcol_drop_all(dsgd_ctx* c) {   // (the ranked CSR is about to change
   if (c->tcol_cache.empty()) return;
   (void)hipStreamSynchronize(c->stream);
   c->tcol_cache.clear();
-}
-static bool tcol_wanted(const dsgd_ctx* c, long long tot, int n_workers) {
-  return c->tcol_enable && tot >= c->tcol_min && tot <= c->tcol_max && n_workers <= 64 && c->n_rows < (1LL << 31) &&
-         (long long)n_workers * c->dp < (1LL << 24) && tot + 64LL * n_workers <= TC_MAX_BITS;
 }
 static dim3 tcol_row_grid(long long mx, int n_workers) {
   return dim3((unsigned)std::max<long long>(1, std::min<long long>((mx + TC_ROWS_PER_WG - 1) / TC_ROWS_PER_WG, 8192)), (unsigned)n_workers);
@@ -2162,22 +2082,11 @@ static int tcol_layout(dsgd_ctx* c, const std::vector<WorkSeg>& segs, long long 
     if (L.gen == c->layout_gen && L.ranges == key) {
       L.used = ++c->tcol_clock;
       if (L.n_wg == 0) return 1;   // (declined before -- no memory, too many entries: not tried again step after step)
-      c->tcol_miss_streak = 0;
+      c->tcol_gate.hit();
       *out = &L;
       return DSGD_OK;
     }
-  // A caller that never repeats a configuration (mini-batches over ever new row ranges) would pay a layout -- milliseconds --
-  // for every 20 us step: more misses in a row than the cache holds, and the column lists leave such a context alone.
-  // Not for good: after TCOL_COOLDOWN declined steps they try again -- a fit that settles on fixed splits after
-  // a phase of ever new ranges gets its column lists back; a context that keeps changing pays 4 layouts per 256 steps.
-  if (c->tcol_cooldown > 0) {
-    if (--c->tcol_cooldown == 0) c->tcol_miss_streak = 8;
-    return 1;
-  }
-  if (++c->tcol_miss_streak > 12) {
-    c->tcol_cooldown = 256;
-    return 1;
-  }
+  if (!c->tcol_gate.miss()) return 1;   // (a caller that never repeats a configuration: the back-off, csrc/dsgd_route.hpp)
   for (size_t i = 0; i < c->tcol_cache.size();)   // layouts of an earlier ranking
     if (c->tcol_cache[i].gen != c->layout_gen) {
       HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2248,7 +2157,7 @@ static int tcol_layout(dsgd_ctx* c, const std::vector<WorkSeg>& segs, long long 
   L.n_ent = (long long)tot[0];
   long long share = (L.n_ent + c->n_cu - 1) / std::max(1, c->n_cu);
   share = std::max<long long>(1024, std::min<long long>(TC_MAX_SHARE, (share + 63) & ~63LL));
-  if (c->tcol_share > 0) share = std::max<long long>(64, std::min<long long>(TC_MAX_SHARE, (c->tcol_share + 3) & ~3));   // (whole 16-byte pieces)
+  if (c->k.tcol_share > 0) share = std::max<long long>(64, std::min<long long>(TC_MAX_SHARE, (c->k.tcol_share + 3) & ~3));   // (whole 16-byte pieces)
   L.share = (int)share;
   L.n_wg = (int)((L.n_ent + share - 1) / share);
   {   // whole 16-byte pieces; the last one's padding is zero
@@ -2278,7 +2187,7 @@ static int launch_tcol(dsgd_ctx* c, const std::vector<WorkSeg>& segs, long long 
   dsgd_ctx::TcolLayout* L = nullptr;
   const int lrc = tcol_layout(c, segs, mx, &L);
   if (lrc != DSGD_OK) return lrc;
-  const int shift = std::max(1, std::min(c->max_shift, 30));   // 64-bit sums: nothing to bound (|contribution| <= 2^shift)
+  const int shift = std::max(1, std::min(c->k.max_shift, 30));   // 64-bit sums: nothing to bound (|contribution| <= 2^shift)
   c->last_shift = shift;
   const float scale = std::ldexp(1.0f, shift - c->vexp);
   size_t slot = 0;
@@ -2349,11 +2258,6 @@ static int plan_revalidate(dsgd_ctx* c, dsgd_plan* p) {
   p->idx_trusted = false;
   p->checked_load = c->load_gen;
   return DSGD_OK;
-}
-static bool plan_kernel_ok(const dsgd_ctx* c, long long step_rows, int n_workers) {
-  // (several hosted workers: their batches would run one after the other in the one workgroup -- 44 us for 3 x 100 --
-  //  while dsgd_mb_grad_kernel gives every worker its own workgroups: 32 us with the four-launch finish, less fused)
-  return c->plan_kernel && !c->comm && n_workers == 1 && step_rows <= c->plan_max_rows;
 }
 static int launch_plan_kernel(dsgd_ctx* c, const int* d_idx, const WorkSeg* d_segs, long long step_begin,
                               long long step_end, float lr, bool mail = false) {
@@ -2607,50 +2511,19 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   DSGD_TRY_B(ensure_g(c, 1));
   DSGD_TRY_B(set_identity_perm(c));
   c->hw_eval = std::min(c->dp, DSGD_LDS_FLOATS);
-  // Switches that stay: one per live decision (A/B measurements, tests that force a path), all read once here.
-  if (const char* e = getenv("DSGD_FIX_SHIFT")) c->max_shift = std::max(8, std::min(FIX_SHIFT, atoi(e)));   // cap of the fixed-point shift
-  if (const char* e = getenv("DSGD_FIX_BOUND")) c->fix_bound = atoi(e) != 0;      // 0: data-independent bound only
-  if (const char* e = getenv("DSGD_PLAN_KERNEL")) c->plan_kernel = atoi(e) != 0;  // 0: small batches through the multi-workgroup kernel
-  if (const char* e = getenv("DSGD_VT")) c->vt_enable = atoi(e) != 0;             // 0: plans' index lists through dsgd_mb_grad_kernel
-  if (const char* e = getenv("DSGD_CS")) c->cs_enable = atoi(e) != 0;             // 0: small plan steps through the row-parallel kernels
-  if (const char* e = getenv("DSGD_CS_G")) c->cs_g = atoi(e) == 16 ? 16 : (atoi(e) == 8 ? 8 : 0);
-  if (const char* e = getenv("DSGD_CS_MAX_MB")) c->cs_max_mb = std::max(0, atoi(e));
-  if (const char* e = getenv("DSGD_CS_HOST_LAYOUT")) c->cs_host_layout = atoi(e) != 0;
-  if (const char* e = getenv("DSGD_CS_REQ")) c->cs_req = atoi(e) != 0;
-  if (const char* e = getenv("DSGD_CACHE_MB")) c->plan_cache.cache_cap = (size_t)std::max(0, atoi(e)) << 20;
-#ifdef DSGD_TEST_COLLECTIVE_SEAM
-  if (const char* e = getenv("DSGD_TEST_CS_SKIP_PUBLISH")) c->cs_test_skip = std::max(0, atoi(e));
-#endif
-  if (const char* e = getenv("DSGD_REQ_MAPPED")) c->req_mapped = atoi(e) != 0;
-  if (const char* e = getenv("DSGD_REQ_PLAN")) c->req_plan = atoi(e) != 0;
-  if (const char* e = getenv("DSGD_STREAM_MIN")) c->stream_min = std::max(1LL, atoll(e));
-  if (const char* e = getenv("DSGD_FSTEP")) c->fstep_enable = atoi(e) != 0;
-  if (const char* e = getenv("DSGD_FSTEP_MIN")) c->fstep_min = std::max(1LL, atoll(e));
-  if (const char* e = getenv("DSGD_FSTEP_MAX")) c->fstep_max = std::max(1LL, atoll(e));
-  if (const char* e = getenv("DSGD_FSTEP_ROWS")) c->fstep_rows = std::max(1LL, atoll(e));
-  if (const char* e = getenv("DSGD_FSTEP_REBALANCE")) c->fstep_rebalance = atoi(e) != 0;
-  if (const char* e = getenv("DSGD_TCOL")) c->tcol_enable = atoi(e) != 0;
-  if (const char* e = getenv("DSGD_TCOL_MIN")) c->tcol_min = std::max(1LL, atoll(e));
-  if (const char* e = getenv("DSGD_TCOL_MAX")) c->tcol_max = std::max(1LL, atoll(e));
-  if (const char* e = getenv("DSGD_TCOL_MAX_NNZ")) c->tcol_max_nnz = std::max(1LL, atoll(e));
-  if (const char* e = getenv("DSGD_TCOL_SHARE")) c->tcol_share = std::max(0, atoi(e));
-  if (const char* e = getenv("DSGD_REQ_SPIN")) c->req_spin = atoi(e) != 0;
-  if (const char* e = getenv("DSGD_CS_NT")) c->cs_nt = atoi(e) == CS_THREADS_NARROW ? CS_THREADS_NARROW : 0;
-  if (const char* e = getenv("DSGD_VT_TPW")) c->vt_tpw = std::max(1, atoi(e));
-  if (const char* e = getenv("DSGD_VT_PACK_MB")) c->vt_pack_mb = std::max(0, atoi(e));
-  if (const char* e = getenv("DSGD_HSPLIT")) c->hsplit = atoi(e);                 // hot/cold split rank (tests: wide models)
-  if (const char* e = getenv("DSGD_RP64_FUSED")) c->rp64_fused = atoi(e) != 0;    // dsgd_sync_steps_f64: 1 = one fused launch per step, 0 = two
+  knobs_read(c->k, getenv);   // every switch, once (csrc/dsgd_route.hpp: the table)
+  c->plan_cache.cache_cap = (size_t)c->k.cache_mb << 20;
   {   // the fused step's wait is bounded in wall-clock time: 2 s of the device's constant-rate clock (kHz; 100 MHz where unknown)
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, cfg->device) != hipSuccess || khz <= 0) khz = 100000;
     c->rp64_wait_ticks = (unsigned long long)khz * 2000ull;
   }
-  if (getenv("DSGD_PLAN_PROF") && atoi(getenv("DSGD_PLAN_PROF"))) {
+  if (c->k.plan_prof) {
     // (16 counters + four words per workgroup of the chunked launch's LAST run: start, end, cycles in the hot tiles, XCC id)
     DSGD_TRY_B(c->d_tprof.alloc(16 + 4 * 1024));
     HIP_TRY_B(hipMemsetAsync(c->d_tprof, 0, sizeof(unsigned long long) * (16 + 4 * 1024), c->stream));
   }
-  c->hsplit = std::max(1, std::min(c->hsplit, (DSGD_LDS_FLOATS - 16 * WS_COEF_STRIDE - 4 - 64) / 2));   // (< 65536: 16-bit ranks)
+  c->hsplit = std::max(1, std::min(c->k.hsplit, HSPLIT_MAX));   // (< 65536: 16-bit ranks)
   if (c->hsplit >= 8) c->hsplit &= ~3;   // 16-byte aligned tile boundaries: the LDS tiles are staged / written back in 16-byte pieces
   const int lds_max = DSGD_LDS_FLOATS * (int)sizeof(float);
 #define DSGD_ATTR(fn) HIP_TRY_B(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max))
@@ -2891,8 +2764,7 @@ static int load_csr_impl(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in,
   ++c->layout_gen;
   ++c->load_gen;
   c->bound_segs.clear();
-  c->tcol_miss_streak = 0;   // (the column lists' misses were about the old rows' ranges)
-  c->tcol_cooldown = 0;
+  c->tcol_gate.reset();   // (the column lists' misses were about the old rows' ranges)
   c->last_grad_kernel = "";  // (dsgd_grad_kernel_name / dsgd_tuning_info report launches over THIS data: calls that record none --
   c->last_shift = FIX_SHIFT; //  the row-parallel fp64 requests -- would go on reporting the old data's)
   // (the wave tiles cover the hot stream and are built with the layout, at the first compute call)
@@ -3062,7 +2934,7 @@ static int stage_lists(dsgd_ctx* c, const int32_t* const* idx_per_worker, const 
   }
   std::vector<WorkSeg> segs(n_workers);
   long long off = 0;
-  if (c->req_mapped && tot <= REQ_MAPPED_ITEMS) {
+  if (c->k.req_mapped && tot <= REQ_MAPPED_ITEMS) {
     // the reference's batch sizes: the lists go into a host-mapped buffer the kernels read in place -- no copy on the
     // stream in front of the launch (every per-request entry point returns behind its kernels: the buffer is free again)
     if (!c->h_req) DSGD_TRY(c->h_req.alloc((size_t)REQ_MAPPED_ITEMS, hipHostMallocMapped));
@@ -3201,7 +3073,7 @@ static int ranges_enqueue(dsgd_ctx* c, const int64_t* row_begin, const int64_t* 
   DSGD_TRY(require_ds(c));
   DSGD_TRY(require_sync_mode(c));
   std::vector<WorkSeg> segs(n_workers);
-  long long mx = 0, tot = 0;
+  long long mx = 0, tot = 0, smallest = LLONG_MAX;
   for (int k = 0; k < n_workers; ++k) {
     if (row_end[k] <= row_begin[k])
       return fail(DSGD_EINVAL, "worker %d has an empty row range: Vec.sum requires a non-empty list", k);
@@ -3211,6 +3083,7 @@ static int ranges_enqueue(dsgd_ctx* c, const int64_t* row_begin, const int64_t* 
     segs[k].begin = row_begin[k];
     segs[k].end = row_end[k];
     mx = std::max<long long>(mx, row_end[k] - row_begin[k]);
+    smallest = std::min<long long>(smallest, row_end[k] - row_begin[k]);
     tot += row_end[k] - row_begin[k];
   }
   DSGD_TRY(prepare_layout(c));
@@ -3218,30 +3091,30 @@ static int ranges_enqueue(dsgd_ctx* c, const int64_t* row_begin, const int64_t* 
   DSGD_TRY(ensure_s(c, true));
   std::vector<StreamSeg> ssegs(n_workers);
   for (int k = 0; k < n_workers; ++k) ssegs[k] = make_sseg(row_begin[k], row_end[k]);
-  // 10^3 .. 10^5 rows: column lists (csrc/dsgd_tcol.hpp) -- dot, column-wise gradient, reduce: no partials
-  int trc = 1;
   long long ent = tot * 75;   // non-zeros of the ranges (the host's copy of the row offsets; else RCV1's mean row)
   if (c->h_row_ptr.size() == (size_t)c->n_rows + 1) {
     ent = 0;
     for (int k = 0; k < n_workers; ++k) ent += c->h_row_ptr[(size_t)row_end[k]] - c->h_row_ptr[(size_t)row_begin[k]];
   }
-  const bool chunks_could = fstep_grid(c, ssegs, tot, ent) > 0;
-  if (tcol_wanted(c, tot, n_workers) && !(chunks_could && ent > c->tcol_max_nnz)) {
+  const RangesRoute r = route_ranges(c->k, route_facts(c), n_workers, tot, ent, smallest);
+  int trc = 1;   // (1: the column lists were not tried, or declined softly -- no memory, the back-off: the ranges' other family)
+  if (r.try_tcol) {
+    // 10^3 .. 10^5 rows: column lists (csrc/dsgd_tcol.hpp) -- dot, column-wise gradient, reduce: no partials
     DSGD_TRY(upload_segs(c, segs));
     trc = launch_tcol(c, segs, mx);
     if (trc != DSGD_OK && trc != 1) return trc;
   }
-  const int fwg = trc == 1 ? fstep_grid(c, ssegs, tot, ent) : 0;
-  if (trc == DSGD_OK) {
-  } else if (fwg > 0) {
-    // shards of 10^4 .. 2 * 10^6 rows: row chunks, the three passes of the split streams in ONE launch (csrc/dsgd_fstep.hpp)
-    DSGD_TRY(launch_fstep(c, ssegs, fwg));
-  } else if (tot >= c->stream_min) {
-    // whole contiguous ranges: the nnz-streaming kernel (coalesced 16-byte loads, no per-row latency chain)
-    DSGD_TRY(launch_stream<true>(c, ssegs));  // (the profiling events bracket the main kernel only)
-  } else {
-    DSGD_TRY(upload_segs(c, segs));
-    DSGD_TRY(launch_grad(c, nullptr, c->d_segs, n_workers, mx, true));
+  if (trc == 1) switch (r.then) {
+    case RANGES_FSTEP:   // shards of 10^4 .. 2 * 10^6 rows: row chunks, the three passes of the split streams in ONE launch (csrc/dsgd_fstep.hpp)
+      DSGD_TRY(launch_fstep(c, ssegs, r.fstep_wg));
+      break;
+    case RANGES_STREAM:   // whole contiguous ranges: the nnz-streaming kernel (coalesced 16-byte loads, no per-row latency chain)
+      DSGD_TRY(launch_stream<true>(c, ssegs));  // (the profiling events bracket the main kernel only)
+      break;
+    case RANGES_ROWWISE:
+      DSGD_TRY(upload_segs(c, segs));
+      DSGD_TRY(launch_grad(c, nullptr, c->d_segs, n_workers, mx, true));
+      break;
   }
   if (finish) DSGD_TRY(launch_finish_sync(c, n_workers, lr));
   *total = tot;
@@ -3382,13 +3255,24 @@ static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int3
   *out = p;
   return DSGD_OK;
 }
+// what route_plan needs from a plan; dsgd_plan_run, plan_run64 and dsgd_plan_info ask the same question
+static PlanRoute plan_route(const dsgd_ctx* c, const dsgd_plan* p) {
+  PlanFacts f;
+  f.rp64 = p->rp64;
+  f.cs_current = p->cs_ok && p->cs_layout == c->layout_gen;
+  f.fits_here = p->fits && p->fits_rows == c->n_rows;
+  f.vt_current = p->vt_ok && p->vt_layout == c->layout_gen;
+  f.max_step_rows = p->max_step_rows;
+  f.n_workers = p->n_workers;
+  return route_plan(c->k, route_facts(c), f);
+}
 static int cs64_refused(dsgd_ctx* c);   // (dsgd_fp64_host.hpp, which in turn needs plan_finish: the one declaration ahead)
 // the lists are in p->d_idx (enqueued on the build stream): lay the plan out for the device, close its set-up
 static int plan_finish(dsgd_ctx* c, dsgd_plan* p, dsgd_plan** out) {
   int rc = DSGD_OK;
   // the column slices of the reference's own step sizes are laid out NOW (by the device, on the build stream), not inside
   // the first dsgd_plan_run -- a call its callers time; without a column layout yet (no data / no dimSparsity) at the first run
-  if (!p->rp64 && (c->cs_enable || c->fp64) && !c->comm && c->d_row_ptr && c->have_ds && !c->async_running) {   // (a row-parallel plan has no layout)
+  if (plan_lays_out_at_creation(c->k, route_facts(c), p->rp64, (bool)c->d_row_ptr, c->have_ds)) {   // (a row-parallel plan has no layout)
     rc = prepare_layout(c);
     if (rc == DSGD_OK) rc = cs_build(c, p);
     if (rc == DSGD_OK && c->fp64 && !p->cs_ok) rc = cs64_refused(c);
@@ -3446,54 +3330,61 @@ int dsgd_sync_step(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int6
   DSGD_TRY(require_ds(c));
   DSGD_TRY(require_sync_mode(c));
   DSGD_TRY(prepare_layout(c));
-  if (c->fp64 && c->comm) return sync_step64_ranks(c, idx_per_worker, n_per_worker, n_workers, (double)lr, stats);
-  if (c->fp64 && c->d_val64) {   // Double data: the row-parallel pair, inside the limits of the one-step plan this call is on float data
-    long long rows = 0;
-    for (int k = 0; k < n_workers; ++k) rows += std::max<long long>(0, n_per_worker[k]);
-    DSGD_TRY(cs64_step_limits(c, n_workers, rows));
-    return sync_step64_rows(c, idx_per_worker, n_per_worker, n_workers, (double)lr, stats);
-  }
-  if (c->fp64) return sync_step64(c, idx_per_worker, n_per_worker, n_workers, (double)lr, stats);
+  long long rows = 0;
+  for (int k = 0; k < n_workers; ++k) rows += std::max<long long>(0, n_per_worker[k]);
+  const RequestRoute r = route_request(
+      c->k, route_facts(c), n_workers, rows,
+      [&] {
+        for (int k = 0; k < n_workers; ++k)
+          if (!idx_per_worker[k] || !list_fits_staged(c, idx_per_worker[k], n_per_worker[k])) return false;
+        return true;
+      },
+      [&] {   // (what is wrong with a list, stage_lists and the row-wise kernel report)
+        for (int k = 0; k < n_workers; ++k) {
+          if (n_per_worker[k] <= 0 || !idx_per_worker[k]) return false;
+          for (int64_t t = 0; t < n_per_worker[k]; ++t)
+            if (idx_per_worker[k][t] < 0 || idx_per_worker[k][t] >= c->n_rows) return false;
+        }
+        return true;
+      });
   long long mx = 0, tot = 0;
-  {
-    long long t = 0;
-    for (int k = 0; k < n_workers; ++k) t += std::max<long long>(0, n_per_worker[k]);
-    bool fits = c->req_plan && plan_kernel_ok(c, t, n_workers);
-    for (int k = 0; k < n_workers && fits; ++k)
-      fits = idx_per_worker[k] && list_fits_staged(c, idx_per_worker[k], n_per_worker[k]);
-    if (fits && c->prof) {   // the reference's batch sizes: one persistent workgroup does the whole closure
+  switch (r.first) {
+    case REQ_F64_RANKS: return sync_step64_ranks(c, idx_per_worker, n_per_worker, n_workers, (double)lr, stats);
+    case REQ_F64_ROWS:   // Double data: the row-parallel pair, inside the limits of the one-step plan this call is on float data
+      DSGD_TRY(cs64_step_limits(c, n_workers, rows));
+      return sync_step64_rows(c, idx_per_worker, n_per_worker, n_workers, (double)lr, stats);
+    case REQ_F64_CS: return sync_step64(c, idx_per_worker, n_per_worker, n_workers, (double)lr, stats);
+    case REQ_ONE_WG_READBACK:   // the reference's batch sizes: one persistent workgroup does the whole closure
       DSGD_TRY(reset_counters(c));
       DSGD_TRY(stage_lists(c, idx_per_worker, n_per_worker, n_workers, &mx, &tot));
       DSGD_TRY(launch_plan_kernel(c, c->cur_idx, c->d_segs, 0, 1, lr));
       return finish_stats(c, stats, tot);
-    }
-    if (fits) {   // ... its statistics through the host-mapped mailbox (see below)
+    case REQ_ONE_WG_MAIL: {   // ... its statistics through the host-mapped mailbox (see below)
       if (!c->ctr_known) DSGD_TRY(reset_counters(c));
       const unsigned long long before = c->ctr_last;
       DSGD_TRY(stage_lists(c, idx_per_worker, n_per_worker, n_workers, &mx, &tot));
       DSGD_TRY(launch_plan_kernel(c, c->cur_idx, c->d_segs, 0, 1, lr, true));
-      return finish_mail(c, stats, tot, before, c->req_spin);
+      return finish_mail(c, stats, tot, before, c->k.req_spin);
     }
-  }
-  {
-    // the reference's own sizes (application.conf:15,27): the step laid out and run by the column-slice kernel, one launch
-    int G = 0;
-    if (cs_request_ok(c, idx_per_worker, n_per_worker, n_workers, &G) == DSGD_OK) {
+    case REQ_CS: {   // the reference's own sizes (application.conf:15,27): the step laid out and run by the column-slice kernel, one launch
       if (!c->ctr_known) DSGD_TRY(reset_counters(c));
       const unsigned long long before = c->ctr_last;
       DSGD_TRY(stage_lists(c, idx_per_worker, n_per_worker, n_workers, &mx, &tot));
-      DSGD_TRY(launch_cs_request(c, G, n_workers, mx, lr));
-      const int rc = finish_mail(c, stats, tot, before, c->req_spin);
+      DSGD_TRY(launch_cs_request(c, r.G, n_workers, mx, lr));
+      const int rc = finish_mail(c, stats, tot, before, c->k.req_spin);
       if (rc != 1) return rc;
       // (the step does not fit the one-step layout -- more than CS_MAX_SLOTS slots or 4,096 columns in one slice: nothing
       //  was applied; the row-parallel kernels below take it.  They work on the rank-ordered vector: the slice-major
       //  copy the request made is dropped -- left "live" it would overwrite their update at the next bind)
       DSGD_TRY(cs_unslice(c));
+      break;
     }
+    case REQ_ROWWISE_READBACK:
+    case REQ_ROWWISE_MAIL: break;
   }
   DSGD_TRY(ensure_g(c, n_workers));
   DSGD_TRY(ensure_s(c, true));
-  if (c->comm || c->prof) {   // (the collective path / profiling brackets: the plain read-back)
+  if (r.rowwise == REQ_ROWWISE_READBACK) {   // (the collective path / profiling brackets: the plain read-back)
     DSGD_TRY(reset_counters(c));
     DSGD_TRY(stage_lists(c, idx_per_worker, n_per_worker, n_workers, &mx, &tot));
     DSGD_TRY(launch_grad(c, c->cur_idx, c->d_segs, n_workers, mx, true));
@@ -3602,7 +3493,7 @@ int dsgd_plan_read_record(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t
 extern "C" int dsgd_test_cs_skip_publish(dsgd_ctx* c, int32_t from_step) {
   DSGD_TRY(check_ctx(c));
   std::lock_guard<std::mutex> lk(c->mu);
-  c->cs_test_skip = from_step < 0 ? 0 : from_step;
+  c->k.cs_test_skip = from_step < 0 ? 0 : from_step;
   return DSGD_OK;
 }
 // ... and the bytes the library holds right now, counted where it allocates (csrc/dsgd_buf.hpp): the whole process', every
@@ -3622,10 +3513,9 @@ int dsgd_plan_info(dsgd_ctx* c, dsgd_plan* p, int32_t* vals, int32_t n) {
     DSGD_TRY(bind(c, true));
     DSGD_TRY(plan_revalidate(c, p));
   }
-  const bool cs = (c->cs_enable || c->fp64) && !c->comm && p->cs_ok && p->cs_layout == c->layout_gen;
-  const bool one_wg = !cs && plan_kernel_ok(c, p->max_step_rows, p->n_workers) && p->fits && p->fits_rows == c->n_rows;
-  const bool vt = !cs && !one_wg && c->vt_enable && p->vt_ok && p->vt_layout == c->layout_gen;
-  const int32_t all[8] = {p->rp64 ? 6 : (cs && c->fp64) ? 5 : cs ? 1 : (one_wg ? 2 : (vt ? 3 : (p->cs_layout == c->layout_gen || p->vt_layout == c->layout_gen ? 4 : 0))),
+  const PlanRoute r = plan_route(c, p);
+  const bool cs = r == PLAN_CS || r == PLAN_CS64;
+  const int32_t all[8] = {plan_info_code(r, p->cs_layout == c->layout_gen || p->vt_layout == c->layout_gen),
                           cs ? p->cs_G : 0, cs ? p->cs_slot_stride : 0, cs ? p->cs_row_stride : 0, cs ? p->cs_cl_stride : 0,
                           cs ? p->cs_spl : 0, (cs && p->cs_device_built) ? 1 : 0, p->gate_words};
   for (int i = 0; i < n; ++i) vals[i] = all[i];
@@ -3663,7 +3553,7 @@ int dsgd_plan_run(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_en
   DSGD_TRY(plan_revalidate(c, p));   // (a plan from before the last load: DSGD_ERANGE here, before anything is enqueued)
   DSGD_TRY(prepare_layout(c));
   // the reference's own batch sizes: column slices, the whole range of steps in ONE launch (csrc/dsgd_cs.hpp)
-  if (c->cs_enable && !c->comm) {
+  if (c->k.cs_enable && !c->comm) {
     if (p->cs_layout != c->layout_gen) {   // (created before the column layout existed, or the layout changed since)
       DSGD_TRY(cs_build(c, p));
       if (p->cs_device_built && c->build_stream) {
@@ -3676,23 +3566,25 @@ int dsgd_plan_run(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_en
     HIP_TRY(hipStreamWaitEvent(c->stream, p->built_ev, 0));
     p->built_pending = false;
   }
-  if (c->cs_enable && !c->comm) {
-    if (p->cs_ok && p->cs_layout == c->layout_gen) {
-      if (step_end > step_begin) DSGD_TRY(launch_cs(c, p, step_begin, step_end, lr));
-      c->pending_samples += p->offsets[step_end * p->n_workers] - p->offsets[step_begin * p->n_workers];
-      return DSGD_OK;
-    }
+  PlanRoute r = plan_route(c, p);
+  if (r == PLAN_CS) {
+    if (step_end > step_begin) DSGD_TRY(launch_cs(c, p, step_begin, step_end, lr));
+    c->pending_samples += p->offsets[step_end * p->n_workers] - p->offsets[step_begin * p->n_workers];
+    return DSGD_OK;
   }
   DSGD_TRY(cs_unslice(c));   // (bound with the slice-major weights kept: the row-parallel kernels below read d_w)
-  if (plan_kernel_ok(c, p->max_step_rows, p->n_workers) && p->fits && p->fits_rows == c->n_rows) {
+  if (r == PLAN_ONE_WG) {
     if (step_end > step_begin) DSGD_TRY(launch_plan_kernel(c, p->d_idx, p->d_segs, step_begin, step_end, lr));
     c->pending_samples += p->offsets[step_end * p->n_workers] - p->offsets[step_begin * p->n_workers];
     return DSGD_OK;
   }
   DSGD_TRY(ensure_g(c, p->n_workers));
   DSGD_TRY(ensure_s(c, true));
-  if (c->vt_enable && p->vt_layout != c->layout_gen) DSGD_TRY(vt_build(c, p));
-  const bool vt = c->vt_enable && p->vt_ok && p->vt_layout == c->layout_gen;
+  if (c->k.vt_enable && p->vt_layout != c->layout_gen) {   // (the tiles are laid out at the first run that needs them)
+    DSGD_TRY(vt_build(c, p));
+    r = plan_route(c, p);
+  }
+  const bool vt = r == PLAN_VT;
   for (int64_t s = step_begin; s < step_end; ++s) {
     if (vt) {   // the lists as virtual tiles over the split streams
       DSGD_TRY(launch_grad_vt(c, p, s));
@@ -5284,7 +5176,7 @@ int dsgd_tuning_info(dsgd_ctx* c, int32_t* vals, int32_t n) {
   if (!vals || n < 0 || n > 7) return fail(DSGD_EINVAL, "bad tuning_info arguments");
   std::lock_guard<std::mutex> lk(c->mu);
   const int32_t all[7] = {4 /* split layout: the only one */, std::min(c->hsplit, c->dp), c->last_shift,
-                          c->cold_col16 ? 1 : 0, c->plan_kernel ? 1 : 0, c->fix_bound ? 1 : 0, c->last_fstep_rebalances};
+                          c->cold_col16 ? 1 : 0, c->k.plan_kernel ? 1 : 0, c->k.fix_bound ? 1 : 0, c->last_fstep_rebalances};
   for (int i = 0; i < n; ++i) vals[i] = all[i];
   return DSGD_OK;
 }

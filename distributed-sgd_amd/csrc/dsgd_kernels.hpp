@@ -20,9 +20,9 @@
 #include <hip/hip_runtime.h>
 
 #include "dsgd_layout_types.hpp"   // (the records and constants the host writes and these kernels read)
+#include "dsgd_limits.hpp"         // (the limits the host's choice of a kernel family reads as well: DSGD_LDS_FLOATS, CT_STRIP, ...)
 
 #define DSGD_EPS 1e-20f  // ref: math/Sparse.scala:104 (Sparse.epsilon); representable in fp32
-#define DSGD_LDS_FLOATS 40960  // 160 KiB / 4
 
 // Sparse(...) constructor filter: entries with abs(v) <= 1e-20 vanish (ref: math/Sparse.scala:108-118)
 __device__ __forceinline__ float filt(float v) { return fabsf(v) > DSGD_EPS ? v : 0.0f; }
@@ -1616,7 +1616,7 @@ __global__ void __launch_bounds__(256) dsgd_split_fill_kernel(CsrView m, int hsp
 
 // ---- the cold tile walk ------------------------------------------------------------------------------------
 // (cold tiles and CT_MAXROWS: csrc/dsgd_layout_types.hpp)
-constexpr int CT_STRIP = 256;        // floats per wave: [0, CT_MAXROWS + 2) by local row, [192, 256) per-lane dummy slots
+// (CT_STRIP, floats per wave: csrc/dsgd_limits.hpp)
 constexpr int CT_DUMMY = 192;
 
 template <bool COL16>

@@ -446,7 +446,7 @@ __global__ void __launch_bounds__(CS_THREADS) dsgd_rp64v_s_sliced_kernel(const d
 //   counting  behind the arrival one lane of workgroup 0 stores the context's running n_active into the step's word of
 //             `cum` (all ones until then): the host takes the differences, and after an abort the written words name the
 //             last completed step.
-constexpr bool RP64_FUSED_DEFAULT = false;   // (DSGD_RP64_FUSED=1 selects the fused form: not measured yet)
+// (RP64_FUSED_DEFAULT: csrc/dsgd_limits.hpp)
 constexpr unsigned long long RP64_GAVE_UP = 1ull << 62;
 struct Rp64StepSync {
   unsigned long long* arrived;     // the arrival counter (monotonic; bit 62: a launch gave up)

@@ -39,9 +39,7 @@ constexpr int TC_G = 16;                 // lanes per row
 constexpr int TC_UNR = 5;                // register-held rounds of a row: 80 non-zeros (RCV1's mean row: 75)
 constexpr int TC_THREADS = 1024;
 constexpr int TC_ROWS_PER_WG = TC_THREADS / TC_G;   // 64: two words of the bitmap
-constexpr int TC_MAX_SHARE = 8192;       // entries per workgroup of the gradient kernel: 64 KB of LDS for its 64-bit table
-constexpr int TC_DC_BITS = 13;           // packed entry: relative column (< TC_MAX_SHARE) below, bit of the row above
-constexpr int TC_MAX_BITS = 1 << (32 - TC_DC_BITS);   // 524,288 bits of bitmap (every worker's range padded to 64 rows)
+// (TC_MAX_SHARE, TC_DC_BITS, TC_MAX_BITS: csrc/dsgd_limits.hpp)
 constexpr int TC_WL = 4096;              // hottest ranks with an LDS copy of their weight in the dot kernel (one 16-byte piece per lane)
 
 struct TcShare {     // per share of the gradient kernel

@@ -604,6 +604,33 @@ def test_plan_kernel_and_multi_launch_path_agree_with_the_oracle(monkeypatch, k_
         assert np.abs(ws["1"][0] - ws["0"][0]).max() <= 2 * tol(ws["1"][0])
 
 
+@pytest.mark.parametrize("k_workers,req_plan,kernel", [(1, "1", "dsgd_plan_kernel"), (3, None, "dsgd_mb_grad_kernel")])
+def test_requests_under_profiling_read_their_statistics_back(monkeypatch, k_workers, req_plan, kernel):
+    """With profiling on a request's statistics are read back from the device, not taken from the mailbox
+    (csrc/dsgd_route.hpp: REQ_ONE_WG_READBACK with DSGD_REQ_PLAN=1, REQ_ROWWISE_READBACK at the defaults): the same kernels,
+    the same weights and the same active-row counts as the oracle's, step by step, and then with profiling off again."""
+    monkeypatch.delenv("DSGD_REQ_PLAN", raising=False)
+    monkeypatch.delenv("DSGD_PLAN_KERNEL", raising=False)
+    if req_plan:
+        monkeypatch.setenv("DSGD_REQ_PLAN", req_plan)
+    n_rows, n_train = 8192, 6553
+    data = dsgd_amd.synth.generate(n_rows, seed=37)
+    steps = batches(np.random.default_rng(37), n_train, k_workers, 100, 8)
+    o, eng = make_pair(data, 1e-5, n_train)
+    with eng:
+        eng.prof_enable(True)
+        w_ref, flips, rows = run_sync(o, eng, steps, 0.5, "request_profiled")
+        assert rows == 8 * k_workers * 100
+        assert kernel in eng.grad_kernel_name(), eng.grad_kernel_name()
+        w_prof = eng.get_weights()
+        eng.prof_enable(False)   # ... and through the mailbox: the same steps, the same bits (integer sums either way)
+        eng.set_weights(np.zeros(data.dim + 1, dtype=np.float32))
+        _, flips_mail, _ = run_sync(o, eng, steps, 0.5, "request_profiled")
+        assert kernel in eng.grad_kernel_name(), eng.grad_kernel_name()
+        if waivers.check("request_profiled:both_finishes", flips == 0 and flips_mail == 0, "flips %d / %d" % (flips, flips_mail)):
+            np.testing.assert_allclose(eng.get_weights(), w_prof, rtol=0, atol=1e-7 * max(1.0, np.abs(w_prof).max()))
+
+
 # ---- the in-library RCCL path with a communicator of size one (the N>1 code path on a 1-GPU box) --------------------
 def test_communicator_of_size_one_changes_nothing():
     """dsgd_comm_init(world=1): column counts, dimSparsity counts, the gradient and the evaluation tallies all go

@@ -232,3 +232,22 @@ def test_a_caller_that_never_repeats_its_ranges_is_left_alone(monkeypatch):
             eng.sync_step_ranges([(0, 4000)], 1e-3, asynchronous=True)
         eng.synchronize()
         assert eng.grad_kernel_name() == TCOL
+
+
+def test_hand_over_to_row_chunks_by_entries(monkeypatch):
+    """From 8,192 rows on, ranges that hold more non-zeros than DSGD_TCOL_MAX_NNZ go to the row chunks although their row
+    count is the column lists' (csrc/dsgd_route.hpp: route_ranges).  The threshold lowered to 100,000 entries so that 8,192
+    rows of ~75 cross it: 8,192 rows take the chunked launch, 8,191 stay with the column lists, each step under the derived
+    bound."""
+    clean(monkeypatch)
+    monkeypatch.setenv("DSGD_TCOL_MAX_NNZ", "100000")
+    data = dsgd_amd.synth.generate(10240, seed=67)
+    n_train = 9000
+    assert data.row_ptr[8191] > 100000
+    o, eng = make_pair(data, 1e-5, n_train)
+    with eng:
+        eng.set_weights(some_weights(data.dim, 67))
+        for ranges, kernel in (([(0, 8192)], "dsgd_fstep_kernel"), ([(0, 8191)], TCOL), ([(0, 4096), (4096, 8192)], "dsgd_fstep_kernel"),
+                               ([(0, 1000)], TCOL)):
+            ranged_step(o, eng, ranges, 0.5 * 100 / n_train * len(ranges))
+            assert eng.grad_kernel_name() == kernel, ranges
