@@ -189,7 +189,8 @@ static int cs64_step_limits(dsgd_ctx* c, int n_workers, long long rows) {
 }
 static int cs64_refused(dsgd_ctx* c) {
   return fail(DSGD_EUNSUPPORTED, "fp64 plan: a row index outside the loaded data, or a step whose layout exceeds dsgd_cs64_step_kernel "
-                                 "(%d slots or %d columns of one slice per step)", CS_MAX_SLOTS, CS_MAX_CLT * CS_THREADS);
+                                 "(%d slots or %d columns of one slice per step), or a layout beyond DSGD_CS_MAX_MB = %d MiB", CS_MAX_SLOTS,
+              CS_MAX_CLT * CS_THREADS, c->k.cs_max_mb);
 }
 
 // ======== 3. The row-parallel step (csrc/dsgd_rp64.hpp): its buffers, its description, its enqueue functions ========

@@ -3507,7 +3507,7 @@ extern "C" void dsgd_test_live_bytes(int64_t* device_bytes, int64_t* pinned_byte
 
 int dsgd_plan_info(dsgd_ctx* c, dsgd_plan* p, int32_t* vals, int32_t n) {
   DSGD_TRY(check_ctx(c));
-  if (!p || !vals || n < 0 || n > 8) return fail(DSGD_EINVAL, "bad plan_info arguments");
+  if (!p || !vals || n < 0 || n > 9) return fail(DSGD_EINVAL, "bad plan_info arguments");
   std::lock_guard<std::mutex> lk(c->mu);
   if (p->checked_load != c->load_gen) {   // (data loaded since: how the plan will run is a question about the new rows)
     DSGD_TRY(bind(c, true));
@@ -3515,9 +3515,9 @@ int dsgd_plan_info(dsgd_ctx* c, dsgd_plan* p, int32_t* vals, int32_t n) {
   }
   const PlanRoute r = plan_route(c, p);
   const bool cs = r == PLAN_CS || r == PLAN_CS64;
-  const int32_t all[8] = {plan_info_code(r, p->cs_layout == c->layout_gen || p->vt_layout == c->layout_gen),
+  const int32_t all[9] = {plan_info_code(r, p->cs_layout == c->layout_gen || p->vt_layout == c->layout_gen),
                           cs ? p->cs_G : 0, cs ? p->cs_slot_stride : 0, cs ? p->cs_row_stride : 0, cs ? p->cs_cl_stride : 0,
-                          cs ? p->cs_spl : 0, (cs && p->cs_device_built) ? 1 : 0, p->gate_words};
+                          cs ? p->cs_spl : 0, (cs && p->cs_device_built) ? 1 : 0, p->gate_words, cs ? p->cs_nt : 0};
   for (int i = 0; i < n; ++i) vals[i] = all[i];
   return DSGD_OK;
 }

@@ -28,12 +28,12 @@ class Plan:
     def info(self):
         """How the plan will run: kind ('column_slices', 'one_workgroup', 'virtual_tiles', 'row_parallel', 'not_laid_out')
         and, for column slices, the layout's shape ('row_parallel_fp64': a plan made with rp64=True); see dsgd_plan_info."""
-        v = (C.c_int32 * 8)()
-        check(_lib.load().dsgd_plan_info(self.engine._ctx, self.handle, v, C.c_int32(8)))
+        v = (C.c_int32 * 9)()
+        check(_lib.load().dsgd_plan_info(self.engine._ctx, self.handle, v, C.c_int32(9)))
         kinds = {0: "not_laid_out", 1: "column_slices", 2: "one_workgroup", 3: "virtual_tiles", 4: "row_parallel", 5: "column_slices_fp64",
                  6: "row_parallel_fp64"}
         return {"kind": kinds.get(int(v[0]), "?"), "slices": int(v[1]), "slot_stride": int(v[2]), "row_stride": int(v[3]),
-                "col_list_stride": int(v[4]), "slots_per_lane": int(v[5]), "device_built": bool(v[6]), "record_words": int(v[7])}
+                "col_list_stride": int(v[4]), "slots_per_lane": int(v[5]), "device_built": bool(v[6]), "record_words": int(v[7]), "threads": int(v[8])}
 
     def record(self, on=True):
         """Keep the gate decision of every row and the regulariser scalar of every step this plan runs (column slices and

@@ -65,7 +65,8 @@ enum {
  *   Limits (a plan beyond them is refused with DSGD_EUNSUPPORTED when it is CREATED): at most 4 workers per step, at
  *   most 1,024 rows per step, and a model that fits the LDS of a slice: D <= 100,847 (1 worker), 75,631 (2),
  *   60,463 (3), 50,415 (4).  RCV1's D = 47,236 fits all four.  A step whose slice layout exceeds 1,024 slots or
- *   4,096 columns of one slice is refused as well (at creation once data and dimSparsity are there, else at the run).
+ *   4,096 columns of one slice is refused as well (at creation once data and dimSparsity are there, else at the run),
+ *   and so is a plan whose slice layout is larger than DSGD_CS_MAX_MB MiB: an fp64 context has no other family to run it.
  *   The existing entry points in an fp64 context:
  *   - dsgd_set_weights / dsgd_set_dim_sparsity (float): the values promoted to fp64.
  *   - dsgd_get_weights (float): the fp64 weights rounded.
@@ -477,8 +478,9 @@ int dsgd_plan_run_f64(dsgd_ctx* ctx, dsgd_plan* plan, int64_t step_begin, int64_
 /* How a plan will run (nothing in the reference; benchmarks, tests): vals[0] = 1 column slices (dsgd_cs_step_kernel),
  * 2 the one-workgroup kernel, 3 virtual tiles, 4 the row-parallel kernels, 5 fp64 column slices, 6 a row-parallel fp64
  * plan (dsgd_plan_create_rp64_n and its kin: strides 0), 0 not laid out yet; [1] slices, [2..4] slot /
- * row / column-list strides, [5] slots per lane, [6] 1 if the device laid it out, [7] words per step of the record.
- * n <= 8 slots.                                                                                                       */
+ * row / column-list strides, [5] slots per lane, [6] 1 if the device laid it out, [7] words per step of the record,
+ * [8] lanes per slice workgroup (512; 256 where DSGD_CS_NT=256 took: [5] is 2 for that kernel and the wide two-slot one).
+ * n <= 9 slots.                                                                                                       */
 int dsgd_plan_info(dsgd_ctx* ctx, dsgd_plan* plan, int32_t* vals, int32_t n);
 /* Parity aid for LONG synchronous runs (nothing in the reference; tests/test_gpu_cs_device.py, tests/test_gpu_host.py, tests/test_sync_replay.py, bench.py): with the record
  * on, every step a column-slice plan runs leaves the GATE DECISION of each of its rows (bit r of the step's words: row r
