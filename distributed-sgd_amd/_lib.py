@@ -46,6 +46,7 @@ SYMBOLS = [
     "dsgd_predict_ranges", "dsgd_predict_ranges_f64",
     "dsgd_plan_create_from_seed_job", "dsgd_plan_create_from_seed_job_rp64",
     "dsgd_loss_acc_list", "dsgd_loss_acc_list_f64", "dsgd_loss_acc_sampled", "dsgd_loss_acc_sampled_f64",
+    "dsgd_async_check", "dsgd_async_check_keep", "dsgd_async_check_weights",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -115,6 +116,10 @@ def load():
         if hasattr(lib, name):   # (ctx, w*, jstate*, row_begin, row_end, samples_count, loss*, acc*, counts*, idx_out*, n*, draws*)
             getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "dsgd_async_check"):   # (ctx, row_begin, row_end, loss*, acc*, counts*, updates_window*)
+        lib.dsgd_async_check.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.dsgd_async_check_keep.argtypes = [C.c_void_p]
+        lib.dsgd_async_check_weights.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     _lib = lib
     return lib
 

@@ -136,6 +136,7 @@ static bool available() {
 #include "dsgd_sparse.hpp" // (the Sparse form at the boundary: compaction and scatter-in)
 #include "dsgd_predict.hpp" // (distributed evaluation: predictions and per-split tallies of K row ranges in one launch)
 #include "dsgd_eval_list.hpp" // (sampled evaluation: the tallies of the rows a device-resident list names in one launch)
+#include "dsgd_snapshot.hpp" // (the consistent loss check beside the lock-free engine: one snapshot of w, its scalars, its window)
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -422,6 +423,13 @@ struct dsgd_ctx {
   long long exchange_every = 0;   // dsgd_async_set_exchange: cross-GPU exchange period in local updates (0 = none)
   DevBuf<float> d_wprev;       // weights at the last exchange
   DevBuf<float> d_wdelta;      // 2 x dp: all-reduced updates, this replica's own part
+  // dsgd_async_check (csrc/dsgd_snapshot.hpp): two snapshots of w in rank order, allocated at the first check -- the last
+  // check's and the best one's (dsgd_async_check_keep makes the last one the best one: the two handles change places, the
+  // next check writes into the other buffer); -1: holds nothing.  reset_layout drops both (the rank order goes).
+  DevBuf<float> d_snap[2];
+  int snap_last = -1, snap_best = -1;
+  DevBuf<unsigned long long> d_snap_win;   // {max ~before, max after} of the last snapshot's update counts
+  HostBuf<unsigned long long> h_snap_win;   // pinned
   bool async_running = false;
   bool join_in_progress = false;            // one thread blocks on the engine (without the mutex); the others wait for it
   std::condition_variable join_cv;
@@ -1743,6 +1751,10 @@ static int prepare_layout(dsgd_ctx* c) {
 }
 // back to the identity layout (before new data is loaded): resident vectors return to key order
 static int reset_layout(dsgd_ctx* c) {
+  // (the snapshots of dsgd_async_check are in the rank order that goes; no engine runs here and the callers have
+  //  synchronised the stream)
+  c->d_snap[0].reset(), c->d_snap[1].reset();
+  c->snap_last = c->snap_best = -1;
   if (c->layout_ready) {
     DSGD_TRY(launch_permute_out(c, c->d_w, c->d_tmp));
     HIP_TRY(hipMemcpyAsync(c->d_w, c->d_tmp, sizeof(float) * c->dp, hipMemcpyDeviceToDevice, c->stream));
@@ -3749,6 +3761,31 @@ static int forward_run(dsgd_ctx* c, const int32_t* idx, int64_t n, float* pred_o
   return check_err_flag(c);
 }
 
+// the row-wise evaluation of rows [row_begin, row_end) on the rank-ordered weights `w` (the resident ones, or a snapshot of
+// them: dsgd_async_check).  beside_engine: the shape that becomes resident next to the persistent Hogwild engine.
+static int launch_eval_rows(dsgd_ctx* c, const float* w, long long row_begin, long long row_end, bool beside_engine) {
+  const int G = c->group;
+  // beside the persistent Hogwild engine (2 waves x 232 VGPRs per SIMD, 136 KB of LDS) only ONE more wave per SIMD
+  // and 16 KB of LDS fit a CU: 256-lane blocks with a small weight tile, one per CU
+  const int bs = beside_engine ? 256 : 1024;
+  const long long groups_per_block = bs / G;
+  const long long rows = row_end - row_begin;
+  dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(c->n_cu, (rows + groups_per_block - 1) / groups_per_block)));
+  // small ranges do not amortise staging 160 KiB of weights per workgroup: shrink the LDS tile
+  const int hw = std::min(beside_engine ? std::min(c->hw_eval, 4096) : (rows >= 4096 ? c->hw_eval : std::min(c->hw_eval, 1024)),
+                          DSGD_LDS_FLOATS - 4);
+  const size_t lds = sizeof(float) * (size_t)(hw + 4);   // (+ the workgroup's three tally words)
+  CsrView m = view(c);
+  switch (G) {
+    case 64: hipLaunchKernelGGL(dsgd_eval_kernel<64>, grid, dim3(bs), lds, c->stream, m, w, row_begin, row_end, c->d_sc, hw); break;
+    case 32: hipLaunchKernelGGL(dsgd_eval_kernel<32>, grid, dim3(bs), lds, c->stream, m, w, row_begin, row_end, c->d_sc, hw); break;
+    case 16: hipLaunchKernelGGL(dsgd_eval_kernel<16>, grid, dim3(bs), lds, c->stream, m, w, row_begin, row_end, c->d_sc, hw); break;
+    default: hipLaunchKernelGGL(dsgd_eval_kernel<8>, grid, dim3(bs), lds, c->stream, m, w, row_begin, row_end, c->d_sc, hw); break;
+  }
+  HIP_TRY(hipGetLastError());
+  return DSGD_OK;
+}
+
 // evaluation in three parts around the all-reduce of its tallies (one host thread, several contexts: dsgd_loss_acc_devices)
 static int eval_enqueue(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row_end) {
   DSGD_TRY(require_data(c));
@@ -3783,25 +3820,7 @@ static int eval_enqueue(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t 
     std::vector<StreamSeg> ssegs(1, make_sseg(row_begin, row_end));
     DSGD_TRY(launch_stream<false>(c, ssegs));
   } else {
-    const int G = c->group;
-    // beside the persistent Hogwild engine (2 waves x 232 VGPRs per SIMD, 136 KB of LDS) only ONE more wave per SIMD
-    // and 16 KB of LDS fit a CU: 256-lane blocks with a small weight tile, one per CU
-    const int bs = c->async_running ? 256 : 1024;
-    const long long groups_per_block = bs / G;
-    const long long rows = row_end - row_begin;
-    dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(c->n_cu, (rows + groups_per_block - 1) / groups_per_block)));
-    // small ranges do not amortise staging 160 KiB of weights per workgroup: shrink the LDS tile
-    const int hw = std::min(c->async_running ? std::min(c->hw_eval, 4096) : (rows >= 4096 ? c->hw_eval : std::min(c->hw_eval, 1024)),
-                            DSGD_LDS_FLOATS - 4);
-    const size_t lds = sizeof(float) * (size_t)(hw + 4);   // (+ the workgroup's three tally words)
-    CsrView m = view(c);
-    switch (G) {
-      case 64: hipLaunchKernelGGL(dsgd_eval_kernel<64>, grid, dim3(bs), lds, c->stream, m, c->d_w, (long long)row_begin, (long long)row_end, c->d_sc, hw); break;
-      case 32: hipLaunchKernelGGL(dsgd_eval_kernel<32>, grid, dim3(bs), lds, c->stream, m, c->d_w, (long long)row_begin, (long long)row_end, c->d_sc, hw); break;
-      case 16: hipLaunchKernelGGL(dsgd_eval_kernel<16>, grid, dim3(bs), lds, c->stream, m, c->d_w, (long long)row_begin, (long long)row_end, c->d_sc, hw); break;
-      default: hipLaunchKernelGGL(dsgd_eval_kernel<8>, grid, dim3(bs), lds, c->stream, m, c->d_w, (long long)row_begin, (long long)row_end, c->d_sc, hw); break;
-    }
-    HIP_TRY(hipGetLastError());
+    DSGD_TRY(launch_eval_rows(c, c->d_w, (long long)row_begin, (long long)row_end, c->async_running));
   }
   return DSGD_OK;
 }
@@ -4640,6 +4659,83 @@ int dsgd_async_stats(dsgd_ctx* c, int64_t* counters, double* s_engine, double* s
     if (c->async_running) c->s_dirty = true;
     *s_exact = (double)c->h_sc->s_reg;
   }
+  return DSGD_OK;
+}
+
+// ---- the consistent loss check (csrc/dsgd_snapshot.hpp; ref: core/MasterAsync.scala:109-138) ----
+// Everything runs on the context's launch stream, beside the engine's: reset of the tallies and of the window, the
+// snapshot kernel (copy + scalars of the copy + window), the row-wise evaluation OF THE SNAPSHOT in the shape that is
+// resident beside the engine -- whether one runs or not: a check's tallies do not depend on the engine's state -- and one
+// read_scalars, the call's only synchronisation.
+int dsgd_async_check(dsgd_ctx* c, int64_t row_begin, int64_t row_end, double* loss, double* acc, int64_t* counts,
+                     int64_t* updates_window) {
+  DSGD_TRY(check_ctx(c));
+  if (row_end <= row_begin)  // samples.map(...).reduce on an empty collection throws (ref: SparseSVM.scala:21-23)
+    return fail(DSGD_EINVAL, "empty row range: reduce on an empty sample list");
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (c->fp64)
+    return fail(DSGD_EUNSUPPORTED, "dsgd_async_check is not available in an fp64 context: its asynchronous schedule runs no "
+                                   "concurrent engine, dsgd_loss_acc between its steps is consistent already");
+  if (c->comm)
+    return fail(DSGD_EUNSUPPORTED, "dsgd_async_check is not available with a communicator attached: dsgd_loss_acc sums the "
+                                   "tallies over the ranks");
+  DSGD_TRY(require_data(c));
+  DSGD_TRY(require_ds(c));
+  if (row_begin < 0 || row_end > c->n_rows)
+    return fail(DSGD_ERANGE, "rows [%lld, %lld) outside the %lld loaded rows", (long long)row_begin, (long long)row_end, c->n_rows);
+  DSGD_TRY(bind(c));
+  DSGD_TRY(prepare_layout(c));   // (done long ago while an engine runs: dsgd_async_start)
+  // the buffer that is not the best one; everything below is ordered on the stream behind the last reader of it
+  const int t = c->snap_best >= 0 ? 1 - c->snap_best : std::max(c->snap_last, 0);
+  DSGD_TRY(c->d_snap[t].reserve((size_t)c->dp));
+  DSGD_TRY(c->d_snap_win.reserve(2));
+  DSGD_TRY(c->h_snap_win.reserve(2));
+  DSGD_TRY(ensure_redpart(c));
+  if (c->snap_last == t) c->snap_last = -1;   // (until the new snapshot is in: a failure below leaves no half-written "last")
+  DSGD_TRY(reset_counters(c));
+  HIP_TRY(hipMemsetAsync(c->d_snap_win, 0, 2 * sizeof(unsigned long long), c->stream));
+  const int blocks = (c->dp + FRA_COLS - 1) / FRA_COLS;
+  hipLaunchKernelGGL(dsgd_snap_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_w, c->d_ds, c->d_snap[t], c->dp,
+                     (float)c->cfg.lambda, c->d_sc, red_out(c), c->d_hog.get(), c->d_snap_win);
+  HIP_TRY(hipGetLastError());
+  // d_sc's s / |w|^2 are the SNAPSHOT's now: dirty for everybody else, as after a check under the engine (eval_enqueue)
+  c->red_par ^= 1;
+  c->s_lazy = false;
+  c->s_dirty = true;
+  DSGD_TRY(launch_eval_rows(c, c->d_snap[t], (long long)row_begin, (long long)row_end, true));
+  HIP_TRY(hipMemcpyAsync(c->h_snap_win, c->d_snap_win, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  DSGD_TRY(eval_read(c, loss, acc, counts));   // (read_scalars: the one synchronisation)
+  c->snap_last = t;
+  if (updates_window) {
+    updates_window[0] = (int64_t)~c->h_snap_win[0];
+    updates_window[1] = (int64_t)c->h_snap_win[1];
+  }
+  return DSGD_OK;
+}
+
+int dsgd_async_check_keep(dsgd_ctx* c) {
+  DSGD_TRY(check_ctx(c));
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (c->snap_last < 0) return fail(DSGD_ESTATE, "no dsgd_async_check since the data was loaded: nothing to keep");
+  c->snap_best = c->snap_last;   // (the handles change places: the next check writes into the other buffer)
+  return DSGD_OK;
+}
+
+int dsgd_async_check_weights(dsgd_ctx* c, int32_t which, float* w_out) {
+  DSGD_TRY(check_ctx(c));
+  if (!w_out) return fail(DSGD_EINVAL, "null w_out");
+  if (which != 0 && which != 1) return fail(DSGD_EINVAL, "which = %d: 0 (the last check's snapshot) or 1 (the best one)", which);
+  std::lock_guard<std::mutex> lk(c->mu);
+  const int t = which == 0 ? c->snap_last : c->snap_best;
+  if (t < 0)
+    return fail(DSGD_ESTATE, which == 0 ? "no dsgd_async_check since the data was loaded" : "no snapshot kept (dsgd_async_check_keep) since the data was loaded");
+  DSGD_TRY(bind(c));
+  const size_t bytes = sizeof(float) * (size_t)c->dp;
+  DSGD_TRY(pin_acquire(c->pin_out, bytes));
+  DSGD_TRY(launch_permute_out(c, c->d_snap[t], c->d_io));
+  HIP_TRY(hipMemcpyAsync(c->pin_out.p, c->d_io, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  memcpy(w_out, c->pin_out.p, bytes);
   return DSGD_OK;
 }
 

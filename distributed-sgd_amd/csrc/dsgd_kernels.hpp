@@ -803,19 +803,26 @@ __global__ void __launch_bounds__(256) dsgd_apply_cols_kernel(float* __restrict_
 
 // s and |w|^2 for weights that were set from outside (dsgd_set_weights, the lock-free engine's weights at a loss
 // check): same blocks, same order as above; 247 blocks instead of one workgroup walking all D + 1 columns (17 us).
+// (the block's part, from ONE weight per lane that owns a column: shared with dsgd_snap_kernel, csrc/dsgd_snapshot.hpp, which
+//  holds the weights it copied in registers -- the two leave the same bits for the same weights)
+__device__ __forceinline__ void wstats_cols_block(bool mine, float wn, float dsj, float lambda, DevScalars* sc,
+                                                  float* __restrict__ redpart, float* fred, int* is_last) {
+  float dot = 0.0f, nsq = 0.0f;
+  if (mine) {
+    dot = filt(wn * dsj);
+    nsq = wn * wn;
+  }
+  fra_scalars(dot, nsq, lambda, sc, redpart, fred, is_last, true);
+}
 __global__ void __launch_bounds__(256) dsgd_wstats_cols_kernel(const float* __restrict__ w, const float* __restrict__ ds,
                                                               int dp, float lambda, DevScalars* sc,
                                                               float* __restrict__ redpart) {
   __shared__ float fred[8];
   __shared__ int is_last;
   const int j = blockIdx.x * FRA_COLS + threadIdx.x;
-  float dot = 0.0f, nsq = 0.0f;
-  if (threadIdx.x < FRA_COLS && j < dp) {
-    const float wn = w[j];
-    dot = filt(wn * ds[j]);
-    nsq = wn * wn;
-  }
-  fra_scalars(dot, nsq, lambda, sc, redpart, fred, &is_last, true);
+  const bool mine = threadIdx.x < FRA_COLS && j < dp;
+  const float wn = mine ? w[j] : 0.0f, dsj = mine ? ds[j] : 0.0f;
+  wstats_cols_block(mine, wn, dsj, lambda, sc, redpart, fred, &is_last);
 }
 
 // segmented scan over the 64 lanes of a wave, DPP only (no LDS round trip)

@@ -554,6 +554,26 @@ class Engine:
         check(self._lib.dsgd_async_stats(self._ctx, cnt, C.byref(a), C.byref(b)))
         return {"updates": cnt[0], "samples": cnt[1], "active": cnt[2], "atomics": cnt[3], "s_engine": a.value, "s_exact": b.value}
 
+    def async_check(self, row_begin, row_end):
+        """MasterAsync's loss check on ONE snapshot of the weights (dsgd_async_check; fp32 engines, running or not):
+        (loss, acc, counts, (updates_lo, updates_hi)) of a copy taken now.  Every update with a commit number <= updates_lo
+        is in the copy whole; later ones may be in it in part.  async_check_keep / async_check_weights hand the copy on."""
+        loss, acc = C.c_double(0), C.c_double(0)
+        counts = (C.c_int64 * 3)()
+        win = (C.c_int64 * 2)()
+        check(self._lib.dsgd_async_check(self._ctx, C.c_int64(row_begin), C.c_int64(row_end), C.byref(loss), C.byref(acc), counts, win))
+        return loss.value, acc.value, list(counts), (win[0], win[1])
+
+    def async_check_keep(self):
+        """The last async_check's snapshot becomes the best one (two device handles change places)."""
+        check(self._lib.dsgd_async_check_keep(self._ctx))
+
+    def async_check_weights(self, which=0):
+        """The snapshot of the last async_check (which = 0) or the kept one (1), key order; the live weights are not touched."""
+        out = np.zeros(self.dp, dtype=np.float32)
+        check(self._lib.dsgd_async_check_weights(self._ctx, C.c_int32(which), ptr(out)))
+        return out
+
     def async_set_trace(self, capacity):
         """Attach a trace of `capacity` update records to the following lock-free runs (0 detaches it)."""
         check(self._lib.dsgd_async_set_trace(self._ctx, C.c_int64(capacity)))

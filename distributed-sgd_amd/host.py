@@ -541,6 +541,11 @@ class _DistributedEval:
 # DSGD_SAMPLED_DEVICE=1: the sample of a sampled check is drawn by the device (Engine.loss_acc_sampled).  Off by default:
 # nobody has measured the device draw of ONE shuffle against the host's (tools/sampled_eval_probe.py is the measurement).
 SAMPLED_DEVICE_DEFAULT = "0"
+# DSGD_ASYNC_SNAPSHOT=1: MasterAsync.fit on an fp32 backend checks the loss through Engine.async_check -- loss, accuracy,
+# update count and best weights of a check describe ONE snapshot of the moving weights (core/MasterAsync.scala:109-138), and
+# the best weights stay on the device until the engine has stopped.  Off by default: nobody has measured a check through it
+# against loss_acc + get_weights (tools/async_check_probe.py is the measurement).
+ASYNC_SNAPSHOT_DEFAULT = "0"
 
 
 def sampled_list(rnd: JavaRandom, length: int, samples_count: int, native: Optional[bool] = None):
@@ -1035,17 +1040,28 @@ class MasterAsync(_DistributedEval, _SampledEval):
         best_w, best_loss = np.asarray(initial_weights, dtype=np.float32), float("inf")
         last_step = -check_every
         state = GradState(best_w)
+        # DSGD_ASYNC_SNAPSHOT=1: loss, accuracy, best weights and the update count of a check describe ONE snapshot
+        snapshot = os.environ.get("DSGD_ASYNC_SNAPSHOT", ASYNC_SNAPSHOT_DEFAULT) == "1" and hasattr(self.backend, "async_check")
+        kept = False
         try:
             while True:
                 updates, running = self.backend.async_updates()
                 if updates - last_step >= check_every or not running:
-                    computed_loss, computed_acc, _ = self.backend.loss_acc(self.n_train, self.n_rows)
+                    if snapshot:
+                        computed_loss, computed_acc, _, window = self.backend.async_check(self.n_train, self.n_rows)
+                        updates = int(window[0])   # (every update up to here is in the weights the loss is of)
+                    else:
+                        computed_loss, computed_acc, _ = self.backend.loss_acc(self.n_train, self.n_rows)
                     prev_l = self.test_losses[0] if self.test_losses else computed_loss
                     prev_a = self.test_accs[0] if self.test_accs else computed_acc
                     loss = leak_loss_coef * computed_loss + (1 - leak_loss_coef) * prev_l   # :122-125
                     acc = leak_loss_coef * computed_acc + (1 - leak_loss_coef) * prev_a
                     if best_loss > loss:                                                     # :132-138
-                        best_loss, best_w = loss, self.backend.get_weights()
+                        if snapshot:
+                            best_loss, kept = loss, True
+                            self.backend.async_check_keep()   # (two device handles change places; read once, after the stop)
+                        else:
+                            best_loss, best_w = loss, self.backend.get_weights()
                     self.test_losses.insert(0, loss)
                     self.test_accs.insert(0, acc)
                     last_step = updates
@@ -1058,6 +1074,8 @@ class MasterAsync(_DistributedEval, _SampledEval):
                     time.sleep(self.poll_s)
         finally:
             self.backend.async_stop()                                                        # endComputation :87-94
+        if kept:
+            best_w = self.backend.async_check_weights(1)
         updates, _ = self.backend.async_updates()
         state = GradState(best_w, updates=int(updates)).finish(best_loss)
         return state

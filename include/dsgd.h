@@ -693,6 +693,31 @@ int dsgd_async_stop(dsgd_ctx* ctx); /* SlaveImpl.stopAsync, core/Slave.scala:187
  * (counters[0], what MasterAsync polls, is exact at any time).                                                      */
 int dsgd_async_stats(dsgd_ctx* ctx, int64_t* counters, double* s_engine, double* s_exact);
 int dsgd_async_wait(dsgd_ctx* ctx); /* block until max_updates reached */
+/* MasterAsync's loss check on ONE weight snapshot (core/MasterAsync.scala:109-138: loss, accuracy, bestGrad and the update
+ * count all come from one innerGradState).  While the lock-free engine runs, dsgd_loss_acc and dsgd_get_weights each see
+ * the weights at another moment; these three calls see one copy of them (csrc/dsgd_snapshot.hpp).  fp32 contexts without
+ * a communicator; allowed while the engine runs and while it does not.
+ * dsgd_async_check: copies the resident weights into a device buffer (every weight read once, as the engine reads it),
+ * and returns loss and accuracy OF THAT COPY over rows [row_begin, row_end): loss = lambda |snap|^2 + (c1 + 2 c2) / n,
+ * acc = c0 / n with the tallies counts = {#p==y, #p==0, #p==-y} (loss, acc, counts may be NULL) -- dsgd_loss_acc's
+ * expression, kernels and summation orders, so on a context at rest the two calls agree bit for bit.  updates_window
+ * (may be NULL) = {lo, hi}, update counts read around the copy: every update with a commit number <= lo is contained in
+ * the snapshot WHOLE (an update's additions are drained before its number is drawn); an update with a larger number may
+ * be contained in part, those above hi included (an update in flight adds before it has a number); hi is the count read
+ * behind the last weight.  With no engine running lo = hi = dsgd_async_updates.  One host synchronisation; the engine's
+ * stream is never touched.
+ * dsgd_async_check_keep: the last check's snapshot becomes the best one (two handles change places: no kernel, no copy).
+ * dsgd_async_check_weights: the last check's snapshot (which = 0) or the kept one (which = 1) in key order, D + 1 floats;
+ * neither call touches the live weights.
+ * Errors, with nothing enqueued and nothing changed: DSGD_EINVAL for a null context or w_out, an empty range, which
+ * outside {0, 1}; DSGD_ERANGE for rows outside the data; DSGD_ESTATE with no data or no dimSparsity, for _keep without a
+ * check and for _weights without the snapshot asked for since the last dsgd_load_csr (a load changes the internal
+ * column order and drops both); DSGD_EUNSUPPORTED on an fp64 context (its asynchronous schedule runs no concurrent
+ * engine: dsgd_loss_acc is consistent there) and with a communicator attached (dsgd_loss_acc sums over the ranks).    */
+int dsgd_async_check(dsgd_ctx* ctx, int64_t row_begin, int64_t row_end, double* loss, double* acc,
+                     int64_t* counts /* 3 or NULL */, int64_t* updates_window /* {lo, hi} or NULL */);
+int dsgd_async_check_keep(dsgd_ctx* ctx);
+int dsgd_async_check_weights(dsgd_ctx* ctx, int32_t which /* 0 last, 1 best */, float* w_out /* D+1, key order */);
 /* Parity aid for the MANY-worker lock-free engine (nothing in the reference; tests/test_gpu_hogwild_trace.py, bench.py):
  * with a trace of `capacity` records attached (0 detaches it), every mini-batch update of the following engine runs
  * leaves one record at index (its commit number - 1): the worker that made it, that worker's iteration number (the key

@@ -347,6 +347,29 @@ class SparseSVM {
     check(dsgd_loss_acc(ctx_, w.data(), rowBegin, rowEnd, &l, &a, nullptr));
     return a;
   }
+  // MasterAsync's loss check on ONE snapshot of the weights while the lock-free engine runs (dsgd_async_check;
+  // core/MasterAsync.scala:109-138): loss, accuracy and tallies of a copy taken now, and the update counts read around the
+  // copy -- every update with a commit number <= updatesLo is in it whole.  asyncCheckKeep makes that copy the best one,
+  // asyncCheckWeights reads the last (best = false) or the kept one (best = true) without touching the live weights.
+  struct AsyncCheck {
+    double loss = 0, accuracy = 0;
+    int64_t counts[3] = {0, 0, 0};   // {#p==y, #p==0, #p==-y}
+    int64_t updatesLo = 0, updatesHi = 0;
+  };
+  AsyncCheck asyncCheck(int64_t rowBegin, int64_t rowEnd) {
+    AsyncCheck r;
+    int64_t win[2] = {0, 0};
+    check(dsgd_async_check(ctx_, rowBegin, rowEnd, &r.loss, &r.accuracy, r.counts, win));
+    r.updatesLo = win[0];
+    r.updatesHi = win[1];
+    return r;
+  }
+  void asyncCheckKeep() { check(dsgd_async_check_keep(ctx_)); }
+  Vec asyncCheckWeights(bool best) {
+    Vec w((size_t)d_ + 1);
+    check(dsgd_async_check_weights(ctx_, best ? 1 : 0, w.data()));
+    return w;
+  }
   // The forward passes of all workers' splits in one launch (dsgd_predict_ranges; core/Master.scala:61-98): one int8 in
   // {-1, 0, +1} per row, range-major, the exact tallies {#p==y, #p==0, #p==-y} per range, and loss / accuracy folded
   // over all the rows.
