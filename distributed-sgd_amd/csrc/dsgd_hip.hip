@@ -2780,8 +2780,7 @@ static int load_csr_impl(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in,
   c->last_grad_kernel = "";  // (dsgd_grad_kernel_name / dsgd_tuning_info report launches over THIS data: calls that record none --
   c->last_shift = FIX_SHIFT; //  the row-parallel fp64 requests -- would go on reporting the old data's)
   // (the wave tiles cover the hot stream and are built with the layout, at the first compute call)
-  const double mean = (double)nnz / (double)n_rows;
-  c->group = mean > 192.0 ? 64 : (mean > 96.0 ? 32 : (mean > 12.0 ? 16 : 8));
+  c->group = eval_group(nnz, n_rows);
   return DSGD_OK;
 }
 
@@ -5269,10 +5268,11 @@ int dsgd_debug_cycles(dsgd_ctx* c, uint64_t* out8, int32_t reset) {
 
 int dsgd_tuning_info(dsgd_ctx* c, int32_t* vals, int32_t n) {
   DSGD_TRY(check_ctx(c));
-  if (!vals || n < 0 || n > 7) return fail(DSGD_EINVAL, "bad tuning_info arguments");
+  if (!vals || n < 0 || n > 8) return fail(DSGD_EINVAL, "bad tuning_info arguments");
   std::lock_guard<std::mutex> lk(c->mu);
-  const int32_t all[7] = {4 /* split layout: the only one */, std::min(c->hsplit, c->dp), c->last_shift,
-                          c->cold_col16 ? 1 : 0, c->k.plan_kernel ? 1 : 0, c->k.fix_bound ? 1 : 0, c->last_fstep_rebalances};
+  const int32_t all[8] = {4 /* split layout: the only one */, std::min(c->hsplit, c->dp), c->last_shift,
+                          c->cold_col16 ? 1 : 0, c->k.plan_kernel ? 1 : 0, c->k.fix_bound ? 1 : 0, c->last_fstep_rebalances,
+                          c->group};
   for (int i = 0; i < n; ++i) vals[i] = all[i];
   return DSGD_OK;
 }

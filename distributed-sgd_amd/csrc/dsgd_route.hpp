@@ -9,6 +9,7 @@
 //                                                                                     virtual tiles / row-wise
 //   route_request  dsgd_sync_step                                                   -> the same families for ONE step of index lists
 //   TcolGate       the column lists' back-off from callers that never repeat a configuration
+//   eval_group     dsgd_load_csr[_f64]: lanes per row of the fp32 row-wise evaluation kernels
 #pragma once
 
 #include <algorithm>
@@ -221,6 +222,16 @@ inline int cs_pick_G(const Knobs& k, const RouteFacts& f, int K, bool request) {
   int G = k.cs_g ? k.cs_g : (K <= 4 ? 8 : 16);
   if (!k.cs_g && G == 8 && !fits(8)) G = 16;
   return fits(G) ? G : 0;
+}
+
+// lanes per row of the fp32 row-wise evaluation kernels (dsgd_forward_kernel, dsgd_eval_kernel, dsgd_predict_kernel,
+// dsgd_eval_list_kernel) for data of nnz non-zeros in n_rows rows, chosen when the data is loaded: a row of mean length
+// gives a lane at most 6 products (below 64 lanes).  The mean is taken in double; a mean ON a threshold keeps the narrower
+// group.  nnz is the count the context HOLDS (dsgd_n_rows): a row without a non-zero owns one explicit zero there, so six
+// empty rows weigh six entries.  (No rows: 0 / 0 compares false everywhere, 8.)  dsgd_tuning_info reports it in slot [7].
+inline int eval_group(long long nnz, long long n_rows) {
+  const double mean = (double)nnz / (double)n_rows;
+  return mean > 192.0 ? 64 : (mean > 96.0 ? 32 : (mean > 12.0 ? 16 : 8));
 }
 
 // ---- row ranges: column lists first where they are wanted, then row chunks / the streaming launches / the row-wise kernel ----

@@ -55,6 +55,15 @@ class Plan:
         return bits, s
 
 
+class TuningInfo(dict):
+    """Engine.tuning_info(): a plain dict by name (what bench.py records); an int key reads the slot of that number."""
+
+    SLOTS = ("stream_mode", "hsplit", "fix_shift", "cold_packed", "plan_kernel", "fix_bound", "fstep_rebalances", "eval_group")
+
+    def __getitem__(self, key):
+        return dict.__getitem__(self, self.SLOTS[key] if isinstance(key, int) else key)
+
+
 class Engine:
     def __init__(self, n_features, lam, device=0, flags=0, precision="fp32"):
         """precision: "fp32" (default) or "fp64" -- the fp64 mode (DSGD_F_FP64, include/dsgd.h "THE FP64 MODE"): fp64
@@ -663,10 +672,15 @@ class Engine:
         return a.value, b.value
 
     def tuning_info(self):
-        v = (C.c_int32 * 7)()
-        if self._lib.dsgd_tuning_info(self._ctx, v, C.c_int32(7)) != 0:   # (an older build in an A/B run: six slots)
+        """dsgd_tuning_info's slots by name; a slot number reads the same value (tuning_info()[7] is "eval_group": the lanes
+        per row of the fp32 row-wise evaluation kernels for the loaded data)."""
+        v = (C.c_int32 * 8)()
+        n = 8
+        while n > 6 and self._lib.dsgd_tuning_info(self._ctx, v, C.c_int32(n)) != 0:   # (an older build in an A/B run: seven or six slots)
+            n -= 1
+        if n == 6:
             check(self._lib.dsgd_tuning_info(self._ctx, v, C.c_int32(6)))
-        return dict(zip(("stream_mode", "hsplit", "fix_shift", "cold_packed", "plan_kernel", "fix_bound", "fstep_rebalances"), [int(x) for x in v]))
+        return TuningInfo(zip(TuningInfo.SLOTS[:max(n, 7)], [int(x) for x in v]))
 
     def column_ranks(self):
         """Internal frequency rank of every key (D + 1 entries); identical on all ranks of a communicator."""

@@ -799,8 +799,12 @@ int dsgd_range_nnz(dsgd_ctx* ctx, int64_t row_begin, int64_t row_end, int64_t* n
  * kernel, which derives 30 - ceil(log2 batch) per batch), [3] = 1 if the cold stream is packed, [4] = 1 if small
  * batches run in the persistent plan kernel, [5] = 1 if the data-dependent fixed-point bound is enabled, [6] = how often
  * the row chunks of the last chunked launch's configuration have been re-cut by their workgroups' measured durations (0-2;
- * only with DSGD_FSTEP_REBALANCE=1: measured at 1 %, off by default -- the re-cut moves rows between workgroups, it changes no bit of any sum).
- * n = number of slots the caller provides (<= 7).                                                                 */
+ * only with DSGD_FSTEP_REBALANCE=1: measured at 1 %, off by default -- the re-cut moves rows between workgroups, it changes no bit of any sum),
+ * [7] = lanes per row of the fp32 row-wise evaluation kernels (dsgd_forward, dsgd_predict_ranges, dsgd_loss_acc_list /
+ * _sampled, dsgd_async_check, dsgd_loss_acc below 4,096 rows) for the loaded data: 8, 16, 32 or 64 from the mean
+ * non-zeros per row (above 12: 16, above 96: 32, above 192: 64; over the non-zeros as dsgd_n_rows reports them, where
+ * a row without a non-zero counts one), chosen by dsgd_load_csr[_f64]; 16 before any data is loaded.  The width fixes the order in which a row's products are added, nothing else; the fp64 kernels always use 16.
+ * n = number of slots the caller provides (<= 8).                                                                 */
 int dsgd_tuning_info(dsgd_ctx* ctx, int32_t* vals, int32_t n);
 
 /* Layout introspection (tests of the multi-GPU path): the internal frequency rank of every key, D + 1 entries.  With a

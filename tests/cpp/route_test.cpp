@@ -4,7 +4,8 @@
 // Two kinds of check:
 //   (a) outright assertions: every knob's default and clamp, both sides of every threshold of the row ranges' route at the
 //       default knobs and RCV1's shape, the order of precedence of the plan and request routes, the slice count against the
-//       host builder's wording, the column lists' back-off step by step;
+//       host builder's wording, the column lists' back-off step by step, both sides of every threshold of the evaluation
+//       kernels' lanes per row (eval_group) against the expression dsgd_load_csr held;
 //   (b) a 64-bit FNV-1a digest of every function's outputs over a fixed grid (the edge values x each knob changed alone x the
 //       context's facts), held to constants recorded from the lines these functions replaced in csrc/dsgd_hip.hip at commit
 //       09dd9cb: the same grid driver (digest_grid below) ran over those lines, pasted around a stand-in context, in a
@@ -542,9 +543,38 @@ static void test_tcol_gate() {
   CHECK(g.cooldown == 256 && !g.miss());
 }
 
+// lanes per row of the fp32 row-wise evaluation kernels: the expression dsgd_load_csr held, `mean > 192.0 ? 64 : (mean > 96.0 ?
+// 32 : (mean > 12.0 ? 16 : 8))` with mean = (double)nnz / (double)n_rows, restated here and compared over a grid; both sides of
+// every threshold at 1, 7 and 2^31 rows (the quotient of 12 n + 1 and n = 2^31 is 12 + 2^-31: a double holds it, a float would
+// not); the degenerate inputs.
+static int load_csr_group(long long nnz, long long n_rows) {
+  const double mean = (double)nnz / (double)n_rows;
+  return mean > 192.0 ? 64 : (mean > 96.0 ? 32 : (mean > 12.0 ? 16 : 8));
+}
+static void test_eval_group() {
+  for (long long n : {1LL, 7LL, 1LL << 31}) {
+    CHECK(eval_group(12 * n, n) == 8 && eval_group(12 * n + 1, n) == 16);
+    CHECK(eval_group(96 * n, n) == 16 && eval_group(96 * n + 1, n) == 32);
+    CHECK(eval_group(192 * n, n) == 32 && eval_group(192 * n + 1, n) == 64);
+    CHECK(eval_group(12 * n - 1, n) == 8 && eval_group(96 * n - 1, n) == 16 && eval_group(192 * n - 1, n) == 32);
+    CHECK(eval_group(0, n) == 8 && eval_group(n, n) == 8 && eval_group(75 * n, n) == 16 && eval_group(1000 * n, n) == 64);
+  }
+  // no rows (dsgd_load_csr refuses them; the expression's own answer): 0 / 0 is no number and compares false, n / 0 is +inf
+  CHECK(eval_group(0, 0) == 8 && eval_group(5, 0) == 64);
+  long long differing = 0;
+  for (long long n : {1LL, 2LL, 3LL, 7LL, 100LL, 4095LL, 804414LL, (1LL << 31) - 1, 1LL << 31, 1LL << 40})
+    for (long long per : {0LL, 1LL, 11LL, 12LL, 13LL, 95LL, 96LL, 97LL, 191LL, 192LL, 193LL, 5000LL})
+      for (long long d = -2; d <= 2; ++d) {
+        const long long nnz = per * n + d;
+        if (nnz >= 0) differing += eval_group(nnz, n) != load_csr_group(nnz, n);
+      }
+  CHECK(differing == 0);
+}
+
 int main() {
   uint64_t got[8];
   digest_grid(got);
+  test_eval_group();
   test_knobs();
   test_route_ranges();
   test_route_plan_and_request();

@@ -2,8 +2,8 @@
 
 The header alone (with csrc/dsgd_limits.hpp and csrc/dsgd_layout_types.hpp), compiled with AddressSanitizer and UBSan and run as
 a program of its own (tests/cpp/route_test.cpp).  The program asserts every knob's default and clamp, both sides of every
-threshold of the row ranges' route, the precedence of the plan and request routes, the slice count over its whole domain and
-the column lists' back-off; it also holds a digest of every function's outputs over a fixed grid to constants recorded from
+threshold of the row ranges' route, the precedence of the plan and request routes, the slice count over its whole domain,
+the column lists' back-off and the lanes per row of the evaluation kernels at their thresholds; it also holds a digest of every function's outputs over a fixed grid to constants recorded from
 the lines of csrc/dsgd_hip.hip that the header replaced."""
 
 import os
