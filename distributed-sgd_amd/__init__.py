@@ -13,7 +13,7 @@ The directory name is not an importable identifier; `import dsgd_amd` (repo root
 
 from . import _build, _lib, host, rcv1, synth, wire  # noqa: F401
 from ._lib import DsgdError, DsgdIndexError, DsgdInvalidArgument  # noqa: F401
-from .dense import DenseLogistic  # noqa: F401
+from .dense import DenseLogistic, DensePlan  # noqa: F401
 from .engine import Engine, EngineGroup, Plan, device_count  # noqa: F401
 
-__all__ = ["Engine", "EngineGroup", "Plan", "DenseLogistic", "device_count", "synth", "host", "rcv1", "wire", "DsgdError", "DsgdIndexError", "DsgdInvalidArgument"]
+__all__ = ["Engine", "EngineGroup", "Plan", "DenseLogistic", "DensePlan", "device_count", "synth", "host", "rcv1", "wire", "DsgdError", "DsgdIndexError", "DsgdInvalidArgument"]

@@ -32,6 +32,8 @@ SYMBOLS = [
     "dsgd_dense_create", "dsgd_dense_destroy", "dsgd_dense_generate", "dsgd_dense_load", "dsgd_dense_set_weights",
     "dsgd_dense_get_weights", "dsgd_dense_step", "dsgd_dense_synchronize", "dsgd_dense_loss", "dsgd_dense_comm_init",
     "dsgd_dense_prof",
+    "dsgd_dense_step_list", "dsgd_dense_loss_list", "dsgd_dense_predict", "dsgd_dense_predict_list",
+    "dsgd_dense_plan_create", "dsgd_dense_plan_run", "dsgd_dense_plan_destroy",
     "dsgd_set_weights_f64", "dsgd_get_weights_f64", "dsgd_set_dim_sparsity_f64", "dsgd_get_dim_sparsity_f64",
     "dsgd_plan_run_f64", "dsgd_precision",
     "dsgd_async_step_f64", "dsgd_update_grad_f64", "dsgd_async_plan_create", "dsgd_plan_run_async_f64",
@@ -120,6 +122,14 @@ def load():
         lib.dsgd_async_check.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.dsgd_async_check_keep.argtypes = [C.c_void_p]
         lib.dsgd_async_check_weights.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    if hasattr(lib, "dsgd_dense_plan_create"):   # (handles are 64-bit: without argtypes ctypes would pass them as C ints)
+        lib.dsgd_dense_step_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float]
+        lib.dsgd_dense_loss_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.dsgd_dense_predict.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        lib.dsgd_dense_predict_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dsgd_dense_plan_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dsgd_dense_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float]
+        lib.dsgd_dense_plan_destroy.argtypes = [C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 

@@ -29,30 +29,49 @@ struct DenseArgs {
   const float* __restrict__ w;      // D
   float* __restrict__ gpart;        // gridDim.x x D per-workgroup sums of (p - y) * x  (null: evaluation only)
   double* __restrict__ lpart;       // gridDim.x x 2: sum of losses, correct predictions
-  long long row_begin, row_end;
+  long long row_begin, row_end;    // positions [row_begin, row_end): a position IS its row (range form) or names idx[k] (list form)
   int D;
+};
+// What the list and probability instantiations take on top (a struct of their own: the range kernels' kernel
+// arguments, and so their code, stay as they were).  List form: position k of [0, n) names row idx[k] -- a.row_begin
+// is 0 and a.row_end is n.  The host has checked every entry against n_rows (csrc/dsgd_hip.hip dn_check_list): no
+// index is looked at again here.
+struct DenseListArgs {
+  DenseArgs a;
+  const int* __restrict__ idx;      // n row numbers (null: range form)
+  float* __restrict__ p_out;        // n probabilities, p_out[k - row_begin] = sigmoid(z) of position k (null: none)
 };
 
 // One workgroup of D / 8 lanes per row block: lane t owns columns [4t, 4t+4) and [D/2 + 4t, D/2 + 4t + 4) of every
 // row (each wave-level load is 1 KB of one row).  Two workgroups share a CU (<= 128 VGPRs each): one computes while
 // the other's loads are in flight.
-__global__ void __launch_bounds__(1024) dsgd_dense_step_kernel(DenseArgs a) {
+//
+// ONE body for every form, LIST: a block is 8 consecutive list POSITIONS, position k reads row idx[k] at
+// (long long)idx[k] * D and label y[idx[k]]; the blocks are dealt to the workgroups by position exactly as row blocks
+// are, so a list step is, operation for operation, the range step over the rows the list names.  PROBA: forward only,
+// the lane that owns a row's z also stores sigmoid(z) to p_out[position - row_begin] (one plain vector store per row).
+// n_lanes / n_wg are the kernel's blockDim.x / gridDim.x, read in the __global__ wrapper (where the compiler knows the
+// workgroups to be uniform) and handed in.
+template <bool LIST, bool PROBA>
+__device__ __forceinline__ void dn_step_body(const DenseArgs& a, const int* __restrict__ idx, float* __restrict__ p_out,
+                                                  const unsigned n_lanes, const unsigned n_wg) {
   __shared__ float zpart[16][DN_ROWS];
   __shared__ float rl[DN_ROWS];
   __shared__ double lred[2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = n_lanes >> 6;
   const int c0 = 4 * tid, c1 = a.D / 2 + 4 * tid;
   const float4 w0 = *reinterpret_cast<const float4*>(a.w + c0), w1 = *reinterpret_cast<const float4*>(a.w + c1);
   float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0;
   double loss_acc = 0.0, corr_acc = 0.0;   // (thread r < DN_ROWS accumulates row r of every block)
   const long long n_blocks = (a.row_end - a.row_begin + DN_ROWS - 1) / DN_ROWS;
-  for (long long blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
+  for (long long blk = blockIdx.x; blk < n_blocks; blk += n_wg) {
     const long long r0 = a.row_begin + blk * DN_ROWS;
     float4 x0[DN_ROWS], x1[DN_ROWS];
 #pragma unroll
     for (int i = 0; i < DN_ROWS; ++i) {
       const bool in = r0 + i < a.row_end;
-      const float* row = a.X + (in ? r0 + i : a.row_begin) * (long long)a.D;
+      const long long k = in ? r0 + i : a.row_begin;   // (a tail position reads a valid row; its residual is 0)
+      const float* row = a.X + (LIST ? (long long)idx[k] : k) * (long long)a.D;
       x0[i] = *reinterpret_cast<const float4*>(row + c0);
       x1[i] = *reinterpret_cast<const float4*>(row + c1);
     }
@@ -75,9 +94,10 @@ __global__ void __launch_bounds__(1024) dsgd_dense_step_kernel(DenseArgs a) {
       float z = 0.0f;
       for (int wv = 0; wv < n_waves; ++wv) z += zpart[wv][tid];
       const bool in = r0 + tid < a.row_end;
-      const float yy = in ? a.y[r0 + tid] : 0.0f;
+      const float yy = in ? a.y[LIST ? (long long)idx[r0 + tid] : r0 + tid] : 0.0f;
       const float p = 1.0f / (1.0f + __expf(-z));
       rl[tid] = in ? p - yy : 0.0f;
+      if (PROBA && in) p_out[r0 + tid - a.row_begin] = p;
       if (in) {
         // softplus(z) - y z, evaluated without overflow: max(z, 0) + log1p(exp(-|z|)) - y z
         loss_acc += (double)(fmaxf(z, 0.0f) + log1pf(__expf(-fabsf(z))) - yy * z);
@@ -86,7 +106,7 @@ __global__ void __launch_bounds__(1024) dsgd_dense_step_kernel(DenseArgs a) {
     }
     __syncthreads();
     // gradient: the same registers
-    if (a.gpart) {
+    if (!PROBA && a.gpart) {
 #pragma unroll
       for (int i = 0; i < DN_ROWS; ++i) {
         const float r = rl[i];
@@ -101,7 +121,7 @@ __global__ void __launch_bounds__(1024) dsgd_dense_step_kernel(DenseArgs a) {
       }
     }
   }
-  if (a.gpart) {
+  if (!PROBA && a.gpart) {
     float* mine = a.gpart + (long long)blockIdx.x * a.D;
     *reinterpret_cast<float4*>(mine + c0) = g0;
     *reinterpret_cast<float4*>(mine + c1) = g1;
@@ -118,6 +138,10 @@ __global__ void __launch_bounds__(1024) dsgd_dense_step_kernel(DenseArgs a) {
     a.lpart[2 * blockIdx.x + 1] = lred[1];
   }
 }
+__global__ void __launch_bounds__(1024) dsgd_dense_step_kernel(DenseArgs a) { dn_step_body<false, false>(a, nullptr, nullptr, blockDim.x, gridDim.x); }
+__global__ void __launch_bounds__(1024) dsgd_dense_step_list_kernel(DenseListArgs l) { dn_step_body<true, false>(l.a, l.idx, l.p_out, blockDim.x, gridDim.x); }
+__global__ void __launch_bounds__(1024) dsgd_dense_proba_kernel(DenseListArgs l) { dn_step_body<false, true>(l.a, l.idx, l.p_out, blockDim.x, gridDim.x); }
+__global__ void __launch_bounds__(1024) dsgd_dense_proba_list_kernel(DenseListArgs l) { dn_step_body<true, true>(l.a, l.idx, l.p_out, blockDim.x, gridDim.x); }
 
 // ---- the MFMA variant north_star names ("mini-batch GEMV via MFMA"), selectable with DSGD_DENSE_MFMA=1 -----------
 // Forward product on the matrix cores: v_mfma_f32_16x16x4_f32 with A = a 16-row x 4-column tile of X (lane l: row
@@ -137,23 +161,27 @@ __global__ void __launch_bounds__(1024) dsgd_dense_step_kernel(DenseArgs a) {
 //  time, tools/dense_check.py; 128 VGPRs + 56 bytes of scratch) -- slower than this form (0.61).  Not kept;
 //  profiles/r06_dense_pmc_summary.txt.)
 typedef float dn_f32x4 __attribute__((ext_vector_type(4)));
-__global__ void __launch_bounds__(1024) dsgd_dense_step_mfma_kernel(DenseArgs a) {
+// (LIST / PROBA as in dn_step_body: a block is 16 consecutive list positions)
+template <bool LIST, bool PROBA>
+__device__ __forceinline__ void dn_step_mfma_body(const DenseArgs& a, const int* __restrict__ idx, float* __restrict__ p_out,
+                                                       const unsigned n_lanes, const unsigned n_wg) {
   extern __shared__ __attribute__((aligned(16))) float wl[];   // D weights
   __shared__ float zpart[16][16];
   __shared__ float rl[16];
   __shared__ double lred[2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = n_lanes >> 6;
   const int i = lane & 15, q = lane >> 4;
-  for (int j = tid * 4; j < a.D; j += blockDim.x * 4) *reinterpret_cast<float4*>(wl + j) = *reinterpret_cast<const float4*>(a.w + j);
+  for (int j = tid * 4; j < a.D; j += n_lanes * 4) *reinterpret_cast<float4*>(wl + j) = *reinterpret_cast<const float4*>(a.w + j);
   __syncthreads();
   const int cw = 256 * wave;
   float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);   // columns cw + 16 i + 4 q .. + 3
   double loss_acc = 0.0, corr_acc = 0.0;
   const long long n_blocks = (a.row_end - a.row_begin + 15) / 16;
-  for (long long blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
+  for (long long blk = blockIdx.x; blk < n_blocks; blk += n_wg) {
     const long long r0 = a.row_begin + blk * 16;
     const bool in_i = r0 + i < a.row_end;
-    const float* row = a.X + (in_i ? r0 + i : a.row_begin) * (long long)a.D + cw + 4 * q;
+    const long long k = in_i ? r0 + i : a.row_begin;
+    const float* row = a.X + (LIST ? (long long)idx[k] : k) * (long long)a.D + cw + 4 * q;
     float4 x[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) x[m] = *reinterpret_cast<const float4*>(row + 16 * m);
@@ -177,16 +205,17 @@ __global__ void __launch_bounds__(1024) dsgd_dense_step_mfma_kernel(DenseArgs a)
       float z = 0.0f;
       for (int wv = 0; wv < n_waves; ++wv) z += zpart[wv][tid];
       const bool in = r0 + tid < a.row_end;
-      const float yy = in ? a.y[r0 + tid] : 0.0f;
+      const float yy = in ? a.y[LIST ? (long long)idx[r0 + tid] : r0 + tid] : 0.0f;
       const float p = 1.0f / (1.0f + __expf(-z));
       rl[tid] = in ? p - yy : 0.0f;
+      if (PROBA && in) p_out[r0 + tid - a.row_begin] = p;
       if (in) {
         loss_acc += (double)(fmaxf(z, 0.0f) + log1pf(__expf(-fabsf(z))) - yy * z);
         corr_acc += ((z > 0.0f) == (yy > 0.5f)) ? 1.0 : 0.0;
       }
     }
     __syncthreads();
-    if (a.gpart) {
+    if (!PROBA && a.gpart) {
       const float r = rl[i];
 #pragma unroll
       for (int m = 0; m < 16; ++m) {
@@ -201,7 +230,7 @@ __global__ void __launch_bounds__(1024) dsgd_dense_step_mfma_kernel(DenseArgs a)
       }
     }
   }
-  if (a.gpart) *reinterpret_cast<float4*>(a.gpart + (long long)blockIdx.x * a.D + cw + 16 * i + 4 * q) = g4;
+  if (!PROBA && a.gpart) *reinterpret_cast<float4*>(a.gpart + (long long)blockIdx.x * a.D + cw + 16 * i + 4 * q) = g4;
   if (tid == 0) lred[0] = lred[1] = 0.0;
   __syncthreads();
   if (tid < 16) {
@@ -214,6 +243,10 @@ __global__ void __launch_bounds__(1024) dsgd_dense_step_mfma_kernel(DenseArgs a)
     a.lpart[2 * blockIdx.x + 1] = lred[1];
   }
 }
+__global__ void __launch_bounds__(1024) dsgd_dense_step_mfma_kernel(DenseArgs a) { dn_step_mfma_body<false, false>(a, nullptr, nullptr, blockDim.x, gridDim.x); }
+__global__ void __launch_bounds__(1024) dsgd_dense_step_list_mfma_kernel(DenseListArgs l) { dn_step_mfma_body<true, false>(l.a, l.idx, l.p_out, blockDim.x, gridDim.x); }
+__global__ void __launch_bounds__(1024) dsgd_dense_proba_mfma_kernel(DenseListArgs l) { dn_step_mfma_body<false, true>(l.a, l.idx, l.p_out, blockDim.x, gridDim.x); }
+__global__ void __launch_bounds__(1024) dsgd_dense_proba_list_mfma_kernel(DenseListArgs l) { dn_step_mfma_body<true, true>(l.a, l.idx, l.p_out, blockDim.x, gridDim.x); }
 
 // g = sum of the per-workgroup partials (fixed order: reproducible) and, without a communicator, the update in the
 // same pass.  Block = 64 columns x 16 phases over the partials (one thread per column summing 512 partials

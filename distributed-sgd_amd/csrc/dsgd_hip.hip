@@ -590,11 +590,12 @@ static int pin_acquire(dsgd_ctx::Pinned& b, size_t bytes) {
   if (!b.ev) HIP_TRY(hipEventCreateWithFlags(&b.ev.e, hipEventDisableTiming));
   return DSGD_OK;
 }
-static int pin_sent(dsgd_ctx* c, dsgd_ctx::Pinned& b, hipStream_t on = nullptr) {
-  HIP_TRY(hipEventRecord(b.ev, on ? on : c->stream));
+static int pin_sent(dsgd_ctx::Pinned& b, hipStream_t on) {   // (owners other than a context: the dense object)
+  HIP_TRY(hipEventRecord(b.ev, on));
   b.armed = true;
   return DSGD_OK;
 }
+static int pin_sent(dsgd_ctx* c, dsgd_ctx::Pinned& b, hipStream_t on = nullptr) { return pin_sent(b, on ? on : c->stream); }
 
 static int ensure_g(dsgd_ctx* c, int n_workers) {
   const size_t n = (size_t)n_workers * c->dp;
@@ -5325,6 +5326,20 @@ struct dsgd_dense {
   size_t ev_used = 0;
   double ms_sum = 0.0;
   long long ms_n = 0;
+  // index lists (dsgd_dense_step_list / _loss_list / _predict_list) cross in pinned memory as the per-request lists of a
+  // context do (pin_acquire / pin_sent above): a second call waits for the first call's copy before it refills the buffer
+  dsgd_ctx::Pinned pin_idx;
+  DevBuf<int> d_idx;          // the list of the call in flight (grown on demand)
+  DevBuf<float> d_p;          // dsgd_dense_predict*: probabilities (grown on demand) ...
+  HostBuf<float> h_p;         // ... and their pinned landing place
+  long long data_gen = 0;     // counts dsgd_dense_load / _generate: a plan checked against other data is refused at its run
+  std::vector<dsgd_dense_plan*> plans;   // the plans this object still owns (dsgd_dense_destroy releases them)
+};
+// an epoch's lists resident on the device: step s is idx[off[s] .. off[s + 1])
+struct dsgd_dense_plan {
+  DevBuf<int> d_idx;
+  std::vector<long long> off;   // n_steps + 1
+  long long data_gen = 0;
 };
 static int dn_bind(dsgd_dense* d) {
   if (!d) return fail(DSGD_EINVAL, "null dense object");
@@ -5341,8 +5356,13 @@ static int dn_collect(dsgd_dense* d) {
   d->ev_used = 0;
   return DSGD_OK;
 }
-static int dn_launch(dsgd_dense* d, long long rb, long long re, bool grad) {
-  DenseArgs a;
+// One launch over positions [rb, re): rows rb .. re - 1 themselves, or -- d_list given, rb == 0 -- the rows a checked list in
+// device memory names.  d_p: the forward-only probability form (grad is false).  Returns the grid, or an error code.
+static int dn_launch(dsgd_dense* d, long long rb, long long re, bool grad, const int* d_list = nullptr, float* d_p = nullptr) {
+  DenseListArgs l;
+  DenseArgs& a = l.a;
+  l.idx = d_list;
+  l.p_out = d_p;
   a.X = d->d_X;
   a.y = d->d_y;
   a.w = d->d_w;
@@ -5369,10 +5389,17 @@ static int dn_launch(dsgd_dense* d, long long rb, long long re, bool grad) {
     slot = d->ev_used++;
     HIP_TRY(hipEventRecord(d->ev[slot].first, d->stream));
   }
-  if (d->mfma)   // the variant on the matrix cores (forward product only; csrc/dsgd_dense.hpp)
-    hipLaunchKernelGGL(dsgd_dense_step_mfma_kernel, dim3(grid), dim3(d->D / 4), sizeof(float) * (size_t)d->D, d->stream, a);
-  else
-    hipLaunchKernelGGL(dsgd_dense_step_kernel, dim3(grid), dim3(d->D / DN_COLS), 0, d->stream, a);
+  // (the variant on the matrix cores: forward product only; csrc/dsgd_dense.hpp.  DSGD_DENSE_MFMA decides for every form.)
+  const dim3 lanes(d->mfma ? d->D / 4 : d->D / DN_COLS);
+  const size_t lds = d->mfma ? sizeof(float) * (size_t)d->D : 0;
+  if (!d_list && !d_p) {
+    hipLaunchKernelGGL(d->mfma ? dsgd_dense_step_mfma_kernel : dsgd_dense_step_kernel, dim3(grid), lanes, lds, d->stream, a);
+  } else {
+    void (*kern)(DenseListArgs) = d_p ? (d_list ? (d->mfma ? dsgd_dense_proba_list_mfma_kernel : dsgd_dense_proba_list_kernel)
+                                                : (d->mfma ? dsgd_dense_proba_mfma_kernel : dsgd_dense_proba_kernel))
+                                      : (d->mfma ? dsgd_dense_step_list_mfma_kernel : dsgd_dense_step_list_kernel);
+    hipLaunchKernelGGL(kern, dim3(grid), lanes, lds, d->stream, l);
+  }
   HIP_TRY(hipGetLastError());
   if (slot != (size_t)-1) HIP_TRY(hipEventRecord(d->ev[slot].second, d->stream));
   return grid;
@@ -5427,6 +5454,7 @@ int dsgd_dense_destroy(dsgd_dense* d) {
     (void)hipEventDestroy(e.first);
     (void)hipEventDestroy(e.second);
   }
+  for (dsgd_dense_plan* p : d->plans) delete p;
   const hipStream_t stream = d->stream;
   delete d;   // (the stream is idle: the members release themselves)
   if (stream) (void)hipStreamDestroy(stream);
@@ -5438,6 +5466,7 @@ static int dn_alloc_rows(dsgd_dense* d, long long n_rows) {
   d->d_X.reset();
   d->d_y.reset();
   d->n_rows = 0;
+  d->data_gen++;   // (whatever the outcome: the plans checked against the rows that just went are stale)
   DSGD_TRY(d->d_X.alloc((size_t)n_rows * (size_t)d->D));
   DSGD_TRY(d->d_y.alloc((size_t)n_rows));
   d->n_rows = n_rows;
@@ -5492,13 +5521,37 @@ static int dn_check_range(dsgd_dense* d, long long rb, long long re) {
   return DSGD_OK;
 }
 
-int dsgd_dense_step(dsgd_dense* d, int64_t row_begin, int64_t row_end, float lr) {
-  DSGD_TRY(dn_bind(d));
-  std::lock_guard<std::mutex> lk(d->mu);
-  DSGD_TRY(dn_check_range(d, row_begin, row_end));
-  const int grid = dn_launch(d, row_begin, row_end, true);
+// A list of the host's: n >= 1 entries, each a resident row.  Host work only -- nothing is enqueued or changed before a
+// list has passed, and no kernel looks at an index again.  `base`: the position of idx[0] in what the caller was given
+// (a plan's lists are checked as one).
+static int dn_check_list(dsgd_dense* d, const int32_t* idx, long long n, long long base = 0) {
+  if (!idx) return fail(DSGD_EINVAL, "null index list");
+  if (n < 1) return fail(DSGD_EINVAL, "empty index list");
+  if (!d->d_X) return fail(DSGD_ESTATE, "no data (dsgd_dense_generate / dsgd_dense_load)");
+  for (long long k = 0; k < n; ++k)
+    if (idx[k] < 0 || idx[k] >= d->n_rows)
+      return fail(DSGD_ERANGE, "idx[%lld] = %d outside the %lld resident rows", base + k, (int)idx[k], d->n_rows);
+  return DSGD_OK;
+}
+// a checked list into d->d_idx, behind whatever still reads the list before it (one stream)
+static int dn_send_list(dsgd_dense* d, const int32_t* idx, long long n) {
+  if ((size_t)n > d->d_idx.cap()) {
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    DSGD_TRY(d->d_idx.reserve((size_t)n, Grow::twice));
+  }
+  DSGD_TRY(pin_acquire(d->pin_idx, sizeof(int) * (size_t)n));
+  memcpy(d->pin_idx.p, idx, sizeof(int) * (size_t)n);
+  HIP_TRY(hipMemcpyAsync(d->d_idx, d->pin_idx.p, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, d->stream));
+  return pin_sent(d->pin_idx, d->stream);
+}
+
+// One step, enqueued: the gradient launch over positions [rb, re) (rows, or the entries of d_list), the reduce and the
+// update -- under a communicator the all-reduce and the apply, every rank contributing an equal batch.  The range step,
+// the list step and every step of a plan run are this.
+static int dn_step(dsgd_dense* d, long long rb, long long re, const int* d_list, float lr) {
+  const int grid = dn_launch(d, rb, re, true, d_list);
   if (grid < 0) return grid;
-  const float scale = lr / ((float)(row_end - row_begin) * (float)d->world);   // every rank contributes an equal batch
+  const float scale = lr / ((float)(re - rb) * (float)d->world);
   hipLaunchKernelGGL(dsgd_dense_reduce_kernel, dim3((d->D + 63) / 64), dim3(1024), 0, d->stream, d->d_gpart, grid, d->D, d->d_g,
                      d->comm ? (float*)nullptr : d->d_w, scale);
   HIP_TRY(hipGetLastError());
@@ -5510,6 +5563,83 @@ int dsgd_dense_step(dsgd_dense* d, int64_t row_begin, int64_t row_end, float lr)
   return DSGD_OK;
 }
 
+int dsgd_dense_step(dsgd_dense* d, int64_t row_begin, int64_t row_end, float lr) {
+  DSGD_TRY(dn_bind(d));
+  std::lock_guard<std::mutex> lk(d->mu);
+  DSGD_TRY(dn_check_range(d, row_begin, row_end));
+  return dn_step(d, row_begin, row_end, nullptr, lr);
+}
+
+int dsgd_dense_step_list(dsgd_dense* d, const int32_t* idx, int64_t n, float lr) {
+  DSGD_TRY(dn_bind(d));
+  std::lock_guard<std::mutex> lk(d->mu);
+  DSGD_TRY(dn_check_list(d, idx, n));
+  DSGD_TRY(dn_send_list(d, idx, n));
+  return dn_step(d, 0, n, d->d_idx, lr);
+}
+
+int dsgd_dense_plan_create(dsgd_dense* d, const int32_t* idx, int64_t n_idx, const int64_t* offsets, int64_t n_steps,
+                           dsgd_dense_plan** out) {
+  DSGD_TRY(dn_bind(d));
+  if (!idx || !offsets || !out) return fail(DSGD_EINVAL, "null argument");
+  if (n_steps < 1 || n_idx < 1) return fail(DSGD_EINVAL, "a plan needs at least one step and one entry");
+  if (offsets[0] != 0 || offsets[n_steps] != n_idx)
+    return fail(DSGD_EINVAL, "offsets must run from 0 to n_idx = %lld (they run from %lld to %lld)", (long long)n_idx,
+                (long long)offsets[0], (long long)offsets[n_steps]);
+  for (int64_t s = 0; s < n_steps; ++s) {
+    if (offsets[s + 1] < offsets[s]) return fail(DSGD_EINVAL, "offsets decrease at step %lld", (long long)s);
+    if (offsets[s + 1] == offsets[s]) return fail(DSGD_EINVAL, "step %lld of the plan is empty", (long long)s);
+  }
+  std::lock_guard<std::mutex> lk(d->mu);
+  DSGD_TRY(dn_check_list(d, idx, n_idx));
+  dsgd_dense_plan* p = new (std::nothrow) dsgd_dense_plan();
+  if (!p) return fail(DSGD_ENOMEM, "out of host memory");
+  p->off.assign(offsets, offsets + n_steps + 1);
+  p->data_gen = d->data_gen;
+  int rc = p->d_idx.alloc((size_t)n_idx);
+  hipError_t e = hipSuccess;   // (once per plan, from the caller's pageable memory: the copy has completed when the call returns)
+  if (!rc && (e = hipMemcpy(p->d_idx, idx, sizeof(int) * (size_t)n_idx, hipMemcpyHostToDevice)) != hipSuccess)
+    rc = fail(DSGD_EHIP, "plan upload: %s", hipGetErrorString(e));
+  if (rc) {
+    delete p;
+    return rc;
+  }
+  d->plans.push_back(p);
+  *out = p;
+  return DSGD_OK;
+}
+
+static int dn_own_plan(dsgd_dense* d, dsgd_dense_plan* p) {
+  if (!p) return fail(DSGD_EINVAL, "null plan");
+  if (std::find(d->plans.begin(), d->plans.end(), p) == d->plans.end()) return fail(DSGD_EINVAL, "the plan is not this object's");
+  return DSGD_OK;
+}
+
+int dsgd_dense_plan_run(dsgd_dense* d, dsgd_dense_plan* p, int64_t step_begin, int64_t step_end, float lr) {
+  DSGD_TRY(dn_bind(d));
+  std::lock_guard<std::mutex> lk(d->mu);
+  DSGD_TRY(dn_own_plan(d, p));
+  const long long n_steps = (long long)p->off.size() - 1;
+  if (step_begin < 0 || step_end > n_steps || step_end < step_begin)
+    return fail(DSGD_EINVAL, "steps [%lld, %lld) outside the plan's %lld steps", (long long)step_begin, (long long)step_end, n_steps);
+  if (!d->d_X) return fail(DSGD_ESTATE, "no data (dsgd_dense_generate / dsgd_dense_load)");
+  if (p->data_gen != d->data_gen) return fail(DSGD_ESTATE, "the plan was created before the last dsgd_dense_load / dsgd_dense_generate");
+  for (long long s = step_begin; s < step_end; ++s)   // (no upload, and no host synchronisation but a full event pool's)
+    DSGD_TRY(dn_step(d, 0, p->off[s + 1] - p->off[s], p->d_idx + p->off[s], lr));
+  return DSGD_OK;
+}
+
+int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* p) {
+  DSGD_TRY(dn_bind(d));
+  if (!p) return DSGD_OK;
+  std::lock_guard<std::mutex> lk(d->mu);
+  DSGD_TRY(dn_own_plan(d, p));
+  HIP_TRY(hipStreamSynchronize(d->stream));   // (steps of it may still be enqueued)
+  d->plans.erase(std::find(d->plans.begin(), d->plans.end(), p));
+  delete p;
+  return DSGD_OK;
+}
+
 int dsgd_dense_synchronize(dsgd_dense* d) {
   DSGD_TRY(dn_bind(d));
   std::lock_guard<std::mutex> lk(d->mu);
@@ -5517,11 +5647,9 @@ int dsgd_dense_synchronize(dsgd_dense* d) {
   return dn_collect(d);
 }
 
-int dsgd_dense_loss(dsgd_dense* d, int64_t row_begin, int64_t row_end, double* loss, double* acc) {
-  DSGD_TRY(dn_bind(d));
-  std::lock_guard<std::mutex> lk(d->mu);
-  DSGD_TRY(dn_check_range(d, row_begin, row_end));
-  const int grid = dn_launch(d, row_begin, row_end, false);
+// the evaluation launch over positions [rb, re) and its reply: the partials in one copy, one synchronisation
+static int dn_loss(dsgd_dense* d, long long rb, long long re, const int* d_list, double* loss, double* acc) {
+  const int grid = dn_launch(d, rb, re, false, d_list);
   if (grid < 0) return grid;
   HIP_TRY(hipMemcpyAsync(d->h_lpart, d->d_lpart, sizeof(double) * 2 * grid, hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
@@ -5530,10 +5658,54 @@ int dsgd_dense_loss(dsgd_dense* d, int64_t row_begin, int64_t row_end, double* l
     l += d->h_lpart[2 * b];
     c += d->h_lpart[2 * b + 1];
   }
-  const double n = (double)(row_end - row_begin);
+  const double n = (double)(re - rb);
   if (loss) *loss = l / n;
   if (acc) *acc = c / n;
   return DSGD_OK;
+}
+int dsgd_dense_loss(dsgd_dense* d, int64_t row_begin, int64_t row_end, double* loss, double* acc) {
+  DSGD_TRY(dn_bind(d));
+  std::lock_guard<std::mutex> lk(d->mu);
+  DSGD_TRY(dn_check_range(d, row_begin, row_end));
+  return dn_loss(d, row_begin, row_end, nullptr, loss, acc);
+}
+int dsgd_dense_loss_list(dsgd_dense* d, const int32_t* idx, int64_t n, double* loss, double* acc) {
+  DSGD_TRY(dn_bind(d));
+  std::lock_guard<std::mutex> lk(d->mu);
+  DSGD_TRY(dn_check_list(d, idx, n));
+  DSGD_TRY(dn_send_list(d, idx, n));
+  return dn_loss(d, 0, n, d->d_idx, loss, acc);
+}
+
+// sigmoid(z) of positions [rb, re) under the resident weights: the forward-only launch, then one copy, one synchronisation
+static int dn_predict(dsgd_dense* d, long long rb, long long re, const int* d_list, float* p_out) {
+  const size_t n = (size_t)(re - rb);
+  if (n > d->d_p.cap()) {
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    DSGD_TRY(d->d_p.reserve(n, Grow::twice));
+  }
+  DSGD_TRY(d->h_p.reserve(std::max<size_t>(n, 1024)));
+  const int grid = dn_launch(d, rb, re, false, d_list, d->d_p);
+  if (grid < 0) return grid;
+  HIP_TRY(hipMemcpyAsync(d->h_p, d->d_p, sizeof(float) * n, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  memcpy(p_out, d->h_p, sizeof(float) * n);
+  return DSGD_OK;
+}
+int dsgd_dense_predict(dsgd_dense* d, int64_t row_begin, int64_t row_end, float* p_out) {
+  DSGD_TRY(dn_bind(d));
+  if (!p_out) return fail(DSGD_EINVAL, "null p_out");
+  std::lock_guard<std::mutex> lk(d->mu);
+  DSGD_TRY(dn_check_range(d, row_begin, row_end));
+  return dn_predict(d, row_begin, row_end, nullptr, p_out);
+}
+int dsgd_dense_predict_list(dsgd_dense* d, const int32_t* idx, int64_t n, float* p_out) {
+  DSGD_TRY(dn_bind(d));
+  if (!p_out) return fail(DSGD_EINVAL, "null p_out");
+  std::lock_guard<std::mutex> lk(d->mu);
+  DSGD_TRY(dn_check_list(d, idx, n));
+  DSGD_TRY(dn_send_list(d, idx, n));
+  return dn_predict(d, 0, n, d->d_idx, p_out);
 }
 
 int dsgd_dense_comm_init(dsgd_dense* d, const char* unique_id, int32_t world_size, int32_t rank) {

@@ -832,7 +832,17 @@ int dsgd_device_ptrs(dsgd_ctx* ctx, void** w_dev, void** g_dev, void** stream);
  *   z = X w, p = sigmoid(z), loss = mean(softplus(z) - y z), g = X^T (p - y) / B, w <- w - lr g
  * over the contiguous rows [row_begin, row_end) of the (pre-shuffled) shard -- one mini-batch.  With a communicator
  * the gradient sums are all-reduced and B is the global batch.  Oracle: oracle/dense_ref.py (fp64, pinned by finite
- * differences -- parity unpinned by construction).                                                                */
+ * differences -- parity unpinned by construction).
+ *
+ * INDEX LISTS.  The _list forms, dsgd_dense_predict_list and the plans take a mini-batch as a list of row numbers
+ * instead: position k of the list names row idx[k], a row named twice counts twice, and a list may be longer than
+ * n_rows -- so the shard is loaded once, in any order, and every epoch draws new batches from it.  A list step is,
+ * operation for operation, the range step over a shard holding the named rows in list order: the same weights, bit
+ * for bit (a block of the kernel is 8 -- matrix cores: 16 -- consecutive list POSITIONS; csrc/dsgd_dense.hpp).
+ * Lists are host memory.  Every check runs on the host before anything is enqueued or changed, and a refused call
+ * leaves the weights as they were: DSGD_EINVAL for a null pointer, n < 1, an empty step of a plan, offsets that do not
+ * run non-decreasing from 0 to n_idx, or a bad step range; DSGD_ERANGE for an entry outside [0, n_rows), naming entry
+ * and position; DSGD_ESTATE without data.  With a communicator every rank passes a list of the same length.         */
 typedef struct dsgd_dense dsgd_dense;
 int dsgd_dense_create(int32_t n_features, int32_t device, dsgd_dense** out);
 int dsgd_dense_destroy(dsgd_dense* d);
@@ -851,6 +861,24 @@ int dsgd_dense_loss(dsgd_dense* d, int64_t row_begin, int64_t row_end, double* l
 int dsgd_dense_comm_init(dsgd_dense* d, const char* unique_id, int32_t world_size, int32_t rank);
 /* average device time (ms) of the step kernel since the last reset (HIP events on the object's stream)             */
 int dsgd_dense_prof(dsgd_dense* d, int32_t enable, double* kernel_ms_avg, int64_t* n_launches);
+/* dsgd_dense_step over the rows a list names; enqueued like it.  The list is copied before the call returns: calls
+ * issued back to back without dsgd_dense_synchronize each use their own list.                                       */
+int dsgd_dense_step_list(dsgd_dense* d, const int32_t* idx, int64_t n, float lr);
+/* dsgd_dense_loss over the rows a list names                                                                        */
+int dsgd_dense_loss_list(dsgd_dense* d, const int32_t* idx, int64_t n, double* loss, double* acc);
+/* p = sigmoid(x . w) of every row of a range / of every position of a list, under the resident weights (no update)  */
+int dsgd_dense_predict(dsgd_dense* d, int64_t row_begin, int64_t row_end, float* p_out /* row_end - row_begin */);
+int dsgd_dense_predict_list(dsgd_dense* d, const int32_t* idx, int64_t n, float* p_out /* n */);
+/* An epoch's lists resident on the device: step s is idx[offsets[s] .. offsets[s + 1]), uploaded once here.
+ * dsgd_dense_plan_run enqueues steps [step_begin, step_end) -- each a dsgd_dense_step_list of its list -- with no
+ * upload and no host synchronisation in between.  A plan belongs to the object it was created on (dsgd_dense_destroy
+ * releases what is left) and to the data resident at its creation: after a dsgd_dense_load / dsgd_dense_generate its
+ * run is refused with DSGD_ESTATE.  dsgd_dense_prof counts list steps and plan steps as it counts range steps.       */
+typedef struct dsgd_dense_plan dsgd_dense_plan;
+int dsgd_dense_plan_create(dsgd_dense* d, const int32_t* idx, int64_t n_idx, const int64_t* offsets /* n_steps + 1 */,
+                           int64_t n_steps, dsgd_dense_plan** out);
+int dsgd_dense_plan_run(dsgd_dense* d, dsgd_dense_plan* plan, int64_t step_begin, int64_t step_end, float lr);
+int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
 
 #ifdef __cplusplus
 }
