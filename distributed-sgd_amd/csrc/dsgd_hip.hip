@@ -125,6 +125,7 @@ static bool available() {
 #include "dsgd_layout_host.hpp"  // (host only: the arithmetic behind every table the gradient kernels read)
 #include "dsgd_route.hpp"        // (host only: the switches, and which kernel family serves a call)
 #include "dsgd_kernels.hpp"
+#include "dsgd_logistic.hpp"   // (the logistic model beside the SVM: its own gradient, finish, evaluation and probabilities)
 #include "dsgd_batch.hpp"
 #include "dsgd_cs.hpp"
 #include "dsgd_dense.hpp"
@@ -517,6 +518,20 @@ struct dsgd_ctx {
   std::vector<unsigned int> sp_seen;        // key -> the stamp of the call that saw it last (the repeated-key check)
   unsigned int sp_stamp = 0;
   std::vector<int32_t> row_len;             // the loaded rows' lengths (the bound on an asynchronous step's delta)
+  // The logistic model (csrc/dsgd_logistic.hpp): [lg_k][lg_stride] fixed-point column sums of its own, zero between calls
+  // (grow-only; nothing is shared with the SVM's accumulators), the gradient in key order, the per-workgroup sums of |w|^2
+  // (lg_finish_blocks words) followed by the evaluation's per-workgroup loss sums (n_cu words), an epoch's list ranges, the
+  // probabilities.  bind_count numbers the entry points' binds: the |w|^2 words describe the resident weights while no other
+  // entry point has bound since the logistic call that left them (lg_nsq_stamp: that call's number).
+  DevBuf<unsigned long long> d_lg_acc;
+  long long lg_stride = 0;
+  int lg_k = 0;
+  DevBuf<float> d_lg_g;
+  DevBuf<double> d_lg_part;
+  DevBuf<WorkSeg> d_lg_ssegs;
+  DevBuf<float> d_lg_p;
+  unsigned long long bind_count = 0;
+  unsigned long long lg_nsq_stamp = ~0ull - 1;
 };
 
 // what the route functions of csrc/dsgd_route.hpp need from the context
@@ -560,6 +575,7 @@ static int cs_unslice(dsgd_ctx* c) {
 }
 static int bind(dsgd_ctx* c, bool keep_sliced = false) {  // host threads migrate (JVM pool): bind the device on every call
   HIP_TRY(hipSetDevice(c->cfg.device));
+  ++c->bind_count;   // (whatever binds may change w: the logistic model's cached |w|^2 is good for its own calls only)
   if (c->comm_broken && !c->comm_broken_ok)
     return fail(DSGD_ERCCL, "the context's communicator was aborted after a collective that not every rank joined: "
                             "dsgd_comm_destroy, then attach a new one (without it the replicas would silently diverge)");
@@ -3856,6 +3872,8 @@ int dsgd_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row_en
   DSGD_TRY(eval_collective(c));
   return eval_read(c, loss, acc, counts);
 }
+
+#include "dsgd_lg_calls.hpp"   // (the logistic model's entry points: dsgd_lg_*)
 
 // ---- distributed evaluation (csrc/dsgd_predict.hpp; ref: core/Master.scala:61-98) ----
 // The checks of dsgd_predict_ranges / _f64 that need no device: nothing has changed when one of them fails.

@@ -1,0 +1,294 @@
+// Host side of the logistic model (include/dsgd.h "THE LOGISTIC MODEL"; device code: csrc/dsgd_logistic.hpp; the shift, the
+// grids and the validation of lists, ranges and offsets: csrc/dsgd_lg_host.hpp).  Included by dsgd_hip.hip inside its
+// extern "C" block, behind the helpers it uses (bind, stage_lists, upload_segs, set_weights_locked, finish_stats).
+//
+// Every check runs on the host before anything of the call is enqueued: a refused call leaves the weights, the accumulators
+// and the context's flags as they were.  Every call returns behind its kernels (ONE synchronisation).
+
+static int lg_refuse(dsgd_ctx* c, const char* what) {
+  if (c->fp64)
+    return fail(DSGD_EUNSUPPORTED, "%s is not available in an fp64 context: the logistic model runs on the fp32 engine's weights and dot", what);
+  if (c->comm)
+    return fail(DSGD_EUNSUPPORTED, "%s is not available with a communicator attached: the logistic model's steps do not span ranks", what);
+  return DSGD_OK;
+}
+// what every call asks first (locked): the mode, the device, the data, the engine
+static int lg_enter(dsgd_ctx* c, const char* what, bool* nsq_fresh) {
+  DSGD_TRY(lg_refuse(c, what));
+  DSGD_TRY(bind(c));
+  *nsq_fresh = c->lg_nsq_stamp + 1 == c->bind_count;   // (no other entry point has bound since the logistic call that left |w|^2)
+  DSGD_TRY(require_data(c));
+  if (c->async_running)
+    return fail(DSGD_ESTATE, "%s: the lock-free engine is running (dsgd_async_stop / dsgd_async_wait first)", what);
+  return DSGD_OK;
+}
+static int lg_report(dsgd_ctx* c, const char* what, const LgCheck& v, int n_workers) {
+  switch (v.kind) {
+    case LG_OK: return DSGD_OK;
+    case LG_NO_WORKERS: return fail(DSGD_EINVAL, "%s: bad arguments (a null table, no workers or no steps)", what);
+    case LG_EMPTY: return fail(DSGD_EINVAL, "%s: Cannot sum an empty list of vectors (worker %lld has no rows)", what, v.worker % std::max(1, n_workers));
+    case LG_TOO_LONG: return fail(DSGD_EINVAL, "%s: worker %lld lists %lld rows, more than 2^40", what, v.worker % std::max(1, n_workers), v.value);
+    case LG_FIRST_OFFSET: return fail(DSGD_EINVAL, "%s: offsets[0] must be 0", what);
+    case LG_END: return fail(DSGD_EINVAL, "%s: offsets end at %lld, not at n_idx", what, v.value);
+    case LG_OFFSETS: return fail(DSGD_EINVAL, "%s: offsets decrease or leave idx at list %lld", what, v.worker);
+    case LG_INDEX: break;
+  }
+  return fail(DSGD_ERANGE, "%s: row %lld (worker %lld, position %lld) is outside the %lld loaded rows", what, v.value, v.worker, v.pos, c->n_rows);
+}
+
+static int lg_ensure(dsgd_ctx* c, int n_workers) {
+  DSGD_TRY(c->d_lg_g.reserve((size_t)c->dp));
+  DSGD_TRY(c->d_lg_part.reserve((size_t)lg_finish_blocks(c->dp) + (size_t)c->n_cu));
+  if (c->lg_k < n_workers) {   // (zeroed once; every finish leaves them zeroed)
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->lg_k = 0;
+    const long long stride = ((long long)c->dp + 63) & ~63LL;
+    const int cap = std::max(n_workers, 4);
+    DSGD_TRY(c->d_lg_acc.alloc((size_t)stride * (size_t)cap));
+    HIP_TRY(hipMemsetAsync(c->d_lg_acc, 0, sizeof(unsigned long long) * (size_t)stride * (size_t)cap, c->stream));
+    c->lg_stride = stride;
+    c->lg_k = cap;
+  }
+  return DSGD_OK;
+}
+
+// The two launches of one worker's gradient (LG_GRADIENT) or of a step (LG_STEP) over K lists of positions in `idx` (list) or
+// K row ranges (segs hold the rows), the longest of `longest` rows.  lg_ensure came first.
+static int lg_launch(dsgd_ctx* c, bool list, int K, long long longest, int mode, float lr, const int* idx, const WorkSeg* segs) {
+  LgArgs a;
+  a.w = c->d_w;
+  a.dp = c->dp;
+  a.vexp = c->vexp;
+  a.K = K;
+  a.idx = idx;
+  a.segs = segs;
+  // lists: two workgroups per compute unit at the most, as the fp64 row-parallel family (each flushes its LDS head once);
+  // ranges are long streams of rows: four, for the loads in flight
+  a.blocks_per_worker = lg_blocks_per_worker(longest, K, c->n_cu, list ? 2 : 4);
+  a.acc = c->d_lg_acc;
+  a.acc_stride = c->lg_stride;
+  a.sc = c->d_sc;
+  const dim3 gg((unsigned)(a.blocks_per_worker * K)), th(LG_THREADS);
+  const CsrView m = view(c);
+  if (list)
+    hipLaunchKernelGGL(dsgd_lg_grad_kernel, gg, th, 0, c->stream, m, a);
+  else
+    hipLaunchKernelGGL(dsgd_lg_grad_range_kernel, gg, th, 0, c->stream, m, a);
+  HIP_TRY(hipGetLastError());
+  LgFinishArgs f;
+  f.acc = a.acc;
+  f.acc_stride = a.acc_stride;
+  f.segs = segs;
+  f.K = K;
+  f.dp = c->dp;
+  f.vexp = c->vexp;
+  f.perm = c->d_perm;
+  f.g_out = c->d_lg_g;
+  f.w = c->d_w;
+  f.lr = (double)lr;
+  f.lambda = c->cfg.lambda;
+  f.nsq_part = c->d_lg_part;
+  const dim3 fg((unsigned)lg_finish_blocks(c->dp));
+  if (mode == LG_STEP)
+    hipLaunchKernelGGL(dsgd_lg_finish_kernel<LG_STEP>, fg, th, 0, c->stream, f);
+  else
+    hipLaunchKernelGGL(dsgd_lg_finish_kernel<LG_GRADIENT>, fg, th, 0, c->stream, f);
+  HIP_TRY(hipGetLastError());
+  c->last_grad_kernel = list ? "dsgd_lg_grad_kernel" : "dsgd_lg_grad_range_kernel";
+  return DSGD_OK;
+}
+// behind a step's launches: the weights moved (the SVM's s and |w|^2 are stale), |w|^2 of the new ones is in d_lg_part; the
+// one synchronisation; every row contributes
+static int lg_step_done(dsgd_ctx* c, dsgd_batch_stats* stats, long long total) {
+  c->s_dirty = true;
+  c->lg_nsq_stamp = c->bind_count;
+  const int rc = finish_stats(c, stats, total);
+  if (rc != DSGD_OK) c->lg_nsq_stamp = ~0ull - 1;
+  if (rc == DSGD_OK && stats) stats->n_active = total;
+  return rc;
+}
+
+int dsgd_lg_gradient(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, float* g_out, dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  if (!g_out) return fail(DSGD_EINVAL, "dsgd_lg_gradient: null g_out");
+  if (n < 1 || !idx) return fail(DSGD_EINVAL, "dsgd_lg_gradient: Cannot sum an empty list of vectors");
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, "dsgd_lg_gradient", &fresh));
+  const int64_t nn = n;
+  const LgCheck v = lg_check_lists(&idx, &nn, 1, c->n_rows);
+  DSGD_TRY(lg_report(c, "dsgd_lg_gradient", v, 1));
+  DSGD_TRY(prepare_layout(c));
+  if (w) DSGD_TRY(set_weights_locked(c, w));
+  DSGD_TRY(lg_ensure(c, 1));
+  DSGD_TRY(reset_counters(c));
+  long long mx = 0, tot = 0;
+  DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
+  DSGD_TRY(lg_launch(c, true, 1, mx, LG_GRADIENT, 0.0f, c->cur_idx, c->d_segs));
+  const size_t bytes = sizeof(float) * (size_t)c->dp;
+  DSGD_TRY(pin_acquire(c->pin_out, bytes));
+  HIP_TRY(hipMemcpyAsync(c->pin_out.p, c->d_lg_g, bytes, hipMemcpyDeviceToHost, c->stream));
+  DSGD_TRY(finish_stats(c, stats, tot));   // the one synchronisation of the call
+  memcpy(g_out, c->pin_out.p, bytes);
+  if (stats) stats->n_active = tot;
+  if (fresh && !w) c->lg_nsq_stamp = c->bind_count;   // (the weights are the ones |w|^2 was taken from)
+  return DSGD_OK;
+}
+
+int dsgd_lg_sync_step(dsgd_ctx* c, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers, float lr,
+                      dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  if (n_workers < 1 || !idx_per_worker || !n_per_worker) return fail(DSGD_EINVAL, "dsgd_lg_sync_step: Cannot sum an empty list of vectors (no workers)");
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, "dsgd_lg_sync_step", &fresh));
+  const LgCheck v = lg_check_lists(idx_per_worker, n_per_worker, n_workers, c->n_rows);
+  DSGD_TRY(lg_report(c, "dsgd_lg_sync_step", v, n_workers));
+  DSGD_TRY(prepare_layout(c));
+  DSGD_TRY(lg_ensure(c, n_workers));
+  DSGD_TRY(reset_counters(c));
+  long long mx = 0, tot = 0;
+  DSGD_TRY(stage_lists(c, idx_per_worker, n_per_worker, n_workers, &mx, &tot));
+  DSGD_TRY(lg_launch(c, true, n_workers, mx, LG_STEP, lr, c->cur_idx, c->d_segs));
+  return lg_step_done(c, stats, tot);
+}
+
+int dsgd_lg_sync_step_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, float lr, dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  if (n_workers < 1 || !row_begin || !row_end) return fail(DSGD_EINVAL, "dsgd_lg_sync_step_ranges: Cannot sum an empty list of vectors (no workers)");
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, "dsgd_lg_sync_step_ranges", &fresh));
+  const LgCheck v = lg_check_ranges(row_begin, row_end, n_workers, c->n_rows);
+  DSGD_TRY(lg_report(c, "dsgd_lg_sync_step_ranges", v, n_workers));
+  DSGD_TRY(prepare_layout(c));
+  DSGD_TRY(lg_ensure(c, n_workers));
+  DSGD_TRY(reset_counters(c));
+  std::vector<WorkSeg> segs((size_t)n_workers);
+  for (int k = 0; k < n_workers; ++k) {
+    segs[(size_t)k].begin = row_begin[k];
+    segs[(size_t)k].end = row_end[k];
+  }
+  DSGD_TRY(upload_segs(c, segs));
+  DSGD_TRY(lg_launch(c, false, n_workers, v.longest, LG_STEP, lr, nullptr, c->d_segs));
+  return lg_step_done(c, stats, v.total);
+}
+
+int dsgd_lg_sync_steps(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const int64_t* offsets, int64_t n_steps, int32_t n_workers, float lr,
+                       dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  if (!idx || !offsets || n_steps < 1 || n_workers < 1 || n_idx < 1) return fail(DSGD_EINVAL, "dsgd_lg_sync_steps: bad arguments (null lists, no steps or no workers)");
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, "dsgd_lg_sync_steps", &fresh));
+  const int K = n_workers;
+  const LgCheck v = lg_check_flat(idx, n_idx, offsets, n_steps, K, c->n_rows);
+  DSGD_TRY(lg_report(c, "dsgd_lg_sync_steps", v, K));
+  const int64_t n_lists = n_steps * K;
+  DSGD_TRY(prepare_layout(c));
+  DSGD_TRY(lg_ensure(c, K));
+  if (c->d_lg_ssegs.cap() < (size_t)n_lists) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    DSGD_TRY(c->d_lg_ssegs.reserve((size_t)n_lists));
+  }
+  DSGD_TRY(reset_counters(c));
+  // ONE upload: the index array and the list ranges of every step
+  DSGD_TRY(ensure_idx(c, n_idx));
+  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int) * (size_t)n_idx));
+  memcpy(c->pin_idx.p, idx, sizeof(int) * (size_t)n_idx);
+  HIP_TRY(hipMemcpyAsync(c->d_idx, c->pin_idx.p, sizeof(int) * (size_t)n_idx, hipMemcpyHostToDevice, c->stream));
+  DSGD_TRY(pin_sent(c, c->pin_idx));
+  c->cur_idx = c->d_idx;
+  DSGD_TRY(pin_acquire(c->pin_segs, sizeof(WorkSeg) * (size_t)n_lists));
+  {
+    WorkSeg* sg = static_cast<WorkSeg*>(c->pin_segs.p.get());
+    for (int64_t i = 0; i < n_lists; ++i) {
+      sg[i].begin = offsets[i];
+      sg[i].end = offsets[i + 1];
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(c->d_lg_ssegs, c->pin_segs.p, sizeof(WorkSeg) * (size_t)n_lists, hipMemcpyHostToDevice, c->stream));
+  DSGD_TRY(pin_sent(c, c->pin_segs));
+  // two launches per step, back to back on the stream: no host synchronisation in between
+  for (int64_t t = 0; t < n_steps; ++t) {
+    long long mx = 0;
+    for (int k = 0; k < K; ++k) mx = std::max<long long>(mx, offsets[t * K + k + 1] - offsets[t * K + k]);
+    DSGD_TRY(lg_launch(c, true, K, mx, LG_STEP, lr, c->d_idx, c->d_lg_ssegs + t * K));
+  }
+  return lg_step_done(c, stats, n_idx);
+}
+
+int dsgd_lg_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row_end, double* loss, double* acc) {
+  DSGD_TRY(check_ctx(c));
+  if (!loss && !acc) return fail(DSGD_EINVAL, "dsgd_lg_loss_acc: null loss and acc");
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, "dsgd_lg_loss_acc", &fresh));
+  const LgCheck v = lg_check_ranges(&row_begin, &row_end, 1, c->n_rows);
+  DSGD_TRY(lg_report(c, "dsgd_lg_loss_acc", v, 1));
+  DSGD_TRY(prepare_layout(c));
+  if (w) DSGD_TRY(set_weights_locked(c, w));
+  DSGD_TRY(lg_ensure(c, 1));
+  const long long nb = lg_finish_blocks(c->dp);
+  if (w || !fresh) {   // |w|^2 of weights the logistic finish did not write: the finish's grid and tree, the same bits
+    hipLaunchKernelGGL(dsgd_lg_nsq_kernel, dim3((unsigned)nb), dim3(LG_THREADS), 0, c->stream, c->d_w, c->dp, c->d_lg_part);
+    HIP_TRY(hipGetLastError());
+  }
+  DSGD_TRY(reset_counters(c));
+  const long long rows = row_end - row_begin;
+  const long long grid = lg_eval_blocks(rows, c->n_cu);
+  // small ranges do not amortise staging 160 KiB of weights per workgroup: a small tile (the rule of dsgd_loss_acc)
+  int hw = rows >= 4096 ? c->hw_eval : std::min(c->hw_eval, 1024);
+  while (lg_eval_lds_floats(hw) > DSGD_LDS_FLOATS) hw -= 64;
+  const size_t lds = sizeof(float) * (size_t)lg_eval_lds_floats(hw);
+  hipLaunchKernelGGL(dsgd_lg_eval_kernel, dim3((unsigned)grid), dim3(LG_EVAL_THREADS), lds, c->stream, view(c), c->d_w, (long long)row_begin,
+                     (long long)row_end, c->d_sc, hw, c->d_lg_part + nb);
+  HIP_TRY(hipGetLastError());
+  const size_t words = (size_t)(nb + grid);
+  DSGD_TRY(pin_acquire(c->pin_out, sizeof(double) * words));
+  HIP_TRY(hipMemcpyAsync(c->pin_out.p, c->d_lg_part, sizeof(double) * words, hipMemcpyDeviceToHost, c->stream));
+  DSGD_TRY(read_scalars(c));   // the one synchronisation of the call
+  DSGD_TRY(check_err_flag(c));
+  c->lg_nsq_stamp = c->bind_count;
+  const double* part = static_cast<const double*>(c->pin_out.p.get());
+  double nsq = 0.0, ls = 0.0;   // (in order: the same bits on every call)
+  for (long long i = 0; i < nb; ++i) nsq += part[i];
+  for (long long i = 0; i < grid; ++i) ls += part[nb + i];
+  const double n = (double)rows;
+  if (loss) *loss = c->cfg.lambda * nsq + ls / n;
+  if (acc) *acc = (double)c->h_sc->counts[0] / n;
+  return DSGD_OK;
+}
+
+int dsgd_lg_predict(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, float* p_out) {
+  DSGD_TRY(check_ctx(c));
+  if (n < 1 || !idx || !p_out) return fail(DSGD_EINVAL, "dsgd_lg_predict: bad arguments (a null pointer or no rows)");
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, "dsgd_lg_predict", &fresh));
+  const int64_t nn = n;
+  const LgCheck v = lg_check_lists(&idx, &nn, 1, c->n_rows);
+  DSGD_TRY(lg_report(c, "dsgd_lg_predict", v, 1));
+  DSGD_TRY(prepare_layout(c));
+  if (w) DSGD_TRY(set_weights_locked(c, w));
+  DSGD_TRY(ensure_idx(c, n));
+  if ((size_t)n > c->d_lg_p.cap()) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    DSGD_TRY(c->d_lg_p.reserve((size_t)std::max<long long>(n, 4096)));
+  }
+  DSGD_TRY(reset_counters(c));
+  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int) * (size_t)n));
+  memcpy(c->pin_idx.p, idx, sizeof(int) * (size_t)n);
+  HIP_TRY(hipMemcpyAsync(c->d_idx, c->pin_idx.p, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  DSGD_TRY(pin_sent(c, c->pin_idx));
+  DSGD_TRY(pin_acquire(c->pin_out, sizeof(float) * (size_t)n));
+  hipLaunchKernelGGL(dsgd_lg_predict_kernel, dim3((unsigned)grid_for(c, n, LG_GROUP)), dim3(LG_THREADS), 0, c->stream, view(c), c->d_w, c->d_idx,
+                     (long long)n, c->d_lg_p, c->d_sc);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(c->pin_out.p, c->d_lg_p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  DSGD_TRY(read_scalars(c));
+  memcpy(p_out, c->pin_out.p, sizeof(float) * (size_t)n);
+  DSGD_TRY(check_err_flag(c));
+  if (fresh && !w) c->lg_nsq_stamp = c->bind_count;
+  return DSGD_OK;
+}

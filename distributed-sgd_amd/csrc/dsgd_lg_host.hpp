@@ -1,0 +1,136 @@
+// The host arithmetic of the logistic model (pure C++, no HIP: tests/cpp/lg_host_test.cpp compiles it alone; csrc/dsgd_logistic.hpp
+// and csrc/dsgd_hip.hip compile the same numbers).
+//
+//   lg_shift            S = 62 - ceil(log2 n): the fixed-point shift of a worker's list of n rows (the rule of csrc/dsgd_rp64.hpp;
+//                       |c_i| <= 1 and |x| <= 2^vexp, so n entries of |q| <= 2^S stay inside 2^62)
+//   lg_blocks_per_worker  the workgroups one worker's list or range is spread over
+//   lg_finish_blocks    the finish kernel's grid: ONE column per lane, so that the per-workgroup sums of |w|^2 do not depend on
+//                       the device (the loss is the same number wherever it is computed)
+//   lg_eval_blocks      the evaluation's persistent grid
+//   lg_check_lists      a step's per-worker lists             (what is wrong, and where: plain data, the callers word the message)
+//   lg_check_ranges     a step's per-worker row ranges
+//   lg_check_flat       an epoch's flat lists                 (csrc/dsgd_plan_check.hpp: flat_lists_check)
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "dsgd_plan_check.hpp"
+
+#ifdef __HIPCC__
+#define LG_HD __host__ __device__
+#else
+#define LG_HD
+#endif
+
+constexpr int LG_THREADS = 256;
+constexpr int LG_GROUP = 16;                          // lanes per row
+constexpr int LG_ROWS_PER_BLOCK = LG_THREADS / LG_GROUP;
+constexpr int LG_EVAL_THREADS = 1024;
+constexpr long long LG_MAX_LIST = 1LL << 40;          // S >= 22: far beyond any list that fits a device; keeps the shift positive
+
+LG_HD constexpr int lg_ceil_log2(long long n) {
+  int l = 0;
+  while ((1LL << l) < n) ++l;
+  return l;
+}
+LG_HD constexpr int lg_shift(long long n) { return 62 - lg_ceil_log2(n); }
+
+// one workgroup per 16 rows of the longest list, all workers together at most `per_cu` workgroups per compute unit (every
+// workgroup flushes its LDS head once: more of them only add flushes)
+inline long long lg_blocks_per_worker(long long max_items, int n_workers, int n_cu, int per_cu) {
+  const long long want = (max_items + LG_ROWS_PER_BLOCK - 1) / LG_ROWS_PER_BLOCK;
+  long long cap = (long long)n_cu * per_cu / (n_workers > 0 ? n_workers : 1);
+  if (cap < 1) cap = 1;
+  const long long b = want < cap ? want : cap;
+  return b < 1 ? 1 : b;
+}
+inline long long lg_finish_blocks(int dp) { return ((long long)dp + LG_THREADS - 1) / LG_THREADS; }
+inline long long lg_eval_blocks(long long rows, int n_cu) {
+  const long long per = LG_EVAL_THREADS / LG_GROUP;
+  long long b = (rows + per - 1) / per;
+  if (b > n_cu) b = n_cu;
+  return b < 1 ? 1 : b;
+}
+
+enum LgFault {
+  LG_OK = 0,
+  LG_NO_WORKERS,    // n_workers < 1 or a null table
+  LG_EMPTY,         // worker `worker`: a null or empty list, an empty or reversed range
+  LG_TOO_LONG,      // worker `worker`: more than LG_MAX_LIST rows
+  LG_INDEX,         // worker `worker`, position `pos`: `value` is not a loaded row (ranges: the range leaves the rows)
+  LG_FIRST_OFFSET,  // (flat lists) offsets[0] != 0
+  LG_END,           // (flat lists) offsets end elsewhere than n_idx
+  LG_OFFSETS,       // (flat lists) offsets decrease or leave idx
+};
+struct LgCheck {
+  LgFault kind = LG_OK;
+  long long worker = -1, pos = -1, value = 0;
+  long long longest = 0, total = 0;   // of a step that is in order
+};
+
+inline LgCheck lg_fault(LgFault kind, long long worker, long long pos, long long value) {
+  LgCheck v;
+  v.kind = kind;
+  v.worker = worker;
+  v.pos = pos;
+  v.value = value;
+  return v;
+}
+
+inline LgCheck lg_check_lists(const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int n_workers, long long n_rows) {
+  if (n_workers < 1 || !idx_per_worker || !n_per_worker) return lg_fault(LG_NO_WORKERS, -1, -1, n_workers);
+  LgCheck v;
+  for (int k = 0; k < n_workers; ++k) {   // (the shape first: an empty list is refused whatever the others hold)
+    if (n_per_worker[k] < 1 || !idx_per_worker[k]) return lg_fault(LG_EMPTY, k, -1, n_per_worker[k]);
+    if (n_per_worker[k] > LG_MAX_LIST) return lg_fault(LG_TOO_LONG, k, -1, n_per_worker[k]);
+    v.total += n_per_worker[k];
+    if (n_per_worker[k] > v.longest) v.longest = n_per_worker[k];
+  }
+  for (int k = 0; k < n_workers; ++k) {
+    const long long t = plan_first_outside(idx_per_worker[k], n_per_worker[k], n_rows);
+    if (t >= 0) return lg_fault(LG_INDEX, k, t, idx_per_worker[k][t]);
+  }
+  return v;
+}
+
+inline LgCheck lg_check_ranges(const int64_t* row_begin, const int64_t* row_end, int n_workers, long long n_rows) {
+  if (n_workers < 1 || !row_begin || !row_end) return lg_fault(LG_NO_WORKERS, -1, -1, n_workers);
+  LgCheck v;
+  for (int k = 0; k < n_workers; ++k) {
+    if (row_end[k] <= row_begin[k]) return lg_fault(LG_EMPTY, k, -1, row_end[k] - row_begin[k]);
+  }
+  for (int k = 0; k < n_workers; ++k) {
+    if (row_begin[k] < 0) return lg_fault(LG_INDEX, k, 0, row_begin[k]);
+    if (row_end[k] > n_rows) return lg_fault(LG_INDEX, k, 1, row_end[k]);
+    const long long n = row_end[k] - row_begin[k];
+    if (n > LG_MAX_LIST) return lg_fault(LG_TOO_LONG, k, -1, n);
+    v.total += n;
+    if (n > v.longest) v.longest = n;
+  }
+  return v;
+}
+
+// offsets: n_steps * n_workers + 1 positions into idx (the layout of dsgd_sync_steps_f64); `worker` is the LIST's number
+// (step * n_workers + worker)
+inline LgCheck lg_check_flat(const int32_t* idx, long long n_idx, const int64_t* offsets, long long n_steps, int n_workers, long long n_rows) {
+  if (!idx || !offsets || n_steps < 1 || n_workers < 1 || n_idx < 1) return lg_fault(LG_NO_WORKERS, -1, -1, n_workers);
+  if (n_steps > INT64_MAX / n_workers - 1) return lg_fault(LG_NO_WORKERS, -1, -1, n_steps);
+  const FlatListsCheck f = flat_lists_check(idx, n_idx, offsets, n_steps, n_workers, n_rows);
+  switch (f.kind) {
+    case FLAT_LISTS_OK: break;
+    case FLAT_LISTS_FIRST_OFFSET: return lg_fault(LG_FIRST_OFFSET, 0, 0, f.value);
+    case FLAT_LISTS_END: return lg_fault(LG_END, f.list, f.pos, f.value);
+    case FLAT_LISTS_OFFSETS: return lg_fault(LG_OFFSETS, f.list, f.pos, f.value);
+    case FLAT_LISTS_EMPTY: return lg_fault(LG_EMPTY, f.list, f.pos, f.value);
+    case FLAT_LISTS_INDEX: return lg_fault(LG_INDEX, -1, f.pos, f.value);
+  }
+  LgCheck v;
+  v.total = n_idx;
+  for (long long i = 0; i < n_steps * n_workers; ++i) {
+    const long long n = offsets[i + 1] - offsets[i];
+    if (n > LG_MAX_LIST) return lg_fault(LG_TOO_LONG, i, -1, n);
+    if (n > v.longest) v.longest = n;
+  }
+  return v;
+}

@@ -370,6 +370,66 @@ class Engine:
         check(self._lib.dsgd_loss_acc(self._ctx, ptr(wv), C.c_int64(row_begin), C.c_int64(row_end), C.byref(loss), C.byref(acc), counts))
         return loss.value, acc.value, list(counts)
 
+    # -- the logistic model (include/dsgd.h "THE LOGISTIC MODEL") ---------------------------------
+    # P(y = +1 | x) = sigma(x . w), class = signum(x . w): the TEXTBOOK sign, not the SVM's -signum.  fp32 engines only.
+    def lg_gradient(self, idx, w=None):
+        """One worker's regularised sum over the listed rows (dsgd_lg_gradient): (g float32 in key order, stats).  w: None
+        (the resident weights) or a vector that replaces them."""
+        idx = i32(idx)
+        g = np.zeros(self.dp, dtype=np.float32)
+        st = BatchStats()
+        wv = None if w is None else f32(w, self.dp)
+        check(self._lib.dsgd_lg_gradient(self._ctx, ptr(wv), ptr(idx), C.c_int64(len(idx)), ptr(g), C.byref(st)))
+        return g, {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def lg_sync_step(self, idx_per_worker, lr):
+        """One synchronous step over the workers' lists (dsgd_lg_sync_step): sum per worker, mean over the workers."""
+        lists = [i32(a) for a in idx_per_worker]
+        k = len(lists)
+        ptrs = (C.c_void_p * max(k, 1))(*[ptr(a) for a in lists])
+        ns = (C.c_int64 * max(k, 1))(*[len(a) for a in lists])
+        st = BatchStats()
+        check(self._lib.dsgd_lg_sync_step(self._ctx, ptrs, ns, C.c_int32(k), C.c_float(lr), C.byref(st)))
+        return {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def lg_sync_step_ranges(self, ranges, lr):
+        """lg_sync_step over (begin, end) row ranges: the bits of the step over the same rows as lists."""
+        k = len(ranges)
+        rb = (C.c_int64 * max(k, 1))(*[int(r[0]) for r in ranges])
+        re_ = (C.c_int64 * max(k, 1))(*[int(r[1]) for r in ranges])
+        st = BatchStats()
+        check(self._lib.dsgd_lg_sync_step_ranges(self._ctx, rb, re_, C.c_int32(k), C.c_float(lr), C.byref(st)))
+        return {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def lg_sync_steps(self, idx, offsets, n_steps, n_workers, lr):
+        """n_steps steps of lg_sync_step in ONE call (dsgd_lg_sync_steps): idx = all lists concatenated (step-major,
+        worker-minor), offsets = n_steps * n_workers + 1 prefix offsets -- the flat form of sync_steps_f64.  The weights get
+        the bits of the loop of lg_sync_step calls."""
+        idx = i32(idx)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if n_steps >= 1 and n_workers >= 1 and len(offsets) != n_steps * n_workers + 1:
+            raise ValueError("offsets do not describe %d x %d lists" % (n_steps, n_workers))
+        st = BatchStats()
+        check(self._lib.dsgd_lg_sync_steps(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers),
+                                           C.c_float(lr), C.byref(st)))
+        return {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def lg_loss_acc(self, row_begin, row_end, w=None):
+        """(loss, acc) of rows [row_begin, row_end): lambda |w|^2 + mean log(1 + exp(-y d)), and the share of rows with
+        signum(d) == y (dsgd_lg_loss_acc)."""
+        loss, acc = C.c_double(0), C.c_double(0)
+        wv = None if w is None else f32(w, self.dp)
+        check(self._lib.dsgd_lg_loss_acc(self._ctx, ptr(wv), C.c_int64(row_begin), C.c_int64(row_end), C.byref(loss), C.byref(acc)))
+        return loss.value, acc.value
+
+    def lg_predict_proba(self, idx, w=None):
+        """P(y = +1 | x) = sigma(x . w) of every listed row, float32 (dsgd_lg_predict)."""
+        idx = i32(idx)
+        p = np.zeros(len(idx), dtype=np.float32)
+        wv = None if w is None else f32(w, self.dp)
+        check(self._lib.dsgd_lg_predict(self._ctx, ptr(wv), ptr(idx), C.c_int64(len(idx)), ptr(p)))
+        return p
+
     predict_max_ranges = 256   # K of one dsgd_predict_ranges call (host.MasterSync asks forward per split beyond it)
 
     def predict_ranges(self, ranges, w=None):

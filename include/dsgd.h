@@ -880,6 +880,66 @@ int dsgd_dense_plan_create(dsgd_dense* d, const int32_t* idx, int64_t n_idx, con
 int dsgd_dense_plan_run(dsgd_dense* d, dsgd_dense_plan* plan, int64_t step_begin, int64_t step_end, float lr);
 int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
 
+/* ---- THE LOGISTIC MODEL on the resident CSR rows (csrc/dsgd_logistic.hpp) ----------------------
+ * A second linear model beside the gated hinge SVM, on the rows, the labels and the weights an fp32 context holds
+ * (the reference's model seam "could use another model", Main.scala:67).  New symbols only: no SVM entry point
+ * changes, DSGD_ABI_VERSION stays 1.
+ *
+ * THE SIGN CONVENTION IS THE TEXTBOOK'S, NOT THE SVM'S.  With d = x . w:  P(y = +1 | x) = sigma(d) and the class is
+ * signum(d) in {-1, 0, +1} -- dsgd_forward and dsgd_loss_acc beside it predict -signum(d) (SparseSVM.scala:14).
+ * Weights trained by one model score the other's labels upside down.
+ *
+ *   labels       y in {-1, +1} as loaded
+ *   d = x . w    the fp32 engine's own dot: its fixed lane order, its 1e-20 product filter.  A finite d is a
+ *                precondition, as for the SVM
+ *   loss         l = log(1 + exp(-y d)), evaluated as max(-a, 0) + log1p(exp(-|a|)), a = y d, in fp64;
+ *                reported: lambda |w|^2 + mean_i l_i  (the lambda |w|^2 of the reference's loss, SparseSVM.scala:20-23)
+ *   gradient     c_i x_i per row, c_i = sigma(d_i) - (1 + y_i) / 2 = -y_i / (1 + exp(y_i d_i)), in fp64 from the fp32
+ *                d_i: no NaN for a finite d (exp -> inf gives -+0, exp -> 0 gives -y)
+ *   regulariser  plain L2: + 2 lambda w_j on EVERY column, per worker -- the exact gradient of the reported loss.
+ *                dimSparsity plays no part: these calls work whether or not it has been set
+ *   step         the reference's flow (Master.scala:184-197): a worker's regularised gradient is a SUM over its rows,
+ *                the MEAN is taken over the K workers, w <- w - lr mean.  Per column j in fp64:
+ *                G_k = acc_k 2^(vexp - S_k), r_k = G_k + 2 lambda w_j, the r_k added in worker order, / K,
+ *                w_j' = (float)(w_j - lr mean): ONE rounding to float per step
+ *   sums         a worker's list of n rows (duplicates count) uses S = 62 - ceil(log2 n); an entry adds
+ *                rn(c_i x_ij 2^(S - vexp)) as a 64-bit integer (2^vexp >= max |x|, |c| <= 1: no column sum leaves its
+ *                word).  Integer adds do not depend on order: a step's weights are bit-reproducible whatever the
+ *                list's order, the launch's shape or the run; dsgd_lg_sync_step_ranges gives the bits of
+ *                dsgd_lg_sync_step on the ranges' rows as lists, dsgd_lg_sync_steps those of its steps one by one
+ *   statistics   n_samples is the number of rows, n_active EQUALS n_samples: every row contributes (there is no gate)
+ *
+ * Refusals -- every check runs on the host before anything is enqueued; a refused call leaves the weights as they
+ * were and the context usable:
+ *   DSGD_EINVAL        a null pointer; n < 1; no workers; an empty worker list; offsets that do not run from 0 to
+ *                      n_idx without decreasing, or an empty list among them; an empty or reversed range
+ *   DSGD_ERANGE        an index (or a range's end) outside the loaded rows
+ *   DSGD_ESTATE        no data loaded, or the lock-free engine is running
+ *   DSGD_EUNSUPPORTED  an fp64 context, or a communicator attached
+ *
+ * LIMITS (out of scope, each refused or simply absent): no JNI / Scala binding; no host mirror (host.MasterSync /
+ * MasterAsync stay the SVM's); no resident dsgd_plan handles and no device-drawn lists (dsgd_lg_sync_steps uploads an
+ * epoch's lists once instead); no asynchronous engine; no fp64 contexts and no Double feature values; no
+ * communicators; no Sparse boundary forms.
+ *
+ * dsgd_lg_gradient: one worker's regularised sum over the listed rows, key order, from the resident weights or from w
+ * (which then replaces them, as in dsgd_gradient).  dsgd_lg_sync_step / _ranges: one step over K lists / K row
+ * ranges [row_begin[k], row_end[k]).  dsgd_lg_sync_steps: an epoch's steps in ONE call -- the lists are uploaded once,
+ * two launches per step, no host synchronisation in between; offsets as in dsgd_sync_steps_f64 (n_steps * n_workers + 1
+ * positions into idx, step-major, worker-minor).  dsgd_lg_loss_acc: the reported loss and the share of rows with
+ * signum(d) == y over rows [row_begin, row_end); the same call gives the same bits (fixed-order sums).
+ * dsgd_lg_predict: sigma(d) of every listed position, computed in fp64 from the fp32 d and rounded to float once.    */
+int dsgd_lg_gradient(dsgd_ctx* ctx, const float* w /* NULL = resident */, const int32_t* idx, int64_t n, float* g_out /* D+1, key order */,
+                     dsgd_batch_stats* stats);
+int dsgd_lg_sync_step(dsgd_ctx* ctx, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers, float lr,
+                      dsgd_batch_stats* stats);
+int dsgd_lg_sync_step_ranges(dsgd_ctx* ctx, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, float lr,
+                             dsgd_batch_stats* stats);
+int dsgd_lg_sync_steps(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const int64_t* offsets /* n_steps * n_workers + 1 */, int64_t n_steps,
+                       int32_t n_workers, float lr, dsgd_batch_stats* stats);
+int dsgd_lg_loss_acc(dsgd_ctx* ctx, const float* w /* NULL = resident */, int64_t row_begin, int64_t row_end, double* loss, double* acc);
+int dsgd_lg_predict(dsgd_ctx* ctx, const float* w /* NULL = resident */, const int32_t* idx, int64_t n, float* p_out /* n */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@ loss and accuracy, fit (sync or async, early stopping by patience / conv-delta),
 accuracy -- with the HIP engine hosting all the workers.
 
     DSGD_DATA_PATH=/data/rcv1 python tools/train.py [--conf application.conf] [--synthetic ROWS] [--device 0] [--weights-out w.txt]
-                                                    [--precision fp64] [--f64-rp-plans]
+                                                    [--precision fp64] [--f64-rp-plans] [--model logistic]
 
 --precision fp64: the engine keeps the reference's Double weights (include/dsgd.h "THE FP64 MODE"); an async fit runs the
 zero-lag schedule of host.MasterAsync (one update at a time, every update seen by every worker).
@@ -13,6 +13,9 @@ feature values, more than 4 workers, batches beyond 1,024 rows -- runs as reside
 "THE FP64 MODE", ROW-PARALLEL PLANS); the asynchronous fit then keeps the files' Doubles too.  With a communicator attached
 (one process per GPU, comm_init_f64 / comm_init_f64v) a synchronous epoch then runs as ONE row-parallel plan run per rank on
 host-drawn lists, one agreement between the ranks per epoch, instead of one sync_step_f64 per step.  Off by default.
+--model logistic: the logistic model on the same rows (include/dsgd.h "THE LOGISTIC MODEL"; fp32, synchronous): per epoch every
+worker's split is shuffled on the host and cut into batches, the epoch's steps run as ONE lg_sync_steps call, and lg_loss_acc
+reports train and test log-loss and accuracy.  The default model is the SVM, and nothing changes on its path.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,7 +30,10 @@ ap.add_argument("--device", type=int, default=0)
 ap.add_argument("--weights-out", help="write the `idx:value` line of Main.scala:114 here instead of logging it")
 ap.add_argument("--precision", choices=("fp32", "fp64"), default="fp32", help="fp64: the reference's Double arithmetic")
 ap.add_argument("--f64-rp-plans", action="store_true", help="fp64: refused plans run as row-parallel plans, under a communicator too: one plan run per epoch and rank (DSGD_F64_RP_PLANS=1)")
+ap.add_argument("--model", choices=("svm", "logistic"), default="svm", help="logistic: log-loss, probabilities, plain L2 (fp32, synchronous)")
 a = ap.parse_args()
+if a.model == "logistic" and a.precision != "fp32":
+    ap.error("--model logistic runs on the fp32 engine")
 if a.f64_rp_plans:
     os.environ["DSGD_F64_RP_PLANS"] = "1"   # (host.MasterSync / host.MasterAsync read it at every fit)
 rp_plans = a.precision == "fp64" and os.environ.get("DSGD_F64_RP_PLANS", host.F64_RP_PLANS_DEFAULT) == "1"
@@ -35,6 +41,30 @@ rp_plans = a.precision == "fp64" and os.environ.get("DSGD_F64_RP_PLANS", host.F6
 
 def log(msg, *args):  # logback's pattern is not reproduced; the messages are
     print(time.strftime("%H:%M:%S"), msg.replace("{}", "%s") % args if args else msg, flush=True)
+
+
+def fit_logistic(eng, cfg, n_train, n_rows):
+    """A plain loop: host-drawn lists, one lg_sync_steps call per epoch, lg_loss_acc on train and test after each."""
+    split = host.split_vanilla(n_train, cfg.node_count)
+    k = len(split)
+    n_steps = max(1, min(len(r) for r in split) // cfg.batch_size)
+    rng = np.random.default_rng(0)
+    log("logistic: {} workers, {} steps of {} rows per epoch, lr {}", k, n_steps, cfg.batch_size, cfg.learning_rate)
+    l0, a0 = eng.lg_loss_acc(0, n_train)
+    log("initial loss: {}", l0)
+    log("initial accuracy: {}", a0)
+    for epoch in range(cfg.max_epochs):
+        perms = [rng.permutation(len(r)).astype(np.int32) + r.start for r in split]
+        lists = [perms[w][t * cfg.batch_size:(t + 1) * cfg.batch_size] for t in range(n_steps) for w in range(k)]
+        offs = np.concatenate([[0], np.cumsum([len(x) for x in lists])])
+        t0 = time.time()
+        eng.lg_sync_steps(np.concatenate(lists), offs, n_steps, k, cfg.learning_rate)
+        dt = time.time() - t0
+        ltr, atr = eng.lg_loss_acc(0, n_train)
+        lte, ate = eng.lg_loss_acc(n_train, n_rows)
+        log("epoch {}: train loss {} acc {}, test loss {} acc {} ({}s)", epoch, round(ltr, 6), round(atr, 4), round(lte, 6), round(ate, 4), round(dt, 3))
+    log("final test loss: {}", lte)
+    log("final test accuracy: {}", ate)
 
 
 cfg = host.Config.load(open(a.conf).read() if a.conf else None)
@@ -53,6 +83,10 @@ with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device, precision=a.precisi
     log("feature values: {} bits{}", eng.value_bits() if a.precision == "fp64" else 32,
         " (fp64 asynchronous fit: resident plans hold float values, NOT the Double feature values)"
         if a.precision == "fp64" and cfg.async_ and not rp_plans and getattr(data, "val64", None) is not None else "")
+    if a.model == "logistic":   # (its own loop; dimSparsity plays no part)
+        eng.set_weights(np.zeros(data.dim + 1, dtype=np.float32))
+        fit_logistic(eng, cfg, n_train, data.n_rows)
+        sys.exit(0)
     t0 = time.time()
     eng.build_dim_sparsity(n_train)                                            # Main.scala:54-65
     log("dim sparsity ({}s)", round(time.time() - t0, 3))
