@@ -50,6 +50,7 @@ SYMBOLS = [
     "dsgd_loss_acc_list", "dsgd_loss_acc_list_f64", "dsgd_loss_acc_sampled", "dsgd_loss_acc_sampled_f64",
     "dsgd_async_check", "dsgd_async_check_keep", "dsgd_async_check_weights",
     "dsgd_lg_gradient", "dsgd_lg_sync_step", "dsgd_lg_sync_step_ranges", "dsgd_lg_sync_steps", "dsgd_lg_loss_acc", "dsgd_lg_predict",
+    "dsgd_plan_create_lg_n", "dsgd_plan_create_from_seed_lg", "dsgd_lg_loss_acc_ranges",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -130,6 +131,14 @@ def load():
         lib.dsgd_lg_sync_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p]
         lib.dsgd_lg_loss_acc.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         lib.dsgd_lg_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    if hasattr(lib, "dsgd_plan_create_lg_n"):   # logistic plans and the several-ranges evaluation
+        # (ctx, idx*, n_idx, offsets*, n_steps, n_workers, out*)
+        lib.dsgd_plan_create_lg_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        # (ctx, jstate*, split_begin*, split_end*, n_splits, max_samples, batch_size, out*, n_steps*, draws*)
+        lib.dsgd_plan_create_from_seed_lg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p]
+        # (ctx, w*, row_begin*, row_end*, n_ranges, loss_out*, acc_out*)
+        lib.dsgd_lg_loss_acc_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     if hasattr(lib, "dsgd_dense_plan_create"):   # (handles are 64-bit: without argtypes ctypes would pass them as C ints)
         lib.dsgd_dense_step_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float]
         lib.dsgd_dense_loss_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

@@ -940,6 +940,7 @@ static int plan_run64(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long
 int dsgd_plan_run_f64(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_end, double lr) {
   DSGD_TRY(check_ctx(c));
   DSGD_TRY(plan_steps_check(p, step_begin, step_end));
+  if (p->lg) return fail(DSGD_EUNSUPPORTED, "dsgd_plan_run_f64: a logistic plan runs through dsgd_plan_run, on an fp32 context");
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(require_fp64(c, "dsgd_plan_run_f64"));
   if (!p->rp64) DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_run_f64"));   // (a row-parallel plan spans the ranks: plan_run_rp64_ranks)
@@ -951,6 +952,7 @@ int dsgd_plan_run_f64(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t ste
 int dsgd_plan_run_async_f64(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_end, double lr) {
   DSGD_TRY(check_ctx(c));
   DSGD_TRY(plan_steps_check(p, step_begin, step_end));
+  if (p->lg) return fail(DSGD_EUNSUPPORTED, "dsgd_plan_run_async_f64: a logistic plan has no asynchronous iteration");
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(require_fp64(c, "dsgd_plan_run_async_f64"));
   DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_run_async_f64"));

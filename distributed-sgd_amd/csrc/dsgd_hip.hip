@@ -190,6 +190,9 @@ struct dsgd_plan {
   // a row-parallel fp64 plan (dsgd_plan_create_rp64_n and its kin): the lists and their ranges only, no layout -- its steps are
   // the two launches of dsgd_sync_step_f64 over d_idx / d_segs, on whichever value type is loaded at the run (plan_run_rp64)
   bool rp64 = false;
+  // a logistic plan (dsgd_plan_create_lg_n, dsgd_plan_create_from_seed_lg): likewise the lists and their ranges only -- its steps
+  // are the two launches of dsgd_lg_sync_step over d_idx / d_segs (plan_run_lg, csrc/dsgd_lg_calls.hpp)
+  bool lg = false;
   void cs_free() {
     d_cs_hdr.reset(), d_cs_meta.reset(), d_cs_rf.reset(), d_cs_col.reset(), d_cs_val.reset(), d_cs_cl.reset();
     cs_ok = false;
@@ -528,6 +531,8 @@ struct dsgd_ctx {
   int lg_k = 0;
   DevBuf<float> d_lg_g;
   DevBuf<double> d_lg_part;
+  DevBuf<unsigned long long> d_lg_tally;   // dsgd_lg_loss_acc_ranges: [LG_MAX_RANGES][LG_TALLY_WORDS] class tallies, one set per range
+  long long lg_pending_active = 0;         // rows of logistic plan runs since the last dsgd_synchronize (every row contributes)
   DevBuf<WorkSeg> d_lg_ssegs;
   DevBuf<float> d_lg_p;
   unsigned long long bind_count = 0;
@@ -3179,10 +3184,11 @@ int dsgd_synchronize(dsgd_ctx* c, dsgd_batch_stats* stats) {
   DSGD_TRY(bind(c, true));
   DSGD_TRY(read_scalars(c));
   DSGD_TRY(prof_collect(c));
-  const long long act = (long long)c->h_sc->n_active;
+  const long long act = (long long)c->h_sc->n_active + c->lg_pending_active;   // (a logistic plan's rows: all of them active)
   const int err = c->h_sc->err;
   const long long pending = c->pending_samples + (c->job_pending ? (long long)c->h_sc->n_samples : 0);
   c->pending_samples = 0;   // (whatever the outcome: the rows of a rejected run are not carried into the next report)
+  c->lg_pending_active = 0;
   c->job_pending = false;
   DSGD_TRY(reset_counters(c));
   if ((err & (8 | 16)) && c->d_cs_sync) HIP_TRY(hipMemsetAsync(c->d_cs_sync, 0, sizeof(unsigned int) * 2, c->stream));   // the abort word, first
@@ -3226,7 +3232,7 @@ static void plan_abandon(dsgd_ctx* c, dsgd_plan* p) {
 }
 // A plan's frame: offsets checked, the two device blocks taken from the cache, the list ranges uploaded (build stream).
 // The caller fills p->d_idx on the build stream and calls plan_finish; on failure everything is given back.
-static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int32_t n_workers, dsgd_plan** out, bool rp64 = false) {
+static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int32_t n_workers, dsgd_plan** out, bool rp64 = false, bool lg = false) {
   const int64_t n_lists = n_steps * n_workers;
   if (offsets[0] != 0) return fail(DSGD_EINVAL, "offsets[0] must be 0");
   long long mx = 0;
@@ -3251,6 +3257,7 @@ static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int3
   if (!p) return fail(DSGD_ENOMEM, "out of host memory");
   c->plans.push_back(p);
   p->rp64 = rp64;
+  p->lg = lg;
   p->n_steps = n_steps;
   p->n_workers = n_workers;
   p->max_items = mx;
@@ -3287,6 +3294,7 @@ static int plan_frame(dsgd_ctx* c, const int64_t* offsets, int64_t n_steps, int3
 static PlanRoute plan_route(const dsgd_ctx* c, const dsgd_plan* p) {
   PlanFacts f;
   f.rp64 = p->rp64;
+  f.lg = p->lg;
   f.cs_current = p->cs_ok && p->cs_layout == c->layout_gen;
   f.fits_here = p->fits && p->fits_rows == c->n_rows;
   f.vt_current = p->vt_ok && p->vt_layout == c->layout_gen;
@@ -3295,12 +3303,15 @@ static PlanRoute plan_route(const dsgd_ctx* c, const dsgd_plan* p) {
   return route_plan(c->k, route_facts(c), f);
 }
 static int cs64_refused(dsgd_ctx* c);   // (dsgd_fp64_host.hpp, which in turn needs plan_finish: the one declaration ahead)
+// (csrc/dsgd_lg_calls.hpp, behind the plans' entry points that dispatch into it: a logistic plan's refusals and its run)
+static int lg_refuse(dsgd_ctx* c, const char* what);
+static int plan_run_lg(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, float lr);
 // the lists are in p->d_idx (enqueued on the build stream): lay the plan out for the device, close its set-up
 static int plan_finish(dsgd_ctx* c, dsgd_plan* p, dsgd_plan** out) {
   int rc = DSGD_OK;
   // the column slices of the reference's own step sizes are laid out NOW (by the device, on the build stream), not inside
   // the first dsgd_plan_run -- a call its callers time; without a column layout yet (no data / no dimSparsity) at the first run
-  if (plan_lays_out_at_creation(c->k, route_facts(c), p->rp64, (bool)c->d_row_ptr, c->have_ds)) {   // (a row-parallel plan has no layout)
+  if (plan_lays_out_at_creation(c->k, route_facts(c), p->rp64 || p->lg, (bool)c->d_row_ptr, c->have_ds)) {   // (a row-parallel or logistic plan has no layout)
     rc = prepare_layout(c);
     if (rc == DSGD_OK) rc = cs_build(c, p);
     if (rc == DSGD_OK && c->fp64 && !p->cs_ok) rc = cs64_refused(c);
@@ -3474,6 +3485,7 @@ int dsgd_plan_read_lists(dsgd_ctx* c, dsgd_plan* p, int32_t* idx_out, int64_t n,
 int dsgd_plan_record(dsgd_ctx* c, dsgd_plan* p, int32_t on) {
   DSGD_TRY(check_ctx(c));
   if (!p) return fail(DSGD_EINVAL, "null plan");
+  if (p->lg) return fail(DSGD_EUNSUPPORTED, "dsgd_plan_record: a logistic plan keeps no record (there is no gate)");
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(bind(c, true));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3498,6 +3510,7 @@ int dsgd_plan_read_record(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t
                           int32_t* mask_words_out) {
   DSGD_TRY(check_ctx(c));
   if (!p) return fail(DSGD_EINVAL, "null plan");
+  if (p->lg) return fail(DSGD_EUNSUPPORTED, "dsgd_plan_read_record: a logistic plan keeps no record (there is no gate)");
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(bind(c, true));
   if (mask_words_out) *mask_words_out = p->gate_words;
@@ -3572,6 +3585,7 @@ int dsgd_plan_run(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_en
   DSGD_TRY(check_ctx(c));
   DSGD_TRY(plan_steps_check(p, step_begin, step_end));
   std::lock_guard<std::mutex> lk(c->mu);
+  if (p->lg) return plan_run_lg(c, p, step_begin, step_end, lr);   // (its own refusals; dimSparsity plays no part)
   if (!p->rp64) DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_run"));   // (a row-parallel plan spans the ranks: plan_run_rp64_ranks)
   DSGD_TRY(bind(c, true));
   if (c->fp64) return plan_run64(c, p, step_begin, step_end, (double)lr);

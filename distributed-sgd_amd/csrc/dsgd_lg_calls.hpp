@@ -38,7 +38,9 @@ static int lg_report(dsgd_ctx* c, const char* what, const LgCheck& v, int n_work
 
 static int lg_ensure(dsgd_ctx* c, int n_workers) {
   DSGD_TRY(c->d_lg_g.reserve((size_t)c->dp));
-  DSGD_TRY(c->d_lg_part.reserve((size_t)lg_finish_blocks(c->dp) + (size_t)c->n_cu));
+  // (the |w|^2 words, then one word per evaluation workgroup: up to LG_MAX_RANGES ranges of n_cu workgroups each)
+  DSGD_TRY(c->d_lg_part.reserve((size_t)lg_finish_blocks(c->dp) + (size_t)c->n_cu * LG_MAX_RANGES));
+  DSGD_TRY(c->d_lg_tally.reserve((size_t)LG_MAX_RANGES * LG_TALLY_WORDS));
   if (c->lg_k < n_workers) {   // (zeroed once; every finish leaves them zeroed)
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->lg_k = 0;
@@ -106,6 +108,69 @@ static int lg_step_done(dsgd_ctx* c, dsgd_batch_stats* stats, long long total) {
   if (rc != DSGD_OK) c->lg_nsq_stamp = ~0ull - 1;
   if (rc == DSGD_OK && stats) stats->n_active = total;
   return rc;
+}
+
+// ---- resident logistic plans: the lists and their ranges only, no layout (as a row-parallel fp64 plan) ----
+// The caller's lists: dsgd_lg_sync_steps' checks on the host, then the lists resident (the build stream, blocks from the cache).
+int dsgd_plan_create_lg_n(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const int64_t* offsets, int64_t n_steps, int32_t n_workers,
+                          dsgd_plan** out) {
+  DSGD_TRY(check_ctx(c));
+  if (!idx || !offsets || !out || n_steps < 1 || n_workers < 1 || n_idx < 1)
+    return fail(DSGD_EINVAL, "dsgd_plan_create_lg_n: bad arguments (null pointers, no steps, no workers or no rows)");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(lg_refuse(c, "dsgd_plan_create_lg_n"));
+  DSGD_TRY(bind(c, true));   // (nothing here touches w: slice-major weights stay as they are)
+  DSGD_TRY(require_data(c));
+  const LgCheck v = lg_check_flat(idx, n_idx, offsets, n_steps, n_workers, c->n_rows);
+  DSGD_TRY(lg_report(c, "dsgd_plan_create_lg_n", v, n_workers));
+  dsgd_plan* p = nullptr;
+  DSGD_TRY(plan_frame(c, offsets, n_steps, n_workers, &p, false, true));
+  p->h_idx.assign(idx, idx + n_idx);
+  hipError_t e = hipMemcpyAsync(p->d_idx, idx, sizeof(int) * (size_t)n_idx, hipMemcpyHostToDevice, c->build_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->build_stream);
+  if (e != hipSuccess) {
+    plan_abandon(c, p);
+    return fail(DSGD_EHIP, "plan upload: %s", hipGetErrorString(e));
+  }
+  return plan_finish(c, p, out);
+}
+// ... drawn by the device from the reference's stream: dsgd_plan_create_from_seed's arguments, limits, refusals and
+// *jstate / *n_steps_out / *draws_out (csrc/dsgd_seed_host.hpp, csrc/dsgd_shuffle.hpp as they stand)
+int dsgd_plan_create_from_seed_lg(dsgd_ctx* c, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
+                                  int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
+  return plan_from_seed_whole(c, "dsgd_plan_create_from_seed_lg", false, jstate, split_begin, split_end, n_splits, max_samples, batch_size, out,
+                              n_steps_out, draws_out, true);
+}
+// The steps [step_begin, step_end) of a logistic plan (dsgd_plan_run holds the lock and has checked the range): per step the
+// two launches of dsgd_lg_sync_step over the plan's resident lists -- no upload, no host synchronisation.  Every refusal comes
+// before the first launch.  dsgd_synchronize reports the rows (every row contributes: n_active == n_samples).
+static int plan_run_lg(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, float lr) {
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, "dsgd_plan_run (a logistic plan)", &fresh));
+  DSGD_TRY(plan_revalidate(c, p));   // (a plan from before the last load: DSGD_ERANGE here, before anything is enqueued)
+  DSGD_TRY(prepare_layout(c));
+  const int K = p->n_workers;
+  DSGD_TRY(lg_ensure(c, K));
+  if (p->built_pending) {   // the plan's set-up ran beside the launch stream: wait for it, once
+    HIP_TRY(hipStreamWaitEvent(c->stream, p->built_ev, 0));
+    p->built_pending = false;
+  }
+  if (step_end <= step_begin) {
+    if (fresh) c->lg_nsq_stamp = c->bind_count;   // (the weights are the ones |w|^2 was taken from)
+    return DSGD_OK;
+  }
+  c->s_dirty = true;
+  c->lg_nsq_stamp = ~0ull - 1;
+  for (long long t = step_begin; t < step_end; ++t) {
+    long long mx = 0;
+    for (int k = 0; k < K; ++k) mx = std::max<long long>(mx, p->offsets[(size_t)(t * K + k + 1)] - p->offsets[(size_t)(t * K + k)]);
+    DSGD_TRY(lg_launch(c, true, K, mx, LG_STEP, lr, p->d_idx, p->d_segs + t * K));
+  }
+  c->lg_nsq_stamp = c->bind_count;   // (the last finish left |w'|^2 in d_lg_part)
+  const long long rows = p->offsets[(size_t)(step_end * K)] - p->offsets[(size_t)(step_begin * K)];
+  c->pending_samples += rows;
+  c->lg_pending_active += rows;
+  return DSGD_OK;
 }
 
 int dsgd_lg_gradient(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, float* g_out, dsgd_batch_stats* stats) {
@@ -257,6 +322,60 @@ int dsgd_lg_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row
   const double n = (double)rows;
   if (loss) *loss = c->cfg.lambda * nsq + ls / n;
   if (acc) *acc = (double)c->h_sc->counts[0] / n;
+  return DSGD_OK;
+}
+
+// dsgd_lg_loss_acc over up to LG_MAX_RANGES ranges (an epoch's train and test passes) in ONE launch with ONE synchronisation:
+// every range's figures are the bits of dsgd_lg_loss_acc on that range alone (csrc/dsgd_lg_host.hpp: lg_eval_table)
+int dsgd_lg_loss_acc_ranges(dsgd_ctx* c, const float* w, const int64_t* row_begin, const int64_t* row_end, int32_t n_ranges, double* loss_out,
+                            double* acc_out) {
+  DSGD_TRY(check_ctx(c));
+  if (!row_begin || !row_end || n_ranges < 1 || (!loss_out && !acc_out))
+    return fail(DSGD_EINVAL, "dsgd_lg_loss_acc_ranges: bad arguments (null ranges, no range, or null loss_out and acc_out)");
+  if (n_ranges > LG_MAX_RANGES) return fail(DSGD_EINVAL, "dsgd_lg_loss_acc_ranges: %d ranges, more than the %d of one call", n_ranges, LG_MAX_RANGES);
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, "dsgd_lg_loss_acc_ranges", &fresh));
+  const LgCheck v = lg_check_ranges(row_begin, row_end, n_ranges, c->n_rows);
+  DSGD_TRY(lg_report(c, "dsgd_lg_loss_acc_ranges", v, n_ranges));
+  LgEvalTable t;
+  if (!lg_eval_table(row_begin, row_end, n_ranges, c->n_cu, &t)) return fail(DSGD_EINVAL, "dsgd_lg_loss_acc_ranges: no grid for %d ranges", n_ranges);
+  DSGD_TRY(prepare_layout(c));
+  if (w) DSGD_TRY(set_weights_locked(c, w));
+  DSGD_TRY(lg_ensure(c, 1));
+  const long long nb = lg_finish_blocks(c->dp);
+  if (w || !fresh) {   // (as dsgd_lg_loss_acc: the finish's grid and tree, the same bits)
+    hipLaunchKernelGGL(dsgd_lg_nsq_kernel, dim3((unsigned)nb), dim3(LG_THREADS), 0, c->stream, c->d_w, c->dp, c->d_lg_part);
+    HIP_TRY(hipGetLastError());
+  }
+  DSGD_TRY(reset_counters(c));
+  HIP_TRY(hipMemsetAsync(c->d_lg_tally, 0, sizeof(unsigned long long) * LG_MAX_RANGES * LG_TALLY_WORDS, c->stream));
+  // ONE tile size for the launch, by its longest range (dsgd_lg_loss_acc's rule for that range); the size moves no bit of any
+  // range: row_dot reads the same float from the tile as from memory and adds in the same order
+  int hw = v.longest >= 4096 ? c->hw_eval : std::min(c->hw_eval, 1024);
+  while (lg_eval_lds_floats(hw) > DSGD_LDS_FLOATS) hw -= 64;
+  const size_t lds = sizeof(float) * (size_t)lg_eval_lds_floats(hw);
+  hipLaunchKernelGGL(dsgd_lg_eval_ranges_kernel, dim3((unsigned)t.grid), dim3(LG_EVAL_THREADS), lds, c->stream, view(c), c->d_w, t, c->d_lg_tally.get(),
+                     hw, c->d_lg_part + nb);
+  HIP_TRY(hipGetLastError());
+  const size_t words = (size_t)(nb + t.grid), tally_words = (size_t)LG_MAX_RANGES * LG_TALLY_WORDS;
+  DSGD_TRY(pin_acquire(c->pin_out, sizeof(double) * words + sizeof(unsigned long long) * tally_words));
+  double* part = static_cast<double*>(c->pin_out.p.get());
+  unsigned long long* tally = reinterpret_cast<unsigned long long*>(part + words);
+  HIP_TRY(hipMemcpyAsync(part, c->d_lg_part, sizeof(double) * words, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(tally, c->d_lg_tally, sizeof(unsigned long long) * tally_words, hipMemcpyDeviceToHost, c->stream));
+  DSGD_TRY(read_scalars(c));   // the one synchronisation of the call
+  DSGD_TRY(check_err_flag(c));
+  c->lg_nsq_stamp = c->bind_count;
+  double nsq = 0.0;   // (in order: the same bits on every call)
+  for (long long i = 0; i < nb; ++i) nsq += part[i];
+  for (int r = 0; r < t.n; ++r) {
+    double ls = 0.0;
+    for (int i = 0; i < t.r[r].n_blocks; ++i) ls += part[nb + t.r[r].first_block + i];
+    const double n = (double)(t.r[r].row_end - t.r[r].row_begin);
+    if (loss_out) loss_out[r] = c->cfg.lambda * nsq + ls / n;
+    if (acc_out) acc_out[r] = (double)tally[(size_t)r * LG_TALLY_WORDS] / n;
+  }
   return DSGD_OK;
 }
 

@@ -7,6 +7,8 @@
 //   lg_finish_blocks    the finish kernel's grid: ONE column per lane, so that the per-workgroup sums of |w|^2 do not depend on
 //                       the device (the loss is the same number wherever it is computed)
 //   lg_eval_blocks      the evaluation's persistent grid
+//   lg_eval_table       the grid of an evaluation of up to LG_MAX_RANGES row ranges in ONE launch: range r gets its own run of
+//                       lg_eval_blocks(rows_r) workgroups, one run behind the other (the grid each range has in a launch of its own)
 //   lg_check_lists      a step's per-worker lists             (what is wrong, and where: plain data, the callers word the message)
 //   lg_check_ranges     a step's per-worker row ranges
 //   lg_check_flat       an epoch's flat lists                 (csrc/dsgd_plan_check.hpp: flat_lists_check)
@@ -51,6 +53,38 @@ inline long long lg_eval_blocks(long long rows, int n_cu) {
   long long b = (rows + per - 1) / per;
   if (b > n_cu) b = n_cu;
   return b < 1 ? 1 : b;
+}
+
+// Several ranges, one launch (dsgd_lg_eval_ranges_kernel): range r is walked by the workgroups [first_block, first_block +
+// n_blocks) and by no other, n_blocks = lg_eval_blocks(rows of r) -- the stride, the per-workgroup sums and their order are
+// those of a launch over that range alone, so its loss has the same bits.  Ranges may overlap or repeat: each has its own
+// workgroups, its own words of partial sums (at its workgroups' numbers) and its own tallies.
+constexpr int LG_MAX_RANGES = 16;
+constexpr int LG_TALLY_WORDS = 4;   // per range: signum(d) == y, == 0, == -y, and a spare (32-byte rows)
+struct LgEvalRange {
+  long long row_begin, row_end;
+  int first_block, n_blocks;
+};
+struct LgEvalTable {
+  LgEvalRange r[LG_MAX_RANGES];
+  int n, grid;
+};
+// false: fewer than one range or more than LG_MAX_RANGES, a null table or no compute unit (the ranges themselves:
+// lg_check_ranges, which the callers ask first)
+inline bool lg_eval_table(const int64_t* row_begin, const int64_t* row_end, int n_ranges, int n_cu, LgEvalTable* t) {
+  if (!row_begin || !row_end || !t || n_ranges < 1 || n_ranges > LG_MAX_RANGES || n_cu < 1) return false;
+  *t = LgEvalTable{};
+  int at = 0;
+  for (int i = 0; i < n_ranges; ++i) {
+    t->r[i].row_begin = row_begin[i];
+    t->r[i].row_end = row_end[i];
+    t->r[i].first_block = at;
+    t->r[i].n_blocks = (int)lg_eval_blocks(row_end[i] - row_begin[i], n_cu);
+    at += t->r[i].n_blocks;
+  }
+  t->n = n_ranges;
+  t->grid = at;
+  return true;
 }
 
 enum LgFault {

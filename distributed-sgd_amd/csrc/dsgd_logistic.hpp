@@ -33,6 +33,8 @@
 //                             same call gives the same bits; nothing is added with floating-point atomics.  Every l_i carries
 //                             at most |d_i - d_i,exact| and a few fp64 roundings of error, the tree at most (n + 64) 2^-53 of the sum
 //                             (tests/logistic_bound.py: dloss).
+//   dsgd_lg_eval_ranges_kernel  the same for up to 16 row ranges in ONE launch: every range has its own run of workgroups (the grid
+//                             of a launch over it alone: the same bits), its own partial sums and its own tally words
 //   dsgd_lg_predict_kernel    sigma(d) per listed position: 1 / (1 + exp(-d)) in fp64 from the fp32 d, rounded to float once.
 //
 // Plain C++ and vector atomics only.
@@ -219,6 +221,70 @@ __global__ void __launch_bounds__(LG_EVAL_THREADS) dsgd_lg_eval_kernel(CsrView m
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&sc->counts[3], (unsigned long long)(row_end - row_begin));
   block_tally3(c0, c1, c2, sc, reinterpret_cast<unsigned int*>(wl + hw));
+  const double s = lg_block_sum(ls, reinterpret_cast<double*>(lds + lg_eval_red_at(hw)), LG_EVAL_THREADS / 64);
+  if (threadIdx.x == 0) loss_part[blockIdx.x] = s;
+}
+
+// block_tally3 into a range's own words (DevScalars::counts holds one set)
+__device__ __forceinline__ void lg_block_tally3(unsigned int c0, unsigned int c1, unsigned int c2, unsigned long long* counts, unsigned int* tally) {
+  __syncthreads();
+  if (threadIdx.x < 3) tally[threadIdx.x] = 0u;
+  __syncthreads();
+  c0 = wave_sum_u32(c0);
+  c1 = wave_sum_u32(c1);
+  c2 = wave_sum_u32(c2);
+  if ((threadIdx.x & 63) == 0) {
+    if (c0) atomicAdd(&tally[0], c0);
+    if (c1) atomicAdd(&tally[1], c1);
+    if (c2) atomicAdd(&tally[2], c2);
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 && tally[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)tally[threadIdx.x]);
+}
+
+// Up to LG_MAX_RANGES row ranges in ONE launch (csrc/dsgd_lg_host.hpp: lg_eval_table).  A workgroup belongs to ONE range and
+// walks it as dsgd_lg_eval_kernel's workgroup of the same number walks it in a launch over that range alone: the same rows in
+// the same order, the same tree, its sum in loss_part[blockIdx.x] -- the host adds a range's words in order.  The tallies go
+// to the range's own LG_TALLY_WORDS words of `tally` (zero on entry).  The tile size hw moves no bit: a weight is the same
+// float from LDS as from memory, and row_dot adds a lane's products in the order of the row either way.
+// grid: t.grid workgroups; dynamic LDS as dsgd_lg_eval_kernel
+__global__ void __launch_bounds__(LG_EVAL_THREADS) dsgd_lg_eval_ranges_kernel(CsrView m, const float* __restrict__ w, LgEvalTable t,
+                                                                             unsigned long long* tally, int hw, double* loss_part) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* wl = lds;
+  for (int j = threadIdx.x; j < hw; j += LG_EVAL_THREADS) wl[j] = w[j];
+  __syncthreads();
+  // this workgroup's range (the same on every lane; selects, not an indexed read of the argument)
+  int range = 0, first = 0, blocks = t.r[0].n_blocks;
+  long long row_begin = t.r[0].row_begin, row_end = t.r[0].row_end;
+#pragma unroll
+  for (int i = 1; i < LG_MAX_RANGES; ++i) {
+    if (i < t.n && (int)blockIdx.x >= t.r[i].first_block) {
+      range = i;
+      first = t.r[i].first_block;
+      blocks = t.r[i].n_blocks;
+      row_begin = t.r[i].row_begin;
+      row_end = t.r[i].row_end;
+    }
+  }
+  const int sub = threadIdx.x % LG_GROUP;
+  const long long group = ((long long)((int)blockIdx.x - first) * LG_EVAL_THREADS + threadIdx.x) / LG_GROUP;
+  const long long n_groups = (long long)blocks * LG_EVAL_THREADS / LG_GROUP;
+  unsigned int c0 = 0, c1 = 0, c2 = 0;
+  double ls = 0.0;
+  for (long long row = row_begin + group; row < row_end; row += n_groups) {
+    RowRegs<LG_GROUP, LG_UNR> r;
+    const float d = row_dot<LG_GROUP, LG_UNR, true>(m, m.row_ptr[row], m.row_ptr[row + 1], wl, w, hw, sub, r);
+    if (sub == 0) {
+      const double a = (double)m.label[row] * (double)d;   // (exact)
+      if (a > 0.0) c0++;
+      else if (a < 0.0) c2++;
+      else c1++;
+      ls = ls + lg_loss(a);
+    }
+  }
+  lg_block_tally3(c0, c1, c2, tally + range * LG_TALLY_WORDS, reinterpret_cast<unsigned int*>(wl + hw));
   const double s = lg_block_sum(ls, reinterpret_cast<double*>(lds + lg_eval_red_at(hw)), LG_EVAL_THREADS / 64);
   if (threadIdx.x == 0) loss_part[blockIdx.x] = s;
 }

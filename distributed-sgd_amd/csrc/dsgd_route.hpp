@@ -254,14 +254,16 @@ inline RangesRoute route_ranges(const Knobs& k, const RouteFacts& f, int n_worke
 // ---- resident plans ----
 struct PlanFacts {
   bool rp64 = false;         // a row-parallel fp64 plan
+  bool lg = false;           // a logistic plan (csrc/dsgd_lg_calls.hpp: plan_run_lg)
   bool cs_current = false;   // its column slices are laid out for the current column ranking
   bool fits_here = false;    // every list fits the staged sub-batch of the one-workgroup kernel, on the rows loaded now
   bool vt_current = false;   // its virtual tiles are laid out for the current split streams
   long long max_step_rows = 0;
   int n_workers = 0;
 };
-enum PlanRoute { PLAN_RP64, PLAN_CS64, PLAN_CS, PLAN_ONE_WG, PLAN_VT, PLAN_ROWWISE };
+enum PlanRoute { PLAN_RP64, PLAN_CS64, PLAN_CS, PLAN_ONE_WG, PLAN_VT, PLAN_ROWWISE, PLAN_LG };
 inline PlanRoute route_plan(const Knobs& k, const RouteFacts& f, const PlanFacts& p) {
+  if (p.lg) return PLAN_LG;   // (the model decides, not a knob: the lists and their ranges only, as PLAN_RP64)
   if (p.rp64) return PLAN_RP64;
   if ((k.cs_enable || f.fp64) && !f.comm && p.cs_current) return f.fp64 ? PLAN_CS64 : PLAN_CS;
   if (plan_kernel_ok(k, f, p.max_step_rows, p.n_workers) && p.fits_here) return PLAN_ONE_WG;
@@ -271,6 +273,7 @@ inline PlanRoute route_plan(const Knobs& k, const RouteFacts& f, const PlanFacts
 // dsgd_plan_info's first word (include/dsgd.h); a row-wise plan says whether a layout was tried for the current ranking
 inline int plan_info_code(PlanRoute r, bool layout_tried) {
   switch (r) {
+    case PLAN_LG: return 7;
     case PLAN_RP64: return 6;
     case PLAN_CS64: return 5;
     case PLAN_CS: return 1;

@@ -34,6 +34,7 @@ struct SeedRequest {
   int chunks;                       // workgroups per list
   int max_rej;                      // rejections inside one shuffle
   std::string too_large;            // the refusal of a batch beyond max_batch or a split beyond JR_MAX_LEN
+  bool lg = false;                  // a logistic plan (an fp32 context without a communicator: lg_refuse) instead of a column-slice one
 };
 
 struct SeedLaps {   // DSGD_SEED_PROF (tuning: where an epoch's 14 ms go)
@@ -200,7 +201,9 @@ static int plan_from_seed(dsgd_ctx* c, const SeedRequest& r, uint64_t* jstate, i
                           int64_t* draws_out) {
   {   // (refused with *out as it was)
     std::lock_guard<std::mutex> lk0(c->mu);
-    if (r.rp64) {
+    if (r.lg) {
+      DSGD_TRY(lg_refuse(c, r.what));
+    } else if (r.rp64) {
       DSGD_TRY(require_fp64(c, r.what));
       if (!r.comm_ok) DSGD_TRY(refuse_fp64_comm(c, r.what));
     } else {
@@ -228,6 +231,7 @@ static int plan_from_seed(dsgd_ctx* c, const SeedRequest& r, uint64_t* jstate, i
   std::lock_guard<std::mutex> lk(c->mu);
   if (!r.comm_ok) DSGD_TRY(refuse_fp64_comm(c, r.what));
   if (!r.rp64) DSGD_TRY(refuse_val64(c, r.what));
+  if (r.lg) DSGD_TRY(lg_refuse(c, r.what));
   DSGD_TRY(bind(c, true));
   for (int i = 0; i < r.n_local; ++i)
     if (r.split_begin[i] + r.len[(size_t)(r.first + i)] > c->n_rows)
@@ -240,7 +244,7 @@ static int plan_from_seed(dsgd_ctx* c, const SeedRequest& r, uint64_t* jstate, i
   DSGD_TRY(seed_walk(c, r, f, s0, max_len, lap, &w));
   // the plan's frame, then pass B straight into its index buffer
   dsgd_plan* p = nullptr;
-  DSGD_TRY(plan_frame(c, f.offsets.data(), n_steps, r.n_local, &p, r.rp64));
+  DSGD_TRY(plan_frame(c, f.offsets.data(), n_steps, r.n_local, &p, r.rp64, r.lg));
   lap("plan frame");
   p->idx_trusted = true;
   p->drawn = true;
@@ -259,12 +263,14 @@ static int plan_from_seed(dsgd_ctx* c, const SeedRequest& r, uint64_t* jstate, i
 
 // a job hosted whole: lengths end - begin, first = 0, n_local = n_splits
 static int plan_from_seed_whole(dsgd_ctx* c, const char* what, bool rp64, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end,
-                                int32_t n_splits, int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
+                                int32_t n_splits, int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out,
+                                bool lg = false) {
   DSGD_TRY(check_ctx(c));
   if (!jstate || !split_begin || !split_end || !out || !n_steps_out || n_splits < 1 || batch_size < 1) return fail(DSGD_EINVAL, "bad arguments");
   char msg[160];
   snprintf(msg, sizeof(msg), "device-drawn lists serve batches up to %d rows of splits up to %d rows (draw them on the host)", JR_MAX_TAKE, JR_MAX_LEN);
   SeedRequest r{what, rp64, false, false, {}, 0, n_splits, split_begin, batch_size, JR_MAX_TAKE, 1, JR_MAX_REJ, msg};
+  r.lg = lg;
   for (int k = 0; k < n_splits; ++k) r.len.push_back((long long)(split_end[k] - split_begin[k]));
   return plan_from_seed(c, r, jstate, max_samples, out, n_steps_out, draws_out);
 }

@@ -13,6 +13,7 @@ the reference.  Citations are relative to /root/reference/src/main/scala/epfl/di
     predict, distributed_loss, distributed_accuracy (both masters)   core/Master.scala:61-98
     local_sampled_loss, local_sampled_accuracy (both masters)        core/Master.scala:109-118
     MasterAsync.fit   core/MasterAsync.scala:32-62, 96-177
+    LogisticSync.fit  core/Master.scala:120-218 with the logistic model of one engine (resident logistic plans)
     Metrics           the Kamon instruments of the path, same names (core/Slave.scala:90-181, core/Master.scala:150-183)
     format_final_weights   the `final weights: idx:val ...` log line (Main.scala:114)
 
@@ -1137,3 +1138,143 @@ class MasterAsync(_DistributedEval, _SampledEval):
             if plan is not None:
                 plan.destroy()
         return GradState(best_w, updates=int(updates)).finish(best_loss)
+
+
+# ---- Master.fit for the logistic model ---------------------------------------------------------------------------------
+class LogisticSync:
+    """core/Master.scala:120-218 for the LOGISTIC model of one engine (include/dsgd.h "THE LOGISTIC MODEL").
+
+    The flow is Master.fit's: SplitStrategy.vanilla splits; per epoch every worker's split is reshuffled for every batch
+    from the reference's random stream; an epoch's steps run as ONE resident logistic plan (Engine.plan_run), whose lists
+    the device draws (Engine.lg_plan_from_seed) -- or, where that is refused (DSGD_EUNSUPPORTED: a batch beyond 1,024
+    rows, ...) or switched off, the host draws from the same stream (epoch_lists) and uploads (Engine.lg_plan_flat).  With
+    `prefetch` the next epoch's plan is created while this one runs.  After the epoch train and test loss and accuracy
+    come from ONE Engine.lg_loss_acc_ranges call, and the reference's stopping criterion looks at the test losses,
+    newest first.  The lists, the weights and the figures are the same bits whichever side drew the lists.
+
+    data layout: rows [0, n_train) are the train set, [n_train, n_rows) the test set (Main.scala:52).
+
+    Limits: one engine hosts every worker; no distributed or sampled evaluation, no asynchronous fit, no JNI."""
+
+    def __init__(self, backend, n_train: int, n_rows: int, node_count: int, rnd: Optional[JavaRandom] = None, log=None,
+                 metrics: Optional[Metrics] = None, device_lists: Optional[bool] = None, prefetch: bool = True):
+        if not 0 < n_train < n_rows:
+            raise ValueError("LogisticSync needs train rows [0, n_train) and test rows [n_train, n_rows)")
+        self.backend, self.n_train, self.n_rows, self.node_count = backend, n_train, n_rows, node_count
+        self.metrics = metrics or Metrics()
+        self.rnd = rnd or JavaRandom(0)
+        self.log = log or (lambda *a: None)
+        self.device_lists = os.environ.get("DSGD_DEVICE_LISTS", "1") != "0" if device_lists is None else bool(device_lists)
+        self.prefetch = prefetch
+        self.losses: List[float] = []
+        self.accs: List[float] = []
+        self.test_losses: List[float] = []
+        self.test_accs: List[float] = []
+        self.steps_run = 0
+        self.device_drawn_epochs = 0
+        self._pending = None
+
+    def local_loss(self, test: bool = False):       # Master.scala:104-106
+        lo, hi = (self.n_train, self.n_rows) if test else (0, self.n_train)
+        return self.backend.lg_loss_acc(lo, hi)[0]
+
+    def local_accuracy(self, test: bool = False):   # Master.scala:100-102
+        lo, hi = (self.n_train, self.n_rows) if test else (0, self.n_train)
+        return self.backend.lg_loss_acc(lo, hi)[1]
+
+    def predict_proba(self, rows):
+        """P(y = +1 | x) of the listed rows under the resident weights (Engine.lg_predict_proba)."""
+        return self.backend.lg_predict_proba(rows)
+
+    def _next_plan(self, split, max_samples, batch_size):
+        """The next epoch as a logistic plan: its lists drawn by the device where that applies, else by the host."""
+        seed_before = self.rnd.seed
+        if self.device_lists and all(r.step == 1 for r in split):
+            try:
+                plan, n_steps, state, _ = self.backend.lg_plan_from_seed(seed_before, split, max_samples, batch_size)
+            except Exception as e:   # (DSGD_EUNSUPPORTED: outside the device form -- the host draws from here on)
+                if getattr(e, "code", None) != -7:
+                    raise
+                self.device_lists = False
+            else:
+                self.rnd.seed = state
+                return {"plan": plan, "n_steps": n_steps, "n_samples": plan.n_samples if plan is not None else 0, "seed_before": seed_before,
+                        "device_drawn": True}
+        idx, offsets, n_steps = epoch_lists(self.rnd, split, max_samples, batch_size)
+        plan = self.backend.lg_plan_flat(idx, offsets, n_steps, len(split)) if n_steps else None
+        return {"plan": plan, "n_steps": n_steps, "n_samples": int(offsets[n_steps * len(split)]), "seed_before": seed_before, "device_drawn": False}
+
+    def _drop_pending(self):
+        """fit is over: the plan of an epoch that never ran is dropped and the stream goes back to where the reference's stands."""
+        p, self._pending = self._pending, None
+        if p is not None:
+            self.rnd.seed = p["seed_before"]
+            if p["plan"] is not None:
+                p["plan"].destroy()
+
+    def _epoch(self, split, max_samples, batch_size, learning_rate, epochs_left):
+        """One epoch's batch loop (core/Master.scala:179-199) as one plan run."""
+        n_expected = len(range(0, max_samples, batch_size))
+        cur, self._pending = self._pending, None
+        if cur is None:
+            cur = self._next_plan(split, max_samples, batch_size)
+        t0 = time.perf_counter_ns()
+        try:
+            if cur["n_steps"]:
+                self.backend.plan_run(cur["plan"], 0, cur["n_steps"], learning_rate)   # enqueued: two launches per step, no read
+            if self.prefetch and epochs_left > 1 and cur["n_steps"] == n_expected:
+                self._pending = self._next_plan(split, max_samples, batch_size)        # ... and while they run: the next epoch's plan
+        finally:
+            if cur["plan"] is not None:
+                cur["plan"].destroy()                                                  # (behind the run; no synchronisation)
+                cur["plan"] = None
+        if cur["n_steps"] < n_expected:
+            self.backend.synchronize()
+            # the reference's next batch hands some slave an empty slice: Vec.sum throws there (math/Vec.scala:129)
+            raise ValueError("Cannot sum an empty list of vectors (batch %d of the epoch: a worker's slice is empty)" % cur["n_steps"])
+        # :206-209 -- the epoch's evaluation passes: one launch, one synchronisation (behind the epoch's steps)
+        (l, a), (tl, ta) = self.backend.lg_loss_acc_ranges([(0, self.n_train), (self.n_train, self.n_rows)])
+        dt = time.perf_counter_ns() - t0
+        self.backend.synchronize()   # (the stream is idle: the rows the plan ran are collected)
+        for s_ in range(cur["n_steps"]):
+            batch = s_ * batch_size
+            self.log("samples %d - %d / %d" % (batch + 1, min(batch + batch_size, max_samples), max_samples))
+        with self.metrics._lock:
+            self.metrics.histograms.setdefault("master.sync.batch.duration", []).extend([dt // cur["n_steps"]] * cur["n_steps"])
+        self.metrics.counter("slave.sync.backward", cur["n_samples"])
+        self.steps_run += cur["n_steps"]
+        self.device_drawn_epochs += 1 if cur["device_drawn"] else 0
+        self.losses.insert(0, l)
+        self.accs.insert(0, a)
+        self.test_losses.insert(0, tl)
+        self.test_accs.insert(0, ta)
+
+    def fit(self, initial_weights, max_epochs: int, batch_size: int, learning_rate: float,
+            stopping_criterion: Callable[[Sequence[float]], bool]) -> GradState:
+        split = split_vanilla(self.n_train, self.node_count)  # Master.scala:136
+        max_samples = max(len(r) for r in split)              # :138
+        self.backend.set_weights(np.asarray(initial_weights, dtype=np.float32))
+        state = GradState(np.asarray(initial_weights, dtype=np.float32))
+        self._pending = None
+        epoch = 0
+        try:
+            while True:
+                if self.losses:
+                    self.log("loss after epoch %d: %s" % (epoch, self.losses[0]))
+                    self.log("acc after epoch %d: %s" % (epoch, self.accs[0]))
+                    self.metrics.histogram("master.sync.loss", self.losses[0])          # Master.scala:150
+                    self.metrics.histogram("master.sync.acc", 100 * int(self.accs[0]))  # :151
+                if epoch >= max_epochs:                             # :154
+                    self.log("Reached max number of epochs: stopping computation")
+                    break
+                if stopping_criterion(self.test_losses):            # :166
+                    self.log("Converged to target: stopping computation")
+                    break
+                self._epoch(split, max_samples, batch_size, learning_rate, epochs_left=max_epochs - epoch)
+                state = state.replace_grad(state.grad)   # (the weights stay on the device between the epochs)
+                epoch += 1
+        finally:
+            self._drop_pending()
+        if state.updates:
+            state = GradState(self.backend.get_weights(), state.loss, state.start, state.updates, state.end)
+        return state.finish(self.losses[0] if self.losses else None)

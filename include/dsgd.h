@@ -477,7 +477,8 @@ int dsgd_plan_run(dsgd_ctx* ctx, dsgd_plan* plan, int64_t step_begin, int64_t st
 int dsgd_plan_run_f64(dsgd_ctx* ctx, dsgd_plan* plan, int64_t step_begin, int64_t step_end, double lr);
 /* How a plan will run (nothing in the reference; benchmarks, tests): vals[0] = 1 column slices (dsgd_cs_step_kernel),
  * 2 the one-workgroup kernel, 3 virtual tiles, 4 the row-parallel kernels, 5 fp64 column slices, 6 a row-parallel fp64
- * plan (dsgd_plan_create_rp64_n and its kin: strides 0), 0 not laid out yet; [1] slices, [2..4] slot /
+ * plan (dsgd_plan_create_rp64_n and its kin: strides 0), 7 a logistic plan (dsgd_plan_create_lg_n, dsgd_plan_create_from_seed_lg:
+ * strides 0), 0 not laid out yet; [1] slices, [2..4] slot /
  * row / column-list strides, [5] slots per lane, [6] 1 if the device laid it out, [7] words per step of the record,
  * [8] lanes per slice workgroup (512; 256 where DSGD_CS_NT=256 took: [5] is 2 for that kernel and the wide two-slot one).
  * n <= 9 slots.                                                                                                       */
@@ -917,10 +918,26 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *   DSGD_ESTATE        no data loaded, or the lock-free engine is running
  *   DSGD_EUNSUPPORTED  an fp64 context, or a communicator attached
  *
- * LIMITS (out of scope, each refused or simply absent): no JNI / Scala binding; no host mirror (host.MasterSync /
- * MasterAsync stay the SVM's); no resident dsgd_plan handles and no device-drawn lists (dsgd_lg_sync_steps uploads an
- * epoch's lists once instead); no asynchronous engine; no fp64 contexts and no Double feature values; no
- * communicators; no Sparse boundary forms.
+ * RESIDENT PLANS.  dsgd_plan_create_lg_n (the arguments of dsgd_plan_create_n; dsgd_lg_sync_steps' checks on the host before
+ * anything is staged) and dsgd_plan_create_from_seed_lg (the arguments, limits, refusals and *jstate / *n_steps_out /
+ * *draws_out of dsgd_plan_create_from_seed: the device draws the epoch's lists from the reference's stream) make a
+ * LOGISTIC plan: the lists and their ranges resident, no layout (as a row-parallel fp64 plan).  dsgd_plan_run on it
+ * enqueues, per step, the two launches of dsgd_lg_sync_step over the resident lists -- no upload, no host synchronisation;
+ * the weights get the bits of dsgd_lg_sync_steps on the same lists.  dsgd_synchronize reports the rows run, n_active ==
+ * n_samples.  dimSparsity is not asked for.  dsgd_plan_info: vals[0] = 7, strides 0.  dsgd_plan_read_lists and
+ * dsgd_plan_destroy as for any plan.  Refused before anything is enqueued: what every call here refuses (above);
+ * dsgd_plan_run_f64, dsgd_plan_run_async_f64, dsgd_plan_record and dsgd_plan_read_record on such a plan
+ * (DSGD_EUNSUPPORTED); a plan from before a dsgd_load_csr whose lists no longer fit the rows (DSGD_ERANGE at the run).
+ *
+ * dsgd_lg_loss_acc_ranges: dsgd_lg_loss_acc over n_ranges <= 16 row ranges (they may overlap or repeat) in ONE launch
+ * with ONE synchronisation -- an epoch's train and test passes.  loss_out[r] and acc_out[r] (either may be NULL) are the
+ * bits of dsgd_lg_loss_acc on range r alone: every range has its own workgroups, the grid of a launch of its own.
+ * DSGD_EINVAL: more than 16 ranges, none, an empty or reversed range; DSGD_ERANGE: a range that leaves the rows.
+ *
+ * LIMITS (out of scope, each refused or simply absent): no JNI / Scala binding; the host mirror is host.LogisticSync
+ * (Master.fit's flow on one context: no distributed or sampled evaluation, no asynchronous fit; host.MasterSync /
+ * MasterAsync stay the SVM's); no fused or persistent one-launch step; no column slices; no asynchronous engine; no fp64
+ * contexts and no Double feature values; no communicators; no Sparse boundary forms; no predict_ranges.
  *
  * dsgd_lg_gradient: one worker's regularised sum over the listed rows, key order, from the resident weights or from w
  * (which then replaces them, as in dsgd_gradient).  dsgd_lg_sync_step / _ranges: one step over K lists / K row
@@ -939,6 +956,12 @@ int dsgd_lg_sync_steps(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const i
                        int32_t n_workers, float lr, dsgd_batch_stats* stats);
 int dsgd_lg_loss_acc(dsgd_ctx* ctx, const float* w /* NULL = resident */, int64_t row_begin, int64_t row_end, double* loss, double* acc);
 int dsgd_lg_predict(dsgd_ctx* ctx, const float* w /* NULL = resident */, const int32_t* idx, int64_t n, float* p_out /* n */);
+int dsgd_plan_create_lg_n(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const int64_t* offsets /* n_steps * n_workers + 1 */, int64_t n_steps,
+                          int32_t n_workers, dsgd_plan** out);
+int dsgd_plan_create_from_seed_lg(dsgd_ctx* ctx, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
+                                  int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out);
+int dsgd_lg_loss_acc_ranges(dsgd_ctx* ctx, const float* w /* NULL = resident */, const int64_t* row_begin, const int64_t* row_end, int32_t n_ranges,
+                            double* loss_out /* n_ranges */, double* acc_out /* n_ranges */);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,7 @@ loss and accuracy, fit (sync or async, early stopping by patience / conv-delta),
 accuracy -- with the HIP engine hosting all the workers.
 
     DSGD_DATA_PATH=/data/rcv1 python tools/train.py [--conf application.conf] [--synthetic ROWS] [--device 0] [--weights-out w.txt]
-                                                    [--precision fp64] [--f64-rp-plans] [--model logistic]
+                                                    [--precision fp64] [--f64-rp-plans] [--model logistic [--lg-plans]]
 
 --precision fp64: the engine keeps the reference's Double weights (include/dsgd.h "THE FP64 MODE"); an async fit runs the
 zero-lag schedule of host.MasterAsync (one update at a time, every update seen by every worker).
@@ -16,6 +16,9 @@ host-drawn lists, one agreement between the ranks per epoch, instead of one sync
 --model logistic: the logistic model on the same rows (include/dsgd.h "THE LOGISTIC MODEL"; fp32, synchronous): per epoch every
 worker's split is shuffled on the host and cut into batches, the epoch's steps run as ONE lg_sync_steps call, and lg_loss_acc
 reports train and test log-loss and accuracy.  The default model is the SVM, and nothing changes on its path.
+--lg-plans (with --model logistic): Master.fit's flow instead (host.LogisticSync) -- the lists drawn from the reference's random
+stream, by the device where it can; an epoch as ONE resident logistic plan, the next one created while it runs; train and test
+evaluated in one launch; the reference's early stopping (patience / conv-delta) over the test losses.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,7 +34,10 @@ ap.add_argument("--weights-out", help="write the `idx:value` line of Main.scala:
 ap.add_argument("--precision", choices=("fp32", "fp64"), default="fp32", help="fp64: the reference's Double arithmetic")
 ap.add_argument("--f64-rp-plans", action="store_true", help="fp64: refused plans run as row-parallel plans, under a communicator too: one plan run per epoch and rank (DSGD_F64_RP_PLANS=1)")
 ap.add_argument("--model", choices=("svm", "logistic"), default="svm", help="logistic: log-loss, probabilities, plain L2 (fp32, synchronous)")
+ap.add_argument("--lg-plans", action="store_true", help="logistic: Master.fit's flow on resident logistic plans (host.LogisticSync)")
 a = ap.parse_args()
+if a.lg_plans and a.model != "logistic":
+    ap.error("--lg-plans goes with --model logistic")
 if a.model == "logistic" and a.precision != "fp32":
     ap.error("--model logistic runs on the fp32 engine")
 if a.f64_rp_plans:
@@ -85,6 +91,17 @@ with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device, precision=a.precisi
         if a.precision == "fp64" and cfg.async_ and not rp_plans and getattr(data, "val64", None) is not None else "")
     if a.model == "logistic":   # (its own loop; dimSparsity plays no part)
         eng.set_weights(np.zeros(data.dim + 1, dtype=np.float32))
+        if a.lg_plans:
+            master = host.LogisticSync(eng, n_train, data.n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log, metrics=metrics)
+            log("initial loss: {}", master.local_loss())
+            log("initial accuracy: {}", master.local_accuracy())
+            t0 = time.time()
+            state = master.fit(np.zeros(data.dim + 1, dtype=np.float32), cfg.max_epochs, cfg.batch_size, cfg.learning_rate,
+                               host.EarlyStopping.no_improvement(cfg.patience, cfg.conv_delta, None))
+            log("fit ({}s, {} epochs, {} of them on device-drawn lists)", round(time.time() - t0, 3), state.updates, master.device_drawn_epochs)
+            log("final test loss: {}", master.local_loss(test=True))
+            log("final test accuracy: {}", master.local_accuracy(test=True))
+            sys.exit(0)
         fit_logistic(eng, cfg, n_train, data.n_rows)
         sys.exit(0)
     t0 = time.time()
