@@ -131,6 +131,7 @@ static bool available() {
 #include "dsgd_dense.hpp"
 #include "dsgd_fstep.hpp"
 #include "dsgd_tcol.hpp"
+#include "dsgd_lg_cols.hpp"   // (the logistic model's whole-split steps by column lists: coefficients, column-wise gradient)
 #include "dsgd_shuffle.hpp"
 #include "dsgd_cs64.hpp"   // (last: the fp64 mode)
 #include "dsgd_rp64.hpp"   // (... and its row-parallel gradient family, on float and on Double feature values)
@@ -535,6 +536,23 @@ struct dsgd_ctx {
   long long lg_pending_active = 0;         // rows of logistic plan runs since the last dsgd_synchronize (every row contributes)
   DevBuf<WorkSeg> d_lg_ssegs;
   DevBuf<float> d_lg_p;
+  // Its column lists (csrc/dsgd_lg_cols.hpp): whole-split steps as coefficients + column-wise gradient + finish.  Per (row
+  // ranges) configuration the device sorts the ranges' entries by (worker, column) once; at most eight configurations stay
+  // cached (the least recently used one makes room), all dropped by a load.
+  struct LgColsLayout {
+    std::vector<long long> ranges;   // row_begin, row_end per worker
+    long long gen = -1;              // layout_gen the ranked columns belong to
+    long long n_ent = 0;             // entries of the ranges' rows
+    int share = 0, n_wg = 0;         // entries per workgroup of the gradient kernel, its workgroups (0: declined for good)
+    DevBuf<uint2> d_ent;             // [n_wg * share] {x, position | first-of-column flag}
+    DevBuf<TcShare> d_shares;
+    DevBuf<int> d_slot_of_cid;       // compact id of a (worker, column) -> its word of d_lg_acc
+    DevBuf<int> d_pos_base;          // [workers] where each worker's rows start in d_cq
+    DevBuf<double> d_cq;             // the coefficients of the last step over these ranges, one per row
+    unsigned long long used = 0;
+  };
+  std::vector<LgColsLayout> lgc_cache;
+  unsigned long long lgc_clock = 0;
   unsigned long long bind_count = 0;
   unsigned long long lg_nsq_stamp = ~0ull - 1;
 };
@@ -2799,6 +2817,7 @@ static int load_csr_impl(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in,
   ++c->load_gen;
   c->bound_segs.clear();
   c->tcol_gate.reset();   // (the column lists' misses were about the old rows' ranges)
+  c->lgc_cache.clear();   // (the logistic column lists hold the old rows' entries; the stream is idle: synchronised above)
   c->last_grad_kernel = "";  // (dsgd_grad_kernel_name / dsgd_tuning_info report launches over THIS data: calls that record none --
   c->last_shift = FIX_SHIFT; //  the row-parallel fp64 requests -- would go on reporting the old data's)
   // (the wave tiles cover the hot stream and are built with the layout, at the first compute call)

@@ -54,6 +54,30 @@ static int lg_ensure(dsgd_ctx* c, int n_workers) {
   return DSGD_OK;
 }
 
+// the finish behind a gradient launch of either form (row-wise or by column lists): one column per lane
+static int lg_launch_finish(dsgd_ctx* c, int K, int mode, float lr, const WorkSeg* segs) {
+  const dim3 th(LG_THREADS);
+  LgFinishArgs f;
+  f.acc = c->d_lg_acc;
+  f.acc_stride = c->lg_stride;
+  f.segs = segs;
+  f.K = K;
+  f.dp = c->dp;
+  f.vexp = c->vexp;
+  f.perm = c->d_perm;
+  f.g_out = c->d_lg_g;
+  f.w = c->d_w;
+  f.lr = (double)lr;
+  f.lambda = c->cfg.lambda;
+  f.nsq_part = c->d_lg_part;
+  const dim3 fg((unsigned)lg_finish_blocks(c->dp));
+  if (mode == LG_STEP)
+    hipLaunchKernelGGL(dsgd_lg_finish_kernel<LG_STEP>, fg, th, 0, c->stream, f);
+  else
+    hipLaunchKernelGGL(dsgd_lg_finish_kernel<LG_GRADIENT>, fg, th, 0, c->stream, f);
+  HIP_TRY(hipGetLastError());
+  return DSGD_OK;
+}
 // The two launches of one worker's gradient (LG_GRADIENT) or of a step (LG_STEP) over K lists of positions in `idx` (list) or
 // K row ranges (segs hold the rows), the longest of `longest` rows.  lg_ensure came first.
 static int lg_launch(dsgd_ctx* c, bool list, int K, long long longest, int mode, float lr, const int* idx, const WorkSeg* segs) {
@@ -77,27 +101,8 @@ static int lg_launch(dsgd_ctx* c, bool list, int K, long long longest, int mode,
   else
     hipLaunchKernelGGL(dsgd_lg_grad_range_kernel, gg, th, 0, c->stream, m, a);
   HIP_TRY(hipGetLastError());
-  LgFinishArgs f;
-  f.acc = a.acc;
-  f.acc_stride = a.acc_stride;
-  f.segs = segs;
-  f.K = K;
-  f.dp = c->dp;
-  f.vexp = c->vexp;
-  f.perm = c->d_perm;
-  f.g_out = c->d_lg_g;
-  f.w = c->d_w;
-  f.lr = (double)lr;
-  f.lambda = c->cfg.lambda;
-  f.nsq_part = c->d_lg_part;
-  const dim3 fg((unsigned)lg_finish_blocks(c->dp));
-  if (mode == LG_STEP)
-    hipLaunchKernelGGL(dsgd_lg_finish_kernel<LG_STEP>, fg, th, 0, c->stream, f);
-  else
-    hipLaunchKernelGGL(dsgd_lg_finish_kernel<LG_GRADIENT>, fg, th, 0, c->stream, f);
-  HIP_TRY(hipGetLastError());
   c->last_grad_kernel = list ? "dsgd_lg_grad_kernel" : "dsgd_lg_grad_range_kernel";
-  return DSGD_OK;
+  return lg_launch_finish(c, K, mode, lr, segs);
 }
 // behind a step's launches: the weights moved (the SVM's s and |w|^2 are stale), |w|^2 of the new ones is in d_lg_part; the
 // one synchronisation; every row contributes
@@ -236,6 +241,160 @@ int dsgd_lg_sync_step_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_
   }
   DSGD_TRY(upload_segs(c, segs));
   DSGD_TRY(lg_launch(c, false, n_workers, v.longest, LG_STEP, lr, nullptr, c->d_segs));
+  return lg_step_done(c, stats, v.total);
+}
+
+// ---- whole-split steps by column lists (csrc/dsgd_lg_cols.hpp; the sizes: csrc/dsgd_lg_cols_host.hpp) ----
+// The layout of these ranges (c->d_segs holds them; the stream may be busy): DSGD_OK with *out, or 1 = none to be had -- too
+// many entries or positions (remembered for the configuration), or no memory (this call only): the caller's row form.
+static int lgc_layout(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int K, long long longest, dsgd_ctx::LgColsLayout** out) {
+  std::vector<long long> key;
+  long long n_ent = 0;
+  for (int k = 0; k < K; ++k) {
+    key.push_back(row_begin[k]);
+    key.push_back(row_end[k]);
+    n_ent += c->h_row_ptr[(size_t)row_end[k]] - c->h_row_ptr[(size_t)row_begin[k]];
+  }
+  for (dsgd_ctx::LgColsLayout& L : c->lgc_cache)
+    if (L.gen == c->layout_gen && L.ranges == key) {
+      L.used = ++c->lgc_clock;
+      if (L.n_wg == 0) return 1;   // (declined before: not tried again step after step)
+      *out = &L;
+      return DSGD_OK;
+    }
+  for (size_t i = 0; i < c->lgc_cache.size();)   // layouts of an earlier ranking
+    if (c->lgc_cache[i].gen != c->layout_gen) {
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      c->lgc_cache.erase(c->lgc_cache.begin() + (long)i);
+    } else {
+      ++i;
+    }
+  if (c->lgc_cache.size() >= 8) {   // the least recently used configuration makes room
+    size_t v = 0;
+    for (size_t i = 1; i < c->lgc_cache.size(); ++i)
+      if (c->lgc_cache[i].used < c->lgc_cache[v].used) v = i;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->lgc_cache.erase(c->lgc_cache.begin() + (long)v);
+  }
+  dsgd_ctx::LgColsLayout L;
+  L.ranges = key;
+  L.gen = c->layout_gen;
+  LgcPlan plan;
+  std::vector<long long> base((size_t)K);
+  if (lgc_plan(row_begin, row_end, K, n_ent, c->dp, c->lg_stride, c->n_cu, &plan, base.data()) != LGC_OK) {
+    L.used = ++c->lgc_clock;   // remembered as declined (n_wg = 0)
+    c->lgc_cache.push_back(std::move(L));
+    return 1;
+  }
+  const int n_keys = K * c->dp;
+  DevBuf<unsigned int> d_cnt, d_ptr, d_cursor;   // (the builder's scratch: released on return, the stream idle by then)
+  DevBuf<int> d_cid;
+  DevBuf<unsigned long long> d_tot;
+  auto give_up = [&]() {   // no memory or a failed call: declined for THIS call only
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(c->stream);
+    return 1;
+  };
+#define LGC_SOFT(expr) \
+  do {                 \
+    if ((expr) != hipSuccess) return give_up(); \
+  } while (0)
+  std::vector<int> pos_base(base.begin(), base.end());   // (below 2^31: lgc_plan)
+  LGC_SOFT(d_cnt.try_alloc((size_t)n_keys));
+  LGC_SOFT(d_ptr.try_alloc((size_t)n_keys + 1));
+  LGC_SOFT(d_cursor.try_alloc((size_t)n_keys));
+  LGC_SOFT(d_cid.try_alloc((size_t)n_keys));
+  LGC_SOFT(d_tot.try_alloc(2));
+  LGC_SOFT(L.d_pos_base.try_alloc((size_t)K));
+  LGC_SOFT(L.d_cq.try_alloc((size_t)plan.positions));
+  LGC_SOFT(L.d_ent.try_alloc((size_t)plan.n_pad));
+  LGC_SOFT(L.d_shares.try_alloc((size_t)plan.n_shares));
+  LGC_SOFT(hipMemcpyAsync(L.d_pos_base, pos_base.data(), sizeof(int) * (size_t)K, hipMemcpyHostToDevice, c->stream));
+  LGC_SOFT(hipMemsetAsync(d_cnt, 0, sizeof(unsigned int) * (size_t)n_keys, c->stream));
+  LGC_SOFT(hipMemsetAsync(L.d_ent + (plan.n_pad - plan.share), 0, sizeof(uint2) * (size_t)plan.share, c->stream));   // the last share's padding
+  const dim3 grid = tcol_row_grid(longest, K);
+  hipLaunchKernelGGL(dsgd_tc_count_kernel, grid, dim3(TC_THREADS), 0, c->stream, view(c), c->d_segs, c->dp, d_cnt);
+  hipLaunchKernelGGL(dsgd_tc_scan_kernel, dim3(1), dim3(TC_THREADS), 0, c->stream, d_cnt, n_keys, d_ptr, d_cursor, d_cid, d_tot);
+  LGC_SOFT(hipGetLastError());
+  unsigned long long tot[2] = {0, 0};
+  LGC_SOFT(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+  LGC_SOFT(hipStreamSynchronize(c->stream));   // (also: pos_base is a local)
+  if (tot[0] != (unsigned long long)n_ent) {
+    (void)hipStreamSynchronize(c->stream);
+    return fail(DSGD_ESTATE, "logistic column lists: the device counted %llu entries in the ranges, the host %lld", tot[0], n_ent);
+  }
+  L.n_ent = n_ent;
+  L.share = plan.share;
+  LGC_SOFT(L.d_slot_of_cid.try_alloc((size_t)std::max<unsigned long long>(1, tot[1])));
+  hipLaunchKernelGGL(dsgd_tc_shares_kernel, dim3((unsigned)((plan.n_shares + 255) / 256)), dim3(256), 0, c->stream, d_ptr, d_cid, n_keys, L.n_ent,
+                     L.share, (int)plan.n_shares, L.d_shares);
+  hipLaunchKernelGGL(dsgd_lgc_fill_kernel, grid, dim3(TC_THREADS), 0, c->stream, view(c), c->d_segs, c->dp, d_ptr.get(), d_cursor.get(), d_cid.get(),
+                     L.d_pos_base.get(), c->lg_stride, L.d_ent.get(), L.d_slot_of_cid.get());
+  LGC_SOFT(hipGetLastError());
+  LGC_SOFT(hipStreamSynchronize(c->stream));
+#undef LGC_SOFT
+  L.n_wg = (int)plan.n_shares;
+  L.used = ++c->lgc_clock;
+  c->lgc_cache.push_back(std::move(L));
+  *out = &c->lgc_cache.back();
+  return DSGD_OK;
+}
+// the three launches of one step over the ranges in c->d_segs, by their layout
+static int lgc_launch(dsgd_ctx* c, const dsgd_ctx::LgColsLayout& L, int K, long long longest, float lr) {
+  LgcCoefArgs q;
+  q.w = c->d_w;
+  q.vexp = c->vexp;
+  q.K = K;
+  q.segs = c->d_segs;
+  q.pos_base = L.d_pos_base;
+  q.blocks_per_worker = lg_blocks_per_worker(longest, K, c->n_cu, 8);   // (no LDS: the 2,048 lanes a compute unit holds)
+  q.cq = L.d_cq;
+  q.sc = c->d_sc;
+  hipLaunchKernelGGL(dsgd_lg_coef_kernel, dim3((unsigned)(q.blocks_per_worker * K)), dim3(LG_THREADS), 0, c->stream, view(c), q);
+  HIP_TRY(hipGetLastError());
+  LgcGradArgs g;
+  g.ent = L.d_ent;
+  g.shares = L.d_shares;
+  g.slot_of_cid = L.d_slot_of_cid;
+  g.cq = L.d_cq;
+  g.acc = c->d_lg_acc;
+  g.n_ent = L.n_ent;
+  g.share = L.share;
+  hipLaunchKernelGGL(dsgd_lg_cgrad_kernel, dim3((unsigned)L.n_wg), dim3(LGC_THREADS), 0, c->stream, g);
+  HIP_TRY(hipGetLastError());
+  c->last_grad_kernel = "dsgd_lg_cgrad_kernel";
+  return lg_launch_finish(c, K, LG_STEP, lr, c->d_segs);
+}
+
+int dsgd_lg_sync_steps_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, int64_t n_steps, float lr,
+                              dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  if (n_workers < 1 || !row_begin || !row_end) return fail(DSGD_EINVAL, "dsgd_lg_sync_steps_ranges: Cannot sum an empty list of vectors (no workers)");
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, "dsgd_lg_sync_steps_ranges", &fresh));
+  const LgCheck v = lg_check_ranges(row_begin, row_end, n_workers, c->n_rows);
+  DSGD_TRY(lg_report(c, "dsgd_lg_sync_steps_ranges", v, n_workers));
+  if (n_steps < 1) return lg_report(c, "dsgd_lg_sync_steps_ranges", lg_fault(LG_NO_WORKERS, -1, -1, n_steps), n_workers);
+  DSGD_TRY(prepare_layout(c));
+  DSGD_TRY(lg_ensure(c, n_workers));
+  DSGD_TRY(reset_counters(c));
+  std::vector<WorkSeg> segs((size_t)n_workers);
+  for (int k = 0; k < n_workers; ++k) {
+    segs[(size_t)k].begin = row_begin[k];
+    segs[(size_t)k].end = row_end[k];
+  }
+  DSGD_TRY(upload_segs(c, segs));
+  dsgd_ctx::LgColsLayout* L = nullptr;
+  const int lrc = lgc_layout(c, row_begin, row_end, n_workers, v.longest, &L);
+  if (lrc != DSGD_OK && lrc != 1) return lrc;
+  c->s_dirty = true;   // (from the first launch on the weights move)
+  c->lg_nsq_stamp = ~0ull - 1;
+  // three launches per step (no layout: the row form's two), back to back on the stream: no host synchronisation in between
+  for (int64_t t = 0; t < n_steps; ++t) {
+    if (L) DSGD_TRY(lgc_launch(c, *L, n_workers, v.longest, lr));
+    else DSGD_TRY(lg_launch(c, false, n_workers, v.longest, LG_STEP, lr, nullptr, c->d_segs));
+  }
   return lg_step_done(c, stats, v.total);
 }
 

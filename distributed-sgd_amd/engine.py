@@ -7,6 +7,7 @@ Dense vectors are numpy float32 arrays of D+1 slots indexed by key (see include/
 from __future__ import annotations
 
 import ctypes as C
+import operator
 
 import numpy as np
 
@@ -400,6 +401,27 @@ class Engine:
         re_ = (C.c_int64 * max(k, 1))(*[int(r[1]) for r in ranges])
         st = BatchStats()
         check(self._lib.dsgd_lg_sync_step_ranges(self._ctx, rb, re_, C.c_int32(k), C.c_float(lr), C.byref(st)))
+        return {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def lg_sync_steps_ranges(self, ranges, n_steps, lr):
+        """n_steps steps of lg_sync_step_ranges over the SAME ranges in ONE call (dsgd_lg_sync_steps_ranges): the ranges' entries
+        are laid out by column once per ranges configuration, then every step is three launches with no atomic per non-zero.
+        The weights and the stats (the rows of one step) get the bits of the loop of lg_sync_step_ranges calls."""
+        pairs = []
+        for r in ranges:
+            if len(r) != 2:
+                raise ValueError("a range is a (begin, end) pair, not %r" % (r,))
+            pairs.append((operator.index(r[0]), operator.index(r[1])))
+        if not pairs:
+            raise ValueError("no ranges")
+        n_steps = operator.index(n_steps)
+        if n_steps < 1:
+            raise ValueError("n_steps must be at least 1, not %d" % n_steps)
+        k = len(pairs)
+        rb = (C.c_int64 * k)(*[a for a, _ in pairs])
+        re_ = (C.c_int64 * k)(*[b for _, b in pairs])
+        st = BatchStats()
+        check(self._lib.dsgd_lg_sync_steps_ranges(self._ctx, rb, re_, C.c_int32(k), C.c_int64(n_steps), C.c_float(lr), C.byref(st)))
         return {"n_samples": st.n_samples, "n_active": st.n_active}
 
     def lg_sync_steps(self, idx, offsets, n_steps, n_workers, lr):

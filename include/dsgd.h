@@ -934,6 +934,17 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  * bits of dsgd_lg_loss_acc on range r alone: every range has its own workgroups, the grid of a launch of its own.
  * DSGD_EINVAL: more than 16 ranges, none, an empty or reversed range; DSGD_ERANGE: a range that leaves the rows.
  *
+ * WHOLE-SPLIT STEPS BY COLUMN LISTS.  dsgd_lg_sync_steps_ranges runs n_steps steps over the SAME K row ranges in one call: the
+ * weights, the |w'|^2 words and the statistics (n_samples = n_active = the rows of ONE step) are the bits of n_steps calls of
+ * dsgd_lg_sync_step_ranges.  The first call over a ranges configuration lays the ranges' entries out by (worker, column) on
+ * the device (8 bytes per entry; at most eight configurations stay cached per context, the least recently used one makes
+ * room, a dsgd_load_csr drops them all); a step is then three launches -- a coefficient per row, the gradient column by
+ * column without an atomic per non-zero, the finish of every logistic step -- with no host synchronisation between steps
+ * and one at the end.  The sums are the same 64-bit integers, so nothing depends on which form ran.  Where no layout can be
+ * had (2^31 entries or more, 2^31 rows or more in the ranges together, no memory) the steps run as dsgd_lg_sync_step_ranges'
+ * do and the call still succeeds; dsgd_grad_kernel_name says "dsgd_lg_cgrad_kernel" or "dsgd_lg_grad_range_kernel".
+ * Refusals: those of dsgd_lg_sync_step_ranges with its codes, and n_steps < 1 (DSGD_EINVAL).  No other call takes this path.
+ *
  * LIMITS (out of scope, each refused or simply absent): no JNI / Scala binding; the host mirror is host.LogisticSync
  * (Master.fit's flow on one context: no distributed or sampled evaluation, no asynchronous fit; host.MasterSync /
  * MasterAsync stay the SVM's); no fused or persistent one-launch step; no column slices; no asynchronous engine; no fp64
@@ -952,6 +963,8 @@ int dsgd_lg_sync_step(dsgd_ctx* ctx, const int32_t* const* idx_per_worker, const
                       dsgd_batch_stats* stats);
 int dsgd_lg_sync_step_ranges(dsgd_ctx* ctx, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, float lr,
                              dsgd_batch_stats* stats);
+int dsgd_lg_sync_steps_ranges(dsgd_ctx* ctx, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, int64_t n_steps, float lr,
+                              dsgd_batch_stats* stats);
 int dsgd_lg_sync_steps(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const int64_t* offsets /* n_steps * n_workers + 1 */, int64_t n_steps,
                        int32_t n_workers, float lr, dsgd_batch_stats* stats);
 int dsgd_lg_loss_acc(dsgd_ctx* ctx, const float* w /* NULL = resident */, int64_t row_begin, int64_t row_end, double* loss, double* acc);
