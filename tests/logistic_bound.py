@@ -153,15 +153,34 @@ def emu_dots(csr, w32, rows):
     return {int(r): emu_dot(row_ptr, col, val, w32, int(r)) for r in np.unique(np.asarray(rows, dtype=np.int64))}
 
 
-def emu_acc(csr, w32, idx, mut=None, n_for_shift=None):
-    """One worker's int64 column sums (python ints: exact) and its shift.  mut: a mutation's name (tests only)."""
+def ranks_of(csr, dp):
+    """The library's column ranking: the count over ALL loaded rows descending, ties by ascending key -> rank of every key."""
+    _, col, _, _ = _csr(csr)
+    order = np.argsort(-np.bincount(col, minlength=dp), kind="stable")
+    rank = np.empty(dp, dtype=np.int64)
+    rank[order] = np.arange(dp)
+    return rank
+
+
+ACC_MUTATIONS = ("drop_last", "label_by_position", "flip_sign", "vexp_qscale", "fold_2048")
+
+
+def emu_acc(csr, w32, idx, mut=None, n_for_shift=None, d=None):
+    """One worker's int64 column sums (python ints: exact) and its shift.  mut: a mutation's name (tests only).  d: the dots
+    of emu_dots for (at least) the listed rows, where the caller has them already."""
     row_ptr, col, val, label = _csr(csr)
     idx = np.asarray(idx, dtype=np.int64)
     S = shift(len(idx) if n_for_shift is None else n_for_shift)
     if mut == "drop_last":
         idx = idx[:-1]
-    qscale = 2.0 ** (S - vexp_of(val))
-    d = emu_dots(csr, w32, idx)
+    # vexp_qscale: vexp one too large where the entries are scaled ONLY (the finish keeps the right one)
+    qscale = 2.0 ** (S - vexp_of(val) - (1 if mut == "vexp_qscale" else 0))
+    if d is None:
+        d = emu_dots(csr, w32, idx)
+    at = col
+    if mut == "fold_2048" and len(w32) > 2048:   # the first rank beyond the LDS head lands on the head's last word
+        rank = ranks_of(csr, len(w32))
+        at = np.where(rank[col] == 2048, int(np.where(rank == 2047)[0][0]), col)
     acc = np.zeros(len(w32), dtype=np.int64)
     for t, r in enumerate(idx):
         y = float(label[t % len(label)] if mut == "label_by_position" else label[r])
@@ -171,19 +190,27 @@ def emu_acc(csr, w32, idx, mut=None, n_for_shift=None):
             c = -c
         st, en = int(row_ptr[r]), int(row_ptr[r + 1])
         q = np.rint(val[st:en].astype(np.float64) * (c * qscale)).astype(np.int64)
-        np.add.at(acc, col[st:en], q)
+        np.add.at(acc, at[st:en], q)
     return acc, S
 
 
-def emu_gradient(csr, w32, idx, lam, mut=None):
+def _finish_vexp(val, mut):
+    """vexp_finish: vexp one too large in the finish ONLY"""
+    return vexp_of(val) + (1 if mut == "vexp_finish" else 0)
+
+
+def emu_gradient(csr, w32, idx, lam, mut=None, d=None):
     _, _, val, _ = _csr(csr)
     w32 = np.asarray(w32, dtype=np.float32)
-    acc, S = emu_acc(csr, w32, idx, mut)
-    Gk = acc.astype(np.float64) * 2.0 ** (vexp_of(val) - S)
-    return (Gk + (2.0 * lam) * w32.astype(np.float64)).astype(np.float32)
+    acc, S = emu_acc(csr, w32, idx, mut if mut in ACC_MUTATIONS else None, d=d)
+    Gk = acc.astype(np.float64) * 2.0 ** (_finish_vexp(val, mut) - S)
+    g = (Gk + (2.0 * lam) * w32.astype(np.float64)).astype(np.float32)
+    if mut == "skip_last_column":   # the gradient goes out in KEY order: key dp - 1 keeps the zero of the output buffer
+        g[-1] = 0.0
+    return g
 
 
-def emu_step(csr, w32, lists, lr, lam, mut=None):
+def emu_step(csr, w32, lists, lr, lam, mut=None, d=None):
     _, _, val, _ = _csr(csr)
     w32 = np.asarray(w32, dtype=np.float32)
     wj = w32.astype(np.float64)
@@ -191,13 +218,17 @@ def emu_step(csr, w32, lists, lr, lam, mut=None):
     total = np.zeros_like(wj)
     for k, idx in enumerate(lists):
         wrong_n = len(lists[(k + 1) % len(lists)]) if mut == "wrong_worker_shift" else None
-        acc, S = emu_acc(csr, w32, idx, mut if mut in ("drop_last", "label_by_position", "flip_sign") else None)
+        acc, S = emu_acc(csr, w32, idx, mut if mut in ACC_MUTATIONS else None, d=d)
         if wrong_n is not None:
             S = shift(wrong_n)   # (the finish reads another worker's length)
-        Gk = acc.astype(np.float64) * 2.0 ** (vexp_of(val) - S)
+        Gk = acc.astype(np.float64) * 2.0 ** (_finish_vexp(val, mut) - S)
         if mut == "support_only_reg":
             total = total + (Gk + np.where(acc != 0, reg, 0.0))
         else:
             total = total + (Gk + reg)
     mean = total if mut == "no_mean" else total / float(len(lists))
-    return (wj - float(np.float32(lr)) * mean).astype(np.float32)
+    wn = (wj - float(np.float32(lr)) * mean).astype(np.float32)
+    if mut == "skip_last_column":   # a step walks the columns in RANK order: the column of rank dp - 1 keeps its weight
+        last = int(np.where(ranks_of(csr, len(w32)) == len(w32) - 1)[0][0])
+        wn[last] = w32[last]
+    return wn

@@ -97,13 +97,15 @@ def share_of(n_ent, n_cu):
 def test_every_round_count_of_a_share():
     """The 4,096-row sets stay at the smallest share (256 entries: ONE round of 64 per wave).  At the MI355X's 256 compute
     units a wave walks 2 rounds from 524,289 entries on and 8 from 3,670,017 on, so 50,000 rows it is: 12,000 of them as one
-    range (2 rounds), two uneven workers (7) and the whole set (8, the largest share)."""
+    range (2 rounds), 17,000, 24,000, 31,000 and 38,000 (3, 4, 5 and 6: the loop is unrolled to LGC_NU = 8 with `u < rounds`
+    guards, every count between takes its own way through them), two uneven workers (7) and the whole set (8, the largest
+    share)."""
     import hard_data as hd
 
     d = dsgd_amd.synth.generate(50000, seed=5)
     csr = (d.row_ptr, d.col, d.val, d.label)
-    cases_ = ([(0, 12000)], [(0, 20000), (20000, 45000)], [(0, 50000)])
-    assert [share_of(sum(int(d.row_ptr[b] - d.row_ptr[a]) for a, b in r), hd.N_CU) // 256 for r in cases_] == [2, 7, 8]
+    cases_ = ([(0, 12000)], [(0, 17000)], [(0, 24000)], [(0, 31000)], [(0, 38000)], [(0, 20000), (20000, 45000)], [(0, 50000)])
+    assert [share_of(sum(int(d.row_ptr[b] - d.row_ptr[a]) for a, b in r), hd.N_CU) // 256 for r in cases_] == [2, 3, 4, 5, 6, 7, 8]
     with engine_of(csr, d.dim, cases.LAM) as cols, engine_of(csr, d.dim, cases.LAM) as rows:
         for ranges in cases_:
             step_both(cols, rows, ranges, 2, 2.0 ** -10, cases.weights(1.0))
