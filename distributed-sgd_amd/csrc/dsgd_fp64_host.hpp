@@ -656,10 +656,7 @@ int dsgd_sync_steps_f64(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const in
   DSGD_TRY(reset_counters(c));
   // ONE upload: the index array and the list ranges of every step
   DSGD_TRY(ensure_idx(c, n_idx));
-  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int) * (size_t)n_idx));
-  memcpy(c->pin_idx.p, idx, sizeof(int) * (size_t)n_idx);
-  HIP_TRY(hipMemcpyAsync(c->d_idx, c->pin_idx.p, sizeof(int) * (size_t)n_idx, hipMemcpyHostToDevice, c->stream));
-  DSGD_TRY(pin_sent(c, c->pin_idx));
+  DSGD_TRY(send_idx(c, idx, n_idx));
   c->cur_idx = c->d_idx;
   DSGD_TRY(pin_acquire(c->pin_segs, sizeof(WorkSeg) * (size_t)n_lists));
   {

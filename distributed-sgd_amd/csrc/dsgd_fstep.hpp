@@ -7,7 +7,7 @@
 // What makes one launch possible WITHOUT a grid-wide wait: the only things that cross the three passes are per ROW --
 // the cold part of x.w (dcold) into the gate, the gate's coefficient (coef8) into the cold gradient.  So workgroup b owns
 // a CHUNK of consecutive rows, with wave tiles of both streams cut at the chunk's boundaries (the host lays these tiles
-// out per (ranges, grid) configuration: dsgd_hip.hip, fstep_layout), and walks its chunk three times:
+// out per (ranges, grid) configuration: csrc/dsgd_fstep_host.hpp, fstep_layout), and walks its chunk three times:
 //
 //   phase A   cold weights -> LDS; the chunk's cold tiles: dcold[row]                              (cd_tile)
 //   phase B   hot weights -> LDS, hot gradient words cleared; the chunk's hot tiles: x.w, gate, coef8[row], hot
@@ -162,9 +162,9 @@ __global__ void __launch_bounds__(1024) dsgd_fstep_kernel(CsrView m, CsrView mfu
     // profiles/r06_fstep_wg_times.txt).  Now a wave with a long row does it FIRST, from registers (w_long_row_regs: four
     // round trips in a row -- row id, bounds, stream, cold weights -- instead of two dozen; ~10 us of the wave's time all
     // the same: a round trip through this kernel's own queues is 2-3 us), requests its first tiles behind it, and draws
-    // fewer tiles than the others; the chunks are cut with that cost in their weight (dsgd_hip.hip: fstep_layout).
+    // fewer tiles than the others; the chunks are cut with that cost in their weight (csrc/dsgd_fstep_host.hpp: fstep_layout).
     // Which wave adds a tile's rows to the workgroup's integer accumulators does not change any sum: the same bits.
-    int* const tile_ctr = x.gl + hw + 64;   // (the four words LDS had left: dsgd_hip.hip launch_fstep)
+    int* const tile_ctr = x.gl + hw + 64;   // (the four words LDS had left: csrc/dsgd_fstep_host.hpp launch_fstep)
     unsigned int n_all = 0, n_neg = 0, n_pos = 0;
     const int t_end = ch.tile_end;
     int qa = ch.tile_begin + wave, qb = qa + stride, qc = qb + stride, qd = qc + stride;

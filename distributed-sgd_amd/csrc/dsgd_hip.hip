@@ -120,6 +120,7 @@ static bool available() {
   } while (0)
 
 #include "dsgd_buf.hpp"      // (host only: the owners of device and pinned memory)
+#include "dsgd_layout_cache.hpp"   // (host only: the few device layouts a gradient family keeps per row-range configuration)
 #include "dsgd_plan_cache.hpp"   // (host only: the device blocks plans take and hand back, and a plan's hold on one)
 #include "dsgd_plan_check.hpp"   // (host only: a plan's lists against the rows loaded now)
 #include "dsgd_layout_host.hpp"  // (host only: the arithmetic behind every table the gradient kernels read)
@@ -314,7 +315,6 @@ struct dsgd_ctx {
   // streams that end at the chunk boundaries; a few configurations stay cached (a fit alternates train steps only; the
   // tests and the bench's legs bring their own).
   struct FstepLayout {
-    std::vector<long long> ranges;   // row_begin, row_end per worker
     int n_wg = 0;                    // workgroups (chunks) per worker
     DevBuf<WTile> d_tiles;
     DevBuf<unsigned short> d_meta;
@@ -323,7 +323,6 @@ struct dsgd_ctx {
     DevBuf<FChunk> d_chunks;
     long long worst_rows = 1;        // rows of the largest chunk
     int shift = -1;                  // the measured fixed-point shift of the hot accumulators (-1: not measured yet)
-    unsigned long long used = 0;
     // measured balance (round 6): the workgroups' own durations, summed by the kernel over `launches` launches, re-cut the
     // chunks once or twice per configuration (a chunk's share of the weight follows its workgroup's measured rate)
     DevBuf<unsigned long long> d_times;
@@ -333,15 +332,12 @@ struct dsgd_ctx {
     int launches = 0, rebalances = 0;
     bool times_pending = false;
   };
-  std::vector<FstepLayout> fstep_cache;
-  unsigned long long fstep_clock = 0;
+  LayoutCache<FstepLayout> fstep_cache;   // (keyed by the ranges and n_wg)
   int last_fstep_rebalances = 0;     // how often the configuration of the last chunked launch has been re-cut (dsgd_tuning_info)
   // Column lists (csrc/dsgd_tcol.hpp): whole-split steps of 10^3 .. 10^5 rows as dot + column-wise gradient + reduce, no
   // partials.  Per (row ranges) configuration the device sorts the ranges' entries by (worker, column) once; a few
   // configurations stay cached.
   struct TcolLayout {
-    std::vector<long long> ranges;   // row_begin, row_end per worker
-    long long gen = -1;              // layout_gen the ranked columns belong to
     long long n_ent = 0;             // entries of the ranges' rows
     int share = 0, n_wg = 0;         // entries per workgroup of the gradient kernel, its workgroups
     int bm_words = 0;                // words of the step's bitmap (every worker's range padded to 64 rows; a multiple of 4)
@@ -351,10 +347,8 @@ struct dsgd_ctx {
     DevBuf<int> d_key_of_cid;
     DevBuf<int> d_bit_base;       // [workers]
     DevBuf<unsigned int> d_bitmap;   // the gate's decisions of the last step over these ranges
-    unsigned long long used = 0;
   };
-  std::vector<TcolLayout> tcol_cache;
-  unsigned long long tcol_clock = 0;
+  LayoutCache<TcolLayout> tcol_cache;
   TcolGate tcol_gate;                // their back-off from callers that never repeat a configuration
   bool fused_apply_pending = false;
   FusedArgs fused_args{};
@@ -540,19 +534,15 @@ struct dsgd_ctx {
   // ranges) configuration the device sorts the ranges' entries by (worker, column) once; at most eight configurations stay
   // cached (the least recently used one makes room), all dropped by a load.
   struct LgColsLayout {
-    std::vector<long long> ranges;   // row_begin, row_end per worker
-    long long gen = -1;              // layout_gen the ranked columns belong to
     long long n_ent = 0;             // entries of the ranges' rows
-    int share = 0, n_wg = 0;         // entries per workgroup of the gradient kernel, its workgroups (0: declined for good)
+    int share = 0, n_wg = 0;         // entries per workgroup of the gradient kernel, its workgroups
     DevBuf<uint2> d_ent;             // [n_wg * share] {x, position | first-of-column flag}
     DevBuf<TcShare> d_shares;
     DevBuf<int> d_slot_of_cid;       // compact id of a (worker, column) -> its word of d_lg_acc
     DevBuf<int> d_pos_base;          // [workers] where each worker's rows start in d_cq
     DevBuf<double> d_cq;             // the coefficients of the last step over these ranges, one per row
-    unsigned long long used = 0;
   };
-  std::vector<LgColsLayout> lgc_cache;
-  unsigned long long lgc_clock = 0;
+  LayoutCache<LgColsLayout> lgc_cache;
   unsigned long long bind_count = 0;
   unsigned long long lg_nsq_stamp = ~0ull - 1;
 };
@@ -653,6 +643,13 @@ static int ensure_idx(dsgd_ctx* c, long long n) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   return c->d_idx.reserve((size_t)n, Grow::twice);
 }
+// one int list through pin_idx into d_idx (ensure_idx came first; the caller says where cur_idx points)
+static int send_idx(dsgd_ctx* c, const int32_t* idx, long long n) {
+  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int) * (size_t)n));
+  memcpy(c->pin_idx.p, idx, sizeof(int) * (size_t)n);
+  HIP_TRY(hipMemcpyAsync(c->d_idx, c->pin_idx.p, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  return pin_sent(c, c->pin_idx);
+}
 static int ensure_segs(dsgd_ctx* c, int n) {
   if ((size_t)n <= c->d_segs.cap()) return DSGD_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -672,6 +669,25 @@ static int upload_segs(dsgd_ctx* c, const std::vector<WorkSeg>& segs) {
   DSGD_TRY(pin_sent(c, c->pin_segs));
   c->segs_last = segs;
   return DSGD_OK;
+}
+
+// The cached layouts of the three gradient families (csrc/dsgd_layout_cache.hpp) go behind an idle launch stream: its
+// kernels may still read them.  layout_room: before a family builds another one.  layouts_drop_all: THE place where they go
+// when the rows or their ranking change (dsgd_load_csr, build_split), with the column lists' back-off, which counted misses
+// over what went; dsgd_destroy leaves them to the members' destructors, every stream idle.
+static auto stream_idle(dsgd_ctx* c) {
+  return [c] { return hipStreamSynchronize(c->stream) == hipSuccess; };
+}
+template <class L>
+static int layout_room(dsgd_ctx* c, LayoutCache<L>& cache) {
+  if (cache.make_room(c->layout_gen, stream_idle(c))) return DSGD_OK;
+  return fail(DSGD_EHIP, "hipStreamSynchronize(c->stream): %s", hipGetErrorString(hipGetLastError()));
+}
+static void layouts_drop_all(dsgd_ctx* c) {
+  c->fstep_cache.clear(stream_idle(c));
+  c->tcol_cache.clear(stream_idle(c));
+  c->lgc_cache.clear(stream_idle(c));
+  c->tcol_gate.reset();
 }
 
 // per-block partial sums of w.ds and |w|^2 (fra_scalars): one pair per FRA_COLS columns
@@ -1610,11 +1626,8 @@ static int upload_wave_tiles(dsgd_ctx* c, HostTiles& ht) {
 
 // split the ranked CSR into the hot stream (rank < hsplit) and the cold stream (rank - hsplit), both in row order with
 // wave tiles of whole rows; rows whose hot or cold part exceeds a wave tile stay on the long-row list and in neither.
-static void fstep_drop_all(dsgd_ctx* c);
-static void tcol_drop_all(dsgd_ctx* c);
 static int build_split(dsgd_ctx* c) {
-  fstep_drop_all(c);
-  tcol_drop_all(c);   // (the chunked tile tables index the streams built here; the column lists are sorted by the ranks about to change)
+  layouts_drop_all(c);   // (the chunked tile tables index the streams built here; the column lists are sorted by the ranks about to change)
   c->d_hcol.reset(), c->d_hval.reset(), c->d_hrow_ptr.reset();
   c->d_ccol.reset(), c->d_cval.reset(), c->d_ctp.reset(), c->d_ctiles.reset(), c->d_cmeta.reset();
   c->d_dcold.reset(), c->d_coef8.reset();
@@ -1942,342 +1955,8 @@ static int launch_stream(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs) {
   return DSGD_OK;
 }
 
-// ---- row chunks: the whole gradient of a row range in one launch (csrc/dsgd_fstep.hpp) -------------------------------
-static void fstep_drop_all(dsgd_ctx* c) {   // (the split streams are about to change, or the context goes away)
-  if (c->fstep_cache.empty()) return;
-  (void)hipStreamSynchronize(c->stream);
-  c->fstep_cache.clear();
-}
-static int fstep_build(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int n_wg, dsgd_ctx::FstepLayout& L);
-static int fstep_layout(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int n_wg, dsgd_ctx::FstepLayout** out) {
-  std::vector<long long> key;
-  for (const StreamSeg& sg : row_segs) {
-    key.push_back(sg.row_begin);
-    key.push_back(sg.row_end);
-  }
-  for (dsgd_ctx::FstepLayout& L : c->fstep_cache)
-    if (L.n_wg == n_wg && L.ranges == key) {
-      L.used = ++c->fstep_clock;
-      *out = &L;
-      return DSGD_OK;
-    }
-  if (c->fstep_cache.size() >= 8) {   // the least recently used configuration makes room
-    size_t v = 0;
-    for (size_t i = 1; i < c->fstep_cache.size(); ++i)
-      if (c->fstep_cache[i].used < c->fstep_cache[v].used) v = i;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->fstep_cache.erase(c->fstep_cache.begin() + (long)v);
-  }
-  dsgd_ctx::FstepLayout L;
-  L.ranges = key;
-  L.n_wg = n_wg;
-  DSGD_TRY(fstep_build(c, row_segs, n_wg, L));
-  L.used = ++c->fstep_clock;
-  c->fstep_cache.push_back(std::move(L));
-  *out = &c->fstep_cache.back();
-  return DSGD_OK;
-}
-// the tile tables and chunk records of a configuration (L.share: the chunks' shares of their worker's weight, or empty)
-static int fstep_build(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int n_wg, dsgd_ctx::FstepLayout& L) {
-  ChunkTables T;
-  cut_row_chunks(row_segs, n_wg, L.share, c->h_hrp, c->h_ctp, c->wlong_rows, c->wlong_weight, c->h_label.data(), T);
-  const std::vector<WTile>&wt = T.wt, &ct = T.ct;
-  const std::vector<unsigned short>&meta = T.meta, &cmeta = T.cmeta;
-  const std::vector<FChunk>& chunks = T.chunks;
-  L.worst_rows = T.worst_rows;
-  L.shift = -1;
-  // (alloc drops the tables of the cut before)
-  hipError_t e = L.d_tiles.try_alloc(wt.size());
-  if (e == hipSuccess) e = L.d_meta.try_alloc(meta.size());
-  if (e == hipSuccess) e = L.d_ctiles.try_alloc(ct.size());
-  if (e == hipSuccess) e = L.d_cmeta.try_alloc(cmeta.size());
-  if (e == hipSuccess) e = L.d_chunks.try_alloc(chunks.size());
-  if (e == hipSuccess) e = hipMemcpy(L.d_tiles, wt.data(), sizeof(WTile) * wt.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(L.d_meta, meta.data(), sizeof(unsigned short) * meta.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(L.d_ctiles, ct.data(), sizeof(WTile) * ct.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(L.d_cmeta, cmeta.data(), sizeof(unsigned short) * cmeta.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(L.d_chunks, chunks.data(), sizeof(FChunk) * chunks.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess && !L.d_times) {
-    e = L.d_times.try_alloc(chunks.size());
-    if (e == hipSuccess) e = L.h_times.try_alloc(chunks.size());
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&L.times_ev.e, hipEventDisableTiming);
-  }
-  if (e == hipSuccess) e = hipMemset(L.d_times, 0, sizeof(unsigned long long) * chunks.size());
-  L.launches = 0;
-  L.times_pending = false;
-  if (e != hipSuccess) {
-    L = dsgd_ctx::FstepLayout();
-    return fail(DSGD_EHIP, "row-chunk layout: %s", hipGetErrorString(e));
-  }
-  return DSGD_OK;
-}
-// Measured balance (opt-in, DSGD_FSTEP_REBALANCE=1): after FSTEP_CAL launches of a configuration the workgroups' summed durations come back (asynchronously);
-// a later launch that finds them cuts the chunks again -- chunk b's share of the weight times (mean time / its time),
-// within 15 % -- twice at most.  The slowest workgroup ends the launch: at N = 804,414 it ran 8 us behind the average of 75,
-// the same workgroups every time (profiles/r06_fstep_wg_times.txt).  Integer sums: the re-cut changes no bit.
-constexpr int FSTEP_CAL = 24;
-static int fstep_maybe_rebalance(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, dsgd_ctx::FstepLayout* L) {
-  if (!c->k.fstep_rebalance || L->rebalances >= 2 || !L->d_times || c->d_tprof) return DSGD_OK;
-  const size_t n = (size_t)L->n_wg * row_segs.size();
-  if (!L->times_pending) {
-    if (L->launches >= FSTEP_CAL) {
-      HIP_TRY(hipMemcpyAsync(L->h_times, L->d_times, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipEventRecord(L->times_ev, c->stream));
-      L->times_pending = true;
-    }
-    return DSGD_OK;
-  }
-  if (hipEventQuery(L->times_ev) != hipSuccess) {
-    (void)hipGetLastError();
-    return DSGD_OK;
-  }
-  // (the copy covered exactly the launches enqueued in front of it; launches since then run on the old cut and are dropped)
-  std::vector<double> share(n, 1.0);
-  const bool had = L->share.size() == n;
-  bool usable = true;
-  for (size_t k = 0; k < row_segs.size() && usable; ++k) {
-    double mean = 0.0;
-    for (int b = 0; b < L->n_wg; ++b) mean += (double)L->h_times[k * (size_t)L->n_wg + (size_t)b];
-    mean /= (double)L->n_wg;
-    if (!(mean > 0.0)) usable = false;
-    for (int b = 0; b < L->n_wg && usable; ++b) {
-      const size_t i = k * (size_t)L->n_wg + (size_t)b;
-      const double t = (double)L->h_times[i];
-      double f = t > 0.0 ? mean / t : 1.0;
-      f = std::min(1.15, std::max(0.85, f));
-      share[i] = (had ? L->share[i] : 1.0) * f;
-    }
-  }
-  L->times_pending = false;
-  ++L->rebalances;
-  if (!usable) return DSGD_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));   // (the tables in use go away)
-  L->share = share;
-  return fstep_build(c, row_segs, L->n_wg, *L);
-}
-
-static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int n_wg) {
-  const int n_workers = (int)row_segs.size();
-  dsgd_ctx::FstepLayout* L = nullptr;
-  DSGD_TRY(fstep_layout(c, row_segs, n_wg, &L));
-  DSGD_TRY(fstep_maybe_rebalance(c, row_segs, L));
-  ++L->launches;
-  c->last_fstep_rebalances = L->rebalances;
-  const int H = std::min(c->hsplit, c->dp);
-  const int nc = c->dp - H;   // (fstep_possible: all of them inside the LDS tile)
-  dim3 grid((unsigned)n_wg, (unsigned)n_workers);
-  DSGD_TRY(ensure_part(c, c->d_part, &c->part_wgs, &c->part_stride, (long long)n_wg * n_workers, H));
-  DSGD_TRY(ensure_part(c, c->d_partc, &c->partc_wgs, &c->partc_stride, (long long)n_wg * n_workers, nc));
-  // LDS: the largest of the three phases' tiles
-  const size_t lds_a = sizeof(float) * (size_t)(((nc + 3) & ~3) + 16 * CT_STRIP);
-  const size_t lds_b = sizeof(float) * (size_t)(16 * WS_COEF_STRIDE + 2 * H + 64 + 4 + 4);   // (+ 4: the hot tiles' counter)
-  const size_t lds_c = sizeof(float) * (size_t)(((nc + 64 + 3) & ~3) + 16 * CT_STRIP);
-  const size_t lds = std::max(lds_a, std::max(lds_b, lds_c));
-  // the fixed-point scale of the hot accumulators: one contribution per row and column, |contribution| <= 2^shift, a
-  // chunk's rows known -- refined once per configuration by the data (dsgd_fstep_bound_kernel)
-  const int shift0 = std::max(1, std::min(c->k.max_shift, 30 - rows_bits(L->worst_rows)));
-  int shift = shift0;
-  if (c->k.fix_bound && shift0 < c->k.max_shift) {
-    if (L->shift < 0) {
-      DSGD_TRY(c->d_bound.reserve(1));
-      HIP_TRY(hipMemsetAsync(c->d_bound, 0, sizeof(unsigned int), c->stream));
-      hipLaunchKernelGGL(dsgd_fstep_bound_kernel, grid, dim3(1024), sizeof(unsigned int) * (size_t)(H + 16), c->stream, c->d_hrow_ptr,
-                         c->d_hcol, c->d_hval, L->d_chunks, view(c), c->d_wlong_rows, H, std::ldexp(1.0f, shift0 - c->vexp), c->d_bound);
-      HIP_TRY(hipGetLastError());
-      unsigned int amax = 0;
-      HIP_TRY(hipMemcpyAsync(&amax, c->d_bound, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      L->shift = refine_shift(shift0, c->k.max_shift, amax, L->worst_rows);
-    }
-    shift = L->shift;
-  }
-  const float main_scale = std::ldexp(1.0f, shift - c->vexp);
-  c->last_shift = std::min(shift, c->cold_shift);   // (the coarser of the two grids of this launch)
-  CsrView mh = view(c);
-  mh.row_ptr = c->d_hrow_ptr;
-  mh.col = reinterpret_cast<const int*>(c->d_hcol.get());   // 16-bit ranks; the kernel reinterprets the pointer
-  mh.val = c->d_hval;
-  size_t slot = 0;
-  DSGD_TRY(prof_begin(c, &slot));
-  c->ctr_known = false;
-  hipLaunchKernelGGL(dsgd_fstep_kernel, grid, dim3(1024), lds, c->stream, mh, view(c), L->d_tiles, L->d_meta, L->d_ctiles, L->d_cmeta,
-                     (const void*)c->d_ccol, c->d_cval, L->d_chunks, c->d_w, c->d_g64, (long long)c->dp, c->d_sc, H, nc, main_scale,
-                     c->fix_scale, c->d_coef8, c->d_dcold, c->d_wlong_rows, c->d_part, c->part_stride, c->d_partc, c->partc_stride,
-                     c->d_tprof, (c->k.fstep_rebalance && L->rebalances < 2) ? L->d_times : nullptr);
-  HIP_TRY(hipGetLastError());
-  DSGD_TRY(prof_end(c, slot));
-  c->last_grad_kernel = "dsgd_fstep_kernel";
-  DSGD_TRY(ensure_redpart(c));
-  c->fused_args = {H, n_wg, H, nc, n_wg, 1.0 / (double)main_scale, 1.0 / (double)c->fix_scale};
-  c->fused_apply_pending = true;   // launched by launch_finish_sync, which knows lr
-  return DSGD_OK;
-}
-
-// ---- column lists: whole-split steps of 10^3 .. 10^5 rows (csrc/dsgd_tcol.hpp) ----------------------------------------
-static void tcol_drop_all(dsgd_ctx* c) {   // (the ranked CSR is about to change, or the context goes away)
-  if (c->tcol_cache.empty()) return;
-  (void)hipStreamSynchronize(c->stream);
-  c->tcol_cache.clear();
-}
-static dim3 tcol_row_grid(long long mx, int n_workers) {
-  return dim3((unsigned)std::max<long long>(1, std::min<long long>((mx + TC_ROWS_PER_WG - 1) / TC_ROWS_PER_WG, 8192)), (unsigned)n_workers);
-}
-// the layout of these ranges (c->d_segs holds them): 1 = not possible (too many entries, no memory: the caller's other path)
-static int tcol_layout(dsgd_ctx* c, const std::vector<WorkSeg>& segs, long long mx, dsgd_ctx::TcolLayout** out) {
-  const int n_workers = (int)segs.size();
-  std::vector<long long> key;
-  for (const WorkSeg& sg : segs) {
-    key.push_back(sg.begin);
-    key.push_back(sg.end);
-  }
-  for (dsgd_ctx::TcolLayout& L : c->tcol_cache)
-    if (L.gen == c->layout_gen && L.ranges == key) {
-      L.used = ++c->tcol_clock;
-      if (L.n_wg == 0) return 1;   // (declined before -- no memory, too many entries: not tried again step after step)
-      c->tcol_gate.hit();
-      *out = &L;
-      return DSGD_OK;
-    }
-  if (!c->tcol_gate.miss()) return 1;   // (a caller that never repeats a configuration: the back-off, csrc/dsgd_route.hpp)
-  for (size_t i = 0; i < c->tcol_cache.size();)   // layouts of an earlier ranking
-    if (c->tcol_cache[i].gen != c->layout_gen) {
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      c->tcol_cache.erase(c->tcol_cache.begin() + (long)i);
-    } else {
-      ++i;
-    }
-  if (c->tcol_cache.size() >= 8) {   // the least recently used configuration makes room
-    size_t v = 0;
-    for (size_t i = 1; i < c->tcol_cache.size(); ++i)
-      if (c->tcol_cache[i].used < c->tcol_cache[v].used) v = i;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->tcol_cache.erase(c->tcol_cache.begin() + (long)v);
-  }
-  const int n_keys = n_workers * c->dp;
-  DevBuf<unsigned int> d_cnt, d_ptr, d_cursor;   // (the builder's scratch: released on return, the stream idle by then)
-  DevBuf<int> d_cid;
-  DevBuf<unsigned long long> d_tot;
-  dsgd_ctx::TcolLayout L;
-  auto give_up = [&](int rc) {
-    (void)hipStreamSynchronize(c->stream);
-    L = dsgd_ctx::TcolLayout();
-    if (rc == 2) return 1;   // out of memory / a failed call: declined for THIS step only (memory may be there the next time)
-    if (rc == 1) {   // remembered as declined (n_wg = 0): the caller's other path takes this configuration from now on
-      L.ranges = key;
-      L.gen = c->layout_gen;
-      L.used = ++c->tcol_clock;
-      c->tcol_cache.push_back(std::move(L));
-    }
-    return rc;
-  };
-#define TC_SOFT(expr)                        \
-  do {                                       \
-    if ((expr) != hipSuccess) {              \
-      (void)hipGetLastError();               \
-      return give_up(2);                     \
-    }                                        \
-  } while (0)
-  // every worker's rows padded to whole 64-row blocks of the bitmap (a workgroup of the dot kernel writes two whole words)
-  std::vector<int> bit_base((size_t)n_workers);
-  long long bits = 0;
-  for (int k = 0; k < n_workers; ++k) {
-    bit_base[(size_t)k] = (int)bits;
-    bits += ((segs[(size_t)k].end - segs[(size_t)k].begin + 63) / 64) * 64;
-  }
-  if (bits > TC_MAX_BITS) return give_up(1);
-  L.bm_words = (int)(((bits >> 5) + 3) & ~3LL);
-  TC_SOFT(d_cnt.try_alloc((size_t)n_keys));
-  TC_SOFT(d_ptr.try_alloc((size_t)n_keys + 1));
-  TC_SOFT(d_cursor.try_alloc((size_t)n_keys));
-  TC_SOFT(d_cid.try_alloc((size_t)n_keys));
-  TC_SOFT(d_tot.try_alloc(2));
-  TC_SOFT(L.d_bit_base.try_alloc((size_t)n_workers));
-  TC_SOFT(L.d_bitmap.try_alloc((size_t)L.bm_words));
-  TC_SOFT(hipMemcpyAsync(L.d_bit_base, bit_base.data(), sizeof(int) * (size_t)n_workers, hipMemcpyHostToDevice, c->stream));
-  TC_SOFT(hipMemsetAsync(L.d_bitmap, 0, sizeof(unsigned int) * (size_t)L.bm_words, c->stream));
-  TC_SOFT(hipMemsetAsync(d_cnt, 0, sizeof(unsigned int) * (size_t)n_keys, c->stream));
-  const dim3 grid = tcol_row_grid(mx, n_workers);
-  hipLaunchKernelGGL(dsgd_tc_count_kernel, grid, dim3(TC_THREADS), 0, c->stream, view(c), c->d_segs, c->dp, d_cnt);
-  hipLaunchKernelGGL(dsgd_tc_scan_kernel, dim3(1), dim3(TC_THREADS), 0, c->stream, d_cnt, n_keys, d_ptr, d_cursor, d_cid, d_tot);
-  TC_SOFT(hipGetLastError());
-  unsigned long long tot[2] = {0, 0};
-  TC_SOFT(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
-  TC_SOFT(hipStreamSynchronize(c->stream));   // (also: bit_base is a local)
-  if (tot[0] == 0 || tot[0] >= (1ULL << 31)) return give_up(1);
-  L.ranges = key;
-  L.gen = c->layout_gen;
-  L.n_ent = (long long)tot[0];
-  long long share = (L.n_ent + c->n_cu - 1) / std::max(1, c->n_cu);
-  share = std::max<long long>(1024, std::min<long long>(TC_MAX_SHARE, (share + 63) & ~63LL));
-  if (c->k.tcol_share > 0) share = std::max<long long>(64, std::min<long long>(TC_MAX_SHARE, (c->k.tcol_share + 3) & ~3));   // (whole 16-byte pieces)
-  L.share = (int)share;
-  L.n_wg = (int)((L.n_ent + share - 1) / share);
-  {   // whole 16-byte pieces; the last one's padding is zero
-    const size_t n_pad = ((size_t)L.n_ent + 3) & ~(size_t)3;
-    TC_SOFT(L.d_ent_pk.try_alloc(n_pad));
-    TC_SOFT(L.d_ent_val.try_alloc(n_pad));
-    TC_SOFT(hipMemsetAsync(L.d_ent_pk + (n_pad - 4), 0, sizeof(unsigned int) * 4, c->stream));
-    TC_SOFT(hipMemsetAsync(L.d_ent_val + (n_pad - 4), 0, sizeof(float) * 4, c->stream));
-  }
-  TC_SOFT(L.d_shares.try_alloc((size_t)L.n_wg));
-  TC_SOFT(L.d_key_of_cid.try_alloc((size_t)std::max<unsigned long long>(1, tot[1])));
-  hipLaunchKernelGGL(dsgd_tc_shares_kernel, dim3((unsigned)((L.n_wg + 255) / 256)), dim3(256), 0, c->stream, d_ptr, d_cid, n_keys, L.n_ent,
-                     L.share, L.n_wg, L.d_shares);
-  hipLaunchKernelGGL(dsgd_tc_fill_kernel, grid, dim3(TC_THREADS), 0, c->stream, view(c), c->d_segs, c->dp, d_cursor, d_cid, L.d_shares, L.share,
-                     L.d_bit_base, L.d_ent_pk, L.d_ent_val, L.d_key_of_cid);
-  TC_SOFT(hipGetLastError());
-  TC_SOFT(hipStreamSynchronize(c->stream));
-#undef TC_SOFT
-  L.used = ++c->tcol_clock;
-  c->tcol_cache.push_back(std::move(L));
-  *out = &c->tcol_cache.back();
-  return DSGD_OK;
-}
-// the gradient of the ranges in c->d_segs by column lists; 1 = declined (nothing launched: the caller's other path)
-static int launch_tcol(dsgd_ctx* c, const std::vector<WorkSeg>& segs, long long mx) {
-  const int n_workers = (int)segs.size();
-  dsgd_ctx::TcolLayout* L = nullptr;
-  const int lrc = tcol_layout(c, segs, mx, &L);
-  if (lrc != DSGD_OK) return lrc;
-  const int shift = std::max(1, std::min(c->k.max_shift, 30));   // 64-bit sums: nothing to bound (|contribution| <= 2^shift)
-  c->last_shift = shift;
-  const float scale = std::ldexp(1.0f, shift - c->vexp);
-  size_t slot = 0;
-  DSGD_TRY(prof_begin(c, &slot));
-  c->ctr_known = false;
-  // 32 rows (512 lanes) per workgroup while that leaves the CUs a few workgroups each: finer grains fill them evenly
-  // (18,519 rows: 290 workgroups of 64 rows leave 34 CUs with two and the rest with one)
-  dim3 dgrid = tcol_row_grid(mx, n_workers);
-  hipLaunchKernelGGL(dsgd_tc_dot_kernel<TC_THREADS>, dgrid, dim3(TC_THREADS), 0, c->stream, view(c), c->d_w, c->d_segs, L->d_bit_base,
-                     L->d_bitmap, std::min(TC_WL, c->dp & ~3));
-  HIP_TRY(hipGetLastError());
-  TcGradArgs a;
-  a.ent_pk = L->d_ent_pk;
-  a.ent_val = L->d_ent_val;
-  a.shares = L->d_shares;
-  a.key_of_cid = L->d_key_of_cid;
-  a.bitmap = L->d_bitmap;
-  a.g64 = c->d_g64;
-  a.sc = c->d_sc;
-  a.n_ent = L->n_ent;
-  a.share = L->share;
-  a.bm_words = L->bm_words;
-  a.scale = scale;
-  {
-    const dim3 g2((unsigned)L->n_wg);
-    const size_t lds = sizeof(long long) * (size_t)L->share + sizeof(unsigned int) * (size_t)L->bm_words + 64;
-    if (L->share <= 4 * TC_THREADS) hipLaunchKernelGGL(dsgd_tc_grad_kernel<1>, g2, dim3(TC_THREADS), lds, c->stream, a);
-    else hipLaunchKernelGGL(dsgd_tc_grad_kernel<2>, g2, dim3(TC_THREADS), lds, c->stream, a);
-  }
-  HIP_TRY(hipGetLastError());
-  DSGD_TRY(prof_end(c, slot));
-  c->last_grad_kernel = "dsgd_tc_grad_kernel";
-  DSGD_TRY(ensure_redpart(c));
-  const double inv = 1.0 / (double)scale;
-  c->fused_args = {0, 0, (c->dp + 3) & ~3, 0, 0, inv, inv};   // no partials: the exact sums are in the 64-bit accumulators
-  c->fused_apply_pending = true;   // launched by launch_finish_sync, which knows lr
-  return DSGD_OK;
-}
+#include "dsgd_fstep_host.hpp"   // (the row chunks: fstep_layout, launch_fstep)
+#include "dsgd_tcol_host.hpp"    // (the column lists: the (worker, column) sort, tcol_layout, launch_tcol)
 
 static int hog_raise_stop(dsgd_ctx* c);
 
@@ -2816,8 +2495,7 @@ static int load_csr_impl(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in,
   ++c->layout_gen;
   ++c->load_gen;
   c->bound_segs.clear();
-  c->tcol_gate.reset();   // (the column lists' misses were about the old rows' ranges)
-  c->lgc_cache.clear();   // (the logistic column lists hold the old rows' entries; the stream is idle: synchronised above)
+  layouts_drop_all(c);   // (they hold the old rows' entries)
   c->last_grad_kernel = "";  // (dsgd_grad_kernel_name / dsgd_tuning_info report launches over THIS data: calls that record none --
   c->last_shift = FIX_SHIFT; //  the row-parallel fp64 requests -- would go on reporting the old data's)
   // (the wave tiles cover the hot stream and are built with the layout, at the first compute call)
@@ -3785,10 +3463,7 @@ static int forward_run(dsgd_ctx* c, const int32_t* idx, int64_t n, float* pred_o
     DSGD_TRY(c->d_pred.reserve((size_t)std::max<long long>(n, 4096)));
   }
   float* d_pred = c->d_pred;
-  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int) * (size_t)n));
-  memcpy(c->pin_idx.p, idx, sizeof(int) * (size_t)n);
-  HIP_TRY(hipMemcpyAsync(c->d_idx, c->pin_idx.p, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  DSGD_TRY(pin_sent(c, c->pin_idx));
+  DSGD_TRY(send_idx(c, idx, n));
   DSGD_TRY(pin_acquire(c->pin_out, sizeof(float) * (size_t)n));
   const int G = c->group;
   dim3 grid(grid_for(c, n, G));
@@ -4135,10 +3810,7 @@ static int loss_acc_list_impl(dsgd_ctx* c, const char* what, bool f64, const flo
   DSGD_TRY(prepare_layout(c));
   DSGD_TRY(eval_list_weights(c, w, w64));
   DSGD_TRY(ensure_idx(c, n));
-  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int) * (size_t)n));
-  memcpy(c->pin_idx.p, idx, sizeof(int) * (size_t)n);
-  HIP_TRY(hipMemcpyAsync(c->d_idx, c->pin_idx.p, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  DSGD_TRY(pin_sent(c, c->pin_idx));
+  DSGD_TRY(send_idx(c, idx, n));
   return eval_list_run(c, n, loss, acc, counts, nullptr);
 }
 int dsgd_loss_acc_list(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, double* loss, double* acc, int64_t* counts) {

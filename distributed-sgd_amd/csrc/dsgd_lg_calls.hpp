@@ -223,6 +223,15 @@ int dsgd_lg_sync_step(dsgd_ctx* c, const int32_t* const* idx_per_worker, const i
   return lg_step_done(c, stats, tot);
 }
 
+// the row ranges of a whole-split call as the WorkSegs in c->d_segs
+static int lg_upload_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int n_workers) {
+  std::vector<WorkSeg> segs((size_t)n_workers);
+  for (int k = 0; k < n_workers; ++k) {
+    segs[(size_t)k].begin = row_begin[k];
+    segs[(size_t)k].end = row_end[k];
+  }
+  return upload_segs(c, segs);
+}
 int dsgd_lg_sync_step_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, float lr, dsgd_batch_stats* stats) {
   DSGD_TRY(check_ctx(c));
   if (n_workers < 1 || !row_begin || !row_end) return fail(DSGD_EINVAL, "dsgd_lg_sync_step_ranges: Cannot sum an empty list of vectors (no workers)");
@@ -234,12 +243,7 @@ int dsgd_lg_sync_step_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_
   DSGD_TRY(prepare_layout(c));
   DSGD_TRY(lg_ensure(c, n_workers));
   DSGD_TRY(reset_counters(c));
-  std::vector<WorkSeg> segs((size_t)n_workers);
-  for (int k = 0; k < n_workers; ++k) {
-    segs[(size_t)k].begin = row_begin[k];
-    segs[(size_t)k].end = row_end[k];
-  }
-  DSGD_TRY(upload_segs(c, segs));
+  DSGD_TRY(lg_upload_ranges(c, row_begin, row_end, n_workers));
   DSGD_TRY(lg_launch(c, false, n_workers, v.longest, LG_STEP, lr, nullptr, c->d_segs));
   return lg_step_done(c, stats, v.total);
 }
@@ -255,88 +259,41 @@ static int lgc_layout(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_
     key.push_back(row_end[k]);
     n_ent += c->h_row_ptr[(size_t)row_end[k]] - c->h_row_ptr[(size_t)row_begin[k]];
   }
-  for (dsgd_ctx::LgColsLayout& L : c->lgc_cache)
-    if (L.gen == c->layout_gen && L.ranges == key) {
-      L.used = ++c->lgc_clock;
-      if (L.n_wg == 0) return 1;   // (declined before: not tried again step after step)
-      *out = &L;
-      return DSGD_OK;
-    }
-  for (size_t i = 0; i < c->lgc_cache.size();)   // layouts of an earlier ranking
-    if (c->lgc_cache[i].gen != c->layout_gen) {
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      c->lgc_cache.erase(c->lgc_cache.begin() + (long)i);
-    } else {
-      ++i;
-    }
-  if (c->lgc_cache.size() >= 8) {   // the least recently used configuration makes room
-    size_t v = 0;
-    for (size_t i = 1; i < c->lgc_cache.size(); ++i)
-      if (c->lgc_cache[i].used < c->lgc_cache[v].used) v = i;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->lgc_cache.erase(c->lgc_cache.begin() + (long)v);
+  if (auto* e = c->lgc_cache.find(key, 0, c->layout_gen)) {
+    if (e->declined) return 1;   // (declined before: not tried again step after step)
+    *out = &e->layout;
+    return DSGD_OK;
   }
+  DSGD_TRY(layout_room(c, c->lgc_cache));
   dsgd_ctx::LgColsLayout L;
-  L.ranges = key;
-  L.gen = c->layout_gen;
   LgcPlan plan;
   std::vector<long long> base((size_t)K);
   if (lgc_plan(row_begin, row_end, K, n_ent, c->dp, c->lg_stride, c->n_cu, &plan, base.data()) != LGC_OK) {
-    L.used = ++c->lgc_clock;   // remembered as declined (n_wg = 0)
-    c->lgc_cache.push_back(std::move(L));
+    c->lgc_cache.insert_declined(std::move(key), 0, c->layout_gen);   // remembered as declined
     return 1;
   }
-  const int n_keys = K * c->dp;
-  DevBuf<unsigned int> d_cnt, d_ptr, d_cursor;   // (the builder's scratch: released on return, the stream idle by then)
-  DevBuf<int> d_cid;
-  DevBuf<unsigned long long> d_tot;
-  auto give_up = [&]() {   // no memory or a failed call: declined for THIS call only
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(c->stream);
-    return 1;
-  };
-#define LGC_SOFT(expr) \
-  do {                 \
-    if ((expr) != hipSuccess) return give_up(); \
-  } while (0)
   std::vector<int> pos_base(base.begin(), base.end());   // (below 2^31: lgc_plan)
-  LGC_SOFT(d_cnt.try_alloc((size_t)n_keys));
-  LGC_SOFT(d_ptr.try_alloc((size_t)n_keys + 1));
-  LGC_SOFT(d_cursor.try_alloc((size_t)n_keys));
-  LGC_SOFT(d_cid.try_alloc((size_t)n_keys));
-  LGC_SOFT(d_tot.try_alloc(2));
-  LGC_SOFT(L.d_pos_base.try_alloc((size_t)K));
-  LGC_SOFT(L.d_cq.try_alloc((size_t)plan.positions));
-  LGC_SOFT(L.d_ent.try_alloc((size_t)plan.n_pad));
-  LGC_SOFT(L.d_shares.try_alloc((size_t)plan.n_shares));
-  LGC_SOFT(hipMemcpyAsync(L.d_pos_base, pos_base.data(), sizeof(int) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-  LGC_SOFT(hipMemsetAsync(d_cnt, 0, sizeof(unsigned int) * (size_t)n_keys, c->stream));
-  LGC_SOFT(hipMemsetAsync(L.d_ent + (plan.n_pad - plan.share), 0, sizeof(uint2) * (size_t)plan.share, c->stream));   // the last share's padding
+  LAYOUT_SOFT(L.d_pos_base.try_alloc((size_t)K));
+  LAYOUT_SOFT(L.d_cq.try_alloc((size_t)plan.positions));
+  LAYOUT_SOFT(L.d_ent.try_alloc((size_t)plan.n_pad));
+  LAYOUT_SOFT(L.d_shares.try_alloc((size_t)plan.n_shares));
+  LAYOUT_SOFT(hipMemcpyAsync(L.d_pos_base, pos_base.data(), sizeof(int) * (size_t)K, hipMemcpyHostToDevice, c->stream));
+  LAYOUT_SOFT(hipMemsetAsync(L.d_ent + (plan.n_pad - plan.share), 0, sizeof(uint2) * (size_t)plan.share, c->stream));   // the last share's padding
   const dim3 grid = tcol_row_grid(longest, K);
-  hipLaunchKernelGGL(dsgd_tc_count_kernel, grid, dim3(TC_THREADS), 0, c->stream, view(c), c->d_segs, c->dp, d_cnt);
-  hipLaunchKernelGGL(dsgd_tc_scan_kernel, dim3(1), dim3(TC_THREADS), 0, c->stream, d_cnt, n_keys, d_ptr, d_cursor, d_cid, d_tot);
-  LGC_SOFT(hipGetLastError());
-  unsigned long long tot[2] = {0, 0};
-  LGC_SOFT(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
-  LGC_SOFT(hipStreamSynchronize(c->stream));   // (also: pos_base is a local)
-  if (tot[0] != (unsigned long long)n_ent) {
-    (void)hipStreamSynchronize(c->stream);
-    return fail(DSGD_ESTATE, "logistic column lists: the device counted %llu entries in the ranges, the host %lld", tot[0], n_ent);
-  }
+  ColSort sort;
+  LAYOUT_SOFT(sort.count(c, grid, K * c->dp));   // (also: pos_base is a local)
+  if (sort.tot[0] != (unsigned long long)n_ent)   // (the stream is idle: count returned behind its kernels)
+    return fail(DSGD_ESTATE, "logistic column lists: the device counted %llu entries in the ranges, the host %lld", sort.tot[0], n_ent);
   L.n_ent = n_ent;
   L.share = plan.share;
-  LGC_SOFT(L.d_slot_of_cid.try_alloc((size_t)std::max<unsigned long long>(1, tot[1])));
-  hipLaunchKernelGGL(dsgd_tc_shares_kernel, dim3((unsigned)((plan.n_shares + 255) / 256)), dim3(256), 0, c->stream, d_ptr, d_cid, n_keys, L.n_ent,
-                     L.share, (int)plan.n_shares, L.d_shares);
-  hipLaunchKernelGGL(dsgd_lgc_fill_kernel, grid, dim3(TC_THREADS), 0, c->stream, view(c), c->d_segs, c->dp, d_ptr.get(), d_cursor.get(), d_cid.get(),
-                     L.d_pos_base.get(), c->lg_stride, L.d_ent.get(), L.d_slot_of_cid.get());
-  LGC_SOFT(hipGetLastError());
-  LGC_SOFT(hipStreamSynchronize(c->stream));
-#undef LGC_SOFT
   L.n_wg = (int)plan.n_shares;
-  L.used = ++c->lgc_clock;
-  c->lgc_cache.push_back(std::move(L));
-  *out = &c->lgc_cache.back();
+  LAYOUT_SOFT(L.d_slot_of_cid.try_alloc((size_t)std::max<unsigned long long>(1, sort.tot[1])));
+  sort.shares(c, L.n_ent, L.share, L.n_wg, L.d_shares);
+  hipLaunchKernelGGL(dsgd_lgc_fill_kernel, grid, dim3(TC_THREADS), 0, c->stream, view(c), c->d_segs, c->dp, sort.d_ptr.get(), sort.d_cursor.get(),
+                     sort.d_cid.get(), L.d_pos_base.get(), c->lg_stride, L.d_ent.get(), L.d_slot_of_cid.get());
+  LAYOUT_SOFT(hipGetLastError());
+  LAYOUT_SOFT(hipStreamSynchronize(c->stream));
+  *out = &c->lgc_cache.insert(std::move(key), 0, c->layout_gen, std::move(L))->layout;
   return DSGD_OK;
 }
 // the three launches of one step over the ranges in c->d_segs, by their layout
@@ -379,12 +336,7 @@ int dsgd_lg_sync_steps_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64
   DSGD_TRY(prepare_layout(c));
   DSGD_TRY(lg_ensure(c, n_workers));
   DSGD_TRY(reset_counters(c));
-  std::vector<WorkSeg> segs((size_t)n_workers);
-  for (int k = 0; k < n_workers; ++k) {
-    segs[(size_t)k].begin = row_begin[k];
-    segs[(size_t)k].end = row_end[k];
-  }
-  DSGD_TRY(upload_segs(c, segs));
+  DSGD_TRY(lg_upload_ranges(c, row_begin, row_end, n_workers));
   dsgd_ctx::LgColsLayout* L = nullptr;
   const int lrc = lgc_layout(c, row_begin, row_end, n_workers, v.longest, &L);
   if (lrc != DSGD_OK && lrc != 1) return lrc;
@@ -418,10 +370,7 @@ int dsgd_lg_sync_steps(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const int
   DSGD_TRY(reset_counters(c));
   // ONE upload: the index array and the list ranges of every step
   DSGD_TRY(ensure_idx(c, n_idx));
-  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int) * (size_t)n_idx));
-  memcpy(c->pin_idx.p, idx, sizeof(int) * (size_t)n_idx);
-  HIP_TRY(hipMemcpyAsync(c->d_idx, c->pin_idx.p, sizeof(int) * (size_t)n_idx, hipMemcpyHostToDevice, c->stream));
-  DSGD_TRY(pin_sent(c, c->pin_idx));
+  DSGD_TRY(send_idx(c, idx, n_idx));
   c->cur_idx = c->d_idx;
   DSGD_TRY(pin_acquire(c->pin_segs, sizeof(WorkSeg) * (size_t)n_lists));
   {
@@ -555,10 +504,7 @@ int dsgd_lg_predict(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, 
     DSGD_TRY(c->d_lg_p.reserve((size_t)std::max<long long>(n, 4096)));
   }
   DSGD_TRY(reset_counters(c));
-  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(int) * (size_t)n));
-  memcpy(c->pin_idx.p, idx, sizeof(int) * (size_t)n);
-  HIP_TRY(hipMemcpyAsync(c->d_idx, c->pin_idx.p, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  DSGD_TRY(pin_sent(c, c->pin_idx));
+  DSGD_TRY(send_idx(c, idx, n));
   DSGD_TRY(pin_acquire(c->pin_out, sizeof(float) * (size_t)n));
   hipLaunchKernelGGL(dsgd_lg_predict_kernel, dim3((unsigned)grid_for(c, n, LG_GROUP)), dim3(LG_THREADS), 0, c->stream, view(c), c->d_w, c->d_idx,
                      (long long)n, c->d_lg_p, c->d_sc);

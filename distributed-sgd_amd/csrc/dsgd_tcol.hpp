@@ -30,7 +30,7 @@
 // Same fixed-point grid as every other path (round(y x 2^shift / vmax2), shift = the context's cap: 21): the integer
 // sums are those the row-parallel kernels would have formed -- same gate decisions => the same bits.
 // The layout is built by the device (count -> scan -> fill; the order inside a column is whatever the fill's atomics
-// produce: integer sums do not care) once per configuration and cached by the host (dsgd_hip.hip: tcol_layout).
+// produce: integer sums do not care) once per configuration and cached by the host (csrc/dsgd_tcol_host.hpp: tcol_layout).
 #pragma once
 
 #include "dsgd_kernels.hpp"

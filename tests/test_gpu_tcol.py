@@ -251,3 +251,36 @@ def test_hand_over_to_row_chunks_by_entries(monkeypatch):
                                ([(0, 1000)], TCOL)):
             ranged_step(o, eng, ranges, 0.5 * 100 / n_train * len(ranges))
             assert eng.grad_kernel_name() == kernel, ranges
+
+
+def test_a_load_releases_the_column_lists_at_once():
+    """A context steps over two ranges of 3,000 rows through the column lists, loads other rows and steps over the same ranges
+    from the same weights (tests/tcol_reload_worker.py, on the tests' seam build: the only one that counts the bytes it holds).
+    The layout of the old rows must not serve: the weights are bit-equal to those of a context that only ever saw the second
+    rows, and differ from the first result.  And the load itself gives the layout back, not the next miss: directly after it
+    the context holds no more device bytes than before it -- less, by at least the 8 bytes (a packed word and a value,
+    csrc/dsgd_tcol.hpp) of every entry of the ranges' rows, once the difference of the two data sets (8 bytes per non-zero:
+    the row count is the same) is taken out.  An exact comparison with the fresh context after its own load is not possible:
+    beside grow-only scratch, the split streams of the old ranking stay until the next ranking replaces them."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from test_rccl_stub import seam_env
+
+    env = seam_env()
+    for k in KNOBS:
+        env.pop(k, None)
+    env["DSGD_TCOL"] = "1"   # (seam_env switches the column lists off for the rank workers)
+    here = os.path.dirname(os.path.abspath(__file__))
+    proc = subprocess.run([sys.executable, os.path.join(here, "tcol_reload_worker.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                          text=True, timeout=300)
+    print(proc.stdout)
+    assert proc.returncode == 0, proc.stdout
+    r = [json.loads(line[7:]) for line in proc.stdout.splitlines() if line.startswith("RELOAD ")][0]
+    assert r["kernels"] == [TCOL, TCOL, TCOL], r
+    assert r["moved"] and r["reloaded_equals_fresh"] and not r["reloaded_equals_first"], r
+    data_delta = 8 * (r["nnz"][1] - r["nnz"][0])
+    assert r["after_load"] <= r["before_load"], r
+    assert r["after_load"] <= r["before_load"] + data_delta - 8 * r["n_ent"], r
