@@ -52,6 +52,7 @@ SYMBOLS = [
     "dsgd_lg_gradient", "dsgd_lg_sync_step", "dsgd_lg_sync_step_ranges", "dsgd_lg_sync_steps", "dsgd_lg_loss_acc", "dsgd_lg_predict",
     "dsgd_plan_create_lg_n", "dsgd_plan_create_from_seed_lg", "dsgd_lg_loss_acc_ranges",
     "dsgd_lg_sync_steps_ranges",
+    "dsgd_plan_create_lg_cs_n", "dsgd_plan_create_from_seed_lg_cs",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -140,6 +141,10 @@ def load():
                                                       C.c_void_p, C.c_void_p]
         # (ctx, w*, row_begin*, row_end*, n_ranges, loss_out*, acc_out*)
         lib.dsgd_lg_loss_acc_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "dsgd_plan_create_lg_cs_n"):   # logistic plans on column slices: the prototypes of the two above
+        lib.dsgd_plan_create_lg_cs_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        lib.dsgd_plan_create_from_seed_lg_cs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p]
     if hasattr(lib, "dsgd_lg_sync_steps_ranges"):   # (ctx, row_begin*, row_end*, n_workers, n_steps, lr, stats*)
         lib.dsgd_lg_sync_steps_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p]
     if hasattr(lib, "dsgd_dense_plan_create"):   # (handles are 64-bit: without argtypes ctypes would pass them as C ints)

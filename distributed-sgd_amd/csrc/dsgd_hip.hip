@@ -129,6 +129,7 @@ static bool available() {
 #include "dsgd_logistic.hpp"   // (the logistic model beside the SVM: its own gradient, finish, evaluation and probabilities)
 #include "dsgd_batch.hpp"
 #include "dsgd_cs.hpp"
+#include "dsgd_lg_cs.hpp"   // (the logistic model on column slices: the cell layout and the exchange above, logistic arithmetic)
 #include "dsgd_dense.hpp"
 #include "dsgd_fstep.hpp"
 #include "dsgd_tcol.hpp"
@@ -195,6 +196,10 @@ struct dsgd_plan {
   // a logistic plan (dsgd_plan_create_lg_n, dsgd_plan_create_from_seed_lg): likewise the lists and their ranges only -- its steps
   // are the two launches of dsgd_lg_sync_step over d_idx / d_segs (plan_run_lg, csrc/dsgd_lg_calls.hpp)
   bool lg = false;
+  // ... that additionally asked for its column slices (dsgd_plan_create_lg_cs_n, dsgd_plan_create_from_seed_lg_cs): laid out at
+  // creation by dsgd_cs_layout_kernel into d_cs_* (LG_CS_G slices); while they are current its steps are ONE launch of
+  // dsgd_lg_cs_step_kernel (plan_run_lg_cs), else plan_run_lg's two per step
+  bool lg_cs = false;
   void cs_free() {
     d_cs_hdr.reset(), d_cs_meta.reset(), d_cs_rf.reset(), d_cs_col.reset(), d_cs_val.reset(), d_cs_cl.reset();
     cs_ok = false;
@@ -1074,8 +1079,10 @@ static int cs_build_device_impl(dsgd_ctx* c, dsgd_plan* p) {
   const long long n_steps = p->n_steps, n_lists = n_steps * K;
   if (K > CS_MAX_K || p->max_step_rows > CS_MAX_SLOTS) return DSGD_OK;
   // (fp64: always CS64_G slices, the fp64 kernel's own LDS budget)
-  const int G = c->fp64 ? ((K <= CS64_MAX_K && cs64_lds_bytes(c->dp, K) <= CS64_LDS_MAX && c->dp >= 4 * CS64_G) ? CS64_G : 0)
-                        : cs_pick_G(c->k, route_facts(c), K, false);
+  // (a logistic plan: its own LDS budget, csrc/dsgd_lg_cs_host.hpp)
+  const int G = p->lg ? lg_cs_pick_G(c->dp, K)
+                      : c->fp64 ? ((K <= CS64_MAX_K && cs64_lds_bytes(c->dp, K) <= CS64_LDS_MAX && c->dp >= 4 * CS64_G) ? CS64_G : 0)
+                                : cs_pick_G(c->k, route_facts(c), K, false);
   if (!G) return DSGD_OK;
   if (n_steps * (long long)G > 0x7fffffffLL) return DSGD_OK;
   if (!p->idx_trusted) {
@@ -1140,8 +1147,8 @@ static int cs_build_device_impl(dsgd_ctx* c, dsgd_plan* p) {
   hipLaunchKernelGGL(dsgd_cs_layout_kernel<true>, dim3((unsigned)(n_steps * G)), dim3(CS_THREADS), 0, bs, ba);
   HIP_TRY(hipGetLastError());
   p->cs_G = G;
-  p->cs_nt = (c->k.cs_nt == CS_THREADS_NARROW && narrow_fits && !c->fp64) ? CS_THREADS_NARROW : CS_THREADS;
-  p->cs_spl = (p->cs_nt == CS_THREADS && one_fits) ? 1 : 2;
+  p->cs_nt = (c->k.cs_nt == CS_THREADS_NARROW && narrow_fits && !c->fp64 && !p->lg) ? CS_THREADS_NARROW : CS_THREADS;
+  p->cs_spl = (p->cs_nt == CS_THREADS && (p->lg ? big <= CS_THREADS : one_fits)) ? 1 : 2;   // (the logistic kernel reads no column list)
   p->cs_slot_stride = slot_stride;
   p->cs_row_stride = row_stride;
   p->cs_cl_stride = cl_stride;
@@ -1320,7 +1327,7 @@ static int cs_build_impl(dsgd_ctx* c, dsgd_plan* p) {
 static int cs_build(dsgd_ctx* c, dsgd_plan* p) {
   int rc;
   try {
-    rc = (c->k.cs_host_layout && !c->fp64) ? cs_build_impl(c, p) : cs_build_device_impl(c, p);
+    rc = (c->k.cs_host_layout && !c->fp64 && !p->lg) ? cs_build_impl(c, p) : cs_build_device_impl(c, p);
   } catch (const std::bad_alloc&) {   // (nothing may unwind across the C ABI)
     rc = 1;
   }
@@ -2282,6 +2289,8 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   DSGD_ATTR((dsgd_cs_step_kernel<CS_THREADS, 1, 4>));
   DSGD_ATTR((dsgd_cs_step_kernel<CS_THREADS, 2, 8>));
   DSGD_ATTR((dsgd_cs_step_kernel<CS_THREADS_NARROW, 2, 8>));
+  DSGD_ATTR((dsgd_lg_cs_step_kernel<1>));
+  DSGD_ATTR((dsgd_lg_cs_step_kernel<2>));
   DSGD_ATTR(dsgd_wseg_kernel<true>);
   DSGD_ATTR(dsgd_wseg_kernel<false>);
   DSGD_ATTR(dsgd_wseg_bound_kernel);
@@ -2993,6 +3002,7 @@ static PlanRoute plan_route(const dsgd_ctx* c, const dsgd_plan* p) {
   f.rp64 = p->rp64;
   f.lg = p->lg;
   f.cs_current = p->cs_ok && p->cs_layout == c->layout_gen;
+  f.lg_cs_current = p->lg && p->lg_cs && f.cs_current;
   f.fits_here = p->fits && p->fits_rows == c->n_rows;
   f.vt_current = p->vt_ok && p->vt_layout == c->layout_gen;
   f.max_step_rows = p->max_step_rows;
@@ -3252,7 +3262,7 @@ int dsgd_plan_info(dsgd_ctx* c, dsgd_plan* p, int32_t* vals, int32_t n) {
     DSGD_TRY(plan_revalidate(c, p));
   }
   const PlanRoute r = plan_route(c, p);
-  const bool cs = r == PLAN_CS || r == PLAN_CS64;
+  const bool cs = r == PLAN_CS || r == PLAN_CS64 || r == PLAN_LG_CS;
   const int32_t all[9] = {plan_info_code(r, p->cs_layout == c->layout_gen || p->vt_layout == c->layout_gen),
                           cs ? p->cs_G : 0, cs ? p->cs_slot_stride : 0, cs ? p->cs_row_stride : 0, cs ? p->cs_cl_stride : 0,
                           cs ? p->cs_spl : 0, (cs && p->cs_device_built) ? 1 : 0, p->gate_words, cs ? p->cs_nt : 0};

@@ -13,9 +13,10 @@ static int lg_refuse(dsgd_ctx* c, const char* what) {
   return DSGD_OK;
 }
 // what every call asks first (locked): the mode, the device, the data, the engine
-static int lg_enter(dsgd_ctx* c, const char* what, bool* nsq_fresh) {
+// (keep_sliced: a plan on column slices keeps the weights slice-major between its runs, as the SVM's -- bind)
+static int lg_enter(dsgd_ctx* c, const char* what, bool* nsq_fresh, bool keep_sliced = false) {
   DSGD_TRY(lg_refuse(c, what));
-  DSGD_TRY(bind(c));
+  DSGD_TRY(bind(c, keep_sliced));
   *nsq_fresh = c->lg_nsq_stamp + 1 == c->bind_count;   // (no other entry point has bound since the logistic call that left |w|^2)
   DSGD_TRY(require_data(c));
   if (c->async_running)
@@ -146,16 +147,131 @@ int dsgd_plan_create_from_seed_lg(dsgd_ctx* c, uint64_t* jstate, const int64_t* 
   return plan_from_seed_whole(c, "dsgd_plan_create_from_seed_lg", false, jstate, split_begin, split_end, n_splits, max_samples, batch_size, out,
                               n_steps_out, draws_out, true);
 }
+
+// ---- logistic plans on column slices (csrc/dsgd_lg_cs.hpp; the decline rule: csrc/dsgd_lg_cs_host.hpp) ----
+static_assert(LG_CS_MAX_SLICE_COLS == CS_MAX_SLICE_COLS, "one cap on a slice's columns for both models");
+// A logistic plan just made additionally gets its column slices: the SVM plans' device builder as it stands (cs_build ->
+// dsgd_cs_layout_kernel, pass 1 and 2) on the build stream, behind the plan's lists, into blocks from the plan cache that
+// the plan owns.  Where lg_cs_pick_G finds no slice count, a step holds more than CS_MAX_SLOTS rows or slots, or the cache
+// cannot hold the layout, the builder declines softly: the plan is a plain logistic plan (plan code 7).
+static int lg_plan_add_slices(dsgd_ctx* c, dsgd_plan* p) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(bind(c, true));   // (nothing here touches w)
+  p->lg_cs = true;
+  if (c->async_running) return DSGD_OK;   // (the lock-free engine owns the launch stream: no layout, the row form)
+  DSGD_TRY(prepare_layout(c));
+  DSGD_TRY(cs_build(c, p));
+  if (c->build_stream) {   // the plan's set-up now ends behind the layout kernels
+    HIP_TRY(hipEventRecord(p->built_ev, c->build_stream));
+    p->built_pending = true;
+  }
+  return DSGD_OK;
+}
+// dsgd_plan_create_lg_n's arguments, checks and refusals; the plan additionally has its column slices laid out
+int dsgd_plan_create_lg_cs_n(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const int64_t* offsets, int64_t n_steps, int32_t n_workers,
+                             dsgd_plan** out) {
+  DSGD_TRY(check_ctx(c));
+  if (!out) return fail(DSGD_EINVAL, "dsgd_plan_create_lg_cs_n: bad arguments (null pointers, no steps, no workers or no rows)");
+  dsgd_plan* p = nullptr;
+  DSGD_TRY(dsgd_plan_create_lg_n(c, idx, n_idx, offsets, n_steps, n_workers, &p));
+  const int rc = lg_plan_add_slices(c, p);
+  if (rc != DSGD_OK) {
+    char msg[sizeof(g_err)];
+    snprintf(msg, sizeof(msg), "%s", g_err);
+    (void)dsgd_plan_destroy(c, p);
+    return fail(rc, "%s", msg);
+  }
+  *out = p;
+  return DSGD_OK;
+}
+// ... and dsgd_plan_create_from_seed_lg's: the same lists, *jstate, *n_steps_out and *draws_out
+int dsgd_plan_create_from_seed_lg_cs(dsgd_ctx* c, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
+                                     int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out) {
+  DSGD_TRY(check_ctx(c));
+  if (!jstate || !out || !n_steps_out) return fail(DSGD_EINVAL, "bad arguments");
+  const uint64_t state_before = *jstate;
+  dsgd_plan* p = nullptr;
+  DSGD_TRY(dsgd_plan_create_from_seed_lg(c, jstate, split_begin, split_end, n_splits, max_samples, batch_size, &p, n_steps_out, draws_out));
+  if (p) {   // (an epoch of no steps has no plan)
+    const int rc = lg_plan_add_slices(c, p);
+    if (rc != DSGD_OK) {   // as if nothing had been drawn
+      char msg[sizeof(g_err)];
+      snprintf(msg, sizeof(msg), "%s", g_err);
+      (void)dsgd_plan_destroy(c, p);
+      *jstate = state_before;
+      *n_steps_out = 0;
+      if (draws_out) *draws_out = 0;
+      return fail(rc, "%s", msg);
+    }
+  }
+  *out = p;
+  return DSGD_OK;
+}
+// The steps [step_begin, step_end) of a logistic plan whose column slices are current: ONE launch of dsgd_lg_cs_step_kernel.
+// plan_run_lg made the refusals, bound with the slice-major weights kept and waited for the plan's set-up.
+static int plan_run_lg_cs(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, float lr) {
+  const int K = p->n_workers, G = p->cs_G;
+  // the weights slice-major for G slices; dimSparsity with them where the context has one (an SVM slice launch that finds
+  // the weights sliced for its G reads both)
+  if (c->cs_w_G != G) {
+    if (c->have_ds) {
+      DSGD_TRY(cs_ensure_sliced(c, G));
+    } else {
+      DSGD_TRY(cs_unslice(c));
+      const int Sp = cs_sp(c->dp, G), n = G * Sp;
+      const size_t cap = (size_t)(c->dp + (CS_MAX_G + 1) * 8);
+      DSGD_TRY(c->d_cs_w.reserve(cap));
+      hipLaunchKernelGGL(dsgd_cs_slice_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_w, c->d_cs_w, c->dp, G, Sp);
+      HIP_TRY(hipGetLastError());
+      c->cs_w_G = G;
+    }
+  }
+  LgCsArgs la;
+  CsArgs& a = la.cs;
+  a.hdr = p->d_cs_hdr;
+  a.slot_meta = p->d_cs_meta;
+  a.row_first = p->d_cs_rf;
+  a.col = p->d_cs_col;
+  a.val = p->d_cs_val;
+  a.clist = p->d_cs_cl;
+  a.cl_stride = p->cs_cl_stride;
+  cs_common_args(c, a, G, K, lr);
+  a.tprof = nullptr;
+  a.test_skip_publish = 0;
+  a.n_steps_plan = p->n_steps;
+  a.step_begin = step_begin;
+  a.step_end = step_end;
+  a.slot_stride = p->cs_slot_stride;
+  a.row_stride = p->cs_row_stride;
+  la.segs = p->d_segs;
+  la.lr = (double)lr;
+  la.lambda = c->cfg.lambda;
+  const size_t lds = sizeof(float) * (size_t)lg_cs_lds(c->dp, G, K).words;
+  DSGD_TRY(cs_take_tags(c, (unsigned long long)(step_end - step_begin), &a.tag0));   // (the one counter of both models' launches)
+  if (p->cs_spl == 1)
+    hipLaunchKernelGGL(dsgd_lg_cs_step_kernel<1>, dim3((unsigned)G), dim3(CS_THREADS), lds, c->stream, la);
+  else
+    hipLaunchKernelGGL(dsgd_lg_cs_step_kernel<2>, dim3((unsigned)G), dim3(CS_THREADS), lds, c->stream, la);
+  HIP_TRY(hipGetLastError());
+  c->last_grad_kernel = "dsgd_lg_cs_step_kernel";
+  c->fused_apply_pending = false;
+  c->s_lazy = false;
+  c->nsq_dirty = false;
+  return DSGD_OK;
+}
 // The steps [step_begin, step_end) of a logistic plan (dsgd_plan_run holds the lock and has checked the range): per step the
 // two launches of dsgd_lg_sync_step over the plan's resident lists -- no upload, no host synchronisation.  Every refusal comes
 // before the first launch.  dsgd_synchronize reports the rows (every row contributes: n_active == n_samples).
 static int plan_run_lg(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, float lr) {
   bool fresh = false;
-  DSGD_TRY(lg_enter(c, "dsgd_plan_run (a logistic plan)", &fresh));
+  DSGD_TRY(lg_enter(c, "dsgd_plan_run (a logistic plan)", &fresh, p->lg_cs));
   DSGD_TRY(plan_revalidate(c, p));   // (a plan from before the last load: DSGD_ERANGE here, before anything is enqueued)
   DSGD_TRY(prepare_layout(c));
   const int K = p->n_workers;
-  DSGD_TRY(lg_ensure(c, K));
+  // a plan made with its column slices runs on them while they are current; declined or stale: the two launches below
+  const bool slices = p->lg_cs && plan_route(c, p) == PLAN_LG_CS && ensure_cs_exchange(c) == DSGD_OK;
+  if (p->lg_cs && !slices) DSGD_TRY(cs_unslice(c));   // (bound with the slice-major weights kept: the row form reads d_w)
+  if (!slices) DSGD_TRY(lg_ensure(c, K));
   if (p->built_pending) {   // the plan's set-up ran beside the launch stream: wait for it, once
     HIP_TRY(hipStreamWaitEvent(c->stream, p->built_ev, 0));
     p->built_pending = false;
@@ -166,12 +282,16 @@ static int plan_run_lg(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long lon
   }
   c->s_dirty = true;
   c->lg_nsq_stamp = ~0ull - 1;
-  for (long long t = step_begin; t < step_end; ++t) {
-    long long mx = 0;
-    for (int k = 0; k < K; ++k) mx = std::max<long long>(mx, p->offsets[(size_t)(t * K + k + 1)] - p->offsets[(size_t)(t * K + k)]);
-    DSGD_TRY(lg_launch(c, true, K, mx, LG_STEP, lr, p->d_idx, p->d_segs + t * K));
+  if (slices) {   // ONE launch; it leaves no |w'|^2 words: the next evaluation takes them from dsgd_lg_nsq_kernel
+    DSGD_TRY(plan_run_lg_cs(c, p, step_begin, step_end, lr));
+  } else {
+    for (long long t = step_begin; t < step_end; ++t) {
+      long long mx = 0;
+      for (int k = 0; k < K; ++k) mx = std::max<long long>(mx, p->offsets[(size_t)(t * K + k + 1)] - p->offsets[(size_t)(t * K + k)]);
+      DSGD_TRY(lg_launch(c, true, K, mx, LG_STEP, lr, p->d_idx, p->d_segs + t * K));
+    }
+    c->lg_nsq_stamp = c->bind_count;   // (the last finish left |w'|^2 in d_lg_part)
   }
-  c->lg_nsq_stamp = c->bind_count;   // (the last finish left |w'|^2 in d_lg_part)
   const long long rows = p->offsets[(size_t)(step_end * K)] - p->offsets[(size_t)(step_begin * K)];
   c->pending_samples += rows;
   c->lg_pending_active += rows;

@@ -255,15 +255,18 @@ inline RangesRoute route_ranges(const Knobs& k, const RouteFacts& f, int n_worke
 struct PlanFacts {
   bool rp64 = false;         // a row-parallel fp64 plan
   bool lg = false;           // a logistic plan (csrc/dsgd_lg_calls.hpp: plan_run_lg)
+  bool lg_cs_current = false;   // ... created with its column slices, and they are laid out for the current column ranking
   bool cs_current = false;   // its column slices are laid out for the current column ranking
   bool fits_here = false;    // every list fits the staged sub-batch of the one-workgroup kernel, on the rows loaded now
   bool vt_current = false;   // its virtual tiles are laid out for the current split streams
   long long max_step_rows = 0;
   int n_workers = 0;
 };
-enum PlanRoute { PLAN_RP64, PLAN_CS64, PLAN_CS, PLAN_ONE_WG, PLAN_VT, PLAN_ROWWISE, PLAN_LG };
+enum PlanRoute { PLAN_RP64, PLAN_CS64, PLAN_CS, PLAN_ONE_WG, PLAN_VT, PLAN_ROWWISE, PLAN_LG, PLAN_LG_CS };
 inline PlanRoute route_plan(const Knobs& k, const RouteFacts& f, const PlanFacts& p) {
-  if (p.lg) return PLAN_LG;   // (the model decides, not a knob: the lists and their ranges only, as PLAN_RP64)
+  // (the model and the entry point that made the plan decide, not a knob: the lists and their ranges only, as PLAN_RP64 --
+  //  or, asked for at creation and current, the logistic column slices of csrc/dsgd_lg_cs.hpp)
+  if (p.lg) return p.lg_cs_current ? PLAN_LG_CS : PLAN_LG;
   if (p.rp64) return PLAN_RP64;
   if ((k.cs_enable || f.fp64) && !f.comm && p.cs_current) return f.fp64 ? PLAN_CS64 : PLAN_CS;
   if (plan_kernel_ok(k, f, p.max_step_rows, p.n_workers) && p.fits_here) return PLAN_ONE_WG;
@@ -274,6 +277,7 @@ inline PlanRoute route_plan(const Knobs& k, const RouteFacts& f, const PlanFacts
 inline int plan_info_code(PlanRoute r, bool layout_tried) {
   switch (r) {
     case PLAN_LG: return 7;
+    case PLAN_LG_CS: return 8;
     case PLAN_RP64: return 6;
     case PLAN_CS64: return 5;
     case PLAN_CS: return 1;

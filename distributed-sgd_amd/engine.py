@@ -32,7 +32,7 @@ class Plan:
         v = (C.c_int32 * 9)()
         check(_lib.load().dsgd_plan_info(self.engine._ctx, self.handle, v, C.c_int32(9)))
         kinds = {0: "not_laid_out", 1: "column_slices", 2: "one_workgroup", 3: "virtual_tiles", 4: "row_parallel", 5: "column_slices_fp64",
-                 6: "row_parallel_fp64", 7: "logistic"}
+                 6: "row_parallel_fp64", 7: "logistic", 8: "logistic_column_slices"}
         return {"kind": kinds.get(int(v[0]), "?"), "slices": int(v[1]), "slot_stride": int(v[2]), "row_stride": int(v[3]),
                 "col_list_stride": int(v[4]), "slots_per_lane": int(v[5]), "device_built": bool(v[6]), "record_words": int(v[7]), "threads": int(v[8])}
 
@@ -467,9 +467,10 @@ class Engine:
         check(self._lib.dsgd_lg_loss_acc_ranges(self._ctx, ptr(wv), rb, re_, C.c_int32(k), ptr(loss), ptr(acc)))
         return [(float(loss[i]), float(acc[i])) for i in range(k)]
 
-    def lg_plan(self, steps):
+    def lg_plan(self, steps, slices=False):
         """A resident LOGISTIC plan (dsgd_plan_create_lg_n) from `steps`: list (per step) of lists (per worker) of index arrays,
-        as Engine.plan takes them.  It runs through plan_run / synchronize; the weights get the bits of lg_sync_steps."""
+        as Engine.plan takes them.  It runs through plan_run / synchronize; the weights get the bits of lg_sync_steps.
+        slices: see lg_plan_flat."""
         n_steps = len(steps)
         n_workers = len(steps[0]) if n_steps else 0
         flat, offs = [], [0]
@@ -481,30 +482,34 @@ class Engine:
                 flat.append(a)
                 offs.append(offs[-1] + len(a))
         idx = np.concatenate(flat) if flat else np.zeros(0, np.int32)
-        return self.lg_plan_flat(idx, np.asarray(offs, dtype=np.int64), n_steps, n_workers)
+        return self.lg_plan_flat(idx, np.asarray(offs, dtype=np.int64), n_steps, n_workers, slices=slices)
 
-    def lg_plan_flat(self, idx, offsets, n_steps, n_workers):
-        """lg_plan from the flat form (what host.epoch_lists returns, what lg_sync_steps takes)."""
+    def lg_plan_flat(self, idx, offsets, n_steps, n_workers, slices=False):
+        """lg_plan from the flat form (what host.epoch_lists returns, what lg_sync_steps takes).
+        slices=True (dsgd_plan_create_lg_cs_n): the plan additionally has its column slices laid out, and plan_run on it is ONE
+        persistent launch (plan_info code 8) -- deterministic and within tests/logistic_cs_bound.py of the fp64 model, but not
+        the bits of lg_sync_steps; where the slices do not apply (include/dsgd.h) it is the plan slices=False makes, code 7."""
         idx = i32(idx)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         if n_steps >= 1 and n_workers >= 1 and len(offsets) != n_steps * n_workers + 1:
             raise ValueError("offsets do not describe %d x %d lists" % (n_steps, n_workers))
         h = C.c_void_p()
-        check(self._lib.dsgd_plan_create_lg_n(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers),
-                                              C.byref(h)))
+        create = self._lib.dsgd_plan_create_lg_cs_n if slices else self._lib.dsgd_plan_create_lg_n
+        check(create(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers), C.byref(h)))
         return Plan(self, h, n_steps, n_workers, int(offsets[-1]))
 
-    def lg_plan_from_seed(self, jstate, split, max_samples, batch_size):
+    def lg_plan_from_seed(self, jstate, split, max_samples, batch_size, slices=False):
         """One epoch of Master.fit as a LOGISTIC plan whose lists the device draws (dsgd_plan_create_from_seed_lg): the
         arguments, the return value -- (plan or None, n_steps, new jstate, draws) -- and the EUNSUPPORTED refusals of
-        plan_from_seed."""
+        plan_from_seed.  slices=True (dsgd_plan_create_from_seed_lg_cs): as in lg_plan_flat; the lists and the state are the same."""
         sb = np.asarray([r.start if isinstance(r, range) else r[0] for r in split], dtype=np.int64)
         se = np.asarray([r.stop if isinstance(r, range) else r[1] for r in split], dtype=np.int64)
         st = C.c_uint64(int(jstate))
         h = C.c_void_p()
         n_steps, draws = C.c_int64(0), C.c_int64(0)
-        check(self._lib.dsgd_plan_create_from_seed_lg(self._ctx, C.byref(st), ptr(sb), ptr(se), C.c_int32(len(sb)), C.c_int64(max_samples),
-                                                      C.c_int32(batch_size), C.byref(h), C.byref(n_steps), C.byref(draws)))
+        create = self._lib.dsgd_plan_create_from_seed_lg_cs if slices else self._lib.dsgd_plan_create_from_seed_lg
+        check(create(self._ctx, C.byref(st), ptr(sb), ptr(se), C.c_int32(len(sb)), C.c_int64(max_samples),
+                     C.c_int32(batch_size), C.byref(h), C.byref(n_steps), C.byref(draws)))
         if not h.value:
             return None, 0, int(st.value), 0
         total = int(sum(min(batch_size, int(e - b) - s_ * batch_size) for s_ in range(n_steps.value) for b, e in zip(sb, se)))

@@ -1151,13 +1151,16 @@ class LogisticSync:
     `prefetch` the next epoch's plan is created while this one runs.  After the epoch train and test loss and accuracy
     come from ONE Engine.lg_loss_acc_ranges call, and the reference's stopping criterion looks at the test losses,
     newest first.  The lists, the weights and the figures are the same bits whichever side drew the lists.
+    `slices` (off by default) asks both plan constructors for the column-slice form (Engine.lg_plan_flat): an epoch is then ONE
+    persistent launch where the slices apply; the lists and the random stream are the same, the weights deterministic but
+    not the bits of the default form.
 
     data layout: rows [0, n_train) are the train set, [n_train, n_rows) the test set (Main.scala:52).
 
     Limits: one engine hosts every worker; no distributed or sampled evaluation, no asynchronous fit, no JNI."""
 
     def __init__(self, backend, n_train: int, n_rows: int, node_count: int, rnd: Optional[JavaRandom] = None, log=None,
-                 metrics: Optional[Metrics] = None, device_lists: Optional[bool] = None, prefetch: bool = True):
+                 metrics: Optional[Metrics] = None, device_lists: Optional[bool] = None, prefetch: bool = True, slices: bool = False):
         if not 0 < n_train < n_rows:
             raise ValueError("LogisticSync needs train rows [0, n_train) and test rows [n_train, n_rows)")
         self.backend, self.n_train, self.n_rows, self.node_count = backend, n_train, n_rows, node_count
@@ -1166,6 +1169,7 @@ class LogisticSync:
         self.log = log or (lambda *a: None)
         self.device_lists = os.environ.get("DSGD_DEVICE_LISTS", "1") != "0" if device_lists is None else bool(device_lists)
         self.prefetch = prefetch
+        self.slices = bool(slices)
         self.losses: List[float] = []
         self.accs: List[float] = []
         self.test_losses: List[float] = []
@@ -1191,7 +1195,8 @@ class LogisticSync:
         seed_before = self.rnd.seed
         if self.device_lists and all(r.step == 1 for r in split):
             try:
-                plan, n_steps, state, _ = self.backend.lg_plan_from_seed(seed_before, split, max_samples, batch_size)
+                kw = {"slices": True} if self.slices else {}   # (a backend without the keyword serves the default)
+                plan, n_steps, state, _ = self.backend.lg_plan_from_seed(seed_before, split, max_samples, batch_size, **kw)
             except Exception as e:   # (DSGD_EUNSUPPORTED: outside the device form -- the host draws from here on)
                 if getattr(e, "code", None) != -7:
                     raise
@@ -1201,7 +1206,8 @@ class LogisticSync:
                 return {"plan": plan, "n_steps": n_steps, "n_samples": plan.n_samples if plan is not None else 0, "seed_before": seed_before,
                         "device_drawn": True}
         idx, offsets, n_steps = epoch_lists(self.rnd, split, max_samples, batch_size)
-        plan = self.backend.lg_plan_flat(idx, offsets, n_steps, len(split)) if n_steps else None
+        kw = {"slices": True} if self.slices else {}
+        plan = self.backend.lg_plan_flat(idx, offsets, n_steps, len(split), **kw) if n_steps else None
         return {"plan": plan, "n_steps": n_steps, "n_samples": int(offsets[n_steps * len(split)]), "seed_before": seed_before, "device_drawn": False}
 
     def _drop_pending(self):

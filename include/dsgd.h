@@ -478,7 +478,8 @@ int dsgd_plan_run_f64(dsgd_ctx* ctx, dsgd_plan* plan, int64_t step_begin, int64_
 /* How a plan will run (nothing in the reference; benchmarks, tests): vals[0] = 1 column slices (dsgd_cs_step_kernel),
  * 2 the one-workgroup kernel, 3 virtual tiles, 4 the row-parallel kernels, 5 fp64 column slices, 6 a row-parallel fp64
  * plan (dsgd_plan_create_rp64_n and its kin: strides 0), 7 a logistic plan (dsgd_plan_create_lg_n, dsgd_plan_create_from_seed_lg:
- * strides 0), 0 not laid out yet; [1] slices, [2..4] slot /
+ * strides 0), 8 a logistic plan on column slices (dsgd_plan_create_lg_cs_n, dsgd_plan_create_from_seed_lg_cs while their
+ * layout is current: dsgd_lg_cs_step_kernel, [1] = 16), 0 not laid out yet; [1] slices, [2..4] slot /
  * row / column-list strides, [5] slots per lane, [6] 1 if the device laid it out, [7] words per step of the record,
  * [8] lanes per slice workgroup (512; 256 where DSGD_CS_NT=256 took: [5] is 2 for that kernel and the wide two-slot one).
  * n <= 9 slots.                                                                                                       */
@@ -929,6 +930,28 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  * dsgd_plan_run_f64, dsgd_plan_run_async_f64, dsgd_plan_record and dsgd_plan_read_record on such a plan
  * (DSGD_EUNSUPPORTED); a plan from before a dsgd_load_csr whose lists no longer fit the rows (DSGD_ERANGE at the run).
  *
+ * COLUMN SLICES (opt-in).  dsgd_plan_create_lg_cs_n and dsgd_plan_create_from_seed_lg_cs take the arguments and make the
+ * checks and refusals of dsgd_plan_create_lg_n and dsgd_plan_create_from_seed_lg; the logistic plan they make additionally
+ * has its column slices laid out (the SVM plans' device builder, on the build stream, into blocks of the plan cache that the
+ * plan owns).  dsgd_plan_run on it is then ONE launch of dsgd_lg_cs_step_kernel for the whole range of steps: 16 persistent
+ * workgroups, each keeping the weights of the frequency ranks r = b (mod 16) and one int64 accumulator per hosted worker and
+ * column in LDS; per step one exchange of the rows' partial x.w through the SVM family's tagged granules (the same bounded
+ * wait: a launch that gives up is reported by dsgd_synchronize as DSGD_ESTATE, the weights as the launch found them), the
+ * scatter of rn(x c 2^(S_k - vexp)) into the accumulators, and dsgd_lg_sync_step's finish on EVERY column of the slice.
+ * dsgd_plan_info: vals[0] = 8; dsgd_grad_kernel_name: "dsgd_lg_cs_step_kernel".
+ *   numerics   x.w is the sum of 16 slice partials (a slot of <= 16 products in sequence, a row's slots in order, the
+ *              slices in order), not the row form's lane order: the weights are NOT the bits of dsgd_lg_sync_steps.  They are
+ *              a function of the lists and the starting weights alone -- the same for one run or the same steps split over
+ *              several, for caller lists or device-drawn ones -- and stay within tests/logistic_cs_bound.py of the fp64 model.
+ *   declines   16 slices need (1 + 2 K) words of LDS per column: at D + 1 = 47,237 that serves K <= 6 hosted workers
+ *              (csrc/dsgd_lg_cs_host.hpp: lg_cs_pick_G).  A plan with more workers, a step of more than 1,024 rows or with more
+ *              than 1,024 slots or 4,096 columns in one slice, a model of fewer than 64 columns, a layout the plan cache
+ *              cannot hold (DSGD_CS_MAX_MB), or a layout from before a dsgd_load_csr: the plan is created and runs all the same,
+ *              as a plan of dsgd_plan_create_lg_n does -- vals[0] = 7, the bits of dsgd_lg_sync_steps.
+ *   state      the run leaves no |w'|^2 words: the next logistic evaluation computes them, as for weights set by the caller.
+ *              The exchange buffer and its tag counter are the SVM slice plans': both kinds may run in turn on one context.
+ *   otherwise  everything RESIDENT PLANS says: n_active == n_samples, dimSparsity not asked for, the same refusals.
+ *
  * dsgd_lg_loss_acc_ranges: dsgd_lg_loss_acc over n_ranges <= 16 row ranges (they may overlap or repeat) in ONE launch
  * with ONE synchronisation -- an epoch's train and test passes.  loss_out[r] and acc_out[r] (either may be NULL) are the
  * bits of dsgd_lg_loss_acc on range r alone: every range has its own workgroups, the grid of a launch of its own.
@@ -947,7 +970,7 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *
  * LIMITS (out of scope, each refused or simply absent): no JNI / Scala binding; the host mirror is host.LogisticSync
  * (Master.fit's flow on one context: no distributed or sampled evaluation, no asynchronous fit; host.MasterSync /
- * MasterAsync stay the SVM's); no fused or persistent one-launch step; no column slices; no asynchronous engine; no fp64
+ * MasterAsync stay the SVM's); no fused or persistent one-launch step and no column slices but those of COLUMN SLICES above; no asynchronous engine; no fp64
  * contexts and no Double feature values; no communicators; no Sparse boundary forms; no predict_ranges.
  *
  * dsgd_lg_gradient: one worker's regularised sum over the listed rows, key order, from the resident weights or from w
@@ -973,6 +996,10 @@ int dsgd_plan_create_lg_n(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, cons
                           int32_t n_workers, dsgd_plan** out);
 int dsgd_plan_create_from_seed_lg(dsgd_ctx* ctx, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
                                   int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out);
+int dsgd_plan_create_lg_cs_n(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const int64_t* offsets /* n_steps * n_workers + 1 */, int64_t n_steps,
+                             int32_t n_workers, dsgd_plan** out);
+int dsgd_plan_create_from_seed_lg_cs(dsgd_ctx* ctx, uint64_t* jstate, const int64_t* split_begin, const int64_t* split_end, int32_t n_splits,
+                                     int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out);
 int dsgd_lg_loss_acc_ranges(dsgd_ctx* ctx, const float* w /* NULL = resident */, const int64_t* row_begin, const int64_t* row_end, int32_t n_ranges,
                             double* loss_out /* n_ranges */, double* acc_out /* n_ranges */);
 

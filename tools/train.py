@@ -4,7 +4,7 @@ loss and accuracy, fit (sync or async, early stopping by patience / conv-delta),
 accuracy -- with the HIP engine hosting all the workers.
 
     DSGD_DATA_PATH=/data/rcv1 python tools/train.py [--conf application.conf] [--synthetic ROWS] [--device 0] [--weights-out w.txt]
-                                                    [--precision fp64] [--f64-rp-plans] [--model logistic [--lg-plans]]
+                                                    [--precision fp64] [--f64-rp-plans] [--model logistic [--lg-plans | --lg-slices]]
 
 --precision fp64: the engine keeps the reference's Double weights (include/dsgd.h "THE FP64 MODE"); an async fit runs the
 zero-lag schedule of host.MasterAsync (one update at a time, every update seen by every worker).
@@ -19,6 +19,8 @@ reports train and test log-loss and accuracy.  The default model is the SVM, and
 --lg-plans (with --model logistic): Master.fit's flow instead (host.LogisticSync) -- the lists drawn from the reference's random
 stream, by the device where it can; an epoch as ONE resident logistic plan, the next one created while it runs; train and test
 evaluated in one launch; the reference's early stopping (patience / conv-delta) over the test losses.
+--lg-slices (implies --lg-plans): the plans additionally get their column slices -- an epoch is ONE persistent launch where they
+apply (include/dsgd.h "THE LOGISTIC MODEL", COLUMN SLICES; up to 6 workers at RCV1's width, batches up to 1,024 rows in all).
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,7 +37,9 @@ ap.add_argument("--precision", choices=("fp32", "fp64"), default="fp32", help="f
 ap.add_argument("--f64-rp-plans", action="store_true", help="fp64: refused plans run as row-parallel plans, under a communicator too: one plan run per epoch and rank (DSGD_F64_RP_PLANS=1)")
 ap.add_argument("--model", choices=("svm", "logistic"), default="svm", help="logistic: log-loss, probabilities, plain L2 (fp32, synchronous)")
 ap.add_argument("--lg-plans", action="store_true", help="logistic: Master.fit's flow on resident logistic plans (host.LogisticSync)")
+ap.add_argument("--lg-slices", action="store_true", help="logistic: --lg-plans on column slices, one persistent launch per epoch (host.LogisticSync(slices=True))")
 a = ap.parse_args()
+a.lg_plans = a.lg_plans or a.lg_slices
 if a.lg_plans and a.model != "logistic":
     ap.error("--lg-plans goes with --model logistic")
 if a.model == "logistic" and a.precision != "fp32":
@@ -92,7 +96,7 @@ with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device, precision=a.precisi
     if a.model == "logistic":   # (its own loop; dimSparsity plays no part)
         eng.set_weights(np.zeros(data.dim + 1, dtype=np.float32))
         if a.lg_plans:
-            master = host.LogisticSync(eng, n_train, data.n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log, metrics=metrics)
+            master = host.LogisticSync(eng, n_train, data.n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log, metrics=metrics, slices=a.lg_slices)
             log("initial loss: {}", master.local_loss())
             log("initial accuracy: {}", master.local_accuracy())
             t0 = time.time()
