@@ -526,9 +526,14 @@ struct dsgd_ctx {
   // (lg_finish_blocks words) followed by the evaluation's per-workgroup loss sums (n_cu words), an epoch's list ranges, the
   // probabilities.  bind_count numbers the entry points' binds: the |w|^2 words describe the resident weights while no other
   // entry point has bound since the logistic call that left them (lg_nsq_stamp: that call's number).
+  // Across ranks (dsgd_comm_init_lg sets comm_lg; csrc/dsgd_lg_gather.hpp): d_lg_acc also holds, in front of the lg_k slots, the
+  // agreement record of lg_world ranks and one header word per slot; h_lg_rec is the pinned copy of the record.
   DevBuf<unsigned long long> d_lg_acc;
   long long lg_stride = 0;
   int lg_k = 0;
+  int lg_world = 1;
+  bool comm_lg = false;
+  HostBuf<long long> h_lg_rec;
   DevBuf<float> d_lg_g;
   DevBuf<double> d_lg_part;
   DevBuf<unsigned long long> d_lg_tally;   // dsgd_lg_loss_acc_ranges: [LG_MAX_RANGES][LG_TALLY_WORDS] class tallies, one set per range
@@ -2890,7 +2895,8 @@ int dsgd_synchronize(dsgd_ctx* c, dsgd_batch_stats* stats) {
   DSGD_TRY(bind(c, true));
   DSGD_TRY(read_scalars(c));
   DSGD_TRY(prof_collect(c));
-  const long long act = (long long)c->h_sc->n_active + c->lg_pending_active;   // (a logistic plan's rows: all of them active)
+  // (a logistic plan's rows: all of them active -- across ranks they are the job's, counted by the device in n_samples)
+  const long long act = (long long)c->h_sc->n_active + c->lg_pending_active + (c->job_pending && !c->fp64 ? (long long)c->h_sc->n_samples : 0);
   const int err = c->h_sc->err;
   const long long pending = c->pending_samples + (c->job_pending ? (long long)c->h_sc->n_samples : 0);
   c->pending_samples = 0;   // (whatever the outcome: the rows of a rejected run are not carried into the next report)
@@ -3011,7 +3017,10 @@ static PlanRoute plan_route(const dsgd_ctx* c, const dsgd_plan* p) {
 }
 static int cs64_refused(dsgd_ctx* c);   // (dsgd_fp64_host.hpp, which in turn needs plan_finish: the one declaration ahead)
 // (csrc/dsgd_lg_calls.hpp, behind the plans' entry points that dispatch into it: a logistic plan's refusals and its run)
-static int lg_refuse(dsgd_ctx* c, const char* what);
+// What a logistic call is to a communicator attached with dsgd_comm_init_lg (include/dsgd.h "ACROSS RANKS"): a step that spans
+// the ranks (collective), a call that stays on the shard, or one that is refused.  Under any other communicator: all refused.
+enum LgScope { LG_SPANS, LG_STAYS_LOCAL, LG_ONE_PROCESS };
+static int lg_refuse(dsgd_ctx* c, const char* what, LgScope scope);
 static int plan_run_lg(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, float lr);
 // the lists are in p->d_idx (enqueued on the build stream): lay the plan out for the device, close its set-up
 static int plan_finish(dsgd_ctx* c, dsgd_plan* p, dsgd_plan** out) {
@@ -4659,6 +4668,42 @@ int dsgd_comm_init_f64v(dsgd_ctx* c, const char* unique_id, int32_t world_size, 
   return comm_init_f64_impl(c, unique_id, world_size, rank, true, "dsgd_comm_init_f64v");
 }
 
+// The communicator the LOGISTIC model's steps span (include/dsgd.h "THE LOGISTIC MODEL -- ACROSS RANKS"): attached as
+// dsgd_comm_init attaches it -- the SVM's entry points behave as under that call -- and additionally comm_lg, which lets the
+// logistic steps through (lg_refuse).  Loaded data is ranked again at once, so that the ranks share ONE column ranking whatever
+// the order of load and attach (data loaded later: at its first use).
+int dsgd_comm_init_lg(dsgd_ctx* c, const char* unique_id, int32_t world_size, int32_t rank) {
+  DSGD_TRY(check_ctx(c));
+  DSGD_TRY(refuse_fp64(c, "dsgd_comm_init_lg"));
+  if (!unique_id || world_size < 1 || rank < 0 || rank >= world_size) return fail(DSGD_EINVAL, "bad communicator arguments");
+  if (world_size > LGG_MAX_WORLD) return fail(DSGD_EUNSUPPORTED, "at most %d ranks", LGG_MAX_WORLD);
+  if (!rccl::available()) return fail(DSGD_ERCCL, "librccl could not be loaded");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(bind(c));   // (rank order: the ranking may be about to change)
+  DSGD_TRY(require_sync_mode(c));
+  if (c->comm) return fail(DSGD_ESTATE, "communicator already attached");
+  rccl::unique_id_t id;
+  memcpy(id.internal, unique_id, DSGD_UNIQUE_ID_BYTES);
+  RCCL_TRY(rccl::CommInitRank(&c->comm, world_size, id, rank));
+  c->comm_broken = false;
+  c->world = world_size;
+  c->rank = rank;
+  c->comm_lg = true;
+  const int rc = c->d_row_ptr ? relayout(c) : DSGD_OK;
+  if (rc != DSGD_OK) {
+    char msg[sizeof(g_err)];
+    snprintf(msg, sizeof(msg), "%s", g_err);
+    (void)hipStreamSynchronize(c->stream);
+    (void)rccl::CommDestroy(c->comm);
+    c->comm = nullptr;
+    c->comm_lg = false;
+    c->world = 1;
+    c->rank = 0;
+    return fail(rc, "%s", msg);
+  }
+  return DSGD_OK;
+}
+
 int dsgd_comm_destroy(dsgd_ctx* c) {
   DSGD_TRY(check_ctx(c));
   std::lock_guard<std::mutex> lk(c->mu);
@@ -4669,6 +4714,7 @@ int dsgd_comm_destroy(dsgd_ctx* c) {
   c->comm_broken = false;   // (an aborted communicator is gone already: the context may attach a new one)
   if (!c->comm) {
     c->comm_v64 = false;
+    c->comm_lg = false;
     c->world = 1;
     c->rank = 0;
     return DSGD_OK;
@@ -4677,6 +4723,7 @@ int dsgd_comm_destroy(dsgd_ctx* c) {
   RCCL_TRY(rccl::CommDestroy(c->comm));
   c->comm = nullptr;
   c->comm_v64 = false;
+  c->comm_lg = false;
   c->world = 1;
   c->rank = 0;
   return DSGD_OK;

@@ -5,17 +5,21 @@
 // Every check runs on the host before anything of the call is enqueued: a refused call leaves the weights, the accumulators
 // and the context's flags as they were.  Every call returns behind its kernels (ONE synchronisation).
 
-static int lg_refuse(dsgd_ctx* c, const char* what) {
+// (LgScope: csrc/dsgd_hip.hip, in front of the plans' entry points)
+static int lg_refuse(dsgd_ctx* c, const char* what, LgScope scope) {
   if (c->fp64)
     return fail(DSGD_EUNSUPPORTED, "%s is not available in an fp64 context: the logistic model runs on the fp32 engine's weights and dot", what);
-  if (c->comm)
-    return fail(DSGD_EUNSUPPORTED, "%s is not available with a communicator attached: the logistic model's steps do not span ranks", what);
+  if (c->comm && !c->comm_lg)
+    return fail(DSGD_EUNSUPPORTED, "%s is not available with a communicator attached: the logistic model's steps do not span ranks "
+                                   "(dsgd_comm_init_lg attaches one they span)", what);
+  if (c->comm && scope == LG_ONE_PROCESS)
+    return fail(DSGD_EUNSUPPORTED, "%s is not available with a communicator attached: device-drawn lists and column slices do not span ranks", what);
   return DSGD_OK;
 }
 // what every call asks first (locked): the mode, the device, the data, the engine
 // (keep_sliced: a plan on column slices keeps the weights slice-major between its runs, as the SVM's -- bind)
-static int lg_enter(dsgd_ctx* c, const char* what, bool* nsq_fresh, bool keep_sliced = false) {
-  DSGD_TRY(lg_refuse(c, what));
+static int lg_enter(dsgd_ctx* c, const char* what, LgScope scope, bool* nsq_fresh, bool keep_sliced = false) {
+  DSGD_TRY(lg_refuse(c, what, scope));
   DSGD_TRY(bind(c, keep_sliced));
   *nsq_fresh = c->lg_nsq_stamp + 1 == c->bind_count;   // (no other entry point has bound since the logistic call that left |w|^2)
   DSGD_TRY(require_data(c));
@@ -37,62 +41,151 @@ static int lg_report(dsgd_ctx* c, const char* what, const LgCheck& v, int n_work
   return fail(DSGD_ERANGE, "%s: row %lld (worker %lld, position %lld) is outside the %lld loaded rows", what, v.value, v.worker, v.pos, c->n_rows);
 }
 
+static void lg_drop(dsgd_ctx* c) {   // (after a failure half way: the next call starts from a zeroed buffer)
+  (void)hipStreamSynchronize(c->stream);
+  c->d_lg_acc.reset();
+  c->lg_k = 0;
+}
+// room for n_workers hosted workers: under dsgd_comm_init_lg's communicator the slots of every rank's (csrc/dsgd_lg_gather.hpp)
 static int lg_ensure(dsgd_ctx* c, int n_workers) {
   DSGD_TRY(c->d_lg_g.reserve((size_t)c->dp));
   // (the |w|^2 words, then one word per evaluation workgroup: up to LG_MAX_RANGES ranges of n_cu workgroups each)
   DSGD_TRY(c->d_lg_part.reserve((size_t)lg_finish_blocks(c->dp) + (size_t)c->n_cu * LG_MAX_RANGES));
   DSGD_TRY(c->d_lg_tally.reserve((size_t)LG_MAX_RANGES * LG_TALLY_WORDS));
-  if (c->lg_k < n_workers) {   // (zeroed once; every finish leaves them zeroed)
+  const int world = c->comm && c->comm_lg ? c->world : 1;
+  if (n_workers > 0x7fffffff / LGG_MAX_WORLD) return fail(DSGD_EINVAL, "%d workers: too many", n_workers);
+  const int need = n_workers * world;
+  if (c->lg_k < need || c->lg_world != world || !c->d_lg_acc) {   // (zeroed once; every finish leaves the slots zeroed)
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->lg_k = 0;
-    const long long stride = ((long long)c->dp + 63) & ~63LL;
-    const int cap = std::max(n_workers, 4);
-    DSGD_TRY(c->d_lg_acc.alloc((size_t)stride * (size_t)cap));
-    HIP_TRY(hipMemsetAsync(c->d_lg_acc, 0, sizeof(unsigned long long) * (size_t)stride * (size_t)cap, c->stream));
-    c->lg_stride = stride;
+    const int cap = std::max(need, 4);
+    const size_t words = (size_t)lgg_total_words(world, cap, c->dp);
+    DSGD_TRY(c->d_lg_acc.alloc(words));
+    HIP_TRY(hipMemsetAsync(c->d_lg_acc, 0, sizeof(unsigned long long) * words, c->stream));
+    c->lg_stride = lgg_stride(c->dp);
     c->lg_k = cap;
+    c->lg_world = world;
   }
   return DSGD_OK;
 }
 
-// the finish behind a gradient launch of either form (row-wise or by column lists): one column per lane
-static int lg_launch_finish(dsgd_ctx* c, int K, int mode, float lr, const WorkSeg* segs) {
+// Whose slots a call's launches sum into and what its finish folds: the context's own k workers on its own vexp (lg_local), or
+// across ranks this rank's block of the K = k * world slots, the call's agreed vexp and the gathered finish (lg_agree).
+struct LgCall {
+  bool ranks = false;
+  int k = 0, K = 0, vexp = 0;
+  unsigned long long* own = nullptr;   // the first slot of this rank's workers
+  unsigned long long* all = nullptr;   // slot 0
+  unsigned long long* hdr = nullptr;   // ranks: the K header words of a step
+};
+static LgCall lg_local(dsgd_ctx* c, int k) {   // (lg_ensure came first)
+  LgCall q;
+  q.k = q.K = k;
+  q.vexp = c->vexp;
+  q.own = q.all = c->d_lg_acc + lgg_slots_at(c->lg_world, c->lg_k);
+  return q;
+}
+// The agreement of a collective call (lg_ensure(c, k) came first; every local check has passed; nothing of the call is enqueued):
+// this rank's k, steps and vexp into its words of the zeroed record, the record all-reduced, read back and zeroed again -- the
+// call's one extra host read.  Ranks that differ in k or in the steps ALL return DSGD_EINVAL here.
+static int lg_agree(dsgd_ctx* c, const char* what, int k, long long steps, LgCall* q) {
+  *q = lg_local(c, k);
+  if (!c->comm || !c->comm_lg) return DSGD_OK;
+  const int W = c->world;
+  DSGD_TRY(c->h_lg_rec.reserve((size_t)LGG_MAX_WORLD * LGG_REC_WORDS));
+  long long* h = c->h_lg_rec;
+  long long* mine = h + lgg_record_at(c->rank);
+  mine[LGG_REC_K] = k;
+  mine[LGG_REC_STEPS] = steps;
+  mine[LGG_REC_VEXP] = c->vexp;
+  unsigned long long* rec = c->d_lg_acc;
+  const size_t rec_bytes = sizeof(unsigned long long) * (size_t)W * LGG_REC_WORDS;
+  // (any failure from here to the read may leave the record non-zero: the buffer goes, the next call starts from a zeroed one)
+  hipError_t he = hipMemcpyAsync(rec + lgg_record_at(c->rank), mine, sizeof(long long) * LGG_REC_WORDS, hipMemcpyHostToDevice, c->stream);
+  if (he == hipSuccess) {
+    const int r = rccl::AllReduce(rec, rec, (size_t)W * LGG_REC_WORDS, rccl::kInt64, rccl::kSum, c->comm, c->stream);
+    if (r) {
+      lg_drop(c);
+      return fail(DSGD_ERCCL, "%s: ncclAllReduce(the call's agreement): %s", what, rccl::GetErrorString(r));
+    }
+    he = hipMemcpyAsync(h, rec, rec_bytes, hipMemcpyDeviceToHost, c->stream);
+  }
+  if (he == hipSuccess) he = hipMemsetAsync(rec, 0, rec_bytes, c->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+  if (he != hipSuccess) {
+    lg_drop(c);
+    return fail(DSGD_EHIP, "%s: the call's agreement: %s (nothing ran, the weights are unchanged)", what, hipGetErrorString(he));
+  }
+  const LggVerdict v = lgg_judge(h, W, c->rank);
+  if (v.fault == LGG_K_DIFFERS)
+    return fail(DSGD_EINVAL, "%s: rank %d hosts %lld workers, this rank (%d) %d: every rank of a step hosts the same number (nothing ran, "
+                             "the weights are unchanged)", what, v.bad_rank, v.theirs, c->rank, k);
+  if (v.fault == LGG_STEPS_DIFFER)
+    return fail(DSGD_EINVAL, "%s: rank %d runs %lld steps, this rank (%d) %lld: every rank of a call runs the same number (nothing ran, "
+                             "the weights are unchanged)", what, v.bad_rank, v.theirs, c->rank, steps);
+  q->ranks = true;
+  q->K = k * W;
+  q->vexp = v.vexp;   // (the call's only: c->vexp stays the shard's own, for the SVM and the local calls)
+  q->own = q->all + lgg_global_worker(c->rank, k, 0) * c->lg_stride;
+  q->hdr = c->d_lg_acc + lgg_step_header_at(W, c->lg_k, q->K);
+  return DSGD_OK;
+}
+
+// The finish behind a gradient launch of either form (row-wise or by column lists): one column per lane.  Across ranks first
+// the step's header words, then ONE in-place all-reduce over the header block and the K slots (cut at LGG_MSG_WORDS), then the
+// gathered finish over every rank's workers.
+static int lg_launch_finish(dsgd_ctx* c, const LgCall& q, int mode, float lr, const WorkSeg* segs) {
   const dim3 th(LG_THREADS);
   LgFinishArgs f;
-  f.acc = c->d_lg_acc;
+  f.acc = q.all;
   f.acc_stride = c->lg_stride;
   f.segs = segs;
-  f.K = K;
+  f.K = q.K;
   f.dp = c->dp;
-  f.vexp = c->vexp;
+  f.vexp = q.vexp;
   f.perm = c->d_perm;
   f.g_out = c->d_lg_g;
   f.w = c->d_w;
   f.lr = (double)lr;
   f.lambda = c->cfg.lambda;
   f.nsq_part = c->d_lg_part;
+  f.hdr = q.hdr;
+  f.sc = c->d_sc;
   const dim3 fg((unsigned)lg_finish_blocks(c->dp));
-  if (mode == LG_STEP)
+  if (q.ranks) {
+    if (mode != LG_STEP) return fail(DSGD_ESTATE, "internal: a gradient across ranks");
+    hipLaunchKernelGGL(dsgd_lg_header_kernel, dim3(1), th, 0, c->stream, q.hdr, q.K, (int)lgg_global_worker(c->rank, q.k, 0), q.k, segs);
+    HIP_TRY(hipGetLastError());
+    const long long words = lgg_step_words(c->dp, q.K);   // (the slots follow the step's header words: one run of words)
+    for (long long off = 0; off < words; off += LGG_MSG_WORDS) {
+      unsigned long long* at = q.hdr + off;
+      const int r = rccl::AllReduce(at, at, (size_t)std::min<long long>(LGG_MSG_WORDS, words - off), rccl::kInt64, rccl::kSum, c->comm, c->stream);
+      if (r) return fail(DSGD_ERCCL, "ncclAllReduce(the workers' sums): %s", rccl::GetErrorString(r));
+    }
+    hipLaunchKernelGGL((dsgd_lg_finish_kernel<LG_STEP, true>), fg, th, 0, c->stream, f);
+  } else if (mode == LG_STEP) {
     hipLaunchKernelGGL(dsgd_lg_finish_kernel<LG_STEP>, fg, th, 0, c->stream, f);
-  else
+  } else {
     hipLaunchKernelGGL(dsgd_lg_finish_kernel<LG_GRADIENT>, fg, th, 0, c->stream, f);
+  }
   HIP_TRY(hipGetLastError());
   return DSGD_OK;
 }
-// The two launches of one worker's gradient (LG_GRADIENT) or of a step (LG_STEP) over K lists of positions in `idx` (list) or
-// K row ranges (segs hold the rows), the longest of `longest` rows.  lg_ensure came first.
-static int lg_launch(dsgd_ctx* c, bool list, int K, long long longest, int mode, float lr, const int* idx, const WorkSeg* segs) {
+// The two launches of one worker's gradient (LG_GRADIENT) or of a step (LG_STEP) over q.k lists of positions in `idx` (list) or
+// q.k row ranges (segs hold the rows), the longest of `longest` rows.  lg_ensure and lg_agree (or lg_local) came first.
+static int lg_launch(dsgd_ctx* c, bool list, const LgCall& q, long long longest, int mode, float lr, const int* idx, const WorkSeg* segs) {
+  const int K = q.k;
   LgArgs a;
   a.w = c->d_w;
   a.dp = c->dp;
-  a.vexp = c->vexp;
+  a.vexp = q.vexp;
   a.K = K;
   a.idx = idx;
   a.segs = segs;
   // lists: two workgroups per compute unit at the most, as the fp64 row-parallel family (each flushes its LDS head once);
   // ranges are long streams of rows: four, for the loads in flight
   a.blocks_per_worker = lg_blocks_per_worker(longest, K, c->n_cu, list ? 2 : 4);
-  a.acc = c->d_lg_acc;
+  a.acc = q.own;
   a.acc_stride = c->lg_stride;
   a.sc = c->d_sc;
   const dim3 gg((unsigned)(a.blocks_per_worker * K)), th(LG_THREADS);
@@ -103,16 +196,36 @@ static int lg_launch(dsgd_ctx* c, bool list, int K, long long longest, int mode,
     hipLaunchKernelGGL(dsgd_lg_grad_range_kernel, gg, th, 0, c->stream, m, a);
   HIP_TRY(hipGetLastError());
   c->last_grad_kernel = list ? "dsgd_lg_grad_kernel" : "dsgd_lg_grad_range_kernel";
-  return lg_launch_finish(c, K, mode, lr, segs);
+  return lg_launch_finish(c, q, mode, lr, segs);
+}
+// Behind the last step of a call across ranks: the header words go, BEHIND the finish on the stream (never by a finish workgroup
+// while others still read them).  rc: what the steps' enqueueing returned -- a failure half way drops the buffer.
+static int lg_steps_end(dsgd_ctx* c, const LgCall& q, int rc) {
+  if (!q.ranks) return rc;
+  if (rc == DSGD_OK) {
+    const hipError_t e = hipMemsetAsync(q.hdr, 0, sizeof(unsigned long long) * (size_t)q.K, c->stream);
+    if (e != hipSuccess) rc = fail(DSGD_EHIP, "clearing the header words: %s", hipGetErrorString(e));
+  }
+  if (rc != DSGD_OK) {
+    char msg[sizeof(g_err)];
+    snprintf(msg, sizeof(msg), "%s", g_err);
+    lg_drop(c);
+    return fail(rc, "%s (the weights are those behind the last completed step)", msg);
+  }
+  return DSGD_OK;
 }
 // behind a step's launches: the weights moved (the SVM's s and |w|^2 are stale), |w|^2 of the new ones is in d_lg_part; the
-// one synchronisation; every row contributes
-static int lg_step_done(dsgd_ctx* c, dsgd_batch_stats* stats, long long total) {
+// one synchronisation; every row contributes.  Across ranks the rows are the JOB's, counted by the gathered finishes of the
+// call's `counted_steps` steps (a call that reports one step's rows divides).
+static int lg_step_done(dsgd_ctx* c, const LgCall& q, dsgd_batch_stats* stats, long long total, long long counted_steps = 1) {
   c->s_dirty = true;
   c->lg_nsq_stamp = c->bind_count;
   const int rc = finish_stats(c, stats, total);
   if (rc != DSGD_OK) c->lg_nsq_stamp = ~0ull - 1;
-  if (rc == DSGD_OK && stats) stats->n_active = total;
+  if (rc == DSGD_OK && stats) {
+    if (q.ranks) stats->n_samples = (int64_t)(c->h_sc->n_samples / (unsigned long long)counted_steps);
+    stats->n_active = stats->n_samples;
+  }
   return rc;
 }
 
@@ -124,7 +237,7 @@ int dsgd_plan_create_lg_n(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const 
   if (!idx || !offsets || !out || n_steps < 1 || n_workers < 1 || n_idx < 1)
     return fail(DSGD_EINVAL, "dsgd_plan_create_lg_n: bad arguments (null pointers, no steps, no workers or no rows)");
   std::lock_guard<std::mutex> lk(c->mu);
-  DSGD_TRY(lg_refuse(c, "dsgd_plan_create_lg_n"));
+  DSGD_TRY(lg_refuse(c, "dsgd_plan_create_lg_n", LG_SPANS));
   DSGD_TRY(bind(c, true));   // (nothing here touches w: slice-major weights stay as they are)
   DSGD_TRY(require_data(c));
   const LgCheck v = lg_check_flat(idx, n_idx, offsets, n_steps, n_workers, c->n_rows);
@@ -172,6 +285,10 @@ int dsgd_plan_create_lg_cs_n(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, con
                              dsgd_plan** out) {
   DSGD_TRY(check_ctx(c));
   if (!out) return fail(DSGD_EINVAL, "dsgd_plan_create_lg_cs_n: bad arguments (null pointers, no steps, no workers or no rows)");
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    DSGD_TRY(lg_refuse(c, "dsgd_plan_create_lg_cs_n", LG_ONE_PROCESS));
+  }
   dsgd_plan* p = nullptr;
   DSGD_TRY(dsgd_plan_create_lg_n(c, idx, n_idx, offsets, n_steps, n_workers, &p));
   const int rc = lg_plan_add_slices(c, p);
@@ -264,7 +381,7 @@ static int plan_run_lg_cs(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long 
 // before the first launch.  dsgd_synchronize reports the rows (every row contributes: n_active == n_samples).
 static int plan_run_lg(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, float lr) {
   bool fresh = false;
-  DSGD_TRY(lg_enter(c, "dsgd_plan_run (a logistic plan)", &fresh, p->lg_cs));
+  DSGD_TRY(lg_enter(c, "dsgd_plan_run (a logistic plan)", p->lg_cs ? LG_ONE_PROCESS : LG_SPANS, &fresh, p->lg_cs));
   DSGD_TRY(plan_revalidate(c, p));   // (a plan from before the last load: DSGD_ERANGE here, before anything is enqueued)
   DSGD_TRY(prepare_layout(c));
   const int K = p->n_workers;
@@ -276,22 +393,31 @@ static int plan_run_lg(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long lon
     HIP_TRY(hipStreamWaitEvent(c->stream, p->built_ev, 0));
     p->built_pending = false;
   }
+  LgCall q;
+  if (!slices) DSGD_TRY(lg_agree(c, "dsgd_plan_run (a logistic plan)", K, std::max<long long>(0, step_end - step_begin), &q));   // (an empty run takes part)
   if (step_end <= step_begin) {
     if (fresh) c->lg_nsq_stamp = c->bind_count;   // (the weights are the ones |w|^2 was taken from)
     return DSGD_OK;
   }
   c->s_dirty = true;
   c->lg_nsq_stamp = ~0ull - 1;
+  if (q.ranks && !c->job_pending) {   // (the job's rows run on from zero in n_samples until dsgd_synchronize, as the fp64 plans')
+    HIP_TRY(hipMemsetAsync(&c->d_sc->n_samples, 0, sizeof(unsigned long long), c->stream));
+    c->job_pending = true;
+  }
   if (slices) {   // ONE launch; it leaves no |w'|^2 words: the next evaluation takes them from dsgd_lg_nsq_kernel
     DSGD_TRY(plan_run_lg_cs(c, p, step_begin, step_end, lr));
   } else {
-    for (long long t = step_begin; t < step_end; ++t) {
+    int rc = DSGD_OK;
+    for (long long t = step_begin; t < step_end && rc == DSGD_OK; ++t) {
       long long mx = 0;
       for (int k = 0; k < K; ++k) mx = std::max<long long>(mx, p->offsets[(size_t)(t * K + k + 1)] - p->offsets[(size_t)(t * K + k)]);
-      DSGD_TRY(lg_launch(c, true, K, mx, LG_STEP, lr, p->d_idx, p->d_segs + t * K));
+      rc = lg_launch(c, true, q, mx, LG_STEP, lr, p->d_idx, p->d_segs + t * K);
     }
+    DSGD_TRY(lg_steps_end(c, q, rc));
     c->lg_nsq_stamp = c->bind_count;   // (the last finish left |w'|^2 in d_lg_part)
   }
+  if (q.ranks) return DSGD_OK;   // (the device counts the job's rows)
   const long long rows = p->offsets[(size_t)(step_end * K)] - p->offsets[(size_t)(step_begin * K)];
   c->pending_samples += rows;
   c->lg_pending_active += rows;
@@ -304,7 +430,7 @@ int dsgd_lg_gradient(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n,
   if (n < 1 || !idx) return fail(DSGD_EINVAL, "dsgd_lg_gradient: Cannot sum an empty list of vectors");
   std::lock_guard<std::mutex> lk(c->mu);
   bool fresh = false;
-  DSGD_TRY(lg_enter(c, "dsgd_lg_gradient", &fresh));
+  DSGD_TRY(lg_enter(c, "dsgd_lg_gradient", LG_STAYS_LOCAL, &fresh));
   const int64_t nn = n;
   const LgCheck v = lg_check_lists(&idx, &nn, 1, c->n_rows);
   DSGD_TRY(lg_report(c, "dsgd_lg_gradient", v, 1));
@@ -314,7 +440,7 @@ int dsgd_lg_gradient(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n,
   DSGD_TRY(reset_counters(c));
   long long mx = 0, tot = 0;
   DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
-  DSGD_TRY(lg_launch(c, true, 1, mx, LG_GRADIENT, 0.0f, c->cur_idx, c->d_segs));
+  DSGD_TRY(lg_launch(c, true, lg_local(c, 1), mx, LG_GRADIENT, 0.0f, c->cur_idx, c->d_segs));
   const size_t bytes = sizeof(float) * (size_t)c->dp;
   DSGD_TRY(pin_acquire(c->pin_out, bytes));
   HIP_TRY(hipMemcpyAsync(c->pin_out.p, c->d_lg_g, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -331,16 +457,18 @@ int dsgd_lg_sync_step(dsgd_ctx* c, const int32_t* const* idx_per_worker, const i
   if (n_workers < 1 || !idx_per_worker || !n_per_worker) return fail(DSGD_EINVAL, "dsgd_lg_sync_step: Cannot sum an empty list of vectors (no workers)");
   std::lock_guard<std::mutex> lk(c->mu);
   bool fresh = false;
-  DSGD_TRY(lg_enter(c, "dsgd_lg_sync_step", &fresh));
+  DSGD_TRY(lg_enter(c, "dsgd_lg_sync_step", LG_SPANS, &fresh));
   const LgCheck v = lg_check_lists(idx_per_worker, n_per_worker, n_workers, c->n_rows);
   DSGD_TRY(lg_report(c, "dsgd_lg_sync_step", v, n_workers));
   DSGD_TRY(prepare_layout(c));
   DSGD_TRY(lg_ensure(c, n_workers));
+  LgCall q;
+  DSGD_TRY(lg_agree(c, "dsgd_lg_sync_step", n_workers, 1, &q));
   DSGD_TRY(reset_counters(c));
   long long mx = 0, tot = 0;
   DSGD_TRY(stage_lists(c, idx_per_worker, n_per_worker, n_workers, &mx, &tot));
-  DSGD_TRY(lg_launch(c, true, n_workers, mx, LG_STEP, lr, c->cur_idx, c->d_segs));
-  return lg_step_done(c, stats, tot);
+  DSGD_TRY(lg_steps_end(c, q, lg_launch(c, true, q, mx, LG_STEP, lr, c->cur_idx, c->d_segs)));
+  return lg_step_done(c, q, stats, tot);
 }
 
 // the row ranges of a whole-split call as the WorkSegs in c->d_segs
@@ -357,15 +485,17 @@ int dsgd_lg_sync_step_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_
   if (n_workers < 1 || !row_begin || !row_end) return fail(DSGD_EINVAL, "dsgd_lg_sync_step_ranges: Cannot sum an empty list of vectors (no workers)");
   std::lock_guard<std::mutex> lk(c->mu);
   bool fresh = false;
-  DSGD_TRY(lg_enter(c, "dsgd_lg_sync_step_ranges", &fresh));
+  DSGD_TRY(lg_enter(c, "dsgd_lg_sync_step_ranges", LG_SPANS, &fresh));
   const LgCheck v = lg_check_ranges(row_begin, row_end, n_workers, c->n_rows);
   DSGD_TRY(lg_report(c, "dsgd_lg_sync_step_ranges", v, n_workers));
   DSGD_TRY(prepare_layout(c));
   DSGD_TRY(lg_ensure(c, n_workers));
+  LgCall q;
+  DSGD_TRY(lg_agree(c, "dsgd_lg_sync_step_ranges", n_workers, 1, &q));
   DSGD_TRY(reset_counters(c));
   DSGD_TRY(lg_upload_ranges(c, row_begin, row_end, n_workers));
-  DSGD_TRY(lg_launch(c, false, n_workers, v.longest, LG_STEP, lr, nullptr, c->d_segs));
-  return lg_step_done(c, stats, v.total);
+  DSGD_TRY(lg_steps_end(c, q, lg_launch(c, false, q, v.longest, LG_STEP, lr, nullptr, c->d_segs)));
+  return lg_step_done(c, q, stats, v.total);
 }
 
 // ---- whole-split steps by column lists (csrc/dsgd_lg_cols.hpp; the sizes: csrc/dsgd_lg_cols_host.hpp) ----
@@ -417,10 +547,11 @@ static int lgc_layout(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_
   return DSGD_OK;
 }
 // the three launches of one step over the ranges in c->d_segs, by their layout
-static int lgc_launch(dsgd_ctx* c, const dsgd_ctx::LgColsLayout& L, int K, long long longest, float lr) {
+static int lgc_launch(dsgd_ctx* c, const LgCall& call, const dsgd_ctx::LgColsLayout& L, long long longest, float lr) {
+  const int K = call.k;
   LgcCoefArgs q;
   q.w = c->d_w;
-  q.vexp = c->vexp;
+  q.vexp = call.vexp;
   q.K = K;
   q.segs = c->d_segs;
   q.pos_base = L.d_pos_base;
@@ -434,13 +565,13 @@ static int lgc_launch(dsgd_ctx* c, const dsgd_ctx::LgColsLayout& L, int K, long 
   g.shares = L.d_shares;
   g.slot_of_cid = L.d_slot_of_cid;
   g.cq = L.d_cq;
-  g.acc = c->d_lg_acc;
+  g.acc = call.own;   // (the layout's words are `worker * lg_stride + column` from here)
   g.n_ent = L.n_ent;
   g.share = L.share;
   hipLaunchKernelGGL(dsgd_lg_cgrad_kernel, dim3((unsigned)L.n_wg), dim3(LGC_THREADS), 0, c->stream, g);
   HIP_TRY(hipGetLastError());
   c->last_grad_kernel = "dsgd_lg_cgrad_kernel";
-  return lg_launch_finish(c, K, LG_STEP, lr, c->d_segs);
+  return lg_launch_finish(c, call, LG_STEP, lr, c->d_segs);
 }
 
 int dsgd_lg_sync_steps_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, int64_t n_steps, float lr,
@@ -449,12 +580,14 @@ int dsgd_lg_sync_steps_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64
   if (n_workers < 1 || !row_begin || !row_end) return fail(DSGD_EINVAL, "dsgd_lg_sync_steps_ranges: Cannot sum an empty list of vectors (no workers)");
   std::lock_guard<std::mutex> lk(c->mu);
   bool fresh = false;
-  DSGD_TRY(lg_enter(c, "dsgd_lg_sync_steps_ranges", &fresh));
+  DSGD_TRY(lg_enter(c, "dsgd_lg_sync_steps_ranges", LG_SPANS, &fresh));
   const LgCheck v = lg_check_ranges(row_begin, row_end, n_workers, c->n_rows);
   DSGD_TRY(lg_report(c, "dsgd_lg_sync_steps_ranges", v, n_workers));
   if (n_steps < 1) return lg_report(c, "dsgd_lg_sync_steps_ranges", lg_fault(LG_NO_WORKERS, -1, -1, n_steps), n_workers);
   DSGD_TRY(prepare_layout(c));
   DSGD_TRY(lg_ensure(c, n_workers));
+  LgCall q;
+  DSGD_TRY(lg_agree(c, "dsgd_lg_sync_steps_ranges", n_workers, n_steps, &q));
   DSGD_TRY(reset_counters(c));
   DSGD_TRY(lg_upload_ranges(c, row_begin, row_end, n_workers));
   dsgd_ctx::LgColsLayout* L = nullptr;
@@ -463,11 +596,11 @@ int dsgd_lg_sync_steps_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64
   c->s_dirty = true;   // (from the first launch on the weights move)
   c->lg_nsq_stamp = ~0ull - 1;
   // three launches per step (no layout: the row form's two), back to back on the stream: no host synchronisation in between
-  for (int64_t t = 0; t < n_steps; ++t) {
-    if (L) DSGD_TRY(lgc_launch(c, *L, n_workers, v.longest, lr));
-    else DSGD_TRY(lg_launch(c, false, n_workers, v.longest, LG_STEP, lr, nullptr, c->d_segs));
-  }
-  return lg_step_done(c, stats, v.total);
+  int rc = DSGD_OK;
+  for (int64_t t = 0; t < n_steps && rc == DSGD_OK; ++t)
+    rc = L ? lgc_launch(c, q, *L, v.longest, lr) : lg_launch(c, false, q, v.longest, LG_STEP, lr, nullptr, c->d_segs);
+  DSGD_TRY(lg_steps_end(c, q, rc));
+  return lg_step_done(c, q, stats, v.total, n_steps);
 }
 
 int dsgd_lg_sync_steps(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const int64_t* offsets, int64_t n_steps, int32_t n_workers, float lr,
@@ -476,13 +609,15 @@ int dsgd_lg_sync_steps(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const int
   if (!idx || !offsets || n_steps < 1 || n_workers < 1 || n_idx < 1) return fail(DSGD_EINVAL, "dsgd_lg_sync_steps: bad arguments (null lists, no steps or no workers)");
   std::lock_guard<std::mutex> lk(c->mu);
   bool fresh = false;
-  DSGD_TRY(lg_enter(c, "dsgd_lg_sync_steps", &fresh));
+  DSGD_TRY(lg_enter(c, "dsgd_lg_sync_steps", LG_SPANS, &fresh));
   const int K = n_workers;
   const LgCheck v = lg_check_flat(idx, n_idx, offsets, n_steps, K, c->n_rows);
   DSGD_TRY(lg_report(c, "dsgd_lg_sync_steps", v, K));
   const int64_t n_lists = n_steps * K;
   DSGD_TRY(prepare_layout(c));
   DSGD_TRY(lg_ensure(c, K));
+  LgCall q;
+  DSGD_TRY(lg_agree(c, "dsgd_lg_sync_steps", K, n_steps, &q));
   if (c->d_lg_ssegs.cap() < (size_t)n_lists) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     DSGD_TRY(c->d_lg_ssegs.reserve((size_t)n_lists));
@@ -503,12 +638,14 @@ int dsgd_lg_sync_steps(dsgd_ctx* c, const int32_t* idx, int64_t n_idx, const int
   HIP_TRY(hipMemcpyAsync(c->d_lg_ssegs, c->pin_segs.p, sizeof(WorkSeg) * (size_t)n_lists, hipMemcpyHostToDevice, c->stream));
   DSGD_TRY(pin_sent(c, c->pin_segs));
   // two launches per step, back to back on the stream: no host synchronisation in between
-  for (int64_t t = 0; t < n_steps; ++t) {
+  int rc = DSGD_OK;
+  for (int64_t t = 0; t < n_steps && rc == DSGD_OK; ++t) {
     long long mx = 0;
     for (int k = 0; k < K; ++k) mx = std::max<long long>(mx, offsets[t * K + k + 1] - offsets[t * K + k]);
-    DSGD_TRY(lg_launch(c, true, K, mx, LG_STEP, lr, c->d_idx, c->d_lg_ssegs + t * K));
+    rc = lg_launch(c, true, q, mx, LG_STEP, lr, c->d_idx, c->d_lg_ssegs + t * K);
   }
-  return lg_step_done(c, stats, n_idx);
+  DSGD_TRY(lg_steps_end(c, q, rc));
+  return lg_step_done(c, q, stats, n_idx);
 }
 
 int dsgd_lg_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row_end, double* loss, double* acc) {
@@ -516,7 +653,7 @@ int dsgd_lg_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row
   if (!loss && !acc) return fail(DSGD_EINVAL, "dsgd_lg_loss_acc: null loss and acc");
   std::lock_guard<std::mutex> lk(c->mu);
   bool fresh = false;
-  DSGD_TRY(lg_enter(c, "dsgd_lg_loss_acc", &fresh));
+  DSGD_TRY(lg_enter(c, "dsgd_lg_loss_acc", LG_STAYS_LOCAL, &fresh));
   const LgCheck v = lg_check_ranges(&row_begin, &row_end, 1, c->n_rows);
   DSGD_TRY(lg_report(c, "dsgd_lg_loss_acc", v, 1));
   DSGD_TRY(prepare_layout(c));
@@ -563,7 +700,7 @@ int dsgd_lg_loss_acc_ranges(dsgd_ctx* c, const float* w, const int64_t* row_begi
   if (n_ranges > LG_MAX_RANGES) return fail(DSGD_EINVAL, "dsgd_lg_loss_acc_ranges: %d ranges, more than the %d of one call", n_ranges, LG_MAX_RANGES);
   std::lock_guard<std::mutex> lk(c->mu);
   bool fresh = false;
-  DSGD_TRY(lg_enter(c, "dsgd_lg_loss_acc_ranges", &fresh));
+  DSGD_TRY(lg_enter(c, "dsgd_lg_loss_acc_ranges", LG_STAYS_LOCAL, &fresh));
   const LgCheck v = lg_check_ranges(row_begin, row_end, n_ranges, c->n_rows);
   DSGD_TRY(lg_report(c, "dsgd_lg_loss_acc_ranges", v, n_ranges));
   LgEvalTable t;
@@ -612,7 +749,7 @@ int dsgd_lg_predict(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, 
   if (n < 1 || !idx || !p_out) return fail(DSGD_EINVAL, "dsgd_lg_predict: bad arguments (a null pointer or no rows)");
   std::lock_guard<std::mutex> lk(c->mu);
   bool fresh = false;
-  DSGD_TRY(lg_enter(c, "dsgd_lg_predict", &fresh));
+  DSGD_TRY(lg_enter(c, "dsgd_lg_predict", LG_STAYS_LOCAL, &fresh));
   const int64_t nn = n;
   const LgCheck v = lg_check_lists(&idx, &nn, 1, c->n_rows);
   DSGD_TRY(lg_report(c, "dsgd_lg_predict", v, 1));

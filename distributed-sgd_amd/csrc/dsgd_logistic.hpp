@@ -23,6 +23,12 @@
 //                             w_j' = (float)(w_j - lr mean): one rounding to float per step.  The accumulators are left zeroed.
 //                             LG_STEP also leaves |w'|^2 per workgroup (lg_block_sum: a fixed tree) in nsq_part[blockIdx.x]:
 //                             the host adds the words in order, so a following evaluation needs no pass over w.
+//   dsgd_lg_finish_kernel<LG_STEP, true>  the GATHERED finish of a step across ranks (dsgd_comm_init_lg; csrc/dsgd_lg_gather.hpp): the
+//                             same body over the K = k * world slots behind the all-reduce, in global worker order; a worker's n
+//                             comes from the header words (uniform reads), vexp is the call's agreed one.  The first lane also
+//                             adds the job's rows of the step to the context's n_samples.
+//   dsgd_lg_header_kernel     in front of such a step's all-reduce: the K header words -- this rank's k lengths from its WorkSegs
+//                             at its own positions, zero everywhere else (so the words of the previous step are gone)
 //   dsgd_lg_nsq_kernel        the same per-workgroup sums of |w|^2 from weights the finish did not write (the same grid, the
 //                             same tree: the same bits)
 //   dsgd_lg_eval_kernel       persistent 1024-lane workgroups, the hw hottest weights in LDS (the shape of dsgd_eval_kernel): the
@@ -39,6 +45,7 @@
 //
 // Plain C++ and vector atomics only.
 #pragma once
+#include "dsgd_lg_gather.hpp"
 #include "dsgd_lg_host.hpp"
 
 constexpr int LG_UNR = 4;   // non-zeros per lane kept in registers between dot and scatter: rows up to 64 non-zeros are read once
@@ -144,11 +151,13 @@ struct LgFinishArgs {
   float* w;                  // rank order; LG_STEP: updated
   double lr, lambda;
   double* nsq_part;          // LG_STEP: [gridDim.x] |w'|^2 of each workgroup's columns
+  const unsigned long long* hdr;   // GATHERED: [K] each global worker's n (segs is not read)
+  DevScalars* sc;                  // GATHERED: n_samples takes the step's rows (all of them active)
 };
 constexpr int LG_GRADIENT = 0, LG_STEP = 1;
 
 // grid: lg_finish_blocks(dp) workgroups -- ONE column per lane
-template <int MODE>
+template <int MODE, bool GATHERED = false>
 __global__ void __launch_bounds__(LG_THREADS) dsgd_lg_finish_kernel(LgFinishArgs a) {
 #pragma clang fp contract(off)
   __shared__ double red[LG_THREADS / 64];
@@ -163,7 +172,7 @@ __global__ void __launch_bounds__(LG_THREADS) dsgd_lg_finish_kernel(LgFinishArgs
       unsigned long long* at = a.acc + (long long)k * a.acc_stride + r;
       const unsigned long long t = *at;
       if (t != 0ull) *at = 0ull;
-      const long long n = a.segs[k].end - a.segs[k].begin;
+      const long long n = GATHERED ? (long long)a.hdr[k] : a.segs[k].end - a.segs[k].begin;
       const double G = (double)(long long)t * ldexp(1.0, a.vexp - lg_shift(n));   // one rounding of the exact sum
       sum = sum + (G + reg);
     }
@@ -179,6 +188,20 @@ __global__ void __launch_bounds__(LG_THREADS) dsgd_lg_finish_kernel(LgFinishArgs
   if (MODE == LG_STEP) {
     const double s = lg_block_sum(sq, red, LG_THREADS / 64);
     if (threadIdx.x == 0) a.nsq_part[blockIdx.x] = s;
+  }
+  if (GATHERED && blockIdx.x == 0 && threadIdx.x == 0) {   // the job's rows of this step (every row contributes)
+    unsigned long long rows = 0ull;
+    for (int k = 0; k < a.K; ++k) rows += a.hdr[k];
+    atomicAdd(&a.sc->n_samples, rows);
+  }
+}
+
+// One step's header words across ranks: hdr[first + j] = the rows of this rank's worker j, every other of the K words zero.
+// grid: one workgroup
+__global__ void __launch_bounds__(LG_THREADS) dsgd_lg_header_kernel(unsigned long long* hdr, int K, int first, int k, const WorkSeg* segs) {
+  for (int g = threadIdx.x; g < K; g += LG_THREADS) {
+    const int j = g - first;
+    hdr[g] = j >= 0 && j < k ? (unsigned long long)(segs[j].end - segs[j].begin) : 0ull;
   }
 }
 

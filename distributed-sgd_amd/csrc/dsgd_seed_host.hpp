@@ -202,7 +202,7 @@ static int plan_from_seed(dsgd_ctx* c, const SeedRequest& r, uint64_t* jstate, i
   {   // (refused with *out as it was)
     std::lock_guard<std::mutex> lk0(c->mu);
     if (r.lg) {
-      DSGD_TRY(lg_refuse(c, r.what));
+      DSGD_TRY(lg_refuse(c, r.what, LG_ONE_PROCESS));
     } else if (r.rp64) {
       DSGD_TRY(require_fp64(c, r.what));
       if (!r.comm_ok) DSGD_TRY(refuse_fp64_comm(c, r.what));
@@ -231,7 +231,7 @@ static int plan_from_seed(dsgd_ctx* c, const SeedRequest& r, uint64_t* jstate, i
   std::lock_guard<std::mutex> lk(c->mu);
   if (!r.comm_ok) DSGD_TRY(refuse_fp64_comm(c, r.what));
   if (!r.rp64) DSGD_TRY(refuse_val64(c, r.what));
-  if (r.lg) DSGD_TRY(lg_refuse(c, r.what));
+  if (r.lg) DSGD_TRY(lg_refuse(c, r.what, LG_ONE_PROCESS));
   DSGD_TRY(bind(c, true));
   for (int i = 0; i < r.n_local; ++i)
     if (r.split_begin[i] + r.len[(size_t)(r.first + i)] > c->n_rows)

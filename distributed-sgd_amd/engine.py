@@ -790,6 +790,14 @@ class Engine:
             raise ValueError("unique id must be %d bytes" % _lib.UNIQUE_ID_BYTES)
         check(self._lib.dsgd_comm_init_f64v(self._ctx, C.c_char_p(unique_id), C.c_int32(world_size), C.c_int32(rank)))
 
+    def comm_init_lg(self, unique_id, world_size, rank):
+        """Attach this fp32 engine to the communicator the LOGISTIC model's steps span (dsgd_comm_init_lg): lg_sync_step,
+        lg_sync_step_ranges, lg_sync_steps_ranges, lg_sync_steps and plan_run on an lg_plan become collective -- every rank
+        with the same number of hosted workers and steps, on its own shard -- and leave on every rank the bits of one engine
+        over all the rows.  lg_gradient, lg_predict_proba, lg_loss_acc and lg_loss_acc_ranges stay local to the shard.  The
+        SVM's calls behave as under comm_init."""
+        check(self._lib.dsgd_comm_init_lg(self._ctx, C.c_char_p(unique_id), C.c_int32(world_size), C.c_int32(rank)))
+
     def comm_destroy(self):
         check(self._lib.dsgd_comm_destroy(self._ctx))
 

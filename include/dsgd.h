@@ -761,6 +761,11 @@ int dsgd_comm_init_f64(dsgd_ctx* ctx, const char* unique_id, int32_t world_size,
  * same communicator, accepted with dsgd_load_csr_f64's data loaded and accepting that load while attached; steps on Double
  * data gather both words of the column sums.  On float data everything is dsgd_comm_init_f64's, bit for bit.          */
 int dsgd_comm_init_f64v(dsgd_ctx* ctx, const char* unique_id, int32_t world_size, int32_t rank);
+/* The communicator the LOGISTIC model's steps span ("THE LOGISTIC MODEL", ACROSS RANKS): fp32 contexts only (an fp64 one:
+ * DSGD_EUNSUPPORTED), at most 64 ranks; dsgd_comm_init's argument checks.  The SVM's entry points behave as under
+ * dsgd_comm_init.  A collective call: every rank attaches in the same state; loaded rows are ranked again here from the column
+ * counts summed over the ranks, rows loaded later at their first use.  dsgd_comm_destroy detaches.                     */
+int dsgd_comm_init_lg(dsgd_ctx* ctx, const char* unique_id, int32_t world_size, int32_t rank);
 
 /* ---- several GPUs driven by ONE host thread --------------------------------------------------------------------
  * The reference's dev role runs the master and every slave in ONE JVM (Main.scala:144-158); SURVEY.md 8(b) lists the
@@ -917,7 +922,7 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *                      n_idx without decreasing, or an empty list among them; an empty or reversed range
  *   DSGD_ERANGE        an index (or a range's end) outside the loaded rows
  *   DSGD_ESTATE        no data loaded, or the lock-free engine is running
- *   DSGD_EUNSUPPORTED  an fp64 context, or a communicator attached
+ *   DSGD_EUNSUPPORTED  an fp64 context, or a communicator attached by anything but dsgd_comm_init_lg ("ACROSS RANKS" below)
  *
  * RESIDENT PLANS.  dsgd_plan_create_lg_n (the arguments of dsgd_plan_create_n; dsgd_lg_sync_steps' checks on the host before
  * anything is staged) and dsgd_plan_create_from_seed_lg (the arguments, limits, refusals and *jstate / *n_steps_out /
@@ -968,10 +973,37 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  * do and the call still succeeds; dsgd_grad_kernel_name says "dsgd_lg_cgrad_kernel" or "dsgd_lg_grad_range_kernel".
  * Refusals: those of dsgd_lg_sync_step_ranges with its codes, and n_steps < 1 (DSGD_EINVAL).  No other call takes this path.
  *
+ * ACROSS RANKS (dsgd_comm_init_lg, declared with the multi-GPU entry points; one process per GPU; csrc/dsgd_lg_gather.hpp,
+ * DESIGN.md 7.5).  A worker's column sums are integers, so they cross the ranks without rounding.  Under this communicator
+ * dsgd_lg_sync_step, dsgd_lg_sync_step_ranges, dsgd_lg_sync_steps_ranges, dsgd_lg_sync_steps and dsgd_plan_run on a plan of
+ * dsgd_plan_create_lg_n (whose creation stays local) are COLLECTIVE: every rank calls with the same k hosted workers and the
+ * same number of steps, on its own shard (row indices are the shard's).  Global worker r * k + j is rank r's worker j.  The
+ * weights on every rank are the bits of ONE context that holds shard 0 || shard 1 || ... and steps those K = k * world lists or
+ * ranges in that order; the statistics are the job's rows (a plan's through dsgd_synchronize).
+ *   agreement  once per call, in front of the first launch: the ranks all-reduce a record of (k, steps, the vexp of the own
+ *              data) and read it back -- the call's one extra host read.  Ranks that differ in k or in the steps ALL return
+ *              DSGD_EINVAL, weights unchanged, and the next agreed call works.  The call runs on the LARGEST vexp, the one a
+ *              single context computes on all the rows; the context's own vexp is not changed.  A rank that fails a check of
+ *              its OWN arguments returns without joining: the callers keep the ranks' arguments valid together
+ *   a step     the gradient kernels sum into the rank's own slots of the K; one ncclAllReduce(int64, sum) over the slots and
+ *              one length word per worker is the exact all-gather; every rank folds the K workers in worker order with the
+ *              single context's finish arithmetic.  Several steps of one call are enqueued without host synchronisation
+ *   local      dsgd_lg_gradient, dsgd_lg_predict, dsgd_lg_loss_acc and dsgd_lg_loss_acc_ranges enter no collective: the shard,
+ *              the shard's own vexp, the figures of a context without a communicator (the caller combines the ranks')
+ *   refused    DSGD_EUNSUPPORTED, weights untouched: dsgd_plan_create_from_seed_lg (the device draw does not span ranks),
+ *              dsgd_plan_create_lg_cs_n, dsgd_plan_create_from_seed_lg_cs, and dsgd_plan_run on a column-slice plan made
+ *              before the attach.  Under dsgd_comm_init and on contexts joined by dsgd_comm_init_all every logistic call
+ *              stays refused
+ *   errors     a collective that fails half way: DSGD_ERCCL, the buffer is dropped, the weights are those behind the last
+ *              completed step
+ * After dsgd_comm_destroy the calls are local again.  Real RCCL with more than one rank has not run; no speed is claimed.
+ *
  * LIMITS (out of scope, each refused or simply absent): no JNI / Scala binding; the host mirror is host.LogisticSync
- * (Master.fit's flow on one context: no distributed or sampled evaluation, no asynchronous fit; host.MasterSync /
- * MasterAsync stay the SVM's); no fused or persistent one-launch step and no column slices but those of COLUMN SLICES above; no asynchronous engine; no fp64
- * contexts and no Double feature values; no communicators; no Sparse boundary forms; no predict_ranges.
+ * (Master.fit's flow on one context, no communicator: no distributed or sampled evaluation, no asynchronous fit;
+ * host.MasterSync / MasterAsync stay the SVM's); no fused or persistent one-launch step and no column slices but those of
+ * COLUMN SLICES above; no asynchronous engine; no fp64 contexts and no Double feature values; across ranks only what ACROSS
+ * RANKS lists -- no device-drawn lists, no column slices, no evaluation over the ranks; no Sparse boundary forms; no
+ * predict_ranges.
  *
  * dsgd_lg_gradient: one worker's regularised sum over the listed rows, key order, from the resident weights or from w
  * (which then replaces them, as in dsgd_gradient).  dsgd_lg_sync_step / _ranges: one step over K lists / K row
