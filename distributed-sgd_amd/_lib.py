@@ -54,6 +54,7 @@ SYMBOLS = [
     "dsgd_lg_sync_steps_ranges",
     "dsgd_plan_create_lg_cs_n", "dsgd_plan_create_from_seed_lg_cs",
     "dsgd_comm_init_lg",
+    "dsgd_lg_predict_ranges", "dsgd_lg_loss_acc_list", "dsgd_lg_loss_acc_sampled",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -150,6 +151,14 @@ def load():
         lib.dsgd_lg_sync_steps_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p]
     if hasattr(lib, "dsgd_comm_init_lg"):
         lib.dsgd_comm_init_lg.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32]
+    if hasattr(lib, "dsgd_lg_predict_ranges"):   # the logistic model's distributed and sampled evaluation
+        # (ctx, w*, row_begin*, row_end*, n_ranges, class_out*, proba_out*, counts_out*, range_loss_out*, loss*, acc*)
+        lib.dsgd_lg_predict_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]
+        # (the prototypes of dsgd_loss_acc_list and dsgd_loss_acc_sampled)
+        lib.dsgd_lg_loss_acc_list.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.dsgd_lg_loss_acc_sampled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(lib, "dsgd_dense_plan_create"):   # (handles are 64-bit: without argtypes ctypes would pass them as C ints)
         lib.dsgd_dense_step_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float]
         lib.dsgd_dense_loss_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

@@ -127,6 +127,7 @@ static bool available() {
 #include "dsgd_route.hpp"        // (host only: the switches, and which kernel family serves a call)
 #include "dsgd_kernels.hpp"
 #include "dsgd_logistic.hpp"   // (the logistic model beside the SVM: its own gradient, finish, evaluation and probabilities)
+#include "dsgd_lg_eval.hpp"    // (... evaluated as Master evaluates: classes and tallies of K row ranges, the rows of a list)
 #include "dsgd_batch.hpp"
 #include "dsgd_cs.hpp"
 #include "dsgd_lg_cs.hpp"   // (the logistic model on column slices: the cell layout and the exchange above, logistic arithmetic)
@@ -540,6 +541,13 @@ struct dsgd_ctx {
   long long lg_pending_active = 0;         // rows of logistic plan runs since the last dsgd_synchronize (every row contributes)
   DevBuf<WorkSeg> d_lg_ssegs;
   DevBuf<float> d_lg_p;
+  // Its distributed evaluation (csrc/dsgd_lg_eval.hpp: dsgd_lg_predict_ranges), grown on demand: the table's three arrays at
+  // LG_PRED_MAX_RANGES ranges, the tallies [LG_PRED_MAX_RANGES][LG_TALLY_WORDS], one loss word per workgroup, the class bytes
+  // (the probabilities go through d_lg_p; the |w|^2 words stay where dsgd_lg_loss_acc keeps them, in d_lg_part)
+  DevBuf<long long> d_lg_pred_tab;
+  DevBuf<unsigned long long> d_lg_pred_tally;
+  DevBuf<double> d_lg_pred_part;
+  DevBuf<signed char> d_lg_cls;
   // Its column lists (csrc/dsgd_lg_cols.hpp): whole-split steps as coefficients + column-wise gradient + finish.  Per (row
   // ranges) configuration the device sorts the ranges' entries by (worker, column) once; at most eight configurations stay
   // cached (the least recently used one makes room), all dropped by a load.
@@ -2282,6 +2290,8 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   DSGD_ATTR(dsgd_eval_list_kernel<32>);
   DSGD_ATTR(dsgd_eval_list_kernel<16>);
   DSGD_ATTR(dsgd_eval_list_kernel<8>);
+  DSGD_ATTR(dsgd_lg_predict_ranges_kernel);
+  DSGD_ATTR(dsgd_lg_eval_list_kernel);
   DSGD_ATTR(dsgd_colcount_kernel);
   DSGD_ATTR((dsgd_hogwild_kernel<false, false>));
   DSGD_ATTR((dsgd_hogwild_kernel<true, false>));

@@ -1,5 +1,6 @@
-// Host side of the logistic model (include/dsgd.h "THE LOGISTIC MODEL"; device code: csrc/dsgd_logistic.hpp; the shift, the
-// grids and the validation of lists, ranges and offsets: csrc/dsgd_lg_host.hpp).  Included by dsgd_hip.hip inside its
+// Host side of the logistic model (include/dsgd.h "THE LOGISTIC MODEL"; device code: csrc/dsgd_logistic.hpp and, for the
+// distributed and sampled evaluation at the end of this file, csrc/dsgd_lg_eval.hpp; the shift, the grids, the tables and the
+// validation of lists, ranges and offsets: csrc/dsgd_lg_host.hpp).  Included by dsgd_hip.hip inside its
 // extern "C" block, behind the helpers it uses (bind, stage_lists, upload_segs, set_weights_locked, finish_stats).
 //
 // Every check runs on the host before anything of the call is enqueued: a refused call leaves the weights, the accumulators
@@ -771,5 +772,216 @@ int dsgd_lg_predict(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, 
   memcpy(p_out, c->pin_out.p, sizeof(float) * (size_t)n);
   DSGD_TRY(check_err_flag(c));
   if (fresh && !w) c->lg_nsq_stamp = c->bind_count;
+  return DSGD_OK;
+}
+
+// ---- distributed and sampled evaluation (csrc/dsgd_lg_eval.hpp; ref: core/Master.scala:61-118) ----
+// the tile of an evaluation launch whose longest range (or list) has `rows` rows, and `extra` floats of LDS behind
+// dsgd_lg_eval_kernel's: dsgd_lg_loss_acc's rule (small ranges do not amortise staging 160 KiB per workgroup)
+static int lg_eval_hw(dsgd_ctx* c, long long rows, int extra) {
+  int hw = rows >= 4096 ? c->hw_eval : std::min(c->hw_eval, 1024);
+  while (hw > 0 && lg_eval_lds_floats(hw) + extra > DSGD_LDS_FLOATS) hw -= 64;
+  return std::max(hw, 0);
+}
+// |w|^2 of weights the logistic finish did not write, as dsgd_lg_loss_acc takes it: the finish's grid and tree, the same bits
+static int lg_nsq_if_stale(dsgd_ctx* c, bool stale) {
+  if (!stale) return DSGD_OK;
+  hipLaunchKernelGGL(dsgd_lg_nsq_kernel, dim3((unsigned)lg_finish_blocks(c->dp)), dim3(LG_THREADS), 0, c->stream, c->d_w, c->dp, c->d_lg_part);
+  HIP_TRY(hipGetLastError());
+  return DSGD_OK;
+}
+
+// the verdict of lg_pred_table (csrc/dsgd_lg_host.hpp) in the words and with the codes of the SVM's dsgd_predict_ranges
+static int lg_report(dsgd_ctx* c, const char* what, const LgPredTable& t, const int64_t* row_begin, const int64_t* row_end) {
+  switch (t.fault) {
+    case LGP_OK: return DSGD_OK;
+    case LGP_ARGS: return fail(DSGD_EINVAL, "%s: bad arguments (null ranges or no range)", what);
+    case LGP_TOO_MANY: return fail(DSGD_EINVAL, "%s: more than %d ranges in one call", what, LG_PRED_MAX_RANGES);
+    case LGP_REVERSED:
+      return fail(DSGD_EINVAL, "%s: range %d: begin %lld > end %lld", what, t.range, (long long)row_begin[t.range], (long long)row_end[t.range]);
+    case LGP_OUTSIDE:
+      return fail(DSGD_ERANGE, "%s: rows [%lld, %lld) of range %d outside the %lld loaded rows", what, (long long)row_begin[t.range],
+                  (long long)row_end[t.range], t.range, c->n_rows);
+    case LGP_OVERLAP:
+      return fail(DSGD_EINVAL, "%s: ranges %d and %d overlap: [%lld, %lld) and [%lld, %lld)", what, t.range, t.other, (long long)row_begin[t.range],
+                  (long long)row_end[t.range], (long long)row_begin[t.other], (long long)row_end[t.other]);
+    case LGP_NO_ROWS: break;
+  }
+  return fail(DSGD_EINVAL, "%s: no rows in any range: reduce on an empty prediction map", what);
+}
+
+int dsgd_lg_predict_ranges(dsgd_ctx* c, const float* w, const int64_t* row_begin, const int64_t* row_end, int32_t n_ranges, int8_t* class_out,
+                           float* proba_out, int64_t* counts_out, double* range_loss_out, double* loss, double* acc) {
+  const char* what = "dsgd_lg_predict_ranges";
+  DSGD_TRY(check_ctx(c));
+  if (n_ranges < 1 || !row_begin || !row_end) return fail(DSGD_EINVAL, "%s: bad arguments (null ranges or no range)", what);
+  if (n_ranges > LG_PRED_MAX_RANGES) return fail(DSGD_EINVAL, "%s: %d ranges in one call (at most %d)", what, n_ranges, LG_PRED_MAX_RANGES);
+  if (!class_out && !proba_out && !counts_out && !range_loss_out && !loss && !acc) return fail(DSGD_EINVAL, "%s: every output is null", what);
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, what, LG_STAYS_LOCAL, &fresh));
+  const int K = n_ranges;
+  const size_t tab_words = (size_t)lg_pred_tab_words(K);
+  std::vector<long long> tab(tab_words);
+  long long* first_block = tab.data();
+  long long* out_off = tab.data() + (2 * K + 1);
+  const LgPredTable t = lg_pred_table(row_begin, row_end, K, c->n_cu, c->n_rows, first_block, tab.data() + (K + 1), out_off);
+  DSGD_TRY(lg_report(c, what, t, row_begin, row_end));
+  DSGD_TRY(prepare_layout(c));
+  if (w) DSGD_TRY(set_weights_locked(c, w));
+  DSGD_TRY(lg_ensure(c, 1));
+  const size_t total = (size_t)t.total, grid = (size_t)t.grid, tally_words = (size_t)K * LG_TALLY_WORDS;
+  if (!c->d_lg_pred_tab || grid > c->d_lg_pred_part.cap() || (class_out && total > c->d_lg_cls.cap()) || (proba_out && total > c->d_lg_p.cap())) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    DSGD_TRY(c->d_lg_pred_tab.reserve((size_t)lg_pred_tab_words(LG_PRED_MAX_RANGES)));
+    DSGD_TRY(c->d_lg_pred_tally.reserve((size_t)LG_PRED_MAX_RANGES * LG_TALLY_WORDS));
+    DSGD_TRY(c->d_lg_pred_part.reserve(std::max<size_t>(grid, (size_t)c->n_cu), Grow::twice));
+    if (class_out) DSGD_TRY(c->d_lg_cls.reserve(std::max<size_t>(total, 4096), Grow::twice));
+    if (proba_out) DSGD_TRY(c->d_lg_p.reserve(std::max<size_t>(total, 4096), Grow::twice));
+  }
+  const long long nb = lg_finish_blocks(c->dp);
+  DSGD_TRY(lg_nsq_if_stale(c, w || !fresh));
+  DSGD_TRY(reset_counters(c));
+  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(long long) * tab_words));
+  memcpy(c->pin_idx.p, tab.data(), sizeof(long long) * tab_words);
+  HIP_TRY(hipMemcpyAsync(c->d_lg_pred_tab, c->pin_idx.p, sizeof(long long) * tab_words, hipMemcpyHostToDevice, c->stream));
+  DSGD_TRY(pin_sent(c, c->pin_idx));
+  HIP_TRY(hipMemsetAsync(c->d_lg_pred_tally, 0, sizeof(unsigned long long) * tally_words, c->stream));
+  // ONE tile size for the launch, by its longest range (dsgd_lg_loss_acc's rule for that range): the size moves no bit
+  const int hw = lg_eval_hw(c, t.longest, 2 * lg_pred_tab_words(K));
+  const size_t lds = sizeof(float) * (size_t)lg_pred_lds_floats(hw, K);
+  LgPredArgs a;
+  a.tab = c->d_lg_pred_tab;
+  a.K = K;
+  a.cls = class_out ? c->d_lg_cls.get() : nullptr;
+  a.proba = proba_out ? c->d_lg_p.get() : nullptr;
+  a.tally = c->d_lg_pred_tally;
+  a.loss_part = c->d_lg_pred_part;
+  hipLaunchKernelGGL(dsgd_lg_predict_ranges_kernel, dim3((unsigned)grid), dim3(LG_EVAL_THREADS), lds, c->stream, view(c), c->d_w, a, hw);
+  HIP_TRY(hipGetLastError());
+  // every reply through the pinned buffer: the |w|^2 words, the workgroups' loss words, the tallies, the probabilities, the bytes
+  const size_t part_words = (size_t)nb + grid;
+  DSGD_TRY(pin_acquire(c->pin_out, sizeof(double) * part_words + sizeof(unsigned long long) * tally_words + (proba_out ? sizeof(float) * total : 0) +
+                                       (class_out ? total : 0)));
+  double* part = static_cast<double*>(c->pin_out.p.get());
+  unsigned long long* tally = reinterpret_cast<unsigned long long*>(part + part_words);
+  float* h_proba = reinterpret_cast<float*>(tally + tally_words);
+  signed char* h_cls = reinterpret_cast<signed char*>(h_proba + (proba_out ? total : 0));
+  HIP_TRY(hipMemcpyAsync(part, c->d_lg_part, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(part + nb, c->d_lg_pred_part, sizeof(double) * grid, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(tally, c->d_lg_pred_tally, sizeof(unsigned long long) * tally_words, hipMemcpyDeviceToHost, c->stream));
+  if (proba_out) HIP_TRY(hipMemcpyAsync(h_proba, c->d_lg_p, sizeof(float) * total, hipMemcpyDeviceToHost, c->stream));
+  if (class_out) HIP_TRY(hipMemcpyAsync(h_cls, c->d_lg_cls, total, hipMemcpyDeviceToHost, c->stream));
+  DSGD_TRY(read_scalars(c));   // the one synchronisation of the call
+  DSGD_TRY(check_err_flag(c));
+  c->lg_nsq_stamp = c->bind_count;
+  for (int r = 0; r < K; ++r) {   // (before anything is written)
+    const unsigned long long* tr = tally + (size_t)r * LG_TALLY_WORDS;
+    const long long rows = out_off[r + 1] - out_off[r];
+    if ((long long)(tr[0] + tr[1] + tr[2]) != rows)
+      return fail(DSGD_ESTATE, "internal: %llu rows tallied of the %lld of range %d", tr[0] + tr[1] + tr[2], rows, r);
+  }
+  double nsq = 0.0, ls_all = 0.0;   // (in order: the same bits on every call)
+  for (long long i = 0; i < nb; ++i) nsq += part[i];
+  unsigned long long right = 0;
+  for (int r = 0; r < K; ++r) {
+    const unsigned long long* tr = tally + (size_t)r * LG_TALLY_WORDS;
+    const long long rows = out_off[r + 1] - out_off[r];
+    double ls = 0.0;
+    for (long long i = first_block[r]; i < first_block[r + 1]; ++i) ls += part[nb + i];
+    ls_all += ls;
+    right += tr[0];
+    if (range_loss_out) range_loss_out[r] = rows ? c->cfg.lambda * nsq + ls / (double)rows : 0.0;   // (dsgd_lg_loss_acc's expression)
+    for (int j = 0; counts_out && j < 3; ++j) counts_out[3 * r + j] = (int64_t)tr[j];
+  }
+  if (proba_out) memcpy(proba_out, h_proba, sizeof(float) * total);
+  if (class_out) memcpy(class_out, h_cls, total);
+  if (loss) *loss = c->cfg.lambda * nsq + ls_all / (double)t.total;
+  if (acc) *acc = (double)right / (double)t.total;
+  return DSGD_OK;
+}
+
+// |w|^2 where stale, ONE launch over the n >= 1 rows c->d_idx names, the replies and the fold (entered, the weights resident, the
+// list enqueued on the context's stream).  Outputs are written when everything has succeeded, idx_out (n entries) among them.
+static int lg_eval_list_run(dsgd_ctx* c, long long n, bool nsq_stale, double* loss, double* acc, int64_t* counts, int32_t* idx_out) {
+  DSGD_TRY(lg_ensure(c, 1));
+  const long long nb = lg_finish_blocks(c->dp);
+  DSGD_TRY(lg_nsq_if_stale(c, nsq_stale));
+  DSGD_TRY(reset_counters(c));
+  const long long grid = lg_eval_blocks(n, c->n_cu);   // (dsgd_lg_loss_acc's grid over n rows: at most n_cu words behind the |w|^2 ones)
+  const int hw = lg_eval_hw(c, n, 0);
+  const size_t lds = sizeof(float) * (size_t)lg_eval_lds_floats(hw);
+  hipLaunchKernelGGL(dsgd_lg_eval_list_kernel, dim3((unsigned)grid), dim3(LG_EVAL_THREADS), lds, c->stream, view(c), c->d_w, c->d_idx.get(), n, c->d_sc,
+                     hw, c->d_lg_part + nb);
+  HIP_TRY(hipGetLastError());
+  const size_t words = (size_t)(nb + grid);
+  DSGD_TRY(pin_acquire(c->pin_out, sizeof(double) * words + (idx_out ? sizeof(int) * (size_t)n : 0)));
+  double* part = static_cast<double*>(c->pin_out.p.get());
+  int* h_idx = reinterpret_cast<int*>(part + words);
+  HIP_TRY(hipMemcpyAsync(part, c->d_lg_part, sizeof(double) * words, hipMemcpyDeviceToHost, c->stream));
+  if (idx_out) HIP_TRY(hipMemcpyAsync(h_idx, c->d_idx, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  DSGD_TRY(read_scalars(c));   // the one synchronisation of the call
+  DSGD_TRY(check_err_flag(c));
+  c->lg_nsq_stamp = c->bind_count;
+  long long t3[3];
+  for (int j = 0; j < 3; ++j) t3[j] = (long long)c->h_sc->counts[j];
+  if (t3[0] + t3[1] + t3[2] != n) return fail(DSGD_ESTATE, "internal: %lld rows tallied of %lld", t3[0] + t3[1] + t3[2], n);
+  double nsq = 0.0, ls = 0.0;   // (in order: the same bits on every call)
+  for (long long i = 0; i < nb; ++i) nsq += part[i];
+  for (long long i = 0; i < grid; ++i) ls += part[nb + i];
+  if (loss) *loss = c->cfg.lambda * nsq + ls / (double)n;   // (dsgd_lg_loss_acc's expression)
+  if (acc) *acc = (double)t3[0] / (double)n;
+  for (int j = 0; counts && j < 3; ++j) counts[j] = (int64_t)t3[j];
+  if (idx_out) memcpy(idx_out, h_idx, sizeof(int) * (size_t)n);
+  return DSGD_OK;
+}
+
+int dsgd_lg_loss_acc_list(dsgd_ctx* c, const float* w, const int32_t* idx, int64_t n, double* loss, double* acc, int64_t* counts) {
+  const char* what = "dsgd_lg_loss_acc_list";
+  DSGD_TRY(check_ctx(c));
+  if (!idx || n < 1)   // samples.map(...).reduce on an empty collection throws (ref: SparseSVM.scala:21-23)
+    return fail(DSGD_EINVAL, "%s: no list, or an empty one (reduce on an empty sample list)", what);
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, what, LG_STAYS_LOCAL, &fresh));
+  const int64_t nn = n;
+  const LgCheck v = lg_check_lists(&idx, &nn, 1, c->n_rows);
+  DSGD_TRY(lg_report(c, what, v, 1));
+  DSGD_TRY(prepare_layout(c));
+  if (w) DSGD_TRY(set_weights_locked(c, w));
+  DSGD_TRY(ensure_idx(c, n));
+  DSGD_TRY(send_idx(c, idx, n));
+  return lg_eval_list_run(c, n, w || !fresh, loss, acc, counts, nullptr);
+}
+
+// (csrc/dsgd_hip.hip, with the SVM's dsgd_loss_acc_sampled: the first n entries of Random.shuffle(0 until len) into c->d_idx)
+static int sampled_draw(dsgd_ctx* c, const char* what, unsigned long long s0, int64_t row_begin, long long len, long long n, long long* draws);
+
+// dsgd_loss_acc_sampled word for word -- the same draw (sampled_draw as it stands), the same limits, the same refusals with
+// *jstate untouched -- with the logistic family's entry checks and the logistic fold over the list
+int dsgd_lg_loss_acc_sampled(dsgd_ctx* c, const float* w, uint64_t* jstate, int64_t row_begin, int64_t row_end, int64_t samples_count, double* loss,
+                             double* acc, int64_t* counts, int32_t* idx_out, int64_t* n_out, int64_t* draws_out) {
+  const char* what = "dsgd_lg_loss_acc_sampled";
+  DSGD_TRY(check_ctx(c));
+  if (!jstate) return fail(DSGD_EINVAL, "%s: null jstate", what);
+  if (samples_count < 1 || row_begin >= row_end)   // (the JVM would have spent the shuffle's draws before .reduce throws; not here)
+    return fail(DSGD_EINVAL, "%s: an empty sample (samples_count %lld of rows [%lld, %lld)): reduce on an empty sample list", what,
+                (long long)samples_count, (long long)row_begin, (long long)row_end);
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, what, LG_STAYS_LOCAL, &fresh));
+  DSGD_TRY(lg_report(c, what, lg_check_ranges(&row_begin, &row_end, 1, c->n_rows), 1));   // (the window leaves the rows: DSGD_ERANGE)
+  const long long len = row_end - row_begin, n = std::min<long long>(samples_count, len);   // (the reference's `take`)
+  if (len > JR_MAX_LEN)
+    return fail(DSGD_EUNSUPPORTED, "%s draws windows up to %d rows (dsgd_jrand_shuffle, then dsgd_lg_loss_acc_list)", what, JR_MAX_LEN);
+  DSGD_TRY(prepare_layout(c));
+  const unsigned long long s0 = *jstate & JR_MASK;
+  long long draws = 0;
+  DSGD_TRY(sampled_draw(c, what, s0, row_begin, len, n, &draws));   // (a refusal leaves the weights as they were)
+  if (w) DSGD_TRY(set_weights_locked(c, w));
+  DSGD_TRY(lg_eval_list_run(c, n, w || !fresh, loss, acc, counts, idx_out));
+  *jstate = jr_jump_dev(s0, (unsigned long long)draws);
+  if (n_out) *n_out = n;
+  if (draws_out) *draws_out = draws;
   return DSGD_OK;
 }

@@ -9,6 +9,8 @@
 //   lg_eval_blocks      the evaluation's persistent grid
 //   lg_eval_table       the grid of an evaluation of up to LG_MAX_RANGES row ranges in ONE launch: range r gets its own run of
 //                       lg_eval_blocks(rows_r) workgroups, one run behind the other (the grid each range has in a launch of its own)
+//   lg_pred_table       the same for up to LG_PRED_MAX_RANGES disjoint ranges (dsgd_lg_predict_ranges): three arrays for the device,
+//                       searched by lg_pred_owner; the refusals of the SVM's dsgd_predict_ranges
 //   lg_check_lists      a step's per-worker lists             (what is wrong, and where: plain data, the callers word the message)
 //   lg_check_ranges     a step's per-worker row ranges
 //   lg_check_flat       an epoch's flat lists                 (csrc/dsgd_plan_check.hpp: flat_lists_check)
@@ -85,6 +87,91 @@ inline bool lg_eval_table(const int64_t* row_begin, const int64_t* row_end, int 
   t->n = n_ranges;
   t->grid = at;
   return true;
+}
+
+// Up to LG_PRED_MAX_RANGES ranges, one launch (dsgd_lg_predict_ranges_kernel, csrc/dsgd_lg_eval.hpp): too many for a select
+// chain over kernel arguments, so the table is three arrays the kernel stages into LDS and searches by bisection.  Range r
+// is walked by the workgroups [first_block[r], first_block[r + 1]), lg_eval_blocks(rows of r) of them -- the grid of a launch
+// of dsgd_lg_eval_kernel over that range alone, so its loss has the same bits -- and its row begin[r] + t writes output
+// position out_off[r] + t (range-major: out_off are the prefix sums of the lengths).  An EMPTY range gets no workgroup and
+// no output: first_block[r] == first_block[r + 1] and out_off[r] == out_off[r + 1].  The owner of workgroup b is the LAST r
+// with first_block[r] <= b (lg_pred_owner: an empty range never is).
+// The refusals are those of the SVM's dsgd_predict_ranges, in its order; n_rows < 0 skips the check against the loaded rows.
+constexpr int LG_PRED_MAX_RANGES = 256;
+enum LgPredFault {
+  LGP_OK = 0,
+  LGP_ARGS,       // a null pointer, n_ranges < 1 or no compute unit
+  LGP_TOO_MANY,   // more than LG_PRED_MAX_RANGES ranges
+  LGP_REVERSED,   // range `range`: begin > end
+  LGP_OUTSIDE,    // range `range` (not empty) leaves the n_rows loaded rows
+  LGP_OVERLAP,    // ranges `range` and `other` share a row
+  LGP_NO_ROWS,    // every range is empty
+};
+struct LgPredTable {
+  LgPredFault fault = LGP_OK;
+  int range = -1, other = -1;     // of a refusal
+  int n = 0;                      // ranges
+  long long grid = 0;             // workgroups: first_block[n]
+  long long total = 0;            // rows: out_off[n]
+  long long longest = 0;          // rows of the longest range (the launch's tile rule)
+};
+// first_block and out_off: n_ranges + 1 words each, begin: n_ranges
+inline LgPredTable lg_pred_table(const int64_t* row_begin, const int64_t* row_end, int n_ranges, int n_cu, long long n_rows, long long* first_block,
+                                 long long* begin, long long* out_off) {
+  LgPredTable t;
+  if (!row_begin || !row_end || !first_block || !begin || !out_off || n_ranges < 1 || n_cu < 1) {
+    t.fault = LGP_ARGS;
+    return t;
+  }
+  if (n_ranges > LG_PRED_MAX_RANGES) {
+    t.fault = LGP_TOO_MANY;
+    return t;
+  }
+  for (int r = 0; r < n_ranges; ++r) {
+    if (row_begin[r] > row_end[r]) {
+      t.fault = LGP_REVERSED, t.range = r;
+      return t;
+    }
+    if (row_begin[r] == row_end[r]) continue;
+    if (n_rows >= 0 && (row_begin[r] < 0 || row_end[r] > n_rows)) {
+      t.fault = LGP_OUTSIDE, t.range = r;
+      return t;
+    }
+  }
+  // (at most 256 ranges: every pair)
+  for (int r = 0; r < n_ranges; ++r)
+    for (int s = r + 1; s < n_ranges; ++s)
+      if (row_begin[r] < row_end[r] && row_begin[s] < row_end[s] && row_begin[r] < row_end[s] && row_begin[s] < row_end[r]) {
+        t.fault = LGP_OVERLAP, t.range = r, t.other = s;
+        return t;
+      }
+  first_block[0] = out_off[0] = 0;
+  for (int r = 0; r < n_ranges; ++r) {
+    const long long rows = row_end[r] - row_begin[r];
+    begin[r] = row_begin[r];
+    first_block[r + 1] = first_block[r] + (rows > 0 ? lg_eval_blocks(rows, n_cu) : 0);
+    out_off[r + 1] = out_off[r] + rows;
+    if (rows > t.longest) t.longest = rows;
+  }
+  if (out_off[n_ranges] == 0) {
+    t.fault = LGP_NO_ROWS;
+    return t;
+  }
+  t.n = n_ranges;
+  t.grid = first_block[n_ranges];
+  t.total = out_off[n_ranges];
+  return t;
+}
+// the range that owns workgroup b < first_block[K]: the last r with first_block[r] <= b (the bisection of pred_range_of,
+// csrc/dsgd_predict.hpp)
+LG_HD inline int lg_pred_owner(const long long* first_block, int K, long long b) {
+  int lo = 0, hi = K;   // first_block[lo] <= b < first_block[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (first_block[mid] <= b) lo = mid;
+    else hi = mid;
+  }
+  return lo;
 }
 
 enum LgFault {

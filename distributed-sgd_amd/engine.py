@@ -467,6 +467,57 @@ class Engine:
         check(self._lib.dsgd_lg_loss_acc_ranges(self._ctx, ptr(wv), rb, re_, C.c_int32(k), ptr(loss), ptr(acc)))
         return [(float(loss[i]), float(acc[i])) for i in range(k)]
 
+    lg_predict_max_ranges = 256   # ranges of one dsgd_lg_predict_ranges call
+
+    def lg_predict_ranges(self, ranges, w=None, want_proba=False):
+        """Master.predict / distributedLoss / distributedAccuracy for the logistic model over the workers' splits in ONE launch
+        (dsgd_lg_predict_ranges): `ranges` = up to 256 disjoint (begin, end) row ranges.  Returns (classes, proba, counts,
+        range_losses, loss, acc): classes int8 signum(x . w) in {-1, 0, +1}, one per row, range after range; proba (want_proba,
+        else None) float32 sigma(x . w), the bits of lg_predict_proba over the same rows; counts int64 [K, 3], every range's
+        exact tallies {#class == y, #class == 0, #class == -y}; range_losses float64 [K], each the bits of lg_loss_acc on
+        that range alone (0.0 for an empty one); loss and accuracy over all the rows.  w as in lg_loss_acc."""
+        k = len(ranges)
+        rb = (C.c_int64 * max(k, 1))(*[int(r[0]) for r in ranges])
+        re_ = (C.c_int64 * max(k, 1))(*[int(r[1]) for r in ranges])
+        total = sum(max(0, int(r[1]) - int(r[0])) for r in ranges)
+        cls = np.zeros(max(total, 1), dtype=np.int8)   # (never a null pointer: the library decides what is refused)
+        proba = np.zeros(max(total, 1), dtype=np.float32) if want_proba else None
+        counts = np.zeros((max(k, 1), 3), dtype=np.int64)
+        range_loss = np.zeros(max(k, 1), dtype=np.float64)
+        loss, acc = C.c_double(0), C.c_double(0)
+        wv = None if w is None else f32(w, self.dp)
+        check(self._lib.dsgd_lg_predict_ranges(self._ctx, ptr(wv), rb, re_, C.c_int32(k), ptr(cls), ptr(proba), ptr(counts), ptr(range_loss),
+                                               C.byref(loss), C.byref(acc)))
+        return cls[:total], (proba[:total] if want_proba else None), counts[:k], range_loss[:k], loss.value, acc.value
+
+    def lg_loss_acc_list(self, idx, w=None):
+        """Loss and accuracy of the logistic model over the rows `idx` names, ONE launch (dsgd_lg_loss_acc_list; the fold of
+        Master.localSampledLoss / localSampledAccuracy over a list drawn elsewhere).  A row named twice counts twice.  Returns
+        (loss, acc, counts); over arange(b, e) the bits of lg_loss_acc(b, e)."""
+        idx = i32(idx)
+        loss, acc = C.c_double(0), C.c_double(0)
+        counts = (C.c_int64 * 3)()
+        wv = None if w is None else f32(w, self.dp)
+        check(self._lib.dsgd_lg_loss_acc_list(self._ctx, ptr(wv), ptr(idx), C.c_int64(len(idx)), C.byref(loss), C.byref(acc), counts))
+        return loss.value, acc.value, list(counts)
+
+    def lg_loss_acc_sampled(self, jstate, row_begin, row_end, samples_count, w=None, want_idx=False):
+        """loss_acc_sampled for the logistic model (dsgd_lg_loss_acc_sampled): the DEVICE draws the sample, draw for draw the
+        reference's stream, and evaluates it.  The arguments, the return value -- (loss, acc, counts, new jstate, draws[, idx])
+        -- and the EUNSUPPORTED refusals (nothing drawn) are loss_acc_sampled's; the figures are the bits of lg_loss_acc_list
+        on idx."""
+        st = C.c_uint64(int(jstate))
+        loss, acc = C.c_double(0), C.c_double(0)
+        counts = (C.c_int64 * 3)()
+        n, draws = C.c_int64(0), C.c_int64(0)
+        cap = max(1, min(int(samples_count), int(row_end) - int(row_begin)))
+        idx = np.zeros(cap, dtype=np.int32) if want_idx else None
+        wv = None if w is None else f32(w, self.dp)
+        check(self._lib.dsgd_lg_loss_acc_sampled(self._ctx, ptr(wv), C.byref(st), C.c_int64(row_begin), C.c_int64(row_end), C.c_int64(samples_count),
+                                                 C.byref(loss), C.byref(acc), counts, ptr(idx), C.byref(n), C.byref(draws)))
+        out = (loss.value, acc.value, list(counts), int(st.value), draws.value)
+        return out + (idx[:n.value],) if want_idx else out
+
     def lg_plan(self, steps, slices=False):
         """A resident LOGISTIC plan (dsgd_plan_create_lg_n) from `steps`: list (per step) of lists (per worker) of index arrays,
         as Engine.plan takes them.  It runs through plan_run / synchronize; the weights get the bits of lg_sync_steps.

@@ -1157,7 +1157,14 @@ class LogisticSync:
 
     data layout: rows [0, n_train) are the train set, [n_train, n_rows) the test set (Main.scala:52).
 
-    Limits: one engine hosts every worker; no distributed or sampled evaluation, no asynchronous fit, no JNI."""
+    Evaluation as Master evaluates: predict / distributed_loss / distributed_accuracy over the splits fit steps on, as ONE
+    Engine.lg_predict_ranges call (classes signum(x . w): the textbook sign, not the SVM's); local_sampled_loss /
+    local_sampled_accuracy with _SampledEval's stream discipline -- every call spends one whole shuffle of the window from
+    self.rnd, drawn by the device (DSGD_SAMPLED_DEVICE=1, Engine.lg_loss_acc_sampled) or here (sampled_list, then
+    Engine.lg_loss_acc_list), the same numbers and the same generator state either way; for use between fits.
+
+    Limits: one engine hosts every worker (at most 256 of them for the distributed calls); the evaluation is this engine's, not
+    summed over ranks; no asynchronous fit, no JNI."""
 
     def __init__(self, backend, n_train: int, n_rows: int, node_count: int, rnd: Optional[JavaRandom] = None, log=None,
                  metrics: Optional[Metrics] = None, device_lists: Optional[bool] = None, prefetch: bool = True, slices: bool = False):
@@ -1189,6 +1196,64 @@ class LogisticSync:
     def predict_proba(self, rows):
         """P(y = +1 | x) of the listed rows under the resident weights (Engine.lg_predict_proba)."""
         return self.backend.lg_predict_proba(rows)
+
+    # -- Master.predict / distributedLoss / distributedAccuracy (core/Master.scala:61-98) --
+    def _predict_ranges(self, weights, want_proba=False):
+        """ONE Engine.lg_predict_ranges call over the splits fit steps on: (split, its return value)."""
+        split = split_vanilla(self.n_train, self.node_count)   # splitStrategy(data, workers.size)
+        if len(split) > getattr(self.backend, "lg_predict_max_ranges", 256):
+            raise ValueError("%d splits: more than the %d ranges of one lg_predict_ranges call"
+                             % (len(split), getattr(self.backend, "lg_predict_max_ranges", 256)))
+        ranges = [(r.start, r.stop) for r in split]
+        out = self.backend.lg_predict_ranges(ranges, weights, True) if want_proba else self.backend.lg_predict_ranges(ranges, weights)
+        return split, out
+
+    def predict(self, weights=None):
+        """Master.predict (:61-75): (rows, classes) in split order -- rows int64, classes int8 signum(x . w), the textbook
+        sign.  weights: None evaluates the resident weights, a vector replaces them."""
+        split, out = self._predict_ranges(weights)
+        rows = np.concatenate([np.arange(r.start, r.stop, dtype=np.int64) for r in split]) if split else np.zeros(0, np.int64)
+        return rows, np.asarray(out[0])
+
+    def distributed_loss_and_accuracy(self, weights=None):
+        """(distributedLoss, distributedAccuracy) from ONE pass over the splits (the reference runs predict once for each)."""
+        _, out = self._predict_ranges(weights)
+        return out[4], out[5]
+
+    def distributed_loss(self, weights=None):       # Master.scala:87-98
+        return self.distributed_loss_and_accuracy(weights)[0]
+
+    def distributed_accuracy(self, weights=None):   # Master.scala:77-85
+        return self.distributed_loss_and_accuracy(weights)[1]
+
+    # -- Master.localSampledLoss / localSampledAccuracy (core/Master.scala:109-118): _SampledEval's stream discipline --
+    _sampled_window = _SampledEval._sampled_window   # (the window, the refusal of an empty sample, and of a pending prefetch)
+
+    def _sampled(self, samples_count, test):
+        """(loss, accuracy, counts) over one freshly drawn sample: ONE whole shuffle of the window is spent from self.rnd.  With
+        DSGD_SAMPLED_DEVICE=1 the device draws (Engine.lg_loss_acc_sampled); otherwise, or where it refuses (EUNSUPPORTED:
+        nothing was drawn), sampled_list feeds Engine.lg_loss_acc_list -- the same numbers and the same generator state."""
+        lo, hi = self._sampled_window(samples_count, test)
+        k = int(samples_count)
+        if os.environ.get("DSGD_SAMPLED_DEVICE", SAMPLED_DEVICE_DEFAULT) == "1" and hasattr(self.backend, "lg_loss_acc_sampled"):
+            try:
+                loss, acc, counts, state, _ = self.backend.lg_loss_acc_sampled(self.rnd.seed, lo, hi, k)[:5]
+                self.rnd.seed = int(state)
+                return loss, acc, [int(c) for c in counts]
+            except Exception as e:   # (refused: nothing was drawn)
+                if not _SampledEval._refusal(e):
+                    raise
+        idx = (sampled_list(self.rnd, hi - lo, k) + np.int32(lo)).astype(np.int32)
+        loss, acc, counts = self.backend.lg_loss_acc_list(idx)
+        return loss, acc, [int(c) for c in counts]
+
+    def local_sampled_loss(self, samples_count: int, test: bool = False):       # Master.scala:109-112
+        with self.metrics.timer("master.sampled.loss.duration"):
+            return self._sampled(samples_count, test)[0]
+
+    def local_sampled_accuracy(self, samples_count: int, test: bool = False):   # Master.scala:114-118
+        with self.metrics.timer("master.sampled.accuracy.duration"):
+            return self._sampled(samples_count, test)[1]
 
     def _next_plan(self, split, max_samples, batch_size):
         """The next epoch as a logistic plan: its lists drawn by the device where that applies, else by the host."""

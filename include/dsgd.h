@@ -989,7 +989,8 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *              one length word per worker is the exact all-gather; every rank folds the K workers in worker order with the
  *              single context's finish arithmetic.  Several steps of one call are enqueued without host synchronisation
  *   local      dsgd_lg_gradient, dsgd_lg_predict, dsgd_lg_loss_acc and dsgd_lg_loss_acc_ranges enter no collective: the shard,
- *              the shard's own vexp, the figures of a context without a communicator (the caller combines the ranks')
+ *              the shard's own vexp, the figures of a context without a communicator (the caller combines the ranks');
+ *              likewise dsgd_lg_predict_ranges, dsgd_lg_loss_acc_list and dsgd_lg_loss_acc_sampled (below)
  *   refused    DSGD_EUNSUPPORTED, weights untouched: dsgd_plan_create_from_seed_lg (the device draw does not span ranks),
  *              dsgd_plan_create_lg_cs_n, dsgd_plan_create_from_seed_lg_cs, and dsgd_plan_run on a column-slice plan made
  *              before the attach.  Under dsgd_comm_init and on contexts joined by dsgd_comm_init_all every logistic call
@@ -998,12 +999,52 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *              completed step
  * After dsgd_comm_destroy the calls are local again.  Real RCCL with more than one rank has not run; no speed is claimed.
  *
- * LIMITS (out of scope, each refused or simply absent): no JNI / Scala binding; the host mirror is host.LogisticSync
- * (Master.fit's flow on one context, no communicator: no distributed or sampled evaluation, no asynchronous fit;
- * host.MasterSync / MasterAsync stay the SVM's); no fused or persistent one-launch step and no column slices but those of
- * COLUMN SLICES above; no asynchronous engine; no fp64 contexts and no Double feature values; across ranks only what ACROSS
- * RANKS lists -- no device-drawn lists, no column slices, no evaluation over the ranks; no Sparse boundary forms; no
- * predict_ranges.
+ * DISTRIBUTED AND SAMPLED EVALUATION (csrc/dsgd_lg_eval.hpp; ref: core/Master.scala:61-118) -- what dsgd_predict_ranges,
+ * dsgd_loss_acc_list and dsgd_loss_acc_sampled are to the SVM, with the logistic model's sign, loss and fixed-order sums.
+ *
+ * dsgd_lg_predict_ranges: Master.predict / distributedLoss / distributedAccuracy over n_ranges <= 256 disjoint row ranges
+ * (the workers' splits) in ONE launch with ONE synchronisation.  Every row is decided ONCE, on one d = x . w:
+ *   class_out       (may be NULL) one int8 per row, range-major (row row_begin[r] + t at off[r] + t, off the prefix sums of
+ *                   the lengths): signum(d) -- +1, -1, or 0 for d == +-0: the TEXTBOOK sign, not the SVM's.
+ *   proba_out       (may be NULL) sigma(d) per row, range-major: the bits of dsgd_lg_predict over the same rows.  class_out[t]
+ *                   is the sign of the d behind proba_out[t]: p > 0.5 means +1, p < 0.5 means -1.
+ *   counts_out      (may be NULL) 3 exact tallies per range, {#signum(d) == y, #signum(d) == 0, #signum(d) == -y}.
+ *   range_loss_out  (may be NULL) one double per range: the bits of dsgd_lg_loss_acc on range r alone (every range has its
+ *                   own workgroups, the grid of a launch of its own, and its own words of partial sums); 0.0 for an empty
+ *                   range.  counts_out[3 r] / rows of r is that call's accuracy.
+ *   loss, acc       (either may be NULL) over all n rows: loss = lambda |w|^2 + (the ranges' sums of l_i, added in range
+ *                   order) / n, acc = (the ranges' first tallies, added) / n; |w|^2 from the same per-workgroup words as
+ *                   dsgd_lg_loss_acc.  The same call gives the same bits.
+ * An empty range (begin == end) is an empty reply: no bytes, zero tallies.  DSGD_EINVAL, nothing written: a null ctx or
+ * null ranges, n_ranges < 1 or > 256, begin > end, ranges that overlap, no rows at all, every output NULL.  Rows outside the
+ * loaded data: DSGD_ERANGE, nothing written.
+ *
+ * dsgd_lg_loss_acc_list: loss and accuracy over the n >= 1 rows idx names, ONE launch.  A row named twice is counted twice.
+ * loss = lambda |w|^2 + (sum of l_i) / n, acc = c0 / n, counts (3, may be NULL) the exact tallies as above; loss and acc may
+ * be NULL.  For idx = b, b + 1, ..., e - 1 the figures are the bits of dsgd_lg_loss_acc(b, e); the same list gives the same
+ * bits every time (a list in another order may differ in the last bits of the loss: the sum follows the list).
+ * DSGD_EINVAL: a null ctx or idx, n < 1; DSGD_ERANGE: an entry outside the loaded rows; nothing written either way.
+ *
+ * dsgd_lg_loss_acc_sampled: dsgd_loss_acc_sampled for this model, word for word -- the same draw on the device from
+ * *jstate (the first n = min(samples_count, len) entries of Random.shuffle(0 until len), entry p naming row row_begin + p),
+ * the same *n_out / *draws_out / idx_out, the same limits (len up to 2^20 rows, at most 512 rejections inside the shuffle)
+ * and beyond them the same DSGD_EUNSUPPORTED with nothing drawn, *jstate untouched and nothing written; len == 1 draws
+ * nothing and evaluates that row.  Its figures are the bits of dsgd_lg_loss_acc_list on idx_out.  DSGD_EINVAL, nothing
+ * written or drawn: a null ctx or jstate, samples_count < 1, row_begin >= row_end; a window outside the loaded rows:
+ * DSGD_ERANGE.
+ *
+ * All three: w == NULL uses the resident weights, otherwise w replaces them (as in dsgd_lg_loss_acc).  The family's other
+ * refusals hold (above): an fp64 context and a communicator of dsgd_comm_init / dsgd_comm_init_all DSGD_EUNSUPPORTED, no data
+ * or a running lock-free engine DSGD_ESTATE.  Under dsgd_comm_init_lg they are LOCAL: no collective is entered, the figures
+ * are the shard's.  They leave the weights, the accumulators and the cached |w|^2 words as dsgd_lg_loss_acc leaves them: a
+ * step, a gradient or an evaluation behind them gives the bits it gives without them.
+ *
+ * LIMITS (out of scope, each refused or simply absent): no JNI / Scala binding and nothing in include/dsgd.hpp; the host
+ * mirror is host.LogisticSync (Master.fit's flow and Master's evaluation calls on one context, no communicator: no
+ * asynchronous fit; host.MasterSync / MasterAsync stay the SVM's); no fused or persistent one-launch step and no column
+ * slices but those of COLUMN SLICES above; no asynchronous engine; no fp64 contexts and no Double feature values; across ranks
+ * only what ACROSS RANKS lists -- no device-drawn lists, no column slices, no evaluation summed over the ranks; no Sparse
+ * boundary forms.
  *
  * dsgd_lg_gradient: one worker's regularised sum over the listed rows, key order, from the resident weights or from w
  * (which then replaces them, as in dsgd_gradient).  dsgd_lg_sync_step / _ranges: one step over K lists / K row
@@ -1034,6 +1075,15 @@ int dsgd_plan_create_from_seed_lg_cs(dsgd_ctx* ctx, uint64_t* jstate, const int6
                                      int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out);
 int dsgd_lg_loss_acc_ranges(dsgd_ctx* ctx, const float* w /* NULL = resident */, const int64_t* row_begin, const int64_t* row_end, int32_t n_ranges,
                             double* loss_out /* n_ranges */, double* acc_out /* n_ranges */);
+int dsgd_lg_predict_ranges(dsgd_ctx* ctx, const float* w /* NULL = resident */, const int64_t* row_begin, const int64_t* row_end, int32_t n_ranges,
+                           int8_t* class_out /* sum of lengths, may be NULL */, float* proba_out /* sum of lengths, may be NULL */,
+                           int64_t* counts_out /* 3 * n_ranges or NULL */, double* range_loss_out /* n_ranges or NULL */,
+                           double* loss /* may be NULL */, double* acc /* may be NULL */);
+int dsgd_lg_loss_acc_list(dsgd_ctx* ctx, const float* w /* NULL = resident */, const int32_t* idx, int64_t n, double* loss, double* acc,
+                          int64_t* counts /* 3 or NULL */);
+int dsgd_lg_loss_acc_sampled(dsgd_ctx* ctx, const float* w /* NULL = resident */, uint64_t* jstate, int64_t row_begin, int64_t row_end,
+                             int64_t samples_count, double* loss, double* acc, int64_t* counts /* 3 or NULL */,
+                             int32_t* idx_out /* min(samples_count, row_end - row_begin) rows or NULL */, int64_t* n_out, int64_t* draws_out);
 
 #ifdef __cplusplus
 }
