@@ -34,6 +34,11 @@
 
 // m: the hot stream (col = 16-bit ranks); mfull: the whole ranked CSR (long rows).  16-bit cold ids, every cold column in
 // the LDS tile (the host takes the three-launch path otherwise).
+// PACKED: m.col / m.val / cval are the packed copies of the streams (dsgd_pack_streams_kernel: row starts in bit 15 of the hot
+// rank words, y * x as values) and `meta` is not read -- 128 bytes and one request per lane less for every hot tile.  Phase A
+// then leaves y times the cold part in dcold, phase B gates on the row sum itself and writes coef8 as 0 / 1, phase C
+// multiplies y * x by that: the same products, the same integers, the same partial sums as the plain form, bit for bit.
+template <bool PACKED>
 __global__ void __launch_bounds__(1024) dsgd_fstep_kernel(CsrView m, CsrView mfull, const WTile* __restrict__ tiles,
                                                          const unsigned short* __restrict__ meta,
                                                          const WTile* __restrict__ ctiles,
@@ -176,13 +181,13 @@ __global__ void __launch_bounds__(1024) dsgd_fstep_kernel(CsrView m, CsrView mfu
 #define DSGD_FB_PROLOGUE                                 \
   {                                                      \
     w_issue_cols(m, qa, t_end, lane, wt0, A);            \
-    w_issue_vals(m, tt, x.dcold, lane, A);               \
+    w_issue_vals<PACKED>(m, tt, x.dcold, lane, A);       \
     __builtin_amdgcn_sched_barrier(0);                   \
     w_issue_cols(m, qb, t_end, lane, wt1, B);            \
-    w_issue_vals(m, tt, x.dcold, lane, B);               \
+    w_issue_vals<PACKED>(m, tt, x.dcold, lane, B);       \
     __builtin_amdgcn_sched_barrier(0);                   \
     w_issue_cols(m, qc, t_end, lane, wt2, C);            \
-    w_issue_vals(m, tt, x.dcold, lane, C);               \
+    w_issue_vals<PACKED>(m, tt, x.dcold, lane, C);       \
     __builtin_amdgcn_sched_barrier(0);                   \
   }
     WgCopy8 cp;
@@ -206,7 +211,7 @@ __global__ void __launch_bounds__(1024) dsgd_fstep_kernel(CsrView m, CsrView mfu
     if (has_long) {   // (the registers of the first tiles' requests are not live yet on this path: the row sits in them)
       const unsigned long long t_l0 = prof ? __builtin_readcyclecounter() : 0ull;
       for (int t = ch.long_begin + wave; t < ch.long_end; t += stride)
-        w_long_row_regs(mfull, w, x, (long long)long_rows[t], n_all, n_neg, n_pos);
+        w_long_row_regs(mfull, w, x, (long long)long_rows[t], n_all, n_neg, n_pos, PACKED);
       if (prof) {   // [10] cycles wave 0 spent on its long rows, [11] how many workgroups had one
         atomicAdd(&tprof[10], __builtin_readcyclecounter() - t_l0);
         atomicAdd(&tprof[11], 1ull);
@@ -225,7 +230,7 @@ __global__ void __launch_bounds__(1024) dsgd_fstep_kernel(CsrView m, CsrView mfu
       int pend = draw();
 #define DSGD_FB(CUR, FAR)                                                                \
   {                                                                                      \
-    w_tile_q<true>(m, tt, x, qd, qe, t_end, CUR, FAR, wt, n_all, n_neg, n_pos);           \
+    w_tile_q<true, PACKED>(m, tt, x, qd, qe, t_end, CUR, FAR, wt, n_all, n_neg, n_pos);   \
     qa = qb; qb = qc; qc = qd; qd = qe;                                                  \
     qe = __builtin_amdgcn_readfirstlane(pend);                                           \
     pend = draw();                                                                       \

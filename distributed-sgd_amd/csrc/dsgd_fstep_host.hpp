@@ -100,10 +100,43 @@ static int fstep_maybe_rebalance(dsgd_ctx* c, const std::vector<StreamSeg>& row_
   return fstep_build(c, row_segs, L->n_wg, *L);
 }
 
+// The packed copies of the split streams for the kernel's PACKED form, built once per split by the first chunked launch that
+// may use them (on the launch stream, in front of that launch).  *packed: they are there.  No memory for them (6 bytes per
+// hot slot + 4 per cold slot) is no error: the plain form runs, and the split is not asked again.
+static int fstep_packed_streams(dsgd_ctx* c, bool* packed) {
+  *packed = false;
+  if (!fstep_packed_wanted(c->k, route_facts(c)) || c->packed_state < 0) return DSGD_OK;
+  if (c->packed_state == 0) {
+    const size_t nh = (size_t)(c->hot_nnz + WS_PAD), nc = (size_t)(c->coldm_nnz + WS_PAD);
+    hipError_t e = c->d_hcolf.try_alloc(nh);
+    if (e == hipSuccess) e = c->d_hvaly.try_alloc(nh);
+    if (e == hipSuccess) e = c->d_cvaly.try_alloc(nc);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      c->d_hcolf.reset(), c->d_hvaly.reset(), c->d_cvaly.reset();
+      c->packed_state = -1;
+      return DSGD_OK;
+    }
+    // (the padding behind the streams: zero ranks without a flag, zero values)
+    HIP_TRY(hipMemsetAsync(c->d_hcolf + c->hot_nnz, 0, sizeof(unsigned short) * WS_PAD, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_hvaly + c->hot_nnz, 0, sizeof(float) * WS_PAD, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_cvaly + c->coldm_nnz, 0, sizeof(float) * WS_PAD, c->stream));
+    const int blocks = (int)std::max<long long>(1, std::min<long long>((c->n_rows + 3) / 4, (long long)c->n_cu * 16));
+    hipLaunchKernelGGL(dsgd_pack_streams_kernel, dim3(blocks), dim3(256), 0, c->stream, c->n_rows, view(c).label, c->d_hrow_ptr,
+                       c->d_ctp, c->d_hcol, c->d_hval, c->d_cval, c->d_hcolf, c->d_hvaly, c->d_cvaly);
+    HIP_TRY(hipGetLastError());
+    c->packed_state = 1;
+  }
+  *packed = true;
+  return DSGD_OK;
+}
+
 static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int n_wg) {
   const int n_workers = (int)row_segs.size();
   dsgd_ctx::FstepLayout* L = nullptr;
   DSGD_TRY(fstep_layout(c, row_segs, n_wg, &L));
+  bool packed = false;
+  DSGD_TRY(fstep_packed_streams(c, &packed));
   DSGD_TRY(fstep_maybe_rebalance(c, row_segs, L));
   ++L->launches;
   c->last_fstep_rebalances = L->rebalances;
@@ -141,13 +174,25 @@ static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
   mh.row_ptr = c->d_hrow_ptr;
   mh.col = reinterpret_cast<const int*>(c->d_hcol.get());   // 16-bit ranks; the kernel reinterprets the pointer
   mh.val = c->d_hval;
+  if (packed) {   // (the same slots, tile tables and chunk records: flags in the rank words, y * x as values)
+    mh.col = reinterpret_cast<const int*>(c->d_hcolf.get());
+    mh.val = c->d_hvaly;
+  }
+  unsigned long long* const wg_times = (c->k.fstep_rebalance && L->rebalances < 2) ? L->d_times.get() : nullptr;
   size_t slot = 0;
   DSGD_TRY(prof_begin(c, &slot));
   c->ctr_known = false;
-  hipLaunchKernelGGL(dsgd_fstep_kernel, grid, dim3(1024), lds, c->stream, mh, view(c), L->d_tiles, L->d_meta, L->d_ctiles, L->d_cmeta,
-                     (const void*)c->d_ccol, c->d_cval, L->d_chunks, c->d_w, c->d_g64, (long long)c->dp, c->d_sc, H, nc, main_scale,
-                     c->fix_scale, c->d_coef8, c->d_dcold, c->d_wlong_rows, c->d_part, c->part_stride, c->d_partc, c->partc_stride,
-                     c->d_tprof, (c->k.fstep_rebalance && L->rebalances < 2) ? L->d_times : nullptr);
+  if (packed)
+    hipLaunchKernelGGL(dsgd_fstep_kernel<true>, grid, dim3(1024), lds, c->stream, mh, view(c), L->d_tiles, L->d_meta, L->d_ctiles,
+                       L->d_cmeta, (const void*)c->d_ccol, c->d_cvaly, L->d_chunks, c->d_w, c->d_g64, (long long)c->dp, c->d_sc, H, nc,
+                       main_scale, c->fix_scale, c->d_coef8, c->d_dcold, c->d_wlong_rows, c->d_part, c->part_stride, c->d_partc,
+                       c->partc_stride, c->d_tprof, wg_times);
+  else
+    hipLaunchKernelGGL(dsgd_fstep_kernel<false>, grid, dim3(1024), lds, c->stream, mh, view(c), L->d_tiles, L->d_meta, L->d_ctiles,
+                       L->d_cmeta, (const void*)c->d_ccol, c->d_cval, L->d_chunks, c->d_w, c->d_g64, (long long)c->dp, c->d_sc, H, nc,
+                       main_scale, c->fix_scale, c->d_coef8, c->d_dcold, c->d_wlong_rows, c->d_part, c->part_stride, c->d_partc,
+                       c->partc_stride, c->d_tprof, wg_times);
+  c->last_fstep_packed = packed;
   HIP_TRY(hipGetLastError());
   DSGD_TRY(prof_end(c, slot));
   c->last_grad_kernel = "dsgd_fstep_kernel";

@@ -340,6 +340,14 @@ struct dsgd_ctx {
   };
   LayoutCache<FstepLayout> fstep_cache;   // (keyed by the ranges and n_wg)
   int last_fstep_rebalances = 0;     // how often the configuration of the last chunked launch has been re-cut (dsgd_tuning_info)
+  // The chunked launch's PACKED form (csrc/dsgd_fstep.hpp): copies of the split streams, slot for slot -- hot ranks with the
+  // row starts in bit 15, y * x of both streams -- built on the device by the first chunked launch of a split that may use
+  // them (csrc/dsgd_fstep_host.hpp: fstep_packed_streams) and dropped with the streams they copy (packed_drop)
+  DevBuf<unsigned short> d_hcolf;    // hot_nnz + WS_PAD
+  DevBuf<float> d_hvaly;             // hot_nnz + WS_PAD
+  DevBuf<float> d_cvaly;             // coldm_nnz + WS_PAD
+  int packed_state = 0;              // 0: not asked for since the split was built, 1: built, -1: no memory for them (the plain form runs)
+  bool last_fstep_packed = false;    // the last chunked launch ran the PACKED form (dsgd_tuning_info slot [0]: 5 instead of 4)
   // Column lists (csrc/dsgd_tcol.hpp): whole-split steps of 10^3 .. 10^5 rows as dot + column-wise gradient + reduce, no
   // partials.  Per (row ranges) configuration the device sorts the ranges' entries by (worker, column) once; a few
   // configurations stay cached.
@@ -700,6 +708,13 @@ template <class L>
 static int layout_room(dsgd_ctx* c, LayoutCache<L>& cache) {
   if (cache.make_room(c->layout_gen, stream_idle(c))) return DSGD_OK;
   return fail(DSGD_EHIP, "hipStreamSynchronize(c->stream): %s", hipGetErrorString(hipGetLastError()));
+}
+// the packed copies of the split streams go where the streams go (build_split, reset_layout); the callers' stream is idle or
+// about to be synchronised by layouts_drop_all
+static void packed_drop(dsgd_ctx* c) {
+  c->d_hcolf.reset(), c->d_hvaly.reset(), c->d_cvaly.reset();
+  c->packed_state = 0;
+  c->last_fstep_packed = false;
 }
 static void layouts_drop_all(dsgd_ctx* c) {
   c->fstep_cache.clear(stream_idle(c));
@@ -1651,6 +1666,7 @@ static int build_split(dsgd_ctx* c) {
   c->d_hcol.reset(), c->d_hval.reset(), c->d_hrow_ptr.reset();
   c->d_ccol.reset(), c->d_cval.reset(), c->d_ctp.reset(), c->d_ctiles.reset(), c->d_cmeta.reset();
   c->d_dcold.reset(), c->d_coef8.reset();
+  packed_drop(c);
   const long long n_rows = c->n_rows;
   const int H = std::min(c->hsplit, c->dp);
   DSGD_TRY(c->d_coef8.alloc((size_t)std::max<long long>(n_rows, 1)));
@@ -1828,6 +1844,7 @@ static int reset_layout(dsgd_ctx* c) {
   //  synchronised the stream)
   c->d_snap[0].reset(), c->d_snap[1].reset();
   c->snap_last = c->snap_best = -1;
+  packed_drop(c);   // (2.9 GB at 8.4 M rows: not kept while the next data is loaded)
   if (c->layout_ready) {
     DSGD_TRY(launch_permute_out(c, c->d_w, c->d_tmp));
     HIP_TRY(hipMemcpyAsync(c->d_w, c->d_tmp, sizeof(float) * c->dp, hipMemcpyDeviceToDevice, c->stream));
@@ -2309,7 +2326,8 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   DSGD_ATTR(dsgd_wseg_kernel<true>);
   DSGD_ATTR(dsgd_wseg_kernel<false>);
   DSGD_ATTR(dsgd_wseg_bound_kernel);
-  DSGD_ATTR(dsgd_fstep_kernel);
+  DSGD_ATTR(dsgd_fstep_kernel<false>);
+  DSGD_ATTR(dsgd_fstep_kernel<true>);
   DSGD_ATTR(dsgd_fstep_bound_kernel);
   if (c->fp64) {   // the fp64 state (csrc/dsgd_cs64.hpp)
     DSGD_TRY_B(c->d_w64.alloc((size_t)c->dp));
@@ -5061,7 +5079,8 @@ int dsgd_tuning_info(dsgd_ctx* c, int32_t* vals, int32_t n) {
   DSGD_TRY(check_ctx(c));
   if (!vals || n < 0 || n > 8) return fail(DSGD_EINVAL, "bad tuning_info arguments");
   std::lock_guard<std::mutex> lk(c->mu);
-  const int32_t all[8] = {4 /* split layout: the only one */, std::min(c->hsplit, c->dp), c->last_shift,
+  // [0]: 4 = the split layout (the only one); 5 = ... and the last chunked launch ran its PACKED form (csrc/dsgd_fstep.hpp)
+  const int32_t all[8] = {c->last_fstep_packed ? 5 : 4, std::min(c->hsplit, c->dp), c->last_shift,
                           c->cold_col16 ? 1 : 0, c->k.plan_kernel ? 1 : 0, c->k.fix_bound ? 1 : 0, c->last_fstep_rebalances,
                           c->group};
   for (int i = 0; i < n; ++i) vals[i] = all[i];

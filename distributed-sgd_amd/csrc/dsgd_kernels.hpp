@@ -897,6 +897,7 @@ struct WRegs {
   long long pos0;      // wave-uniform (scalar registers): window start
   int tc;              // ... clamped tile index
   int r0, nrows, nb;   // wave-uniform: first row, rows, bytes of the window that belong to the tile
+  int ns;              // ... the tile's slots (the PACKED form puts the end mark there)
 };
 
 // the tile record of tile t (clamped), fetched one iteration before w_issue_cols needs it: a load whose
@@ -923,6 +924,7 @@ __device__ __forceinline__ void w_issue_cols(const CsrView& m, int t, int t_end,
   // time -- with three tiles in flight per wave those lines have left the caches again (rocprofv3 FETCH_SIZE was
   // 1.2 x the algorithmic bytes).
   r.nb = (int)(((unsigned int)wt.info >> 16) + 3u & ~3u) * 4;
+  r.ns = (int)((unsigned int)wt.info >> 16);
   typedef int i32x4 __attribute__((ext_vector_type(4)));
   // The hot stream carries 16-BIT column ranks (hot ranks < hsplit <= 65536 always: LDS caps hsplit near 18 K), eight
   // per lane in ONE 16-byte load -- 6 bytes per non-zero instead of 8.  The kernel was moving 5.6 TB/s of physical
@@ -935,6 +937,9 @@ __device__ __forceinline__ void w_issue_cols(const CsrView& m, int t, int t_end,
   const i32x4 a = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, 16 * lane, 0, 0));
   r.c0 = make_int4(a.x, a.y, a.z, a.w);
 }
+// PACKED (the row-chunk kernel's packed form, csrc/dsgd_fstep.hpp): m.col carries the row starts in bit 15 of the rank words
+// and m.val is y * x -- there is no lane descriptor to fetch, one request fewer per lane and tile
+template <bool PACKED = false>
 __device__ __forceinline__ void w_issue_vals(const CsrView& m, const WTables& tt, const float* __restrict__ dcold, int lane,
                                              WRegs& r) {
   const __amdgpu_buffer_rsrc_t rs =
@@ -948,7 +953,7 @@ __device__ __forceinline__ void w_issue_vals(const CsrView& m, const WTables& tt
   r.v1 = make_float4(b.x, b.y, b.z, b.w);
   // lane descriptor, 16 bits (row-start bits | label signs << 8); the local row of the lane's first slot is a wave
   // prefix sum over the start bits (w_rows_below) instead of a stored field
-  r.meta = (tt.meta + (long long)r.tc * 64)[(unsigned int)lane];
+  if (!PACKED) r.meta = (tt.meta + (long long)r.tc * 64)[(unsigned int)lane];
   // The cold part of x.w of the tile's rows, by local row: ONE coalesced load whose address needs the tile record
   // only.  Before round 3 every lane fetched dcold[row ending in this lane] one tile ahead -- an address that needs the
   // lane descriptors, i.e. a load that depends on a load: issued behind the stream requests of the two tiles after it,
@@ -987,6 +992,36 @@ __device__ __forceinline__ int w_rows_below(unsigned int bits) {
   v += dpp_get_i<0x143, 0xc>(v);   // row_bcast:31 -> rows 2 and 3
   return v - pc;
 }
+// ... and the wave's total (wave-uniform), which the PACKED form compares with the tile's row count
+__device__ __forceinline__ int w_rows_below_total(unsigned int bits, int& total) {
+  const int pc = __popc(bits);
+  int v = pc;
+  v += dpp_get_i<0x111, 0xf>(v);   // row_shr:1
+  v += dpp_get_i<0x112, 0xf>(v);   // row_shr:2
+  v += dpp_get_i<0x114, 0xf>(v);   // row_shr:4
+  v += dpp_get_i<0x118, 0xf>(v);   // row_shr:8
+  v += dpp_get_i<0x142, 0xa>(v);   // row_bcast:15 -> rows 1 and 3
+  v += dpp_get_i<0x143, 0xc>(v);   // row_bcast:31 -> rows 2 and 3
+  total = __builtin_amdgcn_readlane(v, 63);
+  return v - pc;
+}
+
+// The PACKED form's start bits: bit 15 of a rank word says "first slot of its row" -- a property of the SLOT, whatever tile
+// looks at it -- so three things turn a lane's eight flags into the descriptor's low byte (csrc/dsgd_layout_host.hpp:
+// packed_lane_bits is the host's copy of these lines, held to wave_tile_meta's bytes by tests/test_packed_streams.py):
+//   * the window is rounded up to 8 slots: flags behind the tile's last slot n belong to the rows after it -- dropped;
+//   * the end mark at slot n (lane n >> 3, bit n & 7) is set here: that slot may lie outside the window (n a multiple of 8,
+//     the end of the stream) or belong to a row that is not the next one's first only by accident of the layout;
+//   * the window starts up to 7 slots before the tile's first row: rows shorter than that may START in front of it.  The
+//     wave's flags then count more than nrows + 1, and lane 0 drops its lowest ones (rare: wave-uniform branch).
+// keep: 0xff, or 0 for a padding tile (its registers hold the clamped record's slots).
+__device__ __forceinline__ unsigned int w_flag_bits(const int4& c0, unsigned int keep) {
+  const unsigned int M = 0x80008000u;
+  // words 2k / 2k + 1 of dword k -> bits 9 + 2k / 25 + 2k, then the two halves interleave
+  const unsigned int a = ((unsigned int)c0.w & M) | (((unsigned int)c0.z & M) >> 2) | (((unsigned int)c0.y & M) >> 4) |
+                         (((unsigned int)c0.x & M) >> 6);
+  return ((a >> 9) | (a >> 24)) & keep;
+}
 
 
 // fixed-point scatter of a lane's eight contributions into the LDS gradient tile.  The host picks the fixed-point
@@ -1008,7 +1043,7 @@ __device__ __forceinline__ void w_scatter(const WCtx& x, const int (&cc)[8], con
 // (w_tile_q: the tile whose requests go out, t_issue, and the one whose record is fetched, t_fetch, are named by the
 //  caller -- the row-chunk kernel hands a workgroup's tiles to its waves as they come free, csrc/dsgd_fstep.hpp;
 //  w_tile is the strided walk of the streaming kernel)
-template <bool SCATTER>
+template <bool SCATTER, bool PACKED = false>
 __device__ __forceinline__ void w_tile_q(const CsrView& m, const WTables& tt, const WCtx& x, int t_issue, int t_fetch,
                                          int t_end, WRegs& cur, WRegs& far, WTile& wt_far, unsigned int& n_all,
                                          unsigned int& n_neg, unsigned int& n_pos);
@@ -1018,7 +1053,10 @@ __device__ __forceinline__ void w_tile(const CsrView& m, const WTables& tt, cons
                                        WTile& wt_far, unsigned int& n_all, unsigned int& n_neg, unsigned int& n_pos) {
   w_tile_q<SCATTER>(m, tt, x, tile + 3 * stride, tile + 4 * stride, t_end, cur, far, wt_far, n_all, n_neg, n_pos);
 }
-template <bool SCATTER>
+// PACKED: the streams are the packed copies (flags in the rank words, y * x as values; dcold holds y times the cold part):
+// every sum below is then y times what it was -- negation commutes with the products, the additions, their rounding and the
+// filter's fabsf -- so yd is the row sum itself, the coefficient is +scale or 0, and coef8 says 0 / 1.
+template <bool SCATTER, bool PACKED>
 __device__ __forceinline__ void w_tile_q(const CsrView& m, const WTables& tt, const WCtx& x, int t_issue, int t_fetch,
                                          int t_end, WRegs& cur, WRegs& far, WTile& wt_far, unsigned int& n_all,
                                          unsigned int& n_neg, unsigned int& n_pos) {
@@ -1028,12 +1066,30 @@ __device__ __forceinline__ void w_tile_q(const CsrView& m, const WTables& tt, co
   const WTile wt_now = wt_far;                                              // record fetched last iteration
   wt_far = w_fetch(tt, t_fetch, t_end);                                     // record used next iteration
   w_issue_cols(m, t_issue, t_end, lane, wt_now, far);
-  w_issue_vals(m, tt, x.dcold, lane, far);   // (values with the column ids: the window descriptor stays in scalar registers)
+  w_issue_vals<PACKED>(m, tt, x.dcold, lane, far);   // (values with the column ids: the window descriptor stays in scalar registers)
 
   const int nrows = cur.nrows;                          // wave-uniform; -1: the whole tile is padding
-  const unsigned int desc = nrows < 0 ? 0u : cur.meta;
-  const unsigned int bits = desc & 255u;
-  const int re_n = w_rows_below(bits);          // local row that ends at the lane's first start
+  unsigned int desc, bits;
+  int re_n;                                     // local row that ends at the lane's first start
+  if (PACKED) {
+    const int n = __builtin_amdgcn_readfirstlane(cur.ns);
+    const unsigned int em = nrows < 0 ? 0u : 1u << (n & 7);       // (scalar; a padding tile: no end mark, em - 1 + em = all ones)
+    bits = w_flag_bits(cur.c0, nrows < 0 ? 0u : 255u);
+    bits = lane == (n >> 3) ? ((bits & (em - 1u + em)) | em) : bits;
+    int total;
+    re_n = w_rows_below_total(bits, total);
+    const int extra = total - nrows - 1;        // starts of earlier rows in the up to 7 slots in front of the tile's first row
+    if (extra > 0) {
+      if (lane == 0)
+        for (int i = 0; i < extra; ++i) bits &= bits - 1u;
+      re_n = w_rows_below(bits);
+    }
+    desc = bits;
+  } else {
+    desc = nrows < 0 ? 0u : cur.meta;
+    bits = desc & 255u;
+    re_n = w_rows_below(bits);
+  }
   const int rf = re_n + (int)(bits & 1u);       // local row of the lane's first slot (a start at slot 0 opens the NEW row)
   // the cold parts of the tile's rows go through the wave's coefficient strip: slot r holds dcold of local row r until the
   // lane that closes row r has read it -- the same lane then overwrites it with the row's gate coefficient (LDS executes a
@@ -1056,8 +1112,8 @@ __device__ __forceinline__ void w_tile_q(const CsrView& m, const WTables& tt, co
       asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0"
           : "=v"(lo4)
           : "v"(2u), "v"(cw[k]));
-      cc[2 * k] = (int)lo4;
-      cc[2 * k + 1] = (int)((cw[k] >> 14) & 0x3fffcu);
+      cc[2 * k] = PACKED ? (int)((cw[k] << 2) & 0x1fffcu) : (int)lo4;                  // (PACKED: ranks < 2^15, the flag bit
+      cc[2 * k + 1] = (int)((cw[k] >> 14) & (PACKED ? 0x1fffcu : 0x3fffcu));           //  stays out of the offset)
     }
   }
   const float vv[8] = {cur.v0.x, cur.v0.y, cur.v0.z, cur.v0.w, cur.v1.x, cur.v1.y, cur.v1.z, cur.v1.w};
@@ -1120,7 +1176,7 @@ __device__ __forceinline__ void w_tile_q(const CsrView& m, const WTables& tt, co
       const bool fin = nb == 1 && r_end >= r_lo && r_end < r_hi;
       const float dc = x.coefw[(nb == 1 && r_end >= 1 && r_end <= nrows) ? r_end : 0];
       const float d = (incoming + head) + dc;              // x . w of that row
-      const bool ypos = (ys & bits) != 0u;
+      const bool ypos = PACKED ? true : (ys & bits) != 0u;
       const float yd = ypos ? d : -d;
       if (SCATTER) {
         const bool active = fin && !(yd < 0.0f);           // ref: core/ml/SparseSVM.scala:27-28
@@ -1180,7 +1236,7 @@ __device__ __forceinline__ void w_tile_q(const CsrView& m, const WTables& tt, co
         if ((bits >> k) & 1u) {
           if (r >= 1 && r <= nrows) {
             const bool in_range = r >= r_lo && r < r_hi;
-            const bool ypos = (ys >> k) & 1u;
+            const bool ypos = PACKED ? true : (ys >> k) & 1u;
             const float dfull = run + x.coefw[r];
             const float yd = ypos ? dfull : -dfull;
             if (SCATTER) {
@@ -1226,9 +1282,12 @@ __device__ __forceinline__ void w_tile_q(const CsrView& m, const WTables& tt, co
 // Run by the waves of dsgd_wseg_kernel after their tiles, from the WHOLE ranked CSR (same LDS weight tile and
 // fixed-point accumulators; cold columns straight to the 64-bit accumulators at the cold scale); rows of 500+
 // non-zeros are 0.5 % of the RCV1-like rows but 3 % of the non-zeros.
+// (unit_gate: coef8 says 0 / 1 instead of 0 / y -- the convention of the row-chunk kernel's PACKED form, whose cold stream
+//  carries y * x; no slot of either stream belongs to a long row, so nothing reads the byte: it is kept consistent)
 template <bool SCATTER>
 __device__ __forceinline__ void w_long_row(const CsrView& m, const float* __restrict__ w, const WCtx& x, long long row,
-                                           unsigned int& n_all, unsigned int& n_neg, unsigned int& n_pos) {
+                                           unsigned int& n_all, unsigned int& n_neg, unsigned int& n_pos,
+                                           bool unit_gate = false) {
   typedef __attribute__((address_space(3))) const volatile float lds_cvfloat;
   const int lane = threadIdx.x & 63;
   const long long start = m.row_ptr[row], end = m.row_ptr[row + 1];
@@ -1254,7 +1313,7 @@ __device__ __forceinline__ void w_long_row(const CsrView& m, const float* __rest
   if (SCATTER) {
     const bool active = !(yd < 0.0f);     // ref: core/ml/SparseSVM.scala:27-28
     if (lane == 0) {
-      x.coef8[row] = (signed char)(active ? (int)y : 0);
+      x.coef8[row] = (signed char)(active ? (unit_gate ? 1 : (int)y) : 0);
       n_all += active;
     }
     if (active) {
@@ -1285,12 +1344,13 @@ __device__ __forceinline__ void w_long_row(const CsrView& m, const float* __rest
 // accumulators: the same bits.
 constexpr int LR_IT = 5;   // 1,280 non-zeros; longer rows take w_long_row
 __device__ __forceinline__ void w_long_row_regs(const CsrView& m, const float* __restrict__ w, const WCtx& x, long long row,
-                                                unsigned int& n_all, unsigned int& n_neg, unsigned int& n_pos) {
+                                                unsigned int& n_all, unsigned int& n_neg, unsigned int& n_pos,
+                                                bool unit_gate = false) {
   typedef __attribute__((address_space(3))) const float lds_cfloat;
   const int lane = threadIdx.x & 63;
   const long long start = m.row_ptr[row], end = m.row_ptr[row + 1];
   if (end - start > 256LL * LR_IT) {
-    w_long_row<true>(m, w, x, row, n_all, n_neg, n_pos);
+    w_long_row<true>(m, w, x, row, n_all, n_neg, n_pos, unit_gate);
     return;
   }
   const float y = (float)m.label[row];
@@ -1329,7 +1389,7 @@ __device__ __forceinline__ void w_long_row_regs(const CsrView& m, const float* _
   const float d = group_sum<64>((a[0] + a[1]) + (a[2] + a[3]));
   const bool active = !(y * d < 0.0f);     // ref: core/ml/SparseSVM.scala:27-28
   if (lane == 0) {
-    x.coef8[row] = (signed char)(active ? (int)y : 0);
+    x.coef8[row] = (signed char)(active ? (unit_gate ? 1 : (int)y) : 0);
     n_all += active;
   }
   if (active) {
@@ -1617,6 +1677,37 @@ __global__ void __launch_bounds__(256) dsgd_split_fill_kernel(CsrView m, int hsp
         else ccol32[cp] = 0u;
         cval[cp] = 0.0f;
       }
+    }
+  }
+}
+
+// The packed copies of the split streams (the row-chunk kernel's PACKED form, csrc/dsgd_fstep.hpp), one wave per row: hcolf =
+// the hot rank with bit 15 set on the FIRST slot of its row (ranks < 2^15: the host checks hsplit), hvaly / cvaly = y * x of
+// the hot / cold stream.  Slot for slot beside the streams they copy: every tile table addresses both.  Long rows own no
+// slot; the padding behind the streams is cleared by the host.  (csrc/dsgd_layout_host.hpp: packed_streams_ref is the host's
+// statement of the same construction.)
+__global__ void __launch_bounds__(256) dsgd_pack_streams_kernel(long long n_rows, const signed char* __restrict__ label,
+                                                               const long long* __restrict__ hrow_ptr,
+                                                               const long long* __restrict__ ctp,
+                                                               const unsigned short* __restrict__ hcol,
+                                                               const float* __restrict__ hval, const float* __restrict__ cval,
+                                                               unsigned short* __restrict__ hcolf, float* __restrict__ hvaly,
+                                                               float* __restrict__ cvaly) {
+  const int lane = threadIdx.x & 63;
+  const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const long long n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
+  for (long long row = wave; row < n_rows; row += n_waves) {
+    const long long h0 = hrow_ptr[row], h1 = hrow_ptr[row + 1];
+    const long long c0 = ctp[row], c1 = ctp[row + 1];
+    const bool pos = label[row] > 0;
+    for (long long e = h0 + lane; e < h1; e += 64) {
+      const float v = hval[e];
+      hcolf[e] = (unsigned short)(hcol[e] | (e == h0 ? 0x8000u : 0u));
+      hvaly[e] = pos ? v : -v;
+    }
+    for (long long e = c0 + lane; e < c1; e += 64) {
+      const float v = cval[e];
+      cvaly[e] = pos ? v : -v;
     }
   }
 }

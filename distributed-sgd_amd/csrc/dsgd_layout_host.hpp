@@ -423,3 +423,41 @@ inline bool vt_tables(const int* idx, const long long* offsets, long long n_step
   }
   return true;
 }
+
+// ---- the packed copies of the split streams (the row-chunk kernel's PACKED form, csrc/dsgd_fstep.hpp) ------------------
+// What dsgd_pack_streams_kernel builds on the device, stated on the host: for the slots [row_ptr[i], row_ptr[i + 1]) of every
+// row, colf = the 16-bit rank with bit 15 set on the row's FIRST slot (col = nullptr: no ranks, the cold stream) and valy =
+// label[i] > 0 ? x : -x.  A pure function of the slot: whichever tile table addresses the stream reads the same words.
+inline void packed_streams_ref(const long long* row_ptr, long long n_rows, const signed char* label, const unsigned short* col,
+                               const float* val, unsigned short* colf, float* valy) {
+  for (long long i = 0; i < n_rows; ++i)
+    for (long long e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
+      if (col) colf[e] = (unsigned short)(col[e] | (e == row_ptr[i] ? 0x8000u : 0u));
+      valy[e] = label[i] > 0 ? val[e] : -val[e];
+    }
+}
+// The start bits of a tile's 64 lanes as the PACKED kernel derives them (w_tile_q, csrc/dsgd_kernels.hpp -- the same steps in
+// the same order): the flags of the window's slots, a window of the tile's slots rounded up to 8 (a lane beyond it reads
+// zeros); in lane n >> 3 the flags behind slot n dropped and the end mark set at n; and, where the wave then counts more
+// starts than the tile's rows + 1, that many of lane 0's lowest flags dropped (rows that start in the up to 7 slots between
+// pos0 and the tile's first row).  colf: the flagged ranks, n_words of them (the stream and its padding).
+inline void packed_lane_bits(const WTile& T, const unsigned short* colf, long long n_words, unsigned int (&bits)[64]) {
+  const int nrows = (int)(short)(T.info & 0xffff);
+  const int n = (int)((unsigned int)T.info >> 16);
+  const int window = (n + 7) & ~7;
+  int total = 0;
+  for (int l = 0; l < 64; ++l) {
+    unsigned int b = 0;
+    for (int k = 0; k < 8; ++k) {
+      const int slot = 8 * l + k;
+      const long long e = T.pos0 + slot;
+      if (slot < window && e >= 0 && e < n_words && (colf[e] & 0x8000u)) b |= 1u << k;
+    }
+    if (nrows < 0) b = 0;
+    const unsigned int em = nrows < 0 ? 0u : 1u << (n & 7);
+    if (l == (n >> 3)) b = (b & (em - 1u + em)) | em;
+    bits[l] = b;
+    for (unsigned int x = b; x; x &= x - 1u) ++total;
+  }
+  for (int extra = total - nrows - 1; extra > 0; --extra) bits[0] &= bits[0] - 1u;
+}

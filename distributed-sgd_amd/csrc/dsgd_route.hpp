@@ -21,6 +21,7 @@
 // ------------------------------------------------------------------------------------------------
 // knobs: fixed at dsgd_create
 // ------------------------------------------------------------------------------------------------
+constexpr bool FSTEP_PACKED_DEFAULT = true;   // (measured: every run of five faster than every run of the parent's library, profiles/fstep_packed_ab.txt)
 struct Knobs {
   // -- the fixed-point grid
   int max_shift = FIX_SHIFT;         // DSGD_FIX_SHIFT: cap of the per-launch fixed-point shift of the split layout
@@ -41,6 +42,10 @@ struct Knobs {
                                      //    3.2 M 374 -> 343, 6.7 M 699 -> 663; at 18.5 K rows the row-wise kernel stays ahead: 37 vs 35-41)
   long long fstep_rows = 512;        // DSGD_FSTEP_ROWS: a chunk holds at least this many rows (fewer workgroups for small ranges:
                                      //   every workgroup moves 378 KB of LDS tiles in and out whatever its chunk)
+  bool fstep_packed = FSTEP_PACKED_DEFAULT;   // DSGD_FSTEP_PACKED=0: the chunked launch on the plain streams.  Default: on packed copies of the split streams (row starts in
+                                     //   bit 15 of the hot rank words, y * x as values: no hot lane tables, 128 bytes and one request per
+                                     //   lane less per hot tile; 6 bytes per hot slot + 4 per cold slot of extra device memory).  Read
+                                     //   by knobs_read beside the table below; the measurement behind the default: profiles/fstep_packed_ab.txt
   bool tcol_enable = true;           // DSGD_TCOL=0: such ranges through the row-wise kernel
   long long tcol_min = 512;          // DSGD_TCOL_MIN / DSGD_TCOL_MAX: row ranges of this many rows in total take the column lists
   long long tcol_max = 98303;        //   (above: row chunks, dsgd_fstep.hpp.  Measured, whole-split steps, us, row-wise / chunks / columns:
@@ -163,6 +168,8 @@ inline void knobs_read(Knobs& k, Lookup lookup) {
       }
     }
   }
+  // (a flag like the table's; outside it: the table's names are the ones tests/cpp/route_test.cpp digests)
+  if (const char* e = lookup("DSGD_FSTEP_PACKED")) k.fstep_packed = atoi(e) != 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -203,6 +210,12 @@ inline int fstep_grid(const Knobs& k, const RouteFacts& f, int n_workers, long l
   if (n_workers > f.n_cu) return 0;
   const long long per_worker = std::max<long long>(1, f.n_cu / n_workers);
   return (int)std::max<long long>(1, std::min(per_worker, std::min(smallest, tot) / std::max<long long>(1, k.fstep_rows)));
+}
+// may a chunked launch (fstep_grid > 0) run its PACKED form?  The hot ranks must leave bit 15 of their 16-bit words free; the
+// extra memory is asked for where the copies are built (csrc/dsgd_fstep_host.hpp: no memory -> the plain form).
+constexpr int FSTEP_PACKED_MAX_HOT = 32768;
+inline bool fstep_packed_wanted(const Knobs& k, const RouteFacts& f) {
+  return k.fstep_packed && std::min(f.hsplit, f.dp) <= FSTEP_PACKED_MAX_HOT;
 }
 inline bool tcol_wanted(const Knobs& k, const RouteFacts& f, long long tot, int n_workers) {
   return k.tcol_enable && tot >= k.tcol_min && tot <= k.tcol_max && n_workers <= TC_MAX_WORKERS && f.n_rows < ROWS_32BIT &&

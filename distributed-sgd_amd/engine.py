@@ -884,7 +884,10 @@ class Engine:
             n -= 1
         if n == 6:
             check(self._lib.dsgd_tuning_info(self._ctx, v, C.c_int32(6)))
-        return TuningInfo(zip(TuningInfo.SLOTS[:max(n, 7)], [int(x) for x in v]))
+        info = TuningInfo(zip(TuningInfo.SLOTS[:max(n, 7)], [int(x) for x in v]))
+        # slot [0]: 4 = the split layout; 5 = ... whose last row-chunk launch read the packed copies of the streams (DSGD_FSTEP_PACKED)
+        info["fstep_packed"] = int(info["stream_mode"] == 5)
+        return info
 
     def column_ranks(self):
         """Internal frequency rank of every key (D + 1 entries); identical on all ranks of a communicator."""
