@@ -55,6 +55,7 @@ SYMBOLS = [
     "dsgd_plan_create_lg_cs_n", "dsgd_plan_create_from_seed_lg_cs",
     "dsgd_comm_init_lg",
     "dsgd_lg_predict_ranges", "dsgd_lg_loss_acc_list", "dsgd_lg_loss_acc_sampled",
+    "dsgd_lg_async_step", "dsgd_lg_update_grad", "dsgd_async_plan_create_lg", "dsgd_async_plan_create_lg_cs", "dsgd_plan_run_async_lg",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -159,6 +160,15 @@ def load():
         lib.dsgd_lg_loss_acc_list.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.dsgd_lg_loss_acc_sampled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "dsgd_lg_async_step"):   # the logistic model's asynchronous iteration
+        # (ctx, idx*, n, lr, delta_out*, stats*)
+        lib.dsgd_lg_async_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]
+        lib.dsgd_lg_update_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]   # (ctx, key*, dv*, nnz)
+        for name in ("dsgd_async_plan_create_lg", "dsgd_async_plan_create_lg_cs"):
+            # (ctx, assigned_begin*, assigned_end*, n_workers, batch, seed, positional_bug, first_update, n_updates, out*)
+            getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int64, C.c_int64,
+                                           C.c_void_p]
+        lib.dsgd_plan_run_async_lg.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double]   # (ctx, plan, begin, end, lr)
     if hasattr(lib, "dsgd_dense_plan_create"):   # (handles are 64-bit: without argtypes ctypes would pass them as C ints)
         lib.dsgd_dense_step_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float]
         lib.dsgd_dense_loss_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

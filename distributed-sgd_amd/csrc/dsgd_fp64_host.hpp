@@ -949,7 +949,7 @@ int dsgd_plan_run_f64(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t ste
 int dsgd_plan_run_async_f64(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_end, double lr) {
   DSGD_TRY(check_ctx(c));
   DSGD_TRY(plan_steps_check(p, step_begin, step_end));
-  if (p->lg) return fail(DSGD_EUNSUPPORTED, "dsgd_plan_run_async_f64: a logistic plan has no asynchronous iteration");
+  if (p->lg) return fail(DSGD_EUNSUPPORTED, "dsgd_plan_run_async_f64: a logistic plan's asynchronous iterations run through dsgd_plan_run_async_lg, on an fp32 context");
   std::lock_guard<std::mutex> lk(c->mu);
   DSGD_TRY(require_fp64(c, "dsgd_plan_run_async_f64"));
   DSGD_TRY(refuse_fp64_comm(c, "dsgd_plan_run_async_f64"));

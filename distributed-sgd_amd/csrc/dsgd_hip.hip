@@ -131,6 +131,7 @@ static bool available() {
 #include "dsgd_batch.hpp"
 #include "dsgd_cs.hpp"
 #include "dsgd_lg_cs.hpp"   // (the logistic model on column slices: the cell layout and the exchange above, logistic arithmetic)
+#include "dsgd_lg_cs_async.hpp"   // (its asynchronous iterations of a one-worker plan: a sibling body, the kernel above untouched)
 #include "dsgd_dense.hpp"
 #include "dsgd_fstep.hpp"
 #include "dsgd_tcol.hpp"
@@ -549,6 +550,11 @@ struct dsgd_ctx {
   long long lg_pending_active = 0;         // rows of logistic plan runs since the last dsgd_synchronize (every row contributes)
   DevBuf<WorkSeg> d_lg_ssegs;
   DevBuf<float> d_lg_p;
+  // Its asynchronous iteration (dsgd_lg_async_step, dsgd_lg_update_grad), grown on demand: the delta in rank order and, behind
+  // it, in key order ([2][dp]); the keys and values of a peer's update
+  DevBuf<double> d_lg_delta;
+  DevBuf<int> d_lg_upd_key;
+  DevBuf<double> d_lg_upd_dv;
   // Its distributed evaluation (csrc/dsgd_lg_eval.hpp: dsgd_lg_predict_ranges), grown on demand: the table's three arrays at
   // LG_PRED_MAX_RANGES ranges, the tallies [LG_PRED_MAX_RANGES][LG_TALLY_WORDS], one loss word per workgroup, the class bytes
   // (the probabilities go through d_lg_p; the |w|^2 words stay where dsgd_lg_loss_acc keeps them, in d_lg_part)
@@ -3389,15 +3395,18 @@ int dsgd_plan_run(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_en
   return DSGD_OK;
 }
 
-// (rp64: dsgd_async_plan_create_rp64 -- the same lists into a row-parallel plan)
-static int async_plan_impl(dsgd_ctx* c, const char* what, bool rp64, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers,
+// (rp64: dsgd_async_plan_create_rp64 -- the same lists into a row-parallel plan; lg: dsgd_async_plan_create_lg -- into a one-worker
+//  LOGISTIC plan of an fp32 context, csrc/dsgd_lg_calls.hpp)
+static int async_plan_impl(dsgd_ctx* c, const char* what, bool rp64, bool lg, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers,
                            int32_t batch, uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out) {
   DSGD_TRY(check_ctx(c));
   if (!assigned_begin || !assigned_end || !out || n_workers < 1 || batch < 1 || first_update < 0 || n_updates < 1)
     return fail(DSGD_EINVAL, "bad async plan arguments");
   {   // (refused with *out as it was)
     std::lock_guard<std::mutex> lk0(c->mu);
-    if (rp64) {
+    if (lg) {
+      DSGD_TRY(lg_refuse(c, what, LG_ONE_PROCESS));
+    } else if (rp64) {
       DSGD_TRY(require_fp64(c, what));
       DSGD_TRY(refuse_fp64_comm(c, what));
     } else {
@@ -3411,10 +3420,15 @@ static int async_plan_impl(dsgd_ctx* c, const char* what, bool rp64, const int64
   }
   if (n_updates > 0x7fffffffLL) return fail(DSGD_EINVAL, "at most 2^31 - 1 updates per plan");
   std::lock_guard<std::mutex> lk(c->mu);
-  DSGD_TRY(require_fp64(c, what));
-  DSGD_TRY(refuse_fp64_comm(c, what));
-  if (!rp64) DSGD_TRY(refuse_val64(c, what));
+  if (lg) {
+    DSGD_TRY(lg_refuse(c, what, LG_ONE_PROCESS));
+  } else {
+    DSGD_TRY(require_fp64(c, what));
+    DSGD_TRY(refuse_fp64_comm(c, what));
+    if (!rp64) DSGD_TRY(refuse_val64(c, what));
+  }
   DSGD_TRY(bind(c, true));   // (nothing here touches w)
+  if (lg) DSGD_TRY(require_data(c));
   for (int k = 0; k < n_workers; ++k)
     if (assigned_end[k] > c->n_rows)
       return fail(DSGD_ERANGE, "worker %d's rows [%lld, %lld) outside the %lld loaded", k, (long long)assigned_begin[k],
@@ -3422,7 +3436,7 @@ static int async_plan_impl(dsgd_ctx* c, const char* what, bool rp64, const int64
   std::vector<int64_t> offsets((size_t)n_updates + 1);
   for (int64_t u = 0; u <= n_updates; ++u) offsets[(size_t)u] = u * batch;
   dsgd_plan* p = nullptr;
-  DSGD_TRY(plan_frame(c, offsets.data(), n_updates, 1, &p, rp64));
+  DSGD_TRY(plan_frame(c, offsets.data(), n_updates, 1, &p, rp64, lg));
   p->idx_trusted = true;   // (drawn here inside the callers' row ranges)
   p->drawn = true;
   p->fits = false;
@@ -3456,12 +3470,12 @@ static int async_plan_impl(dsgd_ctx* c, const char* what, bool rp64, const int64
 }
 int dsgd_async_plan_create(dsgd_ctx* c, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,
                            uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out) {
-  return async_plan_impl(c, "dsgd_async_plan_create", false, assigned_begin, assigned_end, n_workers, batch, seed, positional_bug, first_update,
+  return async_plan_impl(c, "dsgd_async_plan_create", false, false, assigned_begin, assigned_end, n_workers, batch, seed, positional_bug, first_update,
                          n_updates, out);
 }
 int dsgd_async_plan_create_rp64(dsgd_ctx* c, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,
                                 uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out) {
-  return async_plan_impl(c, "dsgd_async_plan_create_rp64", true, assigned_begin, assigned_end, n_workers, batch, seed, positional_bug,
+  return async_plan_impl(c, "dsgd_async_plan_create_rp64", true, false, assigned_begin, assigned_end, n_workers, batch, seed, positional_bug,
                          first_update, n_updates, out);
 }
 
@@ -4002,6 +4016,44 @@ int dsgd_update_grad(dsgd_ctx* c, const int32_t* key, const float* dv, int64_t n
   }
   c->s_dirty = true;
   HIP_TRY(hipStreamSynchronize(st));   // the update is applied when the call returns (the RPC's Ack, proto.proto:40)
+  return DSGD_OK;
+}
+
+// The logistic model's peer update (include/dsgd.h "THE LOGISTIC MODEL": ASYNCHRONOUS; the state rules are lg_enter's,
+// csrc/dsgd_lg_calls.hpp): Double values, w_k = (float)((double)w_k - dv_k), no filter pass and no running engine beside it.
+int dsgd_lg_update_grad(dsgd_ctx* c, const int32_t* key, const double* dv, int64_t nnz) {
+  DSGD_TRY(check_ctx(c));
+  if (nnz < 0 || (nnz > 0 && (!key || !dv))) return fail(DSGD_EINVAL, "dsgd_lg_update_grad: bad update arguments");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(lg_refuse(c, "dsgd_lg_update_grad", LG_ONE_PROCESS));
+  if (nnz == 0) return DSGD_OK;
+  {   // the keys are host data: validated here, before anything moves (a delta holds each key once)
+    std::vector<unsigned char> seen((size_t)c->dp, 0);
+    for (int64_t i = 0; i < nnz; ++i)
+      if (key[i] < 0 || key[i] >= c->dp)
+        return fail(DSGD_ERANGE, "dsgd_lg_update_grad: key %d at position %lld outside [0, %d]", key[i], (long long)i, c->dp - 1);
+    for (int64_t i = 0; i < nnz; ++i) {
+      if (seen[(size_t)key[i]])
+        return fail(DSGD_EINVAL, "dsgd_lg_update_grad: key %d repeated at position %lld: a delta has unique keys", key[i], (long long)i);
+      seen[(size_t)key[i]] = 1;
+    }
+  }
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, "dsgd_lg_update_grad", LG_ONE_PROCESS, &fresh));
+  if (c->d_lg_upd_key.cap() < (size_t)nnz || c->d_lg_upd_dv.cap() < (size_t)nnz) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    DSGD_TRY(c->d_lg_upd_key.reserve((size_t)std::max<long long>(nnz, c->dp)));
+    DSGD_TRY(c->d_lg_upd_dv.reserve((size_t)std::max<long long>(nnz, c->dp)));
+  }
+  HIP_TRY(hipMemcpyAsync(c->d_lg_upd_key, key, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_lg_upd_dv, dv, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
+  const long long blocks = std::max<long long>(1, std::min<long long>((nnz + LG_THREADS - 1) / LG_THREADS, (long long)c->n_cu * 8));
+  hipLaunchKernelGGL(dsgd_lg_update_kernel, dim3((unsigned)blocks), dim3(LG_THREADS), 0, c->stream, c->d_lg_upd_key.get(), c->d_lg_upd_dv.get(),
+                     (long long)nnz, c->d_perm.get(), c->d_w.get(), c->dp);
+  HIP_TRY(hipGetLastError());
+  c->s_dirty = true;                 // weights that came another way: the SVM's s and every |w|^2 word are stale
+  c->lg_nsq_stamp = ~0ull - 1;
+  HIP_TRY(hipStreamSynchronize(c->stream));   // (key and dv are the caller's: done with before the call returns)
   return DSGD_OK;
 }
 

@@ -327,7 +327,8 @@ int dsgd_plan_create_from_seed_lg_cs(dsgd_ctx* c, uint64_t* jstate, const int64_
 }
 // The steps [step_begin, step_end) of a logistic plan whose column slices are current: ONE launch of dsgd_lg_cs_step_kernel.
 // plan_run_lg made the refusals, bound with the slice-major weights kept and waited for the plan's set-up.
-static int plan_run_lg_cs(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, float lr) {
+// async: the asynchronous iterations of a one-worker plan instead (dsgd_plan_run_async_lg): ONE launch of dsgd_lg_cs_async_kernel.
+static int plan_run_lg_cs(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long long step_end, double lr, bool async = false) {
   const int K = p->n_workers, G = p->cs_G;
   // the weights slice-major for G slices; dimSparsity with them where the context has one (an SVM slice launch that finds
   // the weights sliced for its G reads both)
@@ -353,7 +354,7 @@ static int plan_run_lg_cs(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long 
   a.val = p->d_cs_val;
   a.clist = p->d_cs_cl;
   a.cl_stride = p->cs_cl_stride;
-  cs_common_args(c, a, G, K, lr);
+  cs_common_args(c, a, G, K, (float)lr);
   a.tprof = nullptr;
   a.test_skip_publish = 0;
   a.n_steps_plan = p->n_steps;
@@ -362,16 +363,20 @@ static int plan_run_lg_cs(dsgd_ctx* c, dsgd_plan* p, long long step_begin, long 
   a.slot_stride = p->cs_slot_stride;
   a.row_stride = p->cs_row_stride;
   la.segs = p->d_segs;
-  la.lr = (double)lr;
+  la.lr = lr;
   la.lambda = c->cfg.lambda;
   const size_t lds = sizeof(float) * (size_t)lg_cs_lds(c->dp, G, K).words;
   DSGD_TRY(cs_take_tags(c, (unsigned long long)(step_end - step_begin), &a.tag0));   // (the one counter of both models' launches)
-  if (p->cs_spl == 1)
+  if (async && p->cs_spl == 1)
+    hipLaunchKernelGGL(dsgd_lg_cs_async_kernel<1>, dim3((unsigned)G), dim3(CS_THREADS), lds, c->stream, la);
+  else if (async)
+    hipLaunchKernelGGL(dsgd_lg_cs_async_kernel<2>, dim3((unsigned)G), dim3(CS_THREADS), lds, c->stream, la);
+  else if (p->cs_spl == 1)
     hipLaunchKernelGGL(dsgd_lg_cs_step_kernel<1>, dim3((unsigned)G), dim3(CS_THREADS), lds, c->stream, la);
   else
     hipLaunchKernelGGL(dsgd_lg_cs_step_kernel<2>, dim3((unsigned)G), dim3(CS_THREADS), lds, c->stream, la);
   HIP_TRY(hipGetLastError());
-  c->last_grad_kernel = "dsgd_lg_cs_step_kernel";
+  c->last_grad_kernel = async ? "dsgd_lg_cs_async_kernel" : "dsgd_lg_cs_step_kernel";
   c->fused_apply_pending = false;
   c->s_lazy = false;
   c->nsq_dirty = false;
@@ -983,5 +988,159 @@ int dsgd_lg_loss_acc_sampled(dsgd_ctx* c, const float* w, uint64_t* jstate, int6
   *jstate = jr_jump_dev(s0, (unsigned long long)draws);
   if (n_out) *n_out = n;
   if (draws_out) *draws_out = draws;
+  return DSGD_OK;
+}
+
+// ---- the asynchronous iteration (include/dsgd.h "THE LOGISTIC MODEL": ASYNCHRONOUS; core/Slave.scala:79-111, 177-185) ----
+// The two launches of ONE update over the n positions `seg` names in idx: lg_grad_body with K = 1 into the first slot, then the
+// asynchronous finish (csrc/dsgd_logistic.hpp).  d_delta: NULL or dp doubles, rank order.  lg_ensure(c, 1) came first.
+static int lg_async_launch(dsgd_ctx* c, long long n, double lr, const int* idx, const WorkSeg* seg, double* d_delta) {
+  const LgCall q = lg_local(c, 1);
+  LgArgs a;
+  a.w = c->d_w;
+  a.dp = c->dp;
+  a.vexp = q.vexp;
+  a.K = 1;
+  a.idx = idx;
+  a.segs = seg;
+  a.blocks_per_worker = lg_blocks_per_worker(n, 1, c->n_cu, 2);
+  a.acc = q.own;
+  a.acc_stride = c->lg_stride;
+  a.sc = c->d_sc;
+  hipLaunchKernelGGL(dsgd_lg_grad_kernel, dim3((unsigned)a.blocks_per_worker), dim3(LG_THREADS), 0, c->stream, view(c), a);
+  HIP_TRY(hipGetLastError());
+  c->last_grad_kernel = "dsgd_lg_grad_kernel";
+  LgAsyncArgs f;
+  f.acc = q.own;
+  f.seg = seg;
+  f.dp = c->dp;
+  f.vexp = q.vexp;
+  f.w = c->d_w;
+  f.lr = lr;
+  f.lambda = c->cfg.lambda;
+  f.nsq_part = c->d_lg_part;
+  f.delta = d_delta;
+  hipLaunchKernelGGL(dsgd_lg_async_finish_kernel, dim3((unsigned)lg_finish_blocks(c->dp)), dim3(LG_THREADS), 0, c->stream, f);
+  HIP_TRY(hipGetLastError());
+  return DSGD_OK;
+}
+
+int dsgd_lg_async_step(dsgd_ctx* c, const int32_t* idx, int64_t n, double lr, double* delta_out, dsgd_batch_stats* stats) {
+  DSGD_TRY(check_ctx(c));
+  if (n < 1 || !idx) return fail(DSGD_EINVAL, "dsgd_lg_async_step: Cannot take the mean of an empty list of vectors");
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, "dsgd_lg_async_step", LG_ONE_PROCESS, &fresh));
+  const int64_t nn = n;
+  const LgCheck v = lg_check_lists(&idx, &nn, 1, c->n_rows);
+  DSGD_TRY(lg_report(c, "dsgd_lg_async_step", v, 1));
+  DSGD_TRY(prepare_layout(c));
+  DSGD_TRY(lg_ensure(c, 1));
+  const size_t bytes = sizeof(double) * (size_t)c->dp;
+  if (delta_out) {   // everything that can fail for want of memory comes before the first launch: a failing call changes nothing
+    if (c->d_lg_delta.cap() < 2 * (size_t)c->dp) {
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      DSGD_TRY(c->d_lg_delta.reserve(2 * (size_t)c->dp));
+    }
+    DSGD_TRY(pin_acquire(c->pin_out, bytes));
+  }
+  DSGD_TRY(reset_counters(c));
+  long long mx = 0, tot = 0;
+  DSGD_TRY(stage_lists(c, &idx, &nn, 1, &mx, &tot));
+  double* d_rank = delta_out ? c->d_lg_delta.get() : nullptr;
+  DSGD_TRY(lg_async_launch(c, tot, lr, c->cur_idx, c->d_segs, d_rank));
+  if (delta_out) {   // the delta into key order, then to the host behind the call's one synchronisation
+    double* d_key = d_rank + c->dp;
+    hipLaunchKernelGGL(dsgd_permute64_out_kernel, dim3((c->dp + 255) / 256), dim3(256), 0, c->stream, d_rank, d_key, c->d_perm, c->dp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->pin_out.p, d_key, bytes, hipMemcpyDeviceToHost, c->stream));
+  }
+  DSGD_TRY(lg_step_done(c, lg_local(c, 1), stats, tot));
+  if (delta_out) memcpy(delta_out, c->pin_out.p, bytes);
+  return DSGD_OK;
+}
+
+// (dsgd_lg_update_grad, the peer's side of the delta: csrc/dsgd_hip.hip, beside dsgd_update_grad)
+
+// Updates [first_update, first_update + n_updates) of the zero-lag schedule as a ONE-worker logistic plan whose lists the device
+// draws (dsgd_async_lists_kernel as it stands): dsgd_async_plan_create's arguments; any batch size.
+int dsgd_async_plan_create_lg(dsgd_ctx* c, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,
+                              uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out) {
+  return async_plan_impl(c, "dsgd_async_plan_create_lg", false, true, assigned_begin, assigned_end, n_workers, batch, seed, positional_bug,
+                         first_update, n_updates, out);
+}
+// ... additionally with its column slices laid out.  What the slices can never hold is refused here, before anything is drawn: a
+// batch beyond CS_MAX_SLOTS rows, a model lg_cs_pick_G(dp, 1) finds no slice count for.  The builder's softer declines (slots,
+// the plan cache) leave a plain logistic plan, whose asynchronous run is the row form's.
+int dsgd_async_plan_create_lg_cs(dsgd_ctx* c, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,
+                                 uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out) {
+  const char* what = "dsgd_async_plan_create_lg_cs";
+  DSGD_TRY(check_ctx(c));
+  if (!assigned_begin || !assigned_end || !out || n_workers < 1 || batch < 1 || first_update < 0 || n_updates < 1)
+    return fail(DSGD_EINVAL, "bad async plan arguments");
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    DSGD_TRY(lg_refuse(c, what, LG_ONE_PROCESS));
+    if (batch > CS_MAX_SLOTS)
+      return fail(DSGD_EUNSUPPORTED, "%s: column slices take at most %d rows per update (batch %d); dsgd_async_plan_create_lg takes any", what,
+                  CS_MAX_SLOTS, batch);
+    if (lg_cs_pick_G(c->dp, 1) == 0)
+      return fail(DSGD_EUNSUPPORTED, "%s: a model of %d features does not fit %d column slices (%d words of LDS per slice, at most %d; at "
+                                     "least %d features); dsgd_async_plan_create_lg takes any", what, c->cfg.n_features, LG_CS_G,
+                  lg_cs_lds_words(c->dp, LG_CS_G, 1), DSGD_LDS_FLOATS, 4 * LG_CS_G - 1);
+  }
+  dsgd_plan* p = nullptr;
+  DSGD_TRY(dsgd_async_plan_create_lg(c, assigned_begin, assigned_end, n_workers, batch, seed, positional_bug, first_update, n_updates, &p));
+  const int rc = lg_plan_add_slices(c, p);
+  if (rc != DSGD_OK) {
+    char msg[sizeof(g_err)];
+    snprintf(msg, sizeof(msg), "%s", g_err);
+    (void)dsgd_plan_destroy(c, p);
+    return fail(rc, "%s", msg);
+  }
+  *out = p;
+  return DSGD_OK;
+}
+
+// The asynchronous iterations [step_begin, step_end) of ANY one-worker logistic plan on the resident weights: per update the two
+// launches of dsgd_lg_async_step over the plan's resident lists, no host synchronisation in between -- or, where the plan's
+// column slices are current, ONE launch of dsgd_lg_cs_async_kernel for the whole range.  Every refusal comes before the first
+// launch.  dsgd_synchronize reports the rows.
+int dsgd_plan_run_async_lg(dsgd_ctx* c, dsgd_plan* p, int64_t step_begin, int64_t step_end, double lr) {
+  const char* what = "dsgd_plan_run_async_lg";
+  DSGD_TRY(check_ctx(c));
+  DSGD_TRY(plan_steps_check(p, step_begin, step_end));
+  std::lock_guard<std::mutex> lk(c->mu);
+  DSGD_TRY(lg_refuse(c, what, LG_ONE_PROCESS));
+  if (!p->lg) return fail(DSGD_EUNSUPPORTED, "%s: not a logistic plan (dsgd_plan_run_async_f64 runs the SVM's, on an fp64 context)", what);
+  if (p->n_workers != 1)
+    return fail(DSGD_EINVAL, "%s: an asynchronous iteration is one worker's: this plan has %d workers per step", what, p->n_workers);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, what, LG_ONE_PROCESS, &fresh, p->lg_cs));
+  DSGD_TRY(plan_revalidate(c, p));   // (a plan from before the last load: DSGD_ERANGE here, before anything is enqueued)
+  DSGD_TRY(prepare_layout(c));
+  const bool slices = p->lg_cs && plan_route(c, p) == PLAN_LG_CS && ensure_cs_exchange(c) == DSGD_OK;
+  if (p->lg_cs && !slices) DSGD_TRY(cs_unslice(c));   // (bound with the slice-major weights kept: the row form reads d_w)
+  if (!slices) DSGD_TRY(lg_ensure(c, 1));
+  if (p->built_pending) {   // the plan's set-up ran beside the launch stream: wait for it, once
+    HIP_TRY(hipStreamWaitEvent(c->stream, p->built_ev, 0));
+    p->built_pending = false;
+  }
+  if (step_end <= step_begin) {
+    if (fresh) c->lg_nsq_stamp = c->bind_count;   // (the weights are the ones |w|^2 was taken from)
+    return DSGD_OK;
+  }
+  c->s_dirty = true;
+  c->lg_nsq_stamp = ~0ull - 1;
+  if (slices) {   // ONE launch; it leaves no |w'|^2 words: the next evaluation takes them from dsgd_lg_nsq_kernel
+    DSGD_TRY(plan_run_lg_cs(c, p, step_begin, step_end, lr, true));
+  } else {
+    for (long long t = step_begin; t < step_end; ++t)
+      DSGD_TRY(lg_async_launch(c, p->offsets[(size_t)t + 1] - p->offsets[(size_t)t], lr, p->d_idx, p->d_segs + t, nullptr));
+    c->lg_nsq_stamp = c->bind_count;   // (the last finish left |w'|^2 in d_lg_part)
+  }
+  const long long rows = p->offsets[(size_t)step_end] - p->offsets[(size_t)step_begin];
+  c->pending_samples += rows;
+  c->lg_pending_active += rows;
   return DSGD_OK;
 }

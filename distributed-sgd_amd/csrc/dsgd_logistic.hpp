@@ -42,6 +42,9 @@
 //   dsgd_lg_eval_ranges_kernel  the same for up to 16 row ranges in ONE launch: every range has its own run of workgroups (the grid
 //                             of a launch over it alone: the same bits), its own partial sums and its own tally words
 //   dsgd_lg_predict_kernel    sigma(d) per listed position: 1 / (1 + exp(-d)) in fp64 from the fp32 d, rounded to float once.
+//   dsgd_lg_async_finish_kernel  the finish of ONE worker's ASYNCHRONOUS update behind lg_grad_body with K = 1: the mean over the
+//                             list's n rows, regularised once, w_j' = (float)(w_j - lr r); optionally the double delta
+//   dsgd_lg_update_kernel     a peer's update from (key, dv) pairs: w_k = (float)((double)w_k - dv_k)
 //
 // Plain C++ and vector atomics only.
 #pragma once
@@ -202,6 +205,59 @@ __global__ void __launch_bounds__(LG_THREADS) dsgd_lg_header_kernel(unsigned lon
   for (int g = threadIdx.x; g < K; g += LG_THREADS) {
     const int j = g - first;
     hdr[g] = j >= 0 && j < k ? (unsigned long long)(segs[j].end - segs[j].begin) : 0ull;
+  }
+}
+
+// ---- the ASYNCHRONOUS iteration (include/dsgd.h "THE LOGISTIC MODEL": ASYNCHRONOUS; core/Slave.scala:79-111, 177-185) ----
+// One worker's update over a list of n rows: behind lg_grad_body with K = 1 the finish below takes the MEAN over the list,
+// regularises it once, and leaves the weights and (optionally) the delta a peer applies.  Per column, fp64, contraction off:
+//   G = acc 2^(vexp - S),  gm = G / n,  r = gm + 2 lambda w_j,  delta = lr r,  w_j' = (float)(w_j - delta)
+// one rounding to float; the accumulators left zeroed; |w'|^2 per workgroup in nsq_part by LG_STEP's grid and tree.  For
+// n = 1 these are the bits of dsgd_lg_finish_kernel<LG_STEP> with K = 1 (G / 1.0 = G, 0.0 + (G + reg) = G + reg, G never -0.0).
+struct LgAsyncArgs {
+  unsigned long long* acc;   // [dp] the one worker's slot, zeroed here
+  const WorkSeg* seg;        // the list's [begin, end): its length is n
+  int dp, vexp;
+  float* w;                  // rank order, updated
+  double lr, lambda;
+  double* nsq_part;          // [gridDim.x] |w'|^2 of each workgroup's columns
+  double* delta;             // NULL, or [dp] the delta in RANK order (the host permutes it into key order)
+};
+// grid: lg_finish_blocks(dp) workgroups -- ONE column per lane
+__global__ void __launch_bounds__(LG_THREADS) dsgd_lg_async_finish_kernel(LgAsyncArgs a) {
+#pragma clang fp contract(off)
+  __shared__ double red[LG_THREADS / 64];
+  const int j = blockIdx.x * LG_THREADS + threadIdx.x;
+  double sq = 0.0;
+  if (j < a.dp) {
+    const long long n = a.seg->end - a.seg->begin;
+    const double wj = (double)a.w[j];
+    unsigned long long* at = a.acc + j;
+    const unsigned long long t = *at;
+    if (t != 0ull) *at = 0ull;
+    const double G = (double)(long long)t * ldexp(1.0, a.vexp - lg_shift(n));   // one rounding of the exact sum
+    const double gm = G / (double)n;
+    const double r = gm + (2.0 * a.lambda) * wj;
+    const double delta = a.lr * r;
+    const float wn = (float)(wj - delta);
+    a.w[j] = wn;
+    if (a.delta) a.delta[j] = delta;
+    sq = (double)wn * (double)wn;
+  }
+  const double s = lg_block_sum(sq, red, LG_THREADS / 64);
+  if (threadIdx.x == 0) a.nsq_part[blockIdx.x] = s;
+}
+
+// A peer's update: w_k = (float)((double)w_k - dv_k) for each (unique, host-checked) key -- the expression of the finish above,
+// so replicas that apply every delta keep the bits of the replica that made it.  grid-stride over the nnz pairs.
+__global__ void __launch_bounds__(LG_THREADS) dsgd_lg_update_kernel(const int* __restrict__ key, const double* __restrict__ dv, long long nnz,
+                                                                   const int* __restrict__ perm, float* w, int dp) {
+#pragma clang fp contract(off)
+  for (long long i = (long long)blockIdx.x * LG_THREADS + threadIdx.x; i < nnz; i += (long long)gridDim.x * LG_THREADS) {
+    const int k = key[i];
+    if (k < 0 || k >= dp) continue;   // (the host checked the keys: never taken)
+    const int r = perm[k];
+    w[r] = (float)((double)w[r] - dv[i]);
   }
 }
 

@@ -566,6 +566,44 @@ class Engine:
         total = int(sum(min(batch_size, int(e - b) - s_ * batch_size) for s_ in range(n_steps.value) for b, e in zip(sb, se)))
         return Plan(self, h, n_steps.value, len(sb), total), n_steps.value, int(st.value), draws.value
 
+    # -- the logistic model's asynchronous iteration (include/dsgd.h "THE LOGISTIC MODEL": ASYNCHRONOUS) --
+    def lg_async_step(self, idx, lr, want_delta=False):
+        """One iteration of Slave.asyncTask for the logistic model (dsgd_lg_async_step): the MEAN gradient over the listed rows,
+        regularised once, w <- (float)(w - lr r).  Returns (delta float64 in key order, or None; stats); a peer applies the
+        delta with lg_update_grad and gets the same bits."""
+        idx = i32(idx)
+        delta = np.zeros(self.dp, dtype=np.float64) if want_delta else None
+        st = BatchStats()
+        check(self._lib.dsgd_lg_async_step(self._ctx, ptr(idx), C.c_int64(len(idx)), C.c_double(lr), ptr(delta), C.byref(st)))
+        return delta, {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def lg_update_grad(self, keys, values):
+        """A peer's update (dsgd_lg_update_grad): w[k] = float32(float64(w[k]) - v) for every (unique) key."""
+        keys = i32(keys)
+        values = f64(values)
+        if keys.ndim != 1 or keys.shape != values.shape:
+            raise ValueError("keys / values length mismatch")
+        check(self._lib.dsgd_lg_update_grad(self._ctx, ptr(keys), ptr(values), C.c_int64(len(keys))))
+
+    def lg_async_plan(self, assigned_ranges, batch, seed=0, positional_bug=True, first_update=0, n_updates=1, slices=False):
+        """Updates [first_update, first_update + n_updates) of the zero-lag asynchronous schedule as a one-worker LOGISTIC plan
+        whose lists the device draws (dsgd_async_plan_create_lg; async_plan's arguments and lists).  slices=True
+        (dsgd_async_plan_create_lg_cs): additionally with its column slices, so that plan_run_async_lg is ONE persistent launch;
+        a batch beyond 1,024 rows or a model the slices cannot hold is refused (DSGD_EUNSUPPORTED)."""
+        k = len(assigned_ranges)
+        rb = (C.c_int64 * max(k, 1))(*[int(r[0]) for r in assigned_ranges])
+        re_ = (C.c_int64 * max(k, 1))(*[int(r[1]) for r in assigned_ranges])
+        h = C.c_void_p()
+        create = self._lib.dsgd_async_plan_create_lg_cs if slices else self._lib.dsgd_async_plan_create_lg
+        check(create(self._ctx, rb, re_, C.c_int32(k), C.c_int32(batch), C.c_uint64(seed), C.c_int32(1 if positional_bug else 0),
+                     C.c_int64(first_update), C.c_int64(n_updates), C.byref(h)))
+        return Plan(self, h, int(n_updates), 1, int(n_updates) * int(batch))
+
+    def plan_run_async_lg(self, plan, step_begin, step_end, lr):
+        """Enqueue the asynchronous iterations [step_begin, step_end) of a one-worker logistic plan (lg_async_plan, or lg_plan_flat
+        with n_workers = 1): the bits of lg_async_step on the same lists, or on column slices one persistent launch."""
+        check(self._lib.dsgd_plan_run_async_lg(self._ctx, plan.handle, C.c_int64(step_begin), C.c_int64(step_end), C.c_double(lr)))
+
     predict_max_ranges = 256   # K of one dsgd_predict_ranges call (host.MasterSync asks forward per split beyond it)
 
     def predict_ranges(self, ranges, w=None):

@@ -1349,3 +1349,85 @@ class LogisticSync:
         if state.updates:
             state = GradState(self.backend.get_weights(), state.loss, state.start, state.updates, state.end)
         return state.finish(self.losses[0] if self.losses else None)
+
+
+# ---- MasterAsync.fit for the logistic model ---------------------------------------------------------------------------
+class LogisticAsync:
+    """core/MasterAsync.scala:32-178 for the LOGISTIC model of one engine, on the ZERO-LAG schedule (include/dsgd.h "THE LOGISTIC
+    MODEL": ASYNCHRONOUS) -- the way MasterAsync runs an fp64 backend: one update at a time, update u by worker u mod K at its
+    iteration u div K over SplitStrategy.vanilla's splits, every update seen by all workers before the next one.  One
+    deterministic schedule among those the reference allows (its own is racy); no lock-free engine is started.
+
+    The updates run on one-worker logistic plans whose lists the device draws (Engine.lg_async_plan), CHUNK updates per plan,
+    `check_every` of them between two loss checks (Engine.plan_run_async_lg).  A check takes the test loss and accuracy from
+    ONE Engine.lg_loss_acc_ranges call, folds them into the leaky average (MasterAsync.scala:122-125), keeps the best weights
+    (:132-138) and asks the stopping criterion, newest first (:146); the run ends at maxSteps = n_train * max_epoch updates
+    (:83).  `slices` (off by default) asks for the column-slice form: a window of updates is then ONE persistent launch; the
+    lists are the same, the weights deterministic but not the bits of the default form.
+
+    data layout: rows [0, n_train) are the train set, [n_train, n_rows) the test set (Main.scala:52)."""
+
+    CHUNK = 4096   # updates drawn per device plan
+
+    def __init__(self, backend, n_train: int, n_rows: int, node_count: int, log=None, slices: bool = False):
+        if not 0 < n_train < n_rows:
+            raise ValueError("LogisticAsync needs train rows [0, n_train) and test rows [n_train, n_rows)")
+        self.backend, self.n_train, self.n_rows, self.node_count = backend, n_train, n_rows, node_count
+        self.log = log or (lambda *a: None)
+        self.slices = bool(slices)
+        self.test_losses: List[float] = []
+        self.test_accs: List[float] = []
+        self.checks = 0
+
+    def _check(self, leak_loss_coef):
+        """One loss check (MasterAsync.scala:96-146): the leaky average of the test loss / accuracy."""
+        (computed_loss, computed_acc), = self.backend.lg_loss_acc_ranges([(self.n_train, self.n_rows)])
+        prev_l = self.test_losses[0] if self.test_losses else computed_loss
+        prev_a = self.test_accs[0] if self.test_accs else computed_acc
+        loss = leak_loss_coef * computed_loss + (1 - leak_loss_coef) * prev_l   # :122-125
+        acc = leak_loss_coef * computed_acc + (1 - leak_loss_coef) * prev_a
+        self.test_losses.insert(0, loss)
+        self.test_accs.insert(0, acc)
+        self.checks += 1
+        return loss
+
+    def fit(self, initial_weights, max_epoch: int, batch_size: int, learning_rate: float,
+            stopping_criterion: Callable[[Sequence[float]], bool], check_every: int, leak_loss_coef: float,
+            seed: int = 0, positional_bug: bool = True, max_steps: Optional[int] = None) -> GradState:
+        if not (0 <= leak_loss_coef <= 1):
+            raise ValueError("leaking coefficient must be between 0 and 1")  # MasterAsync.scala:97
+        if check_every < 1:
+            raise ValueError("check_every must be at least 1")
+        split = [(r.start, r.stop) for r in split_vanilla(self.n_train, self.node_count)]
+        steps = self.n_train * max_epoch if max_steps is None else max_steps   # :83
+        w0 = np.asarray(initial_weights, dtype=np.float32)
+        self.backend.set_weights(w0)
+        best_w, best_loss = w0.copy(), float("inf")
+        updates, plan, plan_first = 0, None, 0
+        kw = {"slices": True} if self.slices else {}
+        try:
+            while True:
+                loss = self._check(leak_loss_coef)
+                if best_loss > loss:                                                         # :132-138
+                    best_loss, best_w = loss, np.asarray(self.backend.get_weights(), dtype=np.float32).copy()
+                if stopping_criterion(self.test_losses):                                    # :146
+                    self.log("converged to target: stopping computation")
+                    break
+                if updates >= steps:
+                    break
+                target = min(steps, updates + check_every)
+                while updates < target:
+                    if plan is None or updates >= plan_first + plan.n_steps:
+                        if plan is not None:
+                            plan.destroy()
+                        plan, plan_first = None, updates
+                        plan = self.backend.lg_async_plan(split, batch_size, seed=seed, positional_bug=positional_bug, first_update=plan_first,
+                                                          n_updates=min(self.CHUNK, steps - plan_first), **kw)
+                    end = min(target, plan_first + plan.n_steps)
+                    self.backend.plan_run_async_lg(plan, updates - plan_first, end - plan_first, learning_rate)
+                    updates = end
+                self.backend.synchronize()   # (the rows the window ran are collected; the check below reads behind them)
+        finally:
+            if plan is not None:
+                plan.destroy()
+        return GradState(best_w, updates=int(updates)).finish(best_loss)

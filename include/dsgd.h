@@ -1039,12 +1039,44 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  * are the shard's.  They leave the weights, the accumulators and the cached |w|^2 words as dsgd_lg_loss_acc leaves them: a
  * step, a gradient or an evaluation behind them gives the bits it gives without them.
  *
+ * ASYNCHRONOUS (the zero-lag schedule; csrc/dsgd_logistic.hpp, csrc/dsgd_lg_cs_async.hpp; ref: core/Slave.scala:79-111, 177-185,
+ * core/MasterAsync.scala).  One update is ONE worker's, over a list of n >= 1 rows, on the resident fp32 weights: the int64
+ * column sums of dsgd_lg_gradient's launch on S = lg_shift(n), then per column, fp64 with contraction off,
+ *     G = acc 2^(vexp - S),  gm = G / n,  r = gm + 2 lambda w_j,  delta_j = lr r,  w_j' = (float)(w_j - delta_j)
+ * -- the MEAN over the list (not over workers), regularised once, one rounding to float.  For n = 1 the weights are the bits
+ * of dsgd_lg_sync_step with one worker on that row.  The delta is DENSE (plain L2 moves every column) and DOUBLE (the
+ * reference's wire value); a peer applies w_k = (float)((double)w_k - dv_k), the same expression, so replicas that exchange
+ * every delta stay bit-identical.  lr is a double throughout (the reference's learning rate is a Double).
+ *   dsgd_lg_async_step     one update over idx[0 .. n); delta_out NULL or D + 1 doubles in key order; the statistics and the
+ *                          |w'|^2 words as dsgd_lg_sync_step leaves them.  n < 1 or a null idx: DSGD_EINVAL
+ *   dsgd_lg_update_grad    a peer's (key, dv) pairs.  The keys are checked on the host first: outside [0, D] DSGD_ERANGE, repeated
+ *                          DSGD_EINVAL, the weights unchanged either way; nnz == 0 is a no-op.  The |w|^2 words are stale
+ *                          afterwards, as for weights set by the caller
+ *   dsgd_async_plan_create_lg, dsgd_async_plan_create_lg_cs   dsgd_async_plan_create's arguments on an fp32 context: updates
+ *                          [first_update, first_update + n_updates) of the schedule -- update u is worker u mod K at its
+ *                          iteration u div K -- as a ONE-worker logistic plan whose lists the device draws
+ *                          (oracle/hogwild_replay.hog_rows restates them).  The row form takes any batch.  _lg_cs additionally
+ *                          lays out the column slices; a batch beyond 1,024 rows or a model 16 slices cannot hold at one worker
+ *                          is refused at creation (DSGD_EUNSUPPORTED, nothing drawn); COLUMN SLICES' softer declines leave the
+ *                          row form (vals[0] = 7)
+ *   dsgd_plan_run_async_lg the updates [step_begin, step_end) of ANY one-worker logistic plan, a caller's from
+ *                          dsgd_plan_create_lg_n / _lg_cs_n included: two launches per update with no host synchronisation in
+ *                          between (the bits of dsgd_lg_async_step on the same lists), or on current column slices ONE launch
+ *                          of dsgd_lg_cs_async_kernel for the whole range -- COLUMN SLICES' layout, exchange, bounded wait
+ *                          and numerics (deterministic, within tests/logistic_async_bound.py of the fp64 model, not the row
+ *                          form's bits; no |w'|^2 words left).  dsgd_synchronize reports the rows.  dsgd_plan_run on these
+ *                          plans keeps meaning the synchronous step
+ *   refused                nothing enqueued, nothing changed: a plan of more than one worker DSGD_EINVAL; a plan that is not
+ *                          logistic, an fp64 context, ANY communicator attached (dsgd_comm_init_lg's too: the schedule is one
+ *                          process's) DSGD_EUNSUPPORTED; no data or a running lock-free engine DSGD_ESTATE
+ *
  * LIMITS (out of scope, each refused or simply absent): no JNI / Scala binding and nothing in include/dsgd.hpp; the host
- * mirror is host.LogisticSync (Master.fit's flow and Master's evaluation calls on one context, no communicator: no
- * asynchronous fit; host.MasterSync / MasterAsync stay the SVM's); no fused or persistent one-launch step and no column
- * slices but those of COLUMN SLICES above; no asynchronous engine; no fp64 contexts and no Double feature values; across ranks
- * only what ACROSS RANKS lists -- no device-drawn lists, no column slices, no evaluation summed over the ranks; no Sparse
- * boundary forms.
+ * mirrors are host.LogisticSync and host.LogisticAsync (Master.fit's and MasterAsync.fit's flow on one context, no
+ * communicator; host.MasterSync / MasterAsync stay the SVM's); no fused or persistent one-launch step and no column
+ * slices but those of COLUMN SLICES and ASYNCHRONOUS above; no asynchronous engine of the lock-free kind (dsgd_async_start
+ * and dsgd_hogwild_kernel stay the SVM's: their parity rests on gate traces a gateless model does not have); no fp64 contexts
+ * and no Double feature values; across ranks only what ACROSS RANKS lists -- no device-drawn lists, no column slices, no
+ * asynchronous iteration, no evaluation summed over the ranks; no Sparse boundary forms.
  *
  * dsgd_lg_gradient: one worker's regularised sum over the listed rows, key order, from the resident weights or from w
  * (which then replaces them, as in dsgd_gradient).  dsgd_lg_sync_step / _ranges: one step over K lists / K row
@@ -1075,6 +1107,14 @@ int dsgd_plan_create_from_seed_lg_cs(dsgd_ctx* ctx, uint64_t* jstate, const int6
                                      int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out, int64_t* draws_out);
 int dsgd_lg_loss_acc_ranges(dsgd_ctx* ctx, const float* w /* NULL = resident */, const int64_t* row_begin, const int64_t* row_end, int32_t n_ranges,
                             double* loss_out /* n_ranges */, double* acc_out /* n_ranges */);
+int dsgd_lg_async_step(dsgd_ctx* ctx, const int32_t* idx, int64_t n, double lr, double* delta_out /* D+1, key order, or NULL */,
+                       dsgd_batch_stats* stats);
+int dsgd_lg_update_grad(dsgd_ctx* ctx, const int32_t* key, const double* dv, int64_t nnz);
+int dsgd_async_plan_create_lg(dsgd_ctx* ctx, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,
+                              uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out);
+int dsgd_async_plan_create_lg_cs(dsgd_ctx* ctx, const int64_t* assigned_begin, const int64_t* assigned_end, int32_t n_workers, int32_t batch,
+                                 uint64_t seed, int32_t positional_bug, int64_t first_update, int64_t n_updates, dsgd_plan** out);
+int dsgd_plan_run_async_lg(dsgd_ctx* ctx, dsgd_plan* plan, int64_t step_begin, int64_t step_end, double lr);
 int dsgd_lg_predict_ranges(dsgd_ctx* ctx, const float* w /* NULL = resident */, const int64_t* row_begin, const int64_t* row_end, int32_t n_ranges,
                            int8_t* class_out /* sum of lengths, may be NULL */, float* proba_out /* sum of lengths, may be NULL */,
                            int64_t* counts_out /* 3 * n_ranges or NULL */, double* range_loss_out /* n_ranges or NULL */,

@@ -4,7 +4,7 @@ loss and accuracy, fit (sync or async, early stopping by patience / conv-delta),
 accuracy -- with the HIP engine hosting all the workers.
 
     DSGD_DATA_PATH=/data/rcv1 python tools/train.py [--conf application.conf] [--synthetic ROWS] [--device 0] [--weights-out w.txt]
-                                                    [--precision fp64] [--f64-rp-plans] [--model logistic [--lg-plans | --lg-slices]]
+                                                    [--precision fp64] [--f64-rp-plans] [--model logistic [--lg-plans | --lg-slices] [--lg-async]]
 
 --precision fp64: the engine keeps the reference's Double weights (include/dsgd.h "THE FP64 MODE"); an async fit runs the
 zero-lag schedule of host.MasterAsync (one update at a time, every update seen by every worker).
@@ -13,7 +13,7 @@ feature values, more than 4 workers, batches beyond 1,024 rows -- runs as reside
 "THE FP64 MODE", ROW-PARALLEL PLANS); the asynchronous fit then keeps the files' Doubles too.  With a communicator attached
 (one process per GPU, comm_init_f64 / comm_init_f64v) a synchronous epoch then runs as ONE row-parallel plan run per rank on
 host-drawn lists, one agreement between the ranks per epoch, instead of one sync_step_f64 per step.  Off by default.
---model logistic: the logistic model on the same rows (include/dsgd.h "THE LOGISTIC MODEL"; fp32, synchronous): per epoch every
+--model logistic: the logistic model on the same rows (include/dsgd.h "THE LOGISTIC MODEL"; fp32; synchronous unless --lg-async): per epoch every
 worker's split is shuffled on the host and cut into batches, the epoch's steps run as ONE lg_sync_steps call, and lg_loss_acc
 reports train and test log-loss and accuracy.  The default model is the SVM, and nothing changes on its path.
 --lg-plans (with --model logistic): Master.fit's flow instead (host.LogisticSync) -- the lists drawn from the reference's random
@@ -21,6 +21,9 @@ stream, by the device where it can; an epoch as ONE resident logistic plan, the 
 evaluated in one launch; the reference's early stopping (patience / conv-delta) over the test losses.
 --lg-slices (implies --lg-plans): the plans additionally get their column slices -- an epoch is ONE persistent launch where they
 apply (include/dsgd.h "THE LOGISTIC MODEL", COLUMN SLICES; up to 6 workers at RCV1's width, batches up to 1,024 rows in all).
+--lg-async (with --model logistic): MasterAsync.fit's flow on the zero-lag schedule (host.LogisticAsync; include/dsgd.h "THE
+LOGISTIC MODEL", ASYNCHRONOUS): device-drawn one-worker plans, a loss check every check-every updates with the leaky average,
+best weights kept, maxSteps = train rows x max-epochs.  With --lg-slices a window of updates is ONE persistent launch.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,11 +38,16 @@ ap.add_argument("--device", type=int, default=0)
 ap.add_argument("--weights-out", help="write the `idx:value` line of Main.scala:114 here instead of logging it")
 ap.add_argument("--precision", choices=("fp32", "fp64"), default="fp32", help="fp64: the reference's Double arithmetic")
 ap.add_argument("--f64-rp-plans", action="store_true", help="fp64: refused plans run as row-parallel plans, under a communicator too: one plan run per epoch and rank (DSGD_F64_RP_PLANS=1)")
-ap.add_argument("--model", choices=("svm", "logistic"), default="svm", help="logistic: log-loss, probabilities, plain L2 (fp32, synchronous)")
+ap.add_argument("--model", choices=("svm", "logistic"), default="svm", help="logistic: log-loss, probabilities, plain L2 (fp32; synchronous unless --lg-async)")
 ap.add_argument("--lg-plans", action="store_true", help="logistic: Master.fit's flow on resident logistic plans (host.LogisticSync)")
 ap.add_argument("--lg-slices", action="store_true", help="logistic: --lg-plans on column slices, one persistent launch per epoch (host.LogisticSync(slices=True))")
+ap.add_argument("--lg-async", action="store_true", help="logistic: MasterAsync.fit's flow on the zero-lag schedule (host.LogisticAsync); honours --lg-slices")
 a = ap.parse_args()
+if a.lg_async and a.lg_plans:
+    ap.error("--lg-plans and --lg-async are two fits: give one (--lg-slices goes with either)")
 a.lg_plans = a.lg_plans or a.lg_slices
+if a.lg_async and a.model != "logistic":
+    ap.error("--lg-async goes with --model logistic")
 if a.lg_plans and a.model != "logistic":
     ap.error("--lg-plans goes with --model logistic")
 if a.model == "logistic" and a.precision != "fp32":
@@ -95,6 +103,19 @@ with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device, precision=a.precisi
         if a.precision == "fp64" and cfg.async_ and not rp_plans and getattr(data, "val64", None) is not None else "")
     if a.model == "logistic":   # (its own loop; dimSparsity plays no part)
         eng.set_weights(np.zeros(data.dim + 1, dtype=np.float32))
+        if a.lg_async:
+            master = host.LogisticAsync(eng, n_train, data.n_rows, cfg.node_count, log=log, slices=a.lg_slices)
+            l0, a0 = eng.lg_loss_acc(0, n_train)
+            log("initial loss: {}", l0)
+            log("initial accuracy: {}", a0)
+            t0 = time.time()
+            state = master.fit(np.zeros(data.dim + 1, dtype=np.float32), cfg.max_epochs, cfg.batch_size, cfg.learning_rate,
+                               host.EarlyStopping.no_improvement(cfg.patience, cfg.conv_delta, None), cfg.check_every, cfg.leaky_loss)
+            log("fit ({}s, {} updates, {} loss checks, best leaky test loss {})", round(time.time() - t0, 3), state.updates, master.checks, state.loss)
+            lte, ate = eng.lg_loss_acc(n_train, data.n_rows, w=state.grad)
+            log("final test loss: {}", lte)
+            log("final test accuracy: {}", ate)
+            sys.exit(0)
         if a.lg_plans:
             master = host.LogisticSync(eng, n_train, data.n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log, metrics=metrics, slices=a.lg_slices)
             log("initial loss: {}", master.local_loss())
