@@ -56,6 +56,7 @@ SYMBOLS = [
     "dsgd_comm_init_lg",
     "dsgd_lg_predict_ranges", "dsgd_lg_loss_acc_list", "dsgd_lg_loss_acc_sampled",
     "dsgd_lg_async_step", "dsgd_lg_update_grad", "dsgd_async_plan_create_lg", "dsgd_async_plan_create_lg_cs", "dsgd_plan_run_async_lg",
+    "dsgd_plan_create_from_seed_job_lg", "dsgd_lg_eval_job",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -114,7 +115,7 @@ def load():
             fn.restype = C.c_int
     if hasattr(lib, "dsgd_comm_init_f64v"):
         lib.dsgd_comm_init_f64v.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32]
-    for name in ("dsgd_plan_create_from_seed_job", "dsgd_plan_create_from_seed_job_rp64"):
+    for name in ("dsgd_plan_create_from_seed_job", "dsgd_plan_create_from_seed_job_rp64", "dsgd_plan_create_from_seed_job_lg"):
         if hasattr(lib, name):   # (ctx, jstate*, job_len*, n_job, first, n_local, split_begin*, max_samples, batch_size, out*, n_steps*, draws*)
             getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -169,6 +170,9 @@ def load():
             getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int64, C.c_int64,
                                            C.c_void_p]
         lib.dsgd_plan_run_async_lg.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double]   # (ctx, plan, begin, end, lr)
+    if hasattr(lib, "dsgd_lg_eval_job"):   # (ctx, w*, row_begin*, row_end*, n_local, counts_out*, range_loss_out*, loss*, acc*, K_out*)
+        lib.dsgd_lg_eval_job.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
     if hasattr(lib, "dsgd_dense_plan_create"):   # (handles are 64-bit: without argtypes ctypes would pass them as C ints)
         lib.dsgd_dense_step_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float]
         lib.dsgd_dense_loss_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

@@ -128,6 +128,7 @@ static bool available() {
 #include "dsgd_kernels.hpp"
 #include "dsgd_logistic.hpp"   // (the logistic model beside the SVM: its own gradient, finish, evaluation and probabilities)
 #include "dsgd_lg_eval.hpp"    // (... evaluated as Master evaluates: classes and tallies of K row ranges, the rows of a list)
+#include "dsgd_lg_eval_job.hpp"   // (... and the job's evaluation on every rank: the gather record, its fold, the kernel that fills it)
 #include "dsgd_batch.hpp"
 #include "dsgd_cs.hpp"
 #include "dsgd_lg_cs.hpp"   // (the logistic model on column slices: the cell layout and the exchange above, logistic arithmetic)
@@ -562,6 +563,9 @@ struct dsgd_ctx {
   DevBuf<unsigned long long> d_lg_pred_tally;
   DevBuf<double> d_lg_pred_part;
   DevBuf<signed char> d_lg_cls;
+  // The job's evaluation across ranks (csrc/dsgd_lg_eval_job.hpp: dsgd_lg_eval_job): the gather record at LG_PRED_MAX_RANGES
+  // positions, a buffer of its own (dropped after a collective that failed half way)
+  DevBuf<unsigned long long> d_lge_rec;
   // Its column lists (csrc/dsgd_lg_cols.hpp): whole-split steps as coefficients + column-wise gradient + finish.  Per (row
   // ranges) configuration the device sorts the ranges' entries by (worker, column) once; at most eight configurations stay
   // cached (the least recently used one makes room), all dropped by a load.

@@ -261,6 +261,16 @@ int dsgd_plan_create_from_seed_lg(dsgd_ctx* c, uint64_t* jstate, const int64_t* 
   return plan_from_seed_whole(c, "dsgd_plan_create_from_seed_lg", false, jstate, split_begin, split_end, n_splits, max_samples, batch_size, out,
                               n_steps_out, draws_out, true);
 }
+// ... a rank's window of the JOB's lists: dsgd_plan_create_from_seed_job's arguments, limits, refusals and outputs (ONE stream over
+// all n_job workers, the lists of workers first .. first + n_local - 1, any batch size).  A local call: no collective, accepted
+// without a communicator and under dsgd_comm_init_lg's (the scope of dsgd_plan_create_lg_n); dsgd_plan_run on the plan is the
+// collective run of that call's plans.  No column-slice twin: slices do not span ranks.
+int dsgd_plan_create_from_seed_job_lg(dsgd_ctx* c, uint64_t* jstate, const int64_t* job_len, int32_t n_job, int32_t first, int32_t n_local,
+                                      const int64_t* split_begin, int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out,
+                                      int64_t* draws_out) {
+  return plan_from_seed_job(c, "dsgd_plan_create_from_seed_job_lg", false, jstate, job_len, n_job, first, n_local, split_begin, max_samples,
+                            batch_size, out, n_steps_out, draws_out, true);
+}
 
 // ---- logistic plans on column slices (csrc/dsgd_lg_cs.hpp; the decline rule: csrc/dsgd_lg_cs_host.hpp) ----
 static_assert(LG_CS_MAX_SLICE_COLS == CS_MAX_SLICE_COLS, "one cap on a slice's columns for both models");
@@ -903,6 +913,125 @@ int dsgd_lg_predict_ranges(dsgd_ctx* c, const float* w, const int64_t* row_begin
   if (class_out) memcpy(class_out, h_cls, total);
   if (loss) *loss = c->cfg.lambda * nsq + ls_all / (double)t.total;
   if (acc) *acc = (double)right / (double)t.total;
+  return DSGD_OK;
+}
+
+// after a collective of dsgd_lg_eval_job that failed half way: the record goes, the next call starts from a zeroed one (as lg_drop)
+static void lge_drop(dsgd_ctx* c) {
+  (void)hipStreamSynchronize(c->stream);
+  c->d_lge_rec.reset();
+}
+// The JOB's evaluation on every rank (csrc/dsgd_lg_eval_job.hpp; include/dsgd.h "ACROSS RANKS"): this rank's n_local ranges take the
+// positions rank * n_local + j of K = n_local * world.  All local checks, the agreement (lg_agree's record with n_local where a step
+// puts k and -1 where it puts its steps: a rank in a step and a rank in an evaluation disagree too), ONE launch of
+// dsgd_lg_predict_ranges_kernel as it stands, dsgd_lg_eval_fold_kernel, ONE in-place all-reduce of the record, one read-back,
+// lge_fold.  Every output has the bits dsgd_lg_predict_ranges returns on ONE context over the ranks' rows in rank order.
+int dsgd_lg_eval_job(dsgd_ctx* c, const float* w, const int64_t* row_begin, const int64_t* row_end, int32_t n_local, int64_t* counts_out,
+                     double* range_loss_out, double* loss, double* acc, int32_t* K_out) {
+  const char* what = "dsgd_lg_eval_job";
+  DSGD_TRY(check_ctx(c));
+  if (n_local < 1 || !row_begin || !row_end) return fail(DSGD_EINVAL, "%s: bad arguments (null ranges or no range)", what);
+  if (!counts_out && !range_loss_out && !loss && !acc) return fail(DSGD_EINVAL, "%s: every output is null", what);
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool fresh = false;
+  DSGD_TRY(lg_enter(c, what, LG_SPANS, &fresh));
+  const bool ranks = c->comm && c->comm_lg;
+  const int world = ranks ? c->world : 1, rank = ranks ? c->rank : 0;
+  if (n_local > LG_PRED_MAX_RANGES / world)
+    return fail(DSGD_EINVAL, "%s: %d ranges on each of %d ranks (at most %d in the job)", what, n_local, world, LG_PRED_MAX_RANGES);
+  const int k = n_local, K = k * world;
+  const size_t tab_words = (size_t)lg_pred_tab_words(k);
+  std::vector<long long> tab(tab_words);
+  long long* first_block = tab.data();
+  long long* out_off = tab.data() + (2 * k + 1);
+  const LgPredTable t = lg_pred_table(row_begin, row_end, k, c->n_cu, c->n_rows, first_block, tab.data() + (k + 1), out_off);
+  DSGD_TRY(lg_report(c, what, t, row_begin, row_end));
+  DSGD_TRY(prepare_layout(c));
+  DSGD_TRY(lg_ensure(c, 1));
+  const size_t grid = (size_t)t.grid, tally_words = (size_t)k * LG_TALLY_WORDS, rec_words = (size_t)lge_words(K);
+  if (!c->d_lg_pred_tab || !c->d_lge_rec || grid > c->d_lg_pred_part.cap()) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    DSGD_TRY(c->d_lg_pred_tab.reserve((size_t)lg_pred_tab_words(LG_PRED_MAX_RANGES)));
+    DSGD_TRY(c->d_lg_pred_tally.reserve((size_t)LG_PRED_MAX_RANGES * LG_TALLY_WORDS));
+    DSGD_TRY(c->d_lg_pred_part.reserve(std::max<size_t>(grid, (size_t)c->n_cu), Grow::twice));
+    if (!c->d_lge_rec) {   // (zeroed once: the kernel writes or zeroes every word a call's all-reduce covers)
+      const size_t cap = (size_t)lge_words(LG_PRED_MAX_RANGES);
+      DSGD_TRY(c->d_lge_rec.alloc(cap));
+      HIP_TRY(hipMemsetAsync(c->d_lge_rec, 0, sizeof(unsigned long long) * cap, c->stream));
+    }
+  }
+  const long long nb = lg_finish_blocks(c->dp);
+  const size_t pin_bytes = sizeof(double) * (size_t)nb + sizeof(unsigned long long) * rec_words;
+  DSGD_TRY(pin_acquire(c->pin_out, pin_bytes));   // (what can fail for want of memory comes before the agreement)
+  LgCall q;
+  DSGD_TRY(lg_agree(c, what, k, -1, &q));   // (ranks that differ ALL return DSGD_EINVAL here: nothing ran)
+  if (w) DSGD_TRY(set_weights_locked(c, w));
+  DSGD_TRY(lg_nsq_if_stale(c, w || !fresh));
+  DSGD_TRY(reset_counters(c));
+  DSGD_TRY(pin_acquire(c->pin_idx, sizeof(long long) * tab_words));
+  memcpy(c->pin_idx.p, tab.data(), sizeof(long long) * tab_words);
+  HIP_TRY(hipMemcpyAsync(c->d_lg_pred_tab, c->pin_idx.p, sizeof(long long) * tab_words, hipMemcpyHostToDevice, c->stream));
+  DSGD_TRY(pin_sent(c, c->pin_idx));
+  HIP_TRY(hipMemsetAsync(c->d_lg_pred_tally, 0, sizeof(unsigned long long) * tally_words, c->stream));
+  const int hw = lg_eval_hw(c, t.longest, 2 * lg_pred_tab_words(k));   // (the size moves no bit)
+  const size_t lds = sizeof(float) * (size_t)lg_pred_lds_floats(hw, k);
+  LgPredArgs a;
+  a.tab = c->d_lg_pred_tab;
+  a.K = k;
+  a.cls = nullptr;
+  a.proba = nullptr;
+  a.tally = c->d_lg_pred_tally;
+  a.loss_part = c->d_lg_pred_part;
+  hipLaunchKernelGGL(dsgd_lg_predict_ranges_kernel, dim3((unsigned)grid), dim3(LG_EVAL_THREADS), lds, c->stream, view(c), c->d_w, a, hw);
+  HIP_TRY(hipGetLastError());
+  LgeArgs e;
+  e.first_block = c->d_lg_pred_tab;   // (the table's first array)
+  e.loss_part = c->d_lg_pred_part;
+  e.tally = c->d_lg_pred_tally;
+  e.rec = c->d_lge_rec;
+  e.k = k;
+  e.K = K;
+  e.first = (int)lgg_global_worker(rank, k, 0);
+  hipLaunchKernelGGL(dsgd_lg_eval_fold_kernel, dim3((unsigned)k), dim3(LGE_THREADS), 0, c->stream, e);
+  HIP_TRY(hipGetLastError());
+  if (q.ranks) {   // the exact all-gather: every word is non-zero on at most one rank
+    const int r = rccl::AllReduce(c->d_lge_rec.get(), c->d_lge_rec.get(), rec_words, rccl::kInt64, rccl::kSum, c->comm, c->stream);
+    if (r) {
+      lge_drop(c);
+      return fail(DSGD_ERCCL, "%s: ncclAllReduce(the job's ranges): %s", what, rccl::GetErrorString(r));
+    }
+  }
+  double* part = static_cast<double*>(c->pin_out.p.get());
+  unsigned long long* rec = reinterpret_cast<unsigned long long*>(part + nb);
+  int rc = DSGD_OK;
+  hipError_t he = hipMemcpyAsync(part, c->d_lg_part, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, c->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(rec, c->d_lge_rec, sizeof(unsigned long long) * rec_words, hipMemcpyDeviceToHost, c->stream);
+  if (he != hipSuccess) rc = fail(DSGD_EHIP, "%s: reading the record back: %s", what, hipGetErrorString(he));
+  if (rc == DSGD_OK) rc = read_scalars(c);   // the one synchronisation behind the agreement
+  if (rc == DSGD_OK) rc = check_err_flag(c);
+  if (rc != DSGD_OK) {
+    if (q.ranks) {
+      char msg[sizeof(g_err)];
+      snprintf(msg, sizeof(msg), "%s", g_err);
+      lge_drop(c);
+      return fail(rc, "%s", msg);
+    }
+    return rc;
+  }
+  c->lg_nsq_stamp = c->bind_count;
+  for (int j = 0; j < k; ++j) {   // (this rank's own ranges, before anything is written)
+    const unsigned long long* b = rec + lge_at(e.first + j);
+    const long long rows = out_off[j + 1] - out_off[j];
+    if (b[LGE_WRITERS] == 1ull && (long long)(b[LGE_RIGHT] + b[LGE_ZERO] + b[LGE_WRONG]) != rows)
+      return fail(DSGD_ESTATE, "internal: %llu rows tallied of the %lld of range %d", b[LGE_RIGHT] + b[LGE_ZERO] + b[LGE_WRONG], rows, j);
+  }
+  double nsq = 0.0;   // (in order: the same bits on every call and every replica)
+  for (long long i = 0; i < nb; ++i) nsq += part[i];
+  const LgeFold f = lge_fold(rec, K, c->cfg.lambda, nsq, counts_out, range_loss_out, loss, acc);
+  if (f.bad_pos >= 0)
+    return fail(DSGD_ESTATE, "%s: position %d of the job's %d ranges was written by %lld ranks, not by one: the ranks do not agree about "
+                             "the job (nothing was written)", what, f.bad_pos, K, f.writers);
+  if (K_out) *K_out = K;
   return DSGD_OK;
 }
 

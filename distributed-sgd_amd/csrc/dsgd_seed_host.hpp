@@ -10,6 +10,8 @@
 //   dsgd_plan_create_from_seed_job / _rp64   job workers first .. first + n_local - 1 of job_len, any batch size, up to
 //                                            JR_JOB_MAX_REJ rejections, dsgd_jr_slice_job_kernel; the row-parallel form is a
 //                                            LOCAL call that a communicator does not refuse (plan_run_rp64_ranks runs it).
+//   dsgd_plan_create_from_seed_job_lg        (csrc/dsgd_lg_calls.hpp) the job form's draws into a LOGISTIC plan of an fp32 context:
+//                                            a local call, accepted under dsgd_comm_init_lg (plan_run_lg runs it across the ranks).
 // (_rp64: the same draws into a row-parallel plan -- an fp64 context, float or Double data, no limit of the column slices)
 #pragma once
 
@@ -34,7 +36,10 @@ struct SeedRequest {
   int chunks;                       // workgroups per list
   int max_rej;                      // rejections inside one shuffle
   std::string too_large;            // the refusal of a batch beyond max_batch or a split beyond JR_MAX_LEN
-  bool lg = false;                  // a logistic plan (an fp32 context without a communicator: lg_refuse) instead of a column-slice one
+  bool lg = false;                  // a logistic plan (an fp32 context: lg_refuse) instead of a column-slice one.  The whole-job
+                                    // form is one process's; the job form is a local call that dsgd_comm_init_lg's communicator
+                                    // does not refuse (dsgd_plan_run on the plan is the collective run of dsgd_plan_create_lg_n's)
+  LgScope lg_scope() const { return job ? LG_SPANS : LG_ONE_PROCESS; }
 };
 
 struct SeedLaps {   // DSGD_SEED_PROF (tuning: where an epoch's 14 ms go)
@@ -202,7 +207,7 @@ static int plan_from_seed(dsgd_ctx* c, const SeedRequest& r, uint64_t* jstate, i
   {   // (refused with *out as it was)
     std::lock_guard<std::mutex> lk0(c->mu);
     if (r.lg) {
-      DSGD_TRY(lg_refuse(c, r.what, LG_ONE_PROCESS));
+      DSGD_TRY(lg_refuse(c, r.what, r.lg_scope()));
     } else if (r.rp64) {
       DSGD_TRY(require_fp64(c, r.what));
       if (!r.comm_ok) DSGD_TRY(refuse_fp64_comm(c, r.what));
@@ -231,7 +236,7 @@ static int plan_from_seed(dsgd_ctx* c, const SeedRequest& r, uint64_t* jstate, i
   std::lock_guard<std::mutex> lk(c->mu);
   if (!r.comm_ok) DSGD_TRY(refuse_fp64_comm(c, r.what));
   if (!r.rp64) DSGD_TRY(refuse_val64(c, r.what));
-  if (r.lg) DSGD_TRY(lg_refuse(c, r.what, LG_ONE_PROCESS));
+  if (r.lg) DSGD_TRY(lg_refuse(c, r.what, r.lg_scope()));
   DSGD_TRY(bind(c, true));
   for (int i = 0; i < r.n_local; ++i)
     if (r.split_begin[i] + r.len[(size_t)(r.first + i)] > c->n_rows)
@@ -277,7 +282,7 @@ static int plan_from_seed_whole(dsgd_ctx* c, const char* what, bool rp64, uint64
 // a job's share of workers (include/dsgd.h): the stream over all n_job workers, the lists of the n_local hosted here
 static int plan_from_seed_job(dsgd_ctx* c, const char* what, bool rp64, uint64_t* jstate, const int64_t* job_len, int32_t n_job, int32_t first,
                               int32_t n_local, const int64_t* split_begin, int64_t max_samples, int32_t batch_size, dsgd_plan** out,
-                              int64_t* n_steps_out, int64_t* draws_out) {
+                              int64_t* n_steps_out, int64_t* draws_out, bool lg = false) {
   DSGD_TRY(check_ctx(c));
   if (!jstate || !split_begin || !job_len || !out || !n_steps_out || n_job < 1 || batch_size < 1) return fail(DSGD_EINVAL, "bad arguments");
   if (n_local < 1 || first < 0 || (long long)first + n_local > n_job)
@@ -287,6 +292,7 @@ static int plan_from_seed_job(dsgd_ctx* c, const char* what, bool rp64, uint64_t
   const int chunks = (int)(((long long)batch_size + JR_MAX_TAKE - 1) / JR_MAX_TAKE);
   SeedRequest r{what, rp64, rp64, true, std::vector<long long>(job_len, job_len + n_job), first, n_local, split_begin, batch_size, 0x7fffffff, chunks,
                 JR_JOB_MAX_REJ, msg};
+  r.lg = lg;
   return plan_from_seed(c, r, jstate, max_samples, out, n_steps_out, draws_out);
 }
 

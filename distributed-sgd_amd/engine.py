@@ -566,6 +566,44 @@ class Engine:
         total = int(sum(min(batch_size, int(e - b) - s_ * batch_size) for s_ in range(n_steps.value) for b, e in zip(sb, se)))
         return Plan(self, h, n_steps.value, len(sb), total), n_steps.value, int(st.value), draws.value
 
+    def lg_plan_from_seed_job(self, jstate, job_lens, first, split_begins, max_samples, batch_size):
+        """A rank's window of the JOB's epoch as a LOGISTIC plan whose lists the device draws (dsgd_plan_create_from_seed_job_lg):
+        the arguments, the return value -- (plan or None, n_steps, new jstate, draws), the state and the draws the JOB's, the same
+        on every rank -- and the EUNSUPPORTED refusals of plan_from_seed_job.  A local call, accepted without a communicator and
+        under comm_init_lg's; plan_run on the plan is then the collective run of an lg_plan_flat plan.  With first = 0 and every
+        worker hosted here the plan is lg_plan_from_seed's."""
+        jl = np.ascontiguousarray(job_lens, dtype=np.int64)
+        sb = np.ascontiguousarray(split_begins, dtype=np.int64)
+        if jl.ndim != 1 or sb.ndim != 1:
+            raise ValueError("job_lens and split_begins are flat lists")
+        st = C.c_uint64(int(jstate))
+        h = C.c_void_p()
+        n_steps, draws = C.c_int64(0), C.c_int64(0)
+        check(self._lib.dsgd_plan_create_from_seed_job_lg(self._ctx, C.byref(st), ptr(jl), len(jl), int(first), len(sb), ptr(sb), int(max_samples),
+                                                          int(batch_size), C.byref(h), C.byref(n_steps), C.byref(draws)))
+        if not h.value:
+            return None, 0, int(st.value), 0
+        mine = jl[int(first):int(first) + len(sb)]
+        total = int(sum(min(batch_size, int(ln) - s_ * batch_size) for s_ in range(n_steps.value) for ln in mine))
+        return Plan(self, h, n_steps.value, len(sb), total), n_steps.value, int(st.value), draws.value
+
+    def lg_eval_job(self, ranges, w=None):
+        """The JOB's distributedLoss / distributedAccuracy on every rank (dsgd_lg_eval_job; COLLECTIVE under comm_init_lg): this
+        rank's len(ranges) (begin, end) row ranges take the positions rank * len(ranges) + j of a job of K = len(ranges) * world
+        ranges.  Returns (counts int64 [K, 3], range_losses float64 [K], loss, acc), on every rank the bits lg_predict_ranges
+        returns on ONE engine holding the ranks' rows in rank order.  Without a communicator world = 1.  w as in lg_loss_acc."""
+        k = len(ranges)
+        rb = (C.c_int64 * max(k, 1))(*[int(r[0]) for r in ranges])
+        re_ = (C.c_int64 * max(k, 1))(*[int(r[1]) for r in ranges])
+        counts = np.zeros((self.lg_predict_max_ranges, 3), dtype=np.int64)   # (K = k * world is the library's to say)
+        range_loss = np.zeros(self.lg_predict_max_ranges, dtype=np.float64)
+        loss, acc = C.c_double(0), C.c_double(0)
+        K = C.c_int32(0)
+        wv = None if w is None else f32(w, self.dp)
+        check(self._lib.dsgd_lg_eval_job(self._ctx, ptr(wv), rb, re_, C.c_int32(k), ptr(counts), ptr(range_loss), C.byref(loss), C.byref(acc),
+                                         C.byref(K)))
+        return counts[:K.value].copy(), range_loss[:K.value].copy(), loss.value, acc.value
+
     # -- the logistic model's asynchronous iteration (include/dsgd.h "THE LOGISTIC MODEL": ASYNCHRONOUS) --
     def lg_async_step(self, idx, lr, want_delta=False):
         """One iteration of Slave.asyncTask for the logistic model (dsgd_lg_async_step): the MEAN gradient over the listed rows,

@@ -1141,6 +1141,35 @@ class MasterAsync(_DistributedEval, _SampledEval):
 
 
 # ---- Master.fit for the logistic model ---------------------------------------------------------------------------------
+def _logistic_rank_layout(n_train: int, n_rows: int, node_count: int, world: int, rank: int):
+    """(the job's K train splits, k = K / world, the `world` test slices as ranges of global rows) of LogisticSync(ranks=...)."""
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("rank %d of a world of %d" % (rank, world))
+    if not 0 < n_train < n_rows:
+        raise ValueError("train rows [0, n_train) and test rows [n_train, n_rows)")
+    if node_count < world or node_count % world:
+        raise ValueError("a job of %d workers is not k x %d ranks: every rank hosts the same number" % (node_count, world))
+    split = split_vanilla(n_train, node_count)
+    if len(split) != node_count:
+        raise ValueError("SplitStrategy.vanilla cuts %d train rows into %d groups, not %d: some rank would host a worker without rows"
+                         % (n_train, len(split), node_count))
+    tsplit = split_vanilla(n_rows - n_train, world)
+    if len(tsplit) != world:
+        raise ValueError("SplitStrategy.vanilla cuts %d test rows into %d slices, not %d: some rank would hold no test rows"
+                         % (n_rows - n_train, len(tsplit), world))
+    return split, node_count // world, [range(n_train + t.start, n_train + t.stop) for t in tsplit]
+
+
+def logistic_rank_rows(n_train: int, n_rows: int, node_count: int, world: int, rank: int) -> np.ndarray:
+    """The global row numbers rank `rank` of LogisticSync(ranks=(world, rank)) has loaded, in its order: the rows of the job's
+    workers rank * k .. rank * k + k - 1 (k = node_count / world; SplitStrategy.vanilla over the n_train train rows), then test
+    slice `rank` of SplitStrategy.vanilla over the test rows cut into `world`.  ValueError where the job does not cut that way."""
+    split, k, tsplit = _logistic_rank_layout(n_train, n_rows, node_count, world, rank)
+    parts = [np.arange(r.start, r.stop, dtype=np.int64) for r in split[rank * k:(rank + 1) * k]]
+    parts.append(np.arange(tsplit[rank].start, tsplit[rank].stop, dtype=np.int64))
+    return np.concatenate(parts)
+
+
 class LogisticSync:
     """core/Master.scala:120-218 for the LOGISTIC model of one engine (include/dsgd.h "THE LOGISTIC MODEL").
 
@@ -1163,14 +1192,40 @@ class LogisticSync:
     self.rnd, drawn by the device (DSGD_SAMPLED_DEVICE=1, Engine.lg_loss_acc_sampled) or here (sampled_list, then
     Engine.lg_loss_acc_list), the same numbers and the same generator state either way; for use between fits.
 
-    Limits: one engine hosts every worker (at most 256 of them for the distributed calls); the evaluation is this engine's, not
-    summed over ranks; no asynchronous fit, no JNI."""
+    ACROSS RANKS (`ranks=(world, rank)`; the backend is attached with Engine.comm_init_lg; include/dsgd.h "ACROSS RANKS").  n_train,
+    n_rows and node_count stay the JOB's: node_count = K = k x world workers, rank r has loaded logistic_rank_rows(...) -- the rows
+    of the job's workers r k .. r k + k - 1 in order, then test slice r of the test rows cut into `world`.  Per epoch the rank's
+    window of the job's lists comes from Engine.lg_plan_from_seed_job (ONE stream over all K workers) or, where that is refused
+    or switched off, from epoch_lists over the whole job, of which the rank keeps its window mapped to its local rows
+    (Engine.lg_plan_flat): the random stream ends where one process's ends either way.  plan_run is collective; then two
+    Engine.lg_eval_job calls, the k train ranges and the one test range, give train and test loss and accuracy of the JOB --
+    identical on every rank (the bits of ONE engine's lg_predict_ranges over the K splits / the `world` test slices), so every
+    rank takes the same stopping decision with nothing more exchanged.  The weights after every epoch are the bits of the
+    one-process mirror.  distributed_loss / distributed_accuracy / local_loss / local_accuracy go through lg_eval_job (collective);
+    predict returns this rank's rows (global numbers) and classes.  local_sampled_* raise: the sampled window is the master's data,
+    which no rank holds.  slices=True raises: column slices do not span ranks.
+
+    Limits: without `ranks` one engine hosts every worker (at most 256 of them for the distributed calls) and the evaluation is
+    this engine's; with `ranks` at most 256 workers in the job; no asynchronous fit across ranks, no JNI."""
 
     def __init__(self, backend, n_train: int, n_rows: int, node_count: int, rnd: Optional[JavaRandom] = None, log=None,
-                 metrics: Optional[Metrics] = None, device_lists: Optional[bool] = None, prefetch: bool = True, slices: bool = False):
+                 metrics: Optional[Metrics] = None, device_lists: Optional[bool] = None, prefetch: bool = True, slices: bool = False,
+                 ranks: Optional[Sequence[int]] = None):
         if not 0 < n_train < n_rows:
             raise ValueError("LogisticSync needs train rows [0, n_train) and test rows [n_train, n_rows)")
         self.backend, self.n_train, self.n_rows, self.node_count = backend, n_train, n_rows, node_count
+        self.ranks = None
+        if ranks is not None:
+            world, rank = int(ranks[0]), int(ranks[1])
+            if slices:
+                raise ValueError("LogisticSync(ranks=...): column slices do not span ranks (slices=True is one process's)")
+            self._job_split, self._k, tsplit = _logistic_rank_layout(n_train, n_rows, node_count, world, rank)
+            self.ranks = (world, rank)
+            self._first = rank * self._k
+            mine = self._job_split[self._first:self._first + self._k]
+            self._local_begin = [int(b) for b in np.cumsum([0] + [len(r) for r in mine])]   # k + 1: the local train rows end at [-1]
+            self._train_ranges = [(self._local_begin[j], self._local_begin[j + 1]) for j in range(self._k)]
+            self._test_range = (self._local_begin[-1], self._local_begin[-1] + len(tsplit[rank]))
         self.metrics = metrics or Metrics()
         self.rnd = rnd or JavaRandom(0)
         self.log = log or (lambda *a: None)
@@ -1185,11 +1240,20 @@ class LogisticSync:
         self.device_drawn_epochs = 0
         self._pending = None
 
+    def _job_eval(self, test: bool = False, weights=None):
+        """(ranks) (loss, acc) of the JOB's train splits or test slices: ONE collective Engine.lg_eval_job call."""
+        out = self.backend.lg_eval_job([self._test_range] if test else self._train_ranges, weights)
+        return out[2], out[3]
+
     def local_loss(self, test: bool = False):       # Master.scala:104-106
+        if self.ranks:
+            return self._job_eval(test)[0]
         lo, hi = (self.n_train, self.n_rows) if test else (0, self.n_train)
         return self.backend.lg_loss_acc(lo, hi)[0]
 
     def local_accuracy(self, test: bool = False):   # Master.scala:100-102
+        if self.ranks:
+            return self._job_eval(test)[1]
         lo, hi = (self.n_train, self.n_rows) if test else (0, self.n_train)
         return self.backend.lg_loss_acc(lo, hi)[1]
 
@@ -1211,12 +1275,18 @@ class LogisticSync:
     def predict(self, weights=None):
         """Master.predict (:61-75): (rows, classes) in split order -- rows int64, classes int8 signum(x . w), the textbook
         sign.  weights: None evaluates the resident weights, a vector replaces them."""
+        if self.ranks:   # this rank's rows (the job's numbers) and their classes: a local call
+            mine = self._job_split[self._first:self._first + self._k]
+            out = self.backend.lg_predict_ranges(self._train_ranges, weights)
+            return np.concatenate([np.arange(r.start, r.stop, dtype=np.int64) for r in mine]), np.asarray(out[0])
         split, out = self._predict_ranges(weights)
         rows = np.concatenate([np.arange(r.start, r.stop, dtype=np.int64) for r in split]) if split else np.zeros(0, np.int64)
         return rows, np.asarray(out[0])
 
     def distributed_loss_and_accuracy(self, weights=None):
         """(distributedLoss, distributedAccuracy) from ONE pass over the splits (the reference runs predict once for each)."""
+        if self.ranks:
+            return self._job_eval(False, weights)
         _, out = self._predict_ranges(weights)
         return out[4], out[5]
 
@@ -1232,7 +1302,10 @@ class LogisticSync:
     def _sampled(self, samples_count, test):
         """(loss, accuracy, counts) over one freshly drawn sample: ONE whole shuffle of the window is spent from self.rnd.  With
         DSGD_SAMPLED_DEVICE=1 the device draws (Engine.lg_loss_acc_sampled); otherwise, or where it refuses (EUNSUPPORTED:
-        nothing was drawn), sampled_list feeds Engine.lg_loss_acc_list -- the same numbers and the same generator state."""
+        nothing was drawn), sampled_list feeds Engine.lg_loss_acc_list -- the same numbers and the same generator state.
+        Across ranks (ranks=...) it raises: the sampled window is the master's data, which no rank holds."""
+        if self.ranks:
+            raise ValueError("LogisticSync(ranks=...): local_sampled_* draw from the master's data, which no rank holds")
         lo, hi = self._sampled_window(samples_count, test)
         k = int(samples_count)
         if os.environ.get("DSGD_SAMPLED_DEVICE", SAMPLED_DEVICE_DEFAULT) == "1" and hasattr(self.backend, "lg_loss_acc_sampled"):
@@ -1257,6 +1330,8 @@ class LogisticSync:
 
     def _next_plan(self, split, max_samples, batch_size):
         """The next epoch as a logistic plan: its lists drawn by the device where that applies, else by the host."""
+        if self.ranks:
+            return self._next_plan_ranks(split, max_samples, batch_size)
         seed_before = self.rnd.seed
         if self.device_lists and all(r.step == 1 for r in split):
             try:
@@ -1274,6 +1349,35 @@ class LogisticSync:
         kw = {"slices": True} if self.slices else {}
         plan = self.backend.lg_plan_flat(idx, offsets, n_steps, len(split), **kw) if n_steps else None
         return {"plan": plan, "n_steps": n_steps, "n_samples": int(offsets[n_steps * len(split)]), "seed_before": seed_before, "device_drawn": False}
+
+    def _next_plan_ranks(self, split, max_samples, batch_size):
+        """(ranks) This rank's window of the JOB's next epoch: the k hosted workers' lists over the local rows.  The stream advances
+        over the whole job either way."""
+        seed_before = self.rnd.seed
+        k, first = self._k, self._first
+        if self.device_lists:
+            try:
+                plan, n_steps, state, _ = self.backend.lg_plan_from_seed_job(seed_before, [len(r) for r in split], first, self._local_begin[:k],
+                                                                             max_samples, batch_size)
+            except Exception as e:   # (DSGD_EUNSUPPORTED: outside the device form -- the host draws from here on)
+                if getattr(e, "code", None) != -7:
+                    raise
+                self.device_lists = False
+            else:
+                self.rnd.seed = state
+                return {"plan": plan, "n_steps": n_steps, "n_samples": plan.n_samples if plan is not None else 0, "seed_before": seed_before,
+                        "device_drawn": True}
+        idx, offsets, n_steps = epoch_lists(self.rnd, split, max_samples, batch_size)   # the whole job, from the same stream
+        K = len(split)
+        flat, offs = [], [0]
+        for s_ in range(n_steps):
+            for j in range(k):
+                g = s_ * K + first + j
+                rows = np.asarray(idx[int(offsets[g]):int(offsets[g + 1])], dtype=np.int64) - split[first + j].start + self._local_begin[j]
+                flat.append(rows.astype(np.int32))
+                offs.append(offs[-1] + len(rows))
+        plan = self.backend.lg_plan_flat(np.concatenate(flat), np.asarray(offs, dtype=np.int64), n_steps, k) if n_steps else None
+        return {"plan": plan, "n_steps": n_steps, "n_samples": offs[-1], "seed_before": seed_before, "device_drawn": False}
 
     def _drop_pending(self):
         """fit is over: the plan of an epoch that never ran is dropped and the stream goes back to where the reference's stands."""
@@ -1304,7 +1408,10 @@ class LogisticSync:
             # the reference's next batch hands some slave an empty slice: Vec.sum throws there (math/Vec.scala:129)
             raise ValueError("Cannot sum an empty list of vectors (batch %d of the epoch: a worker's slice is empty)" % cur["n_steps"])
         # :206-209 -- the epoch's evaluation passes: one launch, one synchronisation (behind the epoch's steps)
-        (l, a), (tl, ta) = self.backend.lg_loss_acc_ranges([(0, self.n_train), (self.n_train, self.n_rows)])
+        if self.ranks:   # the JOB's figures on every rank: two collective calls, the k train ranges, then the one test range
+            (l, a), (tl, ta) = self._job_eval(False), self._job_eval(True)
+        else:
+            (l, a), (tl, ta) = self.backend.lg_loss_acc_ranges([(0, self.n_train), (self.n_train, self.n_rows)])
         dt = time.perf_counter_ns() - t0
         self.backend.synchronize()   # (the stream is idle: the rows the plan ran are collected)
         for s_ in range(cur["n_steps"]):

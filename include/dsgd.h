@@ -991,12 +991,33 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *   local      dsgd_lg_gradient, dsgd_lg_predict, dsgd_lg_loss_acc and dsgd_lg_loss_acc_ranges enter no collective: the shard,
  *              the shard's own vexp, the figures of a context without a communicator (the caller combines the ranks');
  *              likewise dsgd_lg_predict_ranges, dsgd_lg_loss_acc_list and dsgd_lg_loss_acc_sampled (below)
- *   refused    DSGD_EUNSUPPORTED, weights untouched: dsgd_plan_create_from_seed_lg (the device draw does not span ranks),
- *              dsgd_plan_create_lg_cs_n, dsgd_plan_create_from_seed_lg_cs, and dsgd_plan_run on a column-slice plan made
- *              before the attach.  Under dsgd_comm_init and on contexts joined by dsgd_comm_init_all every logistic call
- *              stays refused
- *   errors     a collective that fails half way: DSGD_ERCCL, the buffer is dropped, the weights are those behind the last
- *              completed step
+ *   lists      dsgd_plan_create_from_seed_job_lg: a rank's window of the JOB's device-drawn lists -- the arguments, limits,
+ *              refusals and *jstate / *n_steps_out / *draws_out of dsgd_plan_create_from_seed_job (ONE stream over all n_job
+ *              workers, the lists of workers first .. first + n_local - 1, any batch size), on an fp32 context with float
+ *              values, into a logistic plan (dsgd_plan_info: 7, nothing laid out).  A LOCAL call: accepted without a
+ *              communicator and under this one; dsgd_plan_run on the plan is the collective run of dsgd_plan_create_lg_n's.
+ *              With first = 0 and n_local = n_job the lists, the step count, the state and the draws are those of
+ *              dsgd_plan_create_from_seed_lg wherever that form accepts the arguments.  There is no column-slice twin
+ *   the job's  dsgd_lg_eval_job (COLLECTIVE): this rank's n_local row ranges take the positions rank * n_local + j of a job of
+ *   evaluation K = n_local * world <= 256 ranges (the global worker order of the steps; without a communicator world = 1).  On
+ *              EVERY rank counts_out (3 K), range_loss_out (K), loss and acc are bit for bit what dsgd_lg_predict_ranges
+ *              returns on ONE context that holds the ranks' rows in rank order, for those K ranges and the same weights: a
+ *              range's workgroups, tree and row order depend on the range and the device alone, the ranking under this
+ *              communicator is the job's, and the |w|^2 words are the same on every replica.  Local checks first (those of
+ *              dsgd_lg_predict_ranges on the local ranges, with its codes); then the agreement above with n_local in k's place
+ *              (ranks that differ, or a rank in a step beside one in an evaluation: DSGD_EINVAL everywhere, nothing ran); ONE
+ *              launch of dsgd_lg_predict_ranges_kernel, dsgd_lg_eval_fold_kernel (csrc/dsgd_lg_eval_job.hpp: per range three
+ *              tallies, the fp64 bit pattern of its sum of l_i, a writer count), ONE in-place ncclAllReduce(int64, sum) of
+ *              pad64(5 K) words -- an exact all-gather -- one read-back, and dsgd_lg_predict_ranges' fold in position order.
+ *              A position not written by exactly one rank: DSGD_ESTATE.  w == NULL: the resident weights, else w replaces
+ *              them; the call leaves weights, accumulators and the cached |w|^2 words as dsgd_lg_predict_ranges does.  Classes
+ *              and probabilities are not gathered (dsgd_lg_predict_ranges gives a rank its own rows')
+ *   refused    DSGD_EUNSUPPORTED, weights untouched: dsgd_plan_create_from_seed_lg (the whole-job form is one process's:
+ *              dsgd_plan_create_from_seed_job_lg is the form for ranks), dsgd_plan_create_lg_cs_n,
+ *              dsgd_plan_create_from_seed_lg_cs, and dsgd_plan_run on a column-slice plan made before the attach.  Under
+ *              dsgd_comm_init and on contexts joined by dsgd_comm_init_all every logistic call stays refused
+ *   errors     a collective that fails half way: DSGD_ERCCL, the buffer is dropped (dsgd_lg_eval_job: its record's buffer),
+ *              the weights are those behind the last completed step
  * After dsgd_comm_destroy the calls are local again.  Real RCCL with more than one rank has not run; no speed is claimed.
  *
  * DISTRIBUTED AND SAMPLED EVALUATION (csrc/dsgd_lg_eval.hpp; ref: core/Master.scala:61-118) -- what dsgd_predict_ranges,
@@ -1072,11 +1093,14 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *
  * LIMITS (out of scope, each refused or simply absent): no JNI / Scala binding and nothing in include/dsgd.hpp; the host
  * mirrors are host.LogisticSync and host.LogisticAsync (Master.fit's and MasterAsync.fit's flow on one context, no
- * communicator; host.MasterSync / MasterAsync stay the SVM's); no fused or persistent one-launch step and no column
+ * communicator -- host.LogisticSync(ranks=(world, rank)) additionally runs Master.fit across dsgd_comm_init_lg's ranks;
+ * host.MasterSync / MasterAsync stay the SVM's); no fused or persistent one-launch step and no column
  * slices but those of COLUMN SLICES and ASYNCHRONOUS above; no asynchronous engine of the lock-free kind (dsgd_async_start
  * and dsgd_hogwild_kernel stay the SVM's: their parity rests on gate traces a gateless model does not have); no fp64 contexts
- * and no Double feature values; across ranks only what ACROSS RANKS lists -- no device-drawn lists, no column slices, no
- * asynchronous iteration, no evaluation summed over the ranks; no Sparse boundary forms.
+ * and no Double feature values; across ranks only what ACROSS RANKS lists -- no device-drawn lists but the job
+ * form's (dsgd_plan_create_from_seed_job_lg), no column slices, no asynchronous iteration, no evaluation summed over the ranks
+ * but dsgd_lg_eval_job's tallies and losses (classes and probabilities are a rank's own rows'; no sampled evaluation across
+ * ranks: the sampled window is the master's data); no Sparse boundary forms.
  *
  * dsgd_lg_gradient: one worker's regularised sum over the listed rows, key order, from the resident weights or from w
  * (which then replaces them, as in dsgd_gradient).  dsgd_lg_sync_step / _ranges: one step over K lists / K row
@@ -1124,6 +1148,13 @@ int dsgd_lg_loss_acc_list(dsgd_ctx* ctx, const float* w /* NULL = resident */, c
 int dsgd_lg_loss_acc_sampled(dsgd_ctx* ctx, const float* w /* NULL = resident */, uint64_t* jstate, int64_t row_begin, int64_t row_end,
                              int64_t samples_count, double* loss, double* acc, int64_t* counts /* 3 or NULL */,
                              int32_t* idx_out /* min(samples_count, row_end - row_begin) rows or NULL */, int64_t* n_out, int64_t* draws_out);
+/* across ranks ("ACROSS RANKS" above): a rank's window of the job's device-drawn lists; the job's evaluation on every rank */
+int dsgd_plan_create_from_seed_job_lg(dsgd_ctx* ctx, uint64_t* jstate, const int64_t* job_len, int32_t n_job, int32_t first, int32_t n_local,
+                                      const int64_t* split_begin, int64_t max_samples, int32_t batch_size, dsgd_plan** out, int64_t* n_steps_out,
+                                      int64_t* draws_out);
+int dsgd_lg_eval_job(dsgd_ctx* ctx, const float* w /* NULL = resident */, const int64_t* row_begin, const int64_t* row_end, int32_t n_local,
+                     int64_t* counts_out /* 3 * K or NULL */, double* range_loss_out /* K or NULL */, double* loss /* may be NULL */,
+                     double* acc /* may be NULL */, int32_t* K_out /* may be NULL */);
 
 #ifdef __cplusplus
 }
