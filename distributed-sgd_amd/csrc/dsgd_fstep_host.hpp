@@ -31,14 +31,20 @@ static int fstep_build(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int 
   L.worst_rows = T.worst_rows;
   L.shift = -1;
   // (alloc drops the tables of the cut before)
-  hipError_t e = L.d_tiles.try_alloc(wt.size());
+  // One guard record in front of both tile tables; the kernel is handed the record behind it.  A chunk without a tile clamps
+  // its record fetches to tile_end - 1 (w_fetch, c_map: unconditional scalar loads whose result is then not used), and for the
+  // FIRST chunk of a launch -- a range that starts on rows of the long list -- that is index -1.
+  const WTile guard = unused_wave_tile();
+  hipError_t e = L.d_tiles.try_alloc(wt.size() + 1);
   if (e == hipSuccess) e = L.d_meta.try_alloc(meta.size());
-  if (e == hipSuccess) e = L.d_ctiles.try_alloc(ct.size());
+  if (e == hipSuccess) e = L.d_ctiles.try_alloc(ct.size() + 1);
   if (e == hipSuccess) e = L.d_cmeta.try_alloc(cmeta.size());
   if (e == hipSuccess) e = L.d_chunks.try_alloc(chunks.size());
-  if (e == hipSuccess) e = hipMemcpy(L.d_tiles, wt.data(), sizeof(WTile) * wt.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(L.d_tiles, &guard, sizeof(WTile), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(L.d_tiles + 1, wt.data(), sizeof(WTile) * wt.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(L.d_meta, meta.data(), sizeof(unsigned short) * meta.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(L.d_ctiles, ct.data(), sizeof(WTile) * ct.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(L.d_ctiles, &guard, sizeof(WTile), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(L.d_ctiles + 1, ct.data(), sizeof(WTile) * ct.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(L.d_cmeta, cmeta.data(), sizeof(unsigned short) * cmeta.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(L.d_chunks, chunks.data(), sizeof(FChunk) * chunks.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess && !L.d_times) {
@@ -183,12 +189,12 @@ static int launch_fstep(dsgd_ctx* c, const std::vector<StreamSeg>& row_segs, int
   DSGD_TRY(prof_begin(c, &slot));
   c->ctr_known = false;
   if (packed)
-    hipLaunchKernelGGL(dsgd_fstep_kernel<true>, grid, dim3(1024), lds, c->stream, mh, view(c), L->d_tiles, L->d_meta, L->d_ctiles,
+    hipLaunchKernelGGL(dsgd_fstep_kernel<true>, grid, dim3(1024), lds, c->stream, mh, view(c), L->d_tiles + 1, L->d_meta, L->d_ctiles + 1,
                        L->d_cmeta, (const void*)c->d_ccol, c->d_cvaly, L->d_chunks, c->d_w, c->d_g64, (long long)c->dp, c->d_sc, H, nc,
                        main_scale, c->fix_scale, c->d_coef8, c->d_dcold, c->d_wlong_rows, c->d_part, c->part_stride, c->d_partc,
                        c->partc_stride, c->d_tprof, wg_times);
   else
-    hipLaunchKernelGGL(dsgd_fstep_kernel<false>, grid, dim3(1024), lds, c->stream, mh, view(c), L->d_tiles, L->d_meta, L->d_ctiles,
+    hipLaunchKernelGGL(dsgd_fstep_kernel<false>, grid, dim3(1024), lds, c->stream, mh, view(c), L->d_tiles + 1, L->d_meta, L->d_ctiles + 1,
                        L->d_cmeta, (const void*)c->d_ccol, c->d_cval, L->d_chunks, c->d_w, c->d_g64, (long long)c->dp, c->d_sc, H, nc,
                        main_scale, c->fix_scale, c->d_coef8, c->d_dcold, c->d_wlong_rows, c->d_part, c->part_stride, c->d_partc,
                        c->partc_stride, c->d_tprof, wg_times);

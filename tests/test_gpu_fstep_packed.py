@@ -13,7 +13,8 @@ weights and active-row counts are compared bit for bit over three steps from non
     and -0.0 entries;
   * a second matrix loaded into a warm context (the copies are rebuilt with the split they copy).
 
-tuning_info()["stream_mode"] says which form the last chunked launch ran (5: packed, 4: plain); every leg asserts it."""
+tuning_info()["stream_mode"] says which form the last chunked launch ran (5: packed, 4: plain); every leg asserts it.
+The window edges of the packed reader, on matrices built to produce them, live in tests/test_gpu_packed_edges.py."""
 
 import numpy as np
 import pytest
