@@ -57,6 +57,8 @@ SYMBOLS = [
     "dsgd_lg_predict_ranges", "dsgd_lg_loss_acc_list", "dsgd_lg_loss_acc_sampled",
     "dsgd_lg_async_step", "dsgd_lg_update_grad", "dsgd_async_plan_create_lg", "dsgd_async_plan_create_lg_cs", "dsgd_plan_run_async_lg",
     "dsgd_plan_create_from_seed_job_lg", "dsgd_lg_eval_job",
+    "dsgd_lg_topics_set", "dsgd_lg_topics_set_weights", "dsgd_lg_topics_get_weights", "dsgd_lg_topics_sync_step", "dsgd_lg_topics_sync_steps",
+    "dsgd_lg_topics_loss_acc", "dsgd_lg_topics_predict", "dsgd_lg_topics_count",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -173,6 +175,15 @@ def load():
     if hasattr(lib, "dsgd_lg_eval_job"):   # (ctx, w*, row_begin*, row_end*, n_local, counts_out*, range_loss_out*, loss*, acc*, K_out*)
         lib.dsgd_lg_eval_job.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
+    if hasattr(lib, "dsgd_lg_topics_set"):   # several topics (include/dsgd.h "SEVERAL TOPICS")
+        lib.dsgd_lg_topics_set.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]   # (ctx, T, planes*)
+        lib.dsgd_lg_topics_count.argtypes = [C.c_void_p, C.c_void_p]               # (ctx, T_out*)
+        lib.dsgd_lg_topics_set_weights.argtypes = [C.c_void_p, C.c_void_p]
+        lib.dsgd_lg_topics_get_weights.argtypes = [C.c_void_p, C.c_void_p]
+        lib.dsgd_lg_topics_sync_step.argtypes = lib.dsgd_lg_sync_step.argtypes     # (the single model's prototypes)
+        lib.dsgd_lg_topics_sync_steps.argtypes = lib.dsgd_lg_sync_steps.argtypes
+        lib.dsgd_lg_topics_loss_acc.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]   # (ctx, begin, end, loss*, acc*)
+        lib.dsgd_lg_topics_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]               # (ctx, idx*, n, p_out*)
     if hasattr(lib, "dsgd_dense_plan_create"):   # (handles are 64-bit: without argtypes ctypes would pass them as C ints)
         lib.dsgd_dense_step_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float]
         lib.dsgd_dense_loss_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

@@ -127,6 +127,7 @@ static bool available() {
 #include "dsgd_route.hpp"        // (host only: the switches, and which kernel family serves a call)
 #include "dsgd_kernels.hpp"
 #include "dsgd_logistic.hpp"   // (the logistic model beside the SVM: its own gradient, finish, evaluation and probabilities)
+#include "dsgd_lg_topics.hpp"  // (... over several topics: one-vs-rest label planes on the same rows, one launch pair per step)
 #include "dsgd_lg_eval.hpp"    // (... evaluated as Master evaluates: classes and tallies of K row ranges, the rows of a list)
 #include "dsgd_lg_eval_job.hpp"   // (... and the job's evaluation on every rank: the gather record, its fold, the kernel that fills it)
 #include "dsgd_batch.hpp"
@@ -579,6 +580,20 @@ struct dsgd_ctx {
     DevBuf<double> d_cq;             // the coefficients of the last step over these ranges, one per row
   };
   LayoutCache<LgColsLayout> lgc_cache;
+  // Several topics (csrc/dsgd_lg_topics.hpp; dsgd_lg_topics_set): lgt_T label planes [T][n_rows] beside d_label, the topics'
+  // weights [T][lgt_w_stride] in rank order beside d_w, their column sums [T][lgt_k][lgt_acc_stride] (zero between calls), the
+  // |w_t|^2 and loss words (lgt_part_words), the tallies [T][LG_TALLY_WORDS], an epoch's list ranges, the probabilities.
+  // lgt_gen: the layout the weights' rank order belongs to; lgt_nsq_stale: the |w_t|^2 words do not describe the weights.
+  int lgt_T = 0, lgt_k = 0;
+  long long lgt_gen = -1;
+  bool lgt_nsq_stale = true;
+  DevBuf<signed char> d_lgt_planes;
+  DevBuf<float> d_lgt_w;
+  DevBuf<unsigned long long> d_lgt_acc;
+  DevBuf<double> d_lgt_part;
+  DevBuf<unsigned long long> d_lgt_tally;
+  DevBuf<WorkSeg> d_lgt_ssegs;
+  DevBuf<float> d_lgt_p;
   unsigned long long bind_count = 0;
   unsigned long long lg_nsq_stamp = ~0ull - 1;
 };
@@ -2319,6 +2334,7 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   DSGD_ATTR(dsgd_eval_list_kernel<8>);
   DSGD_ATTR(dsgd_lg_predict_ranges_kernel);
   DSGD_ATTR(dsgd_lg_eval_list_kernel);
+  DSGD_ATTR(dsgd_lg_topics_eval_kernel);
   DSGD_ATTR(dsgd_colcount_kernel);
   DSGD_ATTR((dsgd_hogwild_kernel<false, false>));
   DSGD_ATTR((dsgd_hogwild_kernel<true, false>));
@@ -2409,6 +2425,7 @@ int dsgd_destroy(dsgd_ctx* c) {
 }
 
 // dsgd_load_csr (val64_in == nullptr) and dsgd_load_csr_f64 (val_in: the same values rounded to float, val64_in: as given)
+static void lgt_drop(dsgd_ctx* c);   // (csrc/dsgd_lg_topics_calls.hpp)
 static int load_csr_impl(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in, const int32_t* col_in, const float* val_in,
                          const double* val64_in, const int8_t* label) {
   if (n_rows < 1 || !row_ptr_in || !label) return fail(DSGD_EINVAL, "n_rows must be >= 1 and arrays non-null");
@@ -2496,6 +2513,7 @@ static int load_csr_impl(dsgd_ctx* c, int64_t n_rows, const int64_t* row_ptr_in,
     return fail(DSGD_EUNSUPPORTED, "dsgd_load_csr_f64 is not available while a communicator is attached (the gather's slots hold one "
                                    "word per column; the data and the weights are unchanged)");
   HIP_TRY(hipStreamSynchronize(c->stream));
+  lgt_drop(c);   // (the topics' planes label the rows that go)
   DSGD_TRY(reset_layout(c));
   c->d_row_ptr.reset();
   c->d_col.reset();
@@ -3647,6 +3665,7 @@ int dsgd_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row_en
 }
 
 #include "dsgd_lg_calls.hpp"   // (the logistic model's entry points: dsgd_lg_*)
+#include "dsgd_lg_topics_calls.hpp"   // (... over several topics: dsgd_lg_topics_*)
 
 // ---- distributed evaluation (csrc/dsgd_predict.hpp; ref: core/Master.scala:61-98) ----
 // The checks of dsgd_predict_ranges / _f64 that need no device: nothing has changed when one of them fails.

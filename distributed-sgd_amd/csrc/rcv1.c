@@ -365,6 +365,99 @@ void dsgd_rcv1_copy(const dsgd_rcv1* h, int64_t* row_ptr, int32_t* col, float* v
   if (label && h->n_rows) memcpy(label, h->label, (size_t)h->n_rows);
   if (doc_id && h->n_rows) memcpy(doc_id, h->doc_id, sizeof(int32_t) * (size_t)h->n_rows);
 }
+/* ---- several topics (rcv1.load_topics): one +1 / -1 plane per named topic over the rows dsgd_rcv1_load returned ----
+ * planes[t][i] = +1 iff ANY qrels line tags document doc_id[i] with topics[t], else -1 -- NOT Dataset.rcv1's rule, whose
+ * `.toMap` lets a document's LAST line decide (dsgd_rcv1_load keeps that rule for the one CCAT label).  A qrels line whose id
+ * no row carries is ignored; a malformed line is the error it is for dsgd_rcv1_load.  T <= 64: a document's tags are one
+ * 64-bit mask in an id -> mask table (open addressing, key 0 = empty, the hash of the label table).
+ * Returns 0, or -1 with `err` filled. */
+typedef struct {
+  const char* const* topics;
+  int T;
+  uint64_t mask; /* the topics this line's first token names (a topic may be listed twice: both planes get the tag) */
+  int32_t id;
+  int have_id, bad;
+} tag_ctx;
+static int tag_tok(void* vctx, int64_t index, const char* p, size_t len) {
+  tag_ctx* c = (tag_ctx*)vctx;
+  if (index == 0) {
+    for (int t = 0; t < c->T; ++t)
+      if (strlen(c->topics[t]) == len && memcmp(p, c->topics[t], len) == 0) c->mask |= 1ull << t;
+  } else if (index == 1) {
+    if (parse_int(p, len, &c->id)) c->bad = 1;
+    else c->have_id = 1;
+  }
+  return 0;
+}
+int dsgd_rcv1_topic_planes(const char* folder, const char* const* topics, int T, const int32_t* doc_id, int64_t n_rows, int8_t* planes, char* err,
+                           int errlen) {
+  if (!folder || !topics || T < 1 || T > 64 || n_rows < 0 || (n_rows > 0 && (!doc_id || !planes))) {
+    set_err(err, errlen, "%s: bad arguments (1 .. 64 topics; got %lld)", "dsgd_rcv1_topic_planes", (long long)T);
+    return -1;
+  }
+  for (int t = 0; t < T; ++t)
+    if (!topics[t]) {
+      set_err(err, errlen, "%s: topic %lld is null", "dsgd_rcv1_topic_planes", (long long)t);
+      return -1;
+    }
+  uint64_t cap = 1 << 16;
+  while (cap < 2 * (uint64_t)n_rows + 2) cap *= 2;
+  int32_t* key = (int32_t*)calloc((size_t)cap, sizeof(int32_t));
+  uint64_t* val = (uint64_t*)calloc((size_t)cap, sizeof(uint64_t));
+  char path[4096];
+  char* line = NULL;
+  size_t lcap = 0;
+  FILE* f = NULL;
+  int rc = -1;
+  if (!key || !val) {
+    set_err(err, errlen, "%s: out of memory (%lld rows)", "dsgd_rcv1_topic_planes", (long long)n_rows);
+    goto done;
+  }
+  for (int64_t i = 0; i < n_rows; ++i) { /* the rows' ids (an id that occurs twice shares one slot: both rows read it) */
+    if (doc_id[i] == 0) {
+      set_err(err, errlen, "%s: row %lld has document id 0", "dsgd_rcv1_topic_planes", (long long)i);
+      goto done;
+    }
+    uint64_t p = ((uint64_t)(uint32_t)doc_id[i] * 0x9E3779B97F4A7C15ull) >> 20;
+    while (key[p & (cap - 1)] && key[p & (cap - 1)] != doc_id[i]) ++p;
+    key[p & (cap - 1)] = doc_id[i];
+  }
+  snprintf(path, sizeof(path), "%s/rcv1-v2.topics.qrels", folder);
+  f = fopen(path, "r");
+  if (!f) {
+    set_err(err, errlen, "cannot open %s (errno %lld)", path, (long long)errno);
+    goto done;
+  }
+  long long ln = 0;
+  ssize_t n;
+  while ((n = read_line(f, &line, &lcap)) >= 0) {
+    ++ln;
+    tag_ctx c = {topics, T, 0, 0, 0, 0};
+    split_java(line, (size_t)n, tag_tok, &c);
+    if (c.bad || !c.have_id) {
+      set_err(err, errlen, "%s: malformed line %lld", path, ln);
+      goto done;
+    }
+    if (!c.mask || c.id == 0) continue;
+    uint64_t p = ((uint64_t)(uint32_t)c.id * 0x9E3779B97F4A7C15ull) >> 20;
+    while (key[p & (cap - 1)] && key[p & (cap - 1)] != c.id) ++p;
+    if (key[p & (cap - 1)] == c.id) val[p & (cap - 1)] |= c.mask; /* (an id no row carries: ignored) */
+  }
+  for (int64_t i = 0; i < n_rows; ++i) {
+    uint64_t p = ((uint64_t)(uint32_t)doc_id[i] * 0x9E3779B97F4A7C15ull) >> 20;
+    while (key[p & (cap - 1)] != doc_id[i]) ++p;
+    const uint64_t m = val[p & (cap - 1)];
+    for (int t = 0; t < T; ++t) planes[(size_t)t * (size_t)n_rows + (size_t)i] = (int8_t)((m >> t) & 1 ? 1 : -1);
+  }
+  rc = 0;
+done:
+  if (f) fclose(f);
+  free(line);
+  free(key);
+  free(val);
+  return rc;
+}
+
 /* the values as the reference holds them: Double, every digit of the file */
 void dsgd_rcv1_copy_f64(const dsgd_rcv1* h, double* val64) {
   if (val64 && h->nnz) memcpy(val64, h->val64, sizeof(double) * (size_t)h->nnz);

@@ -453,6 +453,88 @@ class Engine:
         check(self._lib.dsgd_lg_predict(self._ctx, ptr(wv), ptr(idx), C.c_int64(len(idx)), ptr(p)))
         return p
 
+    # -- several topics: one-vs-rest label planes on the same rows (include/dsgd.h "SEVERAL TOPICS") --------------
+    lg_topics_max = 8
+
+    def lg_topics_set(self, planes):
+        """T <= 8 label planes, int8 [T, n_rows] of +1 / -1 (dsgd_lg_topics_set): the topics' weights start at zero; the
+        engine's own labels and weights are not touched.  None or an empty array drops the topics."""
+        if planes is None or np.size(planes) == 0:
+            check(self._lib.dsgd_lg_topics_set(self._ctx, C.c_int32(0), None))
+            return
+        planes = np.asarray(planes)
+        if planes.ndim != 2 or planes.shape[1] != self.n_rows:
+            raise ValueError("planes must be [T, %d], not %r" % (self.n_rows, planes.shape))
+        if planes.dtype != np.int8 and not np.array_equal(planes, planes.astype(np.int8)):
+            raise ValueError("plane entries must be +1 or -1")
+        planes = np.ascontiguousarray(planes, dtype=np.int8)
+        check(self._lib.dsgd_lg_topics_set(self._ctx, C.c_int32(planes.shape[0]), ptr(planes)))
+
+    @property
+    def n_topics(self):
+        """the topics set now, as the library holds them (dsgd_lg_topics_count); 0: none"""
+        t = C.c_int32(0)
+        check(self._lib.dsgd_lg_topics_count(self._ctx, C.byref(t)))
+        return int(t.value)
+
+    def _lg_topics(self):
+        """T from the library itself: every array below is sized by the number the call will write"""
+        t = self.n_topics
+        if t < 1:
+            raise _lib.DsgdError(_lib.ESTATE, "no topics set (Engine.lg_topics_set; a load drops them)")
+        return t
+
+    def lg_topics_set_weights(self, W):
+        """The topics' weights, float32 [T, D + 1] in key order (dsgd_lg_topics_set_weights)."""
+        t = self._lg_topics()
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        if W.shape != (t, self.dp):
+            raise ValueError("expected weights of shape (%d, %d), got %r" % (t, self.dp, W.shape))
+        check(self._lib.dsgd_lg_topics_set_weights(self._ctx, ptr(W)))
+
+    def lg_topics_get_weights(self):
+        t = self._lg_topics()
+        W = np.zeros((t, self.dp), dtype=np.float32)
+        check(self._lib.dsgd_lg_topics_get_weights(self._ctx, ptr(W)))
+        return W
+
+    def lg_topics_sync_step(self, idx_per_worker, lr):
+        """One synchronous step of EVERY topic over the workers' lists in two launches (dsgd_lg_topics_sync_step): topic t's
+        weights get the bits of lg_sync_step on an engine whose labels are plane t."""
+        lists = [i32(a) for a in idx_per_worker]
+        k = len(lists)
+        ptrs = (C.c_void_p * max(k, 1))(*[ptr(a) for a in lists])
+        ns = (C.c_int64 * max(k, 1))(*[len(a) for a in lists])
+        st = BatchStats()
+        check(self._lib.dsgd_lg_topics_sync_step(self._ctx, ptrs, ns, C.c_int32(k), C.c_float(lr), C.byref(st)))
+        return {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def lg_topics_sync_steps(self, idx, offsets, n_steps, n_workers, lr):
+        """n_steps steps of lg_topics_sync_step in ONE call (dsgd_lg_topics_sync_steps; lg_sync_steps' flat form)."""
+        idx = i32(idx)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if n_steps >= 1 and n_workers >= 1 and len(offsets) != n_steps * n_workers + 1:
+            raise ValueError("offsets do not describe %d x %d lists" % (n_steps, n_workers))
+        st = BatchStats()
+        check(self._lib.dsgd_lg_topics_sync_steps(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers),
+                                                  C.c_float(lr), C.byref(st)))
+        return {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def lg_topics_loss_acc(self, row_begin, row_end):
+        """(loss float64 [T], acc float64 [T]) of rows [row_begin, row_end) in ONE launch (dsgd_lg_topics_loss_acc)."""
+        t = self._lg_topics()
+        loss, acc = np.zeros(t, dtype=np.float64), np.zeros(t, dtype=np.float64)
+        check(self._lib.dsgd_lg_topics_loss_acc(self._ctx, C.c_int64(row_begin), C.c_int64(row_end), ptr(loss), ptr(acc)))
+        return loss, acc
+
+    def lg_topics_predict(self, idx):
+        """P(topic t | x) = sigma(x . w_t) of every listed row: float32 [T, n] (dsgd_lg_topics_predict)."""
+        t = self._lg_topics()
+        idx = i32(idx)
+        p = np.zeros((t, len(idx)), dtype=np.float32)
+        check(self._lib.dsgd_lg_topics_predict(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(p)))
+        return p
+
     lg_max_ranges = 16   # ranges of one dsgd_lg_loss_acc_ranges call
 
     def lg_loss_acc_ranges(self, ranges, w=None):

@@ -1458,6 +1458,83 @@ class LogisticSync:
         return state.finish(self.losses[0] if self.losses else None)
 
 
+# ---- Master.fit over several topics -------------------------------------------------------------------------------
+class LogisticTopics:
+    """Master.fit's flow (core/Master.scala:120-218) for T one-vs-rest logistic models on ONE engine whose topics are set
+    (Engine.lg_topics_set; include/dsgd.h "SEVERAL TOPICS"), the lists shared: SplitStrategy.vanilla's splits, per epoch
+    epoch_lists from ONE JavaRandom, ONE Engine.lg_topics_sync_steps (two launches per step whatever T), ONE
+    Engine.lg_topics_loss_acc each over the train and the test rows.
+
+    The stopping rule is applied PER TOPIC, to that topic's test losses, newest first.  A topic's GradState is taken at the
+    epoch where its own rule first fires (or max_epochs is reached): its weights are read then, the other topics go on --
+    the finished topic keeps being stepped with them, which nobody looks at.  So topic t's GradState (weights, loss,
+    updates) is what host.LogisticSync alone returns for an engine whose labels are plane t, from the same seed.
+
+    data layout: rows [0, n_train) are the train set, [n_train, n_rows) the test set.  Limits: one engine, no plans, no
+    ranks, no column slices, one learning rate and one lambda for all topics."""
+
+    def __init__(self, backend, n_train: int, n_rows: int, node_count: int, rnd: Optional[JavaRandom] = None, log=None):
+        if not 0 < n_train < n_rows:
+            raise ValueError("LogisticTopics needs train rows [0, n_train) and test rows [n_train, n_rows)")
+        self.backend, self.n_train, self.n_rows, self.node_count = backend, n_train, n_rows, node_count
+        self.rnd = rnd or JavaRandom(0)
+        self.log = log or (lambda *a: None)
+        self.losses: List[List[float]] = []        # per topic, newest first
+        self.accs: List[List[float]] = []
+        self.test_losses: List[List[float]] = []
+        self.test_accs: List[List[float]] = []
+        self.steps_run = 0
+
+    def fit(self, initial_weights, max_epochs: int, batch_size: int, learning_rate: float,
+            stopping_criterion: Callable[[Sequence[float]], bool]) -> List[GradState]:
+        split = split_vanilla(self.n_train, self.node_count)
+        max_samples = max(len(r) for r in split)
+        n_expected = len(range(0, max_samples, batch_size))
+        W0 = np.ascontiguousarray(initial_weights, dtype=np.float32)
+        if W0.ndim != 2:
+            raise ValueError("initial_weights must be [T, D + 1]")
+        T = W0.shape[0]
+        self.backend.lg_topics_set_weights(W0)
+        self.losses, self.accs = [[] for _ in range(T)], [[] for _ in range(T)]
+        self.test_losses, self.test_accs = [[] for _ in range(T)], [[] for _ in range(T)]
+        start = time.time()
+        done: List[Optional[GradState]] = [None] * T
+        epoch = 0
+        while True:
+            fired = []
+            for t in range(T):
+                if done[t] is not None:
+                    continue
+                if epoch >= max_epochs:
+                    self.log("topic %d: reached max number of epochs" % t)
+                    fired.append(t)
+                elif stopping_criterion(self.test_losses[t]):
+                    self.log("topic %d: converged to target after epoch %d" % (t, epoch))
+                    fired.append(t)
+            if fired:
+                W = self.backend.lg_topics_get_weights() if epoch else W0
+                for t in fired:
+                    done[t] = GradState(np.array(W[t], dtype=np.float32), None, start, epoch, None).finish(self.losses[t][0] if self.losses[t] else None)
+            if all(s is not None for s in done):
+                break
+            idx, offsets, n_steps = epoch_lists(self.rnd, split, max_samples, batch_size)
+            if n_steps:
+                self.backend.lg_topics_sync_steps(idx, offsets, n_steps, len(split), learning_rate)
+            if n_steps < n_expected:
+                # the reference's next batch hands some slave an empty slice: Vec.sum throws there (math/Vec.scala:129)
+                raise ValueError("Cannot sum an empty list of vectors (batch %d of the epoch: a worker's slice is empty)" % n_steps)
+            l, a = self.backend.lg_topics_loss_acc(0, self.n_train)
+            tl, ta = self.backend.lg_topics_loss_acc(self.n_train, self.n_rows)
+            self.steps_run += n_steps
+            for t in range(T):
+                self.losses[t].insert(0, float(l[t]))
+                self.accs[t].insert(0, float(a[t]))
+                self.test_losses[t].insert(0, float(tl[t]))
+                self.test_accs[t].insert(0, float(ta[t]))
+            epoch += 1
+        return done
+
+
 # ---- MasterAsync.fit for the logistic model ---------------------------------------------------------------------------
 class LogisticAsync:
     """core/MasterAsync.scala:32-178 for the LOGISTIC model of one engine, on the ZERO-LAG schedule (include/dsgd.h "THE LOGISTIC

@@ -71,6 +71,36 @@ def load(folder: str, full: bool = True, dim: int = RCV1_DIM, with_ids: bool = F
     return (data, ids) if with_ids else data
 
 
+def load_topics(folder: str, topics, full: bool = True, dim: int = RCV1_DIM):
+    """`load`'s rows plus one label plane per named topic: (Csr, planes int8 [T, n]) -- what Engine.lg_topics_set takes.
+
+    planes[t, i] is +1 iff ANY qrels line tags document i with topics[t], and -1 otherwise: the multi-label reading of
+    RCV1-v2.  That is NOT `load`'s rule for its one CCAT label, which restates the reference (Dataset.scala:44 and its
+    `.toMap`: the LAST qrels line of a document decides, so a document tagged CCAT and then GCAT is -1 in `load(...).label`
+    and +1 on both planes here).  `load` and the returned Csr's `label` keep the reference's rule.  A topic no line names
+    gives a plane of -1; a qrels line whose id no row carries is ignored; a document without any qrels line makes `load`
+    raise, as in the reference.  The parse is native (csrc/rcv1.c: dsgd_rcv1_topic_planes); at most 64 topics per call."""
+    names = [topics] if isinstance(topics, str) else list(topics)
+    if not 1 <= len(names) <= 64:
+        raise ValueError("load_topics takes 1 .. 64 topic names, not %d" % len(names))
+    enc = []
+    for t in names:
+        if not isinstance(t, str) or not t or " " in t:
+            raise ValueError("a topic is a non-empty name without blanks, not %r" % (t,))
+        enc.append(t.encode("utf-8"))
+    data, ids = load(folder, full, dim, with_ids=True)
+    lib = _load()
+    lib.dsgd_rcv1_topic_planes.restype = C.c_int
+    lib.dsgd_rcv1_topic_planes.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_char_p, C.c_int]
+    arr = (C.c_char_p * len(enc))(*enc)
+    planes = np.empty((len(enc), data.n_rows), dtype=np.int8)
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    err = C.create_string_buffer(512)
+    if lib.dsgd_rcv1_topic_planes(os.fsencode(folder), arr, len(enc), ids.ctypes.data, data.n_rows, planes.ctypes.data, err, len(err)) != 0:
+        raise ValueError(err.value.decode("utf-8", "replace") or "rcv1 topic planes failed")
+    return data, planes
+
+
 def export(folder: str, data: Csr, n_train_file: int = N_TRAIN_OFFICIAL, first_id: int = 2286, other_topic_lines: bool = True):
     """Write `data` as RCV1-v2 text: rows [0, n_train_file) into the train file, the rest split evenly over the four
     test parts, labels into the qrels file.  A +1 row gets the line `CCAT <id> 1` LAST; a -1 row gets only other

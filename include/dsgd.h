@@ -1091,7 +1091,36 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *                          logistic, an fp64 context, ANY communicator attached (dsgd_comm_init_lg's too: the schedule is one
  *                          process's) DSGD_EUNSUPPORTED; no data or a running lock-free engine DSGD_ESTATE
  *
- * LIMITS (out of scope, each refused or simply absent): no JNI / Scala binding and nothing in include/dsgd.hpp; the host
+ * SEVERAL TOPICS (csrc/dsgd_lg_topics.hpp).  One-vs-rest over T label planes on the SAME resident rows: the
+ * rows, their ranking, vexp and the lists do not depend on the label, only c = -y / (1 + exp(y d)) and the weight vector do.
+ * The planes and the topics' weights live beside the context's own labels and weights and touch neither: dsgd_get_weights,
+ * dsgd_lg_loss_acc and every other entry point see what they saw before.  A step is TWO launches whatever T
+ * (dsgd_lg_topics_grad_kernel: a row's first 64 non-zeros fetched once for all topics; dsgd_lg_topics_finish_kernel: one
+ * column per lane, the topic on the grid's second dimension), an evaluation ONE (dsgd_lg_topics_eval_kernel).
+ * THE CONTRACT: topic t's weights, losses, accuracies and probabilities are the BITS that dsgd_lg_sync_step / _sync_steps /
+ * _loss_acc / _predict give on a context that holds the same rows with label = plane t, from the same weights, lists, lr and
+ * lambda (the column sums are exact integers, so sharing the pass and the LDS head moves no bit; the tile rule above covers
+ * the evaluation's smaller per-topic tile).
+ *   dsgd_lg_topics_set          1 <= T <= 8 (LG_TOPICS_MAX) planes of n_rows entries each, topic-major, each +1 or -1; the
+ *                               topics' weights start at zero.  T = 0 drops the topics and frees their memory.  Setting again
+ *                               replaces planes and weights; an allocation failure leaves the context as it was
+ *   dsgd_lg_topics_count        T as it is now (0: no topics) -- what sizes the arrays of the calls below
+ *   dsgd_lg_topics_set_weights / _get_weights   T x (D + 1) floats, topic-major, key order
+ *   dsgd_lg_topics_sync_step    dsgd_lg_sync_step's arguments: one step of every topic over the same K lists
+ *   dsgd_lg_topics_sync_steps   dsgd_lg_sync_steps' arguments: 2 n_steps launches, no host synchronisation in between
+ *   dsgd_lg_topics_loss_acc     loss[t], acc[t] over rows [row_begin, row_end) (either array may be NULL, not both)
+ *   dsgd_lg_topics_predict      sigma(d_t) of every listed position: p_out[t * n + position]
+ *   refused                     before anything is enqueued, nothing written: T outside [0, 8], a null pointer or a plane entry
+ *                               other than +1/-1 DSGD_EINVAL; an index outside the data DSGD_ERANGE; an fp64 context or ANY
+ *                               communicator attached (dsgd_comm_init_lg's too) DSGD_EUNSUPPORTED; no data, a running lock-free
+ *                               engine, or no topics set DSGD_ESTATE.  dsgd_load_csr / _f64 drops the topics (the planes label
+ *                               the rows that went), and so does a new column ranking (a communicator attached and detached):
+ *                               the calls return DSGD_ESTATE until topics are set again (that drop comes BEHIND a call's
+ *                               argument checks: a call refused for its arguments has changed nothing)
+ *
+ * LIMITS (out of scope, each refused or simply absent): several topics run per-call steps over lists only -- no plans, no
+ * row ranges or column lists, no column slices, no ranks, no asynchronous iteration, one lambda and one lr for all topics,
+ * no JNI; no JNI / Scala binding and nothing in include/dsgd.hpp; the host
  * mirrors are host.LogisticSync and host.LogisticAsync (Master.fit's and MasterAsync.fit's flow on one context, no
  * communicator -- host.LogisticSync(ranks=(world, rank)) additionally runs Master.fit across dsgd_comm_init_lg's ranks;
  * host.MasterSync / MasterAsync stay the SVM's); no fused or persistent one-launch step and no column
@@ -1155,6 +1184,17 @@ int dsgd_plan_create_from_seed_job_lg(dsgd_ctx* ctx, uint64_t* jstate, const int
 int dsgd_lg_eval_job(dsgd_ctx* ctx, const float* w /* NULL = resident */, const int64_t* row_begin, const int64_t* row_end, int32_t n_local,
                      int64_t* counts_out /* 3 * K or NULL */, double* range_loss_out /* K or NULL */, double* loss /* may be NULL */,
                      double* acc /* may be NULL */, int32_t* K_out /* may be NULL */);
+/* several topics ("SEVERAL TOPICS" above) */
+int dsgd_lg_topics_set(dsgd_ctx* ctx, int32_t T, const int8_t* planes /* T x n_rows, topic-major, each +1 or -1 */);
+int dsgd_lg_topics_count(dsgd_ctx* ctx, int32_t* T_out /* the topics set now; 0: none */);
+int dsgd_lg_topics_set_weights(dsgd_ctx* ctx, const float* W /* T x (D+1), key order */);
+int dsgd_lg_topics_get_weights(dsgd_ctx* ctx, float* W_out /* T x (D+1), key order */);
+int dsgd_lg_topics_sync_step(dsgd_ctx* ctx, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers, float lr,
+                             dsgd_batch_stats* stats);
+int dsgd_lg_topics_sync_steps(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const int64_t* offsets /* n_steps * n_workers + 1 */,
+                              int64_t n_steps, int32_t n_workers, float lr, dsgd_batch_stats* stats);
+int dsgd_lg_topics_loss_acc(dsgd_ctx* ctx, int64_t row_begin, int64_t row_end, double* loss /* T */, double* acc /* T */);
+int dsgd_lg_topics_predict(dsgd_ctx* ctx, const int32_t* idx, int64_t n, float* p_out /* T x n, topic-major */);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,10 @@ apply (include/dsgd.h "THE LOGISTIC MODEL", COLUMN SLICES; up to 6 workers at RC
 --lg-async (with --model logistic): MasterAsync.fit's flow on the zero-lag schedule (host.LogisticAsync; include/dsgd.h "THE
 LOGISTIC MODEL", ASYNCHRONOUS): device-drawn one-worker plans, a loss check every check-every updates with the leaky average,
 best weights kept, maxSteps = train rows x max-epochs.  With --lg-slices a window of updates is ONE persistent launch.
+--topics CCAT,ECAT,GCAT,MCAT (with --model logistic; up to 8 names): one-vs-rest over the named topics on the same rows
+(include/dsgd.h "THE LOGISTIC MODEL", SEVERAL TOPICS) -- rcv1.load_topics' planes (+1 iff ANY qrels line tags the document),
+host.LogisticTopics: Master.fit's flow with the lists shared, one launch pair per step whatever the number of topics, the early
+stopping applied per topic.  With --synthetic plane 0 is the data's labels and the others are the signs of seeded planted directions.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -42,7 +46,13 @@ ap.add_argument("--model", choices=("svm", "logistic"), default="svm", help="log
 ap.add_argument("--lg-plans", action="store_true", help="logistic: Master.fit's flow on resident logistic plans (host.LogisticSync)")
 ap.add_argument("--lg-slices", action="store_true", help="logistic: --lg-plans on column slices, one persistent launch per epoch (host.LogisticSync(slices=True))")
 ap.add_argument("--lg-async", action="store_true", help="logistic: MasterAsync.fit's flow on the zero-lag schedule (host.LogisticAsync); honours --lg-slices")
+ap.add_argument("--topics", help="logistic: comma-separated topic names, one-vs-rest in one launch pair per step (host.LogisticTopics)")
 a = ap.parse_args()
+topics = [t for t in (a.topics or "").split(",") if t]
+if topics and (a.model != "logistic" or a.lg_plans or a.lg_slices or a.lg_async):
+    ap.error("--topics goes with --model logistic alone (no plans, slices or asynchronous fit over several topics)")
+if len(topics) > dsgd_amd.Engine.lg_topics_max:
+    ap.error("--topics takes at most %d names" % dsgd_amd.Engine.lg_topics_max)
 if a.lg_async and a.lg_plans:
     ap.error("--lg-plans and --lg-async are two fits: give one (--lg-slices goes with either)")
 a.lg_plans = a.lg_plans or a.lg_slices
@@ -85,11 +95,47 @@ def fit_logistic(eng, cfg, n_train, n_rows):
     log("final test accuracy: {}", ate)
 
 
+def synthetic_planes(data, n_topics, seed=1):
+    """plane 0: the data's labels; plane t >= 1: the sign of x . u_t for a seeded planted direction u_t (a zero dot counts as -1)"""
+    rng = np.random.default_rng(seed)
+    planes = [np.asarray(data.label, dtype=np.int8)]
+    rows = np.repeat(np.arange(data.n_rows), np.diff(data.row_ptr))
+    for _ in range(1, n_topics):
+        u = rng.standard_normal(data.dim + 1)
+        d = np.bincount(rows, weights=data.val.astype(np.float64) * u[data.col], minlength=data.n_rows)
+        planes.append(np.where(d > 0, 1, -1).astype(np.int8))
+    return np.ascontiguousarray(np.stack(planes), dtype=np.int8)
+
+
+def fit_topics(eng, cfg, planes, names, n_train, n_rows):
+    eng.lg_topics_set(planes)
+    master = host.LogisticTopics(eng, n_train, n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log)
+    l0, a0 = eng.lg_topics_loss_acc(0, n_train)
+    for t, name in enumerate(names):
+        log("{}: {} of {} rows tagged, initial loss {}, initial accuracy {}", name, int((planes[t] > 0).sum()), n_rows, l0[t], a0[t])
+    t0 = time.time()
+    states = master.fit(np.zeros((len(names), eng.dp), dtype=np.float32), cfg.max_epochs, cfg.batch_size, cfg.learning_rate,
+                        host.EarlyStopping.no_improvement(cfg.patience, cfg.conv_delta, None))
+    log("fit ({}s, {} steps of {} topics)", round(time.time() - t0, 3), master.steps_run, len(names))
+    eng.lg_topics_set_weights(np.stack([s.grad for s in states]))     # every topic at the weights its own rule kept
+    lte, ate = eng.lg_topics_loss_acc(n_train, n_rows)
+    for t, name in enumerate(names):
+        log("{}: {} epochs, train loss {}, final test loss {}, final test accuracy {}", name, states[t].updates, states[t].loss, lte[t], ate[t])
+
+
 cfg = host.Config.load(open(a.conf).read() if a.conf else None)
 log("config: {}", cfg)
 log("loading data in: {}", "synthetic(%d)" % a.synthetic if a.synthetic else cfg.data_path)
 t0 = time.time()
-data = dsgd_amd.synth.generate(a.synthetic, seed=0) if a.synthetic else rcv1.load(cfg.data_path, full=cfg.full)
+planes = None
+if a.synthetic:
+    data = dsgd_amd.synth.generate(a.synthetic, seed=0)
+    if topics:
+        planes = synthetic_planes(data, len(topics))
+elif topics:
+    data, planes = rcv1.load_topics(cfg.data_path, topics, full=cfg.full)
+else:
+    data = rcv1.load(cfg.data_path, full=cfg.full)
 log("data loaded: {} ({}s)", data.n_rows, round(time.time() - t0, 2))
 n_train = int(data.n_rows * 0.8)                                              # Main.scala:52
 metrics = host.Metrics()
@@ -103,6 +149,9 @@ with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device, precision=a.precisi
         if a.precision == "fp64" and cfg.async_ and not rp_plans and getattr(data, "val64", None) is not None else "")
     if a.model == "logistic":   # (its own loop; dimSparsity plays no part)
         eng.set_weights(np.zeros(data.dim + 1, dtype=np.float32))
+        if topics:
+            fit_topics(eng, cfg, planes, topics, n_train, data.n_rows)
+            sys.exit(0)
         if a.lg_async:
             master = host.LogisticAsync(eng, n_train, data.n_rows, cfg.node_count, log=log, slices=a.lg_slices)
             l0, a0 = eng.lg_loss_acc(0, n_train)
