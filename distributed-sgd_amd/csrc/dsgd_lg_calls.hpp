@@ -677,7 +677,7 @@ int dsgd_lg_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row
   DSGD_TRY(lg_ensure(c, 1));
   const long long nb = lg_finish_blocks(c->dp);
   if (w || !fresh) {   // |w|^2 of weights the logistic finish did not write: the finish's grid and tree, the same bits
-    hipLaunchKernelGGL(dsgd_lg_nsq_kernel, dim3((unsigned)nb), dim3(LG_THREADS), 0, c->stream, c->d_w, c->dp, c->d_lg_part);
+    hipLaunchKernelGGL(dsgd_lg_nsq_kernel, dim3((unsigned)nb), dim3(LG_THREADS), 0, c->stream, c->d_w, 0LL, c->dp, c->d_lg_part);
     HIP_TRY(hipGetLastError());
   }
   DSGD_TRY(reset_counters(c));
@@ -726,7 +726,7 @@ int dsgd_lg_loss_acc_ranges(dsgd_ctx* c, const float* w, const int64_t* row_begi
   DSGD_TRY(lg_ensure(c, 1));
   const long long nb = lg_finish_blocks(c->dp);
   if (w || !fresh) {   // (as dsgd_lg_loss_acc: the finish's grid and tree, the same bits)
-    hipLaunchKernelGGL(dsgd_lg_nsq_kernel, dim3((unsigned)nb), dim3(LG_THREADS), 0, c->stream, c->d_w, c->dp, c->d_lg_part);
+    hipLaunchKernelGGL(dsgd_lg_nsq_kernel, dim3((unsigned)nb), dim3(LG_THREADS), 0, c->stream, c->d_w, 0LL, c->dp, c->d_lg_part);
     HIP_TRY(hipGetLastError());
   }
   DSGD_TRY(reset_counters(c));
@@ -801,7 +801,7 @@ static int lg_eval_hw(dsgd_ctx* c, long long rows, int extra) {
 // |w|^2 of weights the logistic finish did not write, as dsgd_lg_loss_acc takes it: the finish's grid and tree, the same bits
 static int lg_nsq_if_stale(dsgd_ctx* c, bool stale) {
   if (!stale) return DSGD_OK;
-  hipLaunchKernelGGL(dsgd_lg_nsq_kernel, dim3((unsigned)lg_finish_blocks(c->dp)), dim3(LG_THREADS), 0, c->stream, c->d_w, c->dp, c->d_lg_part);
+  hipLaunchKernelGGL(dsgd_lg_nsq_kernel, dim3((unsigned)lg_finish_blocks(c->dp)), dim3(LG_THREADS), 0, c->stream, c->d_w, 0LL, c->dp, c->d_lg_part);
   HIP_TRY(hipGetLastError());
   return DSGD_OK;
 }

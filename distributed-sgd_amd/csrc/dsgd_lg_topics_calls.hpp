@@ -267,7 +267,7 @@ int dsgd_lg_topics_loss_acc(dsgd_ctx* c, int64_t row_begin, int64_t row_end, dou
   const int T = c->lgt_T;
   const long long nb = lg_finish_blocks(c->dp);
   if (c->lgt_nsq_stale) {   // |w_t|^2 of weights the finish did not write: the finish's grid and tree, the same bits
-    hipLaunchKernelGGL(dsgd_lg_topics_nsq_kernel, dim3((unsigned)nb, (unsigned)T), dim3(LG_THREADS), 0, c->stream, c->d_lgt_w.get(),
+    hipLaunchKernelGGL(dsgd_lg_nsq_kernel, dim3((unsigned)nb, (unsigned)T), dim3(LG_THREADS), 0, c->stream, c->d_lgt_w.get(),
                        lgt_w_stride(c->dp), c->dp, c->d_lgt_part.get());
     HIP_TRY(hipGetLastError());
   }

@@ -311,6 +311,64 @@ def test_lists_with_duplicates_against_the_reference_and_themselves(big):
     assert many[2] == [70 * c for c in one[2]] and many[1] == one[1]
 
 
+# ---- 2b. ONE evaluation walk (csrc/dsgd_logistic.hpp: lg_eval_walk) behind every entry point -----------------------------------
+def walk_data():
+    """300 rows over 2,100 columns: ranks beyond LG_HOT (2,048) and beyond the 1,024-float tile of a short range.  Row 0 is empty,
+    row 1 holds zeros only, row 2 has 150 non-zeros (the tail loop behind the LG_UNR * 16 = 64 in registers), row 3's two
+    products are +0.5 and -0.5: d == 0 exactly."""
+    rng = np.random.default_rng(77)
+    n, dim = 300, 2100
+    cols, vals = [], []
+    for i in range(n):
+        k = {0: 0, 1: 3, 2: 150, 3: 2}.get(i, int(rng.integers(20, 61)))
+        c = np.sort(rng.choice(np.arange(3, dim + 1), size=k, replace=False)).astype(np.int32)
+        v = (rng.standard_normal(k) + 0.25).astype(np.float32)
+        if i == 1:
+            v[:] = 0.0
+        if i == 3:
+            c, v = np.array([1, 2], np.int32), np.array([1.0, 1.0], np.float32)
+        cols.append(c)
+        vals.append(v)
+    row_ptr = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.int64)
+    label = np.where(rng.random(n) < 0.5, 1, -1).astype(np.int8)
+    csr = (row_ptr, np.concatenate(cols), np.concatenate(vals), label)
+    w = rng.standard_normal(dim + 1)
+    w[1], w[2] = 0.5, -0.5
+    w = (w * np.where(np.arange(dim + 1) < 3, 1.0, 1.0 / np.std(ref.dots(csr, w)))).astype(np.float32)
+    return csr, dim, w
+
+
+def test_one_walk_behind_every_evaluation():
+    csr, dim, w = walk_data()
+    R = Ref(csr, w, cases.LAM)
+    assert int(np.max(np.diff(csr[0]))) > 64 and R.d[3] == 0.0 and len(np.unique(csr[1])) > 2048
+    with engine_of(csr, dim, cases.LAM, w) as eng:
+        for a, b in ((0, 300), (1, 297)):
+            rows = np.arange(a, b, dtype=np.int32)
+            one = eng.lg_loss_acc(a, b)
+            assert eng.lg_loss_acc_ranges([(a, b)]) == [one]
+            assert eng.lg_loss_acc_ranges([(5, 50), (a, b), (a, b)])[1:] == [one, one]
+            cls, proba, counts, range_loss, loss, acc = eng.lg_predict_ranges([(a, b)], want_proba=True)
+            l_list, a_list, c_list = eng.lg_loss_acc_list(rows)
+            assert (range_loss[0], loss, l_list) == (one[0],) * 3 and (acc, a_list) == (one[1],) * 2
+            assert counts[0].tolist() == list(c_list) and sum(c_list) == b - a and one[1] == c_list[0] / float(b - a)
+            # the class is the sign of the d behind the probability, which has the bits of lg_predict_proba
+            assert np.array_equal(bits(proba), bits(eng.lg_predict_proba(rows)))
+            assert np.array_equal(cls, np.sign(proba.astype(np.float64) - 0.5).astype(np.int8))
+            y = R.y[a:b].astype(np.int64)
+            assert counts[0].tolist() == [int(np.sum(cls == y)), int(np.sum(cls == 0)), int(np.sum(cls == -y))]
+            zero = np.array([i - a for i in (0, 1, 3) if a <= i < b])
+            assert np.all(cls[zero] == 0) and np.all(proba[zero] == 0.5)
+            R.check_rows(rows.astype(np.int64), cls, proba, "walk [%d, %d)" % (a, b))
+            R.check_range(a, b, counts[0], one[0], "walk [%d, %d)" % (a, b))
+        # one topic whose plane is the labels: the single model
+        eng.lg_topics_set(csr[3][None, :])
+        eng.lg_topics_set_weights(w[None, :])
+        for a, b in ((0, 300), (1, 297)):
+            loss_t, acc_t = eng.lg_topics_loss_acc(a, b)
+            assert (loss_t[0], acc_t[0]) == eng.lg_loss_acc(a, b)
+
+
 # ---- 3. dsgd_lg_loss_acc_sampled ----------------------------------------------------------------------------------------------
 def test_sampled_form_draws_the_reference_stream_and_has_the_bits_of_the_list_form(synth):
     eng, R = synth

@@ -39,8 +39,11 @@ def test_the_library_uses_the_table_and_checks_first():
     hip = open(os.path.join(CSRC, "dsgd_hip.hip")).read()
     assert len(re.findall(r"\nstatic int sampled_draw\([^)]*\) \{", hip)) == 1 and not re.search(r"\nstatic int sampled_draw\([^)]*\) \{", calls)
     kernels = open(os.path.join(CSRC, "dsgd_lg_eval.hpp")).read()
+    # both kernels are the single model's ONE evaluation body, which holds the dot, the tree and the pragma
     for name in ("dsgd_lg_predict_ranges_kernel", "dsgd_lg_eval_list_kernel"):
-        body = kernels.split("%s(" % name)[-1]
-        assert "row_dot<LG_GROUP, LG_UNR, true>" in body and "lg_block_sum(" in body and "#pragma clang fp contract(off)" in body, name
+        body = kernels.split("%s(" % name)[-1].split("\n}\n")[0]
+        assert "lg_eval_walk(m, w, hw, " in body, name
+    walk = open(os.path.join(CSRC, "dsgd_logistic.hpp")).read().split("void lg_eval_walk(")[1].split("\n}\n")[0]
+    assert "row_dot<LG_GROUP, LG_UNR, true>" in walk and "lg_block_sum(" in walk and "#pragma clang fp contract(off)" in walk
     assert "lg_pred_owner(l_tab" in kernels
     assert hip.index('#include "dsgd_logistic.hpp"') < hip.index('#include "dsgd_lg_eval.hpp"')

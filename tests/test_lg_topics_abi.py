@@ -58,7 +58,7 @@ def test_refusals_that_need_no_device():
 
 def test_the_new_kernels_are_in_the_code_object_without_scratch(tmp_path):
     notes = _kernel_notes(tmp_path)
-    for name in ("dsgd_lg_topics_grad_kernel", "dsgd_lg_topics_finish_kernel", "dsgd_lg_topics_nsq_kernel", "dsgd_lg_topics_eval_kernel",
+    for name in ("dsgd_lg_topics_grad_kernel", "dsgd_lg_topics_finish_kernel", "dsgd_lg_nsq_kernel", "dsgd_lg_topics_eval_kernel",
                  "dsgd_lg_topics_predict_kernel"):
         kn = {k: v for k, v in notes.items() if name in k}
         assert len(kn) == 1, (name, sorted(kn))
