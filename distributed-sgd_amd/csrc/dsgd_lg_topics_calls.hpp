@@ -11,6 +11,8 @@ static void lgt_drop(dsgd_ctx* c) {
   if (c->lgt_T) (void)hipStreamSynchronize(c->stream);
   c->lgt_T = 0;
   c->lgt_k = 0;
+  c->lgt_il = false;
+  c->d_lgti_io.reset();
   c->d_lgt_planes.reset();
   c->d_lgt_w.reset();
   c->d_lgt_acc.reset();
@@ -108,7 +110,8 @@ int dsgd_lg_topics_set_weights(dsgd_ctx* c, const float* W) {
     memcpy(c->pin_w.p, W + (size_t)t * (size_t)c->dp, bytes);
     HIP_TRY(hipMemcpyAsync(c->d_io, c->pin_w.p, bytes, hipMemcpyHostToDevice, c->stream));
     DSGD_TRY(pin_sent(c, c->pin_w));
-    DSGD_TRY(launch_permute_in(c, c->d_io, c->d_lgt_w + (size_t)t * (size_t)lgt_w_stride(c->dp)));
+    DSGD_TRY(launch_permute_in(c, c->d_io, c->lgt_il ? c->d_lgti_io.get() : c->d_lgt_w + (size_t)t * (size_t)lgt_w_stride(c->dp)));
+    if (c->lgt_il) DSGD_TRY(lgti_pack(c, t, true));
   }
   c->lgt_nsq_stale = true;
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -124,7 +127,8 @@ int dsgd_lg_topics_get_weights(dsgd_ctx* c, float* W_out) {
   const size_t bytes = sizeof(float) * (size_t)c->dp;
   DSGD_TRY(pin_acquire(c->pin_out, bytes * (size_t)c->lgt_T));
   for (int t = 0; t < c->lgt_T; ++t) {
-    DSGD_TRY(launch_permute_out(c, c->d_lgt_w + (size_t)t * (size_t)lgt_w_stride(c->dp), c->d_io));
+    if (c->lgt_il) DSGD_TRY(lgti_pack(c, t, false));
+    DSGD_TRY(launch_permute_out(c, c->lgt_il ? c->d_lgti_io.get() : c->d_lgt_w + (size_t)t * (size_t)lgt_w_stride(c->dp), c->d_io));
     HIP_TRY(hipMemcpyAsync(static_cast<char*>(c->pin_out.p.get()) + (size_t)t * bytes, c->d_io, bytes, hipMemcpyDeviceToHost, c->stream));
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -138,7 +142,7 @@ static int lgt_ensure(dsgd_ctx* c, int n_workers) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->lgt_k = 0;
   const int cap = std::max(n_workers, 4);
-  const size_t words = (size_t)lgt_acc_words(c->lgt_T, cap, c->dp);
+  const size_t words = (size_t)(c->lgt_il ? lgti_acc_words(lgti_tp(c->lgt_T), cap, c->dp) : lgt_acc_words(c->lgt_T, cap, c->dp));
   DSGD_TRY(c->d_lgt_acc.alloc(words));
   HIP_TRY(hipMemsetAsync(c->d_lgt_acc, 0, sizeof(unsigned long long) * words, c->stream));
   c->lgt_k = cap;
@@ -147,6 +151,7 @@ static int lgt_ensure(dsgd_ctx* c, int n_workers) {
 
 // The TWO launches of one step over K lists of positions in `idx`, the longest of `longest` rows, whatever T
 static int lgt_launch(dsgd_ctx* c, int K, long long longest, float lr, const int* idx, const WorkSeg* segs) {
+  if (c->lgt_il) return lgti_launch(c, K, longest, lr, idx, segs);
   LgtArgs a;
   a.w = c->d_lgt_w;
   a.w_stride = lgt_w_stride(c->dp);
@@ -266,7 +271,9 @@ int dsgd_lg_topics_loss_acc(dsgd_ctx* c, int64_t row_begin, int64_t row_end, dou
   DSGD_TRY(lgt_ready(c, "dsgd_lg_topics_loss_acc"));
   const int T = c->lgt_T;
   const long long nb = lg_finish_blocks(c->dp);
-  if (c->lgt_nsq_stale) {   // |w_t|^2 of weights the finish did not write: the finish's grid and tree, the same bits
+  if (c->lgt_nsq_stale && c->lgt_il) {
+    DSGD_TRY(lgti_launch_nsq(c));
+  } else if (c->lgt_nsq_stale) {   // |w_t|^2 of weights the finish did not write: the finish's grid and tree, the same bits
     hipLaunchKernelGGL(dsgd_lg_nsq_kernel, dim3((unsigned)nb, (unsigned)T), dim3(LG_THREADS), 0, c->stream, c->d_lgt_w.get(),
                        lgt_w_stride(c->dp), c->dp, c->d_lgt_part.get());
     HIP_TRY(hipGetLastError());
@@ -277,9 +284,12 @@ int dsgd_lg_topics_loss_acc(dsgd_ctx* c, int64_t row_begin, int64_t row_end, dou
   const long long grid = lg_eval_blocks(rows, c->n_cu);
   const int hw = lgt_eval_hw(rows, std::min(c->hw_eval, c->dp), T);
   const size_t lds = sizeof(float) * (size_t)lgt_eval_lds_floats(hw, T);
-  hipLaunchKernelGGL(dsgd_lg_topics_eval_kernel, dim3((unsigned)grid), dim3(LG_EVAL_THREADS), lds, c->stream, view(c), c->d_lgt_w.get(),
-                     lgt_w_stride(c->dp), c->d_lgt_planes.get(), T, (long long)row_begin, (long long)row_end, c->d_lgt_tally.get(), hw,
-                     c->d_lgt_part + lgt_loss_at(T, 0, c->dp, c->n_cu), (long long)c->n_cu);
+  if (c->lgt_il)
+    DSGD_TRY(lgti_launch_eval(c, row_begin, row_end, grid));
+  else
+    hipLaunchKernelGGL(dsgd_lg_topics_eval_kernel, dim3((unsigned)grid), dim3(LG_EVAL_THREADS), lds, c->stream, view(c), c->d_lgt_w.get(),
+                       lgt_w_stride(c->dp), c->d_lgt_planes.get(), T, (long long)row_begin, (long long)row_end, c->d_lgt_tally.get(), hw,
+                       c->d_lgt_part + lgt_loss_at(T, 0, c->dp, c->n_cu), (long long)c->n_cu);
   HIP_TRY(hipGetLastError());
   const size_t words = (size_t)lgt_part_words(T, c->dp, c->n_cu), tally_words = (size_t)T * LG_TALLY_WORDS;
   DSGD_TRY(pin_acquire(c->pin_out, sizeof(double) * words + sizeof(unsigned long long) * tally_words));
@@ -312,8 +322,11 @@ int dsgd_lg_topics_predict(dsgd_ctx* c, const int32_t* idx, int64_t n, float* p_
   DSGD_TRY(reset_counters(c));
   DSGD_TRY(send_idx(c, idx, n));
   DSGD_TRY(pin_acquire(c->pin_out, sizeof(float) * out));
-  hipLaunchKernelGGL(dsgd_lg_topics_predict_kernel, dim3((unsigned)grid_for(c, n, LG_GROUP)), dim3(LG_THREADS), 0, c->stream, view(c),
-                     c->d_lgt_w.get(), lgt_w_stride(c->dp), T, c->d_idx.get(), (long long)n, c->d_lgt_p.get(), c->d_sc.get());
+  if (c->lgt_il)
+    DSGD_TRY(lgti_launch_predict(c, n));
+  else
+    hipLaunchKernelGGL(dsgd_lg_topics_predict_kernel, dim3((unsigned)grid_for(c, n, LG_GROUP)), dim3(LG_THREADS), 0, c->stream, view(c),
+                       c->d_lgt_w.get(), lgt_w_stride(c->dp), T, c->d_idx.get(), (long long)n, c->d_lgt_p.get(), c->d_sc.get());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(c->pin_out.p, c->d_lgt_p, sizeof(float) * out, hipMemcpyDeviceToHost, c->stream));
   DSGD_TRY(read_scalars(c));

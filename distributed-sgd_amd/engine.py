@@ -455,12 +455,15 @@ class Engine:
 
     # -- several topics: one-vs-rest label planes on the same rows (include/dsgd.h "SEVERAL TOPICS") --------------
     lg_topics_max = 8
+    lg_topics_il_max = 32
 
-    def lg_topics_set(self, planes):
+    def lg_topics_set(self, planes, interleaved=False):
         """T <= 8 label planes, int8 [T, n_rows] of +1 / -1 (dsgd_lg_topics_set): the topics' weights start at zero; the
-        engine's own labels and weights are not touched.  None or an empty array drops the topics."""
+        engine's own labels and weights are not touched.  None or an empty array drops the topics.  interleaved: T <= 32,
+        the topics stored side by side (dsgd_lg_topics_set_il) -- the same calls, the same bits."""
+        setter = self._lib.dsgd_lg_topics_set_il if interleaved else self._lib.dsgd_lg_topics_set
         if planes is None or np.size(planes) == 0:
-            check(self._lib.dsgd_lg_topics_set(self._ctx, C.c_int32(0), None))
+            check(setter(self._ctx, C.c_int32(0), None))
             return
         planes = np.asarray(planes)
         if planes.ndim != 2 or planes.shape[1] != self.n_rows:
@@ -468,7 +471,7 @@ class Engine:
         if planes.dtype != np.int8 and not np.array_equal(planes, planes.astype(np.int8)):
             raise ValueError("plane entries must be +1 or -1")
         planes = np.ascontiguousarray(planes, dtype=np.int8)
-        check(self._lib.dsgd_lg_topics_set(self._ctx, C.c_int32(planes.shape[0]), ptr(planes)))
+        check(setter(self._ctx, C.c_int32(planes.shape[0]), ptr(planes)))
 
     @property
     def n_topics(self):

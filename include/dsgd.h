@@ -1117,6 +1117,14 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *                               the rows that went), and so does a new column ranking (a communicator attached and detached):
  *                               the calls return DSGD_ESTATE until topics are set again (that drop comes BEHIND a call's
  *                               argument checks: a call refused for its arguments has changed nothing)
+ *   INTERLEAVED                 dsgd_lg_topics_set_il: the same planes, 1 <= T <= 32 (LG_TOPICS_IL_MAX), stored side by side
+ *                               (csrc/dsgd_lg_topics_il.hpp): with TP = T rounded up to a multiple of 4, weights Wi[rank][TP], labels
+ *                               Pi[row][TP], column sums acc[k][rank][TP] -- per non-zero ONE 16-byte load per four topics, the
+ *                               adds to adjacent words.  THE CONTRACT is the same BITS; every dsgd_lg_topics_* call above serves
+ *                               whichever form is set (a step stays TWO launches whatever T: dsgd_lg_topics_il_grad_kernel,
+ *                               dsgd_lg_topics_il_finish_kernel), with the same refusals in the same order (T outside [0, 32]
+ *                               DSGD_EINVAL).  Setting topics in either form replaces topics set in the other; T = 0 drops the
+ *                               topics in either call; dsgd_lg_topics_set keeps its limit of 8
  *
  * LIMITS (out of scope, each refused or simply absent): several topics run per-call steps over lists only -- no plans, no
  * row ranges or column lists, no column slices, no ranks, no asynchronous iteration, one lambda and one lr for all topics,
@@ -1186,6 +1194,7 @@ int dsgd_lg_eval_job(dsgd_ctx* ctx, const float* w /* NULL = resident */, const 
                      double* acc /* may be NULL */, int32_t* K_out /* may be NULL */);
 /* several topics ("SEVERAL TOPICS" above) */
 int dsgd_lg_topics_set(dsgd_ctx* ctx, int32_t T, const int8_t* planes /* T x n_rows, topic-major, each +1 or -1 */);
+int dsgd_lg_topics_set_il(dsgd_ctx* ctx, int32_t T /* up to 32 */, const int8_t* planes /* T x n_rows, topic-major, each +1 or -1 */);
 int dsgd_lg_topics_count(dsgd_ctx* ctx, int32_t* T_out /* the topics set now; 0: none */);
 int dsgd_lg_topics_set_weights(dsgd_ctx* ctx, const float* W /* T x (D+1), key order */);
 int dsgd_lg_topics_get_weights(dsgd_ctx* ctx, float* W_out /* T x (D+1), key order */);

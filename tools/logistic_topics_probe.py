@@ -10,7 +10,11 @@ not separated.  The defaults make the shortest window (3 x 100, T = 1: 10,000 st
 that no figure rests on a window of milliseconds; each window's length in seconds is reported beside its figure.  Both sides
 are warmed with one call of the timed shape; the two are alternated `repeats` times and the median and the spread (min, max)
 are reported.  The weights are compared bit for bit after the warm-up pair.  A run without a gfx950 device fails:
-there is no fallback.  One JSON line goes to stdout and to --out."""
+there is no fallback.  One JSON line goes to stdout and to --out.
+
+--interleaved: the interleaved form (Engine.lg_topics_set(planes, interleaved=True)) under the same protocol -- for T = 1, 2, 4, 8
+against the planar dsgd_lg_topics_sync_steps on the same engine, for T = 16, 32 against T single-model contexts stepped one
+after the other; the default --out becomes profiles/logistic_topics_il_probe.json."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -22,14 +26,17 @@ ap.add_argument("--steps", type=int, default=1000, help="steps per call")
 ap.add_argument("--calls", type=int, default=10, help="calls per timed window")
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--lam", type=float, default=1e-5)
-ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "logistic_topics_probe.json"))
+ap.add_argument("--interleaved", action="store_true", help="time the interleaved form: against the planar form up to T = 8, against T single models at 16 and 32")
+ap.add_argument("--out")
 a = ap.parse_args()
+a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                              "logistic_topics_il_probe.json" if a.interleaved else "logistic_topics_probe.json")
 if dsgd_amd.device_count() < 1:
     sys.exit("logistic_topics_probe: no gfx950 device (nothing is measured without one)")
 
 data = dsgd_amd.synth.generate(a.rows, seed=0)
 rng = np.random.default_rng(1)
-planes = np.ascontiguousarray(np.vstack([data.label[None].astype(np.int8), rng.choice(np.array([-1, 1], np.int8), size=(7, data.n_rows))]))
+planes = np.ascontiguousarray(np.vstack([data.label[None].astype(np.int8), rng.choice(np.array([-1, 1], np.int8), size=(31 if a.interleaved else 7, data.n_rows))]))
 LR = 2.0 ** -10
 
 
@@ -50,16 +57,18 @@ def timed(fn):
 result = {"rows": data.n_rows, "steps_per_call": a.steps, "calls_per_window": a.calls, "repeats": a.repeats, "unit": "us per step, host wall time around synchronising calls",
           "shapes": []}
 singles = []
-for t in range(8):
+for t in range(32 if a.interleaved else 8):
     e = dsgd_amd.Engine(data.dim, a.lam)
     e.load_csr(data.row_ptr, data.col, data.val, planes[t])
     singles.append(e)
-with dsgd_amd.Engine(data.dim, a.lam) as eng:
+with dsgd_amd.Engine(data.dim, a.lam) as eng, dsgd_amd.Engine(data.dim, a.lam) as other:
     eng.load_csr(data.row_ptr, data.col, data.val, data.label)
+    other.load_csr(data.row_ptr, data.col, data.val, data.label)      # (--interleaved: the planar form's engine)
     for k, batch in ((3, 100), (4, 4096)):
         flat, offs = lists_for(k, batch)
-        for T in (1, 2, 4, 8):
-            eng.lg_topics_set(planes[:T])
+        for T in ((1, 2, 4, 8, 16, 32) if a.interleaved else (1, 2, 4, 8)):
+            planar_side = a.interleaved and T <= 8                       # --interleaved: the other side is the planar form while it can be
+            eng.lg_topics_set(planes[:T], interleaved=a.interleaved)
             zero = np.zeros(data.dim + 1, dtype=np.float32)
 
             def run_topics():
@@ -69,16 +78,26 @@ with dsgd_amd.Engine(data.dim, a.lam) as eng:
                 for t in range(T):
                     singles[t].lg_sync_steps(flat, offs, a.steps, k, LR)
 
+            def run_planar():
+                other.lg_topics_sync_steps(flat, offs, a.steps, k, LR)
+
             for t in range(T):
                 singles[t].set_weights(zero)
+            if planar_side:
+                other.lg_topics_set(planes[:T])
+                run_singles = run_planar
             run_topics(), run_singles()                                   # warm-up of the timed shape; then the bits
             W = eng.lg_topics_get_weights()
-            same = all(np.array_equal(W[t].view(np.uint32), singles[t].get_weights().view(np.uint32)) for t in range(T))
+            if planar_side:
+                same = np.array_equal(W.view(np.uint32), other.lg_topics_get_weights().view(np.uint32))
+            else:
+                same = all(np.array_equal(W[t].view(np.uint32), singles[t].get_weights().view(np.uint32)) for t in range(T))
             tt, ts = [], []
             for _ in range(a.repeats):                                    # alternated
                 tt.append(timed(run_topics))
                 ts.append(timed(run_singles))
             result["shapes"].append({"workers": k, "batch": batch, "T": T, "bits_equal": bool(same),
+                                     "topics_side": "interleaved" if a.interleaved else "planar", "other_side": "planar" if planar_side else "singles",
                                      "shortest_window_s": min(tt + ts) * a.steps * a.calls * 1e-6,
                                      "topics_us": {"median": float(np.median(tt)), "min": min(tt), "max": max(tt)},
                                      "singles_us": {"median": float(np.median(ts)), "min": min(ts), "max": max(ts)}})

@@ -28,6 +28,7 @@ best weights kept, maxSteps = train rows x max-epochs.  With --lg-slices a windo
 (include/dsgd.h "THE LOGISTIC MODEL", SEVERAL TOPICS) -- rcv1.load_topics' planes (+1 iff ANY qrels line tags the document),
 host.LogisticTopics: Master.fit's flow with the lists shared, one launch pair per step whatever the number of topics, the early
 stopping applied per topic.  With --synthetic plane 0 is the data's labels and the others are the signs of seeded planted directions.
+--lg-topics-interleaved (with --topics): up to 32 names, the topics stored side by side (dsgd_lg_topics_set_il): the same bits.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -47,12 +48,14 @@ ap.add_argument("--lg-plans", action="store_true", help="logistic: Master.fit's 
 ap.add_argument("--lg-slices", action="store_true", help="logistic: --lg-plans on column slices, one persistent launch per epoch (host.LogisticSync(slices=True))")
 ap.add_argument("--lg-async", action="store_true", help="logistic: MasterAsync.fit's flow on the zero-lag schedule (host.LogisticAsync); honours --lg-slices")
 ap.add_argument("--topics", help="logistic: comma-separated topic names, one-vs-rest in one launch pair per step (host.LogisticTopics)")
+ap.add_argument("--lg-topics-interleaved", action="store_true", help="--topics: the interleaved form, up to 32 names (Engine.lg_topics_set(interleaved=True))")
 a = ap.parse_args()
-topics = [t for t in (a.topics or "").split(",") if t]
+topics =[t for t in (a.topics or "").split(",") if t]
 if topics and (a.model != "logistic" or a.lg_plans or a.lg_slices or a.lg_async):
     ap.error("--topics goes with --model logistic alone (no plans, slices or asynchronous fit over several topics)")
-if len(topics) > dsgd_amd.Engine.lg_topics_max:
-    ap.error("--topics takes at most %d names" % dsgd_amd.Engine.lg_topics_max)
+topics_max = dsgd_amd.Engine.lg_topics_il_max if a.lg_topics_interleaved else dsgd_amd.Engine.lg_topics_max
+if len(topics) > topics_max:
+    ap.error("--topics takes at most %d names (%d with --lg-topics-interleaved)" % (topics_max, dsgd_amd.Engine.lg_topics_il_max))
 if a.lg_async and a.lg_plans:
     ap.error("--lg-plans and --lg-async are two fits: give one (--lg-slices goes with either)")
 a.lg_plans = a.lg_plans or a.lg_slices
@@ -108,8 +111,8 @@ def synthetic_planes(data, n_topics, seed=1):
 
 
 def fit_topics(eng, cfg, planes, names, n_train, n_rows):
-    eng.lg_topics_set(planes)
-    master = host.LogisticTopics(eng, n_train, n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log)
+    eng.lg_topics_set(planes, interleaved=a.lg_topics_interleaved)
+    master = host.LogisticTopics(eng, n_train, n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log, interleaved=a.lg_topics_interleaved)
     l0, a0 = eng.lg_topics_loss_acc(0, n_train)
     for t, name in enumerate(names):
         log("{}: {} of {} rows tagged, initial loss {}, initial accuracy {}", name, int((planes[t] > 0).sum()), n_rows, l0[t], a0[t])
