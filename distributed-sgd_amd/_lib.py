@@ -59,6 +59,7 @@ SYMBOLS = [
     "dsgd_plan_create_from_seed_job_lg", "dsgd_lg_eval_job",
     "dsgd_lg_topics_set", "dsgd_lg_topics_set_weights", "dsgd_lg_topics_get_weights", "dsgd_lg_topics_sync_step", "dsgd_lg_topics_sync_steps",
     "dsgd_lg_topics_loss_acc", "dsgd_lg_topics_predict", "dsgd_lg_topics_count", "dsgd_lg_topics_set_il",
+    "dsgd_lg_topics_set_wide",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -178,6 +179,7 @@ def load():
     if hasattr(lib, "dsgd_lg_topics_set"):   # several topics (include/dsgd.h "SEVERAL TOPICS")
         lib.dsgd_lg_topics_set.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]   # (ctx, T, planes*)
         lib.dsgd_lg_topics_set_il.argtypes = lib.dsgd_lg_topics_set.argtypes       # (the interleaved form: up to 32 topics)
+        lib.dsgd_lg_topics_set_wide.argtypes = lib.dsgd_lg_topics_set.argtypes     # (the wide form: up to 128 topics)
         lib.dsgd_lg_topics_count.argtypes = [C.c_void_p, C.c_void_p]               # (ctx, T_out*)
         lib.dsgd_lg_topics_set_weights.argtypes = [C.c_void_p, C.c_void_p]
         lib.dsgd_lg_topics_get_weights.argtypes = [C.c_void_p, C.c_void_p]

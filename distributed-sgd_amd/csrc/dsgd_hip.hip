@@ -129,6 +129,7 @@ static bool available() {
 #include "dsgd_logistic.hpp"   // (the logistic model beside the SVM: its own gradient, finish, evaluation and probabilities)
 #include "dsgd_lg_topics.hpp"  // (... over several topics: one-vs-rest label planes on the same rows, one launch pair per step)
 #include "dsgd_lg_topics_il.hpp"   // (... interleaved: up to 32 topics side by side per rank, row and column)
+#include "dsgd_lg_topics_wide.hpp"   // (... wide: up to 128 topics over that layout, the lanes across the topics)
 #include "dsgd_lg_eval.hpp"    // (... evaluated as Master evaluates: classes and tallies of K row ranges, the rows of a list)
 #include "dsgd_lg_eval_job.hpp"   // (... and the job's evaluation on every rank: the gather record, its fold, the kernel that fills it)
 #include "dsgd_batch.hpp"
@@ -590,6 +591,7 @@ struct dsgd_ctx {
   bool lgt_nsq_stale = true;
   bool lgt_il = false;   // the topics are interleaved (dsgd_lg_topics_set_il; csrc/dsgd_lg_topics_il.hpp): d_lgt_planes is Pi[row][TP],
                          // d_lgt_w is Wi[rank][TP], d_lgt_acc is [lgt_k][rank][TP]; d_lgti_io: one topic's rank-order vector on its way in or out
+  bool lgt_wide = false;   // ... and served by the wide kernels (dsgd_lg_topics_set_wide; csrc/dsgd_lg_topics_wide.hpp): lgt_il is set as well
   DevBuf<signed char> d_lgt_planes;
   DevBuf<float> d_lgt_w;
   DevBuf<unsigned long long> d_lgt_acc;
@@ -2340,6 +2342,9 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   DSGD_ATTR(dsgd_lg_eval_list_kernel);
   DSGD_ATTR(dsgd_lg_topics_eval_kernel);
   DSGD_ATTR(dsgd_lg_topics_il_eval_kernel);
+  DSGD_ATTR(dsgd_lg_topics_wide_eval_kernel<16>);
+  DSGD_ATTR(dsgd_lg_topics_wide_eval_kernel<32>);
+  DSGD_ATTR(dsgd_lg_topics_wide_eval_kernel<64>);
   DSGD_ATTR(dsgd_colcount_kernel);
   DSGD_ATTR((dsgd_hogwild_kernel<false, false>));
   DSGD_ATTR((dsgd_hogwild_kernel<true, false>));
@@ -3671,6 +3676,7 @@ int dsgd_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row_en
 
 #include "dsgd_lg_calls.hpp"   // (the logistic model's entry points: dsgd_lg_*)
 #include "dsgd_lg_topics_il_calls.hpp"   // (... interleaved: dsgd_lg_topics_set_il and the interleaved side of every launch site)
+#include "dsgd_lg_topics_wide_calls.hpp"   // (... wide: dsgd_lg_topics_set_wide and the wide side of every launch site)
 #include "dsgd_lg_topics_calls.hpp"   // (... over several topics: dsgd_lg_topics_*)
 
 // ---- distributed evaluation (csrc/dsgd_predict.hpp; ref: core/Master.scala:61-98) ----

@@ -12,6 +12,7 @@ static void lgt_drop(dsgd_ctx* c) {
   c->lgt_T = 0;
   c->lgt_k = 0;
   c->lgt_il = false;
+  c->lgt_wide = false;
   c->d_lgti_io.reset();
   c->d_lgt_planes.reset();
   c->d_lgt_w.reset();
@@ -151,6 +152,7 @@ static int lgt_ensure(dsgd_ctx* c, int n_workers) {
 
 // The TWO launches of one step over K lists of positions in `idx`, the longest of `longest` rows, whatever T
 static int lgt_launch(dsgd_ctx* c, int K, long long longest, float lr, const int* idx, const WorkSeg* segs) {
+  if (c->lgt_wide) return lgtw_launch(c, K, longest, lr, idx, segs);
   if (c->lgt_il) return lgti_launch(c, K, longest, lr, idx, segs);
   LgtArgs a;
   a.w = c->d_lgt_w;
@@ -271,7 +273,9 @@ int dsgd_lg_topics_loss_acc(dsgd_ctx* c, int64_t row_begin, int64_t row_end, dou
   DSGD_TRY(lgt_ready(c, "dsgd_lg_topics_loss_acc"));
   const int T = c->lgt_T;
   const long long nb = lg_finish_blocks(c->dp);
-  if (c->lgt_nsq_stale && c->lgt_il) {
+  if (c->lgt_nsq_stale && c->lgt_wide) {
+    DSGD_TRY(lgtw_launch_nsq(c));
+  } else if (c->lgt_nsq_stale && c->lgt_il) {
     DSGD_TRY(lgti_launch_nsq(c));
   } else if (c->lgt_nsq_stale) {   // |w_t|^2 of weights the finish did not write: the finish's grid and tree, the same bits
     hipLaunchKernelGGL(dsgd_lg_nsq_kernel, dim3((unsigned)nb, (unsigned)T), dim3(LG_THREADS), 0, c->stream, c->d_lgt_w.get(),
@@ -284,7 +288,9 @@ int dsgd_lg_topics_loss_acc(dsgd_ctx* c, int64_t row_begin, int64_t row_end, dou
   const long long grid = lg_eval_blocks(rows, c->n_cu);
   const int hw = lgt_eval_hw(rows, std::min(c->hw_eval, c->dp), T);
   const size_t lds = sizeof(float) * (size_t)lgt_eval_lds_floats(hw, T);
-  if (c->lgt_il)
+  if (c->lgt_wide)
+    DSGD_TRY(lgtw_launch_eval(c, row_begin, row_end, grid));
+  else if (c->lgt_il)
     DSGD_TRY(lgti_launch_eval(c, row_begin, row_end, grid));
   else
     hipLaunchKernelGGL(dsgd_lg_topics_eval_kernel, dim3((unsigned)grid), dim3(LG_EVAL_THREADS), lds, c->stream, view(c), c->d_lgt_w.get(),
@@ -322,7 +328,9 @@ int dsgd_lg_topics_predict(dsgd_ctx* c, const int32_t* idx, int64_t n, float* p_
   DSGD_TRY(reset_counters(c));
   DSGD_TRY(send_idx(c, idx, n));
   DSGD_TRY(pin_acquire(c->pin_out, sizeof(float) * out));
-  if (c->lgt_il)
+  if (c->lgt_wide)
+    DSGD_TRY(lgtw_launch_predict(c, n));
+  else if (c->lgt_il)
     DSGD_TRY(lgti_launch_predict(c, n));
   else
     hipLaunchKernelGGL(dsgd_lg_topics_predict_kernel, dim3((unsigned)grid_for(c, n, LG_GROUP)), dim3(LG_THREADS), 0, c->stream, view(c),

@@ -456,12 +456,16 @@ class Engine:
     # -- several topics: one-vs-rest label planes on the same rows (include/dsgd.h "SEVERAL TOPICS") --------------
     lg_topics_max = 8
     lg_topics_il_max = 32
+    lg_topics_wide_max = 128
 
-    def lg_topics_set(self, planes, interleaved=False):
+    def lg_topics_set(self, planes, interleaved=False, wide=False):
         """T <= 8 label planes, int8 [T, n_rows] of +1 / -1 (dsgd_lg_topics_set): the topics' weights start at zero; the
         engine's own labels and weights are not touched.  None or an empty array drops the topics.  interleaved: T <= 32,
-        the topics stored side by side (dsgd_lg_topics_set_il) -- the same calls, the same bits."""
-        setter = self._lib.dsgd_lg_topics_set_il if interleaved else self._lib.dsgd_lg_topics_set
+        the topics stored side by side (dsgd_lg_topics_set_il) -- the same calls, the same bits.  wide: T <= 128, that layout
+        served with the lanes across the topics (dsgd_lg_topics_set_wide) -- the same calls, the same bits."""
+        if interleaved and wide:
+            raise ValueError("interleaved and wide are two forms: choose one")
+        setter = self._lib.dsgd_lg_topics_set_wide if wide else self._lib.dsgd_lg_topics_set_il if interleaved else self._lib.dsgd_lg_topics_set
         if planes is None or np.size(planes) == 0:
             check(setter(self._ctx, C.c_int32(0), None))
             return

@@ -1472,14 +1472,18 @@ class LogisticTopics:
 
     data layout: rows [0, n_train) are the train set, [n_train, n_rows) the test set.  Limits: one engine, no plans, no
     ranks, no column slices, one learning rate and one lambda for all topics.  interleaved: the engine's topics were set
-    with Engine.lg_topics_set(planes, interleaved=True) -- up to 32 of them; without it more than 8 are refused."""
+    with Engine.lg_topics_set(planes, interleaved=True) -- up to 32 of them; wide: with Engine.lg_topics_set(planes, wide=True)
+    -- up to 128; without either more than 8 are refused."""
 
     def __init__(self, backend, n_train: int, n_rows: int, node_count: int, rnd: Optional[JavaRandom] = None, log=None,
-                 interleaved: bool = False):
+                 interleaved: bool = False, wide: bool = False):
+        if interleaved and wide:
+            raise ValueError("interleaved and wide are two forms: choose one")
         if not 0 < n_train < n_rows:
             raise ValueError("LogisticTopics needs train rows [0, n_train) and test rows [n_train, n_rows)")
         self.backend, self.n_train, self.n_rows, self.node_count = backend, n_train, n_rows, node_count
-        self.max_topics = getattr(backend, "lg_topics_il_max", 32) if interleaved else getattr(backend, "lg_topics_max", 8)
+        self.max_topics = (getattr(backend, "lg_topics_wide_max", 128) if wide else
+                           getattr(backend, "lg_topics_il_max", 32) if interleaved else getattr(backend, "lg_topics_max", 8))
         self.rnd = rnd or JavaRandom(0)
         self.log = log or (lambda *a: None)
         self.losses: List[List[float]] = []        # per topic, newest first
@@ -1498,7 +1502,7 @@ class LogisticTopics:
             raise ValueError("initial_weights must be [T, D + 1]")
         T = W0.shape[0]
         if T > self.max_topics:
-            raise ValueError("%d topics: at most %d (interleaved=True serves up to 32)" % (T, self.max_topics))
+            raise ValueError("%d topics: at most %d (interleaved=True serves up to 32, wide=True up to 128)" % (T, self.max_topics))
         self.backend.lg_topics_set_weights(W0)
         self.losses, self.accs = [[] for _ in range(T)], [[] for _ in range(T)]
         self.test_losses, self.test_accs = [[] for _ in range(T)], [[] for _ in range(T)]

@@ -1125,6 +1125,15 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *                               dsgd_lg_topics_il_finish_kernel), with the same refusals in the same order (T outside [0, 32]
  *                               DSGD_EINVAL).  Setting topics in either form replaces topics set in the other; T = 0 drops the
  *                               topics in either call; dsgd_lg_topics_set keeps its limit of 8
+ *   WIDE                        dsgd_lg_topics_set_wide: the same planes, 1 <= T <= 128 (LG_TOPICS_WIDE_MAX), over the interleaved
+ *                               layout with the LANES ACROSS THE TOPICS (csrc/dsgd_lg_topics_wide.hpp): a row is served by 16, 32
+ *                               or 64 lanes (the smallest with two topics per lane), per non-zero ONE coalesced load of the rank's
+ *                               weights by the group and adds to adjacent words from adjacent lanes, no reduction across lanes.
+ *                               THE CONTRACT is the same BITS; every dsgd_lg_topics_* call above serves whichever of the three
+ *                               forms is set (a step stays TWO launches: dsgd_lg_topics_wide_grad_kernel<GW>,
+ *                               dsgd_lg_topics_wide_finish_kernel), with the same refusals in the same order (T outside [0, 128]
+ *                               DSGD_EINVAL).  Setting topics in any form replaces those of the others; the other setters keep
+ *                               their limits of 8 and 32
  *
  * LIMITS (out of scope, each refused or simply absent): several topics run per-call steps over lists only -- no plans, no
  * row ranges or column lists, no column slices, no ranks, no asynchronous iteration, one lambda and one lr for all topics,
@@ -1195,6 +1204,7 @@ int dsgd_lg_eval_job(dsgd_ctx* ctx, const float* w /* NULL = resident */, const 
 /* several topics ("SEVERAL TOPICS" above) */
 int dsgd_lg_topics_set(dsgd_ctx* ctx, int32_t T, const int8_t* planes /* T x n_rows, topic-major, each +1 or -1 */);
 int dsgd_lg_topics_set_il(dsgd_ctx* ctx, int32_t T /* up to 32 */, const int8_t* planes /* T x n_rows, topic-major, each +1 or -1 */);
+int dsgd_lg_topics_set_wide(dsgd_ctx* ctx, int32_t T /* up to 128 */, const int8_t* planes /* T x n_rows, topic-major, each +1 or -1 */);
 int dsgd_lg_topics_count(dsgd_ctx* ctx, int32_t* T_out /* the topics set now; 0: none */);
 int dsgd_lg_topics_set_weights(dsgd_ctx* ctx, const float* W /* T x (D+1), key order */);
 int dsgd_lg_topics_get_weights(dsgd_ctx* ctx, float* W_out /* T x (D+1), key order */);

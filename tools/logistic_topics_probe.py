@@ -14,7 +14,12 @@ there is no fallback.  One JSON line goes to stdout and to --out.
 
 --interleaved: the interleaved form (Engine.lg_topics_set(planes, interleaved=True)) under the same protocol -- for T = 1, 2, 4, 8
 against the planar dsgd_lg_topics_sync_steps on the same engine, for T = 16, 32 against T single-model contexts stepped one
-after the other; the default --out becomes profiles/logistic_topics_il_probe.json."""
+after the other; the default --out becomes profiles/logistic_topics_il_probe.json.
+
+--wide: the wide form (Engine.lg_topics_set(planes, wide=True)) under the same protocol -- for T = 1, 8, 32 against the interleaved
+form on a second context, for T = 64, 103, 128 against ceil(T / 32) interleaved contexts (each with its own copy of the matrix)
+stepped one after the other, which is what serves that many topics without the wide form; --T picks the topic counts of one
+run; the default --out becomes profiles/logistic_topics_wide_probe.json."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -27,17 +32,22 @@ ap.add_argument("--calls", type=int, default=10, help="calls per timed window")
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--lam", type=float, default=1e-5)
 ap.add_argument("--interleaved", action="store_true", help="time the interleaved form: against the planar form up to T = 8, against T single models at 16 and 32")
+ap.add_argument("--wide", action="store_true", help="time the wide form: against the interleaved form up to T = 32, against ceil(T / 32) interleaved contexts beyond")
+ap.add_argument("--T", help="--wide: comma-separated topic counts (default 1,8,32,64,103,128)")
 ap.add_argument("--out")
 a = ap.parse_args()
 a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "logistic_topics_il_probe.json" if a.interleaved else "logistic_topics_probe.json")
+                              "logistic_topics_wide_probe.json" if a.wide else "logistic_topics_il_probe.json" if a.interleaved else "logistic_topics_probe.json")
+if a.wide and a.interleaved:
+    sys.exit("logistic_topics_probe: --wide and --interleaved are two runs")
 if dsgd_amd.device_count() < 1:
     sys.exit("logistic_topics_probe: no gfx950 device (nothing is measured without one)")
 
 data = dsgd_amd.synth.generate(a.rows, seed=0)
 rng = np.random.default_rng(1)
-planes = np.ascontiguousarray(np.vstack([data.label[None].astype(np.int8), rng.choice(np.array([-1, 1], np.int8), size=(31 if a.interleaved else 7, data.n_rows))]))
+planes = np.ascontiguousarray(np.vstack([data.label[None].astype(np.int8), rng.choice(np.array([-1, 1], np.int8), size=(127 if a.wide else 31 if a.interleaved else 7, data.n_rows))]))
 LR = 2.0 ** -10
+wide_T = tuple(int(t) for t in (a.T or "1,8,32,64,103,128").split(","))
 
 
 def lists_for(k, batch):
@@ -57,18 +67,22 @@ def timed(fn):
 result = {"rows": data.n_rows, "steps_per_call": a.steps, "calls_per_window": a.calls, "repeats": a.repeats, "unit": "us per step, host wall time around synchronising calls",
           "shapes": []}
 singles = []
-for t in range(32 if a.interleaved else 8):
+for t in range(0 if a.wide else 32 if a.interleaved else 8):
     e = dsgd_amd.Engine(data.dim, a.lam)
     e.load_csr(data.row_ptr, data.col, data.val, planes[t])
     singles.append(e)
 with dsgd_amd.Engine(data.dim, a.lam) as eng, dsgd_amd.Engine(data.dim, a.lam) as other:
     eng.load_csr(data.row_ptr, data.col, data.val, data.label)
     other.load_csr(data.row_ptr, data.col, data.val, data.label)      # (--interleaved: the planar form's engine)
+    il_parts = [other]                                                # (--wide: the interleaved contexts, 32 topics each)
+    for _ in range(-(-max(wide_T) // 32) - 1 if a.wide else 0):
+        il_parts.append(dsgd_amd.Engine(data.dim, a.lam))
+        il_parts[-1].load_csr(data.row_ptr, data.col, data.val, data.label)
     for k, batch in ((3, 100), (4, 4096)):
         flat, offs = lists_for(k, batch)
-        for T in ((1, 2, 4, 8, 16, 32) if a.interleaved else (1, 2, 4, 8)):
+        for T in (wide_T if a.wide else (1, 2, 4, 8, 16, 32) if a.interleaved else (1, 2, 4, 8)):
             planar_side = a.interleaved and T <= 8                       # --interleaved: the other side is the planar form while it can be
-            eng.lg_topics_set(planes[:T], interleaved=a.interleaved)
+            eng.lg_topics_set(planes[:T], interleaved=a.interleaved, wide=a.wide)
             zero = np.zeros(data.dim + 1, dtype=np.float32)
 
             def run_topics():
@@ -81,14 +95,24 @@ with dsgd_amd.Engine(data.dim, a.lam) as eng, dsgd_amd.Engine(data.dim, a.lam) a
             def run_planar():
                 other.lg_topics_sync_steps(flat, offs, a.steps, k, LR)
 
-            for t in range(T):
+            def run_il_parts():
+                for e in il_parts[:-(-T // 32)]:
+                    e.lg_topics_sync_steps(flat, offs, a.steps, k, LR)
+
+            for t in range(0 if a.wide else T):
                 singles[t].set_weights(zero)
+            if a.wide:
+                for i, e in enumerate(il_parts[:-(-T // 32)]):
+                    e.lg_topics_set(planes[32 * i:min(32 * i + 32, T)], interleaved=True)
+                run_singles = run_il_parts
             if planar_side:
                 other.lg_topics_set(planes[:T])
                 run_singles = run_planar
             run_topics(), run_singles()                                   # warm-up of the timed shape; then the bits
             W = eng.lg_topics_get_weights()
-            if planar_side:
+            if a.wide:
+                same = np.array_equal(W.view(np.uint32), np.vstack([e.lg_topics_get_weights() for e in il_parts[:-(-T // 32)]]).view(np.uint32))
+            elif planar_side:
                 same = np.array_equal(W.view(np.uint32), other.lg_topics_get_weights().view(np.uint32))
             else:
                 same = all(np.array_equal(W[t].view(np.uint32), singles[t].get_weights().view(np.uint32)) for t in range(T))
@@ -97,11 +121,12 @@ with dsgd_amd.Engine(data.dim, a.lam) as eng, dsgd_amd.Engine(data.dim, a.lam) a
                 tt.append(timed(run_topics))
                 ts.append(timed(run_singles))
             result["shapes"].append({"workers": k, "batch": batch, "T": T, "bits_equal": bool(same),
-                                     "topics_side": "interleaved" if a.interleaved else "planar", "other_side": "planar" if planar_side else "singles",
+                                     "topics_side": "wide" if a.wide else "interleaved" if a.interleaved else "planar",
+                                     "other_side": "%d interleaved" % -(-T // 32) if a.wide else "planar" if planar_side else "singles",
                                      "shortest_window_s": min(tt + ts) * a.steps * a.calls * 1e-6,
                                      "topics_us": {"median": float(np.median(tt)), "min": min(tt), "max": max(tt)},
                                      "singles_us": {"median": float(np.median(ts)), "min": min(ts), "max": max(ts)}})
-for e in singles:
+for e in singles + il_parts[1:]:
     e.close()
 line = json.dumps(result)
 print(line)

@@ -29,6 +29,9 @@ best weights kept, maxSteps = train rows x max-epochs.  With --lg-slices a windo
 host.LogisticTopics: Master.fit's flow with the lists shared, one launch pair per step whatever the number of topics, the early
 stopping applied per topic.  With --synthetic plane 0 is the data's labels and the others are the signs of seeded planted directions.
 --lg-topics-interleaved (with --topics): up to 32 names, the topics stored side by side (dsgd_lg_topics_set_il): the same bits.
+--lg-topics-wide (with --topics): up to 128 names, that layout with the lanes across the topics (dsgd_lg_topics_set_wide): the
+same bits.  --topics all: every topic code of the qrels file under data-path, sorted (RCV1-v2: 103) -- refused with the count
+when there are more than the chosen form serves.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -49,13 +52,20 @@ ap.add_argument("--lg-slices", action="store_true", help="logistic: --lg-plans o
 ap.add_argument("--lg-async", action="store_true", help="logistic: MasterAsync.fit's flow on the zero-lag schedule (host.LogisticAsync); honours --lg-slices")
 ap.add_argument("--topics", help="logistic: comma-separated topic names, one-vs-rest in one launch pair per step (host.LogisticTopics)")
 ap.add_argument("--lg-topics-interleaved", action="store_true", help="--topics: the interleaved form, up to 32 names (Engine.lg_topics_set(interleaved=True))")
+ap.add_argument("--lg-topics-wide", action="store_true", help="--topics: the wide form, up to 128 names (Engine.lg_topics_set(wide=True))")
 a = ap.parse_args()
 topics =[t for t in (a.topics or "").split(",") if t]
+if a.lg_topics_wide and a.lg_topics_interleaved:
+    ap.error("--lg-topics-interleaved and --lg-topics-wide are two forms: give one")
 if topics and (a.model != "logistic" or a.lg_plans or a.lg_slices or a.lg_async):
     ap.error("--topics goes with --model logistic alone (no plans, slices or asynchronous fit over several topics)")
-topics_max = dsgd_amd.Engine.lg_topics_il_max if a.lg_topics_interleaved else dsgd_amd.Engine.lg_topics_max
+topics_max = (dsgd_amd.Engine.lg_topics_wide_max if a.lg_topics_wide else
+              dsgd_amd.Engine.lg_topics_il_max if a.lg_topics_interleaved else dsgd_amd.Engine.lg_topics_max)
 if len(topics) > topics_max:
-    ap.error("--topics takes at most %d names (%d with --lg-topics-interleaved)" % (topics_max, dsgd_amd.Engine.lg_topics_il_max))
+    ap.error("--topics takes at most %d names (%d with --lg-topics-interleaved, %d with --lg-topics-wide)"
+             % (topics_max, dsgd_amd.Engine.lg_topics_il_max, dsgd_amd.Engine.lg_topics_wide_max))
+if topics == ["all"] and a.synthetic:
+    ap.error("--topics all reads the qrels file under data-path: not with --synthetic")
 if a.lg_async and a.lg_plans:
     ap.error("--lg-plans and --lg-async are two fits: give one (--lg-slices goes with either)")
 a.lg_plans = a.lg_plans or a.lg_slices
@@ -111,8 +121,9 @@ def synthetic_planes(data, n_topics, seed=1):
 
 
 def fit_topics(eng, cfg, planes, names, n_train, n_rows):
-    eng.lg_topics_set(planes, interleaved=a.lg_topics_interleaved)
-    master = host.LogisticTopics(eng, n_train, n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log, interleaved=a.lg_topics_interleaved)
+    eng.lg_topics_set(planes, interleaved=a.lg_topics_interleaved, wide=a.lg_topics_wide)
+    master = host.LogisticTopics(eng, n_train, n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log, interleaved=a.lg_topics_interleaved,
+                                 wide=a.lg_topics_wide)
     l0, a0 = eng.lg_topics_loss_acc(0, n_train)
     for t, name in enumerate(names):
         log("{}: {} of {} rows tagged, initial loss {}, initial accuracy {}", name, int((planes[t] > 0).sum()), n_rows, l0[t], a0[t])
@@ -136,7 +147,14 @@ if a.synthetic:
     if topics:
         planes = synthetic_planes(data, len(topics))
 elif topics:
-    data, planes = rcv1.load_topics(cfg.data_path, topics, full=cfg.full)
+    if topics == ["all"]:                                              # every code the qrels file names, sorted
+        with open(os.path.join(cfg.data_path, rcv1.QRELS)) as f:
+            topics = sorted({line.split(None, 1)[0] for line in f if line.strip()})
+        if len(topics) > topics_max:
+            sys.exit("--topics all: the qrels file names %d topics, the chosen form serves %d (--lg-topics-wide: %d)"
+                     % (len(topics), topics_max, dsgd_amd.Engine.lg_topics_wide_max))
+    parts = [rcv1.load_topics(cfg.data_path, topics[i:i + 64], full=cfg.full) for i in range(0, len(topics), 64)]   # (64 names per parse)
+    data, planes = parts[0][0], np.ascontiguousarray(np.vstack([p[1] for p in parts]))
 else:
     data = rcv1.load(cfg.data_path, full=cfg.full)
 log("data loaded: {} ({}s)", data.n_rows, round(time.time() - t0, 2))
