@@ -60,6 +60,7 @@ SYMBOLS = [
     "dsgd_lg_topics_set", "dsgd_lg_topics_set_weights", "dsgd_lg_topics_get_weights", "dsgd_lg_topics_sync_step", "dsgd_lg_topics_sync_steps",
     "dsgd_lg_topics_loss_acc", "dsgd_lg_topics_predict", "dsgd_lg_topics_count", "dsgd_lg_topics_set_il",
     "dsgd_lg_topics_set_wide",
+    "dsgd_lg_topics_sync_step_ranges", "dsgd_lg_topics_sync_steps_ranges",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -185,6 +186,8 @@ def load():
         lib.dsgd_lg_topics_get_weights.argtypes = [C.c_void_p, C.c_void_p]
         lib.dsgd_lg_topics_sync_step.argtypes = lib.dsgd_lg_sync_step.argtypes     # (the single model's prototypes)
         lib.dsgd_lg_topics_sync_steps.argtypes = lib.dsgd_lg_sync_steps.argtypes
+        lib.dsgd_lg_topics_sync_step_ranges.argtypes = lib.dsgd_lg_sync_step_ranges.argtypes
+        lib.dsgd_lg_topics_sync_steps_ranges.argtypes = lib.dsgd_lg_sync_steps_ranges.argtypes
         lib.dsgd_lg_topics_loss_acc.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]   # (ctx, begin, end, loss*, acc*)
         lib.dsgd_lg_topics_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]               # (ctx, idx*, n, p_out*)
     if hasattr(lib, "dsgd_dense_plan_create"):   # (handles are 64-bit: without argtypes ctypes would pass them as C ints)

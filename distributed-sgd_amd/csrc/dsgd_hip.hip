@@ -140,6 +140,7 @@ static bool available() {
 #include "dsgd_fstep.hpp"
 #include "dsgd_tcol.hpp"
 #include "dsgd_lg_cols.hpp"   // (the logistic model's whole-split steps by column lists: coefficients, column-wise gradient)
+#include "dsgd_lg_topics_cols.hpp"   // (... for the topics, interleaved or wide: the lanes across the topics, the sums in registers)
 #include "dsgd_shuffle.hpp"
 #include "dsgd_cs64.hpp"   // (last: the fp64 mode)
 #include "dsgd_rp64.hpp"   // (... and its row-parallel gradient family, on float and on Double feature values)
@@ -600,6 +601,7 @@ struct dsgd_ctx {
   DevBuf<WorkSeg> d_lgt_ssegs;
   DevBuf<float> d_lgt_p;
   DevBuf<float> d_lgti_io;
+  DevBuf<double> d_lgt_cq;   // row ranges (csrc/dsgd_lg_topics_cols.hpp): the step's coefficients cq[position][TP], grown on demand
   unsigned long long bind_count = 0;
   unsigned long long lg_nsq_stamp = ~0ull - 1;
 };
@@ -3678,6 +3680,7 @@ int dsgd_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row_en
 #include "dsgd_lg_topics_il_calls.hpp"   // (... interleaved: dsgd_lg_topics_set_il and the interleaved side of every launch site)
 #include "dsgd_lg_topics_wide_calls.hpp"   // (... wide: dsgd_lg_topics_set_wide and the wide side of every launch site)
 #include "dsgd_lg_topics_calls.hpp"   // (... over several topics: dsgd_lg_topics_*)
+#include "dsgd_lg_topics_cols_calls.hpp"   // (... their whole-split steps over row ranges, by the single model's column lists)
 
 // ---- distributed evaluation (csrc/dsgd_predict.hpp; ref: core/Master.scala:61-98) ----
 // The checks of dsgd_predict_ranges / _f64 that need no device: nothing has changed when one of them fails.

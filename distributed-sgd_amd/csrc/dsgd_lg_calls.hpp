@@ -517,6 +517,7 @@ int dsgd_lg_sync_step_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_
 // ---- whole-split steps by column lists (csrc/dsgd_lg_cols.hpp; the sizes: csrc/dsgd_lg_cols_host.hpp) ----
 // The layout of these ranges (c->d_segs holds them; the stream may be busy): DSGD_OK with *out, or 1 = none to be had -- too
 // many entries or positions (remembered for the configuration), or no memory (this call only): the caller's row form.
+// (The topics' ranges calls, csrc/dsgd_lg_topics_cols_calls.hpp, take the same layouts from the same cache and have no row form.)
 static int lgc_layout(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int K, long long longest, dsgd_ctx::LgColsLayout** out) {
   std::vector<long long> key;
   long long n_ent = 0;

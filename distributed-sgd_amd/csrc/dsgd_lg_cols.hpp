@@ -26,6 +26,8 @@
 //   dsgd_lg_finish_kernel<LG_STEP>   as behind the row form: its code, grid and arguments.
 //
 // The sums are integers: the accumulators hold the bits the row form leaves, whatever the order.
+// The layout holds no label: the topics' whole-split steps (csrc/dsgd_lg_topics_cols.hpp) walk the same entries, shares and
+// slot_of_cid with kernels of their own, and derive their accumulator words from the slots.
 // Plain C++ and vector atomics only.
 #pragma once
 

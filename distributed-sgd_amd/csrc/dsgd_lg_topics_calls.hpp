@@ -14,6 +14,7 @@ static void lgt_drop(dsgd_ctx* c) {
   c->lgt_il = false;
   c->lgt_wide = false;
   c->d_lgti_io.reset();
+  c->d_lgt_cq.reset();
   c->d_lgt_planes.reset();
   c->d_lgt_w.reset();
   c->d_lgt_acc.reset();

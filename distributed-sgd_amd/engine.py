@@ -527,6 +527,38 @@ class Engine:
                                                   C.c_float(lr), C.byref(st)))
         return {"n_samples": st.n_samples, "n_active": st.n_active}
 
+    def lg_topics_sync_step_ranges(self, ranges, lr):
+        """lg_topics_sync_step over (begin, end) row ranges (dsgd_lg_topics_sync_step_ranges; interleaved or wide topics): the
+        bits of the step over the same rows as lists."""
+        k = len(ranges)
+        rb = (C.c_int64 * max(k, 1))(*[int(r[0]) for r in ranges])
+        re_ = (C.c_int64 * max(k, 1))(*[int(r[1]) for r in ranges])
+        st = BatchStats()
+        check(self._lib.dsgd_lg_topics_sync_step_ranges(self._ctx, rb, re_, C.c_int32(k), C.c_float(lr), C.byref(st)))
+        return {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def lg_topics_sync_steps_ranges(self, ranges, n_steps, lr):
+        """n_steps steps of EVERY topic over the SAME ranges in ONE call (dsgd_lg_topics_sync_steps_ranges; interleaved or wide
+        topics): the ranges' entries are laid out by column once per configuration -- lg_sync_steps_ranges' layout and cache --
+        then every step is three launches with no atomic per non-zero and no index array.  The weights get the bits of
+        lg_topics_sync_steps over the same rows as lists; the stats are the rows of one step."""
+        pairs = []
+        for r in ranges:
+            if len(r) != 2:
+                raise ValueError("a range is a (begin, end) pair, not %r" % (r,))
+            pairs.append((operator.index(r[0]), operator.index(r[1])))
+        if not pairs:
+            raise ValueError("no ranges")
+        n_steps = operator.index(n_steps)
+        if n_steps < 1:
+            raise ValueError("n_steps must be at least 1, not %d" % n_steps)
+        k = len(pairs)
+        rb = (C.c_int64 * k)(*[a for a, _ in pairs])
+        re_ = (C.c_int64 * k)(*[b for _, b in pairs])
+        st = BatchStats()
+        check(self._lib.dsgd_lg_topics_sync_steps_ranges(self._ctx, rb, re_, C.c_int32(k), C.c_int64(n_steps), C.c_float(lr), C.byref(st)))
+        return {"n_samples": st.n_samples, "n_active": st.n_active}
+
     def lg_topics_loss_acc(self, row_begin, row_end):
         """(loss float64 [T], acc float64 [T]) of rows [row_begin, row_end) in ONE launch (dsgd_lg_topics_loss_acc)."""
         t = self._lg_topics()

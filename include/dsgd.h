@@ -1134,9 +1134,30 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *                               dsgd_lg_topics_wide_finish_kernel), with the same refusals in the same order (T outside [0, 128]
  *                               DSGD_EINVAL).  Setting topics in any form replaces those of the others; the other setters keep
  *                               their limits of 8 and 32
+ *   ROW RANGES                  dsgd_lg_topics_sync_step_ranges / dsgd_lg_topics_sync_steps_ranges: dsgd_lg_sync_step_ranges' /
+ *                               dsgd_lg_sync_steps_ranges' arguments, for topics in the INTERLEAVED or the WIDE form
+ *                               (csrc/dsgd_lg_topics_cols.hpp).  The ranges' entries are laid out once per configuration by the
+ *                               single model's column lists (WHOLE-SPLIT STEPS BY COLUMN LISTS above: one layout and one cache,
+ *                               a configuration laid out by either model serves both); a step is THREE launches whatever T
+ *                               (dsgd_lg_topics_coef_kernel<GW>: 16, 32 or 64 lanes per row, two topics per lane, one 16-byte
+ *                               store of coefficients per lane; dsgd_lg_topics_cgrad_kernel<GW>: a lane keeps its two topics'
+ *                               column sums in registers between two column boundaries -- no atomic per non-zero, no index
+ *                               array; the form's own finish), all n_steps enqueued back to back with ONE synchronisation.
+ *                               THE CONTRACT: every topic's weights and |w_t|^2 words are the BITS of dsgd_lg_topics_sync_step(s)
+ *                               over the same rows given as lists -- and so of dsgd_lg_sync_steps_ranges on plane t;
+ *                               stats: n_samples = n_active = the rows of ONE step.  The one-step call is the other with
+ *                               n_steps = 1.  Refused, in this order, with nothing changed: what every topic call refuses first
+ *                               (above); a range that is empty, decreasing or outside the rows, as dsgd_lg_sync_step_ranges
+ *                               (DSGD_EINVAL / DSGD_ERANGE); n_steps < 1 DSGD_EINVAL; a new column ranking DSGD_ESTATE; topics
+ *                               in the planar form (dsgd_lg_topics_set) DSGD_ESTATE.  There is NO row-form fallback over ranges
+ *                               for the topics: ranges that cannot be laid out (2^31 entries, rows or worker x column keys, no
+ *                               entry at all, or a coefficient table rows x TP beyond 2^37 doubles) fail with
+ *                               DSGD_EUNSUPPORTED, a failed allocation with DSGD_ENOMEM, both before any weight moves --
+ *                               dsgd_lg_topics_sync_steps over lists serves any rows.  Behind a served call
+ *                               dsgd_grad_kernel_name says "dsgd_lg_topics_cgrad_kernel"
  *
- * LIMITS (out of scope, each refused or simply absent): several topics run per-call steps over lists only -- no plans, no
- * row ranges or column lists, no column slices, no ranks, no asynchronous iteration, one lambda and one lr for all topics,
+ * LIMITS (out of scope, each refused or simply absent): several topics run per-call steps over lists and, interleaved or wide,
+ * over row ranges (ROW RANGES above) only -- no plans, no row ranges or column lists in the planar form, no column slices, no ranks, no asynchronous iteration, one lambda and one lr for all topics,
  * no JNI; no JNI / Scala binding and nothing in include/dsgd.hpp; the host
  * mirrors are host.LogisticSync and host.LogisticAsync (Master.fit's and MasterAsync.fit's flow on one context, no
  * communicator -- host.LogisticSync(ranks=(world, rank)) additionally runs Master.fit across dsgd_comm_init_lg's ranks;
@@ -1212,6 +1233,10 @@ int dsgd_lg_topics_sync_step(dsgd_ctx* ctx, const int32_t* const* idx_per_worker
                              dsgd_batch_stats* stats);
 int dsgd_lg_topics_sync_steps(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const int64_t* offsets /* n_steps * n_workers + 1 */,
                               int64_t n_steps, int32_t n_workers, float lr, dsgd_batch_stats* stats);
+int dsgd_lg_topics_sync_step_ranges(dsgd_ctx* ctx, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, float lr,
+                                    dsgd_batch_stats* stats);
+int dsgd_lg_topics_sync_steps_ranges(dsgd_ctx* ctx, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, int64_t n_steps,
+                                     float lr, dsgd_batch_stats* stats);
 int dsgd_lg_topics_loss_acc(dsgd_ctx* ctx, int64_t row_begin, int64_t row_end, double* loss /* T */, double* acc /* T */);
 int dsgd_lg_topics_predict(dsgd_ctx* ctx, const int32_t* idx, int64_t n, float* p_out /* T x n, topic-major */);
 

@@ -19,7 +19,13 @@ after the other; the default --out becomes profiles/logistic_topics_il_probe.jso
 --wide: the wide form (Engine.lg_topics_set(planes, wide=True)) under the same protocol -- for T = 1, 8, 32 against the interleaved
 form on a second context, for T = 64, 103, 128 against ceil(T / 32) interleaved contexts (each with its own copy of the matrix)
 stepped one after the other, which is what serves that many topics without the wide form; --T picks the topic counts of one
-run; the default --out becomes profiles/logistic_topics_wide_probe.json."""
+run; the default --out becomes profiles/logistic_topics_wide_probe.json.
+
+--ranges: whole-split steps (Engine.lg_topics_sync_steps_ranges: the column lists with the lanes across the topics) -- K = 1 and
+K = 4 equal ranges over all rows, T = 8, 32 interleaved and T = 103, 128 wide (--T picks others), against what serves such a step
+without them: Engine.lg_topics_sync_steps over arange lists in the same form on a second context.  The same protocol; the
+defaults become 50 steps per call and 4 calls per window (a step is milliseconds); the layout of the ranges is built by the
+warm-up call and is not in any window; the default --out becomes profiles/logistic_topics_ranges_probe.json."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -27,25 +33,28 @@ import dsgd_amd
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--rows", type=int, default=23149)
-ap.add_argument("--steps", type=int, default=1000, help="steps per call")
-ap.add_argument("--calls", type=int, default=10, help="calls per timed window")
+ap.add_argument("--steps", type=int, help="steps per call (default 1000; --ranges: 50)")
+ap.add_argument("--calls", type=int, help="calls per timed window (default 10; --ranges: 4)")
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--lam", type=float, default=1e-5)
 ap.add_argument("--interleaved", action="store_true", help="time the interleaved form: against the planar form up to T = 8, against T single models at 16 and 32")
 ap.add_argument("--wide", action="store_true", help="time the wide form: against the interleaved form up to T = 32, against ceil(T / 32) interleaved contexts beyond")
-ap.add_argument("--T", help="--wide: comma-separated topic counts (default 1,8,32,64,103,128)")
+ap.add_argument("--ranges", action="store_true", help="time whole-split steps over row ranges against the same rows as arange lists in the same form")
+ap.add_argument("--T", help="--wide / --ranges: comma-separated topic counts (default 1,8,32,64,103,128 / 8,32,103,128)")
 ap.add_argument("--out")
 a = ap.parse_args()
+a.steps = a.steps or (50 if a.ranges else 1000)
+a.calls = a.calls or (4 if a.ranges else 10)
 a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "logistic_topics_wide_probe.json" if a.wide else "logistic_topics_il_probe.json" if a.interleaved else "logistic_topics_probe.json")
-if a.wide and a.interleaved:
-    sys.exit("logistic_topics_probe: --wide and --interleaved are two runs")
+                              "logistic_topics_ranges_probe.json" if a.ranges else "logistic_topics_wide_probe.json" if a.wide else "logistic_topics_il_probe.json" if a.interleaved else "logistic_topics_probe.json")
+if a.wide + a.interleaved + a.ranges > 1:
+    sys.exit("logistic_topics_probe: --wide, --interleaved and --ranges are separate runs")
 if dsgd_amd.device_count() < 1:
     sys.exit("logistic_topics_probe: no gfx950 device (nothing is measured without one)")
 
 data = dsgd_amd.synth.generate(a.rows, seed=0)
 rng = np.random.default_rng(1)
-planes = np.ascontiguousarray(np.vstack([data.label[None].astype(np.int8), rng.choice(np.array([-1, 1], np.int8), size=(127 if a.wide else 31 if a.interleaved else 7, data.n_rows))]))
+planes = np.ascontiguousarray(np.vstack([data.label[None].astype(np.int8), rng.choice(np.array([-1, 1], np.int8), size=(127 if a.wide or a.ranges else 31 if a.interleaved else 7, data.n_rows))]))
 LR = 2.0 ** -10
 wide_T = tuple(int(t) for t in (a.T or "1,8,32,64,103,128").split(","))
 
@@ -64,8 +73,48 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e6 / (a.steps * a.calls)
 
 
+def write(result):
+    line = json.dumps(result)
+    print(line)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+
+
 result = {"rows": data.n_rows, "steps_per_call": a.steps, "calls_per_window": a.calls, "repeats": a.repeats, "unit": "us per step, host wall time around synchronising calls",
           "shapes": []}
+if a.ranges:
+    with dsgd_amd.Engine(data.dim, a.lam) as eng, dsgd_amd.Engine(data.dim, a.lam) as other:
+        for e in (eng, other):
+            e.load_csr(data.row_ptr, data.col, data.val, data.label)
+        for k in (1, 4):
+            cuts = [data.n_rows * i // k for i in range(k + 1)]
+            ranges = list(zip(cuts[:-1], cuts[1:]))
+            flat = np.tile(np.arange(data.n_rows, dtype=np.int32), a.steps)
+            offs = np.concatenate([[0], np.cumsum([e - b for b, e in ranges] * a.steps)]).astype(np.int64)
+            for T in (int(t) for t in (a.T or "8,32,103,128").split(",")):
+                form = {"interleaved": True} if T <= 32 else {"wide": True}
+                for e in (eng, other):
+                    e.lg_topics_set(planes[:T], **form)               # (from zero weights on both sides)
+
+                def run_ranges():
+                    eng.lg_topics_sync_steps_ranges(ranges, a.steps, LR)
+
+                def run_lists():
+                    other.lg_topics_sync_steps(flat, offs, a.steps, k, LR)
+
+                run_ranges(), run_lists()                                 # warm-up of the timed shape (and the layout); then the bits
+                same = np.array_equal(eng.lg_topics_get_weights().view(np.uint32), other.lg_topics_get_weights().view(np.uint32))
+                tr, tl = [], []
+                for _ in range(a.repeats):                                # alternated
+                    tr.append(timed(run_ranges))
+                    tl.append(timed(run_lists))
+                result["shapes"].append({"workers": k, "rows_per_step": data.n_rows, "T": T, "bits_equal": bool(same), "form": next(iter(form)),
+                                         "kernel": eng.grad_kernel_name(), "shortest_window_s": min(tr + tl) * a.steps * a.calls * 1e-6,
+                                         "ranges_us": {"median": float(np.median(tr)), "min": min(tr), "max": max(tr)},
+                                         "lists_us": {"median": float(np.median(tl)), "min": min(tl), "max": max(tl)}})
+    write(result)
+    sys.exit(0)
 singles = []
 for t in range(0 if a.wide else 32 if a.interleaved else 8):
     e = dsgd_amd.Engine(data.dim, a.lam)
@@ -128,8 +177,4 @@ with dsgd_amd.Engine(data.dim, a.lam) as eng, dsgd_amd.Engine(data.dim, a.lam) a
                                      "singles_us": {"median": float(np.median(ts)), "min": min(ts), "max": max(ts)}})
 for e in singles + il_parts[1:]:
     e.close()
-line = json.dumps(result)
-print(line)
-os.makedirs(os.path.dirname(a.out), exist_ok=True)
-with open(a.out, "w") as f:
-    f.write(line + "\n")
+write(result)
