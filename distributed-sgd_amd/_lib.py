@@ -61,6 +61,8 @@ SYMBOLS = [
     "dsgd_lg_topics_loss_acc", "dsgd_lg_topics_predict", "dsgd_lg_topics_count", "dsgd_lg_topics_set_il",
     "dsgd_lg_topics_set_wide",
     "dsgd_lg_topics_sync_step_ranges", "dsgd_lg_topics_sync_steps_ranges",
+    "dsgd_lg_softmax_set", "dsgd_lg_softmax_count", "dsgd_lg_softmax_sync_step", "dsgd_lg_softmax_sync_steps",
+    "dsgd_lg_softmax_sync_steps_ranges", "dsgd_lg_softmax_loss_acc", "dsgd_lg_softmax_predict",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -190,6 +192,14 @@ def load():
         lib.dsgd_lg_topics_sync_steps_ranges.argtypes = lib.dsgd_lg_sync_steps_ranges.argtypes
         lib.dsgd_lg_topics_loss_acc.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]   # (ctx, begin, end, loss*, acc*)
         lib.dsgd_lg_topics_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]               # (ctx, idx*, n, p_out*)
+    if hasattr(lib, "dsgd_lg_softmax_set"):   # softmax over exclusive classes (include/dsgd.h "SOFTMAX")
+        lib.dsgd_lg_softmax_set.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]     # (ctx, C, cls*)
+        lib.dsgd_lg_softmax_count.argtypes = [C.c_void_p, C.c_void_p]              # (ctx, C_out*)
+        lib.dsgd_lg_softmax_sync_step.argtypes = lib.dsgd_lg_sync_step.argtypes    # (the single model's prototypes)
+        lib.dsgd_lg_softmax_sync_steps.argtypes = lib.dsgd_lg_sync_steps.argtypes
+        lib.dsgd_lg_softmax_sync_steps_ranges.argtypes = lib.dsgd_lg_sync_steps_ranges.argtypes
+        lib.dsgd_lg_softmax_loss_acc.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]   # (ctx, begin, end, loss*, acc*)
+        lib.dsgd_lg_softmax_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]   # (ctx, idx*, n, cls_out*, p_out*)
     if hasattr(lib, "dsgd_dense_plan_create"):   # (handles are 64-bit: without argtypes ctypes would pass them as C ints)
         lib.dsgd_dense_step_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float]
         lib.dsgd_dense_loss_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

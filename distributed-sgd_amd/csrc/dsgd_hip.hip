@@ -141,6 +141,7 @@ static bool available() {
 #include "dsgd_tcol.hpp"
 #include "dsgd_lg_cols.hpp"   // (the logistic model's whole-split steps by column lists: coefficients, column-wise gradient)
 #include "dsgd_lg_topics_cols.hpp"   // (... for the topics, interleaved or wide: the lanes across the topics, the sums in registers)
+#include "dsgd_lg_softmax.hpp"   // (softmax over exclusive classes on the wide layout: one reduction across the lane group)
 #include "dsgd_shuffle.hpp"
 #include "dsgd_cs64.hpp"   // (last: the fp64 mode)
 #include "dsgd_rp64.hpp"   // (... and its row-parallel gradient family, on float and on Double feature values)
@@ -602,6 +603,9 @@ struct dsgd_ctx {
   DevBuf<float> d_lgt_p;
   DevBuf<float> d_lgti_io;
   DevBuf<double> d_lgt_cq;   // row ranges (csrc/dsgd_lg_topics_cols.hpp): the step's coefficients cq[position][TP], grown on demand
+  bool lgt_softmax = false;   // the wide topics are the one-hot planes of lgt_T exclusive classes (dsgd_lg_softmax_set;
+                              // csrc/dsgd_lg_softmax.hpp): the dsgd_lg_softmax_* calls serve them; lgt_drop clears the mark
+  DevBuf<unsigned char> d_lgsm_cls;   // dsgd_lg_softmax_predict: the class bytes, grown on demand
   unsigned long long bind_count = 0;
   unsigned long long lg_nsq_stamp = ~0ull - 1;
 };
@@ -2347,6 +2351,9 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   DSGD_ATTR(dsgd_lg_topics_wide_eval_kernel<16>);
   DSGD_ATTR(dsgd_lg_topics_wide_eval_kernel<32>);
   DSGD_ATTR(dsgd_lg_topics_wide_eval_kernel<64>);
+  DSGD_ATTR(dsgd_lg_softmax_eval_kernel<16>);
+  DSGD_ATTR(dsgd_lg_softmax_eval_kernel<32>);
+  DSGD_ATTR(dsgd_lg_softmax_eval_kernel<64>);
   DSGD_ATTR(dsgd_colcount_kernel);
   DSGD_ATTR((dsgd_hogwild_kernel<false, false>));
   DSGD_ATTR((dsgd_hogwild_kernel<true, false>));
@@ -3681,6 +3688,7 @@ int dsgd_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row_en
 #include "dsgd_lg_topics_wide_calls.hpp"   // (... wide: dsgd_lg_topics_set_wide and the wide side of every launch site)
 #include "dsgd_lg_topics_calls.hpp"   // (... over several topics: dsgd_lg_topics_*)
 #include "dsgd_lg_topics_cols_calls.hpp"   // (... their whole-split steps over row ranges, by the single model's column lists)
+#include "dsgd_lg_softmax_calls.hpp"   // (softmax over the wide layout: dsgd_lg_softmax_*)
 
 // ---- distributed evaluation (csrc/dsgd_predict.hpp; ref: core/Master.scala:61-98) ----
 // The checks of dsgd_predict_ranges / _f64 that need no device: nothing has changed when one of them fails.

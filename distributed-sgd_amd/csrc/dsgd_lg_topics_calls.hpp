@@ -13,6 +13,8 @@ static void lgt_drop(dsgd_ctx* c) {
   c->lgt_k = 0;
   c->lgt_il = false;
   c->lgt_wide = false;
+  c->lgt_softmax = false;
+  c->d_lgsm_cls.reset();
   c->d_lgti_io.reset();
   c->d_lgt_cq.reset();
   c->d_lgt_planes.reset();

@@ -5,10 +5,9 @@
 // The layout of the entries is the single model's (lgc_layout and its cache, csrc/dsgd_lg_calls.hpp): a configuration laid out
 // for either serves both.  The coefficient table cq[position][TP] is the context's own (d_lgt_cq; lgt_drop drops it).
 
-// the THREE launches of one step over the ranges in c->d_segs, by their layout
-static int lgtc_launch(dsgd_ctx* c, int K, const dsgd_ctx::LgColsLayout& L, long long longest, float lr) {
-  const int tp = lgti_tp(c->lgt_T), gw = lgtw_group_width(tp);
-  const dim3 th(LG_THREADS);
+// what the coefficients of the ranges in c->d_segs are launched with (dsgd_lg_topics_coef_kernel and dsgd_lg_softmax_coef_kernel alike)
+static LgtcCoefArgs lgtc_coef_args(dsgd_ctx* c, int K, const dsgd_ctx::LgColsLayout& L, long long longest) {
+  const int tp = lgti_tp(c->lgt_T);
   LgtcCoefArgs q;
   q.wi = c->d_lgt_w;
   q.pi = c->d_lgt_planes;
@@ -18,14 +17,15 @@ static int lgtc_launch(dsgd_ctx* c, int K, const dsgd_ctx::LgColsLayout& L, long
   q.K = K;
   q.segs = c->d_segs;
   q.pos_base = L.d_pos_base;
-  q.blocks_per_worker = lgtw_blocks_per_worker(longest, K, c->n_cu, gw);
+  q.blocks_per_worker = lgtw_blocks_per_worker(longest, K, c->n_cu, lgtw_group_width(tp));
   q.cq = c->d_lgt_cq;
   q.sc = c->d_sc;
-  const dim3 cgrid((unsigned)(q.blocks_per_worker * K));
-  if (gw == 16) hipLaunchKernelGGL(dsgd_lg_topics_coef_kernel<16>, cgrid, th, 0, c->stream, view(c), q);
-  else if (gw == 32) hipLaunchKernelGGL(dsgd_lg_topics_coef_kernel<32>, cgrid, th, 0, c->stream, view(c), q);
-  else hipLaunchKernelGGL(dsgd_lg_topics_coef_kernel<64>, cgrid, th, 0, c->stream, view(c), q);
-  HIP_TRY(hipGetLastError());
+  return q;
+}
+// the column-wise gradient from the coefficient table and the form's finish: the step's second and third launch
+static int lgtc_launch_grad_finish(dsgd_ctx* c, int K, const dsgd_ctx::LgColsLayout& L, float lr) {
+  const int tp = lgti_tp(c->lgt_T), gw = lgtw_group_width(tp);
+  const dim3 th(LG_THREADS);
   LgtcGradArgs g;
   g.ent = L.d_ent;
   g.shares = L.d_shares;
@@ -55,15 +55,29 @@ static int lgtc_launch(dsgd_ctx* c, int K, const dsgd_ctx::LgColsLayout& L, long
   HIP_TRY(hipGetLastError());
   return DSGD_OK;
 }
+// the THREE launches of one step over the ranges in c->d_segs, by their layout
+static int lgtc_launch(dsgd_ctx* c, int K, const dsgd_ctx::LgColsLayout& L, long long longest, float lr) {
+  const LgtcCoefArgs q = lgtc_coef_args(c, K, L, longest);
+  const int gw = lgtw_group_width(q.tp);
+  const dim3 cgrid((unsigned)(q.blocks_per_worker * K)), th(LG_THREADS);
+  if (gw == 16) hipLaunchKernelGGL(dsgd_lg_topics_coef_kernel<16>, cgrid, th, 0, c->stream, view(c), q);
+  else if (gw == 32) hipLaunchKernelGGL(dsgd_lg_topics_coef_kernel<32>, cgrid, th, 0, c->stream, view(c), q);
+  else hipLaunchKernelGGL(dsgd_lg_topics_coef_kernel<64>, cgrid, th, 0, c->stream, view(c), q);
+  HIP_TRY(hipGetLastError());
+  return lgtc_launch_grad_finish(c, K, L, lr);
+}
 
 // both calls (the one-step call is n_steps = 1 of the other).  There is NO row-form fallback over ranges for the topics: where no
 // layout can be had the call fails, before any weight moves.
-static int lgtc_steps(dsgd_ctx* c, const char* what, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, int64_t n_steps, float lr,
-                      dsgd_batch_stats* stats) {
+// (shared with dsgd_lg_softmax_sync_steps_ranges: `enter` is what the call asks first, `launch` one step's three launches)
+typedef int (*LgtEnter)(dsgd_ctx*, const char*);
+typedef int (*LgtcLaunch)(dsgd_ctx*, int, const dsgd_ctx::LgColsLayout&, long long, float);
+static int lgtc_steps(dsgd_ctx* c, const char* what, LgtEnter enter, LgtcLaunch launch, const int64_t* row_begin, const int64_t* row_end,
+                      int32_t n_workers, int64_t n_steps, float lr, dsgd_batch_stats* stats) {
   DSGD_TRY(check_ctx(c));
   if (n_workers < 1 || !row_begin || !row_end) return fail(DSGD_EINVAL, "%s: Cannot sum an empty list of vectors (no workers)", what);
   std::lock_guard<std::mutex> lk(c->mu);
-  DSGD_TRY(lgt_enter(c, what));
+  DSGD_TRY(enter(c, what));
   const LgCheck v = lg_check_ranges(row_begin, row_end, n_workers, c->n_rows);
   DSGD_TRY(lg_report(c, what, v, n_workers));
   if (n_steps < 1) return fail(DSGD_EINVAL, "%s: %lld steps", what, (long long)n_steps);
@@ -99,17 +113,17 @@ static int lgtc_steps(dsgd_ctx* c, const char* what, const int64_t* row_begin, c
   if (lrc != DSGD_OK) return lrc;
   // three launches per step, back to back on the stream: no host synchronisation in between
   int rc = DSGD_OK;
-  for (int64_t t = 0; t < n_steps && rc == DSGD_OK; ++t) rc = lgtc_launch(c, K, *L, v.longest, lr);
+  for (int64_t t = 0; t < n_steps && rc == DSGD_OK; ++t) rc = launch(c, K, *L, v.longest, lr);
   rc = lgt_step_done(c, rc, stats, v.total);
   return rc;
 }
 
 int dsgd_lg_topics_sync_step_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, float lr,
                                     dsgd_batch_stats* stats) {
-  return lgtc_steps(c, "dsgd_lg_topics_sync_step_ranges", row_begin, row_end, n_workers, 1, lr, stats);
+  return lgtc_steps(c, "dsgd_lg_topics_sync_step_ranges", lgt_enter, lgtc_launch, row_begin, row_end, n_workers, 1, lr, stats);
 }
 
 int dsgd_lg_topics_sync_steps_ranges(dsgd_ctx* c, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, int64_t n_steps, float lr,
                                      dsgd_batch_stats* stats) {
-  return lgtc_steps(c, "dsgd_lg_topics_sync_steps_ranges", row_begin, row_end, n_workers, n_steps, lr, stats);
+  return lgtc_steps(c, "dsgd_lg_topics_sync_steps_ranges", lgt_enter, lgtc_launch, row_begin, row_end, n_workers, n_steps, lr, stats);
 }

@@ -6,6 +6,7 @@
 // context's blocks are the interleaved form's, shape for shape (c->lgt_il is set as well: packing, the sizes of the column sums
 // and the staging vector are shared); only the kernels differ.
 
+static int lgtw_install(dsgd_ctx* c, int32_t T, const int8_t* planes);
 int dsgd_lg_topics_set_wide(dsgd_ctx* c, int32_t T, const int8_t* planes) {
   DSGD_TRY(check_ctx(c));
   std::lock_guard<std::mutex> lk(c->mu);
@@ -28,6 +29,12 @@ int dsgd_lg_topics_set_wide(dsgd_ctx* c, int32_t T, const int8_t* planes) {
     case LGT_ENTRY:
       return fail(DSGD_EINVAL, "dsgd_lg_topics_set_wide: plane %d, row %lld = %d, expected +1/-1", v.topic, v.row, v.value);
   }
+  return lgtw_install(c, T, planes);
+}
+
+// the wide setter's body behind its checks (locked; planes: T x n_rows checked entries): dsgd_lg_topics_set_wide above and
+// dsgd_lg_softmax_set (csrc/dsgd_lg_softmax_calls.hpp), whose planes are one-hot
+static int lgtw_install(dsgd_ctx* c, int32_t T, const int8_t* planes) {
   DSGD_TRY(prepare_layout(c));
   // the new blocks first: an allocation failure leaves the context (and the topics it had, in any form) as it was
   const int tp = lgti_tp(T);
@@ -61,8 +68,8 @@ int dsgd_lg_topics_set_wide(dsgd_ctx* c, int32_t T, const int8_t* planes) {
   return DSGD_OK;
 }
 
-// The TWO launches of one step over K lists, whatever T (lgt_launch's wide side)
-static int lgtw_launch(dsgd_ctx* c, int K, long long longest, float lr, const int* idx, const WorkSeg* segs) {
+// what the gradient over K lists is launched with (dsgd_lg_topics_wide_grad_kernel and dsgd_lg_softmax_grad_kernel alike)
+static LgtiArgs lgtw_grad_args(dsgd_ctx* c, int K, long long longest, const int* idx, const WorkSeg* segs) {
   LgtiArgs a;
   a.wi = c->d_lgt_w;
   a.pi = c->d_lgt_planes;
@@ -74,25 +81,35 @@ static int lgtw_launch(dsgd_ctx* c, int K, long long longest, float lr, const in
   a.K = K;
   a.idx = idx;
   a.segs = segs;
-  const int gw = lgtw_group_width(a.tp);
-  a.blocks_per_worker = lgtw_blocks_per_worker(longest, K, c->n_cu, gw);
+  a.blocks_per_worker = lgtw_blocks_per_worker(longest, K, c->n_cu, lgtw_group_width(a.tp));
   a.acc = c->d_lgt_acc;
   a.acc_stride = lgti_acc_stride(c->dp, a.tp);
   a.sc = c->d_sc;
+  return a;
+}
+// the wide finish over K workers' sums (the lists' ranges or the row ranges as `segs`: it reads the lengths)
+static int lgtw_launch_finish(dsgd_ctx* c, int K, float lr, const WorkSeg* segs) {
+  LgtiFinishArgs f = lgti_finish_args(c);
+  f.acc = c->d_lgt_acc;
+  f.acc_stride = lgti_acc_stride(c->dp, f.tp);
+  f.segs = segs;
+  f.K = K;
+  f.lr = (double)lr;
+  hipLaunchKernelGGL(dsgd_lg_topics_wide_finish_kernel<true>, dim3((unsigned)lg_finish_blocks(c->dp)), dim3(LG_THREADS), 0, c->stream, f);
+  HIP_TRY(hipGetLastError());
+  return DSGD_OK;
+}
+
+// The TWO launches of one step over K lists, whatever T (lgt_launch's wide side)
+static int lgtw_launch(dsgd_ctx* c, int K, long long longest, float lr, const int* idx, const WorkSeg* segs) {
+  const LgtiArgs a = lgtw_grad_args(c, K, longest, idx, segs);
+  const int gw = lgtw_group_width(a.tp);
   const dim3 grid((unsigned)(a.blocks_per_worker * K)), th(LG_THREADS);
   if (gw == 16) hipLaunchKernelGGL(dsgd_lg_topics_wide_grad_kernel<16>, grid, th, 0, c->stream, view(c), a);
   else if (gw == 32) hipLaunchKernelGGL(dsgd_lg_topics_wide_grad_kernel<32>, grid, th, 0, c->stream, view(c), a);
   else hipLaunchKernelGGL(dsgd_lg_topics_wide_grad_kernel<64>, grid, th, 0, c->stream, view(c), a);
   HIP_TRY(hipGetLastError());
-  LgtiFinishArgs f = lgti_finish_args(c);
-  f.acc = c->d_lgt_acc;
-  f.acc_stride = a.acc_stride;
-  f.segs = segs;
-  f.K = K;
-  f.lr = (double)lr;
-  hipLaunchKernelGGL(dsgd_lg_topics_wide_finish_kernel<true>, dim3((unsigned)lg_finish_blocks(c->dp)), th, 0, c->stream, f);
-  HIP_TRY(hipGetLastError());
-  return DSGD_OK;
+  return lgtw_launch_finish(c, K, lr, segs);
 }
 
 // |w_t|^2 of weights the finish did not write: the finish's grid and tree

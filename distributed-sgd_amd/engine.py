@@ -574,6 +574,81 @@ class Engine:
         check(self._lib.dsgd_lg_topics_predict(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(p)))
         return p
 
+    # -- softmax over exclusive classes on the wide layout (include/dsgd.h "SOFTMAX") ----------------------------
+    lg_softmax_max = 128
+
+    def lg_softmax_set(self, classes, n_classes=None):
+        """One class per loaded row, each below n_classes (default: the largest + 1), 2 <= n_classes <= 128
+        (dsgd_lg_softmax_set): the classes' weights start at zero and cross through lg_topics_set_weights / _get_weights,
+        float32 [C, D + 1].  None drops the classes."""
+        if classes is None:
+            check(self._lib.dsgd_lg_softmax_set(self._ctx, C.c_int32(0), None))
+            return
+        classes = np.asarray(classes)
+        if classes.shape != (self.n_rows,):
+            raise ValueError("classes must be [%d], not %r" % (self.n_rows, classes.shape))
+        if classes.dtype != np.uint8 and not np.array_equal(classes, classes.astype(np.uint8)):
+            raise ValueError("classes must be integers in [0, 255]")
+        cls = np.ascontiguousarray(classes, dtype=np.uint8)
+        n = int(cls.max()) + 1 if n_classes is None else operator.index(n_classes)
+        check(self._lib.dsgd_lg_softmax_set(self._ctx, C.c_int32(n), ptr(cls)))
+
+    @property
+    def n_classes(self):
+        """the classes set now, as the library holds them (dsgd_lg_softmax_count); 0: none"""
+        t = C.c_int32(0)
+        check(self._lib.dsgd_lg_softmax_count(self._ctx, C.byref(t)))
+        return int(t.value)
+
+    def lg_softmax_sync_step(self, idx_per_worker, lr):
+        """One synchronous softmax step over the workers' lists in two launches (dsgd_lg_softmax_sync_step)."""
+        lists = [i32(a) for a in idx_per_worker]
+        k = len(lists)
+        ptrs = (C.c_void_p * max(k, 1))(*[ptr(a) for a in lists])
+        ns = (C.c_int64 * max(k, 1))(*[len(a) for a in lists])
+        st = BatchStats()
+        check(self._lib.dsgd_lg_softmax_sync_step(self._ctx, ptrs, ns, C.c_int32(k), C.c_float(lr), C.byref(st)))
+        return {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def lg_softmax_sync_steps(self, idx, offsets, n_steps, n_workers, lr):
+        """n_steps steps of lg_softmax_sync_step in ONE call (dsgd_lg_softmax_sync_steps; lg_sync_steps' flat form)."""
+        idx = i32(idx)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if n_steps >= 1 and n_workers >= 1 and len(offsets) != n_steps * n_workers + 1:
+            raise ValueError("offsets do not describe %d x %d lists" % (n_steps, n_workers))
+        st = BatchStats()
+        check(self._lib.dsgd_lg_softmax_sync_steps(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers),
+                                                   C.c_float(lr), C.byref(st)))
+        return {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def lg_softmax_sync_steps_ranges(self, ranges, n_steps, lr):
+        """n_steps softmax steps over the SAME (begin, end) row ranges in ONE call (dsgd_lg_softmax_sync_steps_ranges): the
+        topics' column lists and their cache, three launches per step; the bits of lg_softmax_sync_steps over the same rows
+        as lists.  The stats are the rows of one step."""
+        k = len(ranges)
+        rb = (C.c_int64 * max(k, 1))(*[operator.index(r[0]) for r in ranges])
+        re_ = (C.c_int64 * max(k, 1))(*[operator.index(r[1]) for r in ranges])
+        st = BatchStats()
+        check(self._lib.dsgd_lg_softmax_sync_steps_ranges(self._ctx, rb, re_, C.c_int32(k), C.c_int64(operator.index(n_steps)), C.c_float(lr),
+                                                          C.byref(st)))
+        return {"n_samples": st.n_samples, "n_active": st.n_active}
+
+    def lg_softmax_loss_acc(self, row_begin, row_end):
+        """(loss, acc) of rows [row_begin, row_end): lambda sum_c |w_c|^2 + mean_i (log S_i - (z_iy - m_i)), and the share of
+        rows whose predicted class -- the lowest class of the largest logit -- is theirs (dsgd_lg_softmax_loss_acc)."""
+        loss, acc = C.c_double(0), C.c_double(0)
+        check(self._lib.dsgd_lg_softmax_loss_acc(self._ctx, C.c_int64(row_begin), C.c_int64(row_end), C.byref(loss), C.byref(acc)))
+        return loss.value, acc.value
+
+    def lg_softmax_predict(self, idx, proba=False):
+        """The predicted class of every listed row, uint8 [n]; proba: also P(class c | x), float32 [C, n]
+        (dsgd_lg_softmax_predict)."""
+        idx = i32(idx)
+        cls = np.zeros(len(idx), dtype=np.uint8)
+        p = np.zeros((self.n_classes, len(idx)), dtype=np.float32) if proba else None
+        check(self._lib.dsgd_lg_softmax_predict(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(cls), ptr(p)))
+        return (cls, p) if proba else cls
+
     lg_max_ranges = 16   # ranges of one dsgd_lg_loss_acc_ranges call
 
     def lg_loss_acc_ranges(self, ranges, w=None):

@@ -1544,6 +1544,65 @@ class LogisticTopics:
         return done
 
 
+class LogisticSoftmax:
+    """Master.fit's flow (core/Master.scala:120-218) for ONE softmax model over the classes of one engine
+    (Engine.lg_softmax_set; include/dsgd.h "SOFTMAX"), on LogisticTopics' pattern: SplitStrategy.vanilla's splits, per epoch
+    epoch_lists from ONE JavaRandom, ONE Engine.lg_softmax_sync_steps (two launches per step whatever C), ONE
+    Engine.lg_softmax_loss_acc each over the train and the test rows.  The classes share one loss, so there is ONE stopping
+    rule, applied to the test losses, newest first, and ONE GradState whose `grad` holds the weights [C, D + 1].
+
+    data layout: rows [0, n_train) are the train set, [n_train, n_rows) the test set.  Limits: one engine, no plans, no
+    ranks, no column slices, one learning rate and one lambda for all classes."""
+
+    def __init__(self, backend, n_train: int, n_rows: int, node_count: int, rnd: Optional[JavaRandom] = None, log=None):
+        if not 0 < n_train < n_rows:
+            raise ValueError("LogisticSoftmax needs train rows [0, n_train) and test rows [n_train, n_rows)")
+        self.backend, self.n_train, self.n_rows, self.node_count = backend, n_train, n_rows, node_count
+        self.rnd = rnd or JavaRandom(0)
+        self.log = log or (lambda *a: None)
+        self.losses: List[float] = []        # newest first
+        self.accs: List[float] = []
+        self.test_losses: List[float] = []
+        self.test_accs: List[float] = []
+        self.steps_run = 0
+
+    def fit(self, initial_weights, max_epochs: int, batch_size: int, learning_rate: float,
+            stopping_criterion: Callable[[Sequence[float]], bool]) -> GradState:
+        split = split_vanilla(self.n_train, self.node_count)
+        max_samples = max(len(r) for r in split)
+        n_expected = len(range(0, max_samples, batch_size))
+        W0 = np.ascontiguousarray(initial_weights, dtype=np.float32)
+        if W0.ndim != 2 or W0.shape[0] != self.backend.n_classes:
+            raise ValueError("initial_weights must be [C, D + 1] for the %d classes set" % self.backend.n_classes)
+        self.backend.lg_topics_set_weights(W0)
+        self.losses, self.accs, self.test_losses, self.test_accs = [], [], [], []
+        start = time.time()
+        epoch = 0
+        while True:
+            if epoch >= max_epochs:
+                self.log("reached max number of epochs")
+                break
+            if stopping_criterion(self.test_losses):
+                self.log("converged to target after epoch %d" % epoch)
+                break
+            idx, offsets, n_steps = epoch_lists(self.rnd, split, max_samples, batch_size)
+            if n_steps:
+                self.backend.lg_softmax_sync_steps(idx, offsets, n_steps, len(split), learning_rate)
+            if n_steps < n_expected:
+                # the reference's next batch hands some slave an empty slice: Vec.sum throws there (math/Vec.scala:129)
+                raise ValueError("Cannot sum an empty list of vectors (batch %d of the epoch: a worker's slice is empty)" % n_steps)
+            l, a = self.backend.lg_softmax_loss_acc(0, self.n_train)
+            tl, ta = self.backend.lg_softmax_loss_acc(self.n_train, self.n_rows)
+            self.steps_run += n_steps
+            self.losses.insert(0, l)
+            self.accs.insert(0, a)
+            self.test_losses.insert(0, tl)
+            self.test_accs.insert(0, ta)
+            epoch += 1
+        W = self.backend.lg_topics_get_weights() if epoch else W0
+        return GradState(np.array(W, dtype=np.float32), None, start, epoch, None).finish(self.losses[0] if self.losses else None)
+
+
 # ---- MasterAsync.fit for the logistic model ---------------------------------------------------------------------------
 class LogisticAsync:
     """core/MasterAsync.scala:32-178 for the LOGISTIC model of one engine, on the ZERO-LAG schedule (include/dsgd.h "THE LOGISTIC

@@ -1156,6 +1156,38 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *                               dsgd_lg_topics_sync_steps over lists serves any rows.  Behind a served call
  *                               dsgd_grad_kernel_name says "dsgd_lg_topics_cgrad_kernel"
  *
+ * SOFTMAX (csrc/dsgd_lg_softmax.hpp; DESIGN.md 3.13 "Softmax over the wide layout").  Multinomial logistic regression over
+ * 2 <= C <= 128 mutually exclusive classes on the WIDE layout above: weights W[C][D + 1], per row z_c = x . w_c (the single
+ * model's fp32 dot, per class; a finite z is a precondition), m = max_c z_c, e_c = exp((double)z_c - (double)m), S = sum_c e_c
+ * (a lane's own two terms, then an xor butterfly over the row's lane group: a fixed order, the same bits in every lane),
+ * p_c = e_c / S; row loss l = log(S) - (z_y - m); predicted class the LOWEST c with z_c == m; gradient coefficient of class c
+ * p_c - [c == y] into the fixed-point column sums exactly as the one-vs-rest coefficient; regulariser (+ 2 lambda w on every
+ * column and class), worker mean, update and the one rounding to float: the wide finish, unchanged.  Reported loss
+ * lambda sum_c |w_c|^2 + mean_i l_i.  Padding classes C <= c < TP and idle lanes take no part in m, S or the arg-max.
+ *   dsgd_lg_softmax_set         one class byte per loaded row, each < C; the classes' weights start at zero.  The context then holds
+ *                               the WIDE topics of the one-hot planes (+1 at the row's class), MARKED as classes: weights cross
+ *                               through dsgd_lg_topics_set_weights / _get_weights (C x (D + 1), class-major), and every
+ *                               dsgd_lg_topics_* call keeps serving the context as one-vs-rest on those planes.  C = 0 drops the
+ *                               classes (the topics and the mark); any dsgd_lg_topics_set* call replaces them and clears the mark.
+ *                               Refused before anything changes: C = 1, C < 0, C > 128 or a byte >= C DSGD_ERANGE; a null pointer
+ *                               DSGD_EINVAL; no rows DSGD_ESTATE
+ *   dsgd_lg_softmax_count       C as it is now (0: no classes, or topics that are not classes)
+ *   dsgd_lg_softmax_sync_step / _sync_steps     dsgd_lg_topics_sync_step's / _sync_steps' arguments: TWO launches per step
+ *                               (dsgd_lg_softmax_grad_kernel<GW>, dsgd_lg_topics_wide_finish_kernel)
+ *   dsgd_lg_softmax_sync_steps_ranges           dsgd_lg_topics_sync_steps_ranges' arguments (one step: n_steps = 1): THREE launches
+ *                               per step (dsgd_lg_softmax_coef_kernel<GW>, then dsgd_lg_topics_cgrad_kernel<GW> and the wide finish
+ *                               as they are).  The weights are the BITS of dsgd_lg_softmax_sync_steps over the same rows as lists
+ *   dsgd_lg_softmax_loss_acc    the reported loss and the share of rows whose predicted class is theirs over [row_begin, row_end)
+ *                               (either pointer may be NULL, not both); fixed-order sums, integer tallies: the same call gives
+ *                               the same bits
+ *   dsgd_lg_softmax_predict     per listed position the predicted class byte and, where p_out is not NULL, (float)p_c into
+ *                               p_out[c * n + position]
+ *   refused                     before anything is enqueued, nothing written: a context whose topics are not marked as classes
+ *                               DSGD_ESTATE; ANY communicator attached, a running lock-free engine or an fp64 context
+ *                               DSGD_EUNSUPPORTED; lists, ranges and row ranges that cannot be laid out as the topic calls refuse them
+ *   out of scope                plans, ranks, column slices, the asynchronous iteration and JNI; a faster form for few classes
+ *                               (C <= 32 runs 16 lanes per row, the wide form's floor); per-class lambda or learning rate
+ *
  * LIMITS (out of scope, each refused or simply absent): several topics run per-call steps over lists and, interleaved or wide,
  * over row ranges (ROW RANGES above) only -- no plans, no row ranges or column lists in the planar form, no column slices, no ranks, no asynchronous iteration, one lambda and one lr for all topics,
  * no JNI; no JNI / Scala binding and nothing in include/dsgd.hpp; the host
@@ -1239,6 +1271,17 @@ int dsgd_lg_topics_sync_steps_ranges(dsgd_ctx* ctx, const int64_t* row_begin, co
                                      float lr, dsgd_batch_stats* stats);
 int dsgd_lg_topics_loss_acc(dsgd_ctx* ctx, int64_t row_begin, int64_t row_end, double* loss /* T */, double* acc /* T */);
 int dsgd_lg_topics_predict(dsgd_ctx* ctx, const int32_t* idx, int64_t n, float* p_out /* T x n, topic-major */);
+/* softmax over exclusive classes ("SOFTMAX" above) */
+int dsgd_lg_softmax_set(dsgd_ctx* ctx, int32_t C /* 0, or 2 .. 128 */, const uint8_t* cls /* n_rows, each < C */);
+int dsgd_lg_softmax_count(dsgd_ctx* ctx, int32_t* C_out /* the classes set now; 0: none */);
+int dsgd_lg_softmax_sync_step(dsgd_ctx* ctx, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers, float lr,
+                              dsgd_batch_stats* stats);
+int dsgd_lg_softmax_sync_steps(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const int64_t* offsets /* n_steps * n_workers + 1 */,
+                               int64_t n_steps, int32_t n_workers, float lr, dsgd_batch_stats* stats);
+int dsgd_lg_softmax_sync_steps_ranges(dsgd_ctx* ctx, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, int64_t n_steps,
+                                      float lr, dsgd_batch_stats* stats);
+int dsgd_lg_softmax_loss_acc(dsgd_ctx* ctx, int64_t row_begin, int64_t row_end, double* loss, double* acc);
+int dsgd_lg_softmax_predict(dsgd_ctx* ctx, const int32_t* idx, int64_t n, uint8_t* cls_out /* n */, float* p_out /* C x n, class-major, or NULL */);
 
 #ifdef __cplusplus
 }

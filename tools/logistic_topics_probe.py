@@ -25,7 +25,14 @@ run; the default --out becomes profiles/logistic_topics_wide_probe.json.
 K = 4 equal ranges over all rows, T = 8, 32 interleaved and T = 103, 128 wide (--T picks others), against what serves such a step
 without them: Engine.lg_topics_sync_steps over arange lists in the same form on a second context.  The same protocol; the
 defaults become 50 steps per call and 4 calls per window (a step is milliseconds); the layout of the ranges is built by the
-warm-up call and is not in any window; the default --out becomes profiles/logistic_topics_ranges_probe.json."""
+warm-up call and is not in any window; the default --out becomes profiles/logistic_topics_ranges_probe.json.
+
+--softmax: softmax regression over C exclusive classes (Engine.lg_softmax_sync_steps, Engine.lg_softmax_sync_steps_ranges) against
+the closest thing there is without it, the wide one-vs-rest step of T = C topics on a second context -- C = 8, 53, 103, 128
+(--T picks others) at 3 x 100 and 4 x 4,096 rows per list step and at all rows as ONE range per ranges step.  The same
+protocol (the sides alternated `repeats` times, the median and the spread); the two sides compute different models, so no
+bits are compared; the ranges windows run steps / 20 steps per call; the default --out becomes
+profiles/logistic_softmax_probe.json."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -40,21 +47,22 @@ ap.add_argument("--lam", type=float, default=1e-5)
 ap.add_argument("--interleaved", action="store_true", help="time the interleaved form: against the planar form up to T = 8, against T single models at 16 and 32")
 ap.add_argument("--wide", action="store_true", help="time the wide form: against the interleaved form up to T = 32, against ceil(T / 32) interleaved contexts beyond")
 ap.add_argument("--ranges", action="store_true", help="time whole-split steps over row ranges against the same rows as arange lists in the same form")
-ap.add_argument("--T", help="--wide / --ranges: comma-separated topic counts (default 1,8,32,64,103,128 / 8,32,103,128)")
+ap.add_argument("--softmax", action="store_true", help="time the softmax list and ranges steps against the wide one-vs-rest step of the same C")
+ap.add_argument("--T", help="--softmax: comma-separated class counts (default 8,53,103,128); --wide / --ranges: comma-separated topic counts (default 1,8,32,64,103,128 / 8,32,103,128)")
 ap.add_argument("--out")
 a = ap.parse_args()
 a.steps = a.steps or (50 if a.ranges else 1000)
 a.calls = a.calls or (4 if a.ranges else 10)
 a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "logistic_topics_ranges_probe.json" if a.ranges else "logistic_topics_wide_probe.json" if a.wide else "logistic_topics_il_probe.json" if a.interleaved else "logistic_topics_probe.json")
-if a.wide + a.interleaved + a.ranges > 1:
-    sys.exit("logistic_topics_probe: --wide, --interleaved and --ranges are separate runs")
+                              "logistic_softmax_probe.json" if a.softmax else "logistic_topics_ranges_probe.json" if a.ranges else "logistic_topics_wide_probe.json" if a.wide else "logistic_topics_il_probe.json" if a.interleaved else "logistic_topics_probe.json")
+if a.wide + a.interleaved + a.ranges + a.softmax > 1:
+    sys.exit("logistic_topics_probe: --wide, --interleaved, --ranges and --softmax are separate runs")
 if dsgd_amd.device_count() < 1:
     sys.exit("logistic_topics_probe: no gfx950 device (nothing is measured without one)")
 
 data = dsgd_amd.synth.generate(a.rows, seed=0)
 rng = np.random.default_rng(1)
-planes = np.ascontiguousarray(np.vstack([data.label[None].astype(np.int8), rng.choice(np.array([-1, 1], np.int8), size=(127 if a.wide or a.ranges else 31 if a.interleaved else 7, data.n_rows))]))
+planes = np.ascontiguousarray(np.vstack([data.label[None].astype(np.int8), rng.choice(np.array([-1, 1], np.int8), size=(127 if a.wide or a.ranges or a.softmax else 31 if a.interleaved else 7, data.n_rows))]))
 LR = 2.0 ** -10
 wide_T = tuple(int(t) for t in (a.T or "1,8,32,64,103,128").split(","))
 
@@ -83,6 +91,41 @@ def write(result):
 
 result = {"rows": data.n_rows, "steps_per_call": a.steps, "calls_per_window": a.calls, "repeats": a.repeats, "unit": "us per step, host wall time around synchronising calls",
           "shapes": []}
+if a.softmax:
+    with dsgd_amd.Engine(data.dim, a.lam) as eng, dsgd_amd.Engine(data.dim, a.lam) as other:
+        for e in (eng, other):
+            e.load_csr(data.row_ptr, data.col, data.val, data.label)
+        whole, r_steps = [(0, data.n_rows)], max(1, a.steps // 20)
+        for C in (int(t) for t in (a.T or "8,53,103,128").split(",")):
+            eng.lg_softmax_set(rng.integers(0, C, size=data.n_rows).astype(np.uint8), C)   # (from zero weights on both sides)
+            other.lg_topics_set(planes[:C], wide=True)
+            for k, batch in ((3, 100), (4, 4096), (1, data.n_rows)):
+                per_call = r_steps if batch == data.n_rows else a.steps
+                flat, offs = (None, None) if batch == data.n_rows else lists_for(k, batch)
+
+                def run_softmax():
+                    if flat is None:
+                        eng.lg_softmax_sync_steps_ranges(whole, per_call, LR)
+                    else:
+                        eng.lg_softmax_sync_steps(flat, offs, per_call, k, LR)
+
+                def run_wide():
+                    if flat is None:
+                        other.lg_topics_sync_steps_ranges(whole, per_call, LR)
+                    else:
+                        other.lg_topics_sync_steps(flat, offs, per_call, k, LR)
+
+                run_softmax(), run_wide()                                 # warm-up of the timed shape (and the ranges' layout)
+                tsm, tw = [], []
+                for _ in range(a.repeats):                                # alternated
+                    tsm.append(timed(run_softmax) * a.steps / per_call)
+                    tw.append(timed(run_wide) * a.steps / per_call)
+                result["shapes"].append({"workers": k, "batch": batch, "C": C, "form": "ranges" if flat is None else "lists", "steps_per_call": per_call,
+                                         "shortest_window_s": min(tsm + tw) * per_call * a.calls * 1e-6,
+                                         "softmax_us": {"median": float(np.median(tsm)), "min": min(tsm), "max": max(tsm)},
+                                         "wide_one_vs_rest_us": {"median": float(np.median(tw)), "min": min(tw), "max": max(tw)}})
+    write(result)
+    sys.exit(0)
 if a.ranges:
     with dsgd_amd.Engine(data.dim, a.lam) as eng, dsgd_amd.Engine(data.dim, a.lam) as other:
         for e in (eng, other):

@@ -28,6 +28,8 @@ best weights kept, maxSteps = train rows x max-epochs.  With --lg-slices a windo
 (include/dsgd.h "THE LOGISTIC MODEL", SEVERAL TOPICS) -- rcv1.load_topics' planes (+1 iff ANY qrels line tags the document),
 host.LogisticTopics: Master.fit's flow with the lists shared, one launch pair per step whatever the number of topics, the early
 stopping applied per topic.  With --synthetic plane 0 is the data's labels and the others are the signs of seeded planted directions.
+--model softmax --topics A,B,...: ONE softmax model over exclusive classes on the same rows (include/dsgd.h "SOFTMAX";
+host.LogisticSoftmax): class = the first listed topic a document carries, one more class for a document that carries none.
 --lg-topics-interleaved (with --topics): up to 32 names, the topics stored side by side (dsgd_lg_topics_set_il): the same bits.
 --lg-topics-wide (with --topics): up to 128 names, that layout with the lanes across the topics (dsgd_lg_topics_set_wide): the
 same bits.  --topics all: every topic code of the qrels file under data-path, sorted (RCV1-v2: 103) -- refused with the count
@@ -46,7 +48,8 @@ ap.add_argument("--device", type=int, default=0)
 ap.add_argument("--weights-out", help="write the `idx:value` line of Main.scala:114 here instead of logging it")
 ap.add_argument("--precision", choices=("fp32", "fp64"), default="fp32", help="fp64: the reference's Double arithmetic")
 ap.add_argument("--f64-rp-plans", action="store_true", help="fp64: refused plans run as row-parallel plans, under a communicator too: one plan run per epoch and rank (DSGD_F64_RP_PLANS=1)")
-ap.add_argument("--model", choices=("svm", "logistic"), default="svm", help="logistic: log-loss, probabilities, plain L2 (fp32; synchronous unless --lg-async)")
+ap.add_argument("--model", choices=("svm", "logistic", "softmax"), default="svm",
+                help="logistic: log-loss, probabilities, plain L2 (fp32; synchronous unless --lg-async); softmax: with --topics, exclusive classes")
 ap.add_argument("--lg-plans", action="store_true", help="logistic: Master.fit's flow on resident logistic plans (host.LogisticSync)")
 ap.add_argument("--lg-slices", action="store_true", help="logistic: --lg-plans on column slices, one persistent launch per epoch (host.LogisticSync(slices=True))")
 ap.add_argument("--lg-async", action="store_true", help="logistic: MasterAsync.fit's flow on the zero-lag schedule (host.LogisticAsync); honours --lg-slices")
@@ -57,9 +60,14 @@ a = ap.parse_args()
 topics =[t for t in (a.topics or "").split(",") if t]
 if a.lg_topics_wide and a.lg_topics_interleaved:
     ap.error("--lg-topics-interleaved and --lg-topics-wide are two forms: give one")
-if topics and (a.model != "logistic" or a.lg_plans or a.lg_slices or a.lg_async):
+softmax = a.model == "softmax"
+if softmax and (not topics or topics == ["all"] or a.lg_plans or a.lg_slices or a.lg_async or a.lg_topics_interleaved or a.lg_topics_wide):
+    ap.error("--model softmax takes --topics A,B,... alone: class = the first listed topic a document carries, one more for none")
+if softmax and len(topics) + 1 > dsgd_amd.Engine.lg_softmax_max:
+    ap.error("--model softmax: at most %d topics (one more class stands for none)" % (dsgd_amd.Engine.lg_softmax_max - 1))
+if topics and not softmax and (a.model != "logistic" or a.lg_plans or a.lg_slices or a.lg_async):
     ap.error("--topics goes with --model logistic alone (no plans, slices or asynchronous fit over several topics)")
-topics_max = (dsgd_amd.Engine.lg_topics_wide_max if a.lg_topics_wide else
+topics_max = (dsgd_amd.Engine.lg_softmax_max - 1 if softmax else dsgd_amd.Engine.lg_topics_wide_max if a.lg_topics_wide else
               dsgd_amd.Engine.lg_topics_il_max if a.lg_topics_interleaved else dsgd_amd.Engine.lg_topics_max)
 if len(topics) > topics_max:
     ap.error("--topics takes at most %d names (%d with --lg-topics-interleaved, %d with --lg-topics-wide)"
@@ -73,8 +81,8 @@ if a.lg_async and a.model != "logistic":
     ap.error("--lg-async goes with --model logistic")
 if a.lg_plans and a.model != "logistic":
     ap.error("--lg-plans goes with --model logistic")
-if a.model == "logistic" and a.precision != "fp32":
-    ap.error("--model logistic runs on the fp32 engine")
+if a.model != "svm" and a.precision != "fp32":
+    ap.error("--model %s runs on the fp32 engine" % a.model)
 if a.f64_rp_plans:
     os.environ["DSGD_F64_RP_PLANS"] = "1"   # (host.MasterSync / host.MasterAsync read it at every fit)
 rp_plans = a.precision == "fp64" and os.environ.get("DSGD_F64_RP_PLANS", host.F64_RP_PLANS_DEFAULT) == "1"
@@ -137,6 +145,26 @@ def fit_topics(eng, cfg, planes, names, n_train, n_rows):
         log("{}: {} epochs, train loss {}, final test loss {}, final test accuracy {}", name, states[t].updates, states[t].loss, lte[t], ate[t])
 
 
+def fit_softmax(eng, cfg, planes, names, n_train, n_rows):
+    """class = the first listed topic a document carries, len(names) for a document that carries none"""
+    tagged = planes > 0
+    cls = np.where(tagged.any(axis=0), tagged.argmax(axis=0), len(names)).astype(np.uint8)
+    eng.lg_softmax_set(cls, len(names) + 1)
+    master = host.LogisticSoftmax(eng, n_train, n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log)
+    for c, name in enumerate(list(names) + ["(none)"]):
+        log("{}: {} of {} rows", name, int((cls == c).sum()), n_rows)
+    l0, a0 = eng.lg_softmax_loss_acc(0, n_train)
+    log("initial loss: {}", l0)
+    log("initial accuracy: {}", a0)
+    t0 = time.time()
+    state = master.fit(np.zeros((len(names) + 1, eng.dp), dtype=np.float32), cfg.max_epochs, cfg.batch_size, cfg.learning_rate,
+                       host.EarlyStopping.no_improvement(cfg.patience, cfg.conv_delta, None))
+    log("fit ({}s, {} steps over {} classes, {} epochs, train loss {})", round(time.time() - t0, 3), master.steps_run, len(names) + 1, state.updates, state.loss)
+    lte, ate = eng.lg_softmax_loss_acc(n_train, n_rows)
+    log("final test loss: {}", lte)
+    log("final test accuracy: {}", ate)
+
+
 cfg = host.Config.load(open(a.conf).read() if a.conf else None)
 log("config: {}", cfg)
 log("loading data in: {}", "synthetic(%d)" % a.synthetic if a.synthetic else cfg.data_path)
@@ -168,8 +196,11 @@ with dsgd_amd.Engine(data.dim, cfg.lambda_, device=a.device, precision=a.precisi
     log("feature values: {} bits{}", eng.value_bits() if a.precision == "fp64" else 32,
         " (fp64 asynchronous fit: resident plans hold float values, NOT the Double feature values)"
         if a.precision == "fp64" and cfg.async_ and not rp_plans and getattr(data, "val64", None) is not None else "")
-    if a.model == "logistic":   # (its own loop; dimSparsity plays no part)
+    if a.model != "svm":   # (its own loop; dimSparsity plays no part)
         eng.set_weights(np.zeros(data.dim + 1, dtype=np.float32))
+        if softmax:
+            fit_softmax(eng, cfg, planes, topics, n_train, data.n_rows)
+            sys.exit(0)
         if topics:
             fit_topics(eng, cfg, planes, topics, n_train, data.n_rows)
             sys.exit(0)
