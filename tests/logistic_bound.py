@@ -210,25 +210,34 @@ def emu_gradient(csr, w32, idx, lam, mut=None, d=None):
     return g
 
 
-def emu_step(csr, w32, lists, lr, lam, mut=None, d=None):
+def emu_finish(csr, w32, accs, lr, lam, mut=None):
+    """The finish of a step over the workers' (int64 column sums, shift) pairs, in worker order: float32 [dp].  (The wide finish
+    runs the same expression per class: tests/softmax_bound.py calls this once per class.)"""
     _, _, val, _ = _csr(csr)
     w32 = np.asarray(w32, dtype=np.float32)
     wj = w32.astype(np.float64)
     reg = (2.0 * lam) * wj
     total = np.zeros_like(wj)
-    for k, idx in enumerate(lists):
-        wrong_n = len(lists[(k + 1) % len(lists)]) if mut == "wrong_worker_shift" else None
-        acc, S = emu_acc(csr, w32, idx, mut if mut in ACC_MUTATIONS else None, d=d)
-        if wrong_n is not None:
-            S = shift(wrong_n)   # (the finish reads another worker's length)
+    for acc, S in accs:
         Gk = acc.astype(np.float64) * 2.0 ** (_finish_vexp(val, mut) - S)
         if mut == "support_only_reg":
             total = total + (Gk + np.where(acc != 0, reg, 0.0))
         else:
             total = total + (Gk + reg)
-    mean = total if mut == "no_mean" else total / float(len(lists))
+    mean = total if mut == "no_mean" else total / float(len(accs))
     wn = (wj - float(np.float32(lr)) * mean).astype(np.float32)
     if mut == "skip_last_column":   # a step walks the columns in RANK order: the column of rank dp - 1 keeps its weight
         last = int(np.where(ranks_of(csr, len(w32)) == len(w32) - 1)[0][0])
         wn[last] = w32[last]
     return wn
+
+
+def emu_step(csr, w32, lists, lr, lam, mut=None, d=None):
+    w32 = np.asarray(w32, dtype=np.float32)
+    accs = []
+    for k, idx in enumerate(lists):
+        acc, S = emu_acc(csr, w32, idx, mut if mut in ACC_MUTATIONS else None, d=d)
+        if mut == "wrong_worker_shift":
+            S = shift(len(lists[(k + 1) % len(lists)]))   # (the finish reads another worker's length)
+        accs.append((acc, S))
+    return emu_finish(csr, w32, accs, lr, lam, mut)

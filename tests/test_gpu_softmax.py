@@ -1,5 +1,5 @@
 """Softmax regression on the GPU (csrc/dsgd_lg_softmax.hpp) against a plain fp64 softmax within tests/softmax_bound.py at every
-lane-group width, with padding classes, idle lanes (C = 33, 65) and the full 128; the forms in bits; the edges; the refusals."""
+lane-group width, with padding classes, idle lanes (C = 33, 65), full groups without a padding class (C = 4, 32, 64) and the full 128; the forms in bits; the edges; the refusals."""
 
 import numpy as np
 import pytest
@@ -13,7 +13,7 @@ from test_gpu_logistic_topics import bits, code_of, start_weights
 
 pytestmark = pytest.mark.gpu
 
-CS, LR, N_SMALL, RANGES = (2, 5, 33, 65, 103, 128), 0.5, 600, ((0, 600), (150, 250), (77, 78))
+CS, LR, N_SMALL, RANGES = (2, 3, 4, 5, 32, 33, 64, 65, 103, 128), 0.5, 600, ((0, 600), (150, 250), (77, 78))
 flat = lambda lists, n: (np.concatenate(lists * n), np.concatenate([[0], np.cumsum([len(a) for a in lists] * n)]))   # n steps' flat lists
 
 
