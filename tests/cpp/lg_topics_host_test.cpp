@@ -92,6 +92,7 @@ static void test_sizes() {
   }
   CHECK(lgt_eval_hw(1 << 20, LGT_LDS_FLOATS, 1) > 30000);       // one topic keeps nearly the whole tile
   CHECK(lgt_eval_hw(1 << 20, LGT_LDS_FLOATS, 8) >= 4096);       // eight share it
+  for (int T : {3, 8}) CHECK(lgt_eval_hw(600, 63, T) == 0 && lgt_eval_hw(600, 64, T) == 64 && lgt_eval_hw(600, 127, T) == 64 && lgt_eval_hw(600, 128, T) == 128);   // tests/topics_hard_cases.py: EVAL_TILES
 }
 
 static void test_fold_order() {

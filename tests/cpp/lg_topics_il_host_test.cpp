@@ -69,6 +69,8 @@ static void test_sizes() {
   // at T = 32 the per-group words take 40 KiB of the 160; what is left holds 958 ranks of 32 floats
   CHECK((lgti_eval_lds_floats(0, 32) - lgti_eval_sums_at(0, 32)) * 4 == 40 * 1024);
   CHECK(lgti_eval_hw(1 << 20, LGT_LDS_FLOATS, 32) == 896 && lgti_eval_hw(1 << 20, LGT_LDS_FLOATS, 1) > 8192);
+  CHECK(lgti_hot(lgti_tp(9)) == 170 && lgti_hot(lgti_tp(5)) == 256);   // tests/topics_hard_cases.py: N_HOT, and EVAL_TILES below
+  for (int T : {5, 9, 32}) CHECK(lgti_eval_hw(600, 63, T) == 0 && lgti_eval_hw(600, 64, T) == 64 && lgti_eval_hw(600, 127, T) == 64 && lgti_eval_hw(600, 128, T) == 128);
 }
 
 int main() {

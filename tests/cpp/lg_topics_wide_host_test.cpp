@@ -52,6 +52,8 @@ static void test_sizes() {
   CHECK(lgti_eval_lds_floats(0, 128) > LGT_LDS_FLOATS && lgtw_eval_lds_floats(0, 128) == 4 + 32 + 16384 + 384);
   CHECK(lgtw_eval_hw(1 << 20, LGT_LDS_FLOATS, 128) == 128 && lgtw_eval_hw(1 << 20, LGT_LDS_FLOATS, 103) == 256);
   CHECK(lgtw_eval_hw(1 << 20, LGT_LDS_FLOATS, 33) == 960 && lgtw_eval_hw(1 << 20, LGT_LDS_FLOATS, 1) > 8192);
+  CHECK(lgtw_hot(lgti_tp(33)) == 113 && lgtw_hot(lgti_tp(65)) == 60 && lgtw_hot(lgti_tp(103)) == 39 && lgtw_hot(lgti_tp(128)) == 32);   // tests/topics_hard_cases.py: N_HOT
+  for (int T : {33, 65, 103, 128}) CHECK(lgtw_eval_hw(600, 63, T) == 0 && lgtw_eval_hw(600, 64, T) == 64 && lgtw_eval_hw(600, 127, T) == 64 && lgtw_eval_hw(600, 128, T) == 128);
 }
 
 int main() {

@@ -165,9 +165,10 @@ def ranks_of(csr, dp):
 ACC_MUTATIONS = ("drop_last", "label_by_position", "flip_sign", "vexp_qscale", "fold_2048")
 
 
-def emu_acc(csr, w32, idx, mut=None, n_for_shift=None, d=None):
+def emu_acc(csr, w32, idx, mut=None, n_for_shift=None, d=None, n_hot=2048):
     """One worker's int64 column sums (python ints: exact) and its shift.  mut: a mutation's name (tests only).  d: the dots
-    of emu_dots for (at least) the listed rows, where the caller has them already."""
+    of emu_dots for (at least) the listed rows, where the caller has them already.  n_hot: the ranks of the LDS head that
+    fold_2048 folds at (2,048: the single model's; the topic forms' heads are smaller, tests/topics_hard_cases.py)."""
     row_ptr, col, val, label = _csr(csr)
     idx = np.asarray(idx, dtype=np.int64)
     S = shift(len(idx) if n_for_shift is None else n_for_shift)
@@ -178,9 +179,9 @@ def emu_acc(csr, w32, idx, mut=None, n_for_shift=None, d=None):
     if d is None:
         d = emu_dots(csr, w32, idx)
     at = col
-    if mut == "fold_2048" and len(w32) > 2048:   # the first rank beyond the LDS head lands on the head's last word
+    if mut == "fold_2048" and len(w32) > n_hot:   # the first rank beyond the LDS head lands on the head's last word
         rank = ranks_of(csr, len(w32))
-        at = np.where(rank[col] == 2048, int(np.where(rank == 2047)[0][0]), col)
+        at = np.where(rank[col] == n_hot, int(np.where(rank == n_hot - 1)[0][0]), col)
     acc = np.zeros(len(w32), dtype=np.int64)
     for t, r in enumerate(idx):
         y = float(label[t % len(label)] if mut == "label_by_position" else label[r])
