@@ -62,7 +62,7 @@ SYMBOLS = [
     "dsgd_lg_topics_set_wide",
     "dsgd_lg_topics_sync_step_ranges", "dsgd_lg_topics_sync_steps_ranges",
     "dsgd_lg_softmax_set", "dsgd_lg_softmax_count", "dsgd_lg_softmax_sync_step", "dsgd_lg_softmax_sync_steps",
-    "dsgd_lg_softmax_sync_steps_ranges", "dsgd_lg_softmax_loss_acc", "dsgd_lg_softmax_predict",
+    "dsgd_lg_softmax_sync_steps_ranges", "dsgd_lg_softmax_loss_acc", "dsgd_lg_softmax_predict", "dsgd_lg_softmax_set_il",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -195,6 +195,8 @@ def load():
     if hasattr(lib, "dsgd_lg_softmax_set"):   # softmax over exclusive classes (include/dsgd.h "SOFTMAX")
         lib.dsgd_lg_softmax_set.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]     # (ctx, C, cls*)
         lib.dsgd_lg_softmax_count.argtypes = [C.c_void_p, C.c_void_p]              # (ctx, C_out*)
+        if hasattr(lib, "dsgd_lg_softmax_set_il"):   # (few classes, the lanes across the non-zeros: "SOFTMAX, FEW CLASSES")
+            lib.dsgd_lg_softmax_set_il.argtypes = lib.dsgd_lg_softmax_set.argtypes
         lib.dsgd_lg_softmax_sync_step.argtypes = lib.dsgd_lg_sync_step.argtypes    # (the single model's prototypes)
         lib.dsgd_lg_softmax_sync_steps.argtypes = lib.dsgd_lg_sync_steps.argtypes
         lib.dsgd_lg_softmax_sync_steps_ranges.argtypes = lib.dsgd_lg_sync_steps_ranges.argtypes

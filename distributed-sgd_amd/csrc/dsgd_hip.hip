@@ -142,6 +142,7 @@ static bool available() {
 #include "dsgd_lg_cols.hpp"   // (the logistic model's whole-split steps by column lists: coefficients, column-wise gradient)
 #include "dsgd_lg_topics_cols.hpp"   // (... for the topics, interleaved or wide: the lanes across the topics, the sums in registers)
 #include "dsgd_lg_softmax.hpp"   // (softmax over exclusive classes on the wide layout: one reduction across the lane group)
+#include "dsgd_lg_softmax_il.hpp"   // (... over 2 to 32 classes with the lanes across the non-zeros: the wide form's bits)
 #include "dsgd_shuffle.hpp"
 #include "dsgd_cs64.hpp"   // (last: the fp64 mode)
 #include "dsgd_rp64.hpp"   // (... and its row-parallel gradient family, on float and on Double feature values)
@@ -2354,6 +2355,10 @@ int dsgd_create(const dsgd_config* cfg, dsgd_ctx** out) {
   DSGD_ATTR(dsgd_lg_softmax_eval_kernel<16>);
   DSGD_ATTR(dsgd_lg_softmax_eval_kernel<32>);
   DSGD_ATTR(dsgd_lg_softmax_eval_kernel<64>);
+  DSGD_ATTR(dsgd_lg_softmax_il_eval_kernel<1>);
+  DSGD_ATTR(dsgd_lg_softmax_il_eval_kernel<2>);
+  DSGD_ATTR(dsgd_lg_softmax_il_eval_kernel<4>);
+  DSGD_ATTR(dsgd_lg_softmax_il_eval_kernel<8>);
   DSGD_ATTR(dsgd_colcount_kernel);
   DSGD_ATTR((dsgd_hogwild_kernel<false, false>));
   DSGD_ATTR((dsgd_hogwild_kernel<true, false>));
@@ -3688,6 +3693,7 @@ int dsgd_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row_en
 #include "dsgd_lg_topics_wide_calls.hpp"   // (... wide: dsgd_lg_topics_set_wide and the wide side of every launch site)
 #include "dsgd_lg_topics_calls.hpp"   // (... over several topics: dsgd_lg_topics_*)
 #include "dsgd_lg_topics_cols_calls.hpp"   // (... their whole-split steps over row ranges, by the single model's column lists)
+#include "dsgd_lg_softmax_il_calls.hpp"   // (softmax over few classes: dsgd_lg_softmax_set_il and its side of every launch site below)
 #include "dsgd_lg_softmax_calls.hpp"   // (softmax over the wide layout: dsgd_lg_softmax_*)
 
 // ---- distributed evaluation (csrc/dsgd_predict.hpp; ref: core/Master.scala:61-98) ----

@@ -4,7 +4,8 @@
 // dsgd_lg_topics_cols_calls.hpp: the dsgd_lg_softmax_* entry points, one function per launch site; the steps run the topics' shared bodies.  The context's blocks are the
 // wide topics' (dsgd_lg_topics_set_wide's body lays them out from the one-hot planes), so dsgd_lg_topics_set_weights /
 // _get_weights carry the weights and every dsgd_lg_topics_* call keeps serving the context as one-vs-rest on those planes; only
-// the mark c->lgt_softmax and the launches below are this model's.
+// the mark c->lgt_softmax and the launches below are this model's.  Classes set by dsgd_lg_softmax_set_il (interleaved and not
+// wide: csrc/dsgd_lg_softmax_il_calls.hpp) are served by the same calls: each launch function below hands them to its lgsi_ side.
 //
 // Every check runs on the host before anything of the call is enqueued: a refused call leaves the classes, the weights and the
 // context's flags as they were.  Every call returns behind its kernels (ONE synchronisation).
@@ -59,6 +60,7 @@ int dsgd_lg_softmax_count(dsgd_ctx* c, int32_t* C_out) {
 
 // The TWO launches of one step over K lists, whatever C: the wide form's arguments and finish around the softmax gradient
 static int lgsm_launch(dsgd_ctx* c, int K, long long longest, float lr, const int* idx, const WorkSeg* segs) {
+  if (!c->lgt_wide) return lgsi_launch(c, K, longest, lr, idx, segs);   // (classes set by dsgd_lg_softmax_set_il)
   const LgtiArgs a = lgtw_grad_args(c, K, longest, idx, segs);
   const int gw = lgtw_group_width(a.tp);
   const dim3 grid((unsigned)(a.blocks_per_worker * K)), th(LG_THREADS);
@@ -73,6 +75,7 @@ static int lgsm_launch(dsgd_ctx* c, int K, long long longest, float lr, const in
 // the THREE launches of one step over the ranges in c->d_segs, by their layout: the softmax coefficients, then the topics'
 // column-wise gradient and the wide finish as they are
 static int lgsm_launch_ranges(dsgd_ctx* c, int K, const dsgd_ctx::LgColsLayout& L, long long longest, float lr) {
+  if (!c->lgt_wide) return lgsi_launch_ranges(c, K, L, longest, lr);
   const LgtcCoefArgs q = lgtc_coef_args(c, K, L, longest);
   const int gw = lgtw_group_width(q.tp);
   const dim3 cgrid((unsigned)(q.blocks_per_worker * K)), th(LG_THREADS);
@@ -150,6 +153,41 @@ int dsgd_lg_softmax_sync_steps_ranges(dsgd_ctx* c, const int64_t* row_begin, con
   return lgtc_steps(c, "dsgd_lg_softmax_sync_steps_ranges", lgsm_enter, lgsm_launch_ranges, row_begin, row_end, n_workers, n_steps, lr, stats);
 }
 
+// the evaluation of rows [row_begin, row_end) in `grid` workgroups with a tile of hw ranks, by the context's form: the loss words into `part`
+static int lgsm_launch_eval(dsgd_ctx* c, long long row_begin, long long row_end, long long grid, int hw, double* part) {
+  if (!c->lgt_wide) return lgsi_launch_eval(c, row_begin, row_end, grid, hw, part);
+  const int C = c->lgt_T;
+  const size_t lds = sizeof(float) * (size_t)lgsm_eval_lds_floats(hw, C);
+  const dim3 g((unsigned)grid), th(LGSM_EVAL_THREADS);
+  const int gw = lgtw_group_width(lgti_tp(C));
+#define LGSM_EVAL(GW)                                                                                                                         \
+  hipLaunchKernelGGL(dsgd_lg_softmax_eval_kernel<GW>, g, th, lds, c->stream, view(c), c->d_lgt_w.get(), c->d_lgt_planes.get(), C, row_begin, \
+                     row_end, c->d_lgt_tally.get(), hw, part)
+  if (gw == 16) LGSM_EVAL(16);
+  else if (gw == 32) LGSM_EVAL(32);
+  else LGSM_EVAL(64);
+#undef LGSM_EVAL
+  HIP_TRY(hipGetLastError());
+  return DSGD_OK;
+}
+
+// the classes (and, where dp_out is not null, the probabilities) of the n rows in c->d_idx, by the context's form
+static int lgsm_launch_predict(dsgd_ctx* c, long long n, float* dp_out) {
+  if (!c->lgt_wide) return lgsi_launch_predict(c, n, dp_out);
+  const int C = c->lgt_T;
+  const int gw = lgtw_group_width(lgti_tp(C));
+  const dim3 g((unsigned)grid_for(c, n, gw)), th(LG_THREADS);
+#define LGSM_PREDICT(GW)                                                                                                  \
+  hipLaunchKernelGGL(dsgd_lg_softmax_predict_kernel<GW>, g, th, 0, c->stream, view(c), c->d_lgt_w.get(), C, c->d_idx.get(), n, \
+                     c->d_lgsm_cls.get(), dp_out, c->d_sc.get())
+  if (gw == 16) LGSM_PREDICT(16);
+  else if (gw == 32) LGSM_PREDICT(32);
+  else LGSM_PREDICT(64);
+#undef LGSM_PREDICT
+  HIP_TRY(hipGetLastError());
+  return DSGD_OK;
+}
+
 int dsgd_lg_softmax_loss_acc(dsgd_ctx* c, int64_t row_begin, int64_t row_end, double* loss, double* acc) {
   DSGD_TRY(check_ctx(c));
   if (!loss && !acc) return fail(DSGD_EINVAL, "dsgd_lg_softmax_loss_acc: null loss and acc");
@@ -159,24 +197,14 @@ int dsgd_lg_softmax_loss_acc(dsgd_ctx* c, int64_t row_begin, int64_t row_end, do
   DSGD_TRY(lg_report(c, "dsgd_lg_softmax_loss_acc", v, 1));
   DSGD_TRY(lgt_ready(c, "dsgd_lg_softmax_loss_acc"));
   const int C = c->lgt_T;
-  if (c->lgt_nsq_stale) DSGD_TRY(lgtw_launch_nsq(c));   // |w_c|^2 of weights the finish did not write: the finish's grid and tree
+  if (c->lgt_nsq_stale) DSGD_TRY(c->lgt_wide ? lgtw_launch_nsq(c) : lgti_launch_nsq(c));   // |w_c|^2 of weights the finish did not write: the finish's grid and tree
   DSGD_TRY(reset_counters(c));
   HIP_TRY(hipMemsetAsync(c->d_lgt_tally, 0, sizeof(unsigned long long) * (size_t)C * LG_TALLY_WORDS, c->stream));
   const long long rows = row_end - row_begin;
   const long long grid = lgsm_eval_blocks(rows, c->n_cu);
   const int hw = lgsm_eval_hw(rows, std::min(c->hw_eval, c->dp), C);
-  const size_t lds = sizeof(float) * (size_t)lgsm_eval_lds_floats(hw, C);
   double* part = c->d_lgt_part + lgt_loss_at(C, 0, c->dp, c->n_cu);   // (the first class's n_cu loss words: grid <= n_cu)
-  const dim3 g((unsigned)grid), th(LGSM_EVAL_THREADS);
-  const int gw = lgtw_group_width(lgti_tp(C));
-#define LGSM_EVAL(GW)                                                                                                                         \
-  hipLaunchKernelGGL(dsgd_lg_softmax_eval_kernel<GW>, g, th, lds, c->stream, view(c), c->d_lgt_w.get(), c->d_lgt_planes.get(), C, (long long)row_begin, \
-                     (long long)row_end, c->d_lgt_tally.get(), hw, part)
-  if (gw == 16) LGSM_EVAL(16);
-  else if (gw == 32) LGSM_EVAL(32);
-  else LGSM_EVAL(64);
-#undef LGSM_EVAL
-  HIP_TRY(hipGetLastError());
+  DSGD_TRY(lgsm_launch_eval(c, row_begin, row_end, grid, hw, part));
   const size_t words = (size_t)lgt_part_words(C, c->dp, c->n_cu), tally_words = LG_TALLY_WORDS;
   DSGD_TRY(pin_acquire(c->pin_out, sizeof(double) * words + sizeof(unsigned long long) * tally_words));
   double* hpart = static_cast<double*>(c->pin_out.p.get());
@@ -209,17 +237,7 @@ int dsgd_lg_softmax_predict(dsgd_ctx* c, const int32_t* idx, int64_t n, uint8_t*
   DSGD_TRY(reset_counters(c));
   DSGD_TRY(send_idx(c, idx, n));
   DSGD_TRY(pin_acquire(c->pin_out, sizeof(float) * out + (size_t)n));
-  const int gw = lgtw_group_width(lgti_tp(C));
-  const dim3 g((unsigned)grid_for(c, n, gw)), th(LG_THREADS);
-  float* dp_out = p_out ? c->d_lgt_p.get() : nullptr;
-#define LGSM_PREDICT(GW)                                                                                                               \
-  hipLaunchKernelGGL(dsgd_lg_softmax_predict_kernel<GW>, g, th, 0, c->stream, view(c), c->d_lgt_w.get(), C, c->d_idx.get(), (long long)n, \
-                     c->d_lgsm_cls.get(), dp_out, c->d_sc.get())
-  if (gw == 16) LGSM_PREDICT(16);
-  else if (gw == 32) LGSM_PREDICT(32);
-  else LGSM_PREDICT(64);
-#undef LGSM_PREDICT
-  HIP_TRY(hipGetLastError());
+  DSGD_TRY(lgsm_launch_predict(c, n, p_out ? c->d_lgt_p.get() : nullptr));
   char* host = static_cast<char*>(c->pin_out.p.get());
   if (out) HIP_TRY(hipMemcpyAsync(host, c->d_lgt_p, sizeof(float) * out, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(host + sizeof(float) * out, c->d_lgsm_cls, (size_t)n, hipMemcpyDeviceToHost, c->stream));

@@ -5,6 +5,7 @@
 // topics are interleaved (c->lgt_il) -- one function per launch site.  The context's blocks are the planar form's under the
 // interleaved shapes: d_lgt_planes is Pi, d_lgt_w is Wi, d_lgt_acc is acc[k][rank][TP].
 
+static int lgti_install(dsgd_ctx* c, int32_t T, const int8_t* planes);
 int dsgd_lg_topics_set_il(dsgd_ctx* c, int32_t T, const int8_t* planes) {
   DSGD_TRY(check_ctx(c));
   std::lock_guard<std::mutex> lk(c->mu);
@@ -27,6 +28,12 @@ int dsgd_lg_topics_set_il(dsgd_ctx* c, int32_t T, const int8_t* planes) {
     case LGT_ENTRY:
       return fail(DSGD_EINVAL, "dsgd_lg_topics_set_il: plane %d, row %lld = %d, expected +1/-1", v.topic, v.row, v.value);
   }
+  return lgti_install(c, T, planes);
+}
+
+// the interleaved setter's body behind its checks (locked; planes: T x n_rows checked entries): dsgd_lg_topics_set_il above and
+// dsgd_lg_softmax_set_il (csrc/dsgd_lg_softmax_il_calls.hpp), whose planes are one-hot
+static int lgti_install(dsgd_ctx* c, int32_t T, const int8_t* planes) {
   DSGD_TRY(prepare_layout(c));
   // the new blocks first: an allocation failure leaves the context (and the topics it had, in either form) as it was
   const int tp = lgti_tp(T);
@@ -80,8 +87,8 @@ static LgtiFinishArgs lgti_finish_args(dsgd_ctx* c) {
   return f;
 }
 
-// The TWO launches of one step over K lists, whatever T (lgt_launch's interleaved side)
-static int lgti_launch(dsgd_ctx* c, int K, long long longest, float lr, const int* idx, const WorkSeg* segs) {
+// what the gradient over K lists is launched with (dsgd_lg_topics_il_grad_kernel and dsgd_lg_softmax_il_grad_kernel alike)
+static LgtiArgs lgti_grad_args(dsgd_ctx* c, int K, long long longest, const int* idx, const WorkSeg* segs) {
   LgtiArgs a;
   a.wi = c->d_lgt_w;
   a.pi = c->d_lgt_planes;
@@ -97,18 +104,27 @@ static int lgti_launch(dsgd_ctx* c, int K, long long longest, float lr, const in
   a.acc = c->d_lgt_acc;
   a.acc_stride = lgti_acc_stride(c->dp, a.tp);
   a.sc = c->d_sc;
-  const dim3 th(LG_THREADS);
-  hipLaunchKernelGGL(dsgd_lg_topics_il_grad_kernel<LGTI_TB>, dim3((unsigned)(a.blocks_per_worker * K)), th, 0, c->stream, view(c), a);
-  HIP_TRY(hipGetLastError());
+  return a;
+}
+// the interleaved finish over K workers' sums (`segs`: it reads the lengths)
+static int lgti_launch_finish(dsgd_ctx* c, int K, float lr, const WorkSeg* segs) {
   LgtiFinishArgs f = lgti_finish_args(c);
   f.acc = c->d_lgt_acc;
-  f.acc_stride = a.acc_stride;
+  f.acc_stride = lgti_acc_stride(c->dp, f.tp);
   f.segs = segs;
   f.K = K;
   f.lr = (double)lr;
-  hipLaunchKernelGGL(dsgd_lg_topics_il_finish_kernel<true>, dim3((unsigned)lg_finish_blocks(c->dp)), th, 0, c->stream, f);
+  hipLaunchKernelGGL(dsgd_lg_topics_il_finish_kernel<true>, dim3((unsigned)lg_finish_blocks(c->dp)), dim3(LG_THREADS), 0, c->stream, f);
   HIP_TRY(hipGetLastError());
   return DSGD_OK;
+}
+
+// The TWO launches of one step over K lists, whatever T (lgt_launch's interleaved side)
+static int lgti_launch(dsgd_ctx* c, int K, long long longest, float lr, const int* idx, const WorkSeg* segs) {
+  const LgtiArgs a = lgti_grad_args(c, K, longest, idx, segs);
+  hipLaunchKernelGGL(dsgd_lg_topics_il_grad_kernel<LGTI_TB>, dim3((unsigned)(a.blocks_per_worker * K)), dim3(LG_THREADS), 0, c->stream, view(c), a);
+  HIP_TRY(hipGetLastError());
+  return lgti_launch_finish(c, K, lr, segs);
 }
 
 // |w_t|^2 of weights the finish did not write: the finish's grid and tree

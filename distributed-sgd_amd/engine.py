@@ -577,12 +577,16 @@ class Engine:
     # -- softmax over exclusive classes on the wide layout (include/dsgd.h "SOFTMAX") ----------------------------
     lg_softmax_max = 128
 
-    def lg_softmax_set(self, classes, n_classes=None):
+    lg_softmax_il_max = 32
+
+    def lg_softmax_set(self, classes, n_classes=None, interleaved=False):
         """One class per loaded row, each below n_classes (default: the largest + 1), 2 <= n_classes <= 128
         (dsgd_lg_softmax_set): the classes' weights start at zero and cross through lg_topics_set_weights / _get_weights,
-        float32 [C, D + 1].  None drops the classes."""
+        float32 [C, D + 1].  None drops the classes.  interleaved: at most 32 classes, served with the lanes across the row's
+        non-zeros (dsgd_lg_softmax_set_il): every lg_softmax_* result carries the bits of the default form."""
+        setter = self._lib.dsgd_lg_softmax_set_il if interleaved else self._lib.dsgd_lg_softmax_set
         if classes is None:
-            check(self._lib.dsgd_lg_softmax_set(self._ctx, C.c_int32(0), None))
+            check(setter(self._ctx, C.c_int32(0), None))
             return
         classes = np.asarray(classes)
         if classes.shape != (self.n_rows,):
@@ -591,7 +595,7 @@ class Engine:
             raise ValueError("classes must be integers in [0, 255]")
         cls = np.ascontiguousarray(classes, dtype=np.uint8)
         n = int(cls.max()) + 1 if n_classes is None else operator.index(n_classes)
-        check(self._lib.dsgd_lg_softmax_set(self._ctx, C.c_int32(n), ptr(cls)))
+        check(setter(self._ctx, C.c_int32(n), ptr(cls)))
 
     @property
     def n_classes(self):

@@ -1546,7 +1546,7 @@ class LogisticTopics:
 
 class LogisticSoftmax:
     """Master.fit's flow (core/Master.scala:120-218) for ONE softmax model over the classes of one engine
-    (Engine.lg_softmax_set; include/dsgd.h "SOFTMAX"), on LogisticTopics' pattern: SplitStrategy.vanilla's splits, per epoch
+    (Engine.lg_softmax_set, in either form: interleaved=True gives the same bits; include/dsgd.h "SOFTMAX"), on LogisticTopics' pattern: SplitStrategy.vanilla's splits, per epoch
     epoch_lists from ONE JavaRandom, ONE Engine.lg_softmax_sync_steps (two launches per step whatever C), ONE
     Engine.lg_softmax_loss_acc each over the train and the test rows.  The classes share one loss, so there is ONE stopping
     rule, applied to the test losses, newest first, and ONE GradState whose `grad` holds the weights [C, D + 1].

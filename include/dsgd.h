@@ -1185,8 +1185,20 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *   refused                     before anything is enqueued, nothing written: a context whose topics are not marked as classes
  *                               DSGD_ESTATE; ANY communicator attached, a running lock-free engine or an fp64 context
  *                               DSGD_EUNSUPPORTED; lists, ranges and row ranges that cannot be laid out as the topic calls refuse them
- *   out of scope                plans, ranks, column slices, the asynchronous iteration and JNI; a faster form for few classes
- *                               (C <= 32 runs 16 lanes per row, the wide form's floor); per-class lambda or learning rate
+ *   out of scope                plans, ranks, column slices, the asynchronous iteration and JNI; per-class lambda or learning rate
+ *
+ * SOFTMAX, FEW CLASSES (csrc/dsgd_lg_softmax_il.hpp; DESIGN.md 3.13 "Softmax, few classes").  The same model over 2 <= C <= 32
+ * classes with the 16 lanes of a row ACROSS ITS NON-ZEROS, each lane carrying every class (the interleaved topics' split), opt-in.
+ *   dsgd_lg_softmax_set_il      dsgd_lg_softmax_set's arguments and refusals with 32 in 128's place.  The context then holds the
+ *                               INTERLEAVED topics of the one-hot planes, marked as classes: every dsgd_lg_softmax_* call above
+ *                               serves it through the kernels of this form (dsgd_lg_softmax_il_grad_kernel<NQ>, _coef_, _eval_,
+ *                               _predict_, NQ = 1, 2, 4, 8 quads of classes; the interleaved finish and
+ *                               dsgd_lg_topics_cgrad_kernel<16> as they are), and every dsgd_lg_topics_* call keeps serving it as
+ *                               interleaved one-vs-rest.  dsgd_lg_softmax_set keeps installing the wide form at every C
+ *   the contract                BIT EQUALITY with the wide form on the same rows, classes and weights: the weights after every
+ *                               step call, the |w_c|^2 words, the loss and accuracy, the class bytes and (float)p_c.  Each
+ *                               class's logit keeps the single model's summation tree, and from there on the arithmetic is the
+ *                               wide form's own (lgsm_row at "lane l holds classes 2l and 2l + 1"); column sums are integers
  *
  * LIMITS (out of scope, each refused or simply absent): several topics run per-call steps over lists and, interleaved or wide,
  * over row ranges (ROW RANGES above) only -- no plans, no row ranges or column lists in the planar form, no column slices, no ranks, no asynchronous iteration, one lambda and one lr for all topics,
@@ -1273,6 +1285,7 @@ int dsgd_lg_topics_loss_acc(dsgd_ctx* ctx, int64_t row_begin, int64_t row_end, d
 int dsgd_lg_topics_predict(dsgd_ctx* ctx, const int32_t* idx, int64_t n, float* p_out /* T x n, topic-major */);
 /* softmax over exclusive classes ("SOFTMAX" above) */
 int dsgd_lg_softmax_set(dsgd_ctx* ctx, int32_t C /* 0, or 2 .. 128 */, const uint8_t* cls /* n_rows, each < C */);
+int dsgd_lg_softmax_set_il(dsgd_ctx* ctx, int32_t C /* 0, or 2 .. 32 */, const uint8_t* cls /* n_rows, each < C */);
 int dsgd_lg_softmax_count(dsgd_ctx* ctx, int32_t* C_out /* the classes set now; 0: none */);
 int dsgd_lg_softmax_sync_step(dsgd_ctx* ctx, const int32_t* const* idx_per_worker, const int64_t* n_per_worker, int32_t n_workers, float lr,
                               dsgd_batch_stats* stats);

@@ -47,16 +47,18 @@ ap.add_argument("--lam", type=float, default=1e-5)
 ap.add_argument("--interleaved", action="store_true", help="time the interleaved form: against the planar form up to T = 8, against T single models at 16 and 32")
 ap.add_argument("--wide", action="store_true", help="time the wide form: against the interleaved form up to T = 32, against ceil(T / 32) interleaved contexts beyond")
 ap.add_argument("--ranges", action="store_true", help="time whole-split steps over row ranges against the same rows as arange lists in the same form")
-ap.add_argument("--softmax", action="store_true", help="time the softmax list and ranges steps against the wide one-vs-rest step of the same C")
+ap.add_argument("--softmax", action="store_true", help="time the softmax list and ranges steps against the wide one-vs-rest step of the same C; "
+                                                       "with --interleaved: softmax over 2 to 32 classes with the lanes across the non-zeros against the wide softmax")
 ap.add_argument("--T", help="--softmax: comma-separated class counts (default 8,53,103,128); --wide / --ranges: comma-separated topic counts (default 1,8,32,64,103,128 / 8,32,103,128)")
 ap.add_argument("--out")
 a = ap.parse_args()
 a.steps = a.steps or (50 if a.ranges else 1000)
 a.calls = a.calls or (4 if a.ranges else 10)
 a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "logistic_softmax_probe.json" if a.softmax else "logistic_topics_ranges_probe.json" if a.ranges else "logistic_topics_wide_probe.json" if a.wide else "logistic_topics_il_probe.json" if a.interleaved else "logistic_topics_probe.json")
-if a.wide + a.interleaved + a.ranges + a.softmax > 1:
-    sys.exit("logistic_topics_probe: --wide, --interleaved, --ranges and --softmax are separate runs")
+                              "logistic_softmax_il_probe.json" if a.softmax and a.interleaved else "logistic_softmax_probe.json" if a.softmax else "logistic_topics_ranges_probe.json" if a.ranges else "logistic_topics_wide_probe.json" if a.wide else "logistic_topics_il_probe.json" if a.interleaved else "logistic_topics_probe.json")
+softmax_il = a.softmax and a.interleaved   # softmax over few classes, the lanes across the non-zeros, against the wide softmax
+if a.wide + a.interleaved + a.ranges + a.softmax > 1 and not (softmax_il and not a.wide and not a.ranges):
+    sys.exit("logistic_topics_probe: --wide, --interleaved, --ranges and --softmax are separate runs (--softmax --interleaved is one)")
 if dsgd_amd.device_count() < 1:
     sys.exit("logistic_topics_probe: no gfx950 device (nothing is measured without one)")
 
@@ -91,6 +93,43 @@ def write(result):
 
 result = {"rows": data.n_rows, "steps_per_call": a.steps, "calls_per_window": a.calls, "repeats": a.repeats, "unit": "us per step, host wall time around synchronising calls",
           "shapes": []}
+if softmax_il:
+    # the new form on one context, the wide softmax on a second, the same classes; alternated windows, medians with min and max;
+    # after the warm-up of every shape the two contexts' weights are compared bit for bit
+    with dsgd_amd.Engine(data.dim, a.lam) as eng, dsgd_amd.Engine(data.dim, a.lam) as other:
+        for e in (eng, other):
+            e.load_csr(data.row_ptr, data.col, data.val, data.label)
+        whole, r_steps = [(0, data.n_rows)], max(1, a.steps // 20)
+        for C in (int(t) for t in (a.T or "2,5,8,16,32").split(",")):
+            cls = rng.integers(0, C, size=data.n_rows).astype(np.uint8)
+            eng.lg_softmax_set(cls, C, interleaved=True)
+            other.lg_softmax_set(cls, C)
+            for k, batch in ((3, 100), (4, 4096), (1, data.n_rows), (0, 0)):
+                per_call = a.steps if batch not in (0, data.n_rows) else r_steps
+                flat, offs = lists_for(k, batch) if batch not in (0, data.n_rows) else (None, None)
+
+                def run(e):
+                    if batch == 0:
+                        for _ in range(per_call):
+                            e.lg_softmax_loss_acc(0, data.n_rows)
+                    elif flat is None:
+                        e.lg_softmax_sync_steps_ranges(whole, per_call, LR)
+                    else:
+                        e.lg_softmax_sync_steps(flat, offs, per_call, k, LR)
+
+                run(eng), run(other)                                      # warm-up of the timed shape (and the ranges' layout)
+                same = bool(np.array_equal(eng.lg_topics_get_weights().view(np.uint32), other.lg_topics_get_weights().view(np.uint32)))
+                same = same and eng.lg_softmax_loss_acc(0, data.n_rows) == other.lg_softmax_loss_acc(0, data.n_rows)
+                til, tw = [], []
+                for _ in range(a.repeats):                                # alternated
+                    til.append(timed(lambda: run(eng)) * a.steps / per_call)
+                    tw.append(timed(lambda: run(other)) * a.steps / per_call)
+                result["shapes"].append({"workers": k, "batch": batch, "C": C, "form": "loss_acc" if batch == 0 else "ranges" if flat is None else "lists",
+                                         "steps_per_call": per_call, "shortest_window_s": min(til + tw) * per_call * a.calls * 1e-6, "same_bits": same,
+                                         "interleaved_us": {"median": float(np.median(til)), "min": min(til), "max": max(til)},
+                                         "wide_us": {"median": float(np.median(tw)), "min": min(tw), "max": max(tw)}})
+    write(result)
+    sys.exit(0)
 if a.softmax:
     with dsgd_amd.Engine(data.dim, a.lam) as eng, dsgd_amd.Engine(data.dim, a.lam) as other:
         for e in (eng, other):

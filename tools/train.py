@@ -56,18 +56,23 @@ ap.add_argument("--lg-async", action="store_true", help="logistic: MasterAsync.f
 ap.add_argument("--topics", help="logistic: comma-separated topic names, one-vs-rest in one launch pair per step (host.LogisticTopics)")
 ap.add_argument("--lg-topics-interleaved", action="store_true", help="--topics: the interleaved form, up to 32 names (Engine.lg_topics_set(interleaved=True))")
 ap.add_argument("--lg-topics-wide", action="store_true", help="--topics: the wide form, up to 128 names (Engine.lg_topics_set(wide=True))")
+ap.add_argument("--softmax-interleaved", action="store_true",
+                help="--model softmax: at most 32 classes with the lanes across the non-zeros, the same bits (Engine.lg_softmax_set(interleaved=True))")
 a = ap.parse_args()
 topics =[t for t in (a.topics or "").split(",") if t]
 if a.lg_topics_wide and a.lg_topics_interleaved:
     ap.error("--lg-topics-interleaved and --lg-topics-wide are two forms: give one")
 softmax = a.model == "softmax"
+if a.softmax_interleaved and not softmax:
+    ap.error("--softmax-interleaved goes with --model softmax")
 if softmax and (not topics or topics == ["all"] or a.lg_plans or a.lg_slices or a.lg_async or a.lg_topics_interleaved or a.lg_topics_wide):
     ap.error("--model softmax takes --topics A,B,... alone: class = the first listed topic a document carries, one more for none")
-if softmax and len(topics) + 1 > dsgd_amd.Engine.lg_softmax_max:
-    ap.error("--model softmax: at most %d topics (one more class stands for none)" % (dsgd_amd.Engine.lg_softmax_max - 1))
+softmax_max = dsgd_amd.Engine.lg_softmax_il_max if a.softmax_interleaved else dsgd_amd.Engine.lg_softmax_max
+if softmax and len(topics) + 1 > softmax_max:
+    ap.error("--model softmax: at most %d topics (one more class stands for none)" % (softmax_max - 1))
 if topics and not softmax and (a.model != "logistic" or a.lg_plans or a.lg_slices or a.lg_async):
     ap.error("--topics goes with --model logistic alone (no plans, slices or asynchronous fit over several topics)")
-topics_max = (dsgd_amd.Engine.lg_softmax_max - 1 if softmax else dsgd_amd.Engine.lg_topics_wide_max if a.lg_topics_wide else
+topics_max = (softmax_max - 1 if softmax else dsgd_amd.Engine.lg_topics_wide_max if a.lg_topics_wide else
               dsgd_amd.Engine.lg_topics_il_max if a.lg_topics_interleaved else dsgd_amd.Engine.lg_topics_max)
 if len(topics) > topics_max:
     ap.error("--topics takes at most %d names (%d with --lg-topics-interleaved, %d with --lg-topics-wide)"
@@ -149,7 +154,7 @@ def fit_softmax(eng, cfg, planes, names, n_train, n_rows):
     """class = the first listed topic a document carries, len(names) for a document that carries none"""
     tagged = planes > 0
     cls = np.where(tagged.any(axis=0), tagged.argmax(axis=0), len(names)).astype(np.uint8)
-    eng.lg_softmax_set(cls, len(names) + 1)
+    eng.lg_softmax_set(cls, len(names) + 1, interleaved=a.softmax_interleaved)
     master = host.LogisticSoftmax(eng, n_train, n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log)
     for c, name in enumerate(list(names) + ["(none)"]):
         log("{}: {} of {} rows", name, int((cls == c).sum()), n_rows)
