@@ -63,6 +63,7 @@ SYMBOLS = [
     "dsgd_lg_topics_sync_step_ranges", "dsgd_lg_topics_sync_steps_ranges",
     "dsgd_lg_softmax_set", "dsgd_lg_softmax_count", "dsgd_lg_softmax_sync_step", "dsgd_lg_softmax_sync_steps",
     "dsgd_lg_softmax_sync_steps_ranges", "dsgd_lg_softmax_loss_acc", "dsgd_lg_softmax_predict", "dsgd_lg_softmax_set_il",
+    "dsgd_lg_topics_sync_steps_cols", "dsgd_lg_softmax_sync_steps_cols",
 ]
 
 F_FP64 = 0x1  # dsgd_config.flags: the fp64 mode (include/dsgd.h "THE FP64 MODE")
@@ -202,6 +203,9 @@ def load():
         lib.dsgd_lg_softmax_sync_steps_ranges.argtypes = lib.dsgd_lg_sync_steps_ranges.argtypes
         lib.dsgd_lg_softmax_loss_acc.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]   # (ctx, begin, end, loss*, acc*)
         lib.dsgd_lg_softmax_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]   # (ctx, idx*, n, cls_out*, p_out*)
+    if hasattr(lib, "dsgd_lg_topics_sync_steps_cols"):   # the list steps by column lists (include/dsgd.h "INDEX LISTS BY COLUMN LISTS")
+        lib.dsgd_lg_topics_sync_steps_cols.argtypes = lib.dsgd_lg_sync_steps.argtypes
+        lib.dsgd_lg_softmax_sync_steps_cols.argtypes = lib.dsgd_lg_sync_steps.argtypes
     if hasattr(lib, "dsgd_dense_plan_create"):   # (handles are 64-bit: without argtypes ctypes would pass them as C ints)
         lib.dsgd_dense_step_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float]
         lib.dsgd_dense_loss_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

@@ -143,6 +143,7 @@ static bool available() {
 #include "dsgd_lg_topics_cols.hpp"   // (... for the topics, interleaved or wide: the lanes across the topics, the sums in registers)
 #include "dsgd_lg_softmax.hpp"   // (softmax over exclusive classes on the wide layout: one reduction across the lane group)
 #include "dsgd_lg_softmax_il.hpp"   // (... over 2 to 32 classes with the lanes across the non-zeros: the wide form's bits)
+#include "dsgd_lg_lists_cols.hpp"   // (the topics' and softmax's steps over index lists by the whole matrix's column lists: owner words)
 #include "dsgd_shuffle.hpp"
 #include "dsgd_cs64.hpp"   // (last: the fp64 mode)
 #include "dsgd_rp64.hpp"   // (... and its row-parallel gradient family, on float and on Double feature values)
@@ -604,6 +605,7 @@ struct dsgd_ctx {
   DevBuf<float> d_lgt_p;
   DevBuf<float> d_lgti_io;
   DevBuf<double> d_lgt_cq;   // row ranges (csrc/dsgd_lg_topics_cols.hpp): the step's coefficients cq[position][TP], grown on demand
+  DevBuf<unsigned int> d_lgl_owner;   // lists by column lists (csrc/dsgd_lg_lists_cols.hpp): [n_rows] owner words, LGL_NONE between steps
   bool lgt_softmax = false;   // the wide topics are the one-hot planes of lgt_T exclusive classes (dsgd_lg_softmax_set;
                               // csrc/dsgd_lg_softmax.hpp): the dsgd_lg_softmax_* calls serve them; lgt_drop clears the mark
   DevBuf<unsigned char> d_lgsm_cls;   // dsgd_lg_softmax_predict: the class bytes, grown on demand
@@ -3695,6 +3697,7 @@ int dsgd_loss_acc(dsgd_ctx* c, const float* w, int64_t row_begin, int64_t row_en
 #include "dsgd_lg_topics_cols_calls.hpp"   // (... their whole-split steps over row ranges, by the single model's column lists)
 #include "dsgd_lg_softmax_il_calls.hpp"   // (softmax over few classes: dsgd_lg_softmax_set_il and its side of every launch site below)
 #include "dsgd_lg_softmax_calls.hpp"   // (softmax over the wide layout: dsgd_lg_softmax_*)
+#include "dsgd_lg_lists_cols_calls.hpp"   // (... and both models' list steps by column lists: dsgd_lg_*_sync_steps_cols)
 
 // ---- distributed evaluation (csrc/dsgd_predict.hpp; ref: core/Master.scala:61-98) ----
 // The checks of dsgd_predict_ranges / _f64 that need no device: nothing has changed when one of them fails.

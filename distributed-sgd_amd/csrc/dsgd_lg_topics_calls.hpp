@@ -17,6 +17,7 @@ static void lgt_drop(dsgd_ctx* c) {
   c->d_lgsm_cls.reset();
   c->d_lgti_io.reset();
   c->d_lgt_cq.reset();
+  c->d_lgl_owner.reset();
   c->d_lgt_planes.reset();
   c->d_lgt_w.reset();
   c->d_lgt_acc.reset();

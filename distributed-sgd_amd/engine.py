@@ -516,15 +516,18 @@ class Engine:
         check(self._lib.dsgd_lg_topics_sync_step(self._ctx, ptrs, ns, C.c_int32(k), C.c_float(lr), C.byref(st)))
         return {"n_samples": st.n_samples, "n_active": st.n_active}
 
-    def lg_topics_sync_steps(self, idx, offsets, n_steps, n_workers, lr):
-        """n_steps steps of lg_topics_sync_step in ONE call (dsgd_lg_topics_sync_steps; lg_sync_steps' flat form)."""
+    def lg_topics_sync_steps(self, idx, offsets, n_steps, n_workers, lr, by_columns=False):
+        """n_steps steps of lg_topics_sync_step in ONE call (dsgd_lg_topics_sync_steps; lg_sync_steps' flat form).
+        by_columns: through the whole matrix's column lists and one owner word per row (dsgd_lg_topics_sync_steps_cols;
+        interleaved or wide topics): the same bits; a step that names a row twice runs through the list launches inside the
+        call (grad_kernel_name() says what the last step took)."""
         idx = i32(idx)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         if n_steps >= 1 and n_workers >= 1 and len(offsets) != n_steps * n_workers + 1:
             raise ValueError("offsets do not describe %d x %d lists" % (n_steps, n_workers))
         st = BatchStats()
-        check(self._lib.dsgd_lg_topics_sync_steps(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers),
-                                                  C.c_float(lr), C.byref(st)))
+        call = self._lib.dsgd_lg_topics_sync_steps_cols if by_columns else self._lib.dsgd_lg_topics_sync_steps
+        check(call(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers), C.c_float(lr), C.byref(st)))
         return {"n_samples": st.n_samples, "n_active": st.n_active}
 
     def lg_topics_sync_step_ranges(self, ranges, lr):
@@ -614,15 +617,16 @@ class Engine:
         check(self._lib.dsgd_lg_softmax_sync_step(self._ctx, ptrs, ns, C.c_int32(k), C.c_float(lr), C.byref(st)))
         return {"n_samples": st.n_samples, "n_active": st.n_active}
 
-    def lg_softmax_sync_steps(self, idx, offsets, n_steps, n_workers, lr):
-        """n_steps steps of lg_softmax_sync_step in ONE call (dsgd_lg_softmax_sync_steps; lg_sync_steps' flat form)."""
+    def lg_softmax_sync_steps(self, idx, offsets, n_steps, n_workers, lr, by_columns=False):
+        """n_steps steps of lg_softmax_sync_step in ONE call (dsgd_lg_softmax_sync_steps; lg_sync_steps' flat form).
+        by_columns: through the whole matrix's column lists (dsgd_lg_softmax_sync_steps_cols), as lg_topics_sync_steps'."""
         idx = i32(idx)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         if n_steps >= 1 and n_workers >= 1 and len(offsets) != n_steps * n_workers + 1:
             raise ValueError("offsets do not describe %d x %d lists" % (n_steps, n_workers))
         st = BatchStats()
-        check(self._lib.dsgd_lg_softmax_sync_steps(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers),
-                                                   C.c_float(lr), C.byref(st)))
+        call = self._lib.dsgd_lg_softmax_sync_steps_cols if by_columns else self._lib.dsgd_lg_softmax_sync_steps
+        check(call(self._ctx, ptr(idx), C.c_int64(len(idx)), ptr(offsets), C.c_int64(n_steps), C.c_int32(n_workers), C.c_float(lr), C.byref(st)))
         return {"n_samples": st.n_samples, "n_active": st.n_active}
 
     def lg_softmax_sync_steps_ranges(self, ranges, n_steps, lr):

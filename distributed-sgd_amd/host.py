@@ -1473,12 +1473,16 @@ class LogisticTopics:
     data layout: rows [0, n_train) are the train set, [n_train, n_rows) the test set.  Limits: one engine, no plans, no
     ranks, no column slices, one learning rate and one lambda for all topics.  interleaved: the engine's topics were set
     with Engine.lg_topics_set(planes, interleaved=True) -- up to 32 of them; wide: with Engine.lg_topics_set(planes, wide=True)
-    -- up to 128; without either more than 8 are refused."""
+    -- up to 128; without either more than 8 are refused.  by_columns: the steps go through the whole matrix's column lists
+    (Engine.lg_topics_sync_steps(..., by_columns=True); interleaved or wide topics): the same bits."""
 
     def __init__(self, backend, n_train: int, n_rows: int, node_count: int, rnd: Optional[JavaRandom] = None, log=None,
-                 interleaved: bool = False, wide: bool = False):
+                 interleaved: bool = False, wide: bool = False, by_columns: bool = False):
         if interleaved and wide:
             raise ValueError("interleaved and wide are two forms: choose one")
+        if by_columns and not (interleaved or wide):
+            raise ValueError("by_columns serves the interleaved and the wide topics")
+        self.by_columns = by_columns
         if not 0 < n_train < n_rows:
             raise ValueError("LogisticTopics needs train rows [0, n_train) and test rows [n_train, n_rows)")
         self.backend, self.n_train, self.n_rows, self.node_count = backend, n_train, n_rows, node_count
@@ -1528,7 +1532,7 @@ class LogisticTopics:
                 break
             idx, offsets, n_steps = epoch_lists(self.rnd, split, max_samples, batch_size)
             if n_steps:
-                self.backend.lg_topics_sync_steps(idx, offsets, n_steps, len(split), learning_rate)
+                self.backend.lg_topics_sync_steps(idx, offsets, n_steps, len(split), learning_rate, **({"by_columns": True} if self.by_columns else {}))
             if n_steps < n_expected:
                 # the reference's next batch hands some slave an empty slice: Vec.sum throws there (math/Vec.scala:129)
                 raise ValueError("Cannot sum an empty list of vectors (batch %d of the epoch: a worker's slice is empty)" % n_steps)
@@ -1552,11 +1556,14 @@ class LogisticSoftmax:
     rule, applied to the test losses, newest first, and ONE GradState whose `grad` holds the weights [C, D + 1].
 
     data layout: rows [0, n_train) are the train set, [n_train, n_rows) the test set.  Limits: one engine, no plans, no
-    ranks, no column slices, one learning rate and one lambda for all classes."""
+    ranks, no column slices, one learning rate and one lambda for all classes.  by_columns: the steps go through the whole
+    matrix's column lists (Engine.lg_softmax_sync_steps(..., by_columns=True)): the same bits."""
 
-    def __init__(self, backend, n_train: int, n_rows: int, node_count: int, rnd: Optional[JavaRandom] = None, log=None):
+    def __init__(self, backend, n_train: int, n_rows: int, node_count: int, rnd: Optional[JavaRandom] = None, log=None,
+                 by_columns: bool = False):
         if not 0 < n_train < n_rows:
             raise ValueError("LogisticSoftmax needs train rows [0, n_train) and test rows [n_train, n_rows)")
+        self.by_columns = by_columns
         self.backend, self.n_train, self.n_rows, self.node_count = backend, n_train, n_rows, node_count
         self.rnd = rnd or JavaRandom(0)
         self.log = log or (lambda *a: None)
@@ -1587,7 +1594,7 @@ class LogisticSoftmax:
                 break
             idx, offsets, n_steps = epoch_lists(self.rnd, split, max_samples, batch_size)
             if n_steps:
-                self.backend.lg_softmax_sync_steps(idx, offsets, n_steps, len(split), learning_rate)
+                self.backend.lg_softmax_sync_steps(idx, offsets, n_steps, len(split), learning_rate, **({"by_columns": True} if self.by_columns else {}))
             if n_steps < n_expected:
                 # the reference's next batch hands some slave an empty slice: Vec.sum throws there (math/Vec.scala:129)
                 raise ValueError("Cannot sum an empty list of vectors (batch %d of the epoch: a worker's slice is empty)" % n_steps)

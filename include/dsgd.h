@@ -1155,6 +1155,28 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *                               DSGD_EUNSUPPORTED, a failed allocation with DSGD_ENOMEM, both before any weight moves --
  *                               dsgd_lg_topics_sync_steps over lists serves any rows.  Behind a served call
  *                               dsgd_grad_kernel_name says "dsgd_lg_topics_cgrad_kernel"
+ *   INDEX LISTS BY COLUMN LISTS dsgd_lg_topics_sync_steps_cols: dsgd_lg_topics_sync_steps' arguments, checks and refusals in its
+ *                               order, for topics in the INTERLEAVED or the WIDE form (csrc/dsgd_lg_lists_cols.hpp; the planar form
+ *                               is refused with DSGD_EUNSUPPORTED behind them, nothing changed).  Opt-in; nothing routes here by
+ *                               itself and no environment knob selects it.  The column lists are those of the WHOLE matrix -- the
+ *                               single model's layout over the one range [0, n_rows), made at the first call after a load and
+ *                               kept by its cache -- and a step says which rows take part through one 32-bit owner word per row
+ *                               (worker and position in the step's lists; csrc/dsgd_lg_lists_cols_host.hpp).  A step is FIVE
+ *                               launches whatever T and K: dsgd_lgl_mark_kernel, dsgd_lgl_topics_coef_kernel<GW> into
+ *                               cq[position][TP], dsgd_lgl_cgrad_kernel<GW> (grid shares x workers: every worker walks the
+ *                               matrix's entries once, an entry of a row it does not own costs one 4-byte gather and no
+ *                               coefficient load; the sums stay in registers between column boundaries, no atomic per non-zero),
+ *                               the form's own finish, dsgd_lgl_clear_kernel.  THE CONTRACT: weights and |w_t|^2 words are the
+ *                               BITS of dsgd_lg_topics_sync_steps on the same arguments.  A step that names a row TWICE (in one
+ *                               list or in two), 2^24 rows or more, more than 255 workers, or a matrix whose column lists or
+ *                               tables cannot be had runs through the LIST launches inside the same call: nothing that
+ *                               dsgd_lg_topics_sync_steps accepts is refused.  Behind the call dsgd_grad_kernel_name says what the
+ *                               LAST step took: "dsgd_lgl_cgrad_kernel", or the list form's gradient kernel; a call whose steps took
+ *                               different routes shows the last one only (dsgd_batch_stats carries no route).  On classes
+ *                               (dsgd_lg_softmax_set / _set_il) this call takes the ONE-VS-REST step on their one-hot planes, as
+ *                               dsgd_lg_topics_sync_steps does, whatever route a step takes.  The walk costs the
+ *                               whole matrix per worker and step: it pays where the lists name a large share of the rows
+ *                               (DESIGN.md 3.13 "Index lists by column lists")
  *
  * SOFTMAX (csrc/dsgd_lg_softmax.hpp; DESIGN.md 3.13 "Softmax over the wide layout").  Multinomial logistic regression over
  * 2 <= C <= 128 mutually exclusive classes on the WIDE layout above: weights W[C][D + 1], per row z_c = x . w_c (the single
@@ -1177,6 +1199,11 @@ int dsgd_dense_plan_destroy(dsgd_dense* d, dsgd_dense_plan* plan);
  *   dsgd_lg_softmax_sync_steps_ranges           dsgd_lg_topics_sync_steps_ranges' arguments (one step: n_steps = 1): THREE launches
  *                               per step (dsgd_lg_softmax_coef_kernel<GW>, then dsgd_lg_topics_cgrad_kernel<GW> and the wide finish
  *                               as they are).  The weights are the BITS of dsgd_lg_softmax_sync_steps over the same rows as lists
+ *   dsgd_lg_softmax_sync_steps_cols             dsgd_lg_softmax_sync_steps' arguments, checks and refusals, in either form of the
+ *                               classes: the list steps by the whole matrix's column lists (INDEX LISTS BY COLUMN LISTS above) with
+ *                               dsgd_lgl_smax_coef_kernel<GW> (wide) or dsgd_lgl_smax_few_coef_kernel<NQ> (few classes) for the
+ *                               coefficients.  The BITS of dsgd_lg_softmax_sync_steps; the same fallback to the list launches,
+ *                               step by step, reported by dsgd_grad_kernel_name
  *   dsgd_lg_softmax_loss_acc    the reported loss and the share of rows whose predicted class is theirs over [row_begin, row_end)
  *                               (either pointer may be NULL, not both); fixed-order sums, integer tallies: the same call gives
  *                               the same bits
@@ -1281,6 +1308,8 @@ int dsgd_lg_topics_sync_step_ranges(dsgd_ctx* ctx, const int64_t* row_begin, con
                                     dsgd_batch_stats* stats);
 int dsgd_lg_topics_sync_steps_ranges(dsgd_ctx* ctx, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, int64_t n_steps,
                                      float lr, dsgd_batch_stats* stats);
+int dsgd_lg_topics_sync_steps_cols(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const int64_t* offsets /* n_steps * n_workers + 1 */,
+                                   int64_t n_steps, int32_t n_workers, float lr, dsgd_batch_stats* stats);
 int dsgd_lg_topics_loss_acc(dsgd_ctx* ctx, int64_t row_begin, int64_t row_end, double* loss /* T */, double* acc /* T */);
 int dsgd_lg_topics_predict(dsgd_ctx* ctx, const int32_t* idx, int64_t n, float* p_out /* T x n, topic-major */);
 /* softmax over exclusive classes ("SOFTMAX" above) */
@@ -1293,6 +1322,8 @@ int dsgd_lg_softmax_sync_steps(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx,
                                int64_t n_steps, int32_t n_workers, float lr, dsgd_batch_stats* stats);
 int dsgd_lg_softmax_sync_steps_ranges(dsgd_ctx* ctx, const int64_t* row_begin, const int64_t* row_end, int32_t n_workers, int64_t n_steps,
                                       float lr, dsgd_batch_stats* stats);
+int dsgd_lg_softmax_sync_steps_cols(dsgd_ctx* ctx, const int32_t* idx, int64_t n_idx, const int64_t* offsets /* n_steps * n_workers + 1 */,
+                                    int64_t n_steps, int32_t n_workers, float lr, dsgd_batch_stats* stats);
 int dsgd_lg_softmax_loss_acc(dsgd_ctx* ctx, int64_t row_begin, int64_t row_end, double* loss, double* acc);
 int dsgd_lg_softmax_predict(dsgd_ctx* ctx, const int32_t* idx, int64_t n, uint8_t* cls_out /* n */, float* p_out /* C x n, class-major, or NULL */);
 

@@ -32,7 +32,16 @@ the closest thing there is without it, the wide one-vs-rest step of T = C topics
 (--T picks others) at 3 x 100 and 4 x 4,096 rows per list step and at all rows as ONE range per ranges step.  The same
 protocol (the sides alternated `repeats` times, the median and the spread); the two sides compute different models, so no
 bits are compared; the ranges windows run steps / 20 steps per call; the default --out becomes
-profiles/logistic_softmax_probe.json."""
+profiles/logistic_softmax_probe.json.
+
+--by-columns: the list steps by the whole matrix's column lists (Engine.lg_topics_sync_steps / lg_softmax_sync_steps with
+by_columns=True) on one context against the same call without it on a second, the same lists -- wide topics T = 32 and 103, wide
+softmax C = 103, softmax over few classes C = 5, 16 and 32, at 3 x 100 and 4 x 4,096 rows per step, at --rows and at --rows-large
+(where the lists are a small share of the matrix and the whole-matrix walk is expected to lose).  No step names a row twice (a
+step that does is served by the list launches).  The same protocol; 1000 steps per call at 3 x 100 and 40 at 4 x 4,096 unless
+--steps is given, 3 calls per window, the sides alternated `repeats` times (default here 3); the matrix's layout is built by the
+warm-up call and is in no window; the weights are compared bit for bit after every warm-up pair; the default --out becomes
+profiles/logistic_lists_cols_probe.json."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -49,9 +58,62 @@ ap.add_argument("--wide", action="store_true", help="time the wide form: against
 ap.add_argument("--ranges", action="store_true", help="time whole-split steps over row ranges against the same rows as arange lists in the same form")
 ap.add_argument("--softmax", action="store_true", help="time the softmax list and ranges steps against the wide one-vs-rest step of the same C; "
                                                        "with --interleaved: softmax over 2 to 32 classes with the lanes across the non-zeros against the wide softmax")
+ap.add_argument("--by-columns", action="store_true", help="time the list steps by the whole matrix's column lists against the list form on a second context")
+ap.add_argument("--rows-large", type=int, default=185192, help="--by-columns: the second, larger matrix")
 ap.add_argument("--T", help="--softmax: comma-separated class counts (default 8,53,103,128); --wide / --ranges: comma-separated topic counts (default 1,8,32,64,103,128 / 8,32,103,128)")
 ap.add_argument("--out")
 a = ap.parse_args()
+if a.by_columns:
+    if a.wide or a.interleaved or a.ranges or a.softmax:
+        sys.exit("logistic_topics_probe: --by-columns is a run of its own")
+    if dsgd_amd.device_count() < 1:
+        sys.exit("logistic_topics_probe: no gfx950 device (nothing is measured without one)")
+    a.calls = a.calls or 3
+    a.repeats = 3 if a.repeats == 5 else a.repeats
+    a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "logistic_lists_cols_probe.json")
+    LR = 2.0 ** -10
+    result = {"steps_per_call": {"3x100": a.steps or 1000, "4x4096": a.steps or 40}, "calls_per_window": a.calls, "repeats": a.repeats,
+              "unit": "us per step, host wall time around synchronising calls", "shapes": []}
+    for n_rows in (a.rows, a.rows_large):
+        data = dsgd_amd.synth.generate(n_rows, seed=0)
+        rng = np.random.default_rng(1)
+        planes = np.ascontiguousarray(np.vstack([data.label[None].astype(np.int8), rng.choice(np.array([-1, 1], np.int8), size=(102, n_rows))]))
+        with dsgd_amd.Engine(data.dim, a.lam) as eng, dsgd_amd.Engine(data.dim, a.lam) as other:
+            for e in (eng, other):
+                e.load_csr(data.row_ptr, data.col, data.val, data.label)
+            for k, batch in ((3, 100), (4, 4096)):
+                steps = a.steps or (1000 if batch == 100 else 40)
+                flat = np.concatenate([rng.permutation(n_rows)[:k * batch] for _ in range(steps)]).astype(np.int32)   # no row twice in a step
+                offs = np.arange(0, steps * k * batch + 1, batch, dtype=np.int64)
+                for model, n in (("wide topics", 32), ("wide topics", 103), ("wide softmax", 103), ("few-classes softmax", 5), ("few-classes softmax", 16),
+                                 ("few-classes softmax", 32)):
+                    for e in (eng, other):                                # (from zero weights on both sides)
+                        if model == "wide topics":
+                            e.lg_topics_set(planes[:n], wide=True)
+                        else:
+                            e.lg_softmax_set(np.random.default_rng(n).integers(0, n, size=n_rows).astype(np.uint8), n, interleaved=model != "wide softmax")
+                    call = (lambda e, **kw: e.lg_topics_sync_steps(flat, offs, steps, k, LR, **kw)) if model == "wide topics" else \
+                           (lambda e, **kw: e.lg_softmax_sync_steps(flat, offs, steps, k, LR, **kw))
+                    call(eng, by_columns=True), call(other)               # warm-up of the timed shape (and the matrix's layout); then the bits
+                    same = bool(np.array_equal(eng.lg_topics_get_weights().view(np.uint32), other.lg_topics_get_weights().view(np.uint32)))
+                    tc, tl = [], []
+                    for _ in range(a.repeats):                            # alternated
+                        for side, fn in ((tc, lambda: call(eng, by_columns=True)), (tl, lambda: call(other))):
+                            t0 = time.perf_counter()
+                            for _ in range(a.calls):
+                                fn()
+                            side.append((time.perf_counter() - t0) * 1e6 / (steps * a.calls))
+                    result["shapes"].append({"rows": n_rows, "workers": k, "batch": batch, "share_of_rows": k * batch / n_rows, "model": model, "T_or_C": n,
+                                             "bits_equal": same, "kernel": eng.grad_kernel_name(), "shortest_window_s": min(tc + tl) * steps * a.calls * 1e-6,
+                                             "by_columns_us": {"median": float(np.median(tc)), "min": min(tc), "max": max(tc)},
+                                             "lists_us": {"median": float(np.median(tl)), "min": min(tl), "max": max(tl)}})
+                    print(json.dumps(result["shapes"][-1]), flush=True)
+    line = json.dumps(result)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+    sys.exit(0)
 a.steps = a.steps or (50 if a.ranges else 1000)
 a.calls = a.calls or (4 if a.ranges else 10)
 a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",

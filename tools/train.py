@@ -34,6 +34,8 @@ host.LogisticSoftmax): class = the first listed topic a document carries, one mo
 --lg-topics-wide (with --topics): up to 128 names, that layout with the lanes across the topics (dsgd_lg_topics_set_wide): the
 same bits.  --topics all: every topic code of the qrels file under data-path, sorted (RCV1-v2: 103) -- refused with the count
 when there are more than the chosen form serves.
+--lg-by-columns (with --topics in the interleaved or the wide form, or --model softmax): the steps go through the whole matrix's
+column lists and one owner word per row (dsgd_lg_topics_sync_steps_cols / dsgd_lg_softmax_sync_steps_cols): the same bits.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -58,11 +60,15 @@ ap.add_argument("--lg-topics-interleaved", action="store_true", help="--topics: 
 ap.add_argument("--lg-topics-wide", action="store_true", help="--topics: the wide form, up to 128 names (Engine.lg_topics_set(wide=True))")
 ap.add_argument("--softmax-interleaved", action="store_true",
                 help="--model softmax: at most 32 classes with the lanes across the non-zeros, the same bits (Engine.lg_softmax_set(interleaved=True))")
+ap.add_argument("--lg-by-columns", action="store_true",
+                help="--topics (interleaved or wide) or --model softmax: the list steps by the whole matrix's column lists, the same bits")
 a = ap.parse_args()
 topics =[t for t in (a.topics or "").split(",") if t]
 if a.lg_topics_wide and a.lg_topics_interleaved:
     ap.error("--lg-topics-interleaved and --lg-topics-wide are two forms: give one")
 softmax = a.model == "softmax"
+if a.lg_by_columns and not (softmax or a.lg_topics_interleaved or a.lg_topics_wide):
+    ap.error("--lg-by-columns goes with --lg-topics-interleaved, --lg-topics-wide or --model softmax")
 if a.softmax_interleaved and not softmax:
     ap.error("--softmax-interleaved goes with --model softmax")
 if softmax and (not topics or topics == ["all"] or a.lg_plans or a.lg_slices or a.lg_async or a.lg_topics_interleaved or a.lg_topics_wide):
@@ -136,7 +142,7 @@ def synthetic_planes(data, n_topics, seed=1):
 def fit_topics(eng, cfg, planes, names, n_train, n_rows):
     eng.lg_topics_set(planes, interleaved=a.lg_topics_interleaved, wide=a.lg_topics_wide)
     master = host.LogisticTopics(eng, n_train, n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log, interleaved=a.lg_topics_interleaved,
-                                 wide=a.lg_topics_wide)
+                                 wide=a.lg_topics_wide, by_columns=a.lg_by_columns)
     l0, a0 = eng.lg_topics_loss_acc(0, n_train)
     for t, name in enumerate(names):
         log("{}: {} of {} rows tagged, initial loss {}, initial accuracy {}", name, int((planes[t] > 0).sum()), n_rows, l0[t], a0[t])
@@ -155,7 +161,7 @@ def fit_softmax(eng, cfg, planes, names, n_train, n_rows):
     tagged = planes > 0
     cls = np.where(tagged.any(axis=0), tagged.argmax(axis=0), len(names)).astype(np.uint8)
     eng.lg_softmax_set(cls, len(names) + 1, interleaved=a.softmax_interleaved)
-    master = host.LogisticSoftmax(eng, n_train, n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log)
+    master = host.LogisticSoftmax(eng, n_train, n_rows, cfg.node_count, rnd=host.JavaRandom(0), log=log, by_columns=a.lg_by_columns)
     for c, name in enumerate(list(names) + ["(none)"]):
         log("{}: {} of {} rows", name, int((cls == c).sum()), n_rows)
     l0, a0 = eng.lg_softmax_loss_acc(0, n_train)
